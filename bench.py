@@ -20,6 +20,11 @@ wall time.  Rank 0 prints one JSON line with the contract keys plus
     python bench.py --mode train [--gpus N] ...   BASELINE configs[3]: the data-parallel optimisation step of src/train.py:164-191
 on the HIP modules (per-rank B=32, 32 views, 64x64 patches, fp32), FusedAdam, gradient exchange over RCCL with ShiftNet's 137 MB
 slice all-reduced from a backward hook under HRNet's backward; value = samples/s over all ranks.
+
+    --dump-outputs DIR   after the timed steps, rank 0 writes what its last timed step returned as DIR/<name>.npy (float32):
+forward: sr (B, 1, 3S, 3S); train: loss, hrnet_params (every HRNet weight after the step, flat) and shiftnet_params (ShiftNet's
+weights after the step, flat).  At most 64 MB in all: a larger array is replaced by a fixed sample (see dump_outputs).  Inputs and
+weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -203,6 +208,8 @@ def make_train_step(device, batch, views, patch, overlap=True, precision="fp32")
         return loss
     step.early = False
     step.flat_parameters = opt._flat[0]["p"]                                                        # every weight of both models, one buffer
+    step.n_fusion = sum(p.numel() for p in fusion.parameters())                                    # HRNet's: [0, n_fusion), ShiftNet's next
+    step.n_params = sum(p.numel() for p in params)                                                  # (the buffer is padded past it)
     step.initial = opt._flat[0]["p"].clone()
     return step
 
@@ -293,6 +300,33 @@ def timed_cpu(step, steps, warmup, hdist):
     return hdist.max_over_ranks(time.perf_counter() - t0, None)
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy, float32 (float64 stays float64), DUMP_BYTES in all.  Smaller arrays go first and
+    whole; an array larger than an equal share of what is left becomes the sample flat[idx], idx = the sorted draw
+    numpy.random.default_rng(0).integers(0, numel, k): the same indices on every run with the same arguments.  -> {name: record}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left, record = DUMP_BYTES, {}
+    for i, (name, t) in enumerate(items):
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        files = len(items) - i
+        k = max(0, left - 256 * files) // (files * a.itemsize)          # 256 B per file for the .npy header
+        rec = {"shape": list(a.shape), "dtype": str(a.dtype), "sample": None}
+        if a.size > k:
+            rec["sample"] = f"flat[sorted numpy.random.default_rng(0).integers(0, {a.size}, {k})]"
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, k))]
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        left -= os.path.getsize(path)
+        record[name] = rec
+    return record
+
+
 def extra(extras, key, fn):
     """One extra measurement: whatever goes wrong in it (an OOM on a box with less free HBM, ...) is recorded under its key and never
     costs the contract line."""
@@ -320,9 +354,12 @@ def main():
     ap.add_argument("--profile-steps", type=int, default=3, help="extra instrumented steps for the rooflines (not in `value`)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the fp32 / bf16x3 / config-2 / config-5 / train-step extra measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what rank 0's last timed step returned as DIR/<name>.npy (<= 64 MB)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)                     # the driver's form of the command: this process only launches and collects
@@ -347,9 +384,18 @@ def main():
     if args.mode == "train":
         tprec = "fp32" if args.precision == "bf16" else args.precision       # (bf16 storage has no training path: fp32 unless bf16x3 is asked for)
         step = make_train_step(device, args.batch, args.views, args.patch, precision=tprec)
-        steps = max(1, min(args.steps, 10))
+        steps = args.steps
         warm = max(1, min(args.warmup, 3))
-        elapsed = timed(step, steps, warm, device, hdist)
+        loss = [None]
+
+        def train_step():
+            loss[0] = step()
+        elapsed = timed(train_step, steps, warm, device, hdist)
+        dumped = None
+        if args.dump_outputs and rank == 0:        # before the no-exchange leg below moves the weights on
+            flat = step.flat_parameters
+            dumped = dump_outputs(args.dump_outputs, {"loss": loss[0], "hrnet_params": flat[:step.n_fusion],
+                                                      "shiftnet_params": flat[step.n_fusion:step.n_params]})
         no_x = timed(lambda: step(exchange=False), steps, 1, device, hdist) if ws > 1 else elapsed
         if rank == 0:
             print(json.dumps({
@@ -363,7 +409,8 @@ def main():
                                        f"B={args.batch}/GPU, n_views={args.views}, {args.patch}x{args.patch} patches (BASELINE configs[3])",
                            "global_batch": args.batch * ws,
                            "parallelism": f"dp{ws}: {backend or 'no'} all-reduce of 139 MB of fp32 gradients per step, ShiftNet's slice overlapped with HRNet's backward",
-                           "weights": "random init (seed 1234), fc2 ~ N(0, 1e-3)"}}), flush=True)
+                           "weights": "random init (seed 1234), fc2 ~ N(0, 1e-3)"},
+                **({"dumped_outputs": {"dir": args.dump_outputs, "arrays": dumped}} if dumped else {})}), flush=True)
         hdist.finalize()
         return
 
@@ -383,6 +430,7 @@ def main():
     if rank != 0:
         hdist.finalize()
         return
+    dumped = dump_outputs(args.dump_outputs, {"sr": sr_holder[0]}) if args.dump_outputs else None
 
     storage = {"bf16": "bf16 storage + fp32 accumulate", "fp32": "fp32 storage, exact-fp32 MFMA",
                "bf16x3": "fp32 values as bf16 hi+lo pairs, 3 bf16 MFMAs per product, fp32 accumulate"}[args.precision]
@@ -400,6 +448,8 @@ def main():
         "whole_forward_tflops": round(tf, 1),
         "roofline": None, "roofline_hbm": None, "parity": {}, "cpu_baseline": None, "kernels": {},
     }
+    if dumped:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     try:
         with torch.no_grad():
             measure_rank0(args, ws, device, net, lrs, alphas, step, sr_holder, binding, line)

@@ -122,12 +122,22 @@ TRAIN_WORKER = textwrap.dedent("""
     opt = torch.optim.SGD(params, lr=0.05)
     seen = []
     fusion[0].weight.register_hook(lambda g: seen.append(buckets.early_launched_in_backward))   # fires in the LAST backward node
+
+    def own_gradients(x):
+        # this rank's gradients, computed on detached copies of the weights: once backward() returns, the early slice of flat_g
+        # may already be (partly) summed over the ranks - the hook put it on the wire - so flat_g cannot serve as the local value
+        fp = {k: v.detach().clone().requires_grad_(True) for k, v in fusion.named_parameters()}
+        rp = {k: v.detach().clone().requires_grad_(True) for k, v in regis.named_parameters()}
+        out = torch.func.functional_call(regis, rp, (torch.func.functional_call(fusion, fp, (x,)),))
+        grads = torch.autograd.grad((out ** 2).mean(), list(fp.values()) + list(rp.values()))
+        return torch.cat([g.reshape(-1) for g in grads])
+
     for step in range(3):
         flat_g.zero_(); buckets.begin()
         x = torch.randn(8, 64, generator=torch.Generator().manual_seed(100 * rank + step))     # every rank its own shard
+        local = own_gradients(x)
         loss = (regis(fusion(x)) ** 2).mean()
         loss.backward()
-        local = flat_g.clone()
         nbytes = buckets.finish()
         assert nbytes == n * 4
         both = [torch.zeros_like(local) for _ in range(ws)]
@@ -201,9 +211,11 @@ def test_bench_spawns_its_own_ranks():
     """`python bench.py --gpus 2` launched directly (no torchrun environment) starts two ranks itself, before any GPU call, and rank
     0's line says n_gpus 2 with both ranks seen by an all_gather.  Here: no ROCm device, HRN_DIST_BACKEND=gloo = the launcher
     rehearsal on CPU stand-in steps (no kernel runs, value is null).  Without that variable, or with fewer devices than ranks, the
-    command refuses instead of silently measuring one GPU."""
+    command refuses instead of silently measuring one GPU.  HIP_VISIBLE_DEVICES=-1 hides every device from the commands, so this
+    holds on a machine with GPUs too."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"
     for mode in ("forward", "train"):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--mode", mode],
                            env=dict(env, HRN_DIST_BACKEND="gloo"), capture_output=True, text=True, timeout=300)
@@ -211,10 +223,8 @@ def test_bench_spawns_its_own_ranks():
         line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
         assert line["n_gpus"] == 2 and line["ranks_seen"] == [0, 1] and line["backend"] == "gloo"
         assert line["value"] is None and line["rehearsal"] is True and line["mode"] == mode
-    import torch
-    if not torch.cuda.is_available():
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode != 0 and "refusing" in (r.stderr + r.stdout)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "refusing" in (r.stderr + r.stdout)
 
 
 VAL_WORKER = textwrap.dedent("""

@@ -1,5 +1,5 @@
 """CPU: host-side logic of the package: module surface / state_dict contract, error behaviour without a GPU,
-the sorting network used by the median kernel, the XCD tile remap and the weight-pack index math."""
+the sorting network used by the median kernel, the XCD tile remap, the weight-pack index math and bench.py's output dump."""
 import itertools
 import os
 import re
@@ -106,3 +106,22 @@ def test_stamp_instrumenters_still_apply(tmp_path):
         assert r.returncode == 0, r.stderr[-800:]
         text = (d / fn).read_text()
         assert marker in text and text.count("STAMP(") >= 7
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path):
+    """bench.py --dump-outputs: float32 (float64 stays float64) .npy files, 64 MB in all, headers included; an array over the
+    budget becomes a sample drawn from a fixed seed, identical from run to run."""
+    import bench
+    arrays = {"loss": torch.tensor(0.5, dtype=torch.float64), "sr": torch.rand(2, 1, 6, 6).half(),
+              "params": torch.arange(20 << 20, dtype=torch.float32)}                                   # 80 MB
+    recs = [bench.dump_outputs(str(tmp_path / d), arrays) for d in ("a", "b")]
+    assert recs[0] == recs[1]
+    assert recs[0]["loss"]["sample"] is None and recs[0]["sr"]["sample"] is None and recs[0]["params"]["sample"]
+    for d in ("a", "b"):
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= bench.DUMP_BYTES
+    loss, sr = np.load(tmp_path / "a" / "loss.npy"), np.load(tmp_path / "a" / "sr.npy")
+    assert loss.dtype == np.float64 and float(loss) == 0.5
+    assert sr.dtype == np.float32 and np.array_equal(sr, arrays["sr"].float().numpy())
+    p, q = np.load(tmp_path / "a" / "params.npy"), np.load(tmp_path / "b" / "params.npy")
+    assert p.dtype == np.float32 and np.array_equal(p, q) and p.size > (12 << 20)
+    assert np.all(np.diff(p) >= 0) and p[0] >= 0 and p[-1] <= (20 << 20)                # sorted indices (float32-rounded)
