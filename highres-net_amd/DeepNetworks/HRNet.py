@@ -69,16 +69,20 @@ class Decoder(_Holder):
 
 
 def _check_config(config):
+    """-> the upscale factor.  The kernels take the reference's network (config/config.json:8-34) with any decoder.deconv
+    kernel_size == stride in binding.SCALES (non-overlapping: every LR pixel owns its S x S block of SR pixels)."""
     e, r, d = config["encoder"], config["recursive"], config["decoder"]
     ok = (e["in_channels"] == 2 and e["kernel_size"] == 3 and e["channel_size"] == 64 and 0 <= e["num_layers"] <= binding.MAX_RES_LAYERS
           and r["in_channels"] == 64 and r["kernel_size"] == 3
-          and d["deconv"]["in_channels"] == 64 and d["deconv"]["out_channels"] == 64 and d["deconv"]["kernel_size"] == 3
-          and d["deconv"]["stride"] == 3 and d["final"]["in_channels"] == 64 and d["final"]["out_channels"] == 1
-          and d["final"]["kernel_size"] == 1)
+          and d["deconv"]["in_channels"] == 64 and d["deconv"]["out_channels"] == 64
+          and d["deconv"]["kernel_size"] == d["deconv"]["stride"] and d["deconv"]["stride"] in binding.SCALES
+          and d["final"]["in_channels"] == 64 and d["final"]["out_channels"] == 1 and d["final"]["kernel_size"] == 1)
     if not ok:
         raise NotImplementedError(
-            "the gfx950 kernels are specialised for the reference's shipped network (config/config.json:8-34): "
-            "2->64 stem, 64-channel 3x3 convs, stride-3 k3 deconv, 1x1 final; got " + repr(config))
+            "the gfx950 kernels are specialised for the reference's network (config/config.json:8-34): 2->64 stem, 64-channel "
+            f"3x3 convs, a ConvTranspose2d with kernel_size == stride in {binding.SCALES} (the upscale factor), 1x1 final; got "
+            + repr(config))
+    return d["deconv"]["stride"]
 
 
 class _HRNetLazyTrainFunction(torch.autograd.Function):
@@ -94,7 +98,7 @@ class _HRNetLazyTrainFunction(torch.autograd.Function):
         ctx.module, ctx.names = module, names
         ctx.versions = tuple(p._version for p in params)
         ctx.save_for_backward(lrs, alphas, *params)
-        return binding.hrnet_forward(packed, dt, module._num_layers, module.fuse.alpha_residual, lrs, alphas)
+        return binding.hrnet_forward(packed, dt, module._num_layers, module.fuse.alpha_residual, lrs, alphas, scale=module._scale)
 
     _warned = False
 
@@ -111,19 +115,20 @@ class _HRNetLazyTrainFunction(torch.autograd.Function):
         if tuple(p._version for p in params) != ctx.versions:
             raise RuntimeError("HRNet bf16 train-mode backward: a parameter was modified between forward and backward")
         packed = m._packed_f32()
-        _, tws = binding.hrnet_forward_train(packed, lrs, alphas, m._num_layers, m.fuse.alpha_residual)
+        _, tws = binding.hrnet_forward_train(packed, lrs, alphas, m._num_layers, m.fuse.alpha_residual, scale=m._scale)
         named = dict(zip(ctx.names, params))
         grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for k, p in named.items()}
-        binding.hrnet_backward(packed, named, grads, m._num_layers, m.fuse.alpha_residual, lrs, alphas, d_sr.contiguous(), tws)
+        binding.hrnet_backward(packed, named, grads, m._num_layers, m.fuse.alpha_residual, lrs, alphas, d_sr.contiguous(), tws,
+                               scale=m._scale)
         return (None, None, None, None) + tuple(grads[k].to(named[k].dtype) for k in ctx.names)
 
 
 class HRNet(nn.Module):
-    """HRNet(config["network"]); forward(lrs (B,L,H,W), alphas (B,L)) -> (B,1,3H,3W)."""
+    """HRNet(config["network"]); forward(lrs (B,L,H,W), alphas (B,L)) -> (B,1,SH,SW), S = decoder.deconv.stride (2, 3 or 4)."""
 
     def __init__(self, config):
         super().__init__()
-        _check_config(config)
+        self._scale = _check_config(config)
         self.encode = Encoder(config["encoder"])
         self.fuse = RecuversiveNet(config["recursive"])
         self.decode = Decoder(config["decoder"])
@@ -144,7 +149,7 @@ class HRNet(nn.Module):
         named = dict(self.named_parameters())
         key = (dt, binding.param_epoch) + tuple((p.data_ptr(), p._version) for p in named.values())
         if self._packed is None or self._packed_key != key:
-            self._packed = binding.hrnet_pack(named, self._num_layers, dt)
+            self._packed = binding.hrnet_pack(named, self._num_layers, dt, self._scale)
             self._packed_key = key
         return self._packed, dt
 
@@ -173,16 +178,18 @@ class HRNet(nn.Module):
             dt = self._dtype()
             packed = self.packed_parameters()[0] if dt == binding.BF16X3 else self._packed_f32()
             sr, _tws = torch.ops.hrnet_hip.hrnet_forward_train(packed, lrs.detach().float().contiguous(), alphas.detach().float().contiguous(),
-                                                               params, self._num_layers, bool(self.fuse.alpha_residual), dt)
+                                                               params, self._num_layers, bool(self.fuse.alpha_residual), dt,
+                                                               self._scale)
             return sr
         packed, dt = self.packed_parameters()
-        return torch.ops.hrnet_hip.hrnet_forward(packed, dt, self._num_layers, bool(self.fuse.alpha_residual), lrs.detach(), alphas.detach())
+        return torch.ops.hrnet_hip.hrnet_forward(packed, dt, self._num_layers, bool(self.fuse.alpha_residual), lrs.detach(), alphas.detach(),
+                                                 self._scale)
 
     def _packed_f32(self):
         named = dict(self.named_parameters())
         key = (binding.param_epoch,) + tuple((p.data_ptr(), p._version) for p in named.values())
         if getattr(self, "_packed32", None) is None or self._packed32_key != key:
-            self._packed32 = binding.hrnet_pack(named, self._num_layers, binding.F32)
+            self._packed32 = binding.hrnet_pack(named, self._num_layers, binding.F32, self._scale)
             self._packed32_key = key
         return self._packed32
 
@@ -197,4 +204,4 @@ class HRNet(nn.Module):
 
     def decode_state(self, fused):
         packed, dt = self.packed_parameters()
-        return binding.hrnet_decoder(packed, dt, self._num_layers, fused)
+        return binding.hrnet_decoder(packed, dt, self._num_layers, fused, self._scale)

@@ -81,6 +81,17 @@ SIGNATURES = {
                                               _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_hrnet_backward_dt": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(HrnetParams), _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,
                                          _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(HrnetParams), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_hrnet_packed_bytes_s": (_c.c_size_t, [_c.c_int] * 3),
+    "hrn_hrnet_pack_s": (_c.c_int, [_c.POINTER(HrnetParams), _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_hrnet_forward_s": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                       _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_decoder_forward_s": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+                                         _c.c_void_p, _c.c_void_p]),
+    "hrn_hrnet_forward_train_s": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int,
+                                             _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_hrnet_backward_s": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(HrnetParams), _c.c_int, _c.c_void_p, _c.c_void_p,
+                                        _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(HrnetParams), _c.c_void_p,
+                                        _c.c_size_t, _c.c_void_p]),
     "hrn_shiftnet_packed_bytes": (_c.c_size_t, []),
     "hrn_shiftnet_pack": (_c.c_int, [_c.POINTER(ShiftnetParams), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_shiftnet_workspace_bytes": (_c.c_size_t, [_c.c_int]),
@@ -198,17 +209,24 @@ def hrnet_param_struct(named, num_layers):
     return P, keep
 
 
-def hrnet_pack(named, num_layers, dtype):
-    """named: dict of reference state-dict keys -> device f32 tensors.  Returns the packed uint8 tensor."""
+SCALES = (2, 3, 4)       # upscale factors the decoder kernels are built for (deconv kernel_size == stride)
+
+
+def hrnet_pack(named, num_layers, dtype, scale=3):
+    """named: dict of reference state-dict keys -> device f32 tensors (decode.deconv.0.weight (64,64,scale,scale)).  Returns the
+    packed uint8 tensor, valid for this dtype and scale only."""
     lib = load_library()
-    P, keep = hrnet_param_struct(named, num_layers)
-    nbytes = lib.hrn_hrnet_packed_bytes(dtype, num_layers)
+    nbytes = lib.hrn_hrnet_packed_bytes_s(dtype, num_layers, scale)
     if nbytes == 0:
-        raise HrnetHipError(f"unsupported dtype/num_layers ({dtype}, {num_layers})")
+        raise HrnetHipError(f"unsupported dtype/num_layers/scale ({dtype}, {num_layers}, {scale})")
+    w = named["decode.deconv.0.weight"]
+    if tuple(w.shape) != (64, 64, scale, scale):
+        raise ValueError(f"decode.deconv.0.weight is {tuple(w.shape)}; scale {scale} needs (64, 64, {scale}, {scale})")
+    P, keep = hrnet_param_struct(named, num_layers)
     dev = keep[0].device
     packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _check(lib.hrn_hrnet_pack(ctypes.byref(P), dtype, _ptr(packed), nbytes, _stream()), "hrn_hrnet_pack")
+        _check(lib.hrn_hrnet_pack_s(ctypes.byref(P), dtype, scale, _ptr(packed), nbytes, _stream()), "hrn_hrnet_pack")
     return packed
 
 
@@ -233,7 +251,8 @@ def hrnet_workspace(dtype, B, V, H, W, device):
     return _workspace(n, device, "hrnet")
 
 
-def hrnet_forward(packed, dtype, num_layers, alpha_residual, lrs, alphas, out=None):
+def hrnet_forward(packed, dtype, num_layers, alpha_residual, lrs, alphas, out=None, scale=3):
+    """-> sr (B, 1, scale H, scale W); `packed` is the blob of hrnet_pack at this dtype and scale."""
     lib = load_library()
     lrs = _dev_f32(lrs, "lrs")
     alphas = _dev_f32(alphas, "alphas").to(lrs.device)
@@ -242,9 +261,11 @@ def hrnet_forward(packed, dtype, num_layers, alpha_residual, lrs, alphas, out=No
     B, V, H, W = lrs.shape
     with torch.cuda.device(lrs.device):
         ws = hrnet_workspace(dtype, B, V, H, W, lrs.device)
-        sr = out if out is not None else torch.empty((B, 1, 3 * H, 3 * W), dtype=torch.float32, device=lrs.device)
-        _check(lib.hrn_hrnet_forward(_ptr(packed), dtype, num_layers, int(bool(alpha_residual)), _ptr(lrs), _ptr(alphas),
-                                     B, V, H, W, _ptr(sr), _ptr(ws), ws.numel(), _stream()), "hrn_hrnet_forward")
+        if out is not None and (tuple(out.shape) != (B, 1, scale * H, scale * W) or out.dtype != torch.float32 or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {(B, 1, scale * H, scale * W)}")
+        sr = out if out is not None else torch.empty((B, 1, scale * H, scale * W), dtype=torch.float32, device=lrs.device)
+        _check(lib.hrn_hrnet_forward_s(_ptr(packed), dtype, num_layers, scale, int(bool(alpha_residual)), _ptr(lrs), _ptr(alphas),
+                                       B, V, H, W, _ptr(sr), _ptr(ws), ws.numel(), _stream()), "hrn_hrnet_forward")
     return sr
 
 
@@ -276,18 +297,20 @@ def hrnet_fuse(packed, dtype, num_layers, alpha_residual, emb, alphas):
     return fused
 
 
-def hrnet_decoder(packed, dtype, num_layers, fused):
+def hrnet_decoder(packed, dtype, num_layers, fused, scale=3):
+    """fused (N,H,W,64) in the storage dtype ((2,N,H,W,64) planes for BF16X3) -> sr (N, 1, scale H, scale W)."""
     lib = load_library()
     if fused.dtype != _DT_TORCH[dtype] or not fused.is_contiguous() or not fused.is_cuda or fused.dim() != (5 if dtype == BF16X3 else 4):
         raise ValueError("fused must be a contiguous device tensor in the storage dtype")
     N, H, W, _ = fused.shape[-4:]
     with torch.cuda.device(fused.device):
-        sr = torch.empty((N, 1, 3 * H, 3 * W), dtype=torch.float32, device=fused.device)
-        _check(lib.hrn_decoder_forward(_ptr(packed), dtype, num_layers, _ptr(fused), N, H, W, _ptr(sr), _stream()), "hrn_decoder_forward")
+        sr = torch.empty((N, 1, scale * H, scale * W), dtype=torch.float32, device=fused.device)
+        _check(lib.hrn_decoder_forward_s(_ptr(packed), dtype, num_layers, scale, _ptr(fused), N, H, W, _ptr(sr), _stream()),
+               "hrn_decoder_forward")
     return sr
 
 
-def hrnet_forward_train(packed_f32, lrs, alphas, num_layers, alpha_residual, dtype=F32):
+def hrnet_forward_train(packed_f32, lrs, alphas, num_layers, alpha_residual, dtype=F32, scale=3):
     """Training forward: returns (sr, train_ws); train_ws holds every intermediate for hrnet_backward.  dtype F32 (exact-fp32 MFMA) or
     BF16X3 (split-bf16: `packed_f32` is then the BF16X3 blob and the workspace holds pairs of bf16 planes)."""
     lib = load_library()
@@ -298,30 +321,30 @@ def hrnet_forward_train(packed_f32, lrs, alphas, num_layers, alpha_residual, dty
     if nbytes == 0:
         raise HrnetHipError(f"bad training shape B={B} V={V} H={H} W={W} num_layers={num_layers}")
     tws = torch.empty(nbytes, dtype=torch.uint8, device=lrs.device)
-    sr = torch.empty((B, 1, 3 * H, 3 * W), dtype=torch.float32, device=lrs.device)
+    sr = torch.empty((B, 1, scale * H, scale * W), dtype=torch.float32, device=lrs.device)
     with torch.cuda.device(lrs.device):
-        _check(lib.hrn_hrnet_forward_train_dt(_ptr(packed_f32), int(dtype), num_layers, int(bool(alpha_residual)), _ptr(lrs), _ptr(alphas),
-                                              B, V, H, W, _ptr(sr), _ptr(tws), nbytes, _stream()), "hrn_hrnet_forward_train")
+        _check(lib.hrn_hrnet_forward_train_s(_ptr(packed_f32), int(dtype), num_layers, int(scale), int(bool(alpha_residual)), _ptr(lrs),
+                                             _ptr(alphas), B, V, H, W, _ptr(sr), _ptr(tws), nbytes, _stream()), "hrn_hrnet_forward_train")
     return sr, tws
 
 
-def hrnet_backward(packed_f32, named_params, named_grads, num_layers, alpha_residual, lrs, alphas, d_sr, tws, dtype=F32):
+def hrnet_backward(packed_f32, named_params, named_grads, num_layers, alpha_residual, lrs, alphas, d_sr, tws, dtype=F32, scale=3):
     """Accumulates dLoss/dparam into named_grads (same keys / shapes as named_params, f32, zero them for plain gradients)."""
     lib = load_library()
     lrs = _dev_f32(lrs, "lrs")
     alphas = _dev_f32(alphas, "alphas")
     d_sr = _dev_f32(d_sr, "d_sr")
     B, V, H, W = lrs.shape
-    if tuple(d_sr.shape) != (B, 1, 3 * H, 3 * W):
-        raise ValueError(f"d_sr shape {tuple(d_sr.shape)} != {(B, 1, 3 * H, 3 * W)}")
+    if tuple(d_sr.shape) != (B, 1, scale * H, scale * W):
+        raise ValueError(f"d_sr shape {tuple(d_sr.shape)} != {(B, 1, scale * H, scale * W)}")
     P, keep_p = hrnet_param_struct(named_params, num_layers)
     G, keep_g = hrnet_param_struct(named_grads, num_layers)
     for t, g in zip(keep_p, keep_g):
         if t.shape != g.shape or g.data_ptr() == t.data_ptr():
             raise ValueError("gradient buffers must match the parameters' shapes and not alias them")
     with torch.cuda.device(lrs.device):
-        _check(lib.hrn_hrnet_backward_dt(_ptr(packed_f32), int(dtype), ctypes.byref(P), int(bool(alpha_residual)), _ptr(lrs), _ptr(alphas),
-                                         B, V, H, W, _ptr(d_sr), ctypes.byref(G), _ptr(tws), tws.numel(), _stream()),
+        _check(lib.hrn_hrnet_backward_s(_ptr(packed_f32), int(dtype), int(scale), ctypes.byref(P), int(bool(alpha_residual)), _ptr(lrs),
+                                        _ptr(alphas), B, V, H, W, _ptr(d_sr), ctypes.byref(G), _ptr(tws), tws.numel(), _stream()),
                "hrn_hrnet_backward")
 
 
@@ -588,14 +611,14 @@ def shift_cpsnr(srs, hrs, hr_maps, border_w=3, clip=True):
 # thin shim over the ctypes call above - the C ABI stays the boundary.  The reference-named modules call THESE in eval mode.
 @torch.library.custom_op("hrnet_hip::hrnet_forward", mutates_args=(), device_types="cuda")
 def _op_hrnet_forward(packed: torch.Tensor, dtype: int, num_layers: int, alpha_residual: bool, lrs: torch.Tensor,
-                      alphas: torch.Tensor) -> torch.Tensor:
-    return hrnet_forward(packed, dtype, num_layers, alpha_residual, lrs, alphas)
+                      alphas: torch.Tensor, scale: int = 3) -> torch.Tensor:
+    return hrnet_forward(packed, dtype, num_layers, alpha_residual, lrs, alphas, scale=scale)
 
 
 @_op_hrnet_forward.register_fake
-def _(packed, dtype, num_layers, alpha_residual, lrs, alphas):
+def _(packed, dtype, num_layers, alpha_residual, lrs, alphas, scale=3):
     b, _, h, w = lrs.shape
-    return lrs.new_empty((b, 1, 3 * h, 3 * w), dtype=torch.float32)
+    return lrs.new_empty((b, 1, scale * h, scale * w), dtype=torch.float32)
 
 
 @torch.library.custom_op("hrnet_hip::lanczos_shift", mutates_args=(), device_types="cuda")
@@ -655,51 +678,54 @@ SHIFTNET_BUFFER_NAMES = [f"layer{i}.1.{k}" for i in range(1, 9) for k in ("runni
 
 @torch.library.custom_op("hrnet_hip::hrnet_forward_train", mutates_args=(), device_types="cuda")
 def _op_hrnet_forward_train(packed: torch.Tensor, lrs: torch.Tensor, alphas: torch.Tensor, params: Sequence[torch.Tensor],
-                            num_layers: int, alpha_residual: bool, dtype: int) -> Tuple[torch.Tensor, torch.Tensor]:
+                            num_layers: int, alpha_residual: bool, dtype: int, scale: int = 3) -> Tuple[torch.Tensor, torch.Tensor]:
     """`srs = fusion_model(lrs, alphas)` in training (train.py:174): the forward that keeps every intermediate in `tws`, in fp32 (dtype 0)
     or split-bf16 (dtype 2).  `packed` is the blob of `params` for that dtype (the raw parameters travel along for the backward pass and
-    as the differentiable inputs)."""
-    return hrnet_forward_train(packed, lrs, alphas, num_layers, alpha_residual, dtype)
+    as the differentiable inputs).  `scale`: the upscale factor the blob was packed for; sr is (B, 1, scale H, scale W)."""
+    return hrnet_forward_train(packed, lrs, alphas, num_layers, alpha_residual, dtype, scale)
 
 
 @_op_hrnet_forward_train.register_fake
-def _(packed, lrs, alphas, params, num_layers, alpha_residual, dtype):
+def _(packed, lrs, alphas, params, num_layers, alpha_residual, dtype, scale=3):
     b, v, h, w = lrs.shape
     nbytes = load_library().hrn_hrnet_train_workspace_bytes(num_layers, b, v, h, w)
-    return lrs.new_empty((b, 1, 3 * h, 3 * w), dtype=torch.float32), lrs.new_empty((nbytes,), dtype=torch.uint8)
+    return lrs.new_empty((b, 1, scale * h, scale * w), dtype=torch.float32), lrs.new_empty((nbytes,), dtype=torch.uint8)
 
 
 @torch.library.custom_op("hrnet_hip::hrnet_backward", mutates_args=("tws",), device_types="cuda")     # (tws also holds the backward's scratch buffers)
 def _op_hrnet_backward(packed: torch.Tensor, params: Sequence[torch.Tensor], lrs: torch.Tensor, alphas: torch.Tensor, d_sr: torch.Tensor,
-                       tws: torch.Tensor, num_layers: int, alpha_residual: bool, dtype: int) -> List[torch.Tensor]:
+                       tws: torch.Tensor, num_layers: int, alpha_residual: bool, dtype: int, scale: int = 3) -> List[torch.Tensor]:
     """d_sr -> the gradient of every parameter (train.py:190 through HRNet), in `hrnet_param_names` order."""
     names = hrnet_param_names(num_layers)
     named = dict(zip(names, params))
     grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for k, p in named.items()}
-    hrnet_backward(packed, named, grads, num_layers, alpha_residual, lrs, alphas, d_sr.contiguous(), tws, dtype)
+    hrnet_backward(packed, named, grads, num_layers, alpha_residual, lrs, alphas, d_sr.contiguous(), tws, dtype, scale)
     return [grads[k] for k in names]
 
 
 @_op_hrnet_backward.register_fake
-def _(packed, params, lrs, alphas, d_sr, tws, num_layers, alpha_residual, dtype):
+def _(packed, params, lrs, alphas, d_sr, tws, num_layers, alpha_residual, dtype, scale=3):
     return [p.new_empty(p.shape, dtype=torch.float32) for p in params]
 
 
 def _hrnet_train_setup(ctx, inputs, output):
-    packed, lrs, alphas, params, num_layers, alpha_residual, dtype = inputs
-    ctx.num_layers, ctx.alpha_residual, ctx.n, ctx.dtype = num_layers, alpha_residual, len(params), dtype
+    packed, lrs, alphas, params, num_layers, alpha_residual, dtype, scale = inputs
+    ctx.num_layers, ctx.alpha_residual, ctx.n, ctx.dtype, ctx.scale = num_layers, alpha_residual, len(params), dtype, scale
     ctx.set_materialize_grads(False)          # (or autograd hands the backward a zero-filled "gradient" of the 20 GB workspace output)
     ctx.save_for_backward(packed, lrs, alphas, output[1], *params)
 
 
 def _hrnet_train_backward(ctx, d_sr, _d_tws):
     packed, lrs, alphas, tws, *params = ctx.saved_tensors
+    # one entry per input as the caller passed them: a trailing `scale` equal to its default is not among them
+    tail = (None,) * (len(ctx.needs_input_grad) - 4)
     if d_sr is None:
-        return None, None, None, [None] * len(params), None, None, None
+        return (None, None, None, [None] * len(params)) + tail
     # (tws.data: the backward's scratch buffers live in tws too, so the op declares it mutated; through an alias with its own version
     # counter the saved tensor stays valid for a second backward pass - backward(retain_graph=True), the kept intermediates are only read)
-    grads = torch.ops.hrnet_hip.hrnet_backward(packed, params, lrs, alphas, d_sr, tws.data, ctx.num_layers, ctx.alpha_residual, ctx.dtype)
-    return None, None, None, [g.to(p.dtype) for g, p in zip(grads, params)], None, None, None
+    grads = torch.ops.hrnet_hip.hrnet_backward(packed, params, lrs, alphas, d_sr, tws.data, ctx.num_layers, ctx.alpha_residual, ctx.dtype,
+                                               ctx.scale)
+    return (None, None, None, [g.to(p.dtype) for g, p in zip(grads, params)]) + tail
 
 
 _op_hrnet_forward_train.register_autograd(_hrnet_train_backward, setup_context=_hrnet_train_setup)

@@ -48,6 +48,11 @@ size_t stack_lo(int dt, int B, int V, int H, int W) { return dt == HRN_BF16X3 ? 
 size_t fused_lo(int dt, int B, int H, int W) { return dt == HRN_BF16X3 ? (size_t)B * H * W * 64 * 2 : 0; }
 bool dtype_ok(int dt) { return dt == HRN_F32 || dt == HRN_BF16 || dt == HRN_BF16X3; }
 
+int check_scale(int scale) {
+    HRN_CHECK(hrn_scale_ok(scale), -2, "scale must be 2, 3 or 4 (decoder kernel_size == stride; got %d)", scale);
+    return 0;
+}
+
 int check_common(int dt, int nl, int B, int V, int H, int W) {
     HRN_CHECK(dtype_ok(dt), -2, "dtype must be HRN_DTYPE_F32, HRN_DTYPE_BF16 or HRN_DTYPE_BF16X3 (got %d)", dt);
     HRN_CHECK(nl >= 0 && nl <= HRN_MAX_RES_LAYERS, -2, "num_layers %d out of range 0..%d", nl, HRN_MAX_RES_LAYERS);
@@ -57,7 +62,7 @@ int check_common(int dt, int nl, int B, int V, int H, int W) {
 
 int encoder_impl(const void* pk, int dt, int nl, const float* lrs, int B, int V, int H, int W,
                  void* emb, void* ws, const HrnetWs& wl, hipStream_t s) {
-    const HrnetLayout L = hrnet_layout(dt, nl);
+    const HrnetLayout L = hrnet_layout(dt, nl, 3);        // (the encoder's offsets are the same at every scale)
     const size_t hw = (size_t)H * W;
     float* ref = (float*)at(ws, wl.ref);
     void* bufA = at(ws, wl.buf_a);
@@ -87,7 +92,7 @@ int encoder_impl(const void* pk, int dt, int nl, const float* lrs, int B, int V,
 
 int fuse_impl(const void* pk, int dt, int nl, int alpha_residual, void* emb, const float* alphas, int B, int V, int H, int W,
               void* fused, void* ws, const HrnetWs& wl, hipStream_t s) {
-    const HrnetLayout L = hrnet_layout(dt, nl);
+    const HrnetLayout L = hrnet_layout(dt, nl, 3);        // (the fusion's offsets are the same at every scale)
     const size_t hw = (size_t)H * W, es = hrn_esize(dt);
     void* t1 = at(ws, wl.buf_a);
     void* t2 = at(ws, wl.buf_b);
@@ -127,10 +132,10 @@ int fuse_impl(const void* pk, int dt, int nl, int alpha_residual, void* emb, con
     return 0;
 }
 
-int decoder_impl(const void* pk, int dt, int nl, const void* fused, int N, int H, int W, float* sr, hipStream_t s) {
-    const HrnetLayout L = hrnet_layout(dt, nl);
+int decoder_impl(const void* pk, int dt, int nl, int scale, const void* fused, int N, int H, int W, float* sr, hipStream_t s) {
+    const HrnetLayout L = hrnet_layout(dt, nl, scale);
     return hrn_launch_decoder(dt, fused, at(pk, L.dec_w), (const float*)at(pk, L.dec_b), (const float*)at(pk, L.dec_a),
-                              (const float*)at(pk, L.fin_w), (const float*)at(pk, L.fin_b), sr, N, H, W, s, fused_lo(dt, N, H, W));
+                              (const float*)at(pk, L.fin_w), (const float*)at(pk, L.fin_b), sr, N, H, W, s, fused_lo(dt, N, H, W), scale);
 }
 
 // ---------------------------------------------------------------- ShiftNet layouts (packed parameters: shiftnet_layout.h)
@@ -161,17 +166,24 @@ extern "C" {
 int hrn_version(void) { return HRN_ABI_VERSION; }
 const char* hrn_last_error(void) { return g_err; }
 
-size_t hrn_hrnet_packed_bytes(int dtype, int num_layers) {
-    if (!dtype_ok(dtype) || num_layers < 0 || num_layers > HRN_MAX_RES_LAYERS) return 0;
-    return hrnet_layout(dtype, num_layers).total;
+size_t hrn_hrnet_packed_bytes(int dtype, int num_layers) { return hrn_hrnet_packed_bytes_s(dtype, num_layers, 3); }
+
+size_t hrn_hrnet_packed_bytes_s(int dtype, int num_layers, int scale) {
+    if (!dtype_ok(dtype) || num_layers < 0 || num_layers > HRN_MAX_RES_LAYERS || !hrn_scale_ok(scale)) return 0;
+    return hrnet_layout(dtype, num_layers, scale).total;
 }
 
 int hrn_hrnet_pack(const hrn_hrnet_params* P, int dt, void* packed, size_t packed_bytes, void* stream) {
-    HRN_CHECK(P && packed, -2, "hrn_hrnet_pack: null argument");
+    return hrn_hrnet_pack_s(P, dt, 3, packed, packed_bytes, stream);
+}
+
+int hrn_hrnet_pack_s(const hrn_hrnet_params* P, int dt, int scale, void* packed, size_t packed_bytes, void* stream) {
     int rc;
+    if ((rc = check_scale(scale))) return rc;
+    HRN_CHECK(P && packed, -2, "hrn_hrnet_pack: null argument");
     if ((rc = check_common(dt, P->num_layers, 1, 1, 1, 1))) return rc;
     const int nl = P->num_layers;
-    const HrnetLayout L = hrnet_layout(dt, nl);
+    const HrnetLayout L = hrnet_layout(dt, nl, scale);
     HRN_CHECK(packed_bytes >= L.total, -3, "hrn_hrnet_pack: packed buffer too small (%zu < %zu)", packed_bytes, L.total);
     hipStream_t s = (hipStream_t)stream;
     auto copy = [&](size_t off, const float* src, size_t n) -> int {
@@ -195,7 +207,7 @@ int hrn_hrnet_pack(const hrn_hrnet_params* P, int dt, void* packed, size_t packe
     }
     if ((rc = hrn_launch_conv_pack(dt, 128, 64, P->fuse_out_w, at(packed, L.fout_w), s))) return rc;
     if ((rc = copy(L.fout_b, P->fuse_out_b, 64)) || (rc = copy(L.fout_a, P->fuse_out_a, 1))) return rc;
-    if ((rc = hrn_launch_decoder_pack(dt == HRN_BF16X3 ? HRN_F32 : dt, P->dec_w, at(packed, L.dec_w), s))) return rc;     // bf16x3: the decoder is the fp32 one
+    if ((rc = hrn_launch_decoder_pack(dt == HRN_BF16X3 ? HRN_F32 : dt, P->dec_w, at(packed, L.dec_w), s, scale))) return rc;     // bf16x3: the decoder is the fp32 one
     if ((rc = copy(L.dec_b, P->dec_b, 64)) || (rc = copy(L.dec_a, P->dec_a, 1))) return rc;
     if ((rc = copy(L.fin_w, P->fin_w, 64)) || (rc = copy(L.fin_b, P->fin_b, 1))) return rc;
     return 0;
@@ -227,16 +239,25 @@ int hrn_fuse_forward(const void* packed, int dt, int nl, int alpha_residual, voi
 }
 
 int hrn_decoder_forward(const void* packed, int dt, int nl, const void* fused, int N, int H, int W, float* sr, void* stream) {
+    return hrn_decoder_forward_s(packed, dt, nl, 3, fused, N, H, W, sr, stream);
+}
+
+int hrn_decoder_forward_s(const void* packed, int dt, int nl, int scale, const void* fused, int N, int H, int W, float* sr, void* stream) {
     int rc;
-    if ((rc = check_common(dt, nl, N, 1, H, W))) return rc;
+    if ((rc = check_scale(scale)) || (rc = check_common(dt, nl, N, 1, H, W))) return rc;
     HRN_CHECK(packed && fused && sr, -2, "hrn_decoder_forward: null argument");
-    return decoder_impl(packed, dt, nl, fused, N, H, W, sr, (hipStream_t)stream);
+    return decoder_impl(packed, dt, nl, scale, fused, N, H, W, sr, (hipStream_t)stream);
 }
 
 int hrn_hrnet_forward(const void* packed, int dt, int nl, int alpha_residual, const float* lrs, const float* alphas,
                       int B, int V, int H, int W, float* sr, void* ws, size_t ws_bytes, void* stream) {
+    return hrn_hrnet_forward_s(packed, dt, nl, 3, alpha_residual, lrs, alphas, B, V, H, W, sr, ws, ws_bytes, stream);
+}
+
+int hrn_hrnet_forward_s(const void* packed, int dt, int nl, int scale, int alpha_residual, const float* lrs, const float* alphas,
+                        int B, int V, int H, int W, float* sr, void* ws, size_t ws_bytes, void* stream) {
     int rc;
-    if ((rc = check_common(dt, nl, B, V, H, W))) return rc;
+    if ((rc = check_scale(scale)) || (rc = check_common(dt, nl, B, V, H, W))) return rc;
     HRN_CHECK(packed && lrs && alphas && sr && ws, -2, "hrn_hrnet_forward: null argument");
     const HrnetWs wl = hrnet_ws(dt, B, V, H, W);
     HRN_CHECK(ws_bytes >= wl.total, -3, "hrn_hrnet_forward: workspace too small (%zu < %zu)", ws_bytes, wl.total);
@@ -245,7 +266,7 @@ int hrn_hrnet_forward(const void* packed, int dt, int nl, int alpha_residual, co
     void* fused = at(ws, wl.fused);
     if ((rc = encoder_impl(packed, dt, nl, lrs, B, V, H, W, emb, ws, wl, s))) return rc;
     if ((rc = fuse_impl(packed, dt, nl, alpha_residual, emb, alphas, B, V, H, W, fused, ws, wl, s))) return rc;
-    return decoder_impl(packed, dt, nl, fused, B, H, W, sr, s);
+    return decoder_impl(packed, dt, nl, scale, fused, B, H, W, sr, s);
 }
 
 // ----------------------------------------------------------------- ShiftNet

@@ -40,12 +40,13 @@ int hrn_launch_fuse_df(const float* dsn, const float* alphas, int alpha_vs, int 
                        size_t hw, int B, hipStream_t s, int dt = HRN_F32);
 int hrn_launch_fuse_scatter(const float* dsn, const float* dz, int n_in, int half, int pair_last, int alpha_residual, float* ds,
                             size_t hw, int B, hipStream_t s, int dt = HRN_F32);
-// Decoder backward (HRNet.py:147-156,167-169): fused [N][H][W][64] f32, d_sr [N][3H][3W]; reference-layout parameters
-// wd (64,64,3,3) = (Cin,Cout,kH,kW), bd (64), ad (1), wf (64), bf (1).  Writes d_fused; accumulates the five gradients.
+// Decoder backward (HRNet.py:147-156,167-169), S = scale in {2, 3, 4}: fused [N][H][W][64] f32, d_sr [N][S H][S W]; reference-layout
+// parameters wd (64,64,S,S) = (Cin,Cout,kH,kW), bd (64), ad (1), wf (64), bf (1).  Writes d_fused; accumulates the five gradients.
 int hrn_launch_decoder_bwd(const float* fused, const float* d_sr, const float* wd, const float* bd, const float* ad, const float* wf,
                            float* d_fused, float* dwd, float* dbd, float* dad, float* dwf, float* dbf, int N, int H, int W,
-                           void* scratch, int num_cus, hipStream_t s);
-size_t hrn_decoder_bwd_scratch_bytes(int num_cus);
+                           void* scratch, int num_cus, hipStream_t s, int scale = 3);
+// bytes of the launcher's `scratch` (0 for an unsupported scale); no larger than hrn_bwd_scratch_bytes for any scale
+size_t hrn_decoder_bwd_scratch_bytes(int num_cus, int scale = 3);
 // dx = conv3x3(g, W^T with taps flipped) (+ res): the data gradient of a cin -> cout convolution with raw weights
 // w [cout][cin][3][3], on the forward f32 kernel.  wt / wtp: scratch for the transposed OIHW tensor and its packed form
 // (cin*cout*9 floats each); zero_bias: max(cin, cout) zero floats.

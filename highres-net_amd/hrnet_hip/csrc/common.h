@@ -172,4 +172,6 @@ __device__ __forceinline__ void block_pair_sum(const double* __restrict__ partia
 static inline size_t hrn_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // bytes per element of an activation / weight tensor (bf16x3: both planes together)
 static inline int hrn_esize(int dt) { return dt == HRN_BF16 ? 2 : 4; }
+// HRNet upscale factors the decoder is built for (ConvTranspose2d kernel_size == stride == S)
+static inline bool hrn_scale_ok(int s) { return s >= 2 && s <= 4; }
 

@@ -1,4 +1,5 @@
 // Packed-parameter layout of HRNet (byte offsets into the blob hrn_hrnet_pack() fills), shared by api.hip and train.hip.
+// The decoder's tensors come last, so every offset before dec_w is the same for every upscale factor.
 #pragma once
 #include <string.h>
 #include "../../../include/hrnet_hip.h"
@@ -19,7 +20,7 @@ struct HrnetLayout {
     size_t total;
 };
 
-static inline HrnetLayout hrnet_layout(int dt, int nl) {
+static inline HrnetLayout hrnet_layout(int dt, int nl, int scale) {
     HrnetLayout L;
     memset(&L, 0, sizeof L);
     const size_t es = hrn_esize(dt);
@@ -30,7 +31,8 @@ static inline HrnetLayout hrnet_layout(int dt, int nl) {
     L.encf_w = take(64 * 64 * 9 * es); L.encf_b = take(64 * 4);
     for (int i = 0; i < 2; ++i) { L.fres_w[i] = take(128 * 128 * 9 * es); L.fres_b[i] = take(128 * 4); L.fres_a[i] = take(4); }
     L.fout_w = take(128 * 64 * 9 * es); L.fout_b = take(64 * 4); L.fout_a = take(4);
-    L.dec_w = take(64 * 64 * 9 * es); L.dec_b = take(64 * 4); L.dec_a = take(4);
+    // (Cin, Cout, S, S); bf16x3 keeps the fp32 decoder weights (es = 4)
+    L.dec_w = take((size_t)64 * 64 * scale * scale * es); L.dec_b = take(64 * 4); L.dec_a = take(4);
     L.fin_w = take(64 * 4); L.fin_b = take(4);
     L.total = off;
     return L;

@@ -16,10 +16,13 @@ int hrn_launch_stem_pre(const float* in0, size_t img_stride0, const float* in1, 
 int hrn_launch_plane_mean(const float* x, float* mean, int planes, size_t hw, hipStream_t stream);
 
 // ---- decoder.hip
-// fused [N][HW][64] (dt) -> sr [N][3H][3W] f32.  wpk: packed deconv weights (hrn_launch_decoder_pack), bias/slope/wf/bf f32.
+// fused [N][HW][64] (dt) -> sr [N][S H][S W] f32, S = scale in {2, 3, 4}.  wpk: packed deconv weights (hrn_launch_decoder_pack of
+// the same scale), bias/slope/wf/bf f32.
 int hrn_launch_decoder(int dt, const void* fused, const void* wpk, const float* bias, const float* slope,
-                       const float* wf, const float* bf, float* sr, int N, int H, int W, hipStream_t stream, size_t fused_lo = 0);
-int hrn_launch_decoder_pack(int dt, const float* w_iokk, void* packed, hipStream_t stream);
+                       const float* wf, const float* bf, float* sr, int N, int H, int W, hipStream_t stream, size_t fused_lo = 0,
+                       int scale = 3);
+// w_iokk (64, 64, S, S)
+int hrn_launch_decoder_pack(int dt, const float* w_iokk, void* packed, hipStream_t stream, int scale = 3);
 
 // ---- lanczos.hip
 int hrn_launch_lanczos_taps(const float* d, int n, float* taps, hipStream_t stream);

@@ -7,7 +7,7 @@
 //   encoder   a0 = PReLU(stem);  h_l = PReLU(conv(a_l));  r_l = PReLU(conv(h_l));  a_{l+1} = a_l + r_l;  stack_0 = conv(a_nl)
 //   level     z = cat(s_i, s_partner);  t1 = PReLU(convA(z));  u = PReLU(convB(t1));  t2 = z + u;  f = PReLU(convC(t2));
 //             stack_{l+1}[i] = s_i + alpha_partner f   (i < n/2)
-//   decoder   sr = conv1x1(PReLU(deconv(stack_T)))
+//   decoder   sr = conv1x1(PReLU(deconv(stack_T)))       (kernel_size == stride == S, the upscale factor: 2, 3 or 4)
 // Backward walks it in reverse with three primitives per convolution: PReLU backward on the stored post-activation
 // (+ slope gradient), the weight/bias gradient (backward.hip), and the data gradient, which is the forward convolution
 // kernel run on the transposed, tap-flipped weights.  All gradients are accumulated (+=) into the caller's buffers.
@@ -67,8 +67,9 @@ TrainWs train_ws(int nl, int B, int V, int H, int W) {
     w.wt = take((size_t)128 * 128 * 9 * 4);
     w.wtp = take((size_t)128 * 128 * 9 * 4);
     w.zero_bias = take(128 * 4);
+    // one scratch for every scale: the decoder's largest (S = 4) is below the convolutions' anyway, so the size is scale-free
     size_t sc = hrn_bwd_scratch_bytes(num_cus());
-    const size_t sd = hrn_decoder_bwd_scratch_bytes(num_cus());
+    const size_t sd = hrn_decoder_bwd_scratch_bytes(num_cus(), 4);
     if (sd > sc) sc = sd;
     w.scratch = take(sc);
     w.dec_f = take((size_t)B * hw * 64 * 4);
@@ -137,23 +138,34 @@ size_t hrn_hrnet_train_workspace_bytes(int num_layers, int B, int V, int H, int 
 
 int hrn_hrnet_forward_train(const void* pk, int nl, int alpha_residual, const float* lrs, const float* alphas, int B, int V, int H, int W,
                             float* sr, void* tws, size_t tws_bytes, void* stream) {
-    return hrn_hrnet_forward_train_dt(pk, HRN_F32, nl, alpha_residual, lrs, alphas, B, V, H, W, sr, tws, tws_bytes, stream);
+    return hrn_hrnet_forward_train_s(pk, HRN_F32, nl, 3, alpha_residual, lrs, alphas, B, V, H, W, sr, tws, tws_bytes, stream);
 }
 
 int hrn_hrnet_backward(const void* pk, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas, int B, int V,
                        int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, void* tws, size_t tws_bytes, void* stream) {
-    return hrn_hrnet_backward_dt(pk, HRN_F32, Pr, alpha_residual, lrs, alphas, B, V, H, W, d_sr, Gr, tws, tws_bytes, stream);
+    return hrn_hrnet_backward_s(pk, HRN_F32, 3, Pr, alpha_residual, lrs, alphas, B, V, H, W, d_sr, Gr, tws, tws_bytes, stream);
 }
 
 int hrn_hrnet_forward_train_dt(const void* pk, int dt, int nl, int alpha_residual, const float* lrs, const float* alphas, int B, int V, int H,
                                int W, float* sr, void* tws, size_t tws_bytes, void* stream) {
+    return hrn_hrnet_forward_train_s(pk, dt, nl, 3, alpha_residual, lrs, alphas, B, V, H, W, sr, tws, tws_bytes, stream);
+}
+
+int hrn_hrnet_backward_dt(const void* pk, int dt, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas, int B,
+                          int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, void* tws, size_t tws_bytes, void* stream) {
+    return hrn_hrnet_backward_s(pk, dt, 3, Pr, alpha_residual, lrs, alphas, B, V, H, W, d_sr, Gr, tws, tws_bytes, stream);
+}
+
+int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alpha_residual, const float* lrs, const float* alphas, int B, int V,
+                              int H, int W, float* sr, void* tws, size_t tws_bytes, void* stream) {
     int rc;
+    HRN_CHECK(hrn_scale_ok(scale), -2, "hrn_hrnet_forward_train: scale must be 2, 3 or 4 (got %d)", scale);
     if ((rc = check_train(nl, B, V, H, W))) return rc;
     HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16X3, -2, "hrn_hrnet_forward_train: dtype must be HRN_DTYPE_F32 or HRN_DTYPE_BF16X3 (got %d)", dt);
     HRN_CHECK(pk && lrs && alphas && sr && tws, -2, "hrn_hrnet_forward_train: null argument");
     const TrainWs L = train_ws(nl, B, V, H, W);
     HRN_CHECK(tws_bytes >= L.total, -3, "hrn_hrnet_forward_train: workspace too small (%zu < %zu)", tws_bytes, L.total);
-    const HrnetLayout P = hrnet_layout(dt, nl);
+    const HrnetLayout P = hrnet_layout(dt, nl, scale);
     hipStream_t s = (hipStream_t)stream;
     const size_t hw = (size_t)H * W;
     const int M = B * V;
@@ -200,12 +212,13 @@ int hrn_hrnet_forward_train_dt(const void* pk, int dt, int nl, int alpha_residua
     // views left after the last level: 1 (or V itself for V == 1); torch.mean over them (HRNet.py:134) is the identity
     return hrn_launch_decoder(dt, at(tws, L.stack[L.T]), at(pk, P.dec_w), (const float*)at(pk, P.dec_b), (const float*)at(pk, P.dec_a),
                               (const float*)at(pk, P.fin_w), (const float*)at(pk, P.fin_b), sr, B, H, W, s,
-                              lo_of(dt, (size_t)B * L.n_in[L.T] * hw * 64));
+                              lo_of(dt, (size_t)B * L.n_in[L.T] * hw * 64), scale);
 }
 
-int hrn_hrnet_backward_dt(const void* pk, int dt, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas, int B,
-                          int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, void* tws, size_t tws_bytes, void* stream) {
+int hrn_hrnet_backward_s(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
+                         int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, void* tws, size_t tws_bytes, void* stream) {
     int rc;
+    HRN_CHECK(hrn_scale_ok(scale), -2, "hrn_hrnet_backward: scale must be 2, 3 or 4 (got %d)", scale);
     HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16X3, -2, "hrn_hrnet_backward: dtype must be HRN_DTYPE_F32 or HRN_DTYPE_BF16X3 (got %d)", dt);
     HRN_CHECK(pk && Pr && Gr && lrs && alphas && d_sr && tws, -2, "hrn_hrnet_backward: null argument");
     const int nl = Pr->num_layers;
@@ -224,7 +237,7 @@ int hrn_hrnet_backward_dt(const void* pk, int dt, const hrn_hrnet_params* Pr, in
     // PReLU backward works from the stored post-activation while the slope is positive.  For a slope <= 0 (the reference allows any)
     // the pre-activation is recomputed into `xpre` by the forward kernel without activation - a launch that does nothing unless the
     // slope on the device says so (ConvParams::only_if_nonpos): no host round trip, ~3 us per PReLU in the usual case.
-    const HrnetLayout P = hrnet_layout(dt, nl);
+    const HrnetLayout P = hrnet_layout(dt, nl, scale);
     float* xpre = (float*)at(tws, L.xpre);
     auto pre = [&](int cin, int cout, const void* x, const void* wpk, const float* bias, const float* slope, int Mi) -> int {
         ConvParams q = conv_base(Mi, H, W);
@@ -242,11 +255,13 @@ int hrn_hrnet_backward_dt(const void* pk, int dt, const hrn_hrnet_params* Pr, in
         float* fg = (float*)at(tws, L.dec_g);
         if ((rc = hrn_launch_planes_to_f32(at(tws, L.stack[L.T]), nf * 2, ff, nf, s))) return rc;
         if ((rc = hrn_launch_decoder_bwd(ff, d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, fg,
-                                         mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a), mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s)))
+                                         mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a), mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s,
+                                         scale)))
             return rc;
         if ((rc = hrn_launch_f32_to_planes(fg, dsn, nf * 2, nf, s))) return rc;
     } else if ((rc = hrn_launch_decoder_bwd((const float*)at(tws, L.stack[L.T]), d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, dsn,
-                                            mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a), mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s)))
+                                            mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a), mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s,
+                                            scale)))
         return rc;
 
     // ---- fusion levels, last to first                                                HRNet.py:113-132

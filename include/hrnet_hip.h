@@ -9,6 +9,7 @@
  *   hrn_encoder_forward    <-  median/stack + Encoder.forward         src/DeepNetworks/HRNet.py:200-206, :62-74
  *   hrn_fuse_forward       <-  RecuversiveNet.forward                 src/DeepNetworks/HRNet.py:99-134
  *   hrn_decoder_forward    <-  Decoder.forward                        src/DeepNetworks/HRNet.py:158-169
+ *   hrn_*_s                <-  the same at upscale factor 2, 3 or 4   src/DeepNetworks/HRNet.py:147-156 (config decoder.deconv)
  *   hrn_shiftnet_forward   <-  ShiftNet.forward(x)                    src/DeepNetworks/ShiftNet.py:49-75
  *   hrn_lanczos_shift      <-  lanczos.lanczos_shift(img, shift, ...) src/lanczos.py:47-107
  *                              (and ShiftNet.transform, ShiftNet.py:77-90, which only re-labels its arguments)
@@ -36,7 +37,10 @@
  *                        hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (~2^-16 per product): the
  *                        reference's fp32 arithmetic (train.py:168-171, predict.py:36-37) to ~1e-5 at a third of the bf16
  *                        matrix rate.  Stage tensors (emb, fused) are [2 planes][...][64] bf16, lo plane directly behind hi.
- *     inputs (lrs, alphas, ShiftNet pairs, Lanczos images) and the SR output are always f32.
+ *     inputs (lrs, alphas, ShiftNet pairs, Lanczos images) and the SR output are always f32;
+ *   - a packed HRNet blob is only valid for the dtype AND the upscale factor (`scale`) it was packed with: the *_s entry points take
+ *     the scale explicitly (2, 3 or 4: decoder.deconv kernel_size == stride, src/DeepNetworks/HRNet.py:147-156), the others are
+ *     their scale = 3 case (the reference's shipped config).  Any other scale: -2 before any launch, and 0 from the *_bytes_s sizes.
  */
 #ifndef HRNET_HIP_H
 #define HRNET_HIP_H
@@ -73,7 +77,7 @@ typedef struct hrn_hrnet_params {
     const float* fuse_out_w;                          /* fuse.fuse.1.weight (64,128,3,3) */
     const float* fuse_out_b;
     const float* fuse_out_a;                          /* fuse.fuse.2.weight (1) */
-    const float* dec_w;                               /* decode.deconv.0.weight (64,64,3,3) = (Cin,Cout,kH,kW) */
+    const float* dec_w;                               /* decode.deconv.0.weight (64,64,3,3) = (Cin,Cout,kH,kW); (64,64,S,S) at scale S */
     const float* dec_b;
     const float* dec_a;                               /* decode.deconv.1.weight (1) */
     const float* fin_w;                               /* decode.final.weight (1,64,1,1) */
@@ -100,6 +104,20 @@ int hrn_fuse_forward(const void* packed, int dtype, int num_layers, int alpha_re
 int hrn_decoder_forward(const void* packed, int dtype, int num_layers, const void* fused, int N, int H, int W,
                         float* sr, void* stream);
 
+/* Any upscale factor scale in {2, 3, 4} (ConvTranspose2d(64, 64, scale, stride=scale), HRNet.py:147-156).  Only the decoder
+ * depends on it: the blob's decoder weights, dec_w (64,64,scale,scale), and the SR size (B,1,scale H,scale W).
+ *   hrn_hrnet_packed_bytes_s / hrn_hrnet_pack_s  <-  load_state_dict of a model built with that config (HRNet.py:138-156)
+ *   hrn_hrnet_forward_s                          <-  HRNet.forward(lrs, alphas)   HRNet.py:186-211: sr (B,1,scale H,scale W)
+ *   hrn_decoder_forward_s                        <-  Decoder.forward              HRNet.py:158-169: sr (N,1,scale H,scale W)
+ * The workspace (hrn_hrnet_workspace_bytes) and the encoder / fusion stages above do not depend on the scale. */
+size_t hrn_hrnet_packed_bytes_s(int dtype, int num_layers, int scale);
+int hrn_hrnet_pack_s(const hrn_hrnet_params* params, int dtype, int scale, void* packed, size_t packed_bytes, void* stream);
+int hrn_hrnet_forward_s(const void* packed, int dtype, int num_layers, int scale, int alpha_residual,
+                        const float* lrs, const float* alphas, int B, int V, int H, int W,
+                        float* sr, void* workspace, size_t workspace_bytes, void* stream);
+int hrn_decoder_forward_s(const void* packed, int dtype, int num_layers, int scale, const void* fused, int N, int H, int W,
+                          float* sr, void* stream);
+
 /* Training path (fp32 only): `srs = fusion_model(lrs, alphas)` with grad enabled and `loss.backward()` through HRNet,
  * src/train.py:172-190.  hrn_hrnet_forward_train is hrn_hrnet_forward(HRN_DTYPE_F32) with every intermediate kept in
  * `train_ws`; hrn_hrnet_backward consumes that workspace (same B, V, H, W) and d_sr = dLoss/d sr (B,1,3H,3W) and
@@ -123,6 +141,16 @@ int hrn_hrnet_forward_train_dt(const void* packed, int dtype, int num_layers, in
 int hrn_hrnet_backward_dt(const void* packed, int dtype, const hrn_hrnet_params* params, int alpha_residual, const float* lrs,
                           const float* alphas, int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* grads,
                           void* train_ws, size_t train_ws_bytes, void* stream);
+/* The same at any upscale factor scale in {2, 3, 4} (the _dt forms are scale = 3): sr and d_sr are (B,1,scale H,scale W), `packed` is
+ * the blob of hrn_hrnet_pack_s at that scale and grads->dec_w (64,64,scale,scale).  `srs = fusion_model(lrs, alphas)` ...
+ * `loss.backward()` through HRNet, src/train.py:172-190, for a model whose decoder.deconv has kernel_size == stride == scale.
+ * hrn_hrnet_train_workspace_bytes serves every scale (the decoder's scratch at scale 4 is below the convolutions'). */
+int hrn_hrnet_forward_train_s(const void* packed, int dtype, int num_layers, int scale, int alpha_residual, const float* lrs,
+                              const float* alphas, int B, int V, int H, int W, float* sr, void* train_ws, size_t train_ws_bytes,
+                              void* stream);
+int hrn_hrnet_backward_s(const void* packed, int dtype, int scale, const hrn_hrnet_params* params, int alpha_residual, const float* lrs,
+                         const float* alphas, int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* grads,
+                         void* train_ws, size_t train_ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ ShiftNet */
 typedef struct hrn_shiftnet_params {
