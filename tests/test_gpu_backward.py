@@ -58,6 +58,9 @@ def _oracle_grads(lrs, alphas, cot, alpha_residual, seed=1234, slopes=None):
     (1, 7, 24, 7, True),        # 24 x 24: partial tiles in both directions; odd at two levels
     (2, 6, 16, 6, False),       # alpha_residual = false branch (HRNet.py:123)
     (2, 1, 16, 1, True),        # a single view: no fusion level at all
+    (1, 3, 33, 3, True),        # H % 8 == 1, W % 32 == 1, odd V: the x halo's leftover columns, a one-pixel last bf16x3 strip
+    (2, 2, 5, 2, True),         # smaller than one tile in both directions
+    (1, 9, 37, 1, True),        # one real view among nine
 ])
 @pytest.mark.parametrize("prec", ["fp32", "bf16x3"])
 def test_hrnet_backward_vs_autograd_oracle(B, V, S, n_real, alpha_residual, prec):
@@ -286,7 +289,9 @@ def test_bf16x3_backward_with_nonpositive_slopes():
 _torch_lanczos_shift = torch_port.lanczos_shift      # fp64 torch restatement of lanczos.py:5-107, pinned by tests/golden/train_step.npz
 
 
-@pytest.mark.parametrize("b,c,H,W", [(1, 5, 48, 48), (2, 3, 20, 70), (1, 2, 7, 9)])
+@pytest.mark.parametrize("b,c,H,W", [(1, 5, 48, 48), (2, 3, 20, 70), (1, 2, 7, 9),
+                                     (1, 32, 192, 192),     # apply_shifts at the training shape: b = 1, c = B frames of 3S x 3S
+                                     (1, 1, 520, 520)])     # above 512^2 px: lanczos_adjoint_kernel's grid (capped at 1024) strides
 def test_lanczos_shift_backward_vs_autograd(b, c, H, W):
     import lanczos
     rng = np.random.Generator(np.random.PCG64(11))

@@ -233,7 +233,7 @@ def test_x3_training_bits_unchanged(dt):
 
 
 # ----------------------------------------------------------------------------- gradients at x2 / x4
-@pytest.mark.parametrize("B,V,S,n_real,alpha_residual", [(2, 5, 16, 4, True), (1, 4, 20, 4, False)])
+@pytest.mark.parametrize("B,V,S,n_real,alpha_residual", [(2, 5, 16, 4, True), (1, 4, 20, 4, False), (1, 3, 33, 3, True)])
 @pytest.mark.parametrize("prec", ["fp32", "bf16x3"])
 @pytest.mark.parametrize("scale", [2, 4])
 def test_backward_vs_autograd_oracle(scale, prec, B, V, S, n_real, alpha_residual):
