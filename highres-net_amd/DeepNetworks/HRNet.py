@@ -118,9 +118,15 @@ class _HRNetLazyTrainFunction(torch.autograd.Function):
         _, tws = binding.hrnet_forward_train(packed, lrs, alphas, m._num_layers, m.fuse.alpha_residual, scale=m._scale)
         named = dict(zip(ctx.names, params))
         grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for k, p in named.items()}
+        # input gradients from the same fp32 recompute, when asked for (alphas: only through an alpha residual, as in the reference)
+        need_lrs = ctx.needs_input_grad[2]
+        need_alphas = ctx.needs_input_grad[3] and bool(m.fuse.alpha_residual) and lrs.shape[1] > 1
+        d_lrs = torch.empty(lrs.shape, dtype=torch.float32, device=lrs.device) if need_lrs else None
+        d_alphas = torch.empty(alphas.shape, dtype=torch.float32, device=alphas.device) if need_alphas else None
         binding.hrnet_backward(packed, named, grads, m._num_layers, m.fuse.alpha_residual, lrs, alphas, d_sr.contiguous(), tws,
-                               scale=m._scale)
-        return (None, None, None, None) + tuple(grads[k].to(named[k].dtype) for k in ctx.names)
+                               scale=m._scale, d_lrs=d_lrs, d_alphas=d_alphas)
+        return ((None, None, d_lrs.to(lrs.dtype) if need_lrs else None, d_alphas.to(alphas.dtype) if need_alphas else None)
+                + tuple(grads[k].to(named[k].dtype) for k in ctx.names))
 
 
 class HRNet(nn.Module):
@@ -159,25 +165,29 @@ class HRNet(nn.Module):
         if lrs.shape[2] != lrs.shape[3]:
             raise ValueError("square low-res images only: the reference reinterprets (H,W) as (W,H) in its .view() "
                              "(HRNet.py:204), which is the identity only for H == W")
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        grad_params = self.training and any(p.requires_grad for p in self.parameters())
+        grad_inputs = lrs.requires_grad or alphas.requires_grad
+        if torch.is_grad_enabled() and (grad_params or grad_inputs):
             # .train() mode with grad enabled - the training loop (train.py:160-190), but also src/predict.py, which never calls
             # .eval() and uses no no_grad (predict.py:86-100, :17-49).  Autograd cannot tell us whether a backward pass will follow:
             #   precision "fp32" (default) / "bf16x3": the training forward of that precision (torch.ops.hrnet_hip.hrnet_forward_train), which
             #                               keeps its intermediates for the HIP backward (same numbers as the inference kernels of that mode);
             #   precision "bf16":           the bf16 inference kernels, as asked for; a backward pass, if one comes, first
             #                               recomputes the forward on the fp32 training kernels (_HRNetLazyTrainFunction).
-            # In .eval() mode (validation, train.py:196-215) the inference kernels run and the result carries no autograd graph.
+            # lrs and alphas go in undetached: autograd asks the backward for their gradients when they require grad (in either mode,
+            # frozen parameters included: attribution, learned view weights, input-space optimisation).
+            # Otherwise, in .eval() mode (validation, train.py:196-215), the inference kernels run and the result carries no autograd graph.
             names = [k for k, _ in self.named_parameters()]
             params = [p for _, p in self.named_parameters()]
             if self._dtype() == binding.BF16:
-                return _HRNetLazyTrainFunction.apply(self, names, lrs.detach(), alphas.detach(), *params)
+                return _HRNetLazyTrainFunction.apply(self, names, lrs, alphas, *params)
             # the dispatcher-registered training op (binding.py): hrn_hrnet_forward_train with hrn_hrnet_backward as its autograd formula
             if names != binding.hrnet_param_names(self._num_layers):
                 raise RuntimeError("HRNet parameters are not in the reference's registration order")
             # precision "bf16x3" trains in split-bf16 too (conv forward, data and weight gradients on the bf16 matrix cores, ~2^-16 per product)
             dt = self._dtype()
             packed = self.packed_parameters()[0] if dt == binding.BF16X3 else self._packed_f32()
-            sr, _tws = torch.ops.hrnet_hip.hrnet_forward_train(packed, lrs.detach().float().contiguous(), alphas.detach().float().contiguous(),
+            sr, _tws = torch.ops.hrnet_hip.hrnet_forward_train(packed, lrs.float().contiguous(), alphas.float().contiguous(),
                                                                params, self._num_layers, bool(self.fuse.alpha_residual), dt,
                                                                self._scale)
             return sr

@@ -92,6 +92,9 @@ SIGNATURES = {
     "hrn_hrnet_backward_s": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(HrnetParams), _c.c_int, _c.c_void_p, _c.c_void_p,
                                         _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(HrnetParams), _c.c_void_p,
                                         _c.c_size_t, _c.c_void_p]),
+    "hrn_hrnet_backward_in": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(HrnetParams), _c.c_int, _c.c_void_p, _c.c_void_p,
+                                         _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(HrnetParams), _c.c_void_p,
+                                         _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_shiftnet_packed_bytes": (_c.c_size_t, []),
     "hrn_shiftnet_pack": (_c.c_int, [_c.POINTER(ShiftnetParams), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_shiftnet_workspace_bytes": (_c.c_size_t, [_c.c_int]),
@@ -328,8 +331,10 @@ def hrnet_forward_train(packed_f32, lrs, alphas, num_layers, alpha_residual, dty
     return sr, tws
 
 
-def hrnet_backward(packed_f32, named_params, named_grads, num_layers, alpha_residual, lrs, alphas, d_sr, tws, dtype=F32, scale=3):
-    """Accumulates dLoss/dparam into named_grads (same keys / shapes as named_params, f32, zero them for plain gradients)."""
+def hrnet_backward(packed_f32, named_params, named_grads, num_layers, alpha_residual, lrs, alphas, d_sr, tws, dtype=F32, scale=3,
+                   d_lrs=None, d_alphas=None):
+    """Accumulates dLoss/dparam into named_grads (same keys / shapes as named_params, f32, zero them for plain gradients).  d_lrs
+    (B,V,H,W) / d_alphas (B,V): contiguous f32 device tensors that receive (are overwritten with) the input gradients, or None."""
     lib = load_library()
     lrs = _dev_f32(lrs, "lrs")
     alphas = _dev_f32(alphas, "alphas")
@@ -342,10 +347,19 @@ def hrnet_backward(packed_f32, named_params, named_grads, num_layers, alpha_resi
     for t, g in zip(keep_p, keep_g):
         if t.shape != g.shape or g.data_ptr() == t.data_ptr():
             raise ValueError("gradient buffers must match the parameters' shapes and not alias them")
+    for name, t, shape in (("d_lrs", d_lrs, (B, V, H, W)), ("d_alphas", d_alphas, (B, V))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != lrs.device):
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on {lrs.device}")
     with torch.cuda.device(lrs.device):
-        _check(lib.hrn_hrnet_backward_s(_ptr(packed_f32), int(dtype), int(scale), ctypes.byref(P), int(bool(alpha_residual)), _ptr(lrs),
-                                        _ptr(alphas), B, V, H, W, _ptr(d_sr), ctypes.byref(G), _ptr(tws), tws.numel(), _stream()),
-               "hrn_hrnet_backward")
+        if d_lrs is None and d_alphas is None:
+            _check(lib.hrn_hrnet_backward_s(_ptr(packed_f32), int(dtype), int(scale), ctypes.byref(P), int(bool(alpha_residual)), _ptr(lrs),
+                                            _ptr(alphas), B, V, H, W, _ptr(d_sr), ctypes.byref(G), _ptr(tws), tws.numel(), _stream()),
+                   "hrn_hrnet_backward")
+        else:
+            _check(lib.hrn_hrnet_backward_in(_ptr(packed_f32), int(dtype), int(scale), ctypes.byref(P), int(bool(alpha_residual)),
+                                             _ptr(lrs), _ptr(alphas), B, V, H, W, _ptr(d_sr), ctypes.byref(G),
+                                             _ptr(d_lrs) if d_lrs is not None else None, _ptr(d_alphas) if d_alphas is not None else None,
+                                             _ptr(tws), tws.numel(), _stream()), "hrn_hrnet_backward_in")
 
 
 # --------------------------------------------------------------------------- ShiftNet
@@ -708,6 +722,30 @@ def _(packed, params, lrs, alphas, d_sr, tws, num_layers, alpha_residual, dtype,
     return [p.new_empty(p.shape, dtype=torch.float32) for p in params]
 
 
+@torch.library.custom_op("hrnet_hip::hrnet_backward_in", mutates_args=("tws",), device_types="cuda")
+def _op_hrnet_backward_in(packed: torch.Tensor, params: Sequence[torch.Tensor], lrs: torch.Tensor, alphas: torch.Tensor, d_sr: torch.Tensor,
+                          tws: torch.Tensor, num_layers: int, alpha_residual: bool, dtype: int, scale: int, need_lrs: bool,
+                          need_alphas: bool) -> Tuple[List[torch.Tensor], torch.Tensor, torch.Tensor]:
+    """hrnet_backward that also returns the input gradients (HRNet.py:198-204, :113-132): (parameter gradients in `hrnet_param_names`
+    order, d_lrs (B,V,H,W), d_alphas (B,V)); an input gradient that was not asked for comes back empty."""
+    names = hrnet_param_names(num_layers)
+    named = dict(zip(names, params))
+    grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for k, p in named.items()}
+    d_lrs = torch.empty(lrs.shape, dtype=torch.float32, device=lrs.device) if need_lrs else None
+    d_alphas = torch.empty(alphas.shape, dtype=torch.float32, device=alphas.device) if need_alphas else None
+    hrnet_backward(packed, named, grads, num_layers, alpha_residual, lrs, alphas, d_sr.contiguous(), tws, dtype, scale, d_lrs=d_lrs,
+                   d_alphas=d_alphas)
+    return ([grads[k] for k in names], d_lrs if need_lrs else lrs.new_empty((0,), dtype=torch.float32),
+            d_alphas if need_alphas else alphas.new_empty((0,), dtype=torch.float32))
+
+
+@_op_hrnet_backward_in.register_fake
+def _(packed, params, lrs, alphas, d_sr, tws, num_layers, alpha_residual, dtype, scale, need_lrs, need_alphas):
+    return ([p.new_empty(p.shape, dtype=torch.float32) for p in params],
+            lrs.new_empty(lrs.shape if need_lrs else (0,), dtype=torch.float32),
+            alphas.new_empty(alphas.shape if need_alphas else (0,), dtype=torch.float32))
+
+
 def _hrnet_train_setup(ctx, inputs, output):
     packed, lrs, alphas, params, num_layers, alpha_residual, dtype, scale = inputs
     ctx.num_layers, ctx.alpha_residual, ctx.n, ctx.dtype, ctx.scale = num_layers, alpha_residual, len(params), dtype, scale
@@ -723,9 +761,18 @@ def _hrnet_train_backward(ctx, d_sr, _d_tws):
         return (None, None, None, [None] * len(params)) + tail
     # (tws.data: the backward's scratch buffers live in tws too, so the op declares it mutated; through an alias with its own version
     # counter the saved tensor stays valid for a second backward pass - backward(retain_graph=True), the kept intermediates are only read)
-    grads = torch.ops.hrnet_hip.hrnet_backward(packed, params, lrs, alphas, d_sr, tws.data, ctx.num_layers, ctx.alpha_residual, ctx.dtype,
-                                               ctx.scale)
-    return (None, None, None, [g.to(p.dtype) for g, p in zip(grads, params)]) + tail
+    # input gradients only when autograd asks for them; alphas reach the reference's graph only through the alpha residual of a
+    # fusion level (HRNet.py:124-128), so without one (or with a single view) their gradient stays None, as in the reference
+    need_lrs = ctx.needs_input_grad[1]
+    need_alphas = ctx.needs_input_grad[2] and bool(ctx.alpha_residual) and lrs.shape[1] > 1
+    if not (need_lrs or need_alphas):
+        grads = torch.ops.hrnet_hip.hrnet_backward(packed, params, lrs, alphas, d_sr, tws.data, ctx.num_layers, ctx.alpha_residual,
+                                                   ctx.dtype, ctx.scale)
+        return (None, None, None, [g.to(p.dtype) for g, p in zip(grads, params)]) + tail
+    grads, d_lrs, d_alphas = torch.ops.hrnet_hip.hrnet_backward_in(packed, params, lrs, alphas, d_sr, tws.data, ctx.num_layers,
+                                                                   ctx.alpha_residual, ctx.dtype, ctx.scale, need_lrs, need_alphas)
+    return (None, d_lrs.to(lrs.dtype) if need_lrs else None, d_alphas.to(alphas.dtype) if need_alphas else None,
+            [g.to(p.dtype) for g, p in zip(grads, params)]) + tail
 
 
 _op_hrnet_forward_train.register_autograd(_hrnet_train_backward, setup_context=_hrnet_train_setup)

@@ -52,3 +52,15 @@ size_t hrn_decoder_bwd_scratch_bytes(int num_cus, int scale = 3);
 // (cin*cout*9 floats each); zero_bias: max(cin, cout) zero floats.
 int hrn_conv_dgrad(int cin, int cout, const float* w, const float* g, float* dx, const float* res, int M, int H, int W, float* wt,
                    void* wtp, const float* zero_bias, hipStream_t s, int dt = HRN_F32);
+// Input gradients (input_grad.hip), WRITTEN rather than accumulated.  Stem data gradient plus the median routing: dA [B*V][H][W][64]
+// (dt) is the stem's pre-activation gradient, w the raw stem weights (64, 2, 3, 3), ref [B][H][W] the forward's lower median of
+// lrs[b, :min(V, 9)]; d_lrs [B][V][H][W] gets channel 0 of the input gradient per view plus, at one view per pixel (the lowest-indexed
+// of the first min(V, 9) views equal to the median), channel 1 summed over the sample's views.
+// wt: scratch for 64 * 18 floats (the weights transposed tap-major)
+int hrn_launch_stem_dgrad_route(const float* dA, const float* w, float* wt, const float* lrs, const float* ref, float* d_lrs, int B, int V,
+                                int H, int W, hipStream_t s, int dt = HRN_F32);
+// One fusion level's alpha gradient: d_alphas[b][pair_last - v] = sum over pixels and channels of dsn * f, image b * half + v of the
+// level's outputs ([B*half][hw][64] each, dt); uses hrn_alpha_grad_scratch_bytes(B * half) bytes of `scratch`
+size_t hrn_alpha_grad_scratch_bytes(int nimg);
+int hrn_launch_alpha_grad(const float* dsn, const float* f, int half, int pair_last, float* d_alphas, int B, int V, size_t hw, void* scratch,
+                          size_t scratch_bytes, hipStream_t s, int dt = HRN_F32);

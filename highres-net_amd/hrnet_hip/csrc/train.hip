@@ -217,6 +217,12 @@ int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alp
 
 int hrn_hrnet_backward_s(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
                          int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, void* tws, size_t tws_bytes, void* stream) {
+    return hrn_hrnet_backward_in(pk, dt, scale, Pr, alpha_residual, lrs, alphas, B, V, H, W, d_sr, Gr, nullptr, nullptr, tws, tws_bytes, stream);
+}
+
+int hrn_hrnet_backward_in(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
+                          int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, float* d_lrs, float* d_alphas, void* tws,
+                          size_t tws_bytes, void* stream) {
     int rc;
     HRN_CHECK(hrn_scale_ok(scale), -2, "hrn_hrnet_backward: scale must be 2, 3 or 4 (got %d)", scale);
     HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16X3, -2, "hrn_hrnet_backward: dtype must be HRN_DTYPE_F32 or HRN_DTYPE_BF16X3 (got %d)", dt);
@@ -225,6 +231,8 @@ int hrn_hrnet_backward_s(const void* pk, int dt, int scale, const hrn_hrnet_para
     if ((rc = check_train(nl, B, V, H, W))) return rc;
     const TrainWs L = train_ws(nl, B, V, H, W);
     HRN_CHECK(tws_bytes >= L.total, -3, "hrn_hrnet_backward: workspace too small (%zu < %zu)", tws_bytes, L.total);
+    for (int t = 0; d_alphas && t < L.T; ++t)
+        HRN_CHECK(hrn_alpha_grad_scratch_bytes(B * (L.n_in[t] / 2)) <= L.dec_f - L.scratch, -3, "hrn_hrnet_backward_in: scratch too small for d_alphas");
     hipStream_t s = (hipStream_t)stream;
     const size_t hw = (size_t)H * W;
     const int M = B * V, cus = num_cus();
@@ -232,6 +240,8 @@ int hrn_hrnet_backward_s(const void* pk, int dt, int scale, const hrn_hrnet_para
     float* G[5];
     for (int i = 0; i < 5; ++i) G[i] = (float*)at(tws, L.g[i]);
     HRN_HIP(hipMemsetAsync(at(tws, L.zero_bias), 0, 128 * 4, s));
+    // d alphas: views that are never bob (view 0, views dropped by parity) and every view without the alpha residual get 0
+    if (d_alphas) HRN_HIP(hipMemsetAsync(d_alphas, 0, (size_t)B * V * 4, s));
     // gradients are handed over as mutable buffers in a params-shaped struct
     auto mut = [](const float* p) { return const_cast<float*>(p); };
     // PReLU backward works from the stored post-activation while the slope is positive.  For a slope <= 0 (the reference allows any)
@@ -275,6 +285,10 @@ int hrn_hrnet_backward_s(const void* pk, int dt, int scale, const hrn_hrnet_para
         float* y3 = G[3];                   // d t1 / gA          [Mh][hw][128]
         float* y2 = G[4];                   // gB, later dz       [Mh][hw][128]
         if ((rc = hrn_launch_fuse_df(dsn, alphas, V, pair_last, half, alpha_residual, x1, hw, B, s, dt))) return rc;
+        // x_new = alice + a_bob f: d a_bob = sum dsn f while both are live (the scratch is free until the PReLU backward below)
+        if (d_alphas && alpha_residual &&
+            (rc = hrn_launch_alpha_grad(dsn, (const float*)at(tws, L.f[t]), half, pair_last, d_alphas, B, V, hw, sc, L.dec_f - L.scratch, s, dt)))
+            return rc;
         // f = PReLU(convC(t2))
         if ((rc = pre(128, 64, at(tws, L.t2[t]), at(pk, P.fout_w), (const float*)at(pk, P.fout_b), Pr->fuse_out_a, Mh))) return rc;
         if ((rc = hrn_launch_prelu_bwd_bias(x1, (const float*)at(tws, L.f[t]), xpre, Pr->fuse_out_a, x1, (size_t)Mh * hw, 64, mut(Gr->fuse_out_a), mut(Gr->fuse_out_b), sc, s, dt))) return rc;
@@ -325,7 +339,10 @@ int hrn_hrnet_backward_s(const void* pk, int dt, int scale, const hrn_hrnet_para
     if ((rc = hrn_launch_stem_pre(lrs, hw, (const float*)at(tws, L.ref), V, hw, (const float*)at(pk, P.stem_w), (const float*)at(pk, P.stem_b), xpre, M, H, W,
                                   Pr->enc_init_a, s, dt))) return rc;
     if ((rc = hrn_launch_prelu_bwd_bias(dA, (const float*)at(tws, L.a[0]), xpre, Pr->enc_init_a, dA, (size_t)M * hw, 64, mut(Gr->enc_init_a), mut(Gr->enc_init_b), sc, s, dt))) return rc;
-    return hrn_launch_stem_wgrad(lrs, hw, (const float*)at(tws, L.ref), V, hw, dA, M, H, W, mut(Gr->enc_init_w), sc, cus, s, dt);
+    if ((rc = hrn_launch_stem_wgrad(lrs, hw, (const float*)at(tws, L.ref), V, hw, dA, M, H, W, mut(Gr->enc_init_w), sc, cus, s, dt))) return rc;
+    // d lrs: the stem's input gradient, channel 1 (the reference frame) routed to the view the median picked
+    if (d_lrs) return hrn_launch_stem_dgrad_route(dA, Pr->enc_init_w, (float*)at(tws, L.wt), lrs, (const float*)at(tws, L.ref), d_lrs, B, V, H, W, s, dt);
+    return 0;
 }
 
 }  // extern "C"

@@ -151,6 +151,17 @@ int hrn_hrnet_forward_train_s(const void* packed, int dtype, int num_layers, int
 int hrn_hrnet_backward_s(const void* packed, int dtype, int scale, const hrn_hrnet_params* params, int alpha_residual, const float* lrs,
                          const float* alphas, int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* grads,
                          void* train_ws, size_t train_ws_bytes, void* stream);
+/* hrn_hrnet_backward_s that also returns the gradients of the inputs, as torch autograd does through the reference's HRNet
+ * (HRNet.py:198-204 for lrs, :113-132 for alphas).  d_lrs (B,V,H,W) f32: the stem's input gradient; its first channel goes to each
+ * view, its second (the reference frame, `torch.median(lrs[:, :9], 1)`, HRNet.py:200) is summed over the sample's views and added to
+ * ONE view per pixel: the lowest-indexed of the first min(V, 9) views whose value equals the median (where several are tied, torch
+ * leaves the choice open).  d_alphas (B,V) f32: at each fusion level d alphas_bob = sum over channels and pixels of
+ * dLoss/d x_new * fuse(...) (HRNet.py:124-128); 0 for views that are never bob, and 0 everywhere without the alpha residual.
+ * Either pointer may be NULL, which skips that output; input gradients are WRITTEN, parameter gradients still accumulate.
+ * hrn_hrnet_backward_s is the NULL / NULL case.  Same workspace, no more bytes of it. */
+int hrn_hrnet_backward_in(const void* packed, int dtype, int scale, const hrn_hrnet_params* params, int alpha_residual, const float* lrs,
+                          const float* alphas, int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* grads,
+                          float* d_lrs, float* d_alphas, void* train_ws, size_t train_ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ ShiftNet */
 typedef struct hrn_shiftnet_params {
