@@ -12,6 +12,14 @@ Precision (`HRNet.precision`, or key "precision" in the config dict, or env HRNE
     "bf16"            bf16 activations/weights, fp32 accumulation; the throughput path (BASELINE config 3)
     "bf16x3"          split-bf16: every fp32 value as a (hi, lo) pair of bf16, three bf16 MFMAs per product, fp32 accumulation;
                       matches the reference forward to ~1e-5 relative at ~3x the fp32 path's speed
+
+Training precision (`HRNet.train_precision`, or key "train_precision" in the config dict; default None):
+    None              today's rules: the training forward and backward follow `precision` ("fp32" / "bf16x3"); with
+                      precision "bf16" the forward runs the bf16 inference kernels and a backward recomputes it in fp32
+    "fp32" / "bf16" / "bf16x3" (same aliases as `precision`)
+                      the training forward and backward run in that precision; `precision` then governs only the forward
+                      without a graph (.eval(), no_grad).  "bf16": one bf16 plane per activation and gradient, fp32
+                      accumulation; parameters, their gradients and the optimizer state stay fp32
 """
 import os
 
@@ -140,8 +148,8 @@ class HRNet(nn.Module):
         self.decode = Decoder(config["decoder"])
         self._num_layers = config["encoder"]["num_layers"]
         self.precision = config.get("precision", os.environ.get("HRNET_HIP_PRECISION", "fp32"))
-        self._packed = None
-        self._packed_key = None
+        self.train_precision = config.get("train_precision")
+        self._packed = {}                   # dtype -> (key, blob): the inference and the training blob do not evict each other
 
     # -- packed-parameter cache: re-packed whenever a parameter was modified (optimizer step, load_state_dict, .to())
     def _dtype(self):
@@ -150,14 +158,27 @@ class HRNet(nn.Module):
         except KeyError:
             raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}; got {self.precision!r}")
 
+    def _train_dtype(self):
+        """The dtype of the training forward / backward chosen by `train_precision`, or None (then `precision` decides)."""
+        if self.train_precision is None:
+            return None
+        try:
+            return _PRECISIONS[str(self.train_precision).lower()]
+        except KeyError:
+            raise ValueError(f"train_precision must be None or one of {sorted(_PRECISIONS)}; got {self.train_precision!r}")
+
+    def _packed_for(self, dt):
+        named = dict(self.named_parameters())
+        key = (binding.param_epoch,) + tuple((p.data_ptr(), p._version) for p in named.values())
+        hit = self._packed.get(dt)
+        if hit is None or hit[0] != key:
+            hit = (key, binding.hrnet_pack(named, self._num_layers, dt, self._scale))
+            self._packed[dt] = hit
+        return hit[1]
+
     def packed_parameters(self):
         dt = self._dtype()
-        named = dict(self.named_parameters())
-        key = (dt, binding.param_epoch) + tuple((p.data_ptr(), p._version) for p in named.values())
-        if self._packed is None or self._packed_key != key:
-            self._packed = binding.hrnet_pack(named, self._num_layers, dt, self._scale)
-            self._packed_key = key
-        return self._packed, dt
+        return self._packed_for(dt), dt
 
     def forward(self, lrs, alphas):
         if lrs.dim() != 4:
@@ -177,16 +198,20 @@ class HRNet(nn.Module):
             # lrs and alphas go in undetached: autograd asks the backward for their gradients when they require grad (in either mode,
             # frozen parameters included: attribution, learned view weights, input-space optimisation).
             # Otherwise, in .eval() mode (validation, train.py:196-215), the inference kernels run and the result carries no autograd graph.
+            # With train_precision set, it alone picks the training forward / backward (bf16 included: no recompute, no warning).
             names = [k for k, _ in self.named_parameters()]
             params = [p for _, p in self.named_parameters()]
-            if self._dtype() == binding.BF16:
-                return _HRNetLazyTrainFunction.apply(self, names, lrs, alphas, *params)
+            dt = self._train_dtype()
+            if dt is None:
+                if self._dtype() == binding.BF16:
+                    return _HRNetLazyTrainFunction.apply(self, names, lrs, alphas, *params)
+                dt = self._dtype()
             # the dispatcher-registered training op (binding.py): hrn_hrnet_forward_train with hrn_hrnet_backward as its autograd formula
             if names != binding.hrnet_param_names(self._num_layers):
                 raise RuntimeError("HRNet parameters are not in the reference's registration order")
-            # precision "bf16x3" trains in split-bf16 too (conv forward, data and weight gradients on the bf16 matrix cores, ~2^-16 per product)
-            dt = self._dtype()
-            packed = self.packed_parameters()[0] if dt == binding.BF16X3 else self._packed_f32()
+            # "bf16x3" trains in split-bf16 (conv forward, data and weight gradients on the bf16 matrix cores, ~2^-16 per product), "bf16"
+            # in one bf16 plane (one MFMA per product, fp32 accumulation)
+            packed = self._packed_for(dt)
             sr, _tws = torch.ops.hrnet_hip.hrnet_forward_train(packed, lrs.float().contiguous(), alphas.float().contiguous(),
                                                                params, self._num_layers, bool(self.fuse.alpha_residual), dt,
                                                                self._scale)
@@ -196,12 +221,7 @@ class HRNet(nn.Module):
                                                  self._scale)
 
     def _packed_f32(self):
-        named = dict(self.named_parameters())
-        key = (binding.param_epoch,) + tuple((p.data_ptr(), p._version) for p in named.values())
-        if getattr(self, "_packed32", None) is None or self._packed32_key != key:
-            self._packed32 = binding.hrnet_pack(named, self._num_layers, binding.F32, self._scale)
-            self._packed32_key = key
-        return self._packed32
+        return self._packed_for(binding.F32)
 
     # -- staged access for parity tests / profiling (channels-last tensors in the storage dtype)
     def encode_views(self, lrs):

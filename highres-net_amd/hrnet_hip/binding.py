@@ -314,8 +314,9 @@ def hrnet_decoder(packed, dtype, num_layers, fused, scale=3):
 
 
 def hrnet_forward_train(packed_f32, lrs, alphas, num_layers, alpha_residual, dtype=F32, scale=3):
-    """Training forward: returns (sr, train_ws); train_ws holds every intermediate for hrnet_backward.  dtype F32 (exact-fp32 MFMA) or
-    BF16X3 (split-bf16: `packed_f32` is then the BF16X3 blob and the workspace holds pairs of bf16 planes)."""
+    """Training forward: returns (sr, train_ws); train_ws holds every intermediate for hrnet_backward.  dtype F32 (exact-fp32 MFMA),
+    BF16X3 (split-bf16: `packed_f32` is then the BF16X3 blob and the workspace holds pairs of bf16 planes) or BF16 (`packed_f32` the BF16
+    blob, one bf16 plane per activation, fp32 accumulation)."""
     lib = load_library()
     lrs = _dev_f32(lrs, "lrs")
     alphas = _dev_f32(alphas, "alphas")
@@ -693,8 +694,8 @@ SHIFTNET_BUFFER_NAMES = [f"layer{i}.1.{k}" for i in range(1, 9) for k in ("runni
 @torch.library.custom_op("hrnet_hip::hrnet_forward_train", mutates_args=(), device_types="cuda")
 def _op_hrnet_forward_train(packed: torch.Tensor, lrs: torch.Tensor, alphas: torch.Tensor, params: Sequence[torch.Tensor],
                             num_layers: int, alpha_residual: bool, dtype: int, scale: int = 3) -> Tuple[torch.Tensor, torch.Tensor]:
-    """`srs = fusion_model(lrs, alphas)` in training (train.py:174): the forward that keeps every intermediate in `tws`, in fp32 (dtype 0)
-    or split-bf16 (dtype 2).  `packed` is the blob of `params` for that dtype (the raw parameters travel along for the backward pass and
+    """`srs = fusion_model(lrs, alphas)` in training (train.py:174): the forward that keeps every intermediate in `tws`, in fp32 (dtype 0),
+    bf16 (dtype 1) or split-bf16 (dtype 2).  `packed` is the blob of `params` for that dtype (the raw parameters travel along for the backward pass and
     as the differentiable inputs).  `scale`: the upscale factor the blob was packed for; sr is (B, 1, scale H, scale W)."""
     return hrnet_forward_train(packed, lrs, alphas, num_layers, alpha_residual, dtype, scale)
 

@@ -1,9 +1,18 @@
-// Launchers of the backward building blocks (backward.hip).  dt = HRN_F32 (default) or HRN_BF16X3: in the bf16x3 training mode every
-// activation / gradient tensor is a pair of bf16 planes (hi, then lo directly behind it: a tensor of n elements has its lo plane 2 n
-// bytes further on) behind the same `float*` arguments; parameters and their gradients are always f32.  Same conventions as kernels.h: asynchronous on `stream`, no
+// Launchers of the backward building blocks (backward.hip).  dt = HRN_F32 (default), HRN_BF16 or HRN_BF16X3: in the bf16 training mode
+// every activation / gradient tensor is one bf16 plane, in the bf16x3 mode a pair of bf16 planes (hi, then lo directly behind it: a
+// tensor of n elements has its lo plane 2 n bytes further on), behind the same `float*` arguments; parameters and their gradients are
+// always f32.  Same conventions as kernels.h: asynchronous on `stream`, no
 // allocation, no synchronisation; gradients are ACCUMULATED (+=) into their destination, like autograd's .grad.
 #pragma once
 #include "common.h"
+
+// hipLaunchKernelGGL(KERNEL<ST>, ...) for the storage kind ST of dt: HRN_F32, HRN_BF16 or HRN_BF16X3 (common.h, act_ld4)
+#define HRN_LAUNCH_ST(dt, KERNEL, ...)                                                                   \
+    do {                                                                                                 \
+        if ((dt) == HRN_BF16X3) hipLaunchKernelGGL(KERNEL<HRN_BF16X3>, __VA_ARGS__);                     \
+        else if ((dt) == HRN_BF16) hipLaunchKernelGGL(KERNEL<HRN_BF16>, __VA_ARGS__);                    \
+        else hipLaunchKernelGGL(KERNEL<HRN_F32>, __VA_ARGS__);                                           \
+    } while (0)
 
 // bytes of the `scratch` buffer the launchers below share (wgrad partial slabs, reduction partials)
 size_t hrn_bwd_scratch_bytes(int num_cus);
@@ -24,6 +33,9 @@ int hrn_launch_conv_wgrad(const float* x, const float* stack, int in_pair, int p
 // the same in the bf16x3 training mode (wgrad_x3.hip): x / stack and g are pairs of bf16 planes, x_lo / g_lo the byte offsets of their lo planes
 int hrn_launch_conv_wgrad_x3(const void* x, const void* stack, size_t x_lo, int in_pair, int pair_h, int pair_last, int pair_vs, const void* g,
                              size_t g_lo, int M, int H, int W, int cin, int cout, float* dw, void* scratch, int num_cus, hipStream_t s);
+// the same in the bf16 training mode (wgrad_x3.hip): x / stack and g are one bf16 plane each, one MFMA per product, fp32 accumulation
+int hrn_launch_conv_wgrad_bf16(const void* x, const void* stack, int in_pair, int pair_h, int pair_last, int pair_vs, const void* g, int M,
+                               int H, int W, int cin, int cout, float* dw, void* scratch, int num_cus, hipStream_t s);
 // dW[co][ci][tap] += sum over workgroups of the partial slabs [nblk][9][64][64] of one (cout chunk, cin chunk) pair, fixed order
 int hrn_launch_wgrad_finish(const float* partial, int nblk, float* dw, int cin, int co_chunk, int ci_chunk, hipStream_t s);
 // stem 2 -> 64: in0 = image m (stride0 floats apart), in1 = plane m / rep1; dw [64][2][3][3]

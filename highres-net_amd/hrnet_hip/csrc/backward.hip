@@ -44,23 +44,23 @@ __global__ __launch_bounds__(256) void scalar_finish_kernel(const double* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ column sums (bias grads)
-template <int C, bool X3>
+template <int C, int ST>
 __global__ __launch_bounds__(256) void colsum_kernel(const void* __restrict__ g, size_t rows, double* __restrict__ partial) {
     // thread -> 4 channels c4*4.., row phase tid / (C/4); 16-byte loads, four rows in flight per thread; fixed order
     constexpr int C4 = C / 4, RP = 256 / C4;
     const int c4 = threadIdx.x % C4, rp = threadIdx.x / C4;
-    const size_t lo = rows * C * 2;                             // (X3: the lo plane of the [rows][C] tensor)
+    const size_t lo = rows * C * 2;                             // (bf16x3: the lo plane of the [rows][C] tensor)
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     const size_t stride = (size_t)gridDim.x * RP;
     size_t r = (size_t)blockIdx.x * RP + rp;
     for (; r + 3 * stride < rows; r += 4 * stride) {
-        const f32x4 v0 = act_ld4<X3>(g, lo, r * C4 + c4), v1 = act_ld4<X3>(g, lo, (r + stride) * C4 + c4);
-        const f32x4 v2 = act_ld4<X3>(g, lo, (r + 2 * stride) * C4 + c4), v3 = act_ld4<X3>(g, lo, (r + 3 * stride) * C4 + c4);
+        const f32x4 v0 = act_ld4<ST>(g, lo, r * C4 + c4), v1 = act_ld4<ST>(g, lo, (r + stride) * C4 + c4);
+        const f32x4 v2 = act_ld4<ST>(g, lo, (r + 2 * stride) * C4 + c4), v3 = act_ld4<ST>(g, lo, (r + 3 * stride) * C4 + c4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] += ((double)v0[j] + (double)v1[j]) + ((double)v2[j] + (double)v3[j]);
     }
     for (; r < rows; r += stride) {
-        const f32x4 v = act_ld4<X3>(g, lo, r * C4 + c4);
+        const f32x4 v = act_ld4<ST>(g, lo, r * C4 + c4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] += (double)v[j];
     }
@@ -82,14 +82,14 @@ __global__ __launch_bounds__(256) void colsum_kernel(const void* __restrict__ g,
 // order of colsum_kernel (fixed: bit-reproducible); g may alias dy.  With a positive slope the sign of x is the sign of the stored
 // post-activation y and x = y / slope where it is negative; otherwise (decided here, on the device: no host round trip) the
 // pre-activation itself is read from xpre, which the caller has recomputed under the same condition.
-template <int C, bool X3>
+template <int C, int ST>
 __global__ __launch_bounds__(256) void prelu_bwd_bias_kernel(const void* __restrict__ dy, const void* __restrict__ y,
                                                              const void* __restrict__ xpre, const float* __restrict__ slope,
                                                              void* __restrict__ g, size_t rows, double* __restrict__ colpart,
                                                              double* __restrict__ slopepart) {
     constexpr int C4 = C / 4, RP = 256 / C4;
     const int c4 = threadIdx.x % C4, rp = threadIdx.x / C4;
-    const size_t lo = rows * C * 2;                             // (X3: the lo plane of each [rows][C] tensor)
+    const size_t lo = rows * C * 2;                             // (bf16x3: the lo plane of each [rows][C] tensor)
     const float a = slope[0];
     const bool from_y = a > 0.f;
     const void* __restrict__ src = from_y ? y : xpre;
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void prelu_bwd_bias_kernel(const void* __restr
     const size_t stride = (size_t)gridDim.x * RP;
     auto one = [&](size_t r) __attribute__((always_inline)) {
         const size_t o4 = r * C4 + c4;
-        const f32x4 d = act_ld4<X3>(dy, lo, o4), v = act_ld4<X3>(src, lo, o4);
+        const f32x4 d = act_ld4<ST>(dy, lo, o4), v = act_ld4<ST>(src, lo, o4);
         f32x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -107,8 +107,8 @@ __global__ __launch_bounds__(256) void prelu_bwd_bias_kernel(const void* __restr
             acc[j] += (double)o[j];
             if (!pos) sacc += (double)d[j] * ((double)v[j] * (double)inv_a);      // signed terms that largely cancel: fp64
         }
-        if constexpr (X3) act_st4<true>(g, lo, o4, o);
-        else *((f32x4*)g + o4) = o;
+        if constexpr (ST == HRN_F32) *((f32x4*)g + o4) = o;
+        else act_st4<ST>(g, lo, o4, o);
     };
     size_t r = (size_t)blockIdx.x * RP + rp;
     for (; r + stride < rows; r += 2 * stride) { one(r); one(r + stride); }
@@ -348,7 +348,7 @@ __global__ __launch_bounds__(1024) void wgrad_finish_kernel(const float* __restr
 
 // ------------------------------------------------------------------------------------------------ stem weight gradient
 // dW[co][c2][tap] += sum g[m][p][co] * in_c2[m][p + tap], in_0 = view m, in_1 = reference frame of sample m / rep1
-template <bool X3>
+template <int ST>
 __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict__ in0, size_t stride0, const float* __restrict__ in1,
                                                          int rep1, size_t stride1, const float* __restrict__ sub,
                                                          const void* __restrict__ g, int M, int H, int W, float* __restrict__ partial) {
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int pix = q + 4 * (p8 + u), gy = y0 + (pix >> 5), gx = x0 + (pix & 31);
-                gv[u] = (gy < H && gx < W) ? act_ld1<X3>(g, glo, gb + ((size_t)gy * W + gx) * 64) : 0.f;
+                gv[u] = (gy < H && gx < W) ? act_ld1<ST>(g, glo, gb + ((size_t)gy * W + gx) * 64) : 0.f;
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -423,15 +423,15 @@ __global__ __launch_bounds__(1024) void stem_wgrad_finish_kernel(const float* __
 }
 
 // ------------------------------------------------------------------------------------------------ elementwise helpers
-template <bool X3>
+template <int ST>
 __global__ __launch_bounds__(256) void add_kernel(const void* __restrict__ a, const void* __restrict__ b, void* __restrict__ o, size_t n4) {
     const size_t lo = n4 * 8;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256)
-        act_st4<X3>(o, lo, i, act_ld4<X3>(a, lo, i) + act_ld4<X3>(b, lo, i));
+        act_st4<ST>(o, lo, i, act_ld4<ST>(a, lo, i) + act_ld4<ST>(b, lo, i));
 }
 
 // fusion level, forward: s'[b][i] = s[b][i] + alpha[b][partner(i)] * f[b][i]   (or s' = f without the alpha residual)
-template <bool X3>
+template <int ST>
 __global__ __launch_bounds__(256) void fuse_update_kernel(const void* __restrict__ stack, int n_in, const void* __restrict__ f,
                                                           const float* __restrict__ alphas, int alpha_vs, int pair_last, int half,
                                                           int alpha_residual, void* __restrict__ out, size_t img4, int B) {
@@ -440,17 +440,17 @@ __global__ __launch_bounds__(256) void fuse_update_kernel(const void* __restrict
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const size_t img = i / img4, e = i - img * img4;
         const int b = (int)(img / half), v = (int)(img - (size_t)b * half);
-        const f32x4 fv = act_ld4<X3>(f, lo_f, i);
+        const f32x4 fv = act_ld4<ST>(f, lo_f, i);
         if (alpha_residual) {
             const float al = alphas[(size_t)b * alpha_vs + (pair_last - v)];
-            act_st4<X3>(out, lo_f, i, act_ld4<X3>(stack, lo_s, ((size_t)b * n_in + v) * img4 + e) + al * fv);
+            act_st4<ST>(out, lo_f, i, act_ld4<ST>(stack, lo_s, ((size_t)b * n_in + v) * img4 + e) + al * fv);
         } else {
-            act_st4<X3>(out, lo_f, i, fv);
+            act_st4<ST>(out, lo_f, i, fv);
         }
     }
 }
 // fusion level, backward: df[b][i] = alpha_partner * ds'[b][i]  (or ds')
-template <bool X3>
+template <int ST>
 __global__ __launch_bounds__(256) void fuse_df_kernel(const void* __restrict__ dsn, const float* __restrict__ alphas, int alpha_vs,
                                                       int pair_last, int half, int alpha_residual, void* __restrict__ df, size_t img4,
                                                       int B) {
@@ -459,12 +459,12 @@ __global__ __launch_bounds__(256) void fuse_df_kernel(const void* __restrict__ d
         const size_t img = i / img4;
         const int b = (int)(img / half), v = (int)(img - (size_t)b * half);
         const float al = alpha_residual ? alphas[(size_t)b * alpha_vs + (pair_last - v)] : 1.f;
-        act_st4<X3>(df, lo, i, al * act_ld4<X3>(dsn, lo, i));
+        act_st4<ST>(df, lo, i, al * act_ld4<ST>(dsn, lo, i));
     }
 }
 // fusion level, backward: gradient of the level's input views from ds' (alice pass-through, alpha residual only) and
 // dz [B*half][HW][128] (channels 0..63 -> view i, 64..127 -> view pair_last - i); views that took no part get zero
-template <bool X3>
+template <int ST>
 __global__ __launch_bounds__(256) void fuse_scatter_kernel(const void* __restrict__ dsn, const void* __restrict__ dz, int n_in, int half,
                                                            int pair_last, int alpha_residual, void* __restrict__ ds, size_t hw, int B) {
     const size_t img4 = hw * 16;                                // float4 per 64-channel image
@@ -476,12 +476,12 @@ __global__ __launch_bounds__(256) void fuse_scatter_kernel(const void* __restric
         const size_t pix = e >> 4, part = e & 15;
         f32x4 o = {0.f, 0.f, 0.f, 0.f};
         if (v < half) {
-            if (alpha_residual) o = act_ld4<X3>(dsn, lo_n, ((size_t)b * half + v) * img4 + e);
-            o += act_ld4<X3>(dz, lo_z, (((size_t)b * half + v) * hw + pix) * 32 + part);
+            if (alpha_residual) o = act_ld4<ST>(dsn, lo_n, ((size_t)b * half + v) * img4 + e);
+            o += act_ld4<ST>(dz, lo_z, (((size_t)b * half + v) * hw + pix) * 32 + part);
         } else if (v <= pair_last && pair_last - v < half) {
-            o = act_ld4<X3>(dz, lo_z, (((size_t)b * half + (pair_last - v)) * hw + pix) * 32 + 16 + part);
+            o = act_ld4<ST>(dz, lo_z, (((size_t)b * half + (pair_last - v)) * hw + pix) * 32 + 16 + part);
         }
-        act_st4<X3>(ds, lo_s, i, o);
+        act_st4<ST>(ds, lo_s, i, o);
     }
 }
 
@@ -503,10 +503,9 @@ int hrn_launch_prelu_bwd_bias(const float* dy, const float* y, const float* xpre
     double* colpart = (double*)scratch;
     const int blocks = RED_BLOCKS;
     double* slopepart = colpart + (size_t)blocks * 128;
-    const bool x3 = dt == HRN_BF16X3;
-#define HRN_PB(C_, X_) hipLaunchKernelGGL((prelu_bwd_bias_kernel<C_, X_>), dim3(blocks), dim3(256), 0, s, (const void*)dy, (const void*)y, (const void*)xpre, slope, (void*)g, rows, colpart, slopepart)
-    if (C == 64) { if (x3) HRN_PB(64, true); else HRN_PB(64, false); }
-    else { if (x3) HRN_PB(128, true); else HRN_PB(128, false); }
+#define HRN_PB(C_, ST_) hipLaunchKernelGGL((prelu_bwd_bias_kernel<C_, ST_>), dim3(blocks), dim3(256), 0, s, (const void*)dy, (const void*)y, (const void*)xpre, slope, (void*)g, rows, colpart, slopepart)
+    if (C == 64) { if (dt == HRN_BF16X3) HRN_PB(64, HRN_BF16X3); else if (dt == HRN_BF16) HRN_PB(64, HRN_BF16); else HRN_PB(64, HRN_F32); }
+    else { if (dt == HRN_BF16X3) HRN_PB(128, HRN_BF16X3); else if (dt == HRN_BF16) HRN_PB(128, HRN_BF16); else HRN_PB(128, HRN_F32); }
 #undef HRN_PB
     hipLaunchKernelGGL(colsum_finish_kernel, dim3(C / 32), dim3(1024), 0, s, colpart, blocks, C, db);
     hipLaunchKernelGGL(scalar_finish_kernel, dim3(1), dim3(256), 0, s, slopepart, blocks, dslope);
@@ -518,10 +517,9 @@ int hrn_launch_colsum(const float* g, size_t rows, int C, float* db, void* scrat
     HRN_CHECK(C == 64 || C == 128, -2, "colsum: C must be 64 or 128 (got %d)", C);
     double* partial = (double*)scratch;
     const int blocks = RED_BLOCKS;
-    const bool x3 = dt == HRN_BF16X3;
-#define HRN_CS(C_, X_) hipLaunchKernelGGL((colsum_kernel<C_, X_>), dim3(blocks), dim3(256), 0, s, (const void*)g, rows, partial)
-    if (C == 64) { if (x3) HRN_CS(64, true); else HRN_CS(64, false); }
-    else { if (x3) HRN_CS(128, true); else HRN_CS(128, false); }
+#define HRN_CS(C_, ST_) hipLaunchKernelGGL((colsum_kernel<C_, ST_>), dim3(blocks), dim3(256), 0, s, (const void*)g, rows, partial)
+    if (C == 64) { if (dt == HRN_BF16X3) HRN_CS(64, HRN_BF16X3); else if (dt == HRN_BF16) HRN_CS(64, HRN_BF16); else HRN_CS(64, HRN_F32); }
+    else { if (dt == HRN_BF16X3) HRN_CS(128, HRN_BF16X3); else if (dt == HRN_BF16) HRN_CS(128, HRN_BF16); else HRN_CS(128, HRN_F32); }
 #undef HRN_CS
     hipLaunchKernelGGL(colsum_finish_kernel, dim3(C / 32), dim3(1024), 0, s, partial, blocks, C, db);
     HRN_LAUNCH_CHECK();
@@ -573,8 +571,7 @@ int hrn_launch_stem_wgrad_sub(const float* in0, size_t stride0, const float* in1
     const long tiles = (long)((W + WG_TW - 1) / WG_TW) * ((H + WG_TH - 1) / WG_TH) * M;
     int grid = 4 * num_cus;                 // four workgroups per CU: the kernel waits on memory, not on arithmetic
     if (tiles < grid) grid = (int)tiles;
-    if (dt == HRN_BF16X3) hipLaunchKernelGGL(stem_wgrad_kernel<true>, dim3(grid), dim3(256), 0, s, in0, stride0, in1, rep1, stride1, sub, (const void*)g, M, H, W, (float*)scratch);
-    else hipLaunchKernelGGL(stem_wgrad_kernel<false>, dim3(grid), dim3(256), 0, s, in0, stride0, in1, rep1, stride1, sub, (const void*)g, M, H, W, (float*)scratch);
+    HRN_LAUNCH_ST(dt, stem_wgrad_kernel, dim3(grid), dim3(256), 0, s, in0, stride0, in1, rep1, stride1, sub, (const void*)g, M, H, W, (float*)scratch);
     hipLaunchKernelGGL(stem_wgrad_finish_kernel, dim3(64 * 18 / 16), dim3(1024), 0, s, (const float*)scratch, grid * 4, dw);
     HRN_LAUNCH_CHECK();
     return 0;
@@ -582,8 +579,7 @@ int hrn_launch_stem_wgrad_sub(const float* in0, size_t stride0, const float* in1
 
 int hrn_launch_add(const float* a, const float* b, float* o, size_t n, hipStream_t s, int dt) {
     HRN_CHECK(n % 4 == 0, -2, "add: element count %zu not a multiple of 4", n);
-    if (dt == HRN_BF16X3) hipLaunchKernelGGL(add_kernel<true>, dim3(red_grid(n / 4)), dim3(256), 0, s, (const void*)a, (const void*)b, (void*)o, n / 4);
-    else hipLaunchKernelGGL(add_kernel<false>, dim3(red_grid(n / 4)), dim3(256), 0, s, (const void*)a, (const void*)b, (void*)o, n / 4);
+    HRN_LAUNCH_ST(dt, add_kernel, dim3(red_grid(n / 4)), dim3(256), 0, s, (const void*)a, (const void*)b, (void*)o, n / 4);
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -591,10 +587,8 @@ int hrn_launch_add(const float* a, const float* b, float* o, size_t n, hipStream
 int hrn_launch_fuse_update(const float* stack, int n_in, const float* f, const float* alphas, int alpha_vs, int pair_last, int half,
                            int alpha_residual, float* out, size_t hw, int B, hipStream_t s, int dt) {
     const size_t img4 = hw * 16;
-    if (dt == HRN_BF16X3) hipLaunchKernelGGL(fuse_update_kernel<true>, dim3(red_grid((size_t)B * half * img4)), dim3(256), 0, s, (const void*)stack, n_in, (const void*)f, alphas, alpha_vs,
-                                             pair_last, half, alpha_residual, (void*)out, img4, B);
-    else hipLaunchKernelGGL(fuse_update_kernel<false>, dim3(red_grid((size_t)B * half * img4)), dim3(256), 0, s, (const void*)stack, n_in, (const void*)f, alphas, alpha_vs,
-                            pair_last, half, alpha_residual, (void*)out, img4, B);
+    HRN_LAUNCH_ST(dt, fuse_update_kernel, dim3(red_grid((size_t)B * half * img4)), dim3(256), 0, s, (const void*)stack, n_in, (const void*)f, alphas, alpha_vs,
+                  pair_last, half, alpha_residual, (void*)out, img4, B);
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -602,20 +596,16 @@ int hrn_launch_fuse_update(const float* stack, int n_in, const float* f, const f
 int hrn_launch_fuse_df(const float* dsn, const float* alphas, int alpha_vs, int pair_last, int half, int alpha_residual, float* df,
                        size_t hw, int B, hipStream_t s, int dt) {
     const size_t img4 = hw * 16;
-    if (dt == HRN_BF16X3) hipLaunchKernelGGL(fuse_df_kernel<true>, dim3(red_grid((size_t)B * half * img4)), dim3(256), 0, s, (const void*)dsn, alphas, alpha_vs, pair_last, half,
-                                             alpha_residual, (void*)df, img4, B);
-    else hipLaunchKernelGGL(fuse_df_kernel<false>, dim3(red_grid((size_t)B * half * img4)), dim3(256), 0, s, (const void*)dsn, alphas, alpha_vs, pair_last, half,
-                            alpha_residual, (void*)df, img4, B);
+    HRN_LAUNCH_ST(dt, fuse_df_kernel, dim3(red_grid((size_t)B * half * img4)), dim3(256), 0, s, (const void*)dsn, alphas, alpha_vs, pair_last, half,
+                  alpha_residual, (void*)df, img4, B);
     HRN_LAUNCH_CHECK();
     return 0;
 }
 
 int hrn_launch_fuse_scatter(const float* dsn, const float* dz, int n_in, int half, int pair_last, int alpha_residual, float* ds,
                             size_t hw, int B, hipStream_t s, int dt) {
-    if (dt == HRN_BF16X3) hipLaunchKernelGGL(fuse_scatter_kernel<true>, dim3(red_grid((size_t)B * n_in * hw * 16)), dim3(256), 0, s, (const void*)dsn, (const void*)dz, n_in, half, pair_last,
-                                             alpha_residual, (void*)ds, hw, B);
-    else hipLaunchKernelGGL(fuse_scatter_kernel<false>, dim3(red_grid((size_t)B * n_in * hw * 16)), dim3(256), 0, s, (const void*)dsn, (const void*)dz, n_in, half, pair_last,
-                            alpha_residual, (void*)ds, hw, B);
+    HRN_LAUNCH_ST(dt, fuse_scatter_kernel, dim3(red_grid((size_t)B * n_in * hw * 16)), dim3(256), 0, s, (const void*)dsn, (const void*)dz, n_in, half, pair_last,
+                  alpha_residual, (void*)ds, hw, B);
     HRN_LAUNCH_CHECK();
     return 0;
 }

@@ -119,10 +119,12 @@ template <> __device__ __forceinline__ void store4<HRN_BF16>(void* p, size_t i, 
 }
 
 // ------------------------------------------------------------------ activation tensors of the training path
-// f32, or (X3 = the bf16x3 mode) a PAIR of bf16 planes: hi at p, lo `lo` bytes further on; a tensor of n elements has lo = 2 n (the lo
-// plane directly behind the hi plane), which is how every kernel derives it from the tensor's shape.  Unit: 4 consecutive elements.
-template <bool X3> __device__ __forceinline__ f32x4 act_ld4(const void* p, size_t lo, size_t i4) {
-    if constexpr (X3) {
+// Storage kind ST of a training activation / gradient tensor: HRN_F32; HRN_BF16, one bf16 plane (stores round to nearest even); or
+// HRN_BF16X3, a PAIR of bf16 planes: hi at p, lo `lo` bytes further on.  A bf16x3 tensor of n elements has lo = 2 n (the lo plane
+// directly behind the hi plane), which is how every kernel derives it from the tensor's shape; the other kinds ignore `lo`.
+// Unit: 4 consecutive elements.
+template <int ST> __device__ __forceinline__ f32x4 act_ld4(const void* p, size_t lo, size_t i4) {
+    if constexpr (ST == HRN_BF16X3) {
         const u32x2 h = __builtin_nontemporal_load((const u32x2*)p + i4);
         const u32x2 l = __builtin_nontemporal_load((const u32x2*)((const unsigned char*)p + lo) + i4);
         f32x4 r;
@@ -131,25 +133,35 @@ template <bool X3> __device__ __forceinline__ f32x4 act_ld4(const void* p, size_
         r[2] = __uint_as_float(h[1] << 16) + __uint_as_float(l[1] << 16);
         r[3] = __uint_as_float(h[1] & 0xffff0000u) + __uint_as_float(l[1] & 0xffff0000u);
         return r;
+    } else if constexpr (ST == HRN_BF16) {
+        const u32x2 h = __builtin_nontemporal_load((const u32x2*)p + i4);
+        return f32x4{__uint_as_float(h[0] << 16), __uint_as_float(h[0] & 0xffff0000u), __uint_as_float(h[1] << 16),
+                     __uint_as_float(h[1] & 0xffff0000u)};
     } else {
+        static_assert(ST == HRN_F32, "storage kind");
         return __builtin_nontemporal_load((const f32x4*)p + i4);
     }
 }
-template <bool X3> __device__ __forceinline__ void act_st4(void* p, size_t lo, size_t i4, f32x4 v) {
-    if constexpr (X3) {
+template <int ST> __device__ __forceinline__ void act_st4(void* p, size_t lo, size_t i4, f32x4 v) {
+    if constexpr (ST == HRN_BF16X3) {
         unsigned h0, l0, h1, l1;
         split2_bf16(v[0], v[1], h0, l0);
         split2_bf16(v[2], v[3], h1, l1);
         const u32x2 h = {h0, h1}, l = {l0, l1};
         __builtin_nontemporal_store(h, (u32x2*)p + i4);
         __builtin_nontemporal_store(l, (u32x2*)((unsigned char*)p + lo) + i4);
+    } else if constexpr (ST == HRN_BF16) {
+        const u32x2 h = {pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3])};
+        __builtin_nontemporal_store(h, (u32x2*)p + i4);
     } else {
+        static_assert(ST == HRN_F32, "storage kind");
         __builtin_nontemporal_store(v, (f32x4*)p + i4);
     }
 }
 // one element
-template <bool X3> __device__ __forceinline__ float act_ld1(const void* p, size_t lo, size_t i) {
-    if constexpr (X3) return bf16_bits_to_f32(((const unsigned short*)p)[i]) + bf16_bits_to_f32(((const unsigned short*)((const unsigned char*)p + lo))[i]);
+template <int ST> __device__ __forceinline__ float act_ld1(const void* p, size_t lo, size_t i) {
+    if constexpr (ST == HRN_BF16X3) return bf16_bits_to_f32(((const unsigned short*)p)[i]) + bf16_bits_to_f32(((const unsigned short*)((const unsigned char*)p + lo))[i]);
+    else if constexpr (ST == HRN_BF16) return bf16_bits_to_f32(((const unsigned short*)p)[i]);
     else return ((const float*)p)[i];
 }
 

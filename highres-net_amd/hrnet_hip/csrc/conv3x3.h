@@ -27,7 +27,7 @@ struct ConvParams {
     // HRN_BF16X3 only: every activation tensor is a PAIR of bf16 planes (hi, lo) in the bf16 layout; byte offset of the lo plane from
     // the hi plane of `in` / `stack` / `out` / `res` (0 otherwise)
     size_t in_lo, stack_lo, out_lo, res_lo;
-    const float* only_if_nonpos;      // f32 kernel only: when set, the launch does nothing unless only_if_nonpos[0] <= 0 (the backward's
+    const float* only_if_nonpos;      // when set, the launch does nothing unless only_if_nonpos[0] <= 0 (the training backward's
                                       // recomputation of a pre-activation, needed only behind a PReLU whose slope is not positive)
 };
 
@@ -41,8 +41,9 @@ int hrn_launch_conv3x3(int dt, int cin, int cout, const ConvParams& p, hipStream
 int hrn_launch_conv3x3_r64(const ConvParams& p, hipStream_t stream);
 
 // bf16 128 -> {128, 64}: the three layers of a fusion level; descriptor-based halo DMA issued from the MFMA gaps, epilogue straight
-// from the accumulators in whole pixel rows (conv3x3_v6.hip); -100 = not applicable.
-int hrn_launch_conv3x3_v6(int cout, const ConvParams& p, hipStream_t stream);
+// from the accumulators in whole pixel rows (conv3x3_v6.hip).  Also the two data gradients of the bf16 training path the other
+// kernels do not cover: 128 -> 128 + plain residual and 64 -> 128.  -100 = not applicable.
+int hrn_launch_conv3x3_v6(int cin, int cout, const ConvParams& p, hipStream_t stream);
 
 // bf16x3 (split-bf16: hi/lo planes, three MFMAs per product) on the conv3x3_v6 skeleton: (cin, cout) = (64, 64) with res_mode 0 | 1,
 // (128, 128) with 0 | 2 (+ pair-gather input), (128, 64) with 0 | 3 (conv3x3_v6x3.hip).  No other kernel implements this dtype.

@@ -57,6 +57,7 @@ __device__ __attribute__((aligned(16))) unsigned hrn_r64_zero16[4];
 
 template <bool RES>
 __global__ __launch_bounds__(512, 2) void conv3x3_r64_kernel(const ConvParams p) {
+    if (p.only_if_nonpos && p.only_if_nonpos[0] > 0.f) return;      // uniform, before any barrier (ConvParams::only_if_nonpos)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* w_lds = smem;
     float* bias_lds = (float*)(smem + W_BYTES + 2 * IN_BYTES);

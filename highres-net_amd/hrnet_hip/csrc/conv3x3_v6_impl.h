@@ -106,9 +106,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_v6_kernel(const ConvParams p) 
     constexpr int BAL = COUT == 128 ? V6_BAL : 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* bias_lds = (float*)(smem + GEO::OFF_BIAS);
-    if constexpr (X3) {     // (ConvParams::only_if_nonpos: the backward's recomputation of a pre-activation, needed only behind a PReLU slope <= 0)
-        if (p.only_if_nonpos && p.only_if_nonpos[0] > 0.f) return;
-    }
+    // (ConvParams::only_if_nonpos: the backward's recomputation of a pre-activation, needed only behind a PReLU slope <= 0)
+    if (p.only_if_nonpos && p.only_if_nonpos[0] > 0.f) return;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;

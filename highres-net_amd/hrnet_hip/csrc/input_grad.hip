@@ -17,25 +17,31 @@ namespace {
 // (pixel stride 36 floats: ds_read_b128 of 16 consecutive pixels hits 16 distinct 4-bank groups)
 constexpr int SD_TH = 8, SD_TW = 32, SD_HH = SD_TH + 2, SD_HW = SD_TW + 2, SD_CC = 32, SD_PS = SD_CC + 4;
 
-// 4 consecutive elements of an activation tensor as loaded (f32: the four floats' bits; bf16x3: hi pair then lo pair), converted to f32
-// only when they are stored to LDS, so that the loads stay in flight across the computation
-template <bool X3> __device__ __forceinline__ u32x4 ld_raw(const void* p, size_t lo, size_t i4) {
-    if constexpr (X3) {
+// 4 consecutive elements of an activation tensor as loaded (f32: the four floats' bits; bf16: one pair; bf16x3: hi pair then lo pair),
+// converted to f32 only when they are stored to LDS, so that the loads stay in flight across the computation
+template <int ST> __device__ __forceinline__ u32x4 ld_raw(const void* p, size_t lo, size_t i4) {
+    if constexpr (ST == HRN_BF16X3) {
         const u32x2 h = __builtin_nontemporal_load((const u32x2*)p + i4);
         const u32x2 l = __builtin_nontemporal_load((const u32x2*)((const unsigned char*)p + lo) + i4);
         return u32x4{h[0], h[1], l[0], l[1]};
+    } else if constexpr (ST == HRN_BF16) {
+        const u32x2 h = __builtin_nontemporal_load((const u32x2*)p + i4);
+        return u32x4{h[0], h[1], 0u, 0u};
     } else {
         return __builtin_nontemporal_load((const u32x4*)p + i4);
     }
 }
-template <bool X3> __device__ __forceinline__ f32x4 raw_to_f32(u32x4 r) {
-    if constexpr (X3) {
+template <int ST> __device__ __forceinline__ f32x4 raw_to_f32(u32x4 r) {
+    if constexpr (ST == HRN_BF16X3) {
         f32x4 o;
         o[0] = __uint_as_float(r[0] << 16) + __uint_as_float(r[2] << 16);
         o[1] = __uint_as_float(r[0] & 0xffff0000u) + __uint_as_float(r[2] & 0xffff0000u);
         o[2] = __uint_as_float(r[1] << 16) + __uint_as_float(r[3] << 16);
         o[3] = __uint_as_float(r[1] & 0xffff0000u) + __uint_as_float(r[3] & 0xffff0000u);
         return o;
+    } else if constexpr (ST == HRN_BF16) {
+        return f32x4{__uint_as_float(r[0] << 16), __uint_as_float(r[0] & 0xffff0000u), __uint_as_float(r[1] << 16),
+                     __uint_as_float(r[1] & 0xffff0000u)};
     } else {
         return f32x4{__uint_as_float(r[0]), __uint_as_float(r[1]), __uint_as_float(r[2]), __uint_as_float(r[3])};
     }
@@ -49,7 +55,7 @@ __global__ __launch_bounds__(256) void stem_dgrad_weights_kernel(const float* __
     wt[(tap * 64 + co) * 2 + c] = w[i];
 }
 
-template <bool X3>
+template <int ST>
 __global__ __launch_bounds__(256) void stem_dgrad_route_kernel(const void* __restrict__ dA, const float* __restrict__ wt,
                                                                const float* __restrict__ lrs, const float* __restrict__ ref,
                                                                float* __restrict__ d_lrs, int B, int V, int H, int W) {
@@ -91,7 +97,7 @@ __global__ __launch_bounds__(256) void stem_dgrad_route_kernel(const void* __res
             ok |= (unsigned)in << u;
             // unconditional load from a clamped address (no branch: the loads of all units stay in flight together)
             const int cy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy), cx = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
-            raw[u] = ld_raw<X3>(dA, lo, (img * hw + (size_t)cy * W + cx) * 16 + k * (SD_CC / 4) + q);
+            raw[u] = ld_raw<ST>(dA, lo, (img * hw + (size_t)cy * W + cx) * 16 + k * (SD_CC / 4) + q);
         }
     };
     float acc1 = 0.f, keep = 0.f, o0 = 0.f, o1 = 0.f;
@@ -104,7 +110,7 @@ __global__ __launch_bounds__(256) void stem_dgrad_route_kernel(const void* __res
             const int i = tid + u * 256;
             const int hp = i / (SD_CC / 4), q = i - hp * (SD_CC / 4);
             const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            if (i < NU) *(f32x4*)&tile[hp * SD_PS + q * 4] = (ok >> u) & 1 ? raw_to_f32<X3>(raw[u]) : z;
+            if (i < NU) *(f32x4*)&tile[hp * SD_PS + q * 4] = (ok >> u) & 1 ? raw_to_f32<ST>(raw[u]) : z;
         }
         __syncthreads();
         if (c + 1 < 2 * V) fetch(c + 1);
@@ -140,7 +146,7 @@ __global__ __launch_bounds__(256) void stem_dgrad_route_kernel(const void* __res
 }
 
 // partial[img * P + part] = sum over part `part` of image img of dsn * f (fp32 per thread, double across the block, fixed tree)
-template <bool X3>
+template <int ST>
 __global__ __launch_bounds__(256) void alpha_grad_partial_kernel(const void* __restrict__ dsn, const void* __restrict__ f, size_t img4,
                                                                  int nimg, int P, double* __restrict__ partial) {
     __shared__ double red[4];
@@ -150,7 +156,7 @@ __global__ __launch_bounds__(256) void alpha_grad_partial_kernel(const void* __r
     float s = 0.f;
     for (size_t e = beg + threadIdx.x; e < end; e += 256) {
         const size_t i4 = (size_t)img * img4 + e;
-        const f32x4 a = act_ld4<X3>(dsn, lo, i4), c = act_ld4<X3>(f, lo, i4);
+        const f32x4 a = act_ld4<ST>(dsn, lo, i4), c = act_ld4<ST>(f, lo, i4);
         s = fmaf(a[0], c[0], s); s = fmaf(a[1], c[1], s); s = fmaf(a[2], c[2], s); s = fmaf(a[3], c[3], s);
     }
     double d = s;
@@ -188,8 +194,7 @@ int hrn_launch_stem_dgrad_route(const float* dA, const float* w, float* wt, cons
     const double px = (double)B * V * H * W;
     HrnProfScope prof("stem_dgrad_route", 2.0 * 18 * 64 * px, px * (64.0 * 4 + 4) + (double)B * H * W * 4 * ((V < 9 ? V : 9) + 1), s);
     hipLaunchKernelGGL(stem_dgrad_weights_kernel, dim3((64 * 18 + 255) / 256), dim3(256), 0, s, w, wt);
-    if (dt == HRN_BF16X3) hipLaunchKernelGGL(stem_dgrad_route_kernel<true>, dim3((unsigned)(tiles * B)), dim3(256), 0, s, (const void*)dA, (const float*)wt, lrs, ref, d_lrs, B, V, H, W);
-    else hipLaunchKernelGGL(stem_dgrad_route_kernel<false>, dim3((unsigned)(tiles * B)), dim3(256), 0, s, (const void*)dA, (const float*)wt, lrs, ref, d_lrs, B, V, H, W);
+    HRN_LAUNCH_ST(dt, stem_dgrad_route_kernel, dim3((unsigned)(tiles * B)), dim3(256), 0, s, (const void*)dA, (const float*)wt, lrs, ref, d_lrs, B, V, H, W);
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -201,8 +206,7 @@ int hrn_launch_alpha_grad(const float* dsn, const float* f, int half, int pair_l
     HrnProfScope prof("alpha_grad", 2.0 * nimg * hw * 64, 2.0 * nimg * hw * 64 * 4, s);
     double* partial = (double*)scratch;
     const size_t img4 = hw * 16;
-    if (dt == HRN_BF16X3) hipLaunchKernelGGL(alpha_grad_partial_kernel<true>, dim3(nimg * P), dim3(256), 0, s, (const void*)dsn, (const void*)f, img4, nimg, P, partial);
-    else hipLaunchKernelGGL(alpha_grad_partial_kernel<false>, dim3(nimg * P), dim3(256), 0, s, (const void*)dsn, (const void*)f, img4, nimg, P, partial);
+    HRN_LAUNCH_ST(dt, alpha_grad_partial_kernel, dim3(nimg * P), dim3(256), 0, s, (const void*)dsn, (const void*)f, img4, nimg, P, partial);
     hipLaunchKernelGGL(alpha_grad_finish_kernel, dim3((nimg + 255) / 256), dim3(256), 0, s, (const double*)partial, nimg, P, half, pair_last, V, d_alphas);
     HRN_LAUNCH_CHECK();
     return 0;

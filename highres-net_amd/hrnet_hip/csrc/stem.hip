@@ -308,10 +308,11 @@ __global__ __launch_bounds__(256) void plane_mean_kernel(const float* __restrict
     if (threadIdx.x == 0) mean[blockIdx.x] = (float)(red[0] / (double)hw);
 }
 
-// 8 elements per thread: out = float(hi) + float(lo)
+// 8 elements per thread: out = float(hi) + float(lo); LO = false: one bf16 plane, out = float(hi)
+template <bool LO>
 __global__ __launch_bounds__(256) void planes_to_f32_kernel(const u32x4* __restrict__ hi, const u32x4* __restrict__ lo, float* __restrict__ out, size_t n8) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
-        const u32x4 h = hi[i], l = lo[i];
+        const u32x4 h = hi[i], l = LO ? lo[i] : u32x4{0u, 0u, 0u, 0u};
         f32x4 a, b;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -325,6 +326,8 @@ __global__ __launch_bounds__(256) void planes_to_f32_kernel(const u32x4* __restr
     }
 }
 
+// LO = false: the hi plane alone, which is f32 -> bf16 rounded to nearest even
+template <bool LO>
 __global__ __launch_bounds__(256) void f32_to_planes_kernel(const float* __restrict__ in, u32x4* __restrict__ hi, u32x4* __restrict__ lo, size_t n8) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
         const f32x4 a = *(const f32x4*)(in + i * 8), b = *(const f32x4*)(in + i * 8 + 4);
@@ -332,7 +335,7 @@ __global__ __launch_bounds__(256) void f32_to_planes_kernel(const float* __restr
         split2_bf16(a[0], a[1], h[0], l[0]); split2_bf16(a[2], a[3], h[1], l[1]);
         split2_bf16(b[0], b[1], h[2], l[2]); split2_bf16(b[2], b[3], h[3], l[3]);
         hi[i] = u32x4{h[0], h[1], h[2], h[3]};
-        lo[i] = u32x4{l[0], l[1], l[2], l[3]};
+        if constexpr (LO) lo[i] = u32x4{l[0], l[1], l[2], l[3]};
     }
 }
 
@@ -381,7 +384,8 @@ int hrn_launch_stem(int dt, const float* in0, size_t img_stride0, const float* i
     return 0;
 }
 
-// f32, no activation, and only if only_if_nonpos[0] <= 0: the stem's pre-activation for the backward of a PReLU whose slope is not positive
+// no activation, and only if only_if_nonpos[0] <= 0: the stem's pre-activation for the backward of a PReLU whose slope is not positive,
+// in the training storage of dt (f32, one bf16 plane or bf16x3 planes)
 int hrn_launch_stem_pre(const float* in0, size_t img_stride0, const float* in1, int rep1, size_t img_stride1, const float* w,
                         const float* bias, float* out, int M, int H, int W, const float* only_if_nonpos, hipStream_t stream, int dt) {
     const size_t patches = (size_t)M * ((H + 3) / 4) * ((W + 31) / 32);
@@ -392,29 +396,37 @@ int hrn_launch_stem_pre(const float* in0, size_t img_stride0, const float* in1, 
         HRN_LAUNCH_CHECK();
         return 0;
     }
+    if (dt == HRN_BF16) {
+        hipLaunchKernelGGL(stem_kernel<HRN_BF16>, dim3(blocks), dim3(256), 0, stream, in0, in1, img_stride0, rep1, img_stride1, (const float*)nullptr, w, bias,
+                           (const float*)nullptr, (void*)out, M, H, W, only_if_nonpos, (size_t)0);
+        HRN_LAUNCH_CHECK();
+        return 0;
+    }
     hipLaunchKernelGGL(stem_kernel<HRN_F32>, dim3(blocks), dim3(256), 0, stream, in0, in1, img_stride0, rep1, img_stride1, (const float*)nullptr, w, bias,
                        (const float*)nullptr, (void*)out, M, H, W, only_if_nonpos, (size_t)0);
     HRN_LAUNCH_CHECK();
     return 0;
 }
 
-// bf16x3: (hi, lo) bf16 planes -> f32 (the fused state before the fp32 decoder; staged tensors for the tests)
+// bf16x3: (hi, lo) bf16 planes -> f32 (the fused state before the fp32 decoder; staged tensors for the tests); lo_off == 0: one bf16 plane
 int hrn_launch_planes_to_f32(const void* hi, size_t lo_off, float* out, size_t n, hipStream_t stream) {
     HRN_CHECK(n % 8 == 0 && lo_off % 16 == 0, -2, "planes_to_f32: %zu elements / lo offset %zu not aligned", n, lo_off);
     const size_t n8 = n / 8;
     const int blocks = (int)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
     HrnProfScope prof("planes_to_f32", 0.0, (double)n * 8, stream);
-    hipLaunchKernelGGL(planes_to_f32_kernel, dim3(blocks), dim3(256), 0, stream, (const u32x4*)hi, (const u32x4*)((const unsigned char*)hi + lo_off), out, n8);
+    if (lo_off) hipLaunchKernelGGL(planes_to_f32_kernel<true>, dim3(blocks), dim3(256), 0, stream, (const u32x4*)hi, (const u32x4*)((const unsigned char*)hi + lo_off), out, n8);
+    else hipLaunchKernelGGL(planes_to_f32_kernel<false>, dim3(blocks), dim3(256), 0, stream, (const u32x4*)hi, (const u32x4*)nullptr, out, n8);
     HRN_LAUNCH_CHECK();
     return 0;
 }
 
-// f32 -> (hi, lo) bf16 planes
+// f32 -> (hi, lo) bf16 planes; lo_off == 0: one bf16 plane (round to nearest even)
 int hrn_launch_f32_to_planes(const float* in, void* hi, size_t lo_off, size_t n, hipStream_t stream) {
     HRN_CHECK(n % 8 == 0 && lo_off % 16 == 0, -2, "f32_to_planes: %zu elements / lo offset %zu not aligned", n, lo_off);
     const size_t n8 = n / 8;
     const int blocks = (int)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
-    hipLaunchKernelGGL(f32_to_planes_kernel, dim3(blocks), dim3(256), 0, stream, in, (u32x4*)hi, (u32x4*)((unsigned char*)hi + lo_off), n8);
+    if (lo_off) hipLaunchKernelGGL(f32_to_planes_kernel<true>, dim3(blocks), dim3(256), 0, stream, in, (u32x4*)hi, (u32x4*)((unsigned char*)hi + lo_off), n8);
+    else hipLaunchKernelGGL(f32_to_planes_kernel<false>, dim3(blocks), dim3(256), 0, stream, in, (u32x4*)hi, (u32x4*)nullptr, n8);
     HRN_LAUNCH_CHECK();
     return 0;
 }

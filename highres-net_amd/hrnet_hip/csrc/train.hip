@@ -1,6 +1,8 @@
-// Training path of HRNet (fp32, or bf16x3: every activation / gradient tensor a pair of bf16 planes, three bf16 MFMAs per product - the
-// convolutions, data gradients and weight gradients then run on conv3x3_v6x3.hip / wgrad_x3.hip, the elementwise passes on the same
-// kernels templated on the storage): a forward that keeps what the backward needs, and the backward itself
+// Training path of HRNet (fp32; bf16x3: every activation / gradient tensor a pair of bf16 planes, three bf16 MFMAs per product - the
+// convolutions, data gradients and weight gradients then run on conv3x3_v6x3.hip / wgrad_x3.hip; or bf16: every activation / gradient
+// tensor one bf16 plane, one bf16 MFMA per product with fp32 accumulation - conv3x3_r64.hip / conv3x3_v6.hip and the one-plane instance of
+// wgrad_x3.hip.  The elementwise passes are the same kernels templated on the storage): a forward that keeps what the backward needs,
+// and the backward itself
 // (`srs = fusion_model(lrs, alphas)` ... `loss.backward()`, src/train.py:172-190).
 //
 // Forward (HRNet.py:186-211) is the inference kernel sequence with every intermediate kept in the training workspace:
@@ -30,11 +32,11 @@ struct TrainWs {
     size_t g[5];                            // backward: five gradient buffers of one full activation each
     size_t xpre;                            // backward: a recomputed pre-activation (used only behind a PReLU whose slope is <= 0)
     size_t wt, wtp, zero_bias, scratch;
-    size_t dec_f, dec_g;                    // bf16x3: f32 copies of the fused state and of its gradient (the decoder's backward is the fp32 kernel)
+    size_t dec_f, dec_g;                    // bf16 / bf16x3: f32 copies of the fused state and of its gradient (the decoder's backward is the fp32 kernel)
     size_t total;
 };
 
-// bf16x3: a tensor of n elements is a pair of bf16 planes, the lo plane 2 n bytes behind the hi plane (0 for fp32)
+// bf16x3: a tensor of n elements is a pair of bf16 planes, the lo plane 2 n bytes behind the hi plane (0 for fp32 and bf16: one plane)
 inline size_t lo_of(int dt, size_t n) { return dt == HRN_BF16X3 ? n * 2 : 0; }
 
 int num_cus() { return hrn_device_cus(); }
@@ -85,6 +87,16 @@ int check_train(int nl, int B, int V, int H, int W) {
     return 0;
 }
 
+// `packed` and the training workspace are carved at ALIGN-byte offsets, and every dtype's kernels read them with 16-byte vector and
+// LDS-DMA loads: both base pointers must be ALIGN-aligned (every hipMalloc and caching-allocator block is).  Checked on the host, so a
+// bad pointer is refused before any launch.
+int check_aligned(const char* fn, int dt, const void* pk, const void* tws) {
+    HRN_CHECK((uintptr_t)pk % ALIGN == 0 && (uintptr_t)tws % ALIGN == 0, -2,
+              "%s: packed (%p) and train_ws (%p) must be %zu-byte aligned for the blob and workspace layout of dtype %d", fn, pk, tws,
+              (size_t)ALIGN, dt);
+    return 0;
+}
+
 // y = conv3x3(x) (+ PReLU) on the forward f32 kernel
 int conv_fwd(int dt, int cin, int cout, const void* x, void* y, const void* wpk, const float* bias, const float* slope, int M, int H, int W,
              hipStream_t s) {
@@ -103,7 +115,8 @@ int conv_dgrad(int dt, int cin, int cout, const float* w, const float* g, float*
 // dW += the weight gradient of a cin -> cout convolution: x plain [M][H][W][cin], or (x == nullptr) the pair gather of `stack`
 int conv_wgrad(int dt, const float* x, const float* stack, int pair_h, int pair_last, int pair_vs, int Bn, const float* g, int M, int H, int W,
                int cin, int cout, float* dw, void* sc, int cus, hipStream_t s) {
-    if (dt != HRN_BF16X3) return hrn_launch_conv_wgrad(x, stack, x ? 0 : 1, pair_h, pair_last, pair_vs, g, M, H, W, cin, cout, dw, sc, cus, s);
+    if (dt == HRN_F32) return hrn_launch_conv_wgrad(x, stack, x ? 0 : 1, pair_h, pair_last, pair_vs, g, M, H, W, cin, cout, dw, sc, cus, s);
+    if (dt == HRN_BF16) return hrn_launch_conv_wgrad_bf16(x, stack, x ? 0 : 1, pair_h, pair_last, pair_vs, g, M, H, W, cin, cout, dw, sc, cus, s);
     const size_t hw = (size_t)H * W;
     const size_t x_lo = x ? (size_t)M * hw * cin * 2 : (size_t)Bn * pair_vs * hw * 64 * 2;     // the stack of the level: Bn samples x pair_vs views
     return hrn_launch_conv_wgrad_x3(x, stack, x_lo, x ? 0 : 1, pair_h, pair_last, pair_vs, g, (size_t)M * hw * cout * 2, M, H, W, cin, cout, dw, sc,
@@ -111,7 +124,7 @@ int conv_wgrad(int dt, const float* x, const float* stack, int pair_h, int pair_
 }
 
 // z + u for the pair gather z of a level: t2[b*half + i][p][c] = (c < 64 ? s_i : s_partner)[p][c % 64] + u[...]
-template <bool X3>
+template <int ST>
 __global__ __launch_bounds__(256) void pair_add_kernel(const void* __restrict__ stack, int n_in, int half, int pair_last,
                                                        const void* __restrict__ u, void* __restrict__ t2, size_t hw, int B) {
     const size_t total = (size_t)B * half * hw * 32;            // float4 units, 32 per pixel
@@ -122,8 +135,8 @@ __global__ __launch_bounds__(256) void pair_add_kernel(const void* __restrict__ 
         const size_t img = pixg / hw, pix = pixg - img * hw;
         const int b = (int)(img / half), v = (int)(img - (size_t)b * half);
         const int src = part < 16 ? v : pair_last - v;
-        const f32x4 z = act_ld4<X3>(stack, lo_s, (((size_t)b * n_in + src) * hw + pix) * 16 + (part & 15));
-        act_st4<X3>(t2, lo_u, i, z + act_ld4<X3>(u, lo_u, i));
+        const f32x4 z = act_ld4<ST>(stack, lo_s, (((size_t)b * n_in + src) * hw + pix) * 16 + (part & 15));
+        act_st4<ST>(t2, lo_u, i, z + act_ld4<ST>(u, lo_u, i));
     }
 }
 
@@ -161,8 +174,9 @@ int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alp
     int rc;
     HRN_CHECK(hrn_scale_ok(scale), -2, "hrn_hrnet_forward_train: scale must be 2, 3 or 4 (got %d)", scale);
     if ((rc = check_train(nl, B, V, H, W))) return rc;
-    HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16X3, -2, "hrn_hrnet_forward_train: dtype must be HRN_DTYPE_F32 or HRN_DTYPE_BF16X3 (got %d)", dt);
+    HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16 || dt == HRN_BF16X3, -2, "hrn_hrnet_forward_train: dtype must be HRN_DTYPE_F32, HRN_DTYPE_BF16 or HRN_DTYPE_BF16X3 (got %d)", dt);
     HRN_CHECK(pk && lrs && alphas && sr && tws, -2, "hrn_hrnet_forward_train: null argument");
+    if ((rc = check_aligned("hrn_hrnet_forward_train", dt, pk, tws))) return rc;
     const TrainWs L = train_ws(nl, B, V, H, W);
     HRN_CHECK(tws_bytes >= L.total, -3, "hrn_hrnet_forward_train: workspace too small (%zu < %zu)", tws_bytes, L.total);
     const HrnetLayout P = hrnet_layout(dt, nl, scale);
@@ -198,10 +212,8 @@ int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alp
             const size_t total4 = (size_t)B * half * hw * 32;
             size_t grid = (total4 + 255) / 256;
             if (grid > 4096) grid = 4096;
-            if (dt == HRN_BF16X3) hipLaunchKernelGGL(pair_add_kernel<true>, dim3((unsigned)grid), dim3(256), 0, s, (const void*)st, n, half, pair_last, (const void*)at(tws, L.u[t]),
-                                                     (void*)at(tws, L.t2[t]), hw, B);
-            else hipLaunchKernelGGL(pair_add_kernel<false>, dim3((unsigned)grid), dim3(256), 0, s, (const void*)st, n, half, pair_last, (const void*)at(tws, L.u[t]),
-                                    (void*)at(tws, L.t2[t]), hw, B);
+            HRN_LAUNCH_ST(dt, pair_add_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const void*)st, n, half, pair_last, (const void*)at(tws, L.u[t]),
+                          (void*)at(tws, L.t2[t]), hw, B);
             HRN_LAUNCH_CHECK();
         }
         if ((rc = conv_fwd(dt, 128, 64, at(tws, L.t2[t]), at(tws, L.f[t]), at(pk, P.fout_w), (const float*)at(pk, P.fout_b),
@@ -225,8 +237,9 @@ int hrn_hrnet_backward_in(const void* pk, int dt, int scale, const hrn_hrnet_par
                           size_t tws_bytes, void* stream) {
     int rc;
     HRN_CHECK(hrn_scale_ok(scale), -2, "hrn_hrnet_backward: scale must be 2, 3 or 4 (got %d)", scale);
-    HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16X3, -2, "hrn_hrnet_backward: dtype must be HRN_DTYPE_F32 or HRN_DTYPE_BF16X3 (got %d)", dt);
+    HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16 || dt == HRN_BF16X3, -2, "hrn_hrnet_backward: dtype must be HRN_DTYPE_F32, HRN_DTYPE_BF16 or HRN_DTYPE_BF16X3 (got %d)", dt);
     HRN_CHECK(pk && Pr && Gr && lrs && alphas && d_sr && tws, -2, "hrn_hrnet_backward: null argument");
+    if ((rc = check_aligned("hrn_hrnet_backward", dt, pk, tws))) return rc;
     const int nl = Pr->num_layers;
     if ((rc = check_train(nl, B, V, H, W))) return rc;
     const TrainWs L = train_ws(nl, B, V, H, W);
@@ -258,17 +271,17 @@ int hrn_hrnet_backward_in(const void* pk, int dt, int scale, const hrn_hrnet_par
 
     // ---- decoder: d_sr -> d stack_T (one view left)                                  HRNet.py:147-156,167-169
     float* dsn = G[0];                      // gradient of the views leaving the current level
-    if (dt == HRN_BF16X3) {
+    if (dt != HRN_F32) {
         // the decoder's backward is the fp32 kernel (33 MB of state at the training shape): the fused state as f32, its gradient back as planes
         const size_t nf = (size_t)B * L.n_in[L.T] * hw * 64;
         float* ff = (float*)at(tws, L.dec_f);
         float* fg = (float*)at(tws, L.dec_g);
-        if ((rc = hrn_launch_planes_to_f32(at(tws, L.stack[L.T]), nf * 2, ff, nf, s))) return rc;
+        if ((rc = hrn_launch_planes_to_f32(at(tws, L.stack[L.T]), lo_of(dt, nf), ff, nf, s))) return rc;
         if ((rc = hrn_launch_decoder_bwd(ff, d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, fg,
                                          mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a), mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s,
                                          scale)))
             return rc;
-        if ((rc = hrn_launch_f32_to_planes(fg, dsn, nf * 2, nf, s))) return rc;
+        if ((rc = hrn_launch_f32_to_planes(fg, dsn, lo_of(dt, nf), nf, s))) return rc;
     } else if ((rc = hrn_launch_decoder_bwd((const float*)at(tws, L.stack[L.T]), d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, dsn,
                                             mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a), mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s,
                                             scale)))

@@ -14,6 +14,11 @@
 // rings - x: 5 rows, g: 3 rows, 76 KB in all - so every x row is fetched once and used for three output rows.  Wave (cb, ib) owns the
 // 32 x 32 block (cout 32 cb.., cin 32 ib..) for all nine taps: 36 accumulator tiles = 144 registers, kept across the whole launch.
 // Per row and wave: 8 transposed reads for g (shared by the nine taps), 8 per tap for x, 12 MFMAs per tap.
+//
+// X3 = false is the bf16 training mode: g and x are ONE bf16 plane each and a product is one MFMA (g x), fp32 accumulation.  The rings
+// keep their depth and hold one plane (38 KB); the workgroup shape, the accumulators, the partial slabs and the finish are the same.
+// Per row and wave: 4 transposed reads for g, 4 per tap for x, 4 MFMAs per tap.  Still two workgroups per CU: the 144 accumulators
+// (+ operands) take more than a third of a SIMD's registers, and hrn_bwd_scratch_bytes sizes the partial slabs for two per CU.
 #include "kernels.h"
 #include "backward.h"
 
@@ -25,16 +30,20 @@ namespace {
 
 constexpr int XPX = 40, GPX = 32;                            // pixels per LDS row image (x: 34 used)
 constexpr int XPLANE = XPX * 128, GPLANE = GPX * 128;        // one plane of one row: 5,120 | 4,096 B
-constexpr int XSLOT = 2 * XPLANE, GSLOT = 2 * GPLANE;        // hi + lo
 constexpr int XRING = 5, GRING = 3;
-constexpr int OFF_G = XRING * XSLOT;                         // 51,200
-constexpr int WX_LDS = OFF_G + GRING * GSLOT;                // 75,776
+// one ring slot holds the planes of one row: hi + lo (X3), or the one bf16 plane
+template <bool X3> struct WgRing {
+    static constexpr int NPL = X3 ? 2 : 1;
+    static constexpr int XSLOT = NPL * XPLANE, GSLOT = NPL * GPLANE;
+    static constexpr int OFF_G = XRING * XSLOT;              // 51,200 | 25,600
+    static constexpr int LDS = OFF_G + GRING * GSLOT;        // 75,776 | 37,888
+};
 constexpr unsigned OOBW = 0x80000000u;
 
 struct WgradX3Params {
-    const void* x;          // plain input [M][H][W][cin] bf16 planes (in_pair == 0)
+    const void* x;          // plain input [M][H][W][cin] bf16 planes (in_pair == 0); one plane without X3
     const void* stack;      // pair gather: views [B][pair_vs][H][W][64]
-    size_t x_lo;            // byte offset of the lo plane of x / stack
+    size_t x_lo;            // byte offset of the lo plane of x / stack (X3 only)
     int in_pair, pair_h, pair_last, pair_vs;
     const void* g;          // [M][H][W][cout] planes
     size_t g_lo;
@@ -47,7 +56,9 @@ __device__ __forceinline__ int swz_w(int px) { return (((px >> 1) & 1) << 1) ^ (
 
 template <int N> __device__ __forceinline__ void wait_vm_w() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
+template <bool X3>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_x3_kernel(const WgradX3Params p) {
+    constexpr int NPL = WgRing<X3>::NPL, XSLOT = WgRing<X3>::XSLOT, GSLOT = WgRing<X3>::GSLOT, OFF_G = WgRing<X3>::OFF_G;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -85,7 +96,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x3_kernel(const WgradX3Para
             }
         }
 
-    // (per image row this wave issues 6 (wave 0: x pieces 0 and 4, g piece 0; two planes each) or 4 DMA instructions)
+    // (per image row this wave issues 6 (wave 0: x pieces 0 and 4, g piece 0; two planes each) or 4 DMA instructions; half as many
+    // without X3)
     bool first = true;
     for (long u = blockIdx.x; u < units; u += gridDim.x) {
         const int m = (int)(u / strips);
@@ -102,9 +114,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x3_kernel(const WgradX3Para
         const unsigned char* xbase = (const unsigned char*)(p.in_pair ? p.stack : p.x) + xoff;
         const unsigned char* gbase = (const unsigned char*)p.g + (size_t)m * hw * gpitch;
         const __amdgpu_buffer_rsrc_t rx0 = __builtin_amdgcn_make_buffer_rsrc((void*)xbase, 0, (int)(hw * xpitch), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rx1 = __builtin_amdgcn_make_buffer_rsrc((void*)(xbase + p.x_lo), 0, (int)(hw * xpitch), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rx1 = __builtin_amdgcn_make_buffer_rsrc((void*)(xbase + (X3 ? p.x_lo : 0)), 0, (int)(hw * xpitch), 0x00020000);
         const __amdgpu_buffer_rsrc_t rg0 = __builtin_amdgcn_make_buffer_rsrc((void*)gbase, 0, (int)(hw * gpitch), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rg1 = __builtin_amdgcn_make_buffer_rsrc((void*)(gbase + p.g_lo), 0, (int)(hw * gpitch), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rg1 = __builtin_amdgcn_make_buffer_rsrc((void*)(gbase + (X3 ? p.g_lo : 0)), 0, (int)(hw * gpitch), 0x00020000);
         // per-lane byte offsets inside an image row of this wave's DMA pieces (8 pixels x 128 B each): lane i -> pixel 8 j + (i >> 3),
         // physical chunk i & 7 = logical chunk ^ swz(pixel); outside the image -> an offset the descriptor turns into zeros
         unsigned xv[2], gv;
@@ -121,10 +133,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x3_kernel(const WgradX3Para
             gv = gx < W ? (unsigned)gx * gpitch + gcb + (unsigned)((((lq & 7) ^ swz_w(px))) << 4) : OOBW;
         }
         // one DMA instruction of an image row: item 0 / 1 = x piece w of plane 0 / 1, 2 / 3 = g piece w of plane 0 / 1, 4 / 5 = x piece 4 of
-        // plane 0 / 1 (wave 0 only).  x row `row` -> ring slot (row + 1) % XRING, g row `row` -> slot row % GRING
+        // plane 0 / 1 (wave 0 only; plane 1 only with X3).  x row `row` -> ring slot (row + 1) % XRING, g row `row` -> slot row % GRING
         auto dma_item = [&](int it, int xrow, int grow) __attribute__((always_inline)) {
             if (WGX_ABL & 1) return;
             const int pl = it & 1;
+            if (!X3 && pl) return;
             if (it == 2 || it == 3) {
                 const bool ok = grow < H;
                 const unsigned soff = ok ? (unsigned)grow * (unsigned)W * gpitch : 0u;
@@ -147,7 +160,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x3_kernel(const WgradX3Para
         dma_x(-1); dma_x(0); dma_x(1); dma_g(0); dma_x(2); dma_g(1);
         for (int y = 0; y < H; ++y) {
             // x rows <= y + 1 and g row y have landed once only the newest row's pieces are outstanding
-            if (!(WGX_ABL & 1)) { if (w == 0) wait_vm_w<6>(); else wait_vm_w<4>(); }
+            if (!(WGX_ABL & 1)) { if (w == 0) wait_vm_w<3 * NPL>(); else wait_vm_w<2 * NPL>(); }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (!(WGX_ABL & 8)) __builtin_amdgcn_s_barrier();
             // (x row y + 3 goes into the slot of row y - 2 and g row y + 2 into that of row y - 1: free since the barrier above.  Their six DMA
@@ -161,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x3_kernel(const WgradX3Para
                 else asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(imm));
             };
 #pragma unroll
-            for (int pl = 0; pl < 2; ++pl)
+            for (int pl = 0; pl < NPL; ++pl)
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -173,7 +186,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x3_kernel(const WgradX3Para
                 const int ky = t / 3, kx = t - 3 * ky;
                 const unsigned xs_off = (unsigned)(((y + ky) % XRING) * XSLOT);          // image row y + ky - 1 lives in slot (y + ky) % XRING
 #pragma unroll
-                for (int pl = 0; pl < 2; ++pl)
+                for (int pl = 0; pl < NPL; ++pl)
 #pragma unroll
                     for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -188,7 +201,16 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x3_kernel(const WgradX3Para
                 const int buf = t & 1;
                 if (t + 1 < 9) rd_tap(buf ^ 1, t + 1);
                 // LDS reads return in order: with the next tap's 8 reads allowed outstanding, this tap's (and the row's g) have arrived
-                if (t + 1 < 9) {
+                if constexpr (!X3) {
+                    // one plane: the next tap's 4 reads may stay outstanding
+                    if (t + 1 < 9)
+                        asm volatile("s_waitcnt lgkmcnt(4)"
+                                     : "+v"(xf[buf][0][0][0]), "+v"(xf[buf][0][0][1]), "+v"(xf[buf][0][1][0]), "+v"(xf[buf][0][1][1]),
+                                       "+v"(gf[0][0][0]), "+v"(gf[0][0][1]), "+v"(gf[0][1][0]), "+v"(gf[0][1][1]));
+                    else
+                        asm volatile("s_waitcnt lgkmcnt(0)"
+                                     : "+v"(xf[buf][0][0][0]), "+v"(xf[buf][0][0][1]), "+v"(xf[buf][0][1][0]), "+v"(xf[buf][0][1][1]));
+                } else if (t + 1 < 9) {
                     asm volatile("s_waitcnt lgkmcnt(8)"
                                  : "+v"(xf[buf][0][0][0]), "+v"(xf[buf][0][0][1]), "+v"(xf[buf][0][1][0]), "+v"(xf[buf][0][1][1]),
                                    "+v"(xf[buf][1][0][0]), "+v"(xf[buf][1][0][1]), "+v"(xf[buf][1][1][0]), "+v"(xf[buf][1][1][1]),
@@ -200,6 +222,24 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x3_kernel(const WgradX3Para
                                    "+v"(xf[buf][1][0][0]), "+v"(xf[buf][1][0][1]), "+v"(xf[buf][1][1][0]), "+v"(xf[buf][1][1][1]));
                 }
                 __builtin_amdgcn_sched_barrier(0);
+                if constexpr (!X3) {
+                    bf16x8 ah[2], bh[2];
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
+                        ah[b] = __builtin_bit_cast(bf16x8, u32x4{gf[0][b][0][0], gf[0][b][0][1], gf[0][b][1][0], gf[0][b][1][1]});
+                        bh[b] = __builtin_bit_cast(bf16x8, u32x4{xf[buf][0][b][0][0], xf[buf][0][b][0][1], xf[buf][0][b][1][0], xf[buf][0][b][1][1]});
+                    }
+#pragma unroll
+                    for (int a = 0; a < 2; ++a)
+#pragma unroll
+                        for (int b = 0; b < 2; ++b) {
+                            if (WGX_ABL & 4) { asm volatile("" : "+v"(acc[t][a][b]) : "v"(ah[a]), "v"(bh[b])); continue; }
+                            acc[t][a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[a], bh[b], acc[t][a][b], 0, 0, 0);
+                        }
+                    if (t < 6) dma_item(t, y + 3, y + 2);
+                    __builtin_amdgcn_sched_barrier(0);
+                    continue;
+                }
                 bf16x8 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
@@ -238,14 +278,16 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_x3_kernel(const WgradX3Para
 
 }  // namespace
 
-// dw[co][ci][3][3] += the weight gradient; x / g are bf16x3 plane pairs (x_lo / g_lo: byte offsets of their lo planes).  Scratch and the
-// fixed-order finish are the fp32 kernel's (hrn_bwd_scratch_bytes covers 2 workgroups per CU).
-int hrn_launch_conv_wgrad_x3(const void* x, const void* stack, size_t x_lo, int in_pair, int pair_h, int pair_last, int pair_vs, const void* g,
-                             size_t g_lo, int M, int H, int W, int cin, int cout, float* dw, void* scratch, int num_cus, hipStream_t s) {
+namespace {
+
+template <bool X3>
+int launch_wgrad_x3(const void* x, const void* stack, size_t x_lo, int in_pair, int pair_h, int pair_last, int pair_vs, const void* g,
+                    size_t g_lo, int M, int H, int W, int cin, int cout, float* dw, void* scratch, int num_cus, hipStream_t s) {
     HRN_CHECK((cin == 64 || cin == 128) && (cout == 64 || cout == 128), -2, "conv_wgrad_x3: unsupported %d -> %d", cin, cout);
     HRN_CHECK(!in_pair || cin == 128, -2, "conv_wgrad_x3: the pair gather has 128 input channels");
     HRN_CHECK((long)H * W * 256 < (1L << 31), -2, "conv_wgrad_x3: image too large for 32-bit in-image offsets (H=%d W=%d)", H, W);
-    { const int rc_lds = hrn_allow_lds((const void*)conv_wgrad_x3_kernel, WX_LDS); if (rc_lds) return rc_lds; }
+    constexpr int LDS = WgRing<X3>::LDS;
+    { const int rc_lds = hrn_allow_lds((const void*)conv_wgrad_x3_kernel<X3>, LDS); if (rc_lds) return rc_lds; }
     const long units = (long)M * ((W + 31) / 32);
     int grid = 2 * num_cus;
     if (units < grid) grid = (int)units;
@@ -257,11 +299,26 @@ int hrn_launch_conv_wgrad_x3(const void* x, const void* stack, size_t x_lo, int 
         for (int ic = 0; ic < cin / 64; ++ic) {
             p.co_chunk = cc; p.ci_chunk = ic;
             {
-                HrnProfScope prof("conv_wgrad_bf16x3", 2.0 * 64 * 64 * 9 * px, px * 4 * 128, s);
-                hipLaunchKernelGGL(conv_wgrad_x3_kernel, dim3(grid), dim3(256), WX_LDS, s, p);
+                HrnProfScope prof(X3 ? "conv_wgrad_bf16x3" : "conv_wgrad_bf16", 2.0 * 64 * 64 * 9 * px, px * (X3 ? 4 : 2) * 128, s);
+                hipLaunchKernelGGL(conv_wgrad_x3_kernel<X3>, dim3(grid), dim3(256), LDS, s, p);
             }
             if (int rc = hrn_launch_wgrad_finish((const float*)scratch, grid, dw, cin, cc, ic, s)) return rc;
         }
     HRN_LAUNCH_CHECK();
     return 0;
+}
+
+}  // namespace
+
+// dw[co][ci][3][3] += the weight gradient; x / g are bf16x3 plane pairs (x_lo / g_lo: byte offsets of their lo planes).  Scratch and the
+// fixed-order finish are the fp32 kernel's (hrn_bwd_scratch_bytes covers 2 workgroups per CU).
+int hrn_launch_conv_wgrad_x3(const void* x, const void* stack, size_t x_lo, int in_pair, int pair_h, int pair_last, int pair_vs, const void* g,
+                             size_t g_lo, int M, int H, int W, int cin, int cout, float* dw, void* scratch, int num_cus, hipStream_t s) {
+    return launch_wgrad_x3<true>(x, stack, x_lo, in_pair, pair_h, pair_last, pair_vs, g, g_lo, M, H, W, cin, cout, dw, scratch, num_cus, s);
+}
+
+// the same with x / g one bf16 plane each (the bf16 training mode)
+int hrn_launch_conv_wgrad_bf16(const void* x, const void* stack, int in_pair, int pair_h, int pair_last, int pair_vs, const void* g, int M,
+                               int H, int W, int cin, int cout, float* dw, void* scratch, int num_cus, hipStream_t s) {
+    return launch_wgrad_x3<false>(x, stack, 0, in_pair, pair_h, pair_last, pair_vs, g, 0, M, H, W, cin, cout, dw, scratch, num_cus, s);
 }

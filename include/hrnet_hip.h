@@ -118,7 +118,7 @@ int hrn_hrnet_forward_s(const void* packed, int dtype, int num_layers, int scale
 int hrn_decoder_forward_s(const void* packed, int dtype, int num_layers, int scale, const void* fused, int N, int H, int W,
                           float* sr, void* stream);
 
-/* Training path (fp32 only): `srs = fusion_model(lrs, alphas)` with grad enabled and `loss.backward()` through HRNet,
+/* Training path (fp32; bf16x3 and bf16 through the _dt / _s / _in forms below): `srs = fusion_model(lrs, alphas)` with grad enabled and `loss.backward()` through HRNet,
  * src/train.py:172-190.  hrn_hrnet_forward_train is hrn_hrnet_forward(HRN_DTYPE_F32) with every intermediate kept in
  * `train_ws`; hrn_hrnet_backward consumes that workspace (same B, V, H, W) and d_sr = dLoss/d sr (B,1,3H,3W) and
  * ACCUMULATES (+=, like autograd's .grad) the parameter gradients into the buffers `grads` points at - the same struct,
@@ -132,9 +132,13 @@ int hrn_hrnet_forward_train(const void* packed, int num_layers, int alpha_residu
 int hrn_hrnet_backward(const void* packed, const hrn_hrnet_params* params, int alpha_residual, const float* lrs,
                        const float* alphas, int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* grads,
                        void* train_ws, size_t train_ws_bytes, void* stream);
-/* The same with a dtype: HRN_DTYPE_F32 (what the two entry points above run) or HRN_DTYPE_BF16X3 - every activation and gradient
+/* The same with a dtype: HRN_DTYPE_F32 (what the two entry points above run); HRN_DTYPE_BF16X3 - every activation and gradient
  * tensor of the workspace a pair of bf16 planes, three bf16 MFMAs per product in the convolutions, their data gradients and their
- * weight gradients (same workspace size; `packed` is then the HRN_DTYPE_BF16X3 blob).  Parameters, gradients, lrs, sr, d_sr: f32. */
+ * weight gradients; or HRN_DTYPE_BF16 - every activation and gradient tensor of the workspace ONE bf16 plane (stores round to nearest
+ * even), one bf16 MFMA per product with fp32 accumulation, reductions (bias, slope, alpha, input-gradient sums) in fp32 / f64 as in
+ * the other modes.  `packed` is the blob of that dtype; the workspace size is the same for every dtype (bf16 uses less of it).
+ * Parameters, parameter gradients, lrs, alphas, sr, d_sr, d_lrs, d_alphas: f32 in every mode.  In every dtype `packed` and `train_ws`
+ * must be 256-byte aligned (as any hipMalloc'd block is); otherwise -2 before any launch. */
 int hrn_hrnet_forward_train_dt(const void* packed, int dtype, int num_layers, int alpha_residual, const float* lrs,
                                const float* alphas, int B, int V, int H, int W, float* sr, void* train_ws, size_t train_ws_bytes,
                                void* stream);

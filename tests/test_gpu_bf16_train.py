@@ -1,0 +1,434 @@
+"""GPU (-m gpu): HRNet training in bf16 - bf16 storage of every activation and gradient, one bf16 MFMA per product, fp32 accumulation
+(HRN_DTYPE_BF16 in hrn_hrnet_forward_train_s / hrn_hrnet_backward_in; `HRNet.train_precision = "bf16"`).
+
+Kernel-level checks feed bf16-representable inputs, so that every product is exact in fp32 and only the accumulation order (and, for
+the convolutions, the one rounding of the stored output) separates the kernels from fp64.  End to end the bf16 path is held to fp64
+autograd through oracle/torch_port with relative L2 bounds set from measurement (the bf16 forward alone is ~1e-2 from fp32).
+"""
+import ctypes
+import warnings
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import synth
+import util
+from test_gpu_backward import NONPOS, _SLOPE_KEYS, _fresh_model, _oracle_grads
+from test_gpu_input_grad import _oracle as _oracle_in, _tie_invariant_err
+from test_gpu_upscale import _model
+
+pytestmark = pytest.mark.gpu
+
+BF16 = 1
+
+
+def _lib():
+    from hrnet_hip import binding
+    lib = binding.load_library()
+    vp, i = ctypes.c_void_p, ctypes.c_int
+    lib.hrn_kt_wgrad_scratch_bytes.restype = ctypes.c_size_t
+    lib.hrn_kt_wgrad_scratch_bytes.argtypes = []
+    lib.hrn_kt_conv_wgrad.restype = i
+    lib.hrn_kt_conv_wgrad.argtypes = [i, vp, vp, i, i, i, vp, i, i, i, i, i, vp, vp, vp]
+    lib.hrn_kt_conv_dgrad.restype = i
+    lib.hrn_kt_conv_dgrad.argtypes = [i, i, i, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp]
+    lib.hrn_kt_conv3x3.restype = i
+    lib.hrn_kt_conv3x3.argtypes = [i, i, i, vp, vp, i, i, i, vp, vp, vp, i, i, i, vp]
+    lib.hrn_kt_conv_pack.restype = i
+    lib.hrn_kt_conv_pack.argtypes = [i, i, i, vp, vp, vp]
+    return lib
+
+
+def _p(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _bf(shape, seed, scale=1.0):
+    """a bf16 device tensor (and its exact fp64 CPU copy) of random values"""
+    g = torch.Generator().manual_seed(seed)
+    t = (torch.randn(shape, generator=g) * scale).to(torch.bfloat16)
+    return t.cuda(), t.double()
+
+
+def _nchw(t):
+    return t.permute(0, 3, 1, 2)
+
+
+def _cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _pair_gather(stack, half, pair_last):
+    """stack (B, n, H, W, 64) -> (B * half, H, W, 128): cat(view i, view pair_last - i) on channels"""
+    B = stack.shape[0]
+    idx = torch.arange(half)
+    return torch.cat([stack[:, idx], stack[:, pair_last - idx]], -1).reshape((B * half,) + tuple(stack.shape[2:4]) + (128,))
+
+
+# ----------------------------------------------------------------------------- 1. the ABI and the ops accept BF16
+@pytest.mark.parametrize("scale", [2, 3, 4])
+def test_bf16_training_op_runs_at_every_scale(scale):
+    """hrn_hrnet_forward_train_s / hrn_hrnet_backward_in with HRN_DTYPE_BF16 (the parent refused it with -2); the three ops pass opcheck."""
+    from hrnet_hip import binding
+    ops = torch.ops.hrnet_hip
+    lrs, alphas = synth.fast_batch(5, 2, 4, 16)
+    x, a = util.dev(lrs), util.dev(alphas)
+    m = _model(scale, "bf16")
+    pk = m.packed_parameters()[0]
+    params = [p for _, p in m.named_parameters()]
+    full = ("test_schema", "test_faketensor", "test_autograd_registration")
+    torch.library.opcheck(ops.hrnet_forward_train.default, (pk, x, a, params, 2, True, binding.BF16, scale), test_utils=full)
+    sr, tws = ops.hrnet_forward_train(pk, x, a, params, 2, True, binding.BF16, scale)
+    assert tuple(sr.shape) == (2, 1, scale * 16, scale * 16) and bool(torch.isfinite(sr).all())
+    d = torch.rand_like(sr)
+    det = [p.detach() for p in params]
+    torch.library.opcheck(ops.hrnet_backward.default, (pk, det, x, a, d, tws, 2, True, binding.BF16, scale),
+                          test_utils=("test_schema", "test_faketensor"))
+    torch.library.opcheck(ops.hrnet_backward_in.default, (pk, det, x, a, d, tws, 2, True, binding.BF16, scale, True, True),
+                          test_utils=("test_schema", "test_faketensor"))
+    grads, d_lrs, d_alphas = ops.hrnet_backward_in(pk, det, x, a, d, tws, 2, True, binding.BF16, scale, True, True)
+    for g in list(grads) + [d_lrs, d_alphas]:
+        assert bool(torch.isfinite(g).all())
+    assert float(grads[0].abs().sum()) > 0 and float(d_lrs.abs().sum()) > 0
+
+
+# ----------------------------------------------------------------------------- 2. the bf16 weight gradient
+def _wgrad_case(lib, M, H, W, cin, cout, pair=None, seed=0):
+    """-> (got, want, sum |terms|) for dW of a cin -> cout conv; pair = (B, n): the input is the pair gather of a (B, n) view stack"""
+    g, g64 = _bf((M, H, W, cout), seed + 1)
+    if pair:
+        B, n = pair
+        half, pair_last = n // 2, n - (n & 1) - 1
+        assert B * half == M and cin == 128
+        st, st64 = _bf((B, n, H, W, 64), seed)
+        x, x64 = None, _pair_gather(st64, half, pair_last)
+        args = (None, _p(st), half, pair_last, n)
+    else:
+        x, x64 = _bf((M, H, W, cin), seed)
+        args = (_p(x), None, 0, 0, 0)
+    dw0 = torch.randn((cout, cin, 3, 3), generator=torch.Generator().manual_seed(seed + 7))
+    dw = dw0.cuda()                                                     # the kernel adds (+=) to what is there
+    scratch = torch.empty(lib.hrn_kt_wgrad_scratch_bytes(), dtype=torch.uint8, device="cuda")
+    assert lib.hrn_kt_conv_wgrad(BF16, args[0], args[1], args[2], args[3], args[4], _p(g), M, H, W, cin, cout, _p(dw), _p(scratch),
+                                 _stream()) == 0
+    torch.cuda.synchronize()
+    want = torch.nn.grad.conv2d_weight(_nchw(x64), (cout, cin, 3, 3), _nchw(g64), padding=1)
+    terms = torch.nn.grad.conv2d_weight(_nchw(x64).abs(), (cout, cin, 3, 3), _nchw(g64).abs(), padding=1)
+    return (dw.double().cpu() - dw0.double()).numpy(), want.numpy(), terms.numpy()
+
+
+@pytest.mark.parametrize("case", ["plain64", "plain128x64", "pair", "ragged33", "multi_strip"])
+def test_bf16_wgrad_vs_fp64(case):
+    """The one-plane instance of conv_wgrad_x3_kernel: error <= 1e-5 of sum |terms| per element (bf16 products are exact in fp32)."""
+    lib = _lib()
+    if case == "plain64":
+        got, want, terms = _wgrad_case(lib, 3, 16, 32, 64, 64)
+    elif case == "plain128x64":
+        got, want, terms = _wgrad_case(lib, 2, 12, 40, 128, 64, seed=3)
+    elif case == "pair":
+        got, want, terms = _wgrad_case(lib, 2 * 2, 9, 24, 128, 128, pair=(2, 5), seed=5)
+    elif case == "ragged33":
+        got, want, terms = _wgrad_case(lib, 2, 7, 33, 64, 128, seed=9)
+    else:
+        # each workgroup walks several 32-pixel strips: units = M * ceil(W / 32), grid = min(2 CUs, units) (hrn_launch_conv_wgrad_bf16)
+        M, H, W = 4 * _cus() + 3, 4, 32
+        units, grid = M, min(2 * _cus(), M)
+        assert units >= 2 * grid, (units, grid)
+        got, want, terms = _wgrad_case(lib, M, H, W, 64, 64, seed=11)
+    err = np.abs(got - want)
+    print(case, "max err / sum|terms|", float((err / np.maximum(terms, 1e-30)).max()))
+    assert (err <= 1e-5 * terms + 1e-30).all()
+
+
+# ----------------------------------------------------------------------------- 3. the bf16 convolutions of the data gradients
+@pytest.mark.parametrize("cin,cout,res", [(64, 64, False), (64, 64, True), (128, 128, False), (128, 128, True), (128, 64, False)])
+def test_bf16_dgrad_vs_fp64(cin, cout, res):
+    """dx = conv3x3(g, W^T flipped) (+ res) for a cin -> cout layer, i.e. a cout -> cin convolution on the bf16 kernels (r64, v6; the
+    64 -> 128 and 128 -> 128 + res shapes are the new v6 instances).  Bound per element: one bf16 rounding of the output (2^-8 of it)
+    plus 1e-5 of sum |terms|."""
+    lib = _lib()
+    M, H, W = 3, 13, 37
+    g, g64 = _bf((M, H, W, cout), 21)
+    w, w64 = _bf((cout, cin, 3, 3), 22, 0.05)
+    w32 = w.float().contiguous()
+    r, r64 = _bf((M, H, W, cin), 23) if res else (None, None)
+    dx = torch.empty((M, H, W, cin), dtype=torch.bfloat16, device="cuda")
+    wt = torch.empty(cin * cout * 9, device="cuda")
+    wtp = torch.empty(cin * cout * 9, device="cuda")
+    zb = torch.zeros(128, device="cuda")
+    assert lib.hrn_kt_conv_dgrad(BF16, cin, cout, _p(w32), _p(g), _p(dx), _p(r), M, H, W, _p(wt), _p(wtp), _p(zb), _stream()) == 0
+    torch.cuda.synchronize()
+    want = torch.nn.grad.conv2d_input((M, cin, H, W), w64, _nchw(g64), padding=1)
+    terms = torch.nn.grad.conv2d_input((M, cin, H, W), w64.abs(), _nchw(g64).abs(), padding=1)
+    if res:
+        want = want + _nchw(r64)
+        terms = terms + _nchw(r64).abs()
+    got = _nchw(dx.double().cpu())
+    err = (got - want).abs()
+    bound = 2.0 ** -8 * want.abs() + 1e-5 * terms + 1e-30
+    print(cin, cout, res, "max err / bound", float((err / bound).max()))
+    assert bool((err <= bound).all())
+
+
+def test_bf16_pair_gather_conv_vs_fp64():
+    """The 128 -> 128 convolution of the pair gather cat(view i, view pair_last - i) (fusion convA: forward and its gated recompute)."""
+    lib = _lib()
+    B, n, H, W = 2, 5, 11, 35
+    half, pair_last = n // 2, n - (n & 1) - 1
+    st, st64 = _bf((B, n, H, W, 64), 31)
+    w, w64 = _bf((128, 128, 3, 3), 32, 0.05)
+    bias = torch.randn(128, generator=torch.Generator().manual_seed(33)).to(torch.bfloat16).float()
+    pk = torch.empty(128 * 128 * 9, dtype=torch.bfloat16, device="cuda")
+    assert lib.hrn_kt_conv_pack(BF16, 128, 128, _p(w.float().contiguous()), _p(pk), _stream()) == 0
+    out = torch.empty((B * half, H, W, 128), dtype=torch.bfloat16, device="cuda")
+    bias_d = bias.cuda()
+    assert lib.hrn_kt_conv3x3(BF16, 128, 128, None, _p(st), half, pair_last, n, _p(pk), _p(bias_d), _p(out), B * half, H, W, _stream()) == 0
+    torch.cuda.synchronize()
+    z = _nchw(_pair_gather(st64, half, pair_last))
+    want = F.conv2d(z, w64, bias.double(), padding=1)
+    terms = F.conv2d(z.abs(), w64.abs(), bias.double().abs(), padding=1)
+    err = (_nchw(out.double().cpu()) - want).abs()
+    assert bool((err <= 2.0 ** -8 * want.abs() + 1e-5 * terms + 1e-30).all()), float(err.max())
+
+
+# ----------------------------------------------------------------------------- 4. end to end against fp64 autograd
+def _rel_l2(got, want):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    return float(np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-30))
+
+
+def _tie_invariant_l2(got, want, lrs):
+    """relative L2 error of d lrs with the views tied with the median at a pixel (torch leaves open which one gets the reference frame's
+    gradient) compared by their sum: both sides are projected onto (the tied views' sum at the first of them, zeros at the others)"""
+    n = min(lrs.shape[1], 9)
+    med = torch.median(torch.from_numpy(lrs[:, :n]), 1).values.numpy()
+    tied = lrs[:, :n] == med[:, None]
+    first = np.argmax(tied, 1)[:, None]
+    out = []
+    for t in (got, want):
+        t = np.array(t, np.float64)
+        s = np.where(tied, t[:, :n], 0).sum(1)[:, None]
+        head = np.where(tied, 0.0, t[:, :n])
+        np.put_along_axis(head, first, s, 1)
+        out.append(np.concatenate([head, t[:, n:]], 1))
+    return _rel_l2(out[0], out[1])
+
+
+# Bounds from measurement (commit message).  Tensors: relative L2 per tensor; single-slope gradients: |error| against sum |terms| of their
+# own defining sum (torch_port.ABS_TERMS), as in test_gpu_backward.  With every PReLU slope at 1 nothing can change sign, so the error is
+# the bf16 storage alone: these bounds are ~3x the worst measured (tensors 8.8e-3, stem weight 7.0e-3, d lrs 7.6e-3, d alphas 4.7e-3,
+# scalars 8.9e-5, sr 7.2e-3) and pin the kernels.  At the reference's slopes and at slopes <= 0, activations near zero take the other
+# PReLU branch in a forward ~1e-2 from fp64, and at these small shapes (<= 1,152 pixels per image) each flip moves a gradient by a large
+# share (the same effect test_gpu_backward documents for fp32 and bf16x3): measured worst tensor 0.168 (a bias of the encoder), stem
+# weight 0.127, d lrs 0.151, d alphas 0.092, scalars 1.6e-3.  Those runs are held to ~1.5x that.
+_BOUNDS = {  # (tensor, stem weight, d lrs, d alphas, scalar / sum|terms|, sr)
+    "ones": (2.5e-2, 2e-2, 2e-2, 1.4e-2, 2.5e-4, 2e-2),
+    "flips": (2.5e-1, 2e-1, 2.5e-1, 1.5e-1, 5e-3, 2e-2),
+}
+
+
+def _bf16_model(alpha_residual=True, slopes=None):
+    m = _fresh_model(alpha_residual, slopes=slopes, precision="fp32")
+    m.train_precision = "bf16"
+    return m
+
+
+@pytest.mark.parametrize("B,V,S,n_real,alpha_residual", [
+    (2, 4, 16, 4, True),
+    (2, 5, 16, 4, True),        # odd V, one padded view
+    (2, 6, 16, 6, False),       # no alpha residual
+    (2, 1, 16, 1, True),        # V = 1
+    (1, 7, 24, 7, True),
+])
+@pytest.mark.parametrize("slopes", ["ones", "ref", "nonpos"])
+def test_bf16_training_vs_autograd_oracle(B, V, S, n_real, alpha_residual, slopes):
+    sl = {"ones": {k: 1.0 for k in _SLOPE_KEYS}, "ref": None, "nonpos": NONPOS}[slopes]
+    lrs, alphas, _ = synth.make_batch(5, B, V, S, n_real)
+    cot = np.random.Generator(np.random.PCG64(77)).standard_normal((B, 1, 3 * S, 3 * S)).astype(np.float32)
+    want_sr, want = _oracle_grads(lrs, alphas, cot, alpha_residual, slopes=sl)
+    want_lrs, want_alphas, _ = _oracle_in(lrs, alphas, cot, alpha_residual, sl)
+    abs_terms = want["__abs_terms__"]
+    m = _bf16_model(alpha_residual, sl)
+    x = util.dev(lrs).requires_grad_(True)
+    a = util.dev(alphas).requires_grad_(True)
+    sr = m(x, a)
+    (sr * util.dev(cot)).sum().backward()
+    tens, scal = {}, {}
+    for k, p in m.named_parameters():
+        got = p.grad.cpu().numpy()
+        if p.numel() > 1:
+            if np.abs(want[k]).max() > 0:
+                tens[k] = _rel_l2(got, want[k])
+        elif k in abs_terms:
+            scal[k] = abs(float(got.ravel()[0]) - float(want[k].ravel()[0])) / max(abs_terms[k], 1e-30)
+    stem_w = tens.pop("encode.init_layer.0.weight")
+    e_lrs = _tie_invariant_l2(x.grad.cpu().numpy(), want_lrs, lrs)
+    e_sr = _rel_l2(sr.detach().cpu().numpy(), want_sr)
+    e_alpha = None
+    if want_alphas is not None and np.abs(want_alphas).max() > 0:
+        e_alpha = _rel_l2(a.grad.cpu().numpy(), want_alphas)
+    top = lambda d: sorted(d.items(), key=lambda kv: -kv[1])[:2]
+    print(f"bf16 e2e B={B} V={V} S={S} {slopes}: sr {e_sr:.2e}, tensors {top(tens)}, stem weight {stem_w:.2e}, scalars / sum|terms| "
+          f"{top(scal)}, d_lrs {e_lrs:.2e}, d_alphas {e_alpha}")
+    b_tens, b_stem, b_lrs, b_alpha, b_scal, b_sr = _BOUNDS["ones" if slopes == "ones" else "flips"]
+    assert e_sr <= b_sr
+    for k, e in tens.items():
+        assert e <= b_tens, (k, e)
+    assert stem_w <= b_stem
+    for k, e in scal.items():
+        assert e <= b_scal, (k, e)
+    assert e_lrs <= b_lrs
+    if e_alpha is not None:
+        assert e_alpha <= b_alpha
+
+
+# ----------------------------------------------------------------------------- 5. the training forward
+def test_bf16_training_forward_matches_inference():
+    """sr of the bf16 training forward against the fp32 path (the bf16 parity bound) and against the bf16 inference kernels."""
+    lrs, alphas, _ = synth.make_batch(3, 4, 8, 32, 7)
+    x, a = util.dev(lrs), util.dev(alphas)
+    m = _bf16_model()
+    m.precision = "bf16"
+    sr_train = m(x, a).detach()
+    m.eval()
+    with torch.no_grad():
+        sr_inf = m(x, a)
+        m.precision = "fp32"
+        sr_f32 = m(x, a)
+    e_f32 = util.rel_err(sr_train.cpu().numpy(), sr_f32.cpu().numpy())
+    e_inf = util.rel_err(sr_train.cpu().numpy(), sr_inf.cpu().numpy())
+    print(f"bf16 training forward: {e_f32:.2e} from fp32, {e_inf:.2e} from bf16 inference (max-norm relative)")
+    assert e_f32 <= 3e-2
+    assert e_inf <= 3e-2
+
+
+# ----------------------------------------------------------------------------- 6. training tracks fp32
+def test_bf16_training_tracks_fp32_training():
+    lrs, alphas, _ = synth.make_batch(9, 2, 4, 16, 4)
+    x, a = util.dev(lrs), util.dev(alphas)
+    target = torch.zeros((2, 1, 48, 48), device="cuda") + 0.1
+    curves = {}
+    for prec in ("fp32", "bf16"):
+        m = _fresh_model(precision="fp32")
+        m.train_precision = prec
+        opt = torch.optim.Adam(m.parameters(), lr=1e-3)
+        curve = []
+        for _ in range(20):
+            opt.zero_grad()
+            loss = ((m(x, a) - target) ** 2).mean()
+            loss.backward()
+            opt.step()
+            curve.append(float(loss.detach()))
+        curves[prec] = np.array(curve)
+    rel = np.abs(curves["bf16"] - curves["fp32"]) / curves["fp32"]
+    print("fp32 vs bf16 training: loss", curves["fp32"][[0, 9, 19]], curves["bf16"][[0, 9, 19]], "max rel diff", rel.max())
+    assert curves["fp32"][-1] < 0.5 * curves["fp32"][0] and curves["bf16"][-1] < 0.5 * curves["bf16"][0]
+    assert rel.max() <= 1e-1, rel
+
+
+# ----------------------------------------------------------------------------- 7. determinism at the training shape
+def test_bf16_backward_is_deterministic_at_train_shape():
+    B, V, S = 32, 32, 64
+    lrs, alphas = synth.fast_batch(4, B, V, S)
+    x, a = util.dev(lrs), util.dev(alphas)
+    cot = torch.randn((B, 1, 3 * S, 3 * S), generator=torch.Generator().manual_seed(5)).cuda()
+    m = _bf16_model()
+    runs = []
+    for _ in range(2):
+        m.zero_grad(set_to_none=True)
+        (m(x, a) * cot).sum().backward()
+        runs.append([p.grad.clone() for p in m.parameters()])
+    for g0, g1 in zip(*runs):
+        assert torch.equal(g0, g1)
+
+
+# ----------------------------------------------------------------------------- 8. the module surface
+def test_train_precision_bf16_uses_bf16_kernels_without_warning():
+    lrs, alphas, _ = synth.make_batch(5, 2, 4, 16, 4)
+    x, a = util.dev(lrs), util.dev(alphas)
+    cot = util.dev(np.random.Generator(np.random.PCG64(3)).standard_normal((2, 1, 48, 48)).astype(np.float32))
+    grads = {}
+    for name, prec, tp in (("bf16", "bf16", "bf16"), ("fp32", "fp32", "fp32"), ("lazy", "bf16", None)):
+        m = _fresh_model(precision=prec)
+        m.train_precision = tp
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            from DeepNetworks.HRNet import _HRNetLazyTrainFunction
+            _HRNetLazyTrainFunction._warned = False
+            (m(x, a) * cot).sum().backward()
+        warned = any(issubclass(i.category, RuntimeWarning) for i in w)
+        assert warned == (tp is None), name
+        grads[name] = [p.grad.clone() for p in m.parameters()]
+    # train_precision None with precision "bf16" keeps the lazy fp32 recompute: its gradients are the fp32 path's, bit for bit
+    for g0, g1 in zip(grads["lazy"], grads["fp32"]):
+        assert torch.equal(g0, g1)
+    # train_precision "bf16" is a different (bf16) computation, close to fp32 (the decoder's deconv weight gradient)
+    names = [k for k, _ in m.named_parameters()]
+    k = names.index("decode.deconv.0.weight")
+    e = _rel_l2(grads["bf16"][k].cpu().numpy(), grads["fp32"][k].cpu().numpy())
+    print(f"train_precision bf16 vs fp32, decode.deconv.0.weight gradient: relative L2 {e:.2e}")
+    assert not torch.equal(grads["bf16"][k], grads["fp32"][k])
+    assert e <= 1e-1                                                    # measured 4.9e-2 (PReLU flips, see _BOUNDS)
+
+
+def test_train_and_eval_blobs_do_not_evict_each_other():
+    from hrnet_hip import binding
+    lrs, alphas, _ = synth.make_batch(5, 1, 4, 16, 4)
+    x, a = util.dev(lrs), util.dev(alphas)
+    m = _fresh_model(precision="bf16x3")
+    m.train_precision = "bf16"
+    calls = []
+    orig = binding.hrnet_pack
+
+    def counting(*args, **kw):
+        calls.append(args[2])
+        return orig(*args, **kw)
+
+    binding.hrnet_pack = counting
+    try:
+        for _ in range(3):
+            m.train()
+            m(x, a).sum().backward()
+            m.eval()
+            with torch.no_grad():
+                m(x, a)
+    finally:
+        binding.hrnet_pack = orig
+    assert sorted(calls) == sorted([binding.BF16, binding.BF16X3]), calls
+
+
+# ----------------------------------------------------------------------------- 9. speed
+def test_bf16_training_is_faster_than_bf16x3():
+    """HRNet training forward + backward at B = 32, V = 32, 64 x 64: bf16 <= 0.75 x bf16x3 (device events, after warm-up)."""
+    B, V, S = 32, 32, 64
+    lrs, alphas = synth.fast_batch(4, B, V, S)
+    x, a = util.dev(lrs), util.dev(alphas)
+    cot = torch.randn((B, 1, 3 * S, 3 * S), generator=torch.Generator().manual_seed(5)).cuda()
+    ms = {}
+    models = {}
+    for prec in ("bf16x3", "bf16"):
+        m = _fresh_model(precision="fp32", slopes=None)
+        m.train_precision = prec
+        models[prec] = m
+    for prec, m in models.items():              # warm-up
+        for _ in range(2):
+            (m(x, a) * cot).sum().backward()
+    torch.cuda.synchronize()
+    for prec in ("bf16x3", "bf16", "bf16x3", "bf16"):
+        m = models[prec]
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(5):
+            (m(x, a) * cot).sum().backward()
+        t1.record()
+        t1.synchronize()
+        ms.setdefault(prec, []).append(t0.elapsed_time(t1) / 5)
+    r = min(ms["bf16"]) / min(ms["bf16x3"])
+    print(f"HRNet fwd+bwd B={B} V={V} {S}x{S}: bf16 {ms['bf16']} ms, bf16x3 {ms['bf16x3']} ms, ratio {r:.3f}")
+    assert r <= 0.75, ms

@@ -5,7 +5,10 @@
     loss = -cPSNR(srs_shifted, hrs, mask) + lambda mean(shifts)^2; loss.backward(); optimizer.step()
 
 at the reference's training shape (config/config.json: batch 32, up to 32 views, 64 x 64 patches) with synthetic data.
-usage: python tools/train_step_bench.py [B V S steps] [--torch-adam]
+usage: python tools/train_step_bench.py [B V S steps] [--torch-adam] [--precision P[,P...]] [--repeats R]
+
+--precision sets HRNet.train_precision (fp32, bf16x3 or bf16; default: not set, i.e. the module's default rules).  With several
+precisions, one model per precision is built and their timing rounds alternate, R rounds each (--repeats, default 1).
 """
 import os
 import sys
@@ -38,9 +41,27 @@ def get_loss_cpsnr(srs, hrs, hr_maps):                        # train.py:66-87
     return -10 * torch.log10(torch.sum(hr_maps * (srs + bright.view(-1, 1, 1) - hrs) ** 2, dim=(1, 2)) / nclear)
 
 
+def _options(argv):
+    pos, opts, i = [], {}, 0
+    while i < len(argv):
+        if argv[i] in ("--precision", "--repeats"):
+            opts[argv[i]] = argv[i + 1]
+            i += 2
+        else:
+            if not argv[i].startswith("--"):
+                pos.append(argv[i])
+            i += 1
+    return pos, opts
+
+
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    args, opts = _options(sys.argv[1:])
     B, V, S, steps = (int(a) for a in args[:4]) if len(args) >= 4 else (32, 32, 64, 5)
+    precs = opts["--precision"].split(",") if "--precision" in opts else [None]
+    repeats = int(opts.get("--repeats", 1))
+    for p in precs:
+        if p not in (None, "fp32", "bf16x3", "bf16"):
+            raise SystemExit(f"--precision: fp32, bf16x3 or bf16 (got {p!r})")
     dev = torch.device("cuda:0")
     lrs, alphas = synth.fast_batch(3, B, V, S)
     rng = np.random.Generator(np.random.PCG64(1))
@@ -48,16 +69,20 @@ def main():
     maps = torch.ones((B, 3 * S, 3 * S), device=dev)
     maps[:, :3] = 0; maps[:, -3:] = 0; maps[:, :, :3] = 0; maps[:, :, -3:] = 0
     x, a = torch.from_numpy(lrs).to(dev), torch.from_numpy(alphas).to(dev)
-    fusion = HRNet({k: dict(v) for k, v in weights.HRNET_CONFIG.items()})
-    fusion.load_state_dict(weights.to_torch_state(weights.hrnet_state(1234)))
-    regis = ShiftNet()
-    regis.load_state_dict(weights.to_torch_state(weights.shiftnet_state(4321)))
-    fusion, regis = fusion.to(dev).train(), regis.to(dev).train()
-    params = list(fusion.parameters()) + list(regis.parameters())
-    opt = torch.optim.Adam(params, lr=1e-4) if "--torch-adam" in sys.argv else FusedAdam(params, lr=1e-4)
     off = (3 * S - 128) // 2
 
-    def step():
+    def setup(prec):
+        fusion = HRNet({k: dict(v) for k, v in weights.HRNET_CONFIG.items()})
+        fusion.load_state_dict(weights.to_torch_state(weights.hrnet_state(1234)))
+        fusion.train_precision = prec
+        regis = ShiftNet()
+        regis.load_state_dict(weights.to_torch_state(weights.shiftnet_state(4321)))
+        fusion, regis = fusion.to(dev).train(), regis.to(dev).train()
+        params = list(fusion.parameters()) + list(regis.parameters())
+        opt = torch.optim.Adam(params, lr=1e-4) if "--torch-adam" in sys.argv else FusedAdam(params, lr=1e-4)
+        return fusion, regis, opt
+
+    def step(fusion, regis, opt):
         opt.zero_grad()
         srs = fusion(x, a)
         shifts = register_batch(regis, srs[:, :, off:off + 128, off:off + 128], hrs[:, off:off + 128, off:off + 128].reshape(-1, 1, 128, 128))
@@ -68,16 +93,27 @@ def main():
         opt.step()
         return loss
 
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    t0 = time.time()
-    for _ in range(steps):
-        loss = step()
-    torch.cuda.synchronize()
-    dt = (time.time() - t0) / steps
-    print(f"train step B={B} V={V} S={S}: {dt * 1e3:.1f} ms/step ({B / dt:.0f} samples/s), loss {float(loss.detach()):.3f}, "
-          f"peak memory {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB, optimiser {type(opt).__name__}")
+    runs = {p: setup(p) for p in precs}
+    for r in runs.values():
+        for _ in range(2):
+            step(*r)
+    times = {p: [] for p in precs}
+    for _ in range(repeats):
+        for p, r in runs.items():
+            torch.cuda.synchronize()
+            t0 = time.time()
+            for _ in range(steps):
+                loss = step(*r)
+            torch.cuda.synchronize()
+            dt = (time.time() - t0) / steps
+            times[p].append(dt)
+            print(f"train step B={B} V={V} S={S} train_precision={p}: {dt * 1e3:.1f} ms/step ({B / dt:.0f} samples/s, {1 / dt:.2f} steps/s), "
+                  f"loss {float(loss.detach()):.3f}, peak memory {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB, "
+                  f"optimiser {type(r[2]).__name__}")
+    if repeats > 1 or len(precs) > 1:
+        for p, t in times.items():
+            ms = np.array(t) * 1e3
+            print(f"summary train_precision={p}: median {np.median(ms):.1f} ms/step, min {ms.min():.1f}, max {ms.max():.1f} over {len(ms)} rounds")
 
 
 if __name__ == "__main__":
