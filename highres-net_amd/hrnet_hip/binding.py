@@ -105,6 +105,11 @@ SIGNATURES = {
                                               _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_shiftnet_backward": (_c.c_int, [_c.POINTER(ShiftnetParams), _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
                                          _c.POINTER(ShiftnetParams), _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_shiftnet_train_workspace_bytes_dt": (_c.c_size_t, [_c.c_int, _c.c_int]),
+    "hrn_shiftnet_forward_train_dt": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(ShiftnetParams), _c.c_void_p, _c.c_int, _c.c_float,
+                                                 _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_shiftnet_backward_dt": (_c.c_int, [_c.POINTER(ShiftnetParams), _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                            _c.POINTER(ShiftnetParams), _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_adam_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_float, _c.c_float, _c.c_float,
                                  _c.c_float, _c.c_float, _c.c_int, _c.c_void_p]),
     "hrn_lanczos_kernel": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p]),
@@ -435,25 +440,33 @@ def _check_shiftnet_input(x, dropout_mask):
     return _ptr(dropout_mask), dropout_mask
 
 
-def shiftnet_forward_train(packed, named, x, momentum=0.1, dropout_mask=None):
-    """Train-mode forward that keeps its intermediates: returns (theta (B,2), train_ws)."""
+def shiftnet_forward_train(packed, named, x, momentum=0.1, dropout_mask=None, dtype=F32):
+    """Train-mode forward that keeps its intermediates: returns (theta (B,2), train_ws).  dtype: storage of the workspace's activations,
+    F32 (hrn_shiftnet_forward_train) or BF16 (hrn_shiftnet_forward_train_dt); `packed` is the fp32 blob in both."""
     lib = load_library()
     x = _dev_f32(x, "x")
     mptr, dropout_mask = _check_shiftnet_input(x, dropout_mask)
     B = x.shape[0]
     keep = []
     P = _shiftnet_struct(named, keep, True)        # (fc1.weight is read in place by the kernel: not part of `packed`)
-    nbytes = lib.hrn_shiftnet_train_workspace_bytes(B)
+    nbytes = lib.hrn_shiftnet_train_workspace_bytes(B) if dtype == F32 else lib.hrn_shiftnet_train_workspace_bytes_dt(int(dtype), B)
+    if nbytes == 0:
+        raise ValueError(f"ShiftNet training supports dtype F32 ({F32}) or BF16 ({BF16}); got {dtype}")
     tws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     theta = torch.empty((B, 2), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _check(lib.hrn_shiftnet_forward_train(_ptr(packed), ctypes.byref(P), _ptr(x), B, float(momentum), mptr, _ptr(theta),
-                                              _ptr(tws), nbytes, _stream()), "hrn_shiftnet_forward_train")
+        if dtype == F32:
+            _check(lib.hrn_shiftnet_forward_train(_ptr(packed), ctypes.byref(P), _ptr(x), B, float(momentum), mptr, _ptr(theta),
+                                                  _ptr(tws), nbytes, _stream()), "hrn_shiftnet_forward_train")
+        else:
+            _check(lib.hrn_shiftnet_forward_train_dt(_ptr(packed), int(dtype), ctypes.byref(P), _ptr(x), B, float(momentum), mptr,
+                                                     _ptr(theta), _ptr(tws), nbytes, _stream()), "hrn_shiftnet_forward_train_dt")
     return theta, tws
 
 
-def shiftnet_backward(named, named_grads, x, dropout_mask, d_theta, tws, need_input_grad=True):
-    """Accumulates the parameter gradients into named_grads (parameter keys only); returns d_x (B,2,128,128) or None."""
+def shiftnet_backward(named, named_grads, x, dropout_mask, d_theta, tws, need_input_grad=True, dtype=F32):
+    """Accumulates the parameter gradients into named_grads (parameter keys only); returns d_x (B,2,128,128) or None.  dtype: the
+    forward's (the workspace `tws` it filled)."""
     lib = load_library()
     x = _dev_f32(x, "x")
     d_theta = _dev_f32(d_theta, "d_theta")
@@ -467,9 +480,14 @@ def shiftnet_backward(named, named_grads, x, dropout_mask, d_theta, tws, need_in
     G = _shiftnet_struct(gfull, keep, True)
     d_x = torch.empty_like(x) if need_input_grad else None
     with torch.cuda.device(x.device):
-        _check(lib.hrn_shiftnet_backward(ctypes.byref(P), _ptr(x), B, mptr, _ptr(d_theta), ctypes.byref(G),
-                                         _ptr(d_x) if need_input_grad else None, _ptr(tws), tws.numel(), _stream()),
-               "hrn_shiftnet_backward")
+        if dtype == F32:
+            _check(lib.hrn_shiftnet_backward(ctypes.byref(P), _ptr(x), B, mptr, _ptr(d_theta), ctypes.byref(G),
+                                             _ptr(d_x) if need_input_grad else None, _ptr(tws), tws.numel(), _stream()),
+                   "hrn_shiftnet_backward")
+        else:
+            _check(lib.hrn_shiftnet_backward_dt(ctypes.byref(P), int(dtype), _ptr(x), B, mptr, _ptr(d_theta), ctypes.byref(G),
+                                                _ptr(d_x) if need_input_grad else None, _ptr(tws), tws.numel(), _stream()),
+                   "hrn_shiftnet_backward_dt")
     return d_x
 
 
@@ -787,56 +805,65 @@ def _shiftnet_named(params, buffers):
 
 @torch.library.custom_op("hrnet_hip::shiftnet_forward_train", mutates_args=(), device_types="cuda")
 def _op_shiftnet_forward_train(packed: torch.Tensor, x: torch.Tensor, params: Sequence[torch.Tensor], bn_running: Sequence[torch.Tensor],
-                               momentum: float, dropout_mask: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, List[torch.Tensor]]:
+                               momentum: float, dropout_mask: Optional[torch.Tensor],
+                               dtype: int = 0) -> Tuple[torch.Tensor, torch.Tensor, List[torch.Tensor]]:
     """`shifts = regis_model(pairs)` in training (train.py:40): batch-statistics BatchNorm, the given dropout keep-mask; keeps each layer's
     pre-BatchNorm tensor and statistics in `tws` for the backward.  Functional (an op with an autograd formula must be): the updated
-    running statistics come back as new tensors, in SHIFTNET_BUFFER_NAMES order, and the module copies them into its buffers."""
+    running statistics come back as new tensors, in SHIFTNET_BUFFER_NAMES order, and the module copies them into its buffers.  dtype:
+    the storage of the kept activations and gradients, fp32 (0, the default) or bf16 (1); `packed` is the fp32 blob in both."""
     new_running = [b.clone() for b in bn_running]
-    theta, tws = shiftnet_forward_train(packed, _shiftnet_named(params, new_running), x, momentum=momentum, dropout_mask=dropout_mask)
+    theta, tws = shiftnet_forward_train(packed, _shiftnet_named(params, new_running), x, momentum=momentum, dropout_mask=dropout_mask,
+                                        dtype=dtype)
     return theta, tws, new_running
 
 
 @_op_shiftnet_forward_train.register_fake
-def _(packed, x, params, bn_running, momentum, dropout_mask):
-    nbytes = load_library().hrn_shiftnet_train_workspace_bytes(x.shape[0])
+def _(packed, x, params, bn_running, momentum, dropout_mask, dtype=0):
+    nbytes = load_library().hrn_shiftnet_train_workspace_bytes_dt(dtype, x.shape[0])
     return x.new_empty((x.shape[0], 2), dtype=torch.float32), x.new_empty((nbytes,), dtype=torch.uint8), [b.new_empty(b.shape) for b in bn_running]
 
 
 @torch.library.custom_op("hrnet_hip::shiftnet_backward", mutates_args=("tws",), device_types="cuda")  # (tws also holds the backward's scratch buffers)
 def _op_shiftnet_backward(params: Sequence[torch.Tensor], x: torch.Tensor,
                           dropout_mask: Optional[torch.Tensor], d_theta: torch.Tensor, tws: torch.Tensor,
-                          need_input_grad: bool) -> Tuple[List[torch.Tensor], torch.Tensor]:
+                          need_input_grad: bool, dtype: int = 0) -> Tuple[List[torch.Tensor], torch.Tensor]:
     """d_theta -> (parameter gradients in SHIFTNET_PARAM_NAMES order, d_x (empty when not needed)).  The batch statistics the backward
     needs are in `tws`; the running statistics take no part (the BatchNorm weights stand in for them in the C struct)."""
     named = dict(zip(SHIFTNET_PARAM_NAMES, params))
     for k in SHIFTNET_BUFFER_NAMES:
         named[k] = named[k.rsplit(".", 1)[0] + ".weight"]
     grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for k, p in zip(SHIFTNET_PARAM_NAMES, params)}
-    d_x = shiftnet_backward(named, grads, x, dropout_mask, d_theta.contiguous(), tws, need_input_grad=need_input_grad)
+    d_x = shiftnet_backward(named, grads, x, dropout_mask, d_theta.contiguous(), tws, need_input_grad=need_input_grad, dtype=dtype)
     return [grads[k] for k in SHIFTNET_PARAM_NAMES], (d_x if d_x is not None else x.new_empty((0,)))
 
 
 @_op_shiftnet_backward.register_fake
-def _(params, x, dropout_mask, d_theta, tws, need_input_grad):
+def _(params, x, dropout_mask, d_theta, tws, need_input_grad, dtype=0):
     return [p.new_empty(p.shape, dtype=torch.float32) for p in params], (x.new_empty(x.shape) if need_input_grad else x.new_empty((0,)))
 
 
 def _shiftnet_train_setup(ctx, inputs, output):
-    packed, x, params, bn_running, momentum, dropout_mask = inputs
+    packed, x, params, bn_running, momentum, dropout_mask = inputs[:6]
     ctx.np, ctx.has_mask = len(params), dropout_mask is not None
+    ctx.dtype = inputs[6] if len(inputs) > 6 else F32
     ctx.set_materialize_grads(False)
     ctx.save_for_backward(x, output[1], *params, *([dropout_mask] if dropout_mask is not None else []))
 
 
 def _shiftnet_train_backward(ctx, d_theta, _d_tws, _d_running):
     x, tws, *rest = ctx.saved_tensors
+    # one entry per input as the caller passed them: a trailing `dtype` equal to its default is not among them
+    tail = (None,) * (len(ctx.needs_input_grad) - 4)
     if d_theta is None:
-        return None, None, [None] * ctx.np, [None] * len(SHIFTNET_BUFFER_NAMES), None, None
+        return (None, None, [None] * ctx.np, [None] * len(SHIFTNET_BUFFER_NAMES)) + tail
     params = rest[:ctx.np]
     mask = rest[ctx.np] if ctx.has_mask else None
     need_x = ctx.needs_input_grad[1]
-    grads, d_x = torch.ops.hrnet_hip.shiftnet_backward(params, x, mask, d_theta, tws.data, need_x)      # (tws.data: see _hrnet_train_backward)
-    return None, (d_x if need_x else None), grads, [None] * len(SHIFTNET_BUFFER_NAMES), None, None
+    if ctx.dtype == F32:
+        grads, d_x = torch.ops.hrnet_hip.shiftnet_backward(params, x, mask, d_theta, tws.data, need_x)      # (tws.data: see _hrnet_train_backward)
+    else:
+        grads, d_x = torch.ops.hrnet_hip.shiftnet_backward(params, x, mask, d_theta, tws.data, need_x, ctx.dtype)
+    return (None, (d_x if need_x else None), grads, [None] * len(SHIFTNET_BUFFER_NAMES)) + tail
 
 
 _op_shiftnet_forward_train.register_autograd(_shiftnet_train_backward, setup_context=_shiftnet_train_setup)

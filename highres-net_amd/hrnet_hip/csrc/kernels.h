@@ -44,17 +44,28 @@ int hrn_launch_loss_backward(const float* srs, const float* hrs, const float* ma
 int hrn_launch_shift_cpsnr(const float* srs, const float* hrs, const float* maps, int B, int S, int border, int clip,
                            double* scores, float* out, hipStream_t stream);
 
-// ---- shiftnet.hip
+// ---- shiftnet.hip.  dt: storage of the activation tensors behind the `float*` arguments x / out / y - HRN_F32 (default) or HRN_BF16,
+// one bf16 plane (ShiftNet's bf16 training mode); statistics, scale / shift and fc1's input xr are f32 in both
 int hrn_launch_bn_stats(const float* x, size_t npix, int C, const float* gamma, const float* beta, float eps,
                         float* scale, float* shift, float* running_mean, float* running_var, float momentum,
-                        double* partial, int partial_blocks, hipStream_t stream);
+                        double* partial, int partial_blocks, hipStream_t stream, int dt = HRN_F32);
 int hrn_launch_bn_fold(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
                        const float* conv_bias, float* scale, float* shift, int C, hipStream_t stream);
 int hrn_launch_bn_act_pool(const float* x, const float* scale, const float* shift, float* out, int N, int H, int W, int C,
-                           int pool, hipStream_t stream);
+                           int pool, hipStream_t stream, int dt = HRN_F32);
 // fc1: xr = the input in the reference's flatten order (hrn_launch_fc_to_ref: from the NHWC activation, dropout folded in), w = the raw
 // fc1.weight (1024, 32768), partial = hrn_fc1_partial_bytes() of scratch
-int hrn_launch_fc_to_ref(const float* y, const unsigned char* mask, float* xr, int B, hipStream_t stream);
+int hrn_launch_fc_to_ref(const float* y, const unsigned char* mask, float* xr, int B, hipStream_t stream, int dt = HRN_F32);
 size_t hrn_fc1_partial_bytes(void);
 int hrn_launch_fc1(const float* xr, const float* w, const float* b, float* y, int B, float* partial, hipStream_t stream);
 int hrn_launch_fc2(const float* y, const float* w, float* theta, int B, hipStream_t stream);
+// ---- shiftnet_bwd.hip: the backward's own passes, launchable alone (kernel_test.hip).  dt as above (HRN_F32 or HRN_BF16).
+// BatchNorm (+ ReLU, + MaxPool2d(2) when pool) backward of one layer: x = the pre-BatchNorm tensor [N][H][W][C], dy = the gradient of
+// the layer's output [N][H/p][W/p][C], stats = {mean, invstd, scale, shift} x 128 floats; writes dx [N][H][W][C], accumulates
+// dgamma / dbeta.  partial: SN_PARTIAL_BLOCKS x 128 x 2 doubles, sums: 128 x 2 doubles.
+int hrn_launch_sn_bn_bwd(const float* x, const float* dy, const float* stats, const float* gamma, float* dx, float* dgamma, float* dbeta,
+                         int N, int H, int W, int C, int pool, double* partial, double* sums, hipStream_t s, int dt = HRN_F32);
+// the stem's (2 -> 64, ShiftNet.py:17) input gradient: g [M][H][W][64] (dt), w the raw weights (64, 2, 3, 3) -> din [M][2][H][W] f32
+int hrn_launch_sn_stem_dgrad(const float* g, const float* w, float* din, int M, int H, int W, hipStream_t s, int dt = HRN_F32);
+// dy [B][16*16][128] (dt) = the gradient of fc1's input dxr (B, 32768) f32 in the reference's flatten order, dropout mask applied
+int hrn_launch_fc_from_ref(const float* dxr, const unsigned char* mask, float* dy, int B, hipStream_t s, int dt = HRN_F32);

@@ -7,25 +7,55 @@
 namespace {
 
 // ---- BatchNorm2d batch statistics (train mode): deterministic two-stage reduction in fp64
-// stage 1: partial[blk][c] = (sum, sumsq) over a contiguous slice of pixels
-__global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ x, size_t npix, int C, double* __restrict__ partial) {
-    __shared__ double red[2][256];
-    const int groups = 256 / C;                 // C = 64 -> 4 pixel groups, C = 128 -> 2
-    const int c = threadIdx.x % C, g = threadIdx.x / C;
-    const size_t per_blk = (npix + gridDim.x - 1) / gridDim.x;
-    const size_t p0 = (size_t)blockIdx.x * per_blk;
-    const size_t p1 = p0 + per_blk < npix ? p0 + per_blk : npix;
-    double s = 0.0, ss = 0.0;
-    for (size_t p = p0 + g; p < p1; p += groups) {
-        const double v = (double)x[p * C + c];
-        s += v; ss += v * v;
-    }
-    red[0][threadIdx.x] = s; red[1][threadIdx.x] = ss;
-    __syncthreads();
-    if (g == 0) {
-        for (int k = 1; k < groups; ++k) { s += red[0][k * C + c]; ss += red[1][k * C + c]; }
-        partial[((size_t)blockIdx.x * C + c) * 2 + 0] = s;
-        partial[((size_t)blockIdx.x * C + c) * 2 + 1] = ss;
+// stage 1: partial[blk][c] = (sum, sumsq) over a contiguous slice of pixels.  ST: storage of x (HRN_F32, or HRN_BF16 in the bf16
+// training mode: the statistics are those of the stored bf16 values, which bn_act_pool_kernel then normalises).  The bf16 instance reads
+// 4 channels (8 bytes) per thread and load; the f32 instance is the original one-channel-per-thread pass.
+template <int ST>
+__global__ __launch_bounds__(256) void bn_partial_kernel(const void* __restrict__ x, size_t npix, int C, double* __restrict__ partial) {
+    if constexpr (ST == HRN_BF16) {
+        __shared__ double red4[2][4][256];
+        const int c4n = C / 4, groups = 256 / c4n;           // C = 64 -> 16 pixel groups, C = 128 -> 8
+        const int c = (threadIdx.x % c4n) * 4, g = threadIdx.x / c4n;
+        const size_t per_blk = (npix + gridDim.x - 1) / gridDim.x;
+        const size_t p0 = (size_t)blockIdx.x * per_blk;
+        const size_t p1 = p0 + per_blk < npix ? p0 + per_blk : npix;
+        double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
+        for (size_t p = p0 + g; p < p1; p += groups) {
+            const f32x4 v = load4<HRN_BF16>(x, p * C + c);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const double d = (double)v[j]; s[j] += d; ss[j] += d * d; }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { red4[0][j][threadIdx.x] = s[j]; red4[1][j][threadIdx.x] = ss[j]; }
+        __syncthreads();
+        if (g == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                double a = s[j], b = ss[j];
+                for (int k = 1; k < groups; ++k) { a += red4[0][j][k * c4n + threadIdx.x]; b += red4[1][j][k * c4n + threadIdx.x]; }
+                partial[((size_t)blockIdx.x * C + c + j) * 2 + 0] = a;
+                partial[((size_t)blockIdx.x * C + c + j) * 2 + 1] = b;
+            }
+        }
+    } else {
+        __shared__ double red[2][256];
+        const int groups = 256 / C;                 // C = 64 -> 4 pixel groups, C = 128 -> 2
+        const int c = threadIdx.x % C, g = threadIdx.x / C;
+        const size_t per_blk = (npix + gridDim.x - 1) / gridDim.x;
+        const size_t p0 = (size_t)blockIdx.x * per_blk;
+        const size_t p1 = p0 + per_blk < npix ? p0 + per_blk : npix;
+        double s = 0.0, ss = 0.0;
+        for (size_t p = p0 + g; p < p1; p += groups) {
+            const double v = (double)load_elem<ST>(x, p * C + c);
+            s += v; ss += v * v;
+        }
+        red[0][threadIdx.x] = s; red[1][threadIdx.x] = ss;
+        __syncthreads();
+        if (g == 0) {
+            for (int k = 1; k < groups; ++k) { s += red[0][k * C + c]; ss += red[1][k * C + c]; }
+            partial[((size_t)blockIdx.x * C + c) * 2 + 0] = s;
+            partial[((size_t)blockIdx.x * C + c) * 2 + 1] = ss;
+        }
     }
 }
 // stage 2: mean / biased var -> scale, shift; running stats (momentum, unbiased var) updated in place when given
@@ -62,10 +92,12 @@ __global__ void bn_fold_kernel(const float* __restrict__ gamma, const float* __r
     shift[c] = beta[c] + ((conv_bias ? conv_bias[c] : 0.f) - rm[c]) * sc;
 }
 
-// ---- y = max(0, x*scale + shift), optionally followed by MaxPool2d(2).  One thread = 4 channels of one output pixel.
-template <int POOL>
-__global__ __launch_bounds__(256) void bn_act_pool_kernel(const float* __restrict__ x, const float* __restrict__ scale,
-                                                          const float* __restrict__ shift, float* __restrict__ out,
+// ---- y = max(0, x*scale + shift), optionally followed by MaxPool2d(2).  One thread = 4 channels of one output pixel.  ST: storage of
+// x and out (HRN_F32 or HRN_BF16: fp32 arithmetic, out rounded to nearest even once, after the max - rounding is monotonic, so the
+// pooled value is the rounded maximum either way)
+template <int POOL, int ST>
+__global__ __launch_bounds__(256) void bn_act_pool_kernel(const void* __restrict__ x, const float* __restrict__ scale,
+                                                          const float* __restrict__ shift, void* __restrict__ out,
                                                           int N, int H, int W, int C) {
     const int Ho = H / POOL, Wo = W / POOL, c4n = C / 4;
     const size_t total = (size_t)N * Ho * Wo * c4n;
@@ -83,7 +115,7 @@ __global__ __launch_bounds__(256) void bn_act_pool_kernel(const float* __restric
 #pragma unroll
             for (int dx = 0; dx < POOL; ++dx) {
                 const size_t ip = (n * H + (size_t)(yo * POOL + dy)) * W + (xo * POOL + dx);
-                f32x4 v = *(const f32x4*)(x + ip * C + c) * sc + sh;
+                f32x4 v = load4<ST>(x, ip * C + c) * sc + sh;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
                 if (dy == 0 && dx == 0) best = v;
@@ -92,7 +124,7 @@ __global__ __launch_bounds__(256) void bn_act_pool_kernel(const float* __restric
                     for (int j = 0; j < 4; ++j) best[j] = fmaxf(best[j], v[j]);
                 }
             }
-        *(f32x4*)(out + op * C + c) = best;
+        store4<ST>(out, op * C + c, best);
     }
 }
 
@@ -100,11 +132,6 @@ __global__ __launch_bounds__(256) void bn_act_pool_kernel(const float* __restric
 // A 32 x 1024 x 32768 GEMM whose time is ONE read of the 134 MB weight matrix.  Both operands are in the REFERENCE's flatten order
 // k = c*256 + hw: the weights are read in place (no packed copy, nothing to re-pack after an optimiser step) and the 4 MB input is
 // brought into that order - dropout folded in - by fc_to_ref_kernel (the backward wants exactly that tensor too).
-// Exact-fp32 MFMA 32x32x2: D[m = sample][n = neuron].  K is split into FC_SPLIT = 32 slices of 1,024; one wave = one (neuron block of
-// 32, slice): 1,024 waves, four per CU.  Per 32-deep super-step a lane (r, hh) loads 64 contiguous bytes of its weight row r (so every
-// row is consumed in whole 128-byte lines) and of its sample row r: k = ks + 16 hh + t feeds MFMA t of the step on both sides - the
-// order in which a product's k is visited is free.  Weights are read once: non-temporal; xr (L2 resident) by plain loads.  The
-// slices' partial sums land in `partial` [FC_SPLIT][32][1024] and fc1_finish_kernel adds them in slice order: bit-reproducible.
 // fc1 (ShiftNet.py:44,69-72): y[b][j] = sum_k x[b][k] w[j][k], K = 32,768, 1,024 neurons, <= 32 samples per pass: 134 MB of weights read
 // once, nothing else of size: an HBM-bound kernel.  Round 2's version loaded the MFMA operand layout straight from global memory - lane r
 // = weight row r, 16 bytes per lane: 64 scattered 16-byte requests per instruction - and stayed at 1.8 TB/s whatever its depth.  Here the
@@ -182,14 +209,16 @@ __global__ __launch_bounds__(256) void fc1_finish_kernel(const float* __restrict
 }
 
 // xr[b][c*256 + hw] = y[b][hw*128 + c] * (mask ? 2 * mask[b][c*256 + hw] : 1): the fc1 input in the reference's flatten order, the
-// train-mode dropout (p = 0.5, kept activations x 2) folded in.  Through an LDS tile so that both sides move whole lines.
-__global__ __launch_bounds__(256) void fc_to_ref_kernel(const float* __restrict__ y, const unsigned char* __restrict__ mask,
+// train-mode dropout (p = 0.5, kept activations x 2) folded in.  Through an LDS tile so that both sides move whole lines.  ST: storage of
+// y (HRN_F32, or HRN_BF16 in the bf16 training mode); xr is f32 in both (fc1 stays on the exact-fp32 MFMA path)
+template <int ST>
+__global__ __launch_bounds__(256) void fc_to_ref_kernel(const void* __restrict__ y, const unsigned char* __restrict__ mask,
                                                         float* __restrict__ xr) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z, hw0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;               // 32 x 8
 #pragma unroll
-    for (int i = 0; i < 4; ++i) tile[ty + 8 * i][tx] = y[(size_t)b * FC_K + (size_t)(hw0 + ty + 8 * i) * 128 + c0 + tx];
+    for (int i = 0; i < 4; ++i) tile[ty + 8 * i][tx] = load_elem<ST>(y, (size_t)b * FC_K + (size_t)(hw0 + ty + 8 * i) * 128 + c0 + tx);
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -220,11 +249,13 @@ __global__ __launch_bounds__(256) void fc2_kernel(const float* __restrict__ y, c
 
 int hrn_launch_bn_stats(const float* x, size_t npix, int C, const float* gamma, const float* beta, float eps,
                         float* scale, float* shift, float* running_mean, float* running_var, float momentum,
-                        double* partial, int partial_blocks, hipStream_t stream) {
+                        double* partial, int partial_blocks, hipStream_t stream, int dt) {
     HRN_CHECK(C == 64 || C == 128, -2, "bn_stats: unsupported channel count %d", C);
     HRN_CHECK(partial_blocks > 0, -2, "bn_stats: no partial buffer");
-    HrnProfScope prof("bn_stats", 0.0, (double)npix * C * 4, stream);
-    hipLaunchKernelGGL(bn_partial_kernel, dim3(partial_blocks), dim3(256), 0, stream, x, npix, C, partial);
+    HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16, -2, "bn_stats: unsupported dtype %d", dt);
+    HrnProfScope prof("bn_stats", 0.0, (double)npix * C * hrn_esize(dt), stream);
+    if (dt == HRN_BF16) hipLaunchKernelGGL(bn_partial_kernel<HRN_BF16>, dim3(partial_blocks), dim3(256), 0, stream, (const void*)x, npix, C, partial);
+    else hipLaunchKernelGGL(bn_partial_kernel<HRN_F32>, dim3(partial_blocks), dim3(256), 0, stream, (const void*)x, npix, C, partial);
     HRN_LAUNCH_CHECK();
     hipLaunchKernelGGL(bn_finish_kernel, dim3(1), dim3(1024), 0, stream, partial, partial_blocks, npix, C, gamma, beta, eps,
                        scale, shift, running_mean, running_var, momentum);
@@ -240,21 +271,31 @@ int hrn_launch_bn_fold(const float* gamma, const float* beta, const float* rm, c
 }
 
 int hrn_launch_bn_act_pool(const float* x, const float* scale, const float* shift, float* out, int N, int H, int W, int C,
-                           int pool, hipStream_t stream) {
+                           int pool, hipStream_t stream, int dt) {
     const int p = pool ? 2 : 1;
     HRN_CHECK(!pool || (H % 2 == 0 && W % 2 == 0), -2, "maxpool2 needs even H, W");
+    HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16, -2, "bn_relu_pool: unsupported dtype %d", dt);
     const size_t total = (size_t)N * (H / p) * (W / p) * (C / 4);
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    HrnProfScope prof("bn_relu_pool", 0.0, (double)N * H * W * C * 4 * (1.0 + 1.0 / (p * p)), stream);
-    if (pool) hipLaunchKernelGGL(bn_act_pool_kernel<2>, dim3(blocks), dim3(256), 0, stream, x, scale, shift, out, N, H, W, C);
-    else hipLaunchKernelGGL(bn_act_pool_kernel<1>, dim3(blocks), dim3(256), 0, stream, x, scale, shift, out, N, H, W, C);
+    HrnProfScope prof("bn_relu_pool", 0.0, (double)N * H * W * C * hrn_esize(dt) * (1.0 + 1.0 / (p * p)), stream);
+    const void* xv = x;
+    void* ov = out;
+    if (dt == HRN_BF16) {
+        if (pool) hipLaunchKernelGGL((bn_act_pool_kernel<2, HRN_BF16>), dim3(blocks), dim3(256), 0, stream, xv, scale, shift, ov, N, H, W, C);
+        else hipLaunchKernelGGL((bn_act_pool_kernel<1, HRN_BF16>), dim3(blocks), dim3(256), 0, stream, xv, scale, shift, ov, N, H, W, C);
+    } else {
+        if (pool) hipLaunchKernelGGL((bn_act_pool_kernel<2, HRN_F32>), dim3(blocks), dim3(256), 0, stream, xv, scale, shift, ov, N, H, W, C);
+        else hipLaunchKernelGGL((bn_act_pool_kernel<1, HRN_F32>), dim3(blocks), dim3(256), 0, stream, xv, scale, shift, ov, N, H, W, C);
+    }
     HRN_LAUNCH_CHECK();
     return 0;
 }
 
-int hrn_launch_fc_to_ref(const float* y, const unsigned char* mask, float* xr, int B, hipStream_t stream) {
-    HrnProfScope prof("fc_to_ref", 0.0, (double)B * FC_K * 8, stream);
-    hipLaunchKernelGGL(fc_to_ref_kernel, dim3(256 / 32, 128 / 32, B), dim3(256), 0, stream, y, mask, xr);
+int hrn_launch_fc_to_ref(const float* y, const unsigned char* mask, float* xr, int B, hipStream_t stream, int dt) {
+    HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16, -2, "fc_to_ref: unsupported dtype %d", dt);
+    HrnProfScope prof("fc_to_ref", 0.0, (double)B * FC_K * (4 + hrn_esize(dt)), stream);
+    if (dt == HRN_BF16) hipLaunchKernelGGL(fc_to_ref_kernel<HRN_BF16>, dim3(256 / 32, 128 / 32, B), dim3(256), 0, stream, (const void*)y, mask, xr);
+    else hipLaunchKernelGGL(fc_to_ref_kernel<HRN_F32>, dim3(256 / 32, 128 / 32, B), dim3(256), 0, stream, (const void*)y, mask, xr);
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -269,6 +310,7 @@ int hrn_launch_fc1(const float* xr, const float* w, const float* b, float* y, in
             HrnProfScope prof("fc1", 2.0 * nb * 1024 * 32768, 1024.0 * 32768 * 4 + (double)nb * 32768 * 4, stream);
             { const int rc_lds = hrn_allow_lds((const void*)fc1_mfma_kernel, FC_LDS_BYTES); if (rc_lds) return rc_lds; }
             hipLaunchKernelGGL(fc1_mfma_kernel, dim3(32 * FC_SLICES), dim3(256), FC_LDS_BYTES, stream, xr + (size_t)b0 * FC_K, w, partial, nb);
+            HRN_LAUNCH_CHECK();
         }
         hipLaunchKernelGGL(fc1_finish_kernel, dim3((nb * 1024 + 255) / 256), dim3(256), 0, stream, (const float*)partial, b, y + (size_t)b0 * 1024, nb);
         HRN_LAUNCH_CHECK();

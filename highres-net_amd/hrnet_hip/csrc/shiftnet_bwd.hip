@@ -1,4 +1,4 @@
-// ShiftNet training path (fp32): train-mode forward that keeps every layer's tensors, and the backward
+// ShiftNet training path (fp32 or bf16 storage): train-mode forward that keeps every layer's tensors, and the backward
 // (src/DeepNetworks/ShiftNet.py:16-75; `shifts = register_batch(regis_model, ...)` ... `loss.backward()`, train.py:176-190).
 //
 // Forward per layer i (ShiftNet.py:16-41): xpre_i = conv_i(ypost_{i-1});  v = BN_train(xpre_i);  ypost_i = [MaxPool2](ReLU(v)).
@@ -11,6 +11,12 @@
 //            then the per-plane mean subtraction's own backward (g - mean(g))
 // Tail (ShiftNet.py:43-47, :69-74): theta = fc2(ReLU(fc1(dropout(flatten)))) with the reference's (C, H, W) flatten order.
 // All reductions are two-stage with a fixed order (deterministic).
+//
+// bf16 mode (HRN_DTYPE_BF16): every activation and activation gradient of the workspace - xpre, ypost, ga, gb - is ONE bf16 plane
+// (stores round to nearest even); the convolutions, their data and weight gradients run on the bf16 kernels of HRNet's bf16 training
+// (conv3x3_r64 / conv3x3_v6, conv_wgrad_x3_kernel<false>), one bf16 MFMA per product with fp32 accumulation, from conv weights packed
+// into the workspace each step.  The BatchNorm passes read and write bf16 with fp32 arithmetic and f64 sums; the input pairs, the
+// per-plane means, fc1 / fc2 (fc_to_ref / fc_from_ref convert at their edge), parameters and their gradients stay f32.
 #include "../../../include/hrnet_hip.h"
 #include "kernels.h"
 #include "backward.h"
@@ -37,19 +43,21 @@ __global__ __launch_bounds__(1024) void bn_save_stats_kernel(const double* __res
     invstd[c] = 1.0f / sqrtf((float)var + eps);
 }
 
-// d v for the 4 channels c..c+3 of output pixel `op` at its POOL x POOL input positions; returns x values too
-template <int POOL>
-__device__ __forceinline__ void bn_dv(const float* __restrict__ x, const float* __restrict__ dy, const f32x4 sc, const f32x4 sh, size_t n,
+// d v for the 4 channels c..c+3 of output pixel `op` at its POOL x POOL input positions; returns x values too.  ST: storage of x and dy
+// (HRN_F32 or HRN_BF16).  The window's routing recomputes v = x * scale + shift from the same stored values and with the same
+// arithmetic as bn_act_pool_kernel, so it picks the position the forward's maximum came from (the first in row-major order on ties).
+template <int POOL, int ST>
+__device__ __forceinline__ void bn_dv(const void* __restrict__ x, const void* __restrict__ dy, const f32x4 sc, const f32x4 sh, size_t n,
                                       int yo, int xo, int H, int W, int C, int c, size_t op, f32x4 (&xv)[POOL * POOL],
                                       f32x4 (&dv)[POOL * POOL]) {
-    const f32x4 g = *(const f32x4*)(dy + op * C + c);
+    const f32x4 g = load4<ST>(dy, op * C + c);
     f32x4 best;
     int arg[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int k = 0; k < POOL * POOL; ++k) {
         const int dyy = k / POOL, dxx = k % POOL;
         const size_t ip = (n * H + (size_t)(yo * POOL + dyy)) * W + (xo * POOL + dxx);
-        xv[k] = *(const f32x4*)(x + ip * C + c);
+        xv[k] = load4<ST>(x, ip * C + c);
         f32x4 v = xv[k] * sc + sh;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -64,8 +72,8 @@ __device__ __forceinline__ void bn_dv(const float* __restrict__ x, const float* 
 }
 
 // partial[blk][c] = (sum d v, sum d v * xhat)
-template <int POOL>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+template <int POOL, int ST>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const void* __restrict__ x, const void* __restrict__ dy,
                                                             const float* __restrict__ stats, int N, int H, int W, int C,
                                                             double* __restrict__ partial) {
     __shared__ double red[2][4][256];
@@ -80,7 +88,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
         const int xo = (int)(op % Wo), yo = (int)((op / Wo) % Ho);
         const size_t n = op / ((size_t)Wo * Ho);
         f32x4 xv[POOL * POOL], dv[POOL * POOL];
-        bn_dv<POOL>(x, dy, sc, sh, n, yo, xo, H, W, C, c, op, xv, dv);
+        bn_dv<POOL, ST>(x, dy, sc, sh, n, yo, xo, H, W, C, c, op, xv, dv);
 #pragma unroll
         for (int k = 0; k < POOL * POOL; ++k)
 #pragma unroll
@@ -113,10 +121,10 @@ __global__ __launch_bounds__(1024) void bn_bwd_finish_kernel(const double* __res
     dbeta[c] += (float)a;
     dgamma[c] += (float)b;
 }
-template <int POOL>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+template <int POOL, int ST>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const void* __restrict__ x, const void* __restrict__ dy,
                                                            const float* __restrict__ stats, const float* __restrict__ gamma,
-                                                           const double* __restrict__ sums, float* __restrict__ dx, int N, int H, int W,
+                                                           const double* __restrict__ sums, void* __restrict__ dx, int N, int H, int W,
                                                            int C) {
     const int c4n = C / 4;
     const int Ho = H / POOL, Wo = W / POOL;
@@ -131,7 +139,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
         const f32x4 sc = *(const f32x4*)(stats + 256 + c), sh = *(const f32x4*)(stats + 384 + c);
         const f32x4 gm = *(const f32x4*)(gamma + c);
         f32x4 xv[POOL * POOL], dv[POOL * POOL];
-        bn_dv<POOL>(x, dy, sc, sh, n, yo, xo, H, W, C, c, op, xv, dv);
+        bn_dv<POOL, ST>(x, dy, sc, sh, n, yo, xo, H, W, C, c, op, xv, dv);
 #pragma unroll
         for (int k = 0; k < POOL * POOL; ++k) {
             const int dyy = k / POOL, dxx = k % POOL;
@@ -142,14 +150,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                 const float xh = (xv[k][j] - mean[j]) * istd[j];
                 o[j] = gm[j] * istd[j] * (dv[k][j] - (float)sums[(c + j) * 2] * inv_n - xh * (float)sums[(c + j) * 2 + 1] * inv_n);
             }
-            *(f32x4*)(dx + ip * C + c) = o;
+            store4<ST>(dx, ip * C + c, o);
         }
     }
 }
 
 // ------------------------------------------------------------------------------------------------ stem data gradient
 // d in[m][c2][y][x] = sum_co sum_tap g[m][y - ky + 1][x - kx + 1][co] * w[co][c2][ky][kx]      (planes layout [m][2][H][W])
-__global__ __launch_bounds__(256) void stem_dgrad_kernel(const float* __restrict__ g, const float* __restrict__ w, float* __restrict__ din,
+// ST: storage of g (HRN_F32 or HRN_BF16); fp32 arithmetic, din f32
+template <int ST>
+__global__ __launch_bounds__(256) void stem_dgrad_kernel(const void* __restrict__ g, const float* __restrict__ w, float* __restrict__ din,
                                                          int M, int H, int W) {
     __shared__ float ws[64 * 18];
     for (int i = threadIdx.x; i < 64 * 18; i += 256) ws[i] = w[i];
@@ -165,11 +175,18 @@ __global__ __launch_bounds__(256) void stem_dgrad_kernel(const float* __restrict
             for (int kx = 0; kx < 3; ++kx) {
                 const int gy = y - ky + 1, gx = x - kx + 1;
                 if ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) {
-                    const f32x4* gp = (const f32x4*)(g + ((m * H + gy) * (size_t)W + gx) * 64);
+                    const size_t gpix = (m * H + gy) * (size_t)W + gx;
+                    const f32x4* gp = (const f32x4*)g + gpix * 16;
+                    const u32x2* gh = (const u32x2*)g + gpix * 16;
                     const int tap = ky * 3 + kx;
 #pragma unroll 4
                     for (int q = 0; q < 16; ++q) {
-                        const f32x4 gv = gp[q];
+                        f32x4 gv;
+                        if constexpr (ST == HRN_BF16) {
+                            const u32x2 u = gh[q];
+                            gv = f32x4{__uint_as_float(u[0] << 16), __uint_as_float(u[0] & 0xffff0000u), __uint_as_float(u[1] << 16),
+                                       __uint_as_float(u[1] & 0xffff0000u)};
+                        } else gv = gp[q];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const int co = 4 * q + j;
@@ -190,15 +207,16 @@ __global__ __launch_bounds__(256) void sub_plane_mean_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ fully connected tail
-// dy[b][hw*128 + c] = dxr[b][c*256 + hw] * (mask ? 2 * mask : 1)
+// dy[b][hw*128 + c] = dxr[b][c*256 + hw] * (mask ? 2 * mask : 1); ST: storage of dy (HRN_F32 or HRN_BF16)
+template <int ST>
 __global__ __launch_bounds__(256) void fc_from_ref_kernel(const float* __restrict__ dxr, const unsigned char* __restrict__ mask,
-                                                          float* __restrict__ dy, size_t total) {
+                                                          void* __restrict__ dy, size_t total) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const size_t b = i / FCK;
         const int k = (int)(i - b * FCK), hw = k >> 7, c = k & 127;
         const size_t r = b * FCK + (size_t)c * 256 + hw;
         const float v = dxr[r];
-        dy[i] = mask ? (mask[r] ? 2.f * v : 0.f) : v;
+        store_elem<ST>(dy, i, mask ? (mask[r] ? 2.f * v : 0.f) : v);
     }
 }
 // thread j: dz1[b][j] = (y1[b][j] > 0) * sum_o dtheta[b][o] w2[o][j];  dw2[o][j] += sum_b dtheta[b][o] y1[b][j];  db1[j] += sum_b dz1
@@ -300,25 +318,28 @@ __global__ __launch_bounds__(256) void fc1_bwd_x_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------ workspace
+// dt = HRN_F32: the layout the fp32 entry points have always used.  HRN_BF16: xpre / ypost / ga / gb take 2 bytes per element, and the
+// forward's bf16-packed conv weights (layers 2-8) follow the scratch.
 struct SnTrainWs {
     int hin[8], hout[8];
     size_t means, xpre[8], ypost[8], stats[8], y1, partial;
-    size_t ga, gb, xr, dxr, dz1, sums, wt, wtp, zero_bias, dxin, gmeans, fc_partial, scratch;
+    size_t ga, gb, xr, dxr, dz1, sums, wt, wtp, zero_bias, dxin, gmeans, fc_partial, scratch, wpk[8];
     size_t total;
 };
 int sn_cus() { return hrn_device_cus(); }
-SnTrainWs sn_train_ws(int B) {
+SnTrainWs sn_train_ws(int B, int dt) {
     SnTrainWs w;
     memset(&w, 0, sizeof w);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = hrn_align_up(off + bytes, 256); return o; };
+    const size_t es = (size_t)hrn_esize(dt);
     w.means = take((size_t)B * 2 * 4);
     int h = 128;
     size_t big = 0;
     for (int i = 0; i < 8; ++i) {
         w.hin[i] = h;
         w.hout[i] = SN_POOL[i] ? h / 2 : h;
-        const size_t a = (size_t)B * h * h * SN_CO[i] * 4, o = (size_t)B * w.hout[i] * w.hout[i] * SN_CO[i] * 4;
+        const size_t a = (size_t)B * h * h * SN_CO[i] * es, o = (size_t)B * w.hout[i] * w.hout[i] * SN_CO[i] * es;
         w.xpre[i] = take(a);
         w.ypost[i] = take(o);
         w.stats[i] = take(4 * 128 * 4);
@@ -334,6 +355,8 @@ SnTrainWs sn_train_ws(int B) {
     w.dxin = take((size_t)B * 2 * 128 * 128 * 4); w.gmeans = take((size_t)B * 2 * 4);
     w.fc_partial = take(hrn_fc1_partial_bytes());
     w.scratch = take(hrn_bwd_scratch_bytes(sn_cus()));
+    if (dt == HRN_BF16)
+        for (int i = 1; i < 8; ++i) w.wpk[i] = take(conv_packed_elems(SN_CI[i], SN_CO[i]) * 2);
     w.total = off;
     return w;
 }
@@ -341,62 +364,123 @@ int ew_grid(size_t n) {
     size_t g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
+bool sn_dtype_ok(int dt) { return dt == HRN_F32 || dt == HRN_BF16; }
 
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------ the backward's passes
+int hrn_launch_sn_bn_bwd(const float* x, const float* dy, const float* stats, const float* gamma, float* dx, float* dgamma, float* dbeta,
+                         int N, int H, int W, int C, int pool, double* partial, double* sums, hipStream_t s, int dt) {
+    HRN_CHECK(C == 64 || C == 128, -2, "sn_bn_bwd: unsupported channel count %d", C);
+    HRN_CHECK(sn_dtype_ok(dt), -2, "sn_bn_bwd: unsupported dtype %d", dt);
+    HRN_CHECK(!pool || (H % 2 == 0 && W % 2 == 0), -2, "sn_bn_bwd: maxpool2 needs even H, W");
+    const void *xv = x, *dyv = dy;
+    void* dxv = dx;
+#define HRN_SN_BN(P_, ST_)                                                                                                              \
+    do {                                                                                                                                \
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<P_, ST_>), dim3(SN_PARTIAL_BLOCKS), dim3(256), 0, s, xv, dyv, stats, N, H, W, C, partial); \
+        HRN_LAUNCH_CHECK();                                                                                                             \
+        hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3(1), dim3(1024), 0, s, (const double*)partial, SN_PARTIAL_BLOCKS, C, sums, dgamma, dbeta); \
+        HRN_LAUNCH_CHECK();                                                                                                             \
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<P_, ST_>), dim3(eg), dim3(256), 0, s, xv, dyv, stats, gamma, (const double*)sums, dxv, N, H, W, C); \
+        HRN_LAUNCH_CHECK();                                                                                                             \
+    } while (0)
+    const int eg = ew_grid((size_t)N * H * W * C / 4 / (pool ? 4 : 1));
+    if (dt == HRN_BF16) { if (pool) HRN_SN_BN(2, HRN_BF16); else HRN_SN_BN(1, HRN_BF16); }
+    else { if (pool) HRN_SN_BN(2, HRN_F32); else HRN_SN_BN(1, HRN_F32); }
+#undef HRN_SN_BN
+    return 0;
+}
+
+int hrn_launch_sn_stem_dgrad(const float* g, const float* w, float* din, int M, int H, int W, hipStream_t s, int dt) {
+    HRN_CHECK(sn_dtype_ok(dt), -2, "sn_stem_dgrad: unsupported dtype %d", dt);
+    const size_t npix = (size_t)M * H * W;
+    if (dt == HRN_BF16) hipLaunchKernelGGL(stem_dgrad_kernel<HRN_BF16>, dim3(ew_grid(npix)), dim3(256), 0, s, (const void*)g, w, din, M, H, W);
+    else hipLaunchKernelGGL(stem_dgrad_kernel<HRN_F32>, dim3(ew_grid(npix)), dim3(256), 0, s, (const void*)g, w, din, M, H, W);
+    HRN_LAUNCH_CHECK();
+    return 0;
+}
+
+int hrn_launch_fc_from_ref(const float* dxr, const unsigned char* mask, float* dy, int B, hipStream_t s, int dt) {
+    HRN_CHECK(sn_dtype_ok(dt), -2, "fc_from_ref: unsupported dtype %d", dt);
+    const size_t nflat = (size_t)B * FCK;
+    if (dt == HRN_BF16) hipLaunchKernelGGL(fc_from_ref_kernel<HRN_BF16>, dim3(ew_grid(nflat)), dim3(256), 0, s, dxr, mask, (void*)dy, nflat);
+    else hipLaunchKernelGGL(fc_from_ref_kernel<HRN_F32>, dim3(ew_grid(nflat)), dim3(256), 0, s, dxr, mask, (void*)dy, nflat);
+    HRN_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" {
 
-size_t hrn_shiftnet_train_workspace_bytes(int B) { return B > 0 ? sn_train_ws(B).total : 0; }
+size_t hrn_shiftnet_train_workspace_bytes_dt(int dtype, int B) { return B > 0 && sn_dtype_ok(dtype) ? sn_train_ws(B, dtype).total : 0; }
+size_t hrn_shiftnet_train_workspace_bytes(int B) { return hrn_shiftnet_train_workspace_bytes_dt(HRN_F32, B); }
 
-int hrn_shiftnet_forward_train(const void* packed, const hrn_shiftnet_params* P, const float* x, int B, float momentum,
-                               const unsigned char* dropout_mask, float* theta, void* tws, size_t tws_bytes, void* stream) {
+int hrn_shiftnet_forward_train_dt(const void* packed, int dt, const hrn_shiftnet_params* P, const float* x, int B, float momentum,
+                                  const unsigned char* dropout_mask, float* theta, void* tws, size_t tws_bytes, void* stream) {
+    HRN_CHECK(sn_dtype_ok(dt), -2, "hrn_shiftnet_forward_train: unsupported dtype %d (HRN_DTYPE_F32 or HRN_DTYPE_BF16)", dt);
     HRN_CHECK(packed && P && x && theta && tws, -2, "hrn_shiftnet_forward_train: null argument");
     HRN_CHECK(B > 0, -2, "hrn_shiftnet_forward_train: empty batch");
+    if (dt == HRN_BF16)
+        HRN_CHECK(((uintptr_t)packed & 255) == 0 && ((uintptr_t)tws & 255) == 0, -2,
+                  "hrn_shiftnet_forward_train: packed and train_ws must be 256-byte aligned");
     const SnLayout L = sn_layout();
-    const SnTrainWs T = sn_train_ws(B);
+    const SnTrainWs T = sn_train_ws(B, dt);
     HRN_CHECK(tws_bytes >= T.total, -3, "hrn_shiftnet_forward_train: workspace too small (%zu < %zu)", tws_bytes, T.total);
+    for (int i = 0; i < 8; ++i) {
+        HRN_CHECK(P->bn_g[i] && P->bn_b[i] && P->bn_rm[i] && P->bn_rv[i], -2, "hrn_shiftnet_forward_train: null BatchNorm tensor %d", i);
+        HRN_CHECK(dt != HRN_BF16 || i == 0 || P->conv_w[i], -2, "hrn_shiftnet_forward_train: params->conv_w[%d] is null (bf16 packs it)", i);
+    }
+    HRN_CHECK(P->fc1_w, -2, "hrn_shiftnet_forward_train: params->fc1_w is null (fc1.weight is read in place)");
     hipStream_t s = (hipStream_t)stream;
     float* means = (float*)at(tws, T.means);
     double* partial = (double*)at(tws, T.partial);
     const size_t plane = 128 * 128;
     int rc;
+    if (dt == HRN_BF16)        // the bf16 convolutions' weights: RNE of the live f32 parameters, this step's values
+        for (int i = 1; i < 8; ++i)
+            if ((rc = hrn_launch_conv_pack(HRN_BF16, SN_CI[i], SN_CO[i], P->conv_w[i], at(tws, T.wpk[i]), s))) return rc;
     if ((rc = hrn_launch_plane_mean(x, means, B * 2, plane, s))) return rc;                      // ShiftNet.py:58
     for (int i = 0; i < 8; ++i) {
-        HRN_CHECK(P->bn_g[i] && P->bn_b[i] && P->bn_rm[i] && P->bn_rv[i], -2, "hrn_shiftnet_forward_train: null BatchNorm tensor %d", i);
         const int h = T.hin[i], C = SN_CO[i];
         float* xp = (float*)at(tws, T.xpre[i]);
         float* yp = (float*)at(tws, T.ypost[i]);
         float* st = (float*)at(tws, T.stats[i]);
         if (i == 0) {
-            if ((rc = hrn_launch_stem(HRN_F32, x, 2 * plane, x + plane, 1, 2 * plane, means, (const float*)at(packed, L.conv_w[0]),
+            if ((rc = hrn_launch_stem(dt, x, 2 * plane, x + plane, 1, 2 * plane, means, (const float*)at(packed, L.conv_w[0]),
                                       (const float*)at(packed, L.conv_b[0]), nullptr, xp, B, h, h, s))) return rc;
         } else {
             ConvParams p = conv_base(B, h, h);
             p.in = at(tws, T.ypost[i - 1]); p.out = xp;
-            p.wpk = at(packed, L.conv_w[i]); p.bias = (const float*)at(packed, L.conv_b[i]);
-            if ((rc = hrn_launch_conv3x3(HRN_F32, SN_CI[i], C, p, s))) return rc;
+            p.wpk = dt == HRN_BF16 ? at(tws, T.wpk[i]) : at(packed, L.conv_w[i]); p.bias = (const float*)at(packed, L.conv_b[i]);
+            if ((rc = hrn_launch_conv3x3(dt, SN_CI[i], C, p, s))) return rc;
         }
         const size_t npix = (size_t)B * h * h;
         if ((rc = hrn_launch_bn_stats(xp, npix, C, P->bn_g[i], P->bn_b[i], 1e-5f, st + 256, st + 384, P->bn_rm[i], P->bn_rv[i], momentum,
-                                      partial, SN_PARTIAL_BLOCKS, s))) return rc;
+                                      partial, SN_PARTIAL_BLOCKS, s, dt))) return rc;
         hipLaunchKernelGGL(bn_save_stats_kernel, dim3(1), dim3(1024), 0, s, (const double*)partial, SN_PARTIAL_BLOCKS, npix, C, 1e-5f, st, st + 128);
         HRN_LAUNCH_CHECK();
-        if ((rc = hrn_launch_bn_act_pool(xp, st + 256, st + 384, yp, B, h, h, C, SN_POOL[i], s))) return rc;
+        if ((rc = hrn_launch_bn_act_pool(xp, st + 256, st + 384, yp, B, h, h, C, SN_POOL[i], s, dt))) return rc;
     }
     float* y1 = (float*)at(tws, T.y1);
     // fc1's input in the reference's flatten order, dropout folded in: kept in the workspace - the backward's weight gradient reads it
-    HRN_CHECK(P->fc1_w, -2, "hrn_shiftnet_forward_train: params->fc1_w is null (fc1.weight is read in place)");
     float* xr = (float*)at(tws, T.xr);
-    if ((rc = hrn_launch_fc_to_ref((const float*)at(tws, T.ypost[7]), dropout_mask, xr, B, s))) return rc;
+    if ((rc = hrn_launch_fc_to_ref((const float*)at(tws, T.ypost[7]), dropout_mask, xr, B, s, dt))) return rc;
     if ((rc = hrn_launch_fc1(xr, P->fc1_w, (const float*)at(packed, L.fc1_b), y1, B, (float*)at(tws, T.fc_partial), s))) return rc;
     return hrn_launch_fc2(y1, (const float*)at(packed, L.fc2_w), theta, B, s);
 }
 
-int hrn_shiftnet_backward(const hrn_shiftnet_params* P, const float* x, int B, const unsigned char* dropout_mask, const float* d_theta,
-                          const hrn_shiftnet_params* G, float* d_x, void* tws, size_t tws_bytes, void* stream) {
+int hrn_shiftnet_forward_train(const void* packed, const hrn_shiftnet_params* P, const float* x, int B, float momentum,
+                               const unsigned char* dropout_mask, float* theta, void* tws, size_t tws_bytes, void* stream) {
+    return hrn_shiftnet_forward_train_dt(packed, HRN_F32, P, x, B, momentum, dropout_mask, theta, tws, tws_bytes, stream);
+}
+
+int hrn_shiftnet_backward_dt(const hrn_shiftnet_params* P, int dt, const float* x, int B, const unsigned char* dropout_mask,
+                             const float* d_theta, const hrn_shiftnet_params* G, float* d_x, void* tws, size_t tws_bytes, void* stream) {
+    HRN_CHECK(sn_dtype_ok(dt), -2, "hrn_shiftnet_backward: unsupported dtype %d (HRN_DTYPE_F32 or HRN_DTYPE_BF16)", dt);
     HRN_CHECK(P && G && x && d_theta && tws, -2, "hrn_shiftnet_backward: null argument");
     HRN_CHECK(B > 0, -2, "hrn_shiftnet_backward: empty batch");
-    const SnTrainWs T = sn_train_ws(B);
+    if (dt == HRN_BF16) HRN_CHECK(((uintptr_t)tws & 255) == 0, -2, "hrn_shiftnet_backward: train_ws must be 256-byte aligned");
+    const SnTrainWs T = sn_train_ws(B, dt);
     HRN_CHECK(tws_bytes >= T.total, -3, "hrn_shiftnet_backward: workspace too small (%zu < %zu)", tws_bytes, T.total);
     hipStream_t s = (hipStream_t)stream;
     auto mut = [](const float* p) { return const_cast<float*>(p); };
@@ -413,7 +497,6 @@ int hrn_shiftnet_backward(const hrn_shiftnet_params* P, const float* x, int B, c
     HRN_HIP(hipMemsetAsync(at(tws, T.zero_bias), 0, 128 * 4, s));
     // ---- tail: theta = fc2(ReLU(fc1(dropout(flatten(y8)))))                                ShiftNet.py:69-74
     hipLaunchKernelGGL(fc2_bwd_kernel, dim3(4), dim3(256), 0, s, d_theta, (const float*)at(tws, T.y1), P->fc2_w, dz1, mut(G->fc2_w), mut(G->fc1_b), B);
-    const size_t nflat = (size_t)B * FCK;
     // (xr, the fc1 input in the reference's flatten order with the dropout folded in, was left in the workspace by the forward)
     for (int b0 = 0; b0 < B; b0 += 32)
         hipLaunchKernelGGL(fc1_bwd_w_kernel, dim3(FCK / 256, 1024 / FC1_BWD_JT), dim3(256), 0, s, (const float*)dz1 + (size_t)b0 * 1024,
@@ -422,35 +505,33 @@ int hrn_shiftnet_backward(const hrn_shiftnet_params* P, const float* x, int B, c
     for (int b0 = 0; b0 < B; b0 += 32)      // 32 samples are the MFMA's M: larger batches go in groups
         hipLaunchKernelGGL(fc1_bwd_x_kernel, dim3(FCK / 128), dim3(256), FCX_LDS_BYTES, s, (const float*)dz1 + (size_t)b0 * 1024, P->fc1_w,
                            dxr + (size_t)b0 * FCK, B - b0 < 32 ? B - b0 : 32);
-    hipLaunchKernelGGL(fc_from_ref_kernel, dim3(ew_grid(nflat)), dim3(256), 0, s, (const float*)dxr, dropout_mask, cur, nflat);
     HRN_LAUNCH_CHECK();
+    if ((rc = hrn_launch_fc_from_ref(dxr, dropout_mask, cur, B, s, dt))) return rc;
     // ---- layers 8 .. 1                                                                        ShiftNet.py:16-41, :59-67
     for (int i = 7; i >= 0; --i) {
         const int h = T.hin[i], C = SN_CO[i];
         const float* xp = (const float*)at(tws, T.xpre[i]);
         const float* st = (const float*)at(tws, T.stats[i]);
         const size_t npix = (size_t)B * h * h;
-        if (SN_POOL[i]) hipLaunchKernelGGL(bn_bwd_reduce_kernel<2>, dim3(SN_PARTIAL_BLOCKS), dim3(256), 0, s, xp, (const float*)cur, st, B, h, h, C, partial);
-        else hipLaunchKernelGGL(bn_bwd_reduce_kernel<1>, dim3(SN_PARTIAL_BLOCKS), dim3(256), 0, s, xp, (const float*)cur, st, B, h, h, C, partial);
-        hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3(1), dim3(1024), 0, s, (const double*)partial, SN_PARTIAL_BLOCKS, C, sums, mut(G->bn_g[i]), mut(G->bn_b[i]));
-        const int eg = ew_grid(npix * C / 4 / (SN_POOL[i] ? 4 : 1));
-        if (SN_POOL[i]) hipLaunchKernelGGL(bn_bwd_apply_kernel<2>, dim3(eg), dim3(256), 0, s, xp, (const float*)cur, st, P->bn_g[i], (const double*)sums, oth, B, h, h, C);
-        else hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(eg), dim3(256), 0, s, xp, (const float*)cur, st, P->bn_g[i], (const double*)sums, oth, B, h, h, C);
-        HRN_LAUNCH_CHECK();
+        if ((rc = hrn_launch_sn_bn_bwd(xp, cur, st, P->bn_g[i], oth, mut(G->bn_g[i]), mut(G->bn_b[i]), B, h, h, C, SN_POOL[i], partial, sums, s,
+                                       dt))) return rc;
         // oth = d xpre_i
-        if ((rc = hrn_launch_colsum(oth, npix, C, mut(G->conv_b[i]), sc, s))) return rc;
+        if ((rc = hrn_launch_colsum(oth, npix, C, mut(G->conv_b[i]), sc, s, dt))) return rc;
         if (i > 0) {
-            if ((rc = hrn_launch_conv_wgrad((const float*)at(tws, T.ypost[i - 1]), nullptr, 0, 0, 0, 0, oth, B, h, h, SN_CI[i], C, mut(G->conv_w[i]), sc, cus, s))) return rc;
+            const float* xin = (const float*)at(tws, T.ypost[i - 1]);
+            if (dt == HRN_BF16) rc = hrn_launch_conv_wgrad_bf16(xin, nullptr, 0, 0, 0, 0, oth, B, h, h, SN_CI[i], C, mut(G->conv_w[i]), sc, cus, s);
+            else rc = hrn_launch_conv_wgrad(xin, nullptr, 0, 0, 0, 0, oth, B, h, h, SN_CI[i], C, mut(G->conv_w[i]), sc, cus, s);
+            if (rc) return rc;
             if ((rc = hrn_conv_dgrad(SN_CI[i], C, P->conv_w[i], oth, cur, nullptr, B, h, h, (float*)at(tws, T.wt), at(tws, T.wtp),
-                                     (const float*)at(tws, T.zero_bias), s))) return rc;
+                                     (const float*)at(tws, T.zero_bias), s, dt))) return rc;
         } else {
             const size_t plane = 128 * 128;
-            if ((rc = hrn_launch_stem_wgrad_sub(x, 2 * plane, x + plane, 1, 2 * plane, (const float*)at(tws, T.means), oth, B, h, h, mut(G->conv_w[0]), sc, cus, s))) return rc;
+            if ((rc = hrn_launch_stem_wgrad_sub(x, 2 * plane, x + plane, 1, 2 * plane, (const float*)at(tws, T.means), oth, B, h, h, mut(G->conv_w[0]), sc,
+                                                cus, s, dt))) return rc;
             if (d_x) {
                 float* dxin = (float*)at(tws, T.dxin);
                 float* gm = (float*)at(tws, T.gmeans);
-                hipLaunchKernelGGL(stem_dgrad_kernel, dim3(ew_grid(npix)), dim3(256), 0, s, (const float*)oth, P->conv_w[0], dxin, B, h, h);
-                HRN_LAUNCH_CHECK();
+                if ((rc = hrn_launch_sn_stem_dgrad(oth, P->conv_w[0], dxin, B, h, h, s, dt))) return rc;
                 if ((rc = hrn_launch_plane_mean(dxin, gm, B * 2, plane, s))) return rc;
                 hipLaunchKernelGGL(sub_plane_mean_kernel, dim3(ew_grid((size_t)B * 2 * plane)), dim3(256), 0, s, (const float*)dxin, (const float*)gm, d_x, plane, (size_t)B * 2 * plane);
                 HRN_LAUNCH_CHECK();
@@ -458,6 +539,11 @@ int hrn_shiftnet_backward(const hrn_shiftnet_params* P, const float* x, int B, c
         }
     }
     return 0;
+}
+
+int hrn_shiftnet_backward(const hrn_shiftnet_params* P, const float* x, int B, const unsigned char* dropout_mask, const float* d_theta,
+                          const hrn_shiftnet_params* G, float* d_x, void* tws, size_t tws_bytes, void* stream) {
+    return hrn_shiftnet_backward_dt(P, HRN_F32, x, B, dropout_mask, d_theta, G, d_x, tws, tws_bytes, stream);
 }
 
 }  // extern "C"

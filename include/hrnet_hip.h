@@ -206,6 +206,20 @@ int hrn_shiftnet_forward_train(const void* packed, const hrn_shiftnet_params* pa
 int hrn_shiftnet_backward(const hrn_shiftnet_params* params, const float* x, int B, const unsigned char* dropout_mask,
                           const float* d_theta, const hrn_shiftnet_params* grads, float* d_x, void* train_ws,
                           size_t train_ws_bytes, void* stream);
+/* The same with a dtype: HRN_DTYPE_F32 (what the three functions above run) or HRN_DTYPE_BF16 - every activation and activation
+ * gradient of the workspace ONE bf16 plane (stores round to nearest even), the convolutions, their data and weight gradients one bf16
+ * MFMA per product with fp32 accumulation, the conv weights packed to bf16 into the workspace by the forward (from params->conv_w, which
+ * must then be set); BatchNorm statistics and every reduction in f32 / f64 as in fp32.  fc1 / fc2 and their backward, x, d_x, theta,
+ * d_theta, the running statistics, parameters and parameter gradients: f32 in both modes; `packed` is the fp32 blob of
+ * hrn_shiftnet_pack in both.  The workspace (hrn_shiftnet_train_workspace_bytes_dt of the same dtype) is smaller in bf16.  Any other
+ * dtype: 0 bytes, and -2 before any launch.  HRN_DTYPE_BF16 also wants `packed` and `train_ws` 256-byte aligned (as any hipMalloc'd
+ * block is); otherwise -2 before any launch. */
+size_t hrn_shiftnet_train_workspace_bytes_dt(int dtype, int B);
+int hrn_shiftnet_forward_train_dt(const void* packed, int dtype, const hrn_shiftnet_params* params, const float* x, int B, float momentum,
+                                  const unsigned char* dropout_mask, float* theta, void* train_ws, size_t train_ws_bytes, void* stream);
+int hrn_shiftnet_backward_dt(const hrn_shiftnet_params* params, int dtype, const float* x, int B, const unsigned char* dropout_mask,
+                             const float* d_theta, const hrn_shiftnet_params* grads, float* d_x, void* train_ws, size_t train_ws_bytes,
+                             void* stream);
 
 /* ------------------------------------------------------------------ Lanczos */
 /* dx (n) f32 -> taps (n,7) f32;  a = 3, N = 7 (the only values the reference's call sites use). */

@@ -5,10 +5,11 @@
     loss = -cPSNR(srs_shifted, hrs, mask) + lambda mean(shifts)^2; loss.backward(); optimizer.step()
 
 at the reference's training shape (config/config.json: batch 32, up to 32 views, 64 x 64 patches) with synthetic data.
-usage: python tools/train_step_bench.py [B V S steps] [--torch-adam] [--precision P[,P...]] [--repeats R]
+usage: python tools/train_step_bench.py [B V S steps] [--torch-adam] [--precision P[,P...]] [--shiftnet-precision P[,P...]] [--repeats R]
 
---precision sets HRNet.train_precision (fp32, bf16x3 or bf16; default: not set, i.e. the module's default rules).  With several
-precisions, one model per precision is built and their timing rounds alternate, R rounds each (--repeats, default 1).
+--precision sets HRNet.train_precision (fp32, bf16x3 or bf16; default: not set, i.e. the module's default rules), --shiftnet-precision
+ShiftNet.train_precision (fp32 or bf16; default: not set).  With several values, one pair of models per combination is built and their
+timing rounds alternate, R rounds each (--repeats, default 1).
 """
 import os
 import sys
@@ -44,7 +45,7 @@ def get_loss_cpsnr(srs, hrs, hr_maps):                        # train.py:66-87
 def _options(argv):
     pos, opts, i = [], {}, 0
     while i < len(argv):
-        if argv[i] in ("--precision", "--repeats"):
+        if argv[i] in ("--precision", "--shiftnet-precision", "--repeats"):
             opts[argv[i]] = argv[i + 1]
             i += 2
         else:
@@ -54,14 +55,23 @@ def _options(argv):
     return pos, opts
 
 
+def _label(key):
+    p, sp = key
+    return f"train_precision={p}" + (f" shiftnet_train_precision={sp}" if sp is not None else "")
+
+
 def main():
     args, opts = _options(sys.argv[1:])
     B, V, S, steps = (int(a) for a in args[:4]) if len(args) >= 4 else (32, 32, 64, 5)
     precs = opts["--precision"].split(",") if "--precision" in opts else [None]
+    sprecs = opts["--shiftnet-precision"].split(",") if "--shiftnet-precision" in opts else [None]
     repeats = int(opts.get("--repeats", 1))
     for p in precs:
         if p not in (None, "fp32", "bf16x3", "bf16"):
             raise SystemExit(f"--precision: fp32, bf16x3 or bf16 (got {p!r})")
+    for p in sprecs:
+        if p not in (None, "fp32", "bf16"):
+            raise SystemExit(f"--shiftnet-precision: fp32 or bf16 (got {p!r})")
     dev = torch.device("cuda:0")
     lrs, alphas = synth.fast_batch(3, B, V, S)
     rng = np.random.Generator(np.random.PCG64(1))
@@ -71,11 +81,13 @@ def main():
     x, a = torch.from_numpy(lrs).to(dev), torch.from_numpy(alphas).to(dev)
     off = (3 * S - 128) // 2
 
-    def setup(prec):
+    def setup(prec, sprec):
         fusion = HRNet({k: dict(v) for k, v in weights.HRNET_CONFIG.items()})
         fusion.load_state_dict(weights.to_torch_state(weights.hrnet_state(1234)))
         fusion.train_precision = prec
         regis = ShiftNet()
+        if sprec is not None:
+            regis.train_precision = sprec
         regis.load_state_dict(weights.to_torch_state(weights.shiftnet_state(4321)))
         fusion, regis = fusion.to(dev).train(), regis.to(dev).train()
         params = list(fusion.parameters()) + list(regis.parameters())
@@ -93,11 +105,11 @@ def main():
         opt.step()
         return loss
 
-    runs = {p: setup(p) for p in precs}
+    runs = {(p, sp): setup(p, sp) for p in precs for sp in sprecs}
     for r in runs.values():
         for _ in range(2):
             step(*r)
-    times = {p: [] for p in precs}
+    times = {k: [] for k in runs}
     for _ in range(repeats):
         for p, r in runs.items():
             torch.cuda.synchronize()
@@ -107,13 +119,13 @@ def main():
             torch.cuda.synchronize()
             dt = (time.time() - t0) / steps
             times[p].append(dt)
-            print(f"train step B={B} V={V} S={S} train_precision={p}: {dt * 1e3:.1f} ms/step ({B / dt:.0f} samples/s, {1 / dt:.2f} steps/s), "
+            print(f"train step B={B} V={V} S={S} {_label(p)}: {dt * 1e3:.1f} ms/step ({B / dt:.0f} samples/s, {1 / dt:.2f} steps/s), "
                   f"loss {float(loss.detach()):.3f}, peak memory {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB, "
                   f"optimiser {type(r[2]).__name__}")
-    if repeats > 1 or len(precs) > 1:
+    if repeats > 1 or len(runs) > 1:
         for p, t in times.items():
             ms = np.array(t) * 1e3
-            print(f"summary train_precision={p}: median {np.median(ms):.1f} ms/step, min {ms.min():.1f}, max {ms.max():.1f} over {len(ms)} rounds")
+            print(f"summary {_label(p)}: median {np.median(ms):.1f} ms/step, min {ms.min():.1f}, max {ms.max():.1f} over {len(ms)} rounds")
 
 
 if __name__ == "__main__":
