@@ -376,14 +376,15 @@ __global__ void conv_pack_x3_kernel(const float* __restrict__ w, unsigned short*
 
 }  // namespace
 
-int hrn_launch_conv3x3(int dt, int cin, int cout, const ConvParams& p, hipStream_t stream) {
+int hrn_launch_conv3x3(int dt, int cin, int cout, const ConvParams& p, hipStream_t stream, bool general_only) {
     HRN_CHECK(p.M > 0 && p.H > 0 && p.W > 0, -2, "conv3x3: empty problem M=%d H=%d W=%d", p.M, p.H, p.W);
     HRN_CHECK(!p.in_pair || (cin == 128 && p.pair_h > 0 && p.stack), -2, "conv3x3: pair input needs cin=128 and a pair descriptor");
     HRN_CHECK(p.res_mode != 2 || (p.pair_h > 0 && p.stack && cout == 128), -2, "conv3x3: res_mode 2 needs a pair descriptor and cout=128");
     HRN_CHECK(p.in_pair || p.in, -2, "conv3x3: null input");
     HRN_CHECK(p.res_mode != 3 || p.out_h > 0, -2, "conv3x3: res_mode 3 needs slot output");
+    HRN_CHECK(!(general_only && dt == HRN_BF16X3), -2, "conv3x3: bf16x3 has no general kernel");
     if (dt == HRN_BF16X3) return hrn_launch_conv3x3_v6x3(cin, cout, p, stream);      // the only kernel of this precision mode
-    if (dt == HRN_BF16 && !p.scale && !p.relu) {
+    if (dt == HRN_BF16 && !p.scale && !p.relu && !general_only) {
         // the HRNet layers in bf16: resident-weights kernel (conv3x3_r64.hip) for the encoder's 64 -> 64 layers, conv3x3_v6.hip for the
         // three layers of a fusion level.  What they decline (images beyond their 32-bit in-image offsets, > 8.3 Mpixel) runs on this
         // file's general kernel; HRN_CONV_R64=0 / HRN_CONV_V6=0 force that route (A/B timing, and the test that covers it).

@@ -1,5 +1,6 @@
-// Kernel-level hooks for the test suite (tests/test_gpu_bf16_train.py, tests/test_gpu_shiftnet_bf16.py): the training path's convolution,
-// data-gradient and weight-gradient launchers and ShiftNet's BatchNorm / stem / fc adapter passes called on their own, so that each can be checked against fp64 with inputs chosen for it.  Not part of the
+// Kernel-level hooks for the test suite (tests/test_gpu_bf16_train.py, tests/test_gpu_shiftnet_bf16.py, tests/test_gpu_kernels_fwd.py): the
+// convolution (with its whole epilogue), stem and decoder launchers, the training path's data-gradient and weight-gradient launchers and
+// ShiftNet's BatchNorm / stem / fc adapter passes called on their own, so that each can be checked against fp64 with inputs chosen for it.  Not part of the
 // public C ABI (include/hrnet_hip.h); same conventions as its entry points: asynchronous on `stream`, 0 or a negative error.
 #include <string.h>
 #include "kernels.h"
@@ -11,12 +12,20 @@ extern "C" {
 size_t hrn_kt_wgrad_scratch_bytes(void) { return hrn_bwd_scratch_bytes(hrn_device_cus()); }
 
 // dw [cout][cin][3][3] f32 += the weight gradient of a cin -> cout conv3x3 (pad 1): x plain [M][H][W][cin] or (x == NULL) the pair
-// gather of `stack` [B][pair_vs][H][W][64]; g [M][H][W][cout].  dt HRN_DTYPE_BF16 (x / stack / g one bf16 plane each) or F32.
+// gather of `stack` [B][pair_vs][H][W][64] (B = M / pair_h); g [M][H][W][cout].  dt HRN_DTYPE_BF16 (x / stack / g one bf16 plane each),
+// HRN_DTYPE_BF16X3 (a pair of bf16 planes each, the lo plane directly behind the hi plane, as hrn_conv_dgrad lays them out) or F32.
 int hrn_kt_conv_wgrad(int dt, const void* x, const void* stack, int pair_h, int pair_last, int pair_vs, const void* g, int M, int H, int W,
                       int cin, int cout, float* dw, void* scratch, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const int cus = hrn_device_cus();
     if (dt == HRN_BF16) return hrn_launch_conv_wgrad_bf16(x, stack, x ? 0 : 1, pair_h, pair_last, pair_vs, g, M, H, W, cin, cout, dw, scratch, cus, s);
+    if (dt == HRN_BF16X3) {
+        HRN_CHECK(x || pair_h > 0, -2, "hrn_kt_conv_wgrad: pair descriptor missing");
+        const size_t hw = (size_t)H * W;
+        const size_t x_lo = x ? (size_t)M * hw * cin * 2 : (size_t)(M / pair_h) * pair_vs * hw * 64 * 2;
+        return hrn_launch_conv_wgrad_x3(x, stack, x_lo, x ? 0 : 1, pair_h, pair_last, pair_vs, g, (size_t)M * hw * cout * 2, M, H, W, cin, cout,
+                                        dw, scratch, cus, s);
+    }
     HRN_CHECK(dt == HRN_F32, -2, "hrn_kt_conv_wgrad: dtype %d", dt);
     return hrn_launch_conv_wgrad((const float*)x, (const float*)stack, x ? 0 : 1, pair_h, pair_last, pair_vs, (const float*)g, M, H, W, cin, cout,
                                  dw, scratch, cus, s);
@@ -39,6 +48,46 @@ int hrn_kt_conv3x3(int dt, int cin, int cout, const void* in, const void* stack,
     p.in = in; p.out = out; p.wpk = wpk; p.bias = bias;
     if (!in) { p.in_pair = 1; p.stack = stack; p.pair_h = pair_h; p.pair_last = pair_last; p.pair_vs = pair_vs; }
     return hrn_launch_conv3x3(dt, cin, cout, p, (hipStream_t)stream);
+}
+
+// One conv3x3 layer with the whole epilogue encoder_impl / fuse_impl (api.hip) set in ConvParams, in storage dt (HRN_DTYPE_BF16,
+// BF16X3 or F32): in plain [M][H][W][cin] or (in == NULL) the pair gather of `stack` [B][pair_vs][H][W][64]; the pair descriptor
+// (pair_h > 0) also feeds res_mode 2, and pair_last alone res_mode 3's alpha index; wpk: hrn_kt_conv_pack(dt) of the OIHW weights;
+// slope: 1 float (device) or NULL; res / res_mode / res_vs, alphas / alpha_vs and the slot output out_h / out_vs as in ConvParams;
+// in_lo / stack_lo / out_lo / res_lo: HRN_DTYPE_BF16X3's lo-plane byte offsets.  route 0: hrn_launch_conv3x3 as production calls it
+// (r64 / v6 / v6x3); route 1: conv3x3.hip's general kernel, the path HRN_CONV_R64=0 HRN_CONV_V6=0 select.
+int hrn_kt_conv3x3_epi(int dt, int route, int cin, int cout, const void* in, const void* stack, int pair_h, int pair_last, int pair_vs,
+                       const void* wpk, const float* bias, const float* slope, const void* res, int res_mode, int res_vs, const float* alphas,
+                       int alpha_vs, void* out, int out_h, int out_vs, size_t in_lo, size_t stack_lo, size_t out_lo, size_t res_lo, int M,
+                       int H, int W, void* stream) {
+    HRN_CHECK(route == 0 || route == 1, -2, "hrn_kt_conv3x3_epi: route %d", route);
+    ConvParams p;
+    memset(&p, 0, sizeof p);
+    p.M = M; p.H = H; p.W = W;
+    p.in = in; p.in_pair = in ? 0 : 1; p.stack = stack; p.pair_h = pair_h; p.pair_last = pair_last; p.pair_vs = pair_vs;
+    p.out = out; p.wpk = wpk; p.bias = bias; p.slope = slope;
+    p.res = res; p.res_mode = res_mode; p.res_vs = res_vs; p.alphas = alphas; p.alpha_vs = alpha_vs;
+    p.out_h = out_h; p.out_vs = out_vs;
+    p.in_lo = in_lo; p.stack_lo = stack_lo; p.out_lo = out_lo; p.res_lo = res_lo;
+    return hrn_launch_conv3x3(dt, cin, cout, p, (hipStream_t)stream, route == 1);
+}
+
+// out [M][H][W][64] (dt) = the 2 -> 64 stem + PReLU (slope NULL: none) over channel 0 = image m of in0 (img_stride0 floats apart) and
+// channel 1 = image m / rep1 of in1, as hrn_launch_stem: sub == NULL reaches stem_mfma_kernel (bf16 / bf16x3), `sub` [M][2] the VALU
+// stem_kernel; out_lo: HRN_DTYPE_BF16X3's lo-plane byte offset
+int hrn_kt_stem(int dt, const float* in0, size_t img_stride0, const float* in1, int rep1, size_t img_stride1, const float* sub,
+                const float* w, const float* bias, const float* slope, void* out, size_t out_lo, int M, int H, int W, void* stream) {
+    return hrn_launch_stem(dt, in0, img_stride0, in1, rep1, img_stride1, sub, w, bias, slope, out, M, H, W, (hipStream_t)stream, out_lo);
+}
+
+// sr [N][S H][S W] f32 = the decoder at scale S of fused [N][H][W][64] (dt; HRN_DTYPE_BF16X3: a pair of bf16 planes, lo fused_lo bytes
+// further on), as decoder_impl runs it: w_iokk (64, 64, S, S) f32 packed into wpk first (64 * 64 * S * S floats of scratch), then
+// bias / slope / wf / bf f32 (device)
+int hrn_kt_decoder(int dt, int scale, const void* fused, size_t fused_lo, const float* w_iokk, void* wpk, const float* bias,
+                   const float* slope, const float* wf, const float* bf, float* sr, int N, int H, int W, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = hrn_launch_decoder_pack(dt == HRN_BF16X3 ? HRN_F32 : dt, w_iokk, wpk, s, scale)) return rc;     // (as api.hip packs it)
+    return hrn_launch_decoder(dt, fused, wpk, bias, slope, wf, bf, sr, N, H, W, s, fused_lo, scale);
 }
 
 int hrn_kt_conv_pack(int dt, int cin, int cout, const float* w_oihw, void* packed, void* stream) {

@@ -21,13 +21,13 @@ from test_gpu_upscale import _model
 
 pytestmark = pytest.mark.gpu
 
-BF16 = 1
+BF16, BF16X3 = 1, 2
 
 
 def _lib():
     from hrnet_hip import binding
     lib = binding.load_library()
-    vp, i = ctypes.c_void_p, ctypes.c_int
+    vp, i, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
     lib.hrn_kt_wgrad_scratch_bytes.restype = ctypes.c_size_t
     lib.hrn_kt_wgrad_scratch_bytes.argtypes = []
     lib.hrn_kt_conv_wgrad.restype = i
@@ -36,8 +36,14 @@ def _lib():
     lib.hrn_kt_conv_dgrad.argtypes = [i, i, i, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp]
     lib.hrn_kt_conv3x3.restype = i
     lib.hrn_kt_conv3x3.argtypes = [i, i, i, vp, vp, i, i, i, vp, vp, vp, i, i, i, vp]
+    lib.hrn_kt_conv3x3_epi.restype = i
+    lib.hrn_kt_conv3x3_epi.argtypes = [i, i, i, i, vp, vp, i, i, i, vp, vp, vp, vp, i, i, vp, i, vp, i, i, sz, sz, sz, sz, i, i, i, vp]
     lib.hrn_kt_conv_pack.restype = i
     lib.hrn_kt_conv_pack.argtypes = [i, i, i, vp, vp, vp]
+    lib.hrn_kt_stem.restype = i
+    lib.hrn_kt_stem.argtypes = [i, vp, sz, vp, i, sz, vp, vp, vp, vp, vp, sz, i, i, i, vp]
+    lib.hrn_kt_decoder.restype = i
+    lib.hrn_kt_decoder.argtypes = [i, i, vp, sz, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
     return lib
 
 
@@ -54,6 +60,16 @@ def _bf(shape, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     t = (torch.randn(shape, generator=g) * scale).to(torch.bfloat16)
     return t.cuda(), t.double()
+
+
+def _x3(shape, seed, scale=1.0):
+    """a bf16x3 device tensor (2, *shape) - plane 0 hi = bf16(v), plane 1 lo = bf16(v - hi) of random fp32 v, the lo plane directly behind
+    the hi plane - and the exact fp64 CPU value hi + lo"""
+    g = torch.Generator().manual_seed(seed)
+    v = torch.randn(shape, generator=g) * scale
+    hi = v.to(torch.bfloat16)
+    lo = (v - hi.float()).to(torch.bfloat16)
+    return torch.stack([hi, lo]).cuda(), hi.double() + lo.double()
 
 
 def _nchw(t):
@@ -99,23 +115,25 @@ def test_bf16_training_op_runs_at_every_scale(scale):
 
 
 # ----------------------------------------------------------------------------- 2. the bf16 weight gradient
-def _wgrad_case(lib, M, H, W, cin, cout, pair=None, seed=0):
-    """-> (got, want, sum |terms|) for dW of a cin -> cout conv; pair = (B, n): the input is the pair gather of a (B, n) view stack"""
-    g, g64 = _bf((M, H, W, cout), seed + 1)
+def _wgrad_case(lib, M, H, W, cin, cout, pair=None, seed=0, dt=BF16):
+    """-> (got, want, sum |terms|) for dW of a cin -> cout conv; pair = (B, n): the input is the pair gather of a (B, n) view stack.
+    dt BF16: one bf16 plane per tensor; BF16X3: hi + lo planes of random fp32 values"""
+    act = _bf if dt == BF16 else _x3
+    g, g64 = act((M, H, W, cout), seed + 1)
     if pair:
         B, n = pair
         half, pair_last = n // 2, n - (n & 1) - 1
         assert B * half == M and cin == 128
-        st, st64 = _bf((B, n, H, W, 64), seed)
+        st, st64 = act((B, n, H, W, 64), seed)
         x, x64 = None, _pair_gather(st64, half, pair_last)
         args = (None, _p(st), half, pair_last, n)
     else:
-        x, x64 = _bf((M, H, W, cin), seed)
+        x, x64 = act((M, H, W, cin), seed)
         args = (_p(x), None, 0, 0, 0)
     dw0 = torch.randn((cout, cin, 3, 3), generator=torch.Generator().manual_seed(seed + 7))
     dw = dw0.cuda()                                                     # the kernel adds (+=) to what is there
     scratch = torch.empty(lib.hrn_kt_wgrad_scratch_bytes(), dtype=torch.uint8, device="cuda")
-    assert lib.hrn_kt_conv_wgrad(BF16, args[0], args[1], args[2], args[3], args[4], _p(g), M, H, W, cin, cout, _p(dw), _p(scratch),
+    assert lib.hrn_kt_conv_wgrad(dt, args[0], args[1], args[2], args[3], args[4], _p(g), M, H, W, cin, cout, _p(dw), _p(scratch),
                                  _stream()) == 0
     torch.cuda.synchronize()
     want = torch.nn.grad.conv2d_weight(_nchw(x64), (cout, cin, 3, 3), _nchw(g64), padding=1)
@@ -123,56 +141,77 @@ def _wgrad_case(lib, M, H, W, cin, cout, pair=None, seed=0):
     return (dw.double().cpu() - dw0.double()).numpy(), want.numpy(), terms.numpy()
 
 
-@pytest.mark.parametrize("case", ["plain64", "plain128x64", "pair", "ragged33", "multi_strip"])
-def test_bf16_wgrad_vs_fp64(case):
-    """The one-plane instance of conv_wgrad_x3_kernel: error <= 1e-5 of sum |terms| per element (bf16 products are exact in fp32)."""
+_WGRAD_CASES = ["plain64", "plain128x64", "pair", "ragged33", "multi_strip"]
+
+
+@pytest.mark.parametrize("case,dt", [pytest.param(c, BF16, id=c) for c in _WGRAD_CASES] +
+                         [pytest.param(c, BF16X3, id=f"{c}-bf16x3") for c in _WGRAD_CASES])
+def test_bf16_wgrad_vs_fp64(case, dt):
+    """conv_wgrad_x3_kernel, one-plane (bf16) and two-plane (bf16x3) instance: error <= 1e-5 of sum |terms| per element (bf16 products are
+    exact in fp32; bf16x3 drops only the g lo x x lo term, <= 2^-18 of |g x|)."""
     lib = _lib()
     if case == "plain64":
-        got, want, terms = _wgrad_case(lib, 3, 16, 32, 64, 64)
+        got, want, terms = _wgrad_case(lib, 3, 16, 32, 64, 64, dt=dt)
     elif case == "plain128x64":
-        got, want, terms = _wgrad_case(lib, 2, 12, 40, 128, 64, seed=3)
+        got, want, terms = _wgrad_case(lib, 2, 12, 40, 128, 64, seed=3, dt=dt)
     elif case == "pair":
-        got, want, terms = _wgrad_case(lib, 2 * 2, 9, 24, 128, 128, pair=(2, 5), seed=5)
+        got, want, terms = _wgrad_case(lib, 2 * 2, 9, 24, 128, 128, pair=(2, 5), seed=5, dt=dt)
     elif case == "ragged33":
-        got, want, terms = _wgrad_case(lib, 2, 7, 33, 64, 128, seed=9)
+        got, want, terms = _wgrad_case(lib, 2, 7, 33, 64, 128, seed=9, dt=dt)
     else:
-        # each workgroup walks several 32-pixel strips: units = M * ceil(W / 32), grid = min(2 CUs, units) (hrn_launch_conv_wgrad_bf16)
+        # each workgroup walks several 32-pixel strips: units = M * ceil(W / 32), grid = min(2 CUs, units) (launch_wgrad_x3, both dtypes)
         M, H, W = 4 * _cus() + 3, 4, 32
         units, grid = M, min(2 * _cus(), M)
         assert units >= 2 * grid, (units, grid)
-        got, want, terms = _wgrad_case(lib, M, H, W, 64, 64, seed=11)
+        got, want, terms = _wgrad_case(lib, M, H, W, 64, 64, seed=11, dt=dt)
     err = np.abs(got - want)
-    print(case, "max err / sum|terms|", float((err / np.maximum(terms, 1e-30)).max()))
+    print(case, dt, "max err / sum|terms|", float((err / np.maximum(terms, 1e-30)).max()))
     assert (err <= 1e-5 * terms + 1e-30).all()
 
 
 # ----------------------------------------------------------------------------- 3. the bf16 convolutions of the data gradients
-@pytest.mark.parametrize("cin,cout,res", [(64, 64, False), (64, 64, True), (128, 128, False), (128, 128, True), (128, 64, False)])
-def test_bf16_dgrad_vs_fp64(cin, cout, res):
+_DGRAD_LAYERS = [(64, 64, False), (64, 64, True), (128, 128, False), (128, 128, True), (128, 64, False)]
+
+
+@pytest.mark.parametrize("cin,cout,res,dt", [pytest.param(*l, BF16, id="-".join(map(str, l))) for l in _DGRAD_LAYERS] +
+                         [pytest.param(*l, BF16X3, id="-".join(map(str, l)) + "-bf16x3") for l in _DGRAD_LAYERS])
+def test_bf16_dgrad_vs_fp64(cin, cout, res, dt):
     """dx = conv3x3(g, W^T flipped) (+ res) for a cin -> cout layer, i.e. a cout -> cin convolution on the bf16 kernels (r64, v6; the
-    64 -> 128 and 128 -> 128 + res shapes are the new v6 instances).  Bound per element: one bf16 rounding of the output (2^-8 of it)
-    plus 1e-5 of sum |terms|."""
+    64 -> 128 and 128 -> 128 + res shapes are the new v6 instances) and on v6x3.  Bound per element: bf16, one bf16 rounding of the
+    output (2^-8 of it) plus 1e-5 of sum |terms|; bf16x3 (hi + lo planes of random fp32 g / res, general fp32 weights), 2^-16 of the
+    output (the split of the fp32 result) plus 1e-5 of sum |terms|."""
     lib = _lib()
     M, H, W = 3, 13, 37
-    g, g64 = _bf((M, H, W, cout), 21)
-    w, w64 = _bf((cout, cin, 3, 3), 22, 0.05)
-    w32 = w.float().contiguous()
-    r, r64 = _bf((M, H, W, cin), 23) if res else (None, None)
-    dx = torch.empty((M, H, W, cin), dtype=torch.bfloat16, device="cuda")
+    if dt == BF16:
+        g, g64 = _bf((M, H, W, cout), 21)
+        w, w64 = _bf((cout, cin, 3, 3), 22, 0.05)
+        w32 = w.float().contiguous()
+        r, r64 = _bf((M, H, W, cin), 23) if res else (None, None)
+        dx = torch.empty((M, H, W, cin), dtype=torch.bfloat16, device="cuda")
+    else:
+        g, g64 = _x3((M, H, W, cout), 21)
+        w32 = (torch.randn((cout, cin, 3, 3), generator=torch.Generator().manual_seed(22)) * 0.05).cuda()
+        w64 = w32.double().cpu()
+        r, r64 = _x3((M, H, W, cin), 23) if res else (None, None)
+        dx = torch.empty((2, M, H, W, cin), dtype=torch.bfloat16, device="cuda")
     wt = torch.empty(cin * cout * 9, device="cuda")
     wtp = torch.empty(cin * cout * 9, device="cuda")
     zb = torch.zeros(128, device="cuda")
-    assert lib.hrn_kt_conv_dgrad(BF16, cin, cout, _p(w32), _p(g), _p(dx), _p(r), M, H, W, _p(wt), _p(wtp), _p(zb), _stream()) == 0
+    assert lib.hrn_kt_conv_dgrad(dt, cin, cout, _p(w32), _p(g), _p(dx), _p(r), M, H, W, _p(wt), _p(wtp), _p(zb), _stream()) == 0
     torch.cuda.synchronize()
     want = torch.nn.grad.conv2d_input((M, cin, H, W), w64, _nchw(g64), padding=1)
     terms = torch.nn.grad.conv2d_input((M, cin, H, W), w64.abs(), _nchw(g64).abs(), padding=1)
     if res:
         want = want + _nchw(r64)
         terms = terms + _nchw(r64).abs()
-    got = _nchw(dx.double().cpu())
+    if dt == BF16:
+        got = _nchw(dx.double().cpu())
+        bound = 2.0 ** -8 * want.abs() + 1e-5 * terms + 1e-30
+    else:
+        got = _nchw(dx[0].double().cpu() + dx[1].double().cpu())
+        bound = 2.0 ** -16 * want.abs() + 1e-5 * terms + 1e-30
     err = (got - want).abs()
-    bound = 2.0 ** -8 * want.abs() + 1e-5 * terms + 1e-30
-    print(cin, cout, res, "max err / bound", float((err / bound).max()))
+    print(cin, cout, res, dt, "max err / bound", float((err / bound).max()))
     assert bool((err <= bound).all())
 
 
