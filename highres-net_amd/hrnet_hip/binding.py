@@ -95,6 +95,9 @@ SIGNATURES = {
     "hrn_hrnet_backward_in": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(HrnetParams), _c.c_int, _c.c_void_p, _c.c_void_p,
                                          _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(HrnetParams), _c.c_void_p,
                                          _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_hrnet_backward_sel": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(HrnetParams), _c.c_int, _c.c_void_p, _c.c_void_p,
+                                          _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(HrnetParams), _c.c_void_p,
+                                          _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_shiftnet_packed_bytes": (_c.c_size_t, []),
     "hrn_shiftnet_pack": (_c.c_int, [_c.POINTER(ShiftnetParams), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_shiftnet_workspace_bytes": (_c.c_size_t, [_c.c_int]),
@@ -110,6 +113,8 @@ SIGNATURES = {
                                                  _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_shiftnet_backward_dt": (_c.c_int, [_c.POINTER(ShiftnetParams), _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
                                             _c.POINTER(ShiftnetParams), _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_shiftnet_backward_sel": (_c.c_int, [_c.POINTER(ShiftnetParams), _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                             _c.POINTER(ShiftnetParams), _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_adam_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_float, _c.c_float, _c.c_float,
                                  _c.c_float, _c.c_float, _c.c_int, _c.c_void_p]),
     "hrn_lanczos_kernel": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p]),
@@ -189,11 +194,14 @@ def _ptr(t):
 
 
 # --------------------------------------------------------------------------- HRNet
-def hrnet_param_struct(named, num_layers):
-    """named: dict of reference state-dict keys -> device f32 tensors.  Returns (HrnetParams, tensors kept alive)."""
+def hrnet_param_struct(named, num_layers, optional=False):
+    """named: dict of reference state-dict keys -> device f32 tensors.  Returns (HrnetParams, tensors kept alive).  optional: a key
+    missing from `named` becomes a NULL field (a frozen parameter's gradient for hrn_hrnet_backward_sel)."""
     keep = []
 
     def p(key):
+        if optional and key not in named:
+            return None
         t = _dev_f32(named[key].detach(), key)
         keep.append(t)
         return t.data_ptr()
@@ -338,9 +346,10 @@ def hrnet_forward_train(packed_f32, lrs, alphas, num_layers, alpha_residual, dty
 
 
 def hrnet_backward(packed_f32, named_params, named_grads, num_layers, alpha_residual, lrs, alphas, d_sr, tws, dtype=F32, scale=3,
-                   d_lrs=None, d_alphas=None):
+                   d_lrs=None, d_alphas=None, select=False):
     """Accumulates dLoss/dparam into named_grads (same keys / shapes as named_params, f32, zero them for plain gradients).  d_lrs
-    (B,V,H,W) / d_alphas (B,V): contiguous f32 device tensors that receive (are overwritten with) the input gradients, or None."""
+    (B,V,H,W) / d_alphas (B,V): contiguous f32 device tensors that receive (are overwritten with) the input gradients, or None.
+    select: named_grads holds only the parameters that want a gradient (hrn_hrnet_backward_sel: the work of the others is skipped)."""
     lib = load_library()
     lrs = _dev_f32(lrs, "lrs")
     alphas = _dev_f32(alphas, "alphas")
@@ -349,15 +358,23 @@ def hrnet_backward(packed_f32, named_params, named_grads, num_layers, alpha_resi
     if tuple(d_sr.shape) != (B, 1, scale * H, scale * W):
         raise ValueError(f"d_sr shape {tuple(d_sr.shape)} != {(B, 1, scale * H, scale * W)}")
     P, keep_p = hrnet_param_struct(named_params, num_layers)
-    G, keep_g = hrnet_param_struct(named_grads, num_layers)
-    for t, g in zip(keep_p, keep_g):
+    G, keep_g = hrnet_param_struct(named_grads, num_layers, optional=select)
+    pairs = zip(keep_p, keep_g) if not select else ((named_params[k], g) for k, g in named_grads.items())
+    for t, g in pairs:
         if t.shape != g.shape or g.data_ptr() == t.data_ptr():
             raise ValueError("gradient buffers must match the parameters' shapes and not alias them")
+    if select and (set(named_grads) - set(hrnet_param_names(num_layers))):
+        raise ValueError(f"unknown HRNet parameters among the gradients: {sorted(set(named_grads) - set(hrnet_param_names(num_layers)))}")
     for name, t, shape in (("d_lrs", d_lrs, (B, V, H, W)), ("d_alphas", d_alphas, (B, V))):
         if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != lrs.device):
             raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on {lrs.device}")
     with torch.cuda.device(lrs.device):
-        if d_lrs is None and d_alphas is None:
+        if select:
+            _check(lib.hrn_hrnet_backward_sel(_ptr(packed_f32), int(dtype), int(scale), ctypes.byref(P), int(bool(alpha_residual)),
+                                              _ptr(lrs), _ptr(alphas), B, V, H, W, _ptr(d_sr), ctypes.byref(G),
+                                              _ptr(d_lrs) if d_lrs is not None else None, _ptr(d_alphas) if d_alphas is not None else None,
+                                              _ptr(tws), tws.numel(), _stream()), "hrn_hrnet_backward_sel")
+        elif d_lrs is None and d_alphas is None:
             _check(lib.hrn_hrnet_backward_s(_ptr(packed_f32), int(dtype), int(scale), ctypes.byref(P), int(bool(alpha_residual)), _ptr(lrs),
                                             _ptr(alphas), B, V, H, W, _ptr(d_sr), ctypes.byref(G), _ptr(tws), tws.numel(), _stream()),
                    "hrn_hrnet_backward")
@@ -369,10 +386,12 @@ def hrnet_backward(packed_f32, named_params, named_grads, num_layers, alpha_resi
 
 
 # --------------------------------------------------------------------------- ShiftNet
-def _shiftnet_struct(named, keep, with_weights):
+def _shiftnet_struct(named, keep, with_weights, optional=False):
     P = ShiftnetParams()
 
     def p(key):
+        if optional and key not in named:
+            return None                                      # a frozen parameter's gradient (hrn_shiftnet_backward_sel)
         t = named[key].detach()
         if not t.is_cuda:
             raise RuntimeError(f"{key} is on '{t.device}': ShiftNet parameters must live on the ROCm device")
@@ -464,9 +483,10 @@ def shiftnet_forward_train(packed, named, x, momentum=0.1, dropout_mask=None, dt
     return theta, tws
 
 
-def shiftnet_backward(named, named_grads, x, dropout_mask, d_theta, tws, need_input_grad=True, dtype=F32):
+def shiftnet_backward(named, named_grads, x, dropout_mask, d_theta, tws, need_input_grad=True, dtype=F32, select=False):
     """Accumulates the parameter gradients into named_grads (parameter keys only); returns d_x (B,2,128,128) or None.  dtype: the
-    forward's (the workspace `tws` it filled)."""
+    forward's (the workspace `tws` it filled).  select: named_grads holds only the parameters that want a gradient
+    (hrn_shiftnet_backward_sel: the work of the others is skipped)."""
     lib = load_library()
     x = _dev_f32(x, "x")
     d_theta = _dev_f32(d_theta, "d_theta")
@@ -476,11 +496,16 @@ def shiftnet_backward(named, named_grads, x, dropout_mask, d_theta, tws, need_in
     P = _shiftnet_struct(named, keep, True)
     gfull = dict(named_grads)
     for k, v in named.items():                               # the struct builder also wants the (unused) running stats
-        gfull.setdefault(k, v)
-    G = _shiftnet_struct(gfull, keep, True)
+        if not select or k in SHIFTNET_BUFFER_NAMES:
+            gfull.setdefault(k, v)
+    G = _shiftnet_struct(gfull, keep, True, optional=select)
     d_x = torch.empty_like(x) if need_input_grad else None
     with torch.cuda.device(x.device):
-        if dtype == F32:
+        if select:
+            _check(lib.hrn_shiftnet_backward_sel(ctypes.byref(P), int(dtype), _ptr(x), B, mptr, _ptr(d_theta), ctypes.byref(G),
+                                                 _ptr(d_x) if need_input_grad else None, _ptr(tws), tws.numel(), _stream()),
+                   "hrn_shiftnet_backward_sel")
+        elif dtype == F32:
             _check(lib.hrn_shiftnet_backward(ctypes.byref(P), _ptr(x), B, mptr, _ptr(d_theta), ctypes.byref(G),
                                              _ptr(d_x) if need_input_grad else None, _ptr(tws), tws.numel(), _stream()),
                    "hrn_shiftnet_backward")
@@ -765,9 +790,40 @@ def _(packed, params, lrs, alphas, d_sr, tws, num_layers, alpha_residual, dtype,
             alphas.new_empty(alphas.shape if need_alphas else (0,), dtype=torch.float32))
 
 
+@torch.library.custom_op("hrnet_hip::hrnet_backward_sel", mutates_args=("tws",), device_types="cuda")
+def _op_hrnet_backward_sel(packed: torch.Tensor, params: Sequence[torch.Tensor], lrs: torch.Tensor, alphas: torch.Tensor, d_sr: torch.Tensor,
+                           tws: torch.Tensor, num_layers: int, alpha_residual: bool, dtype: int, scale: int, need_params: Sequence[bool],
+                           need_lrs: bool, need_alphas: bool) -> Tuple[List[torch.Tensor], torch.Tensor, torch.Tensor]:
+    """hrnet_backward_in for a partly frozen model (hrn_hrnet_backward_sel): need_params[i] says whether params[i] wants a gradient.
+    Returns (parameter gradients in `hrnet_param_names` order, an empty tensor for every frozen one; d_lrs; d_alphas); only the work the
+    requested outputs depend on is launched, and each of them is bit-identical to hrnet_backward_in's."""
+    names = hrnet_param_names(num_layers)
+    if len(need_params) != len(names):
+        raise ValueError(f"need_params has {len(need_params)} entries for {len(names)} parameters")
+    named = dict(zip(names, params))
+    grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
+             for k, p, need in zip(names, params, need_params) if need}
+    d_lrs = torch.empty(lrs.shape, dtype=torch.float32, device=lrs.device) if need_lrs else None
+    d_alphas = torch.empty(alphas.shape, dtype=torch.float32, device=alphas.device) if need_alphas else None
+    hrnet_backward(packed, named, grads, num_layers, alpha_residual, lrs, alphas, d_sr.contiguous(), tws, dtype, scale, d_lrs=d_lrs,
+                   d_alphas=d_alphas, select=True)
+    return ([grads[k] if k in grads else named[k].new_empty((0,), dtype=torch.float32) for k in names],
+            d_lrs if need_lrs else lrs.new_empty((0,), dtype=torch.float32),
+            d_alphas if need_alphas else alphas.new_empty((0,), dtype=torch.float32))
+
+
+@_op_hrnet_backward_sel.register_fake
+def _(packed, params, lrs, alphas, d_sr, tws, num_layers, alpha_residual, dtype, scale, need_params, need_lrs, need_alphas):
+    return ([p.new_empty(p.shape if need else (0,), dtype=torch.float32) for p, need in zip(params, need_params)],
+            lrs.new_empty(lrs.shape if need_lrs else (0,), dtype=torch.float32),
+            alphas.new_empty(alphas.shape if need_alphas else (0,), dtype=torch.float32))
+
+
 def _hrnet_train_setup(ctx, inputs, output):
     packed, lrs, alphas, params, num_layers, alpha_residual, dtype, scale = inputs
     ctx.num_layers, ctx.alpha_residual, ctx.n, ctx.dtype, ctx.scale = num_layers, alpha_residual, len(params), dtype, scale
+    # which parameters autograd will ask for (requires_grad_(False): frozen); all of them take the full backward of every release
+    ctx.need_params = [bool(p.requires_grad) for p in params]
     ctx.set_materialize_grads(False)          # (or autograd hands the backward a zero-filled "gradient" of the 20 GB workspace output)
     ctx.save_for_backward(packed, lrs, alphas, output[1], *params)
 
@@ -784,6 +840,15 @@ def _hrnet_train_backward(ctx, d_sr, _d_tws):
     # fusion level (HRNet.py:124-128), so without one (or with a single view) their gradient stays None, as in the reference
     need_lrs = ctx.needs_input_grad[1]
     need_alphas = ctx.needs_input_grad[2] and bool(ctx.alpha_residual) and lrs.shape[1] > 1
+    if not all(ctx.need_params):
+        # a partly frozen model: frozen parameters get None (their .grad stays None) and their work is not launched
+        if not (any(ctx.need_params) or need_lrs or need_alphas):
+            return (None, None, None, [None] * len(params)) + tail
+        grads, d_lrs, d_alphas = torch.ops.hrnet_hip.hrnet_backward_sel(packed, params, lrs, alphas, d_sr, tws.data, ctx.num_layers,
+                                                                        ctx.alpha_residual, ctx.dtype, ctx.scale, ctx.need_params,
+                                                                        need_lrs, need_alphas)
+        return (None, d_lrs.to(lrs.dtype) if need_lrs else None, d_alphas.to(alphas.dtype) if need_alphas else None,
+                [g.to(p.dtype) if need else None for g, p, need in zip(grads, params, ctx.need_params)]) + tail
     if not (need_lrs or need_alphas):
         grads = torch.ops.hrnet_hip.hrnet_backward(packed, params, lrs, alphas, d_sr, tws.data, ctx.num_layers, ctx.alpha_residual,
                                                    ctx.dtype, ctx.scale)
@@ -842,9 +907,35 @@ def _(params, x, dropout_mask, d_theta, tws, need_input_grad, dtype=0):
     return [p.new_empty(p.shape, dtype=torch.float32) for p in params], (x.new_empty(x.shape) if need_input_grad else x.new_empty((0,)))
 
 
+@torch.library.custom_op("hrnet_hip::shiftnet_backward_sel", mutates_args=("tws",), device_types="cuda")
+def _op_shiftnet_backward_sel(params: Sequence[torch.Tensor], x: torch.Tensor, dropout_mask: Optional[torch.Tensor], d_theta: torch.Tensor,
+                              tws: torch.Tensor, need_input_grad: bool, dtype: int,
+                              need_params: Sequence[bool]) -> Tuple[List[torch.Tensor], torch.Tensor]:
+    """shiftnet_backward for a partly frozen ShiftNet (hrn_shiftnet_backward_sel): need_params[i] says whether params[i] wants a gradient.
+    Returns (parameter gradients in SHIFTNET_PARAM_NAMES order, an empty tensor for every frozen one; d_x, empty when not needed)."""
+    if len(need_params) != len(SHIFTNET_PARAM_NAMES):
+        raise ValueError(f"need_params has {len(need_params)} entries for {len(SHIFTNET_PARAM_NAMES)} parameters")
+    named = dict(zip(SHIFTNET_PARAM_NAMES, params))
+    for k in SHIFTNET_BUFFER_NAMES:
+        named[k] = named[k.rsplit(".", 1)[0] + ".weight"]
+    grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
+             for k, p, need in zip(SHIFTNET_PARAM_NAMES, params, need_params) if need}
+    d_x = shiftnet_backward(named, grads, x, dropout_mask, d_theta.contiguous(), tws, need_input_grad=need_input_grad, dtype=dtype,
+                            select=True)
+    return ([grads[k] if k in grads else named[k].new_empty((0,), dtype=torch.float32) for k in SHIFTNET_PARAM_NAMES],
+            (d_x if d_x is not None else x.new_empty((0,))))
+
+
+@_op_shiftnet_backward_sel.register_fake
+def _(params, x, dropout_mask, d_theta, tws, need_input_grad, dtype, need_params):
+    return ([p.new_empty(p.shape if need else (0,), dtype=torch.float32) for p, need in zip(params, need_params)],
+            (x.new_empty(x.shape) if need_input_grad else x.new_empty((0,))))
+
+
 def _shiftnet_train_setup(ctx, inputs, output):
     packed, x, params, bn_running, momentum, dropout_mask = inputs[:6]
     ctx.np, ctx.has_mask = len(params), dropout_mask is not None
+    ctx.need_params = [bool(p.requires_grad) for p in params]          # as in _hrnet_train_setup
     ctx.dtype = inputs[6] if len(inputs) > 6 else F32
     ctx.set_materialize_grads(False)
     ctx.save_for_backward(x, output[1], *params, *([dropout_mask] if dropout_mask is not None else []))
@@ -859,6 +950,13 @@ def _shiftnet_train_backward(ctx, d_theta, _d_tws, _d_running):
     params = rest[:ctx.np]
     mask = rest[ctx.np] if ctx.has_mask else None
     need_x = ctx.needs_input_grad[1]
+    if not all(ctx.need_params):
+        # a partly (or wholly) frozen ShiftNet, e.g. a fixed pretrained registration model that only passes d_x back into HRNet
+        if not (any(ctx.need_params) or need_x):
+            return (None, None, [None] * ctx.np, [None] * len(SHIFTNET_BUFFER_NAMES)) + tail
+        grads, d_x = torch.ops.hrnet_hip.shiftnet_backward_sel(params, x, mask, d_theta, tws.data, need_x, ctx.dtype, ctx.need_params)
+        return (None, (d_x if need_x else None), [g if need else None for g, need in zip(grads, ctx.need_params)],
+                [None] * len(SHIFTNET_BUFFER_NAMES)) + tail
     if ctx.dtype == F32:
         grads, d_x = torch.ops.hrnet_hip.shiftnet_backward(params, x, mask, d_theta, tws.data, need_x)      # (tws.data: see _hrnet_train_backward)
     else:

@@ -507,8 +507,16 @@ int hrn_launch_prelu_bwd_bias(const float* dy, const float* y, const float* xpre
     if (C == 64) { if (dt == HRN_BF16X3) HRN_PB(64, HRN_BF16X3); else if (dt == HRN_BF16) HRN_PB(64, HRN_BF16); else HRN_PB(64, HRN_F32); }
     else { if (dt == HRN_BF16X3) HRN_PB(128, HRN_BF16X3); else if (dt == HRN_BF16) HRN_PB(128, HRN_BF16); else HRN_PB(128, HRN_F32); }
 #undef HRN_PB
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3(C / 32), dim3(1024), 0, s, colpart, blocks, C, db);
-    hipLaunchKernelGGL(scalar_finish_kernel, dim3(1), dim3(256), 0, s, slopepart, blocks, dslope);
+    hrn_count_launch(HRN_LC_PRELU_BWD);
+    // a NULL db / dslope (a frozen bias / slope, hrn_hrnet_backward_sel): its finish launch has no reader
+    if (db) {
+        hipLaunchKernelGGL(colsum_finish_kernel, dim3(C / 32), dim3(1024), 0, s, colpart, blocks, C, db);
+        hrn_count_launch(HRN_LC_BIAS_FINISH);
+    }
+    if (dslope) {
+        hipLaunchKernelGGL(scalar_finish_kernel, dim3(1), dim3(256), 0, s, slopepart, blocks, dslope);
+        hrn_count_launch(HRN_LC_SLOPE_FINISH);
+    }
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -522,6 +530,7 @@ int hrn_launch_colsum(const float* g, size_t rows, int C, float* db, void* scrat
     else { if (dt == HRN_BF16X3) HRN_CS(128, HRN_BF16X3); else if (dt == HRN_BF16) HRN_CS(128, HRN_BF16); else HRN_CS(128, HRN_F32); }
 #undef HRN_CS
     hipLaunchKernelGGL(colsum_finish_kernel, dim3(C / 32), dim3(1024), 0, s, partial, blocks, C, db);
+    hrn_count_launch(HRN_LC_BIAS_FINISH);
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -555,6 +564,7 @@ int hrn_launch_conv_wgrad(const float* x, const float* stack, int in_pair, int p
         for (int ic = 0; ic < cin / 64; ++ic) {
             p.co_chunk = cc; p.ci_chunk = ic;
             hipLaunchKernelGGL(conv_wgrad_kernel, dim3(grid), dim3(256), WG_LDS, s, p);
+            hrn_count_launch(HRN_LC_CONV_WGRAD_F32);
             hipLaunchKernelGGL(wgrad_finish_kernel, dim3(9 * 4096 / 64), dim3(1024), 0, s, (const float*)scratch, grid, dw, cin, cc, ic);
         }
     HRN_LAUNCH_CHECK();
@@ -573,6 +583,7 @@ int hrn_launch_stem_wgrad_sub(const float* in0, size_t stride0, const float* in1
     if (tiles < grid) grid = (int)tiles;
     HRN_LAUNCH_ST(dt, stem_wgrad_kernel, dim3(grid), dim3(256), 0, s, in0, stride0, in1, rep1, stride1, sub, (const void*)g, M, H, W, (float*)scratch);
     hipLaunchKernelGGL(stem_wgrad_finish_kernel, dim3(64 * 18 / 16), dim3(1024), 0, s, (const float*)scratch, grid * 4, dw);
+    hrn_count_launch(HRN_LC_STEM_WGRAD);
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -606,6 +617,7 @@ int hrn_launch_fuse_scatter(const float* dsn, const float* dz, int n_in, int hal
                             size_t hw, int B, hipStream_t s, int dt) {
     HRN_LAUNCH_ST(dt, fuse_scatter_kernel, dim3(red_grid((size_t)B * n_in * hw * 16)), dim3(256), 0, s, (const void*)dsn, (const void*)dz, n_in, half, pair_last,
                   alpha_residual, (void*)ds, hw, B);
+    hrn_count_launch(HRN_LC_FUSE_SCATTER);
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -613,6 +625,7 @@ int hrn_launch_fuse_scatter(const float* dsn, const float* dz, int n_in, int hal
 int hrn_conv_dgrad(int cin, int cout, const float* w, const float* g, float* dx, const float* res, int M, int H, int W, float* wt,
                    void* wtp, const float* zero_bias, hipStream_t s, int dt) {
     int rc;
+    hrn_count_launch(HRN_LC_CONV_DGRAD);
     if ((rc = hrn_launch_dgrad_weights(w, wt, cin, cout, s))) return rc;
     if ((rc = hrn_launch_conv_pack(dt, cout, cin, wt, wtp, s))) return rc;               // a cout -> cin convolution
     ConvParams p = ConvParams();

@@ -140,10 +140,11 @@ __global__ __launch_bounds__(1024) void decoder_bwd_finish_kernel(const float* _
     s = 0.0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) s += red[k][el];
+    // a NULL output: a frozen parameter (hrn_hrnet_backward_sel), whose sum nobody reads
     if (!scalar) {
-        if (idx < DB_DW) dwd[idx] += (float)s;
-        else if (idx < DB_DW + 64) dbd[idx - DB_DW] += (float)s;
-        else dwf[idx - DB_DW - 64] += (float)s;
+        if (idx < DB_DW) { if (dwd) dwd[idx] += (float)s; }
+        else if (idx < DB_DW + 64) { if (dbd) dbd[idx - DB_DW] += (float)s; }
+        else if (dwf) dwf[idx - DB_DW - 64] += (float)s;
         return;
     }
     // the 64 lane terms of a scalar: one wave, fixed order
@@ -151,8 +152,8 @@ __global__ __launch_bounds__(1024) void decoder_bwd_finish_kernel(const float* _
     if (el == 0) {
         double t = 0.0;
         for (int l = 0; l < 64; ++l) t += red[0][l];
-        if ((int)blockIdx.x == NEB) dad[0] += (float)t;
-        else dbf[0] += (float)t;
+        if ((int)blockIdx.x == NEB) { if (dad) dad[0] += (float)t; }
+        else if (dbf) dbf[0] += (float)t;
     }
 }
 
@@ -161,12 +162,18 @@ int launch_decoder_bwd(const float* fused, const float* d_sr, const float* wd, c
                        float* dwd, float* dbd, float* dad, float* dwf, float* dbf, int N, int H, int W, void* scratch, int grid, hipStream_t s) {
     constexpr int NP = db_npos(S), DB_DW = db_dw(S);
     static_assert(S * S % NP == 0 && NP % S == 0, "decoder_bwd: a launch covers whole rows");
-    for (int pos0 = 0; pos0 < S * S; pos0 += NP)
+    for (int pos0 = 0; pos0 < S * S; pos0 += NP) {
         hipLaunchKernelGGL((decoder_bwd_kernel<S, NP>), dim3(grid), dim3(256), 0, s, fused, d_sr, wd, bd, ad, wf, d_fused, (float*)scratch, N, H,
                            W, pos0);
+        hrn_count_launch(HRN_LC_DECODER_BWD);
+    }
     static_assert((DB_DW + 128) % 64 == 0, "decoder_bwd_finish: 64 elements per block");
-    hipLaunchKernelGGL(decoder_bwd_finish_kernel<S>, dim3((DB_DW + 128) / 64 + 2), dim3(1024), 0, s, (const float*)scratch, grid, dwd, dbd,
-                       dad, dwf, dbf);
+    // every decoder parameter frozen (hrn_hrnet_backward_sel): the partial slabs have no reader
+    if (dwd || dbd || dad || dwf || dbf) {
+        hipLaunchKernelGGL(decoder_bwd_finish_kernel<S>, dim3((DB_DW + 128) / 64 + 2), dim3(1024), 0, s, (const float*)scratch, grid, dwd, dbd,
+                           dad, dwf, dbf);
+        hrn_count_launch(HRN_LC_DECODER_BWD_FINISH);
+    }
     HRN_LAUNCH_CHECK();
     return 0;
 }

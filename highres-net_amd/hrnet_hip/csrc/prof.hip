@@ -2,6 +2,7 @@
 #include "common.h"
 #include "../../../include/hrnet_hip.h"
 
+#include <atomic>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -15,6 +16,10 @@ bool g_on = false;
 std::vector<Family> g_fam;
 std::vector<Rec> g_rec;          // pending (not yet folded into g_fam)
 std::vector<hipEvent_t> g_pool;  // recycled events
+std::atomic<long> g_launches[HRN_LC_COUNT];
+const char* const g_launch_names[HRN_LC_COUNT] = {"conv_wgrad_f32", "stem_wgrad", "prelu_bwd", "bias_finish", "slope_finish", "conv_dgrad",
+                                                   "decoder_bwd", "decoder_bwd_finish", "fuse_scatter", "sn_bn_bwd", "fc2_bwd",
+                                                   "fc1_bwd_w", "fc1_bwd_x"};
 
 hipEvent_t get_event() {
     if (!g_pool.empty()) { hipEvent_t e = g_pool.back(); g_pool.pop_back(); return e; }
@@ -53,7 +58,20 @@ HrnProfScope::~HrnProfScope() {
     if (rec < (int)g_rec.size() && g_rec[rec].b) (void)hipEventRecord(g_rec[rec].b, stream);
 }
 
+void hrn_count_launch(int which) {
+    if (which >= 0 && which < HRN_LC_COUNT) g_launches[which].fetch_add(1, std::memory_order_relaxed);
+}
+
 extern "C" {
+// test hooks (not part of include/hrnet_hip.h): launches of counter `name` since the last reset, -1 for a name it does not know
+long hrn_kt_launch_count(const char* name) {
+    for (int i = 0; i < HRN_LC_COUNT; ++i)
+        if (name && strcmp(name, g_launch_names[i]) == 0) return g_launches[i].load(std::memory_order_relaxed);
+    return -1;
+}
+void hrn_kt_launch_count_reset(void) {
+    for (int i = 0; i < HRN_LC_COUNT; ++i) g_launches[i].store(0, std::memory_order_relaxed);
+}
 int hrn_profile_enable(int on) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (on) { fold_locked(); g_fam.clear(); g_on = true; }

@@ -118,8 +118,8 @@ __global__ __launch_bounds__(1024) void bn_bwd_finish_kernel(const double* __res
     block_pair_sum(partial, nblk, C, a, b);
     if (c >= C) return;
     sums[c * 2] = a; sums[c * 2 + 1] = b;
-    dbeta[c] += (float)a;
-    dgamma[c] += (float)b;
+    if (dbeta) dbeta[c] += (float)a;        // NULL: a frozen BatchNorm affine (hrn_shiftnet_backward_sel); the sums are still read
+    if (dgamma) dgamma[c] += (float)b;
 }
 template <int POOL, int ST>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const void* __restrict__ x, const void* __restrict__ dy,
@@ -233,9 +233,8 @@ __global__ __launch_bounds__(256) void fc2_bwd_kernel(const float* __restrict__ 
         dz1[(size_t)b * 1024 + j] = dz;
         g0 += t0 * yv; g1 += t1 * yv; gb += dz;
     }
-    dw2[j] += g0;
-    dw2[1024 + j] += g1;
-    db1[j] += gb;
+    if (dw2) { dw2[j] += g0; dw2[1024 + j] += g1; }    // NULL: frozen (hrn_shiftnet_backward_sel); dz1 is still read
+    if (db1) db1[j] += gb;
 }
 // dw1[j][k] += sum_b dz1[b][j] * xr[b][k]      grid (FCK / 256, 1024 / 64), B <= 32 per launch.  A thread keeps its column of xr (32
 // samples) in registers and walks 64 neurons: xr is read 16 times in all (it was once per neuron: 4.3 GB of L2 reads for a 268 MB
@@ -389,6 +388,7 @@ int hrn_launch_sn_bn_bwd(const float* x, const float* dy, const float* stats, co
     if (dt == HRN_BF16) { if (pool) HRN_SN_BN(2, HRN_BF16); else HRN_SN_BN(1, HRN_BF16); }
     else { if (pool) HRN_SN_BN(2, HRN_F32); else HRN_SN_BN(1, HRN_F32); }
 #undef HRN_SN_BN
+    hrn_count_launch(HRN_LC_SN_BN_BWD);
     return 0;
 }
 
@@ -474,14 +474,29 @@ int hrn_shiftnet_forward_train(const void* packed, const hrn_shiftnet_params* P,
     return hrn_shiftnet_forward_train_dt(packed, HRN_F32, P, x, B, momentum, dropout_mask, theta, tws, tws_bytes, stream);
 }
 
-int hrn_shiftnet_backward_dt(const hrn_shiftnet_params* P, int dt, const float* x, int B, const unsigned char* dropout_mask,
-                             const float* d_theta, const hrn_shiftnet_params* G, float* d_x, void* tws, size_t tws_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// The backward behind hrn_shiftnet_backward_dt (sel = false: every gradient of `G`, the launch sequence of every release) and
+// hrn_shiftnet_backward_sel (sel = true: a NULL field of `G` is a frozen parameter).  The walk stops at the deepest layer below which
+// nothing is wanted (d_x NULL); a frozen layer above it keeps its BatchNorm backward and data gradient and skips its weight and bias
+// gradients.  fc2_bwd_kernel (dz1, d fc2.weight, d fc1.bias in one pass) runs whenever anything is wanted.
+int shiftnet_backward_impl(const hrn_shiftnet_params* P, int dt, const float* x, int B, const unsigned char* dropout_mask, const float* d_theta,
+                           const hrn_shiftnet_params* G, float* d_x, void* tws, size_t tws_bytes, void* stream, bool sel) {
     HRN_CHECK(sn_dtype_ok(dt), -2, "hrn_shiftnet_backward: unsupported dtype %d (HRN_DTYPE_F32 or HRN_DTYPE_BF16)", dt);
     HRN_CHECK(P && G && x && d_theta && tws, -2, "hrn_shiftnet_backward: null argument");
     HRN_CHECK(B > 0, -2, "hrn_shiftnet_backward: empty batch");
     if (dt == HRN_BF16) HRN_CHECK(((uintptr_t)tws & 255) == 0, -2, "hrn_shiftnet_backward: train_ws must be 256-byte aligned");
     const SnTrainWs T = sn_train_ws(B, dt);
     HRN_CHECK(tws_bytes >= T.total, -3, "hrn_shiftnet_backward: workspace too small (%zu < %zu)", tws_bytes, T.total);
+    auto want = [&](const float* g) { return !sel || g != nullptr; };
+    // lowest: the first layer (counted from the input) whose d ypost is read; 8: none of them
+    int lowest = d_x ? 0 : 8;
+    for (int i = 0; i < 8 && lowest == 8; ++i)
+        if (want(G->conv_w[i]) || want(G->conv_b[i]) || want(G->bn_g[i]) || want(G->bn_b[i])) lowest = i;
+    const bool fc1w = want(G->fc1_w);
+    if (lowest == 8 && !fc1w && !want(G->fc1_b) && !want(G->fc2_w)) return 0;
     hipStream_t s = (hipStream_t)stream;
     auto mut = [](const float* p) { return const_cast<float*>(p); };
     const int cus = sn_cus();
@@ -497,18 +512,24 @@ int hrn_shiftnet_backward_dt(const hrn_shiftnet_params* P, int dt, const float* 
     HRN_HIP(hipMemsetAsync(at(tws, T.zero_bias), 0, 128 * 4, s));
     // ---- tail: theta = fc2(ReLU(fc1(dropout(flatten(y8)))))                                ShiftNet.py:69-74
     hipLaunchKernelGGL(fc2_bwd_kernel, dim3(4), dim3(256), 0, s, d_theta, (const float*)at(tws, T.y1), P->fc2_w, dz1, mut(G->fc2_w), mut(G->fc1_b), B);
+    hrn_count_launch(HRN_LC_FC2_BWD);
     // (xr, the fc1 input in the reference's flatten order with the dropout folded in, was left in the workspace by the forward)
-    for (int b0 = 0; b0 < B; b0 += 32)
+    for (int b0 = 0; fc1w && b0 < B; b0 += 32) {
         hipLaunchKernelGGL(fc1_bwd_w_kernel, dim3(FCK / 256, 1024 / FC1_BWD_JT), dim3(256), 0, s, (const float*)dz1 + (size_t)b0 * 1024,
                            (const float*)xr + (size_t)b0 * FCK, mut(G->fc1_w), B - b0 < 32 ? B - b0 : 32);
+        hrn_count_launch(HRN_LC_FC1_BWD_W);
+    }
+    if (lowest == 8) { HRN_LAUNCH_CHECK(); return 0; }
     { const int rc_lds = hrn_allow_lds((const void*)fc1_bwd_x_kernel, FCX_LDS_BYTES); if (rc_lds) return rc_lds; }
-    for (int b0 = 0; b0 < B; b0 += 32)      // 32 samples are the MFMA's M: larger batches go in groups
+    for (int b0 = 0; b0 < B; b0 += 32) {    // 32 samples are the MFMA's M: larger batches go in groups
         hipLaunchKernelGGL(fc1_bwd_x_kernel, dim3(FCK / 128), dim3(256), FCX_LDS_BYTES, s, (const float*)dz1 + (size_t)b0 * 1024, P->fc1_w,
                            dxr + (size_t)b0 * FCK, B - b0 < 32 ? B - b0 : 32);
+        hrn_count_launch(HRN_LC_FC1_BWD_X);
+    }
     HRN_LAUNCH_CHECK();
     if ((rc = hrn_launch_fc_from_ref(dxr, dropout_mask, cur, B, s, dt))) return rc;
     // ---- layers 8 .. 1                                                                        ShiftNet.py:16-41, :59-67
-    for (int i = 7; i >= 0; --i) {
+    for (int i = 7; i >= lowest; --i) {
         const int h = T.hin[i], C = SN_CO[i];
         const float* xp = (const float*)at(tws, T.xpre[i]);
         const float* st = (const float*)at(tws, T.stats[i]);
@@ -516,18 +537,20 @@ int hrn_shiftnet_backward_dt(const hrn_shiftnet_params* P, int dt, const float* 
         if ((rc = hrn_launch_sn_bn_bwd(xp, cur, st, P->bn_g[i], oth, mut(G->bn_g[i]), mut(G->bn_b[i]), B, h, h, C, SN_POOL[i], partial, sums, s,
                                        dt))) return rc;
         // oth = d xpre_i
-        if ((rc = hrn_launch_colsum(oth, npix, C, mut(G->conv_b[i]), sc, s, dt))) return rc;
+        if (want(G->conv_b[i]) && (rc = hrn_launch_colsum(oth, npix, C, mut(G->conv_b[i]), sc, s, dt))) return rc;
         if (i > 0) {
             const float* xin = (const float*)at(tws, T.ypost[i - 1]);
-            if (dt == HRN_BF16) rc = hrn_launch_conv_wgrad_bf16(xin, nullptr, 0, 0, 0, 0, oth, B, h, h, SN_CI[i], C, mut(G->conv_w[i]), sc, cus, s);
-            else rc = hrn_launch_conv_wgrad(xin, nullptr, 0, 0, 0, 0, oth, B, h, h, SN_CI[i], C, mut(G->conv_w[i]), sc, cus, s);
-            if (rc) return rc;
-            if ((rc = hrn_conv_dgrad(SN_CI[i], C, P->conv_w[i], oth, cur, nullptr, B, h, h, (float*)at(tws, T.wt), at(tws, T.wtp),
-                                     (const float*)at(tws, T.zero_bias), s, dt))) return rc;
+            if (want(G->conv_w[i])) {
+                if (dt == HRN_BF16) rc = hrn_launch_conv_wgrad_bf16(xin, nullptr, 0, 0, 0, 0, oth, B, h, h, SN_CI[i], C, mut(G->conv_w[i]), sc, cus, s);
+                else rc = hrn_launch_conv_wgrad(xin, nullptr, 0, 0, 0, 0, oth, B, h, h, SN_CI[i], C, mut(G->conv_w[i]), sc, cus, s);
+                if (rc) return rc;
+            }
+            if (i > lowest && (rc = hrn_conv_dgrad(SN_CI[i], C, P->conv_w[i], oth, cur, nullptr, B, h, h, (float*)at(tws, T.wt), at(tws, T.wtp),
+                                                   (const float*)at(tws, T.zero_bias), s, dt))) return rc;
         } else {
             const size_t plane = 128 * 128;
-            if ((rc = hrn_launch_stem_wgrad_sub(x, 2 * plane, x + plane, 1, 2 * plane, (const float*)at(tws, T.means), oth, B, h, h, mut(G->conv_w[0]), sc,
-                                                cus, s, dt))) return rc;
+            if (want(G->conv_w[0]) && (rc = hrn_launch_stem_wgrad_sub(x, 2 * plane, x + plane, 1, 2 * plane, (const float*)at(tws, T.means), oth, B,
+                                                                      h, h, mut(G->conv_w[0]), sc, cus, s, dt))) return rc;
             if (d_x) {
                 float* dxin = (float*)at(tws, T.dxin);
                 float* gm = (float*)at(tws, T.gmeans);
@@ -539,6 +562,20 @@ int hrn_shiftnet_backward_dt(const hrn_shiftnet_params* P, int dt, const float* 
         }
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hrn_shiftnet_backward_dt(const hrn_shiftnet_params* P, int dt, const float* x, int B, const unsigned char* dropout_mask,
+                             const float* d_theta, const hrn_shiftnet_params* G, float* d_x, void* tws, size_t tws_bytes, void* stream) {
+    return shiftnet_backward_impl(P, dt, x, B, dropout_mask, d_theta, G, d_x, tws, tws_bytes, stream, false);
+}
+
+int hrn_shiftnet_backward_sel(const hrn_shiftnet_params* P, int dt, const float* x, int B, const unsigned char* dropout_mask,
+                              const float* d_theta, const hrn_shiftnet_params* G, float* d_x, void* tws, size_t tws_bytes, void* stream) {
+    return shiftnet_backward_impl(P, dt, x, B, dropout_mask, d_theta, G, d_x, tws, tws_bytes, stream, true);
 }
 
 int hrn_shiftnet_backward(const hrn_shiftnet_params* P, const float* x, int B, const unsigned char* dropout_mask, const float* d_theta,

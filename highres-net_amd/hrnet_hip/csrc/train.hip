@@ -140,6 +140,180 @@ __global__ __launch_bounds__(256) void pair_add_kernel(const void* __restrict__ 
     }
 }
 
+
+// The backward behind hrn_hrnet_backward_in (sel = false: every gradient of `Gr` is produced, the launch sequence of every release) and
+// hrn_hrnet_backward_sel (sel = true: a NULL field of `Gr` is a frozen parameter).  A launch is left out only when nothing downstream reads
+// any of its outputs; what runs computes what it computes on the full path, so every produced gradient is bit-identical to it.
+//   need_ds[t]   the gradient of the views entering fusion level t (t = T: the decoder's data gradient, t = 0: d stack_0)
+//   need_da[l]   the gradient of the encoder activation a_l (l = 0: the stem's output)
+// Decoder parameters need only the decoder's weight-gradient part; fusion parameters (shared by every level) and d_alphas (alpha
+// residual only) every level's data gradient above them; encoder / stem parameters and d_lrs the chain down to stack_0.
+int hrnet_backward_impl(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
+                        int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, float* d_lrs, float* d_alphas, void* tws,
+                        size_t tws_bytes, void* stream, bool sel) {
+    int rc;
+    HRN_CHECK(hrn_scale_ok(scale), -2, "hrn_hrnet_backward: scale must be 2, 3 or 4 (got %d)", scale);
+    HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16 || dt == HRN_BF16X3, -2, "hrn_hrnet_backward: dtype must be HRN_DTYPE_F32, HRN_DTYPE_BF16 or HRN_DTYPE_BF16X3 (got %d)", dt);
+    HRN_CHECK(pk && Pr && Gr && lrs && alphas && d_sr && tws, -2, "hrn_hrnet_backward: null argument");
+    if ((rc = check_aligned("hrn_hrnet_backward", dt, pk, tws))) return rc;
+    const int nl = Pr->num_layers;
+    if ((rc = check_train(nl, B, V, H, W))) return rc;
+    const TrainWs L = train_ws(nl, B, V, H, W);
+    HRN_CHECK(tws_bytes >= L.total, -3, "hrn_hrnet_backward: workspace too small (%zu < %zu)", tws_bytes, L.total);
+    for (int t = 0; d_alphas && t < L.T; ++t)
+        HRN_CHECK(hrn_alpha_grad_scratch_bytes(B * (L.n_in[t] / 2)) <= L.dec_f - L.scratch, -3, "hrn_hrnet_backward_in: scratch too small for d_alphas");
+    // ---- what is needed (all of it unless sel)
+    auto want = [&](const float* g) { return !sel || g != nullptr; };
+    auto want_prelu = [&](const float* w, const float* b, const float* a) { return want(w) || want(b) || want(a); };
+    const bool dec = want(Gr->dec_w) || want(Gr->dec_b) || want(Gr->dec_a) || want(Gr->fin_w) || want(Gr->fin_b);
+    const bool fuse = want_prelu(Gr->fuse_res_w[0], Gr->fuse_res_b[0], Gr->fuse_res_a[0]) ||
+                      want_prelu(Gr->fuse_res_w[1], Gr->fuse_res_b[1], Gr->fuse_res_a[1]) ||
+                      want_prelu(Gr->fuse_out_w, Gr->fuse_out_b, Gr->fuse_out_a);
+    const bool alpha = d_alphas && alpha_residual;
+    bool need_da[HRN_MAX_RES_LAYERS + 1], need_ds[TMAX + 1];
+    need_da[0] = want_prelu(Gr->enc_init_w, Gr->enc_init_b, Gr->enc_init_a) || d_lrs;
+    for (int l = 0; l < nl; ++l)
+        need_da[l + 1] = need_da[l] || want_prelu(Gr->enc_res_w[2 * l], Gr->enc_res_b[2 * l], Gr->enc_res_a[2 * l]) ||
+                         want_prelu(Gr->enc_res_w[2 * l + 1], Gr->enc_res_b[2 * l + 1], Gr->enc_res_a[2 * l + 1]);
+    need_ds[0] = need_da[nl] || want(Gr->enc_final_w) || want(Gr->enc_final_b);
+    for (int t = 0; t < L.T; ++t) need_ds[t + 1] = need_ds[t] || fuse || alpha;
+
+    hipStream_t s = (hipStream_t)stream;
+    const size_t hw = (size_t)H * W;
+    const int M = B * V, cus = num_cus();
+    void* sc = at(tws, L.scratch);
+    float* G[5];
+    for (int i = 0; i < 5; ++i) G[i] = (float*)at(tws, L.g[i]);
+    HRN_HIP(hipMemsetAsync(at(tws, L.zero_bias), 0, 128 * 4, s));
+    // d alphas: views that are never bob (view 0, views dropped by parity) and every view without the alpha residual get 0
+    if (d_alphas) HRN_HIP(hipMemsetAsync(d_alphas, 0, (size_t)B * V * 4, s));
+    if (!dec && !need_ds[L.T]) return 0;
+    // gradients are handed over as mutable buffers in a params-shaped struct
+    auto mut = [](const float* p) { return const_cast<float*>(p); };
+    // PReLU backward works from the stored post-activation while the slope is positive.  For a slope <= 0 (the reference allows any)
+    // the pre-activation is recomputed into `xpre` by the forward kernel without activation - a launch that does nothing unless the
+    // slope on the device says so (ConvParams::only_if_nonpos): no host round trip, ~3 us per PReLU in the usual case.
+    const HrnetLayout P = hrnet_layout(dt, nl, scale);
+    float* xpre = (float*)at(tws, L.xpre);
+    auto pre = [&](int cin, int cout, const void* x, const void* wpk, const float* bias, const float* slope, int Mi) -> int {
+        ConvParams q = conv_base(Mi, H, W);
+        q.in = x; q.out = xpre; q.wpk = wpk; q.bias = bias; q.only_if_nonpos = slope;
+        q.in_lo = lo_of(dt, (size_t)Mi * hw * cin); q.out_lo = lo_of(dt, (size_t)Mi * hw * cout);
+        return hrn_launch_conv3x3(dt, cin, cout, q, s);
+    };
+
+    // ---- decoder: d_sr -> d stack_T (one view left)                                  HRNet.py:147-156,167-169
+    // (one launch gives the weight-gradient partials and d stack_T; its finish, which only sums the partials, runs for decoder parameters)
+    float* dsn = G[0];                      // gradient of the views leaving the current level
+    if (dt != HRN_F32) {
+        // the decoder's backward is the fp32 kernel (33 MB of state at the training shape): the fused state as f32, its gradient back as planes
+        const size_t nf = (size_t)B * L.n_in[L.T] * hw * 64;
+        float* ff = (float*)at(tws, L.dec_f);
+        float* fg = (float*)at(tws, L.dec_g);
+        if ((rc = hrn_launch_planes_to_f32(at(tws, L.stack[L.T]), lo_of(dt, nf), ff, nf, s))) return rc;
+        if ((rc = hrn_launch_decoder_bwd(ff, d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, fg,
+                                         mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a), mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s,
+                                         scale)))
+            return rc;
+        if (need_ds[L.T] && (rc = hrn_launch_f32_to_planes(fg, dsn, lo_of(dt, nf), nf, s))) return rc;
+    } else if ((rc = hrn_launch_decoder_bwd((const float*)at(tws, L.stack[L.T]), d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, dsn,
+                                            mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a), mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s,
+                                            scale)))
+        return rc;
+    if (!need_ds[L.T]) return 0;
+
+    // ---- fusion levels, last to first                                                HRNet.py:113-132
+    // below: the level's input gradient ds is read (a lower level or the encoder); each convolution's PReLU backward runs when its data
+    // gradient or one of its own parameters is wanted, and its data gradient when the PReLU backward before it runs
+    const bool wA = want_prelu(Gr->fuse_res_w[0], Gr->fuse_res_b[0], Gr->fuse_res_a[0]);
+    const bool wB = want_prelu(Gr->fuse_res_w[1], Gr->fuse_res_b[1], Gr->fuse_res_a[1]);
+    const bool wC = want_prelu(Gr->fuse_out_w, Gr->fuse_out_b, Gr->fuse_out_a);
+    for (int t = L.T - 1; t >= 0; --t) {
+        const int n = L.n_in[t], half = n / 2, pair_last = n - (n & 1) - 1, Mh = B * half;
+        const bool below = need_ds[t];
+        const bool prA = below || wA, prB = prA || wB, dgC = prB || below, prC = dgC || wC;
+        const float* st = (const float*)at(tws, L.stack[t]);
+        // every G buffer holds B*V*hw*64 floats; Mh <= B*V/2, so one buffer also holds an [Mh][hw][128] tensor
+        float* y1 = G[1];                   // d t2               [Mh][hw][128]; dead before ds is written into the same buffer
+        float* ds = G[1];                   // gradient of the views entering the level  [B*n][hw][64]
+        float* x1 = G[2];                   // df / gC            [Mh][hw][64]
+        float* y3 = G[3];                   // d t1 / gA          [Mh][hw][128]
+        float* y2 = G[4];                   // gB, later dz       [Mh][hw][128]
+        if (prC && (rc = hrn_launch_fuse_df(dsn, alphas, V, pair_last, half, alpha_residual, x1, hw, B, s, dt))) return rc;
+        // x_new = alice + a_bob f: d a_bob = sum dsn f while both are live (the scratch is free until the PReLU backward below)
+        if (alpha && (rc = hrn_launch_alpha_grad(dsn, (const float*)at(tws, L.f[t]), half, pair_last, d_alphas, B, V, hw, sc, L.dec_f - L.scratch, s, dt)))
+            return rc;
+        // f = PReLU(convC(t2))
+        if (prC) {
+            if ((rc = pre(128, 64, at(tws, L.t2[t]), at(pk, P.fout_w), (const float*)at(pk, P.fout_b), Pr->fuse_out_a, Mh))) return rc;
+            if ((rc = hrn_launch_prelu_bwd_bias(x1, (const float*)at(tws, L.f[t]), xpre, Pr->fuse_out_a, x1, (size_t)Mh * hw, 64, mut(Gr->fuse_out_a), mut(Gr->fuse_out_b), sc, s, dt))) return rc;
+        }
+        if (want(Gr->fuse_out_w) && (rc = conv_wgrad(dt, (const float*)at(tws, L.t2[t]), nullptr, 0, 0, 0, B, x1, Mh, H, W, 128, 64, mut(Gr->fuse_out_w), sc, cus, s))) return rc;
+        if (dgC && (rc = conv_dgrad(dt, 128, 64, Pr->fuse_out_w, x1, y1, nullptr, Mh, H, W, tws, L, s))) return rc;
+        // t2 = z + u, u = PReLU(convB(t1))
+        if (prB) {
+            if ((rc = pre(128, 128, at(tws, L.t1[t]), at(pk, P.fres_w[1]), (const float*)at(pk, P.fres_b[1]), Pr->fuse_res_a[1], Mh))) return rc;
+            if ((rc = hrn_launch_prelu_bwd_bias(y1, (const float*)at(tws, L.u[t]), xpre, Pr->fuse_res_a[1], y2, (size_t)Mh * hw, 128, mut(Gr->fuse_res_a[1]), mut(Gr->fuse_res_b[1]), sc, s, dt))) return rc;
+        }
+        if (want(Gr->fuse_res_w[1]) && (rc = conv_wgrad(dt, (const float*)at(tws, L.t1[t]), nullptr, 0, 0, 0, B, y2, Mh, H, W, 128, 128, mut(Gr->fuse_res_w[1]), sc, cus, s))) return rc;
+        if (prA && (rc = conv_dgrad(dt, 128, 128, Pr->fuse_res_w[1], y2, y3, nullptr, Mh, H, W, tws, L, s))) return rc;
+        // t1 = PReLU(convA(z))
+        if (prA) {
+            ConvParams q = conv_base(Mh, H, W);
+            q.in_pair = 1; q.stack = st; q.pair_h = half; q.pair_last = pair_last; q.pair_vs = n;
+            q.out = xpre; q.wpk = at(pk, P.fres_w[0]); q.bias = (const float*)at(pk, P.fres_b[0]); q.only_if_nonpos = Pr->fuse_res_a[0];
+            q.stack_lo = lo_of(dt, (size_t)B * n * hw * 64); q.out_lo = lo_of(dt, (size_t)Mh * hw * 128);
+            if ((rc = hrn_launch_conv3x3(dt, 128, 128, q, s))) return rc;
+            if ((rc = hrn_launch_prelu_bwd_bias(y3, (const float*)at(tws, L.t1[t]), xpre, Pr->fuse_res_a[0], y3, (size_t)Mh * hw, 128, mut(Gr->fuse_res_a[0]), mut(Gr->fuse_res_b[0]), sc, s, dt))) return rc;
+        }
+        if (want(Gr->fuse_res_w[0]) && (rc = conv_wgrad(dt, nullptr, st, half, pair_last, n, B, y3, Mh, H, W, 128, 128, mut(Gr->fuse_res_w[0]), sc, cus, s))) return rc;
+        if (!below) continue;               // (then no level below and not the encoder reads ds: the levels left run only their alpha_grad)
+        if ((rc = conv_dgrad(dt, 128, 128, Pr->fuse_res_w[0], y3, y2, y1, Mh, H, W, tws, L, s))) return rc;     // dz = d t2 + dgradA(gA)
+        // dz -> the two views of each pair (+ the alice pass-through)
+        if ((rc = hrn_launch_fuse_scatter(dsn, y2, n, half, pair_last, alpha_residual, ds, hw, B, s, dt))) return rc;
+        float* tmp = G[0]; G[0] = G[1]; G[1] = tmp;
+        dsn = G[0];
+    }
+    if (!need_ds[0]) return 0;
+
+    // ---- encoder                                                                     HRNet.py:51-60,62-74
+    float* dA = G[1];
+    if (want(Gr->enc_final_w) && (rc = conv_wgrad(dt, (const float*)at(tws, L.a[nl]), nullptr, 0, 0, 0, B, dsn, M, H, W, 64, 64, mut(Gr->enc_final_w), sc, cus, s))) return rc;
+    if (want(Gr->enc_final_b) && (rc = hrn_launch_colsum(dsn, (size_t)M * hw, 64, mut(Gr->enc_final_b), sc, s, dt))) return rc;
+    if (!need_da[nl]) return 0;
+    if ((rc = conv_dgrad(dt, 64, 64, Pr->enc_final_w, dsn, dA, nullptr, M, H, W, tws, L, s))) return rc;
+    float* e2 = G[2];
+    float* e3 = G[3];
+    for (int l = nl - 1; l >= 0; --l) {
+        // a_{l+1} = a_l + r_l,  r_l = PReLU(conv2(h_l)),  h_l = PReLU(conv1(a_l));  d a_{l+1} (dA) is wanted here
+        const int j1 = 2 * l, j2 = 2 * l + 1;
+        const bool pr1 = need_da[l] || want_prelu(Gr->enc_res_w[j1], Gr->enc_res_b[j1], Gr->enc_res_a[j1]);
+        const bool pr2 = pr1 || want_prelu(Gr->enc_res_w[j2], Gr->enc_res_b[j2], Gr->enc_res_a[j2]);
+        if (pr2) {
+            if ((rc = pre(64, 64, at(tws, L.h[l]), at(pk, P.enc_w[j2]), (const float*)at(pk, P.enc_b[j2]), Pr->enc_res_a[j2], M))) return rc;
+            if ((rc = hrn_launch_prelu_bwd_bias(dA, (const float*)at(tws, L.r[l]), xpre, Pr->enc_res_a[j2], e2, (size_t)M * hw, 64, mut(Gr->enc_res_a[j2]), mut(Gr->enc_res_b[j2]), sc, s, dt))) return rc;
+        }
+        if (want(Gr->enc_res_w[j2]) && (rc = conv_wgrad(dt, (const float*)at(tws, L.h[l]), nullptr, 0, 0, 0, B, e2, M, H, W, 64, 64, mut(Gr->enc_res_w[j2]), sc, cus, s))) return rc;
+        if (pr1) {
+            if ((rc = conv_dgrad(dt, 64, 64, Pr->enc_res_w[j2], e2, e3, nullptr, M, H, W, tws, L, s))) return rc;
+            if ((rc = pre(64, 64, at(tws, L.a[l]), at(pk, P.enc_w[j1]), (const float*)at(pk, P.enc_b[j1]), Pr->enc_res_a[j1], M))) return rc;
+            if ((rc = hrn_launch_prelu_bwd_bias(e3, (const float*)at(tws, L.h[l]), xpre, Pr->enc_res_a[j1], e3, (size_t)M * hw, 64, mut(Gr->enc_res_a[j1]), mut(Gr->enc_res_b[j1]), sc, s, dt))) return rc;
+        }
+        if (want(Gr->enc_res_w[j1]) && (rc = conv_wgrad(dt, (const float*)at(tws, L.a[l]), nullptr, 0, 0, 0, B, e3, M, H, W, 64, 64, mut(Gr->enc_res_w[j1]), sc, cus, s))) return rc;
+        if (!need_da[l]) return 0;
+        if ((rc = conv_dgrad(dt, 64, 64, Pr->enc_res_w[j1], e3, e2, dA, M, H, W, tws, L, s))) return rc;       // d a_l = d a_{l+1} + dgrad1(g1)
+        float* tmp = dA; dA = e2; e2 = tmp;
+    }
+    // stem: a_0 = PReLU(conv(cat(view, reference frame)))                               HRNet.py:200-204, :51-53
+    if ((rc = hrn_launch_stem_pre(lrs, hw, (const float*)at(tws, L.ref), V, hw, (const float*)at(pk, P.stem_w), (const float*)at(pk, P.stem_b), xpre, M, H, W,
+                                  Pr->enc_init_a, s, dt))) return rc;
+    if ((rc = hrn_launch_prelu_bwd_bias(dA, (const float*)at(tws, L.a[0]), xpre, Pr->enc_init_a, dA, (size_t)M * hw, 64, mut(Gr->enc_init_a), mut(Gr->enc_init_b), sc, s, dt))) return rc;
+    if (want(Gr->enc_init_w) && (rc = hrn_launch_stem_wgrad(lrs, hw, (const float*)at(tws, L.ref), V, hw, dA, M, H, W, mut(Gr->enc_init_w), sc, cus, s, dt))) return rc;
+    // d lrs: the stem's input gradient, channel 1 (the reference frame) routed to the view the median picked
+    if (d_lrs) return hrn_launch_stem_dgrad_route(dA, Pr->enc_init_w, (float*)at(tws, L.wt), lrs, (const float*)at(tws, L.ref), d_lrs, B, V, H, W, s, dt);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -235,127 +409,13 @@ int hrn_hrnet_backward_s(const void* pk, int dt, int scale, const hrn_hrnet_para
 int hrn_hrnet_backward_in(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
                           int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, float* d_lrs, float* d_alphas, void* tws,
                           size_t tws_bytes, void* stream) {
-    int rc;
-    HRN_CHECK(hrn_scale_ok(scale), -2, "hrn_hrnet_backward: scale must be 2, 3 or 4 (got %d)", scale);
-    HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16 || dt == HRN_BF16X3, -2, "hrn_hrnet_backward: dtype must be HRN_DTYPE_F32, HRN_DTYPE_BF16 or HRN_DTYPE_BF16X3 (got %d)", dt);
-    HRN_CHECK(pk && Pr && Gr && lrs && alphas && d_sr && tws, -2, "hrn_hrnet_backward: null argument");
-    if ((rc = check_aligned("hrn_hrnet_backward", dt, pk, tws))) return rc;
-    const int nl = Pr->num_layers;
-    if ((rc = check_train(nl, B, V, H, W))) return rc;
-    const TrainWs L = train_ws(nl, B, V, H, W);
-    HRN_CHECK(tws_bytes >= L.total, -3, "hrn_hrnet_backward: workspace too small (%zu < %zu)", tws_bytes, L.total);
-    for (int t = 0; d_alphas && t < L.T; ++t)
-        HRN_CHECK(hrn_alpha_grad_scratch_bytes(B * (L.n_in[t] / 2)) <= L.dec_f - L.scratch, -3, "hrn_hrnet_backward_in: scratch too small for d_alphas");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t hw = (size_t)H * W;
-    const int M = B * V, cus = num_cus();
-    void* sc = at(tws, L.scratch);
-    float* G[5];
-    for (int i = 0; i < 5; ++i) G[i] = (float*)at(tws, L.g[i]);
-    HRN_HIP(hipMemsetAsync(at(tws, L.zero_bias), 0, 128 * 4, s));
-    // d alphas: views that are never bob (view 0, views dropped by parity) and every view without the alpha residual get 0
-    if (d_alphas) HRN_HIP(hipMemsetAsync(d_alphas, 0, (size_t)B * V * 4, s));
-    // gradients are handed over as mutable buffers in a params-shaped struct
-    auto mut = [](const float* p) { return const_cast<float*>(p); };
-    // PReLU backward works from the stored post-activation while the slope is positive.  For a slope <= 0 (the reference allows any)
-    // the pre-activation is recomputed into `xpre` by the forward kernel without activation - a launch that does nothing unless the
-    // slope on the device says so (ConvParams::only_if_nonpos): no host round trip, ~3 us per PReLU in the usual case.
-    const HrnetLayout P = hrnet_layout(dt, nl, scale);
-    float* xpre = (float*)at(tws, L.xpre);
-    auto pre = [&](int cin, int cout, const void* x, const void* wpk, const float* bias, const float* slope, int Mi) -> int {
-        ConvParams q = conv_base(Mi, H, W);
-        q.in = x; q.out = xpre; q.wpk = wpk; q.bias = bias; q.only_if_nonpos = slope;
-        q.in_lo = lo_of(dt, (size_t)Mi * hw * cin); q.out_lo = lo_of(dt, (size_t)Mi * hw * cout);
-        return hrn_launch_conv3x3(dt, cin, cout, q, s);
-    };
+    return hrnet_backward_impl(pk, dt, scale, Pr, alpha_residual, lrs, alphas, B, V, H, W, d_sr, Gr, d_lrs, d_alphas, tws, tws_bytes, stream, false);
+}
 
-    // ---- decoder: d_sr -> d stack_T (one view left)                                  HRNet.py:147-156,167-169
-    float* dsn = G[0];                      // gradient of the views leaving the current level
-    if (dt != HRN_F32) {
-        // the decoder's backward is the fp32 kernel (33 MB of state at the training shape): the fused state as f32, its gradient back as planes
-        const size_t nf = (size_t)B * L.n_in[L.T] * hw * 64;
-        float* ff = (float*)at(tws, L.dec_f);
-        float* fg = (float*)at(tws, L.dec_g);
-        if ((rc = hrn_launch_planes_to_f32(at(tws, L.stack[L.T]), lo_of(dt, nf), ff, nf, s))) return rc;
-        if ((rc = hrn_launch_decoder_bwd(ff, d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, fg,
-                                         mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a), mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s,
-                                         scale)))
-            return rc;
-        if ((rc = hrn_launch_f32_to_planes(fg, dsn, lo_of(dt, nf), nf, s))) return rc;
-    } else if ((rc = hrn_launch_decoder_bwd((const float*)at(tws, L.stack[L.T]), d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, dsn,
-                                            mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a), mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s,
-                                            scale)))
-        return rc;
-
-    // ---- fusion levels, last to first                                                HRNet.py:113-132
-    for (int t = L.T - 1; t >= 0; --t) {
-        const int n = L.n_in[t], half = n / 2, pair_last = n - (n & 1) - 1, Mh = B * half;
-        const float* st = (const float*)at(tws, L.stack[t]);
-        // every G buffer holds B*V*hw*64 floats; Mh <= B*V/2, so one buffer also holds an [Mh][hw][128] tensor
-        float* y1 = G[1];                   // d t2               [Mh][hw][128]; dead before ds is written into the same buffer
-        float* ds = G[1];                   // gradient of the views entering the level  [B*n][hw][64]
-        float* x1 = G[2];                   // df / gC            [Mh][hw][64]
-        float* y3 = G[3];                   // d t1 / gA          [Mh][hw][128]
-        float* y2 = G[4];                   // gB, later dz       [Mh][hw][128]
-        if ((rc = hrn_launch_fuse_df(dsn, alphas, V, pair_last, half, alpha_residual, x1, hw, B, s, dt))) return rc;
-        // x_new = alice + a_bob f: d a_bob = sum dsn f while both are live (the scratch is free until the PReLU backward below)
-        if (d_alphas && alpha_residual &&
-            (rc = hrn_launch_alpha_grad(dsn, (const float*)at(tws, L.f[t]), half, pair_last, d_alphas, B, V, hw, sc, L.dec_f - L.scratch, s, dt)))
-            return rc;
-        // f = PReLU(convC(t2))
-        if ((rc = pre(128, 64, at(tws, L.t2[t]), at(pk, P.fout_w), (const float*)at(pk, P.fout_b), Pr->fuse_out_a, Mh))) return rc;
-        if ((rc = hrn_launch_prelu_bwd_bias(x1, (const float*)at(tws, L.f[t]), xpre, Pr->fuse_out_a, x1, (size_t)Mh * hw, 64, mut(Gr->fuse_out_a), mut(Gr->fuse_out_b), sc, s, dt))) return rc;
-        if ((rc = conv_wgrad(dt, (const float*)at(tws, L.t2[t]), nullptr, 0, 0, 0, B, x1, Mh, H, W, 128, 64, mut(Gr->fuse_out_w), sc, cus, s))) return rc;
-        if ((rc = conv_dgrad(dt, 128, 64, Pr->fuse_out_w, x1, y1, nullptr, Mh, H, W, tws, L, s))) return rc;
-        // t2 = z + u, u = PReLU(convB(t1))
-        if ((rc = pre(128, 128, at(tws, L.t1[t]), at(pk, P.fres_w[1]), (const float*)at(pk, P.fres_b[1]), Pr->fuse_res_a[1], Mh))) return rc;
-        if ((rc = hrn_launch_prelu_bwd_bias(y1, (const float*)at(tws, L.u[t]), xpre, Pr->fuse_res_a[1], y2, (size_t)Mh * hw, 128, mut(Gr->fuse_res_a[1]), mut(Gr->fuse_res_b[1]), sc, s, dt))) return rc;
-        if ((rc = conv_wgrad(dt, (const float*)at(tws, L.t1[t]), nullptr, 0, 0, 0, B, y2, Mh, H, W, 128, 128, mut(Gr->fuse_res_w[1]), sc, cus, s))) return rc;
-        if ((rc = conv_dgrad(dt, 128, 128, Pr->fuse_res_w[1], y2, y3, nullptr, Mh, H, W, tws, L, s))) return rc;
-        // t1 = PReLU(convA(z))
-        {
-            ConvParams q = conv_base(Mh, H, W);
-            q.in_pair = 1; q.stack = st; q.pair_h = half; q.pair_last = pair_last; q.pair_vs = n;
-            q.out = xpre; q.wpk = at(pk, P.fres_w[0]); q.bias = (const float*)at(pk, P.fres_b[0]); q.only_if_nonpos = Pr->fuse_res_a[0];
-            q.stack_lo = lo_of(dt, (size_t)B * n * hw * 64); q.out_lo = lo_of(dt, (size_t)Mh * hw * 128);
-            if ((rc = hrn_launch_conv3x3(dt, 128, 128, q, s))) return rc;
-        }
-        if ((rc = hrn_launch_prelu_bwd_bias(y3, (const float*)at(tws, L.t1[t]), xpre, Pr->fuse_res_a[0], y3, (size_t)Mh * hw, 128, mut(Gr->fuse_res_a[0]), mut(Gr->fuse_res_b[0]), sc, s, dt))) return rc;
-        if ((rc = conv_wgrad(dt, nullptr, st, half, pair_last, n, B, y3, Mh, H, W, 128, 128, mut(Gr->fuse_res_w[0]), sc, cus, s))) return rc;
-        if ((rc = conv_dgrad(dt, 128, 128, Pr->fuse_res_w[0], y3, y2, y1, Mh, H, W, tws, L, s))) return rc;     // dz = d t2 + dgradA(gA)
-        // dz -> the two views of each pair (+ the alice pass-through)
-        if ((rc = hrn_launch_fuse_scatter(dsn, y2, n, half, pair_last, alpha_residual, ds, hw, B, s, dt))) return rc;
-        float* tmp = G[0]; G[0] = G[1]; G[1] = tmp;
-        dsn = G[0];
-    }
-
-    // ---- encoder                                                                     HRNet.py:51-60,62-74
-    float* dA = G[1];
-    if ((rc = conv_wgrad(dt, (const float*)at(tws, L.a[nl]), nullptr, 0, 0, 0, B, dsn, M, H, W, 64, 64, mut(Gr->enc_final_w), sc, cus, s))) return rc;
-    if ((rc = hrn_launch_colsum(dsn, (size_t)M * hw, 64, mut(Gr->enc_final_b), sc, s, dt))) return rc;
-    if ((rc = conv_dgrad(dt, 64, 64, Pr->enc_final_w, dsn, dA, nullptr, M, H, W, tws, L, s))) return rc;
-    float* e2 = G[2];
-    float* e3 = G[3];
-    for (int l = nl - 1; l >= 0; --l) {
-        // a_{l+1} = a_l + r_l,  r_l = PReLU(conv2(h_l)),  h_l = PReLU(conv1(a_l))
-        if ((rc = pre(64, 64, at(tws, L.h[l]), at(pk, P.enc_w[2 * l + 1]), (const float*)at(pk, P.enc_b[2 * l + 1]), Pr->enc_res_a[2 * l + 1], M))) return rc;
-        if ((rc = hrn_launch_prelu_bwd_bias(dA, (const float*)at(tws, L.r[l]), xpre, Pr->enc_res_a[2 * l + 1], e2, (size_t)M * hw, 64, mut(Gr->enc_res_a[2 * l + 1]), mut(Gr->enc_res_b[2 * l + 1]), sc, s, dt))) return rc;
-        if ((rc = conv_wgrad(dt, (const float*)at(tws, L.h[l]), nullptr, 0, 0, 0, B, e2, M, H, W, 64, 64, mut(Gr->enc_res_w[2 * l + 1]), sc, cus, s))) return rc;
-        if ((rc = conv_dgrad(dt, 64, 64, Pr->enc_res_w[2 * l + 1], e2, e3, nullptr, M, H, W, tws, L, s))) return rc;
-        if ((rc = pre(64, 64, at(tws, L.a[l]), at(pk, P.enc_w[2 * l]), (const float*)at(pk, P.enc_b[2 * l]), Pr->enc_res_a[2 * l], M))) return rc;
-        if ((rc = hrn_launch_prelu_bwd_bias(e3, (const float*)at(tws, L.h[l]), xpre, Pr->enc_res_a[2 * l], e3, (size_t)M * hw, 64, mut(Gr->enc_res_a[2 * l]), mut(Gr->enc_res_b[2 * l]), sc, s, dt))) return rc;
-        if ((rc = conv_wgrad(dt, (const float*)at(tws, L.a[l]), nullptr, 0, 0, 0, B, e3, M, H, W, 64, 64, mut(Gr->enc_res_w[2 * l]), sc, cus, s))) return rc;
-        if ((rc = conv_dgrad(dt, 64, 64, Pr->enc_res_w[2 * l], e3, e2, dA, M, H, W, tws, L, s))) return rc;       // d a_l = d a_{l+1} + dgrad1(g1)
-        float* tmp = dA; dA = e2; e2 = tmp;
-    }
-    // stem: a_0 = PReLU(conv(cat(view, reference frame)))                               HRNet.py:200-204, :51-53
-    if ((rc = hrn_launch_stem_pre(lrs, hw, (const float*)at(tws, L.ref), V, hw, (const float*)at(pk, P.stem_w), (const float*)at(pk, P.stem_b), xpre, M, H, W,
-                                  Pr->enc_init_a, s, dt))) return rc;
-    if ((rc = hrn_launch_prelu_bwd_bias(dA, (const float*)at(tws, L.a[0]), xpre, Pr->enc_init_a, dA, (size_t)M * hw, 64, mut(Gr->enc_init_a), mut(Gr->enc_init_b), sc, s, dt))) return rc;
-    if ((rc = hrn_launch_stem_wgrad(lrs, hw, (const float*)at(tws, L.ref), V, hw, dA, M, H, W, mut(Gr->enc_init_w), sc, cus, s, dt))) return rc;
-    // d lrs: the stem's input gradient, channel 1 (the reference frame) routed to the view the median picked
-    if (d_lrs) return hrn_launch_stem_dgrad_route(dA, Pr->enc_init_w, (float*)at(tws, L.wt), lrs, (const float*)at(tws, L.ref), d_lrs, B, V, H, W, s, dt);
-    return 0;
+int hrn_hrnet_backward_sel(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
+                           int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, float* d_lrs, float* d_alphas, void* tws,
+                           size_t tws_bytes, void* stream) {
+    return hrnet_backward_impl(pk, dt, scale, Pr, alpha_residual, lrs, alphas, B, V, H, W, d_sr, Gr, d_lrs, d_alphas, tws, tws_bytes, stream, true);
 }
 
 }  // extern "C"

@@ -6,10 +6,14 @@
 
 at the reference's training shape (config/config.json: batch 32, up to 32 views, 64 x 64 patches) with synthetic data.
 usage: python tools/train_step_bench.py [B V S steps] [--torch-adam] [--precision P[,P...]] [--shiftnet-precision P[,P...]] [--repeats R]
+                                        [--freeze F[,F...]]
 
 --precision sets HRNet.train_precision (fp32, bf16x3 or bf16; default: not set, i.e. the module's default rules), --shiftnet-precision
 ShiftNet.train_precision (fp32 or bf16; default: not set).  With several values, one pair of models per combination is built and their
-timing rounds alternate, R rounds each (--repeats, default 1).
+timing rounds alternate, R rounds each (--repeats, default 1).  --freeze times the step with part of the models frozen
+(requires_grad_(False) before the optimiser is built, as in fine-tuning): none (default), encoder (HRNet's encoder), encoder+fuse (HRNet's
+encoder and fusion block: only the decoder trains) or shiftnet (a fixed ShiftNet that only passes d x back into HRNet); several values
+alternate in one process like the precisions.
 """
 import os
 import sys
@@ -45,7 +49,7 @@ def get_loss_cpsnr(srs, hrs, hr_maps):                        # train.py:66-87
 def _options(argv):
     pos, opts, i = [], {}, 0
     while i < len(argv):
-        if argv[i] in ("--precision", "--shiftnet-precision", "--repeats"):
+        if argv[i] in ("--precision", "--shiftnet-precision", "--repeats", "--freeze"):
             opts[argv[i]] = argv[i + 1]
             i += 2
         else:
@@ -55,9 +59,13 @@ def _options(argv):
     return pos, opts
 
 
+FREEZE = {"none": lambda k: False, "encoder": lambda k: k.startswith("fusion.encode."),
+          "encoder+fuse": lambda k: k.startswith(("fusion.encode.", "fusion.fuse.")), "shiftnet": lambda k: k.startswith("regis.")}
+
+
 def _label(key):
-    p, sp = key
-    return f"train_precision={p}" + (f" shiftnet_train_precision={sp}" if sp is not None else "")
+    p, sp, fr = key
+    return f"train_precision={p}" + (f" shiftnet_train_precision={sp}" if sp is not None else "") + (f" freeze={fr}" if fr != "none" else "")
 
 
 def main():
@@ -66,6 +74,10 @@ def main():
     precs = opts["--precision"].split(",") if "--precision" in opts else [None]
     sprecs = opts["--shiftnet-precision"].split(",") if "--shiftnet-precision" in opts else [None]
     repeats = int(opts.get("--repeats", 1))
+    freezes = opts.get("--freeze", "none").split(",")
+    for f in freezes:
+        if f not in FREEZE:
+            raise SystemExit(f"--freeze: {', '.join(FREEZE)} (got {f!r})")
     for p in precs:
         if p not in (None, "fp32", "bf16x3", "bf16"):
             raise SystemExit(f"--precision: fp32, bf16x3 or bf16 (got {p!r})")
@@ -81,7 +93,7 @@ def main():
     x, a = torch.from_numpy(lrs).to(dev), torch.from_numpy(alphas).to(dev)
     off = (3 * S - 128) // 2
 
-    def setup(prec, sprec):
+    def setup(prec, sprec, freeze):
         fusion = HRNet({k: dict(v) for k, v in weights.HRNET_CONFIG.items()})
         fusion.load_state_dict(weights.to_torch_state(weights.hrnet_state(1234)))
         fusion.train_precision = prec
@@ -90,6 +102,9 @@ def main():
             regis.train_precision = sprec
         regis.load_state_dict(weights.to_torch_state(weights.shiftnet_state(4321)))
         fusion, regis = fusion.to(dev).train(), regis.to(dev).train()
+        for prefix, mod in (("fusion.", fusion), ("regis.", regis)):
+            for k, p in mod.named_parameters():
+                p.requires_grad_(not FREEZE[freeze](prefix + k))
         params = list(fusion.parameters()) + list(regis.parameters())
         opt = torch.optim.Adam(params, lr=1e-4) if "--torch-adam" in sys.argv else FusedAdam(params, lr=1e-4)
         return fusion, regis, opt
@@ -105,7 +120,7 @@ def main():
         opt.step()
         return loss
 
-    runs = {(p, sp): setup(p, sp) for p in precs for sp in sprecs}
+    runs = {(p, sp, f): setup(p, sp, f) for p in precs for sp in sprecs for f in freezes}
     for r in runs.values():
         for _ in range(2):
             step(*r)
