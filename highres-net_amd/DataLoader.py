@@ -5,7 +5,9 @@
 Directory listing, clearance loading, the clearance-softmax view sampling and the random patch corner stay in Python and
 draw from numpy's global RNG in the reference's order (so a seeded run picks the same views and patch); the byte work -
 PNG decode, crop, uint16 -> float32, padding - runs in libhrnet_io.so (`hrnet_hip.io_binding`).  Beyond the reference's
-surface, `ImagesetDataset.load_batch()` collates a whole batch straight into (optionally pinned) buffers on a thread pool.
+surface, `ImagesetDataset.load_batch()` collates a whole batch straight into (optionally pinned) buffers on a thread pool,
+and `ImagesetDataset.to_device()` decodes the whole split once into HBM (DeviceImagesetCache), after which every batch is one
+kernel launch (`hrn_collate_device`) with the same RNG draws and bit-identical values.
 """
 from collections import OrderedDict
 import operator
@@ -16,7 +18,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-from hrnet_hip import io_binding
+from hrnet_hip import binding, io_binding
 
 _QM_FILE = re.compile(r"^QM(.*)\.png$", re.S)       # one quality map per LR view; the text between "QM" and ".png" is the view id
 
@@ -55,18 +57,27 @@ def sample_clearest(clearances, n=None, beta=50, seed=None):
     return np.random.choice(len(weights), size=n, replace=False, p=weights / np.sum(weights))
 
 
-def _views_in_use_order(imset_dir, top_k, beta, seed):
-    """(view ids, clearances) of an imageset in the order the model consumes them: `top_k` > 0 -> a clearance-weighted sample of
-    min(top_k, L) views (sample_clearest), else all views from the clearest down."""
+def _list_views(imset_dir):
+    """(sorted view ids, clearances) of an imageset directory; no RNG."""
     ids = np.sort(np.array([m.group(1) for m in map(_QM_FILE.match, os.listdir(imset_dir)) if m]))
     score_file = os.path.join(imset_dir, "clearance.npy")
     if not os.path.isfile(score_file):
         raise Exception("please call the save_clearance.py before call DataLoader")
-    scores = np.load(score_file)
+    return ids, np.load(score_file)
+
+
+def _pick_views(scores, n_views, top_k, beta, seed):
+    """Positions (into the sorted ids) of the views in use order: `top_k` > 0 -> a clearance-weighted sample of min(top_k, L)
+    views (sample_clearest), else all views from the clearest down."""
     if top_k is not None and top_k > 0:
-        pick = sample_clearest(scores, n=min(top_k, len(ids)), beta=beta, seed=seed)
-    else:
-        pick = np.flip(np.argsort(scores))
+        return sample_clearest(scores, n=min(top_k, n_views), beta=beta, seed=seed)
+    return np.flip(np.argsort(scores))
+
+
+def _views_in_use_order(imset_dir, top_k, beta, seed):
+    """(view ids, clearances) of an imageset in the order the model consumes them (_pick_views)."""
+    ids, scores = _list_views(imset_dir)
+    pick = _pick_views(scores, len(ids), top_k, beta, seed)
     return ids[pick], scores[pick]
 
 
@@ -163,6 +174,174 @@ class ImagesetDataset(Dataset):
         io_binding.collate([p["lr_paths"] for p in plans], [p["hr"] for p in plans] if have_hr else None, [p["sm"] for p in plans],
                            min_L=min_L, lr_size=side, patch=patch, corners=[p["corner"] for p in plans], out=out, n_threads=n_threads)
         return out["lrs"], out["alphas"], out["hrs"] if have_hr else [], out["maps"], [p["name"] for p in plans]
+
+
+    def to_device(self, device="cuda", n_threads=0):
+        """Decode every imageset once into HBM and return a DeviceImagesetCache: `cache.load_batch(indices, min_L)` then
+        builds each batch on the GPU with one kernel, bit-identical to `load_batch` and from the same numpy RNG draws."""
+        return DeviceImagesetCache(self, device=device, n_threads=n_threads)
+
+
+def _round4(n):
+    return (n + 3) // 4 * 4
+
+
+class ImagesetIndex:
+    """The host half of DeviceImagesetCache, no GPU: every imageset directory listed once, clearance.npy loaded once, the LR
+    side read from one header, and where each image lives in the three arenas (LR / HR uint16, SM uint8; every image starts
+    at a multiple of 4 elements, as hrn_collate_device requires).  `plan()` turns a batch of indices into the kernel's plan
+    table with exactly the numpy RNG calls ImagesetDataset._plan makes, in the same order."""
+
+    def __init__(self, dataset):
+        self.dataset = dataset
+        self.dirs = list(dataset.imset_dir)
+        self.names = [os.path.basename(d) for d in self.dirs]
+        self.position = dict(zip(self.names, range(len(self.dirs))))      # a repeated name resolves to its last directory, as name_to_dir
+        self.ids, self.clearances, self.sides, self.lr_off, self.hr_off, self.sm_off = [], [], [], [], [], []
+        lr_total = hr_total = sm_total = 0
+        for d in self.dirs:
+            ids, scores = _list_views(d)
+            if len(ids) == 0:
+                raise ValueError(f"{d}: no LR views")
+            side = io_binding.png_info(os.path.join(d, f"LR{ids[0]}.png"))[0]
+            self.ids.append(ids)
+            self.clearances.append(scores)
+            self.sides.append(side)
+            slot = _round4(side * side)
+            self.lr_off.append(lr_total + slot * np.arange(len(ids), dtype=np.int64))
+            lr_total += slot * len(ids)
+            if os.path.exists(os.path.join(d, "HR.png")):
+                self.hr_off.append(hr_total)
+                hr_total += _round4(9 * side * side)
+            else:
+                self.hr_off.append(-1)
+            self.sm_off.append(sm_total)
+            sm_total += _round4(9 * side * side)
+        self.lr_elems, self.hr_elems, self.sm_elems = lr_total, hr_total, sm_total
+
+    def __len__(self):
+        return len(self.dirs)
+
+    def resolve(self, index):
+        """Position of an int index or an imageset name (KeyError for an unknown name), as ImagesetDataset.load_batch."""
+        return range(len(self.dirs))[index] if isinstance(index, int) else self.position[index]
+
+    def plan(self, indices, min_L):
+        """-> (plan (B, COLLATE_META + min_L) int64, names, S, have_hr) for hrn_collate_device.  RNG: per imageset, in order,
+        _pick_views (sample_clearest, or the clearance sort for top_k <= 0) and then _corner, with the dataset's seed."""
+        ds = self.dataset
+        rows = []
+        for i in indices:
+            k = self.resolve(i)
+            pick = _pick_views(self.clearances[k], len(self.ids[k]), ds.top_k, ds.beta, ds.seed)
+            corner = _corner(self.sides[k], ds.patch_size, ds.seed) if ds.create_patches else (0, 0)
+            rows.append((k, pick, corner))
+        side = self.sides[rows[0][0]]
+        if any(self.sides[k] != side for k, _, _ in rows):
+            raise ValueError("imagesets of one batch must share the LR size")
+        patch = ds.patch_size if ds.create_patches else 0
+        S = patch if patch else side
+        have_hr = all(self.hr_off[k] >= 0 for k, _, _ in rows)
+        plan = np.full((len(rows), binding.COLLATE_META + min_L), -1, np.int64)
+        for b, (k, pick, (row, col)) in enumerate(rows):
+            used = self.lr_off[k][pick[:min_L]]
+            plan[b, :binding.COLLATE_META] = (self.hr_off[k] if have_hr else -1, self.sm_off[k], side, row if patch else 0,
+                                              col if patch else 0)
+            plan[b, binding.COLLATE_META:binding.COLLATE_META + len(used)] = used
+        return plan, [self.names[k] for k, _, _ in rows], S, have_hr
+
+
+class DeviceImagesetCache:
+    """Every imageset of an ImagesetDataset decoded once and kept on the device (LR / HR as uint16, SM as uint8, allocated
+    through torch's caching allocator), and batches built there by one hrn_collate_device launch each:
+
+        cache = dataset.to_device("cuda", n_threads=16)
+        lrs, alphas, hrs, hr_maps, names = cache.load_batch(indices, min_L)      # device tensors, no file I/O
+
+    `load_batch` has the contract of ImagesetDataset.load_batch (same tuple, values bit-identical, hrs == [] when an imageset
+    lacks HR.png, ValueError for mixed LR sizes, KeyError for an unknown name) and makes the same numpy RNG calls in the same
+    order, so a seeded run picks the same views and patches on either path.  Per batch: the plan (Python, ImagesetIndex.plan),
+    one small pinned host-to-device copy of the plan table and one kernel, all enqueued on the current stream; no
+    device-to-host copy and no synchronisation.  Memory: `nbytes` (2 B per LR / HR sample, 1 B per SM sample)."""
+
+    def __init__(self, dataset, device="cuda", n_threads=0, chunk_elems=1 << 26):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"DeviceImagesetCache needs a ROCm device, got '{self.device}' (the host path is ImagesetDataset.load_batch)")
+        if not torch.cuda.is_available():
+            raise RuntimeError("DeviceImagesetCache: device is cuda but no GPU is available")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        binding.load_library()
+        self.index = idx = ImagesetIndex(dataset)
+        dev = self.device
+        self.lr = torch.empty(idx.lr_elems, dtype=torch.uint16, device=dev)
+        self.hr = torch.empty(idx.hr_elems, dtype=torch.uint16, device=dev) if idx.hr_elems else None
+        self.sm = torch.empty(idx.sm_elems, dtype=torch.uint8, device=dev)
+        # decode in chunks of consecutive imagesets (contiguous ranges of each arena) to bound host memory
+        start = 0
+        while start < len(idx):
+            stop, elems = start, 0
+            while stop < len(idx) and (stop == start or elems < chunk_elems):
+                elems += len(idx.ids[stop]) * idx.sides[stop] ** 2
+                stop += 1
+            self._decode(start, stop, n_threads)
+            start = stop
+
+    def _decode(self, start, stop, n_threads):
+        idx = self.index
+        lr_paths, lr_offs, lr_sides = [], [], []
+        hr_paths, hr_offs, hr_sides, sm_paths, sm_offs, sm_sides = [], [], [], [], [], []
+        for k in range(start, stop):
+            d, side = idx.dirs[k], idx.sides[k]
+            lr_paths += [os.path.join(d, f"LR{i}.png") for i in idx.ids[k]]
+            lr_offs += list(idx.lr_off[k])
+            lr_sides += [side] * len(idx.ids[k])
+            if idx.hr_off[k] >= 0:
+                hr_paths.append(os.path.join(d, "HR.png"))
+                hr_offs.append(idx.hr_off[k])
+                hr_sides.append(3 * side)
+            sm_paths.append(os.path.join(d, "SM.png"))
+            sm_offs.append(idx.sm_off[k])
+            sm_sides.append(3 * side)
+        for paths, offs, sides, arena, to_host in ((lr_paths, lr_offs, lr_sides, self.lr, None), (hr_paths, hr_offs, hr_sides, self.hr, None),
+                                                   (sm_paths, sm_offs, sm_sides, self.sm, lambda a: (a != 0).astype(np.uint8))):
+            if not paths:
+                continue
+            offs = np.asarray(offs, np.int64)
+            lo = int(offs[0])
+            hi = int(offs[-1]) + _round4(sides[-1] ** 2)
+            host = np.zeros(hi - lo, np.uint16)
+            io_binding.read_many(paths, host, offs - lo, sides, sides, n_threads=n_threads)
+            if to_host is None:
+                arena.view(torch.int16)[lo:hi].copy_(torch.from_numpy(host.view(np.int16)))
+            else:
+                arena[lo:hi].copy_(torch.from_numpy(to_host(host)))
+
+    def __len__(self):
+        return len(self.index)
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.lr, self.hr, self.sm) if t is not None)
+
+    def load_batch(self, indices, min_L):
+        """(lrs (B,min_L,S,S), alphas (B,min_L), hrs (B,3S,3S) or [], hr_maps (B,3S,3S), names) on the cache's device."""
+        plan, names, S, have_hr = self.index.plan(indices, min_L)
+        B = len(names)
+        with torch.cuda.device(self.device):
+            plan_d = torch.from_numpy(plan).pin_memory().to(self.device, non_blocking=True)
+            mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+            lrs, alphas, maps = mk(B, min_L, S, S), mk(B, min_L), mk(B, 3 * S, 3 * S)
+            hrs = mk(B, 3 * S, 3 * S) if have_hr else None
+            binding.collate_device(self.lr, self.hr, self.sm, plan_d, S, lrs, alphas, hrs, maps)
+        return lrs, alphas, hrs if have_hr else [], maps, names
+
+    def batches(self, index_lists, min_L):
+        """Batches of `index_lists` in order, in the role of BatchPrefetcher.  Nothing needs a worker thread: a batch costs its
+        plan and one launch on the current stream, which runs after the work already queued there (the previous step)."""
+        for idx in index_lists:
+            yield self.load_batch(list(idx), min_L)
 
 
 class BatchPrefetcher:

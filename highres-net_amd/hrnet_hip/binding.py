@@ -131,6 +131,8 @@ SIGNATURES = {
     "hrn_shift_cpsnr_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int]),
     "hrn_shift_cpsnr": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
                                    _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_collate_device": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                      _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_profile_enable": (_c.c_int, [_c.c_int]),
     "hrn_profile_count": (_c.c_int, []),
     "hrn_profile_get": (_c.c_int, [_c.c_int, _c.c_char_p, _c.c_int, _c.POINTER(_c.c_long), _c.POINTER(_c.c_double),
@@ -577,6 +579,34 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_
         _check(lib.hrn_adam_step(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), params.numel(), float(lr), float(beta1),
                                  float(beta2), float(eps), float(weight_decay), int(step), _stream()), "hrn_adam_step")
     bump_param_epoch()
+
+
+# --------------------------------------------------------------------------- input pipeline
+COLLATE_META = 5          # leading int64 fields of a plan row (HRN_COLLATE_META): hr_off, sm_off, side, row, col
+
+
+def collate_device(lr_arena, hr_arena, sm_arena, plan, S, lrs, alphas, hrs, maps):
+    """One launch on the current stream: gather + convert a batch from the device arenas (uint16 LR / HR, uint8 SM) into
+    lrs (B,min_L,S,S), alphas (B,min_L), hrs (B,3S,3S) or None, maps (B,3S,3S) f32, following `plan`, a device int64
+    (B, COLLATE_META + min_L) table (include/hrnet_hip.h, hrn_collate_device)."""
+    B, min_L = alphas.shape
+    use_hr = hrs is not None
+    arenas = [("lr_arena", lr_arena, torch.uint16), ("sm_arena", sm_arena, torch.uint8), ("plan", plan, torch.int64)]
+    for name, t, dt in arenas + ([("hr_arena", hr_arena, torch.uint16)] if use_hr else []):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() or t.dtype != dt:
+            raise RuntimeError(f"{name} must be a contiguous {dt} ROCm device tensor")
+    if tuple(plan.shape) != (B, COLLATE_META + min_L):
+        raise ValueError(f"plan is {tuple(plan.shape)}, expected {(B, COLLATE_META + min_L)}")
+    outs = [("lrs", lrs, (B, min_L, S, S)), ("alphas", alphas, (B, min_L)), ("maps", maps, (B, 3 * S, 3 * S))]
+    if hrs is not None:
+        outs.append(("hrs", hrs, (B, 3 * S, 3 * S)))
+    for name, t, shape in outs:
+        if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be a contiguous float32 device tensor of shape {shape}")
+    _check(load_library().hrn_collate_device(_ptr(lr_arena), lr_arena.numel(), _ptr(hr_arena) if use_hr else None,
+                                             hr_arena.numel() if use_hr else 0, _ptr(sm_arena), sm_arena.numel(), _ptr(plan), B, min_L, S,
+                                             _ptr(lrs), _ptr(alphas), _ptr(hrs) if use_hr else None, _ptr(maps), _stream()),
+           "hrn_collate_device")
 
 
 # --------------------------------------------------------------------------- built-in kernel timing

@@ -1,6 +1,7 @@
 // libhrnet_io.so - host-side input pipeline (include/hrnet_io.h).
 // A minimal PNG reader (grayscale, non-interlaced, bit depths 1..16: everything the PROBA-V assets use) on zlib's inflate,
-// and the decode -> crop -> float -> pad-to-min_L collate of one batch on a pool of threads.
+// the decode -> crop -> float -> pad-to-min_L collate of one batch on a pool of threads, and the bulk decode of many files into
+// one uint16 arena (the HBM-resident cache of DataLoader.DeviceImagesetCache).
 // Semantics follow src/DataLoader.py:72-148,:195-199 and src/utils.py:85-95 (cited per function); no code of theirs is used.
 #include "../../../include/hrnet_io.h"
 
@@ -216,6 +217,43 @@ int hrn_io_collate(int n_sets, const char* const* lr_paths, const int* n_views, 
     int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
     if (nt < 1) nt = 1;
     if ((size_t)nt > items.size()) nt = (int)items.size();
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt; ++t) pool.emplace_back(worker);
+    worker();
+    for (auto& th : pool) th.join();
+    if (status.load() != 0) { set_err("%s", first_error.c_str()); return status.load(); }
+    return 0;
+}
+
+int hrn_io_read_many_u16(int n, const char* const* paths, uint16_t* out, const int64_t* offsets, const int* expect_w,
+                         const int* expect_h, int n_threads) {
+    if (n <= 0 || !paths || !out || !offsets || !expect_w || !expect_h) { set_err("hrn_io_read_many_u16: bad argument"); return -2; }
+    for (int i = 0; i < n; ++i) {
+        if (!paths[i] || offsets[i] < 0 || expect_w[i] <= 0 || expect_h[i] <= 0) {
+            set_err("hrn_io_read_many_u16: bad argument for image %d", i);
+            return -2;
+        }
+    }
+    std::atomic<int> next(0);
+    std::atomic<int> status(0);
+    std::string first_error;
+    std::atomic<bool> have_error(false);
+    auto worker = [&]() {
+        for (;;) {
+            const int i = next.fetch_add(1);
+            if (i >= n || status.load() != 0) return;
+            const int rc = read_crop(paths[i], expect_w[i], expect_h[i], out + offsets[i], 0, expect_h[i], 0, expect_w[i], (size_t)expect_w[i]);
+            if (rc) {
+                bool expected = false;
+                if (have_error.compare_exchange_strong(expected, true)) first_error = g_err;
+                status.store(rc);
+                return;
+            }
+        }
+    };
+    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
+    if (nt < 1) nt = 1;
+    if (nt > n) nt = n;
     std::vector<std::thread> pool;
     for (int t = 1; t < nt; ++t) pool.emplace_back(worker);
     worker();

@@ -19,6 +19,7 @@ SIGNATURES = {
     "hrn_io_png_read_u16": (_c.c_int, [_c.c_char_p, _c.c_void_p, _c.c_int, _c.c_int]),
     "hrn_io_collate": (_c.c_int, [_c.c_int, _pp, _ip, _pp, _pp, _c.c_int, _c.c_int, _c.c_int, _ip, _ip,
                                   _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int]),
+    "hrn_io_read_many_u16": (_c.c_int, [_c.c_int, _pp, _c.c_void_p, _c.POINTER(_c.c_int64), _ip, _ip, _c.c_int]),
 }
 _lib = None
 
@@ -104,4 +105,24 @@ def collate(lr_paths_per_set, hr_paths, sm_paths, min_L, lr_size, patch=0, corne
                               int(patch), px, py, ptr(out["lrs"], (B, min_L, S, S)), ptr(out["alphas"], (B, min_L)),
                               ptr(out.get("hrs") if have_hr else None, (B, 3 * S, 3 * S)), ptr(out["maps"], (B, 3 * S, 3 * S)),
                               int(n_threads)), "hrn_io_collate")
+    return out
+
+
+def read_many(paths, out, offsets, widths, heights, n_threads=0):
+    """Decode every PNG of `paths` into the uint16 numpy arena `out` (C-contiguous, 1-D): image i lands at
+    out[offsets[i] : offsets[i] + widths[i] * heights[i]] as rows of widths[i] samples.  Sizes must match the files."""
+    n = len(paths)
+    if not (len(offsets) == len(widths) == len(heights) == n):
+        raise ValueError("read_many: paths, offsets, widths and heights must have the same length")
+    if n == 0:
+        return out
+    if out.dtype != np.uint16 or out.ndim != 1 or not out.flags["C_CONTIGUOUS"]:
+        raise ValueError("read_many: out must be a C-contiguous 1-D uint16 array")
+    off = np.ascontiguousarray(offsets, np.int64)
+    w = np.ascontiguousarray(widths, np.int32)
+    h = np.ascontiguousarray(heights, np.int32)
+    if off.min() < 0 or int((off + w.astype(np.int64) * h).max()) > out.size:
+        raise ValueError("read_many: an image does not fit in the arena")
+    _check(load_library().hrn_io_read_many_u16(n, _strs(paths), out.ctypes.data_as(_c.c_void_p), off.ctypes.data_as(_c.POINTER(_c.c_int64)),
+                                               w.ctypes.data_as(_ip), h.ctypes.data_as(_ip), int(n_threads)), "hrn_io_read_many_u16")
     return out

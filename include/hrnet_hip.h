@@ -20,6 +20,8 @@
  *   hrn_lanczos_shift_backward  <-  torch autograd through the three symbols above, src/train.py:172-190
  *   hrn_adam_step          <-  optimizer.step() of torch.optim.Adam   src/train.py:191, :252
  *   hrn_get_loss / hrn_shift_cpsnr  <-  get_loss (train.py:66-87) / shift_cPSNR (Evaluator.py:52-73)
+ *   hrn_collate_device     <-  collateFunction(min_L) over ImagesetDataset items (src/utils.py:63-113), gathered from
+ *                              imagesets decoded once into HBM (DataLoader.DeviceImagesetCache)
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor's data_ptr) unless stated;
@@ -45,6 +47,7 @@
 #ifndef HRNET_HIP_H
 #define HRNET_HIP_H
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -55,6 +58,7 @@ extern "C" {
 #define HRN_DTYPE_BF16X3 2
 #define HRN_MAX_RES_LAYERS 8
 #define HRN_ABI_VERSION 1
+#define HRN_COLLATE_META 5     /* leading int64 fields of a hrn_collate_device plan row */
 
 int hrn_version(void);
 const char* hrn_last_error(void);
@@ -278,6 +282,25 @@ int hrn_shift_cpsnr(const float* srs, const float* hrs, const float* hr_maps, in
  *                    p -= lr / (1 - b1^step) * m / (sqrt(v) / sqrt(1 - b2^step) + eps).  step counts from 1. */
 int hrn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int step, void* stream);
+
+/* ------------------------------------------------------------------ input pipeline: batch assembly on the device
+ * hrn_collate_device  <-  ImagesetDataset.load_batch (highres-net_amd/DataLoader.py) from imagesets decoded once into HBM:
+ *   lr_arena / hr_arena : uint16 samples of every stored LR view / HR image, each image starting at a multiple of 4 elements;
+ *                         lr_elems / hr_elems their sizes (multiples of 4).  hr_arena may be NULL when hrs is NULL.
+ *   sm_arena            : uint8 status maps (any non-zero sample -> 1.0), same layout rules, sm_elems its size
+ *   plan                : (B, HRN_COLLATE_META + min_L) int64, one row per sample:
+ *                         hr_off, sm_off, side (stored LR side; HR / SM are 3 * side), row, col (patch corner in LR pixels:
+ *                         row first, as get_patch), then min_L LR offsets in use order, -1 for a padding slot.
+ *                         hr_off -1: that sample's HR plane is zeros.  Offsets are in elements of the arena.
+ *   S                   : output LR side (the patch size, or side for whole images)
+ *   lrs (B,min_L,S,S), alphas (B,min_L), hrs (B,3S,3S) or NULL, maps (B,3S,3S): f32 outputs, all written by ONE launch,
+ *   padding included: lrs / hrs = (float)((double)u / 65535.0), alphas = 1 for a used slot and 0 for a padding slot.
+ * A plan row whose image lies outside its arena or is not 4-aligned, whose corner leaves the stored image, or whose side is
+ * not in 1..2^20 gives NaN planes (never an out-of-bounds read); the alpha of such an LR slot stays 1.  Enqueues on `stream`;
+ * no synchronisation. */
+int hrn_collate_device(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems,
+                       const uint8_t* sm_arena, int64_t sm_elems, const int64_t* plan, int B, int min_L, int S,
+                       float* lrs, float* alphas, float* hrs, float* maps, void* stream);
 
 /* ------------------------------------------------------------------ built-in kernel timing (hipEvent pairs)
  * The reference has no profiling hooks; these exist so that bench.py can state, live, the

@@ -51,6 +51,12 @@ int hrn_io_collate(int n_sets, const char* const* lr_paths, const int* n_views, 
                    const char* const* sm_paths, int min_L, int lr_size, int patch, const int* px, const int* py,
                    float* lrs, float* alphas, float* hrs, float* maps, int n_threads);
 
+/* Decode n PNGs (8- or 16-bit grayscale, as hrn_io_png_read_u16) into one caller-owned uint16 arena: image i goes to
+ * out[offsets[i] .. offsets[i] + expect_w[i] * expect_h[i]) as rows of expect_w[i] samples; its size must match the file.
+ * Decoded on n_threads worker threads (<= 0: hardware concurrency).  On a failure the first error names the file. */
+int hrn_io_read_many_u16(int n, const char* const* paths, uint16_t* out, const int64_t* offsets, const int* expect_w,
+                         const int* expect_h, int n_threads);
+
 #ifdef __cplusplus
 }
 #endif
