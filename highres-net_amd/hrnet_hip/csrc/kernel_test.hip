@@ -1,6 +1,7 @@
 // Kernel-level hooks for the test suite (tests/test_gpu_bf16_train.py, tests/test_gpu_shiftnet_bf16.py, tests/test_gpu_kernels_fwd.py): the
 // convolution (with its whole epilogue), stem and decoder launchers, the training path's data-gradient and weight-gradient launchers and
-// ShiftNet's BatchNorm / stem / fc adapter passes called on their own, so that each can be checked against fp64 with inputs chosen for it.  Not part of the
+// ShiftNet's BatchNorm / stem / fc adapter passes, and (tests/test_gpu_kernels_bwd.py) the backward's non-convolution launchers called on
+// their own, so that each can be checked against fp64 with inputs chosen for it.  Not part of the
 // public C ABI (include/hrnet_hip.h); same conventions as its entry points: asynchronous on `stream`, 0 or a negative error.
 #include <string.h>
 #include "kernels.h"
@@ -123,6 +124,80 @@ int hrn_kt_sn_fc_to_ref(int dt, const void* y, const unsigned char* mask, float*
 }
 int hrn_kt_sn_fc_from_ref(int dt, const float* dxr, const unsigned char* mask, void* dy, int B, void* stream) {
     return hrn_launch_fc_from_ref(dxr, mask, (float*)dy, B, (hipStream_t)stream, dt);
+}
+
+// ---- the backward's non-convolution launchers (tests/test_gpu_kernels_bwd.py), each called as train.hip / api.hip call it.  Activation
+// and gradient tensors in storage dt; HRN_DTYPE_BF16X3: the lo plane directly behind the hi plane (each kernel derives its offset from
+// the element count).  scratch: hrn_kt_wgrad_scratch_bytes() bytes unless said otherwise.
+// g [rows][C] = dy * PReLU'(x), dslope[0] += sum dy min(x, 0), db[c] += sum_rows g (db / dslope NULL: a frozen parameter)
+int hrn_kt_prelu_bwd_bias(int dt, const void* dy, const void* y, const void* xpre, const float* slope, void* g, size_t rows, int C,
+                          float* dslope, float* db, void* scratch, void* stream) {
+    return hrn_launch_prelu_bwd_bias((const float*)dy, (const float*)y, (const float*)xpre, slope, (float*)g, rows, C, dslope, db, scratch,
+                                     (hipStream_t)stream, dt);
+}
+// db[c] += sum_rows g[row][c]
+int hrn_kt_colsum(int dt, const void* g, size_t rows, int C, float* db, void* scratch, void* stream) {
+    return hrn_launch_colsum((const float*)g, rows, C, db, scratch, (hipStream_t)stream, dt);
+}
+// o = a + b, n elements
+int hrn_kt_add(int dt, const void* a, const void* b, void* o, size_t n, void* stream) {
+    return hrn_launch_add((const float*)a, (const float*)b, (float*)o, n, (hipStream_t)stream, dt);
+}
+// the fusion level's helpers: stack [B][n_in][hw][64], f / dsn / out / df [B * half][hw][64], dz [B * half][hw][128], ds [B][n_in][hw][64]
+int hrn_kt_fuse_update(int dt, const void* stack, int n_in, const void* f, const float* alphas, int alpha_vs, int pair_last, int half,
+                       int alpha_residual, void* out, size_t hw, int B, void* stream) {
+    return hrn_launch_fuse_update((const float*)stack, n_in, (const float*)f, alphas, alpha_vs, pair_last, half, alpha_residual, (float*)out, hw,
+                                  B, (hipStream_t)stream, dt);
+}
+int hrn_kt_fuse_df(int dt, const void* dsn, const float* alphas, int alpha_vs, int pair_last, int half, int alpha_residual, void* df, size_t hw,
+                   int B, void* stream) {
+    return hrn_launch_fuse_df((const float*)dsn, alphas, alpha_vs, pair_last, half, alpha_residual, (float*)df, hw, B, (hipStream_t)stream, dt);
+}
+int hrn_kt_fuse_scatter(int dt, const void* dsn, const void* dz, int n_in, int half, int pair_last, int alpha_residual, void* ds, size_t hw,
+                        int B, void* stream) {
+    return hrn_launch_fuse_scatter((const float*)dsn, (const float*)dz, n_in, half, pair_last, alpha_residual, (float*)ds, hw, B,
+                                   (hipStream_t)stream, dt);
+}
+// d_alphas[b][pair_last - v] = sum dsn * f of image b * half + v; scratch: hrn_kt_alpha_grad_scratch_bytes(B * half) bytes
+size_t hrn_kt_alpha_grad_scratch_bytes(int nimg) { return hrn_alpha_grad_scratch_bytes(nimg); }
+int hrn_kt_alpha_grad(int dt, const void* dsn, const void* f, int half, int pair_last, float* d_alphas, int B, int V, size_t hw, void* scratch,
+                      size_t scratch_bytes, void* stream) {
+    return hrn_launch_alpha_grad((const float*)dsn, (const float*)f, half, pair_last, d_alphas, B, V, hw, scratch, scratch_bytes,
+                                 (hipStream_t)stream, dt);
+}
+// dw [64][2][3][3] += the stem's weight gradient; sub NULL: hrn_launch_stem_wgrad (HRNet), else hrn_launch_stem_wgrad_sub (ShiftNet)
+int hrn_kt_stem_wgrad(int dt, const float* in0, size_t stride0, const float* in1, int rep1, size_t stride1, const float* sub, const void* g,
+                      int M, int H, int W, float* dw, void* scratch, void* stream) {
+    const int cus = hrn_device_cus();
+    if (!sub) return hrn_launch_stem_wgrad(in0, stride0, in1, rep1, stride1, (const float*)g, M, H, W, dw, scratch, cus, (hipStream_t)stream, dt);
+    return hrn_launch_stem_wgrad_sub(in0, stride0, in1, rep1, stride1, sub, (const float*)g, M, H, W, dw, scratch, cus, (hipStream_t)stream, dt);
+}
+// d_lrs [B][V][H][W] = the stem's input gradient with the median routing; wt: 64 * 18 floats of scratch
+int hrn_kt_stem_dgrad_route(int dt, const void* dA, const float* w, float* wt, const float* lrs, const float* ref, float* d_lrs, int B, int V,
+                            int H, int W, void* stream) {
+    return hrn_launch_stem_dgrad_route((const float*)dA, w, wt, lrs, ref, d_lrs, B, V, H, W, (hipStream_t)stream, dt);
+}
+// out [M][H][W][64] (dt) = the stem's pre-activation, only if only_if_nonpos[0] <= 0
+int hrn_kt_stem_pre(int dt, const float* in0, size_t img_stride0, const float* in1, int rep1, size_t img_stride1, const float* w,
+                    const float* bias, void* out, int M, int H, int W, const float* only_if_nonpos, void* stream) {
+    return hrn_launch_stem_pre(in0, img_stride0, in1, rep1, img_stride1, w, bias, (float*)out, M, H, W, only_if_nonpos, (hipStream_t)stream, dt);
+}
+// the f32 decoder backward at scale S: writes d_fused, accumulates the five gradients (NULL: a frozen parameter)
+int hrn_kt_decoder_bwd(int scale, const float* fused, const float* d_sr, const float* wd, const float* bd, const float* ad, const float* wf,
+                       float* d_fused, float* dwd, float* dbd, float* dad, float* dwf, float* dbf, int N, int H, int W, void* scratch,
+                       void* stream) {
+    return hrn_launch_decoder_bwd(fused, d_sr, wd, bd, ad, wf, d_fused, dwd, dbd, dad, dwf, dbf, N, H, W, scratch, hrn_device_cus(),
+                                  (hipStream_t)stream, scale);
+}
+int hrn_kt_planes_to_f32(const void* hi, size_t lo_off, float* out, size_t n, void* stream) {
+    return hrn_launch_planes_to_f32(hi, lo_off, out, n, (hipStream_t)stream);
+}
+int hrn_kt_f32_to_planes(const float* in, void* hi, size_t lo_off, size_t n, void* stream) {
+    return hrn_launch_f32_to_planes(in, hi, lo_off, n, (hipStream_t)stream);
+}
+// ref [B][H][W] = the lower median of lrs[b, :min(V, 9)]
+int hrn_kt_median(const float* lrs, float* ref, int B, int V, int H, int W, void* stream) {
+    return hrn_launch_median(lrs, ref, B, V, H, W, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -312,14 +312,24 @@ __global__ __launch_bounds__(256) void plane_mean_kernel(const float* __restrict
 template <bool LO>
 __global__ __launch_bounds__(256) void planes_to_f32_kernel(const u32x4* __restrict__ hi, const u32x4* __restrict__ lo, float* __restrict__ out, size_t n8) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
-        const u32x4 h = hi[i], l = LO ? lo[i] : u32x4{0u, 0u, 0u, 0u};
+        const u32x4 h = hi[i];
         f32x4 a, b;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            a[2 * k] = __uint_as_float(h[k] << 16) + __uint_as_float(l[k] << 16);
-            a[2 * k + 1] = __uint_as_float(h[k] & 0xffff0000u) + __uint_as_float(l[k] & 0xffff0000u);
-            b[2 * k] = __uint_as_float(h[2 + k] << 16) + __uint_as_float(l[2 + k] << 16);
-            b[2 * k + 1] = __uint_as_float(h[2 + k] & 0xffff0000u) + __uint_as_float(l[2 + k] & 0xffff0000u);
+            a[2 * k] = __uint_as_float(h[k] << 16);
+            a[2 * k + 1] = __uint_as_float(h[k] & 0xffff0000u);
+            b[2 * k] = __uint_as_float(h[2 + k] << 16);
+            b[2 * k + 1] = __uint_as_float(h[2 + k] & 0xffff0000u);
+        }
+        if constexpr (LO) {                                     // (one plane: float(hi) itself - adding a +0 lo would turn -0 into +0)
+            const u32x4 l = lo[i];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                a[2 * k] += __uint_as_float(l[k] << 16);
+                a[2 * k + 1] += __uint_as_float(l[k] & 0xffff0000u);
+                b[2 * k] += __uint_as_float(l[2 + k] << 16);
+                b[2 * k + 1] += __uint_as_float(l[2 + k] & 0xffff0000u);
+            }
         }
         *(f32x4*)(out + i * 8) = a;
         *(f32x4*)(out + i * 8 + 4) = b;

@@ -21,7 +21,7 @@ from test_gpu_upscale import _model
 
 pytestmark = pytest.mark.gpu
 
-BF16, BF16X3 = 1, 2
+F32, BF16, BF16X3 = 0, 1, 2
 
 
 def _lib():
@@ -44,6 +44,20 @@ def _lib():
     lib.hrn_kt_stem.argtypes = [i, vp, sz, vp, i, sz, vp, vp, vp, vp, vp, sz, i, i, i, vp]
     lib.hrn_kt_decoder.restype = i
     lib.hrn_kt_decoder.argtypes = [i, i, vp, sz, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
+    # the backward's non-convolution launchers (tests/test_gpu_kernels_bwd.py)
+    for name, args in (("prelu_bwd_bias", [i, vp, vp, vp, vp, vp, sz, i, vp, vp, vp, vp]), ("colsum", [i, vp, sz, i, vp, vp, vp]),
+                       ("add", [i, vp, vp, vp, sz, vp]), ("fuse_update", [i, vp, i, vp, vp, i, i, i, i, vp, sz, i, vp]),
+                       ("fuse_df", [i, vp, vp, i, i, i, i, vp, sz, i, vp]), ("fuse_scatter", [i, vp, vp, i, i, i, i, vp, sz, i, vp]),
+                       ("alpha_grad", [i, vp, vp, i, i, vp, i, i, sz, vp, sz, vp]),
+                       ("stem_wgrad", [i, vp, sz, vp, i, sz, vp, vp, i, i, i, vp, vp, vp]),
+                       ("stem_dgrad_route", [i, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]),
+                       ("stem_pre", [i, vp, sz, vp, i, sz, vp, vp, vp, i, i, i, vp, vp]),
+                       ("decoder_bwd", [i] + [vp] * 12 + [i, i, i, vp, vp]), ("planes_to_f32", [vp, sz, vp, sz, vp]),
+                       ("f32_to_planes", [vp, vp, sz, sz, vp]), ("median", [vp, vp, i, i, i, i, vp])):
+        fn = getattr(lib, "hrn_kt_" + name)
+        fn.restype, fn.argtypes = i, args
+    lib.hrn_kt_alpha_grad_scratch_bytes.restype = ctypes.c_size_t
+    lib.hrn_kt_alpha_grad_scratch_bytes.argtypes = [i]
     return lib
 
 
@@ -70,6 +84,12 @@ def _x3(shape, seed, scale=1.0):
     hi = v.to(torch.bfloat16)
     lo = (v - hi.float()).to(torch.bfloat16)
     return torch.stack([hi, lo]).cuda(), hi.double() + lo.double()
+
+
+def _f32(shape, seed, scale=1.0):
+    """an f32 device tensor of bf16-representable random values (and its exact fp64 CPU copy): the fp32 kernels' products are exact too"""
+    t, t64 = _bf(shape, seed, scale)
+    return t.float().contiguous(), t64
 
 
 def _nchw(t):
@@ -117,8 +137,8 @@ def test_bf16_training_op_runs_at_every_scale(scale):
 # ----------------------------------------------------------------------------- 2. the bf16 weight gradient
 def _wgrad_case(lib, M, H, W, cin, cout, pair=None, seed=0, dt=BF16):
     """-> (got, want, sum |terms|) for dW of a cin -> cout conv; pair = (B, n): the input is the pair gather of a (B, n) view stack.
-    dt BF16: one bf16 plane per tensor; BF16X3: hi + lo planes of random fp32 values"""
-    act = _bf if dt == BF16 else _x3
+    dt BF16: one bf16 plane per tensor; BF16X3: hi + lo planes of random fp32 values; F32: bf16-representable values stored as f32"""
+    act = {F32: _f32, BF16: _bf, BF16X3: _x3}[dt]
     g, g64 = act((M, H, W, cout), seed + 1)
     if pair:
         B, n = pair
@@ -145,10 +165,12 @@ _WGRAD_CASES = ["plain64", "plain128x64", "pair", "ragged33", "multi_strip"]
 
 
 @pytest.mark.parametrize("case,dt", [pytest.param(c, BF16, id=c) for c in _WGRAD_CASES] +
-                         [pytest.param(c, BF16X3, id=f"{c}-bf16x3") for c in _WGRAD_CASES])
+                         [pytest.param(c, BF16X3, id=f"{c}-bf16x3") for c in _WGRAD_CASES] +
+                         [pytest.param(c, F32, id=f"{c}-f32") for c in _WGRAD_CASES])
 def test_bf16_wgrad_vs_fp64(case, dt):
     """conv_wgrad_x3_kernel, one-plane (bf16) and two-plane (bf16x3) instance: error <= 1e-5 of sum |terms| per element (bf16 products are
-    exact in fp32; bf16x3 drops only the g lo x x lo term, <= 2^-18 of |g x|)."""
+    exact in fp32; bf16x3 drops only the g lo x x lo term, <= 2^-18 of |g x|).  The f32 ids: conv_wgrad_kernel, the exact-fp32 MFMA weight
+    gradient of the fp32 training path (8 x 32 tiles, grid = min(CUs, tiles)), on bf16-representable values stored as f32."""
     lib = _lib()
     if case == "plain64":
         got, want, terms = _wgrad_case(lib, 3, 16, 32, 64, 64, dt=dt)
@@ -174,15 +196,23 @@ _DGRAD_LAYERS = [(64, 64, False), (64, 64, True), (128, 128, False), (128, 128, 
 
 
 @pytest.mark.parametrize("cin,cout,res,dt", [pytest.param(*l, BF16, id="-".join(map(str, l))) for l in _DGRAD_LAYERS] +
-                         [pytest.param(*l, BF16X3, id="-".join(map(str, l)) + "-bf16x3") for l in _DGRAD_LAYERS])
+                         [pytest.param(*l, BF16X3, id="-".join(map(str, l)) + "-bf16x3") for l in _DGRAD_LAYERS] +
+                         [pytest.param(*l, F32, id="-".join(map(str, l)) + "-f32") for l in _DGRAD_LAYERS])
 def test_bf16_dgrad_vs_fp64(cin, cout, res, dt):
     """dx = conv3x3(g, W^T flipped) (+ res) for a cin -> cout layer, i.e. a cout -> cin convolution on the bf16 kernels (r64, v6; the
     64 -> 128 and 128 -> 128 + res shapes are the new v6 instances) and on v6x3.  Bound per element: bf16, one bf16 rounding of the
     output (2^-8 of it) plus 1e-5 of sum |terms|; bf16x3 (hi + lo planes of random fp32 g / res, general fp32 weights), 2^-16 of the
-    output (the split of the fp32 result) plus 1e-5 of sum |terms|."""
+    output (the split of the fp32 result) plus 1e-5 of sum |terms|; f32 (the fp32 forward kernel on bf16-representable g / w / res stored
+    as f32), 2^-24 of the output plus 1e-5 of sum |terms|."""
     lib = _lib()
     M, H, W = 3, 13, 37
-    if dt == BF16:
+    if dt == F32:
+        g, g64 = _f32((M, H, W, cout), 21)
+        w, w64 = _bf((cout, cin, 3, 3), 22, 0.05)
+        w32 = w.float().contiguous()
+        r, r64 = _f32((M, H, W, cin), 23) if res else (None, None)
+        dx = torch.empty((M, H, W, cin), dtype=torch.float32, device="cuda")
+    elif dt == BF16:
         g, g64 = _bf((M, H, W, cout), 21)
         w, w64 = _bf((cout, cin, 3, 3), 22, 0.05)
         w32 = w.float().contiguous()
@@ -204,7 +234,10 @@ def test_bf16_dgrad_vs_fp64(cin, cout, res, dt):
     if res:
         want = want + _nchw(r64)
         terms = terms + _nchw(r64).abs()
-    if dt == BF16:
+    if dt == F32:
+        got = _nchw(dx.double().cpu())
+        bound = 2.0 ** -24 * want.abs() + 1e-5 * terms + 1e-30
+    elif dt == BF16:
         got = _nchw(dx.double().cpu())
         bound = 2.0 ** -8 * want.abs() + 1e-5 * terms + 1e-30
     else:
