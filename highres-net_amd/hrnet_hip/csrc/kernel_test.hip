@@ -1,7 +1,9 @@
 // Kernel-level hooks for the test suite (tests/test_gpu_bf16_train.py, tests/test_gpu_shiftnet_bf16.py, tests/test_gpu_kernels_fwd.py): the
 // convolution (with its whole epilogue), stem and decoder launchers, the training path's data-gradient and weight-gradient launchers and
 // ShiftNet's BatchNorm / stem / fc adapter passes, and (tests/test_gpu_kernels_bwd.py) the backward's non-convolution launchers called on
-// their own, so that each can be checked against fp64 with inputs chosen for it.  Not part of the
+// their own and (tests/test_gpu_kernels_shiftnet.py) the rest of ShiftNet's passes - BatchNorm fold / saved statistics, the f32
+// convolution's folded-BatchNorm epilogue, the plane means, fc1 / fc2 and the tail's backward -
+// so that each can be checked against fp64 with inputs chosen for it.  Not part of the
 // public C ABI (include/hrnet_hip.h); same conventions as its entry points: asynchronous on `stream`, 0 or a negative error.
 #include <string.h>
 #include "kernels.h"
@@ -124,6 +126,53 @@ int hrn_kt_sn_fc_to_ref(int dt, const void* y, const unsigned char* mask, float*
 }
 int hrn_kt_sn_fc_from_ref(int dt, const float* dxr, const unsigned char* mask, void* dy, int B, void* stream) {
     return hrn_launch_fc_from_ref(dxr, mask, (float*)dy, B, (hipStream_t)stream, dt);
+}
+
+// ---- ShiftNet's remaining passes (tests/test_gpu_kernels_shiftnet.py), each the production launcher as api.hip / shiftnet_bwd.hip call it
+// mean / invstd (C f32 each) from the `partial` sums hrn_kt_sn_bn_stats left
+int hrn_kt_sn_bn_save_stats(const double* partial, size_t npix, int C, float* mean, float* invstd, void* stream) {
+    return hrn_launch_sn_bn_save_stats(partial, npix, C, 1e-5f, mean, invstd, (hipStream_t)stream);
+}
+// eval mode's folded BatchNorm: scale / shift from the running statistics (conv_bias NULL: none)
+int hrn_kt_sn_bn_fold(const float* gamma, const float* beta, const float* rm, const float* rv, const float* conv_bias, float* scale,
+                      float* shift, int C, void* stream) {
+    return hrn_launch_bn_fold(gamma, beta, rm, rv, 1e-5f, conv_bias, scale, shift, C, (hipStream_t)stream);
+}
+// out [M][H][W][cout] f32 = ReLU(conv3x3(in) * scale + shift): the f32 convolution with eval mode's folded-BatchNorm epilogue
+int hrn_kt_sn_conv_bn_relu(int cin, int cout, const float* in, const void* wpk, const float* scale, const float* shift, float* out, int M, int H,
+                           int W, void* stream) {
+    ConvParams p;
+    memset(&p, 0, sizeof p);
+    p.M = M; p.H = H; p.W = W;
+    p.in = in; p.out = out;
+    p.wpk = wpk; p.scale = scale; p.bias = shift; p.relu = 1;
+    return hrn_launch_conv3x3(HRN_F32, cin, cout, p, (hipStream_t)stream);
+}
+// mean [planes] of x [planes][hw], and out = g - means[plane]
+int hrn_kt_sn_plane_mean(const float* x, float* mean, int planes, size_t hw, void* stream) {
+    return hrn_launch_plane_mean(x, mean, planes, hw, (hipStream_t)stream);
+}
+int hrn_kt_sn_sub_plane_mean(const float* g, const float* means, float* out, int planes, size_t hw, void* stream) {
+    return hrn_launch_sn_sub_plane_mean(g, means, out, planes, hw, (hipStream_t)stream);
+}
+// y (B, 1024) = ReLU(bias + xr w^T), xr (B, 32768), w (1024, 32768); partial: hrn_kt_sn_fc1_partial_bytes() of scratch
+size_t hrn_kt_sn_fc1_partial_bytes(void) { return hrn_fc1_partial_bytes(); }
+int hrn_kt_sn_fc1(const float* xr, const float* w, const float* bias, float* y, int B, float* partial, void* stream) {
+    return hrn_launch_fc1(xr, w, bias, y, B, partial, (hipStream_t)stream);
+}
+// theta (B, 2) = y w2^T, w2 (2, 1024)
+int hrn_kt_sn_fc2(const float* y, const float* w2, float* theta, int B, void* stream) {
+    return hrn_launch_fc2(y, w2, theta, B, (hipStream_t)stream);
+}
+// the tail's backward (dw2 / db1 NULL: frozen)
+int hrn_kt_sn_fc2_bwd(const float* dtheta, const float* y1, const float* w2, float* dz1, float* dw2, float* db1, int B, void* stream) {
+    return hrn_launch_sn_fc2_bwd(dtheta, y1, w2, dz1, dw2, db1, B, (hipStream_t)stream);
+}
+int hrn_kt_sn_fc1_bwd_w(const float* dz1, const float* xr, float* dw1, int B, void* stream) {
+    return hrn_launch_sn_fc1_bwd_w(dz1, xr, dw1, B, (hipStream_t)stream);
+}
+int hrn_kt_sn_fc1_bwd_x(const float* dz1, const float* w1, float* dxr, int B, void* stream) {
+    return hrn_launch_sn_fc1_bwd_x(dz1, w1, dxr, B, (hipStream_t)stream);
 }
 
 // ---- the backward's non-convolution launchers (tests/test_gpu_kernels_bwd.py), each called as train.hip / api.hip call it.  Activation

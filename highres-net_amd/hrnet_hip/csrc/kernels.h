@@ -69,3 +69,12 @@ int hrn_launch_sn_bn_bwd(const float* x, const float* dy, const float* stats, co
 int hrn_launch_sn_stem_dgrad(const float* g, const float* w, float* din, int M, int H, int W, hipStream_t s, int dt = HRN_F32);
 // dy [B][16*16][128] (dt) = the gradient of fc1's input dxr (B, 32768) f32 in the reference's flatten order, dropout mask applied
 int hrn_launch_fc_from_ref(const float* dxr, const unsigned char* mask, float* dy, int B, hipStream_t s, int dt = HRN_F32);
+// mean[c], invstd[c] (what the BatchNorm backward reads) from the `partial` sums hrn_launch_bn_stats left (SN_PARTIAL_BLOCKS of them)
+int hrn_launch_sn_bn_save_stats(const double* partial, size_t npix, int C, float eps, float* mean, float* invstd, hipStream_t s);
+// out [planes][hw] = g - means[plane]: the backward of the per-plane mean subtraction (ShiftNet.py:58)
+int hrn_launch_sn_sub_plane_mean(const float* g, const float* means, float* out, int planes, size_t hw, hipStream_t s);
+// the tail's backward, any batch size: dz1 (B, 1024) = (y1 > 0) dtheta w2, dw2 (2, 1024) += dtheta^T y1, db1 (1024) += sum_b dz1 (dw2 /
+// db1 NULL: frozen); dw1 (1024, 32768) += dz1^T xr and dxr (B, 32768) = dz1 w1, both in groups of 32 samples (one launch per group)
+int hrn_launch_sn_fc2_bwd(const float* dtheta, const float* y1, const float* w2, float* dz1, float* dw2, float* db1, int B, hipStream_t s);
+int hrn_launch_sn_fc1_bwd_w(const float* dz1, const float* xr, float* dw1, int B, hipStream_t s);
+int hrn_launch_sn_fc1_bwd_x(const float* dz1, const float* w1, float* dxr, int B, hipStream_t s);

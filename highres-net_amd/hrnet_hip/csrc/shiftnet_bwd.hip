@@ -410,6 +410,47 @@ int hrn_launch_fc_from_ref(const float* dxr, const unsigned char* mask, float* d
     return 0;
 }
 
+int hrn_launch_sn_bn_save_stats(const double* partial, size_t npix, int C, float eps, float* mean, float* invstd, hipStream_t s) {
+    hipLaunchKernelGGL(bn_save_stats_kernel, dim3(1), dim3(1024), 0, s, partial, SN_PARTIAL_BLOCKS, npix, C, eps, mean, invstd);
+    HRN_LAUNCH_CHECK();
+    return 0;
+}
+
+int hrn_launch_sn_sub_plane_mean(const float* g, const float* means, float* out, int planes, size_t hw, hipStream_t s) {
+    const size_t total = (size_t)planes * hw;
+    hipLaunchKernelGGL(sub_plane_mean_kernel, dim3(ew_grid(total)), dim3(256), 0, s, g, means, out, hw, total);
+    HRN_LAUNCH_CHECK();
+    return 0;
+}
+
+int hrn_launch_sn_fc2_bwd(const float* dtheta, const float* y1, const float* w2, float* dz1, float* dw2, float* db1, int B, hipStream_t s) {
+    hipLaunchKernelGGL(fc2_bwd_kernel, dim3(4), dim3(256), 0, s, dtheta, y1, w2, dz1, dw2, db1, B);
+    hrn_count_launch(HRN_LC_FC2_BWD);
+    HRN_LAUNCH_CHECK();
+    return 0;
+}
+
+int hrn_launch_sn_fc1_bwd_w(const float* dz1, const float* xr, float* dw1, int B, hipStream_t s) {
+    for (int b0 = 0; b0 < B; b0 += 32) {    // the kernel keeps 32 samples of xr in registers: larger batches go in groups
+        hipLaunchKernelGGL(fc1_bwd_w_kernel, dim3(FCK / 256, 1024 / FC1_BWD_JT), dim3(256), 0, s, dz1 + (size_t)b0 * 1024,
+                           xr + (size_t)b0 * FCK, dw1, B - b0 < 32 ? B - b0 : 32);
+        hrn_count_launch(HRN_LC_FC1_BWD_W);
+    }
+    HRN_LAUNCH_CHECK();
+    return 0;
+}
+
+int hrn_launch_sn_fc1_bwd_x(const float* dz1, const float* w1, float* dxr, int B, hipStream_t s) {
+    { const int rc_lds = hrn_allow_lds((const void*)fc1_bwd_x_kernel, FCX_LDS_BYTES); if (rc_lds) return rc_lds; }
+    for (int b0 = 0; b0 < B; b0 += 32) {    // 32 samples are the MFMA's M: larger batches go in groups
+        hipLaunchKernelGGL(fc1_bwd_x_kernel, dim3(FCK / 128), dim3(256), FCX_LDS_BYTES, s, dz1 + (size_t)b0 * 1024, w1,
+                           dxr + (size_t)b0 * FCK, B - b0 < 32 ? B - b0 : 32);
+        hrn_count_launch(HRN_LC_FC1_BWD_X);
+    }
+    HRN_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" {
 
 size_t hrn_shiftnet_train_workspace_bytes_dt(int dtype, int B) { return B > 0 && sn_dtype_ok(dtype) ? sn_train_ws(B, dtype).total : 0; }
@@ -457,8 +498,7 @@ int hrn_shiftnet_forward_train_dt(const void* packed, int dt, const hrn_shiftnet
         const size_t npix = (size_t)B * h * h;
         if ((rc = hrn_launch_bn_stats(xp, npix, C, P->bn_g[i], P->bn_b[i], 1e-5f, st + 256, st + 384, P->bn_rm[i], P->bn_rv[i], momentum,
                                       partial, SN_PARTIAL_BLOCKS, s, dt))) return rc;
-        hipLaunchKernelGGL(bn_save_stats_kernel, dim3(1), dim3(1024), 0, s, (const double*)partial, SN_PARTIAL_BLOCKS, npix, C, 1e-5f, st, st + 128);
-        HRN_LAUNCH_CHECK();
+        if ((rc = hrn_launch_sn_bn_save_stats(partial, npix, C, 1e-5f, st, st + 128, s))) return rc;
         if ((rc = hrn_launch_bn_act_pool(xp, st + 256, st + 384, yp, B, h, h, C, SN_POOL[i], s, dt))) return rc;
     }
     float* y1 = (float*)at(tws, T.y1);
@@ -511,22 +551,11 @@ int shiftnet_backward_impl(const hrn_shiftnet_params* P, int dt, const float* x,
     int rc;
     HRN_HIP(hipMemsetAsync(at(tws, T.zero_bias), 0, 128 * 4, s));
     // ---- tail: theta = fc2(ReLU(fc1(dropout(flatten(y8)))))                                ShiftNet.py:69-74
-    hipLaunchKernelGGL(fc2_bwd_kernel, dim3(4), dim3(256), 0, s, d_theta, (const float*)at(tws, T.y1), P->fc2_w, dz1, mut(G->fc2_w), mut(G->fc1_b), B);
-    hrn_count_launch(HRN_LC_FC2_BWD);
+    if ((rc = hrn_launch_sn_fc2_bwd(d_theta, (const float*)at(tws, T.y1), P->fc2_w, dz1, mut(G->fc2_w), mut(G->fc1_b), B, s))) return rc;
     // (xr, the fc1 input in the reference's flatten order with the dropout folded in, was left in the workspace by the forward)
-    for (int b0 = 0; fc1w && b0 < B; b0 += 32) {
-        hipLaunchKernelGGL(fc1_bwd_w_kernel, dim3(FCK / 256, 1024 / FC1_BWD_JT), dim3(256), 0, s, (const float*)dz1 + (size_t)b0 * 1024,
-                           (const float*)xr + (size_t)b0 * FCK, mut(G->fc1_w), B - b0 < 32 ? B - b0 : 32);
-        hrn_count_launch(HRN_LC_FC1_BWD_W);
-    }
-    if (lowest == 8) { HRN_LAUNCH_CHECK(); return 0; }
-    { const int rc_lds = hrn_allow_lds((const void*)fc1_bwd_x_kernel, FCX_LDS_BYTES); if (rc_lds) return rc_lds; }
-    for (int b0 = 0; b0 < B; b0 += 32) {    // 32 samples are the MFMA's M: larger batches go in groups
-        hipLaunchKernelGGL(fc1_bwd_x_kernel, dim3(FCK / 128), dim3(256), FCX_LDS_BYTES, s, (const float*)dz1 + (size_t)b0 * 1024, P->fc1_w,
-                           dxr + (size_t)b0 * FCK, B - b0 < 32 ? B - b0 : 32);
-        hrn_count_launch(HRN_LC_FC1_BWD_X);
-    }
-    HRN_LAUNCH_CHECK();
+    if (fc1w && (rc = hrn_launch_sn_fc1_bwd_w(dz1, xr, mut(G->fc1_w), B, s))) return rc;
+    if (lowest == 8) return 0;
+    if ((rc = hrn_launch_sn_fc1_bwd_x(dz1, P->fc1_w, dxr, B, s))) return rc;
     if ((rc = hrn_launch_fc_from_ref(dxr, dropout_mask, cur, B, s, dt))) return rc;
     // ---- layers 8 .. 1                                                                        ShiftNet.py:16-41, :59-67
     for (int i = 7; i >= lowest; --i) {
@@ -556,8 +585,7 @@ int shiftnet_backward_impl(const hrn_shiftnet_params* P, int dt, const float* x,
                 float* gm = (float*)at(tws, T.gmeans);
                 if ((rc = hrn_launch_sn_stem_dgrad(oth, P->conv_w[0], dxin, B, h, h, s, dt))) return rc;
                 if ((rc = hrn_launch_plane_mean(dxin, gm, B * 2, plane, s))) return rc;
-                hipLaunchKernelGGL(sub_plane_mean_kernel, dim3(ew_grid((size_t)B * 2 * plane)), dim3(256), 0, s, (const float*)dxin, (const float*)gm, d_x, plane, (size_t)B * 2 * plane);
-                HRN_LAUNCH_CHECK();
+                if ((rc = hrn_launch_sn_sub_plane_mean(dxin, gm, d_x, B * 2, plane, s))) return rc;
             }
         }
     }
