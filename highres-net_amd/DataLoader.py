@@ -7,7 +7,12 @@ draw from numpy's global RNG in the reference's order (so a seeded run picks the
 PNG decode, crop, uint16 -> float32, padding - runs in libhrnet_io.so (`hrnet_hip.io_binding`).  Beyond the reference's
 surface, `ImagesetDataset.load_batch()` collates a whole batch straight into (optionally pinned) buffers on a thread pool,
 and `ImagesetDataset.to_device()` decodes the whole split once into HBM (DeviceImagesetCache), after which every batch is one
-kernel launch (`hrn_collate_device`) with the same RNG draws and bit-identical values.
+kernel launch (`hrn_collate_device_s`) with the same RNG draws and bit-identical values.
+
+Target scale: HR / SM batches are `scale * S` a side for LR patches of side S, `scale` in {2, 3, 4} (the dataset's `scale`
+argument, else config["scale"], else 3).  The patch corner is always drawn in LR pixels, so a seeded run picks the same views and
+corner at every scale.  The host path reads files stored at that ratio and never resamples; the device cache can resample
+HR / SM stored at another ratio once, when it is built (`to_device(resample_targets=True)`, hrnet_hip/resample.py).
 """
 from collections import OrderedDict
 import operator
@@ -18,7 +23,8 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-from hrnet_hip import binding, io_binding
+from hrnet_hip import binding, io_binding, resample
+from hrnet_hip.resample import check_scale
 
 _QM_FILE = re.compile(r"^QM(.*)\.png$", re.S)       # one quality map per LR view; the text between "QM" and ".png" is the view id
 
@@ -91,30 +97,43 @@ def _corner(lr_side, patch_size, seed):
     return row, col
 
 
-def read_imageset(imset_dir, create_patches=False, patch_size=64, seed=None, top_k=None, beta=0.):
+def _ratio_error(name, lr_side, scale, found):
+    """The ValueError for an imageset whose HR / SM files are not `scale` times its LR side."""
+    return ValueError(f"{name}: HR / SM side is {found} but scale {scale} needs {scale * lr_side} ({scale} x the LR side {lr_side}); the host "
+                      f"path does not resample - build a device cache with to_device(resample_targets=True)")
+
+
+def read_imageset(imset_dir, create_patches=False, patch_size=64, seed=None, top_k=None, beta=0., scale=3):
     """ImageSet(name, lr uint16 (L,H,W), hr uint16 or None, hr_map bool, clearances) of one imageset directory, PNGs decoded by
-    the native reader.  With `create_patches` one random `patch_size` window is cut from every LR view and the matching 3x
-    window from SM / HR."""
+    the native reader.  With `create_patches` one random `patch_size` window is cut from every LR view and the matching
+    `scale`x window from SM / HR, whose files must be `scale` times the LR side (ValueError otherwise)."""
+    scale = check_scale(scale)
     ids, scores = _views_in_use_order(imset_dir, top_k, beta, seed)
     asset = lambda name: os.path.join(imset_dir, name)
     lr = np.stack([io_binding.png_read(asset(f"LR{i}.png")) for i in ids]).astype(np.uint16, copy=False)
     hr_map = io_binding.png_read(asset("SM.png")) != 0
     hr = io_binding.png_read(asset("HR.png")).astype(np.uint16, copy=False) if os.path.exists(asset("HR.png")) else None
+    for img in (hr_map, hr):
+        if img is not None and img.shape != (scale * lr.shape[1], scale * lr.shape[2]):
+            raise _ratio_error(os.path.basename(imset_dir), lr.shape[1], scale, img.shape[0])
     if create_patches:
         row, col = _corner(lr.shape[1], patch_size, seed)
         lr = get_patch(lr, row, col, patch_size)
-        hr_map = get_patch(hr_map, 3 * row, 3 * col, 3 * patch_size)
+        hr_map = get_patch(hr_map, scale * row, scale * col, scale * patch_size)
         if hr is not None:
-            hr = get_patch(hr, 3 * row, 3 * col, 3 * patch_size)
+            hr = get_patch(hr, scale * row, scale * col, scale * patch_size)
     return ImageSet(name=os.path.basename(imset_dir), lr=np.array(lr), hr=hr, hr_map=hr_map, clearances=scores)
 
 
 class ImagesetDataset(Dataset):
     """Dataset over imageset directories.  `dataset[i]` (int), `dataset["imgsetXXXX"]` (name) -> one ImageSet of float32
-    tensors (lr (L,S,S), hr / hr_map (3S,3S); test imagesets keep hr = None and a bool numpy hr_map); a slice -> a list."""
+    tensors (lr (L,S,S), hr / hr_map (kS,kS) with k = `scale`; test imagesets keep hr = None and a bool numpy hr_map); a slice
+    -> a list.  `scale` (2, 3 or 4; None: config.get("scale", 3)) is the HR / LR ratio of the batches and, on this host path, of
+    the files."""
 
-    def __init__(self, imset_dir, config, seed=None, top_k=-1, beta=0.):
+    def __init__(self, imset_dir, config, seed=None, top_k=-1, beta=0., scale=None):
         super().__init__()
+        self.scale = check_scale(config.get("scale", 3) if scale is None else scale)
         self.imset_dir = imset_dir
         self.name_to_dir = dict(zip(map(os.path.basename, imset_dir), imset_dir))
         self.create_patches, self.patch_size = config["create_patches"], config["patch_size"]
@@ -149,37 +168,55 @@ class ImagesetDataset(Dataset):
         return dict(name=os.path.basename(dir_), lr_paths=lr_paths, clearances=clearances, lr_side=lr_side, corner=corner, hr=hr_path,
                     sm=os.path.join(dir_, "SM.png"))
 
+    def _collate(self, plans, **kw):
+        """io_binding.collate at the dataset's scale.  A failure is looked at only after the fact (no extra file read on the
+        good path): if an HR / SM file of the batch is not scale x its LR side, that is the ValueError to raise."""
+        try:
+            return io_binding.collate(scale=self.scale, **kw)
+        except io_binding.HrnetIoError as err:
+            for pl in plans:
+                for path in (pl["sm"], pl["hr"]):
+                    if path is not None and os.path.exists(path):
+                        w, h, _ = io_binding.png_info(path)
+                        if (w, h) != (self.scale * pl["lr_side"],) * 2:
+                            raise _ratio_error(pl["name"], pl["lr_side"], self.scale, w if w == h else f"{w}x{h}") from err
+            raise
+
     def _load_one(self, dir_):
         pl = self._plan(dir_)
         patch = self.patch_size if self.create_patches else 0
-        out = io_binding.collate([pl["lr_paths"]], [pl["hr"]], [pl["sm"]], min_L=len(pl["lr_paths"]), lr_size=pl["lr_side"], patch=patch,
-                                 corners=[pl["corner"]])
+        out = self._collate([pl], lr_paths_per_set=[pl["lr_paths"]], hr_paths=[pl["hr"]], sm_paths=[pl["sm"]], min_L=len(pl["lr_paths"]),
+                            lr_size=pl["lr_side"], patch=patch, corners=[pl["corner"]])
         labelled = pl["hr"] is not None
         return ImageSet(name=pl["name"], lr=torch.from_numpy(out["lrs"][0]), hr=torch.from_numpy(out["hrs"][0]) if labelled else None,
                         hr_map=torch.from_numpy(out["maps"][0]) if labelled else out["maps"][0].astype(bool), clearances=pl["clearances"])
 
     def load_batch(self, indices, min_L, pin_memory=False, n_threads=0):
-        """One collated batch (padded_lr (B,min_L,S,S), alphas (B,min_L), hrs (B,3S,3S) or [], hr_maps (B,3S,3S), names) decoded
-        straight into (optionally pinned) buffers by the native thread pool: __getitem__ + collateFunction in one call."""
+        """One collated batch (padded_lr (B,min_L,S,S), alphas (B,min_L), hrs (B,kS,kS) or [], hr_maps (B,kS,kS), names; k = scale)
+        decoded straight into (optionally pinned) buffers by the native thread pool: __getitem__ + collateFunction in one call."""
         plans = [self._plan(self.imset_dir[i] if isinstance(i, int) else self.name_to_dir[i]) for i in indices]
         side = plans[0]["lr_side"]
         if any(p["lr_side"] != side for p in plans):
             raise ValueError("imagesets of one batch must share the LR size")
         patch = self.patch_size if self.create_patches else 0
         S = patch if patch else side
+        T = self.scale * S
         B = len(plans)
         have_hr = all(p["hr"] is not None for p in plans)
         mk = lambda *shape: torch.empty(shape, dtype=torch.float32, pin_memory=pin_memory)
-        out = dict(lrs=mk(B, min_L, S, S), alphas=mk(B, min_L), hrs=mk(B, 3 * S, 3 * S) if have_hr else None, maps=mk(B, 3 * S, 3 * S))
-        io_binding.collate([p["lr_paths"] for p in plans], [p["hr"] for p in plans] if have_hr else None, [p["sm"] for p in plans],
-                           min_L=min_L, lr_size=side, patch=patch, corners=[p["corner"] for p in plans], out=out, n_threads=n_threads)
+        out = dict(lrs=mk(B, min_L, S, S), alphas=mk(B, min_L), hrs=mk(B, T, T) if have_hr else None, maps=mk(B, T, T))
+        self._collate(plans, lr_paths_per_set=[p["lr_paths"] for p in plans], hr_paths=[p["hr"] for p in plans] if have_hr else None,
+                      sm_paths=[p["sm"] for p in plans], min_L=min_L, lr_size=side, patch=patch, corners=[p["corner"] for p in plans], out=out,
+                      n_threads=n_threads)
         return out["lrs"], out["alphas"], out["hrs"] if have_hr else [], out["maps"], [p["name"] for p in plans]
 
 
-    def to_device(self, device="cuda", n_threads=0):
+    def to_device(self, device="cuda", n_threads=0, resample_targets=False):
         """Decode every imageset once into HBM and return a DeviceImagesetCache: `cache.load_batch(indices, min_L)` then
-        builds each batch on the GPU with one kernel, bit-identical to `load_batch` and from the same numpy RNG draws."""
-        return DeviceImagesetCache(self, device=device, n_threads=n_threads)
+        builds each batch on the GPU with one kernel, bit-identical to `load_batch` and from the same numpy RNG draws.
+        `resample_targets`: HR / SM files stored at another ratio than the dataset's scale (2, 3 or 4 times the LR side) are
+        resampled to it on the device while the cache is built; without it such an imageset raises, as on the host path."""
+        return DeviceImagesetCache(self, device=device, n_threads=n_threads, resample_targets=resample_targets)
 
 
 def _round4(n):
@@ -188,16 +225,20 @@ def _round4(n):
 
 class ImagesetIndex:
     """The host half of DeviceImagesetCache, no GPU: every imageset directory listed once, clearance.npy loaded once, the LR
-    side read from one header, and where each image lives in the three arenas (LR / HR uint16, SM uint8; every image starts
-    at a multiple of 4 elements, as hrn_collate_device requires).  `plan()` turns a batch of indices into the kernel's plan
-    table with exactly the numpy RNG calls ImagesetDataset._plan makes, in the same order."""
+    side and the stored HR / SM side read from one header each, and where each image lives in the three arenas (LR / HR
+    uint16, SM uint8; every image starts at a multiple of 4 elements, as hrn_collate_device requires).  HR / SM slots hold
+    scale^2 side^2 samples, scale = dataset.scale.  `ratios[k]` is the ratio imageset k is stored at; one that differs from
+    the scale needs `resample_targets` (the cache then resamples it into its slot), else it is the host path's ValueError.
+    `plan()` turns a batch of indices into the kernel's plan table with exactly the numpy RNG calls ImagesetDataset._plan makes,
+    in the same order."""
 
-    def __init__(self, dataset):
+    def __init__(self, dataset, resample_targets=False):
         self.dataset = dataset
+        self.scale = scale = dataset.scale
         self.dirs = list(dataset.imset_dir)
         self.names = [os.path.basename(d) for d in self.dirs]
         self.position = dict(zip(self.names, range(len(self.dirs))))      # a repeated name resolves to its last directory, as name_to_dir
-        self.ids, self.clearances, self.sides, self.lr_off, self.hr_off, self.sm_off = [], [], [], [], [], []
+        self.ids, self.clearances, self.sides, self.lr_off, self.hr_off, self.sm_off, self.ratios = [], [], [], [], [], [], []
         lr_total = hr_total = sm_total = 0
         for d in self.dirs:
             ids, scores = _list_views(d)
@@ -210,14 +251,30 @@ class ImagesetIndex:
             slot = _round4(side * side)
             self.lr_off.append(lr_total + slot * np.arange(len(ids), dtype=np.int64))
             lr_total += slot * len(ids)
-            if os.path.exists(os.path.join(d, "HR.png")):
+            have_hr = os.path.exists(os.path.join(d, "HR.png"))
+            self.ratios.append(self._stored_ratio(d, side, have_hr, resample_targets))
+            if have_hr:
                 self.hr_off.append(hr_total)
-                hr_total += _round4(9 * side * side)
+                hr_total += _round4(scale * scale * side * side)
             else:
                 self.hr_off.append(-1)
             self.sm_off.append(sm_total)
-            sm_total += _round4(9 * side * side)
+            sm_total += _round4(scale * scale * side * side)
         self.lr_elems, self.hr_elems, self.sm_elems = lr_total, hr_total, sm_total
+
+    def _stored_ratio(self, d, side, have_hr, resample_targets):
+        """HR / LR ratio of the files of imageset `d`, from the SM (and HR) header: the scale itself, or with `resample_targets`
+        any of 2, 3, 4."""
+        found = [io_binding.png_info(os.path.join(d, f))[:2] for f in ["SM.png"] + (["HR.png"] if have_hr else [])]
+        w, h = found[0]
+        ok = all(wh == (w, h) for wh in found) and w == h and w % side == 0
+        ratio = w // side if ok else 0
+        if ratio != self.scale and not (resample_targets and ratio in resample.SCALES):
+            shown = w if ok else " / ".join(f"{a}x{b}" for a, b in found)
+            if resample_targets:
+                raise ValueError(f"{os.path.basename(d)}: HR / SM side {shown} is not 2, 3 or 4 times the LR side {side}: cannot resample")
+            raise _ratio_error(os.path.basename(d), side, self.scale, shown)
+        return ratio
 
     def __len__(self):
         return len(self.dirs)
@@ -253,7 +310,7 @@ class ImagesetIndex:
 
 class DeviceImagesetCache:
     """Every imageset of an ImagesetDataset decoded once and kept on the device (LR / HR as uint16, SM as uint8, allocated
-    through torch's caching allocator), and batches built there by one hrn_collate_device launch each:
+    through torch's caching allocator), and batches built there by one hrn_collate_device_s launch each:
 
         cache = dataset.to_device("cuda", n_threads=16)
         lrs, alphas, hrs, hr_maps, names = cache.load_batch(indices, min_L)      # device tensors, no file I/O
@@ -262,9 +319,15 @@ class DeviceImagesetCache:
     lacks HR.png, ValueError for mixed LR sizes, KeyError for an unknown name) and makes the same numpy RNG calls in the same
     order, so a seeded run picks the same views and patches on either path.  Per batch: the plan (Python, ImagesetIndex.plan),
     one small pinned host-to-device copy of the plan table and one kernel, all enqueued on the current stream; no
-    device-to-host copy and no synchronisation.  Memory: `nbytes` (2 B per LR / HR sample, 1 B per SM sample)."""
+    device-to-host copy and no synchronisation.  Memory: `nbytes` (2 B per LR / HR sample, 1 B per SM sample).
 
-    def __init__(self, dataset, device="cuda", n_threads=0, chunk_elems=1 << 26):
+    `resample_targets=True`: an imageset whose HR / SM files are stored at another ratio R than the dataset's scale is decoded
+    at R into a staging buffer and resampled into its arena slot by hrn_resample_targets (hrnet_hip/resample.py gives the rule:
+    Lanczos-3, widened when shrinking; a resampled SM sample is clear only if every source sample under its filter is), one
+    launch per (LR side, R) and arena; imagesets stored at the scale are kept as decoded.  The staging buffers are gone once the
+    cache is built; batches cost what they cost without resampling."""
+
+    def __init__(self, dataset, device="cuda", n_threads=0, chunk_elems=1 << 26, resample_targets=False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError(f"DeviceImagesetCache needs a ROCm device, got '{self.device}' (the host path is ImagesetDataset.load_batch)")
@@ -273,11 +336,13 @@ class DeviceImagesetCache:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         binding.load_library()
-        self.index = idx = ImagesetIndex(dataset)
+        self.index = idx = ImagesetIndex(dataset, resample_targets=resample_targets)
+        self.scale = idx.scale
         dev = self.device
         self.lr = torch.empty(idx.lr_elems, dtype=torch.uint16, device=dev)
         self.hr = torch.empty(idx.hr_elems, dtype=torch.uint16, device=dev) if idx.hr_elems else None
         self.sm = torch.empty(idx.sm_elems, dtype=torch.uint8, device=dev)
+        tables = {}                                                # (side, R) -> resampling weight table, for the build only
         # decode in chunks of consecutive imagesets (contiguous ranges of each arena) to bound host memory
         start = 0
         while start < len(idx):
@@ -285,29 +350,39 @@ class DeviceImagesetCache:
             while stop < len(idx) and (stop == start or elems < chunk_elems):
                 elems += len(idx.ids[stop]) * idx.sides[stop] ** 2
                 stop += 1
-            self._decode(start, stop, n_threads)
+            self._decode(start, stop, n_threads, tables)
             start = stop
 
-    def _decode(self, start, stop, n_threads):
-        idx = self.index
+    def _decode(self, start, stop, n_threads, tables):
+        idx, scale = self.index, self.scale
         lr_paths, lr_offs, lr_sides = [], [], []
         hr_paths, hr_offs, hr_sides, sm_paths, sm_offs, sm_sides = [], [], [], [], [], []
+        hr_stage, sm_stage = [], []                                # (path, arena offset, LR side, stored ratio) of images to resample
         for k in range(start, stop):
-            d, side = idx.dirs[k], idx.sides[k]
+            d, side, ratio = idx.dirs[k], idx.sides[k], idx.ratios[k]
             lr_paths += [os.path.join(d, f"LR{i}.png") for i in idx.ids[k]]
             lr_offs += list(idx.lr_off[k])
             lr_sides += [side] * len(idx.ids[k])
             if idx.hr_off[k] >= 0:
-                hr_paths.append(os.path.join(d, "HR.png"))
-                hr_offs.append(idx.hr_off[k])
-                hr_sides.append(3 * side)
-            sm_paths.append(os.path.join(d, "SM.png"))
-            sm_offs.append(idx.sm_off[k])
-            sm_sides.append(3 * side)
+                if ratio == scale:
+                    hr_paths.append(os.path.join(d, "HR.png"))
+                    hr_offs.append(idx.hr_off[k])
+                    hr_sides.append(scale * side)
+                else:
+                    hr_stage.append((os.path.join(d, "HR.png"), idx.hr_off[k], side, ratio))
+            if ratio == scale:
+                sm_paths.append(os.path.join(d, "SM.png"))
+                sm_offs.append(idx.sm_off[k])
+                sm_sides.append(scale * side)
+            else:
+                sm_stage.append((os.path.join(d, "SM.png"), idx.sm_off[k], side, ratio))
+        is_clear = lambda a: (a != 0).astype(np.uint8)
         for paths, offs, sides, arena, to_host in ((lr_paths, lr_offs, lr_sides, self.lr, None), (hr_paths, hr_offs, hr_sides, self.hr, None),
-                                                   (sm_paths, sm_offs, sm_sides, self.sm, lambda a: (a != 0).astype(np.uint8))):
+                                                   (sm_paths, sm_offs, sm_sides, self.sm, is_clear)):
             if not paths:
                 continue
+            # one contiguous host range from the first to the last image; slots of images to resample inside it are written
+            # (as zeros) here and filled afterwards, on the same stream
             offs = np.asarray(offs, np.int64)
             lo = int(offs[0])
             hi = int(offs[-1]) + _round4(sides[-1] ** 2)
@@ -317,6 +392,24 @@ class DeviceImagesetCache:
                 arena.view(torch.int16)[lo:hi].copy_(torch.from_numpy(host.view(np.int16)))
             else:
                 arena[lo:hi].copy_(torch.from_numpy(to_host(host)))
+        for stage, arena, to_host in ((hr_stage, self.hr, None), (sm_stage, self.sm, is_clear)):
+            for side, ratio in sorted({(s, r) for _, _, s, r in stage}):
+                group = [(p, o) for p, o, s, r in stage if (s, r) == (side, ratio)]
+                n_in, slot = ratio * side, _round4((ratio * side) ** 2)
+                host = np.zeros(slot * len(group), np.uint16)
+                src_offs = slot * np.arange(len(group), dtype=np.int64)
+                io_binding.read_many([p for p, _ in group], host, src_offs, [n_in] * len(group), [n_in] * len(group), n_threads=n_threads)
+                if to_host is None:
+                    staged = torch.from_numpy(host.view(np.int16)).to(self.device).view(torch.uint16)
+                else:
+                    staged = torch.from_numpy(to_host(host)).to(self.device)
+                if (side, ratio) not in tables:
+                    tables[side, ratio] = resample.weight_table(side, ratio, scale)
+                jobs = np.stack([src_offs, np.asarray([o for _, o in group], np.int64)], axis=1)
+                with torch.cuda.device(self.device):
+                    for at in range(0, len(jobs), 65535):
+                        binding.resample_targets(staged, arena, jobs[at:at + 65535], n_in, scale * side, tables[side, ratio])
+                    staged.record_stream(torch.cuda.current_stream())
 
     def __len__(self):
         return len(self.index)
@@ -326,15 +419,16 @@ class DeviceImagesetCache:
         return sum(t.numel() * t.element_size() for t in (self.lr, self.hr, self.sm) if t is not None)
 
     def load_batch(self, indices, min_L):
-        """(lrs (B,min_L,S,S), alphas (B,min_L), hrs (B,3S,3S) or [], hr_maps (B,3S,3S), names) on the cache's device."""
+        """(lrs (B,min_L,S,S), alphas (B,min_L), hrs (B,kS,kS) or [], hr_maps (B,kS,kS), names) on the cache's device; k = scale."""
         plan, names, S, have_hr = self.index.plan(indices, min_L)
         B = len(names)
         with torch.cuda.device(self.device):
             plan_d = torch.from_numpy(plan).pin_memory().to(self.device, non_blocking=True)
             mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
-            lrs, alphas, maps = mk(B, min_L, S, S), mk(B, min_L), mk(B, 3 * S, 3 * S)
-            hrs = mk(B, 3 * S, 3 * S) if have_hr else None
-            binding.collate_device(self.lr, self.hr, self.sm, plan_d, S, lrs, alphas, hrs, maps)
+            T = self.scale * S
+            lrs, alphas, maps = mk(B, min_L, S, S), mk(B, min_L), mk(B, T, T)
+            hrs = mk(B, T, T) if have_hr else None
+            binding.collate_device(self.lr, self.hr, self.sm, plan_d, S, lrs, alphas, hrs, maps, scale=self.scale)
         return lrs, alphas, hrs if have_hr else [], maps, names
 
     def batches(self, index_lists, min_L):

@@ -8,7 +8,10 @@ import ctypes
 import os
 import threading
 
+import numpy as np
 import torch
+
+from .resample import check_scale
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HRNET_HIP_LIB") or os.path.join(_HERE, "libhrnet_hip.so")   # override: A/B-testing a build
@@ -133,6 +136,11 @@ SIGNATURES = {
                                    _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_collate_device": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
                                       _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hrn_collate_device_s": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                        _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                        _c.c_void_p]),
+    "hrn_resample_targets": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int,
+                                        _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_profile_enable": (_c.c_int, [_c.c_int]),
     "hrn_profile_count": (_c.c_int, []),
     "hrn_profile_get": (_c.c_int, [_c.c_int, _c.c_char_p, _c.c_int, _c.POINTER(_c.c_long), _c.POINTER(_c.c_double),
@@ -585,28 +593,69 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_
 COLLATE_META = 5          # leading int64 fields of a plan row (HRN_COLLATE_META): hr_off, sm_off, side, row, col
 
 
-def collate_device(lr_arena, hr_arena, sm_arena, plan, S, lrs, alphas, hrs, maps):
+def collate_device(lr_arena, hr_arena, sm_arena, plan, S, lrs, alphas, hrs, maps, scale=3):
     """One launch on the current stream: gather + convert a batch from the device arenas (uint16 LR / HR, uint8 SM) into
-    lrs (B,min_L,S,S), alphas (B,min_L), hrs (B,3S,3S) or None, maps (B,3S,3S) f32, following `plan`, a device int64
-    (B, COLLATE_META + min_L) table (include/hrnet_hip.h, hrn_collate_device)."""
+    lrs (B,min_L,S,S), alphas (B,min_L), hrs (B,kS,kS) or None, maps (B,kS,kS) f32 with k = `scale` (2, 3 or 4: the HR / LR ratio
+    the arenas are stored at), following `plan`, a device int64 (B, COLLATE_META + min_L) table (include/hrnet_hip.h,
+    hrn_collate_device_s)."""
     B, min_L = alphas.shape
     use_hr = hrs is not None
+    scale = check_scale(scale)
     arenas = [("lr_arena", lr_arena, torch.uint16), ("sm_arena", sm_arena, torch.uint8), ("plan", plan, torch.int64)]
     for name, t, dt in arenas + ([("hr_arena", hr_arena, torch.uint16)] if use_hr else []):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() or t.dtype != dt:
             raise RuntimeError(f"{name} must be a contiguous {dt} ROCm device tensor")
     if tuple(plan.shape) != (B, COLLATE_META + min_L):
         raise ValueError(f"plan is {tuple(plan.shape)}, expected {(B, COLLATE_META + min_L)}")
-    outs = [("lrs", lrs, (B, min_L, S, S)), ("alphas", alphas, (B, min_L)), ("maps", maps, (B, 3 * S, 3 * S))]
+    outs = [("lrs", lrs, (B, min_L, S, S)), ("alphas", alphas, (B, min_L)), ("maps", maps, (B, scale * S, scale * S))]
     if hrs is not None:
-        outs.append(("hrs", hrs, (B, 3 * S, 3 * S)))
+        outs.append(("hrs", hrs, (B, scale * S, scale * S)))
     for name, t, shape in outs:
         if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32 or tuple(t.shape) != shape:
             raise ValueError(f"{name} must be a contiguous float32 device tensor of shape {shape}")
-    _check(load_library().hrn_collate_device(_ptr(lr_arena), lr_arena.numel(), _ptr(hr_arena) if use_hr else None,
-                                             hr_arena.numel() if use_hr else 0, _ptr(sm_arena), sm_arena.numel(), _ptr(plan), B, min_L, S,
-                                             _ptr(lrs), _ptr(alphas), _ptr(hrs) if use_hr else None, _ptr(maps), _stream()),
-           "hrn_collate_device")
+    _check(load_library().hrn_collate_device_s(_ptr(lr_arena), lr_arena.numel(), _ptr(hr_arena) if use_hr else None,
+                                               hr_arena.numel() if use_hr else 0, _ptr(sm_arena), sm_arena.numel(), _ptr(plan), B, min_L, S,
+                                               scale, _ptr(lrs), _ptr(alphas), _ptr(hrs) if use_hr else None, _ptr(maps), _stream()),
+           "hrn_collate_device_s")
+
+
+RESAMPLE_TAPS = 12        # HRN_RESAMPLE_TAPS: weights per output sample in a resampling table
+
+
+def resample_targets(src, dst, jobs, n_in, n_out, table):
+    """One launch on the current stream: every image of `jobs` - a host (n, 2) integer array of element offsets (source image in
+    `src`, result in `dst`) - resampled from n_in x n_in to n_out x n_out.  src / dst: 1-D device tensors, both uint16 (HR images:
+    fp64 sum, clip, round half to even) or both uint8 (status maps: clear only if every sample under a non-zero weight is clear).
+    table = (first, count, weights) from hrnet_hip.resample.weight_table, host arrays.  Everything is checked here, before the
+    launch (include/hrnet_hip.h, hrn_resample_targets)."""
+    for name, t in (("src", src), ("dst", dst)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() or t.dim() != 1 or t.dtype not in (torch.uint16, torch.uint8):
+            raise RuntimeError(f"{name} must be a contiguous 1-D uint16 or uint8 ROCm device tensor")
+    if src.dtype != dst.dtype or src.device != dst.device:
+        raise ValueError(f"src ({src.dtype}, {src.device}) and dst ({dst.dtype}, {dst.device}) must share dtype and device")
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in <= 0 or n_out <= 0 or not any(n_in * s == n_out * r for r in (2, 3, 4) for s in (2, 3, 4)):
+        raise ValueError(f"n_in : n_out must be R : S with R, S in {{2, 3, 4}}, got {n_in} : {n_out}")
+    jobs = np.ascontiguousarray(jobs, dtype=np.int64)
+    if jobs.ndim != 2 or jobs.shape[1] != 2 or not 0 < jobs.shape[0] <= 65535:
+        raise ValueError(f"jobs must be (n, 2) with 1 <= n <= 65535, got {jobs.shape}")
+    if jobs.min() < 0 or int(jobs[:, 0].max()) + n_in * n_in > src.numel() or int(jobs[:, 1].max()) + n_out * n_out > dst.numel():
+        raise ValueError("jobs: an image lies outside src / dst")
+    first, count, weights = (np.ascontiguousarray(a, dtype=dt) for a, dt in zip(table, (np.int32, np.int32, np.float64)))
+    if first.shape != (n_out,) or count.shape != (n_out,) or weights.shape != (n_out, RESAMPLE_TAPS):
+        raise ValueError(f"table must be first ({n_out},), count ({n_out},), weights ({n_out}, {RESAMPLE_TAPS})")
+    if first.min() < 0 or count.min() < 1 or count.max() > RESAMPLE_TAPS or int((first.astype(np.int64) + count).max()) > n_in:
+        raise ValueError("table: taps must lie inside the source image, 1..12 per output sample")
+    if not np.isfinite(weights).all():
+        raise ValueError("table: weights must be finite")
+    with torch.cuda.device(src.device):
+        dev = lambda a: torch.from_numpy(a).to(src.device)
+        jobs_d, first_d, count_d, weights_d = dev(jobs), dev(first), dev(count), dev(weights)
+        _check(load_library().hrn_resample_targets(_ptr(src), src.numel(), _ptr(dst), dst.numel(), src.element_size(), _ptr(jobs_d),
+                                                   jobs.shape[0], n_in, n_out, _ptr(first_d), _ptr(count_d), _ptr(weights_d), _stream()),
+               "hrn_resample_targets")
+        for t in (jobs_d, first_d, count_d, weights_d):
+            t.record_stream(torch.cuda.current_stream())
 
 
 # --------------------------------------------------------------------------- built-in kernel timing

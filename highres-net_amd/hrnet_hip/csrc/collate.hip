@@ -1,11 +1,12 @@
 // Batch assembly from the HBM-resident imageset cache (DataLoader.DeviceImagesetCache): the device side of
 // ImagesetDataset.load_batch.  The PNGs were decoded once into three arenas (LR and HR uint16, SM uint8); a small plan table
 // (one row per sample, built on the host from the same numpy RNG draws as the host path) says which stored views fill the
-// min_L slots and where the patch sits.  ONE launch writes lrs (B,min_L,S,S), alphas (B,min_L), hrs and maps (B,3S,3S), f32,
-// padding included, with the host's value rules: (float)((double)u / 65535.0) for LR / HR, (u != 0) for the map.
+// min_L slots and where the patch sits.  ONE launch writes lrs (B,min_L,S,S), alphas (B,min_L), hrs and maps (B,kS,kS), f32,
+// padding included, with the host's value rules: (float)((double)u / 65535.0) for LR / HR, (u != 0) for the map.  k is the
+// target scale (2, 3 or 4; hrn_collate_device is k = 3): HR / SM are stored at k * side.
 //
-// Work unit = one block per (sample, S*S output elements): the min_L LR slots, then the 9 S*S pieces of the SM plane, then
-// (with hrs) the 9 pieces of the HR plane, so every block moves the same bytes.  A gather + convert: 2 B (LR / HR) or 1 B (SM)
+// Work unit = one block per (sample, S*S output elements): the min_L LR slots, then the k*k S*S pieces of the SM plane, then
+// (with hrs) the k*k pieces of the HR plane, so every block moves the same bytes.  A gather + convert: 2 B (LR / HR) or 1 B (SM)
 // read and 4 B written per element, no reuse - bound by HBM and, at these sizes, by the launch itself.  Vector path (S % 4 == 0):
 // a lane owns 4 consecutive outputs of one row, reads them with one or two aligned 8-byte (uint16) / 4-byte (uint8) loads
 // (the patch corner is arbitrary, so the 4 samples are funnel-shifted out of two words) and writes one 16-byte store.
@@ -16,7 +17,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMeta = HRN_COLLATE_META;                 // plan row: hr_off, sm_off, side, row, col, then min_L LR offsets
-constexpr long long kMaxSide = 1 << 20;                  // a larger stored side is a bad row (keeps 9 side^2 far from int64 overflow)
+constexpr long long kMaxSide = 1 << 20;                  // a larger stored side is a bad row (keeps 16 side^2 far from int64 overflow)
 
 // 4 consecutive samples from element i of an arena whose images start at multiples of 4 elements and whose size is a multiple
 // of 4: the second word is read only when i is not 4-aligned, and then it holds element i + 3, so it lies inside the arena.
@@ -41,13 +42,14 @@ template <bool VEC>
 __global__ __launch_bounds__(kThreads) void collate_kernel(const uint16_t* __restrict__ lr_arena, long long lr_n,
                                                            const uint16_t* __restrict__ hr_arena, long long hr_n,
                                                            const uint8_t* __restrict__ sm_arena, long long sm_n,
-                                                           const long long* __restrict__ plan, int min_L, int S,
+                                                           const long long* __restrict__ plan, int min_L, int S, int scale,
                                                            float* __restrict__ lrs, float* __restrict__ alphas,
                                                            float* __restrict__ hrs, float* __restrict__ maps) {
     const int b = blockIdx.y, unit = blockIdx.x;
     const long long* p = plan + (size_t)b * (kMeta + min_L);
     const long long side = p[2], r0 = p[3], c0 = p[4];
     const unsigned SS = (unsigned)S * (unsigned)S;
+    const int pieces = scale * scale;                    // S*S pieces per HR / SM plane (S <= 8192: 16 SS fits in 32 bits)
     int kind;                                            // 0 LR, 1 HR, 2 SM
     long long off, n;
     unsigned W, e0;
@@ -62,17 +64,17 @@ __global__ __launch_bounds__(kThreads) void collate_kernel(const uint16_t* __res
         if (threadIdx.x == 0) alphas[(size_t)b * min_L + unit] = off >= 0 ? 1.f : 0.f;
     } else {
         const int k = unit - min_L;
-        kind = k < 9 ? 2 : 1;
+        kind = k < pieces ? 2 : 1;
         off = kind == 1 ? p[0] : p[1];
         n = kind == 1 ? hr_n : sm_n;
-        W = 3 * S;
-        e0 = (unsigned)(k % 9) * SS;
-        out = (kind == 1 ? hrs : maps) + (size_t)b * 9 * SS;
+        W = (unsigned)scale * S;
+        e0 = (unsigned)(k % pieces) * SS;
+        out = (kind == 1 ? hrs : maps) + (size_t)b * pieces * SS;
     }
     // a plan row that points outside its arena or a corner outside the stored image: NaN, never an out-of-bounds read.  Every
-    // comparison is arranged so that no int64 sum overflows, whatever the row holds (side is bounded first).
+    // comparison is arranged so that no int64 sum overflows, whatever the row holds (side is bounded first: pitch <= 2^22).
     const bool bad_row = side <= 0 || side > kMaxSide || r0 < 0 || c0 < 0 || r0 > side - S || c0 > side - S;
-    const long long scale = kind == 0 ? 1 : 3, pitch = scale * (bad_row ? 0 : side), sr0 = scale * r0, sc0 = scale * c0;
+    const long long mul = kind == 0 ? 1 : scale, pitch = mul * (bad_row ? 0 : side), sr0 = mul * r0, sc0 = mul * c0;
     const bool bad = off >= 0 && (bad_row || (off & 3) || off > n - pitch * pitch);
     if (off < 0 || bad) {                                // padding slot (alpha 0) / sample without HR: zeros
         const float fill = bad ? __builtin_nanf("") : 0.f;
@@ -111,9 +113,10 @@ __global__ __launch_bounds__(kThreads) void collate_kernel(const uint16_t* __res
 
 }  // namespace
 
-extern "C" int hrn_collate_device(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems,
-                                  const uint8_t* sm_arena, int64_t sm_elems, const int64_t* plan, int B, int min_L, int S,
-                                  float* lrs, float* alphas, float* hrs, float* maps, void* stream) {
+extern "C" int hrn_collate_device_s(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems,
+                                    const uint8_t* sm_arena, int64_t sm_elems, const int64_t* plan, int B, int min_L, int S, int scale,
+                                    float* lrs, float* alphas, float* hrs, float* maps, void* stream) {
+    HRN_CHECK(hrn_scale_ok(scale), -2, "hrn_collate_device: scale must be 2, 3 or 4 (got %d)", scale);
     HRN_CHECK(lr_arena && sm_arena && plan && lrs && alphas && maps, -2, "hrn_collate_device: null argument");
     HRN_CHECK(!hrs || hr_arena, -2, "hrn_collate_device: hrs given without an HR arena");
     HRN_CHECK(B > 0 && B <= 65535, -2, "hrn_collate_device: B must be in 1..65535 (got %d)", B);
@@ -124,13 +127,23 @@ extern "C" int hrn_collate_device(const uint16_t* lr_arena, int64_t lr_elems, co
     HRN_CHECK(((uintptr_t)lr_arena | (uintptr_t)hr_arena) % 8 == 0 && (uintptr_t)sm_arena % 4 == 0, -2,
               "hrn_collate_device: arenas must be 8-byte (uint16) / 4-byte (uint8) aligned");
     const bool vec = S % 4 == 0 && ((uintptr_t)lrs | (uintptr_t)hrs | (uintptr_t)maps) % 16 == 0;
-    const dim3 grid((unsigned)(min_L + 9 + (hrs ? 9 : 0)), (unsigned)B);
+    const int pieces = scale * scale;
+    const dim3 grid((unsigned)(min_L + pieces + (hrs ? pieces : 0)), (unsigned)B);
     if (vec)
         hipLaunchKernelGGL(collate_kernel<true>, grid, dim3(kThreads), 0, (hipStream_t)stream, lr_arena, (long long)lr_elems, hr_arena,
-                           (long long)hr_elems, sm_arena, (long long)sm_elems, (const long long*)plan, min_L, S, lrs, alphas, hrs, maps);
+                           (long long)hr_elems, sm_arena, (long long)sm_elems, (const long long*)plan, min_L, S, scale, lrs, alphas, hrs,
+                           maps);
     else
         hipLaunchKernelGGL(collate_kernel<false>, grid, dim3(kThreads), 0, (hipStream_t)stream, lr_arena, (long long)lr_elems, hr_arena,
-                           (long long)hr_elems, sm_arena, (long long)sm_elems, (const long long*)plan, min_L, S, lrs, alphas, hrs, maps);
+                           (long long)hr_elems, sm_arena, (long long)sm_elems, (const long long*)plan, min_L, S, scale, lrs, alphas, hrs,
+                           maps);
     HRN_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int hrn_collate_device(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems,
+                                  const uint8_t* sm_arena, int64_t sm_elems, const int64_t* plan, int B, int min_L, int S,
+                                  float* lrs, float* alphas, float* hrs, float* maps, void* stream) {
+    return hrn_collate_device_s(lr_arena, lr_elems, hr_arena, hr_elems, sm_arena, sm_elems, plan, B, min_L, S, 3, lrs, alphas, hrs, maps,
+                                stream);
 }

@@ -150,9 +150,10 @@ int hrn_io_png_read_u16(const char* path, uint16_t* out, int width, int height) 
     return read_crop(path, width, height, out, 0, height, 0, width, (size_t)width);
 }
 
-int hrn_io_collate(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,
-                   const char* const* sm_paths, int min_L, int lr_size, int patch, const int* px, const int* py,
-                   float* lrs, float* alphas, float* hrs, float* maps, int n_threads) {
+int hrn_io_collate_s(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,
+                     const char* const* sm_paths, int min_L, int lr_size, int patch, int scale, const int* px, const int* py,
+                     float* lrs, float* alphas, float* hrs, float* maps, int n_threads) {
+    if (scale < 2 || scale > 4) { set_err("hrn_io_collate: scale must be 2, 3 or 4 (got %d)", scale); return -2; }
     if (n_sets <= 0 || !lr_paths || !n_views || !sm_paths || min_L <= 0 || lr_size <= 0 || patch < 0 || !lrs || !alphas || !maps ||
         (patch > 0 && (!px || !py)) || (hr_paths && !hrs)) {
         set_err("hrn_io_collate: bad argument");
@@ -184,7 +185,7 @@ int hrn_io_collate(int n_sets, const char* const* lr_paths, const int* n_views, 
     std::string first_error;
     std::atomic<bool> have_error(false);
     auto worker = [&]() {
-        std::vector<uint16_t> buf((size_t)9 * S * S);
+        std::vector<uint16_t> buf((size_t)scale * scale * S * S);
         for (;;) {
             const size_t i = next.fetch_add(1);
             if (i >= items.size() || status.load() != 0) return;
@@ -198,8 +199,9 @@ int hrn_io_collate(int n_sets, const char* const* lr_paths, const int* n_views, 
                     for (size_t k = 0; k < (size_t)S * S; ++k) o[k] = (float)((double)buf[k] / 65535.0);   // img_as_float -> float32
                 }
             } else {
-                const int S3 = 3 * S;
-                rc = read_crop(it.path, 3 * lr_size, 3 * lr_size, buf.data(), 3 * x, 3 * x + S3, 3 * y, 3 * y + S3, (size_t)S3);
+                const int S3 = scale * S;                                                   // HR / SM side of the batch
+                rc = read_crop(it.path, scale * lr_size, scale * lr_size, buf.data(), scale * x, scale * x + S3, scale * y, scale * y + S3,
+                               (size_t)S3);
                 if (!rc) {
                     float* o = (it.kind == 1 ? hrs : maps) + (size_t)it.set * S3 * S3;
                     if (it.kind == 1) for (size_t k = 0; k < (size_t)S3 * S3; ++k) o[k] = (float)((double)buf[k] / 65535.0);
@@ -223,6 +225,12 @@ int hrn_io_collate(int n_sets, const char* const* lr_paths, const int* n_views, 
     for (auto& th : pool) th.join();
     if (status.load() != 0) { set_err("%s", first_error.c_str()); return status.load(); }
     return 0;
+}
+
+int hrn_io_collate(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,
+                   const char* const* sm_paths, int min_L, int lr_size, int patch, const int* px, const int* py,
+                   float* lrs, float* alphas, float* hrs, float* maps, int n_threads) {
+    return hrn_io_collate_s(n_sets, lr_paths, n_views, hr_paths, sm_paths, min_L, lr_size, patch, 3, px, py, lrs, alphas, hrs, maps, n_threads);
 }
 
 int hrn_io_read_many_u16(int n, const char* const* paths, uint16_t* out, const int64_t* offsets, const int* expect_w,

@@ -6,6 +6,8 @@ import os
 
 import numpy as np
 
+from .resample import check_scale
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HRNET_IO_LIB") or os.path.join(_HERE, "libhrnet_io.so")
 
@@ -19,6 +21,8 @@ SIGNATURES = {
     "hrn_io_png_read_u16": (_c.c_int, [_c.c_char_p, _c.c_void_p, _c.c_int, _c.c_int]),
     "hrn_io_collate": (_c.c_int, [_c.c_int, _pp, _ip, _pp, _pp, _c.c_int, _c.c_int, _c.c_int, _ip, _ip,
                                   _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int]),
+    "hrn_io_collate_s": (_c.c_int, [_c.c_int, _pp, _ip, _pp, _pp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _ip, _ip,
+                                    _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int]),
     "hrn_io_read_many_u16": (_c.c_int, [_c.c_int, _pp, _c.c_void_p, _c.POINTER(_c.c_int64), _ip, _ip, _c.c_int]),
 }
 _lib = None
@@ -69,18 +73,21 @@ def _strs(paths):
     return arr
 
 
-def collate(lr_paths_per_set, hr_paths, sm_paths, min_L, lr_size, patch=0, corners=None, out=None, n_threads=0):
+def collate(lr_paths_per_set, hr_paths, sm_paths, min_L, lr_size, patch=0, corners=None, out=None, n_threads=0, scale=3):
     """lr_paths_per_set: list (one per imageset) of lists of LR files in use order; hr_paths: list of paths / None entries
     or None; sm_paths: list of paths; corners: list of (x, y) = (row, column) per imageset when patch > 0.
-    out: optional dict of preallocated float32 buffers 'lrs' (B,min_L,S,S), 'alphas' (B,min_L), 'hrs', 'maps' (B,3S,3S) -
-    numpy arrays or CPU torch tensors (e.g. pinned).  Returns that dict (numpy arrays when it allocates)."""
+    out: optional dict of preallocated float32 buffers 'lrs' (B,min_L,S,S), 'alphas' (B,min_L), 'hrs', 'maps' (B,kS,kS) -
+    numpy arrays or CPU torch tensors (e.g. pinned).  Returns that dict (numpy arrays when it allocates).
+    scale: k, the HR / LR ratio of the files (2, 3 or 4); a file of another size is an HrnetIoError that names it."""
+    scale = check_scale(scale)
     lib = load_library()
     B = len(lr_paths_per_set)
     S = patch if patch > 0 else lr_size
+    T = scale * S                                                 # HR / SM side of the batch
     have_hr = hr_paths is not None and any(p is not None for p in hr_paths)
     if out is None:
         out = dict(lrs=np.empty((B, min_L, S, S), np.float32), alphas=np.empty((B, min_L), np.float32),
-                   hrs=np.empty((B, 3 * S, 3 * S), np.float32) if have_hr else None, maps=np.empty((B, 3 * S, 3 * S), np.float32))
+                   hrs=np.empty((B, T, T), np.float32) if have_hr else None, maps=np.empty((B, T, T), np.float32))
 
     def ptr(t, shape):
         if t is None:
@@ -101,10 +108,10 @@ def collate(lr_paths_per_set, hr_paths, sm_paths, min_L, lr_size, patch=0, corne
     if patch > 0:
         px = (_c.c_int * B)(*[int(c[0]) for c in corners])
         py = (_c.c_int * B)(*[int(c[1]) for c in corners])
-    _check(lib.hrn_io_collate(B, _strs(flat), nv, _strs(hr_paths) if have_hr else None, _strs(sm_paths), int(min_L), int(lr_size),
-                              int(patch), px, py, ptr(out["lrs"], (B, min_L, S, S)), ptr(out["alphas"], (B, min_L)),
-                              ptr(out.get("hrs") if have_hr else None, (B, 3 * S, 3 * S)), ptr(out["maps"], (B, 3 * S, 3 * S)),
-                              int(n_threads)), "hrn_io_collate")
+    _check(lib.hrn_io_collate_s(B, _strs(flat), nv, _strs(hr_paths) if have_hr else None, _strs(sm_paths), int(min_L), int(lr_size),
+                                int(patch), scale, px, py, ptr(out["lrs"], (B, min_L, S, S)), ptr(out["alphas"], (B, min_L)),
+                                ptr(out.get("hrs") if have_hr else None, (B, T, T)), ptr(out["maps"], (B, T, T)), int(n_threads)),
+           "hrn_io_collate_s")
     return out
 
 

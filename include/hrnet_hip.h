@@ -21,7 +21,9 @@
  *   hrn_adam_step          <-  optimizer.step() of torch.optim.Adam   src/train.py:191, :252
  *   hrn_get_loss / hrn_shift_cpsnr  <-  get_loss (train.py:66-87) / shift_cPSNR (Evaluator.py:52-73)
  *   hrn_collate_device     <-  collateFunction(min_L) over ImagesetDataset items (src/utils.py:63-113), gathered from
- *                              imagesets decoded once into HBM (DataLoader.DeviceImagesetCache)
+ *                              imagesets decoded once into HBM (DataLoader.DeviceImagesetCache); hrn_collate_device_s
+ *                              is the same for x2 / x3 / x4 targets
+ *   hrn_resample_targets   <-  (no counterpart) HR / SM stored at one ratio resampled to another when the cache is built
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor's data_ptr) unless stated;
@@ -301,6 +303,28 @@ int hrn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
 int hrn_collate_device(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems,
                        const uint8_t* sm_arena, int64_t sm_elems, const int64_t* plan, int B, int min_L, int S,
                        float* lrs, float* alphas, float* hrs, float* maps, void* stream);
+/* The same at target scale 2, 3 or 4 (anything else: -2 before any launch): the stored HR / SM images are scale * side,
+ * hrs / maps are (B, scale*S, scale*S) and the HR / SM window starts at (scale*row, scale*col).  The plan row layout does
+ * not change.  hrn_collate_device is this call with scale = 3. */
+int hrn_collate_device_s(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems,
+                         const uint8_t* sm_arena, int64_t sm_elems, const int64_t* plan, int B, int min_L, int S, int scale,
+                         float* lrs, float* alphas, float* hrs, float* maps, void* stream);
+
+/* hrn_resample_targets: HR images (elem_bytes 2, uint16) or status maps (elem_bytes 1, uint8, 0 / non-zero) stored at
+ * n_in x n_in resampled to n_out x n_out, for a cache whose target scale differs from the ratio the files were stored at
+ * (DataLoader.DeviceImagesetCache, resample_targets=True).  One launch for all `n_jobs` images (1..65535):
+ *   jobs                  : (n_jobs, 2) int64: element offset of the source image in `src`, of the result in `dst`
+ *   first, count, weights : the separable filter, one row per output sample j (used for rows and for columns):
+ *                           source taps first[j] .. first[j] + count[j] - 1 with weights[j * HRN_RESAMPLE_TAPS + t], fp64,
+ *                           computed on the host (hrnet_hip/resample.py: Lanczos-3, widened when shrinking, rows normalised)
+ *   uint16 : v = sum_r w_r (sum_c w_c u[r][c]) in fp64, clipped to [0, 65535], rounded half-to-even
+ *   uint8  : 1 if every source sample under a non-zero weight (both axes) is non-zero, else 0
+ * n_in : n_out must be R : S for some R, S in {2, 3, 4}.  A job that does not fit `src_elems` / `dst_elems` writes nothing;
+ * table entries are clamped to the source image (never an out-of-bounds read).  Deterministic, no atomics. */
+#define HRN_RESAMPLE_TAPS 12
+int hrn_resample_targets(const void* src, int64_t src_elems, void* dst, int64_t dst_elems, int elem_bytes,
+                         const int64_t* jobs, int n_jobs, int n_in, int n_out, const int32_t* first, const int32_t* count,
+                         const double* weights, void* stream);
 
 /* ------------------------------------------------------------------ built-in kernel timing (hipEvent pairs)
  * The reference has no profiling hooks; these exist so that bench.py can state, live, the

@@ -50,6 +50,12 @@ int hrn_io_png_read_u16(const char* path, uint16_t* out, int width, int height);
 int hrn_io_collate(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,
                    const char* const* sm_paths, int min_L, int lr_size, int patch, const int* px, const int* py,
                    float* lrs, float* alphas, float* hrs, float* maps, int n_threads);
+/* The same at target scale 2, 3 or 4 (anything else: -2, no buffer touched): HR / SM files are scale * lr_size a side (a file
+ * of another size is a -4 error that names it), the HR / SM window is [scale*x : scale*x + scale*patch, ...] and hrs / maps
+ * are (n_sets, scale*S, scale*S).  hrn_io_collate is this call with scale = 3. */
+int hrn_io_collate_s(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,
+                     const char* const* sm_paths, int min_L, int lr_size, int patch, int scale, const int* px, const int* py,
+                     float* lrs, float* alphas, float* hrs, float* maps, int n_threads);
 
 /* Decode n PNGs (8- or 16-bit grayscale, as hrn_io_png_read_u16) into one caller-owned uint16 arena: image i goes to
  * out[offsets[i] .. offsets[i] + expect_w[i] * expect_h[i]) as rows of expect_w[i] samples; its size must match the file.

@@ -6,15 +6,17 @@
 
 at the reference's training shape (config/config.json: batch 32, up to 32 views, 64 x 64 patches) with synthetic data.
 usage: python tools/train_step_bench.py [B V S steps] [--torch-adam] [--precision P[,P...]] [--shiftnet-precision P[,P...]] [--repeats R]
-                                        [--freeze F[,F...]]
+                                        [--freeze F[,F...]] [--scale K]
 
 --precision sets HRNet.train_precision (fp32, bf16x3 or bf16; default: not set, i.e. the module's default rules), --shiftnet-precision
 ShiftNet.train_precision (fp32 or bf16; default: not set).  With several values, one pair of models per combination is built and their
 timing rounds alternate, R rounds each (--repeats, default 1).  --freeze times the step with part of the models frozen
 (requires_grad_(False) before the optimiser is built, as in fine-tuning): none (default), encoder (HRNet's encoder), encoder+fuse (HRNet's
 encoder and fusion block: only the decoder trains) or shiftnet (a fixed ShiftNet that only passes d x back into HRNet); several values
-alternate in one process like the precisions.
+alternate in one process like the precisions.  --scale K (2, 3 or 4; default 3) times the x2 / x4 step: a stride-K decoder (freshly
+initialised for K != 3, on the seeded x3 encoder and fusion block) and K S x K S targets; K * S must reach ShiftNet's 128-pixel window.
 """
+import copy
 import os
 import sys
 import time
@@ -49,7 +51,7 @@ def get_loss_cpsnr(srs, hrs, hr_maps):                        # train.py:66-87
 def _options(argv):
     pos, opts, i = [], {}, 0
     while i < len(argv):
-        if argv[i] in ("--precision", "--shiftnet-precision", "--repeats", "--freeze"):
+        if argv[i] in ("--precision", "--shiftnet-precision", "--repeats", "--freeze", "--scale"):
             opts[argv[i]] = argv[i + 1]
             i += 2
         else:
@@ -84,18 +86,26 @@ def main():
     for p in sprecs:
         if p not in (None, "fp32", "bf16"):
             raise SystemExit(f"--shiftnet-precision: fp32 or bf16 (got {p!r})")
+    scale = int(opts.get("--scale", 3))                      # upscale factor: decoder stride and HR / LR ratio of the targets
+    if scale not in (2, 3, 4) or scale * S < 128:
+        raise SystemExit(f"--scale: 2, 3 or 4 with scale * S >= 128, ShiftNet's window (got {scale}, S = {S})")
     dev = torch.device("cuda:0")
     lrs, alphas = synth.fast_batch(3, B, V, S)
     rng = np.random.Generator(np.random.PCG64(1))
-    hrs = torch.from_numpy((rng.random((B, 3 * S, 3 * S), dtype=np.float32) * 0.25)).to(dev)
-    maps = torch.ones((B, 3 * S, 3 * S), device=dev)
+    hrs = torch.from_numpy((rng.random((B, scale * S, scale * S), dtype=np.float32) * 0.25)).to(dev)
+    maps = torch.ones((B, scale * S, scale * S), device=dev)
     maps[:, :3] = 0; maps[:, -3:] = 0; maps[:, :, :3] = 0; maps[:, :, -3:] = 0
     x, a = torch.from_numpy(lrs).to(dev), torch.from_numpy(alphas).to(dev)
-    off = (3 * S - 128) // 2
+    off = (scale * S - 128) // 2
 
     def setup(prec, sprec, freeze):
-        fusion = HRNet({k: dict(v) for k, v in weights.HRNET_CONFIG.items()})
-        fusion.load_state_dict(weights.to_torch_state(weights.hrnet_state(1234)))
+        cfg = copy.deepcopy(weights.HRNET_CONFIG)
+        cfg["decoder"]["deconv"]["kernel_size"] = cfg["decoder"]["deconv"]["stride"] = scale
+        fusion = HRNet(cfg)
+        state = weights.to_torch_state(weights.hrnet_state(1234))
+        if scale != 3:                                       # the x3 -> x2 / x4 recipe: a freshly initialised decoder on the x3 body
+            state = {k: v for k, v in state.items() if not k.startswith("decode.")}
+        fusion.load_state_dict(state, strict=scale == 3)
         fusion.train_precision = prec
         regis = ShiftNet()
         if sprec is not None:
@@ -134,7 +144,7 @@ def main():
             torch.cuda.synchronize()
             dt = (time.time() - t0) / steps
             times[p].append(dt)
-            print(f"train step B={B} V={V} S={S} {_label(p)}: {dt * 1e3:.1f} ms/step ({B / dt:.0f} samples/s, {1 / dt:.2f} steps/s), "
+            print(f"train step B={B} V={V} S={S}{f' scale={scale}' if scale != 3 else ''} {_label(p)}: {dt * 1e3:.1f} ms/step ({B / dt:.0f} samples/s, {1 / dt:.2f} steps/s), "
                   f"loss {float(loss.detach()):.3f}, peak memory {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB, "
                   f"optimiser {type(r[2]).__name__}")
     if repeats > 1 or len(runs) > 1:
