@@ -359,7 +359,8 @@ def hrnet_backward(packed_f32, named_params, named_grads, num_layers, alpha_resi
                    d_lrs=None, d_alphas=None, select=False):
     """Accumulates dLoss/dparam into named_grads (same keys / shapes as named_params, f32, zero them for plain gradients).  d_lrs
     (B,V,H,W) / d_alphas (B,V): contiguous f32 device tensors that receive (are overwritten with) the input gradients, or None.
-    select: named_grads holds only the parameters that want a gradient (hrn_hrnet_backward_sel: the work of the others is skipped)."""
+    select: named_grads holds only the parameters that want a gradient (the work of the others is skipped); otherwise it must hold
+    every parameter.  One C call either way: hrn_hrnet_backward_sel, which leaves out whatever a NULL field or pointer does not ask for."""
     lib = load_library()
     lrs = _dev_f32(lrs, "lrs")
     alphas = _dev_f32(alphas, "alphas")
@@ -379,20 +380,10 @@ def hrnet_backward(packed_f32, named_params, named_grads, num_layers, alpha_resi
         if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != lrs.device):
             raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on {lrs.device}")
     with torch.cuda.device(lrs.device):
-        if select:
-            _check(lib.hrn_hrnet_backward_sel(_ptr(packed_f32), int(dtype), int(scale), ctypes.byref(P), int(bool(alpha_residual)),
-                                              _ptr(lrs), _ptr(alphas), B, V, H, W, _ptr(d_sr), ctypes.byref(G),
-                                              _ptr(d_lrs) if d_lrs is not None else None, _ptr(d_alphas) if d_alphas is not None else None,
-                                              _ptr(tws), tws.numel(), _stream()), "hrn_hrnet_backward_sel")
-        elif d_lrs is None and d_alphas is None:
-            _check(lib.hrn_hrnet_backward_s(_ptr(packed_f32), int(dtype), int(scale), ctypes.byref(P), int(bool(alpha_residual)), _ptr(lrs),
-                                            _ptr(alphas), B, V, H, W, _ptr(d_sr), ctypes.byref(G), _ptr(tws), tws.numel(), _stream()),
-                   "hrn_hrnet_backward")
-        else:
-            _check(lib.hrn_hrnet_backward_in(_ptr(packed_f32), int(dtype), int(scale), ctypes.byref(P), int(bool(alpha_residual)),
-                                             _ptr(lrs), _ptr(alphas), B, V, H, W, _ptr(d_sr), ctypes.byref(G),
-                                             _ptr(d_lrs) if d_lrs is not None else None, _ptr(d_alphas) if d_alphas is not None else None,
-                                             _ptr(tws), tws.numel(), _stream()), "hrn_hrnet_backward_in")
+        _check(lib.hrn_hrnet_backward_sel(_ptr(packed_f32), int(dtype), int(scale), ctypes.byref(P), int(bool(alpha_residual)),
+                                          _ptr(lrs), _ptr(alphas), B, V, H, W, _ptr(d_sr), ctypes.byref(G),
+                                          _ptr(d_lrs) if d_lrs is not None else None, _ptr(d_alphas) if d_alphas is not None else None,
+                                          _ptr(tws), tws.numel(), _stream()), "hrn_hrnet_backward")
 
 
 # --------------------------------------------------------------------------- ShiftNet
@@ -432,31 +423,6 @@ def shiftnet_pack(named):
     return packed
 
 
-def shiftnet_forward(packed, named, x, train_bn=False, momentum=0.1, dropout_mask=None):
-    """x (B,2,128,128) -> theta (B,2).  `named` supplies the live BatchNorm tensors (running stats are updated in
-    place when train_bn) and fc1.weight, which the kernel reads in place.  dropout_mask: None or uint8 (B,32768) keep-mask in the reference's flatten order."""
-    lib = load_library()
-    x = _dev_f32(x, "x")
-    if x.dim() != 4 or tuple(x.shape[1:]) != (2, 128, 128):
-        raise ValueError(f"ShiftNet input must be (B,2,128,128) (fc1 is hard-wired to 128*16*16, ShiftNet.py:44); got {tuple(x.shape)}")
-    B = x.shape[0]
-    keep = []
-    P = _shiftnet_struct(named, keep, True)        # (fc1.weight is read in place by the kernel: not part of `packed`)
-    mptr = ctypes.c_void_p(0)
-    if dropout_mask is not None:
-        if dropout_mask.dtype != torch.uint8 or tuple(dropout_mask.shape) != (B, 32768) or not dropout_mask.is_cuda:
-            raise ValueError("dropout_mask must be a uint8 device tensor of shape (B, 32768)")
-        dropout_mask = dropout_mask.contiguous()
-        mptr = _ptr(dropout_mask)
-    with torch.cuda.device(x.device):
-        nws = lib.hrn_shiftnet_workspace_bytes(B)
-        ws = _workspace(nws, x.device, "shiftnet")
-        theta = torch.empty((B, 2), dtype=torch.float32, device=x.device)
-        _check(lib.hrn_shiftnet_forward(_ptr(packed), ctypes.byref(P), _ptr(x), B, int(bool(train_bn)), float(momentum), mptr,
-                                        _ptr(theta), _ptr(ws), ws.numel(), _stream()), "hrn_shiftnet_forward")
-    return theta
-
-
 def _check_shiftnet_input(x, dropout_mask):
     if x.dim() != 4 or tuple(x.shape[1:]) != (2, 128, 128):
         raise ValueError(f"ShiftNet input must be (B,2,128,128) (fc1 is hard-wired to 128*16*16, ShiftNet.py:44); got {tuple(x.shape)}")
@@ -469,34 +435,48 @@ def _check_shiftnet_input(x, dropout_mask):
     return _ptr(dropout_mask), dropout_mask
 
 
-def shiftnet_forward_train(packed, named, x, momentum=0.1, dropout_mask=None, dtype=F32):
-    """Train-mode forward that keeps its intermediates: returns (theta (B,2), train_ws).  dtype: storage of the workspace's activations,
-    F32 (hrn_shiftnet_forward_train) or BF16 (hrn_shiftnet_forward_train_dt); `packed` is the fp32 blob in both."""
+def shiftnet_forward(packed, named, x, train_bn=False, momentum=0.1, dropout_mask=None):
+    """x (B,2,128,128) -> theta (B,2).  `named` supplies the live BatchNorm tensors (running stats are updated in
+    place when train_bn) and fc1.weight, which the kernel reads in place.  dropout_mask: None or uint8 (B,32768) keep-mask in the reference's flatten order."""
     lib = load_library()
     x = _dev_f32(x, "x")
     mptr, dropout_mask = _check_shiftnet_input(x, dropout_mask)
     B = x.shape[0]
     keep = []
     P = _shiftnet_struct(named, keep, True)        # (fc1.weight is read in place by the kernel: not part of `packed`)
-    nbytes = lib.hrn_shiftnet_train_workspace_bytes(B) if dtype == F32 else lib.hrn_shiftnet_train_workspace_bytes_dt(int(dtype), B)
+    with torch.cuda.device(x.device):
+        nws = lib.hrn_shiftnet_workspace_bytes(B)
+        ws = _workspace(nws, x.device, "shiftnet")
+        theta = torch.empty((B, 2), dtype=torch.float32, device=x.device)
+        _check(lib.hrn_shiftnet_forward(_ptr(packed), ctypes.byref(P), _ptr(x), B, int(bool(train_bn)), float(momentum), mptr,
+                                        _ptr(theta), _ptr(ws), ws.numel(), _stream()), "hrn_shiftnet_forward")
+    return theta
+
+
+def shiftnet_forward_train(packed, named, x, momentum=0.1, dropout_mask=None, dtype=F32):
+    """Train-mode forward that keeps its intermediates: returns (theta (B,2), train_ws).  dtype: storage of the workspace's activations,
+    F32 or BF16; `packed` is the fp32 blob in both."""
+    lib = load_library()
+    x = _dev_f32(x, "x")
+    mptr, dropout_mask = _check_shiftnet_input(x, dropout_mask)
+    B = x.shape[0]
+    keep = []
+    P = _shiftnet_struct(named, keep, True)        # (fc1.weight is read in place by the kernel: not part of `packed`)
+    nbytes = lib.hrn_shiftnet_train_workspace_bytes_dt(int(dtype), B)
     if nbytes == 0:
         raise ValueError(f"ShiftNet training supports dtype F32 ({F32}) or BF16 ({BF16}); got {dtype}")
     tws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     theta = torch.empty((B, 2), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        if dtype == F32:
-            _check(lib.hrn_shiftnet_forward_train(_ptr(packed), ctypes.byref(P), _ptr(x), B, float(momentum), mptr, _ptr(theta),
-                                                  _ptr(tws), nbytes, _stream()), "hrn_shiftnet_forward_train")
-        else:
-            _check(lib.hrn_shiftnet_forward_train_dt(_ptr(packed), int(dtype), ctypes.byref(P), _ptr(x), B, float(momentum), mptr,
-                                                     _ptr(theta), _ptr(tws), nbytes, _stream()), "hrn_shiftnet_forward_train_dt")
+        _check(lib.hrn_shiftnet_forward_train_dt(_ptr(packed), int(dtype), ctypes.byref(P), _ptr(x), B, float(momentum), mptr,
+                                                 _ptr(theta), _ptr(tws), nbytes, _stream()), "hrn_shiftnet_forward_train")
     return theta, tws
 
 
 def shiftnet_backward(named, named_grads, x, dropout_mask, d_theta, tws, need_input_grad=True, dtype=F32, select=False):
     """Accumulates the parameter gradients into named_grads (parameter keys only); returns d_x (B,2,128,128) or None.  dtype: the
-    forward's (the workspace `tws` it filled).  select: named_grads holds only the parameters that want a gradient
-    (hrn_shiftnet_backward_sel: the work of the others is skipped)."""
+    forward's (the workspace `tws` it filled).  select: named_grads holds only the parameters that want a gradient (the work of the
+    others is skipped).  One C call either way: hrn_shiftnet_backward_sel."""
     lib = load_library()
     x = _dev_f32(x, "x")
     d_theta = _dev_f32(d_theta, "d_theta")
@@ -511,18 +491,9 @@ def shiftnet_backward(named, named_grads, x, dropout_mask, d_theta, tws, need_in
     G = _shiftnet_struct(gfull, keep, True, optional=select)
     d_x = torch.empty_like(x) if need_input_grad else None
     with torch.cuda.device(x.device):
-        if select:
-            _check(lib.hrn_shiftnet_backward_sel(ctypes.byref(P), int(dtype), _ptr(x), B, mptr, _ptr(d_theta), ctypes.byref(G),
-                                                 _ptr(d_x) if need_input_grad else None, _ptr(tws), tws.numel(), _stream()),
-                   "hrn_shiftnet_backward_sel")
-        elif dtype == F32:
-            _check(lib.hrn_shiftnet_backward(ctypes.byref(P), _ptr(x), B, mptr, _ptr(d_theta), ctypes.byref(G),
+        _check(lib.hrn_shiftnet_backward_sel(ctypes.byref(P), int(dtype), _ptr(x), B, mptr, _ptr(d_theta), ctypes.byref(G),
                                              _ptr(d_x) if need_input_grad else None, _ptr(tws), tws.numel(), _stream()),
-                   "hrn_shiftnet_backward")
-        else:
-            _check(lib.hrn_shiftnet_backward_dt(ctypes.byref(P), int(dtype), _ptr(x), B, mptr, _ptr(d_theta), ctypes.byref(G),
-                                                _ptr(d_x) if need_input_grad else None, _ptr(tws), tws.numel(), _stream()),
-                   "hrn_shiftnet_backward_dt")
+               "hrn_shiftnet_backward")
     return d_x
 
 
@@ -829,15 +800,30 @@ def _(packed, lrs, alphas, params, num_layers, alpha_residual, dtype, scale=3):
     return lrs.new_empty((b, 1, scale * h, scale * w), dtype=torch.float32), lrs.new_empty((nbytes,), dtype=torch.uint8)
 
 
+def _hrnet_backward_body(packed, params, lrs, alphas, d_sr, tws, num_layers, alpha_residual, dtype, scale, need_params=None,
+                         need_lrs=False, need_alphas=False):
+    """The three HRNet backward ops: (parameter gradients in `hrnet_param_names` order, d_lrs, d_alphas), an empty tensor for whatever
+    was not asked for.  need_params None: every parameter; else need_params[i] says whether params[i] wants a gradient."""
+    names = hrnet_param_names(num_layers)
+    if need_params is not None and len(need_params) != len(names):
+        raise ValueError(f"need_params has {len(need_params)} entries for {len(names)} parameters")
+    named = dict(zip(names, params))
+    grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
+             for i, (k, p) in enumerate(named.items()) if need_params is None or need_params[i]}
+    d_lrs = torch.empty(lrs.shape, dtype=torch.float32, device=lrs.device) if need_lrs else None
+    d_alphas = torch.empty(alphas.shape, dtype=torch.float32, device=alphas.device) if need_alphas else None
+    hrnet_backward(packed, named, grads, num_layers, alpha_residual, lrs, alphas, d_sr.contiguous(), tws, dtype, scale, d_lrs=d_lrs,
+                   d_alphas=d_alphas, select=need_params is not None)
+    return ([grads[k] if k in grads else named[k].new_empty((0,), dtype=torch.float32) for k in names],
+            d_lrs if need_lrs else lrs.new_empty((0,), dtype=torch.float32),
+            d_alphas if need_alphas else alphas.new_empty((0,), dtype=torch.float32))
+
+
 @torch.library.custom_op("hrnet_hip::hrnet_backward", mutates_args=("tws",), device_types="cuda")     # (tws also holds the backward's scratch buffers)
 def _op_hrnet_backward(packed: torch.Tensor, params: Sequence[torch.Tensor], lrs: torch.Tensor, alphas: torch.Tensor, d_sr: torch.Tensor,
                        tws: torch.Tensor, num_layers: int, alpha_residual: bool, dtype: int, scale: int = 3) -> List[torch.Tensor]:
     """d_sr -> the gradient of every parameter (train.py:190 through HRNet), in `hrnet_param_names` order."""
-    names = hrnet_param_names(num_layers)
-    named = dict(zip(names, params))
-    grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for k, p in named.items()}
-    hrnet_backward(packed, named, grads, num_layers, alpha_residual, lrs, alphas, d_sr.contiguous(), tws, dtype, scale)
-    return [grads[k] for k in names]
+    return _hrnet_backward_body(packed, params, lrs, alphas, d_sr, tws, num_layers, alpha_residual, dtype, scale)[0]
 
 
 @_op_hrnet_backward.register_fake
@@ -851,15 +837,7 @@ def _op_hrnet_backward_in(packed: torch.Tensor, params: Sequence[torch.Tensor], 
                           need_alphas: bool) -> Tuple[List[torch.Tensor], torch.Tensor, torch.Tensor]:
     """hrnet_backward that also returns the input gradients (HRNet.py:198-204, :113-132): (parameter gradients in `hrnet_param_names`
     order, d_lrs (B,V,H,W), d_alphas (B,V)); an input gradient that was not asked for comes back empty."""
-    names = hrnet_param_names(num_layers)
-    named = dict(zip(names, params))
-    grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for k, p in named.items()}
-    d_lrs = torch.empty(lrs.shape, dtype=torch.float32, device=lrs.device) if need_lrs else None
-    d_alphas = torch.empty(alphas.shape, dtype=torch.float32, device=alphas.device) if need_alphas else None
-    hrnet_backward(packed, named, grads, num_layers, alpha_residual, lrs, alphas, d_sr.contiguous(), tws, dtype, scale, d_lrs=d_lrs,
-                   d_alphas=d_alphas)
-    return ([grads[k] for k in names], d_lrs if need_lrs else lrs.new_empty((0,), dtype=torch.float32),
-            d_alphas if need_alphas else alphas.new_empty((0,), dtype=torch.float32))
+    return _hrnet_backward_body(packed, params, lrs, alphas, d_sr, tws, num_layers, alpha_residual, dtype, scale, None, need_lrs, need_alphas)
 
 
 @_op_hrnet_backward_in.register_fake
@@ -876,19 +854,8 @@ def _op_hrnet_backward_sel(packed: torch.Tensor, params: Sequence[torch.Tensor],
     """hrnet_backward_in for a partly frozen model (hrn_hrnet_backward_sel): need_params[i] says whether params[i] wants a gradient.
     Returns (parameter gradients in `hrnet_param_names` order, an empty tensor for every frozen one; d_lrs; d_alphas); only the work the
     requested outputs depend on is launched, and each of them is bit-identical to hrnet_backward_in's."""
-    names = hrnet_param_names(num_layers)
-    if len(need_params) != len(names):
-        raise ValueError(f"need_params has {len(need_params)} entries for {len(names)} parameters")
-    named = dict(zip(names, params))
-    grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
-             for k, p, need in zip(names, params, need_params) if need}
-    d_lrs = torch.empty(lrs.shape, dtype=torch.float32, device=lrs.device) if need_lrs else None
-    d_alphas = torch.empty(alphas.shape, dtype=torch.float32, device=alphas.device) if need_alphas else None
-    hrnet_backward(packed, named, grads, num_layers, alpha_residual, lrs, alphas, d_sr.contiguous(), tws, dtype, scale, d_lrs=d_lrs,
-                   d_alphas=d_alphas, select=True)
-    return ([grads[k] if k in grads else named[k].new_empty((0,), dtype=torch.float32) for k in names],
-            d_lrs if need_lrs else lrs.new_empty((0,), dtype=torch.float32),
-            d_alphas if need_alphas else alphas.new_empty((0,), dtype=torch.float32))
+    return _hrnet_backward_body(packed, params, lrs, alphas, d_sr, tws, num_layers, alpha_residual, dtype, scale, list(need_params), need_lrs,
+                                need_alphas)
 
 
 @_op_hrnet_backward_sel.register_fake
@@ -901,7 +868,7 @@ def _(packed, params, lrs, alphas, d_sr, tws, num_layers, alpha_residual, dtype,
 def _hrnet_train_setup(ctx, inputs, output):
     packed, lrs, alphas, params, num_layers, alpha_residual, dtype, scale = inputs
     ctx.num_layers, ctx.alpha_residual, ctx.n, ctx.dtype, ctx.scale = num_layers, alpha_residual, len(params), dtype, scale
-    # which parameters autograd will ask for (requires_grad_(False): frozen); all of them take the full backward of every release
+    # which parameters autograd will ask for (requires_grad_(False): frozen)
     ctx.need_params = [bool(p.requires_grad) for p in params]
     ctx.set_materialize_grads(False)          # (or autograd hands the backward a zero-filled "gradient" of the 20 GB workspace output)
     ctx.save_for_backward(packed, lrs, alphas, output[1], *params)
@@ -919,23 +886,14 @@ def _hrnet_train_backward(ctx, d_sr, _d_tws):
     # fusion level (HRNet.py:124-128), so without one (or with a single view) their gradient stays None, as in the reference
     need_lrs = ctx.needs_input_grad[1]
     need_alphas = ctx.needs_input_grad[2] and bool(ctx.alpha_residual) and lrs.shape[1] > 1
-    if not all(ctx.need_params):
-        # a partly frozen model: frozen parameters get None (their .grad stays None) and their work is not launched
-        if not (any(ctx.need_params) or need_lrs or need_alphas):
-            return (None, None, None, [None] * len(params)) + tail
-        grads, d_lrs, d_alphas = torch.ops.hrnet_hip.hrnet_backward_sel(packed, params, lrs, alphas, d_sr, tws.data, ctx.num_layers,
-                                                                        ctx.alpha_residual, ctx.dtype, ctx.scale, ctx.need_params,
-                                                                        need_lrs, need_alphas)
-        return (None, d_lrs.to(lrs.dtype) if need_lrs else None, d_alphas.to(alphas.dtype) if need_alphas else None,
-                [g.to(p.dtype) if need else None for g, p, need in zip(grads, params, ctx.need_params)]) + tail
-    if not (need_lrs or need_alphas):
-        grads = torch.ops.hrnet_hip.hrnet_backward(packed, params, lrs, alphas, d_sr, tws.data, ctx.num_layers, ctx.alpha_residual,
-                                                   ctx.dtype, ctx.scale)
-        return (None, None, None, [g.to(p.dtype) for g, p in zip(grads, params)]) + tail
-    grads, d_lrs, d_alphas = torch.ops.hrnet_hip.hrnet_backward_in(packed, params, lrs, alphas, d_sr, tws.data, ctx.num_layers,
-                                                                   ctx.alpha_residual, ctx.dtype, ctx.scale, need_lrs, need_alphas)
+    if not (any(ctx.need_params) or need_lrs or need_alphas):
+        return (None, None, None, [None] * len(params)) + tail
+    # frozen parameters get None (their .grad stays None) and their work is not launched
+    grads, d_lrs, d_alphas = torch.ops.hrnet_hip.hrnet_backward_sel(packed, params, lrs, alphas, d_sr, tws.data, ctx.num_layers,
+                                                                    ctx.alpha_residual, ctx.dtype, ctx.scale, ctx.need_params,
+                                                                    need_lrs, need_alphas)
     return (None, d_lrs.to(lrs.dtype) if need_lrs else None, d_alphas.to(alphas.dtype) if need_alphas else None,
-            [g.to(p.dtype) for g, p in zip(grads, params)]) + tail
+            [g.to(p.dtype) if need else None for g, p, need in zip(grads, params, ctx.need_params)]) + tail
 
 
 _op_hrnet_forward_train.register_autograd(_hrnet_train_backward, setup_context=_hrnet_train_setup)
@@ -967,18 +925,29 @@ def _(packed, x, params, bn_running, momentum, dropout_mask, dtype=0):
     return x.new_empty((x.shape[0], 2), dtype=torch.float32), x.new_empty((nbytes,), dtype=torch.uint8), [b.new_empty(b.shape) for b in bn_running]
 
 
+def _shiftnet_backward_body(params, x, dropout_mask, d_theta, tws, need_input_grad, dtype, need_params=None):
+    """The two ShiftNet backward ops: (parameter gradients in SHIFTNET_PARAM_NAMES order, an empty tensor for every frozen one; d_x, empty
+    when not needed).  need_params None: every parameter.  The batch statistics the backward needs are in `tws`; the running statistics
+    take no part (the BatchNorm weights stand in for them in the C struct)."""
+    if need_params is not None and len(need_params) != len(SHIFTNET_PARAM_NAMES):
+        raise ValueError(f"need_params has {len(need_params)} entries for {len(SHIFTNET_PARAM_NAMES)} parameters")
+    named = dict(zip(SHIFTNET_PARAM_NAMES, params))
+    for k in SHIFTNET_BUFFER_NAMES:
+        named[k] = named[k.rsplit(".", 1)[0] + ".weight"]
+    grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
+             for i, (k, p) in enumerate(zip(SHIFTNET_PARAM_NAMES, params)) if need_params is None or need_params[i]}
+    d_x = shiftnet_backward(named, grads, x, dropout_mask, d_theta.contiguous(), tws, need_input_grad=need_input_grad, dtype=dtype,
+                            select=need_params is not None)
+    return ([grads[k] if k in grads else named[k].new_empty((0,), dtype=torch.float32) for k in SHIFTNET_PARAM_NAMES],
+            (d_x if d_x is not None else x.new_empty((0,))))
+
+
 @torch.library.custom_op("hrnet_hip::shiftnet_backward", mutates_args=("tws",), device_types="cuda")  # (tws also holds the backward's scratch buffers)
 def _op_shiftnet_backward(params: Sequence[torch.Tensor], x: torch.Tensor,
                           dropout_mask: Optional[torch.Tensor], d_theta: torch.Tensor, tws: torch.Tensor,
                           need_input_grad: bool, dtype: int = 0) -> Tuple[List[torch.Tensor], torch.Tensor]:
-    """d_theta -> (parameter gradients in SHIFTNET_PARAM_NAMES order, d_x (empty when not needed)).  The batch statistics the backward
-    needs are in `tws`; the running statistics take no part (the BatchNorm weights stand in for them in the C struct)."""
-    named = dict(zip(SHIFTNET_PARAM_NAMES, params))
-    for k in SHIFTNET_BUFFER_NAMES:
-        named[k] = named[k.rsplit(".", 1)[0] + ".weight"]
-    grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for k, p in zip(SHIFTNET_PARAM_NAMES, params)}
-    d_x = shiftnet_backward(named, grads, x, dropout_mask, d_theta.contiguous(), tws, need_input_grad=need_input_grad, dtype=dtype)
-    return [grads[k] for k in SHIFTNET_PARAM_NAMES], (d_x if d_x is not None else x.new_empty((0,)))
+    """d_theta -> (parameter gradients in SHIFTNET_PARAM_NAMES order, d_x (empty when not needed))."""
+    return _shiftnet_backward_body(params, x, dropout_mask, d_theta, tws, need_input_grad, dtype)
 
 
 @_op_shiftnet_backward.register_fake
@@ -992,17 +961,7 @@ def _op_shiftnet_backward_sel(params: Sequence[torch.Tensor], x: torch.Tensor, d
                               need_params: Sequence[bool]) -> Tuple[List[torch.Tensor], torch.Tensor]:
     """shiftnet_backward for a partly frozen ShiftNet (hrn_shiftnet_backward_sel): need_params[i] says whether params[i] wants a gradient.
     Returns (parameter gradients in SHIFTNET_PARAM_NAMES order, an empty tensor for every frozen one; d_x, empty when not needed)."""
-    if len(need_params) != len(SHIFTNET_PARAM_NAMES):
-        raise ValueError(f"need_params has {len(need_params)} entries for {len(SHIFTNET_PARAM_NAMES)} parameters")
-    named = dict(zip(SHIFTNET_PARAM_NAMES, params))
-    for k in SHIFTNET_BUFFER_NAMES:
-        named[k] = named[k.rsplit(".", 1)[0] + ".weight"]
-    grads = {k: torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
-             for k, p, need in zip(SHIFTNET_PARAM_NAMES, params, need_params) if need}
-    d_x = shiftnet_backward(named, grads, x, dropout_mask, d_theta.contiguous(), tws, need_input_grad=need_input_grad, dtype=dtype,
-                            select=True)
-    return ([grads[k] if k in grads else named[k].new_empty((0,), dtype=torch.float32) for k in SHIFTNET_PARAM_NAMES],
-            (d_x if d_x is not None else x.new_empty((0,))))
+    return _shiftnet_backward_body(params, x, dropout_mask, d_theta, tws, need_input_grad, dtype, list(need_params))
 
 
 @_op_shiftnet_backward_sel.register_fake
@@ -1029,18 +988,13 @@ def _shiftnet_train_backward(ctx, d_theta, _d_tws, _d_running):
     params = rest[:ctx.np]
     mask = rest[ctx.np] if ctx.has_mask else None
     need_x = ctx.needs_input_grad[1]
-    if not all(ctx.need_params):
-        # a partly (or wholly) frozen ShiftNet, e.g. a fixed pretrained registration model that only passes d_x back into HRNet
-        if not (any(ctx.need_params) or need_x):
-            return (None, None, [None] * ctx.np, [None] * len(SHIFTNET_BUFFER_NAMES)) + tail
-        grads, d_x = torch.ops.hrnet_hip.shiftnet_backward_sel(params, x, mask, d_theta, tws.data, need_x, ctx.dtype, ctx.need_params)
-        return (None, (d_x if need_x else None), [g if need else None for g, need in zip(grads, ctx.need_params)],
-                [None] * len(SHIFTNET_BUFFER_NAMES)) + tail
-    if ctx.dtype == F32:
-        grads, d_x = torch.ops.hrnet_hip.shiftnet_backward(params, x, mask, d_theta, tws.data, need_x)      # (tws.data: see _hrnet_train_backward)
-    else:
-        grads, d_x = torch.ops.hrnet_hip.shiftnet_backward(params, x, mask, d_theta, tws.data, need_x, ctx.dtype)
-    return (None, (d_x if need_x else None), grads, [None] * len(SHIFTNET_BUFFER_NAMES)) + tail
+    # a wholly frozen ShiftNet (e.g. a fixed pretrained registration model) only passes d_x back into HRNet, or nothing at all
+    if not (any(ctx.need_params) or need_x):
+        return (None, None, [None] * ctx.np, [None] * len(SHIFTNET_BUFFER_NAMES)) + tail
+    grads, d_x = torch.ops.hrnet_hip.shiftnet_backward_sel(params, x, mask, d_theta, tws.data, need_x, ctx.dtype,      # (tws.data: see
+                                                           ctx.need_params)                                           # _hrnet_train_backward)
+    return (None, (d_x if need_x else None), [g if need else None for g, need in zip(grads, ctx.need_params)],
+            [None] * len(SHIFTNET_BUFFER_NAMES)) + tail
 
 
 _op_shiftnet_forward_train.register_autograd(_shiftnet_train_backward, setup_context=_shiftnet_train_setup)

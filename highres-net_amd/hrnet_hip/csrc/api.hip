@@ -1,5 +1,6 @@
 // extern "C" entry points of libhrnet_hip.so (declared in include/hrnet_hip.h): argument checks, packed-parameter
-// and workspace layouts, and the kernel sequences of HRNet.forward / ShiftNet.forward.
+// and workspace layouts, and the kernel sequences of HRNet.forward / ShiftNet.forward.  (The entry points that are another one with an
+// argument fixed are in abi_fixed.hip.)
 #include "../../../include/hrnet_hip.h"
 #include "kernels.h"
 #include "hrnet_layout.h"
@@ -78,16 +79,16 @@ int encoder_impl(const void* pk, int dt, int nl, const float* lrs, int B, int V,
         ConvParams p = conv_base(B * V, H, W);
         p.in = bufA; p.out = bufB; p.in_lo = p.out_lo = lo;
         p.wpk = at(pk, L.enc_w[2 * l]); p.bias = (const float*)at(pk, L.enc_b[2 * l]); p.slope = (const float*)at(pk, L.enc_a[2 * l]);
-        if ((rc = hrn_launch_conv3x3(dt, 64, 64, p, s))) return rc;
+        if ((rc = hrn_launch_conv3x3(dt, 64, 64, p, s, false))) return rc;
         ConvParams q = conv_base(B * V, H, W);
         q.in = bufB; q.out = bufA; q.res = bufA; q.res_mode = 1; q.in_lo = q.out_lo = q.res_lo = lo;
         q.wpk = at(pk, L.enc_w[2 * l + 1]); q.bias = (const float*)at(pk, L.enc_b[2 * l + 1]); q.slope = (const float*)at(pk, L.enc_a[2 * l + 1]);
-        if ((rc = hrn_launch_conv3x3(dt, 64, 64, q, s))) return rc;
+        if ((rc = hrn_launch_conv3x3(dt, 64, 64, q, s, false))) return rc;
     }
     ConvParams f = conv_base(B * V, H, W);
     f.in = bufA; f.out = emb; f.in_lo = f.out_lo = lo;
     f.wpk = at(pk, L.encf_w); f.bias = (const float*)at(pk, L.encf_b); f.slope = nullptr;
-    return hrn_launch_conv3x3(dt, 64, 64, f, s);
+    return hrn_launch_conv3x3(dt, 64, 64, f, s, false);
 }
 
 int fuse_impl(const void* pk, int dt, int nl, int alpha_residual, void* emb, const float* alphas, int B, int V, int H, int W,
@@ -110,14 +111,14 @@ int fuse_impl(const void* pk, int dt, int nl, int alpha_residual, void* emb, con
         a.in_pair = 1; a.stack = emb; a.pair_h = half; a.pair_last = n - parity - 1; a.pair_vs = V;
         a.out = t1; a.stack_lo = a.out_lo = lo;
         a.wpk = at(pk, L.fres_w[0]); a.bias = (const float*)at(pk, L.fres_b[0]); a.slope = (const float*)at(pk, L.fres_a[0]);
-        if ((rc = hrn_launch_conv3x3(dt, 128, 128, a, s))) return rc;
+        if ((rc = hrn_launch_conv3x3(dt, 128, 128, a, s, false))) return rc;
         // t2 = z + PReLU(conv(t1))                                          (HRNet.py:20-21, :33)
         ConvParams b = conv_base(B * half, H, W);
         b.in = t1; b.out = t2; b.in_lo = b.out_lo = b.stack_lo = lo;
         b.res_mode = 2;      // residual = the same pair gather, straight from the stack
         b.stack = emb; b.pair_h = half; b.pair_last = n - parity - 1; b.pair_vs = V;
         b.wpk = at(pk, L.fres_w[1]); b.bias = (const float*)at(pk, L.fres_b[1]); b.slope = (const float*)at(pk, L.fres_a[1]);
-        if ((rc = hrn_launch_conv3x3(dt, 128, 128, b, s))) return rc;
+        if ((rc = hrn_launch_conv3x3(dt, 128, 128, b, s, false))) return rc;
         // f = PReLU(conv(t2)); s_i <- s_i + alpha_partner * f  (or s_i <- f)  (HRNet.py:95-97, :123-128)
         ConvParams c = conv_base(B * half, H, W);
         c.in = t2; c.in_lo = c.res_lo = lo;
@@ -126,7 +127,7 @@ int fuse_impl(const void* pk, int dt, int nl, int alpha_residual, void* emb, con
         c.pair_last = n - parity - 1;
         if (alpha_residual) { c.res_mode = 3; c.res = emb; c.res_vs = V; c.alphas = alphas; c.alpha_vs = V; }
         c.wpk = at(pk, L.fout_w); c.bias = (const float*)at(pk, L.fout_b); c.slope = (const float*)at(pk, L.fout_a);
-        if ((rc = hrn_launch_conv3x3(dt, 128, 64, c, s))) return rc;
+        if ((rc = hrn_launch_conv3x3(dt, 128, 64, c, s, false))) return rc;
         n = half;
     }
     return 0;
@@ -166,15 +167,9 @@ extern "C" {
 int hrn_version(void) { return HRN_ABI_VERSION; }
 const char* hrn_last_error(void) { return g_err; }
 
-size_t hrn_hrnet_packed_bytes(int dtype, int num_layers) { return hrn_hrnet_packed_bytes_s(dtype, num_layers, 3); }
-
 size_t hrn_hrnet_packed_bytes_s(int dtype, int num_layers, int scale) {
     if (!dtype_ok(dtype) || num_layers < 0 || num_layers > HRN_MAX_RES_LAYERS || !hrn_scale_ok(scale)) return 0;
     return hrnet_layout(dtype, num_layers, scale).total;
-}
-
-int hrn_hrnet_pack(const hrn_hrnet_params* P, int dt, void* packed, size_t packed_bytes, void* stream) {
-    return hrn_hrnet_pack_s(P, dt, 3, packed, packed_bytes, stream);
 }
 
 int hrn_hrnet_pack_s(const hrn_hrnet_params* P, int dt, int scale, void* packed, size_t packed_bytes, void* stream) {
@@ -238,20 +233,11 @@ int hrn_fuse_forward(const void* packed, int dt, int nl, int alpha_residual, voi
     return fuse_impl(packed, dt, nl, alpha_residual, emb, alphas, B, V, H, W, fused, ws, wl, (hipStream_t)stream);
 }
 
-int hrn_decoder_forward(const void* packed, int dt, int nl, const void* fused, int N, int H, int W, float* sr, void* stream) {
-    return hrn_decoder_forward_s(packed, dt, nl, 3, fused, N, H, W, sr, stream);
-}
-
 int hrn_decoder_forward_s(const void* packed, int dt, int nl, int scale, const void* fused, int N, int H, int W, float* sr, void* stream) {
     int rc;
     if ((rc = check_scale(scale)) || (rc = check_common(dt, nl, N, 1, H, W))) return rc;
     HRN_CHECK(packed && fused && sr, -2, "hrn_decoder_forward: null argument");
     return decoder_impl(packed, dt, nl, scale, fused, N, H, W, sr, (hipStream_t)stream);
-}
-
-int hrn_hrnet_forward(const void* packed, int dt, int nl, int alpha_residual, const float* lrs, const float* alphas,
-                      int B, int V, int H, int W, float* sr, void* ws, size_t ws_bytes, void* stream) {
-    return hrn_hrnet_forward_s(packed, dt, nl, 3, alpha_residual, lrs, alphas, B, V, H, W, sr, ws, ws_bytes, stream);
 }
 
 int hrn_hrnet_forward_s(const void* packed, int dt, int nl, int scale, int alpha_residual, const float* lrs, const float* alphas,
@@ -325,9 +311,9 @@ int hrn_shiftnet_forward(const void* packed, const hrn_shiftnet_params* P, const
             ConvParams p = conv_base(B, hsz, hsz);
             p.in = by; p.out = bx;
             p.wpk = at(packed, L.conv_w[i]); p.scale = scale; p.bias = shift; p.relu = 1;
-            if ((rc = hrn_launch_conv3x3(HRN_F32, SN_CI[i], C, p, s))) return rc;
+            if ((rc = hrn_launch_conv3x3(HRN_F32, SN_CI[i], C, p, s, false))) return rc;
             if (SN_POOL[i]) {
-                if ((rc = hrn_launch_bn_act_pool(bx, nullptr, nullptr, by, B, hsz, hsz, C, 1, s))) return rc;
+                if ((rc = hrn_launch_bn_act_pool(HRN_F32, bx, nullptr, nullptr, by, B, hsz, hsz, C, 1, s))) return rc;
                 hsz /= 2;
             } else {
                 float* t = bx; bx = by; by = t;             // the activation is where the conv wrote it
@@ -336,25 +322,25 @@ int hrn_shiftnet_forward(const void* packed, const hrn_shiftnet_params* P, const
         }
         if (i == 0) {
             if ((rc = hrn_launch_stem(HRN_F32, x, 2 * plane, x + plane, 1, 2 * plane, means, (const float*)at(packed, L.conv_w[0]),
-                                      (const float*)at(packed, L.conv_b[0]), nullptr, bx, B, hsz, hsz, s))) return rc;
+                                      (const float*)at(packed, L.conv_b[0]), nullptr, bx, B, hsz, hsz, s, 0))) return rc;
         } else {
             ConvParams p = conv_base(B, hsz, hsz);
             p.in = by; p.out = bx;
             p.wpk = at(packed, L.conv_w[i]); p.bias = (const float*)at(packed, L.conv_b[i]);
-            if ((rc = hrn_launch_conv3x3(HRN_F32, SN_CI[i], SN_CO[i], p, s))) return rc;
+            if ((rc = hrn_launch_conv3x3(HRN_F32, SN_CI[i], SN_CO[i], p, s, false))) return rc;
         }
         if (train_bn) {
-            if ((rc = hrn_launch_bn_stats(bx, (size_t)B * hsz * hsz, C, P->bn_g[i], P->bn_b[i], 1e-5f, scale, shift,
+            if ((rc = hrn_launch_bn_stats(HRN_F32, bx, (size_t)B * hsz * hsz, C, P->bn_g[i], P->bn_b[i], 1e-5f, scale, shift,
                                           P->bn_rm[i], P->bn_rv[i], momentum, partial, SN_PARTIAL_BLOCKS, s))) return rc;
         } else {
             if ((rc = hrn_launch_bn_fold(P->bn_g[i], P->bn_b[i], P->bn_rm[i], P->bn_rv[i], 1e-5f, nullptr, scale, shift, C, s))) return rc;
         }
-        if ((rc = hrn_launch_bn_act_pool(bx, scale, shift, by, B, hsz, hsz, C, SN_POOL[i], s))) return rc;
+        if ((rc = hrn_launch_bn_act_pool(HRN_F32, bx, scale, shift, by, B, hsz, hsz, C, SN_POOL[i], s))) return rc;
         if (SN_POOL[i]) hsz /= 2;
     }
     // by: [B][16][16][128] NHWC -> xr [B][c*256 + hw], the reference's flatten order (dropout folded in); fc1.weight is read in place
     float* xr = (float*)at(ws, wl.xr);
-    if ((rc = hrn_launch_fc_to_ref(by, dropout_mask, xr, B, s))) return rc;
+    if ((rc = hrn_launch_fc_to_ref(HRN_F32, by, dropout_mask, xr, B, s))) return rc;
     if ((rc = hrn_launch_fc1(xr, P->fc1_w, (const float*)at(packed, L.fc1_b), fc, B, (float*)at(ws, wl.fc_partial), s))) return rc;
     return hrn_launch_fc2(fc, (const float*)at(packed, L.fc2_w), theta, B, s);
 }

@@ -497,13 +497,13 @@ size_t hrn_bwd_scratch_bytes(int num_cus) {
     return (size_t)2 * num_cus * 9 * 4096 * 4 + (size_t)RED_BLOCKS * (128 + 1) * 8 + 4096;
 }
 
-int hrn_launch_prelu_bwd_bias(const float* dy, const float* y, const float* xpre, const float* slope, float* g, size_t rows, int C,
-                              float* dslope, float* db, void* scratch, hipStream_t s, int dt) {
+int hrn_launch_prelu_bwd_bias(int dt, const void* dy, const void* y, const void* xpre, const float* slope, void* g, size_t rows, int C,
+                              float* dslope, float* db, void* scratch, hipStream_t s) {
     HRN_CHECK(C == 64 || C == 128, -2, "prelu_bwd_bias: C must be 64 or 128 (got %d)", C);
     double* colpart = (double*)scratch;
     const int blocks = RED_BLOCKS;
     double* slopepart = colpart + (size_t)blocks * 128;
-#define HRN_PB(C_, ST_) hipLaunchKernelGGL((prelu_bwd_bias_kernel<C_, ST_>), dim3(blocks), dim3(256), 0, s, (const void*)dy, (const void*)y, (const void*)xpre, slope, (void*)g, rows, colpart, slopepart)
+#define HRN_PB(C_, ST_) hipLaunchKernelGGL((prelu_bwd_bias_kernel<C_, ST_>), dim3(blocks), dim3(256), 0, s, dy, y, xpre, slope, g, rows, colpart, slopepart)
     if (C == 64) { if (dt == HRN_BF16X3) HRN_PB(64, HRN_BF16X3); else if (dt == HRN_BF16) HRN_PB(64, HRN_BF16); else HRN_PB(64, HRN_F32); }
     else { if (dt == HRN_BF16X3) HRN_PB(128, HRN_BF16X3); else if (dt == HRN_BF16) HRN_PB(128, HRN_BF16); else HRN_PB(128, HRN_F32); }
 #undef HRN_PB
@@ -521,11 +521,11 @@ int hrn_launch_prelu_bwd_bias(const float* dy, const float* y, const float* xpre
     return 0;
 }
 
-int hrn_launch_colsum(const float* g, size_t rows, int C, float* db, void* scratch, hipStream_t s, int dt) {
+int hrn_launch_colsum(int dt, const void* g, size_t rows, int C, float* db, void* scratch, hipStream_t s) {
     HRN_CHECK(C == 64 || C == 128, -2, "colsum: C must be 64 or 128 (got %d)", C);
     double* partial = (double*)scratch;
     const int blocks = RED_BLOCKS;
-#define HRN_CS(C_, ST_) hipLaunchKernelGGL((colsum_kernel<C_, ST_>), dim3(blocks), dim3(256), 0, s, (const void*)g, rows, partial)
+#define HRN_CS(C_, ST_) hipLaunchKernelGGL((colsum_kernel<C_, ST_>), dim3(blocks), dim3(256), 0, s, g, rows, partial)
     if (C == 64) { if (dt == HRN_BF16X3) HRN_CS(64, HRN_BF16X3); else if (dt == HRN_BF16) HRN_CS(64, HRN_BF16); else HRN_CS(64, HRN_F32); }
     else { if (dt == HRN_BF16X3) HRN_CS(128, HRN_BF16X3); else if (dt == HRN_BF16) HRN_CS(128, HRN_BF16); else HRN_CS(128, HRN_F32); }
 #undef HRN_CS
@@ -548,8 +548,23 @@ int hrn_launch_wgrad_finish(const float* partial, int nblk, float* dw, int cin, 
     return 0;
 }
 
-int hrn_launch_conv_wgrad(const float* x, const float* stack, int in_pair, int pair_h, int pair_last, int pair_vs, const float* g,
+int hrn_launch_conv_wgrad(int dt, const void* x, const void* stack, int in_pair, int pair_h, int pair_last, int pair_vs, const void* g,
                           int M, int H, int W, int cin, int cout, float* dw, void* scratch, int num_cus, hipStream_t s) {
+    if (dt == HRN_F32)
+        return hrn_launch_conv_wgrad_f32((const float*)x, (const float*)stack, in_pair, pair_h, pair_last, pair_vs, (const float*)g, M, H, W, cin,
+                                         cout, dw, scratch, num_cus, s);
+    if (dt == HRN_BF16) return hrn_launch_conv_wgrad_bf16(x, stack, in_pair, pair_h, pair_last, pair_vs, g, M, H, W, cin, cout, dw, scratch, num_cus, s);
+    HRN_CHECK(dt == HRN_BF16X3, -2, "conv_wgrad: dtype %d", dt);
+    HRN_CHECK(!in_pair || pair_h > 0, -2, "conv_wgrad: pair descriptor missing");
+    // the lo plane directly behind the hi plane: of x [M][H][W][cin], or of the level's whole stack, M / pair_h samples x pair_vs views
+    const size_t hw = (size_t)H * W;
+    const size_t x_lo = in_pair ? (size_t)(M / pair_h) * pair_vs * hw * 64 * 2 : (size_t)M * hw * cin * 2;
+    return hrn_launch_conv_wgrad_x3(x, stack, x_lo, in_pair, pair_h, pair_last, pair_vs, g, (size_t)M * hw * cout * 2, M, H, W, cin, cout, dw,
+                                    scratch, num_cus, s);
+}
+
+int hrn_launch_conv_wgrad_f32(const float* x, const float* stack, int in_pair, int pair_h, int pair_last, int pair_vs, const float* g,
+                              int M, int H, int W, int cin, int cout, float* dw, void* scratch, int num_cus, hipStream_t s) {
     HRN_CHECK((cin == 64 || cin == 128) && (cout == 64 || cout == 128), -2, "conv_wgrad: unsupported %d -> %d", cin, cout);
     HRN_CHECK(!in_pair || cin == 128, -2, "conv_wgrad: the pair gather has 128 input channels");
     { const int rc_lds = hrn_allow_lds((const void*)conv_wgrad_kernel, WG_LDS); if (rc_lds) return rc_lds; }
@@ -571,59 +586,59 @@ int hrn_launch_conv_wgrad(const float* x, const float* stack, int in_pair, int p
     return 0;
 }
 
-int hrn_launch_stem_wgrad(const float* in0, size_t stride0, const float* in1, int rep1, size_t stride1, const float* g, int M, int H,
-                          int W, float* dw, void* scratch, int num_cus, hipStream_t s, int dt) {
-    return hrn_launch_stem_wgrad_sub(in0, stride0, in1, rep1, stride1, nullptr, g, M, H, W, dw, scratch, num_cus, s, dt);
+int hrn_launch_stem_wgrad(int dt, const float* in0, size_t stride0, const float* in1, int rep1, size_t stride1, const void* g, int M, int H,
+                          int W, float* dw, void* scratch, int num_cus, hipStream_t s) {
+    return hrn_launch_stem_wgrad_sub(dt, in0, stride0, in1, rep1, stride1, nullptr, g, M, H, W, dw, scratch, num_cus, s);
 }
 
-int hrn_launch_stem_wgrad_sub(const float* in0, size_t stride0, const float* in1, int rep1, size_t stride1, const float* sub,
-                              const float* g, int M, int H, int W, float* dw, void* scratch, int num_cus, hipStream_t s, int dt) {
+int hrn_launch_stem_wgrad_sub(int dt, const float* in0, size_t stride0, const float* in1, int rep1, size_t stride1, const float* sub,
+                              const void* g, int M, int H, int W, float* dw, void* scratch, int num_cus, hipStream_t s) {
     const long tiles = (long)((W + WG_TW - 1) / WG_TW) * ((H + WG_TH - 1) / WG_TH) * M;
     int grid = 4 * num_cus;                 // four workgroups per CU: the kernel waits on memory, not on arithmetic
     if (tiles < grid) grid = (int)tiles;
-    HRN_LAUNCH_ST(dt, stem_wgrad_kernel, dim3(grid), dim3(256), 0, s, in0, stride0, in1, rep1, stride1, sub, (const void*)g, M, H, W, (float*)scratch);
+    HRN_LAUNCH_ST(dt, stem_wgrad_kernel, dim3(grid), dim3(256), 0, s, in0, stride0, in1, rep1, stride1, sub, g, M, H, W, (float*)scratch);
     hipLaunchKernelGGL(stem_wgrad_finish_kernel, dim3(64 * 18 / 16), dim3(1024), 0, s, (const float*)scratch, grid * 4, dw);
     hrn_count_launch(HRN_LC_STEM_WGRAD);
     HRN_LAUNCH_CHECK();
     return 0;
 }
 
-int hrn_launch_add(const float* a, const float* b, float* o, size_t n, hipStream_t s, int dt) {
+int hrn_launch_add(int dt, const void* a, const void* b, void* o, size_t n, hipStream_t s) {
     HRN_CHECK(n % 4 == 0, -2, "add: element count %zu not a multiple of 4", n);
-    HRN_LAUNCH_ST(dt, add_kernel, dim3(red_grid(n / 4)), dim3(256), 0, s, (const void*)a, (const void*)b, (void*)o, n / 4);
+    HRN_LAUNCH_ST(dt, add_kernel, dim3(red_grid(n / 4)), dim3(256), 0, s, a, b, o, n / 4);
     HRN_LAUNCH_CHECK();
     return 0;
 }
 
-int hrn_launch_fuse_update(const float* stack, int n_in, const float* f, const float* alphas, int alpha_vs, int pair_last, int half,
-                           int alpha_residual, float* out, size_t hw, int B, hipStream_t s, int dt) {
+int hrn_launch_fuse_update(int dt, const void* stack, int n_in, const void* f, const float* alphas, int alpha_vs, int pair_last, int half,
+                           int alpha_residual, void* out, size_t hw, int B, hipStream_t s) {
     const size_t img4 = hw * 16;
-    HRN_LAUNCH_ST(dt, fuse_update_kernel, dim3(red_grid((size_t)B * half * img4)), dim3(256), 0, s, (const void*)stack, n_in, (const void*)f, alphas, alpha_vs,
-                  pair_last, half, alpha_residual, (void*)out, img4, B);
+    HRN_LAUNCH_ST(dt, fuse_update_kernel, dim3(red_grid((size_t)B * half * img4)), dim3(256), 0, s, stack, n_in, f, alphas, alpha_vs, pair_last, half,
+                  alpha_residual, out, img4, B);
     HRN_LAUNCH_CHECK();
     return 0;
 }
 
-int hrn_launch_fuse_df(const float* dsn, const float* alphas, int alpha_vs, int pair_last, int half, int alpha_residual, float* df,
-                       size_t hw, int B, hipStream_t s, int dt) {
+int hrn_launch_fuse_df(int dt, const void* dsn, const float* alphas, int alpha_vs, int pair_last, int half, int alpha_residual, void* df,
+                       size_t hw, int B, hipStream_t s) {
     const size_t img4 = hw * 16;
-    HRN_LAUNCH_ST(dt, fuse_df_kernel, dim3(red_grid((size_t)B * half * img4)), dim3(256), 0, s, (const void*)dsn, alphas, alpha_vs, pair_last, half,
-                  alpha_residual, (void*)df, img4, B);
+    HRN_LAUNCH_ST(dt, fuse_df_kernel, dim3(red_grid((size_t)B * half * img4)), dim3(256), 0, s, dsn, alphas, alpha_vs, pair_last, half, alpha_residual, df,
+                  img4, B);
     HRN_LAUNCH_CHECK();
     return 0;
 }
 
-int hrn_launch_fuse_scatter(const float* dsn, const float* dz, int n_in, int half, int pair_last, int alpha_residual, float* ds,
-                            size_t hw, int B, hipStream_t s, int dt) {
-    HRN_LAUNCH_ST(dt, fuse_scatter_kernel, dim3(red_grid((size_t)B * n_in * hw * 16)), dim3(256), 0, s, (const void*)dsn, (const void*)dz, n_in, half, pair_last,
-                  alpha_residual, (void*)ds, hw, B);
+int hrn_launch_fuse_scatter(int dt, const void* dsn, const void* dz, int n_in, int half, int pair_last, int alpha_residual, void* ds,
+                            size_t hw, int B, hipStream_t s) {
+    HRN_LAUNCH_ST(dt, fuse_scatter_kernel, dim3(red_grid((size_t)B * n_in * hw * 16)), dim3(256), 0, s, dsn, dz, n_in, half, pair_last, alpha_residual, ds,
+                  hw, B);
     hrn_count_launch(HRN_LC_FUSE_SCATTER);
     HRN_LAUNCH_CHECK();
     return 0;
 }
 
-int hrn_conv_dgrad(int cin, int cout, const float* w, const float* g, float* dx, const float* res, int M, int H, int W, float* wt,
-                   void* wtp, const float* zero_bias, hipStream_t s, int dt) {
+int hrn_conv_dgrad(int dt, int cin, int cout, const float* w, const void* g, void* dx, const void* res, int M, int H, int W, float* wt,
+                   void* wtp, const float* zero_bias, hipStream_t s) {
     int rc;
     hrn_count_launch(HRN_LC_CONV_DGRAD);
     if ((rc = hrn_launch_dgrad_weights(w, wt, cin, cout, s))) return rc;
@@ -636,5 +651,5 @@ int hrn_conv_dgrad(int cin, int cout, const float* w, const float* g, float* dx,
         const size_t px = (size_t)M * H * W;
         p.in_lo = px * cout * 2; p.out_lo = px * cin * 2; p.res_lo = px * cin * 2;
     }
-    return hrn_launch_conv3x3(dt, cout, cin, p, s);
+    return hrn_launch_conv3x3(dt, cout, cin, p, s, false);
 }

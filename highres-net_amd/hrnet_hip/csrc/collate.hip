@@ -140,10 +140,3 @@ extern "C" int hrn_collate_device_s(const uint16_t* lr_arena, int64_t lr_elems, 
     HRN_LAUNCH_CHECK();
     return 0;
 }
-
-extern "C" int hrn_collate_device(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems,
-                                  const uint8_t* sm_arena, int64_t sm_elems, const int64_t* plan, int B, int min_L, int S,
-                                  float* lrs, float* alphas, float* hrs, float* maps, void* stream) {
-    return hrn_collate_device_s(lr_arena, lr_elems, hr_arena, hr_elems, sm_arena, sm_elems, plan, B, min_L, S, 3, lrs, alphas, hrs, maps,
-                                stream);
-}

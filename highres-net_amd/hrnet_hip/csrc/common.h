@@ -165,6 +165,14 @@ template <int ST> __device__ __forceinline__ float act_ld1(const void* p, size_t
     else return ((const float*)p)[i];
 }
 
+// hipLaunchKernelGGL(KERNEL<ST>, ...) for the storage kind ST of dt: HRN_F32, HRN_BF16 or HRN_BF16X3 (act_ld4 above)
+#define HRN_LAUNCH_ST(dt, KERNEL, ...)                                                                   \
+    do {                                                                                                 \
+        if ((dt) == HRN_BF16X3) hipLaunchKernelGGL(KERNEL<HRN_BF16X3>, __VA_ARGS__);                     \
+        else if ((dt) == HRN_BF16) hipLaunchKernelGGL(KERNEL<HRN_BF16>, __VA_ARGS__);                    \
+        else hipLaunchKernelGGL(KERNEL<HRN_F32>, __VA_ARGS__);                                           \
+    } while (0)
+
 // (s, ss) = sum over k < nblk of partial[(k * C + c) * 2 + {0, 1}] for channel c = threadIdx.x % C, by a block of 1024 threads = C channels
 // x (1024 / C) phases (C = 64 or 128), fixed order; valid in the threads with threadIdx.x < C.  A finish kernel is a chain of dependent
 // loads: one thread per channel took 65 us for 256 slabs, this takes ~5.

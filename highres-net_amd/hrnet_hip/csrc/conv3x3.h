@@ -36,7 +36,7 @@ static inline size_t conv_packed_elems(int cin, int cout) { return (size_t)cin *
 
 // Launch on `stream`.  dt: HRN_F32 / HRN_BF16; (cin, cout) in {64,128}^2.  Returns 0 or a negative error.  general_only: this file's
 // general kernel even where r64 / v6 apply (the route HRN_CONV_R64=0 HRN_CONV_V6=0 selects; kernel_test.hip's route 1)
-int hrn_launch_conv3x3(int dt, int cin, int cout, const ConvParams& p, hipStream_t stream, bool general_only = false);
+int hrn_launch_conv3x3(int dt, int cin, int cout, const ConvParams& p, hipStream_t stream, bool general_only);
 
 // bf16 64 -> 64 with LDS-resident weights (conv3x3_r64.hip); -100 = not applicable, caller picks another kernel.
 int hrn_launch_conv3x3_r64(const ConvParams& p, hipStream_t stream);

@@ -187,26 +187,26 @@ int alpha_parts(int nimg) {
 
 size_t hrn_alpha_grad_scratch_bytes(int nimg) { return (size_t)nimg * alpha_parts(nimg) * sizeof(double); }
 
-int hrn_launch_stem_dgrad_route(const float* dA, const float* w, float* wt, const float* lrs, const float* ref, float* d_lrs, int B, int V,
-                                int H, int W, hipStream_t s, int dt) {
+int hrn_launch_stem_dgrad_route(int dt, const void* dA, const float* w, float* wt, const float* lrs, const float* ref, float* d_lrs, int B,
+                                int V, int H, int W, hipStream_t s) {
     const long tiles = (long)((W + SD_TW - 1) / SD_TW) * ((H + SD_TH - 1) / SD_TH);
     HRN_CHECK(tiles * B < (1L << 31), -2, "stem dgrad: %d samples of %d x %d exceed the grid", B, H, W);
     const double px = (double)B * V * H * W;
     HrnProfScope prof("stem_dgrad_route", 2.0 * 18 * 64 * px, px * (64.0 * 4 + 4) + (double)B * H * W * 4 * ((V < 9 ? V : 9) + 1), s);
     hipLaunchKernelGGL(stem_dgrad_weights_kernel, dim3((64 * 18 + 255) / 256), dim3(256), 0, s, w, wt);
-    HRN_LAUNCH_ST(dt, stem_dgrad_route_kernel, dim3((unsigned)(tiles * B)), dim3(256), 0, s, (const void*)dA, (const float*)wt, lrs, ref, d_lrs, B, V, H, W);
+    HRN_LAUNCH_ST(dt, stem_dgrad_route_kernel, dim3((unsigned)(tiles * B)), dim3(256), 0, s, dA, (const float*)wt, lrs, ref, d_lrs, B, V, H, W);
     HRN_LAUNCH_CHECK();
     return 0;
 }
 
-int hrn_launch_alpha_grad(const float* dsn, const float* f, int half, int pair_last, float* d_alphas, int B, int V, size_t hw, void* scratch,
-                          size_t scratch_bytes, hipStream_t s, int dt) {
+int hrn_launch_alpha_grad(int dt, const void* dsn, const void* f, int half, int pair_last, float* d_alphas, int B, int V, size_t hw,
+                          void* scratch, size_t scratch_bytes, hipStream_t s) {
     const int nimg = B * half, P = alpha_parts(nimg);
     HRN_CHECK(hrn_alpha_grad_scratch_bytes(nimg) <= scratch_bytes, -2, "alpha grad: scratch too small for %d images", nimg);
     HrnProfScope prof("alpha_grad", 2.0 * nimg * hw * 64, 2.0 * nimg * hw * 64 * 4, s);
     double* partial = (double*)scratch;
     const size_t img4 = hw * 16;
-    HRN_LAUNCH_ST(dt, alpha_grad_partial_kernel, dim3(nimg * P), dim3(256), 0, s, (const void*)dsn, (const void*)f, img4, nimg, P, partial);
+    HRN_LAUNCH_ST(dt, alpha_grad_partial_kernel, dim3(nimg * P), dim3(256), 0, s, dsn, f, img4, nimg, P, partial);
     hipLaunchKernelGGL(alpha_grad_finish_kernel, dim3((nimg + 255) / 256), dim3(256), 0, s, (const double*)partial, nimg, P, half, pair_last, V, d_alphas);
     HRN_LAUNCH_CHECK();
     return 0;

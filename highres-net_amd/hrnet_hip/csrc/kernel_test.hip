@@ -19,26 +19,14 @@ size_t hrn_kt_wgrad_scratch_bytes(void) { return hrn_bwd_scratch_bytes(hrn_devic
 // HRN_DTYPE_BF16X3 (a pair of bf16 planes each, the lo plane directly behind the hi plane, as hrn_conv_dgrad lays them out) or F32.
 int hrn_kt_conv_wgrad(int dt, const void* x, const void* stack, int pair_h, int pair_last, int pair_vs, const void* g, int M, int H, int W,
                       int cin, int cout, float* dw, void* scratch, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const int cus = hrn_device_cus();
-    if (dt == HRN_BF16) return hrn_launch_conv_wgrad_bf16(x, stack, x ? 0 : 1, pair_h, pair_last, pair_vs, g, M, H, W, cin, cout, dw, scratch, cus, s);
-    if (dt == HRN_BF16X3) {
-        HRN_CHECK(x || pair_h > 0, -2, "hrn_kt_conv_wgrad: pair descriptor missing");
-        const size_t hw = (size_t)H * W;
-        const size_t x_lo = x ? (size_t)M * hw * cin * 2 : (size_t)(M / pair_h) * pair_vs * hw * 64 * 2;
-        return hrn_launch_conv_wgrad_x3(x, stack, x_lo, x ? 0 : 1, pair_h, pair_last, pair_vs, g, (size_t)M * hw * cout * 2, M, H, W, cin, cout,
-                                        dw, scratch, cus, s);
-    }
-    HRN_CHECK(dt == HRN_F32, -2, "hrn_kt_conv_wgrad: dtype %d", dt);
-    return hrn_launch_conv_wgrad((const float*)x, (const float*)stack, x ? 0 : 1, pair_h, pair_last, pair_vs, (const float*)g, M, H, W, cin, cout,
-                                 dw, scratch, cus, s);
+    return hrn_launch_conv_wgrad(dt, x, stack, x ? 0 : 1, pair_h, pair_last, pair_vs, g, M, H, W, cin, cout, dw, scratch, hrn_device_cus(), (hipStream_t)stream);
 }
 
 // dx [M][H][W][cin] = the data gradient of a cin -> cout conv3x3 with raw weights w [cout][cin][3][3] f32 at g [M][H][W][cout]
 // (+ res [M][H][W][cin] when not NULL), in storage dt; wt / wtp: cin * cout * 9 floats each, zero_bias: 128 zero floats
 int hrn_kt_conv_dgrad(int dt, int cin, int cout, const float* w, const void* g, void* dx, const void* res, int M, int H, int W, float* wt,
                       void* wtp, const float* zero_bias, void* stream) {
-    return hrn_conv_dgrad(cin, cout, w, (const float*)g, (float*)dx, (const float*)res, M, H, W, wt, wtp, zero_bias, (hipStream_t)stream, dt);
+    return hrn_conv_dgrad(dt, cin, cout, w, g, dx, res, M, H, W, wt, wtp, zero_bias, (hipStream_t)stream);
 }
 
 // out [M][H][W][cout] = conv3x3(in) + bias (no activation), in storage dt; in plain [M][H][W][cin] or (in == NULL) the pair gather of
@@ -50,7 +38,7 @@ int hrn_kt_conv3x3(int dt, int cin, int cout, const void* in, const void* stack,
     p.M = M; p.H = H; p.W = W;
     p.in = in; p.out = out; p.wpk = wpk; p.bias = bias;
     if (!in) { p.in_pair = 1; p.stack = stack; p.pair_h = pair_h; p.pair_last = pair_last; p.pair_vs = pair_vs; }
-    return hrn_launch_conv3x3(dt, cin, cout, p, (hipStream_t)stream);
+    return hrn_launch_conv3x3(dt, cin, cout, p, (hipStream_t)stream, false);
 }
 
 // One conv3x3 layer with the whole epilogue encoder_impl / fuse_impl (api.hip) set in ConvParams, in storage dt (HRN_DTYPE_BF16,
@@ -101,31 +89,30 @@ int hrn_kt_conv_pack(int dt, int cin, int cout, const float* w_oihw, void* packe
 // BatchNorm statistics of x [npix][C]: scale / shift (C f32 each), running stats updated with `momentum`; partial: 256 x 128 x 2 doubles
 int hrn_kt_sn_bn_stats(int dt, const void* x, size_t npix, int C, const float* gamma, const float* beta, float* scale, float* shift,
                        float* running_mean, float* running_var, float momentum, double* partial, void* stream) {
-    return hrn_launch_bn_stats((const float*)x, npix, C, gamma, beta, 1e-5f, scale, shift, running_mean, running_var, momentum, partial, 256,
-                               (hipStream_t)stream, dt);
+    return hrn_launch_bn_stats(dt, x, npix, C, gamma, beta, 1e-5f, scale, shift, running_mean, running_var, momentum, partial, 256,
+                               (hipStream_t)stream);
 }
 // out = [MaxPool2d(2)](ReLU(x * scale + shift)), x [N][H][W][C]
 int hrn_kt_sn_bn_act_pool(int dt, const void* x, const float* scale, const float* shift, void* out, int N, int H, int W, int C, int pool,
                           void* stream) {
-    return hrn_launch_bn_act_pool((const float*)x, scale, shift, (float*)out, N, H, W, C, pool, (hipStream_t)stream, dt);
+    return hrn_launch_bn_act_pool(dt, x, scale, shift, out, N, H, W, C, pool, (hipStream_t)stream);
 }
 // the BatchNorm + ReLU (+ pool) backward of one layer; stats = {mean, invstd, scale, shift} x 128 f32; partial: 256 x 128 x 2 doubles,
 // sums: 128 x 2 doubles
 int hrn_kt_sn_bn_bwd(int dt, const void* x, const void* dy, const float* stats, const float* gamma, void* dx, float* dgamma, float* dbeta,
                      int N, int H, int W, int C, int pool, double* partial, double* sums, void* stream) {
-    return hrn_launch_sn_bn_bwd((const float*)x, (const float*)dy, stats, gamma, (float*)dx, dgamma, dbeta, N, H, W, C, pool, partial, sums,
-                                (hipStream_t)stream, dt);
+    return hrn_launch_sn_bn_bwd(dt, x, dy, stats, gamma, dx, dgamma, dbeta, N, H, W, C, pool, partial, sums, (hipStream_t)stream);
 }
 // din [M][2][H][W] f32 = the stem's input gradient from g [M][H][W][64], w (64, 2, 3, 3) f32
 int hrn_kt_sn_stem_dgrad(int dt, const void* g, const float* w, float* din, int M, int H, int W, void* stream) {
-    return hrn_launch_sn_stem_dgrad((const float*)g, w, din, M, H, W, (hipStream_t)stream, dt);
+    return hrn_launch_sn_stem_dgrad(dt, g, w, din, M, H, W, (hipStream_t)stream);
 }
 // xr (B, 32768) f32 <- y [B][256][128] (dropout mask folded in), and back: dy [B][256][128] <- dxr (B, 32768) f32
 int hrn_kt_sn_fc_to_ref(int dt, const void* y, const unsigned char* mask, float* xr, int B, void* stream) {
-    return hrn_launch_fc_to_ref((const float*)y, mask, xr, B, (hipStream_t)stream, dt);
+    return hrn_launch_fc_to_ref(dt, y, mask, xr, B, (hipStream_t)stream);
 }
 int hrn_kt_sn_fc_from_ref(int dt, const float* dxr, const unsigned char* mask, void* dy, int B, void* stream) {
-    return hrn_launch_fc_from_ref(dxr, mask, (float*)dy, B, (hipStream_t)stream, dt);
+    return hrn_launch_fc_from_ref(dt, dxr, mask, dy, B, (hipStream_t)stream);
 }
 
 // ---- ShiftNet's remaining passes (tests/test_gpu_kernels_shiftnet.py), each the production launcher as api.hip / shiftnet_bwd.hip call it
@@ -146,7 +133,7 @@ int hrn_kt_sn_conv_bn_relu(int cin, int cout, const float* in, const void* wpk, 
     p.M = M; p.H = H; p.W = W;
     p.in = in; p.out = out;
     p.wpk = wpk; p.scale = scale; p.bias = shift; p.relu = 1;
-    return hrn_launch_conv3x3(HRN_F32, cin, cout, p, (hipStream_t)stream);
+    return hrn_launch_conv3x3(HRN_F32, cin, cout, p, (hipStream_t)stream, false);
 }
 // mean [planes] of x [planes][hw], and out = g - means[plane]
 int hrn_kt_sn_plane_mean(const float* x, float* mean, int planes, size_t hw, void* stream) {
@@ -181,55 +168,51 @@ int hrn_kt_sn_fc1_bwd_x(const float* dz1, const float* w1, float* dxr, int B, vo
 // g [rows][C] = dy * PReLU'(x), dslope[0] += sum dy min(x, 0), db[c] += sum_rows g (db / dslope NULL: a frozen parameter)
 int hrn_kt_prelu_bwd_bias(int dt, const void* dy, const void* y, const void* xpre, const float* slope, void* g, size_t rows, int C,
                           float* dslope, float* db, void* scratch, void* stream) {
-    return hrn_launch_prelu_bwd_bias((const float*)dy, (const float*)y, (const float*)xpre, slope, (float*)g, rows, C, dslope, db, scratch,
-                                     (hipStream_t)stream, dt);
+    return hrn_launch_prelu_bwd_bias(dt, dy, y, xpre, slope, g, rows, C, dslope, db, scratch, (hipStream_t)stream);
 }
 // db[c] += sum_rows g[row][c]
 int hrn_kt_colsum(int dt, const void* g, size_t rows, int C, float* db, void* scratch, void* stream) {
-    return hrn_launch_colsum((const float*)g, rows, C, db, scratch, (hipStream_t)stream, dt);
+    return hrn_launch_colsum(dt, g, rows, C, db, scratch, (hipStream_t)stream);
 }
 // o = a + b, n elements
 int hrn_kt_add(int dt, const void* a, const void* b, void* o, size_t n, void* stream) {
-    return hrn_launch_add((const float*)a, (const float*)b, (float*)o, n, (hipStream_t)stream, dt);
+    return hrn_launch_add(dt, a, b, o, n, (hipStream_t)stream);
 }
 // the fusion level's helpers: stack [B][n_in][hw][64], f / dsn / out / df [B * half][hw][64], dz [B * half][hw][128], ds [B][n_in][hw][64]
 int hrn_kt_fuse_update(int dt, const void* stack, int n_in, const void* f, const float* alphas, int alpha_vs, int pair_last, int half,
                        int alpha_residual, void* out, size_t hw, int B, void* stream) {
-    return hrn_launch_fuse_update((const float*)stack, n_in, (const float*)f, alphas, alpha_vs, pair_last, half, alpha_residual, (float*)out, hw,
-                                  B, (hipStream_t)stream, dt);
+    return hrn_launch_fuse_update(dt, stack, n_in, f, alphas, alpha_vs, pair_last, half, alpha_residual, out, hw, B, (hipStream_t)stream);
 }
 int hrn_kt_fuse_df(int dt, const void* dsn, const float* alphas, int alpha_vs, int pair_last, int half, int alpha_residual, void* df, size_t hw,
                    int B, void* stream) {
-    return hrn_launch_fuse_df((const float*)dsn, alphas, alpha_vs, pair_last, half, alpha_residual, (float*)df, hw, B, (hipStream_t)stream, dt);
+    return hrn_launch_fuse_df(dt, dsn, alphas, alpha_vs, pair_last, half, alpha_residual, df, hw, B, (hipStream_t)stream);
 }
 int hrn_kt_fuse_scatter(int dt, const void* dsn, const void* dz, int n_in, int half, int pair_last, int alpha_residual, void* ds, size_t hw,
                         int B, void* stream) {
-    return hrn_launch_fuse_scatter((const float*)dsn, (const float*)dz, n_in, half, pair_last, alpha_residual, (float*)ds, hw, B,
-                                   (hipStream_t)stream, dt);
+    return hrn_launch_fuse_scatter(dt, dsn, dz, n_in, half, pair_last, alpha_residual, ds, hw, B, (hipStream_t)stream);
 }
 // d_alphas[b][pair_last - v] = sum dsn * f of image b * half + v; scratch: hrn_kt_alpha_grad_scratch_bytes(B * half) bytes
 size_t hrn_kt_alpha_grad_scratch_bytes(int nimg) { return hrn_alpha_grad_scratch_bytes(nimg); }
 int hrn_kt_alpha_grad(int dt, const void* dsn, const void* f, int half, int pair_last, float* d_alphas, int B, int V, size_t hw, void* scratch,
                       size_t scratch_bytes, void* stream) {
-    return hrn_launch_alpha_grad((const float*)dsn, (const float*)f, half, pair_last, d_alphas, B, V, hw, scratch, scratch_bytes,
-                                 (hipStream_t)stream, dt);
+    return hrn_launch_alpha_grad(dt, dsn, f, half, pair_last, d_alphas, B, V, hw, scratch, scratch_bytes, (hipStream_t)stream);
 }
 // dw [64][2][3][3] += the stem's weight gradient; sub NULL: hrn_launch_stem_wgrad (HRNet), else hrn_launch_stem_wgrad_sub (ShiftNet)
 int hrn_kt_stem_wgrad(int dt, const float* in0, size_t stride0, const float* in1, int rep1, size_t stride1, const float* sub, const void* g,
                       int M, int H, int W, float* dw, void* scratch, void* stream) {
     const int cus = hrn_device_cus();
-    if (!sub) return hrn_launch_stem_wgrad(in0, stride0, in1, rep1, stride1, (const float*)g, M, H, W, dw, scratch, cus, (hipStream_t)stream, dt);
-    return hrn_launch_stem_wgrad_sub(in0, stride0, in1, rep1, stride1, sub, (const float*)g, M, H, W, dw, scratch, cus, (hipStream_t)stream, dt);
+    if (!sub) return hrn_launch_stem_wgrad(dt, in0, stride0, in1, rep1, stride1, g, M, H, W, dw, scratch, cus, (hipStream_t)stream);
+    return hrn_launch_stem_wgrad_sub(dt, in0, stride0, in1, rep1, stride1, sub, g, M, H, W, dw, scratch, cus, (hipStream_t)stream);
 }
 // d_lrs [B][V][H][W] = the stem's input gradient with the median routing; wt: 64 * 18 floats of scratch
 int hrn_kt_stem_dgrad_route(int dt, const void* dA, const float* w, float* wt, const float* lrs, const float* ref, float* d_lrs, int B, int V,
                             int H, int W, void* stream) {
-    return hrn_launch_stem_dgrad_route((const float*)dA, w, wt, lrs, ref, d_lrs, B, V, H, W, (hipStream_t)stream, dt);
+    return hrn_launch_stem_dgrad_route(dt, dA, w, wt, lrs, ref, d_lrs, B, V, H, W, (hipStream_t)stream);
 }
 // out [M][H][W][64] (dt) = the stem's pre-activation, only if only_if_nonpos[0] <= 0
 int hrn_kt_stem_pre(int dt, const float* in0, size_t img_stride0, const float* in1, int rep1, size_t img_stride1, const float* w,
                     const float* bias, void* out, int M, int H, int W, const float* only_if_nonpos, void* stream) {
-    return hrn_launch_stem_pre(in0, img_stride0, in1, rep1, img_stride1, w, bias, (float*)out, M, H, W, only_if_nonpos, (hipStream_t)stream, dt);
+    return hrn_launch_stem_pre(dt, in0, img_stride0, in1, rep1, img_stride1, w, bias, out, M, H, W, only_if_nonpos, (hipStream_t)stream);
 }
 // the f32 decoder backward at scale S: writes d_fused, accumulates the five gradients (NULL: a frozen parameter)
 int hrn_kt_decoder_bwd(int scale, const float* fused, const float* d_sr, const float* wd, const float* bd, const float* ad, const float* wf,

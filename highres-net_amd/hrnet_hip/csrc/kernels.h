@@ -1,5 +1,7 @@
 // Internal launcher declarations (one per kernel family).  All launch asynchronously on `stream`, allocate
 // nothing and never synchronise (graph-capturable); they return 0 or a negative error with hrn_set_error() set.
+// A launcher whose tensors' storage varies takes dt (HRN_F32 / HRN_BF16 / HRN_BF16X3) first and those tensors as `void*`; a `float*` is
+// always f32.  No argument has a default.
 #pragma once
 #include "common.h"
 #include "conv3x3.h"
@@ -8,21 +10,20 @@
 int hrn_launch_median(const float* lrs, float* ref, int B, int V, int H, int W, hipStream_t stream);
 int hrn_launch_stem(int dt, const float* in0, size_t img_stride0, const float* in1, int rep1, size_t img_stride1,
                     const float* sub, const float* w, const float* bias, const float* slope, void* out,
-                    int M, int H, int W, hipStream_t stream, size_t out_lo = 0);       // out_lo: HRN_BF16X3's lo-plane byte offset
+                    int M, int H, int W, hipStream_t stream, size_t out_lo);       // out_lo: HRN_BF16X3's lo-plane byte offset (else 0)
 int hrn_launch_planes_to_f32(const void* hi, size_t lo_off, float* out, size_t n, hipStream_t stream);
 int hrn_launch_f32_to_planes(const float* in, void* hi, size_t lo_off, size_t n, hipStream_t stream);
-int hrn_launch_stem_pre(const float* in0, size_t img_stride0, const float* in1, int rep1, size_t img_stride1, const float* w,
-                        const float* bias, float* out, int M, int H, int W, const float* only_if_nonpos, hipStream_t stream, int dt = HRN_F32);
+int hrn_launch_stem_pre(int dt, const float* in0, size_t img_stride0, const float* in1, int rep1, size_t img_stride1, const float* w,
+                        const float* bias, void* out, int M, int H, int W, const float* only_if_nonpos, hipStream_t stream);
 int hrn_launch_plane_mean(const float* x, float* mean, int planes, size_t hw, hipStream_t stream);
 
 // ---- decoder.hip
 // fused [N][HW][64] (dt) -> sr [N][S H][S W] f32, S = scale in {2, 3, 4}.  wpk: packed deconv weights (hrn_launch_decoder_pack of
-// the same scale), bias/slope/wf/bf f32.
+// the same scale), bias/slope/wf/bf f32.  fused_lo: HRN_BF16X3's lo-plane byte offset (else 0)
 int hrn_launch_decoder(int dt, const void* fused, const void* wpk, const float* bias, const float* slope,
-                       const float* wf, const float* bf, float* sr, int N, int H, int W, hipStream_t stream, size_t fused_lo = 0,
-                       int scale = 3);
+                       const float* wf, const float* bf, float* sr, int N, int H, int W, hipStream_t stream, size_t fused_lo, int scale);
 // w_iokk (64, 64, S, S)
-int hrn_launch_decoder_pack(int dt, const float* w_iokk, void* packed, hipStream_t stream, int scale = 3);
+int hrn_launch_decoder_pack(int dt, const float* w_iokk, void* packed, hipStream_t stream, int scale);
 
 // ---- lanczos.hip
 int hrn_launch_lanczos_taps(const float* d, int n, float* taps, hipStream_t stream);
@@ -44,18 +45,18 @@ int hrn_launch_loss_backward(const float* srs, const float* hrs, const float* ma
 int hrn_launch_shift_cpsnr(const float* srs, const float* hrs, const float* maps, int B, int S, int border, int clip,
                            double* scores, float* out, hipStream_t stream);
 
-// ---- shiftnet.hip.  dt: storage of the activation tensors behind the `float*` arguments x / out / y - HRN_F32 (default) or HRN_BF16,
-// one bf16 plane (ShiftNet's bf16 training mode); statistics, scale / shift and fc1's input xr are f32 in both
-int hrn_launch_bn_stats(const float* x, size_t npix, int C, const float* gamma, const float* beta, float eps,
+// ---- shiftnet.hip.  dt: storage of the activation tensors x / out / y - HRN_F32 or HRN_BF16, one bf16 plane (ShiftNet's bf16
+// training mode); statistics, scale / shift and fc1's input xr are f32 in both
+int hrn_launch_bn_stats(int dt, const void* x, size_t npix, int C, const float* gamma, const float* beta, float eps,
                         float* scale, float* shift, float* running_mean, float* running_var, float momentum,
-                        double* partial, int partial_blocks, hipStream_t stream, int dt = HRN_F32);
+                        double* partial, int partial_blocks, hipStream_t stream);
 int hrn_launch_bn_fold(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
                        const float* conv_bias, float* scale, float* shift, int C, hipStream_t stream);
-int hrn_launch_bn_act_pool(const float* x, const float* scale, const float* shift, float* out, int N, int H, int W, int C,
-                           int pool, hipStream_t stream, int dt = HRN_F32);
+int hrn_launch_bn_act_pool(int dt, const void* x, const float* scale, const float* shift, void* out, int N, int H, int W, int C,
+                           int pool, hipStream_t stream);
 // fc1: xr = the input in the reference's flatten order (hrn_launch_fc_to_ref: from the NHWC activation, dropout folded in), w = the raw
 // fc1.weight (1024, 32768), partial = hrn_fc1_partial_bytes() of scratch
-int hrn_launch_fc_to_ref(const float* y, const unsigned char* mask, float* xr, int B, hipStream_t stream, int dt = HRN_F32);
+int hrn_launch_fc_to_ref(int dt, const void* y, const unsigned char* mask, float* xr, int B, hipStream_t stream);
 size_t hrn_fc1_partial_bytes(void);
 int hrn_launch_fc1(const float* xr, const float* w, const float* b, float* y, int B, float* partial, hipStream_t stream);
 int hrn_launch_fc2(const float* y, const float* w, float* theta, int B, hipStream_t stream);
@@ -63,12 +64,12 @@ int hrn_launch_fc2(const float* y, const float* w, float* theta, int B, hipStrea
 // BatchNorm (+ ReLU, + MaxPool2d(2) when pool) backward of one layer: x = the pre-BatchNorm tensor [N][H][W][C], dy = the gradient of
 // the layer's output [N][H/p][W/p][C], stats = {mean, invstd, scale, shift} x 128 floats; writes dx [N][H][W][C], accumulates
 // dgamma / dbeta.  partial: SN_PARTIAL_BLOCKS x 128 x 2 doubles, sums: 128 x 2 doubles.
-int hrn_launch_sn_bn_bwd(const float* x, const float* dy, const float* stats, const float* gamma, float* dx, float* dgamma, float* dbeta,
-                         int N, int H, int W, int C, int pool, double* partial, double* sums, hipStream_t s, int dt = HRN_F32);
+int hrn_launch_sn_bn_bwd(int dt, const void* x, const void* dy, const float* stats, const float* gamma, void* dx, float* dgamma, float* dbeta,
+                         int N, int H, int W, int C, int pool, double* partial, double* sums, hipStream_t s);
 // the stem's (2 -> 64, ShiftNet.py:17) input gradient: g [M][H][W][64] (dt), w the raw weights (64, 2, 3, 3) -> din [M][2][H][W] f32
-int hrn_launch_sn_stem_dgrad(const float* g, const float* w, float* din, int M, int H, int W, hipStream_t s, int dt = HRN_F32);
+int hrn_launch_sn_stem_dgrad(int dt, const void* g, const float* w, float* din, int M, int H, int W, hipStream_t s);
 // dy [B][16*16][128] (dt) = the gradient of fc1's input dxr (B, 32768) f32 in the reference's flatten order, dropout mask applied
-int hrn_launch_fc_from_ref(const float* dxr, const unsigned char* mask, float* dy, int B, hipStream_t s, int dt = HRN_F32);
+int hrn_launch_fc_from_ref(int dt, const float* dxr, const unsigned char* mask, void* dy, int B, hipStream_t s);
 // mean[c], invstd[c] (what the BatchNorm backward reads) from the `partial` sums hrn_launch_bn_stats left (SN_PARTIAL_BLOCKS of them)
 int hrn_launch_sn_bn_save_stats(const double* partial, size_t npix, int C, float eps, float* mean, float* invstd, hipStream_t s);
 // out [planes][hw] = g - means[plane]: the backward of the per-plane mean subtraction (ShiftNet.py:58)

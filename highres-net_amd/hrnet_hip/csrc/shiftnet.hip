@@ -247,15 +247,15 @@ __global__ __launch_bounds__(256) void fc2_kernel(const float* __restrict__ y, c
 
 }  // namespace
 
-int hrn_launch_bn_stats(const float* x, size_t npix, int C, const float* gamma, const float* beta, float eps,
+int hrn_launch_bn_stats(int dt, const void* x, size_t npix, int C, const float* gamma, const float* beta, float eps,
                         float* scale, float* shift, float* running_mean, float* running_var, float momentum,
-                        double* partial, int partial_blocks, hipStream_t stream, int dt) {
+                        double* partial, int partial_blocks, hipStream_t stream) {
     HRN_CHECK(C == 64 || C == 128, -2, "bn_stats: unsupported channel count %d", C);
     HRN_CHECK(partial_blocks > 0, -2, "bn_stats: no partial buffer");
     HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16, -2, "bn_stats: unsupported dtype %d", dt);
     HrnProfScope prof("bn_stats", 0.0, (double)npix * C * hrn_esize(dt), stream);
-    if (dt == HRN_BF16) hipLaunchKernelGGL(bn_partial_kernel<HRN_BF16>, dim3(partial_blocks), dim3(256), 0, stream, (const void*)x, npix, C, partial);
-    else hipLaunchKernelGGL(bn_partial_kernel<HRN_F32>, dim3(partial_blocks), dim3(256), 0, stream, (const void*)x, npix, C, partial);
+    if (dt == HRN_BF16) hipLaunchKernelGGL(bn_partial_kernel<HRN_BF16>, dim3(partial_blocks), dim3(256), 0, stream, x, npix, C, partial);
+    else hipLaunchKernelGGL(bn_partial_kernel<HRN_F32>, dim3(partial_blocks), dim3(256), 0, stream, x, npix, C, partial);
     HRN_LAUNCH_CHECK();
     hipLaunchKernelGGL(bn_finish_kernel, dim3(1), dim3(1024), 0, stream, partial, partial_blocks, npix, C, gamma, beta, eps,
                        scale, shift, running_mean, running_var, momentum);
@@ -270,32 +270,30 @@ int hrn_launch_bn_fold(const float* gamma, const float* beta, const float* rm, c
     return 0;
 }
 
-int hrn_launch_bn_act_pool(const float* x, const float* scale, const float* shift, float* out, int N, int H, int W, int C,
-                           int pool, hipStream_t stream, int dt) {
+int hrn_launch_bn_act_pool(int dt, const void* x, const float* scale, const float* shift, void* out, int N, int H, int W, int C,
+                           int pool, hipStream_t stream) {
     const int p = pool ? 2 : 1;
     HRN_CHECK(!pool || (H % 2 == 0 && W % 2 == 0), -2, "maxpool2 needs even H, W");
     HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16, -2, "bn_relu_pool: unsupported dtype %d", dt);
     const size_t total = (size_t)N * (H / p) * (W / p) * (C / 4);
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     HrnProfScope prof("bn_relu_pool", 0.0, (double)N * H * W * C * hrn_esize(dt) * (1.0 + 1.0 / (p * p)), stream);
-    const void* xv = x;
-    void* ov = out;
     if (dt == HRN_BF16) {
-        if (pool) hipLaunchKernelGGL((bn_act_pool_kernel<2, HRN_BF16>), dim3(blocks), dim3(256), 0, stream, xv, scale, shift, ov, N, H, W, C);
-        else hipLaunchKernelGGL((bn_act_pool_kernel<1, HRN_BF16>), dim3(blocks), dim3(256), 0, stream, xv, scale, shift, ov, N, H, W, C);
+        if (pool) hipLaunchKernelGGL((bn_act_pool_kernel<2, HRN_BF16>), dim3(blocks), dim3(256), 0, stream, x, scale, shift, out, N, H, W, C);
+        else hipLaunchKernelGGL((bn_act_pool_kernel<1, HRN_BF16>), dim3(blocks), dim3(256), 0, stream, x, scale, shift, out, N, H, W, C);
     } else {
-        if (pool) hipLaunchKernelGGL((bn_act_pool_kernel<2, HRN_F32>), dim3(blocks), dim3(256), 0, stream, xv, scale, shift, ov, N, H, W, C);
-        else hipLaunchKernelGGL((bn_act_pool_kernel<1, HRN_F32>), dim3(blocks), dim3(256), 0, stream, xv, scale, shift, ov, N, H, W, C);
+        if (pool) hipLaunchKernelGGL((bn_act_pool_kernel<2, HRN_F32>), dim3(blocks), dim3(256), 0, stream, x, scale, shift, out, N, H, W, C);
+        else hipLaunchKernelGGL((bn_act_pool_kernel<1, HRN_F32>), dim3(blocks), dim3(256), 0, stream, x, scale, shift, out, N, H, W, C);
     }
     HRN_LAUNCH_CHECK();
     return 0;
 }
 
-int hrn_launch_fc_to_ref(const float* y, const unsigned char* mask, float* xr, int B, hipStream_t stream, int dt) {
+int hrn_launch_fc_to_ref(int dt, const void* y, const unsigned char* mask, float* xr, int B, hipStream_t stream) {
     HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16, -2, "fc_to_ref: unsupported dtype %d", dt);
     HrnProfScope prof("fc_to_ref", 0.0, (double)B * FC_K * (4 + hrn_esize(dt)), stream);
-    if (dt == HRN_BF16) hipLaunchKernelGGL(fc_to_ref_kernel<HRN_BF16>, dim3(256 / 32, 128 / 32, B), dim3(256), 0, stream, (const void*)y, mask, xr);
-    else hipLaunchKernelGGL(fc_to_ref_kernel<HRN_F32>, dim3(256 / 32, 128 / 32, B), dim3(256), 0, stream, (const void*)y, mask, xr);
+    if (dt == HRN_BF16) hipLaunchKernelGGL(fc_to_ref_kernel<HRN_BF16>, dim3(256 / 32, 128 / 32, B), dim3(256), 0, stream, y, mask, xr);
+    else hipLaunchKernelGGL(fc_to_ref_kernel<HRN_F32>, dim3(256 / 32, 128 / 32, B), dim3(256), 0, stream, y, mask, xr);
     HRN_LAUNCH_CHECK();
     return 0;
 }

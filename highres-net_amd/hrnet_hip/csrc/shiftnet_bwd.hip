@@ -368,20 +368,18 @@ bool sn_dtype_ok(int dt) { return dt == HRN_F32 || dt == HRN_BF16; }
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ the backward's passes
-int hrn_launch_sn_bn_bwd(const float* x, const float* dy, const float* stats, const float* gamma, float* dx, float* dgamma, float* dbeta,
-                         int N, int H, int W, int C, int pool, double* partial, double* sums, hipStream_t s, int dt) {
+int hrn_launch_sn_bn_bwd(int dt, const void* x, const void* dy, const float* stats, const float* gamma, void* dx, float* dgamma, float* dbeta,
+                         int N, int H, int W, int C, int pool, double* partial, double* sums, hipStream_t s) {
     HRN_CHECK(C == 64 || C == 128, -2, "sn_bn_bwd: unsupported channel count %d", C);
     HRN_CHECK(sn_dtype_ok(dt), -2, "sn_bn_bwd: unsupported dtype %d", dt);
     HRN_CHECK(!pool || (H % 2 == 0 && W % 2 == 0), -2, "sn_bn_bwd: maxpool2 needs even H, W");
-    const void *xv = x, *dyv = dy;
-    void* dxv = dx;
 #define HRN_SN_BN(P_, ST_)                                                                                                              \
     do {                                                                                                                                \
-        hipLaunchKernelGGL((bn_bwd_reduce_kernel<P_, ST_>), dim3(SN_PARTIAL_BLOCKS), dim3(256), 0, s, xv, dyv, stats, N, H, W, C, partial); \
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<P_, ST_>), dim3(SN_PARTIAL_BLOCKS), dim3(256), 0, s, x, dy, stats, N, H, W, C, partial); \
         HRN_LAUNCH_CHECK();                                                                                                             \
         hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3(1), dim3(1024), 0, s, (const double*)partial, SN_PARTIAL_BLOCKS, C, sums, dgamma, dbeta); \
         HRN_LAUNCH_CHECK();                                                                                                             \
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<P_, ST_>), dim3(eg), dim3(256), 0, s, xv, dyv, stats, gamma, (const double*)sums, dxv, N, H, W, C); \
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<P_, ST_>), dim3(eg), dim3(256), 0, s, x, dy, stats, gamma, (const double*)sums, dx, N, H, W, C); \
         HRN_LAUNCH_CHECK();                                                                                                             \
     } while (0)
     const int eg = ew_grid((size_t)N * H * W * C / 4 / (pool ? 4 : 1));
@@ -392,20 +390,20 @@ int hrn_launch_sn_bn_bwd(const float* x, const float* dy, const float* stats, co
     return 0;
 }
 
-int hrn_launch_sn_stem_dgrad(const float* g, const float* w, float* din, int M, int H, int W, hipStream_t s, int dt) {
+int hrn_launch_sn_stem_dgrad(int dt, const void* g, const float* w, float* din, int M, int H, int W, hipStream_t s) {
     HRN_CHECK(sn_dtype_ok(dt), -2, "sn_stem_dgrad: unsupported dtype %d", dt);
     const size_t npix = (size_t)M * H * W;
-    if (dt == HRN_BF16) hipLaunchKernelGGL(stem_dgrad_kernel<HRN_BF16>, dim3(ew_grid(npix)), dim3(256), 0, s, (const void*)g, w, din, M, H, W);
-    else hipLaunchKernelGGL(stem_dgrad_kernel<HRN_F32>, dim3(ew_grid(npix)), dim3(256), 0, s, (const void*)g, w, din, M, H, W);
+    if (dt == HRN_BF16) hipLaunchKernelGGL(stem_dgrad_kernel<HRN_BF16>, dim3(ew_grid(npix)), dim3(256), 0, s, g, w, din, M, H, W);
+    else hipLaunchKernelGGL(stem_dgrad_kernel<HRN_F32>, dim3(ew_grid(npix)), dim3(256), 0, s, g, w, din, M, H, W);
     HRN_LAUNCH_CHECK();
     return 0;
 }
 
-int hrn_launch_fc_from_ref(const float* dxr, const unsigned char* mask, float* dy, int B, hipStream_t s, int dt) {
+int hrn_launch_fc_from_ref(int dt, const float* dxr, const unsigned char* mask, void* dy, int B, hipStream_t s) {
     HRN_CHECK(sn_dtype_ok(dt), -2, "fc_from_ref: unsupported dtype %d", dt);
     const size_t nflat = (size_t)B * FCK;
-    if (dt == HRN_BF16) hipLaunchKernelGGL(fc_from_ref_kernel<HRN_BF16>, dim3(ew_grid(nflat)), dim3(256), 0, s, dxr, mask, (void*)dy, nflat);
-    else hipLaunchKernelGGL(fc_from_ref_kernel<HRN_F32>, dim3(ew_grid(nflat)), dim3(256), 0, s, dxr, mask, (void*)dy, nflat);
+    if (dt == HRN_BF16) hipLaunchKernelGGL(fc_from_ref_kernel<HRN_BF16>, dim3(ew_grid(nflat)), dim3(256), 0, s, dxr, mask, dy, nflat);
+    else hipLaunchKernelGGL(fc_from_ref_kernel<HRN_F32>, dim3(ew_grid(nflat)), dim3(256), 0, s, dxr, mask, dy, nflat);
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -454,7 +452,6 @@ int hrn_launch_sn_fc1_bwd_x(const float* dz1, const float* w1, float* dxr, int B
 extern "C" {
 
 size_t hrn_shiftnet_train_workspace_bytes_dt(int dtype, int B) { return B > 0 && sn_dtype_ok(dtype) ? sn_train_ws(B, dtype).total : 0; }
-size_t hrn_shiftnet_train_workspace_bytes(int B) { return hrn_shiftnet_train_workspace_bytes_dt(HRN_F32, B); }
 
 int hrn_shiftnet_forward_train_dt(const void* packed, int dt, const hrn_shiftnet_params* P, const float* x, int B, float momentum,
                                   const unsigned char* dropout_mask, float* theta, void* tws, size_t tws_bytes, void* stream) {
@@ -483,54 +480,45 @@ int hrn_shiftnet_forward_train_dt(const void* packed, int dt, const hrn_shiftnet
     if ((rc = hrn_launch_plane_mean(x, means, B * 2, plane, s))) return rc;                      // ShiftNet.py:58
     for (int i = 0; i < 8; ++i) {
         const int h = T.hin[i], C = SN_CO[i];
-        float* xp = (float*)at(tws, T.xpre[i]);
-        float* yp = (float*)at(tws, T.ypost[i]);
+        void* xp = at(tws, T.xpre[i]);
+        void* yp = at(tws, T.ypost[i]);
         float* st = (float*)at(tws, T.stats[i]);
         if (i == 0) {
             if ((rc = hrn_launch_stem(dt, x, 2 * plane, x + plane, 1, 2 * plane, means, (const float*)at(packed, L.conv_w[0]),
-                                      (const float*)at(packed, L.conv_b[0]), nullptr, xp, B, h, h, s))) return rc;
+                                      (const float*)at(packed, L.conv_b[0]), nullptr, xp, B, h, h, s, 0))) return rc;
         } else {
             ConvParams p = conv_base(B, h, h);
             p.in = at(tws, T.ypost[i - 1]); p.out = xp;
             p.wpk = dt == HRN_BF16 ? at(tws, T.wpk[i]) : at(packed, L.conv_w[i]); p.bias = (const float*)at(packed, L.conv_b[i]);
-            if ((rc = hrn_launch_conv3x3(dt, SN_CI[i], C, p, s))) return rc;
+            if ((rc = hrn_launch_conv3x3(dt, SN_CI[i], C, p, s, false))) return rc;
         }
         const size_t npix = (size_t)B * h * h;
-        if ((rc = hrn_launch_bn_stats(xp, npix, C, P->bn_g[i], P->bn_b[i], 1e-5f, st + 256, st + 384, P->bn_rm[i], P->bn_rv[i], momentum,
-                                      partial, SN_PARTIAL_BLOCKS, s, dt))) return rc;
+        if ((rc = hrn_launch_bn_stats(dt, xp, npix, C, P->bn_g[i], P->bn_b[i], 1e-5f, st + 256, st + 384, P->bn_rm[i], P->bn_rv[i], momentum,
+                                      partial, SN_PARTIAL_BLOCKS, s))) return rc;
         if ((rc = hrn_launch_sn_bn_save_stats(partial, npix, C, 1e-5f, st, st + 128, s))) return rc;
-        if ((rc = hrn_launch_bn_act_pool(xp, st + 256, st + 384, yp, B, h, h, C, SN_POOL[i], s, dt))) return rc;
+        if ((rc = hrn_launch_bn_act_pool(dt, xp, st + 256, st + 384, yp, B, h, h, C, SN_POOL[i], s))) return rc;
     }
     float* y1 = (float*)at(tws, T.y1);
     // fc1's input in the reference's flatten order, dropout folded in: kept in the workspace - the backward's weight gradient reads it
     float* xr = (float*)at(tws, T.xr);
-    if ((rc = hrn_launch_fc_to_ref((const float*)at(tws, T.ypost[7]), dropout_mask, xr, B, s, dt))) return rc;
+    if ((rc = hrn_launch_fc_to_ref(dt, at(tws, T.ypost[7]), dropout_mask, xr, B, s))) return rc;
     if ((rc = hrn_launch_fc1(xr, P->fc1_w, (const float*)at(packed, L.fc1_b), y1, B, (float*)at(tws, T.fc_partial), s))) return rc;
     return hrn_launch_fc2(y1, (const float*)at(packed, L.fc2_w), theta, B, s);
 }
 
-int hrn_shiftnet_forward_train(const void* packed, const hrn_shiftnet_params* P, const float* x, int B, float momentum,
-                               const unsigned char* dropout_mask, float* theta, void* tws, size_t tws_bytes, void* stream) {
-    return hrn_shiftnet_forward_train_dt(packed, HRN_F32, P, x, B, momentum, dropout_mask, theta, tws, tws_bytes, stream);
-}
-
-}  // extern "C"
-
-namespace {
-
-// The backward behind hrn_shiftnet_backward_dt (sel = false: every gradient of `G`, the launch sequence of every release) and
-// hrn_shiftnet_backward_sel (sel = true: a NULL field of `G` is a frozen parameter).  The walk stops at the deepest layer below which
+// The backward of every hrn_shiftnet_backward* entry point (abi_fixed.hip holds the forms with an argument fixed).  A NULL field of `G`
+// is a frozen parameter; with every field set, every gradient is produced.  The walk stops at the deepest layer below which
 // nothing is wanted (d_x NULL); a frozen layer above it keeps its BatchNorm backward and data gradient and skips its weight and bias
 // gradients.  fc2_bwd_kernel (dz1, d fc2.weight, d fc1.bias in one pass) runs whenever anything is wanted.
-int shiftnet_backward_impl(const hrn_shiftnet_params* P, int dt, const float* x, int B, const unsigned char* dropout_mask, const float* d_theta,
-                           const hrn_shiftnet_params* G, float* d_x, void* tws, size_t tws_bytes, void* stream, bool sel) {
+int hrn_shiftnet_backward_sel(const hrn_shiftnet_params* P, int dt, const float* x, int B, const unsigned char* dropout_mask,
+                              const float* d_theta, const hrn_shiftnet_params* G, float* d_x, void* tws, size_t tws_bytes, void* stream) {
     HRN_CHECK(sn_dtype_ok(dt), -2, "hrn_shiftnet_backward: unsupported dtype %d (HRN_DTYPE_F32 or HRN_DTYPE_BF16)", dt);
     HRN_CHECK(P && G && x && d_theta && tws, -2, "hrn_shiftnet_backward: null argument");
     HRN_CHECK(B > 0, -2, "hrn_shiftnet_backward: empty batch");
     if (dt == HRN_BF16) HRN_CHECK(((uintptr_t)tws & 255) == 0, -2, "hrn_shiftnet_backward: train_ws must be 256-byte aligned");
     const SnTrainWs T = sn_train_ws(B, dt);
     HRN_CHECK(tws_bytes >= T.total, -3, "hrn_shiftnet_backward: workspace too small (%zu < %zu)", tws_bytes, T.total);
-    auto want = [&](const float* g) { return !sel || g != nullptr; };
+    auto want = [](const float* g) { return g != nullptr; };
     // lowest: the first layer (counted from the input) whose d ypost is read; 8: none of them
     int lowest = d_x ? 0 : 8;
     for (int i = 0; i < 8 && lowest == 8; ++i)
@@ -543,8 +531,8 @@ int shiftnet_backward_impl(const hrn_shiftnet_params* P, int dt, const float* x,
     void* sc = at(tws, T.scratch);
     double* partial = (double*)at(tws, T.partial);
     double* sums = (double*)at(tws, T.sums);
-    float* cur = (float*)at(tws, T.ga);
-    float* oth = (float*)at(tws, T.gb);
+    void* cur = at(tws, T.ga);
+    void* oth = at(tws, T.gb);
     float* xr = (float*)at(tws, T.xr);
     float* dxr = (float*)at(tws, T.dxr);
     float* dz1 = (float*)at(tws, T.dz1);
@@ -556,59 +544,36 @@ int shiftnet_backward_impl(const hrn_shiftnet_params* P, int dt, const float* x,
     if (fc1w && (rc = hrn_launch_sn_fc1_bwd_w(dz1, xr, mut(G->fc1_w), B, s))) return rc;
     if (lowest == 8) return 0;
     if ((rc = hrn_launch_sn_fc1_bwd_x(dz1, P->fc1_w, dxr, B, s))) return rc;
-    if ((rc = hrn_launch_fc_from_ref(dxr, dropout_mask, cur, B, s, dt))) return rc;
+    if ((rc = hrn_launch_fc_from_ref(dt, dxr, dropout_mask, cur, B, s))) return rc;
     // ---- layers 8 .. 1                                                                        ShiftNet.py:16-41, :59-67
     for (int i = 7; i >= lowest; --i) {
         const int h = T.hin[i], C = SN_CO[i];
-        const float* xp = (const float*)at(tws, T.xpre[i]);
+        const void* xp = at(tws, T.xpre[i]);
         const float* st = (const float*)at(tws, T.stats[i]);
         const size_t npix = (size_t)B * h * h;
-        if ((rc = hrn_launch_sn_bn_bwd(xp, cur, st, P->bn_g[i], oth, mut(G->bn_g[i]), mut(G->bn_b[i]), B, h, h, C, SN_POOL[i], partial, sums, s,
-                                       dt))) return rc;
+        if ((rc = hrn_launch_sn_bn_bwd(dt, xp, cur, st, P->bn_g[i], oth, mut(G->bn_g[i]), mut(G->bn_b[i]), B, h, h, C, SN_POOL[i], partial, sums,
+                                       s))) return rc;
         // oth = d xpre_i
-        if (want(G->conv_b[i]) && (rc = hrn_launch_colsum(oth, npix, C, mut(G->conv_b[i]), sc, s, dt))) return rc;
+        if (want(G->conv_b[i]) && (rc = hrn_launch_colsum(dt, oth, npix, C, mut(G->conv_b[i]), sc, s))) return rc;
         if (i > 0) {
-            const float* xin = (const float*)at(tws, T.ypost[i - 1]);
-            if (want(G->conv_w[i])) {
-                if (dt == HRN_BF16) rc = hrn_launch_conv_wgrad_bf16(xin, nullptr, 0, 0, 0, 0, oth, B, h, h, SN_CI[i], C, mut(G->conv_w[i]), sc, cus, s);
-                else rc = hrn_launch_conv_wgrad(xin, nullptr, 0, 0, 0, 0, oth, B, h, h, SN_CI[i], C, mut(G->conv_w[i]), sc, cus, s);
-                if (rc) return rc;
-            }
-            if (i > lowest && (rc = hrn_conv_dgrad(SN_CI[i], C, P->conv_w[i], oth, cur, nullptr, B, h, h, (float*)at(tws, T.wt), at(tws, T.wtp),
-                                                   (const float*)at(tws, T.zero_bias), s, dt))) return rc;
+            if (want(G->conv_w[i]) && (rc = hrn_launch_conv_wgrad(dt, at(tws, T.ypost[i - 1]), nullptr, 0, 0, 0, 0, oth, B, h, h, SN_CI[i], C,
+                                                                  mut(G->conv_w[i]), sc, cus, s))) return rc;
+            if (i > lowest && (rc = hrn_conv_dgrad(dt, SN_CI[i], C, P->conv_w[i], oth, cur, nullptr, B, h, h, (float*)at(tws, T.wt), at(tws, T.wtp),
+                                                   (const float*)at(tws, T.zero_bias), s))) return rc;
         } else {
             const size_t plane = 128 * 128;
-            if (want(G->conv_w[0]) && (rc = hrn_launch_stem_wgrad_sub(x, 2 * plane, x + plane, 1, 2 * plane, (const float*)at(tws, T.means), oth, B,
-                                                                      h, h, mut(G->conv_w[0]), sc, cus, s, dt))) return rc;
+            if (want(G->conv_w[0]) && (rc = hrn_launch_stem_wgrad_sub(dt, x, 2 * plane, x + plane, 1, 2 * plane, (const float*)at(tws, T.means), oth, B,
+                                                                      h, h, mut(G->conv_w[0]), sc, cus, s))) return rc;
             if (d_x) {
                 float* dxin = (float*)at(tws, T.dxin);
                 float* gm = (float*)at(tws, T.gmeans);
-                if ((rc = hrn_launch_sn_stem_dgrad(oth, P->conv_w[0], dxin, B, h, h, s, dt))) return rc;
+                if ((rc = hrn_launch_sn_stem_dgrad(dt, oth, P->conv_w[0], dxin, B, h, h, s))) return rc;
                 if ((rc = hrn_launch_plane_mean(dxin, gm, B * 2, plane, s))) return rc;
                 if ((rc = hrn_launch_sn_sub_plane_mean(dxin, gm, d_x, B * 2, plane, s))) return rc;
             }
         }
     }
     return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int hrn_shiftnet_backward_dt(const hrn_shiftnet_params* P, int dt, const float* x, int B, const unsigned char* dropout_mask,
-                             const float* d_theta, const hrn_shiftnet_params* G, float* d_x, void* tws, size_t tws_bytes, void* stream) {
-    return shiftnet_backward_impl(P, dt, x, B, dropout_mask, d_theta, G, d_x, tws, tws_bytes, stream, false);
-}
-
-int hrn_shiftnet_backward_sel(const hrn_shiftnet_params* P, int dt, const float* x, int B, const unsigned char* dropout_mask,
-                              const float* d_theta, const hrn_shiftnet_params* G, float* d_x, void* tws, size_t tws_bytes, void* stream) {
-    return shiftnet_backward_impl(P, dt, x, B, dropout_mask, d_theta, G, d_x, tws, tws_bytes, stream, true);
-}
-
-int hrn_shiftnet_backward(const hrn_shiftnet_params* P, const float* x, int B, const unsigned char* dropout_mask, const float* d_theta,
-                          const hrn_shiftnet_params* G, float* d_x, void* tws, size_t tws_bytes, void* stream) {
-    return hrn_shiftnet_backward_dt(P, HRN_F32, x, B, dropout_mask, d_theta, G, d_x, tws, tws_bytes, stream);
 }
 
 }  // extern "C"

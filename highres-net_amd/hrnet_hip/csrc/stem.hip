@@ -396,24 +396,13 @@ int hrn_launch_stem(int dt, const float* in0, size_t img_stride0, const float* i
 
 // no activation, and only if only_if_nonpos[0] <= 0: the stem's pre-activation for the backward of a PReLU whose slope is not positive,
 // in the training storage of dt (f32, one bf16 plane or bf16x3 planes)
-int hrn_launch_stem_pre(const float* in0, size_t img_stride0, const float* in1, int rep1, size_t img_stride1, const float* w,
-                        const float* bias, float* out, int M, int H, int W, const float* only_if_nonpos, hipStream_t stream, int dt) {
+int hrn_launch_stem_pre(int dt, const float* in0, size_t img_stride0, const float* in1, int rep1, size_t img_stride1, const float* w,
+                        const float* bias, void* out, int M, int H, int W, const float* only_if_nonpos, hipStream_t stream) {
     const size_t patches = (size_t)M * ((H + 3) / 4) * ((W + 31) / 32);
     const int blocks = (int)(patches < 16384 ? patches : 16384);
-    if (dt == HRN_BF16X3) {
-        hipLaunchKernelGGL(stem_kernel<HRN_BF16X3>, dim3(blocks), dim3(256), 0, stream, in0, in1, img_stride0, rep1, img_stride1, (const float*)nullptr, w, bias,
-                           (const float*)nullptr, (void*)out, M, H, W, only_if_nonpos, (size_t)M * H * W * 64 * 2);
-        HRN_LAUNCH_CHECK();
-        return 0;
-    }
-    if (dt == HRN_BF16) {
-        hipLaunchKernelGGL(stem_kernel<HRN_BF16>, dim3(blocks), dim3(256), 0, stream, in0, in1, img_stride0, rep1, img_stride1, (const float*)nullptr, w, bias,
-                           (const float*)nullptr, (void*)out, M, H, W, only_if_nonpos, (size_t)0);
-        HRN_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(stem_kernel<HRN_F32>, dim3(blocks), dim3(256), 0, stream, in0, in1, img_stride0, rep1, img_stride1, (const float*)nullptr, w, bias,
-                       (const float*)nullptr, (void*)out, M, H, W, only_if_nonpos, (size_t)0);
+    const size_t out_lo = dt == HRN_BF16X3 ? (size_t)M * H * W * 64 * 2 : 0;        // the lo plane directly behind the hi plane
+    HRN_LAUNCH_ST(dt, stem_kernel, dim3(blocks), dim3(256), 0, stream, in0, in1, img_stride0, rep1, img_stride1, (const float*)nullptr, w, bias,
+                  (const float*)nullptr, out, M, H, W, only_if_nonpos, out_lo);
     HRN_LAUNCH_CHECK();
     return 0;
 }

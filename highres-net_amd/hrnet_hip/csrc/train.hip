@@ -103,24 +103,13 @@ int conv_fwd(int dt, int cin, int cout, const void* x, void* y, const void* wpk,
     ConvParams p = conv_base(M, H, W);
     p.in = x; p.out = y; p.wpk = wpk; p.bias = bias; p.slope = slope;
     p.in_lo = lo_of(dt, (size_t)M * H * W * cin); p.out_lo = lo_of(dt, (size_t)M * H * W * cout);
-    return hrn_launch_conv3x3(dt, cin, cout, p, s);
+    return hrn_launch_conv3x3(dt, cin, cout, p, s, false);
 }
 
 // dx = conv3x3(g, W^T flipped) (+ res): the data gradient of a cin -> cout convolution with raw weights w [cout][cin][3][3]
-int conv_dgrad(int dt, int cin, int cout, const float* w, const float* g, float* dx, const float* res, int M, int H, int W, void* tws,
+int conv_dgrad(int dt, int cin, int cout, const float* w, const void* g, void* dx, const void* res, int M, int H, int W, void* tws,
                const TrainWs& L, hipStream_t s) {
-    return hrn_conv_dgrad(cin, cout, w, g, dx, res, M, H, W, (float*)at(tws, L.wt), at(tws, L.wtp), (const float*)at(tws, L.zero_bias), s, dt);
-}
-
-// dW += the weight gradient of a cin -> cout convolution: x plain [M][H][W][cin], or (x == nullptr) the pair gather of `stack`
-int conv_wgrad(int dt, const float* x, const float* stack, int pair_h, int pair_last, int pair_vs, int Bn, const float* g, int M, int H, int W,
-               int cin, int cout, float* dw, void* sc, int cus, hipStream_t s) {
-    if (dt == HRN_F32) return hrn_launch_conv_wgrad(x, stack, x ? 0 : 1, pair_h, pair_last, pair_vs, g, M, H, W, cin, cout, dw, sc, cus, s);
-    if (dt == HRN_BF16) return hrn_launch_conv_wgrad_bf16(x, stack, x ? 0 : 1, pair_h, pair_last, pair_vs, g, M, H, W, cin, cout, dw, sc, cus, s);
-    const size_t hw = (size_t)H * W;
-    const size_t x_lo = x ? (size_t)M * hw * cin * 2 : (size_t)Bn * pair_vs * hw * 64 * 2;     // the stack of the level: Bn samples x pair_vs views
-    return hrn_launch_conv_wgrad_x3(x, stack, x_lo, x ? 0 : 1, pair_h, pair_last, pair_vs, g, (size_t)M * hw * cout * 2, M, H, W, cin, cout, dw, sc,
-                                    cus, s);
+    return hrn_conv_dgrad(dt, cin, cout, w, g, dx, res, M, H, W, (float*)at(tws, L.wt), at(tws, L.wtp), (const float*)at(tws, L.zero_bias), s);
 }
 
 // z + u for the pair gather z of a level: t2[b*half + i][p][c] = (c < 64 ? s_i : s_partner)[p][c % 64] + u[...]
@@ -140,17 +129,25 @@ __global__ __launch_bounds__(256) void pair_add_kernel(const void* __restrict__ 
     }
 }
 
+}  // namespace
 
-// The backward behind hrn_hrnet_backward_in (sel = false: every gradient of `Gr` is produced, the launch sequence of every release) and
-// hrn_hrnet_backward_sel (sel = true: a NULL field of `Gr` is a frozen parameter).  A launch is left out only when nothing downstream reads
+extern "C" {
+
+size_t hrn_hrnet_train_workspace_bytes(int num_layers, int B, int V, int H, int W) {
+    if (num_layers < 0 || num_layers > HRN_MAX_RES_LAYERS || B <= 0 || V <= 0 || H <= 0 || W <= 0 || V >= (1 << TMAX)) return 0;
+    return train_ws(num_layers, B, V, H, W).total;
+}
+
+// The backward of every hrn_hrnet_backward* entry point (abi_fixed.hip holds the forms with an argument fixed).  A NULL field of `Gr` is
+// a frozen parameter; with every field set, every gradient is produced.  A launch is left out only when nothing downstream reads
 // any of its outputs; what runs computes what it computes on the full path, so every produced gradient is bit-identical to it.
 //   need_ds[t]   the gradient of the views entering fusion level t (t = T: the decoder's data gradient, t = 0: d stack_0)
 //   need_da[l]   the gradient of the encoder activation a_l (l = 0: the stem's output)
 // Decoder parameters need only the decoder's weight-gradient part; fusion parameters (shared by every level) and d_alphas (alpha
 // residual only) every level's data gradient above them; encoder / stem parameters and d_lrs the chain down to stack_0.
-int hrnet_backward_impl(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
-                        int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, float* d_lrs, float* d_alphas, void* tws,
-                        size_t tws_bytes, void* stream, bool sel) {
+int hrn_hrnet_backward_sel(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
+                           int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, float* d_lrs, float* d_alphas, void* tws,
+                           size_t tws_bytes, void* stream) {
     int rc;
     HRN_CHECK(hrn_scale_ok(scale), -2, "hrn_hrnet_backward: scale must be 2, 3 or 4 (got %d)", scale);
     HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16 || dt == HRN_BF16X3, -2, "hrn_hrnet_backward: dtype must be HRN_DTYPE_F32, HRN_DTYPE_BF16 or HRN_DTYPE_BF16X3 (got %d)", dt);
@@ -162,8 +159,8 @@ int hrnet_backward_impl(const void* pk, int dt, int scale, const hrn_hrnet_param
     HRN_CHECK(tws_bytes >= L.total, -3, "hrn_hrnet_backward: workspace too small (%zu < %zu)", tws_bytes, L.total);
     for (int t = 0; d_alphas && t < L.T; ++t)
         HRN_CHECK(hrn_alpha_grad_scratch_bytes(B * (L.n_in[t] / 2)) <= L.dec_f - L.scratch, -3, "hrn_hrnet_backward_in: scratch too small for d_alphas");
-    // ---- what is needed (all of it unless sel)
-    auto want = [&](const float* g) { return !sel || g != nullptr; };
+    // ---- what is needed
+    auto want = [](const float* g) { return g != nullptr; };
     auto want_prelu = [&](const float* w, const float* b, const float* a) { return want(w) || want(b) || want(a); };
     const bool dec = want(Gr->dec_w) || want(Gr->dec_b) || want(Gr->dec_a) || want(Gr->fin_w) || want(Gr->fin_b);
     const bool fuse = want_prelu(Gr->fuse_res_w[0], Gr->fuse_res_b[0], Gr->fuse_res_a[0]) ||
@@ -182,8 +179,8 @@ int hrnet_backward_impl(const void* pk, int dt, int scale, const hrn_hrnet_param
     const size_t hw = (size_t)H * W;
     const int M = B * V, cus = num_cus();
     void* sc = at(tws, L.scratch);
-    float* G[5];
-    for (int i = 0; i < 5; ++i) G[i] = (float*)at(tws, L.g[i]);
+    void* G[5];
+    for (int i = 0; i < 5; ++i) G[i] = at(tws, L.g[i]);
     HRN_HIP(hipMemsetAsync(at(tws, L.zero_bias), 0, 128 * 4, s));
     // d alphas: views that are never bob (view 0, views dropped by parity) and every view without the alpha residual get 0
     if (d_alphas) HRN_HIP(hipMemsetAsync(d_alphas, 0, (size_t)B * V * 4, s));
@@ -194,17 +191,17 @@ int hrnet_backward_impl(const void* pk, int dt, int scale, const hrn_hrnet_param
     // the pre-activation is recomputed into `xpre` by the forward kernel without activation - a launch that does nothing unless the
     // slope on the device says so (ConvParams::only_if_nonpos): no host round trip, ~3 us per PReLU in the usual case.
     const HrnetLayout P = hrnet_layout(dt, nl, scale);
-    float* xpre = (float*)at(tws, L.xpre);
+    void* xpre = at(tws, L.xpre);
     auto pre = [&](int cin, int cout, const void* x, const void* wpk, const float* bias, const float* slope, int Mi) -> int {
         ConvParams q = conv_base(Mi, H, W);
         q.in = x; q.out = xpre; q.wpk = wpk; q.bias = bias; q.only_if_nonpos = slope;
         q.in_lo = lo_of(dt, (size_t)Mi * hw * cin); q.out_lo = lo_of(dt, (size_t)Mi * hw * cout);
-        return hrn_launch_conv3x3(dt, cin, cout, q, s);
+        return hrn_launch_conv3x3(dt, cin, cout, q, s, false);
     };
 
     // ---- decoder: d_sr -> d stack_T (one view left)                                  HRNet.py:147-156,167-169
     // (one launch gives the weight-gradient partials and d stack_T; its finish, which only sums the partials, runs for decoder parameters)
-    float* dsn = G[0];                      // gradient of the views leaving the current level
+    void* dsn = G[0];                       // gradient of the views leaving the current level
     if (dt != HRN_F32) {
         // the decoder's backward is the fp32 kernel (33 MB of state at the training shape): the fused state as f32, its gradient back as planes
         const size_t nf = (size_t)B * L.n_in[L.T] * hw * 64;
@@ -216,7 +213,7 @@ int hrnet_backward_impl(const void* pk, int dt, int scale, const hrn_hrnet_param
                                          scale)))
             return rc;
         if (need_ds[L.T] && (rc = hrn_launch_f32_to_planes(fg, dsn, lo_of(dt, nf), nf, s))) return rc;
-    } else if ((rc = hrn_launch_decoder_bwd((const float*)at(tws, L.stack[L.T]), d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, dsn,
+    } else if ((rc = hrn_launch_decoder_bwd((const float*)at(tws, L.stack[L.T]), d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, (float*)dsn,
                                             mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a), mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s,
                                             scale)))
         return rc;
@@ -232,30 +229,30 @@ int hrnet_backward_impl(const void* pk, int dt, int scale, const hrn_hrnet_param
         const int n = L.n_in[t], half = n / 2, pair_last = n - (n & 1) - 1, Mh = B * half;
         const bool below = need_ds[t];
         const bool prA = below || wA, prB = prA || wB, dgC = prB || below, prC = dgC || wC;
-        const float* st = (const float*)at(tws, L.stack[t]);
+        const void* st = at(tws, L.stack[t]);
         // every G buffer holds B*V*hw*64 floats; Mh <= B*V/2, so one buffer also holds an [Mh][hw][128] tensor
-        float* y1 = G[1];                   // d t2               [Mh][hw][128]; dead before ds is written into the same buffer
-        float* ds = G[1];                   // gradient of the views entering the level  [B*n][hw][64]
-        float* x1 = G[2];                   // df / gC            [Mh][hw][64]
-        float* y3 = G[3];                   // d t1 / gA          [Mh][hw][128]
-        float* y2 = G[4];                   // gB, later dz       [Mh][hw][128]
-        if (prC && (rc = hrn_launch_fuse_df(dsn, alphas, V, pair_last, half, alpha_residual, x1, hw, B, s, dt))) return rc;
+        void* y1 = G[1];                   // d t2               [Mh][hw][128]; dead before ds is written into the same buffer
+        void* ds = G[1];                   // gradient of the views entering the level  [B*n][hw][64]
+        void* x1 = G[2];                   // df / gC            [Mh][hw][64]
+        void* y3 = G[3];                   // d t1 / gA          [Mh][hw][128]
+        void* y2 = G[4];                   // gB, later dz       [Mh][hw][128]
+        if (prC && (rc = hrn_launch_fuse_df(dt, dsn, alphas, V, pair_last, half, alpha_residual, x1, hw, B, s))) return rc;
         // x_new = alice + a_bob f: d a_bob = sum dsn f while both are live (the scratch is free until the PReLU backward below)
-        if (alpha && (rc = hrn_launch_alpha_grad(dsn, (const float*)at(tws, L.f[t]), half, pair_last, d_alphas, B, V, hw, sc, L.dec_f - L.scratch, s, dt)))
+        if (alpha && (rc = hrn_launch_alpha_grad(dt, dsn, at(tws, L.f[t]), half, pair_last, d_alphas, B, V, hw, sc, L.dec_f - L.scratch, s)))
             return rc;
         // f = PReLU(convC(t2))
         if (prC) {
             if ((rc = pre(128, 64, at(tws, L.t2[t]), at(pk, P.fout_w), (const float*)at(pk, P.fout_b), Pr->fuse_out_a, Mh))) return rc;
-            if ((rc = hrn_launch_prelu_bwd_bias(x1, (const float*)at(tws, L.f[t]), xpre, Pr->fuse_out_a, x1, (size_t)Mh * hw, 64, mut(Gr->fuse_out_a), mut(Gr->fuse_out_b), sc, s, dt))) return rc;
+            if ((rc = hrn_launch_prelu_bwd_bias(dt, x1, at(tws, L.f[t]), xpre, Pr->fuse_out_a, x1, (size_t)Mh * hw, 64, mut(Gr->fuse_out_a), mut(Gr->fuse_out_b), sc, s))) return rc;
         }
-        if (want(Gr->fuse_out_w) && (rc = conv_wgrad(dt, (const float*)at(tws, L.t2[t]), nullptr, 0, 0, 0, B, x1, Mh, H, W, 128, 64, mut(Gr->fuse_out_w), sc, cus, s))) return rc;
+        if (want(Gr->fuse_out_w) && (rc = hrn_launch_conv_wgrad(dt, at(tws, L.t2[t]), nullptr, 0, 0, 0, 0, x1, Mh, H, W, 128, 64, mut(Gr->fuse_out_w), sc, cus, s))) return rc;
         if (dgC && (rc = conv_dgrad(dt, 128, 64, Pr->fuse_out_w, x1, y1, nullptr, Mh, H, W, tws, L, s))) return rc;
         // t2 = z + u, u = PReLU(convB(t1))
         if (prB) {
             if ((rc = pre(128, 128, at(tws, L.t1[t]), at(pk, P.fres_w[1]), (const float*)at(pk, P.fres_b[1]), Pr->fuse_res_a[1], Mh))) return rc;
-            if ((rc = hrn_launch_prelu_bwd_bias(y1, (const float*)at(tws, L.u[t]), xpre, Pr->fuse_res_a[1], y2, (size_t)Mh * hw, 128, mut(Gr->fuse_res_a[1]), mut(Gr->fuse_res_b[1]), sc, s, dt))) return rc;
+            if ((rc = hrn_launch_prelu_bwd_bias(dt, y1, at(tws, L.u[t]), xpre, Pr->fuse_res_a[1], y2, (size_t)Mh * hw, 128, mut(Gr->fuse_res_a[1]), mut(Gr->fuse_res_b[1]), sc, s))) return rc;
         }
-        if (want(Gr->fuse_res_w[1]) && (rc = conv_wgrad(dt, (const float*)at(tws, L.t1[t]), nullptr, 0, 0, 0, B, y2, Mh, H, W, 128, 128, mut(Gr->fuse_res_w[1]), sc, cus, s))) return rc;
+        if (want(Gr->fuse_res_w[1]) && (rc = hrn_launch_conv_wgrad(dt, at(tws, L.t1[t]), nullptr, 0, 0, 0, 0, y2, Mh, H, W, 128, 128, mut(Gr->fuse_res_w[1]), sc, cus, s))) return rc;
         if (prA && (rc = conv_dgrad(dt, 128, 128, Pr->fuse_res_w[1], y2, y3, nullptr, Mh, H, W, tws, L, s))) return rc;
         // t1 = PReLU(convA(z))
         if (prA) {
@@ -263,27 +260,27 @@ int hrnet_backward_impl(const void* pk, int dt, int scale, const hrn_hrnet_param
             q.in_pair = 1; q.stack = st; q.pair_h = half; q.pair_last = pair_last; q.pair_vs = n;
             q.out = xpre; q.wpk = at(pk, P.fres_w[0]); q.bias = (const float*)at(pk, P.fres_b[0]); q.only_if_nonpos = Pr->fuse_res_a[0];
             q.stack_lo = lo_of(dt, (size_t)B * n * hw * 64); q.out_lo = lo_of(dt, (size_t)Mh * hw * 128);
-            if ((rc = hrn_launch_conv3x3(dt, 128, 128, q, s))) return rc;
-            if ((rc = hrn_launch_prelu_bwd_bias(y3, (const float*)at(tws, L.t1[t]), xpre, Pr->fuse_res_a[0], y3, (size_t)Mh * hw, 128, mut(Gr->fuse_res_a[0]), mut(Gr->fuse_res_b[0]), sc, s, dt))) return rc;
+            if ((rc = hrn_launch_conv3x3(dt, 128, 128, q, s, false))) return rc;
+            if ((rc = hrn_launch_prelu_bwd_bias(dt, y3, at(tws, L.t1[t]), xpre, Pr->fuse_res_a[0], y3, (size_t)Mh * hw, 128, mut(Gr->fuse_res_a[0]), mut(Gr->fuse_res_b[0]), sc, s))) return rc;
         }
-        if (want(Gr->fuse_res_w[0]) && (rc = conv_wgrad(dt, nullptr, st, half, pair_last, n, B, y3, Mh, H, W, 128, 128, mut(Gr->fuse_res_w[0]), sc, cus, s))) return rc;
+        if (want(Gr->fuse_res_w[0]) && (rc = hrn_launch_conv_wgrad(dt, nullptr, st, 1, half, pair_last, n, y3, Mh, H, W, 128, 128, mut(Gr->fuse_res_w[0]), sc, cus, s))) return rc;
         if (!below) continue;               // (then no level below and not the encoder reads ds: the levels left run only their alpha_grad)
         if ((rc = conv_dgrad(dt, 128, 128, Pr->fuse_res_w[0], y3, y2, y1, Mh, H, W, tws, L, s))) return rc;     // dz = d t2 + dgradA(gA)
         // dz -> the two views of each pair (+ the alice pass-through)
-        if ((rc = hrn_launch_fuse_scatter(dsn, y2, n, half, pair_last, alpha_residual, ds, hw, B, s, dt))) return rc;
-        float* tmp = G[0]; G[0] = G[1]; G[1] = tmp;
+        if ((rc = hrn_launch_fuse_scatter(dt, dsn, y2, n, half, pair_last, alpha_residual, ds, hw, B, s))) return rc;
+        void* tmp = G[0]; G[0] = G[1]; G[1] = tmp;
         dsn = G[0];
     }
     if (!need_ds[0]) return 0;
 
     // ---- encoder                                                                     HRNet.py:51-60,62-74
-    float* dA = G[1];
-    if (want(Gr->enc_final_w) && (rc = conv_wgrad(dt, (const float*)at(tws, L.a[nl]), nullptr, 0, 0, 0, B, dsn, M, H, W, 64, 64, mut(Gr->enc_final_w), sc, cus, s))) return rc;
-    if (want(Gr->enc_final_b) && (rc = hrn_launch_colsum(dsn, (size_t)M * hw, 64, mut(Gr->enc_final_b), sc, s, dt))) return rc;
+    void* dA = G[1];
+    if (want(Gr->enc_final_w) && (rc = hrn_launch_conv_wgrad(dt, at(tws, L.a[nl]), nullptr, 0, 0, 0, 0, dsn, M, H, W, 64, 64, mut(Gr->enc_final_w), sc, cus, s))) return rc;
+    if (want(Gr->enc_final_b) && (rc = hrn_launch_colsum(dt, dsn, (size_t)M * hw, 64, mut(Gr->enc_final_b), sc, s))) return rc;
     if (!need_da[nl]) return 0;
     if ((rc = conv_dgrad(dt, 64, 64, Pr->enc_final_w, dsn, dA, nullptr, M, H, W, tws, L, s))) return rc;
-    float* e2 = G[2];
-    float* e3 = G[3];
+    void* e2 = G[2];
+    void* e3 = G[3];
     for (int l = nl - 1; l >= 0; --l) {
         // a_{l+1} = a_l + r_l,  r_l = PReLU(conv2(h_l)),  h_l = PReLU(conv1(a_l));  d a_{l+1} (dA) is wanted here
         const int j1 = 2 * l, j2 = 2 * l + 1;
@@ -291,56 +288,27 @@ int hrnet_backward_impl(const void* pk, int dt, int scale, const hrn_hrnet_param
         const bool pr2 = pr1 || want_prelu(Gr->enc_res_w[j2], Gr->enc_res_b[j2], Gr->enc_res_a[j2]);
         if (pr2) {
             if ((rc = pre(64, 64, at(tws, L.h[l]), at(pk, P.enc_w[j2]), (const float*)at(pk, P.enc_b[j2]), Pr->enc_res_a[j2], M))) return rc;
-            if ((rc = hrn_launch_prelu_bwd_bias(dA, (const float*)at(tws, L.r[l]), xpre, Pr->enc_res_a[j2], e2, (size_t)M * hw, 64, mut(Gr->enc_res_a[j2]), mut(Gr->enc_res_b[j2]), sc, s, dt))) return rc;
+            if ((rc = hrn_launch_prelu_bwd_bias(dt, dA, at(tws, L.r[l]), xpre, Pr->enc_res_a[j2], e2, (size_t)M * hw, 64, mut(Gr->enc_res_a[j2]), mut(Gr->enc_res_b[j2]), sc, s))) return rc;
         }
-        if (want(Gr->enc_res_w[j2]) && (rc = conv_wgrad(dt, (const float*)at(tws, L.h[l]), nullptr, 0, 0, 0, B, e2, M, H, W, 64, 64, mut(Gr->enc_res_w[j2]), sc, cus, s))) return rc;
+        if (want(Gr->enc_res_w[j2]) && (rc = hrn_launch_conv_wgrad(dt, at(tws, L.h[l]), nullptr, 0, 0, 0, 0, e2, M, H, W, 64, 64, mut(Gr->enc_res_w[j2]), sc, cus, s))) return rc;
         if (pr1) {
             if ((rc = conv_dgrad(dt, 64, 64, Pr->enc_res_w[j2], e2, e3, nullptr, M, H, W, tws, L, s))) return rc;
             if ((rc = pre(64, 64, at(tws, L.a[l]), at(pk, P.enc_w[j1]), (const float*)at(pk, P.enc_b[j1]), Pr->enc_res_a[j1], M))) return rc;
-            if ((rc = hrn_launch_prelu_bwd_bias(e3, (const float*)at(tws, L.h[l]), xpre, Pr->enc_res_a[j1], e3, (size_t)M * hw, 64, mut(Gr->enc_res_a[j1]), mut(Gr->enc_res_b[j1]), sc, s, dt))) return rc;
+            if ((rc = hrn_launch_prelu_bwd_bias(dt, e3, at(tws, L.h[l]), xpre, Pr->enc_res_a[j1], e3, (size_t)M * hw, 64, mut(Gr->enc_res_a[j1]), mut(Gr->enc_res_b[j1]), sc, s))) return rc;
         }
-        if (want(Gr->enc_res_w[j1]) && (rc = conv_wgrad(dt, (const float*)at(tws, L.a[l]), nullptr, 0, 0, 0, B, e3, M, H, W, 64, 64, mut(Gr->enc_res_w[j1]), sc, cus, s))) return rc;
+        if (want(Gr->enc_res_w[j1]) && (rc = hrn_launch_conv_wgrad(dt, at(tws, L.a[l]), nullptr, 0, 0, 0, 0, e3, M, H, W, 64, 64, mut(Gr->enc_res_w[j1]), sc, cus, s))) return rc;
         if (!need_da[l]) return 0;
         if ((rc = conv_dgrad(dt, 64, 64, Pr->enc_res_w[j1], e3, e2, dA, M, H, W, tws, L, s))) return rc;       // d a_l = d a_{l+1} + dgrad1(g1)
-        float* tmp = dA; dA = e2; e2 = tmp;
+        void* tmp = dA; dA = e2; e2 = tmp;
     }
     // stem: a_0 = PReLU(conv(cat(view, reference frame)))                               HRNet.py:200-204, :51-53
-    if ((rc = hrn_launch_stem_pre(lrs, hw, (const float*)at(tws, L.ref), V, hw, (const float*)at(pk, P.stem_w), (const float*)at(pk, P.stem_b), xpre, M, H, W,
-                                  Pr->enc_init_a, s, dt))) return rc;
-    if ((rc = hrn_launch_prelu_bwd_bias(dA, (const float*)at(tws, L.a[0]), xpre, Pr->enc_init_a, dA, (size_t)M * hw, 64, mut(Gr->enc_init_a), mut(Gr->enc_init_b), sc, s, dt))) return rc;
-    if (want(Gr->enc_init_w) && (rc = hrn_launch_stem_wgrad(lrs, hw, (const float*)at(tws, L.ref), V, hw, dA, M, H, W, mut(Gr->enc_init_w), sc, cus, s, dt))) return rc;
+    if ((rc = hrn_launch_stem_pre(dt, lrs, hw, (const float*)at(tws, L.ref), V, hw, (const float*)at(pk, P.stem_w), (const float*)at(pk, P.stem_b), xpre, M, H, W,
+                                  Pr->enc_init_a, s))) return rc;
+    if ((rc = hrn_launch_prelu_bwd_bias(dt, dA, at(tws, L.a[0]), xpre, Pr->enc_init_a, dA, (size_t)M * hw, 64, mut(Gr->enc_init_a), mut(Gr->enc_init_b), sc, s))) return rc;
+    if (want(Gr->enc_init_w) && (rc = hrn_launch_stem_wgrad(dt, lrs, hw, (const float*)at(tws, L.ref), V, hw, dA, M, H, W, mut(Gr->enc_init_w), sc, cus, s))) return rc;
     // d lrs: the stem's input gradient, channel 1 (the reference frame) routed to the view the median picked
-    if (d_lrs) return hrn_launch_stem_dgrad_route(dA, Pr->enc_init_w, (float*)at(tws, L.wt), lrs, (const float*)at(tws, L.ref), d_lrs, B, V, H, W, s, dt);
+    if (d_lrs) return hrn_launch_stem_dgrad_route(dt, dA, Pr->enc_init_w, (float*)at(tws, L.wt), lrs, (const float*)at(tws, L.ref), d_lrs, B, V, H, W, s);
     return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t hrn_hrnet_train_workspace_bytes(int num_layers, int B, int V, int H, int W) {
-    if (num_layers < 0 || num_layers > HRN_MAX_RES_LAYERS || B <= 0 || V <= 0 || H <= 0 || W <= 0 || V >= (1 << TMAX)) return 0;
-    return train_ws(num_layers, B, V, H, W).total;
-}
-
-int hrn_hrnet_forward_train(const void* pk, int nl, int alpha_residual, const float* lrs, const float* alphas, int B, int V, int H, int W,
-                            float* sr, void* tws, size_t tws_bytes, void* stream) {
-    return hrn_hrnet_forward_train_s(pk, HRN_F32, nl, 3, alpha_residual, lrs, alphas, B, V, H, W, sr, tws, tws_bytes, stream);
-}
-
-int hrn_hrnet_backward(const void* pk, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas, int B, int V,
-                       int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, void* tws, size_t tws_bytes, void* stream) {
-    return hrn_hrnet_backward_s(pk, HRN_F32, 3, Pr, alpha_residual, lrs, alphas, B, V, H, W, d_sr, Gr, tws, tws_bytes, stream);
-}
-
-int hrn_hrnet_forward_train_dt(const void* pk, int dt, int nl, int alpha_residual, const float* lrs, const float* alphas, int B, int V, int H,
-                               int W, float* sr, void* tws, size_t tws_bytes, void* stream) {
-    return hrn_hrnet_forward_train_s(pk, dt, nl, 3, alpha_residual, lrs, alphas, B, V, H, W, sr, tws, tws_bytes, stream);
-}
-
-int hrn_hrnet_backward_dt(const void* pk, int dt, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas, int B,
-                          int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, void* tws, size_t tws_bytes, void* stream) {
-    return hrn_hrnet_backward_s(pk, dt, 3, Pr, alpha_residual, lrs, alphas, B, V, H, W, d_sr, Gr, tws, tws_bytes, stream);
 }
 
 int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alpha_residual, const float* lrs, const float* alphas, int B, int V,
@@ -366,56 +334,38 @@ int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alp
                            (const float*)at(pk, P.enc_a[2 * l]), M, H, W, s))) return rc;
         if ((rc = conv_fwd(dt, 64, 64, at(tws, L.h[l]), at(tws, L.r[l]), at(pk, P.enc_w[2 * l + 1]), (const float*)at(pk, P.enc_b[2 * l + 1]),
                            (const float*)at(pk, P.enc_a[2 * l + 1]), M, H, W, s))) return rc;
-        if ((rc = hrn_launch_add((const float*)at(tws, L.a[l]), (const float*)at(tws, L.r[l]), (float*)at(tws, L.a[l + 1]),
-                                 (size_t)M * hw * 64, s, dt))) return rc;
+        if ((rc = hrn_launch_add(dt, at(tws, L.a[l]), at(tws, L.r[l]), at(tws, L.a[l + 1]), (size_t)M * hw * 64, s))) return rc;
     }
     if ((rc = conv_fwd(dt, 64, 64, at(tws, L.a[nl]), at(tws, L.stack[0]), at(pk, P.encf_w), (const float*)at(pk, P.encf_b), nullptr, M, H, W, s)))
         return rc;
     for (int t = 0; t < L.T; ++t) {
         const int n = L.n_in[t], half = n / 2, pair_last = n - (n & 1) - 1;
-        const float* st = (const float*)at(tws, L.stack[t]);
+        const void* st = at(tws, L.stack[t]);
         ConvParams a = conv_base(B * half, H, W);
         a.in_pair = 1; a.stack = st; a.pair_h = half; a.pair_last = pair_last; a.pair_vs = n;
         a.out = at(tws, L.t1[t]);
         a.stack_lo = lo_of(dt, (size_t)B * n * hw * 64); a.out_lo = lo_of(dt, (size_t)B * half * hw * 128);
         a.wpk = at(pk, P.fres_w[0]); a.bias = (const float*)at(pk, P.fres_b[0]); a.slope = (const float*)at(pk, P.fres_a[0]);
-        if ((rc = hrn_launch_conv3x3(dt, 128, 128, a, s))) return rc;
+        if ((rc = hrn_launch_conv3x3(dt, 128, 128, a, s, false))) return rc;
         if ((rc = conv_fwd(dt, 128, 128, at(tws, L.t1[t]), at(tws, L.u[t]), at(pk, P.fres_w[1]), (const float*)at(pk, P.fres_b[1]),
                            (const float*)at(pk, P.fres_a[1]), B * half, H, W, s))) return rc;
         {
             const size_t total4 = (size_t)B * half * hw * 32;
             size_t grid = (total4 + 255) / 256;
             if (grid > 4096) grid = 4096;
-            HRN_LAUNCH_ST(dt, pair_add_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const void*)st, n, half, pair_last, (const void*)at(tws, L.u[t]),
-                          (void*)at(tws, L.t2[t]), hw, B);
+            HRN_LAUNCH_ST(dt, pair_add_kernel, dim3((unsigned)grid), dim3(256), 0, s, st, n, half, pair_last, at(tws, L.u[t]), at(tws, L.t2[t]),
+                          hw, B);
             HRN_LAUNCH_CHECK();
         }
         if ((rc = conv_fwd(dt, 128, 64, at(tws, L.t2[t]), at(tws, L.f[t]), at(pk, P.fout_w), (const float*)at(pk, P.fout_b),
                            (const float*)at(pk, P.fout_a), B * half, H, W, s))) return rc;
-        if ((rc = hrn_launch_fuse_update(st, n, (const float*)at(tws, L.f[t]), alphas, V, pair_last, half, alpha_residual,
-                                         (float*)at(tws, L.stack[t + 1]), hw, B, s, dt))) return rc;
+        if ((rc = hrn_launch_fuse_update(dt, st, n, at(tws, L.f[t]), alphas, V, pair_last, half, alpha_residual,
+                                         at(tws, L.stack[t + 1]), hw, B, s))) return rc;
     }
     // views left after the last level: 1 (or V itself for V == 1); torch.mean over them (HRNet.py:134) is the identity
     return hrn_launch_decoder(dt, at(tws, L.stack[L.T]), at(pk, P.dec_w), (const float*)at(pk, P.dec_b), (const float*)at(pk, P.dec_a),
                               (const float*)at(pk, P.fin_w), (const float*)at(pk, P.fin_b), sr, B, H, W, s,
                               lo_of(dt, (size_t)B * L.n_in[L.T] * hw * 64), scale);
-}
-
-int hrn_hrnet_backward_s(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
-                         int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, void* tws, size_t tws_bytes, void* stream) {
-    return hrn_hrnet_backward_in(pk, dt, scale, Pr, alpha_residual, lrs, alphas, B, V, H, W, d_sr, Gr, nullptr, nullptr, tws, tws_bytes, stream);
-}
-
-int hrn_hrnet_backward_in(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
-                          int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, float* d_lrs, float* d_alphas, void* tws,
-                          size_t tws_bytes, void* stream) {
-    return hrnet_backward_impl(pk, dt, scale, Pr, alpha_residual, lrs, alphas, B, V, H, W, d_sr, Gr, d_lrs, d_alphas, tws, tws_bytes, stream, false);
-}
-
-int hrn_hrnet_backward_sel(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
-                           int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, float* d_lrs, float* d_alphas, void* tws,
-                           size_t tws_bytes, void* stream) {
-    return hrnet_backward_impl(pk, dt, scale, Pr, alpha_residual, lrs, alphas, B, V, H, W, d_sr, Gr, d_lrs, d_alphas, tws, tws_bytes, stream, true);
 }
 
 }  // extern "C"

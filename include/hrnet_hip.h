@@ -177,7 +177,8 @@ int hrn_hrnet_backward_in(const void* packed, int dtype, int scale, const hrn_hr
  * Decoder parameters need the decoder's weight-gradient part alone; any fusion parameter (shared by every level), or d_alphas with the
  * alpha residual, the data gradients of the decoder and of the fusion levels; encoder / stem parameters or d_lrs the chain down to the
  * stem.  Every requested gradient, d_lrs and d_alphas is bit-identical to what hrn_hrnet_backward_in gives with every field set, which
- * is also what this entry point runs then.  Same arguments, checks, workspace and return codes as hrn_hrnet_backward_in. */
+ * is also what this entry point runs then.  Same arguments, checks, workspace and return codes as hrn_hrnet_backward_in.  The other
+ * hrn_hrnet_backward* forms are this function with arguments fixed, so they treat a NULL field of `grads` the same way. */
 int hrn_hrnet_backward_sel(const void* packed, int dtype, int scale, const hrn_hrnet_params* params, int alpha_residual, const float* lrs,
                            const float* alphas, int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* grads,
                            float* d_lrs, float* d_alphas, void* train_ws, size_t train_ws_bytes, void* stream);
@@ -238,7 +239,8 @@ int hrn_shiftnet_backward_dt(const hrn_shiftnet_params* params, int dtype, const
 /* hrn_shiftnet_backward_dt for a partly frozen ShiftNet: a NULL field of `grads` means "not requested" (`grads` itself must not be NULL).
  * A frozen layer's weight / bias gradients and a frozen fc1.weight / fc1.bias / fc2.weight are not computed; the walk back stops at the
  * first layer (from the input) below which nothing is requested, with d_x NULL.  Requested gradients and d_x are bit-identical to the
- * full backward's.  Same arguments, checks, workspace and return codes as hrn_shiftnet_backward_dt. */
+ * full backward's.  Same arguments, checks, workspace and return codes as hrn_shiftnet_backward_dt.  The other hrn_shiftnet_backward*
+ * forms are this function with the dtype fixed or passed on, so they treat a NULL field of `grads` the same way. */
 int hrn_shiftnet_backward_sel(const hrn_shiftnet_params* params, int dtype, const float* x, int B, const unsigned char* dropout_mask,
                               const float* d_theta, const hrn_shiftnet_params* grads, float* d_x, void* train_ws, size_t train_ws_bytes,
                               void* stream);
