@@ -13,6 +13,14 @@ Target scale: HR / SM batches are `scale * S` a side for LR patches of side S, `
 argument, else config["scale"], else 3).  The patch corner is always drawn in LR pixels, so a seeded run picks the same views and
 corner at every scale.  The host path reads files stored at that ratio and never resamples; the device cache can resample
 HR / SM stored at another ratio once, when it is built (`to_device(resample_targets=True)`, hrnet_hip/resample.py).
+
+Augmentation (`augment`, else config["augment"]; off by default): "flip" or "dihedral" draws one code per imageset - one of the
+4 flips or of all 8 flips and rotations of the square (hrnet_hip/augment.py) - and applies it to the cropped window of every LR
+view and of HR / SM.  The draw is one extra `np.random.randint(0, MODES[mode])` per imageset, after `_pick_views` and `_corner`
+(after `_pick_views` alone when no patches are cut), re-seeded like `_corner` when `seed` is set: a seeded run picks the same
+views and corner with or without it, and with augmentation off no RNG call is added anywhere.  The transform is an addressing
+change inside the gathers that run anyway (hrn_io_collate_a on the host, hrn_collate_device_a in the cache); the codes of the last
+batch are kept in `last_augment` so that a caller can undo them (`augment.inverse`).
 """
 from collections import OrderedDict
 import operator
@@ -23,6 +31,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
+from hrnet_hip import augment as _augment
 from hrnet_hip import binding, io_binding, resample
 from hrnet_hip.resample import check_scale
 
@@ -97,17 +106,26 @@ def _corner(lr_side, patch_size, seed):
     return row, col
 
 
+def _draw_code(mode, seed):
+    """Augmentation code of one imageset: an optional re-seed (as _corner), then one `np.random.randint(0, MODES[mode])`."""
+    if seed is not None:
+        np.random.seed(seed)
+    return int(np.random.randint(low=0, high=_augment.MODES[mode]))
+
+
 def _ratio_error(name, lr_side, scale, found):
     """The ValueError for an imageset whose HR / SM files are not `scale` times its LR side."""
     return ValueError(f"{name}: HR / SM side is {found} but scale {scale} needs {scale * lr_side} ({scale} x the LR side {lr_side}); the host "
                       f"path does not resample - build a device cache with to_device(resample_targets=True)")
 
 
-def read_imageset(imset_dir, create_patches=False, patch_size=64, seed=None, top_k=None, beta=0., scale=3):
+def read_imageset(imset_dir, create_patches=False, patch_size=64, seed=None, top_k=None, beta=0., scale=3, augment=None):
     """ImageSet(name, lr uint16 (L,H,W), hr uint16 or None, hr_map bool, clearances) of one imageset directory, PNGs decoded by
     the native reader.  With `create_patches` one random `patch_size` window is cut from every LR view and the matching
-    `scale`x window from SM / HR, whose files must be `scale` times the LR side (ValueError otherwise)."""
+    `scale`x window from SM / HR, whose files must be `scale` times the LR side (ValueError otherwise).  `augment` (a mode of
+    hrnet_hip/augment.py): one code is drawn after the views and the corner and applied to lr, hr_map and hr."""
     scale = check_scale(scale)
+    mode = _augment.check_mode(augment)
     ids, scores = _views_in_use_order(imset_dir, top_k, beta, seed)
     asset = lambda name: os.path.join(imset_dir, name)
     lr = np.stack([io_binding.png_read(asset(f"LR{i}.png")) for i in ids]).astype(np.uint16, copy=False)
@@ -122,6 +140,11 @@ def read_imageset(imset_dir, create_patches=False, patch_size=64, seed=None, top
         hr_map = get_patch(hr_map, scale * row, scale * col, scale * patch_size)
         if hr is not None:
             hr = get_patch(hr, scale * row, scale * col, scale * patch_size)
+    if mode is not None:
+        code = _draw_code(mode, seed)
+        lr, hr_map = _augment.apply(lr, code), np.ascontiguousarray(_augment.apply(hr_map, code))
+        if hr is not None:
+            hr = np.ascontiguousarray(_augment.apply(hr, code))
     return ImageSet(name=os.path.basename(imset_dir), lr=np.array(lr), hr=hr, hr_map=hr_map, clearances=scores)
 
 
@@ -129,11 +152,16 @@ class ImagesetDataset(Dataset):
     """Dataset over imageset directories.  `dataset[i]` (int), `dataset["imgsetXXXX"]` (name) -> one ImageSet of float32
     tensors (lr (L,S,S), hr / hr_map (kS,kS) with k = `scale`; test imagesets keep hr = None and a bool numpy hr_map); a slice
     -> a list.  `scale` (2, 3 or 4; None: config.get("scale", 3)) is the HR / LR ratio of the batches and, on this host path, of
-    the files."""
+    the files.  `augment` (None: config.get("augment"); then None / False / "none" off, "flip", "dihedral" or True): one flip /
+    rotation code per imageset (module docstring); `last_augment` holds the codes of the last item or batch loaded (a list of
+    ints, None while augmentation is off).  None defers to the config, so a dataset built from a config that carries the key
+    is switched off with `augment=False`."""
 
-    def __init__(self, imset_dir, config, seed=None, top_k=-1, beta=0., scale=None):
+    def __init__(self, imset_dir, config, seed=None, top_k=-1, beta=0., scale=None, augment=None):
         super().__init__()
         self.scale = check_scale(config.get("scale", 3) if scale is None else scale)
+        self.augment = _augment.check_mode(config.get("augment") if augment is None else augment)
+        self.last_augment = None
         self.imset_dir = imset_dir
         self.name_to_dir = dict(zip(map(os.path.basename, imset_dir), imset_dir))
         self.create_patches, self.patch_size = config["create_patches"], config["patch_size"]
@@ -164,9 +192,15 @@ class ImagesetDataset(Dataset):
         lr_paths = [os.path.join(dir_, f"LR{i}.png") for i in idx_names]
         lr_side = io_binding.png_info(lr_paths[0])[0]
         corner = _corner(lr_side, self.patch_size, self.seed) if self.create_patches else (0, 0)
+        code = _draw_code(self.augment, self.seed) if self.augment is not None else None
         hr_path = os.path.join(dir_, "HR.png") if os.path.exists(os.path.join(dir_, "HR.png")) else None
         return dict(name=os.path.basename(dir_), lr_paths=lr_paths, clearances=clearances, lr_side=lr_side, corner=corner, hr=hr_path,
-                    sm=os.path.join(dir_, "SM.png"))
+                    sm=os.path.join(dir_, "SM.png"), code=code)
+
+    def _codes(self, plans):
+        """Codes of a batch for io_binding.collate (None while augmentation is off), recorded in `last_augment`."""
+        self.last_augment = [p["code"] for p in plans] if self.augment is not None else None
+        return self.last_augment
 
     def _collate(self, plans, **kw):
         """io_binding.collate at the dataset's scale.  A failure is looked at only after the fact (no extra file read on the
@@ -186,7 +220,7 @@ class ImagesetDataset(Dataset):
         pl = self._plan(dir_)
         patch = self.patch_size if self.create_patches else 0
         out = self._collate([pl], lr_paths_per_set=[pl["lr_paths"]], hr_paths=[pl["hr"]], sm_paths=[pl["sm"]], min_L=len(pl["lr_paths"]),
-                            lr_size=pl["lr_side"], patch=patch, corners=[pl["corner"]])
+                            lr_size=pl["lr_side"], patch=patch, corners=[pl["corner"]], codes=self._codes([pl]))
         labelled = pl["hr"] is not None
         return ImageSet(name=pl["name"], lr=torch.from_numpy(out["lrs"][0]), hr=torch.from_numpy(out["hrs"][0]) if labelled else None,
                         hr_map=torch.from_numpy(out["maps"][0]) if labelled else out["maps"][0].astype(bool), clearances=pl["clearances"])
@@ -207,7 +241,7 @@ class ImagesetDataset(Dataset):
         out = dict(lrs=mk(B, min_L, S, S), alphas=mk(B, min_L), hrs=mk(B, T, T) if have_hr else None, maps=mk(B, T, T))
         self._collate(plans, lr_paths_per_set=[p["lr_paths"] for p in plans], hr_paths=[p["hr"] for p in plans] if have_hr else None,
                       sm_paths=[p["sm"] for p in plans], min_L=min_L, lr_size=side, patch=patch, corners=[p["corner"] for p in plans], out=out,
-                      n_threads=n_threads)
+                      n_threads=n_threads, codes=self._codes(plans))
         return out["lrs"], out["alphas"], out["hrs"] if have_hr else [], out["maps"], [p["name"] for p in plans]
 
 
@@ -230,7 +264,7 @@ class ImagesetIndex:
     scale^2 side^2 samples, scale = dataset.scale.  `ratios[k]` is the ratio imageset k is stored at; one that differs from
     the scale needs `resample_targets` (the cache then resamples it into its slot), else it is the host path's ValueError.
     `plan()` turns a batch of indices into the kernel's plan table with exactly the numpy RNG calls ImagesetDataset._plan makes,
-    in the same order."""
+    in the same order; `plan_a()` returns the augmentation codes of the batch beside it (`last_augment` keeps them as a list)."""
 
     def __init__(self, dataset, resample_targets=False):
         self.dataset = dataset
@@ -261,6 +295,7 @@ class ImagesetIndex:
             self.sm_off.append(sm_total)
             sm_total += _round4(scale * scale * side * side)
         self.lr_elems, self.hr_elems, self.sm_elems = lr_total, hr_total, sm_total
+        self.last_augment = None
 
     def _stored_ratio(self, d, side, have_hr, resample_targets):
         """HR / LR ratio of the files of imageset `d`, from the SM (and HR) header: the scale itself, or with `resample_targets`
@@ -284,15 +319,24 @@ class ImagesetIndex:
         return range(len(self.dirs))[index] if isinstance(index, int) else self.position[index]
 
     def plan(self, indices, min_L):
-        """-> (plan (B, COLLATE_META + min_L) int64, names, S, have_hr) for hrn_collate_device.  RNG: per imageset, in order,
-        _pick_views (sample_clearest, or the clearance sort for top_k <= 0) and then _corner, with the dataset's seed."""
+        """-> (plan (B, COLLATE_META + min_L) int64, names, S, have_hr) for hrn_collate_device: plan_a without the codes."""
+        plan, _, names, S, have_hr = self.plan_a(indices, min_L)
+        return plan, names, S, have_hr
+
+    def plan_a(self, indices, min_L):
+        """-> (plan (B, COLLATE_META + min_L) int64, codes (B,) int32 or None, names, S, have_hr) for hrn_collate_device_a.
+        RNG: per imageset, in order, _pick_views (sample_clearest, or the clearance sort for top_k <= 0), then _corner and,
+        with augmentation on, _draw_code, with the dataset's seed.  codes is None while augmentation is off."""
         ds = self.dataset
-        rows = []
+        rows, codes = [], []
         for i in indices:
             k = self.resolve(i)
             pick = _pick_views(self.clearances[k], len(self.ids[k]), ds.top_k, ds.beta, ds.seed)
             corner = _corner(self.sides[k], ds.patch_size, ds.seed) if ds.create_patches else (0, 0)
+            if ds.augment is not None:
+                codes.append(_draw_code(ds.augment, ds.seed))
             rows.append((k, pick, corner))
+        self.last_augment = codes if ds.augment is not None else None
         side = self.sides[rows[0][0]]
         if any(self.sides[k] != side for k, _, _ in rows):
             raise ValueError("imagesets of one batch must share the LR size")
@@ -305,7 +349,7 @@ class ImagesetIndex:
             plan[b, :binding.COLLATE_META] = (self.hr_off[k] if have_hr else -1, self.sm_off[k], side, row if patch else 0,
                                               col if patch else 0)
             plan[b, binding.COLLATE_META:binding.COLLATE_META + len(used)] = used
-        return plan, [self.names[k] for k, _, _ in rows], S, have_hr
+        return plan, np.asarray(codes, np.int32) if ds.augment is not None else None, [self.names[k] for k, _, _ in rows], S, have_hr
 
 
 class DeviceImagesetCache:
@@ -317,9 +361,11 @@ class DeviceImagesetCache:
 
     `load_batch` has the contract of ImagesetDataset.load_batch (same tuple, values bit-identical, hrs == [] when an imageset
     lacks HR.png, ValueError for mixed LR sizes, KeyError for an unknown name) and makes the same numpy RNG calls in the same
-    order, so a seeded run picks the same views and patches on either path.  Per batch: the plan (Python, ImagesetIndex.plan),
-    one small pinned host-to-device copy of the plan table and one kernel, all enqueued on the current stream; no
-    device-to-host copy and no synchronisation.  Memory: `nbytes` (2 B per LR / HR sample, 1 B per SM sample).
+    order, so a seeded run picks the same views, patches and (with the dataset's `augment` on) flip / rotation codes on either
+    path; `last_augment` holds the codes of the last batch (a list of ints, None while augmentation is off).  Per batch: the
+    plan (Python, ImagesetIndex.plan_a), one small pinned host-to-device copy of the plan table (the codes ride in the same
+    buffer) and one kernel, all enqueued on the current stream; no device-to-host copy and no synchronisation.  Memory: `nbytes`
+    (2 B per LR / HR sample, 1 B per SM sample).
 
     `resample_targets=True`: an imageset whose HR / SM files are stored at another ratio R than the dataset's scale is decoded
     at R into a staging buffer and resampled into its arena slot by hrn_resample_targets (hrnet_hip/resample.py gives the rule:
@@ -338,6 +384,7 @@ class DeviceImagesetCache:
         binding.load_library()
         self.index = idx = ImagesetIndex(dataset, resample_targets=resample_targets)
         self.scale = idx.scale
+        self.last_augment = None
         dev = self.device
         self.lr = torch.empty(idx.lr_elems, dtype=torch.uint16, device=dev)
         self.hr = torch.empty(idx.hr_elems, dtype=torch.uint16, device=dev) if idx.hr_elems else None
@@ -420,15 +467,25 @@ class DeviceImagesetCache:
 
     def load_batch(self, indices, min_L):
         """(lrs (B,min_L,S,S), alphas (B,min_L), hrs (B,kS,kS) or [], hr_maps (B,kS,kS), names) on the cache's device; k = scale."""
-        plan, names, S, have_hr = self.index.plan(indices, min_L)
+        plan, codes, names, S, have_hr = self.index.plan_a(indices, min_L)
+        self.last_augment = self.index.last_augment
         B = len(names)
         with torch.cuda.device(self.device):
-            plan_d = torch.from_numpy(plan).pin_memory().to(self.device, non_blocking=True)
+            codes_d = None
+            if codes is None:
+                plan_d = torch.from_numpy(plan).pin_memory().to(self.device, non_blocking=True)
+            else:                                                  # one allocation, two pointers: plan rows, then B int32 codes
+                words = plan.size
+                host = np.zeros(words + (B + 1) // 2, np.int64)
+                host[:words] = plan.ravel()
+                host[words:].view(np.int32)[:B] = codes
+                both = torch.from_numpy(host).pin_memory().to(self.device, non_blocking=True)
+                plan_d, codes_d = both[:words].view(plan.shape), both[words:].view(torch.int32)[:B]
             mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
             T = self.scale * S
             lrs, alphas, maps = mk(B, min_L, S, S), mk(B, min_L), mk(B, T, T)
             hrs = mk(B, T, T) if have_hr else None
-            binding.collate_device(self.lr, self.hr, self.sm, plan_d, S, lrs, alphas, hrs, maps, scale=self.scale)
+            binding.collate_device(self.lr, self.hr, self.sm, plan_d, S, lrs, alphas, hrs, maps, scale=self.scale, codes=codes_d)
         return lrs, alphas, hrs if have_hr else [], maps, names
 
     def batches(self, index_lists, min_L):
@@ -450,7 +507,8 @@ class BatchPrefetcher:
     on a private stream; the consumer's stream waits on that copy's event only when it takes the batch, so PCIe traffic and
     decode overlap the kernels of batch n.  Tensors are handed over with `record_stream`, i.e. their memory is not reused
     before the consumer's queued work has finished.  With device=None or "cpu" it is a plain background decoder.
-    Errors raised by the worker are re-raised in the consumer at the batch they belong to."""
+    Errors raised by the worker are re-raised in the consumer at the batch they belong to.  `last_augment` holds the augmentation
+    codes of the batch most recently handed to the consumer (the dataset's own attribute runs ahead with the worker)."""
 
     def __init__(self, dataset, batches, min_L, device=None, depth=2, n_threads=0):
         import queue
@@ -461,6 +519,7 @@ class BatchPrefetcher:
         if self.on_gpu and not torch.cuda.is_available():
             raise RuntimeError("BatchPrefetcher: device is cuda but no GPU is available")
         self.n_threads = n_threads
+        self.last_augment = None
         self._q = queue.Queue(maxsize=max(1, int(depth)))
         self._stop = threading.Event()
         self._thread = threading.Thread(target=self._work, name="hrn-batch-prefetch", daemon=True)
@@ -488,7 +547,7 @@ class BatchPrefetcher:
                                 hrs = hrs.to(self.device, non_blocking=True)
                             event = torch.cuda.Event()
                             event.record(stream)
-                    item = ("ok", (lrs, alphas, hrs, maps, names), event, stream)
+                    item = ("ok", (lrs, alphas, hrs, maps, names, getattr(self.dataset, "last_augment", None)), event, stream)
                 except Exception as exc:                     # handed to the consumer, in order
                     item = ("err", exc, None, None)
                 while not self._stop.is_set():
@@ -525,7 +584,8 @@ class BatchPrefetcher:
                     for t in payload[:4]:
                         if isinstance(t, torch.Tensor):
                             t.record_stream(cur)
-                yield payload
+                self.last_augment = payload[5]
+                yield payload[:5]
         finally:
             self.close()
 

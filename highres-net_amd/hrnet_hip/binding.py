@@ -139,6 +139,9 @@ SIGNATURES = {
     "hrn_collate_device_s": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
                                         _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                         _c.c_void_p]),
+    "hrn_collate_device_a": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                        _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                        _c.c_void_p, _c.c_void_p]),
     "hrn_resample_targets": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int,
                                         _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_profile_enable": (_c.c_int, [_c.c_int]),
@@ -564,11 +567,12 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_
 COLLATE_META = 5          # leading int64 fields of a plan row (HRN_COLLATE_META): hr_off, sm_off, side, row, col
 
 
-def collate_device(lr_arena, hr_arena, sm_arena, plan, S, lrs, alphas, hrs, maps, scale=3):
+def collate_device(lr_arena, hr_arena, sm_arena, plan, S, lrs, alphas, hrs, maps, scale=3, codes=None):
     """One launch on the current stream: gather + convert a batch from the device arenas (uint16 LR / HR, uint8 SM) into
     lrs (B,min_L,S,S), alphas (B,min_L), hrs (B,kS,kS) or None, maps (B,kS,kS) f32 with k = `scale` (2, 3 or 4: the HR / LR ratio
     the arenas are stored at), following `plan`, a device int64 (B, COLLATE_META + min_L) table (include/hrnet_hip.h,
-    hrn_collate_device_s)."""
+    hrn_collate_device_a).  `codes`: None, or a device int32 (B,) tensor of augmentation codes (hrnet_hip/augment.py), one per
+    sample; they are not read back, so a code outside 0..7 shows as NaN planes of that sample, not as an error."""
     B, min_L = alphas.shape
     use_hr = hrs is not None
     scale = check_scale(scale)
@@ -578,16 +582,20 @@ def collate_device(lr_arena, hr_arena, sm_arena, plan, S, lrs, alphas, hrs, maps
             raise RuntimeError(f"{name} must be a contiguous {dt} ROCm device tensor")
     if tuple(plan.shape) != (B, COLLATE_META + min_L):
         raise ValueError(f"plan is {tuple(plan.shape)}, expected {(B, COLLATE_META + min_L)}")
+    if codes is not None and not (isinstance(codes, torch.Tensor) and codes.is_cuda and codes.is_contiguous() and codes.dtype == torch.int32
+                                  and tuple(codes.shape) == (B,)):
+        raise ValueError(f"codes must be a contiguous int32 ROCm device tensor of shape {(B,)}")
     outs = [("lrs", lrs, (B, min_L, S, S)), ("alphas", alphas, (B, min_L)), ("maps", maps, (B, scale * S, scale * S))]
     if hrs is not None:
         outs.append(("hrs", hrs, (B, scale * S, scale * S)))
     for name, t, shape in outs:
         if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32 or tuple(t.shape) != shape:
             raise ValueError(f"{name} must be a contiguous float32 device tensor of shape {shape}")
-    _check(load_library().hrn_collate_device_s(_ptr(lr_arena), lr_arena.numel(), _ptr(hr_arena) if use_hr else None,
+    _check(load_library().hrn_collate_device_a(_ptr(lr_arena), lr_arena.numel(), _ptr(hr_arena) if use_hr else None,
                                                hr_arena.numel() if use_hr else 0, _ptr(sm_arena), sm_arena.numel(), _ptr(plan), B, min_L, S,
-                                               scale, _ptr(lrs), _ptr(alphas), _ptr(hrs) if use_hr else None, _ptr(maps), _stream()),
-           "hrn_collate_device_s")
+                                               scale, _ptr(lrs), _ptr(alphas), _ptr(hrs) if use_hr else None, _ptr(maps),
+                                               _ptr(codes) if codes is not None else None, _stream()),
+           "hrn_collate_device_a")
 
 
 RESAMPLE_TAPS = 12        # HRN_RESAMPLE_TAPS: weights per output sample in a resampling table

@@ -1,5 +1,5 @@
 // The entry points of include/hrnet_hip.h that are another entry point with an argument fixed: scale = 3, dtype = HRN_DTYPE_F32, no
-// input gradients.  Each is one `return` of the general form, which does the checking and the work (api.hip, train.hip,
+// input gradients, no augmentation codes.  Each is one `return` of the general form, which does the checking and the work (api.hip, train.hip,
 // shiftnet_bwd.hip, collate.hip).  Host code only: this file has no kernel.
 #include "../../../include/hrnet_hip.h"
 
@@ -72,7 +72,13 @@ int hrn_shiftnet_backward_dt(const hrn_shiftnet_params* P, int dt, const float* 
     return hrn_shiftnet_backward_sel(P, dt, x, B, dropout_mask, d_theta, G, d_x, tws, tws_bytes, stream);
 }
 
-// ---- input pipeline: scale = 3
+// ---- input pipeline: no augmentation codes; scale = 3
+int hrn_collate_device_s(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems, const uint8_t* sm_arena,
+                         int64_t sm_elems, const int64_t* plan, int B, int min_L, int S, int scale, float* lrs, float* alphas, float* hrs,
+                         float* maps, void* stream) {
+    return hrn_collate_device_a(lr_arena, lr_elems, hr_arena, hr_elems, sm_arena, sm_elems, plan, B, min_L, S, scale, lrs, alphas, hrs, maps,
+                                nullptr, stream);
+}
 int hrn_collate_device(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems, const uint8_t* sm_arena,
                        int64_t sm_elems, const int64_t* plan, int B, int min_L, int S, float* lrs, float* alphas, float* hrs, float* maps,
                        void* stream) {

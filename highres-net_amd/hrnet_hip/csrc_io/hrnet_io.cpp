@@ -9,6 +9,7 @@
 
 #include <atomic>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -129,6 +130,22 @@ int read_crop(const char* path, int want_w, int want_h, uint16_t* out, int r0, i
     return decode(path, png, out, r0, r1, c0, c1, pitch);
 }
 
+// One cropped n x n window -> float, with the augmentation code t applied on the way (include/hrnet_io.h, hrn_io_collate_a):
+// out[i][j] = f(win[t & 4 ? (j', i') : (i', j')]), as a start index and one stride per output axis.  Code 0 is the plain copy loop.
+template <class F>
+void convert_window(const uint16_t* win, float* out, int n, int code, F f) {
+    const bool flip_i = code & 2, flip_j = code & 1, transposed = code & 4;
+    const ptrdiff_t N = n, last_row = (N - 1) * N, last_col = N - 1;
+    const ptrdiff_t start = transposed ? (flip_j ? last_row : 0) + (flip_i ? last_col : 0) : (flip_i ? last_row : 0) + (flip_j ? last_col : 0);
+    const ptrdiff_t di = transposed ? (flip_i ? -1 : 1) : (flip_i ? -N : N), dj = transposed ? (flip_j ? -N : N) : (flip_j ? -1 : 1);
+    for (int i = 0; i < n; ++i) {
+        const uint16_t* s = win + start + i * di;
+        float* o = out + (size_t)i * n;
+        if (dj == 1) for (int j = 0; j < n; ++j) o[j] = f(s[j]);
+        else for (int j = 0; j < n; ++j) o[j] = f(s[j * dj]);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -150,10 +167,12 @@ int hrn_io_png_read_u16(const char* path, uint16_t* out, int width, int height) 
     return read_crop(path, width, height, out, 0, height, 0, width, (size_t)width);
 }
 
-int hrn_io_collate_s(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,
+int hrn_io_collate_a(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,
                      const char* const* sm_paths, int min_L, int lr_size, int patch, int scale, const int* px, const int* py,
-                     float* lrs, float* alphas, float* hrs, float* maps, int n_threads) {
+                     float* lrs, float* alphas, float* hrs, float* maps, int n_threads, const int* codes) {
     if (scale < 2 || scale > 4) { set_err("hrn_io_collate: scale must be 2, 3 or 4 (got %d)", scale); return -2; }
+    for (int s = 0; codes && s < n_sets; ++s)
+        if (codes[s] < 0 || codes[s] > 7) { set_err("hrn_io_collate: augmentation code %d of imageset %d is not in 0..7", codes[s], s); return -2; }
     if (n_sets <= 0 || !lr_paths || !n_views || !sm_paths || min_L <= 0 || lr_size <= 0 || patch < 0 || !lrs || !alphas || !maps ||
         (patch > 0 && (!px || !py)) || (hr_paths && !hrs)) {
         set_err("hrn_io_collate: bad argument");
@@ -191,21 +210,20 @@ int hrn_io_collate_s(int n_sets, const char* const* lr_paths, const int* n_views
             if (i >= items.size() || status.load() != 0) return;
             const Item& it = items[i];
             const int x = patch > 0 ? px[it.set] : 0, y = patch > 0 ? py[it.set] : 0;     // x = row corner, y = column corner
+            const int code = codes ? codes[it.set] : 0;
+            const auto as_float = [](uint16_t u) { return (float)((double)u / 65535.0); };          // img_as_float -> float32
             int rc;
             if (it.kind == 0) {
                 rc = read_crop(it.path, lr_size, lr_size, buf.data(), x, x + S, y, y + S, (size_t)S);
-                if (!rc) {
-                    float* o = lrs + ((size_t)it.set * min_L + it.slot) * S * S;
-                    for (size_t k = 0; k < (size_t)S * S; ++k) o[k] = (float)((double)buf[k] / 65535.0);   // img_as_float -> float32
-                }
+                if (!rc) convert_window(buf.data(), lrs + ((size_t)it.set * min_L + it.slot) * S * S, S, code, as_float);
             } else {
                 const int S3 = scale * S;                                                   // HR / SM side of the batch
                 rc = read_crop(it.path, scale * lr_size, scale * lr_size, buf.data(), scale * x, scale * x + S3, scale * y, scale * y + S3,
                                (size_t)S3);
                 if (!rc) {
                     float* o = (it.kind == 1 ? hrs : maps) + (size_t)it.set * S3 * S3;
-                    if (it.kind == 1) for (size_t k = 0; k < (size_t)S3 * S3; ++k) o[k] = (float)((double)buf[k] / 65535.0);
-                    else for (size_t k = 0; k < (size_t)S3 * S3; ++k) o[k] = buf[k] ? 1.f : 0.f;             // dtype=bool -> float32
+                    if (it.kind == 1) convert_window(buf.data(), o, S3, code, as_float);
+                    else convert_window(buf.data(), o, S3, code, [](uint16_t u) { return u ? 1.f : 0.f; });   // dtype=bool -> float32
                 }
             }
             if (rc) {
@@ -225,6 +243,13 @@ int hrn_io_collate_s(int n_sets, const char* const* lr_paths, const int* n_views
     for (auto& th : pool) th.join();
     if (status.load() != 0) { set_err("%s", first_error.c_str()); return status.load(); }
     return 0;
+}
+
+int hrn_io_collate_s(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,
+                     const char* const* sm_paths, int min_L, int lr_size, int patch, int scale, const int* px, const int* py,
+                     float* lrs, float* alphas, float* hrs, float* maps, int n_threads) {
+    return hrn_io_collate_a(n_sets, lr_paths, n_views, hr_paths, sm_paths, min_L, lr_size, patch, scale, px, py, lrs, alphas, hrs, maps, n_threads,
+                            nullptr);
 }
 
 int hrn_io_collate(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,

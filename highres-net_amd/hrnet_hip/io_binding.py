@@ -23,6 +23,8 @@ SIGNATURES = {
                                   _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int]),
     "hrn_io_collate_s": (_c.c_int, [_c.c_int, _pp, _ip, _pp, _pp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _ip, _ip,
                                     _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int]),
+    "hrn_io_collate_a": (_c.c_int, [_c.c_int, _pp, _ip, _pp, _pp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _ip, _ip,
+                                    _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _ip]),
     "hrn_io_read_many_u16": (_c.c_int, [_c.c_int, _pp, _c.c_void_p, _c.POINTER(_c.c_int64), _ip, _ip, _c.c_int]),
 }
 _lib = None
@@ -73,12 +75,14 @@ def _strs(paths):
     return arr
 
 
-def collate(lr_paths_per_set, hr_paths, sm_paths, min_L, lr_size, patch=0, corners=None, out=None, n_threads=0, scale=3):
+def collate(lr_paths_per_set, hr_paths, sm_paths, min_L, lr_size, patch=0, corners=None, out=None, n_threads=0, scale=3, codes=None):
     """lr_paths_per_set: list (one per imageset) of lists of LR files in use order; hr_paths: list of paths / None entries
     or None; sm_paths: list of paths; corners: list of (x, y) = (row, column) per imageset when patch > 0.
     out: optional dict of preallocated float32 buffers 'lrs' (B,min_L,S,S), 'alphas' (B,min_L), 'hrs', 'maps' (B,kS,kS) -
     numpy arrays or CPU torch tensors (e.g. pinned).  Returns that dict (numpy arrays when it allocates).
-    scale: k, the HR / LR ratio of the files (2, 3 or 4); a file of another size is an HrnetIoError that names it."""
+    scale: k, the HR / LR ratio of the files (2, 3 or 4); a file of another size is an HrnetIoError that names it.
+    codes: None, or one augmentation code per imageset (hrnet_hip/augment.py), applied to every cropped window of that imageset
+    while it is converted; a code outside 0..7 is an HrnetIoError (-2) and leaves the buffers as they were."""
     scale = check_scale(scale)
     lib = load_library()
     B = len(lr_paths_per_set)
@@ -108,10 +112,14 @@ def collate(lr_paths_per_set, hr_paths, sm_paths, min_L, lr_size, patch=0, corne
     if patch > 0:
         px = (_c.c_int * B)(*[int(c[0]) for c in corners])
         py = (_c.c_int * B)(*[int(c[1]) for c in corners])
-    _check(lib.hrn_io_collate_s(B, _strs(flat), nv, _strs(hr_paths) if have_hr else None, _strs(sm_paths), int(min_L), int(lr_size),
+    if codes is not None:
+        if len(codes) != B:
+            raise ValueError(f"codes has {len(codes)} entries for {B} imagesets")
+        codes = (_c.c_int * B)(*[int(c) for c in codes])
+    _check(lib.hrn_io_collate_a(B, _strs(flat), nv, _strs(hr_paths) if have_hr else None, _strs(sm_paths), int(min_L), int(lr_size),
                                 int(patch), scale, px, py, ptr(out["lrs"], (B, min_L, S, S)), ptr(out["alphas"], (B, min_L)),
-                                ptr(out.get("hrs") if have_hr else None, (B, T, T)), ptr(out["maps"], (B, T, T)), int(n_threads)),
-           "hrn_io_collate_s")
+                                ptr(out.get("hrs") if have_hr else None, (B, T, T)), ptr(out["maps"], (B, T, T)), int(n_threads), codes),
+           "hrn_io_collate_a")
     return out
 
 

@@ -23,6 +23,8 @@
  *   hrn_collate_device     <-  collateFunction(min_L) over ImagesetDataset items (src/utils.py:63-113), gathered from
  *                              imagesets decoded once into HBM (DataLoader.DeviceImagesetCache); hrn_collate_device_s
  *                              is the same for x2 / x3 / x4 targets
+ *   hrn_collate_device_a   <-  (no counterpart: the reference trains without augmentation) the same gather with one of the
+ *                              eight flips / rotations of the square applied per sample
  *   hrn_resample_targets   <-  (no counterpart) HR / SM stored at one ratio resampled to another when the cache is built
  *
  * Conventions
@@ -311,6 +313,17 @@ int hrn_collate_device(const uint16_t* lr_arena, int64_t lr_elems, const uint16_
 int hrn_collate_device_s(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems,
                          const uint8_t* sm_arena, int64_t sm_elems, const int64_t* plan, int B, int min_L, int S, int scale,
                          float* lrs, float* alphas, float* hrs, float* maps, void* stream);
+/* The same with flip / rotate augmentation (nothing in the reference stands behind this one: its loader never augments;
+ * highres-net_amd/hrnet_hip/augment.py states the rule and is what the tests compare against).  codes: device array of B
+ * int32, one per sample, or NULL for identity (hrn_collate_device_s is this call with NULL).  A code t in 0..7 acts on every
+ * cropped window of the sample - each LR slot (n = S), the SM and the HR window (n = scale*S) - after the crop:
+ *     i' = t & 2 ? n-1-i : i,  j' = t & 1 ? n-1-j : j,  out[i][j] = window[t & 4 ? (j', i') : (i', j')]
+ * (transpose, then flip rows, then flip columns).  Padding slots stay zeros with alpha 0 and a sample without HR keeps its
+ * zero HR plane.  The codes live on the device, so a code outside 0..7 cannot be refused here: every plane of that sample
+ * is NaN (alphas as usual), other samples are unaffected, and nothing is read out of bounds.  Still one launch. */
+int hrn_collate_device_a(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems,
+                         const uint8_t* sm_arena, int64_t sm_elems, const int64_t* plan, int B, int min_L, int S, int scale,
+                         float* lrs, float* alphas, float* hrs, float* maps, const int32_t* codes, void* stream);
 
 /* hrn_resample_targets: HR images (elem_bytes 2, uint16) or status maps (elem_bytes 1, uint8, 0 / non-zero) stored at
  * n_in x n_in resampled to n_out x n_out, for a cache whose target scale differs from the ratio the files were stored at

@@ -1,7 +1,7 @@
 """Input-pipeline rate: the host path (ImagesetDataset.load_batch, BatchPrefetcher) against the HBM-resident cache
 (DeviceImagesetCache, one hrn_collate_device launch per batch) on synthetic imagesets in the PROBA-V layout.
 
-    python tools/loader_rate.py [--sets 64] [--threads 16] [--json out.json] [--no-prof]
+    python tools/loader_rate.py [--sets 64] [--threads 16] [--json out.json] [--no-prof] [--augment flip|dihedral]
 
 Writes the imagesets to a temporary directory (the stdlib zlib PNG writer of tests/imageset_png.py; smooth 16-bit fields plus
 noise, 19-35 views of 128x128, HR / SM 384x384), then per shape (B / top_k / min_L / patch):
@@ -12,6 +12,7 @@ noise, 19-35 views of 128x128, HR / SM 384x384), then per shape (B / top_k / min
   - batches/s of load_batch (pageable and pinned), of BatchPrefetcher(device="cuda") in steady state with an idle consumer and
     (first shape) with a consumer that spends one training step (26.2 / 55 ms) per batch, of cache.load_batch and cache.batches,
   - the kernel time of hrn_collate_device from `rocprofv3 --kernel-trace --stats` (a child process of this script).
+`--augment MODE` measures the same with flip / rotate augmentation on (one code per imageset, hrnet_hip/augment.py), on both paths.
 Needs a ROCm device; prints one JSON object."""
 import argparse
 import csv
@@ -33,6 +34,7 @@ from imageset_png import write_png                 # the stdlib PNG writer the t
 SHAPES = [dict(B=32, top_k=32, min_L=32, patch=64), dict(B=8, top_k=8, min_L=2, patch=64)]      # README step; shipped config.json
 STEPS_MS = (26.2, 55.0)            # README: the training step at SHAPES[0] with HRNet + ShiftNet in bf16, and with HRNet in bf16x3
 MIN_WINDOW_S = 1.5
+AUGMENT = None                     # --augment: the datasets' augmentation mode
 
 
 def smooth_field(rng, n, waves=6):
@@ -71,7 +73,7 @@ def batch_lists(n_sets, B, n_batches, seed):
 
 def dataset(dirs, shape):
     import DataLoader as DL
-    return DL.ImagesetDataset(dirs, {"create_patches": True, "patch_size": shape["patch"]}, top_k=shape["top_k"], beta=50.0)
+    return DL.ImagesetDataset(dirs, {"create_patches": True, "patch_size": shape["patch"]}, top_k=shape["top_k"], beta=50.0, augment=AUGMENT)
 
 
 def rate(n, seconds):
@@ -141,7 +143,8 @@ def measure(dirs, shape, threads, repeats, steps_ms):
             plans = [ds._plan(ds.imset_dir[i]) for i in idx]
             t1 = time.perf_counter()
             io_binding.collate([p["lr_paths"] for p in plans], [p["hr"] for p in plans], [p["sm"] for p in plans], min_L=min_L,
-                               lr_size=plans[0]["lr_side"], patch=P, corners=[p["corner"] for p in plans], out=buf, n_threads=threads)
+                               lr_size=plans[0]["lr_side"], patch=P, corners=[p["corner"] for p in plans], out=buf, n_threads=threads,
+                               codes=[p["code"] for p in plans] if AUGMENT else None)
             t_dec += time.perf_counter() - t1
             t_plan += t1 - t0
         plan_ms.append(1e3 * t_plan / n)
@@ -203,7 +206,7 @@ def kernel_stats(data_dir, threads, n_batches):
         with tempfile.TemporaryDirectory() as prof:
             cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", prof, "-o", "lr", "--",
                    sys.executable, os.path.abspath(__file__), "--child", data_dir, "--threads", str(threads), "--shape", str(k),
-                   "--batches", str(n_batches)]
+                   "--batches", str(n_batches)] + (["--augment", AUGMENT] if AUGMENT else [])
             r = subprocess.run(cmd, cwd=prof, capture_output=True, text=True, timeout=600)
             if r.returncode != 0:
                 raise RuntimeError(f"rocprofv3 run failed ({r.returncode}): {r.stderr[-2000:]}")
@@ -229,7 +232,10 @@ def main():
     ap.add_argument("--shape", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--batches", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5, help="timed windows per rate (the spread is reported)")
+    ap.add_argument("--augment", default=None, choices=["flip", "dihedral"], help="measure with this augmentation mode on")
     a = ap.parse_args()
+    global AUGMENT
+    AUGMENT = a.augment
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("loader_rate.py measures the device path: it needs a ROCm device")
@@ -246,7 +252,7 @@ def main():
         t0 = time.perf_counter()
         dirs = write_imagesets(root, a.sets)
         lr_png = [os.path.getsize(p) for p in glob.glob(os.path.join(root, "*", "LR*.png"))]
-        res = dict(sets=a.sets, threads=a.threads, synthetic_pngs=True, write_s=round(time.perf_counter() - t0, 1),
+        res = dict(sets=a.sets, threads=a.threads, augment=a.augment, synthetic_pngs=True, write_s=round(time.perf_counter() - t0, 1),
                    lr_views=len(lr_png), lr_png_kb=round(np.mean(lr_png) / 1024, 1),
                    hr_png_kb=round(np.mean([os.path.getsize(os.path.join(d, "HR.png")) for d in dirs]) / 1024, 1),
                    repeats=a.repeats, min_window_s=MIN_WINDOW_S,
