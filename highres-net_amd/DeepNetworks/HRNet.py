@@ -20,13 +20,20 @@ Training precision (`HRNet.train_precision`, or key "train_precision" in the con
                       the training forward and backward run in that precision; `precision` then governs only the forward
                       without a graph (.eval(), no_grad).  "bf16": one bf16 plane per activation and gradient, fp32
                       accumulation; parameters, their gradients and the optimizer state stay fp32
+
+Self-ensemble (`HRNet.ensemble`, or key "ensemble" in the config dict; default None; values as the loaders' `augment`):
+    None / False / "none"   off: `forward` is the code path it always was
+    "flip" / "dihedral" (True)
+                      the forward WITHOUT a graph (.eval(), no_grad) returns `forward_ensemble(lrs, alphas, mode)`: the mean of the
+                      4 / 8 predictions from the flipped / rotated view stacks, each transformed back (hrnet_hip/augment.py).  The
+                      training branch is never ensembled.
 """
 import os
 
 import torch
 import torch.nn as nn
 
-from hrnet_hip import binding
+from hrnet_hip import augment, binding
 
 _PRECISIONS = {"fp32": binding.F32, "f32": binding.F32, "float32": binding.F32, "bf16": binding.BF16, "bfloat16": binding.BF16,
                "bf16x3": binding.BF16X3}
@@ -149,6 +156,7 @@ class HRNet(nn.Module):
         self._num_layers = config["encoder"]["num_layers"]
         self.precision = config.get("precision", os.environ.get("HRNET_HIP_PRECISION", "fp32"))
         self.train_precision = config.get("train_precision")
+        self.ensemble = config.get("ensemble")
         self._packed = {}                   # dtype -> (key, blob): the inference and the training blob do not evict each other
 
     # -- packed-parameter cache: re-packed whenever a parameter was modified (optimizer step, load_state_dict, .to())
@@ -216,9 +224,43 @@ class HRNet(nn.Module):
                                                                params, self._num_layers, bool(self.fuse.alpha_residual), dt,
                                                                self._scale)
             return sr
+        if self.ensemble is not None and augment.check_mode(self.ensemble) is not None:
+            return self.forward_ensemble(lrs, alphas, self.ensemble)
         packed, dt = self.packed_parameters()
         return torch.ops.hrnet_hip.hrnet_forward(packed, dt, self._num_layers, bool(self.fuse.alpha_residual), lrs.detach(), alphas.detach(),
                                                  self._scale)
+
+    def forward_ensemble(self, lrs, alphas, mode="dihedral", members_per_pass=None):
+        """Self-ensemble at inference: (B,L,H,W), (B,L) -> (B,1,SH,SW), the mean over the K = 4 ("flip") or 8 ("dihedral") members
+        of augment.ensemble_codes(mode) of `forward(apply(lrs, code))` transformed back with the inverse code; bit for bit
+        `augment.mean_inverse(forward(member-major batch), codes)`.  Always the inference kernels of `precision`, no autograd graph.
+        One hrn_dihedral_expand launch builds the (K*B, L, H, W) member-major batch, the forward writes into slices of one
+        (K, B, 1, SH, SW) buffer, one hrn_dihedral_mean launch averages.  members_per_pass (1..K, default K): how many members one
+        forward takes, which bounds its workspace; a sample's result does not depend on its batch, so this changes no bit."""
+        codes = augment.ensemble_codes(mode)
+        K = len(codes)
+        per_pass = K if members_per_pass is None else members_per_pass
+        if not isinstance(per_pass, int) or not 1 <= per_pass <= K:
+            raise ValueError(f"members_per_pass must be an integer in 1..{K}, got {members_per_pass!r}")
+        if lrs.dim() != 4:
+            raise ValueError(f"lrs must be (B, L, H, W); got {tuple(lrs.shape)}")
+        if lrs.shape[2] != lrs.shape[3]:
+            # the forward's restriction, not the ensemble's: the two kernels take non-square planes when no member transposes ("flip")
+            raise ValueError(f"square low-res images only, as in forward (every member is one); got {tuple(lrs.shape)}")
+        if tuple(alphas.shape) != tuple(lrs.shape[:2]):
+            raise ValueError(f"alphas must be {tuple(lrs.shape[:2])}; got {tuple(alphas.shape)}")
+        B, V, H, W = lrs.shape
+        S = self._scale
+        packed, dt = self.packed_parameters()
+        with torch.no_grad():
+            members = torch.ops.hrnet_hip.dihedral_expand(lrs.detach().float().contiguous(), codes)         # (K,B,V,H,W)
+            alphas = alphas.detach().float().contiguous()
+            srs = torch.empty((K, B, 1, S * H, S * W), dtype=torch.float32, device=members.device)
+            for k0 in range(0, K, per_pass):
+                k1 = min(K, k0 + per_pass)
+                binding.hrnet_forward(packed, dt, self._num_layers, self.fuse.alpha_residual, members[k0:k1].view(-1, V, H, W),
+                                      alphas.repeat(k1 - k0, 1), out=srs[k0:k1].view(-1, 1, S * H, S * W), scale=S)
+            return torch.ops.hrnet_hip.dihedral_mean(srs, codes)
 
     def _packed_f32(self):
         return self._packed_for(binding.F32)

@@ -1,7 +1,8 @@
 """Flip / rotate augmentation of the input pipeline: the eight symmetries of the square, one code per sample.  Pure Python,
 no GPU and no native library: this module states the rule that hrn_io_collate_a (host path) and hrn_collate_device_a (HBM cache)
-implement inside their gathers, it is the reference their tests compare against, and it lets a user undo a transform (for
-example to average the eight predictions of a self-ensemble at test time).
+implement inside their gathers, it is the reference their tests compare against, and it lets a user undo a transform.  The
+self-ensemble at test time (HRNet.forward_ensemble; hrn_dihedral_expand / hrn_dihedral_mean on the device) is stated here too:
+`ensemble_codes`, `expand` and `mean_inverse`, which those kernels are compared against bit for bit.
 
 A code t in 0..7 acts on the last two axes of a square array:
 
@@ -62,3 +63,50 @@ def inverse(code):
     turns, 5 and 6, which undo each other (with a transpose, the row flip of one is the column flip of the other)."""
     code = check_code(code)
     return {5: 6, 6: 5}.get(code, code)
+
+
+# --------------------------------------------------------------------------- self-ensemble: the rule of hrn_dihedral_expand / _mean
+def ensemble_codes(mode):
+    """The members of a self-ensemble: [0, 1, 2, 3] for "flip", [0 .. 7] for "dihedral" (True).  A mode that `check_mode` refuses, or
+    one that means "off", is a ValueError: an ensemble needs members."""
+    mode = check_mode(mode)
+    if mode is None:
+        raise ValueError(f"an ensemble needs a mode, one of {sorted(MODES)}")
+    return list(range(MODES[mode]))
+
+
+def check_codes(codes):
+    """A member list: 1..8 distinct codes in 0..7 -> list of int."""
+    codes = [check_code(c) for c in codes]
+    if not 1 <= len(codes) <= 8:
+        raise ValueError(f"a member list holds 1..8 codes, got {len(codes)}")
+    if len(set(codes)) != len(codes):
+        raise ValueError(f"the codes of a member list must be distinct, got {codes}")
+    return codes
+
+
+def expand(x, codes):
+    """x (..., H, W) -> (K, ..., H, W), member-major: out[k] = apply(x, codes[k])."""
+    parts = [apply(x, c) for c in check_codes(codes)]
+    if isinstance(x, np.ndarray):
+        return np.stack(parts)
+    import torch
+    return torch.stack(parts)
+
+
+def mean_inverse(y, codes):
+    """y (K, ..., H, W) -> (..., H, W): every member transformed back and averaged, with the summation rule of hrn_dihedral_mean:
+
+        m_k = apply(y[k], inverse(codes[k]));   out = r * ((..((m_0 + m_1) + m_2)..) + m_{K-1}),   r = 1 / K rounded to y's dtype
+
+    adds in member order in y's own dtype, then ONE multiply - no division - so fp32 arrays give the kernel's bits."""
+    codes = check_codes(codes)
+    if len(y) != len(codes):
+        raise ValueError(f"y has {len(y)} members for {len(codes)} codes")
+    total = apply(y[0], inverse(codes[0]))
+    for k in range(1, len(codes)):
+        total = total + apply(y[k], inverse(codes[k]))
+    if isinstance(y, np.ndarray):
+        return total * y.dtype.type(1.0 / len(codes))
+    import torch
+    return total * torch.tensor(1.0 / len(codes), dtype=y.dtype).item()

@@ -8,9 +8,12 @@ import ctypes
 import os
 import threading
 
+from typing import List, Optional, Sequence, Tuple
+
 import numpy as np
 import torch
 
+from . import augment
 from .resample import check_scale
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -142,6 +145,8 @@ SIGNATURES = {
     "hrn_collate_device_a": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
                                         _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                         _c.c_void_p, _c.c_void_p]),
+    "hrn_dihedral_expand": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int32), _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "hrn_dihedral_mean": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int32), _c.c_int, _c.c_void_p, _c.c_void_p]),
     "hrn_resample_targets": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int,
                                         _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_profile_enable": (_c.c_int, [_c.c_int]),
@@ -598,6 +603,42 @@ def collate_device(lr_arena, hr_arena, sm_arena, plan, S, lrs, alphas, hrs, maps
            "hrn_collate_device_a")
 
 
+# --------------------------------------------------------------------------- flip / rotate self-ensemble
+def _dihedral_args(t, name, codes, lead):
+    """-> (contiguous f32 device tensor, host int32 array of the codes, K, N, H, W); `lead`: leading axes that are not planes."""
+    codes = augment.check_codes(codes)
+    t = _dev_f32(t, name)
+    if t.dim() < 2 + lead:
+        raise ValueError(f"{name} must have at least {2 + lead} axes, got {tuple(t.shape)}")
+    if lead and t.shape[0] != len(codes):
+        raise ValueError(f"{name} has {t.shape[0]} members for {len(codes)} codes")
+    H, W = t.shape[-2:]
+    N = int(np.prod(t.shape[lead:-2], dtype=np.int64))
+    if t.numel() == 0:
+        raise ValueError(f"{name} is empty: {tuple(t.shape)}")
+    return t, (ctypes.c_int32 * len(codes))(*codes), len(codes), N, H, W
+
+
+def dihedral_expand(x, codes):
+    """x (..., H, W) -> (K, ..., H, W), member-major: out[k] = augment.apply(x, codes[k]).  `codes`: a host sequence of 1..8 distinct
+    codes in 0..7 (hrnet_hip/augment.py); one launch of hrn_dihedral_expand on the current stream."""
+    x, carr, K, N, H, W = _dihedral_args(x, "x", codes, 0)
+    out = torch.empty((K,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(load_library().hrn_dihedral_expand(_ptr(x), N, H, W, carr, K, _ptr(out), _stream()), "hrn_dihedral_expand")
+    return out
+
+
+def dihedral_mean(y, codes):
+    """y (K, ..., H, W) -> (..., H, W): the mean over the members of augment.apply(y[k], augment.inverse(codes[k])), summed in fp32
+    in list order and multiplied once by float32(1 / K) - bit for bit augment.mean_inverse.  One launch of hrn_dihedral_mean."""
+    y, carr, K, N, H, W = _dihedral_args(y, "y", codes, 1)
+    out = torch.empty(tuple(y.shape[1:]), dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device):
+        _check(load_library().hrn_dihedral_mean(_ptr(y), N, H, W, carr, K, _ptr(out), _stream()), "hrn_dihedral_mean")
+    return out
+
+
 RESAMPLE_TAPS = 12        # HRN_RESAMPLE_TAPS: weights per output sample in a resampling table
 
 
@@ -767,13 +808,31 @@ def _(srs, hrs, hr_maps, border_w, clip):
     return srs.new_empty((srs.shape[0] if srs.dim() == 3 else 1,), dtype=torch.float32)
 
 
+# the two ends of the self-ensemble (HRNet.forward_ensemble): inference only, so no autograd formula
+@torch.library.custom_op("hrnet_hip::dihedral_expand", mutates_args=(), device_types="cuda")
+def _op_dihedral_expand(x: torch.Tensor, codes: Sequence[int]) -> torch.Tensor:
+    return dihedral_expand(x, codes)
+
+
+@_op_dihedral_expand.register_fake
+def _(x, codes):
+    return x.new_empty((len(codes),) + tuple(x.shape), dtype=torch.float32)
+
+
+@torch.library.custom_op("hrnet_hip::dihedral_mean", mutates_args=(), device_types="cuda")
+def _op_dihedral_mean(y: torch.Tensor, codes: Sequence[int]) -> torch.Tensor:
+    return dihedral_mean(y, codes)
+
+
+@_op_dihedral_mean.register_fake
+def _(y, codes):
+    return y.new_empty(tuple(y.shape[1:]), dtype=torch.float32)
+
+
 # --------------------------------------------------------------------------- the TRAINING entry points as dispatcher-registered ops
 # (call sites: src/train.py:174-191).  Each is registered with a fake (meta) implementation and, where the reference differentiates
 # through it, with `register_autograd`: the backward formula is itself a registered op over the C ABI's *_backward entry point.  The
 # reference-named modules call these through torch.ops.hrnet_hip.* in .train() mode.
-from typing import List, Optional, Sequence, Tuple  # noqa: E402
-
-
 def hrnet_param_names(num_layers):
     """HRNet's parameters in the module's registration order (== the reference's state_dict order, HRNet.py:36-169)."""
     names = ["encode.init_layer.0.weight", "encode.init_layer.0.bias", "encode.init_layer.1.weight"]

@@ -25,7 +25,7 @@
 //              converts them and writes them down one column of the f32 tile with 4 ds_write_b32; after one barrier it reads a
 //              row of the tile with one ds_read_b128 and stores it.  Two tile buffers alternate, so one barrier per tile
 //              suffices (a wave can only reach the write of tile t+2 after every wave has finished reading tile t).
-//     LDS layout: pitch kTile = 32 dwords (no padding - ds_read_b128 needs 16-byte rows), the 16-byte slot of element (R, C)
+//     LDS layout (swizzle_tile.h): pitch kTile = 32 dwords (no padding - ds_read_b128 needs 16-byte rows), the 16-byte slot of element (R, C)
 //              XOR-swizzled with the row block: dword R*32 + 4*((C/4) ^ (R/4)) + C%4.  Derived conflict count: 0 and 0.
 //              - ds_write_b32, bank (a/4) % 32, groups = 32-lane halves: a half holds 4 tile columns c..c+3 (c % 4 == 0) times
 //                8 row blocks R/4 = 0..7; the bank is 4*((c/4) ^ (R/4)) + c%4 - the XOR with a constant permutes 0..7, so the 32
@@ -42,13 +42,13 @@
 // No instance uses scratch.
 #include "../../../include/hrnet_hip.h"
 #include "common.h"
+#include "swizzle_tile.h"                                // kTile, tile_at (shared with dihedral.hip)
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMeta = HRN_COLLATE_META;                 // plan row: hr_off, sm_off, side, row, col, then min_L LR offsets
 constexpr long long kMaxSide = 1 << 20;                  // a larger stored side is a bad row (keeps 16 side^2 far from int64 overflow)
-constexpr int kTile = 32;                                // side of a transposed sub-tile: kThreads lanes x 4 samples = one tile
 
 // 4 consecutive samples from element i of an arena whose images start at multiples of 4 elements and whose size is a multiple
 // of 4: the second word is read only when i is not 4-aligned, and then it holds element i + 3, so it lies inside the arena.
@@ -83,9 +83,6 @@ __device__ __forceinline__ f32x4 convert4_u8(uint32_t m, bool reversed) {
     if (reversed) v = f32x4{v[3], v[2], v[1], v[0]};
     return v;
 }
-
-// dword index of element (R, C) of a kTile x kTile f32 tile: 16-byte slots XOR-swizzled with the row block (header comment)
-__device__ __forceinline__ int tile_at(int R, int C) { return R * kTile + ((((C >> 2) ^ (R >> 2)) & 7) << 2) + (C & 3); }
 
 // Codes 4..7 on the vector path: tiles t0, t0 + tstep, ... of the n x n output plane `out`, out[i][j] = window[j'][i'] with
 // `window` the element index of the window's corner in the arena (n % 4 == 0).  A lane reads window[sr][sc .. sc+3] with

@@ -5,7 +5,16 @@ The reference scores every validation imageset on rank 0: `srs = fusion_model(lr
 scores ITS imagesets on the device (`HRNet` in eval mode + `hrn_shift_cpsnr`, 49 shifted cPSNRs per image in one launch) and the two
 scalars (sum of scores, number of samples) are all-reduced: one 16-byte collective per validation pass, no image ever leaves its GPU.
 Without a process group the result is the single-process score.
+
+With a baseline table (the `norm.csv` of a PROBA-V directory: imageset name -> ESA baseline cPSNR) the score is the reference's
+`mean(ESA[name] / shift_cPSNR)` (train.py:213-217), the number that drives its best-checkpoint selection; the batches then carry the
+`names` that collateFunction, load_batch, BatchPrefetcher and DeviceImagesetCache.batches produce as their fifth element.  `ensemble`
+("flip" / "dihedral") scores the self-ensembled prediction (HRNet.forward_ensemble).  `evaluate` is the same pass on one rank that
+also returns the per-imageset cPSNRs.
 """
+import collections
+
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -17,23 +26,74 @@ def shard_indices(n_items, rank, world_size):
     return list(range(rank, n_items, world_size))
 
 
-def sharded_val_score(fusion_model, batches, border_w=3, score_fn=None, device=None):
-    """`batches`: this rank's validation batches of (lrs, alphas, hrs, hr_maps) tensors (the reference loads them one imageset at a
-    time, train.py:281).  Returns -mean(shift_cPSNR) over ALL ranks' samples, as `val_score` of train.py:199-215.
-    score_fn(srs (B,S,S), hrs, hr_maps) -> (B,) replaces `hrn_shift_cpsnr` in the CPU rehearsal of the collective (tests/test_dist_cpu.py)."""
+Evaluation = collections.namedtuple("Evaluation", "names cpsnr score")
+
+
+def _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, members_per_pass, keep):
+    """The validation loop of train.py:196-215 over this rank's batches, (lrs, alphas, hrs, hr_maps) or (..., names): -> (float64
+    sum on the device of cPSNR - or of ESA[name] / cPSNR with a baseline table - or None without a batch, the number of samples,
+    names, the list of per-batch float64 cPSNR tensors when `keep`).  The model's training flag is restored."""
+    from . import augment
     score_fn = score_fn or (lambda s, h, m: binding.shift_cpsnr(s, h, m, border_w, True))
+    mode = augment.check_mode(ensemble)
+    if mode is not None and not hasattr(fusion_model, "forward_ensemble"):
+        raise TypeError(f"ensemble={ensemble!r} needs a model with forward_ensemble (DeepNetworks.HRNet), got {type(fusion_model).__name__}")
     was_training = fusion_model.training
     fusion_model.eval()
-    total, count = None, 0
+    total, count, all_names, kept = None, 0, [], []
     try:
         with torch.no_grad():
-            for lrs, alphas, hrs, hr_maps in batches:
-                srs = fusion_model(lrs, alphas)[:, 0]
-                sc = score_fn(srs, hrs, hr_maps).double().sum()
+            for batch in batches:
+                if len(batch) not in (4, 5):
+                    raise ValueError(f"a validation batch is (lrs, alphas, hrs, hr_maps) or (..., names); got {len(batch)} elements")
+                lrs, alphas, hrs, hr_maps = batch[:4]
+                names = list(batch[4]) if len(batch) == 5 else None
+                if baseline_cpsnrs is not None and names is None:
+                    raise ValueError("a baseline table needs batches with names: (lrs, alphas, hrs, hr_maps, names)")
+                if names is not None and len(names) != lrs.shape[0]:
+                    raise ValueError(f"{len(names)} names for a batch of {lrs.shape[0]}")
+                if mode is None:
+                    srs = fusion_model(lrs, alphas)[:, 0]
+                else:
+                    srs = fusion_model.forward_ensemble(lrs, alphas, mode, members_per_pass)[:, 0]
+                cpsnr = score_fn(srs, hrs, hr_maps).double()
+                if baseline_cpsnrs is None:
+                    sc = cpsnr.sum()
+                else:       # the batch's ESA values go up as one small tensor; a missing name is the reference's KeyError
+                    esa = torch.tensor([float(baseline_cpsnrs[n]) for n in names], dtype=torch.float64).to(cpsnr.device)
+                    sc = (esa / cpsnr).sum()
                 total = sc if total is None else total + sc
                 count += int(srs.shape[0])
+                if names is not None:
+                    all_names += names
+                if keep:
+                    kept.append(cpsnr)
     finally:
         fusion_model.train(was_training)
+    return total, count, all_names, kept
+
+
+def evaluate(fusion_model, batches, baseline_cpsnrs=None, ensemble=None, border_w=3, score_fn=None, members_per_pass=None):
+    """One rank's evaluation pass over `batches` of (lrs, alphas, hrs, hr_maps, names) (names may be left out without a baseline table):
+    -> Evaluation(names, cpsnr, score) with the per-imageset shift_cPSNR as a float64 numpy array in batch order and `score` the
+    reference's validation score (train.py:209-217): -mean(cPSNR) without a baseline table, mean(ESA[name] / cPSNR) with one
+    (`baseline_cpsnrs`: name -> ESA baseline cPSNR).  ensemble: None, or "flip" / "dihedral" to score
+    `fusion_model.forward_ensemble(lrs, alphas, ensemble, members_per_pass)` instead of the plain forward.  The sums stay in float64
+    on the device; one read-back at the end.  score_fn as in sharded_val_score."""
+    total, count, names, kept = _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, members_per_pass, True)
+    if count == 0:
+        raise ValueError("evaluate: no sample in `batches`")
+    mean = float(total / count)
+    return Evaluation(names, torch.cat(kept).cpu().numpy().astype(np.float64), mean if baseline_cpsnrs is not None else -mean)
+
+
+def sharded_val_score(fusion_model, batches, border_w=3, score_fn=None, device=None, baseline_cpsnrs=None, ensemble=None):
+    """`batches`: this rank's validation batches of (lrs, alphas, hrs, hr_maps) tensors, or the same with `names` as a fifth element
+    (the reference loads them one imageset at a time, train.py:281).  Returns `val_score` of train.py:199-217 over ALL ranks' samples:
+    -mean(shift_cPSNR), or with `baseline_cpsnrs` (name -> ESA baseline cPSNR; needs the names) mean(ESA[name] / shift_cPSNR).  Either
+    way only (sum, count) is all-reduced.  ensemble: None, or "flip" / "dihedral" to score the model's forward_ensemble.
+    score_fn(srs (B,S,S), hrs, hr_maps) -> (B,) replaces `hrn_shift_cpsnr` in the CPU rehearsal of the collective (tests/test_dist_cpu.py)."""
+    total, count, _, _ = _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, None, False)
     if total is None:
         total = torch.zeros((), dtype=torch.float64, device=device or "cpu")
     acc = torch.stack([total.reshape(()), torch.tensor(float(count), dtype=torch.float64, device=total.device)])
@@ -43,4 +103,5 @@ def sharded_val_score(fusion_model, batches, border_w=3, score_fn=None, device=N
         dist.all_reduce(acc, op=dist.ReduceOp.SUM)
     if float(acc[1]) == 0:
         raise ValueError("sharded_val_score: no validation sample on any rank")
-    return -float(acc[0] / acc[1])
+    mean = float(acc[0] / acc[1])
+    return mean if baseline_cpsnrs is not None else -mean

@@ -26,6 +26,9 @@
  *   hrn_collate_device_a   <-  (no counterpart: the reference trains without augmentation) the same gather with one of the
  *                              eight flips / rotations of the square applied per sample
  *   hrn_resample_targets   <-  (no counterpart) HR / SM stored at one ratio resampled to another when the cache is built
+ *   hrn_dihedral_expand / hrn_dihedral_mean  <-  (no counterpart: the reference predicts from one orientation) the two ends of a
+ *                              flip / rotate self-ensemble at inference: the K transformed copies of the view stack, and the mean
+ *                              of the K predictions after each is transformed back
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor's data_ptr) unless stated;
@@ -38,7 +41,8 @@
  *     -5 HIP runtime error); hrn_last_error() returns a thread-local message for the last failing call;
  *   - dtype selects storage of activations and the MFMA input type:
  *       HRN_DTYPE_F32  : f32 activations, v_mfma_f32_32x32x2_f32 (exact fp32 products and accumulation)
- *       HRN_DTYPE_BF16 : bf16 activations/weights, v_mfma_f32_32x32x16_bf16, fp32 accumulation
+ *       HRN_DTYPE_BF16 : bf16 activations/weights, fp32 accumulation: v_mfma_f32_32x32x16_bf16 in the stem, the encoder and the
+ *                        decoder, v_mfma_f32_16x16x32_bf16 in the fusion levels (128 -> {128, 64} convs)
  *       HRN_DTYPE_BF16X3 : every fp32 activation / weight as two bf16 planes (hi = bf16(v), lo = bf16(v - hi)); a product is
  *                        hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (~2^-16 per product): the
  *                        reference's fp32 arithmetic (train.py:168-171, predict.py:36-37) to ~1e-5 at a third of the bf16
@@ -216,7 +220,8 @@ int hrn_shiftnet_forward(const void* packed, const hrn_shiftnet_params* params, 
  * and batch statistics kept in `train_ws`; hrn_shiftnet_backward turns d_theta (B,2) into the parameter gradients,
  * ACCUMULATED (+=) into the buffers of `grads` (conv_w/conv_b/bn_g/bn_b/fc1_w/fc1_b/fc2_w in the parameters' own
  * reference layouts; bn_rm/bn_rv are not read), and, when d_x is not NULL, writes the gradient of the input pairs
- * d_x (B,2,128,128).  `params` are the raw reference-layout tensors, `dropout_mask` the mask the forward used.  B <= 32. */
+ * d_x (B,2,128,128).  `params` are the raw reference-layout tensors, `dropout_mask` the mask the forward used.  Any B > 0:
+ * the fc1 kernels take 32 samples per launch and larger batches go through them in slices. */
 size_t hrn_shiftnet_train_workspace_bytes(int B);
 int hrn_shiftnet_forward_train(const void* packed, const hrn_shiftnet_params* params, const float* x, int B, float momentum,
                                const unsigned char* dropout_mask, float* theta, void* train_ws, size_t train_ws_bytes,
@@ -324,6 +329,23 @@ int hrn_collate_device_s(const uint16_t* lr_arena, int64_t lr_elems, const uint1
 int hrn_collate_device_a(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems,
                          const uint8_t* sm_arena, int64_t sm_elems, const int64_t* plan, int B, int min_L, int S, int scale,
                          float* lrs, float* alphas, float* hrs, float* maps, const int32_t* codes, void* stream);
+
+/* ------------------------------------------------------------------ flip / rotate self-ensemble at inference
+ * Nothing in the reference stands behind these two: its predict.py runs one orientation.  highres-net_amd/hrnet_hip/augment.py states
+ * the rule (apply, inverse, expand, mean_inverse) and is what the tests compare against, bit for bit.  A code t in 0..7 acts on an
+ * (H, W) plane as in hrn_collate_device_a: transpose if t & 4, then flip rows if t & 2, then flip columns if t & 1.
+ *   codes : the member list, a HOST array of K int32 (1 <= K <= 8), each in 0..7, all distinct.  It is read and validated during
+ *           the call, before any launch, and reaches the kernel by value; the caller may free it as soon as the call returns.
+ *   hrn_dihedral_expand : x (N,H,W) f32 -> out (K,N,H,W) f32, member-major: out[k][n] = apply(x[n], codes[k]).  One launch.
+ *   hrn_dihedral_mean   : y (K,N,H,W) f32 -> out (N,H,W) f32.  With m_k = apply(y[k][n], inverse(codes[k])):
+ *                             out[n] = r * ((..((m_0 + m_1) + m_2)..) + m_{K-1}),   r = (float)(1.0 / K)
+ *                         i.e. fp32 adds in member order and ONE fp32 multiply.  One launch, no atomics, deterministic.
+ * x / y and out are device pointers and must not overlap.  Non-square planes are accepted when no code transposes.
+ * -2 before any launch, with hrn_last_error() naming the fault: a null pointer, K outside 1..8, a code outside 0..7, a duplicate
+ * code, a code with `t & 4` (the transpose bit) set while H != W, N / H / W not positive, a side above 32768, or (16-byte path) 2^24
+ * or more 32 x 32 tiles in all. */
+int hrn_dihedral_expand(const float* x, int N, int H, int W, const int32_t* codes, int K, float* out, void* stream);
+int hrn_dihedral_mean(const float* y, int N, int H, int W, const int32_t* codes, int K, float* out, void* stream);
 
 /* hrn_resample_targets: HR images (elem_bytes 2, uint16) or status maps (elem_bytes 1, uint8, 0 / non-zero) stored at
  * n_in x n_in resampled to n_out x n_out, for a cache whose target scale differs from the ratio the files were stored at
