@@ -27,13 +27,19 @@ Self-ensemble (`HRNet.ensemble`, or key "ensemble" in the config dict; default N
                       the forward WITHOUT a graph (.eval(), no_grad) returns `forward_ensemble(lrs, alphas, mode)`: the mean of the
                       4 / 8 predictions from the flipped / rotated view stacks, each transformed back (hrnet_hip/augment.py).  The
                       training branch is never ensembled.
+
+Tiled inference (`HRNet.tile`, or key "tile" in the config dict; default None):
+    None              off: `forward` is the code path it always was, square low-res images only
+    an integer        the forward WITHOUT a graph routes an input that is not square, or larger than `tile` pixels a side, through
+                      `forward_tiled(lrs, alphas, tile, ensemble=self.ensemble)`: overlapping square windows whose cores tile the
+                      scene (hrnet_hip/tiling.py).  Scenes of any size and aspect ratio; the training branch is never tiled.
 """
 import os
 
 import torch
 import torch.nn as nn
 
-from hrnet_hip import augment, binding
+from hrnet_hip import augment, binding, tiling
 
 _PRECISIONS = {"fp32": binding.F32, "f32": binding.F32, "float32": binding.F32, "bf16": binding.BF16, "bfloat16": binding.BF16,
                "bf16x3": binding.BF16X3}
@@ -157,6 +163,7 @@ class HRNet(nn.Module):
         self.precision = config.get("precision", os.environ.get("HRNET_HIP_PRECISION", "fp32"))
         self.train_precision = config.get("train_precision")
         self.ensemble = config.get("ensemble")
+        self.tile = config.get("tile")
         self._packed = {}                   # dtype -> (key, blob): the inference and the training blob do not evict each other
 
     # -- packed-parameter cache: re-packed whenever a parameter was modified (optimizer step, load_state_dict, .to())
@@ -191,12 +198,16 @@ class HRNet(nn.Module):
     def forward(self, lrs, alphas):
         if lrs.dim() != 4:
             raise ValueError(f"lrs must be (B, L, H, W); got {tuple(lrs.shape)}")
-        if lrs.shape[2] != lrs.shape[3]:
-            raise ValueError("square low-res images only: the reference reinterprets (H,W) as (W,H) in its .view() "
-                             "(HRNet.py:204), which is the identity only for H == W")
         grad_params = self.training and any(p.requires_grad for p in self.parameters())
         grad_inputs = lrs.requires_grad or alphas.requires_grad
-        if torch.is_grad_enabled() and (grad_params or grad_inputs):
+        graph = torch.is_grad_enabled() and (grad_params or grad_inputs)
+        if self.tile is not None and not graph and (lrs.shape[2] != lrs.shape[3] or lrs.shape[2] > self._tile_side(self.tile)):
+            return self.forward_tiled(lrs, alphas, self.tile, ensemble=self.ensemble)
+        if lrs.shape[2] != lrs.shape[3]:
+            raise ValueError("square low-res images only: the reference reinterprets (H,W) as (W,H) in its .view() "
+                             "(HRNet.py:204), which is the identity only for H == W"
+                             + ("" if graph else "; forward_tiled (or the `tile` attribute) takes scenes of any shape at inference"))
+        if graph:
             # .train() mode with grad enabled - the training loop (train.py:160-190), but also src/predict.py, which never calls
             # .eval() and uses no no_grad (predict.py:86-100, :17-49).  Autograd cannot tell us whether a backward pass will follow:
             #   precision "fp32" (default) / "bf16x3": the training forward of that precision (torch.ops.hrnet_hip.hrnet_forward_train), which
@@ -261,6 +272,81 @@ class HRNet(nn.Module):
                 binding.hrnet_forward(packed, dt, self._num_layers, self.fuse.alpha_residual, members[k0:k1].view(-1, V, H, W),
                                       alphas.repeat(k1 - k0, 1), out=srs[k0:k1].view(-1, 1, S * H, S * W), scale=S)
             return torch.ops.hrnet_hip.dihedral_mean(srs, codes)
+
+    @staticmethod
+    def _tile_side(tile):
+        if isinstance(tile, bool) or not isinstance(tile, int) or tile < 1:
+            raise ValueError(f"tile must be a positive integer, got {tile!r}")
+        return tile
+
+    def forward_tiled(self, lrs, alphas, tile=128, windows_per_pass=None, ensemble=None, members_per_pass=None):
+        """Inference on a scene of any size and aspect ratio: (B,L,H,W), (B,L) -> (B,1,SH,SW), H, W >= 1, from overlapping square
+        windows of side t = min(tile, H, W) (hrnet_hip/tiling.py).  A window is responsible for its core, whose every edge is on the
+        scene's border or at least R = tiling.halo(num_layers, L) LR pixels inside the window - the network's receptive field - so
+        the result is what a whole-frame forward would give, where one exists.  Always the inference kernels of `precision`, no
+        autograd graph.
+
+        The plan's windows go through in chunks of `windows_per_pass` (default max(1, 32 // B): 32 samples per forward): one
+        hrn_tile_gather launch builds the (chunk, B, L, t, t) window-major batch, one forward takes it as chunk * B samples, one
+        hrn_tile_scatter launch puts the cores into the output.  Peak memory: the output, one chunk of windows (LR and SR) and one
+        forward's workspace; all windows are never materialised at once.  A sample's result does not depend on its batch, so the
+        chunking changes no bit.  The work grows by the plan's overhead factor n_windows * t * t / (H * W).
+
+        ensemble ("flip" / "dihedral"; None: off): every chunk of windows goes through the self-ensemble of forward_ensemble
+        (expand / forward / mean, `members_per_pass` members per forward).  For a square scene this is forward_ensemble of the whole
+        frame; for a rectangular one it DEFINES the ensemble, transposing members included: the windows are square.
+
+        A scene that is one window (H == W <= tile) goes straight to the plain forward (or forward_ensemble)."""
+        tile = self._tile_side(tile)
+        if lrs.dim() != 4 or lrs.numel() == 0:
+            raise ValueError(f"lrs must be a non-empty (B, L, H, W); got {tuple(lrs.shape)}")
+        if tuple(alphas.shape) != tuple(lrs.shape[:2]):
+            raise ValueError(f"alphas must be {tuple(lrs.shape[:2])}; got {tuple(alphas.shape)}")
+        mode = augment.check_mode(ensemble)
+        B, V, H, W = lrs.shape
+        S = self._scale
+        per_pass = max(1, 32 // B) if windows_per_pass is None else windows_per_pass
+        if isinstance(per_pass, bool) or not isinstance(per_pass, int) or per_pass < 1:
+            raise ValueError(f"windows_per_pass must be a positive integer, got {windows_per_pass!r}")
+        codes = augment.ensemble_codes(mode) if mode is not None else None
+        K = len(codes) if codes else 1
+        m_pass = K if members_per_pass is None else members_per_pass
+        if codes and (isinstance(m_pass, bool) or not isinstance(m_pass, int) or not 1 <= m_pass <= K):
+            raise ValueError(f"members_per_pass must be an integer in 1..{K}, got {members_per_pass!r}")
+        if H == W and H <= tile:
+            if mode is not None:
+                return self.forward_ensemble(lrs, alphas, mode, members_per_pass)
+            packed, dt = self.packed_parameters()
+            return torch.ops.hrnet_hip.hrnet_forward(packed, dt, self._num_layers, bool(self.fuse.alpha_residual), lrs.detach(),
+                                                     alphas.detach(), S)
+        R = tiling.halo(self._num_layers, V)
+        p = tiling.plan(H, W, tile, R)
+        t, n = p.t, len(p.windows)
+        packed, dt = self.packed_parameters()
+        ops = torch.ops.hrnet_hip
+        with torch.no_grad():
+            lrs = lrs.detach().float().contiguous()
+            alphas = alphas.detach().float().contiguous()
+            out = torch.empty((B, 1, S * H, S * W), dtype=torch.float32, device=lrs.device)
+            for w0 in range(0, n, per_pass):
+                w1 = min(n, w0 + per_pass)
+                c = w1 - w0
+                wins = ops.tile_gather(lrs, t, R, w0, w1)                                                   # (c,B,V,t,t)
+                a = alphas.repeat(c, 1)
+                if codes is None:
+                    srs = binding.hrnet_forward(packed, dt, self._num_layers, self.fuse.alpha_residual, wins.view(-1, V, t, t), a, scale=S)
+                else:                                                                                       # forward_ensemble on c * B samples
+                    members = ops.dihedral_expand(wins.view(-1, V, t, t), codes)                            # (K,c*B,V,t,t)
+                    srs = torch.empty((K, c * B, 1, S * t, S * t), dtype=torch.float32, device=lrs.device)
+                    for k0 in range(0, K, m_pass):
+                        k1 = min(K, k0 + m_pass)
+                        binding.hrnet_forward(packed, dt, self._num_layers, self.fuse.alpha_residual, members[k0:k1].view(-1, V, t, t),
+                                              a.repeat(k1 - k0, 1), out=srs[k0:k1].view(-1, 1, S * t, S * t), scale=S)
+                    srs = ops.dihedral_mean(srs, codes)
+                    del members
+                ops.tile_scatter(out, srs.view(c, B, 1, S * t, S * t), t, R, S, w0, w1)
+                del wins, srs                     # before the next chunk is allocated: one chunk at a time, as the bound says
+            return out
 
     def _packed_f32(self):
         return self._packed_for(binding.F32)

@@ -147,6 +147,10 @@ SIGNATURES = {
                                         _c.c_void_p, _c.c_void_p]),
     "hrn_dihedral_expand": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int32), _c.c_int, _c.c_void_p, _c.c_void_p]),
     "hrn_dihedral_mean": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int32), _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "hrn_hrnet_halo": (_c.c_int, [_c.c_int, _c.c_int]),
+    "hrn_tile_count": (_c.c_int, [_c.c_int] * 4),
+    "hrn_tile_gather": (_c.c_int, [_c.c_void_p] + [_c.c_int] * 8 + [_c.c_void_p, _c.c_void_p]),
+    "hrn_tile_scatter": (_c.c_int, [_c.c_void_p] + [_c.c_int] * 8 + [_c.c_void_p, _c.c_void_p]),
     "hrn_resample_targets": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int,
                                         _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_profile_enable": (_c.c_int, [_c.c_int]),
@@ -639,6 +643,64 @@ def dihedral_mean(y, codes):
     return out
 
 
+# --------------------------------------------------------------------------- tiled inference
+def hrnet_halo(num_layers, n_views):
+    """hrn_hrnet_halo: the network's one-sided receptive field in LR pixels (== tiling.halo)."""
+    r = load_library().hrn_hrnet_halo(int(num_layers), int(n_views))
+    _check(min(r, 0), "hrn_hrnet_halo")
+    return r
+
+
+def tile_count(H, W, t, R):
+    """hrn_tile_count: the number of windows of the plan (== len(tiling.plan(H, W, t, R).windows) for t <= min(H, W))."""
+    n = load_library().hrn_tile_count(int(H), int(W), int(t), int(R))
+    _check(min(n, 0), "hrn_tile_count")
+    return n
+
+
+def _window_range(w0, w1):
+    w0, w1 = int(w0), int(w1)
+    if not 0 <= w0 < w1:
+        raise ValueError(f"the window range must satisfy 0 <= w0 < w1, got [{w0}, {w1})")
+    return w0, w1
+
+
+def tile_gather(lrs, t, R, w0, w1):
+    """lrs (B,V,H,W) -> (w1-w0, B, V, t, t), window-major: the windows w0 <= w < w1 of tiling.plan(H, W, t, R), bit for bit
+    tiling.gather(lrs, plan.windows[w0:w1], t).  One launch of hrn_tile_gather on the current stream."""
+    lrs = _dev_f32(lrs, "lrs")
+    if lrs.dim() != 4 or lrs.numel() == 0:
+        raise ValueError(f"lrs must be a non-empty (B,V,H,W); got {tuple(lrs.shape)}")
+    w0, w1 = _window_range(w0, w1)
+    B, V, H, W = lrs.shape
+    t = int(t)
+    with torch.cuda.device(lrs.device):
+        out = torch.empty((w1 - w0, B, V, max(t, 0), max(t, 0)), dtype=torch.float32, device=lrs.device)
+        _check(load_library().hrn_tile_gather(_ptr(lrs), B, V, H, W, t, int(R), w0, w1, _ptr(out), _stream()), "hrn_tile_gather")
+    return out
+
+
+def tile_scatter(out, srs, t, R, scale, w0, w1):
+    """srs (w1-w0, B, 1, S t, S t), the forwards of the windows w0 <= w < w1 of tiling.plan(H, W, t, R) -> their cores in
+    out (B, 1, S H, S W), in place (contiguous float32 on srs's device); bit for bit tiling.scatter(out, srs, plan.windows[w0:w1], t,
+    scale).  One launch of hrn_tile_scatter on the current stream."""
+    srs = _dev_f32(srs, "srs")
+    w0, w1 = _window_range(w0, w1)
+    t, S = int(t), int(scale)
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 4 \
+            or out.shape[1] != 1 or out.device != srs.device or out.numel() == 0:
+        raise ValueError("out must be a contiguous float32 (B, 1, S H, S W) tensor on srs's device")
+    B = out.shape[0]
+    if S not in SCALES or out.shape[2] % S or out.shape[3] % S:
+        raise ValueError(f"scale must be one of {SCALES} and divide out's sides; got scale {scale!r} for out {tuple(out.shape)}")
+    if tuple(srs.shape) != (w1 - w0, B, 1, S * t, S * t):
+        raise ValueError(f"srs must be {(w1 - w0, B, 1, S * t, S * t)}; got {tuple(srs.shape)}")
+    with torch.cuda.device(srs.device):
+        _check(load_library().hrn_tile_scatter(_ptr(srs), B, out.shape[2] // S, out.shape[3] // S, t, int(R), S, w0, w1, _ptr(out), _stream()),
+               "hrn_tile_scatter")
+    return out
+
+
 RESAMPLE_TAPS = 12        # HRN_RESAMPLE_TAPS: weights per output sample in a resampling table
 
 
@@ -827,6 +889,22 @@ def _op_dihedral_mean(y: torch.Tensor, codes: Sequence[int]) -> torch.Tensor:
 @_op_dihedral_mean.register_fake
 def _(y, codes):
     return y.new_empty(tuple(y.shape[1:]), dtype=torch.float32)
+
+
+# the two ends of tiled inference (HRNet.forward_tiled): inference only, so no autograd formula
+@torch.library.custom_op("hrnet_hip::tile_gather", mutates_args=(), device_types="cuda")
+def _op_tile_gather(lrs: torch.Tensor, t: int, R: int, w0: int, w1: int) -> torch.Tensor:
+    return tile_gather(lrs, t, R, w0, w1)
+
+
+@_op_tile_gather.register_fake
+def _(lrs, t, R, w0, w1):
+    return lrs.new_empty((w1 - w0,) + tuple(lrs.shape[:2]) + (t, t), dtype=torch.float32)
+
+
+@torch.library.custom_op("hrnet_hip::tile_scatter", mutates_args=("out",), device_types="cuda")
+def _op_tile_scatter(out: torch.Tensor, srs: torch.Tensor, t: int, R: int, scale: int, w0: int, w1: int) -> None:
+    tile_scatter(out, srs, t, R, scale, w0, w1)
 
 
 # --------------------------------------------------------------------------- the TRAINING entry points as dispatcher-registered ops

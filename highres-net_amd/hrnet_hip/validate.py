@@ -9,8 +9,9 @@ Without a process group the result is the single-process score.
 With a baseline table (the `norm.csv` of a PROBA-V directory: imageset name -> ESA baseline cPSNR) the score is the reference's
 `mean(ESA[name] / shift_cPSNR)` (train.py:213-217), the number that drives its best-checkpoint selection; the batches then carry the
 `names` that collateFunction, load_batch, BatchPrefetcher and DeviceImagesetCache.batches produce as their fifth element.  `ensemble`
-("flip" / "dihedral") scores the self-ensembled prediction (HRNet.forward_ensemble).  `evaluate` is the same pass on one rank that
-also returns the per-imageset cPSNRs.
+("flip" / "dihedral") scores the self-ensembled prediction (HRNet.forward_ensemble).  `tile` predicts through HRNet.forward_tiled
+(windows of that side; scoring stays square-only, because hrn_shift_cpsnr is).  `evaluate` is the same pass on one rank that also
+returns the per-imageset cPSNRs.
 """
 import collections
 
@@ -29,7 +30,7 @@ def shard_indices(n_items, rank, world_size):
 Evaluation = collections.namedtuple("Evaluation", "names cpsnr score")
 
 
-def _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, members_per_pass, keep):
+def _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, members_per_pass, keep, tile=None):
     """The validation loop of train.py:196-215 over this rank's batches, (lrs, alphas, hrs, hr_maps) or (..., names): -> (float64
     sum on the device of cPSNR - or of ESA[name] / cPSNR with a baseline table - or None without a batch, the number of samples,
     names, the list of per-batch float64 cPSNR tensors when `keep`).  The model's training flag is restored."""
@@ -38,6 +39,8 @@ def _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, s
     mode = augment.check_mode(ensemble)
     if mode is not None and not hasattr(fusion_model, "forward_ensemble"):
         raise TypeError(f"ensemble={ensemble!r} needs a model with forward_ensemble (DeepNetworks.HRNet), got {type(fusion_model).__name__}")
+    if tile is not None and not hasattr(fusion_model, "forward_tiled"):
+        raise TypeError(f"tile={tile!r} needs a model with forward_tiled (DeepNetworks.HRNet), got {type(fusion_model).__name__}")
     was_training = fusion_model.training
     fusion_model.eval()
     total, count, all_names, kept = None, 0, [], []
@@ -52,7 +55,9 @@ def _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, s
                     raise ValueError("a baseline table needs batches with names: (lrs, alphas, hrs, hr_maps, names)")
                 if names is not None and len(names) != lrs.shape[0]:
                     raise ValueError(f"{len(names)} names for a batch of {lrs.shape[0]}")
-                if mode is None:
+                if tile is not None:
+                    srs = fusion_model.forward_tiled(lrs, alphas, tile, ensemble=mode, members_per_pass=members_per_pass)[:, 0]
+                elif mode is None:
                     srs = fusion_model(lrs, alphas)[:, 0]
                 else:
                     srs = fusion_model.forward_ensemble(lrs, alphas, mode, members_per_pass)[:, 0]
@@ -73,27 +78,30 @@ def _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, s
     return total, count, all_names, kept
 
 
-def evaluate(fusion_model, batches, baseline_cpsnrs=None, ensemble=None, border_w=3, score_fn=None, members_per_pass=None):
+def evaluate(fusion_model, batches, baseline_cpsnrs=None, ensemble=None, border_w=3, score_fn=None, members_per_pass=None, tile=None):
     """One rank's evaluation pass over `batches` of (lrs, alphas, hrs, hr_maps, names) (names may be left out without a baseline table):
     -> Evaluation(names, cpsnr, score) with the per-imageset shift_cPSNR as a float64 numpy array in batch order and `score` the
     reference's validation score (train.py:209-217): -mean(cPSNR) without a baseline table, mean(ESA[name] / cPSNR) with one
     (`baseline_cpsnrs`: name -> ESA baseline cPSNR).  ensemble: None, or "flip" / "dihedral" to score
     `fusion_model.forward_ensemble(lrs, alphas, ensemble, members_per_pass)` instead of the plain forward.  The sums stay in float64
-    on the device; one read-back at the end.  score_fn as in sharded_val_score."""
-    total, count, names, kept = _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, members_per_pass, True)
+    on the device; one read-back at the end.  score_fn as in sharded_val_score.  tile: None, or the window side with which
+    `fusion_model.forward_tiled(lrs, alphas, tile, ensemble=ensemble, members_per_pass=members_per_pass)` predicts instead."""
+    total, count, names, kept = _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, members_per_pass, True,
+                                               tile)
     if count == 0:
         raise ValueError("evaluate: no sample in `batches`")
     mean = float(total / count)
     return Evaluation(names, torch.cat(kept).cpu().numpy().astype(np.float64), mean if baseline_cpsnrs is not None else -mean)
 
 
-def sharded_val_score(fusion_model, batches, border_w=3, score_fn=None, device=None, baseline_cpsnrs=None, ensemble=None):
+def sharded_val_score(fusion_model, batches, border_w=3, score_fn=None, device=None, baseline_cpsnrs=None, ensemble=None, tile=None):
     """`batches`: this rank's validation batches of (lrs, alphas, hrs, hr_maps) tensors, or the same with `names` as a fifth element
     (the reference loads them one imageset at a time, train.py:281).  Returns `val_score` of train.py:199-217 over ALL ranks' samples:
     -mean(shift_cPSNR), or with `baseline_cpsnrs` (name -> ESA baseline cPSNR; needs the names) mean(ESA[name] / shift_cPSNR).  Either
-    way only (sum, count) is all-reduced.  ensemble: None, or "flip" / "dihedral" to score the model's forward_ensemble.
+    way only (sum, count) is all-reduced.  ensemble: None, or "flip" / "dihedral" to score the model's forward_ensemble.  tile: None, or
+    the window side of the model's forward_tiled, which then predicts (with `ensemble`).
     score_fn(srs (B,S,S), hrs, hr_maps) -> (B,) replaces `hrn_shift_cpsnr` in the CPU rehearsal of the collective (tests/test_dist_cpu.py)."""
-    total, count, _, _ = _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, None, False)
+    total, count, _, _ = _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, None, False, tile)
     if total is None:
         total = torch.zeros((), dtype=torch.float64, device=device or "cpu")
     acc = torch.stack([total.reshape(()), torch.tensor(float(count), dtype=torch.float64, device=total.device)])

@@ -29,6 +29,9 @@
  *   hrn_dihedral_expand / hrn_dihedral_mean  <-  (no counterpart: the reference predicts from one orientation) the two ends of a
  *                              flip / rotate self-ensemble at inference: the K transformed copies of the view stack, and the mean
  *                              of the K predictions after each is transformed back
+ *   hrn_tile_gather / hrn_tile_scatter / hrn_tile_count / hrn_hrnet_halo  <-  (no counterpart in the reference: it predicts
+ *                              square chips whole) the two ends of tiled inference: overlapping square windows of a scene of
+ *                              any size and aspect ratio, and the windows' cores put back into the scene's prediction
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor's data_ptr) unless stated;
@@ -346,6 +349,40 @@ int hrn_collate_device_a(const uint16_t* lr_arena, int64_t lr_elems, const uint1
  * or more 32 x 32 tiles in all. */
 int hrn_dihedral_expand(const float* x, int N, int H, int W, const int32_t* codes, int K, float* out, void* stream);
 int hrn_dihedral_mean(const float* y, int N, int H, int W, const int32_t* codes, int K, float* out, void* stream);
+
+/* ------------------------------------------------------------------ tiled inference: scenes of any size and aspect ratio
+ * No counterpart in the reference, which predicts a square chip whole.  highres-net_amd/hrnet_hip/tiling.py states the rule (halo,
+ * axis_plan, plan, gather, scatter) and is what the tests compare against, bit for bit.
+ *
+ * hrn_hrnet_halo (no counterpart in the reference): R = 2 + 2 * num_layers + 3 * floor(log2 V), the distance in LR pixels beyond
+ * which an LR pixel cannot influence an SR pixel (stem conv, two convs per encoder block, the encoder's final conv, three convs per
+ * fusion level; everything else acts per pixel).  -2 for num_layers outside 0..HRN_MAX_RES_LAYERS or V < 1.
+ *
+ * The plan of an (H, W) scene for square windows of side t <= min(H, W) and halo R: along an axis of length L, with k = t - 2R,
+ *     window i :  core_lo = i == 0 ? 0 : (t - R) + (i - 1) * k,   start = min(max(core_lo - R, 0), L - t),
+ *                 core_hi = start + t == L ? L : start + t - R;      1 window if L == t, else ceil((L - 2R) / k)
+ * and the scene's windows are the row-major product (rows of windows first) of the plans of H and W.  Every window lies inside
+ * the scene, the cores [core_lo, core_hi) partition it, and every core edge is on the scene's border or at least R from its
+ * window's edge - so a window's forward predicts its core exactly as the whole frame's forward does.
+ *
+ * hrn_tile_count (no counterpart in the reference): the number of windows of that plan (>= 1), so that a C caller can size its
+ * loop; -2 for a plan the two kernels refuse.  Host only.
+ *
+ * hrn_tile_gather (no counterpart in the reference): lrs (B,V,H,W) f32 -> out (w1-w0, B, V, t, t) f32, window-major, the windows
+ * w0 <= w < w1 of the plan.  One launch.
+ * hrn_tile_scatter (no counterpart in the reference): srs (w1-w0, B, 1, S t, S t) f32, the forwards of those windows -> their cores
+ * in out (B, 1, S H, S W) f32, S = scale in {2, 3, 4}.  Every output pixel of a core is written once; nothing outside the cores
+ * of [w0, w1) is touched, so scattering every window of the plan, in any chunks and any order, fills `out` exactly.  One launch.
+ * The geometry is computed on the device from (H, W, t, R, window index): no table, no upload, graph-capturable.  Rows whose
+ * source and destination are equally aligned move by 16-byte loads and stores, the others per element; any 4-byte aligned pointer
+ * is accepted.  The two buffers of a call must not overlap.
+ * -2 before any launch, with hrn_last_error() naming the fault: a null pointer, a size that is not positive, t > min(H, W),
+ * t < 2R + 1 while the scene needs more than one window, [w0, w1) empty or outside the plan, a scale outside 2..4, H * W (gather)
+ * or S H * S W (scatter) beyond 32-bit in-plane offsets, or 2^31 or more window rows in one call. */
+int hrn_hrnet_halo(int num_layers, int V);
+int hrn_tile_count(int H, int W, int t, int R);
+int hrn_tile_gather(const float* lrs, int B, int V, int H, int W, int t, int R, int w0, int w1, float* out, void* stream);
+int hrn_tile_scatter(const float* srs, int B, int H, int W, int t, int R, int scale, int w0, int w1, float* out, void* stream);
 
 /* hrn_resample_targets: HR images (elem_bytes 2, uint16) or status maps (elem_bytes 1, uint8, 0 / non-zero) stored at
  * n_in x n_in resampled to n_out x n_out, for a cache whose target scale differs from the ratio the files were stored at
