@@ -1,5 +1,6 @@
 #include "prof.h"
 #include "common.h"
+#include "kernel_test.h"
 #include "../../../include/hrnet_hip.h"
 
 #include <atomic>
@@ -63,7 +64,7 @@ void hrn_count_launch(int which) {
 }
 
 extern "C" {
-// test hooks (not part of include/hrnet_hip.h): launches of counter `name` since the last reset, -1 for a name it does not know
+// the launch counters' test hooks (kernel_test.h)
 long hrn_kt_launch_count(const char* name) {
     for (int i = 0; i < HRN_LC_COUNT; ++i)
         if (name && strcmp(name, g_launch_names[i]) == 0) return g_launches[i].load(std::memory_order_relaxed);

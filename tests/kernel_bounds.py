@@ -1,0 +1,203 @@
+"""The conventions of the per-element kernel tests (tests/test_gpu_kernels_fwd.py, test_gpu_kernels_bwd.py, test_gpu_kernels_shiftnet.py,
+test_gpu_bf16_train.py, test_gpu_shiftnet_bf16.py): the bound |got - want| <= rounding + C T with its one constant C, the sentinel
+patterns, the tensor builders whose values make a kernel's products exact, and the shapes and launcher grids the tests share."""
+import numpy as np
+import torch
+
+from kt import BF16, BF16X3, F32, _cus, _p
+
+C = 1e-5                    # the one constant of every bound (derived in tests/test_gpu_kernels_fwd.py's docstring)
+GUARD = 512                 # sentinel int16 words behind every tensor
+SENT = 0x7F7F               # sentinel bit pattern: bf16 3.4e38, and 0x7F7F7F7F as f32
+NAN16 = 0x7FC0              # NaN as bf16, and 0x7FC07FC0 as f32
+BF = lambda v: float(torch.tensor(v).to(torch.bfloat16))
+
+
+def _ulp_bf16(x):
+    """ulp of bf16 at |x| (fp64 tensor): 2^(e - 7) for |x| in [2^e, 2^(e + 1)), the smallest normal's below it"""
+    _, e = torch.frexp(x.abs().clamp_min(2.0 ** -126))
+    return torch.ldexp(torch.ones_like(x), (e - 8).to(torch.int32))
+
+
+def _rounding(kind, got, want):
+    """the bound's output-rounding term"""
+    if kind == "bf16":
+        return 0.5 * _ulp_bf16(torch.maximum(got.abs(), want.abs()))
+    if kind == "x3":
+        return 2.0 ** -16 * want.abs()
+    return torch.zeros_like(want)
+
+
+def _bound(kind, got, want, T):
+    return _rounding(kind, got, want) + C * T
+
+
+def _ratio(kind, got, want, T):
+    """-> (max error / bound, index of the worst element)"""
+    r = (got - want).abs() / (_bound(kind, got, want, T) + 1e-300)
+    i = int(torch.argmax(r))
+    return float(r.reshape(-1)[i]), np.unravel_index(i, tuple(r.shape))
+
+
+def _assert_close(tag, kind, got, want, T, layout="m c y x"):
+    r, idx = _ratio(kind, got, want, T)
+    c_used = float((((got - want).abs() - _rounding(kind, got, want)).clamp_min(0) / (T + 1e-300)).max())    # the smallest C that passes
+    print(f"{tag}: max error / bound {r:.3e} at ({layout}) = {tuple(int(i) for i in idx)}; C needed {c_used:.2e}")
+    assert r <= 1.0, (f"{tag}: element ({layout}) = {tuple(int(i) for i in idx)}: got {float(got[idx]):.9g}, want {float(want[idx]):.9g}, "
+                      f"bound {float(_bound(kind, got, want, T)[idx]):.3g} (error / bound {r:.3g})")
+    return r
+
+
+def _ulp_ok(got, want, n_ulp=1.0, floor=0.0):
+    """|got - want| <= n_ulp bf16 ulps of want (+ floor): got a bf16 tensor, want fp64"""
+    got, want = got.double().cpu(), want.double().cpu()
+    e = torch.floor(torch.log2(want.abs().clamp_min(1e-30)))
+    ulp = torch.pow(2.0, e - 7)
+    bad = (got - want).abs() > n_ulp * ulp + floor
+    return int(bad.sum()), float(((got - want).abs() / ulp).max())
+
+
+# (H, W); "multi": many 3 x 33 images, enough that a workgroup walks two tiles at least
+SHAPES = {"1x1": (1, 1), "2x3": (2, 3), "9x27": (9, 27), "15x33": (15, 33), "17x50": (17, 50), "9x63": (9, 63), "16x64": (16, 64),
+          "multi": (3, 33)}
+
+
+def _grid(route, cout, total):
+    """the launcher's persistent grid: r64 / v6 / v6x3 min(CUs, total), the general kernel min((2 / (cout / 64)) CUs, total); & ~7"""
+    g = (2 // (cout // 64)) * _cus() if route == 1 else _cus()
+    g = min(g, total)
+    return g & ~7 if g >= 8 else g
+
+
+def _tiles(dt, route, cin, cout, H, W):
+    th, tw = (8, 32) if route == 1 or (dt == BF16 and cin == 64 and cout == 64) else (16, 32)   # conv3x3.hip / r64: 8 x 32; v6 / v6x3: 16 x 32
+    return -(-H // th) * -(-W // tw)
+
+
+def _bf(shape, seed, scale=1.0):
+    """a bf16 device tensor (and its exact fp64 CPU copy) of random values"""
+    g = torch.Generator().manual_seed(seed)
+    t = (torch.randn(shape, generator=g) * scale).to(torch.bfloat16)
+    return t.cuda(), t.double()
+
+
+def _x3(shape, seed, scale=1.0):
+    """a bf16x3 device tensor (2, *shape) - plane 0 hi = bf16(v), plane 1 lo = bf16(v - hi) of random fp32 v, the lo plane directly behind
+    the hi plane - and the exact fp64 CPU value hi + lo"""
+    g = torch.Generator().manual_seed(seed)
+    v = torch.randn(shape, generator=g) * scale
+    hi = v.to(torch.bfloat16)
+    lo = (v - hi.float()).to(torch.bfloat16)
+    return torch.stack([hi, lo]).cuda(), hi.double() + lo.double()
+
+
+def _f32(shape, seed, scale=1.0):
+    """an f32 device tensor of bf16-representable random values (and its exact fp64 CPU copy): the fp32 kernels' products are exact too"""
+    t, t64 = _bf(shape, seed, scale)
+    return t.float().contiguous(), t64
+
+
+def _nchw(t):
+    return t.permute(0, 3, 1, 2)
+
+
+def _pair_gather(stack, half, pair_last):
+    """stack (B, n, H, W, 64) -> (B * half, H, W, 128): cat(view i, view pair_last - i) on channels"""
+    B = stack.shape[0]
+    idx = torch.arange(half)
+    return torch.cat([stack[:, idx], stack[:, pair_last - idx]], -1).reshape((B * half,) + tuple(stack.shape[2:4]) + (128,))
+
+
+def _quantised(shape, seed, levels=16, scale=0.25):
+    """bf16-exact values on a coarse grid (k / 8 * scale, |k| < levels): many ties inside pool windows"""
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randint(-levels, levels, shape, generator=g).double() / 8 * scale)
+
+
+def _exact_affine(C, seed):
+    """scale a power of two, shift on a coarse bf16 grid: x * scale + shift is exact in fp32 for the quantised x"""
+    g = torch.Generator().manual_seed(seed)
+    sc = torch.pow(2.0, torch.randint(-1, 2, (C,), generator=g).float())
+    sh = torch.randint(-4, 5, (C,), generator=g).float() / 16
+    return sc, sh
+
+
+def q16(v):
+    """fp32 tensor -> at most 16 significant bits: hi + lo of its bf16 split is then exact, in fp32 too"""
+    return (v.contiguous().view(torch.int32) & ~0xFF).view(torch.float32)
+
+
+def rnd(shape, seed, dt, scale=1.0):
+    """random fp32 values representable in storage dt with at most 16 significant bits (bf16: 8)"""
+    v = torch.randn(shape, generator=torch.Generator().manual_seed(seed)) * scale
+    return v.to(torch.bfloat16).float() if dt == BF16 else q16(v)
+
+
+class Ten:
+    """a tensor in storage dt inside an int16 device buffer: f32 (two words per element), one bf16 plane, or bf16x3 = the hi plane and the
+    lo plane directly behind it (as every backward kernel derives it from the element count); GUARD sentinels behind.  v: fp32 CPU values
+    (rounded to bf16 for BF16; split into hi + lo for BF16X3), or None: filled with `fill`.  val: the exact fp64 value the kernel reads."""
+
+    def __init__(self, shape, dt, v=None, fill=SENT):
+        self.shape, self.dt = tuple(shape), dt
+        self.n = int(np.prod(shape))
+        self.words = self.n * (1 if dt == BF16 else 2)
+        raw = torch.full((self.words + GUARD,), SENT, dtype=torch.int16)
+        raw[:self.words] = fill
+        self.val = None
+        if v is not None:
+            v = v.contiguous().reshape(-1)
+            assert v.dtype == torch.float32 and v.numel() == self.n
+            if dt == F32:
+                raw[:self.words], self.val = v.view(torch.int16), v.double()
+            else:
+                hi = v.to(torch.bfloat16)
+                raw[:self.n], self.val = hi.view(torch.int16), hi.double()
+                if dt == BF16X3:
+                    lo = (v - hi.float()).to(torch.bfloat16)
+                    raw[self.n:2 * self.n], self.val = lo.view(torch.int16), hi.double() + lo.double()
+            self.val = self.val.reshape(self.shape)
+        self.bits0 = raw
+        self.raw = raw.cuda()
+
+    @property
+    def ptr(self):
+        return _p(self.raw)
+
+    def planes(self):
+        """the payload as CPU tensors: [f32] or [hi] or [hi, lo]"""
+        raw = self.raw[:self.words].cpu()
+        if self.dt == F32:
+            return [raw.view(torch.float32).reshape(self.shape)]
+        return [raw[k * self.n:(k + 1) * self.n].view(torch.bfloat16).reshape(self.shape) for k in range(self.words // self.n)]
+
+    def value(self):
+        return sum(p.double() for p in self.planes())
+
+    def unchanged(self):
+        return torch.equal(self.raw.cpu(), self.bits0)
+
+    def guard_ok(self):
+        return bool((self.raw[self.words:] == SENT).all())
+
+
+class Acc:
+    """an f32 gradient the kernel accumulates into (+=): starts from random values, NaN guard behind; none = True: handed over as NULL"""
+
+    def __init__(self, shape, seed, none=False):
+        self.shape, self.n = tuple(shape), int(np.prod(shape))
+        self.start = torch.randn(self.n, generator=torch.Generator().manual_seed(seed))
+        self.buf = None if none else torch.cat([self.start, torch.full((64,), float("nan"))]).cuda()
+
+    @property
+    def ptr(self):
+        return _p(self.buf)
+
+    def check(self, tag, want, T, c=C, layout="i"):
+        """got against start + want, T = |start| + sum |terms|"""
+        if self.buf is None:
+            return None
+        got = self.buf.double().cpu()
+        assert bool(torch.isnan(got[self.n:]).all()), f"{tag}: a write past the gradient"
+        s0 = self.start.double().reshape(self.shape)
+        return _assert_close(tag, "f32", got[:self.n].reshape(self.shape), s0 + want, (s0.abs() + T) * (c / C), layout=layout)

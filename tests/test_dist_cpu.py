@@ -1,10 +1,11 @@
 """CPU, world_size 2, gloo: the N>1 plumbing bench.py relies on (rendezvous on 127.0.0.1, barrier, max-over-ranks
 timing, contiguous batch shards, whole-job frame count)."""
 import os
-import socket
 import subprocess
 import sys
 import textwrap
+
+from util import _free_port
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -32,14 +33,6 @@ WORKER = textwrap.dedent("""
         print(json.dumps({"value": frames / t, "n_gpus": ws}))
     hdist.finalize()
 """) % ROOT
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def test_two_rank_gloo_plumbing(tmp_path):

@@ -3,7 +3,6 @@ hrnet_hip/augment.py (ensemble_codes, expand, mean_inverse), the refusals of hrn
 launched), the fake kernels of the two dispatcher ops, and hrnet_hip.validate.evaluate / sharded_val_score on CPU stand-ins."""
 import ctypes
 import os
-import socket
 import subprocess
 import sys
 import textwrap
@@ -13,7 +12,7 @@ import pytest
 import torch
 
 from hrnet_hip import augment
-from oracle import hrnet_np as O
+from util import Toy, _esa_table, _free_port, _score, _sets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -172,39 +171,6 @@ def test_hrnet_ensemble_attribute():
 
 
 # --------------------------------------------------------------------------- evaluate / sharded_val_score on CPU stand-ins
-class Toy(torch.nn.Module):
-    """Bicubic x3 of the first view; its "ensemble" is the rule of augment.py around its own forward."""
-
-    def forward(self, lrs, alphas):
-        return torch.nn.functional.interpolate(lrs[:, :1], scale_factor=3, mode="bicubic", align_corners=False)
-
-    def forward_ensemble(self, lrs, alphas, mode="dihedral", members_per_pass=None):
-        codes = augment.ensemble_codes(mode)
-        self.seen = (mode, members_per_pass)
-        y = torch.stack([self.forward(m, alphas) for m in augment.expand(lrs, codes)])
-        return augment.mean_inverse(y, codes)
-
-
-def _score(srs, hrs, maps):
-    return torch.tensor([O.shift_cpsnr(np.clip(s.numpy(), 0, 1), h.numpy(), m.numpy()) for s, h, m in zip(srs, hrs, maps)])
-
-
-def _sets(n, with_names=True, batch=1):
-    g = torch.Generator().manual_seed(3)
-    sets = []
-    for i in range(n):
-        b = batch + (i % 2 if batch > 1 else 0)
-        item = (torch.rand(b, 3, 16, 16, generator=g), torch.ones(b, 3), torch.rand(b, 48, 48, generator=g),
-                (torch.rand(b, 48, 48, generator=g) > 0.1).float())
-        sets.append(item + ([f"imgset{i:04d}_{j}" for j in range(b)],) if with_names else item)
-    return sets
-
-
-def _esa_table(sets):
-    rng = np.random.Generator(np.random.PCG64(9))
-    return {n: float(40 + 10 * rng.random()) for s in sets for n in s[4]}
-
-
 def test_evaluate_esa_score_is_the_references_formula():
     from hrnet_hip import validate
     sets = _sets(5, batch=2)
@@ -286,7 +252,7 @@ VAL_WORKER = textwrap.dedent("""
     sys.path.insert(0, os.path.join(%r, "tests"))
     import numpy as np, torch
     from hrnet_hip import dist as hdist, validate
-    import test_ensemble_host as T
+    import util as T
     rank, local_rank, ws = hdist.init(backend="gloo")
     sets = T._sets(7)                                       # 7 imagesets dealt round-robin: rank 0 scores 4, rank 1 scores 3
     table = T._esa_table(sets)
@@ -304,14 +270,6 @@ VAL_WORKER = textwrap.dedent("""
     print("esa val score ok", rank, got)
     hdist.finalize()
 """) % (ROOT, ROOT, ROOT)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def test_two_rank_esa_validation(tmp_path):

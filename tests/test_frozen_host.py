@@ -8,22 +8,19 @@ import re
 import pytest
 
 from hrnet_hip import binding
+import kt
+from kt import COUNTERS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("hrn_hrnet_backward_sel", "hrn_shiftnet_backward_sel")
-COUNTERS = ("conv_wgrad_f32", "stem_wgrad", "prelu_bwd", "bias_finish", "slope_finish", "conv_dgrad", "decoder_bwd", "decoder_bwd_finish",
-            "fuse_scatter", "sn_bn_bwd", "fc2_bwd", "fc1_bwd_w", "fc1_bwd_x")
 
 
 @pytest.fixture(scope="module")
 def lib():
     try:
-        lib = binding.load_library()
+        return kt.lib()
     except (RuntimeError, OSError) as e:
         pytest.skip(f"libhrnet_hip.so not built: {e}")
-    lib.hrn_kt_launch_count.restype = ctypes.c_long
-    lib.hrn_kt_launch_count.argtypes = [ctypes.c_char_p]
-    return lib
 
 
 def test_declared_bound_and_exported(lib):

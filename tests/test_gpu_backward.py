@@ -12,44 +12,9 @@ import torch
 
 from oracle import synth, torch_port, weights
 import util
+from util import NONPOS, _SLOPE_KEYS, _fresh_model, _get_loss_cpsnr, _oracle_grads, _register_batch
 
 pytestmark = pytest.mark.gpu
-
-
-_SLOPE_KEYS = ["encode.init_layer.1.weight", "encode.res_layers.0.block.1.weight", "encode.res_layers.0.block.3.weight",
-               "encode.res_layers.1.block.1.weight", "encode.res_layers.1.block.3.weight", "fuse.fuse.0.block.1.weight",
-               "fuse.fuse.0.block.3.weight", "fuse.fuse.2.weight", "decode.deconv.1.weight"]
-
-
-def _fresh_model(alpha_residual=True, seed=1234, slopes=None, precision="fp32"):
-    from DeepNetworks.HRNet import HRNet
-    cfg = {k: dict(v) for k, v in weights.HRNET_CONFIG.items()}
-    cfg["recursive"]["alpha_residual"] = alpha_residual
-    m = HRNet(cfg)
-    st = weights.to_torch_state(weights.hrnet_state(seed))
-    st.update({k: torch.full_like(st[k], v) for k, v in (slopes or {}).items()})
-    m.load_state_dict(st)
-    m.precision = precision
-    return m.cuda().train()
-
-
-def _oracle_grads(lrs, alphas, cot, alpha_residual, seed=1234, slopes=None):
-    st = weights.to_torch_state(weights.hrnet_state(seed))
-    st.update({k: torch.full_like(st[k], v) for k, v in (slopes or {}).items()})
-    st = {k: v.double().requires_grad_(True) for k, v in st.items()}
-    abs_terms = {}
-    torch_port.ABS_TERMS = abs_terms             # sum |terms| of every single-slope / final-bias gradient (oracle/torch_port.py)
-    try:
-        with torch.enable_grad():
-            sr = torch_port.hrnet_forward.__wrapped__(torch.from_numpy(lrs).double(), torch.from_numpy(alphas).double(), st,
-                                                      num_layers=weights.HRNET_CONFIG["encoder"]["num_layers"], alpha_residual=alpha_residual)
-            (sr * torch.from_numpy(cot).double()).sum().backward()
-    finally:
-        torch_port.ABS_TERMS = None
-    # parameters the graph never touched (the fusion block when V == 1) have no gradient in torch: zero here
-    grads = {k: (v.grad.numpy() if v.grad is not None else np.zeros(tuple(v.shape))) for k, v in st.items()}
-    grads["__abs_terms__"] = abs_terms
-    return sr.detach().numpy(), grads
 
 
 @pytest.mark.parametrize("B,V,S,n_real,alpha_residual", [
@@ -219,11 +184,6 @@ def test_bf16x3_training_tracks_fp32_training():
     assert rel.max() <= 2e-2, rel
 
 
-NONPOS = {"encode.init_layer.1.weight": -0.2, "encode.res_layers.0.block.1.weight": 0.0, "encode.res_layers.0.block.3.weight": -0.05,
-          "encode.res_layers.1.block.3.weight": -0.3, "fuse.fuse.0.block.1.weight": -0.1, "fuse.fuse.0.block.3.weight": 0.0,
-          "fuse.fuse.2.weight": -0.25, "decode.deconv.1.weight": -0.1}
-
-
 @pytest.mark.parametrize("slopes", [NONPOS, {"fuse.fuse.2.weight": -0.25}, {"encode.res_layers.1.block.1.weight": 1.5}])
 def test_hrnet_backward_with_nonpositive_slopes(slopes):
     """nn.PReLU puts no constraint on its slope and training can drive one through zero.  With a positive slope the HIP backward reads
@@ -371,18 +331,6 @@ def test_shiftnet_backward_vs_autograd(B):
 
 
 # ----------------------------------------------------------------------------- the whole train step of src/train.py
-def _register_batch(shiftNet, lrs, reference):                 # train.py:26-44, restated
-    thetas = [shiftNet(torch.cat([reference, lrs[:, i:i + 1]], 1)) for i in range(lrs.size(1))]
-    return torch.stack(thetas, 1)
-
-
-def _get_loss_cpsnr(srs, hrs, hr_maps):                        # train.py:66-87, metric='cPSNR'
-    nclear = torch.sum(hr_maps, dim=(1, 2))
-    bright = torch.sum(hr_maps * (hrs - srs), dim=(1, 2)).clone().detach() / nclear
-    loss = torch.sum(hr_maps * (srs + bright.view(-1, 1, 1) - hrs) ** 2, dim=(1, 2)) / nclear
-    return -10 * torch.log10(loss)
-
-
 def test_full_train_step_vs_autograd_oracle():
     """srs = fusion_model(lrs, alphas); shifts = register_batch(...); srs_shifted = apply_shifts(...); loss = -cPSNR + lambda
     mean(shifts)^2; loss.backward()  (train.py:172-190) on the HIP modules, against the same chain in fp64 torch on the CPU."""

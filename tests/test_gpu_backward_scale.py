@@ -22,12 +22,11 @@ import pytest
 import torch
 
 from oracle import synth
-import test_gpu_backward as gb
 import util
 
 pytestmark = pytest.mark.gpu
 
-_ONES = {k: 1.0 for k in gb._SLOPE_KEYS}
+_ONES = {k: 1.0 for k in util._SLOPE_KEYS}
 RED_BLOCKS = 512                        # csrc/backward.hip: RED_BLOCKS, the grid of colsum_kernel / prelu_bwd_bias_kernel
 
 
@@ -81,7 +80,7 @@ def _multi_tile_oracle():
         lrs, alphas, _ = synth.make_batch(5, B, V, S, _MT["n_real"])
         cot = np.random.Generator(np.random.PCG64(77)).standard_normal((B, 1, 3 * S, 3 * S)).astype(np.float32)
         t0 = time.perf_counter()
-        want_sr, want = gb._oracle_grads(lrs, alphas, cot, True, slopes=_ONES)
+        want_sr, want = util._oracle_grads(lrs, alphas, cot, True, slopes=_ONES)
         _oracle_cache.update(lrs=lrs, alphas=alphas, cot=cot, want_sr=want_sr, want=want, seconds=time.perf_counter() - t0)
     return _oracle_cache
 
@@ -106,7 +105,7 @@ def test_hrnet_backward_multi_tile_vs_autograd_oracle(prec):
 
     o = _multi_tile_oracle()
     lrs, alphas, cot, want = o["lrs"], o["alphas"], o["cot"], o["want"]
-    m = gb._fresh_model(True, precision=prec, slopes=_ONES)
+    m = util._fresh_model(True, precision=prec, slopes=_ONES)
     t0 = time.perf_counter()
     sr = m(util.dev(lrs), util.dev(alphas))
     (sr * util.dev(cot)).sum().backward()
@@ -159,7 +158,7 @@ def test_bf16x3_vs_fp32_gradients_at_train_shape():
     cot = np.random.Generator(np.random.PCG64(78)).standard_normal((B, 1, 3 * S, 3 * S)).astype(np.float32)
     out, grads = {}, {}
     for prec in ("fp32", "bf16x3"):
-        m = gb._fresh_model(True, precision=prec, slopes=_ONES)
+        m = util._fresh_model(True, precision=prec, slopes=_ONES)
         sr = m(util.dev(lrs), util.dev(alphas))
         (sr * util.dev(cot)).sum().backward()
         out[prec] = sr.detach().cpu().numpy()

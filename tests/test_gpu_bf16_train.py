@@ -5,7 +5,6 @@ Kernel-level checks feed bf16-representable inputs, so that every product is exa
 the convolutions, the one rounding of the stored output) separates the kernels from fp64.  End to end the bf16 path is held to fp64
 autograd through oracle/torch_port with relative L2 bounds set from measurement (the bf16 forward alone is ~1e-2 from fp32).
 """
-import ctypes
 import warnings
 
 import numpy as np
@@ -15,96 +14,11 @@ import torch.nn.functional as F
 
 from oracle import synth
 import util
-from test_gpu_backward import NONPOS, _SLOPE_KEYS, _fresh_model, _oracle_grads
-from test_gpu_input_grad import _oracle as _oracle_in, _tie_invariant_err
-from test_gpu_upscale import _model
+from kernel_bounds import _bf, _f32, _nchw, _pair_gather, _x3
+from kt import BF16, BF16X3, F32, _cus, _p, _stream, lib as _lib
+from util import NONPOS, _SLOPE_KEYS, _fresh_model, _model, _oracle as _oracle_in, _oracle_grads
 
 pytestmark = pytest.mark.gpu
-
-F32, BF16, BF16X3 = 0, 1, 2
-
-
-def _lib():
-    from hrnet_hip import binding
-    lib = binding.load_library()
-    vp, i, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-    lib.hrn_kt_wgrad_scratch_bytes.restype = ctypes.c_size_t
-    lib.hrn_kt_wgrad_scratch_bytes.argtypes = []
-    lib.hrn_kt_conv_wgrad.restype = i
-    lib.hrn_kt_conv_wgrad.argtypes = [i, vp, vp, i, i, i, vp, i, i, i, i, i, vp, vp, vp]
-    lib.hrn_kt_conv_dgrad.restype = i
-    lib.hrn_kt_conv_dgrad.argtypes = [i, i, i, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp]
-    lib.hrn_kt_conv3x3.restype = i
-    lib.hrn_kt_conv3x3.argtypes = [i, i, i, vp, vp, i, i, i, vp, vp, vp, i, i, i, vp]
-    lib.hrn_kt_conv3x3_epi.restype = i
-    lib.hrn_kt_conv3x3_epi.argtypes = [i, i, i, i, vp, vp, i, i, i, vp, vp, vp, vp, i, i, vp, i, vp, i, i, sz, sz, sz, sz, i, i, i, vp]
-    lib.hrn_kt_conv_pack.restype = i
-    lib.hrn_kt_conv_pack.argtypes = [i, i, i, vp, vp, vp]
-    lib.hrn_kt_stem.restype = i
-    lib.hrn_kt_stem.argtypes = [i, vp, sz, vp, i, sz, vp, vp, vp, vp, vp, sz, i, i, i, vp]
-    lib.hrn_kt_decoder.restype = i
-    lib.hrn_kt_decoder.argtypes = [i, i, vp, sz, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]
-    # the backward's non-convolution launchers (tests/test_gpu_kernels_bwd.py)
-    for name, args in (("prelu_bwd_bias", [i, vp, vp, vp, vp, vp, sz, i, vp, vp, vp, vp]), ("colsum", [i, vp, sz, i, vp, vp, vp]),
-                       ("add", [i, vp, vp, vp, sz, vp]), ("fuse_update", [i, vp, i, vp, vp, i, i, i, i, vp, sz, i, vp]),
-                       ("fuse_df", [i, vp, vp, i, i, i, i, vp, sz, i, vp]), ("fuse_scatter", [i, vp, vp, i, i, i, i, vp, sz, i, vp]),
-                       ("alpha_grad", [i, vp, vp, i, i, vp, i, i, sz, vp, sz, vp]),
-                       ("stem_wgrad", [i, vp, sz, vp, i, sz, vp, vp, i, i, i, vp, vp, vp]),
-                       ("stem_dgrad_route", [i, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]),
-                       ("stem_pre", [i, vp, sz, vp, i, sz, vp, vp, vp, i, i, i, vp, vp]),
-                       ("decoder_bwd", [i] + [vp] * 12 + [i, i, i, vp, vp]), ("planes_to_f32", [vp, sz, vp, sz, vp]),
-                       ("f32_to_planes", [vp, vp, sz, sz, vp]), ("median", [vp, vp, i, i, i, i, vp])):
-        fn = getattr(lib, "hrn_kt_" + name)
-        fn.restype, fn.argtypes = i, args
-    lib.hrn_kt_alpha_grad_scratch_bytes.restype = ctypes.c_size_t
-    lib.hrn_kt_alpha_grad_scratch_bytes.argtypes = [i]
-    return lib
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _bf(shape, seed, scale=1.0):
-    """a bf16 device tensor (and its exact fp64 CPU copy) of random values"""
-    g = torch.Generator().manual_seed(seed)
-    t = (torch.randn(shape, generator=g) * scale).to(torch.bfloat16)
-    return t.cuda(), t.double()
-
-
-def _x3(shape, seed, scale=1.0):
-    """a bf16x3 device tensor (2, *shape) - plane 0 hi = bf16(v), plane 1 lo = bf16(v - hi) of random fp32 v, the lo plane directly behind
-    the hi plane - and the exact fp64 CPU value hi + lo"""
-    g = torch.Generator().manual_seed(seed)
-    v = torch.randn(shape, generator=g) * scale
-    hi = v.to(torch.bfloat16)
-    lo = (v - hi.float()).to(torch.bfloat16)
-    return torch.stack([hi, lo]).cuda(), hi.double() + lo.double()
-
-
-def _f32(shape, seed, scale=1.0):
-    """an f32 device tensor of bf16-representable random values (and its exact fp64 CPU copy): the fp32 kernels' products are exact too"""
-    t, t64 = _bf(shape, seed, scale)
-    return t.float().contiguous(), t64
-
-
-def _nchw(t):
-    return t.permute(0, 3, 1, 2)
-
-
-def _cus():
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def _pair_gather(stack, half, pair_last):
-    """stack (B, n, H, W, 64) -> (B * half, H, W, 128): cat(view i, view pair_last - i) on channels"""
-    B = stack.shape[0]
-    idx = torch.arange(half)
-    return torch.cat([stack[:, idx], stack[:, pair_last - idx]], -1).reshape((B * half,) + tuple(stack.shape[2:4]) + (128,))
 
 
 # ----------------------------------------------------------------------------- 1. the ABI and the ops accept BF16

@@ -13,7 +13,9 @@ import textwrap
 
 import pytest
 
-from test_dist_cpu import _free_port, ROOT
+from util import _free_port
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 

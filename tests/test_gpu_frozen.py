@@ -7,14 +7,14 @@ hrn_shiftnet_backward_sel and the registered ops hrnet_backward_sel / shiftnet_b
    nothing downstream reads, and the all-trainable step launches exactly what the entry points of the parent release launch.
 """
 import copy
-import ctypes
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import weights
-from test_gpu_upscale import _state
+from kt import _launches
+from util import _state
 
 pytestmark = pytest.mark.gpu
 
@@ -26,37 +26,6 @@ PATTERNS = {
     "hrnet+inputs": lambda k: True,
     "one_slope": lambda k: k == "fuse.fuse.2.weight",
 }
-
-
-def _lib():
-    from hrnet_hip import binding
-    lib = binding.load_library()
-    lib.hrn_kt_launch_count.restype = ctypes.c_long
-    lib.hrn_kt_launch_count.argtypes = [ctypes.c_char_p]
-    return lib
-
-
-COUNTERS = ("conv_wgrad_f32", "stem_wgrad", "prelu_bwd", "bias_finish", "slope_finish", "conv_dgrad", "decoder_bwd", "decoder_bwd_finish",
-            "fuse_scatter", "sn_bn_bwd", "fc2_bwd", "fc1_bwd_w", "fc1_bwd_x")
-
-
-def _launches(fn):
-    """Run fn() with the launch counters reset and the profiler on -> {name: launches} of both (profiled families as 'prof:<family>')."""
-    from hrnet_hip import binding
-    lib = _lib()
-    torch.cuda.synchronize()
-    lib.hrn_kt_launch_count_reset()
-    binding.profile_enable(True)
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-    finally:
-        binding.profile_enable(False)
-    got = {c: lib.hrn_kt_launch_count(c.encode()) for c in COUNTERS}
-    assert all(v >= 0 for v in got.values()), got
-    for name, row in binding.profile_read().items():
-        got["prof:" + name] = row["launches"]
-    return got, out
 
 
 def _hrnet(scale, prec, alpha_residual=True):

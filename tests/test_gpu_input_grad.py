@@ -1,7 +1,7 @@
 """GPU (-m gpu): HRNet's input gradients, d lrs and d alphas (reference HRNet.py:198-204 and :113-132), through
 hrn_hrnet_backward_in.
 
-Oracle: fp64 torch autograd on the CPU through oracle/torch_port.hrnet_forward (tests/test_gpu_upscale._hrnet_forward_s at x2 / x4)
+Oracle: fp64 torch autograd on the CPU through oracle/torch_port.hrnet_forward (tests/util._hrnet_forward_s at x2 / x4)
 with lrs and alphas requiring grad.  The reference frame is the lower median of the first min(V, 9) views; torch.median's gradient goes
 to the one index it returns, which torch leaves open among tied views (the zero padding views always tie).  So every oracle runs twice:
 as is (torch's routing), and with the median's values as a separate leaf, which yields the stem's channel-0 gradient per view (c0) and
@@ -9,47 +9,15 @@ the reference frame's gradient (R) apart.  The HIP side must then
   - agree with torch's routing tie-invariantly: elementwise where the median is unique, summed over the tied views where it is not;
   - put R on exactly one view per pixel, the lowest-indexed tied one (the documented rule): c0 + R there, c0 elsewhere.
 """
-import types
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import synth, torch_port, weights
 import util
-from test_gpu_backward import _SLOPE_KEYS, _fresh_model
-from test_gpu_upscale import _hrnet_forward_s, _model, _state
+from util import _SLOPE_KEYS, _forward, _fresh_model, _model, _oracle, _real_median, _state, _tie_invariant_err
 
 pytestmark = pytest.mark.gpu
-
-_real_median = torch.median
-
-
-def _forward(x, a, st, alpha_residual, scale):
-    return _hrnet_forward_s(x, a, st, num_layers=weights.HRNET_CONFIG["encoder"]["num_layers"], alpha_residual=alpha_residual, scale=scale)
-
-
-def _oracle(lrs, alphas, cot, alpha_residual, slopes=None, scale=3, split=False):
-    """-> (d lrs, d alphas or None, R or None).  split: the median's values as a leaf of their own, so d lrs is c0 and R comes apart."""
-    st = {k: v.double() for k, v in _state(scale, slopes=slopes).items()}
-    x = torch.from_numpy(lrs).double().requires_grad_(True)
-    a = torch.from_numpy(alphas).double().requires_grad_(True)
-    leaves = []
-
-    def median(t, dim, keepdim=False):
-        r = _real_median(t.detach(), dim, keepdim=keepdim)
-        leaf = r.values.clone().requires_grad_(True)
-        leaves.append(leaf)
-        return types.SimpleNamespace(values=leaf, indices=r.indices)
-
-    try:
-        if split:
-            torch.median = median
-        with torch.enable_grad():
-            (_forward(x, a, st, alpha_residual, scale) * torch.from_numpy(cot).double()).sum().backward()
-    finally:
-        torch.median = _real_median
-    return x.grad.numpy(), (None if a.grad is None else a.grad.numpy()), (leaves[0].grad.numpy()[:, 0] if split else None)
 
 
 def _check(got_lrs, got_alphas, lrs, alphas, cot, alpha_residual, slopes=None, scale=3, tol=2e-4):
@@ -86,19 +54,6 @@ def _check(got_lrs, got_alphas, lrs, alphas, cot, alpha_residual, slopes=None, s
         err = np.abs(got_alphas - want_alphas)
         bound = 2e-5 * _abs_alpha_terms(lrs, alphas, cot, alpha_residual, slopes, scale) + 1e-12
         assert (err <= bound).all(), (err, bound)
-
-
-def _tie_invariant_err(got, want, lrs):
-    """max-norm relative error of d lrs with the tied views of each pixel (several of the first min(V, 9) equal to the median) compared
-    by their sum, every other element directly."""
-    n = min(lrs.shape[1], 9)
-    med = _real_median(torch.from_numpy(lrs[:, :n]), 1).values.numpy()
-    tied = lrs[:, :n] == med[:, None]
-    multi = np.broadcast_to(tied.sum(1)[:, None] > 1, tied.shape)
-    direct = np.concatenate([~multi, np.ones((lrs.shape[0], lrs.shape[1] - n) + lrs.shape[2:], bool)], 1)
-    e = np.abs(got - want)[direct].max(initial=0.0)
-    e_sum = np.abs(np.where(tied, got[:, :n], 0).sum(1) - np.where(tied, want[:, :n], 0).sum(1)).max()
-    return float(max(e, e_sum) / max(np.abs(want).max(), 1e-30))
 
 
 def _abs_alpha_terms(lrs, alphas, cot, alpha_residual, slopes=None, scale=3):
@@ -188,7 +143,6 @@ def test_full_train_step_input_grad_vs_autograd_oracle():
     in fp64.  The chain is ill-conditioned in fp32 (see test_gpu_backward.test_full_train_step_vs_autograd_oracle): 2e-2 of the
     max-norm, where torch's own fp32 autograd is 3e-3..7e-3 off."""
     from DeepNetworks.ShiftNet import ShiftNet
-    import test_gpu_backward as TB
     B, V, S, lam = 2, 3, 48, 1e-6
     lrs, alphas, hrs = synth.make_batch(31, B, V, S, V)
     rng = np.random.Generator(np.random.PCG64(5))
@@ -216,13 +170,13 @@ def test_full_train_step_input_grad_vs_autograd_oracle():
     try:
         torch.rand = lambda *s, **k: (dmask.float() * 0.75 + 0.125).reshape(s[0]) if s and tuple(s[0]) == (B, 32768) else orig_rand(*s, **k)
         g_srs = fusion(g_x, g_a)
-        g_shifts = TB._register_batch(regis, g_srs[:, :, off:off + 128, off:off + 128],
+        g_shifts = util._register_batch(regis, g_srs[:, :, off:off + 128, off:off + 128],
                                       d_hrs[:, off:off + 128, off:off + 128].reshape(-1, 1, 128, 128))
         bsz, nv, hh, ww = g_srs.shape
         g_shifted = regis.transform(g_shifts.view(-1, 2), g_srs.view(-1, 1, hh, ww), device="cuda").view(-1, nv, hh, ww)[:, 0]
     finally:
         torch.rand = orig_rand
-    g_loss = -TB._get_loss_cpsnr(g_shifted, d_hrs, util.dev(crop * maps))
+    g_loss = -util._get_loss_cpsnr(g_shifted, d_hrs, util.dev(crop * maps))
     g_loss = g_loss.mean() + lam * g_shifts.mean() ** 2
     g_loss.backward()
     assert abs(float(g_loss.detach()) - float(loss.detach())) <= 2e-4 * abs(float(loss.detach()))

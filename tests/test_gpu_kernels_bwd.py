@@ -1,11 +1,11 @@
 """GPU (-m gpu): the non-convolution kernels of HRNet's backward, per element, against torch CPU float64.
 
-Each launcher is called on its own through kernel_test.hip (hrn_kt_*), exactly as train.hip / api.hip call it, on the stored tensors it
-would see in production; the reference (the ref_* functions below, checked against torch autograd by tests/test_kernels_bwd_host.py) is
+Each launcher is called on its own through the hooks of kernel_test.h (hrn_kt_*, bound by tests/kt.py), exactly as train.hip / api.hip call it, on the stored tensors it
+would see in production; the reference (the ref_* functions of tests/kernel_refs.py, checked against torch autograd by tests/test_kernels_bwd_host.py) is
 the same operation in fp64 on the exact values the kernel reads (hi + lo for bf16x3), so no PReLU sign can differ between the two.
 Operands are chosen so that the products a kernel forms in fp32 are exact (dy / dsn of at most 16 significant bits, slopes 0.25, 1,
 BF(-0.3), 1.5, 2^-20, 0; alphas 0, 1, 0.75): only the accumulation order and one rounding of the stored output remain.
-Bound per element, T = the same expression on absolute values, C = test_gpu_kernels_fwd.C = 1e-5 (168 fp32 roundings):
+Bound per element, T = the same expression on absolute values, C = kernel_bounds.C = 1e-5 (168 fp32 roundings):
   bf16 output                          |got - want| <= 1/2 ulp_bf16(max(|got|, |want|)) + C T
   bf16x3 output (hi + lo)              |got - want| <= 2^-16 |want| + C T
   f32 output, every parameter gradient |got - want| <= C T       (accumulated gradients: want = start + sum, T = |start| + sum |terms|)
@@ -37,307 +37,25 @@ Negative controls (test_negative_control) run on the CPU against the GPU output 
 """
 import ctypes
 
-import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
-from test_gpu_kernels_fwd import C, _assert_close, _bound, _ratio, _rounding, _ulp_bf16   # noqa: F401  (the file's conventions)
-from test_gpu_bf16_train import _cus, _lib, _nchw, _p, _stream
+from kernel_bounds import BF, C, GUARD, NAN16, SENT, Acc, Ten, _assert_close, _nchw, _ratio, rnd
+from kernel_refs import (DEC_SLOPES, LEVELS, PRELU_SLOPES, _alphas, decoder_inputs, prelu_inputs, ref_alpha_grad, ref_decoder_bwd, ref_decoder_up,
+                         ref_fuse_df, ref_fuse_scatter, ref_fuse_update, ref_median, ref_prelu_bwd, ref_split_planes, ref_stem_dgrad_route,
+                         ref_stem_pre, ref_stem_wgrad, route_inputs, split_inputs)
+from kt import BF16, BF16X3, F32, _cus, _p, _stream, lib as _lib
 
 pytestmark = pytest.mark.gpu
 
-F32, BF16, BF16X3 = 0, 1, 2
 DTS = [pytest.param(F32, id="f32"), pytest.param(BF16, id="bf16"), pytest.param(BF16X3, id="bf16x3")]
 KIND = {F32: "f32", BF16: "bf16", BF16X3: "x3"}
-GUARD = 512                 # sentinel int16 words behind every tensor
-SENT = 0x7F7F               # sentinel bit pattern: bf16 3.4e38, and 0x7F7F7F7F as f32
-NAN16 = 0x7FC0              # NaN as bf16, and 0x7FC07FC0 as f32
-BF = lambda v: float(torch.tensor(v).to(torch.bfloat16))
-
-
-# ----------------------------------------------------------------------------------------------------------- the fp64 references
-def ref_prelu_bwd(dy, src, a, zero_is_positive=False, no_inv=False):
-    """PReLU backward + bias gradient.  dy, src (rows, C) fp64; src = the stored post-activation y when a > 0, else the pre-activation.
-    -> g, dslope, sum |dslope terms|, db, sum |db terms|.  At zero the derivative is the slope's branch (x > 0 ? dy : a dy)."""
-    pos = src >= 0 if zero_is_positive else src > 0
-    g = torch.where(pos, dy, a * dy)
-    x = src / a if (a > 0 and not no_inv) else src
-    t = torch.where(pos, torch.zeros_like(dy), dy * x)
-    return g, t.sum(), t.abs().sum(), g.sum(0), g.abs().sum(0)
-
-
-def _partner_alpha(alphas, half, pair_last, own=False):
-    i = torch.arange(half)
-    return (alphas[:, i] if own else alphas[:, pair_last - i]).double()[:, :, None, None]
-
-
-def ref_fuse_update(stack, f, alphas, pair_last, alpha_residual):
-    """stack (B, n, hw, 64), f (B, half, hw, 64), alphas (B, V) -> the kept views s_i + alpha[partner(i)] f_i (or f), and T"""
-    half = f.shape[1]
-    if not alpha_residual:
-        return f.clone(), f.abs()
-    al = _partner_alpha(alphas, half, pair_last)
-    return stack[:, :half] + al * f, stack[:, :half].abs() + al.abs() * f.abs()
-
-
-def ref_fuse_df(dsn, alphas, pair_last, alpha_residual, own_alpha=False):
-    """dsn (B, half, hw, 64) -> d f = alpha[partner] dsn (or dsn), and T"""
-    if not alpha_residual:
-        return dsn.clone(), dsn.abs()
-    al = _partner_alpha(alphas, dsn.shape[1], pair_last, own_alpha)
-    return al * dsn, al.abs() * dsn.abs()
-
-
-def ref_fuse_scatter(dsn, dz, n, pair_last, alpha_residual, swap_halves=False):
-    """dsn (B, half, hw, 64), dz (B, half, hw, 128) -> d views (B, n, hw, 64): view i < half gets dz[..., :64] (+ dsn with the alpha
-    residual), view pair_last - i gets dz[..., 64:] of image i, the unpaired view of an odd level exact zeros; and T"""
-    B, half, hw, _ = dsn.shape
-    lo, hi = (dz[..., 64:], dz[..., :64]) if swap_halves else (dz[..., :64], dz[..., 64:])
-    ds = torch.zeros((B, n, hw, 64), dtype=torch.float64)
-    T = torch.zeros_like(ds)
-    ds[:, :half], T[:, :half] = lo, lo.abs()
-    if alpha_residual:
-        ds[:, :half] += dsn
-        T[:, :half] += dsn.abs()
-    i = torch.arange(half)
-    ds[:, pair_last - i], T[:, pair_last - i] = hi, hi.abs()
-    return ds, T
-
-
-def ref_alpha_grad(dsn, f):
-    """dsn, f (B, half, hw, 64) -> sum over pixels and channels of dsn f per (b, v) (it belongs to d_alphas[b][pair_last - v]), and T"""
-    p = dsn * f
-    return p.sum((2, 3)), p.abs().sum((2, 3))
-
-
-def _stem_input(x0, x1, rep1, sub, m0, m1):
-    """images m0..m1 of the stem's two-channel input: (view m, frame m // rep1), `sub` [M][2] subtracted inside the image"""
-    a, b = x0[m0:m1], x1[torch.arange(m0, m1) // rep1]
-    if sub is not None:
-        a, b = a - sub[m0:m1, 0, None, None], b - sub[m0:m1, 1, None, None]
-    return torch.stack([a, b], 1)
-
-
-def ref_stem_wgrad(x0, x1, rep1, sub, g, step=256):
-    """x0 (M, H, W), x1 (ceil(M / rep1), H, W), g (M, H, W, 64) fp64 -> dw (64, 2, 3, 3) of conv2d(cat(x0, x1), pad 1), and T; in chunks of images"""
-    M = x0.shape[0]
-    dw = torch.zeros((64, 2, 3, 3), dtype=torch.float64)
-    T = torch.zeros_like(dw)
-    for m0 in range(0, M, step):
-        m1 = min(M, m0 + step)
-        z, gg = _stem_input(x0, x1, rep1, sub, m0, m1), _nchw(g[m0:m1])
-        dw += torch.nn.grad.conv2d_weight(z, (64, 2, 3, 3), gg, padding=1)
-        T += torch.nn.grad.conv2d_weight(z.abs(), (64, 2, 3, 3), gg.abs(), padding=1)
-    return dw, T
-
-
-def ref_stem_pre(x0, x1, rep1, w, b):
-    """the stem's pre-activation (M, 64, H, W) and T"""
-    z = _stem_input(x0, x1, rep1, None, 0, x0.shape[0])
-    return F.conv2d(z, w, b, padding=1), F.conv2d(z.abs(), w.abs(), b.abs(), padding=1)
-
-
-def ref_route_index(lrs, ref, highest=False):
-    """lrs (B, V, H, W), ref (B, H, W) -> the view (B, H, W) that receives the reference frame's gradient: the lowest-indexed of the
-    first min(V, 9) views equal to the median"""
-    n = min(lrs.shape[1], 9)
-    eq = lrs[:, :n] == ref[:, None]
-    idx = torch.arange(n)[None, :, None, None].expand_as(eq)
-    if highest:
-        return torch.where(eq, idx, torch.full_like(idx, -1)).amax(1)
-    return torch.where(eq, idx, torch.full_like(idx, n)).amin(1)
-
-
-def ref_stem_dgrad_route(dA, w, lrs, ref, highest=False):
-    """dA (B V, H, W, 64), w (64, 2, 3, 3) fp64 -> d_lrs (B, V, H, W) = channel 0 of conv_transpose(dA) per view plus, at the routed
-    view, channel 1 summed over the sample's views; and T"""
-    B, V, H, W = lrs.shape
-    d = torch.nn.grad.conv2d_input((B * V, 2, H, W), w, _nchw(dA), padding=1).reshape(B, V, 2, H, W)
-    Ta = torch.nn.grad.conv2d_input((B * V, 2, H, W), w.abs(), _nchw(dA).abs(), padding=1).reshape(B, V, 2, H, W)
-    out, T = d[:, :, 0].clone(), Ta[:, :, 0].clone()
-    sel = ref_route_index(lrs, ref, highest)[:, None]
-    out.scatter_add_(1, sel, d[:, :, 1].sum(1, keepdim=True))
-    T.scatter_add_(1, sel, Ta[:, :, 1].sum(1, keepdim=True))
-    return out, T
-
-
-def ref_decoder_up(fused, wd, bd, S):
-    return F.conv_transpose2d(_nchw(fused), wd, bd, stride=S)
-
-
-def ref_decoder_bwd(fused, d_sr, wd, bd, a, wf, S, transpose_taps=False):
-    """fused (N, H, W, 64), d_sr (N, S H, S W), wd (64 ci, 64 co, S, S), bd (64), a, wf (64), all fp64 -> dict name -> (value, T) of
-    d_fused (N, H, W, 64), dwd, dbd, dad, dwf, dbf of sr = conv1x1(PReLU(conv_transpose(fused)))"""
-    if transpose_taps:
-        wd = wd.transpose(2, 3).contiguous()
-    z = _nchw(fused)
-    up = ref_decoder_up(fused, wd, bd, S)
-    ds = d_sr[:, None]
-    dy = wf.view(1, 64, 1, 1) * ds
-    pos = up > 0
-    dup = torch.where(pos, dy, a * dy)
-    y = torch.where(pos, up, a * up)
-    neg = torch.where(pos, torch.zeros_like(up), dy * up)
-    return {
-        "d_fused": (F.conv2d(dup, wd, stride=S).permute(0, 2, 3, 1), F.conv2d(dup.abs(), wd.abs(), stride=S).permute(0, 2, 3, 1)),
-        "dwd": (torch.nn.grad.conv2d_weight(dup, wd.shape, z, stride=S), torch.nn.grad.conv2d_weight(dup.abs(), wd.shape, z.abs(), stride=S)),
-        "dbd": (dup.sum((0, 2, 3)), dup.abs().sum((0, 2, 3))),
-        "dad": (neg.sum(), neg.abs().sum()),
-        "dwf": ((y * ds).sum((0, 2, 3)), (y * ds).abs().sum((0, 2, 3))),
-        "dbf": (ds.sum(), ds.abs().sum()),
-    }
-
-
-def ref_split_planes(v, truncate_hi=False):
-    """f32 tensor -> (hi, lo) bf16: hi = bf16(v) round to nearest even, lo = bf16(v - hi)"""
-    if truncate_hi:
-        hi = (v.view(torch.int32) & ~0xFFFF).view(torch.float32).to(torch.bfloat16)
-    else:
-        hi = v.to(torch.bfloat16)
-    return hi, (v - hi.float()).to(torch.bfloat16)
-
-
-def ref_median(lrs, upper=False):
-    """lrs (B, V, H, W) -> the lower median of the first min(V, 9) views"""
-    x = lrs[:, :min(lrs.shape[1], 9)]
-    if upper:
-        return x.sort(1).values[:, x.shape[1] // 2]
-    return torch.median(x, 1).values
 
 
 # ----------------------------------------------------------------------------------------------------------- the test inputs
-def q16(v):
-    """fp32 tensor -> at most 16 significant bits: hi + lo of its bf16 split is then exact, in fp32 too"""
-    return (v.contiguous().view(torch.int32) & ~0xFF).view(torch.float32)
-
-
-def rnd(shape, seed, dt, scale=1.0):
-    """random fp32 values representable in storage dt with at most 16 significant bits (bf16: 8)"""
-    v = torch.randn(shape, generator=torch.Generator().manual_seed(seed)) * scale
-    return v.to(torch.bfloat16).float() if dt == BF16 else q16(v)
-
-
 def k16(shape, g):
     """values k / 2^16, 0 <= k < 2^16"""
     return (torch.randint(0, 1 << 16, shape, generator=g).double() / 65536.0).float()
-
-
-def prelu_inputs(rows, Cc, dt, seed):
-    """dy and the PReLU's stored tensor (y or the pre-activation): both signs, exact +0 and -0"""
-    dy, src = rnd((rows, Cc), seed, dt), rnd((rows, Cc), seed + 1, dt)
-    flat = src.view(-1)
-    flat[::7] = 0.0
-    flat[3::11] = -0.0
-    return dy, src
-
-
-def decoder_inputs(N, H, W, S, seed):
-    """fused in k / 16 (|k| <= 32), wd in k / 64 (|k| <= 16), bd in k / 1024 (|k| <= 1024): every product is a multiple of 2^-10 of size <=
-    1/2 and a sum of 64 plus the bias stays below 2^6, so `up` has 16 significant bits at most and is exact in fp32 in any order.
-    Pixel 0 is the unit vector of channel 0 and bd[co] = -wd[0][co][0][0] at the even co: up == 0 exactly there.  d_sr, wf general."""
-    g = torch.Generator().manual_seed(seed)
-    fused = torch.randint(-32, 33, (N, H, W, 64), generator=g).float() / 16
-    wd = torch.randint(-16, 17, (64, 64, S, S), generator=g).float() / 64
-    bd = torch.randint(-1024, 1025, (64,), generator=g).float() / 1024
-    fused[0, 0, 0] = 0
-    fused[0, 0, 0, 0] = 1.0
-    bd[::2] = -wd[0, ::2, 0, 0]
-    d_sr = torch.randn((N, S * H, S * W), generator=g)
-    wf = torch.randn(64, generator=g) * 0.2
-    return fused, d_sr, wd, bd, wf
-
-
-def route_inputs(B, V, H, W, seed):
-    """lrs of small integers 0..3 (0..1 for V <= 3, where four values would rarely tie) and their median: the median is tied between
-    views at more than half of the pixels for V >= 3, at about half of them for V = 2"""
-    lrs = torch.randint(0, 2 if V <= 3 else 4, (B, V, H, W), generator=torch.Generator().manual_seed(seed)).float()
-    return lrs, ref_median(lrs)
-
-
-def split_inputs(n, seed):
-    """fp32 values for f32_to_planes: random, ties of the bf16 rounding (low half 0x8000 under an even and an odd hi), their neighbours,
-    values whose lo part lies in bf16's denormal range, +0 and -0"""
-    g = torch.Generator().manual_seed(seed)
-    v = torch.randn(n, generator=g)
-    bits = v.view(torch.int32)
-    pat = torch.tensor([0x8000, 0x18000, 0x7FFF, 0x8001, 0x17FFF, 0x18001], dtype=torch.int32)
-    k = torch.arange(0, n, 3)
-    bits[k] = (bits[k] & ~0x1FFFF) | pat[(k // 3) % 6]
-    v[1::16] = v[1::16] * 2.0 ** -118          # lo around 2^-127 and below: bf16 denormals
-    v[5::64] = 0.0
-    v[6::64] = -0.0
-    return v
-
-
-class Ten:
-    """a tensor in storage dt inside an int16 device buffer: f32 (two words per element), one bf16 plane, or bf16x3 = the hi plane and the
-    lo plane directly behind it (as every backward kernel derives it from the element count); GUARD sentinels behind.  v: fp32 CPU values
-    (rounded to bf16 for BF16; split into hi + lo for BF16X3), or None: filled with `fill`.  val: the exact fp64 value the kernel reads."""
-
-    def __init__(self, shape, dt, v=None, fill=SENT):
-        self.shape, self.dt = tuple(shape), dt
-        self.n = int(np.prod(shape))
-        self.words = self.n * (1 if dt == BF16 else 2)
-        raw = torch.full((self.words + GUARD,), SENT, dtype=torch.int16)
-        raw[:self.words] = fill
-        self.val = None
-        if v is not None:
-            v = v.contiguous().reshape(-1)
-            assert v.dtype == torch.float32 and v.numel() == self.n
-            if dt == F32:
-                raw[:self.words], self.val = v.view(torch.int16), v.double()
-            else:
-                hi = v.to(torch.bfloat16)
-                raw[:self.n], self.val = hi.view(torch.int16), hi.double()
-                if dt == BF16X3:
-                    lo = (v - hi.float()).to(torch.bfloat16)
-                    raw[self.n:2 * self.n], self.val = lo.view(torch.int16), hi.double() + lo.double()
-            self.val = self.val.reshape(self.shape)
-        self.bits0 = raw
-        self.raw = raw.cuda()
-
-    @property
-    def ptr(self):
-        return _p(self.raw)
-
-    def planes(self):
-        """the payload as CPU tensors: [f32] or [hi] or [hi, lo]"""
-        raw = self.raw[:self.words].cpu()
-        if self.dt == F32:
-            return [raw.view(torch.float32).reshape(self.shape)]
-        return [raw[k * self.n:(k + 1) * self.n].view(torch.bfloat16).reshape(self.shape) for k in range(self.words // self.n)]
-
-    def value(self):
-        return sum(p.double() for p in self.planes())
-
-    def unchanged(self):
-        return torch.equal(self.raw.cpu(), self.bits0)
-
-    def guard_ok(self):
-        return bool((self.raw[self.words:] == SENT).all())
-
-
-class Acc:
-    """an f32 gradient the kernel accumulates into (+=): starts from random values, NaN guard behind; none = True: handed over as NULL"""
-
-    def __init__(self, shape, seed, none=False):
-        self.shape, self.n = tuple(shape), int(np.prod(shape))
-        self.start = torch.randn(self.n, generator=torch.Generator().manual_seed(seed))
-        self.buf = None if none else torch.cat([self.start, torch.full((64,), float("nan"))]).cuda()
-
-    @property
-    def ptr(self):
-        return _p(self.buf)
-
-    def check(self, tag, want, T, c=C, layout="i"):
-        """got against start + want, T = |start| + sum |terms|"""
-        if self.buf is None:
-            return None
-        got = self.buf.double().cpu()
-        assert bool(torch.isnan(got[self.n:]).all()), f"{tag}: a write past the gradient"
-        s0 = self.start.double().reshape(self.shape)
-        return _assert_close(tag, "f32", got[:self.n].reshape(self.shape), s0 + want, (s0.abs() + T) * (c / C), layout=layout)
 
 
 def _scratch(lib):
@@ -349,7 +67,6 @@ def _dev1(a):
 
 
 # ----------------------------------------------------------------------------------------------------------- prelu_bwd_bias, colsum
-PRELU_SLOPES = [0.25, 1.0, 1.5, 2.0 ** -20, 0.0, BF(-0.3)]
 ROWS = ["1", "RP-1", "S-1", "S", "S+1", "2S+1", "4S+3", "5S+RP+1"]
 
 
@@ -420,8 +137,6 @@ def test_colsum(dt, Cc, rows_name):
 
 
 # ----------------------------------------------------------------------------------------------------------- the fusion level helpers
-ALPHA_PATTERN = [0.0, 1.0, 0.75, 0.75, 1.0, 0.0, 0.75]
-LEVELS = [2, 5, 6, 9]
 LEVEL_SIZES = [(1, "1"), (3, "1"), (1, "33x33"), (3, "33x33"), (1, "cap"), (3, "cap")]
 LEVEL_CASES = []
 for _dt in (F32, BF16, BF16X3):
@@ -439,15 +154,6 @@ def _level(n, B, hw_name):
     if hw_name == "cap":
         assert B * half * hw > 32768
     return half, pair_last, n + 2, hw
-
-
-def _alphas(B, V, zero_at=None):
-    """alphas (B, V) mixed 0 / 1 / 0.75 per sample; zero_at: a slot of the last sample set to 0 (the partner of view 0: every case then has
-    an alpha = 0 output)"""
-    al = torch.tensor([[ALPHA_PATTERN[(b + j) % 7] for j in range(V)] for b in range(B)], dtype=torch.float32)
-    if zero_at is not None:
-        al[B - 1, zero_at] = 0.0
-    return al
 
 
 def _fuse_update_case(dt, n, B, hw_name, ar):
@@ -696,7 +402,6 @@ def test_stem_pre(dt, a, shape):
 
 # ----------------------------------------------------------------------------------------------------------- the decoder's backward
 DEC_SHAPES = {"1x1": (1, 1, 1), "2x3": (2, 2, 3), "9x27": (3, 9, 27), "straddle": (5, 7, 33), "2.5cus": None}
-DEC_SLOPES = [0.25, 0.0, BF(-0.3), 1.5, 1.0]
 DEC_GRADS = ["dwd", "dbd", "dad", "dwf", "dbf"]
 
 

@@ -1,6 +1,6 @@
 """GPU (-m gpu): the bf16 and bf16x3 forward kernels, per element, against torch CPU float64.
 
-Each kernel is launched on its own through kernel_test.hip (hrn_kt_conv3x3_epi with the epilogue encoder_impl / fuse_impl set in ConvParams,
+Each kernel is launched on its own through the hooks of kernel_test.h, bound by tests/kt.py (hrn_kt_conv3x3_epi with the epilogue encoder_impl / fuse_impl set in ConvParams,
 hrn_kt_stem, hrn_kt_decoder), with operands chosen so that the kernel's products are exact and only the accumulation order and the
 rounding of the stored output remain:
   bf16     activations, weights, bias, slope and alpha bf16-representable;
@@ -13,7 +13,7 @@ PReLU; with a residual |r| + |alpha| times that; torch_port.ABS_TERMS per elemen
   bf16 storage     |got - want| <= 1/2 ulp_bf16(max(|got|, |want|)) + C T     (half an ulp: truncation and double rounding fail)
   bf16x3 (hi + lo) |got - want| <= 2^-16 |want| + C T
   decoder (fp32)   |got - want| <= C T
-with one C for the whole file.  Every test prints its worst error / bound.
+with one C (kernel_bounds.C) for the whole file and the two that follow it.  Every test prints its worst error / bound.
 
 Template instance -> production call site -> tests
   stem_mfma_kernel<false> / <true>   encoder_impl (api.hip), bf16 / bf16x3          test_stem[bf16-*], test_stem[bf16x3-*]
@@ -30,23 +30,17 @@ Template instance -> production call site -> tests
   decoder_kernel<F32, true, S>       decoder_impl, bf16x3 (the split decoder)        test_decoder[bf16x3-S*]
 Negative controls (test_negative_control) run on the CPU against the same GPU output and assert that the comparison FAILS.
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from test_gpu_bf16_train import _cus, _lib, _nchw, _p, _pair_gather, _stream
+from kernel_bounds import BF, GUARD, SENT, SHAPES, _assert_close, _grid, _nchw, _pair_gather, _ratio, _tiles, _ulp_bf16
+from kt import BF16, BF16X3, _p, _stream, lib as _lib
 
 pytestmark = pytest.mark.gpu
 
-F32, BF16, BF16X3 = 0, 1, 2
-C = 1e-5                    # the one constant of the file (see the module docstring)
-GUARD = 512                 # sentinel elements behind every plane
 PAD = 1024                  # gap in front of a lo plane: its offset is never the plane's size (as fuse_impl's t1 / t2)
-SENT = 0x7F7F               # sentinel bf16 bit pattern (3.4e38)
-BF = lambda v: float(torch.tensor(v).to(torch.bfloat16))
 # slope classes: None (no PReLU), ACT 1 (0 <= a <= 1) and ACT 2 (a < 0 or a > 1) of conv3x3_r64, v6's act_pick for a > 1
 SLOPES = [None, 0.25, 0.0, 1.0, BF(-0.3), 1.5]
 
@@ -101,41 +95,6 @@ class Act:
         return all(bool((p == SENT).all()) for p in pieces)
 
 
-def _ulp_bf16(x):
-    """ulp of bf16 at |x| (fp64 tensor): 2^(e - 7) for |x| in [2^e, 2^(e + 1)), the smallest normal's below it"""
-    _, e = torch.frexp(x.abs().clamp_min(2.0 ** -126))
-    return torch.ldexp(torch.ones_like(x), (e - 8).to(torch.int32))
-
-
-def _rounding(kind, got, want):
-    """the bound's output-rounding term"""
-    if kind == "bf16":
-        return 0.5 * _ulp_bf16(torch.maximum(got.abs(), want.abs()))
-    if kind == "x3":
-        return 2.0 ** -16 * want.abs()
-    return torch.zeros_like(want)
-
-
-def _bound(kind, got, want, T):
-    return _rounding(kind, got, want) + C * T
-
-
-def _ratio(kind, got, want, T):
-    """-> (max error / bound, index of the worst element)"""
-    r = (got - want).abs() / (_bound(kind, got, want, T) + 1e-300)
-    i = int(torch.argmax(r))
-    return float(r.reshape(-1)[i]), np.unravel_index(i, tuple(r.shape))
-
-
-def _assert_close(tag, kind, got, want, T, layout="m c y x"):
-    r, idx = _ratio(kind, got, want, T)
-    c_used = float((((got - want).abs() - _rounding(kind, got, want)).clamp_min(0) / (T + 1e-300)).max())    # the smallest C that passes
-    print(f"{tag}: max error / bound {r:.3e} at ({layout}) = {tuple(int(i) for i in idx)}; C needed {c_used:.2e}")
-    assert r <= 1.0, (f"{tag}: element ({layout}) = {tuple(int(i) for i in idx)}: got {float(got[idx]):.9g}, want {float(want[idx]):.9g}, "
-                      f"bound {float(_bound(kind, got, want, T)[idx]):.3g} (error / bound {r:.3g})")
-    return r
-
-
 def _prelu(x, T, a):
     if a is None:
         return x, T
@@ -171,21 +130,6 @@ INSTANCES = {
     "genpairres": (BF16, 1, 128, 128, 2, False, False),
     "genalpha": (BF16, 1, 128, 64, 3, False, "stack"),
 }
-# (H, W); "multi": many 3 x 33 images, enough that a workgroup walks two tiles at least
-SHAPES = {"1x1": (1, 1), "2x3": (2, 3), "9x27": (9, 27), "15x33": (15, 33), "17x50": (17, 50), "9x63": (9, 63), "16x64": (16, 64),
-          "multi": (3, 33)}
-
-
-def _grid(route, cout, total):
-    """the launcher's persistent grid: r64 / v6 / v6x3 min(CUs, total), the general kernel min((2 / (cout / 64)) CUs, total); & ~7"""
-    g = (2 // (cout // 64)) * _cus() if route == 1 else _cus()
-    g = min(g, total)
-    return g & ~7 if g >= 8 else g
-
-
-def _tiles(dt, route, cin, cout, H, W):
-    th, tw = (8, 32) if route == 1 or (dt == BF16 and cin == 64 and cout == 64) else (16, 32)   # conv3x3.hip / r64: 8 x 32; v6 / v6x3: 16 x 32
-    return -(-H // th) * -(-W // tw)
 
 
 def _conv_case(name, shape, seed, slope=None, alphas="mix", wset="bf16", ctrl=None):

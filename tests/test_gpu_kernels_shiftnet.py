@@ -1,14 +1,14 @@
 """GPU (-m gpu): ShiftNet's own kernels (shiftnet.hip, shiftnet_bwd.hip, the per-plane mean of stem.hip, the f32 convolution's folded
 BatchNorm epilogue) and the fused Adam, per element, against torch CPU float64.
 
-Each launcher is called on its own through kernel_test.hip (hrn_kt_sn_*), exactly as api.hip / shiftnet_bwd.hip call it, on the stored
-tensors it would see in production; Adam through the public hrn_adam_step.  The reference (the ref_* functions below, checked against
+Each launcher is called on its own through the hooks of kernel_test.h (hrn_kt_sn_*, bound by tests/kt.py), exactly as api.hip / shiftnet_bwd.hip call it, on the stored
+tensors it would see in production; Adam through the public hrn_adam_step.  The reference (the ref_* functions of tests/kernel_refs.py, checked against
 torch autograd / torch.optim.Adam by tests/test_kernels_shiftnet_host.py) is the same operation in fp64 on the exact values the kernel
 reads.  A kernel fed its stored tensors has no ReLU / max-pool flip to excuse: where a gate depends on computed values the inputs make
 them exact (quantised x with a power-of-two scale and a coarse shift), and one test holds the forward's and the backward's gate to each
 other with general values.  Operands are chosen so that the products a kernel forms in fp32 are exact (bf16-representable values, or 16
 significant bits against 8): only the accumulation order and one rounding of the stored output remain.
-Bound per element, T = the same expression on absolute values, C = test_gpu_kernels_fwd.C = 1e-5:
+Bound per element, T = the same expression on absolute values, C = kernel_bounds.C = 1e-5:
   bf16 output                          |got - want| <= 1/2 ulp_bf16(max(|got|, |want|)) + c T
   f32 output, every parameter gradient |got - want| <= c T       (accumulated gradients: want = start + sum, T = |start| + sum |terms|)
 c = C, except where an fp32 chain is longer than 128 terms by construction: c = max(C, n_seq 2^-24), n_seq computed from the kernel's
@@ -41,193 +41,23 @@ Template instance -> production call site -> tests
   adam_kernel (adam.hip)                                hrn_adam_step, FusedAdam.step             test_adam[n*-s*]
 Negative controls (test_negative_control) run on the CPU against the GPU output that passed and assert that the comparison FAILS.
 """
-import ctypes
 import functools
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
-from test_gpu_kernels_fwd import C, SHAPES, _assert_close, _grid, _ratio, _tiles
-from test_gpu_kernels_bwd import BF, BF16, F32, NAN16, SENT, Acc, Ten, q16, rnd     # noqa: F401  (the file's conventions)
-from test_gpu_bf16_train import _cus, _lib as _lib_train, _nchw, _p, _stream         # noqa: F401
-from test_gpu_shiftnet_bf16 import _exact_affine, _lib as _lib_sn, _quantised
+from kernel_bounds import NAN16, SENT, SHAPES, Acc, C, Ten, _assert_close, _exact_affine, _grid, _nchw, _quantised, _ratio, _tiles, rnd
+from kernel_refs import (ADAM_EPS, ADAM_SETTINGS, BN_NPIX, D, FC1_NSEQ, FCK, FCX_NSEQ, HIGH, MOM, _adam_p_ratio, _mask, _stem_dgrad_w,
+                         _window_counts, adam_inputs, bn_stats_inputs, ref_adam, ref_bn_act_pool, ref_bn_bwd, ref_bn_fold, ref_bn_stats,
+                         ref_conv_bn_relu, ref_fc1, ref_fc1_bwd_w, ref_fc1_bwd_x, ref_fc2, ref_fc2_bwd, ref_fc_from_ref, ref_fc_to_ref,
+                         ref_stem_dgrad)
+from kt import BF16, F32, _p, _stream, lib as _lib
 
 pytestmark = pytest.mark.gpu
 
 DTS = [pytest.param(F32, id="f32"), pytest.param(BF16, id="bf16")]
 KIND = {F32: "f32", BF16: "bf16"}
-FCK = 32768                                   # fc1's K
-EPS = float(np.float32(1e-5))                 # BatchNorm's eps as the kernels receive it
-MOM = float(np.float32(0.1))                  # and the momentum
-D = torch.float64
-
-
-def _lib():
-    _lib_train()
-    lib = _lib_sn()
-    vp, i, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-    for name, args in (("bn_save_stats", [vp, sz, i, vp, vp, vp]), ("bn_fold", [vp, vp, vp, vp, vp, vp, vp, i, vp]),
-                       ("conv_bn_relu", [i, i, vp, vp, vp, vp, vp, i, i, i, vp]), ("plane_mean", [vp, vp, i, sz, vp]),
-                       ("sub_plane_mean", [vp, vp, vp, i, sz, vp]), ("fc1", [vp, vp, vp, vp, i, vp, vp]), ("fc2", [vp, vp, vp, i, vp]),
-                       ("fc2_bwd", [vp, vp, vp, vp, vp, vp, i, vp]), ("fc1_bwd_w", [vp, vp, vp, i, vp]), ("fc1_bwd_x", [vp, vp, vp, i, vp])):
-        fn = getattr(lib, "hrn_kt_sn_" + name)
-        fn.restype, fn.argtypes = i, args
-    lib.hrn_kt_sn_fc1_partial_bytes.restype = sz
-    lib.hrn_kt_sn_fc1_partial_bytes.argtypes = []
-    return lib
-
-
-# ----------------------------------------------------------------------------------------------------------- the fp64 references
-def ref_bn_stats(x, gamma, beta, rm, rv, unbiased_scale=False, biased_running=False):
-    """BatchNorm2d in train mode over x (npix, C) fp64 -> name -> (value, T): mean, invstd = 1 / sqrt(biased var + eps), scale = gamma
-    invstd, shift = beta - mean scale, and (rm given) the running statistics after one step of momentum MOM (unbiased variance)"""
-    n = x.shape[0]
-    mean, var = x.mean(0), x.var(0, unbiased=False)
-    varu = var * n / (n - 1) if n > 1 else var
-    invstd = 1.0 / torch.sqrt((varu if unbiased_scale else var) + EPS)
-    scale = gamma * invstd
-    out = dict(mean=(mean, mean.abs()), invstd=(invstd, invstd.abs()), scale=(scale, scale.abs()),
-               shift=(beta - mean * scale, beta.abs() + (mean * scale).abs()))
-    if rm is not None:
-        stat = var if biased_running else varu
-        out["running_mean"] = ((1 - MOM) * rm + MOM * mean, ((1 - MOM) * rm).abs() + (MOM * mean).abs())
-        out["running_var"] = ((1 - MOM) * rv + MOM * stat, ((1 - MOM) * rv).abs() + (MOM * stat).abs())
-    return out
-
-
-def ref_bn_fold(gamma, beta, rm, rv, conv_bias):
-    """eval mode: BatchNorm(conv_nobias + conv_bias) = conv_nobias scale + shift -> (scale, T), (shift, T)"""
-    scale = gamma / torch.sqrt(rv + EPS)
-    cb = conv_bias if conv_bias is not None else torch.zeros_like(rm)
-    return (scale, scale.abs()), (beta + (cb - rm) * scale, beta.abs() + (cb.abs() + rm.abs()) * scale.abs())
-
-
-def _windows(t):
-    """(N, H, W, C) -> (N, H / 2, W / 2, C, 4): the 2 x 2 windows, row-major inside"""
-    N, H, W, Cc = t.shape
-    return t.reshape(N, H // 2, 2, W // 2, 2, Cc).permute(0, 1, 3, 5, 2, 4).reshape(N, H // 2, W // 2, Cc, 4)
-
-
-def _unwindows(w):
-    N, Ho, Wo, Cc, _ = w.shape
-    return w.reshape(N, Ho, Wo, Cc, 2, 2).permute(0, 1, 4, 2, 5, 3).reshape(N, 2 * Ho, 2 * Wo, Cc)
-
-
-def ref_bn_act_pool(x, sc, sh, pool):
-    """x (N, H, W, C) fp64 -> [MaxPool2d(2)](ReLU(x sc + sh)) (sc, sh None: of x itself), and T = |x sc| + |sh| (its maximum over the window:
-    the maximum of rounded values is within the largest single error of the maximum)"""
-    v = x if sc is None else x * sc + sh
-    T = x.abs() if sc is None else (x * sc).abs() + sh.abs()
-    v = torch.relu(v)
-    if pool:
-        v, T = _windows(v).amax(-1), _windows(T.expand_as(x)).amax(-1)
-    return v, T.expand_as(v)
-
-
-def ref_bn_dv(x, dy, sc, sh, pool, last_max=False):
-    """d v of v = x sc + sh behind ReLU (+ MaxPool2d(2)): dy where v > 0; pooled: at the FIRST maximum of the window in row-major order (as
-    torch), nothing where the whole window is <= 0"""
-    r = torch.relu(x * sc + sh)
-    if not pool:
-        return torch.where(r > 0, dy, torch.zeros_like(dy))
-    w = _windows(r)
-    arg = 3 - w.flip(-1).argmax(-1) if last_max else w.argmax(-1)
-    sel = F.one_hot(arg, 4).to(D) * (w.amax(-1) > 0).to(D).unsqueeze(-1) * dy.unsqueeze(-1)
-    return _unwindows(sel)
-
-
-def ref_bn_bwd(x, dy, mean, istd, sc, sh, gamma, pool, last_max=False):
-    """the BatchNorm (train) + ReLU (+ pool) backward -> name -> (value, T): dx = gamma istd (dv - s1 / n - xhat s2 / n), dbeta = s1 = sum dv,
-    dgamma = s2 = sum dv xhat, xhat = (x - mean) istd"""
-    dv = ref_bn_dv(x, dy, sc, sh, pool, last_max)
-    n = x.shape[0] * x.shape[1] * x.shape[2]
-    xh = (x - mean) * istd
-    s1, s2 = dv.sum((0, 1, 2)), (dv * xh).sum((0, 1, 2))
-    k = gamma * istd
-    return dict(dx=(k * (dv - s1 / n - xh * s2 / n), k.abs() * (dv.abs() + s1.abs() / n + xh.abs() * s2.abs() / n)),
-                dbeta=(s1, dv.abs().sum((0, 1, 2))), dgamma=(s2, (dv * xh).abs().sum((0, 1, 2))))
-
-
-def ref_conv_bn_relu(x, w, scale, shift):
-    """x (M, H, W, cin), w (cout, cin, 3, 3) fp64 -> ReLU(conv(x) scale + shift) (M, cout, H, W), T = |scale| sum |terms| + |shift|"""
-    z, s, b = _nchw(x), scale.view(1, -1, 1, 1), shift.view(1, -1, 1, 1)
-    return torch.relu(F.conv2d(z, w, None, padding=1) * s + b), F.conv2d(z.abs(), w.abs(), None, padding=1) * s.abs() + b.abs()
-
-
-def ref_stem_dgrad(g, w, step=4096):
-    """g (M, H, W, 64), w (64, 2, 3, 3) fp64 -> d in (M, 2, H, W) of conv2d(in, w, padding=1), and T; in chunks of images"""
-    out, T = [], []
-    for m0 in range(0, g.shape[0], step):
-        z = _nchw(g[m0:m0 + step].to(D))
-        out.append(F.conv_transpose2d(z, w, padding=1))
-        T.append(F.conv_transpose2d(z.abs(), w.abs(), padding=1))
-    return torch.cat(out), torch.cat(T)
-
-
-def ref_fc_to_ref(y, mask, keep=2.0, hwc=False):
-    """y (B, 256, 128) NHWC -> fc1's input (B, 32768) in the reference's (C, H, W) flatten order k = c 256 + hw, times the train-mode dropout
-    `mask` (B, 32768, in that order; None: eval) with the kept activations scaled by 1 / (1 - p) = 2"""
-    xr = y.reshape(y.shape[0], FCK) if hwc else y.permute(0, 2, 1).reshape(y.shape[0], FCK)
-    return xr if mask is None else xr * mask.to(D) * keep
-
-
-def ref_fc_from_ref(dxr, mask):
-    """dxr (B, 32768) -> d y (B, 256, 128)"""
-    g = dxr if mask is None else dxr * mask.to(D) * 2.0
-    return g.reshape(-1, 128, 256).permute(0, 2, 1)
-
-
-def ref_fc1(xr, w, b, block=128, shift_group=False):
-    """xr (B, 32768) fp64, w (1024, 32768) f32 (taken in blocks of rows), b (1024) -> ReLU(b + xr w^T) (B, 1024), and T"""
-    if shift_group:         # the wrong reference: samples 32.. read from the group in front of theirs
-        xr = torch.cat([xr[:32], xr[:xr.shape[0] - 32]])
-    y = torch.empty((xr.shape[0], w.shape[0]), dtype=D)
-    T = torch.empty_like(y)
-    for j0 in range(0, w.shape[0], block):
-        wb = w[j0:j0 + block].to(D)
-        y[:, j0:j0 + block], T[:, j0:j0 + block] = xr @ wb.T, xr.abs() @ wb.abs().T
-    return torch.relu(y + b), T + b.abs()
-
-
-def ref_fc1_bwd_w(dz1, xr, j0, j1):
-    """rows j0..j1 of d fc1.weight = dz1^T xr, and T"""
-    a = dz1[:, j0:j1].T
-    return a @ xr, a.abs() @ xr.abs()
-
-
-def ref_fc1_bwd_x(dz1, w, block=128):
-    """dxr (B, 32768) = dz1 w, w (J, 32768) f32 taken in blocks of rows, and T"""
-    want, T = torch.zeros((dz1.shape[0], w.shape[1]), dtype=D), torch.zeros((dz1.shape[0], w.shape[1]), dtype=D)
-    for j0 in range(0, w.shape[0], block):
-        wb = w[j0:j0 + block].to(D)
-        want += dz1[:, j0:j0 + block] @ wb
-        T += dz1[:, j0:j0 + block].abs() @ wb.abs()
-    return want, T
-
-
-def ref_fc2(y, w2):
-    return y @ w2.T, y.abs() @ w2.abs().T
-
-
-def ref_fc2_bwd(dtheta, y1, w2, gate_ge=False):
-    """theta = ReLU-output y1 (B, 1024) times w2^T (2, 1024) -> name -> (value, T): dz1 = (y1 > 0) dtheta w2, dw2 = dtheta^T y1, db1 = sum_b dz1"""
-    gate = (y1 >= 0 if gate_ge else y1 > 0).to(D)
-    dz, Tz = gate * (dtheta @ w2), gate * (dtheta.abs() @ w2.abs())
-    return dict(dz1=(dz, Tz), dw2=(dtheta.T @ y1, dtheta.abs().T @ y1.abs()), db1=(dz.sum(0), Tz.sum(0)))
-
-
-def ref_adam(p, g, m, v, lr, b1, b2, eps, wd, step, m_new=None, v_new=None, no_bc2=False, eps_inside=False):
-    """torch.optim.Adam's step (no amsgrad) in fp64 -> m', T_m, v', T_v, p', |update|; p' from (m_new, v_new) when given"""
-    gj, ga = g + wd * p, g.abs() + wd * p.abs()
-    m1, Tm = b1 * m + (1 - b1) * gj, b1 * m.abs() + (1 - b1) * ga
-    v1, Tv = b2 * v + (1 - b2) * gj * gj, b2 * v.abs() + (1 - b2) * ga * ga
-    mm, vv = (m1, v1) if m_new is None else (m_new, v_new)
-    bc1, bc2 = 1.0 - b1 ** step, 1.0 if no_bc2 else 1.0 - b2 ** step
-    denom = torch.sqrt(vv / bc2 + eps) if eps_inside else torch.sqrt(vv) / np.sqrt(bc2) + eps
-    upd = (lr / bc1) * mm / denom
-    return m1, Tm, v1, Tv, p - upd, upd.abs()
 
 
 # ----------------------------------------------------------------------------------------------------------- helpers
@@ -291,28 +121,6 @@ def _payload(t):
 
 
 # ----------------------------------------------------------------------------------------------------------- BatchNorm statistics, fold
-BN_NPIX = {"256": 256, "257": 257, "255x256+1": 255 * 256 + 1, "147456": 147456}
-HIGH = {F32: 1e8, BF16: 1e4}         # mean^2 / var of the worst channel (bf16's 8 bits hold no more than 4 x 256^2)
-
-
-def bn_stats_inputs(npix, Cc, dt, seed):
-    """x (npix, C) in dt: ordinary channels; channel 3 (f32: 4 too) a large mean with a small spread, mean^2 / var >= HIGH[dt] (bf16: 100 +-
-    one ulp, which survives the rounding); channels 5, 6, 7 exactly constant (0, 0.37, -3.25).  gamma of both signs."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn((npix, Cc), generator=g) * 0.7 + torch.linspace(-1, 1, Cc)
-    if dt == BF16:
-        x[:, 3] = 100.0 + 0.5 * torch.randint(-1, 2, (npix,), generator=g).float()
-    else:
-        x[:, 3] = 100.0 + 0.008 * torch.randn(npix, generator=g)
-        x[:, 4] = -1000.0 + 0.08 * torch.randn(npix, generator=g)
-    x[:, 5], x[:, 6], x[:, 7] = 0.0, 0.37, -3.25
-    if dt == BF16:
-        x = x.to(torch.bfloat16).float()
-    gamma = torch.rand(Cc, generator=g) + 0.5
-    gamma[1::2] *= -1
-    return x, gamma, torch.randn(Cc, generator=g) * 0.1, torch.randn(Cc, generator=g) * 0.1, torch.rand(Cc, generator=g) + 0.5
-
-
 def _bn_stats_case(dt, Cc, npix, running=True):
     lib = _lib()
     xv, gamma, beta, rm0, rv0 = bn_stats_inputs(npix, Cc, dt, 7 + Cc + npix % 1000)
@@ -404,13 +212,6 @@ def _act_pool_case(dt, pool, N, H, Cc, mode, seed):
     torch.cuda.synchronize()
     assert x.unchanged() and out.guard_ok() and (mode == "null" or (scd.unchanged() and shd.unchanged()))
     return dict(x=x, out=out, sc=None if mode == "null" else sc.double(), sh=None if mode == "null" else sh.double())
-
-
-def _window_counts(v):
-    """(tied windows, windows that are all <= 0) of the pre-pool activation v (N, H, W, C), already through ReLU"""
-    w = _windows(v)
-    top = w.amax(-1, keepdim=True)
-    return int((((w == top).sum(-1) > 1) & (top[..., 0] > 0)).sum()), int((top[..., 0] <= 0).sum())
 
 
 def _act_pool_check(tag, dt, pool, mode, r):
@@ -598,10 +399,6 @@ def test_sub_plane_mean(hw, planes):
 STEM_DGRAD_SHAPES = {"1x1": (3, 1, 1), "2x3": (4, 2, 3), "17x50": (2, 17, 50)}
 
 
-def _stem_dgrad_w(seed):
-    return (torch.randn((64, 2, 3, 3), generator=torch.Generator().manual_seed(seed)) * 0.2).to(torch.bfloat16).float()
-
-
 @pytest.mark.parametrize("shape", list(STEM_DGRAD_SHAPES))
 @pytest.mark.parametrize("dt", DTS)
 def test_stem_dgrad(dt, shape):
@@ -645,10 +442,6 @@ def test_stem_dgrad_grid_cap(dt):
 
 
 # ----------------------------------------------------------------------------------------------------------- fc1's input adapters
-def _mask(B, seed):
-    return (torch.rand((B, FCK), generator=torch.Generator().manual_seed(seed)) >= 0.5).to(torch.uint8)
-
-
 def _fc_to_ref_case(dt, B, masked, seed=60):
     lib = _lib()
     y = Ten((B, 256, 128), dt, rnd((B, 256, 128), seed + B, dt))
@@ -691,8 +484,6 @@ def test_fc_from_ref(dt, B, masked):
 
 # ----------------------------------------------------------------------------------------------------------- the fully connected tail
 FC_B = [1, 2, 31, 32, 33, 64, 65]
-FC1_NSEQ = 16 * 64 + 32 + 1          # per wave 16 stages x 64 k on one accumulator, then 32 slabs and the bias in fc1_finish_kernel
-FCX_NSEQ = 256 + 3                   # per wave 128 steps x 2 j on one accumulator, then the four waves' sums
 
 
 @functools.lru_cache(maxsize=1)
@@ -836,17 +627,6 @@ def test_fc1_bwd_x(B):
 
 # ----------------------------------------------------------------------------------------------------------- fused Adam
 ADAM_N = [1, 3, 4, 5, 1027, 4096 * 256 * 4 + 7]          # the last: above the grid of 4096 x 256 threads x 4 elements, with a scalar tail
-ADAM_SETTINGS = [(1e-3, 0.9, 0.999, 0.0, 1), (3e-3, 0.9, 0.99, 1e-2, 2), (1e-4, 0.9, 0.999, 0.0, 1000)]     # lr, beta1, beta2, wd, step
-ADAM_EPS = 1e-8
-
-
-def adam_inputs(n, seed):
-    """p, g, m, v (>= 0) fp32, with elements of g = 0, v = 0, m = 0 and g = 1e-30 (g^2 underflows)"""
-    gen = torch.Generator().manual_seed(seed)
-    p, g, m = torch.randn(n, generator=gen), torch.randn(n, generator=gen) * 0.1, torch.randn(n, generator=gen) * 0.05
-    v = torch.rand(n, generator=gen) * 0.01
-    g[4::7], v[5::11], m[6::13], g[7::17] = 0.0, 0.0, 0.0, 1e-30
-    return p, g, m, v
 
 
 def _adam_case(n, setting):
@@ -863,12 +643,6 @@ def _adam_case(n, setting):
     assert torch.equal(got[1][:n].view(torch.int32), cpu[1].view(torch.int32)), "the gradient was written"
     hyper = [float(np.float32(h)) for h in (lr, b1, b2, ADAM_EPS, wd)] + [step]          # as the ABI receives them
     return dict(p=got[0][:n].double(), m=got[2][:n].double(), v=got[3][:n].double(), ins=[t.double() for t in cpu], hyper=hyper)
-
-
-def _adam_p_ratio(r, **wrong):
-    """p' against the fp64 formula on the m', v' the kernel stored: 2^-24 max(|got|, |want|) + C |update|"""
-    _, _, _, _, want, upd = ref_adam(*r["ins"], *r["hyper"], m_new=r["m"], v_new=r["v"], **wrong)
-    return (r["p"] - want).abs() / (2.0 ** -24 * torch.maximum(r["p"].abs(), want.abs()) + C * upd + 1e-300)
 
 
 @pytest.mark.parametrize("si", range(len(ADAM_SETTINGS)), ids=lambda v: f"s{v}")

@@ -6,8 +6,6 @@ Kernel-level checks feed bf16 inputs (and scales / shifts chosen so that x * sca
 to one bf16 ulp of an fp64 restatement and an f32 output to 1e-5.  End to end the bf16 path is held to fp64 autograd through
 oracle.torch_port.shiftnet_forward_train with bounds set from measurement (recorded next to each bound).
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -15,53 +13,12 @@ import torch.nn.functional as F
 
 from oracle import synth, torch_port, weights
 import util
+from kernel_bounds import _exact_affine, _quantised, _ulp_ok
+from kt import BF16, _p, _stream, lib as _lib
 
 pytestmark = pytest.mark.gpu
 
-F32, BF16 = 0, 1
 ENV = "HRNET_HIP_SHIFTNET_TRAIN_PRECISION"
-
-
-def _lib():
-    from hrnet_hip import binding
-    lib = binding.load_library()
-    vp, i, sz, fl = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
-    lib.hrn_kt_sn_bn_stats.restype = i
-    lib.hrn_kt_sn_bn_stats.argtypes = [i, vp, sz, i, vp, vp, vp, vp, vp, vp, fl, vp, vp]
-    lib.hrn_kt_sn_bn_act_pool.restype = i
-    lib.hrn_kt_sn_bn_act_pool.argtypes = [i, vp, vp, vp, vp, i, i, i, i, i, vp]
-    lib.hrn_kt_sn_bn_bwd.restype = i
-    lib.hrn_kt_sn_bn_bwd.argtypes = [i, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp]
-    lib.hrn_kt_sn_stem_dgrad.restype = i
-    lib.hrn_kt_sn_stem_dgrad.argtypes = [i, vp, vp, vp, i, i, i, vp]
-    lib.hrn_kt_sn_fc_to_ref.restype = i
-    lib.hrn_kt_sn_fc_to_ref.argtypes = [i, vp, vp, vp, i, vp]
-    lib.hrn_kt_sn_fc_from_ref.restype = i
-    lib.hrn_kt_sn_fc_from_ref.argtypes = [i, vp, vp, vp, i, vp]
-    return lib
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ulp_ok(got, want, n_ulp=1.0, floor=0.0):
-    """|got - want| <= n_ulp bf16 ulps of want (+ floor): got a bf16 tensor, want fp64"""
-    got, want = got.double().cpu(), want.double().cpu()
-    e = torch.floor(torch.log2(want.abs().clamp_min(1e-30)))
-    ulp = torch.pow(2.0, e - 7)
-    bad = (got - want).abs() > n_ulp * ulp + floor
-    return int(bad.sum()), float(((got - want).abs() / ulp).max())
-
-
-def _quantised(shape, seed, levels=16, scale=0.25):
-    """bf16-exact values on a coarse grid (k / 8 * scale, |k| < levels): many ties inside pool windows"""
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randint(-levels, levels, shape, generator=g).double() / 8 * scale)
 
 
 # ----------------------------------------------------------------------------- 1. the new passes, kernel level
@@ -85,14 +42,6 @@ def test_bn_stats_bf16_vs_fp64(C, npix):
     assert util.rel_err(sh.cpu().numpy(), want_sh.numpy()) <= 1e-5
     assert util.rel_err(rm.cpu().numpy(), (0.9 * rm0.double() + 0.1 * mean).numpy()) <= 1e-5
     assert util.rel_err(rv.cpu().numpy(), (0.9 * rv0.double() + 0.1 * xv.var(0, unbiased=True)).numpy()) <= 1e-5
-
-
-def _exact_affine(C, seed):
-    """scale a power of two, shift on a coarse bf16 grid: x * scale + shift is exact in fp32 for the quantised x"""
-    g = torch.Generator().manual_seed(seed)
-    sc = torch.pow(2.0, torch.randint(-1, 2, (C,), generator=g).float())
-    sh = torch.randint(-4, 5, (C,), generator=g).float() / 16
-    return sc, sh
 
 
 @pytest.mark.parametrize("pool", [0, 1])

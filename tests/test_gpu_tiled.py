@@ -13,7 +13,7 @@ import torch
 
 from hrnet_hip import augment, tiling
 from oracle import synth, torch_port, weights
-from test_gpu_parity import _check            # the parity bounds: FP32_GUARD, X3_REL, BF16_REL / BF16_PSNR
+from util import _check                       # the parity bounds: FP32_GUARD, X3_REL, BF16_REL / BF16_PSNR
 import util
 
 pytestmark = pytest.mark.gpu

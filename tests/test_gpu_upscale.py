@@ -1,82 +1,23 @@
 """GPU (-m gpu): HRNet at upscale factors x2 / x4 (decoder.deconv kernel_size == stride == S, src/DeepNetworks/HRNet.py:147-156).
 
-Oracle: `_hrnet_forward_s` below, oracle/torch_port.hrnet_forward restated with the decoder's stride as a parameter (built from
+Oracle: `util._hrnet_forward_s`, oracle/torch_port.hrnet_forward restated with the decoder's stride as a parameter (built from
 the port's own helpers), run in float64 on the CPU.  It is first pinned to torch_port.hrnet_forward at S = 3.  Bounds are those of
 test_gpu_parity.py (forward) and test_gpu_backward.py (gradients, train step).  At S = 3 every scale-taking entry point must give
 the very bits of the entry point it generalises."""
-import copy
 import ctypes
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from oracle import synth, torch_port, weights
 import util
+from util import _decode_s, _hrnet_forward_s, _model, _state
 
 pytestmark = pytest.mark.gpu
 
 FP32_REL, X3_REL, BF16_REL, BF16_PSNR = 2e-5, 1e-4, 2.5e-2, 45.0
 _SLOPE_KEYS = [k for k, shape in weights.HRNET_SHAPES if shape == (1,) and k.endswith(".weight")]
-
-
-def _hrnet_forward_s(lrs, alphas, st, num_layers=2, alpha_residual=True, scale=3):
-    """torch_port.hrnet_forward (HRNet.py:186-211) with ConvTranspose2d(64, 64, scale, stride=scale) in the decoder."""
-    b, v, h, w = lrs.shape
-    ref = torch.median(lrs[:, :9], 1, keepdim=True).values
-    x = torch.stack([lrs, ref.expand(-1, v, -1, -1)], 2).reshape(b * v, 2, h, w)
-    x = torch_port._prelu(F.conv2d(x, st["encode.init_layer.0.weight"], st["encode.init_layer.0.bias"], padding=1), st,
-                          "encode.init_layer.1.weight")
-    for i in range(num_layers):
-        x = torch_port._res_block(x, st, f"encode.res_layers.{i}")
-    x = F.conv2d(x, st["encode.final.0.weight"], st["encode.final.0.bias"], padding=1).reshape(b, v, 64, h, w)
-    n = v
-    while n // 2 > 0:
-        parity, half = n % 2, n // 2
-        alice = x[:, :half]
-        bob = x[:, half:n - parity].flip(1)
-        z = torch_port._res_block(torch.cat([alice, bob], 2).reshape(b * half, 128, h, w), st, "fuse.fuse.0")
-        f = torch_port._prelu(F.conv2d(z, st["fuse.fuse.1.weight"], st["fuse.fuse.1.bias"], padding=1), st, "fuse.fuse.2.weight")
-        f = f.reshape(b, half, 64, h, w)
-        if alpha_residual:
-            f = alice + alphas[:, half:n - parity].flip(1).reshape(b, half, 1, 1, 1) * f
-        x, n = f, half
-    return _decode_s(x.mean(1), st, scale)
-
-
-def _decode_s(x, st, scale):
-    x = torch_port._prelu(F.conv_transpose2d(x, st["decode.deconv.0.weight"], st["decode.deconv.0.bias"], stride=scale), st,
-                          "decode.deconv.1.weight")
-    y = F.conv2d(x, st["decode.final.weight"], st["decode.final.bias"])
-    if torch_port.ABS_TERMS is not None and y.requires_grad:
-        rec = torch_port.ABS_TERMS
-        y.register_hook(lambda g: rec.__setitem__("decode.final.bias", rec.get("decode.final.bias", 0.0) + float(g.abs().sum())))
-    return y
-
-
-def _state(scale, seed=1234, slopes=None):
-    """weights.hrnet_state with a seeded (64, 64, S, S) deconv weight of the same scale as the x3 one."""
-    st = weights.to_torch_state(weights.hrnet_state(seed))
-    if scale != 3:
-        rng = np.random.Generator(np.random.PCG64(seed + 100 * scale))
-        w3 = st["decode.deconv.0.weight"]
-        w = rng.standard_normal((64, 64, scale, scale)) * float(w3.std())
-        st["decode.deconv.0.weight"] = torch.from_numpy(w.astype(np.float32))
-    st.update({k: torch.full_like(st[k], v) for k, v in (slopes or {}).items()})
-    return st
-
-
-def _model(scale, precision="fp32", alpha_residual=True, slopes=None, train=False):
-    from DeepNetworks.HRNet import HRNet
-    cfg = copy.deepcopy(weights.HRNET_CONFIG)
-    cfg["decoder"]["deconv"]["kernel_size"] = cfg["decoder"]["deconv"]["stride"] = scale
-    cfg["recursive"]["alpha_residual"] = alpha_residual
-    m = HRNet(cfg)
-    m.load_state_dict(_state(scale, slopes=slopes))
-    m.precision = precision
-    m = m.cuda()
-    return m.train() if train else m.eval()
 
 
 def _check(got, want, prec):

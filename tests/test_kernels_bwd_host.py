@@ -5,7 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import test_gpu_kernels_bwd as K
+import kernel_refs as K
 
 D = torch.float64
 

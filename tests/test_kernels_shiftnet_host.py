@@ -7,8 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import test_gpu_kernels_shiftnet as K
-from test_gpu_shiftnet_bf16 import _exact_affine, _quantised
+import kernel_refs as K
+from kernel_bounds import _exact_affine, _quantised
 
 D = torch.float64
 
