@@ -137,6 +137,10 @@ SIGNATURES = {
     "hrn_shift_cpsnr_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int]),
     "hrn_shift_cpsnr": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
                                    _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_shift_loss_workspace_bytes": (_c.c_size_t, [_c.c_int] * 4),
+    "hrn_shift_loss_train": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p] + [_c.c_int] * 6 + [_c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                                                                                  _c.c_size_t, _c.c_void_p]),
+    "hrn_shift_loss_backward": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 6 + [_c.c_void_p, _c.c_void_p]),
     "hrn_collate_device": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
                                       _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_collate_device_s": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
@@ -824,6 +828,48 @@ def shift_cpsnr(srs, hrs, hr_maps, border_w=3, clip=True):
     return out
 
 
+def _shift_loss_args(srs, hrs, hr_maps, metric, border_w):
+    if metric not in ("cMSE", "cPSNR"):
+        raise ValueError(f"the searched loss is defined for 'cMSE' and 'cPSNR'; got {metric!r}")
+    srs, hrs, hr_maps = _dev_f32(srs, "srs"), _dev_f32(hrs, "hrs"), _dev_f32(hr_maps, "hr_maps")
+    if srs.dim() != 3 or srs.shape != hrs.shape or srs.shape != hr_maps.shape:
+        raise ValueError(f"srs, hrs, hr_maps must be equal (B,H,W) tensors; got {tuple(srs.shape)}, {tuple(hrs.shape)}, {tuple(hr_maps.shape)}")
+    border_w = int(border_w)
+    if border_w < 0 or min(srs.shape[1:]) <= 2 * border_w:
+        raise ValueError(f"border_w={border_w} needs frames larger than {2 * border_w} pixels each way; got {tuple(srs.shape[1:])}")
+    return srs, hrs, hr_maps, border_w
+
+
+def shift_loss_train(srs, hrs, hr_maps, metric="cPSNR", border_w=3, clip=False):
+    """Forward of the shift-searched loss (Evaluator.py:52-73 over train.py:66-87) on (B,H,W) frames of any aspect ratio: -> (out (B,),
+    stats (B,4) f64 = {n, bias, cMSE, k} of the selected offset k = u (2 border_w + 1) + v)."""
+    lib = load_library()
+    srs, hrs, hr_maps, border_w = _shift_loss_args(srs, hrs, hr_maps, metric, border_w)
+    B, H, W = srs.shape
+    out = torch.empty((B,), dtype=torch.float32, device=srs.device)
+    stats = torch.empty((B, 4), dtype=torch.float64, device=srs.device)
+    with torch.cuda.device(srs.device):
+        ws = _workspace(lib.hrn_shift_loss_workspace_bytes(B, H, W, border_w), srs.device, "shift_loss")
+        _check(lib.hrn_shift_loss_train(_ptr(srs), _ptr(hrs), _ptr(hr_maps), B, H, W, border_w, _METRICS[metric], int(bool(clip)), _ptr(out),
+                                        _ptr(stats), _ptr(ws), ws.numel(), _stream()), "hrn_shift_loss_train")
+    return out, stats
+
+
+def shift_loss_backward(srs, hrs, hr_maps, stats, d_out, metric="cPSNR", border_w=3, clip=False):
+    """d_out (B,) -> d_srs (B,H,W) through the offset `stats` selected; zero on the border frame and where clip clamped."""
+    lib = load_library()
+    srs, hrs, hr_maps, border_w = _shift_loss_args(srs, hrs, hr_maps, metric, border_w)
+    d_out = _dev_f32(d_out, "d_out")
+    B, H, W = srs.shape
+    if tuple(stats.shape) != (B, 4) or stats.dtype != torch.float64 or tuple(d_out.shape) != (B,):
+        raise ValueError(f"stats must be ({B}, 4) float64 and d_out ({B},); got {tuple(stats.shape)} {stats.dtype}, {tuple(d_out.shape)}")
+    d_srs = torch.empty_like(srs)
+    with torch.cuda.device(srs.device):
+        _check(lib.hrn_shift_loss_backward(_ptr(srs), _ptr(hrs), _ptr(hr_maps), _ptr(stats.contiguous()), _ptr(d_out), B, H, W, border_w,
+                                           _METRICS[metric], int(bool(clip)), _ptr(d_srs), _stream()), "hrn_shift_loss_backward")
+    return d_srs
+
+
 # --------------------------------------------------------------------------- PyTorch-ROCm custom ops (north_star: "exposed to Python as
 # PyTorch-ROCm custom ops"): the inference entry points are registered with the dispatcher as torch.ops.hrnet_hip.*, with fake
 # (meta) implementations, so that they are visible to torch.compile / export and to anyone calling through torch.ops.  Each is a
@@ -1211,6 +1257,46 @@ def _loss_backward(ctx, d_out, _d_stats):
 
 
 _op_get_loss_train.register_autograd(_loss_backward, setup_context=_loss_setup)
+
+
+@torch.library.custom_op("hrnet_hip::shift_loss_train", mutates_args=(), device_types="cuda")
+def _op_shift_loss_train(srs: torch.Tensor, hrs: torch.Tensor, hr_maps: torch.Tensor, metric: str, border_w: int,
+                         clip: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The shift-searched loss (Evaluator.py:52-73 over train.py:66-87): (loss per sample (B,), stats (B,4) f64 = {n, bias, cMSE, k})."""
+    return shift_loss_train(srs, hrs, hr_maps, metric, border_w, clip)
+
+
+@_op_shift_loss_train.register_fake
+def _(srs, hrs, hr_maps, metric, border_w, clip):
+    return srs.new_empty((srs.shape[0],), dtype=torch.float32), srs.new_empty((srs.shape[0], 4), dtype=torch.float64)
+
+
+@torch.library.custom_op("hrnet_hip::shift_loss_backward", mutates_args=(), device_types="cuda")
+def _op_shift_loss_backward(srs: torch.Tensor, hrs: torch.Tensor, hr_maps: torch.Tensor, stats: torch.Tensor, d_out: torch.Tensor,
+                            metric: str, border_w: int, clip: bool) -> torch.Tensor:
+    return shift_loss_backward(srs, hrs, hr_maps, stats, d_out.contiguous(), metric, border_w, clip)
+
+
+@_op_shift_loss_backward.register_fake
+def _(srs, hrs, hr_maps, stats, d_out, metric, border_w, clip):
+    return srs.new_empty(srs.shape, dtype=torch.float32)
+
+
+def _shift_loss_setup(ctx, inputs, output):
+    srs, hrs, hr_maps, ctx.metric, ctx.border_w, ctx.clip = inputs
+    ctx.save_for_backward(srs, hrs, hr_maps, output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _shift_loss_backward(ctx, d_out, _d_stats):
+    srs, hrs, hr_maps, stats = ctx.saved_tensors
+    if d_out is None:
+        return None, None, None, None, None, None
+    d_srs = torch.ops.hrnet_hip.shift_loss_backward(srs, hrs, hr_maps, stats, d_out, ctx.metric, ctx.border_w, ctx.clip)
+    return d_srs, None, None, None, None, None          # the targets and their status maps get no gradient
+
+
+_op_shift_loss_train.register_autograd(_shift_loss_backward, setup_context=_shift_loss_setup)
 
 
 @torch.library.custom_op("hrnet_hip::adam_step", mutates_args=("params", "exp_avg", "exp_avg_sq"), device_types="cuda")

@@ -411,4 +411,35 @@ int hrn_shift_cpsnr(const float* srs, const float* hrs, const float* maps, int B
     return hrn_launch_shift_cpsnr(srs, hrs, maps, B, S, border, clip, (double*)ws, out, (hipStream_t)stream);
 }
 
+// shift_cPSNR's offset search (Evaluator.py:52-73) over get_loss's cMSE (train.py:66-87), differentiable, frames of any aspect ratio
+static int shift_loss_check(const char* who, int B, int H, int W, int border, int metric) {
+    HRN_CHECK(border >= 0 && border <= 8, -2, "%s: border %d outside 0..8", who, border);
+    HRN_CHECK(B > 0 && H > 2 * border && W > 2 * border, -2, "%s: bad shape B=%d H=%d W=%d border=%d", who, B, H, W, border);
+    HRN_CHECK(B <= 65535, -2, "%s: batch %d exceeds the grid limit", who, B);
+    HRN_CHECK(metric == 1 || metric == 2, -2, "%s: metric must be 1 (cMSE) or 2 (cPSNR); masked_MSE has no searched form", who);
+    return 0;
+}
+
+size_t hrn_shift_loss_workspace_bytes(int B, int H, int W, int border) {
+    if (B <= 0 || border < 0 || border > 8 || H <= 2 * border || W <= 2 * border) return 0;
+    return hrn_shift_loss_workspace_bytes_impl(B, H, W, border);
+}
+
+// Evaluator.py:52-73 and train.py:66-87: the forward of the searched loss
+int hrn_shift_loss_train(const float* srs, const float* hrs, const float* maps, int B, int H, int W, int border, int metric, int clip,
+                         float* out, double* stats, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = shift_loss_check("hrn_shift_loss_train", B, H, W, border, metric)) return rc;
+    HRN_CHECK(srs && hrs && maps && out && stats && ws, -2, "hrn_shift_loss_train: null argument");
+    HRN_CHECK(ws_bytes >= hrn_shift_loss_workspace_bytes_impl(B, H, W, border), -3, "hrn_shift_loss_train: workspace too small");
+    return hrn_launch_shift_loss_train(srs, hrs, maps, B, H, W, border, metric, clip != 0, out, stats, (double*)ws, (hipStream_t)stream);
+}
+
+// Evaluator.py:52-73 and train.py:66-87: its backward, through the selected offset
+int hrn_shift_loss_backward(const float* srs, const float* hrs, const float* maps, const double* stats, const float* d_out, int B, int H,
+                            int W, int border, int metric, int clip, float* d_srs, void* stream) {
+    if (int rc = shift_loss_check("hrn_shift_loss_backward", B, H, W, border, metric)) return rc;
+    HRN_CHECK(srs && hrs && maps && stats && d_out && d_srs, -2, "hrn_shift_loss_backward: null argument");
+    return hrn_launch_shift_loss_backward(srs, hrs, maps, stats, d_out, B, H, W, border, metric, clip != 0, d_srs, (hipStream_t)stream);
+}
+
 }  // extern "C"

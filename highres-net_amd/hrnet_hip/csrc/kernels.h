@@ -45,6 +45,16 @@ int hrn_launch_loss_backward(const float* srs, const float* hrs, const float* ma
 int hrn_launch_shift_cpsnr(const float* srs, const float* hrs, const float* maps, int B, int S, int border, int clip,
                            double* scores, float* out, hipStream_t stream);
 
+// ---- shift_loss.hip: the shift-searched cMSE / cPSNR as a training tail (Evaluator.py:52-73 over train.py:66-87), rectangular frames,
+// border 0..8.  Forward: per-tile fp64 sums at every offset into `partial`, fixed-order finish -> out [B], stats [B][4] = {n*, bias*,
+// cMSE*, k*} of the selected offset k* = u (2 border + 1) + v (n* = 0, k* = -1, out NaN without a clear pixel).  Backward: d_srs [B][H][W],
+// every element written, through the selected offset only.
+size_t hrn_shift_loss_workspace_bytes_impl(int B, int H, int W, int border);
+int hrn_launch_shift_loss_train(const float* srs, const float* hrs, const float* maps, int B, int H, int W, int border, int metric,
+                                int clip, float* out, double* stats, double* partial, hipStream_t stream);
+int hrn_launch_shift_loss_backward(const float* srs, const float* hrs, const float* maps, const double* stats, const float* d_out, int B,
+                                   int H, int W, int border, int metric, int clip, float* d_srs, hipStream_t stream);
+
 // ---- shiftnet.hip.  dt: storage of the activation tensors x / out / y - HRN_F32 or HRN_BF16, one bf16 plane (ShiftNet's bf16
 // training mode); statistics, scale / shift and fc1's input xr are f32 in both
 int hrn_launch_bn_stats(int dt, const void* x, size_t npix, int C, const float* gamma, const float* beta, float eps,

@@ -5,7 +5,12 @@
 'cPSNR' with a gradient-requiring `srs` it is the dispatcher-registered op `torch.ops.hrnet_hip.get_loss_train` (autograd formula: `get_loss_backward`) over `hrn_get_loss_train` / `hrn_get_loss_backward`:
 ONE forward pass over the Lanczos output producing n, the brightness bias b and cMSE per sample, and ONE backward pass producing
 d(srs) with b held constant - the reference detaches it (train.py:83).  Without gradients (validation) it is the forward-only
-`hrn_get_loss`.  No PyTorch fallback."""
+`hrn_get_loss`.  No PyTorch fallback.
+
+`shift_loss(srs, hrs, hr_maps, metric, border_w, clip)` is the score the project is judged on, as a loss: shift_cPSNR's search over the
+(2 border_w + 1)^2 integer offsets of the target (Evaluator.py:52-73) around the same brightness-corrected cMSE, differentiable through
+the selected offset (`torch.ops.hrnet_hip.shift_loss_train` / `.shift_loss_backward`).  It has no parameters, takes frames of any size
+and aspect ratio, and is bit-reproducible: the training tail that needs no ShiftNet."""
 import torch
 
 from . import binding
@@ -19,3 +24,37 @@ def get_loss(srs, hrs, hr_maps, metric="cMSE", crop=0):
         out, _stats = torch.ops.hrnet_hip.get_loss_train(srs if srs.dtype == torch.float32 else srs.float(), hrs.float(), hr_maps.float(), metric, int(crop))
         return out
     return binding.get_loss(srs, hrs, hr_maps, metric, crop)
+
+
+def shift_loss(srs, hrs, hr_maps, metric="cPSNR", border_w=3, clip=False, return_shift=False):
+    """(B,H,W) x 3 -> (B,): the lowest cMSE over the integer offsets (u - border_w, v - border_w), |.| <= border_w, of `hrs` against the
+    centre crop of `srs`, as 'cMSE' or 'cPSNR' (= -10 log10 cMSE, the reference's sign: negate to minimise).  clip clamps srs to [0, 1]
+    first, as the scorer does.  A (B,1,H,W) `srs` is taken as srs[:, 0].  With grad enabled and a gradient-requiring `srs` the result
+    is differentiable (no gradient to hrs / hr_maps).  return_shift: also the (B,2) int64 offsets (row, column) the loss selected, the
+    registration diagnostic ((-border_w - 1, ...) rows mark a sample without a clear pixel, whose loss is NaN)."""
+    for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name} must be a torch.Tensor; got {type(t).__name__}")
+    if metric not in ("cMSE", "cPSNR"):
+        raise ValueError(f"metric must be 'cMSE' or 'cPSNR'; got {metric!r}")
+    if srs.dim() == 4 and srs.shape[1] == 1:
+        srs = srs[:, 0]
+    if srs.dim() != 3 or srs.shape != hrs.shape or srs.shape != hr_maps.shape:
+        raise ValueError(f"srs, hrs, hr_maps must be equal (B,H,W) tensors; got {tuple(srs.shape)}, {tuple(hrs.shape)}, {tuple(hr_maps.shape)}")
+    border_w = int(border_w)
+    if border_w < 0 or border_w > 8 or min(srs.shape[1:]) <= 2 * border_w:
+        raise ValueError(f"border_w must be 0..8 and smaller than half of each side; got {border_w} for frames {tuple(srs.shape[1:])}")
+    for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
+        if not t.is_cuda:
+            raise TypeError(f"{name} is on '{t.device}': the searched loss runs on a ROCm device only (no CPU fallback)")
+    srs = srs if srs.dtype == torch.float32 else srs.float()
+    if torch.is_grad_enabled() and srs.requires_grad:
+        out, stats = torch.ops.hrnet_hip.shift_loss_train(srs.contiguous(), hrs.float().contiguous(), hr_maps.float().contiguous(), metric,
+                                                          border_w, bool(clip))
+    else:
+        out, stats = binding.shift_loss_train(srs, hrs, hr_maps, metric, border_w, clip)
+    if not return_shift:
+        return out
+    k = stats[:, 3].detach().long()
+    nb = 2 * border_w + 1
+    return out, torch.stack([torch.div(k, nb, rounding_mode="floor") - border_w, k % nb - border_w], 1)

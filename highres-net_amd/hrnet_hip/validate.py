@@ -2,7 +2,8 @@
 
 The reference scores every validation imageset on rank 0: `srs = fusion_model(lrs, alphas)[:, 0]`, then per sample
 `val_score -= shift_cPSNR(np.clip(srs[i], 0, 1), hrs[i], hr_maps[i])` on the host, finally `val_score /= len(dataset)`.  Here every rank
-scores ITS imagesets on the device (`HRNet` in eval mode + `hrn_shift_cpsnr`, 49 shifted cPSNRs per image in one launch) and the two
+scores ITS imagesets on the device (`HRNet` in eval mode + `hrn_shift_cpsnr`, 49 shifted cPSNRs per image in one launch; scenes with
+H != W go through the forward of the searched loss, `hrn_shift_loss_train` with clip, which takes any aspect ratio) and the two
 scalars (sum of scores, number of samples) are all-reduced: one 16-byte collective per validation pass, no image ever leaves its GPU.
 Without a process group the result is the single-process score.
 
@@ -10,7 +11,7 @@ With a baseline table (the `norm.csv` of a PROBA-V directory: imageset name -> E
 `mean(ESA[name] / shift_cPSNR)` (train.py:213-217), the number that drives its best-checkpoint selection; the batches then carry the
 `names` that collateFunction, load_batch, BatchPrefetcher and DeviceImagesetCache.batches produce as their fifth element.  `ensemble`
 ("flip" / "dihedral") scores the self-ensembled prediction (HRNet.forward_ensemble).  `tile` predicts through HRNet.forward_tiled
-(windows of that side; scoring stays square-only, because hrn_shift_cpsnr is).  `evaluate` is the same pass on one rank that also
+(windows of that side; a rectangular scene is scored like a square one).  `evaluate` is the same pass on one rank that also
 returns the per-imageset cPSNRs.
 """
 import collections
@@ -30,12 +31,20 @@ def shard_indices(n_items, rank, world_size):
 Evaluation = collections.namedtuple("Evaluation", "names cpsnr score")
 
 
+def _default_score(srs, hrs, hr_maps, border_w):
+    """shift_cPSNR(np.clip(sr, 0, 1), hr, hr_map, border_w) per sample on the device: square batches through hrn_shift_cpsnr, as ever;
+    batches with H != W through the searched loss's forward, the same definition on frames of any aspect ratio."""
+    if srs.shape[-1] == srs.shape[-2]:
+        return binding.shift_cpsnr(srs, hrs, hr_maps, border_w, True)
+    return binding.shift_loss_train(srs, hrs, hr_maps, "cPSNR", border_w, True)[0]
+
+
 def _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, members_per_pass, keep, tile=None):
     """The validation loop of train.py:196-215 over this rank's batches, (lrs, alphas, hrs, hr_maps) or (..., names): -> (float64
     sum on the device of cPSNR - or of ESA[name] / cPSNR with a baseline table - or None without a batch, the number of samples,
     names, the list of per-batch float64 cPSNR tensors when `keep`).  The model's training flag is restored."""
     from . import augment
-    score_fn = score_fn or (lambda s, h, m: binding.shift_cpsnr(s, h, m, border_w, True))
+    score_fn = score_fn or (lambda s, h, m: _default_score(s, h, m, border_w))
     mode = augment.check_mode(ensemble)
     if mode is not None and not hasattr(fusion_model, "forward_ensemble"):
         raise TypeError(f"ensemble={ensemble!r} needs a model with forward_ensemble (DeepNetworks.HRNet), got {type(fusion_model).__name__}")

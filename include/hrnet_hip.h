@@ -20,6 +20,7 @@
  *   hrn_lanczos_shift_backward  <-  torch autograd through the three symbols above, src/train.py:172-190
  *   hrn_adam_step          <-  optimizer.step() of torch.optim.Adam   src/train.py:191, :252
  *   hrn_get_loss / hrn_shift_cpsnr  <-  get_loss (train.py:66-87) / shift_cPSNR (Evaluator.py:52-73)
+ *   hrn_shift_loss_train / hrn_shift_loss_backward  <-  the two combined as a differentiable loss (the searched score, trainable)
  *   hrn_collate_device     <-  collateFunction(min_L) over ImagesetDataset items (src/utils.py:63-113), gathered from
  *                              imagesets decoded once into HBM (DataLoader.DeviceImagesetCache); hrn_collate_device_s
  *                              is the same for x2 / x3 / x4 targets
@@ -288,6 +289,25 @@ int hrn_get_loss_backward(const float* srs, const float* hrs, const float* hr_ma
 size_t hrn_shift_cpsnr_workspace_bytes(int B, int border);
 int hrn_shift_cpsnr(const float* srs, const float* hrs, const float* hr_maps, int B, int S, int border, int clip, float* out,
                     void* workspace, size_t workspace_bytes, void* stream);
+/* The shift-searched score as a differentiable training loss: shift_cPSNR's search over the (2 border + 1)^2 integer offsets of hr
+ * (src/Evaluator.py:52-73) around get_loss's brightness-corrected cMSE (src/train.py:66-87), on frames of any size and aspect ratio.
+ * srs/hrs/hr_maps (B,H,W) f32, H and W > 2 border, border 0..8; with h = H - 2 border, w = W - 2 border, s = srs[border:border+h,
+ * border:border+w] (clamped to [0,1] when clip != 0) and, for the offset k = u (2 border + 1) + v, g = hrs[u:u+h, v:v+w], m =
+ * hr_maps[u:u+h, v:v+w]:  n_k = sum m, bias_k = sum m (g - s) / n_k, cMSE_k = sum m (s + bias_k - g)^2 / n_k.  k* is the lowest k of
+ * minimal cMSE_k among n_k > 0.  metric: 1 'cMSE' -> out = cMSE_k*, 2 'cPSNR' -> out = -10 log10(cMSE_k*) (the reference's sign).
+ * hrn_shift_loss_train      <-  shift_cPSNR (Evaluator.py:52-73) over get_loss (train.py:66-87): out (B) f32 and stats (B,4) f64 =
+ *                               {n*, bias*, cMSE*, k*}; without a clear pixel at any offset out is NaN and stats {0, 0, NaN, -1}.
+ *                               Fixed-order fp64 sums, no atomics: bit-reproducible.
+ * hrn_shift_loss_backward   <-  autograd through that loss (Evaluator.py:52-73, train.py:66-87; the bias term's own contribution is
+ *                               sum m (s + bias - g) = 0): d_srs (B,H,W), every element written = d_out[b] c m*(s + bias* - g*) at
+ *                               the selected offset, c = 2 / n* (cMSE) or -20 / (ln 10 n* cMSE*) (cPSNR); 0 on the border frame,
+ *                               where clip clamped s, and for a sample without a clear pixel.  No gradient to hrs / hr_maps.
+ * hrn_shift_loss_workspace_bytes: the forward's fp64 partial sums (0 for arguments the entry points refuse). */
+size_t hrn_shift_loss_workspace_bytes(int B, int H, int W, int border);
+int hrn_shift_loss_train(const float* srs, const float* hrs, const float* hr_maps, int B, int H, int W, int border, int metric, int clip,
+                         float* out, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+int hrn_shift_loss_backward(const float* srs, const float* hrs, const float* hr_maps, const double* stats, const float* d_out, int B,
+                            int H, int W, int border, int metric, int clip, float* d_srs, void* stream);
 
 /* ------------------------------------------------------------------ optimiser
  * hrn_adam_step  <-  optimizer.step() of torch.optim.Adam (src/train.py:191, :252), one launch over a flat fp32 buffer

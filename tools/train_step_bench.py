@@ -6,7 +6,7 @@
 
 at the reference's training shape (config/config.json: batch 32, up to 32 views, 64 x 64 patches) with synthetic data.
 usage: python tools/train_step_bench.py [B V S steps] [--torch-adam] [--precision P[,P...]] [--shiftnet-precision P[,P...]] [--repeats R]
-                                        [--freeze F[,F...]] [--scale K]
+                                        [--freeze F[,F...]] [--scale K] [--loss L[,L...]]
 
 --precision sets HRNet.train_precision (fp32, bf16x3 or bf16; default: not set, i.e. the module's default rules), --shiftnet-precision
 ShiftNet.train_precision (fp32 or bf16; default: not set).  With several values, one pair of models per combination is built and their
@@ -15,6 +15,9 @@ timing rounds alternate, R rounds each (--repeats, default 1).  --freeze times t
 encoder and fusion block: only the decoder trains) or shiftnet (a fixed ShiftNet that only passes d x back into HRNet); several values
 alternate in one process like the precisions.  --scale K (2, 3 or 4; default 3) times the x2 / x4 step: a stride-K decoder (freshly
 initialised for K != 3, on the seeded x3 encoder and fusion block) and K S x K S targets; K * S must reach ShiftNet's 128-pixel window.
+--loss picks the tail of the step: shiftnet (default) is the reference's ShiftNet -> Lanczos -> cPSNR above; shift is the searched loss,
+loss = -shift_loss(srs, hrs, hr_maps) (hrnet_hip.losses): no ShiftNet is built, the optimiser holds HRNet's parameters
+only, and the 128-pixel window does not apply.  Several values alternate in one process like the precisions.
 """
 import copy
 import os
@@ -30,6 +33,7 @@ import torch
 from oracle import synth, weights            # seeded weights / synthetic inputs only (no oracle arithmetic on the path)
 from DeepNetworks.HRNet import HRNet
 from DeepNetworks.ShiftNet import ShiftNet
+from hrnet_hip.losses import shift_loss
 from hrnet_hip.optim import FusedAdam
 
 
@@ -51,7 +55,7 @@ def get_loss_cpsnr(srs, hrs, hr_maps):                        # train.py:66-87
 def _options(argv):
     pos, opts, i = [], {}, 0
     while i < len(argv):
-        if argv[i] in ("--precision", "--shiftnet-precision", "--repeats", "--freeze", "--scale"):
+        if argv[i] in ("--precision", "--shiftnet-precision", "--repeats", "--freeze", "--scale", "--loss"):
             opts[argv[i]] = argv[i + 1]
             i += 2
         else:
@@ -66,8 +70,9 @@ FREEZE = {"none": lambda k: False, "encoder": lambda k: k.startswith("fusion.enc
 
 
 def _label(key):
-    p, sp, fr = key
-    return f"train_precision={p}" + (f" shiftnet_train_precision={sp}" if sp is not None else "") + (f" freeze={fr}" if fr != "none" else "")
+    p, sp, fr, ls = key
+    return (f"train_precision={p}" + (f" shiftnet_train_precision={sp}" if sp is not None else "") + (f" freeze={fr}" if fr != "none" else "")
+            + (f" loss={ls}" if ls != "shiftnet" else ""))
 
 
 def main():
@@ -86,9 +91,13 @@ def main():
     for p in sprecs:
         if p not in (None, "fp32", "bf16"):
             raise SystemExit(f"--shiftnet-precision: fp32 or bf16 (got {p!r})")
+    tails = opts.get("--loss", "shiftnet").split(",")
+    for t in tails:
+        if t not in ("shiftnet", "shift"):
+            raise SystemExit(f"--loss: shiftnet or shift (got {t!r})")
     scale = int(opts.get("--scale", 3))                      # upscale factor: decoder stride and HR / LR ratio of the targets
-    if scale not in (2, 3, 4) or scale * S < 128:
-        raise SystemExit(f"--scale: 2, 3 or 4 with scale * S >= 128, ShiftNet's window (got {scale}, S = {S})")
+    if scale not in (2, 3, 4) or ("shiftnet" in tails and scale * S < 128):
+        raise SystemExit(f"--scale: 2, 3 or 4, and with --loss shiftnet scale * S >= 128, ShiftNet's window (got {scale}, S = {S})")
     dev = torch.device("cuda:0")
     lrs, alphas = synth.fast_batch(3, B, V, S)
     rng = np.random.Generator(np.random.PCG64(1))
@@ -98,7 +107,7 @@ def main():
     x, a = torch.from_numpy(lrs).to(dev), torch.from_numpy(alphas).to(dev)
     off = (scale * S - 128) // 2
 
-    def setup(prec, sprec, freeze):
+    def setup(prec, sprec, freeze, tail):
         cfg = copy.deepcopy(weights.HRNET_CONFIG)
         cfg["decoder"]["deconv"]["kernel_size"] = cfg["decoder"]["deconv"]["stride"] = scale
         fusion = HRNet(cfg)
@@ -107,6 +116,12 @@ def main():
             state = {k: v for k, v in state.items() if not k.startswith("decode.")}
         fusion.load_state_dict(state, strict=scale == 3)
         fusion.train_precision = prec
+        if tail == "shift":                                  # the searched loss has no parameters: HRNet alone is built and optimised
+            fusion = fusion.to(dev).train()
+            for k, p in fusion.named_parameters():
+                p.requires_grad_(not FREEZE[freeze]("fusion." + k))
+            params = list(fusion.parameters())
+            return fusion, None, torch.optim.Adam(params, lr=1e-4) if "--torch-adam" in sys.argv else FusedAdam(params, lr=1e-4)
         regis = ShiftNet()
         if sprec is not None:
             regis.train_precision = sprec
@@ -122,6 +137,11 @@ def main():
     def step(fusion, regis, opt):
         opt.zero_grad()
         srs = fusion(x, a)
+        if regis is None:
+            loss = torch.mean(-shift_loss(srs, hrs, maps))
+            loss.backward()
+            opt.step()
+            return loss
         shifts = register_batch(regis, srs[:, :, off:off + 128, off:off + 128], hrs[:, off:off + 128, off:off + 128].reshape(-1, 1, 128, 128))
         shifted = apply_shifts(regis, srs, shifts, dev)[:, 0]
         loss = -get_loss_cpsnr(shifted, hrs, maps)
@@ -130,7 +150,8 @@ def main():
         opt.step()
         return loss
 
-    runs = {(p, sp, f): setup(p, sp, f) for p in precs for sp in sprecs for f in freezes}
+    runs = {(p, sp, f, t): setup(p, sp, f, t) for p in precs for t in tails for sp in (sprecs if t == "shiftnet" else [None]) for f in freezes
+            if not (t == "shift" and f == "shiftnet")}
     for r in runs.values():
         for _ in range(2):
             step(*r)
@@ -138,6 +159,7 @@ def main():
     for _ in range(repeats):
         for p, r in runs.items():
             torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()             # the round's own peak (every run's models and optimiser state stay resident)
             t0 = time.time()
             for _ in range(steps):
                 loss = step(*r)
@@ -146,7 +168,7 @@ def main():
             times[p].append(dt)
             print(f"train step B={B} V={V} S={S}{f' scale={scale}' if scale != 3 else ''} {_label(p)}: {dt * 1e3:.1f} ms/step ({B / dt:.0f} samples/s, {1 / dt:.2f} steps/s), "
                   f"loss {float(loss.detach()):.3f}, peak memory {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB, "
-                  f"optimiser {type(r[2]).__name__}")
+                  f"optimiser {type(r[2]).__name__} over {sum(q.numel() for g in r[2].param_groups for q in g['params']) / 1e6:.2f} M parameters")
     if repeats > 1 or len(runs) > 1:
         for p, t in times.items():
             ms = np.array(t) * 1e3
