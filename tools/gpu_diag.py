@@ -1,21 +1,18 @@
 #!/usr/bin/env python3
 """GPU-box diagnostic: runs every HIP stage against the goldens / oracle and PRINTS the errors (no asserts).
 Usage on the box:  python tools/gpu_diag.py > gpurun_out/diag.log 2>&1"""
-import os
 import sys
 import time
 import traceback
 
+import _common
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "highres-net_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from oracle import hrnet_np as O
+from oracle import synth, weights
 
-from oracle import hrnet_np as O  # noqa: E402
-from oracle import synth, weights  # noqa: E402
+_common.tests_on_path()
 import util  # noqa: E402
 
 
@@ -24,9 +21,11 @@ def section(name):
 
 
 def guarded(fn):
+    """Print and go on past a failed comparison only.  Anything else (HrnetHipError, a RuntimeError from torch after a device fault)
+    ends the run: nothing more is started on a card that has just faulted."""
     try:
         fn()
-    except Exception:
+    except (AssertionError, ValueError):
         traceback.print_exc()
     sys.stdout.flush()
 
@@ -56,20 +55,25 @@ def hrnet_cases():
             print(line, flush=True)
 
 
+def timed_forward(m, inputs, n=3):
+    """(last output, seconds per forward): host clock round n forwards and a synchronise, after one untimed forward."""
+    with torch.no_grad():
+        sr = m(*inputs())
+        torch.cuda.synchronize()
+        t0 = time.time()
+        for _ in range(n):
+            sr = m(*inputs())
+        torch.cuda.synchronize()
+    return sr, (time.time() - t0) / n
+
+
 def c1_case():
     g = util.golden("hrnet_c1_b4_v4_s128")
     b, v, s = (int(x) for x in g["shape"])
     lrs, alphas, _ = synth.make_batch(int(g["seed"]), b, v, s, [int(x) for x in g["n_real"]])
     for prec in ("fp32", "bf16"):
         m = util.hip_hrnet(prec)
-        with torch.no_grad():
-            sr = m(util.dev(lrs), util.dev(alphas))
-            torch.cuda.synchronize()
-            t0 = time.time()
-            for _ in range(3):
-                sr = m(util.dev(lrs), util.dev(alphas))
-            torch.cuda.synchronize()
-            dt = (time.time() - t0) / 3
+        sr, dt = timed_forward(m, lambda: (util.dev(lrs), util.dev(alphas)))
         sr = sr.cpu().numpy()
         print(f"c1 {prec}: sr {util.rel_err(sr, g['sr']):.2e} psnr {util.psnr_db(sr, g['sr']):.1f} dB  {dt * 1e3:.2f} ms/fwd", flush=True)
 
@@ -111,20 +115,16 @@ def timing():
         lrs, alphas = synth.fast_batch(7, b, v, 128)
         m = util.hip_hrnet(prec)
         x, a = util.dev(lrs), util.dev(alphas)
-        with torch.no_grad():
-            m(x, a)
-            torch.cuda.synchronize()
-            t0 = time.time()
-            n = 3
-            for _ in range(n):
-                m(x, a)
-            torch.cuda.synchronize()
-        dt = (time.time() - t0) / n
+        _, dt = timed_forward(m, lambda: (x, a))
         gf = b * (6.078 * v + 12.080 * (v - 1) + 1.227)
         print(f"timing {prec} B={b} V={v}: {dt * 1e3:.2f} ms/fwd  {b / dt:.1f} frames/s  {gf / dt / 1e3:.1f} TFLOP/s", flush=True)
 
 
+PARSER = _common.parser(__doc__)
+
 if __name__ == "__main__":
+    PARSER.parse_args()
+    _common.require_gpu("gpu_diag")
     print(torch.cuda.get_device_name(0), torch.version.hip)
     for name, fn in (("hrnet small", hrnet_cases), ("hrnet c1", c1_case), ("lanczos", lanczos_cases),
                      ("shiftnet", shiftnet_cases), ("timing", timing)):

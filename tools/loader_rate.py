@@ -24,11 +24,10 @@ import sys
 import tempfile
 import time
 
+import _common
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "highres-net_amd"), os.path.join(ROOT, "tests")]
-
+_common.tests_on_path()
 from imageset_png import write_png                 # the stdlib PNG writer the tests use  # noqa: E402
 
 SHAPES = [dict(B=32, top_k=32, min_L=32, patch=64), dict(B=8, top_k=8, min_L=2, patch=64)]      # README step; shipped config.json
@@ -82,9 +81,8 @@ def rate(n, seconds):
 
 def spread(ms):
     """Median, min and max over the timed windows of the ms per batch (and the median as batches/s)."""
-    ms = sorted(float(m) for m in ms)
-    med = float(np.median(ms))
-    return dict(ms_median=round(med, 3), ms_min=round(ms[0], 3), ms_max=round(ms[-1], 3), per_s_median=round(1e3 / med, 1), windows=len(ms))
+    med, lo, hi = _common.spread(ms)
+    return dict(ms_median=round(med, 3), ms_min=round(lo, 3), ms_max=round(hi, 3), per_s_median=round(1e3 / med, 1), windows=len(ms))
 
 
 def window(est_ms):
@@ -222,23 +220,17 @@ def kernel_stats(data_dir, threads, n_batches):
     return res
 
 
+PARSER = _common.parser(__doc__, sets=64, threads=16, json=None, no_prof=False, batches=200, repeats=5)
+PARSER.add_argument("--augment", default=None, choices=["flip", "dihedral"])
+PARSER.add_argument("--child", default=None, help=argparse.SUPPRESS)                   # kernel_stats' child under rocprofv3: the data directory
+PARSER.add_argument("--shape", type=int, default=None, help=argparse.SUPPRESS)         # ... and which of SHAPES it runs
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sets", type=int, default=64)
-    ap.add_argument("--threads", type=int, default=16)
-    ap.add_argument("--json", default=None)
-    ap.add_argument("--no-prof", action="store_true")
-    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--shape", type=int, default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--batches", type=int, default=200)
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows per rate (the spread is reported)")
-    ap.add_argument("--augment", default=None, choices=["flip", "dihedral"], help="measure with this augmentation mode on")
-    a = ap.parse_args()
+    a = PARSER.parse_args()
     global AUGMENT
     AUGMENT = a.augment
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("loader_rate.py measures the device path: it needs a ROCm device")
+    _common.require_gpu("loader_rate")
     if a.child:
         dirs = sorted(glob.glob(os.path.join(a.child, "imgset*")))
         global SHAPES

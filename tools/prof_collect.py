@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""tools/prof_collect.py TAG: turn gpurun_out/final/ (written by tools/prof_all.sh on the GPU box) into the committed evidence
+"""tools/prof_collect.py TAG: turn $HRN_OUT/TAG/ (default scratch/out/TAG/; written by tools/prof_all.sh TAG on the GPU box) into the committed evidence
 profiles/TAG_*: bench lines, the rocprofv3 kernel stats, the HBM traffic summary + profiles/<bench.TRAFFIC_JSON> (bytes per launch
 per kernel family, with a hash of the kernel sources so that bench.py never reports stale numbers), MFMA-busy / clock, stamps."""
-import collections, csv, json, os, re, shutil, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import collections, csv, json, os, re, shutil
+import _common
+ap = _common.parser(__doc__)
+ap.add_argument("tag", nargs="?", default="r03_final")
+tag = ap.parse_args().tag
 import bench
-tag = sys.argv[1] if len(sys.argv) > 1 else "r03_final"
-O, P = os.path.join(ROOT, "gpurun_out", "final"), os.path.join(ROOT, "profiles")
+from pmc_busy_summary import busy
+O, P = os.path.join(os.environ.get("HRN_OUT", os.path.join(_common.ROOT, "scratch", "out")), tag), os.path.join(_common.ROOT, "profiles")
 for src, dst in (("bench_steps20.json", "bench_steps20.json"), ("bench_train.json", "bench_train_steps5.json"), ("bench_steps5_kernel_stats.csv", "bench_steps5_kernel_stats.csv"),
                  ("bench_steps5_under_rocprof.json", "bench_steps5_under_rocprof.json"), ("kbench_c5.txt", "kbench_c5.txt"), ("v6_stamps.txt", "v6_stamps.txt"),
                  ("bench_x3_steps10.json", "bench_bf16x3_steps10.json"), ("bench_train_x3.json", "bench_train_bf16x3_steps5.json"),
@@ -62,25 +64,11 @@ json.dump({"_comment": "HBM bytes per average launch at the bench workload (B=32
            "bytes_per_launch": per_launch}, open(os.path.join(P, bench.TRAFFIC_JSON), "w"), indent=2)
 
 # MFMA busy / clock
-dur = {}
-for r in csv.DictReader(open(os.path.join(O, "pmc_busy_kt.csv"))):
-    dur[r["Dispatch_Id"]] = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
-acc = collections.defaultdict(lambda: collections.defaultdict(float))
-for r in csv.DictReader(open(os.path.join(O, "pmc_busy_cc.csv"))):
-    fam, short = family(r["Kernel_Name"])
-    if not fam:
-        continue
-    acc[short][r["Counter_Name"]] += float(r["Counter_Value"])
-    if r["Counter_Name"] == "GRBM_GUI_ACTIVE":
-        acc[short]["ns"] += dur.get(r["Dispatch_Id"], 0)
-        acc[short]["n"] += 1
 out = ["# rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --kernel-trace -- python3 tools/kbench.py bf16",
        "# clk = GRBM_GUI_ACTIVE / 8 / duration (effective clock); mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs / (duration x clk);",
        "# busy x clk = matrix-pipe cycles delivered per ns per SIMD: what the chip sustains at its power limit on this data"]
-for k, c in sorted(acc.items(), key=lambda kv: -kv[1]["ns"]):
-    clk = c["GRBM_GUI_ACTIVE"] / 8 / max(c["ns"], 1)
-    util = c["SQ_VALU_MFMA_BUSY_CYCLES"] / 1024 / max(c["ns"] * clk, 1)
-    out.append(f"{k:40s} n={int(c['n']):4d} total={c['ns'] / 1e6:8.2f} ms clk={clk:5.2f} GHz  mfma_busy={util:5.2f}  busy x clk={util * clk:5.2f}")
+for k, n, ns, clk, util in busy(os.path.join(O, "pmc_busy_kt.csv"), os.path.join(O, "pmc_busy_cc.csv"), lambda name: family(name)[1]):
+    out.append(f"{k:40s} n={n:4d} total={ns / 1e6:8.2f} ms clk={clk:5.2f} GHz  mfma_busy={util:5.2f}  busy x clk={util * clk:5.2f}")
 open(os.path.join(P, f"{tag}_pmc_mfma_busy_clock.txt"), "w").write("\n".join(out) + "\n")
 print("\n".join(lines[3:]))
 print("\n".join(out[3:]))

@@ -16,32 +16,16 @@ threshold on time.
 
 usage: python tools/shift_loss_bench.py [B] [--sizes S[,S...]] [--border W] [--rounds R] [--reps N]
 """
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "highres-net_amd"))
-import numpy as np
+import _common
 import torch
 
+from _common import HBM_ACHIEVABLE, LLC_BYTES
 from hrnet_hip import binding
 
-HBM_ACHIEVABLE = 6.3e12                      # bytes / s: a float4 copy on the MI355X (79 % of the 8 TB/s peak)
-LLC_BYTES = 256 << 20
 FAMILIES = ("shift_loss_fwd", "shift_loss_bwd", "shift_cpsnr")
 
 
-def _options(argv):
-    pos, opts, i = [], {}, 0
-    while i < len(argv):
-        if argv[i] in ("--sizes", "--border", "--rounds", "--reps"):
-            opts[argv[i]] = argv[i + 1]
-            i += 2
-        else:
-            pos.append(argv[i])
-            i += 1
-    return pos, opts
+PARSER = _common.parser(__doc__, positional=dict(B=32), sizes=[192, 384], border=3, rounds=7, reps=20)
 
 
 def floors_us(B, S):
@@ -89,23 +73,19 @@ def bench(B, S, border, rounds, reps):
     print(f"B={B} {S}x{S} border {border}: median of {rounds} rounds x {reps} calls over {nsets} input sets "
           f"(forward vs hrn_shift_cpsnr: {worst:.1e} relative)")
     for f in FAMILIES:
-        t = np.array(per_round[f])
-        res[f] = {"median_us": float(np.median(t)), "min_us": float(t.min()), "max_us": float(t.max())}
+        med, lo, hi = _common.spread(per_round[f])
+        res[f] = {"median_us": med, "min_us": lo, "max_us": hi}
         floor = bwd_floor if f == "shift_loss_bwd" else fwd_floor
-        print(f"    {f:15s} {np.median(t):9.1f} us   (min {t.min():.1f}, max {t.max():.1f})   byte floor {floor:.1f} us = "
-              f"{100 * floor / np.median(t):.0f} % of it")
+        print(f"    {f:15s} {med:9.1f} us   (min {lo:.1f}, max {hi:.1f})   byte floor {floor:.1f} us = "
+              f"{100 * floor / med:.0f} % of it")
     print(f"    hrn_shift_cpsnr / hrn_shift_loss_train: {res['shift_cpsnr']['median_us'] / res['shift_loss_fwd']['median_us']:.2f} x")
     return res
 
 
 def main():
-    args, opts = _options(sys.argv[1:])
-    B = int(args[0]) if args else 32
-    sizes = [int(s) for s in opts.get("--sizes", "192,384").split(",")]
-    border, rounds, reps = int(opts.get("--border", 3)), int(opts.get("--rounds", 7)), int(opts.get("--reps", 20))
-    if not torch.cuda.is_available():
-        raise SystemExit("shift_loss_bench needs a ROCm device: a time cannot be measured without one")
-    print(json.dumps({"shift_loss_bench": [bench(B, S, border, rounds, reps) for S in sizes]}))
+    o = PARSER.parse_args()
+    _common.require_gpu("shift_loss_bench")
+    _common.emit("shift_loss_bench", [bench(o.B, S, o.border, o.rounds, o.reps) for S in o.sizes])
 
 
 if __name__ == "__main__":

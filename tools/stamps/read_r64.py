@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Read the r64 phase stamps of the diagnostic build (HRNET_HIP_LIB=scratch/x/st/lib.so) after one bf16 forward."""
 import os, sys, ctypes
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "highres-net_amd"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # tools/, where _common lives
+import _common
+_common.parser(__doc__).parse_args()
+_common.require_gpu("read_r64")
 import numpy as np, torch
 import bench
 from hrnet_hip import binding

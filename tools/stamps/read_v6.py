@@ -2,8 +2,10 @@
 """Read the conv3x3_v6 stamps of a diagnostic build (-DV6_STAMP; HRNET_HIP_LIB=scratch/x/v6_stamp/lib.so): tile 1 of the largest
 128 -> 128 + residual launch; per stage of chunk 1: MFMA loop, counted DMA wait, barrier; the tile's last stage and epilogue."""
 import os, sys, ctypes
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "highres-net_amd"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # tools/, where _common lives
+import _common
+_common.parser(__doc__).parse_args()
+_common.require_gpu("read_v6")
 import numpy as np, torch
 import bench
 from hrnet_hip import binding

@@ -16,57 +16,24 @@ There is no pass / fail threshold on time.
 usage: python tools/tiled_bench.py [--only tax,kernels,big] [--precision P[,P...]] [--tiles 128,256] [--scene B,V,H,W] [--big B,V,H,W]
                                    [--big-tile T] [--rounds R] [--reps N]
 """
-import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "highres-net_amd"))
-import numpy as np
+import _common
 import torch
 
+from _common import HBM_ACHIEVABLE
 from oracle import synth, weights            # seeded weights / synthetic inputs only (no oracle arithmetic on the path)
 from DeepNetworks.HRNet import HRNet
 from hrnet_hip import binding, tiling
 
-HBM_ACHIEVABLE = 6.3e12                      # bytes / s: a float4 copy on the MI355X (79 % of the 8 TB/s peak)
-OPTIONS = ("--only", "--precision", "--tiles", "--scene", "--big", "--big-tile", "--rounds", "--reps")
+
+PARSER = _common.parser(__doc__, only=["tax", "kernels", "big"], precision=["bf16", "bf16x3"], tiles=[128, 256], scene=[1, 32, 512, 512],
+                        big=[1, 32, 2048, 1536], big_tile=128, rounds=5, reps=3)
 
 
-def _options(argv):
-    opts, i = {}, 0
-    while i < len(argv):
-        if argv[i] not in OPTIONS or i + 1 >= len(argv):
-            raise SystemExit(__doc__)
-        opts[argv[i]] = argv[i + 1]
-        i += 2
-    return opts
-
-
-def _timed(fn, reps):
-    """Microseconds per call: device events around `reps` calls enqueued back to back."""
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(reps):
-        fn()
-    stop.record()
-    stop.synchronize()
-    return start.elapsed_time(stop) * 1e3 / reps
-
-
-def _alternate(runs, rounds, reps):
-    """{name: fn} -> {name: (median, min, max) microseconds}: a warm-up of every shape, then the candidates round by round."""
-    for fn in runs.values():
-        for _ in range(2):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in runs}
-    for _ in range(rounds):
-        for name, fn in runs.items():
-            times[name].append(_timed(fn, reps))
-    return {k: (float(np.median(v)), float(np.min(v)), float(np.max(v))) for k, v in times.items()}
+def _spreads(runs, rounds, reps):
+    """{name: fn} -> {name: (median, min, max) microseconds} of the candidates alternating round by round after a warm-up."""
+    return {k: _common.spread(v) for k, v in _common.alternate(runs, rounds, reps, warmup=2).items()}
 
 
 def _scene(seed, B, V, H, W, dev):
@@ -95,7 +62,7 @@ def tax(precs, tiles, scene, rounds, reps, dev):
         runs = {"whole": lambda: m(x, a)}
         for t in tiles:
             runs[f"tile {t}"] = lambda t=t: m.forward_tiled(x, a, t)
-        med = _alternate(runs, rounds, reps)
+        med = _spreads(runs, rounds, reps)
         same = {t: bool(torch.equal(m.forward_tiled(x, a, t), m(x, a))) for t in tiles}
         print(f"tax: B={B} V={V} {H}x{W} {prec}, R={R}, median of {rounds} rounds x {reps} calls:")
         print(f"    whole frame   {med['whole'][0] / 1e3:10.2f} ms   (min {med['whole'][1] / 1e3:.2f}, max {med['whole'][2] / 1e3:.2f})")
@@ -131,7 +98,7 @@ def kernels(tiles, scene, scale, rounds, reps, dev):
 
         runs = {"gather": lambda: binding.tile_gather(x, t, R, 0, n), "scatter": lambda: binding.tile_scatter(big, srs, t, R, S, 0, n),
                 "gather by slicing": slice_gather, "scatter by slicing": lambda: tiling.scatter(big, srs, p.windows, t, S)}
-        med = _alternate(runs, rounds, reps)
+        med = _spreads(runs, rounds, reps)
         g_bytes = 2 * n * B * V * t * t * 4
         s_bytes = 2 * B * S * H * S * W * 4
         print(f"kernels: B={B} V={V} {H}x{W} x{S} tile {t}, R={R}, {n} windows, median of {rounds} rounds x {reps} calls:")
@@ -181,25 +148,18 @@ def big(precs, scene, tile, dev):
 
 
 def main():
-    opts = _options(sys.argv[1:])
-    if not torch.cuda.is_available():
-        raise SystemExit("tiled_bench needs a ROCm device: a time cannot be measured without one")
+    o = PARSER.parse_args()
+    _common.require_gpu("tiled_bench")
     dev = torch.device("cuda:0")
-    only = opts.get("--only", "tax,kernels,big").split(",")
-    precs = opts.get("--precision", "bf16,bf16x3").split(",")
-    tiles = [int(t) for t in opts.get("--tiles", "128,256").split(",")]
-    scene = tuple(int(v) for v in opts.get("--scene", "1,32,512,512").split(","))
-    big_scene = tuple(int(v) for v in opts.get("--big", "1,32,2048,1536").split(","))
-    rounds, reps = int(opts.get("--rounds", 5)), int(opts.get("--reps", 3))
     result = {}
     with torch.no_grad():
-        if "tax" in only:
-            result["tax"] = tax(precs, tiles, scene, rounds, reps, dev)
-        if "kernels" in only:
-            result["kernels"] = kernels(tiles, scene, weights.HRNET_CONFIG["decoder"]["deconv"]["stride"], rounds, max(reps, 10), dev)
-        if "big" in only:
-            result["big"] = big(precs, big_scene, int(opts.get("--big-tile", 128)), dev)
-    print(json.dumps({"tiled_bench": result}))
+        if "tax" in o.only:
+            result["tax"] = tax(o.precision, o.tiles, tuple(o.scene), o.rounds, o.reps, dev)
+        if "kernels" in o.only:
+            result["kernels"] = kernels(o.tiles, tuple(o.scene), weights.HRNET_CONFIG["decoder"]["deconv"]["stride"], o.rounds, max(o.reps, 10), dev)
+        if "big" in o.only:
+            result["big"] = big(o.precision, tuple(o.big), o.big_tile, dev)
+    _common.emit("tiled_bench", result)
 
 
 if __name__ == "__main__":

@@ -20,13 +20,9 @@ loss = -shift_loss(srs, hrs, hr_maps) (hrnet_hip.losses): 
 only, and the 128-pixel window does not apply.  Several values alternate in one process like the precisions.
 """
 import copy
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "highres-net_amd"))
+import _common
 import numpy as np
 import torch
 
@@ -52,19 +48,6 @@ def get_loss_cpsnr(srs, hrs, hr_maps):                        # train.py:66-87
     return -10 * torch.log10(torch.sum(hr_maps * (srs + bright.view(-1, 1, 1) - hrs) ** 2, dim=(1, 2)) / nclear)
 
 
-def _options(argv):
-    pos, opts, i = [], {}, 0
-    while i < len(argv):
-        if argv[i] in ("--precision", "--shiftnet-precision", "--repeats", "--freeze", "--scale", "--loss"):
-            opts[argv[i]] = argv[i + 1]
-            i += 2
-        else:
-            if not argv[i].startswith("--"):
-                pos.append(argv[i])
-            i += 1
-    return pos, opts
-
-
 FREEZE = {"none": lambda k: False, "encoder": lambda k: k.startswith("fusion.encode."),
           "encoder+fuse": lambda k: k.startswith(("fusion.encode.", "fusion.fuse.")), "shiftnet": lambda k: k.startswith("regis.")}
 
@@ -75,29 +58,28 @@ def _label(key):
             + (f" loss={ls}" if ls != "shiftnet" else ""))
 
 
+PARSER = _common.parser(__doc__, group=("B V S steps", (32, 32, 64, 5)), torch_adam=False, precision=[None], shiftnet_precision=[None], repeats=1,
+                        freeze=["none"], scale=3, loss=["shiftnet"])      # scale: decoder stride and HR / LR ratio of the targets
+
+
+def options(argv=None):
+    o = PARSER.parse_args(argv)
+    for flag, got, allowed in (("--freeze", o.freeze, tuple(FREEZE)), ("--precision", o.precision, (None, "fp32", "bf16x3", "bf16")),
+                               ("--shiftnet-precision", o.shiftnet_precision, (None, "fp32", "bf16")), ("--loss", o.loss, ("shiftnet", "shift"))):
+        for v in got:
+            if v not in allowed:
+                PARSER.error(f"{flag}: {', '.join(a for a in allowed if a)} (got {v!r})")
+    if o.scale not in (2, 3, 4) or ("shiftnet" in o.loss and o.scale * o.S < 128):
+        PARSER.error(f"--scale: 2, 3 or 4, and with --loss shiftnet scale * S >= 128, ShiftNet's window (got {o.scale}, S = {o.S})")
+    return o
+
+
 def main():
-    args, opts = _options(sys.argv[1:])
-    B, V, S, steps = (int(a) for a in args[:4]) if len(args) >= 4 else (32, 32, 64, 5)
-    precs = opts["--precision"].split(",") if "--precision" in opts else [None]
-    sprecs = opts["--shiftnet-precision"].split(",") if "--shiftnet-precision" in opts else [None]
-    repeats = int(opts.get("--repeats", 1))
-    freezes = opts.get("--freeze", "none").split(",")
-    for f in freezes:
-        if f not in FREEZE:
-            raise SystemExit(f"--freeze: {', '.join(FREEZE)} (got {f!r})")
-    for p in precs:
-        if p not in (None, "fp32", "bf16x3", "bf16"):
-            raise SystemExit(f"--precision: fp32, bf16x3 or bf16 (got {p!r})")
-    for p in sprecs:
-        if p not in (None, "fp32", "bf16"):
-            raise SystemExit(f"--shiftnet-precision: fp32 or bf16 (got {p!r})")
-    tails = opts.get("--loss", "shiftnet").split(",")
-    for t in tails:
-        if t not in ("shiftnet", "shift"):
-            raise SystemExit(f"--loss: shiftnet or shift (got {t!r})")
-    scale = int(opts.get("--scale", 3))                      # upscale factor: decoder stride and HR / LR ratio of the targets
-    if scale not in (2, 3, 4) or ("shiftnet" in tails and scale * S < 128):
-        raise SystemExit(f"--scale: 2, 3 or 4, and with --loss shiftnet scale * S >= 128, ShiftNet's window (got {scale}, S = {S})")
+    o = options()
+    B, V, S, steps, scale, repeats = o.B, o.V, o.S, o.steps, o.scale, o.repeats
+    precs, sprecs, freezes, tails = o.precision, o.shiftnet_precision, o.freeze, o.loss
+    adam = torch.optim.Adam if o.torch_adam else FusedAdam
+    _common.require_gpu("train_step_bench")
     dev = torch.device("cuda:0")
     lrs, alphas = synth.fast_batch(3, B, V, S)
     rng = np.random.Generator(np.random.PCG64(1))
@@ -121,7 +103,7 @@ def main():
             for k, p in fusion.named_parameters():
                 p.requires_grad_(not FREEZE[freeze]("fusion." + k))
             params = list(fusion.parameters())
-            return fusion, None, torch.optim.Adam(params, lr=1e-4) if "--torch-adam" in sys.argv else FusedAdam(params, lr=1e-4)
+            return fusion, None, adam(params, lr=1e-4)
         regis = ShiftNet()
         if sprec is not None:
             regis.train_precision = sprec
@@ -131,8 +113,7 @@ def main():
             for k, p in mod.named_parameters():
                 p.requires_grad_(not FREEZE[freeze](prefix + k))
         params = list(fusion.parameters()) + list(regis.parameters())
-        opt = torch.optim.Adam(params, lr=1e-4) if "--torch-adam" in sys.argv else FusedAdam(params, lr=1e-4)
-        return fusion, regis, opt
+        return fusion, regis, adam(params, lr=1e-4)
 
     def step(fusion, regis, opt):
         opt.zero_grad()
@@ -171,8 +152,8 @@ def main():
                   f"optimiser {type(r[2]).__name__} over {sum(q.numel() for g in r[2].param_groups for q in g['params']) / 1e6:.2f} M parameters")
     if repeats > 1 or len(runs) > 1:
         for p, t in times.items():
-            ms = np.array(t) * 1e3
-            print(f"summary {_label(p)}: median {np.median(ms):.1f} ms/step, min {ms.min():.1f}, max {ms.max():.1f} over {len(ms)} rounds")
+            med, lo, hi = _common.spread(dt * 1e3 for dt in t)
+            print(f"summary {_label(p)}: median {med:.1f} ms/step, min {lo:.1f}, max {hi:.1f} over {len(t)} rounds")
 
 
 if __name__ == "__main__":
