@@ -141,6 +141,9 @@ SIGNATURES = {
     "hrn_shift_loss_train": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p] + [_c.c_int] * 6 + [_c.c_void_p, _c.c_void_p, _c.c_void_p,
                                                                                                   _c.c_size_t, _c.c_void_p]),
     "hrn_shift_loss_backward": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 6 + [_c.c_void_p, _c.c_void_p]),
+    "hrn_mncc_grid": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 5 + [_c.c_float, _c.c_void_p, _c.c_void_p]),
+    "hrn_mncc_search": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hrn_mncc_apply": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 4 + [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_collate_device": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
                                       _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_collate_device_s": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
@@ -870,6 +873,89 @@ def shift_loss_backward(srs, hrs, hr_maps, stats, d_out, metric="cPSNR", border_
     return d_srs
 
 
+# --------------------------------------------------------------------------- sub-pixel registration of LR views (registration.hip)
+MNCC_SIDES, MNCC_POINTS, MNCC_LEVELS, MNCC_MAX_RADIUS = (16, 128), (3, 9), (1, 16), 4.0     # the limits of include/hrnet_hip.h
+
+
+def mncc_int(name, value, limits):
+    value = int(value)
+    if not limits[0] <= value <= limits[1]:
+        raise ValueError(f"{name} must be {limits[0]}..{limits[1]}; got {value}")
+    return value
+
+
+def _mncc_args(ref, ref_mask, views, view_masks):
+    """-> the four tensors as contiguous device f32 (a mask may be None: all ones) after the shape checks."""
+    ref, views = _dev_f32(ref, "ref"), _dev_f32(views, "views")
+    if views.dim() != 4 or ref.dim() != 3 or tuple(ref.shape) != (views.shape[0],) + tuple(views.shape[2:]):
+        raise ValueError(f"ref must be (B,H,W) and views (B,V,H,W); got {tuple(ref.shape)}, {tuple(views.shape)}")
+    if ref_mask is not None:
+        ref_mask = _dev_f32(ref_mask, "ref_mask")
+        if ref_mask.shape != ref.shape:
+            raise ValueError(f"ref_mask must have ref's shape {tuple(ref.shape)}; got {tuple(ref_mask.shape)}")
+    if view_masks is not None:
+        view_masks = _dev_f32(view_masks, "view_masks")
+        if view_masks.shape != views.shape:
+            raise ValueError(f"view_masks must have views' shape {tuple(views.shape)}; got {tuple(view_masks.shape)}")
+    return ref, ref_mask, views, view_masks
+
+
+def _opt_ptr(t):
+    return ctypes.c_void_p(0) if t is None else _ptr(t)
+
+
+def mncc_grid(ref, ref_mask, views, view_masks, centres, points_per_dim, width):
+    """One level of the masked-NCC search (include/hrnet_hip.h): centres (B,V,2) = (cy, cx) -> scores (B,V,P,P) f32 for the grid points
+    (dy_i, dx_j) of `width` around them.  A mask may be None (all ones)."""
+    lib = load_library()
+    ref, ref_mask, views, view_masks = _mncc_args(ref, ref_mask, views, view_masks)
+    B, V, H, W = views.shape
+    centres = _dev_f32(centres, "centres")
+    if tuple(centres.shape) != (B, V, 2):
+        raise ValueError(f"centres must be ({B}, {V}, 2); got {tuple(centres.shape)}")
+    P = mncc_int("points_per_dim", points_per_dim, MNCC_POINTS)
+    scores = torch.empty((B, V, P, P), dtype=torch.float32, device=views.device)
+    with torch.cuda.device(views.device):
+        _check(lib.hrn_mncc_grid(_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks), _ptr(centres), B, V, H, W, P, float(width),
+                                 _ptr(scores), _stream()), "hrn_mncc_grid")
+    return scores
+
+
+def mncc_search(ref, ref_mask, views, view_masks, points_per_dim=7, levels=6, radius=1.0):
+    """The whole search in one launch: -> (shifts (B,V,2) f32 = (dy, dx), trace (B,V,levels,3) f32 = (dy, dx, score) per level)."""
+    lib = load_library()
+    ref, ref_mask, views, view_masks = _mncc_args(ref, ref_mask, views, view_masks)
+    B, V, H, W = views.shape
+    P, levels = mncc_int("points_per_dim", points_per_dim, MNCC_POINTS), mncc_int("levels", levels, MNCC_LEVELS)
+    shifts = torch.empty((B, V, 2), dtype=torch.float32, device=views.device)
+    trace = torch.empty((B, V, levels, 3), dtype=torch.float32, device=views.device)
+    with torch.cuda.device(views.device):
+        _check(lib.hrn_mncc_search(_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks), B, V, H, W, P, levels, float(radius),
+                                   _ptr(shifts), _ptr(trace), _stream()), "hrn_mncc_search")
+    return shifts, trace
+
+
+def mncc_apply(views, view_masks, shifts):
+    """-> (out (B,V,H,W) = S(view, shift), valid (B,V,H,W) f32 0 / 1 = V(mask, shift)); invalid pixels of `out` are 0."""
+    lib = load_library()
+    views = _dev_f32(views, "views")
+    if views.dim() != 4:
+        raise ValueError(f"views must be (B,V,H,W); got {tuple(views.shape)}")
+    B, V, H, W = views.shape
+    if view_masks is not None:
+        view_masks = _dev_f32(view_masks, "view_masks")
+        if view_masks.shape != views.shape:
+            raise ValueError(f"view_masks must have views' shape {tuple(views.shape)}; got {tuple(view_masks.shape)}")
+    shifts = _dev_f32(shifts, "shifts")
+    if tuple(shifts.shape) != (B, V, 2):
+        raise ValueError(f"shifts must be ({B}, {V}, 2); got {tuple(shifts.shape)}")
+    out, valid = torch.empty_like(views), torch.empty_like(views)
+    with torch.cuda.device(views.device):
+        _check(lib.hrn_mncc_apply(_ptr(views), _opt_ptr(view_masks), _ptr(shifts), B, V, H, W, _ptr(out), _ptr(valid), _stream()),
+               "hrn_mncc_apply")
+    return out, valid
+
+
 # --------------------------------------------------------------------------- PyTorch-ROCm custom ops (north_star: "exposed to Python as
 # PyTorch-ROCm custom ops"): the inference entry points are registered with the dispatcher as torch.ops.hrnet_hip.*, with fake
 # (meta) implementations, so that they are visible to torch.compile / export and to anyone calling through torch.ops.  Each is a
@@ -1297,6 +1383,40 @@ def _shift_loss_backward(ctx, d_out, _d_stats):
 
 
 _op_shift_loss_train.register_autograd(_shift_loss_backward, setup_context=_shift_loss_setup)
+
+
+# The registration search has no autograd formula: a shift found by a grid search is piecewise constant in the frames.
+@torch.library.custom_op("hrnet_hip::mncc_grid", mutates_args=(), device_types="cuda")
+def _op_mncc_grid(ref: torch.Tensor, ref_mask: Optional[torch.Tensor], views: torch.Tensor, view_masks: Optional[torch.Tensor],
+                  centres: torch.Tensor, points_per_dim: int, width: float) -> torch.Tensor:
+    return mncc_grid(ref, ref_mask, views, view_masks, centres, points_per_dim, width)
+
+
+@_op_mncc_grid.register_fake
+def _(ref, ref_mask, views, view_masks, centres, points_per_dim, width):
+    return views.new_empty((views.shape[0], views.shape[1], points_per_dim, points_per_dim), dtype=torch.float32)
+
+
+@torch.library.custom_op("hrnet_hip::mncc_search", mutates_args=(), device_types="cuda")
+def _op_mncc_search(ref: torch.Tensor, ref_mask: Optional[torch.Tensor], views: torch.Tensor, view_masks: Optional[torch.Tensor],
+                    points_per_dim: int, levels: int, radius: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    return mncc_search(ref, ref_mask, views, view_masks, points_per_dim, levels, radius)
+
+
+@_op_mncc_search.register_fake
+def _(ref, ref_mask, views, view_masks, points_per_dim, levels, radius):
+    B, V = views.shape[:2]
+    return views.new_empty((B, V, 2), dtype=torch.float32), views.new_empty((B, V, levels, 3), dtype=torch.float32)
+
+
+@torch.library.custom_op("hrnet_hip::shift_views", mutates_args=(), device_types="cuda")
+def _op_shift_views(views: torch.Tensor, view_masks: Optional[torch.Tensor], shifts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return mncc_apply(views, view_masks, shifts)
+
+
+@_op_shift_views.register_fake
+def _(views, view_masks, shifts):
+    return views.new_empty(views.shape, dtype=torch.float32), views.new_empty(views.shape, dtype=torch.float32)
 
 
 @torch.library.custom_op("hrnet_hip::adam_step", mutates_args=("params", "exp_avg", "exp_avg_sq"), device_types="cuda")

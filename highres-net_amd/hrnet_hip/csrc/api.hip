@@ -442,4 +442,44 @@ int hrn_shift_loss_backward(const float* srs, const float* hrs, const float* map
     return hrn_launch_shift_loss_backward(srs, hrs, maps, stats, d_out, B, H, W, border, metric, clip != 0, d_srs, (hipStream_t)stream);
 }
 
+// the masked-NCC registration search (registration.hip): the reference fork's recursive_mncc_search / compute_grid_mncc, restated
+static int mncc_check(const char* who, int B, int V, int H, int W) {
+    HRN_CHECK(B > 0 && V > 0 && (long)B * V <= 0x7fffffffL, -2, "%s: bad batch B=%d V=%d", who, B, V);
+    HRN_CHECK(H >= HRN_MNCC_MIN_SIDE && H <= HRN_MNCC_MAX_SIDE && W >= HRN_MNCC_MIN_SIDE && W <= HRN_MNCC_MAX_SIDE, -2,
+              "%s: bad shape H=%d W=%d: the sides of a frame must be %d..%d", who, H, W, HRN_MNCC_MIN_SIDE, HRN_MNCC_MAX_SIDE);
+    return 0;
+}
+
+static int mncc_check_points(const char* who, int P) {
+    HRN_CHECK(P >= HRN_MNCC_MIN_POINTS && P <= HRN_MNCC_MAX_POINTS, -2, "%s: points per axis P=%d outside %d..%d", who, P, HRN_MNCC_MIN_POINTS,
+              HRN_MNCC_MAX_POINTS);
+    return 0;
+}
+
+int hrn_mncc_grid(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* centres, int B, int V,
+                  int H, int W, int P, float width, float* scores, void* stream) {
+    if (int rc = mncc_check("hrn_mncc_grid", B, V, H, W)) return rc;
+    if (int rc = mncc_check_points("hrn_mncc_grid", P)) return rc;
+    HRN_CHECK(width > 0.f && width <= 8.f, -2, "hrn_mncc_grid: width %g outside (0, 8]", (double)width);
+    HRN_CHECK(ref && views && centres && scores, -2, "hrn_mncc_grid: null argument");
+    return hrn_launch_mncc_grid(ref, ref_mask, views, view_masks, centres, B, V, H, W, P, width, scores, (hipStream_t)stream);
+}
+
+int hrn_mncc_search(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H, int W, int P,
+                    int levels, float radius, float* shifts, float* trace, void* stream) {
+    if (int rc = mncc_check("hrn_mncc_search", B, V, H, W)) return rc;
+    if (int rc = mncc_check_points("hrn_mncc_search", P)) return rc;
+    HRN_CHECK(levels >= 1 && levels <= HRN_MNCC_MAX_LEVELS, -2, "hrn_mncc_search: levels %d outside 1..%d", levels, HRN_MNCC_MAX_LEVELS);
+    HRN_CHECK(radius > 0.f && radius <= 4.f, -2, "hrn_mncc_search: radius %g outside (0, 4]", (double)radius);
+    HRN_CHECK(ref && views && shifts, -2, "hrn_mncc_search: null argument");
+    return hrn_launch_mncc_search(ref, ref_mask, views, view_masks, B, V, H, W, P, levels, radius, shifts, trace, (hipStream_t)stream);
+}
+
+int hrn_mncc_apply(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
+                   float* out_valid, void* stream) {
+    if (int rc = mncc_check("hrn_mncc_apply", B, V, H, W)) return rc;
+    HRN_CHECK(views && shifts && out && out_valid, -2, "hrn_mncc_apply: null argument");
+    return hrn_launch_mncc_apply(views, view_masks, shifts, B, V, H, W, out, out_valid, (hipStream_t)stream);
+}
+
 }  // extern "C"

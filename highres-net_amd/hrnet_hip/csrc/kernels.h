@@ -55,6 +55,17 @@ int hrn_launch_shift_loss_train(const float* srs, const float* hrs, const float*
 int hrn_launch_shift_loss_backward(const float* srs, const float* hrs, const float* maps, const double* stats, const float* d_out, int B,
                                    int H, int W, int border, int metric, int clip, float* d_srs, hipStream_t stream);
 
+// ---- registration.hip: the masked-NCC sub-pixel registration of LR views (the definitions are in
+// include/hrnet_hip.h).  One workgroup per view; a mask pointer may be null (all ones); the callers have checked the limits below.
+constexpr int HRN_MNCC_MIN_SIDE = 16, HRN_MNCC_MAX_SIDE = 128;     // a view, its row-pass buffer and its mask patterns fit one CU's LDS
+constexpr int HRN_MNCC_MIN_POINTS = 3, HRN_MNCC_MAX_POINTS = 9, HRN_MNCC_MAX_LEVELS = 16;
+int hrn_launch_mncc_grid(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* centres, int B,
+                         int V, int H, int W, int P, float width, float* scores, hipStream_t stream);
+int hrn_launch_mncc_search(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H, int W,
+                           int P, int levels, float radius, float* shifts, float* trace, hipStream_t stream);
+int hrn_launch_mncc_apply(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
+                          float* out_valid, hipStream_t stream);
+
 // ---- shiftnet.hip.  dt: storage of the activation tensors x / out / y - HRN_F32 or HRN_BF16, one bf16 plane (ShiftNet's bf16
 // training mode); statistics, scale / shift and fc1's input xr are f32 in both
 int hrn_launch_bn_stats(int dt, const void* x, size_t npix, int C, const float* gamma, const float* beta, float eps,

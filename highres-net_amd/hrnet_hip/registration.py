@@ -1,0 +1,118 @@
+"""Sub-pixel registration of the LR views of an imageset on device: the shift of every view against a reference
+frame by a recursive grid search for the maximal masked normalised cross-correlation, and the views resampled by those shifts.
+
+The method is the reference fork's (registration_search.py: compute_shift_ncc -> recursive_mncc_search -> compute_grid_mncc); the
+definitions are this project's own and are written out in include/hrnet_hip.h: a six-tap windowed-sinc sampler that is continuous in the
+shift and has no padding rule, a bilinear mask sample thresholded at 0.5, and a score standardised on both sides over the common valid
+pixels, so that it stays in [-1, 1].  A shift (dy, dx) means Output(y, x) = Input(y + dy, x + dx): the order and sign of
+`lanczos_shift`'s argument, the negative of the fork's.
+
+`mncc_search` is one launch of `hrn_mncc_search`: a workgroup owns a view, keeps it in LDS and walks every level, argmax included.
+`shift_views` is `hrn_mncc_apply`.  Both are bit-reproducible.  There is no autograd formula - a shift found by a grid search is
+piecewise constant in the frames - and no CPU fallback: tensors must be on a ROCm device.  Frames are 16..128 pixels a side."""
+import torch
+
+from . import binding
+
+
+def _frames(lrs, lr_masks, what="lrs"):
+    if not torch.is_tensor(lrs):
+        raise TypeError(f"{what} must be a torch.Tensor; got {type(lrs).__name__}")
+    if lrs.dim() != 4:
+        raise ValueError(f"{what} must be (B,V,H,W); got {tuple(lrs.shape)}")
+    if lr_masks is not None:
+        if not torch.is_tensor(lr_masks):
+            raise TypeError(f"lr_masks must be a torch.Tensor or None; got {type(lr_masks).__name__}")
+        if lr_masks.shape != lrs.shape:
+            raise ValueError(f"lr_masks must have the shape of {what}, {tuple(lrs.shape)}; got {tuple(lr_masks.shape)}")
+    lo, hi = binding.MNCC_SIDES
+    if not (lo <= lrs.shape[2] <= hi and lo <= lrs.shape[3] <= hi):
+        raise ValueError(f"frames must be {lo}..{hi} pixels a side; got {tuple(lrs.shape[2:])}")
+
+
+def _reference(lrs, lr_masks, ref, ref_mask):
+    """ref=None: the first view and its mask (the loaders order the views from the clearest down)."""
+    if ref is None:
+        if ref_mask is not None:
+            raise ValueError("ref_mask is given without ref: the first view's mask is lr_masks[:, 0]")
+        return lrs[:, 0], None if lr_masks is None else lr_masks[:, 0]
+    if not torch.is_tensor(ref):
+        raise TypeError(f"ref must be a torch.Tensor or None; got {type(ref).__name__}")
+    if tuple(ref.shape) != (lrs.shape[0],) + tuple(lrs.shape[2:]):
+        raise ValueError(f"ref must be (B,H,W) = {(lrs.shape[0],) + tuple(lrs.shape[2:])}; got {tuple(ref.shape)}")
+    if ref_mask is not None:
+        if not torch.is_tensor(ref_mask):
+            raise TypeError(f"ref_mask must be a torch.Tensor or None; got {type(ref_mask).__name__}")
+        if ref_mask.shape != ref.shape:
+            raise ValueError(f"ref_mask must have ref's shape {tuple(ref.shape)}; got {tuple(ref_mask.shape)}")
+    return ref, ref_mask
+
+
+def _on_device(**tensors):
+    for name, t in tensors.items():
+        if t is not None and not t.is_cuda:
+            raise TypeError(f"{name} is on '{t.device}': the registration search runs on a ROCm device only (no CPU fallback)")
+
+
+def _search_args(points_per_dim, levels, radius):
+    P = binding.mncc_int("points_per_dim", points_per_dim, binding.MNCC_POINTS)
+    levels = binding.mncc_int("levels", levels, binding.MNCC_LEVELS)
+    radius = float(radius)
+    if not 0.0 < radius <= binding.MNCC_MAX_RADIUS:
+        raise ValueError(f"radius must be in (0, {binding.MNCC_MAX_RADIUS:g}]; got {radius}")
+    return P, levels, radius
+
+
+def mncc_search(lrs, lr_masks=None, ref=None, ref_mask=None, points_per_dim=7, levels=6, radius=1.0, return_trace=False):
+    """lrs (B,V,H,W), lr_masks (B,V,H,W) 0 / non-zero or None (all clear) -> shifts (B,V,2) f32 = (dy, dx): S(view, shift) lies on the
+    reference frame.  ref (B,H,W) / ref_mask (B,H,W): the frame to register against; None takes lrs[:, 0] and lr_masks[:, 0].  Level k
+    of `levels` searches a points_per_dim^2 grid of width 2 radius s^k around the previous level's best point, s = 1 / (points_per_dim
+    - 2) kept within [0.25, 0.9].  return_trace: also (B,V,levels,3) = (dy, dx, score) of every level's best point.  A view without a
+    valid score (all zeros, or masked out) gets shift (0, 0) and a score of -inf.  Not differentiable."""
+    _frames(lrs, lr_masks)
+    ref, ref_mask = _reference(lrs, lr_masks, ref, ref_mask)
+    P, levels, radius = _search_args(points_per_dim, levels, radius)
+    _on_device(lrs=lrs, lr_masks=lr_masks, ref=ref, ref_mask=ref_mask)
+    shifts, trace = torch.ops.hrnet_hip.mncc_search(ref, ref_mask, lrs, lr_masks, P, levels, radius)
+    return (shifts, trace) if return_trace else shifts
+
+
+def mncc_grid(lrs, lr_masks=None, ref=None, ref_mask=None, centres=None, points_per_dim=7, width=2.0):
+    """One level of the search, the diagnostic: -> scores (B,V,P,P) f32 at the grid points (cy - width / 2 + i width / (P - 1), cx - width
+    / 2 + j width / (P - 1)) around centres (B,V,2) = (cy, cx) (None: zeros); -inf where no pixel is valid or a variance is zero."""
+    _frames(lrs, lr_masks)
+    ref, ref_mask = _reference(lrs, lr_masks, ref, ref_mask)
+    P = binding.mncc_int("points_per_dim", points_per_dim, binding.MNCC_POINTS)
+    width = float(width)
+    if not 0.0 < width <= 2.0 * binding.MNCC_MAX_RADIUS:
+        raise ValueError(f"width must be in (0, {2.0 * binding.MNCC_MAX_RADIUS:g}]; got {width}")
+    if centres is None:
+        centres = torch.zeros(tuple(lrs.shape[:2]) + (2,), dtype=torch.float32, device=lrs.device)
+    elif not torch.is_tensor(centres):
+        raise TypeError(f"centres must be a torch.Tensor or None; got {type(centres).__name__}")
+    elif tuple(centres.shape) != tuple(lrs.shape[:2]) + (2,):
+        raise ValueError(f"centres must be (B,V,2) = {tuple(lrs.shape[:2]) + (2,)}; got {tuple(centres.shape)}")
+    _on_device(lrs=lrs, lr_masks=lr_masks, ref=ref, ref_mask=ref_mask, centres=centres)
+    return torch.ops.hrnet_hip.mncc_grid(ref, ref_mask, lrs, lr_masks, centres, P, width)
+
+
+def shift_views(lrs, lr_masks, shifts):
+    """-> (registered (B,V,H,W) = S(view, shift), valid (B,V,H,W) f32 0 / 1): the views resampled by shifts (B,V,2) and which of their
+    pixels are valid - the six-tap footprint inside the frame and the bilinear sample of the mask above 0.5.  Invalid pixels are 0."""
+    _frames(lrs, lr_masks)
+    if not torch.is_tensor(shifts):
+        raise TypeError(f"shifts must be a torch.Tensor; got {type(shifts).__name__}")
+    if tuple(shifts.shape) != tuple(lrs.shape[:2]) + (2,):
+        raise ValueError(f"shifts must be (B,V,2) = {tuple(lrs.shape[:2]) + (2,)}; got {tuple(shifts.shape)}")
+    _on_device(lrs=lrs, lr_masks=lr_masks, shifts=shifts)
+    return torch.ops.hrnet_hip.shift_views(lrs, lr_masks, shifts)
+
+
+def register_views(lrs, lr_masks=None, **search_kwargs):
+    """mncc_search, then shift_views by what it found: -> (registered, valid, shifts).  search_kwargs: ref, ref_mask, points_per_dim,
+    levels, radius."""
+    if "return_trace" in search_kwargs:
+        raise TypeError("register_views returns no trace: call mncc_search(..., return_trace=True) and shift_views")
+    shifts = mncc_search(lrs, lr_masks, **search_kwargs)
+    registered, valid = shift_views(lrs, lr_masks, shifts)
+    return registered, valid, shifts

@@ -21,6 +21,8 @@
  *   hrn_adam_step          <-  optimizer.step() of torch.optim.Adam   src/train.py:191, :252
  *   hrn_get_loss / hrn_shift_cpsnr  <-  get_loss (train.py:66-87) / shift_cPSNR (Evaluator.py:52-73)
  *   hrn_shift_loss_train / hrn_shift_loss_backward  <-  the two combined as a differentiable loss (the searched score, trainable)
+ *   hrn_mncc_grid / hrn_mncc_search / hrn_mncc_apply  <-  the method of the fork's registration_search.py (recursive_mncc_search over
+ *                              compute_grid_mncc), restated: sub-pixel registration of the LR views against a reference frame
  *   hrn_collate_device     <-  collateFunction(min_L) over ImagesetDataset items (src/utils.py:63-113), gathered from
  *                              imagesets decoded once into HBM (DataLoader.DeviceImagesetCache); hrn_collate_device_s
  *                              is the same for x2 / x3 / x4 targets
@@ -308,6 +310,41 @@ int hrn_shift_loss_train(const float* srs, const float* hrs, const float* hr_map
                          float* out, double* stats, void* workspace, size_t workspace_bytes, void* stream);
 int hrn_shift_loss_backward(const float* srs, const float* hrs, const float* hr_maps, const double* stats, const float* d_out, int B,
                             int H, int W, int border, int metric, int clip, float* d_srs, void* stream);
+
+/* ------------------------------------------------------------------ sub-pixel registration of LR views: a masked-NCC grid search
+ * The method of the reference fork's registration_search.py / registration_metrics.py (compute_shift_ncc -> recursive_mncc_search ->
+ * compute_grid_mncc), on definitions of this project's own; tests/registration_ref.py restates them in fp64 and is what the tests
+ * compare against.  ref / ref_mask (B,H,W), views / view_masks (B,V,H,W), all f32; a mask is 0 / non-zero and a NULL mask pointer
+ * means all ones.  16 <= H, W <= 128.
+ *   shift    s = (dy, dx):  Output(y, x) = Input(y + dy, x + dx) - the order and sign of hrn_lanczos_shift's `shift`, the negative of the
+ *            fork's ndi_shift convention.
+ *   sampler  S(T, s), per axis: n = floor(d), f = d - n on the fp32 value of d; six taps at sample offsets o = -2..3, k_o = sinc(o - f)
+ *            sinc((o - f) / 3), sinc(t) = sin(pi t) / (pi t), k = 0 for |o - f| >= 3, normalised to sum 1; applied along rows, then along
+ *            columns.  The footprint of pixel (y, x) is rows y + n_y - 2 .. y + n_y + 3 and columns x + n_x - 2 .. x + n_x + 3; there is
+ *            no padding rule: a pixel whose footprint leaves the frame is invalid and its value is 0.  Continuous in s.
+ *   mask     V(M, s): the bilinear sample of M at (y + dy, x + dx), zeros outside the frame, (1 - f_y) ((1 - f_x) M00 + f_x M01) + f_y
+ *            ((1 - f_x) M10 + f_x M11); a pixel is valid iff the sample is > 0.5 and its footprint is inside the frame.
+ *   score    c = M_ref V(M_t, s), n = sum c, t = S(T, s), r = R, both standardised over c: score = sum c (r - mu_r)(t - mu_t) / (n sigma_r
+ *            sigma_t), in [-1, 1]; -inf when n = 0 or either variance is <= 0.
+ *   grid     centre (cy, cx), width w, P points per axis: d_i = c - w / 2 + i w / (P - 1) in fp64, rounded to fp32; scores[i][j] belongs
+ *            to (dy_i, dx_j).  The best point is the first maximum in row-major order (strict >); without a finite score the centre stays
+ *            and the level's score is -inf.
+ *   search   level k = 0..levels-1 has width w_0 = 2 radius, w_{k+1} = w_k s (fp64), s = 1 / (P - 2), raised to 0.25 if smaller and set
+ *            to 0.9 if >= 1; the first centre is (0, 0), every later one the previous level's best point.
+ * hrn_mncc_grid    one grid level: centres (B,V,2) f32 = (cy, cx), width in (0, 8] -> scores (B,V,P,P) f32.
+ * hrn_mncc_search  the whole search in ONE launch (a workgroup owns a view and walks every level, argmax included): shifts (B,V,2) f32
+ *                  = the last best point, trace (B,V,levels,3) f32 = (dy, dx, score) per level, or NULL.  P 3..9, levels 1..16, radius in
+ *                  (0, 4].  Its level-k scores are hrn_mncc_grid's, bit for bit.
+ * hrn_mncc_apply   out (B,V,H,W) = S(view, shift), out_valid (B,V,H,W) = 1 where V(mask, shift) holds, else 0; shifts (B,V,2).  Invalid
+ *                  pixels of `out` are 0.
+ * Fixed-order sums, no atomics: bit-reproducible.  -2 before any launch, with hrn_last_error() naming the fault: a null pointer other
+ * than a mask or `trace`, B or V not positive, H or W outside 16..128, P, levels, radius or width out of range. */
+int hrn_mncc_grid(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* centres, int B, int V,
+                  int H, int W, int P, float width, float* scores, void* stream);
+int hrn_mncc_search(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H, int W, int P,
+                    int levels, float radius, float* shifts, float* trace, void* stream);
+int hrn_mncc_apply(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
+                   float* out_valid, void* stream);
 
 /* ------------------------------------------------------------------ optimiser
  * hrn_adam_step  <-  optimizer.step() of torch.optim.Adam (src/train.py:191, :252), one launch over a flat fp32 buffer
