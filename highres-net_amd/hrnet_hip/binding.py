@@ -144,6 +144,11 @@ SIGNATURES = {
     "hrn_mncc_grid": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 5 + [_c.c_float, _c.c_void_p, _c.c_void_p]),
     "hrn_mncc_search": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_mncc_apply": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 4 + [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hrn_mncc_scene_workspace_bytes": (_c.c_size_t, [_c.c_int] * 5),
+    "hrn_mncc_grid_scene": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 5 + [_c.c_float, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_mncc_search_scene": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                                                                             _c.c_void_p]),
+    "hrn_mncc_apply_scene": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 4 + [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_collate_device": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
                                       _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_collate_device_s": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
@@ -873,8 +878,11 @@ def shift_loss_backward(srs, hrs, hr_maps, stats, d_out, metric="cPSNR", border_
     return d_srs
 
 
-# --------------------------------------------------------------------------- sub-pixel registration of LR views (registration.hip)
+# --------------------------------------------------------------------------- sub-pixel registration of LR views (registration.hip,
+# registration_scene.hip).  Every call below has a `scene` form for frames of any size; the two differ in the entry point, in the
+# workspace the scene form allocates, and in the limit on a frame's side, nothing else.
 MNCC_SIDES, MNCC_POINTS, MNCC_LEVELS, MNCC_MAX_RADIUS = (16, 128), (3, 9), (1, 16), 4.0     # the limits of include/hrnet_hip.h
+MNCC_SCENE_SIDES = (16, 16384)
 
 
 def mncc_int(name, value, limits):
@@ -904,9 +912,16 @@ def _opt_ptr(t):
     return ctypes.c_void_p(0) if t is None else _ptr(t)
 
 
-def mncc_grid(ref, ref_mask, views, view_masks, centres, points_per_dim, width):
-    """One level of the masked-NCC search (include/hrnet_hip.h): centres (B,V,2) = (cy, cx) -> scores (B,V,P,P) f32 for the grid points
-    (dy_i, dx_j) of `width` around them.  A mask may be None (all ones)."""
+def _mncc_scene_workspace(lib, B, V, H, W, P, device):
+    """-> the (pointer, bytes) pair of the scene entry points' workspace arguments; the caller is inside torch.cuda.device(device)"""
+    nbytes = lib.hrn_mncc_scene_workspace_bytes(B, V, H, W, P)
+    if nbytes == 0:
+        raise HrnetHipError(f"bad registration problem size B={B} V={V} H={H} W={W} P={P}")
+    ws = _workspace(nbytes, device, "mncc_scene")
+    return _ptr(ws), ws.numel()
+
+
+def _mncc_grid(scene, ref, ref_mask, views, view_masks, centres, points_per_dim, width):
     lib = load_library()
     ref, ref_mask, views, view_masks = _mncc_args(ref, ref_mask, views, view_masks)
     B, V, H, W = views.shape
@@ -915,28 +930,33 @@ def mncc_grid(ref, ref_mask, views, view_masks, centres, points_per_dim, width):
         raise ValueError(f"centres must be ({B}, {V}, 2); got {tuple(centres.shape)}")
     P = mncc_int("points_per_dim", points_per_dim, MNCC_POINTS)
     scores = torch.empty((B, V, P, P), dtype=torch.float32, device=views.device)
+    args = (_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks), _ptr(centres), B, V, H, W, P, float(width), _ptr(scores))
     with torch.cuda.device(views.device):
-        _check(lib.hrn_mncc_grid(_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks), _ptr(centres), B, V, H, W, P, float(width),
-                                 _ptr(scores), _stream()), "hrn_mncc_grid")
+        if scene:
+            _check(lib.hrn_mncc_grid_scene(*args, *_mncc_scene_workspace(lib, B, V, H, W, P, views.device), _stream()), "hrn_mncc_grid_scene")
+        else:
+            _check(lib.hrn_mncc_grid(*args, _stream()), "hrn_mncc_grid")
     return scores
 
 
-def mncc_search(ref, ref_mask, views, view_masks, points_per_dim=7, levels=6, radius=1.0):
-    """The whole search in one launch: -> (shifts (B,V,2) f32 = (dy, dx), trace (B,V,levels,3) f32 = (dy, dx, score) per level)."""
+def _mncc_search(scene, ref, ref_mask, views, view_masks, points_per_dim, levels, radius):
     lib = load_library()
     ref, ref_mask, views, view_masks = _mncc_args(ref, ref_mask, views, view_masks)
     B, V, H, W = views.shape
     P, levels = mncc_int("points_per_dim", points_per_dim, MNCC_POINTS), mncc_int("levels", levels, MNCC_LEVELS)
     shifts = torch.empty((B, V, 2), dtype=torch.float32, device=views.device)
     trace = torch.empty((B, V, levels, 3), dtype=torch.float32, device=views.device)
+    args = (_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks), B, V, H, W, P, levels, float(radius), _ptr(shifts), _ptr(trace))
     with torch.cuda.device(views.device):
-        _check(lib.hrn_mncc_search(_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks), B, V, H, W, P, levels, float(radius),
-                                   _ptr(shifts), _ptr(trace), _stream()), "hrn_mncc_search")
+        if scene:
+            _check(lib.hrn_mncc_search_scene(*args, *_mncc_scene_workspace(lib, B, V, H, W, P, views.device), _stream()),
+                   "hrn_mncc_search_scene")
+        else:
+            _check(lib.hrn_mncc_search(*args, _stream()), "hrn_mncc_search")
     return shifts, trace
 
 
-def mncc_apply(views, view_masks, shifts):
-    """-> (out (B,V,H,W) = S(view, shift), valid (B,V,H,W) f32 0 / 1 = V(mask, shift)); invalid pixels of `out` are 0."""
+def _mncc_apply(scene, views, view_masks, shifts):
     lib = load_library()
     views = _dev_f32(views, "views")
     if views.dim() != 4:
@@ -950,10 +970,41 @@ def mncc_apply(views, view_masks, shifts):
     if tuple(shifts.shape) != (B, V, 2):
         raise ValueError(f"shifts must be ({B}, {V}, 2); got {tuple(shifts.shape)}")
     out, valid = torch.empty_like(views), torch.empty_like(views)
+    name = "hrn_mncc_apply_scene" if scene else "hrn_mncc_apply"
     with torch.cuda.device(views.device):
-        _check(lib.hrn_mncc_apply(_ptr(views), _opt_ptr(view_masks), _ptr(shifts), B, V, H, W, _ptr(out), _ptr(valid), _stream()),
-               "hrn_mncc_apply")
+        _check(getattr(lib, name)(_ptr(views), _opt_ptr(view_masks), _ptr(shifts), B, V, H, W, _ptr(out), _ptr(valid), _stream()), name)
     return out, valid
+
+
+def mncc_grid(ref, ref_mask, views, view_masks, centres, points_per_dim, width):
+    """One level of the masked-NCC search (include/hrnet_hip.h): centres (B,V,2) = (cy, cx) -> scores (B,V,P,P) f32 for the grid points
+    (dy_i, dx_j) of `width` around them.  A mask may be None (all ones)."""
+    return _mncc_grid(False, ref, ref_mask, views, view_masks, centres, points_per_dim, width)
+
+
+def mncc_search(ref, ref_mask, views, view_masks, points_per_dim=7, levels=6, radius=1.0):
+    """The whole search in one launch: -> (shifts (B,V,2) f32 = (dy, dx), trace (B,V,levels,3) f32 = (dy, dx, score) per level)."""
+    return _mncc_search(False, ref, ref_mask, views, view_masks, points_per_dim, levels, radius)
+
+
+def mncc_apply(views, view_masks, shifts):
+    """-> (out (B,V,H,W) = S(view, shift), valid (B,V,H,W) f32 0 / 1 = V(mask, shift)); invalid pixels of `out` are 0."""
+    return _mncc_apply(False, views, view_masks, shifts)
+
+
+def mncc_grid_scene(ref, ref_mask, views, view_masks, centres, points_per_dim, width):
+    """mncc_grid for frames of any size (hrn_mncc_grid_scene): tiles, a workspace from the cache, the same scores."""
+    return _mncc_grid(True, ref, ref_mask, views, view_masks, centres, points_per_dim, width)
+
+
+def mncc_search_scene(ref, ref_mask, views, view_masks, points_per_dim=7, levels=6, radius=1.0):
+    """mncc_search for frames of any size (hrn_mncc_search_scene): 1 + 2 levels launches, nothing returns to the host between them."""
+    return _mncc_search(True, ref, ref_mask, views, view_masks, points_per_dim, levels, radius)
+
+
+def mncc_apply_scene(views, view_masks, shifts):
+    """mncc_apply for frames of any size (hrn_mncc_apply_scene); bit-identical to it where both run."""
+    return _mncc_apply(True, views, view_masks, shifts)
 
 
 # --------------------------------------------------------------------------- PyTorch-ROCm custom ops (north_star: "exposed to Python as
@@ -1393,7 +1444,7 @@ def _op_mncc_grid(ref: torch.Tensor, ref_mask: Optional[torch.Tensor], views: to
 
 
 @_op_mncc_grid.register_fake
-def _(ref, ref_mask, views, view_masks, centres, points_per_dim, width):
+def _fake_mncc_grid(ref, ref_mask, views, view_masks, centres, points_per_dim, width):
     return views.new_empty((views.shape[0], views.shape[1], points_per_dim, points_per_dim), dtype=torch.float32)
 
 
@@ -1404,7 +1455,7 @@ def _op_mncc_search(ref: torch.Tensor, ref_mask: Optional[torch.Tensor], views: 
 
 
 @_op_mncc_search.register_fake
-def _(ref, ref_mask, views, view_masks, points_per_dim, levels, radius):
+def _fake_mncc_search(ref, ref_mask, views, view_masks, points_per_dim, levels, radius):
     B, V = views.shape[:2]
     return views.new_empty((B, V, 2), dtype=torch.float32), views.new_empty((B, V, levels, 3), dtype=torch.float32)
 
@@ -1415,8 +1466,31 @@ def _op_shift_views(views: torch.Tensor, view_masks: Optional[torch.Tensor], shi
 
 
 @_op_shift_views.register_fake
-def _(views, view_masks, shifts):
+def _fake_shift_views(views, view_masks, shifts):
     return views.new_empty(views.shape, dtype=torch.float32), views.new_empty(views.shape, dtype=torch.float32)
+
+
+# the same three for frames of any size (registration_scene.hip)
+@torch.library.custom_op("hrnet_hip::mncc_grid_scene", mutates_args=(), device_types="cuda")
+def _op_mncc_grid_scene(ref: torch.Tensor, ref_mask: Optional[torch.Tensor], views: torch.Tensor, view_masks: Optional[torch.Tensor],
+                        centres: torch.Tensor, points_per_dim: int, width: float) -> torch.Tensor:
+    return mncc_grid_scene(ref, ref_mask, views, view_masks, centres, points_per_dim, width)
+
+
+@torch.library.custom_op("hrnet_hip::mncc_search_scene", mutates_args=(), device_types="cuda")
+def _op_mncc_search_scene(ref: torch.Tensor, ref_mask: Optional[torch.Tensor], views: torch.Tensor, view_masks: Optional[torch.Tensor],
+                          points_per_dim: int, levels: int, radius: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    return mncc_search_scene(ref, ref_mask, views, view_masks, points_per_dim, levels, radius)
+
+
+@torch.library.custom_op("hrnet_hip::shift_scene", mutates_args=(), device_types="cuda")
+def _op_shift_scene(views: torch.Tensor, view_masks: Optional[torch.Tensor], shifts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return mncc_apply_scene(views, view_masks, shifts)
+
+
+_op_mncc_grid_scene.register_fake(_fake_mncc_grid)
+_op_mncc_search_scene.register_fake(_fake_mncc_search)
+_op_shift_scene.register_fake(_fake_shift_views)
 
 
 @torch.library.custom_op("hrnet_hip::adam_step", mutates_args=("params", "exp_avg", "exp_avg_sq"), device_types="cuda")

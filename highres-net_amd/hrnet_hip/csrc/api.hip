@@ -443,10 +443,9 @@ int hrn_shift_loss_backward(const float* srs, const float* hrs, const float* map
 }
 
 // the masked-NCC registration search (registration.hip): the reference fork's recursive_mncc_search / compute_grid_mncc, restated
-static int mncc_check(const char* who, int B, int V, int H, int W) {
+static int mncc_check(const char* who, int B, int V, int H, int W, int lo = HRN_MNCC_MIN_SIDE, int hi = HRN_MNCC_MAX_SIDE) {
     HRN_CHECK(B > 0 && V > 0 && (long)B * V <= 0x7fffffffL, -2, "%s: bad batch B=%d V=%d", who, B, V);
-    HRN_CHECK(H >= HRN_MNCC_MIN_SIDE && H <= HRN_MNCC_MAX_SIDE && W >= HRN_MNCC_MIN_SIDE && W <= HRN_MNCC_MAX_SIDE, -2,
-              "%s: bad shape H=%d W=%d: the sides of a frame must be %d..%d", who, H, W, HRN_MNCC_MIN_SIDE, HRN_MNCC_MAX_SIDE);
+    HRN_CHECK(H >= lo && H <= hi && W >= lo && W <= hi, -2, "%s: bad shape H=%d W=%d: the sides of a frame must be %d..%d", who, H, W, lo, hi);
     return 0;
 }
 
@@ -480,6 +479,51 @@ int hrn_mncc_apply(const float* views, const float* view_masks, const float* shi
     if (int rc = mncc_check("hrn_mncc_apply", B, V, H, W)) return rc;
     HRN_CHECK(views && shifts && out && out_valid, -2, "hrn_mncc_apply: null argument");
     return hrn_launch_mncc_apply(views, view_masks, shifts, B, V, H, W, out, out_valid, (hipStream_t)stream);
+}
+
+// the same search and resampling for frames of any size, in tiles (registration_scene.hip)
+static int mncc_scene_check(const char* who, int B, int V, int H, int W) {
+    if (int rc = mncc_check(who, B, V, H, W, HRN_MNCC_SCENE_MIN_SIDE, HRN_MNCC_SCENE_MAX_SIDE)) return rc;
+    HRN_CHECK(hrn_mncc_scene_grid_fits(B, V, H, W), -2, "%s: bad batch B=%d V=%d: the tiles of %d x %d frames exceed one launch", who, B, V, H, W);
+    return 0;
+}
+
+size_t hrn_mncc_scene_workspace_bytes(int B, int V, int H, int W, int P) {
+    if (B <= 0 || V <= 0 || (long)B * V > 0x7fffffffL || H < HRN_MNCC_SCENE_MIN_SIDE || H > HRN_MNCC_SCENE_MAX_SIDE ||
+        W < HRN_MNCC_SCENE_MIN_SIDE || W > HRN_MNCC_SCENE_MAX_SIDE || P < HRN_MNCC_MIN_POINTS || P > HRN_MNCC_MAX_POINTS ||
+        !hrn_mncc_scene_grid_fits(B, V, H, W))
+        return 0;
+    return hrn_mncc_scene_workspace_bytes_impl(B, V, H, W, P);
+}
+
+int hrn_mncc_grid_scene(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* centres, int B,
+                        int V, int H, int W, int P, float width, float* scores, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = mncc_scene_check("hrn_mncc_grid_scene", B, V, H, W)) return rc;
+    if (int rc = mncc_check_points("hrn_mncc_grid_scene", P)) return rc;
+    HRN_CHECK(width > 0.f && width <= 8.f, -2, "hrn_mncc_grid_scene: width %g outside (0, 8]", (double)width);
+    HRN_CHECK(ref && views && centres && scores && workspace, -2, "hrn_mncc_grid_scene: null argument");
+    HRN_CHECK(workspace_bytes >= hrn_mncc_scene_workspace_bytes_impl(B, V, H, W, P), -3, "hrn_mncc_grid_scene: workspace too small");
+    return hrn_launch_mncc_grid_scene(ref, ref_mask, views, view_masks, centres, B, V, H, W, P, width, scores, workspace, (hipStream_t)stream);
+}
+
+int hrn_mncc_search_scene(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H, int W,
+                          int P, int levels, float radius, float* shifts, float* trace, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    if (int rc = mncc_scene_check("hrn_mncc_search_scene", B, V, H, W)) return rc;
+    if (int rc = mncc_check_points("hrn_mncc_search_scene", P)) return rc;
+    HRN_CHECK(levels >= 1 && levels <= HRN_MNCC_MAX_LEVELS, -2, "hrn_mncc_search_scene: levels %d outside 1..%d", levels, HRN_MNCC_MAX_LEVELS);
+    HRN_CHECK(radius > 0.f && radius <= 4.f, -2, "hrn_mncc_search_scene: radius %g outside (0, 4]", (double)radius);
+    HRN_CHECK(ref && views && shifts && workspace, -2, "hrn_mncc_search_scene: null argument");
+    HRN_CHECK(workspace_bytes >= hrn_mncc_scene_workspace_bytes_impl(B, V, H, W, P), -3, "hrn_mncc_search_scene: workspace too small");
+    return hrn_launch_mncc_search_scene(ref, ref_mask, views, view_masks, B, V, H, W, P, levels, radius, shifts, trace, workspace,
+                                        (hipStream_t)stream);
+}
+
+int hrn_mncc_apply_scene(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
+                         float* out_valid, void* stream) {
+    if (int rc = mncc_scene_check("hrn_mncc_apply_scene", B, V, H, W)) return rc;
+    HRN_CHECK(views && shifts && out && out_valid, -2, "hrn_mncc_apply_scene: null argument");
+    return hrn_launch_mncc_apply_scene(views, view_masks, shifts, B, V, H, W, out, out_valid, (hipStream_t)stream);
 }
 
 }  // extern "C"

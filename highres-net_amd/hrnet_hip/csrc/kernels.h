@@ -66,6 +66,20 @@ int hrn_launch_mncc_search(const float* ref, const float* ref_mask, const float*
 int hrn_launch_mncc_apply(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
                           float* out_valid, hipStream_t stream);
 
+// ---- registration_scene.hip: the same search and resampling for frames of any size, in tiles.  workspace:
+// hrn_mncc_scene_workspace_bytes_impl bytes; hrn_mncc_scene_grid_fits: the tiles of all views fit one launch's grid.
+constexpr int HRN_MNCC_SCENE_MIN_SIDE = 16, HRN_MNCC_SCENE_MAX_SIDE = 16384;
+constexpr int HRN_MNCC_SCENE_TILE = 64;                            // the core tile a workgroup owns, a side
+constexpr int HRN_MNCC_SCENE_MEAN_CHUNK = 16384, HRN_MNCC_SCENE_MEAN_CHUNKS = 64;  // a frame's mean: chunks of at least this many pixels, at most so many
+size_t hrn_mncc_scene_workspace_bytes_impl(int B, int V, int H, int W, int P);
+bool hrn_mncc_scene_grid_fits(int B, int V, int H, int W);
+int hrn_launch_mncc_grid_scene(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* centres,
+                               int B, int V, int H, int W, int P, float width, float* scores, void* workspace, hipStream_t stream);
+int hrn_launch_mncc_search_scene(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H,
+                                 int W, int P, int levels, float radius, float* shifts, float* trace, void* workspace, hipStream_t stream);
+int hrn_launch_mncc_apply_scene(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
+                                float* out_valid, hipStream_t stream);
+
 // ---- shiftnet.hip.  dt: storage of the activation tensors x / out / y - HRN_F32 or HRN_BF16, one bf16 plane (ShiftNet's bf16
 // training mode); statistics, scale / shift and fc1's input xr are f32 in both
 int hrn_launch_bn_stats(int dt, const void* x, size_t npix, int C, const float* gamma, const float* beta, float eps,

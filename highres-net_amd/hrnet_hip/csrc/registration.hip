@@ -17,8 +17,7 @@
 // hrn_mncc_grid and a level of hrn_mncc_search are the same device function, so their scores agree bit for bit.
 #include "kernels.h"
 #include "wave_sums.h"
-
-#pragma clang fp contract(off)      // every fused multiply-add below is written out: the two kernels that share a level must round alike
+#include "mncc_common.h"            // what the tiled path (registration_scene.hip) shares; it also turns fp contraction off
 
 namespace {
 
@@ -26,8 +25,6 @@ constexpr int RG_MAX = HRN_MNCC_MAX_SIDE, RG_PMAX = HRN_MNCC_MAX_POINTS;
 constexpr int RG_THREADS = 512, RG_WAVES = RG_THREADS / 64;
 constexpr int RG_RUN = 8;                       // rows of one column that a thread takes at a time
 constexpr int RG_ITEMS = (RG_MAX / RG_RUN) * RG_MAX / RG_THREADS;   // such runs per thread at 128 x 128
-constexpr int RG_NSUM = 6;                      // n, sum t, sum r, sum t^2, sum r^2, sum r t
-constexpr float RG_DMAX = 256.f;                // a coordinate beyond this leaves no pixel valid at any allowed frame size
 
 struct RegShared {
     double red[RG_PMAX][RG_WAVES][8];
@@ -40,42 +37,6 @@ struct RegShared {
     float score[RG_PMAX * RG_PMAX];
     float best[3];
 };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// d -> n = floor(d), f = d - n (exact in fp64) and the six normalised taps k_o = sinc(o - f) sinc((o - f) / 3), o = -2..3
-__device__ void split_and_taps(float d, int* n, double* f, float* tap) {
-    const float dc = fminf(fmaxf(d, -RG_DMAX), RG_DMAX);        // also takes a NaN to a finite value; beyond +-RG_DMAX nothing is valid anyway
-    const double fl = floor((double)dc);
-    const double fr = (double)dc - fl;
-    double k[6], sum = 0.0;
-#pragma unroll
-    for (int o = 0; o < 6; ++o) {
-        const double x = (double)(o - 2) - fr;
-        const double px = 3.141592653589793 * x, px3 = 3.141592653589793 * (x / 3.0);
-        const double a = x == 0.0 ? 1.0 : sin(px) / px;
-        const double b = x == 0.0 ? 1.0 : sin(px3) / px3;
-        k[o] = fabs(x) >= 3.0 ? 0.0 : a * b;
-        sum += k[o];
-    }
-#pragma unroll
-    for (int o = 0; o < 6; ++o) tap[o] = (float)(k[o] / sum);
-    *n = (int)fl;
-    *f = fr;
-}
-
-// bit q of the result: (1 - fy) ((1 - fx) q0 + fx q1) + fy ((1 - fx) q2 + fx q3) > 0.5, q0..q3 the bits of q: the mask at (y, x), (y, x + 1),
-// (y + 1, x), (y + 1, x + 1).  fp64, in the order the definition writes it.
-__device__ unsigned mask_table(double fy, double fx) {
-    unsigned bits = 0;
-    for (int q = 0; q < 16; ++q) {
-        const double q0 = q & 1, q1 = (q >> 1) & 1, q2 = (q >> 2) & 1, q3 = (q >> 3) & 1;
-        const double top = (1.0 - fx) * q0 + fx * q1, bot = (1.0 - fx) * q2 + fx * q3;
-        const double v = (1.0 - fy) * top + fy * bot;
-        bits |= (unsigned)(v > 0.5) << q;
-    }
-    return bits;
-}
 
 // the sums of the whole workgroup, in a fixed order: every thread gets sum over threads of v[i], i < N (N a power of two <= 8)
 template <int N>
@@ -199,7 +160,7 @@ __device__ void mncc_level(const float* T, float* A, const unsigned char* pat, R
     if (tid < 2 * P) {
         const int axis = tid / P, i = tid - axis * P;
         const double c = (double)(axis ? cx : cy);
-        const float d = (float)(c - width / 2.0 + (double)i * width / (double)(P - 1));
+        const float d = grid_coord(c, width, i, P);
         S.coord[axis][i] = d;
         split_and_taps(d, &S.whole[axis][i], &S.frac[axis][i], S.tap[axis][i]);
     }
@@ -249,13 +210,8 @@ __device__ void mncc_level(const float* T, float* A, const unsigned char* pat, R
     __syncthreads();
     if (tid < P * P) {
         const double* s = S.tot[tid];
-        const double n = s[0];
-        float score = -INFINITY;
-        if (n > 0.0) {
-            const double mt = s[1] / n, mr = s[2] / n;
-            const double vt = s[3] / n - mt * mt, vr = s[4] / n - mr * mr;
-            if (vt > 0.0 && vr > 0.0) score = (float)((s[5] / n - mr * mt) / (sqrt(vr) * sqrt(vt)));
-        }
+        float score;
+        MNCC_SCORE(s, score);
         S.score[tid] = score;
     }
     __syncthreads();
@@ -331,10 +287,8 @@ __global__ __launch_bounds__(RG_THREADS) void mncc_kernel(const float* __restric
     for (int k = 0; k < levels; ++k) {
         mncc_level(l.T, l.A, l.pat, S, th, H, W, P, cy, cx, width, tid);
         if (tid == 0) {                          // the first maximum in row-major order; without a finite score the centre stays
-            float best = -INFINITY;
-            for (int i = 0; i < P; ++i)
-                for (int j = 0; j < P; ++j)
-                    if (S.score[i * P + j] > best) { best = S.score[i * P + j]; cy = S.coord[0][i]; cx = S.coord[1][j]; }
+            float best;
+            MNCC_FIRST_MAXIMUM(S.score, S.coord[0], S.coord[1], P, best, cy, cx);
             S.best[0] = cy; S.best[1] = cx; S.best[2] = best;
             if (trace) {
                 float* tr = trace + (view * levels + k) * 3;

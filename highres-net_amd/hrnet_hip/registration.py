@@ -9,13 +9,18 @@ pixels, so that it stays in [-1, 1].  A shift (dy, dx) means Output(y, x) = Inpu
 
 `mncc_search` is one launch of `hrn_mncc_search`: a workgroup owns a view, keeps it in LDS and walks every level, argmax included.
 `shift_views` is `hrn_mncc_apply`.  Both are bit-reproducible.  There is no autograd formula - a shift found by a grid search is
-piecewise constant in the frames - and no CPU fallback: tensors must be on a ROCm device.  Frames are 16..128 pixels a side."""
+piecewise constant in the frames - and no CPU fallback: tensors must be on a ROCm device.  Frames are 16..128 pixels a side.
+
+`mncc_search_scene`, `mncc_grid_scene`, `shift_scene` and `register_scene` are the same four for frames of 16..16384 pixels a side
+(DESIGN.md section 7g): the scenes `HRNet.forward_tiled` takes, the large benchmark shape, an SR / HR pair.  A frame is cut into tiles
+of 64 x 64; a level of the search is two launches and the next level reads its centre from device memory.  Same definitions, same
+arguments, same errors; `shift_scene` is bit-identical to `shift_views` where both run."""
 import torch
 
 from . import binding
 
 
-def _frames(lrs, lr_masks, what="lrs"):
+def _frames(lrs, lr_masks, scene=False, what="lrs"):
     if not torch.is_tensor(lrs):
         raise TypeError(f"{what} must be a torch.Tensor; got {type(lrs).__name__}")
     if lrs.dim() != 4:
@@ -25,7 +30,7 @@ def _frames(lrs, lr_masks, what="lrs"):
             raise TypeError(f"lr_masks must be a torch.Tensor or None; got {type(lr_masks).__name__}")
         if lr_masks.shape != lrs.shape:
             raise ValueError(f"lr_masks must have the shape of {what}, {tuple(lrs.shape)}; got {tuple(lr_masks.shape)}")
-    lo, hi = binding.MNCC_SIDES
+    lo, hi = binding.MNCC_SCENE_SIDES if scene else binding.MNCC_SIDES
     if not (lo <= lrs.shape[2] <= hi and lo <= lrs.shape[3] <= hi):
         raise ValueError(f"frames must be {lo}..{hi} pixels a side; got {tuple(lrs.shape[2:])}")
 
@@ -69,18 +74,27 @@ def mncc_search(lrs, lr_masks=None, ref=None, ref_mask=None, points_per_dim=7, l
     of `levels` searches a points_per_dim^2 grid of width 2 radius s^k around the previous level's best point, s = 1 / (points_per_dim
     - 2) kept within [0.25, 0.9].  return_trace: also (B,V,levels,3) = (dy, dx, score) of every level's best point.  A view without a
     valid score (all zeros, or masked out) gets shift (0, 0) and a score of -inf.  Not differentiable."""
-    _frames(lrs, lr_masks)
+    return _search(False, lrs, lr_masks, ref, ref_mask, points_per_dim, levels, radius, return_trace)
+
+
+def _search(scene, lrs, lr_masks, ref, ref_mask, points_per_dim, levels, radius, return_trace):
+    _frames(lrs, lr_masks, scene)
     ref, ref_mask = _reference(lrs, lr_masks, ref, ref_mask)
     P, levels, radius = _search_args(points_per_dim, levels, radius)
     _on_device(lrs=lrs, lr_masks=lr_masks, ref=ref, ref_mask=ref_mask)
-    shifts, trace = torch.ops.hrnet_hip.mncc_search(ref, ref_mask, lrs, lr_masks, P, levels, radius)
+    op = torch.ops.hrnet_hip.mncc_search_scene if scene else torch.ops.hrnet_hip.mncc_search
+    shifts, trace = op(ref, ref_mask, lrs, lr_masks, P, levels, radius)
     return (shifts, trace) if return_trace else shifts
 
 
 def mncc_grid(lrs, lr_masks=None, ref=None, ref_mask=None, centres=None, points_per_dim=7, width=2.0):
     """One level of the search, the diagnostic: -> scores (B,V,P,P) f32 at the grid points (cy - width / 2 + i width / (P - 1), cx - width
     / 2 + j width / (P - 1)) around centres (B,V,2) = (cy, cx) (None: zeros); -inf where no pixel is valid or a variance is zero."""
-    _frames(lrs, lr_masks)
+    return _grid(False, lrs, lr_masks, ref, ref_mask, centres, points_per_dim, width)
+
+
+def _grid(scene, lrs, lr_masks, ref, ref_mask, centres, points_per_dim, width):
+    _frames(lrs, lr_masks, scene)
     ref, ref_mask = _reference(lrs, lr_masks, ref, ref_mask)
     P = binding.mncc_int("points_per_dim", points_per_dim, binding.MNCC_POINTS)
     width = float(width)
@@ -93,19 +107,24 @@ def mncc_grid(lrs, lr_masks=None, ref=None, ref_mask=None, centres=None, points_
     elif tuple(centres.shape) != tuple(lrs.shape[:2]) + (2,):
         raise ValueError(f"centres must be (B,V,2) = {tuple(lrs.shape[:2]) + (2,)}; got {tuple(centres.shape)}")
     _on_device(lrs=lrs, lr_masks=lr_masks, ref=ref, ref_mask=ref_mask, centres=centres)
-    return torch.ops.hrnet_hip.mncc_grid(ref, ref_mask, lrs, lr_masks, centres, P, width)
+    op = torch.ops.hrnet_hip.mncc_grid_scene if scene else torch.ops.hrnet_hip.mncc_grid
+    return op(ref, ref_mask, lrs, lr_masks, centres, P, width)
 
 
 def shift_views(lrs, lr_masks, shifts):
     """-> (registered (B,V,H,W) = S(view, shift), valid (B,V,H,W) f32 0 / 1): the views resampled by shifts (B,V,2) and which of their
     pixels are valid - the six-tap footprint inside the frame and the bilinear sample of the mask above 0.5.  Invalid pixels are 0."""
-    _frames(lrs, lr_masks)
+    return _shift(False, lrs, lr_masks, shifts)
+
+
+def _shift(scene, lrs, lr_masks, shifts):
+    _frames(lrs, lr_masks, scene)
     if not torch.is_tensor(shifts):
         raise TypeError(f"shifts must be a torch.Tensor; got {type(shifts).__name__}")
     if tuple(shifts.shape) != tuple(lrs.shape[:2]) + (2,):
         raise ValueError(f"shifts must be (B,V,2) = {tuple(lrs.shape[:2]) + (2,)}; got {tuple(shifts.shape)}")
     _on_device(lrs=lrs, lr_masks=lr_masks, shifts=shifts)
-    return torch.ops.hrnet_hip.shift_views(lrs, lr_masks, shifts)
+    return (torch.ops.hrnet_hip.shift_scene if scene else torch.ops.hrnet_hip.shift_views)(lrs, lr_masks, shifts)
 
 
 def register_views(lrs, lr_masks=None, **search_kwargs):
@@ -115,4 +134,32 @@ def register_views(lrs, lr_masks=None, **search_kwargs):
         raise TypeError("register_views returns no trace: call mncc_search(..., return_trace=True) and shift_views")
     shifts = mncc_search(lrs, lr_masks, **search_kwargs)
     registered, valid = shift_views(lrs, lr_masks, shifts)
+    return registered, valid, shifts
+
+
+# ----------------------------------------------------------------------------- the same four for frames of any size (section 7g)
+def mncc_search_scene(lrs, lr_masks=None, ref=None, ref_mask=None, points_per_dim=7, levels=6, radius=1.0, return_trace=False):
+    """`mncc_search` for frames of 16..16384 pixels a side: 1 + 2 levels launches of `hrn_mncc_search_scene` on tiles of 64 x 64, no
+    return to the host between them.  The level-k scores are `mncc_grid_scene`'s bit for bit, and a view's result does not depend on
+    the batch around it."""
+    return _search(True, lrs, lr_masks, ref, ref_mask, points_per_dim, levels, radius, return_trace)
+
+
+def mncc_grid_scene(lrs, lr_masks=None, ref=None, ref_mask=None, centres=None, points_per_dim=7, width=2.0):
+    """`mncc_grid` for frames of 16..16384 pixels a side.  A grid coordinate beyond +-256 is taken as +-256."""
+    return _grid(True, lrs, lr_masks, ref, ref_mask, centres, points_per_dim, width)
+
+
+def shift_scene(lrs, lr_masks, shifts):
+    """`shift_views` for frames of 16..16384 pixels a side; bit-identical to it where both run."""
+    return _shift(True, lrs, lr_masks, shifts)
+
+
+def register_scene(lrs, lr_masks=None, **search_kwargs):
+    """mncc_search_scene, then shift_scene by what it found: -> (registered, valid, shifts).  search_kwargs: ref, ref_mask,
+    points_per_dim, levels, radius.  `registered` goes to `HRNet.forward_tiled` as the views did."""
+    if "return_trace" in search_kwargs:
+        raise TypeError("register_scene returns no trace: call mncc_search_scene(..., return_trace=True) and shift_scene")
+    shifts = mncc_search_scene(lrs, lr_masks, **search_kwargs)
+    registered, valid = shift_scene(lrs, lr_masks, shifts)
     return registered, valid, shifts

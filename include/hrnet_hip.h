@@ -22,7 +22,8 @@
  *   hrn_get_loss / hrn_shift_cpsnr  <-  get_loss (train.py:66-87) / shift_cPSNR (Evaluator.py:52-73)
  *   hrn_shift_loss_train / hrn_shift_loss_backward  <-  the two combined as a differentiable loss (the searched score, trainable)
  *   hrn_mncc_grid / hrn_mncc_search / hrn_mncc_apply  <-  the method of the fork's registration_search.py (recursive_mncc_search over
- *                              compute_grid_mncc), restated: sub-pixel registration of the LR views against a reference frame
+ *                              compute_grid_mncc), restated: sub-pixel registration of the LR views against a reference frame;
+ *                              hrn_mncc_grid_scene / hrn_mncc_search_scene / hrn_mncc_apply_scene: the same for frames of any size
  *   hrn_collate_device     <-  collateFunction(min_L) over ImagesetDataset items (src/utils.py:63-113), gathered from
  *                              imagesets decoded once into HBM (DataLoader.DeviceImagesetCache); hrn_collate_device_s
  *                              is the same for x2 / x3 / x4 targets
@@ -315,7 +316,7 @@ int hrn_shift_loss_backward(const float* srs, const float* hrs, const float* hr_
  * The method of the reference fork's registration_search.py / registration_metrics.py (compute_shift_ncc -> recursive_mncc_search ->
  * compute_grid_mncc), on definitions of this project's own; tests/registration_ref.py restates them in fp64 and is what the tests
  * compare against.  ref / ref_mask (B,H,W), views / view_masks (B,V,H,W), all f32; a mask is 0 / non-zero and a NULL mask pointer
- * means all ones.  16 <= H, W <= 128.
+ * means all ones.  16 <= H, W <= 128 for the first three entry points (a view resident in one CU's LDS), 16..16384 for the *_scene ones.
  *   shift    s = (dy, dx):  Output(y, x) = Input(y + dy, x + dx) - the order and sign of hrn_lanczos_shift's `shift`, the negative of the
  *            fork's ndi_shift convention.
  *   sampler  S(T, s), per axis: n = floor(d), f = d - n on the fp32 value of d; six taps at sample offsets o = -2..3, k_o = sinc(o - f)
@@ -345,6 +346,29 @@ int hrn_mncc_search(const float* ref, const float* ref_mask, const float* views,
                     int levels, float radius, float* shifts, float* trace, void* stream);
 int hrn_mncc_apply(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
                    float* out_valid, void* stream);
+/* The same definitions for frames of any size, 16 <= H, W <= 16384 (the "scene" path, beside hrn_hrnet_forward's tiled inference): a
+ * frame is cut into tiles of 64 x 64 pixels, a workgroup stages a tile of the view plus a halo into LDS per level, and a second, small
+ * launch per level adds the tiles' fp64 sums in index order, forms the scores and takes the first maximum.  The next level reads its
+ * centre from device memory: nothing returns to the host.  Both images are centred on their whole-frame masked means (fixed-order
+ * fp64 sums, the mean rounded to fp32) before a score's sums are taken, as above; tiles are never centred apart.
+ * hrn_mncc_scene_workspace_bytes  the workspace of the two entry points below; 0 for arguments they refuse.  With T = ceil(H / 64)
+ *                  ceil(W / 64) tiles and C = min(64, ceil(H W / 16384)) chunks of a frame's mean:
+ *                      16 (B V + B) C  +  48 P^2 B V T  +  8 B V   bytes
+ *                  (the chunks' {sum, count}, the tiles' six sums per grid point, the centres): at most the 4 B V H W bytes of `views`
+ *                  wherever H, W >= 64.
+ * hrn_mncc_grid_scene    as hrn_mncc_grid.  A grid coordinate beyond +-256 is taken as +-256.
+ * hrn_mncc_search_scene  as hrn_mncc_search, in 1 + 2 levels launches.  Its level-k scores are hrn_mncc_grid_scene's, bit for bit.
+ * hrn_mncc_apply_scene   as hrn_mncc_apply, and bit-identical to it wherever both run.  No workspace.
+ * Fixed-order sums, no atomics: bit-reproducible, and a view's result does not depend on the batch around it.  -2 before any launch as
+ * above (H or W outside 16..16384; a null workspace; B V T beyond 2^31 - 1), -3 for a workspace that is too small. */
+size_t hrn_mncc_scene_workspace_bytes(int B, int V, int H, int W, int P);
+int hrn_mncc_grid_scene(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* centres, int B,
+                        int V, int H, int W, int P, float width, float* scores, void* workspace, size_t workspace_bytes, void* stream);
+int hrn_mncc_search_scene(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H, int W,
+                          int P, int levels, float radius, float* shifts, float* trace, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int hrn_mncc_apply_scene(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
+                         float* out_valid, void* stream);
 
 /* ------------------------------------------------------------------ optimiser
  * hrn_adam_step  <-  optimizer.step() of torch.optim.Adam (src/train.py:191, :252), one launch over a flat fp32 buffer
