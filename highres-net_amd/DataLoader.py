@@ -21,6 +21,14 @@ view and of HR / SM.  The draw is one extra `np.random.randint(0, MODES[mode])` 
 views and corner with or without it, and with augmentation off no RNG call is added anywhere.  The transform is an addressing
 change inside the gathers that run anyway (hrn_io_collate_a on the host, hrn_collate_device_a in the cache); the codes of the last
 batch are kept in `last_augment` so that a caller can undo them (`augment.inverse`).
+
+LR quality masks (`lr_masks`, else config["lr_masks"]; off by default): the per-view quality maps `QM*.png` of the views a batch
+carries, in the order, window and orientation of its `lrs` - float32, 1.0 where the stored QM sample is non-zero (the rule of
+`hr_map` for SM.png), zeros in padding slots - as a sixth item of every batch, ready to be the `lr_masks` of
+`hrnet_hip.registration.register_views` / `register_scene`.  They ride in the gathers that build the batch anyway
+(hrn_io_collate_m on the host, hrn_collate_device_m from a fourth arena in the cache) and draw nothing from the RNG.  With the
+switch off no QM file is opened and every return value is what it was.  `save_clearance_scores` writes the `clearance.npy` the
+loaders ask for from the same files.
 """
 from collections import OrderedDict
 import operator
@@ -119,16 +127,30 @@ def _ratio_error(name, lr_side, scale, found):
                       f"path does not resample - build a device cache with to_device(resample_targets=True)")
 
 
-def read_imageset(imset_dir, create_patches=False, patch_size=64, seed=None, top_k=None, beta=0., scale=3, augment=None):
+def _qm_mismatch(path, found, side):
+    """The ValueError for a quality map that is not the size of its LR view."""
+    return ValueError(f"{path} is {found[1]}x{found[0]} but its LR view is {side[1]}x{side[0]}")
+
+
+def read_imageset(imset_dir, create_patches=False, patch_size=64, seed=None, top_k=None, beta=0., scale=3, augment=None, lr_masks=False):
     """ImageSet(name, lr uint16 (L,H,W), hr uint16 or None, hr_map bool, clearances) of one imageset directory, PNGs decoded by
     the native reader.  With `create_patches` one random `patch_size` window is cut from every LR view and the matching
     `scale`x window from SM / HR, whose files must be `scale` times the LR side (ValueError otherwise).  `augment` (a mode of
-    hrnet_hip/augment.py): one code is drawn after the views and the corner and applied to lr, hr_map and hr."""
+    hrnet_hip/augment.py): one code is drawn after the views and the corner and applied to lr, hr_map and hr.  `lr_masks`: a
+    further key `lr_maps` after `clearances`, bool (L,H,W): QM*.png != 0 of the views of `lr`, in their order, window and code."""
     scale = check_scale(scale)
     mode = _augment.check_mode(augment)
     ids, scores = _views_in_use_order(imset_dir, top_k, beta, seed)
     asset = lambda name: os.path.join(imset_dir, name)
     lr = np.stack([io_binding.png_read(asset(f"LR{i}.png")) for i in ids]).astype(np.uint16, copy=False)
+    lr_maps = None
+    if lr_masks:
+        lr_maps = []
+        for i in ids:
+            lr_maps.append(io_binding.png_read(asset(f"QM{i}.png")) != 0)
+            if lr_maps[-1].shape != lr.shape[1:]:
+                raise _qm_mismatch(asset(f"QM{i}.png"), lr_maps[-1].shape, lr.shape[1:])
+        lr_maps = np.stack(lr_maps)
     hr_map = io_binding.png_read(asset("SM.png")) != 0
     hr = io_binding.png_read(asset("HR.png")).astype(np.uint16, copy=False) if os.path.exists(asset("HR.png")) else None
     for img in (hr_map, hr):
@@ -138,6 +160,8 @@ def read_imageset(imset_dir, create_patches=False, patch_size=64, seed=None, top
         row, col = _corner(lr.shape[1], patch_size, seed)
         lr = get_patch(lr, row, col, patch_size)
         hr_map = get_patch(hr_map, scale * row, scale * col, scale * patch_size)
+        if lr_maps is not None:
+            lr_maps = get_patch(lr_maps, row, col, patch_size)
         if hr is not None:
             hr = get_patch(hr, scale * row, scale * col, scale * patch_size)
     if mode is not None:
@@ -145,7 +169,26 @@ def read_imageset(imset_dir, create_patches=False, patch_size=64, seed=None, top
         lr, hr_map = _augment.apply(lr, code), np.ascontiguousarray(_augment.apply(hr_map, code))
         if hr is not None:
             hr = np.ascontiguousarray(_augment.apply(hr, code))
-    return ImageSet(name=os.path.basename(imset_dir), lr=np.array(lr), hr=hr, hr_map=hr_map, clearances=scores)
+        if lr_maps is not None:
+            lr_maps = _augment.apply(lr_maps, code)
+    out = ImageSet(name=os.path.basename(imset_dir), lr=np.array(lr), hr=hr, hr_map=hr_map, clearances=scores)
+    if lr_maps is not None:
+        out["lr_maps"] = np.array(lr_maps)
+    return out
+
+
+def save_clearance_scores(dataset_directories):
+    """Write `clearance.npy` into every imageset directory of `dataset_directories`: per view, in sorted view-id order, the sum of
+    the stored sample values of its QM*.png (uint16 samples summed by numpy.sum, so the saved array is uint64) - the score the
+    loaders sort and sample the views by.  Returns the arrays, one per directory."""
+    saved = []
+    for d in dataset_directories:
+        ids = np.sort(np.array([m.group(1) for m in map(_QM_FILE.match, os.listdir(d)) if m]))
+        maps = np.array([io_binding.png_read(os.path.join(d, f"QM{i}.png")).astype(np.uint16, copy=False) for i in ids])
+        scores = np.sum(maps, axis=(1, 2))
+        np.save(os.path.join(d, "clearance.npy"), scores)
+        saved.append(scores)
+    return saved
 
 
 class ImagesetDataset(Dataset):
@@ -155,13 +198,15 @@ class ImagesetDataset(Dataset):
     the files.  `augment` (None: config.get("augment"); then None / False / "none" off, "flip", "dihedral" or True): one flip /
     rotation code per imageset (module docstring); `last_augment` holds the codes of the last item or batch loaded (a list of
     ints, None while augmentation is off).  None defers to the config, so a dataset built from a config that carries the key
-    is switched off with `augment=False`."""
+    is switched off with `augment=False`.  `lr_masks` (None: config.get("lr_masks", False)): items carry `lr_maps`, float32
+    (L,S,S), and `load_batch` returns a sixth item, the (B,min_L,S,S) quality masks of the views in `lrs` (module docstring)."""
 
-    def __init__(self, imset_dir, config, seed=None, top_k=-1, beta=0., scale=None, augment=None):
+    def __init__(self, imset_dir, config, seed=None, top_k=-1, beta=0., scale=None, augment=None, lr_masks=None):
         super().__init__()
         self.scale = check_scale(config.get("scale", 3) if scale is None else scale)
         self.augment = _augment.check_mode(config.get("augment") if augment is None else augment)
         self.last_augment = None
+        self.lr_masks = bool(config.get("lr_masks", False) if lr_masks is None else lr_masks)
         self.imset_dir = imset_dir
         self.name_to_dir = dict(zip(map(os.path.basename, imset_dir), imset_dir))
         self.create_patches, self.patch_size = config["create_patches"], config["patch_size"]
@@ -194,8 +239,9 @@ class ImagesetDataset(Dataset):
         corner = _corner(lr_side, self.patch_size, self.seed) if self.create_patches else (0, 0)
         code = _draw_code(self.augment, self.seed) if self.augment is not None else None
         hr_path = os.path.join(dir_, "HR.png") if os.path.exists(os.path.join(dir_, "HR.png")) else None
+        qm_paths = [os.path.join(dir_, f"QM{i}.png") for i in idx_names] if self.lr_masks else None
         return dict(name=os.path.basename(dir_), lr_paths=lr_paths, clearances=clearances, lr_side=lr_side, corner=corner, hr=hr_path,
-                    sm=os.path.join(dir_, "SM.png"), code=code)
+                    sm=os.path.join(dir_, "SM.png"), code=code, qm_paths=qm_paths)
 
     def _codes(self, plans):
         """Codes of a batch for io_binding.collate (None while augmentation is off), recorded in `last_augment`."""
@@ -205,6 +251,8 @@ class ImagesetDataset(Dataset):
     def _collate(self, plans, **kw):
         """io_binding.collate at the dataset's scale.  A failure is looked at only after the fact (no extra file read on the
         good path): if an HR / SM file of the batch is not scale x its LR side, that is the ValueError to raise."""
+        if self.lr_masks:
+            kw["qm_paths_per_set"] = [pl["qm_paths"] for pl in plans]
         try:
             return io_binding.collate(scale=self.scale, **kw)
         except io_binding.HrnetIoError as err:
@@ -222,12 +270,16 @@ class ImagesetDataset(Dataset):
         out = self._collate([pl], lr_paths_per_set=[pl["lr_paths"]], hr_paths=[pl["hr"]], sm_paths=[pl["sm"]], min_L=len(pl["lr_paths"]),
                             lr_size=pl["lr_side"], patch=patch, corners=[pl["corner"]], codes=self._codes([pl]))
         labelled = pl["hr"] is not None
-        return ImageSet(name=pl["name"], lr=torch.from_numpy(out["lrs"][0]), hr=torch.from_numpy(out["hrs"][0]) if labelled else None,
+        item = ImageSet(name=pl["name"], lr=torch.from_numpy(out["lrs"][0]), hr=torch.from_numpy(out["hrs"][0]) if labelled else None,
                         hr_map=torch.from_numpy(out["maps"][0]) if labelled else out["maps"][0].astype(bool), clearances=pl["clearances"])
+        if self.lr_masks:
+            item["lr_maps"] = torch.from_numpy(out["lr_masks"][0])
+        return item
 
     def load_batch(self, indices, min_L, pin_memory=False, n_threads=0):
         """One collated batch (padded_lr (B,min_L,S,S), alphas (B,min_L), hrs (B,kS,kS) or [], hr_maps (B,kS,kS), names; k = scale)
-        decoded straight into (optionally pinned) buffers by the native thread pool: __getitem__ + collateFunction in one call."""
+        decoded straight into (optionally pinned) buffers by the native thread pool: __getitem__ + collateFunction in one call.
+        With `lr_masks` on, a sixth item: the quality masks (B,min_L,S,S) of the views in padded_lr, zeros in padding slots."""
         plans = [self._plan(self.imset_dir[i] if isinstance(i, int) else self.name_to_dir[i]) for i in indices]
         side = plans[0]["lr_side"]
         if any(p["lr_side"] != side for p in plans):
@@ -239,11 +291,13 @@ class ImagesetDataset(Dataset):
         have_hr = all(p["hr"] is not None for p in plans)
         mk = lambda *shape: torch.empty(shape, dtype=torch.float32, pin_memory=pin_memory)
         out = dict(lrs=mk(B, min_L, S, S), alphas=mk(B, min_L), hrs=mk(B, T, T) if have_hr else None, maps=mk(B, T, T))
+        if self.lr_masks:
+            out["lr_masks"] = mk(B, min_L, S, S)
         self._collate(plans, lr_paths_per_set=[p["lr_paths"] for p in plans], hr_paths=[p["hr"] for p in plans] if have_hr else None,
                       sm_paths=[p["sm"] for p in plans], min_L=min_L, lr_size=side, patch=patch, corners=[p["corner"] for p in plans], out=out,
                       n_threads=n_threads, codes=self._codes(plans))
-        return out["lrs"], out["alphas"], out["hrs"] if have_hr else [], out["maps"], [p["name"] for p in plans]
-
+        batch = out["lrs"], out["alphas"], out["hrs"] if have_hr else [], out["maps"], [p["name"] for p in plans]
+        return batch + (out["lr_masks"],) if self.lr_masks else batch
 
     def to_device(self, device="cuda", n_threads=0, resample_targets=False):
         """Decode every imageset once into HBM and return a DeviceImagesetCache: `cache.load_batch(indices, min_L)` then
@@ -260,7 +314,8 @@ def _round4(n):
 class ImagesetIndex:
     """The host half of DeviceImagesetCache, no GPU: every imageset directory listed once, clearance.npy loaded once, the LR
     side and the stored HR / SM side read from one header each, and where each image lives in the three arenas (LR / HR
-    uint16, SM uint8; every image starts at a multiple of 4 elements, as hrn_collate_device requires).  HR / SM slots hold
+    uint16, SM uint8; every image starts at a multiple of 4 elements, as hrn_collate_device requires; with the dataset's `lr_masks`
+    on, a fourth arena QM, uint8, at the LR arena's offsets: `qm_elems` == `lr_elems`, else 0).  HR / SM slots hold
     scale^2 side^2 samples, scale = dataset.scale.  `ratios[k]` is the ratio imageset k is stored at; one that differs from
     the scale needs `resample_targets` (the cache then resamples it into its slot), else it is the host path's ValueError.
     `plan()` turns a batch of indices into the kernel's plan table with exactly the numpy RNG calls ImagesetDataset._plan makes,
@@ -295,6 +350,7 @@ class ImagesetIndex:
             self.sm_off.append(sm_total)
             sm_total += _round4(scale * scale * side * side)
         self.lr_elems, self.hr_elems, self.sm_elems = lr_total, hr_total, sm_total
+        self.qm_elems = lr_total if dataset.lr_masks else 0          # the mask of the view at LR offset o lives at QM offset o
         self.last_augment = None
 
     def _stored_ratio(self, d, side, have_hr, resample_targets):
@@ -367,6 +423,10 @@ class DeviceImagesetCache:
     buffer) and one kernel, all enqueued on the current stream; no device-to-host copy and no synchronisation.  Memory: `nbytes`
     (2 B per LR / HR sample, 1 B per SM sample).
 
+    With the dataset's `lr_masks` on, a fourth arena `qm` (uint8, 0 / 1, one byte per LR sample at the LR arena's offsets; `nbytes`
+    counts it) is decoded beside the others, and `load_batch` / `batches` return the 6-tuple of ImagesetDataset.load_batch from the
+    same single launch (hrn_collate_device_m).
+
     `resample_targets=True`: an imageset whose HR / SM files are stored at another ratio R than the dataset's scale is decoded
     at R into a staging buffer and resampled into its arena slot by hrn_resample_targets (hrnet_hip/resample.py gives the rule:
     Lanczos-3, widened when shrinking; a resampled SM sample is clear only if every source sample under its filter is), one
@@ -389,6 +449,7 @@ class DeviceImagesetCache:
         self.lr = torch.empty(idx.lr_elems, dtype=torch.uint16, device=dev)
         self.hr = torch.empty(idx.hr_elems, dtype=torch.uint16, device=dev) if idx.hr_elems else None
         self.sm = torch.empty(idx.sm_elems, dtype=torch.uint8, device=dev)
+        self.qm = torch.empty(idx.qm_elems, dtype=torch.uint8, device=dev) if idx.qm_elems else None
         tables = {}                                                # (side, R) -> resampling weight table, for the build only
         # decode in chunks of consecutive imagesets (contiguous ranges of each arena) to bound host memory
         start = 0
@@ -402,7 +463,7 @@ class DeviceImagesetCache:
 
     def _decode(self, start, stop, n_threads, tables):
         idx, scale = self.index, self.scale
-        lr_paths, lr_offs, lr_sides = [], [], []
+        lr_paths, lr_offs, lr_sides, qm_paths = [], [], [], []      # a mask shares offset and side with its LR view
         hr_paths, hr_offs, hr_sides, sm_paths, sm_offs, sm_sides = [], [], [], [], [], []
         hr_stage, sm_stage = [], []                                # (path, arena offset, LR side, stored ratio) of images to resample
         for k in range(start, stop):
@@ -410,6 +471,8 @@ class DeviceImagesetCache:
             lr_paths += [os.path.join(d, f"LR{i}.png") for i in idx.ids[k]]
             lr_offs += list(idx.lr_off[k])
             lr_sides += [side] * len(idx.ids[k])
+            if self.qm is not None:
+                qm_paths += [os.path.join(d, f"QM{i}.png") for i in idx.ids[k]]
             if idx.hr_off[k] >= 0:
                 if ratio == scale:
                     hr_paths.append(os.path.join(d, "HR.png"))
@@ -425,7 +488,7 @@ class DeviceImagesetCache:
                 sm_stage.append((os.path.join(d, "SM.png"), idx.sm_off[k], side, ratio))
         is_clear = lambda a: (a != 0).astype(np.uint8)
         for paths, offs, sides, arena, to_host in ((lr_paths, lr_offs, lr_sides, self.lr, None), (hr_paths, hr_offs, hr_sides, self.hr, None),
-                                                   (sm_paths, sm_offs, sm_sides, self.sm, is_clear)):
+                                                   (sm_paths, sm_offs, sm_sides, self.sm, is_clear), (qm_paths, lr_offs, lr_sides, self.qm, is_clear)):
             if not paths:
                 continue
             # one contiguous host range from the first to the last image; slots of images to resample inside it are written
@@ -463,10 +526,11 @@ class DeviceImagesetCache:
 
     @property
     def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in (self.lr, self.hr, self.sm) if t is not None)
+        return sum(t.numel() * t.element_size() for t in (self.lr, self.hr, self.sm, self.qm) if t is not None)
 
     def load_batch(self, indices, min_L):
-        """(lrs (B,min_L,S,S), alphas (B,min_L), hrs (B,kS,kS) or [], hr_maps (B,kS,kS), names) on the cache's device; k = scale."""
+        """(lrs (B,min_L,S,S), alphas (B,min_L), hrs (B,kS,kS) or [], hr_maps (B,kS,kS), names) on the cache's device; k = scale.
+        With the dataset's `lr_masks` on, a sixth item: lr_masks (B,min_L,S,S)."""
         plan, codes, names, S, have_hr = self.index.plan_a(indices, min_L)
         self.last_augment = self.index.last_augment
         B = len(names)
@@ -485,8 +549,11 @@ class DeviceImagesetCache:
             T = self.scale * S
             lrs, alphas, maps = mk(B, min_L, S, S), mk(B, min_L), mk(B, T, T)
             hrs = mk(B, T, T) if have_hr else None
-            binding.collate_device(self.lr, self.hr, self.sm, plan_d, S, lrs, alphas, hrs, maps, scale=self.scale, codes=codes_d)
-        return lrs, alphas, hrs if have_hr else [], maps, names
+            masks = mk(B, min_L, S, S) if self.qm is not None else None
+            binding.collate_device(self.lr, self.hr, self.sm, plan_d, S, lrs, alphas, hrs, maps, scale=self.scale, codes=codes_d,
+                                   qm_arena=self.qm, lr_masks=masks)
+        batch = lrs, alphas, hrs if have_hr else [], maps, names
+        return batch + (masks,) if masks is not None else batch
 
     def batches(self, index_lists, min_L):
         """Batches of `index_lists` in order, in the role of BatchPrefetcher.  Nothing needs a worker thread: a batch costs its
@@ -508,7 +575,8 @@ class BatchPrefetcher:
     decode overlap the kernels of batch n.  Tensors are handed over with `record_stream`, i.e. their memory is not reused
     before the consumer's queued work has finished.  With device=None or "cpu" it is a plain background decoder.
     Errors raised by the worker are re-raised in the consumer at the batch they belong to.  `last_augment` holds the augmentation
-    codes of the batch most recently handed to the consumer (the dataset's own attribute runs ahead with the worker)."""
+    codes of the batch most recently handed to the consumer (the dataset's own attribute runs ahead with the worker).  A dataset
+    with `lr_masks` on yields 6-tuples; the masks are copied and handed over like the other tensors."""
 
     def __init__(self, dataset, batches, min_L, device=None, depth=2, n_threads=0):
         import queue
@@ -535,8 +603,8 @@ class BatchPrefetcher:
                 if self._stop.is_set():
                     return
                 try:
-                    lrs, alphas, hrs, maps, names = self.dataset.load_batch(idx, self.min_L, pin_memory=self.on_gpu,
-                                                                            n_threads=self.n_threads)
+                    lrs, alphas, hrs, maps, names, *masks = self.dataset.load_batch(idx, self.min_L, pin_memory=self.on_gpu,
+                                                                                    n_threads=self.n_threads)
                     event = None
                     if self.on_gpu:
                         with torch.cuda.stream(stream):
@@ -545,9 +613,10 @@ class BatchPrefetcher:
                             maps = maps.to(self.device, non_blocking=True)
                             if isinstance(hrs, torch.Tensor):
                                 hrs = hrs.to(self.device, non_blocking=True)
+                            masks = [m.to(self.device, non_blocking=True) for m in masks]
                             event = torch.cuda.Event()
                             event.record(stream)
-                    item = ("ok", (lrs, alphas, hrs, maps, names, getattr(self.dataset, "last_augment", None)), event, stream)
+                    item = ("ok", ((lrs, alphas, hrs, maps, names, *masks), getattr(self.dataset, "last_augment", None)), event, stream)
                 except Exception as exc:                     # handed to the consumer, in order
                     item = ("err", exc, None, None)
                 while not self._stop.is_set():
@@ -581,11 +650,11 @@ class BatchPrefetcher:
                 if event is not None:
                     cur = torch.cuda.current_stream(self.device)
                     cur.wait_event(event)
-                    for t in payload[:4]:
+                    for t in payload[0]:
                         if isinstance(t, torch.Tensor):
                             t.record_stream(cur)
-                self.last_augment = payload[5]
-                yield payload[:5]
+                self.last_augment = payload[1]
+                yield payload[0]
         finally:
             self.close()
 

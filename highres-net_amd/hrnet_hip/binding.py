@@ -157,6 +157,9 @@ SIGNATURES = {
     "hrn_collate_device_a": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
                                         _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                         _c.c_void_p, _c.c_void_p]),
+    "hrn_collate_device_m": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
+                                        _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                        _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_dihedral_expand": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int32), _c.c_int, _c.c_void_p, _c.c_void_p]),
     "hrn_dihedral_mean": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int32), _c.c_int, _c.c_void_p, _c.c_void_p]),
     "hrn_hrnet_halo": (_c.c_int, [_c.c_int, _c.c_int]),
@@ -588,16 +591,22 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_
 COLLATE_META = 5          # leading int64 fields of a plan row (HRN_COLLATE_META): hr_off, sm_off, side, row, col
 
 
-def collate_device(lr_arena, hr_arena, sm_arena, plan, S, lrs, alphas, hrs, maps, scale=3, codes=None):
+def collate_device(lr_arena, hr_arena, sm_arena, plan, S, lrs, alphas, hrs, maps, scale=3, codes=None, qm_arena=None, lr_masks=None):
     """One launch on the current stream: gather + convert a batch from the device arenas (uint16 LR / HR, uint8 SM) into
     lrs (B,min_L,S,S), alphas (B,min_L), hrs (B,kS,kS) or None, maps (B,kS,kS) f32 with k = `scale` (2, 3 or 4: the HR / LR ratio
     the arenas are stored at), following `plan`, a device int64 (B, COLLATE_META + min_L) table (include/hrnet_hip.h,
     hrn_collate_device_a).  `codes`: None, or a device int32 (B,) tensor of augmentation codes (hrnet_hip/augment.py), one per
-    sample; they are not read back, so a code outside 0..7 shows as NaN planes of that sample, not as an error."""
+    sample; they are not read back, so a code outside 0..7 shows as NaN planes of that sample, not as an error.
+    `qm_arena` with `lr_masks` (both or neither): the uint8 arena of LR quality masks, laid out like `lr_arena`, and the
+    (B,min_L,S,S) f32 output for the masks of the views in `lrs` - the same launch then writes it too (hrn_collate_device_m)."""
     B, min_L = alphas.shape
     use_hr = hrs is not None
     scale = check_scale(scale)
+    if (qm_arena is None) != (lr_masks is None):
+        raise ValueError("qm_arena and lr_masks go together: give both or neither")
     arenas = [("lr_arena", lr_arena, torch.uint16), ("sm_arena", sm_arena, torch.uint8), ("plan", plan, torch.int64)]
+    if qm_arena is not None:
+        arenas.append(("qm_arena", qm_arena, torch.uint8))
     for name, t, dt in arenas + ([("hr_arena", hr_arena, torch.uint16)] if use_hr else []):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() or t.dtype != dt:
             raise RuntimeError(f"{name} must be a contiguous {dt} ROCm device tensor")
@@ -609,14 +618,20 @@ def collate_device(lr_arena, hr_arena, sm_arena, plan, S, lrs, alphas, hrs, maps
     outs = [("lrs", lrs, (B, min_L, S, S)), ("alphas", alphas, (B, min_L)), ("maps", maps, (B, scale * S, scale * S))]
     if hrs is not None:
         outs.append(("hrs", hrs, (B, scale * S, scale * S)))
+    if lr_masks is not None:
+        outs.append(("lr_masks", lr_masks, (B, min_L, S, S)))
     for name, t, shape in outs:
         if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32 or tuple(t.shape) != shape:
             raise ValueError(f"{name} must be a contiguous float32 device tensor of shape {shape}")
-    _check(load_library().hrn_collate_device_a(_ptr(lr_arena), lr_arena.numel(), _ptr(hr_arena) if use_hr else None,
-                                               hr_arena.numel() if use_hr else 0, _ptr(sm_arena), sm_arena.numel(), _ptr(plan), B, min_L, S,
-                                               scale, _ptr(lrs), _ptr(alphas), _ptr(hrs) if use_hr else None, _ptr(maps),
-                                               _ptr(codes) if codes is not None else None, _stream()),
-           "hrn_collate_device_a")
+    head = (_ptr(lr_arena), lr_arena.numel(), _ptr(hr_arena) if use_hr else None, hr_arena.numel() if use_hr else 0, _ptr(sm_arena),
+            sm_arena.numel())
+    tail = (_ptr(lrs), _ptr(alphas), _ptr(hrs) if use_hr else None, _ptr(maps))
+    codes_p = _ptr(codes) if codes is not None else None
+    if lr_masks is None:
+        _check(load_library().hrn_collate_device_a(*head, _ptr(plan), B, min_L, S, scale, *tail, codes_p, _stream()), "hrn_collate_device_a")
+    else:
+        _check(load_library().hrn_collate_device_m(*head, _ptr(qm_arena), qm_arena.numel(), _ptr(plan), B, min_L, S, scale, *tail,
+                                                   _ptr(lr_masks), codes_p, _stream()), "hrn_collate_device_m")
 
 
 # --------------------------------------------------------------------------- flip / rotate self-ensemble

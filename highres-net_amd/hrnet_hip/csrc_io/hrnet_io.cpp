@@ -167,9 +167,11 @@ int hrn_io_png_read_u16(const char* path, uint16_t* out, int width, int height) 
     return read_crop(path, width, height, out, 0, height, 0, width, (size_t)width);
 }
 
-int hrn_io_collate_a(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,
+int hrn_io_collate_m(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,
                      const char* const* sm_paths, int min_L, int lr_size, int patch, int scale, const int* px, const int* py,
-                     float* lrs, float* alphas, float* hrs, float* maps, int n_threads, const int* codes) {
+                     float* lrs, float* alphas, float* hrs, float* maps, int n_threads, const int* codes,
+                     const char* const* qm_paths, float* lr_masks) {
+    if (!qm_paths != !lr_masks) { set_err("hrn_io_collate: qm_paths and lr_masks go together (one of them is null)"); return -2; }
     if (scale < 2 || scale > 4) { set_err("hrn_io_collate: scale must be 2, 3 or 4 (got %d)", scale); return -2; }
     for (int s = 0; codes && s < n_sets; ++s)
         if (codes[s] < 0 || codes[s] > 7) { set_err("hrn_io_collate: augmentation code %d of imageset %d is not in 0..7", codes[s], s); return -2; }
@@ -180,7 +182,7 @@ int hrn_io_collate_a(int n_sets, const char* const* lr_paths, const int* n_views
     }
     const int S = patch > 0 ? patch : lr_size;
     // work items: (set, view slot) for LR, plus HR and SM per set
-    struct Item { int set, kind, slot; const char* path; };      // kind 0 LR, 1 HR, 2 SM
+    struct Item { int set, kind, slot; const char* path; };      // kind 0 LR, 1 HR, 2 SM, 3 QM (the quality mask of an LR slot)
     std::vector<Item> items;
     size_t base = 0;
     for (int s = 0; s < n_sets; ++s) {
@@ -194,6 +196,8 @@ int hrn_io_collate_a(int n_sets, const char* const* lr_paths, const int* n_views
             alphas[(size_t)s * min_L + v] = v < used ? 1.f : 0.f;                    // utils.py:87-95
             if (v < used) items.push_back({s, 0, v, lr_paths[base + v]});
             else memset(lrs + ((size_t)s * min_L + v) * S * S, 0, sizeof(float) * S * S);
+            if (qm_paths && v < used) items.push_back({s, 3, v, qm_paths[base + v]});
+            else if (qm_paths) memset(lr_masks + ((size_t)s * min_L + v) * S * S, 0, sizeof(float) * S * S);
         }
         base += (size_t)n_views[s];
         if (hr_paths && hr_paths[s]) items.push_back({s, 1, 0, hr_paths[s]});
@@ -213,9 +217,12 @@ int hrn_io_collate_a(int n_sets, const char* const* lr_paths, const int* n_views
             const int code = codes ? codes[it.set] : 0;
             const auto as_float = [](uint16_t u) { return (float)((double)u / 65535.0); };          // img_as_float -> float32
             int rc;
-            if (it.kind == 0) {
+            const auto as_clear = [](uint16_t u) { return u ? 1.f : 0.f; };                         // dtype=bool -> float32
+            if (it.kind == 0 || it.kind == 3) {                                              // an LR view or its mask: the same window
                 rc = read_crop(it.path, lr_size, lr_size, buf.data(), x, x + S, y, y + S, (size_t)S);
-                if (!rc) convert_window(buf.data(), lrs + ((size_t)it.set * min_L + it.slot) * S * S, S, code, as_float);
+                const size_t at = ((size_t)it.set * min_L + it.slot) * S * S;
+                if (!rc && it.kind == 0) convert_window(buf.data(), lrs + at, S, code, as_float);
+                else if (!rc) convert_window(buf.data(), lr_masks + at, S, code, as_clear);
             } else {
                 const int S3 = scale * S;                                                   // HR / SM side of the batch
                 rc = read_crop(it.path, scale * lr_size, scale * lr_size, buf.data(), scale * x, scale * x + S3, scale * y, scale * y + S3,
@@ -223,7 +230,7 @@ int hrn_io_collate_a(int n_sets, const char* const* lr_paths, const int* n_views
                 if (!rc) {
                     float* o = (it.kind == 1 ? hrs : maps) + (size_t)it.set * S3 * S3;
                     if (it.kind == 1) convert_window(buf.data(), o, S3, code, as_float);
-                    else convert_window(buf.data(), o, S3, code, [](uint16_t u) { return u ? 1.f : 0.f; });   // dtype=bool -> float32
+                    else convert_window(buf.data(), o, S3, code, as_clear);
                 }
             }
             if (rc) {
@@ -243,6 +250,13 @@ int hrn_io_collate_a(int n_sets, const char* const* lr_paths, const int* n_views
     for (auto& th : pool) th.join();
     if (status.load() != 0) { set_err("%s", first_error.c_str()); return status.load(); }
     return 0;
+}
+
+int hrn_io_collate_a(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,
+                     const char* const* sm_paths, int min_L, int lr_size, int patch, int scale, const int* px, const int* py,
+                     float* lrs, float* alphas, float* hrs, float* maps, int n_threads, const int* codes) {
+    return hrn_io_collate_m(n_sets, lr_paths, n_views, hr_paths, sm_paths, min_L, lr_size, patch, scale, px, py, lrs, alphas, hrs, maps, n_threads,
+                            codes, nullptr, nullptr);
 }
 
 int hrn_io_collate_s(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,

@@ -25,6 +25,8 @@ SIGNATURES = {
                                     _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int]),
     "hrn_io_collate_a": (_c.c_int, [_c.c_int, _pp, _ip, _pp, _pp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _ip, _ip,
                                     _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _ip]),
+    "hrn_io_collate_m": (_c.c_int, [_c.c_int, _pp, _ip, _pp, _pp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _ip, _ip,
+                                    _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _ip, _pp, _c.c_void_p]),
     "hrn_io_read_many_u16": (_c.c_int, [_c.c_int, _pp, _c.c_void_p, _c.POINTER(_c.c_int64), _ip, _ip, _c.c_int]),
 }
 _lib = None
@@ -75,14 +77,18 @@ def _strs(paths):
     return arr
 
 
-def collate(lr_paths_per_set, hr_paths, sm_paths, min_L, lr_size, patch=0, corners=None, out=None, n_threads=0, scale=3, codes=None):
+def collate(lr_paths_per_set, hr_paths, sm_paths, min_L, lr_size, patch=0, corners=None, out=None, n_threads=0, scale=3, codes=None,
+            qm_paths_per_set=None):
     """lr_paths_per_set: list (one per imageset) of lists of LR files in use order; hr_paths: list of paths / None entries
     or None; sm_paths: list of paths; corners: list of (x, y) = (row, column) per imageset when patch > 0.
     out: optional dict of preallocated float32 buffers 'lrs' (B,min_L,S,S), 'alphas' (B,min_L), 'hrs', 'maps' (B,kS,kS) -
     numpy arrays or CPU torch tensors (e.g. pinned).  Returns that dict (numpy arrays when it allocates).
     scale: k, the HR / LR ratio of the files (2, 3 or 4); a file of another size is an HrnetIoError that names it.
     codes: None, or one augmentation code per imageset (hrnet_hip/augment.py), applied to every cropped window of that imageset
-    while it is converted; a code outside 0..7 is an HrnetIoError (-2) and leaves the buffers as they were."""
+    while it is converted; a code outside 0..7 is an HrnetIoError (-2) and leaves the buffers as they were.
+    qm_paths_per_set: None, or the quality-mask file of every entry of lr_paths_per_set (same nesting and order); the masks of the
+    used views then land in out['lr_masks'] (B,min_L,S,S), 1.0 where the stored sample is non-zero, through the same window and
+    code as the views; a mask file that is missing or not lr_size a side is an HrnetIoError that names it."""
     scale = check_scale(scale)
     lib = load_library()
     B = len(lr_paths_per_set)
@@ -92,6 +98,8 @@ def collate(lr_paths_per_set, hr_paths, sm_paths, min_L, lr_size, patch=0, corne
     if out is None:
         out = dict(lrs=np.empty((B, min_L, S, S), np.float32), alphas=np.empty((B, min_L), np.float32),
                    hrs=np.empty((B, T, T), np.float32) if have_hr else None, maps=np.empty((B, T, T), np.float32))
+        if qm_paths_per_set is not None:
+            out["lr_masks"] = np.empty((B, min_L, S, S), np.float32)
 
     def ptr(t, shape):
         if t is None:
@@ -116,10 +124,18 @@ def collate(lr_paths_per_set, hr_paths, sm_paths, min_L, lr_size, patch=0, corne
         if len(codes) != B:
             raise ValueError(f"codes has {len(codes)} entries for {B} imagesets")
         codes = (_c.c_int * B)(*[int(c) for c in codes])
-    _check(lib.hrn_io_collate_a(B, _strs(flat), nv, _strs(hr_paths) if have_hr else None, _strs(sm_paths), int(min_L), int(lr_size),
-                                int(patch), scale, px, py, ptr(out["lrs"], (B, min_L, S, S)), ptr(out["alphas"], (B, min_L)),
-                                ptr(out.get("hrs") if have_hr else None, (B, T, T)), ptr(out["maps"], (B, T, T)), int(n_threads), codes),
-           "hrn_io_collate_a")
+    args = (B, _strs(flat), nv, _strs(hr_paths) if have_hr else None, _strs(sm_paths), int(min_L), int(lr_size), int(patch), scale, px, py,
+            ptr(out["lrs"], (B, min_L, S, S)), ptr(out["alphas"], (B, min_L)), ptr(out.get("hrs") if have_hr else None, (B, T, T)),
+            ptr(out["maps"], (B, T, T)), int(n_threads), codes)
+    if qm_paths_per_set is None:
+        _check(lib.hrn_io_collate_a(*args), "hrn_io_collate_a")
+    else:
+        if [len(q) for q in qm_paths_per_set] != [len(v) for v in lr_paths_per_set]:
+            raise ValueError("qm_paths_per_set must name one mask file per LR file")
+        if out.get("lr_masks") is None:
+            raise ValueError("out has no 'lr_masks' buffer for the masks of qm_paths_per_set")
+        _check(lib.hrn_io_collate_m(*args, _strs([q for masks in qm_paths_per_set for q in masks]), ptr(out["lr_masks"], (B, min_L, S, S))),
+               "hrn_io_collate_m")
     return out
 
 

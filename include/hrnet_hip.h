@@ -28,7 +28,8 @@
  *                              imagesets decoded once into HBM (DataLoader.DeviceImagesetCache); hrn_collate_device_s
  *                              is the same for x2 / x3 / x4 targets
  *   hrn_collate_device_a   <-  (no counterpart: the reference trains without augmentation) the same gather with one of the
- *                              eight flips / rotations of the square applied per sample
+ *                              eight flips / rotations of the square applied per sample; hrn_collate_device_m also gathers the
+ *                              LR quality masks (QM*.png) of the views it picks
  *   hrn_resample_targets   <-  (no counterpart) HR / SM stored at one ratio resampled to another when the cache is built
  *   hrn_dihedral_expand / hrn_dihedral_mean  <-  (no counterpart: the reference predicts from one orientation) the two ends of a
  *                              flip / rotate self-ensemble at inference: the K transformed copies of the view stack, and the mean
@@ -413,6 +414,18 @@ int hrn_collate_device_s(const uint16_t* lr_arena, int64_t lr_elems, const uint1
 int hrn_collate_device_a(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems,
                          const uint8_t* sm_arena, int64_t sm_elems, const int64_t* plan, int B, int min_L, int S, int scale,
                          float* lrs, float* alphas, float* hrs, float* maps, const int32_t* codes, void* stream);
+/* The same with the LR quality masks (the QM*.png of the PROBA-V imagesets; the reference never reads them into a batch, they
+ * are the `lr_masks` of hrn_mncc_*).  qm_arena: uint8, one byte per LR sample, 1 clear / 0 not (any non-zero byte counts as
+ * clear), laid out with exactly the LR arena's element offsets - the mask of the view at LR offset o is at QM offset o - so
+ * qm_elems must equal lr_elems and the plan row does not change; 4-byte aligned.  lr_masks: out (B, min_L, S, S) f32, 1.0 / 0.0:
+ * slot v of sample b is the window of lrs[b][v] cut from that view's mask and put through the sample's code; a padding slot is
+ * zeros, a bad plan row or a bad code makes it NaN like the LR plane beside it.  qm_arena and lr_masks are both NULL (then this is
+ * hrn_collate_device_a, qm_elems ignored) or both given; anything else, or qm_elems != lr_elems: -2 before any launch.  Still
+ * one launch for all five outputs. */
+int hrn_collate_device_m(const uint16_t* lr_arena, int64_t lr_elems, const uint16_t* hr_arena, int64_t hr_elems,
+                         const uint8_t* sm_arena, int64_t sm_elems, const uint8_t* qm_arena, int64_t qm_elems, const int64_t* plan,
+                         int B, int min_L, int S, int scale, float* lrs, float* alphas, float* hrs, float* maps, float* lr_masks,
+                         const int32_t* codes, void* stream);
 
 /* ------------------------------------------------------------------ flip / rotate self-ensemble at inference
  * Nothing in the reference stands behind these two: its predict.py runs one orientation.  highres-net_amd/hrnet_hip/augment.py states

@@ -65,6 +65,15 @@ int hrn_io_collate_s(int n_sets, const char* const* lr_paths, const int* n_views
 int hrn_io_collate_a(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,
                      const char* const* sm_paths, int min_L, int lr_size, int patch, int scale, const int* px, const int* py,
                      float* lrs, float* alphas, float* hrs, float* maps, int n_threads, const int* codes);
+/* The same with the LR quality masks (QM*.png, one per LR view; the reference lists them for the view ids and never decodes one).
+ * qm_paths: the mask file of every entry of lr_paths, same layout and order; lr_masks: out (n_sets, min_L, S, S) f32.  The mask
+ * of each used view is decoded on the same pool, cropped with the LR window and put through the imageset's code while it is
+ * converted (any non-zero sample -> 1.0, as the status map); unused slots are zeros.  A mask file that is not lr_size a side is a
+ * -4 error that names it.  Both NULL: this is hrn_io_collate_a.  One of the two NULL: -2, no buffer touched. */
+int hrn_io_collate_m(int n_sets, const char* const* lr_paths, const int* n_views, const char* const* hr_paths,
+                     const char* const* sm_paths, int min_L, int lr_size, int patch, int scale, const int* px, const int* py,
+                     float* lrs, float* alphas, float* hrs, float* maps, int n_threads, const int* codes,
+                     const char* const* qm_paths, float* lr_masks);
 
 /* Decode n PNGs (8- or 16-bit grayscale, as hrn_io_png_read_u16) into one caller-owned uint16 arena: image i goes to
  * out[offsets[i] .. offsets[i] + expect_w[i] * expect_h[i]) as rows of expect_w[i] samples; its size must match the file.

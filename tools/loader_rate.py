@@ -1,7 +1,8 @@
 """Input-pipeline rate: the host path (ImagesetDataset.load_batch, BatchPrefetcher) against the HBM-resident cache
 (DeviceImagesetCache, one hrn_collate_device launch per batch) on synthetic imagesets in the PROBA-V layout.
 
-    python tools/loader_rate.py [--sets 64] [--threads 16] [--json out.json] [--no-prof] [--augment flip|dihedral]
+    python tools/loader_rate.py [--sets 64] [--threads 16] [--json out.json] [--no-prof] [--augment flip|dihedral] [--lr-masks]
+                                [--full-frames] [--kernel-only]
 
 Writes the imagesets to a temporary directory (the stdlib zlib PNG writer of tests/imageset_png.py; smooth 16-bit fields plus
 noise, 19-35 views of 128x128, HR / SM 384x384), then per shape (B / top_k / min_L / patch):
@@ -13,6 +14,9 @@ noise, 19-35 views of 128x128, HR / SM 384x384), then per shape (B / top_k / min
     (first shape) with a consumer that spends one training step (26.2 / 55 ms) per batch, of cache.load_batch and cache.batches,
   - the kernel time of hrn_collate_device from `rocprofv3 --kernel-trace --stats` (a child process of this script).
 `--augment MODE` measures the same with flip / rotate augmentation on (one code per imageset, hrnet_hip/augment.py), on both paths.
+`--lr-masks` measures the same with the LR quality masks on (ImagesetDataset(lr_masks=True): one more PNG decode per view on the host
+path, a fourth arena and hrn_collate_device_m in the cache), on both paths.  `--full-frames` loads whole 128 x 128 views instead of
+patches; `--kernel-only` skips the rates and runs the rocprofv3 child alone.
 Needs a ROCm device; prints one JSON object."""
 import argparse
 import csv
@@ -34,6 +38,8 @@ SHAPES = [dict(B=32, top_k=32, min_L=32, patch=64), dict(B=8, top_k=8, min_L=2, 
 STEPS_MS = (26.2, 55.0)            # README: the training step at SHAPES[0] with HRNet + ShiftNet in bf16, and with HRNet in bf16x3
 MIN_WINDOW_S = 1.5
 AUGMENT = None                     # --augment: the datasets' augmentation mode
+LR_MASKS = False                   # --lr-masks: the datasets carry the LR quality masks
+FULL_FRAMES = False                # --full-frames: no patches
 
 
 def smooth_field(rng, n, waves=6):
@@ -72,7 +78,8 @@ def batch_lists(n_sets, B, n_batches, seed):
 
 def dataset(dirs, shape):
     import DataLoader as DL
-    return DL.ImagesetDataset(dirs, {"create_patches": True, "patch_size": shape["patch"]}, top_k=shape["top_k"], beta=50.0, augment=AUGMENT)
+    return DL.ImagesetDataset(dirs, {"create_patches": not FULL_FRAMES, "patch_size": shape["patch"]}, top_k=shape["top_k"], beta=50.0,
+                              augment=AUGMENT, lr_masks=LR_MASKS)
 
 
 def rate(n, seconds):
@@ -121,7 +128,7 @@ def measure(dirs, shape, threads, repeats, steps_ms):
     import torch
     from hrnet_hip import io_binding
     ds = dataset(dirs, shape)
-    B, min_L, P = shape["B"], shape["min_L"], shape["patch"]
+    B, min_L, P = shape["B"], shape["min_L"], 128 if FULL_FRAMES else shape["patch"]
     out = dict(shape)
     seeds = iter(range(1000))
     batches = lambda n: batch_lists(len(dirs), B, n, next(seeds))
@@ -133,6 +140,8 @@ def measure(dirs, shape, threads, repeats, steps_ms):
     # host path, planning and decoding apart
     buf = dict(lrs=np.empty((B, min_L, P, P), np.float32), alphas=np.empty((B, min_L), np.float32),
                hrs=np.empty((B, 3 * P, 3 * P), np.float32), maps=np.empty((B, 3 * P, 3 * P), np.float32))
+    if LR_MASKS:
+        buf["lr_masks"] = np.empty((B, min_L, P, P), np.float32)
     plan_ms, dec_ms = [], []
     for _ in range(repeats):
         t_plan = t_dec = 0.0
@@ -141,8 +150,9 @@ def measure(dirs, shape, threads, repeats, steps_ms):
             plans = [ds._plan(ds.imset_dir[i]) for i in idx]
             t1 = time.perf_counter()
             io_binding.collate([p["lr_paths"] for p in plans], [p["hr"] for p in plans], [p["sm"] for p in plans], min_L=min_L,
-                               lr_size=plans[0]["lr_side"], patch=P, corners=[p["corner"] for p in plans], out=buf, n_threads=threads,
-                               codes=[p["code"] for p in plans] if AUGMENT else None)
+                               lr_size=plans[0]["lr_side"], patch=0 if FULL_FRAMES else P, corners=[p["corner"] for p in plans], out=buf,
+                               n_threads=threads, codes=[p["code"] for p in plans] if AUGMENT else None,
+                               qm_paths_per_set=[p["qm_paths"] for p in plans] if LR_MASKS else None)
             t_dec += time.perf_counter() - t1
             t_plan += t1 - t0
         plan_ms.append(1e3 * t_plan / n)
@@ -182,7 +192,7 @@ def measure(dirs, shape, threads, repeats, steps_ms):
     out["cache_batches"] = spread([through_batches(batches(n)) for _ in range(repeats)])
     # the planner alone (Python, RNG, plan table): what the device path costs the host per batch
     out["cache_plan"] = spread([ms_per_call(lambda idx: cache.index.plan(idx, min_L), batches(n)) for _ in range(repeats)])
-    out["output_bytes_per_batch"] = 4 * B * (min_L * P * P + min_L + 2 * 9 * P * P)
+    out["output_bytes_per_batch"] = 4 * B * ((2 if LR_MASKS else 1) * min_L * P * P + min_L + 2 * 9 * P * P)
     return out
 
 
@@ -204,7 +214,8 @@ def kernel_stats(data_dir, threads, n_batches):
         with tempfile.TemporaryDirectory() as prof:
             cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", prof, "-o", "lr", "--",
                    sys.executable, os.path.abspath(__file__), "--child", data_dir, "--threads", str(threads), "--shape", str(k),
-                   "--batches", str(n_batches)] + (["--augment", AUGMENT] if AUGMENT else [])
+                   "--batches", str(n_batches)] + (["--augment", AUGMENT] if AUGMENT else []) + (["--lr-masks"] if LR_MASKS else []) + (
+                       ["--full-frames"] if FULL_FRAMES else [])
             r = subprocess.run(cmd, cwd=prof, capture_output=True, text=True, timeout=600)
             if r.returncode != 0:
                 raise RuntimeError(f"rocprofv3 run failed ({r.returncode}): {r.stderr[-2000:]}")
@@ -212,7 +223,7 @@ def kernel_stats(data_dir, threads, n_batches):
             if not files:
                 raise RuntimeError("rocprofv3 wrote no kernel_stats.csv")
             for row in csv.DictReader(open(files[0])):
-                if "collate_kernel" in row["Name"]:
+                if "collate_kernel" in row["Name"] or "collate_mask_kernel" in row["Name"]:
                     res[f"B{shape['B']}_minL{shape['min_L']}"] = dict(name=row["Name"], calls=int(row["Calls"]),
                                                                      avg_us=round(float(row["AverageNs"]) / 1e3, 2),
                                                                      min_us=round(float(row["MinNs"]) / 1e3, 2),
@@ -220,7 +231,8 @@ def kernel_stats(data_dir, threads, n_batches):
     return res
 
 
-PARSER = _common.parser(__doc__, sets=64, threads=16, json=None, no_prof=False, batches=200, repeats=5)
+PARSER = _common.parser(__doc__, sets=64, threads=16, json=None, no_prof=False, batches=200, repeats=5, lr_masks=False, full_frames=False,
+                        kernel_only=False)
 PARSER.add_argument("--augment", default=None, choices=["flip", "dihedral"])
 PARSER.add_argument("--child", default=None, help=argparse.SUPPRESS)                   # kernel_stats' child under rocprofv3: the data directory
 PARSER.add_argument("--shape", type=int, default=None, help=argparse.SUPPRESS)         # ... and which of SHAPES it runs
@@ -228,8 +240,8 @@ PARSER.add_argument("--shape", type=int, default=None, help=argparse.SUPPRESS)  
 
 def main():
     a = PARSER.parse_args()
-    global AUGMENT
-    AUGMENT = a.augment
+    global AUGMENT, LR_MASKS, FULL_FRAMES
+    AUGMENT, LR_MASKS, FULL_FRAMES = a.augment, a.lr_masks, a.full_frames
     _common.require_gpu("loader_rate")
     if a.child:
         dirs = sorted(glob.glob(os.path.join(a.child, "imgset*")))
@@ -244,11 +256,12 @@ def main():
         t0 = time.perf_counter()
         dirs = write_imagesets(root, a.sets)
         lr_png = [os.path.getsize(p) for p in glob.glob(os.path.join(root, "*", "LR*.png"))]
-        res = dict(sets=a.sets, threads=a.threads, augment=a.augment, synthetic_pngs=True, write_s=round(time.perf_counter() - t0, 1),
+        res = dict(sets=a.sets, threads=a.threads, augment=a.augment, lr_masks=a.lr_masks, full_frames=a.full_frames, synthetic_pngs=True, write_s=round(time.perf_counter() - t0, 1),
                    lr_views=len(lr_png), lr_png_kb=round(np.mean(lr_png) / 1024, 1),
                    hr_png_kb=round(np.mean([os.path.getsize(os.path.join(d, "HR.png")) for d in dirs]) / 1024, 1),
                    repeats=a.repeats, min_window_s=MIN_WINDOW_S,
-                   shapes=[measure(dirs, s, a.threads, a.repeats, STEPS_MS if k == 0 else ()) for k, s in enumerate(SHAPES)])
+                   shapes=[] if a.kernel_only else [measure(dirs, s, a.threads, a.repeats, STEPS_MS if k == 0 else ())
+                                                    for k, s in enumerate(SHAPES)])
         if not a.no_prof:
             res["collate_kernel"] = kernel_stats(root, a.threads, a.batches)
     print(json.dumps(res))
