@@ -2,13 +2,16 @@
 exact values a kernel reads, what the kernel computes, and returns with it T = the same expression on absolute values.
 tests/test_gpu_kernels_bwd.py and tests/test_gpu_kernels_shiftnet.py hold the kernels to them on the GPU; tests/test_kernels_bwd_host.py
 and tests/test_kernels_shiftnet_host.py check the references themselves against torch autograd / torch.optim.Adam on the CPU, on the same
-inputs and constants, which is why those live here too."""
+inputs and constants, which is why those live here too.  The fp32 forward kernels' section serves tests/test_gpu_kernels_fwd.py (GPU)
+and tests/test_kernels_fwd_f32_host.py (CPU) in the same way: the instances, the two operand sets, the references and the negative
+controls of conv3x3_kernel<F32>, stem_kernel<F32> and decoder_kernel<F32, false, S>."""
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 from kt import BF16, BF16X3, F32                        # noqa: F401
-from kernel_bounds import BF, C, _nchw, rnd             # noqa: F401  (the host tests reach the conventions through this module)
+from kernel_bounds import BF, C, C_F32, SHAPES, _full32, _grid, _nchw, _pair_gather, _tiles, rnd, round_sig, sig_bits    # noqa: F401
+# (the host tests reach the conventions through this module)
 
 # ----------------------------------------------------------------------------------------------------------- HRNet's backward
 def ref_prelu_bwd(dy, src, a, zero_is_positive=False, no_inv=False):
@@ -221,6 +224,229 @@ def _alphas(B, V, zero_at=None):
     if zero_at is not None:
         al[B - 1, zero_at] = 0.0
     return al
+
+
+# ----------------------------------------------------------------------------------------------------------- the fp32 forward kernels
+# tests/test_gpu_kernels_fwd.py holds conv3x3_kernel<F32>, stem_kernel<F32> and decoder_kernel<F32, false, S> to these on the GPU;
+# tests/test_kernels_fwd_f32_host.py checks on the CPU, with the same seeds, that the `full` operands carry more than 16 significant
+# bits, that a float32 evaluation stays inside the bound and that every asserted negative control is further from the right reference
+# than the bound can hide.
+# instance: (dt, route, cin, cout, res_mode, in_pair, slot output); F32 reaches conv3x3_kernel<F32, cin, cout> on route 0 and on route 1
+F32_INSTANCES = {
+    "f32enc": (F32, 0, 64, 64, 0, False, False),
+    "f32encres": (F32, 0, 64, 64, 1, False, False),
+    "f32pairin": (F32, 0, 128, 128, 0, True, False),
+    "f32pairres": (F32, 0, 128, 128, 2, False, False),
+    "f32alpha": (F32, 0, 128, 64, 3, False, "stack"),
+    "f32alphalast": (F32, 0, 128, 64, 3, False, "fused"),
+    "f32slot": (F32, 0, 128, 64, 0, False, "stack"),
+    "f32slotlast": (F32, 0, 128, 64, 0, False, "fused"),
+}
+# slope classes: None (no PReLU), 0 <= a <= 1, 0, 1, a < 0, a > 1; the `full` set's are general fp32 values of the same classes
+SLOPES = [None, 0.25, 0.0, 1.0, BF(-0.3), 1.5]
+_F = lambda v: float(np.float32(v))
+SLOPES_FULL = [None, _F(0.3), 0.0, 1.0, _F(-0.3), _F(1.7)]
+ALPHA_FULL = _F(0.7)
+
+
+def f32_slope(a, opset):
+    """the slope an fp32 case runs with: the `full` set's value of the class of `a`"""
+    return SLOPES_FULL[SLOPES.index(a)] if opset == "full" else a
+
+
+def f32_opset(ii, si):
+    """the operand set of fp32 instance number ii at shape number si: `full` at every odd shape (15x33 and multi among them) and where
+    (ii + si) % 3 == 0, `exact` (bf16-representable values stored as f32: every product exact) at the other even shapes"""
+    return "full" if si % 2 == 1 or (ii + si) % 3 == 0 else "exact"
+
+
+def conv_geometry(inst, shape):
+    """-> dict B, V, n, half, pair_last, per, M, uses_stack of instance tuple `inst` at `shape` (a key of SHAPES).  A level of n views
+    (pair_last = n - 2 for odd n) inside a stack of V > n slots; "multi" (needs the GPU's CU count): a workgroup walks two tiles at least"""
+    dt, route, cin, cout, res_mode, in_pair, slot = inst
+    H, W = SHAPES[shape]
+    uses_stack = bool(in_pair or res_mode in (2, 3) or slot)
+    n = 3 if slot == "fused" else 5
+    V = n + 2
+    half, pair_last = n // 2, n - (n & 1) - 1
+    per = half if uses_stack else 1
+    tiles = _tiles(dt, route, cin, cout, H, W)
+    if shape == "multi":
+        B = 1
+        while (B * per * tiles) < 2 * _grid(route, cout, B * per * tiles, dt):
+            B += 1
+        B += 1
+    else:
+        B = 2 if shape != "1x1" or uses_stack else 1
+    M = B * per
+    if shape == "multi":
+        assert M * tiles >= 2 * _grid(route, cout, M * tiles, dt), (M * tiles, _grid(route, cout, M * tiles, dt))
+    return dict(B=B, V=V, n=n, half=half, pair_last=pair_last, per=per, M=M, uses_stack=uses_stack, H=H, W=W)
+
+
+def f32_values(shape, seed, scale, opset):
+    """fp32 CPU values of operand set `exact` (bf16-representable) or `full` (general fp32)"""
+    v = _full32(shape, seed, scale)
+    return v.to(torch.bfloat16).float() if opset == "exact" else v
+
+
+def f32_conv_operands(inst, geo, seed, opset):
+    """the fp32 CPU operands of an F32 conv case: w (cout, cin, 3, 3), bias, and whichever of stack (B, V, H, W, 64), inp (M, H, W, cin),
+    res (M, H, W, cout: res_mode 1, in place) the instance reads.  No operand holds a zero (an alpha = 0 slot is compared bit for bit with
+    its residual, and -0.0 + 0 v is +0.0)."""
+    _, _, cin, cout, res_mode, in_pair, slot = inst
+    H, W = geo["H"], geo["W"]
+    g = torch.Generator().manual_seed(seed)
+    w = torch.randn((cout, cin, 3, 3), generator=g) * (0.05 if cin == 64 else 0.035)
+    bias = torch.randn(cout, generator=g) * 0.1
+    if opset == "exact":
+        w, bias = w.to(torch.bfloat16).float(), bias.to(torch.bfloat16).float()
+    ops = dict(w=w, bias=bias, stack=None, inp=None, res=None)
+    if geo["uses_stack"]:
+        ops["stack"] = f32_values((geo["B"], geo["V"], H, W, 64), seed + 1, 1.0, opset)
+    if not in_pair:
+        ops["inp"] = f32_values((geo["M"], H, W, cin), seed + 2, 1.0, opset)
+    if res_mode == 1:
+        ops["res"] = f32_values((geo["M"], H, W, cout), seed + 3, 1.0, opset)
+    for t in ops.values():
+        assert t is None or not bool((t == 0).any())
+    return ops
+
+
+def conv_alphas(B, V, opset="exact"):
+    """alphas [B][V]: 0, 1, 0.75 (`full`: fp32(0.7)) mixed in the batch (the partner of slot i is pair_last - i)"""
+    al = torch.tensor([[ALPHA_PATTERN[(b + j) % 7] for j in range(V)] for b in range(B)], dtype=torch.float32)
+    return torch.where(al == 0.75, torch.full_like(al, ALPHA_FULL), al) if opset == "full" else al
+
+
+def ref_prelu_fwd(x, T, a):
+    if a is None:
+        return x, T
+    return torch.where(x >= 0, x, a * x), (None if T is None else T * max(1.0, abs(a)))
+
+
+def ref_conv_epi(x, w, b, slope, res_mode, res=None, stack=None, geo=None, alph=None, own_alpha=False, swap_halves=False, with_T=True):
+    """One conv3x3 layer with the epilogue of ConvParams, in the dtype of its arguments (fp64: the reference; fp32: a plain CPU evaluation):
+    x (M, H, W, cin), w (cout, cin, 3, 3), b; PReLU `slope` (None: none); res_mode 1: + res (M, H, W, cout); 2: + the pair gather of
+    stack[:, :n]; 3: stack slot i + alpha[partner(i)] conv (alph None: 1).  -> (M, cout, H, W) and T, the same on absolute values.
+    The wrong references of the negative controls: own_alpha (the view's own alpha), swap_halves (res_mode 2's 64-channel halves exchanged)."""
+    z = _nchw(x)
+    y = F.conv2d(z, w, b, padding=1)
+    T = F.conv2d(z.abs(), w.abs(), b.abs(), padding=1) if with_T else None
+    y, T = ref_prelu_fwd(y, T, slope)
+    add = lambda T, t: T + t if with_T else None
+    if res_mode == 1:
+        y, T = y + _nchw(res), add(T, _nchw(res).abs())
+    elif res_mode == 2:
+        st = stack[:, :geo["n"]]
+        zz = _pair_gather(st, geo["half"], geo["pair_last"])
+        if swap_halves:
+            zz = torch.cat([zz[..., 64:], zz[..., :64]], -1)
+        y, T = y + _nchw(zz), add(T, _nchw(zz).abs())
+    elif res_mode == 3:
+        half, M = geo["half"], x.shape[0]
+        r = _nchw(stack[:, :half].reshape((M,) + tuple(stack.shape[2:])))
+        if alph is None:
+            al = torch.ones(M, dtype=y.dtype)
+        else:
+            i = torch.arange(half)
+            al = (alph[:, i] if own_alpha else alph[:, geo["pair_last"] - i]).reshape(M).to(y.dtype)
+        al = al[:, None, None, None]
+        y, T = r + al * y, (r.abs() + al.abs() * T if with_T else None)
+    return y, T
+
+
+def f32_stem_operands(mode, M, H, W, seed):
+    """general fp32 operands of the fp32 stem (unlike the bf16 modes' k / 2^16 they are no 16-bit values): mode `f32` as encoder_impl calls
+    it - x0 (M, H, W), x1 (ceil(M / 3), H, W), rep1 = 3, no `sub`; `f32sub` as ShiftNet's eval pass - one tensor x (M, 2, H, W) whose
+    plane 0 / 1 are in0 / in1 (image stride 2 H W, rep1 = 1) and sub (M, 2) = the plane means.  w (64, 2, 3, 3), bias (64) general fp32."""
+    g = torch.Generator().manual_seed(seed)
+    if mode == "f32sub":
+        x = torch.rand((M, 2, H, W), generator=g) + 0.25 * torch.randn((M, 2, 1, 1), generator=g)
+        x0, x1, rep1 = x[:, 0], x[:, 1], 1
+        sub = x.double().mean((2, 3)).float()
+    else:
+        rep1 = 3
+        x, sub = None, None
+        x0, x1 = torch.rand((M, H, W), generator=g), torch.rand((-(-M // rep1), H, W), generator=g)
+    w = torch.randn((64, 2, 3, 3), generator=g) * 0.3
+    bias = torch.randn(64, generator=g) * 0.1
+    return dict(x=x, x0=x0, x1=x1, rep1=rep1, sub=sub, w=w, bias=bias)
+
+
+def ref_stem_fwd(x0, x1, rep1, sub, w, b, slope, m0, m1, with_T=True):
+    """images m0..m1 of the stem: PReLU(conv2d(cat(x0[m] - sub[m, 0], x1[m // rep1] - sub[m, 1]), pad 1) + b) (M, 64, H, W), and T"""
+    z = _stem_input(x0, x1, rep1, sub, m0, m1)
+    y = F.conv2d(z, w, b, padding=1)
+    T = F.conv2d(z.abs(), w.abs(), b.abs(), padding=1) if with_T else None
+    return ref_prelu_fwd(y, T, slope)
+
+
+def f32_decoder_operands(N, H, W, S, seed):
+    """general fp32 operands of the fp32 decoder: fused (N, H, W, 64), wd (64, 64, S, S), bd (64), wf (64), bf (1)"""
+    g = torch.Generator().manual_seed(seed)
+    return dict(fused=torch.randn((N, H, W, 64), generator=g), wd=torch.randn((64, 64, S, S), generator=g) * 0.05,
+                bd=torch.randn(64, generator=g) * 0.1, wf=torch.randn(64, generator=g) * 0.2, bf=torch.randn(1, generator=g) * 0.1)
+
+
+def ref_decoder_fwd(fused, wd, bd, slope, wf, bf, S, with_T=True):
+    """sr (N, S H, S W) = conv1x1(PReLU(conv_transpose(fused, wd, stride S) + bd), wf) + bf, and T"""
+    z = _nchw(fused)
+    y = F.conv_transpose2d(z, wd, bd, stride=S)
+    T = F.conv_transpose2d(z.abs(), wd.abs(), bd.abs(), stride=S) if with_T else None
+    y, T = ref_prelu_fwd(y, T, slope)
+    want = F.conv2d(y, wf.view(1, 64, 1, 1), bf)[:, 0]
+    T = F.conv2d(T, wf.abs().view(1, 64, 1, 1), bf.abs())[:, 0] if with_T else None
+    return want, T
+
+
+# the fp32 negative controls, at 15x33 on the `full` operand set (the decoder, whose shape table has no 15x33, at 17x50 and S = 3).
+# (control, target): target an F32 conv instance, "stem" or "decoder".
+# Structural: tap_swap (two taps of one (co, ci) pair exchanged), own_alpha, swap_halves (res_mode 2's halves), swap_in (the pair-gather
+# INPUT's 64-channel halves exchanged: the chunk -> src0 / src1 selection).  Operand rounding, of the activations (x) or the weights (w),
+# to 8 (bf16), 11 (10 mantissa bits) or 16 significant bits (the bf16x3 class).
+F32_CONTROL_SHAPE, F32_CONTROL_SEED, F32_CONTROL_SLOPE = "15x33", 321, 0.25
+F32_CONTROL_DECODER = ("17x50", 3)            # (shape, S)
+_CONV_ROUND = ("f32enc", "f32pairin", "f32slot")
+F32_CONTROLS = ([("tap_swap", "f32encres"), ("tap_swap", "f32pairres"), ("own_alpha", "f32alpha"), ("swap_halves", "f32pairres"),
+                 ("swap_in", "f32pairin")] +
+                [(f"round{b}_{o}", n) for b in (8, 11) for o in ("x", "w") for n in _CONV_ROUND] +
+                [("round16_x", "stem"), ("round8_x", "decoder")])
+# Controls whose wrong reference is closer than twice the bound to the right one under C_F32, asserted nowhere (the host test prints their
+# separation and fails if one of them clears 2): one operand of a convolution rounded to 16 significant bits moves the worst element by
+# 1.2 (f32enc x), 1.1 (f32enc w), 0.73 .. 0.76 (f32pairin, f32slot) times C_F32 T, and the kernels themselves need up to 0.2 C_F32 T.
+F32_CONTROLS_UNASSERTED = [(f"round16_{o}", n) for o in ("x", "w") for n in _CONV_ROUND]
+
+
+def f32_control_reference(control, case):
+    """the wrong reference of `control` (None: the right one): case = dict(kind "conv" / "stem" / "decoder", args: the keyword arguments
+    of its ref_* function in fp64) -> (value, T)"""
+    a = dict(case["args"])
+    fn = {"conv": ref_conv_epi, "stem": ref_stem_fwd, "decoder": ref_decoder_fwd}[case["kind"]]
+    xkey = {"conv": "x", "stem": None, "decoder": "fused"}[case["kind"]]
+    wkey = {"conv": "w", "stem": "w", "decoder": "wd"}[case["kind"]]
+    if control is None:
+        pass
+    elif control == "tap_swap":
+        w = a["w"].clone()
+        w[5, 7, 0, 0], w[5, 7, 2, 2] = a["w"][5, 7, 2, 2], a["w"][5, 7, 0, 0]
+        assert w[5, 7, 0, 0] != w[5, 7, 2, 2]
+        a["w"] = w
+    elif control == "own_alpha":
+        a["own_alpha"] = True
+    elif control == "swap_halves":
+        a["swap_halves"] = True
+    elif control == "swap_in":
+        a["x"] = torch.cat([a["x"][..., 64:], a["x"][..., :64]], -1)
+    else:
+        bits, which = int(control[5:control.index("_")]), control[-1]
+        if which == "w":
+            a[wkey] = round_sig(a[wkey], bits)
+        elif case["kind"] == "stem":
+            a["x0"], a["x1"] = round_sig(a["x0"], bits), round_sig(a["x1"], bits)
+        else:
+            a[xkey] = round_sig(a[xkey], bits)
+    return fn(**a)
 
 
 # ----------------------------------------------------------------------------------------------------------- ShiftNet and Adam

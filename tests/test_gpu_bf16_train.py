@@ -14,7 +14,7 @@ import torch.nn.functional as F
 
 from oracle import synth
 import util
-from kernel_bounds import _bf, _f32, _nchw, _pair_gather, _x3
+from kernel_bounds import _bf, _f32, _full32, _nchw, _pair_gather, _x3
 from kt import BF16, BF16X3, F32, _cus, _p, _stream, lib as _lib
 from util import NONPOS, _SLOPE_KEYS, _fresh_model, _model, _oracle as _oracle_in, _oracle_grads
 
@@ -49,10 +49,19 @@ def test_bf16_training_op_runs_at_every_scale(scale):
 
 
 # ----------------------------------------------------------------------------- 2. the bf16 weight gradient
-def _wgrad_case(lib, M, H, W, cin, cout, pair=None, seed=0, dt=BF16):
+def _f32_full(shape, seed, scale=1.0):
+    """an f32 device tensor of general fp32 random values (24 significant bits) and its fp64 CPU copy: a kernel that drops operand bits
+    passes on _f32's bf16-representable values and fails here"""
+    t = _full32(shape, seed, scale)
+    return t.cuda(), t.double()
+
+
+def _wgrad_case(lib, M, H, W, cin, cout, pair=None, seed=0, dt=BF16, full=False):
     """-> (got, want, sum |terms|) for dW of a cin -> cout conv; pair = (B, n): the input is the pair gather of a (B, n) view stack.
-    dt BF16: one bf16 plane per tensor; BF16X3: hi + lo planes of random fp32 values; F32: bf16-representable values stored as f32"""
-    act = {F32: _f32, BF16: _bf, BF16X3: _x3}[dt]
+    dt BF16: one bf16 plane per tensor; BF16X3: hi + lo planes of random fp32 values; F32: bf16-representable values stored as f32, or
+    (full) general fp32 values"""
+    act = _f32_full if full else {F32: _f32, BF16: _bf, BF16X3: _x3}[dt]
+    assert not full or dt == F32
     g, g64 = act((M, H, W, cout), seed + 1)
     if pair:
         B, n = pair
@@ -78,20 +87,22 @@ def _wgrad_case(lib, M, H, W, cin, cout, pair=None, seed=0, dt=BF16):
 _WGRAD_CASES = ["plain64", "plain128x64", "pair", "ragged33", "multi_strip"]
 
 
-@pytest.mark.parametrize("case,dt", [pytest.param(c, BF16, id=c) for c in _WGRAD_CASES] +
-                         [pytest.param(c, BF16X3, id=f"{c}-bf16x3") for c in _WGRAD_CASES] +
-                         [pytest.param(c, F32, id=f"{c}-f32") for c in _WGRAD_CASES])
-def test_bf16_wgrad_vs_fp64(case, dt):
+@pytest.mark.parametrize("case,dt,full", [pytest.param(c, BF16, False, id=c) for c in _WGRAD_CASES] +
+                         [pytest.param(c, BF16X3, False, id=f"{c}-bf16x3") for c in _WGRAD_CASES] +
+                         [pytest.param(c, F32, False, id=f"{c}-f32") for c in _WGRAD_CASES] +
+                         [pytest.param(c, F32, True, id=f"{c}-f32full") for c in ("plain128x64", "pair")])
+def test_bf16_wgrad_vs_fp64(case, dt, full):
     """conv_wgrad_x3_kernel, one-plane (bf16) and two-plane (bf16x3) instance: error <= 1e-5 of sum |terms| per element (bf16 products are
     exact in fp32; bf16x3 drops only the g lo x x lo term, <= 2^-18 of |g x|).  The f32 ids: conv_wgrad_kernel, the exact-fp32 MFMA weight
-    gradient of the fp32 training path (8 x 32 tiles, grid = min(CUs, tiles)), on bf16-representable values stored as f32."""
+    gradient of the fp32 training path (8 x 32 tiles, grid = min(CUs, tiles)), on bf16-representable values stored as f32; the f32full
+    ids: the same kernel on general fp32 x / stack / g with 24 significant bits (the same bound), where dropped operand bits show."""
     lib = _lib()
     if case == "plain64":
         got, want, terms = _wgrad_case(lib, 3, 16, 32, 64, 64, dt=dt)
     elif case == "plain128x64":
-        got, want, terms = _wgrad_case(lib, 2, 12, 40, 128, 64, seed=3, dt=dt)
+        got, want, terms = _wgrad_case(lib, 2, 12, 40, 128, 64, seed=3, dt=dt, full=full)
     elif case == "pair":
-        got, want, terms = _wgrad_case(lib, 2 * 2, 9, 24, 128, 128, pair=(2, 5), seed=5, dt=dt)
+        got, want, terms = _wgrad_case(lib, 2 * 2, 9, 24, 128, 128, pair=(2, 5), seed=5, dt=dt, full=full)
     elif case == "ragged33":
         got, want, terms = _wgrad_case(lib, 2, 7, 33, 64, 128, seed=9, dt=dt)
     else:
@@ -101,7 +112,7 @@ def test_bf16_wgrad_vs_fp64(case, dt):
         assert units >= 2 * grid, (units, grid)
         got, want, terms = _wgrad_case(lib, M, H, W, 64, 64, seed=11, dt=dt)
     err = np.abs(got - want)
-    print(case, dt, "max err / sum|terms|", float((err / np.maximum(terms, 1e-30)).max()))
+    print(case, dt, "full" if full else "", "max err / sum|terms|", float((err / np.maximum(terms, 1e-30)).max()))
     assert (err <= 1e-5 * terms + 1e-30).all()
 
 
@@ -109,18 +120,25 @@ def test_bf16_wgrad_vs_fp64(case, dt):
 _DGRAD_LAYERS = [(64, 64, False), (64, 64, True), (128, 128, False), (128, 128, True), (128, 64, False)]
 
 
-@pytest.mark.parametrize("cin,cout,res,dt", [pytest.param(*l, BF16, id="-".join(map(str, l))) for l in _DGRAD_LAYERS] +
-                         [pytest.param(*l, BF16X3, id="-".join(map(str, l)) + "-bf16x3") for l in _DGRAD_LAYERS] +
-                         [pytest.param(*l, F32, id="-".join(map(str, l)) + "-f32") for l in _DGRAD_LAYERS])
-def test_bf16_dgrad_vs_fp64(cin, cout, res, dt):
+@pytest.mark.parametrize("cin,cout,res,dt,full", [pytest.param(*l, BF16, False, id="-".join(map(str, l))) for l in _DGRAD_LAYERS] +
+                         [pytest.param(*l, BF16X3, False, id="-".join(map(str, l)) + "-bf16x3") for l in _DGRAD_LAYERS] +
+                         [pytest.param(*l, F32, False, id="-".join(map(str, l)) + "-f32") for l in _DGRAD_LAYERS] +
+                         [pytest.param(*l, F32, True, id="-".join(map(str, l)) + "-f32full") for l in ((128, 128, True), (128, 64, False))])
+def test_bf16_dgrad_vs_fp64(cin, cout, res, dt, full):
     """dx = conv3x3(g, W^T flipped) (+ res) for a cin -> cout layer, i.e. a cout -> cin convolution on the bf16 kernels (r64, v6; the
     64 -> 128 and 128 -> 128 + res shapes are the new v6 instances) and on v6x3.  Bound per element: bf16, one bf16 rounding of the
     output (2^-8 of it) plus 1e-5 of sum |terms|; bf16x3 (hi + lo planes of random fp32 g / res, general fp32 weights), 2^-16 of the
     output (the split of the fp32 result) plus 1e-5 of sum |terms|; f32 (the fp32 forward kernel on bf16-representable g / w / res stored
-    as f32), 2^-24 of the output plus 1e-5 of sum |terms|."""
+    as f32), 2^-24 of the output plus 1e-5 of sum |terms|; f32full: the same kernel and bound on general fp32 g / w / res."""
     lib = _lib()
     M, H, W = 3, 13, 37
-    if dt == F32:
+    if full:
+        assert dt == F32
+        g, g64 = _f32_full((M, H, W, cout), 21)
+        w32, w64 = _f32_full((cout, cin, 3, 3), 22, 0.05)
+        r, r64 = _f32_full((M, H, W, cin), 23) if res else (None, None)
+        dx = torch.empty((M, H, W, cin), dtype=torch.float32, device="cuda")
+    elif dt == F32:
         g, g64 = _f32((M, H, W, cout), 21)
         w, w64 = _bf((cout, cin, 3, 3), 22, 0.05)
         w32 = w.float().contiguous()
@@ -158,7 +176,7 @@ def test_bf16_dgrad_vs_fp64(cin, cout, res, dt):
         got = _nchw(dx[0].double().cpu() + dx[1].double().cpu())
         bound = 2.0 ** -16 * want.abs() + 1e-5 * terms + 1e-30
     err = (got - want).abs()
-    print(cin, cout, res, dt, "max err / bound", float((err / bound).max()))
+    print(cin, cout, res, dt, "full" if full else "", "max err / bound", float((err / bound).max()))
     assert bool((err <= bound).all())
 
 

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the bf16 and bf16x3 forward kernels, per element, against torch CPU float64.
+"""GPU (-m gpu): the bf16, bf16x3 and fp32 forward kernels, per element, against torch CPU float64.
 
 Each kernel is launched on its own through the hooks of kernel_test.h, bound by tests/kt.py (hrn_kt_conv3x3_epi with the epilogue encoder_impl / fuse_impl set in ConvParams,
 hrn_kt_stem, hrn_kt_decoder), with operands chosen so that the kernel's products are exact and only the accumulation order and the
@@ -8,12 +8,23 @@ rounding of the stored output remain:
            fp32 and an alpha = 0 slot can be compared bit for bit), weights either bf16-exact (lo = 0: every product exact) or general
            fp32 (the W lo x X hi pass; the dropped lo x lo term is <= 2^-18 of |x w|);
   stem     inputs k / 2^16 (16 significant bits: hi + lo exact), bias of that form, weights bf16 (bf16) or general fp32 (bf16x3).
+  fp32     two operand sets (kernel_refs.f32_opset rotates them over the shapes; every lo offset handed to a hook is 0):
+           exact   bf16-representable values stored as f32: every product exact, only the accumulation order remains;
+           full    activations, view stack, residual, weights, bias, slope and alphas general fp32 with 24 significant bits (slope
+                   fp32(0.3), alphas from {0, 1, fp32(0.7)}), the fp64 reference computed from exactly those values: a kernel that
+                   loses operand bits (a bf16 staging buffer, a reduced-precision matrix instruction, a dropped lo term) passes
+                   `exact` unchanged and fails `full`.  The fp32 stem and decoder run on general fp32 values only.
 Bound per element, T = the same expression evaluated on absolute values (sum |terms| of the conv + |bias|, times max(1, |a|) through the
 PReLU; with a residual |r| + |alpha| times that; torch_port.ABS_TERMS per element):
   bf16 storage     |got - want| <= 1/2 ulp_bf16(max(|got|, |want|)) + C T     (half an ulp: truncation and double rounding fail)
   bf16x3 (hi + lo) |got - want| <= 2^-16 |want| + C T
   decoder (fp32)   |got - want| <= C T
-with one C (kernel_bounds.C) for the whole file and the two that follow it.  Every test prints its worst error / bound.
+  fp32 kernels     |got - want| <= C_F32 T      (conv3x3_kernel<F32>, stem_kernel<F32>, decoder_kernel<F32, false, S>)
+with one C (kernel_bounds.C) for the whole file and the two that follow it, and C_F32 = 2e-6 <= C (kernel_bounds.C_F32: four times the
+largest "C needed" the fp32 cases measured on the MI355X, 4.02e-7).  On the `full` set an operand rounded to bf16 or to 10 mantissa bits
+moves the worst element by 186 .. 265 / 24 .. 35 times C_F32 T; one rounded to 16 significant bits (the bf16x3 class) by 4 times in the
+stem, but only by 0.7 .. 1.2 times in a convolution: those six controls are listed, not asserted (kernel_refs.F32_CONTROLS_UNASSERTED).
+Every test prints its worst error / bound.
 
 Template instance -> production call site -> tests
   stem_mfma_kernel<false> / <true>   encoder_impl (api.hip), bf16 / bf16x3          test_stem[bf16-*], test_stem[bf16x3-*]
@@ -28,37 +39,60 @@ Template instance -> production call site -> tests
   conv3x3_kernel<BF16, CI, CO>       the route HRN_CONV_R64=0 HRN_CONV_V6=0 select   test_conv[gen*-*]
   decoder_kernel<BF16, false, S>     decoder_impl, bf16                              test_decoder[bf16-S*]
   decoder_kernel<F32, true, S>       decoder_impl, bf16x3 (the split decoder)        test_decoder[bf16x3-S*]
-Negative controls (test_negative_control) run on the CPU against the same GPU output and assert that the comparison FAILS.
+fp32 (for F32 route 0 and route 1 of the hook reach the same instance, conv3x3_kernel<F32, CI, CO> on 8 x 32 tiles: only route 0 runs)
+  conv3x3_kernel<F32,64,64>          encoder_impl: conv 1 / the final conv, PReLU     test_conv[f32enc-*]
+  conv3x3_kernel<F32,64,64>          encoder_impl: conv 2 (res_mode 1 in place)       test_conv[f32encres-*]
+  conv3x3_kernel<F32,128,128>        fuse_impl convA (pair gather in)                 test_conv[f32pairin-*]
+  conv3x3_kernel<F32,128,128>        fuse_impl convB (res_mode 2)                     test_conv[f32pairres-*]
+  conv3x3_kernel<F32,128,64>         fuse_impl output conv, res_mode 3 in place with partner alphas / alphas NULL, stack slot and
+                                     last level                                      test_conv[f32alpha-*], test_conv[f32alphalast-*]
+  conv3x3_kernel<F32,128,64>         fuse_impl output conv, alpha_residual False      test_conv[f32slot-*], test_conv[f32slotlast-*]
+  (conv3x3_kernel<F32> with ShiftNet's scale / relu epilogue: tests/test_gpu_kernels_shiftnet.py::test_conv_bn_relu)
+  stem_kernel<F32>, sub NULL         encoder_impl, fp32 (rep1 = V)                    test_stem[f32-*]
+  stem_kernel<F32>, `sub`            ShiftNet's eval stem (plane means, stride 2 HW)  test_stem[f32sub-*]
+  decoder_kernel<F32, false, S>      decoder_impl, fp32                               test_decoder[f32-S*]
+Negative controls (test_negative_control; the fp32 ones from kernel_refs.F32_CONTROLS) run on the CPU against the same GPU output and
+assert that the comparison FAILS.
 """
+import ctypes
+
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
-from kernel_bounds import BF, GUARD, SENT, SHAPES, _assert_close, _grid, _nchw, _pair_gather, _ratio, _tiles, _ulp_bf16
-from kt import BF16, BF16X3, _p, _stream, lib as _lib
+import kernel_refs as K
+from kernel_bounds import BF, C, C_F32, GUARD, SENT, SHAPES, Ten, _assert_close, _nchw, _pair_gather, _ratio, _ulp_bf16
+from kernel_refs import SLOPES
+from kt import BF16, BF16X3, F32, _p, _stream, lib as _lib
 
 pytestmark = pytest.mark.gpu
 
 PAD = 1024                  # gap in front of a lo plane: its offset is never the plane's size (as fuse_impl's t1 / t2)
-# slope classes: None (no PReLU), ACT 1 (0 <= a <= 1) and ACT 2 (a < 0 or a > 1) of conv3x3_r64, v6's act_pick for a > 1
-SLOPES = [None, 0.25, 0.0, 1.0, BF(-0.3), 1.5]
+# SLOPES (kernel_refs): None (no PReLU), ACT 1 (0 <= a <= 1) and ACT 2 (a < 0 or a > 1) of conv3x3_r64, v6's act_pick for a > 1
 
 
 # ----------------------------------------------------------------------------------------------------------- tensors and bounds
 class Act:
     """an activation tensor in storage dt inside a sentinel-filled int16 device buffer: the hi plane [0, n), GUARD sentinels; bf16x3:
-    PAD sentinels, the lo plane at lo_off bytes, GUARD sentinels.  val: the exact fp64 CPU value (hi + lo)."""
+    PAD sentinels, the lo plane at lo_off bytes, GUARD sentinels; f32: two words per element, GUARD sentinels, lo_off 0.  val: the exact
+    fp64 CPU value (hi + lo).  F32 takes its values from v (fp32, CPU), the other storages draw theirs from seed."""
 
-    def __init__(self, shape, dt, seed=None, scale=1.0, bits16=False):
+    def __init__(self, shape, dt, seed=None, scale=1.0, bits16=False, v=None):
         self.shape, self.dt = tuple(shape), dt
         self.n = int(np.prod(shape))
+        self.words = self.n * (2 if dt == F32 else 1)           # int16 words of the first (f32: the only) plane
         self.lo_e = self.n + GUARD + PAD if dt == BF16X3 else 0
-        total = self.lo_e + self.n + GUARD if dt == BF16X3 else self.n + GUARD
+        total = self.lo_e + self.n + GUARD if dt == BF16X3 else self.words + GUARD
         self.raw = torch.full((total,), SENT, dtype=torch.int16, device="cuda")
         self.lo_off = 2 * self.lo_e
         self.val = None
-        if seed is not None:
+        if dt == F32:
+            assert seed is None
+            if v is not None:
+                assert v.dtype == torch.float32 and tuple(v.shape) == self.shape
+                self.raw[:self.words] = v.contiguous().reshape(-1).view(torch.int16).cuda()
+                self.val = v.double()
+        elif seed is not None:
             v = torch.randn(self.shape, generator=torch.Generator().manual_seed(seed)) * scale
             if dt == BF16:
                 hi, lo = v.to(torch.bfloat16), None
@@ -77,28 +111,26 @@ class Act:
         return _p(self.raw)
 
     def planes(self):
-        """-> (hi, lo or None) as int16 CPU tensors of self.shape"""
+        """-> (hi, lo or None) as int16 CPU tensors of self.shape (f32: the bit patterns as one int32 tensor, None)"""
         raw = self.raw.cpu()
+        if self.dt == F32:
+            return raw[:self.words].view(torch.int32).reshape(self.shape), None
         hi = raw[:self.n].reshape(self.shape)
         lo = raw[self.lo_e:self.lo_e + self.n].reshape(self.shape) if self.dt == BF16X3 else None
         return hi, lo
 
     def value(self):
         hi, lo = self.planes()
+        if self.dt == F32:
+            return hi.view(torch.float32).double()
         v = hi.view(torch.bfloat16).double()
         return v + lo.view(torch.bfloat16).double() if lo is not None else v
 
     def guards_intact(self):
-        pieces = [self.raw[self.n:self.n + GUARD]]
+        pieces = [self.raw[self.words:self.words + GUARD]]
         if self.dt == BF16X3:
             pieces += [self.raw[self.n + GUARD:self.lo_e], self.raw[self.lo_e + self.n:]]
         return all(bool((p == SENT).all()) for p in pieces)
-
-
-def _prelu(x, T, a):
-    if a is None:
-        return x, T
-    return torch.where(x >= 0, x, a * x), T * max(1.0, abs(a))
 
 
 def _slope_dev(a):
@@ -130,69 +162,66 @@ INSTANCES = {
     "genpairres": (BF16, 1, 128, 128, 2, False, False),
     "genalpha": (BF16, 1, 128, 64, 3, False, "stack"),
 }
+INSTANCES.update(K.F32_INSTANCES)       # f32enc .. f32slotlast: conv3x3_kernel<F32> at its HRNet call sites
 
 
 def _conv_case(name, shape, seed, slope=None, alphas="mix", wset="bf16", ctrl=None):
-    """Launch instance `name` at `shape`; -> dict with the GPU output (fp64), the reference and T, plus what a control needs"""
+    """Launch instance `name` at `shape`; -> dict with the GPU output (fp64), the reference and T, plus what a control needs.
+    wset: bf16x3's weight set (bf16 / fp32); for an F32 instance the operand set (exact / full), which also picks slope and alphas"""
     dt, route, cin, cout, res_mode, in_pair, slot = INSTANCES[name]
     lib = _lib()
     H, W = SHAPES[shape]
-    uses_stack = in_pair or res_mode in (2, 3) or slot
     # view stack: B samples x V slots; a level of n views (pair_last = n - 2 for odd n) inside it, pair_vs = V > n
-    n = 3 if slot == "fused" else 5
-    V = n + 2
-    half, pair_last = n // 2, n - (n & 1) - 1
-    per = half if uses_stack else 1
-    if shape == "multi":
-        tiles = _tiles(dt, route, cin, cout, H, W)
-        B = 1
-        while (B * per * tiles) < 2 * _grid(route, cout, B * per * tiles):
-            B += 1
-        B += 1
-    else:
-        B = 2 if shape != "1x1" or uses_stack else 1
-    M = B * per
-    total = M * _tiles(dt, route, cin, cout, H, W)
-    if shape == "multi":
-        assert total >= 2 * _grid(route, cout, total), (total, _grid(route, cout, total))
-    x3 = dt == BF16X3
-    kind = "x3" if x3 else "bf16"
+    geo = K.conv_geometry(INSTANCES[name], shape)
+    uses_stack, n, V, half, pair_last, B, M = (geo[k] for k in ("uses_stack", "n", "V", "half", "pair_last", "B", "M"))
+    x3, f32 = dt == BF16X3, dt == F32
+    kind = "x3" if x3 else ("f32" if f32 else "bf16")
+    opset = wset if f32 else None
+    assert (opset in ("exact", "full")) == f32, (name, wset)
 
     # operands
-    g = torch.Generator().manual_seed(seed)
-    w = torch.randn((cout, cin, 3, 3), generator=g) * (0.05 if cin == 64 else 0.035)
-    if not x3 or wset == "bf16":
-        w = w.to(torch.bfloat16).float()
-    bias = torch.randn(cout, generator=g) * 0.1
-    if not x3:
-        bias = bias.to(torch.bfloat16).float()
+    if f32:
+        ops = K.f32_conv_operands(INSTANCES[name], geo, seed, opset)
+        w, bias = ops["w"], ops["bias"]
+        slope = K.f32_slope(slope, opset)
+    else:
+        g = torch.Generator().manual_seed(seed)
+        w = torch.randn((cout, cin, 3, 3), generator=g) * (0.05 if cin == 64 else 0.035)
+        if not x3 or wset == "bf16":
+            w = w.to(torch.bfloat16).float()
+        bias = torch.randn(cout, generator=g) * 0.1
+        if not x3:
+            bias = bias.to(torch.bfloat16).float()
     w64, b64 = w.double(), bias.double()
     wd, bd = w.cuda(), bias.cuda()
-    pk = torch.empty(cin * cout * 9 * (2 if x3 else 1), dtype=torch.bfloat16, device="cuda")
+    pk = torch.empty(cin * cout * 9 * (2 if x3 or f32 else 1), dtype=torch.bfloat16, device="cuda")
     assert lib.hrn_kt_conv_pack(dt, cin, cout, _p(wd), _p(pk), _stream()) == 0
 
-    stack = Act((B, V, H, W, 64), dt, seed + 1, bits16=True) if uses_stack else None
+    def act(key, shp, sd, **kw):          # an operand tensor: F32 from the builder's values, bf16 / bf16x3 drawn from the seed
+        return Act(shp, dt, v=ops[key]) if f32 else Act(shp, dt, sd, **kw)
+
+    stack = act("stack", (B, V, H, W, 64), seed + 1, bits16=True) if uses_stack else None
     stack0 = stack.planes() if stack is not None else None
-    inp = None if in_pair else Act((M, H, W, cin), dt, seed + 2)
+    inp = None if in_pair else act("inp", (M, H, W, cin), seed + 2)
     if in_pair:
         x64 = _pair_gather(stack.val[:, :n], half, pair_last)
     else:
         x64 = inp.val
-    # alphas [B][V]: 0, 1, 0.75 mixed in the batch (the partner of slot i is pair_last - i)
+    # alphas [B][V]: 0, 1, 0.75 (the full set: fp32(0.7)) mixed in the batch (the partner of slot i is pair_last - i)
     alph = None
     if res_mode == 3 and alphas == "mix":
-        pattern = [0.0, 1.0, 0.75, 0.75, 1.0, 0.0, 0.75]
-        alph = torch.tensor([[pattern[(b + j) % 7] for j in range(V)] for b in range(B)], dtype=torch.float32)
+        alph = K.conv_alphas(B, V, opset or "exact")
     out_vs = 1 if slot == "fused" else V
     if slot == "stack":
         out, out_h = stack, half                                  # res_mode 3: in place, out == res == stack
     elif slot == "fused":
         out, out_h = Act((B, H, W, 64), dt), half                 # the last level: fused [B][H][W][64], the residual from the stack
     elif res_mode == 1:
-        out, out_h = Act((M, H, W, cout), dt, seed + 3), 0        # in place: out == res, as the encoder's second conv
+        out, out_h = act("res", (M, H, W, cout), seed + 3), 0     # in place: out == res, as the encoder's second conv
     else:
         out, out_h = Act((M, H, W, cout), dt), 0
     res_ptr, res_lo, res_vs = None, 0, 0
+    r64 = None
     if res_mode == 1:
         res_ptr, res_lo = out.ptr, out.lo_off
         r64 = out.val
@@ -201,39 +230,20 @@ def _conv_case(name, shape, seed, slope=None, alphas="mix", wset="bf16", ctrl=No
     ad = alph.cuda() if alph is not None else None
     sd = _slope_dev(slope)
     pair_h = half if (in_pair or res_mode == 2) else 0
+    lo_offs = (0 if in_pair else inp.lo_off, stack.lo_off if stack is not None else 0, out.lo_off, res_lo)
+    assert not f32 or lo_offs == (0, 0, 0, 0)
     rc = lib.hrn_kt_conv3x3_epi(dt, route, cin, cout, None if in_pair else inp.ptr, stack.ptr if stack is not None else None, pair_h,
                                 pair_last, V if uses_stack else 0, _p(pk), _p(bd), _p(sd), res_ptr, res_mode, res_vs, _p(ad),
-                                V if ad is not None else 0, out.ptr, out_h, out_vs if slot else 0, 0 if in_pair else inp.lo_off,
-                                stack.lo_off if stack is not None else 0, out.lo_off, res_lo, M, H, W, _stream())
+                                V if ad is not None else 0, out.ptr, out_h, out_vs if slot else 0, *lo_offs, M, H, W, _stream())
     assert rc == 0, rc
     torch.cuda.synchronize()
 
-    # reference
+    # reference (kernel_refs.ref_conv_epi), in fp64 on the exact values the kernel read
+    args = dict(x=x64, w=w64, b=b64, slope=slope, res_mode=res_mode, res=r64, stack=stack.val if stack is not None else None, geo=geo,
+                alph=alph)
+
     def reference(w64=w64, own_alpha=False, swap_halves=False):
-        z = _nchw(x64)
-        y = F.conv2d(z, w64, b64, padding=1)
-        T = F.conv2d(z.abs(), w64.abs(), b64.abs(), padding=1)
-        y, T = _prelu(y, T, slope)
-        if res_mode == 1:
-            y, T = y + _nchw(r64), T + _nchw(r64).abs()
-        elif res_mode == 2:
-            st = stack.val[:, :n]
-            if swap_halves:
-                idx = torch.arange(half)
-                zz = torch.cat([st[:, pair_last - idx], st[:, idx]], -1).reshape((M, H, W, 128))
-            else:
-                zz = _pair_gather(st, half, pair_last)
-            y, T = y + _nchw(zz), T + _nchw(zz).abs()
-        elif res_mode == 3:
-            r = _nchw(stack.val[:, :half].reshape(M, H, W, 64))
-            if alph is None:
-                al = torch.ones(M, dtype=torch.float64)
-            else:
-                i = torch.arange(half)
-                al = (alph[:, i] if own_alpha else alph[:, pair_last - i]).reshape(M).double()
-            al = al[:, None, None, None]
-            y, T = r + al * y, r.abs() + al.abs() * T
-        return y, T
+        return K.ref_conv_epi(**dict(args, w=w64, own_alpha=own_alpha, swap_halves=swap_halves))
 
     if slot == "stack":
         got = _nchw(out.value()[:, :half].reshape(M, H, W, 64))
@@ -241,23 +251,26 @@ def _conv_case(name, shape, seed, slope=None, alphas="mix", wset="bf16", ctrl=No
         got = _nchw(out.value())
     want, T = reference()
     return dict(got=got, want=want, T=T, kind=kind, reference=reference, w64=w64, stack=stack, stack0=stack0, half=half, V=V, out=out,
-                inp=inp, alph=alph, slot=slot, M=M, res_mode=res_mode, pair_last=pair_last)
+                inp=inp, alph=alph, slot=slot, M=M, res_mode=res_mode, pair_last=pair_last, args=args, c=C_F32 if f32 else None)
 
 
 # the case matrix: every instance at every shape; the slope class, the alphas (mixed / NULL) and the weight set (bf16x3: bf16-exact or
-# general fp32) rotate over the shapes instead of taking the full product
+# general fp32; F32: the operand set exact / full of kernel_refs.f32_opset - every F32 instance meets `full` at 2x3, 15x33, 9x63 and
+# multi) rotate over the shapes instead of taking the full product
 CASES = []
 for ii, name in enumerate(INSTANCES):
     for si, shape in enumerate(SHAPES):
-        CASES.append(pytest.param(name, shape, SLOPES[(ii + si) % len(SLOPES)], "null" if (ii + si) % 4 == 3 else "mix",
-                                  "fp32" if (ii + si) % 2 else "bf16", id=f"{name}-{shape}"))
+        wset = K.f32_opset(ii, si) if INSTANCES[name][0] == F32 else ("fp32" if (ii + si) % 2 else "bf16")
+        CASES.append(pytest.param(name, shape, SLOPES[(ii + si) % len(SLOPES)], "null" if (ii + si) % 4 == 3 else "mix", wset,
+                                  id=f"{name}-{shape}"))
 
 
 @pytest.mark.parametrize("name,shape,slope,alphas,wset", CASES)
 def test_conv(name, shape, slope, alphas, wset):
     r = _conv_case(name, shape, 100 + 7 * list(SHAPES).index(shape), slope=slope, alphas=alphas, wset=wset)
-    tag = f"{name} {shape} slope={slope} alphas={alphas} w={wset}"
-    _assert_close(tag, r["kind"], r["got"], r["want"], r["T"])
+    shown = K.f32_slope(slope, wset) if INSTANCES[name][0] == F32 else slope       # (the full set runs its own value of the slope's class)
+    tag = f"{name} {shape} slope={shown} alphas={alphas} w={wset}"
+    _assert_close(tag, r["kind"], r["got"], r["want"], r["T"], c=r["c"] or C)
     out = r["out"]
     assert out.guards_intact(), f"{tag}: a write past the output"
     if r["stack"] is not None:
@@ -292,14 +305,44 @@ def _rz_bf16(x):
     return torch.sign(x) * torch.floor(x.abs() / u) * u
 
 
+def _f32_control_case(target):
+    """the GPU output a fp32 control is judged on: target an F32 conv instance, "stem" or "decoder", at the case kernel_refs names"""
+    if target == "stem":
+        r = _stem_case("f32", K.F32_CONTROL_SHAPE)
+        return dict(kind="stem", got=_nchw(r["out"].value()), args=dict(r["args"], m0=0, m1=r["M"]), layout="m c y x")
+    if target == "decoder":
+        r = _decoder_case(K.F32_CONTROL_DECODER[0], "f32", K.F32_CONTROL_DECODER[1])
+        return dict(kind="decoder", got=r["got"], args=r["args"], layout="n y x")
+    r = _conv_case(target, K.F32_CONTROL_SHAPE, K.F32_CONTROL_SEED, slope=K.F32_CONTROL_SLOPE, alphas="mix", wset="full")
+    return dict(kind="conv", got=r["got"], args=r["args"], layout="m c y x")
+
+
 @pytest.mark.parametrize("control,name", [("tap_swap", "v6pairres"), ("tap_swap", "x3alpha"), ("tap_swap", "r64res"),
                                           ("round_to_zero", "r64"), ("round_to_zero", "v6alpha"),
                                           ("own_alpha", "v6alpha"), ("own_alpha", "x3alpha"), ("own_alpha", "genalpha"),
-                                          ("swap_halves", "v6pairres"), ("swap_halves", "x3pairres"), ("swap_halves", "genpairres")])
+                                          ("swap_halves", "v6pairres"), ("swap_halves", "x3pairres"), ("swap_halves", "genpairres")] +
+                         K.F32_CONTROLS)
 def test_negative_control(control, name):
     """The comparison against a reference that is wrong in one way must FAIL on the same GPU output that passes against the right one:
     one (co, ci) pair with two taps swapped; the reference rounded toward zero (bf16); the view's own alpha instead of its partner's
-    (res_mode 3); the pair residual with its 64-channel halves swapped (res_mode 2)."""
+    (res_mode 3); the pair residual with its 64-channel halves swapped (res_mode 2).
+    fp32 (kernel_refs.F32_CONTROLS: the f32* instances, "stem", "decoder"), all on the `full` operand set under C_F32: the structural
+    controls above plus swap_in (the pair-gather input's halves exchanged: the chunk -> src0 / src1 selection), and the operand-rounding
+    controls round<bits>_x / round<bits>_w - the reference computed from activations (stem: inputs; decoder: `fused`) or weights rounded
+    to 8 (bf16), 11 (10 mantissa bits) or 16 significant bits (the bf16x3 class: what stem_mfma_kernel keeps of an input).  On the
+    `exact` operand set the rounding controls are no-ops - rounding a bf16-representable value changes nothing, so a kernel that drops
+    operand bits passes there: the gap the `full` set closes.  tests/test_kernels_fwd_f32_host.py asserts on the CPU that each of these
+    wrong references is at least twice the bound from the right one, which the kernel's own error (at most once the bound) cannot hide."""
+    if (control, name) in K.F32_CONTROLS:
+        case = _f32_control_case(name)
+        got = case["got"]
+        want, T = K.f32_control_reference(None, case)
+        ok = _assert_close(f"{name} (right reference)", "f32", got, want, T, layout=case["layout"], c=C_F32)
+        bad, Tb = K.f32_control_reference(control, case)
+        worst, idx = _ratio("f32", got, bad, Tb, C_F32)
+        print(f"{control} {name}: error / bound against the wrong reference {worst:.3e} (right one {ok:.3e})")
+        assert worst > 1.0, f"{control} {name}: the comparison does not tell the wrong reference from the right one"
+        return
     r = _conv_case(name, "15x33", 321, slope=0.25, alphas="mix", wset="fp32")
     got, kind = r["got"], r["kind"]
     ok = _assert_close(f"{name} (right reference)", kind, got, r["want"], r["T"])
@@ -329,10 +372,8 @@ def _k16(shape, g):
     return torch.randint(0, 1 << 16, shape, generator=g).double() / 65536.0
 
 
-@pytest.mark.parametrize("mode", ["bf16", "bf16x3", "bf16sub"])
-@pytest.mark.parametrize("shape", list(STEM_SHAPES))
-def test_stem(mode, shape):
-    """stem_mfma_kernel<false> (bf16), <true> (bf16x3) and the VALU stem_kernel<BF16> (`sub`): 2 -> 64 conv + PReLU of (view m, frame m / rep1)"""
+def _stem_case(mode, shape):
+    """Launch the stem in `mode` at `shape` -> dict: the output tensor, the fp64 operands (args of kernel_refs.ref_stem_fwd), kind, c"""
     lib = _lib()
     H, W, M = STEM_SHAPES[shape]
     segs_x = -(-W // 32)
@@ -341,44 +382,73 @@ def test_stem(mode, shape):
         nseg = M * H * segs_x
         waves = 4 * min(-(-nseg // 4), 8192)
         assert nseg >= 2 * waves and segs_x % 2 == 1 and (waves // segs_x) % H != 0, (nseg, waves)
-    rep1 = 3
-    dt = BF16 if mode != "bf16x3" else BF16X3
-    g = torch.Generator().manual_seed(17 + M + H)
-    x0 = _k16((M, H, W), g)
-    x1 = _k16((-(-M // rep1), H, W), g)
-    w = torch.randn((64, 2, 3, 3), generator=g) * 0.3
-    if mode == "bf16":
-        w = w.to(torch.bfloat16).float()        # (bf16x3 and the VALU stem take general fp32 weights)
-    bias = (torch.randint(-(1 << 14), 1 << 14, (64,), generator=g).double() / 65536.0).float()
+        # (the VALU stem_kernel of bf16sub / f32 / f32sub: more 4 x 32 patches than its 16,384 blocks, so blocks walk a second patch)
+        assert M * -(-H // 4) * segs_x > 16384
     slope = [None, 0.25, BF(-0.3), 1.5][list(STEM_SHAPES).index(shape) % 4]
-    sub = _k16((M, 2), g) if mode == "bf16sub" else None
+    if mode in ("f32", "f32sub"):
+        # general fp32 inputs, weights and bias (kernel_refs.f32_stem_operands); the inputs sit in guarded buffers that must stay unchanged
+        dt, kind, c = F32, "f32", C_F32
+        slope = K.f32_slope(slope, "full")
+        ops = K.f32_stem_operands(mode, M, H, W, 17 + M + H)
+        rep1, sub, w, bias = ops["rep1"], ops["sub"], ops["w"], ops["bias"]
+        x0, x1 = ops["x0"].double(), ops["x1"].double()
+        if mode == "f32sub":        # as ShiftNet's eval pass: one tensor [M][2][H][W], in1 = in0 + plane, both 2 planes apart, rep1 = 1
+            held = [Ten(ops["x"].shape, F32, ops["x"])]
+            p0, p1, stride = held[0].ptr, ctypes.c_void_p(held[0].raw.data_ptr() + 4 * H * W), 2 * H * W
+        else:
+            held = [Ten(ops["x0"].shape, F32, ops["x0"]), Ten(ops["x1"].shape, F32, ops["x1"])]
+            p0, p1, stride = held[0].ptr, held[1].ptr, H * W
+        held += [Ten(w.shape, F32, w), Ten(bias.shape, F32, bias)] + ([Ten(sub.shape, F32, sub)] if sub is not None else [])
+        dw, db, dsub = held[2 if mode == "f32" else 1].ptr, held[3 if mode == "f32" else 2].ptr, held[-1].ptr if sub is not None else None
+        sub = sub.double() if sub is not None else None
+    else:
+        rep1, held, c = 3, [], C
+        dt = BF16 if mode != "bf16x3" else BF16X3
+        kind = "x3" if dt == BF16X3 else "bf16"
+        g = torch.Generator().manual_seed(17 + M + H)
+        x0 = _k16((M, H, W), g)
+        x1 = _k16((-(-M // rep1), H, W), g)
+        w = torch.randn((64, 2, 3, 3), generator=g) * 0.3
+        if mode == "bf16":
+            w = w.to(torch.bfloat16).float()        # (bf16x3 and the VALU stem take general fp32 weights)
+        bias = (torch.randint(-(1 << 14), 1 << 14, (64,), generator=g).double() / 65536.0).float()
+        sub = _k16((M, 2), g) if mode == "bf16sub" else None
+        keep = [x0.float().cuda(), x1.float().cuda(), w.cuda(), bias.cuda(), sub.float().cuda() if sub is not None else None]
+        p0, p1, dw, db, dsub = (_p(t) for t in keep)
+        stride = H * W
     out = Act((M, H, W, 64), dt)
-    d0, d1, dw, db, ds = x0.float().cuda(), x1.float().cuda(), w.cuda(), bias.cuda(), _slope_dev(slope)
-    dsub = sub.float().cuda() if sub is not None else None
-    rc = lib.hrn_kt_stem(dt, _p(d0), H * W, _p(d1), rep1, H * W, _p(dsub), _p(dw), _p(db), _p(ds), out.ptr, out.lo_off, M, H, W, _stream())
+    ds = _slope_dev(slope)
+    rc = lib.hrn_kt_stem(dt, p0, stride, p1, rep1, stride, dsub, dw, db, _p(ds), out.ptr, out.lo_off, M, H, W, _stream())
     assert rc == 0, rc
     torch.cuda.synchronize()
     assert out.guards_intact()
-    hi, lo = out.planes()
-    kind = "x3" if dt == BF16X3 else "bf16"
+    assert all(t.unchanged() for t in held), "the stem wrote one of its inputs"
+    return dict(out=out, M=M, kind=kind, c=c, slope=slope,
+                args=dict(x0=x0, x1=x1, rep1=rep1, sub=sub, w=w.double(), b=bias.double(), slope=slope))
+
+
+@pytest.mark.parametrize("mode", ["bf16", "bf16x3", "bf16sub", "f32", "f32sub"])
+@pytest.mark.parametrize("shape", list(STEM_SHAPES))
+def test_stem(mode, shape):
+    """stem_mfma_kernel<false> (bf16), <true> (bf16x3) and the VALU stem_kernel<BF16> (`sub`): 2 -> 64 conv + PReLU of (view m, frame m / rep1);
+    stem_kernel<F32> as encoder_impl calls it (f32: sub NULL, rep1 = V) and as ShiftNet's eval pass does (f32sub: in1 = in0 + plane, image
+    stride 2 planes, rep1 = 1, sub = the plane means), on general fp32 inputs and weights"""
+    r = _stem_case(mode, shape)
+    M, kind, slope = r["M"], r["kind"], r["slope"]
+    hi, lo = r["out"].planes()
     worst = 0.0
-    w64, b64 = w.double(), bias.double()
     step = 512
     for m0 in range(0, M, step):          # in chunks of images: host memory stays small at the multi-item shape
         m1 = min(M, m0 + step)
-        idx = torch.arange(m0, m1)
-        a, b = x0[m0:m1], x1[idx // rep1]
-        if sub is not None:
-            a, b = a - sub[m0:m1, 0, None, None], b - sub[m0:m1, 1, None, None]
-        z = torch.stack([a, b], 1)
-        y = F.conv2d(z, w64, b64, padding=1)
-        T = F.conv2d(z.abs(), w64.abs(), b64.abs(), padding=1)
-        y, T = _prelu(y, T, slope)
-        got = hi[m0:m1].view(torch.bfloat16).double()
+        y, T = K.ref_stem_fwd(m0=m0, m1=m1, **r["args"])
+        if kind == "f32":
+            got = hi[m0:m1].view(torch.float32).double()
+        else:
+            got = hi[m0:m1].view(torch.bfloat16).double()
         if lo is not None:
             got = got + lo[m0:m1].view(torch.bfloat16).double()
-        r = _assert_close(f"stem {mode} {shape} M={M} slope={slope} images {m0}..", kind, _nchw(got), y, T)
-        worst = max(worst, r)
+        e = _assert_close(f"stem {mode} {shape} M={M} slope={slope} images {m0}..", kind, _nchw(got), y, T, c=r["c"])
+        worst = max(worst, e)
     print(f"stem {mode} {shape}: worst error / bound {worst:.3e}")
 
 
@@ -387,23 +457,26 @@ def test_stem(mode, shape):
 DEC_SHAPES = {"1x1": (1, 1, 1), "2x3": (2, 2, 3), "9x27": (3, 9, 27), "17x50": (2, 17, 50), "16x64": (2, 16, 64), "straddle": (5, 7, 33)}
 
 
-@pytest.mark.parametrize("scale", [2, 3, 4])
-@pytest.mark.parametrize("mode", ["bf16", "bf16x3"])
-@pytest.mark.parametrize("shape", list(DEC_SHAPES))
-def test_decoder(shape, mode, scale):
-    """decoder_kernel<BF16, false, S> and the split decoder <F32, true, S>: deconv S x S stride S + PReLU + 1 x 1 conv to one channel"""
+def _decoder_case(shape, mode, scale):
+    """Launch the decoder -> dict: sr (fp64, N images; the guard image checked), the fp64 args of kernel_refs.ref_decoder_fwd, c"""
     lib = _lib()
     N, H, W = DEC_SHAPES[shape]
-    dt = BF16 if mode == "bf16" else BF16X3
-    g = torch.Generator().manual_seed(1000 + 10 * scale + N)
-    fused = Act((N, H, W, 64), dt, 5 + scale)
-    wd = torch.randn((64, 64, scale, scale), generator=g) * 0.05
-    if dt == BF16:
-        wd = wd.to(torch.bfloat16).float()
-    bd = torch.randn(64, generator=g) * 0.1
-    wf = torch.randn(64, generator=g) * 0.2
-    bf = torch.randn(1, generator=g) * 0.1
+    dt = {"bf16": BF16, "bf16x3": BF16X3, "f32": F32}[mode]
     slope = [0.25, BF(-0.3), 1.5, 0.0][(scale + list(DEC_SHAPES).index(shape)) % 4]
+    if dt == F32:       # `fused` stored as f32, general fp32 values like the weights (kernel_refs.f32_decoder_operands)
+        slope = K.f32_slope(slope, "full")
+        ops = K.f32_decoder_operands(N, H, W, scale, 1000 + 10 * scale + N)
+        fused = Act((N, H, W, 64), dt, v=ops["fused"])
+        wd, bd, wf, bf = (ops[k] for k in ("wd", "bd", "wf", "bf"))
+    else:
+        g = torch.Generator().manual_seed(1000 + 10 * scale + N)
+        fused = Act((N, H, W, 64), dt, 5 + scale)
+        wd = torch.randn((64, 64, scale, scale), generator=g) * 0.05
+        if dt == BF16:
+            wd = wd.to(torch.bfloat16).float()
+        bd = torch.randn(64, generator=g) * 0.1
+        wf = torch.randn(64, generator=g) * 0.2
+        bf = torch.randn(1, generator=g) * 0.1
     wpk = torch.empty(64 * 64 * scale * scale, dtype=torch.float32, device="cuda")
     sr = torch.full((N + 1, scale * H, scale * W), float("nan"), device="cuda")        # image N: a guard that must stay untouched
     dev = [t.cuda() for t in (wd, bd, wf, bf)] + [_slope_dev(slope)]
@@ -413,10 +486,17 @@ def test_decoder(shape, mode, scale):
     torch.cuda.synchronize()
     got = sr.double().cpu()
     assert bool(torch.isnan(got[N]).all()), "a write past the SR output"
-    z = _nchw(fused.val)
-    y = F.conv_transpose2d(z, wd.double(), bd.double(), stride=scale)
-    T = F.conv_transpose2d(z.abs(), wd.double().abs(), bd.double().abs(), stride=scale)
-    y, T = _prelu(y, T, slope)
-    want = F.conv2d(y, wf.double().view(1, 64, 1, 1), bf.double())[:, 0]
-    T = F.conv2d(T, wf.double().abs().view(1, 64, 1, 1), bf.double().abs())[:, 0]
-    _assert_close(f"decoder {mode} S={scale} {shape} slope={slope}", "f32", got[:N], want, T, layout="n y x")
+    assert fused.guards_intact() and torch.equal(fused.value(), fused.val), "the decoder wrote its input"
+    return dict(got=got[:N], slope=slope, c=C_F32 if dt == F32 else C,
+                args=dict(fused=fused.val, wd=wd.double(), bd=bd.double(), slope=slope, wf=wf.double(), bf=bf.double(), S=scale))
+
+
+@pytest.mark.parametrize("scale", [2, 3, 4])
+@pytest.mark.parametrize("mode", ["bf16", "bf16x3", "f32"])
+@pytest.mark.parametrize("shape", list(DEC_SHAPES))
+def test_decoder(shape, mode, scale):
+    """decoder_kernel<BF16, false, S>, the split decoder <F32, true, S> and the fp32 decoder <F32, false, S> (`fused` stored as f32, general
+    fp32 values): deconv S x S stride S + PReLU + 1 x 1 conv to one channel"""
+    r = _decoder_case(shape, mode, scale)
+    want, T = K.ref_decoder_fwd(**r["args"])
+    _assert_close(f"decoder {mode} S={scale} {shape} slope={r['slope']}", "f32", r["got"], want, T, layout="n y x", c=r["c"])
