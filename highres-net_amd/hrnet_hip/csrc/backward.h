@@ -45,6 +45,8 @@ int hrn_launch_add(int dt, const void* a, const void* b, void* o, size_t n, hipS
 // fusion level helpers (HRNet.py:113-132): forward update of the kept views, and the two backward maps
 int hrn_launch_fuse_update(int dt, const void* stack, int n_in, const void* f, const float* alphas, int alpha_vs, int pair_last, int half,
                            int alpha_residual, void* out, size_t hw, int B, hipStream_t s);
+// t2 = z + u for the pair gather z = cat(view i, view pair_last - i) of stack [B][n_in][hw][64]; u, t2 [B * half][hw][128] (train.hip)
+int hrn_launch_pair_add(int dt, const void* stack, int n_in, int half, int pair_last, const void* u, void* t2, size_t hw, int B, hipStream_t s);
 int hrn_launch_fuse_df(int dt, const void* dsn, const float* alphas, int alpha_vs, int pair_last, int half, int alpha_residual, void* df,
                        size_t hw, int B, hipStream_t s);
 int hrn_launch_fuse_scatter(int dt, const void* dsn, const void* dz, int n_in, int half, int pair_last, int alpha_residual, void* ds,

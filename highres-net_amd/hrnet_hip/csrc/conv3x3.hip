@@ -330,6 +330,7 @@ int launch(const ConvParams& p, hipStream_t stream) {
     HrnProfScope prof(fam_names[DT][CIN / 128][COUT / 128], 2.0 * CIN * COUT * 9 * px,
                       px * es * (CIN + COUT + (p.res_mode ? COUT : 0)), stream);
     hipLaunchKernelGGL((conv3x3_kernel<DT, CIN, COUT>), dim3((unsigned)grid), dim3(256 * (COUT / 64)), LDS_BYTES, stream, p);
+    hrn_count_launch(HRN_LC_CONV_GENERAL);
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -386,8 +387,9 @@ int hrn_launch_conv3x3(int dt, int cin, int cout, const ConvParams& p, hipStream
     if (dt == HRN_BF16X3) return hrn_launch_conv3x3_v6x3(cin, cout, p, stream);      // the only kernel of this precision mode
     if (dt == HRN_BF16 && !p.scale && !p.relu && !general_only) {
         // the HRNet layers in bf16: resident-weights kernel (conv3x3_r64.hip) for the encoder's 64 -> 64 layers, conv3x3_v6.hip for the
-        // three layers of a fusion level.  What they decline (images beyond their 32-bit in-image offsets, > 8.3 Mpixel) runs on this
-        // file's general kernel; HRN_CONV_R64=0 / HRN_CONV_V6=0 force that route (A/B timing, and the test that covers it).
+        // three layers of a fusion level.  What they decline (images beyond their 32-bit in-image offsets: 2^31 bytes of the wider of the
+        // input and output image, i.e. 16.7 Mpixel at 64 channels, 8.3 Mpixel at 128) runs on this file's general kernel;
+        // HRN_CONV_R64=0 / HRN_CONV_V6=0 force that route (A/B timing, and the test that covers it).
         static const int r64 = [] { const char* e = getenv("HRN_CONV_R64"); return e ? atoi(e) : 1; }();
         static const int v6 = [] { const char* e = getenv("HRN_CONV_V6"); return e ? atoi(e) : 1; }();
         if (cin == 64 && cout == 64 && r64) { const int rc = hrn_launch_conv3x3_r64(p, stream); if (rc != -100) return rc; }

@@ -61,7 +61,7 @@ int hrn_launch_conv3x3_v6(int cin, int cout, const ConvParams& p, hipStream_t st
     if (p.res_mode == 3 && (p.out_h <= 0 || !p.res)) return -100;
     if (p.res_mode == 1 && !p.res) return -100;
     long grid = 0;
-    { const int rc = v6_grid(p, cin, grid); if (rc) return rc; }
+    { const int rc = v6_grid(p, cin, cout, grid); if (rc) return rc; }
     const double px = (double)p.M * p.H * p.W;
     const char* fam = cin == 64 ? "conv3x3_bf16_64x128"
                     : cout == 128 ? (p.res_mode ? "conv3x3_bf16_128x128+res" : "conv3x3_bf16_128x128")

@@ -511,7 +511,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_v6_kernel(const ConvParams p) 
                                 ol[i] = pack2_bf16(xa - __uint_as_float(h << 16), xb - __uint_as_float(h & 0xffff0000u));
                             }
                             const int gx = x0 + 16 * (r & 1) + 4 * qe + j;
-                            const unsigned voff = (unsigned)((gy * W + gx) * ROW + c15e * LB) | ((unsigned)(W - 1 - gx) & OOB6) | (gy < H ? 0u : OOB6);
+                            const unsigned voff = ((unsigned)(gy * W + gx) * (unsigned)ROW + (unsigned)(c15e * LB)) | ((unsigned)(W - 1 - gx) & OOB6) | (gy < H ? 0u : OOB6);
                             if constexpr (LB == 16) {
                                 __builtin_amdgcn_raw_buffer_store_b128(oh, rs_out, voff, 0, V6_ST_AUX);
                                 __builtin_amdgcn_raw_buffer_store_b128(ol, rs_out_lo, voff, 0, V6_ST_AUX);
@@ -584,7 +584,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_v6_kernel(const ConvParams p) 
                                 }
                                 const int gx = x0 + 16 * (r & 1) + 4 * qe + j;
                                 // a pixel outside the image gets an offset the descriptor's range check drops: no branch around the store
-                                const unsigned voff = (unsigned)((gy * W + gx) * ROW + c15e * LB) | ((unsigned)(W - 1 - gx) & OOB6) | (gy < H ? 0u : OOB6);
+                                const unsigned voff = ((unsigned)(gy * W + gx) * (unsigned)ROW + (unsigned)(c15e * LB)) | ((unsigned)(W - 1 - gx) & OOB6) | (gy < H ? 0u : OOB6);
                                 if (V6_ABL & 8) asm volatile("" :: "v"(o), "v"(voff));
                                 else if constexpr (LB == 16) __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, voff, 0, V6_ST_AUX);
                                 else __builtin_amdgcn_raw_buffer_store_b64(o, rs_out, voff, 0, V6_ST_AUX);
@@ -630,11 +630,16 @@ int launch_v6(const ConvParams& p, long grid, hipStream_t stream) {
 }
 
 // tiles, the 32-bit arithmetic limits, the persistent grid: shared by both launchers.  Returns 0, or -100 when not applicable.
-inline int v6_grid(const ConvParams& p, int cin, long& grid) {
+// One image of the WIDER of input and output must stay below 2^31 bytes: the halo offsets and the input descriptor count in_pitch =
+// 2 cin bytes per pixel, the output offsets, the output descriptor ((int)(hw * ROW)) and the plain residual ROW = 2 cout, and an
+// out-of-image lane is marked with bit 31 of its offset (OOB6), which only a descriptor of fewer than 2^31 bytes drops.  (The limit
+// counted the input alone until the 64 -> 128 data gradient joined the family: its output is twice as wide as its input.)
+inline int v6_grid(const ConvParams& p, int cin, int cout, long& grid) {
     const long tiles = (long)((p.W + T6_W - 1) / T6_W) * ((p.H + T6_H - 1) / T6_H);
     const long total = tiles * p.M;
     HRN_CHECK(total > 0, -2, "conv3x3_v6: bad tile count %ld", total);
-    if (total >= (1L << 30) || (long)p.H * p.W * (cin * 2) >= (1L << 31)) return -100;     // 32-bit tile / in-image byte arithmetic
+    const int wide = cin > cout ? cin : cout;
+    if (total >= (1L << 30) || (long)p.H * p.W * (wide * 2) >= (1L << 31)) return -100;     // 32-bit tile / in-image byte arithmetic
     grid = hrn_device_cus();
     if (total < grid) grid = total;
     if (grid >= 8) grid &= ~7L;

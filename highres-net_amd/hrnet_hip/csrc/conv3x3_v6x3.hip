@@ -21,7 +21,7 @@ int hrn_launch_conv3x3_v6x3(int cin, int cout, const ConvParams& p, hipStream_t 
     HRN_CHECK(!(p.res_mode == 1 && !p.res), -2, "conv3x3 bf16x3: res_mode 1 needs a residual tensor");
     HRN_CHECK(p.out_lo != 0 && (p.in_pair ? p.stack_lo != 0 : p.in_lo != 0), -2, "conv3x3 bf16x3: lo-plane offsets missing");
     long grid = 0;
-    const int rc = v6_grid(p, cin, grid);
+    const int rc = v6_grid(p, cin, cout, grid);
     HRN_CHECK(rc != -100, -2, "conv3x3 bf16x3: image too large for 32-bit in-image offsets (H=%d W=%d)", p.H, p.W);
     if (rc) return rc;
     const double px = (double)p.M * p.H * p.W;

@@ -110,6 +110,8 @@ int hrn_kt_add(int dt, const void* a, const void* b, void* o, size_t n, void* st
 // the fusion level's helpers: stack [B][n_in][hw][64], f / dsn / out / df [B * half][hw][64], dz [B * half][hw][128], ds [B][n_in][hw][64]
 int hrn_kt_fuse_update(int dt, const void* stack, int n_in, const void* f, const float* alphas, int alpha_vs, int pair_last, int half,
                        int alpha_residual, void* out, size_t hw, int B, void* stream);
+// t2 [B * half][hw][128] = cat(view v, view pair_last - v of stack) + u: the training forward's z + u of a fusion level
+int hrn_kt_pair_add(int dt, const void* stack, int n_in, int half, int pair_last, const void* u, void* t2, size_t hw, int B, void* stream);
 int hrn_kt_fuse_df(int dt, const void* dsn, const float* alphas, int alpha_vs, int pair_last, int half, int alpha_residual, void* df, size_t hw,
                    int B, void* stream);
 int hrn_kt_fuse_scatter(int dt, const void* dsn, const void* dz, int n_in, int half, int pair_last, int alpha_residual, void* ds, size_t hw,

@@ -136,6 +136,9 @@ int hrn_kt_fuse_update(int dt, const void* stack, int n_in, const void* f, const
                        int alpha_residual, void* out, size_t hw, int B, void* stream) {
     return hrn_launch_fuse_update(dt, stack, n_in, f, alphas, alpha_vs, pair_last, half, alpha_residual, out, hw, B, (hipStream_t)stream);
 }
+int hrn_kt_pair_add(int dt, const void* stack, int n_in, int half, int pair_last, const void* u, void* t2, size_t hw, int B, void* stream) {
+    return hrn_launch_pair_add(dt, stack, n_in, half, pair_last, u, t2, hw, B, (hipStream_t)stream);
+}
 int hrn_kt_fuse_df(int dt, const void* dsn, const float* alphas, int alpha_vs, int pair_last, int half, int alpha_residual, void* df, size_t hw,
                    int B, void* stream) {
     return hrn_launch_fuse_df(dt, dsn, alphas, alpha_vs, pair_last, half, alpha_residual, df, hw, B, (hipStream_t)stream);

@@ -29,6 +29,8 @@ enum HrnLaunchCounter {
     HRN_LC_FC2_BWD,             // fc2_bwd_kernel
     HRN_LC_FC1_BWD_W,           // fc1_bwd_w_kernel
     HRN_LC_FC1_BWD_X,           // fc1_bwd_x_kernel
+    HRN_LC_CONV_GENERAL,        // conv3x3_kernel (conv3x3.hip's general kernel: every f32 layer, and the bf16 layers r64 / v6 decline -
+                                // their plain layers share its profiler family names, so only this tells the routes apart)
     HRN_LC_COUNT
 };
 void hrn_count_launch(int which);

@@ -20,7 +20,7 @@ std::vector<hipEvent_t> g_pool;  // recycled events
 std::atomic<long> g_launches[HRN_LC_COUNT];
 const char* const g_launch_names[HRN_LC_COUNT] = {"conv_wgrad_f32", "stem_wgrad", "prelu_bwd", "bias_finish", "slope_finish", "conv_dgrad",
                                                    "decoder_bwd", "decoder_bwd_finish", "fuse_scatter", "sn_bn_bwd", "fc2_bwd",
-                                                   "fc1_bwd_w", "fc1_bwd_x"};
+                                                   "fc1_bwd_w", "fc1_bwd_x", "conv_general"};
 
 hipEvent_t get_event() {
     if (!g_pool.empty()) { hipEvent_t e = g_pool.back(); g_pool.pop_back(); return e; }

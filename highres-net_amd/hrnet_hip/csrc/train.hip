@@ -131,6 +131,18 @@ __global__ __launch_bounds__(256) void pair_add_kernel(const void* __restrict__ 
 
 }  // namespace
 
+int hrn_launch_pair_add(int dt, const void* stack, int n_in, int half, int pair_last, const void* u, void* t2, size_t hw, int B, hipStream_t s) {
+    HRN_CHECK(stack && u && t2, -2, "pair_add: null argument");
+    HRN_CHECK(B > 0 && half > 0 && hw > 0 && n_in >= 2 * half && pair_last >= half - 1 && pair_last < n_in, -2,
+              "pair_add: bad level B=%d n_in=%d half=%d pair_last=%d hw=%zu", B, n_in, half, pair_last, hw);
+    const size_t total4 = (size_t)B * half * hw * 32;
+    size_t grid = (total4 + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    HRN_LAUNCH_ST(dt, pair_add_kernel, dim3((unsigned)grid), dim3(256), 0, s, stack, n_in, half, pair_last, u, t2, hw, B);
+    HRN_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" {
 
 size_t hrn_hrnet_train_workspace_bytes(int num_layers, int B, int V, int H, int W) {
@@ -349,14 +361,7 @@ int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alp
         if ((rc = hrn_launch_conv3x3(dt, 128, 128, a, s, false))) return rc;
         if ((rc = conv_fwd(dt, 128, 128, at(tws, L.t1[t]), at(tws, L.u[t]), at(pk, P.fres_w[1]), (const float*)at(pk, P.fres_b[1]),
                            (const float*)at(pk, P.fres_a[1]), B * half, H, W, s))) return rc;
-        {
-            const size_t total4 = (size_t)B * half * hw * 32;
-            size_t grid = (total4 + 255) / 256;
-            if (grid > 4096) grid = 4096;
-            HRN_LAUNCH_ST(dt, pair_add_kernel, dim3((unsigned)grid), dim3(256), 0, s, st, n, half, pair_last, at(tws, L.u[t]), at(tws, L.t2[t]),
-                          hw, B);
-            HRN_LAUNCH_CHECK();
-        }
+        if ((rc = hrn_launch_pair_add(dt, st, n, half, pair_last, at(tws, L.u[t]), at(tws, L.t2[t]), hw, B, s))) return rc;
         if ((rc = conv_fwd(dt, 128, 64, at(tws, L.t2[t]), at(tws, L.f[t]), at(pk, P.fout_w), (const float*)at(pk, P.fout_b),
                            (const float*)at(pk, P.fout_a), B * half, H, W, s))) return rc;
         if ((rc = hrn_launch_fuse_update(dt, st, n, at(tws, L.f[t]), alphas, V, pair_last, half, alpha_residual,

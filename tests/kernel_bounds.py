@@ -231,3 +231,139 @@ class Acc:
         assert bool(torch.isnan(got[self.n:]).all()), f"{tag}: a write past the gradient"
         s0 = self.start.double().reshape(self.shape)
         return _assert_close(tag, "f32", got[:self.n].reshape(self.shape), s0 + want, (s0.abs() + T) * (c / C), layout=layout)
+
+
+# ----------------------------------------------------------------------------------------------------------- tensors of several GiB
+# tests/test_gpu_large_offsets.py: tensors that cross 2^31 bytes, 2^32 bytes and 2^31 elements are generated on the device from a seed and
+# only the checked images (or rows) ever reach the host.
+def crossings(n, esize):
+    """the element offsets inside a plane of n elements of esize bytes at which a 32-bit offset wraps: byte 2^31, byte 2^32, element 2^31"""
+    return sorted({e for e in ((1 << 31) // esize, (1 << 32) // esize, 1 << 31) if e < n})
+
+
+def crossed(n, esize):
+    """what a plane of n elements of esize bytes crosses, as the case ids name it: '2^31B', '2^32B', '2^31el'"""
+    return [name for name, e in (("2^31B", (1 << 31) // esize), ("2^32B", (1 << 32) // esize), ("2^31el", 1 << 31)) if e < n]
+
+
+def boundary_images(M, per, esize):
+    """the images worth checking of M images of `per` elements (esize bytes each) in one plane: image 0, the last one, and for every
+    crossing the image it falls into - or, where it falls exactly between two images, both of them"""
+    out = {0, M - 1}
+    for e in crossings(M * per, esize):
+        out.add(e // per)
+        if e % per == 0:
+            out.add(e // per - 1)
+    return sorted(out)
+
+
+class Big:
+    """M images of shape `img` in storage dt, generated ON THE DEVICE inside a sentinel-guarded int16 buffer: f32 (two words per element),
+    one bf16 plane, or bf16x3 = hi plane and lo plane (apart = False: the lo plane directly behind the hi plane, as every backward kernel
+    derives it from the element count; apart = True: GUARD + 1024 sentinel words between the planes, as the convolutions' free lo offsets
+    allow).  fill: "rand" (normal values x scale from `seed`: bf16 values for BF16, fp32 values for F32, hi + lo of fp32 values for
+    BF16X3), "zero", or "sent" (an output: every word a sentinel).  Only img() / rows() copy anything to the host."""
+    CHUNK = 1 << 27
+
+    def __init__(self, M, img, dt, fill="sent", seed=0, scale=1.0, apart=False):
+        self.M, self.img_shape, self.dt = M, tuple(img), dt
+        self.per = int(np.prod(img))
+        self.n = M * self.per
+        self.wpe = 2 if dt == F32 else 1
+        self.esize = 2 * self.wpe
+        words = self.n * self.wpe
+        self.lo_e = (self.n + (GUARD + 1024 if apart else 0)) if dt == BF16X3 else 0
+        total = (self.lo_e + self.n if dt == BF16X3 else words) + GUARD
+        total += -total % 4                                     # (checksum() reads the buffer as int64)
+        self.raw = torch.empty(total, dtype=torch.int16, device="cuda")
+        self.raw.fill_(SENT)
+        self.lo_off = 2 * self.lo_e
+        self.gen = torch.Generator(device="cuda").manual_seed(seed)
+        self.scale = scale
+        if fill == "zero":
+            for a, b in self._planes(0, self.n):
+                self.raw[a:b].zero_()
+        elif fill == "rand":
+            for a in range(0, self.n, self.CHUNK):
+                self._rand(a, min(self.n, a + self.CHUNK))
+        else:
+            assert fill == "sent", fill
+
+    def _planes(self, a, b):
+        """the word ranges of elements a..b in each plane"""
+        if self.dt == BF16X3:
+            return [(a, b), (self.lo_e + a, self.lo_e + b)]
+        return [(a * self.wpe, b * self.wpe)]
+
+    def _rand(self, a, b):
+        if self.dt == BF16:
+            self.raw[a:b].view(torch.bfloat16).normal_(0.0, self.scale, generator=self.gen)
+        elif self.dt == F32:
+            self.raw[2 * a:2 * b].view(torch.float32).normal_(0.0, self.scale, generator=self.gen)
+        else:
+            v = torch.empty(b - a, dtype=torch.float32, device="cuda").normal_(0.0, self.scale, generator=self.gen)
+            hi = v.to(torch.bfloat16)
+            self.raw[a:b] = hi.view(torch.int16)
+            self.raw[self.lo_e + a:self.lo_e + b] = (v - hi.float()).to(torch.bfloat16).view(torch.int16)
+
+    def rand_images(self, images):
+        """random values at the listed images (of a zero tensor: the sparse inputs of the kernels whose output is a sum over all images)"""
+        for m in images:
+            self._rand(m * self.per, (m + 1) * self.per)
+
+    def set_img(self, m, v):
+        """image m <- the fp32 CPU values v (exact in dt or not: the kernel's value is what img() reads back)"""
+        v = v.contiguous().reshape(-1).cuda()
+        assert v.dtype == torch.float32 and v.numel() == self.per
+        a, b = m * self.per, (m + 1) * self.per
+        if self.dt == F32:
+            self.raw[2 * a:2 * b] = v.view(torch.int16)
+        else:
+            hi = v.to(torch.bfloat16)
+            self.raw[a:b] = hi.view(torch.int16)
+            if self.dt == BF16X3:
+                self.raw[self.lo_e + a:self.lo_e + b] = (v - hi.float()).to(torch.bfloat16).view(torch.int16)
+
+    @property
+    def ptr(self):
+        return _p(self.raw)
+
+    def _val(self, a, b, shape):
+        if self.dt == F32:
+            return self.raw[2 * a:2 * b].cpu().view(torch.float32).double().reshape(shape)
+        v = self.raw[a:b].cpu().view(torch.bfloat16).double()
+        if self.dt == BF16X3:
+            v = v + self.raw[self.lo_e + a:self.lo_e + b].cpu().view(torch.bfloat16).double()
+        return v.reshape(shape)
+
+    def img(self, m):
+        """the exact fp64 CPU value of image m (hi + lo)"""
+        assert 0 <= m < self.M
+        return self._val(m * self.per, (m + 1) * self.per, self.img_shape)
+
+    def rows(self, m, y0, y1, v=None):
+        """rows y0..y1 of image m (img (H, W, C)), or of its view v (img (V, H, W, C)): fp64 (y1 - y0, W, C)"""
+        shp = self.img_shape if v is None else self.img_shape[1:]
+        row = shp[1] * shp[2]
+        base = m * self.per + (0 if v is None else v * shp[0] * row)
+        assert 0 <= y0 <= y1 <= shp[0]
+        return self._val(base + y0 * row, base + y1 * row, (y1 - y0,) + tuple(shp[1:]))
+
+    def bits(self, m):
+        """the raw words of image m, every plane (to compare an input or an untouched slot bit for bit)"""
+        return torch.cat([self.raw[a:b].cpu() for a, b in self._planes(m * self.per, (m + 1) * self.per)])
+
+    def checksum(self):
+        """a wrapping int64 sum of every word, guards included, computed on the device: equal before and after <=> (for a test) unchanged"""
+        return int(self.raw.view(torch.int64).sum())
+
+    def guards_intact(self):
+        words = self.n * self.wpe
+        if self.dt == BF16X3:
+            pieces = [self.raw[self.n:self.lo_e], self.raw[self.lo_e + self.n:]]
+        else:
+            pieces = [self.raw[words:]]
+        return all(bool((p == SENT).all()) for p in pieces)
+
+    def all_sentinels(self):
+        return bool((self.raw == SENT).all())

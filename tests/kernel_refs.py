@@ -62,6 +62,14 @@ def ref_fuse_scatter(dsn, dz, n, pair_last, alpha_residual, swap_halves=False):
     return ds, T
 
 
+def ref_pair_add(stack, u, pair_last):
+    """stack (B, n, hw, 64), u (B, half, hw, 128) -> t2 = cat(view v, view pair_last - v) + u, and T"""
+    half = u.shape[1]
+    v = torch.arange(half)
+    z = torch.cat([stack[:, v], stack[:, pair_last - v]], -1)
+    return z + u, z.abs() + u.abs()
+
+
 def ref_alpha_grad(dsn, f):
     """dsn, f (B, half, hw, 64) -> sum over pixels and channels of dsn f per (b, v) (it belongs to d_alphas[b][pair_last - v]), and T"""
     p = dsn * f
@@ -354,6 +362,41 @@ def ref_conv_epi(x, w, b, slope, res_mode, res=None, stack=None, geo=None, alph=
         al = al[:, None, None, None]
         y, T = r + al * y, (r.abs() + al.abs() * T if with_T else None)
     return y, T
+
+
+def ref_conv_rows(xpad, w, b, slope, res_mode=0, res=None, alpha=1.0):
+    """Output rows y0..y1 of one image of a conv3x3 layer with the epilogue of ConvParams, from the rows the kernel reads for them:
+    xpad (y1 - y0 + 2, W, cin) = input rows y0 - 1 .. y1, the REAL neighbour rows inside the image and zeros where they lie outside it (the
+    convolution's padding); res (y1 - y0, W, cout): res_mode 1 the residual's rows, 2 the pair gather's, 3 the stack slot's (then
+    res + alpha conv).  -> (cout, y1 - y0, W) and T.  With y0 = 0, y1 = H it is ref_conv_epi of the whole image."""
+    z = xpad.permute(2, 0, 1)[None]
+    y = F.conv2d(z, w, b, padding=(0, 1))
+    T = F.conv2d(z.abs(), w.abs(), b.abs(), padding=(0, 1))
+    y, T = ref_prelu_fwd(y, T, slope)
+    if res_mode in (1, 2):
+        r = res.permute(2, 0, 1)[None]
+        y, T = y + r, T + r.abs()
+    elif res_mode == 3:
+        r = res.permute(2, 0, 1)[None]
+        y, T = r + alpha * y, r.abs() + abs(alpha) * T
+    return y[0], T[0]
+
+
+def ref_conv_dgrad(g, w, res=None):
+    """g (M, H, W, cout), raw weights w (cout, cin, 3, 3) fp64 -> dx (M, cin, H, W) = the input gradient of conv2d(x, w, padding=1)
+    (+ res (M, H, W, cin)), and T"""
+    z = _nchw(g)
+    dx, T = F.conv_transpose2d(z, w, padding=1), F.conv_transpose2d(z.abs(), w.abs(), padding=1)
+    if res is not None:
+        dx, T = dx + _nchw(res), T + _nchw(res).abs()
+    return dx, T
+
+
+def ref_conv_wgrad(x, g):
+    """x (M, H, W, cin), g (M, H, W, cout) fp64 -> dw (cout, cin, 3, 3) of conv2d(x, w, padding=1), and T"""
+    shape = (g.shape[-1], x.shape[-1], 3, 3)
+    return (torch.nn.grad.conv2d_weight(_nchw(x), shape, _nchw(g), padding=1),
+            torch.nn.grad.conv2d_weight(_nchw(x).abs(), shape, _nchw(g).abs(), padding=1))
 
 
 def f32_stem_operands(mode, M, H, W, seed):

@@ -45,6 +45,7 @@ SIGNATURES = {
     "hrn_kt_colsum": (i, [i, vp, sz, i, vp, vp, vp]),
     "hrn_kt_add": (i, [i, vp, vp, vp, sz, vp]),
     "hrn_kt_fuse_update": (i, [i, vp, i, vp, vp, i, i, i, i, vp, sz, i, vp]),
+    "hrn_kt_pair_add": (i, [i, vp, i, i, i, vp, vp, sz, i, vp]),
     "hrn_kt_fuse_df": (i, [i, vp, vp, i, i, i, i, vp, sz, i, vp]),
     "hrn_kt_fuse_scatter": (i, [i, vp, vp, i, i, i, i, vp, sz, i, vp]),
     "hrn_kt_alpha_grad_scratch_bytes": (sz, [i]),
@@ -87,7 +88,7 @@ def _cus():
 
 
 COUNTERS = ("conv_wgrad_f32", "stem_wgrad", "prelu_bwd", "bias_finish", "slope_finish", "conv_dgrad", "decoder_bwd", "decoder_bwd_finish",
-            "fuse_scatter", "sn_bn_bwd", "fc2_bwd", "fc1_bwd_w", "fc1_bwd_x")
+            "fuse_scatter", "sn_bn_bwd", "fc2_bwd", "fc1_bwd_w", "fc1_bwd_x", "conv_general")
 
 
 def _launches(fn):

@@ -21,6 +21,7 @@ Template instance -> production call site (train.hip unless noted) -> tests
   colsum_kernel<64|128, *>              the encoder's final bias; ShiftNet's conv biases       test_colsum[*-C*-*]
   add_kernel<*>                         residual sums of the training forward                    test_add[*]
   fuse_update_kernel<*>                 the fusion levels, forward for training                  test_fuse_update[*-n*-B*-*]
+  pair_add_kernel<*>                    t2 = z + u of a fusion level, forward for training       test_pair_add[*-n*-B*-*]
   fuse_df_kernel<*>                     d f of a level                                           test_fuse_df[*-n*-B*-*]
   fuse_scatter_kernel<*>                d views of a level                                       test_fuse_scatter[*-n*-B*-*]
   alpha_grad_partial_kernel<*> + finish d alphas per level                                       test_alpha_grad[*-*]
@@ -42,7 +43,7 @@ import torch
 
 from kernel_bounds import BF, C, GUARD, NAN16, SENT, Acc, Ten, _assert_close, _nchw, _ratio, rnd
 from kernel_refs import (DEC_SLOPES, LEVELS, PRELU_SLOPES, _alphas, decoder_inputs, prelu_inputs, ref_alpha_grad, ref_decoder_bwd, ref_decoder_up,
-                         ref_fuse_df, ref_fuse_scatter, ref_fuse_update, ref_median, ref_prelu_bwd, ref_split_planes, ref_stem_dgrad_route,
+                         ref_fuse_df, ref_fuse_scatter, ref_fuse_update, ref_median, ref_pair_add, ref_prelu_bwd, ref_split_planes, ref_stem_dgrad_route,
                          ref_stem_pre, ref_stem_wgrad, route_inputs, split_inputs)
 from kt import BF16, BF16X3, F32, _cus, _p, _stream, lib as _lib
 
@@ -181,6 +182,31 @@ def test_fuse_update(dt, n, B, hw_name, ar):
         assert bool(zero.any())
         for po, ps in zip(r["out"].planes(), r["stack"].planes()):
             assert torch.equal(po[zero].view(torch.int16 if dt != F32 else torch.int32), ps[:, :r["half"]][zero].view(torch.int16 if dt != F32 else torch.int32))
+
+
+PAIR_ADD_CASES = [c for c in LEVEL_CASES if c.values[4] == 0]          # (no alpha residual in this kernel: one case per level and size)
+
+
+@pytest.mark.parametrize("dt,n,B,hw_name,ar", PAIR_ADD_CASES)
+def test_pair_add(dt, n, B, hw_name, ar):
+    """pair_add_kernel<ST>: t2[b * half + v] = cat(s[b][v], s[b][pair_last - v]) + u, the unpaired view of an odd level unread; "cap": the
+    grid-stride loop of its 4096 x 256 threads runs twice (B half hw 32 float4 units)"""
+    lib = _lib()
+    half, pair_last, _, hw = _level(n, B, hw_name)
+    if hw_name == "cap":
+        assert B * half * hw * 32 > 4096 * 256
+    v = rnd((B, n, hw, 64), 14 + n, dt)
+    if n & 1:
+        v[:, n - 1] = float("nan")          # takes no part in any pair
+    stack = Ten((B, n, hw, 64), dt, v)
+    u = Ten((B, half, hw, 128), dt, rnd((B, half, hw, 128), 15 + n, dt))
+    t2 = Ten((B, half, hw, 128), dt)
+    assert lib.hrn_kt_pair_add(dt, stack.ptr, n, half, pair_last, u.ptr, t2.ptr, hw, B, _stream()) == 0
+    torch.cuda.synchronize()
+    assert stack.unchanged() and u.unchanged() and t2.guard_ok()
+    want, T = ref_pair_add(stack.val, u.val, pair_last)
+    assert bool(torch.isfinite(want).all())
+    _assert_close(f"pair_add {KIND[dt]} n={n} B={B} hw={hw_name}", KIND[dt], t2.value(), want, T, layout="b v p c")
 
 
 def _fuse_df_case(dt, n, B, hw_name, ar):
