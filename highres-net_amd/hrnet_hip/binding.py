@@ -231,34 +231,45 @@ def _ptr(t):
 
 
 # --------------------------------------------------------------------------- HRNet
+def hrnet_param_table(num_layers):
+    """HRNet's parameters in the module's registration order (== the reference's state_dict order, HRNet.py:36-169), one row each:
+    (state-dict key, HrnetParams field, index into that field's array or None)."""
+    def block(prefix, field, first):          # a ResidualBlock: conv, PReLU, conv, PReLU
+        return [(f"{prefix}.block.{m}.{leaf}", f"{field}_{x}", first + j)
+                for j in (0, 1) for m, leaf, x in ((2 * j, "weight", "w"), (2 * j, "bias", "b"), (2 * j + 1, "weight", "a"))]
+
+    rows = [("encode.init_layer.0.weight", "enc_init_w", None), ("encode.init_layer.0.bias", "enc_init_b", None),
+            ("encode.init_layer.1.weight", "enc_init_a", None)]
+    for l in range(num_layers):
+        rows += block(f"encode.res_layers.{l}", "enc_res", 2 * l)
+    rows += [("encode.final.0.weight", "enc_final_w", None), ("encode.final.0.bias", "enc_final_b", None)]
+    rows += block("fuse.fuse.0", "fuse_res", 0)
+    rows += [("fuse.fuse.1.weight", "fuse_out_w", None), ("fuse.fuse.1.bias", "fuse_out_b", None), ("fuse.fuse.2.weight", "fuse_out_a", None),
+             ("decode.deconv.0.weight", "dec_w", None), ("decode.deconv.0.bias", "dec_b", None), ("decode.deconv.1.weight", "dec_a", None),
+             ("decode.final.weight", "fin_w", None), ("decode.final.bias", "fin_b", None)]
+    return rows
+
+
+def hrnet_param_names(num_layers):
+    """HRNet's parameters in the module's registration order (== the reference's state_dict order, HRNet.py:36-169)."""
+    return [key for key, _, _ in hrnet_param_table(num_layers)]
+
+
 def hrnet_param_struct(named, num_layers, optional=False):
     """named: dict of reference state-dict keys -> device f32 tensors.  Returns (HrnetParams, tensors kept alive).  optional: a key
     missing from `named` becomes a NULL field (a frozen parameter's gradient for hrn_hrnet_backward_sel)."""
     keep = []
-
-    def p(key):
-        if optional and key not in named:
-            return None
-        t = _dev_f32(named[key].detach(), key)
-        keep.append(t)
-        return t.data_ptr()
-
     P = HrnetParams()
     P.num_layers = num_layers
-    P.enc_init_w, P.enc_init_b, P.enc_init_a = p("encode.init_layer.0.weight"), p("encode.init_layer.0.bias"), p("encode.init_layer.1.weight")
-    for l in range(num_layers):
-        for j, (cw, ca) in enumerate(((0, 1), (2, 3))):
-            P.enc_res_w[2 * l + j] = p(f"encode.res_layers.{l}.block.{cw}.weight")
-            P.enc_res_b[2 * l + j] = p(f"encode.res_layers.{l}.block.{cw}.bias")
-            P.enc_res_a[2 * l + j] = p(f"encode.res_layers.{l}.block.{ca}.weight")
-    P.enc_final_w, P.enc_final_b = p("encode.final.0.weight"), p("encode.final.0.bias")
-    for j, (cw, ca) in enumerate(((0, 1), (2, 3))):
-        P.fuse_res_w[j] = p(f"fuse.fuse.0.block.{cw}.weight")
-        P.fuse_res_b[j] = p(f"fuse.fuse.0.block.{cw}.bias")
-        P.fuse_res_a[j] = p(f"fuse.fuse.0.block.{ca}.weight")
-    P.fuse_out_w, P.fuse_out_b, P.fuse_out_a = p("fuse.fuse.1.weight"), p("fuse.fuse.1.bias"), p("fuse.fuse.2.weight")
-    P.dec_w, P.dec_b, P.dec_a = p("decode.deconv.0.weight"), p("decode.deconv.0.bias"), p("decode.deconv.1.weight")
-    P.fin_w, P.fin_b = p("decode.final.weight"), p("decode.final.bias")
+    for key, field, index in hrnet_param_table(num_layers):
+        if optional and key not in named:
+            continue                          # (a fresh struct is all NULL)
+        t = _dev_f32(named[key].detach(), key)
+        keep.append(t)
+        if index is None:
+            setattr(P, field, t.data_ptr())
+        else:
+            getattr(P, field)[index] = t.data_ptr()
     return P, keep
 
 
@@ -1109,20 +1120,6 @@ def _op_tile_scatter(out: torch.Tensor, srs: torch.Tensor, t: int, R: int, scale
 # (call sites: src/train.py:174-191).  Each is registered with a fake (meta) implementation and, where the reference differentiates
 # through it, with `register_autograd`: the backward formula is itself a registered op over the C ABI's *_backward entry point.  The
 # reference-named modules call these through torch.ops.hrnet_hip.* in .train() mode.
-def hrnet_param_names(num_layers):
-    """HRNet's parameters in the module's registration order (== the reference's state_dict order, HRNet.py:36-169)."""
-    names = ["encode.init_layer.0.weight", "encode.init_layer.0.bias", "encode.init_layer.1.weight"]
-    for l in range(num_layers):
-        names += [f"encode.res_layers.{l}.block.0.weight", f"encode.res_layers.{l}.block.0.bias", f"encode.res_layers.{l}.block.1.weight",
-                  f"encode.res_layers.{l}.block.2.weight", f"encode.res_layers.{l}.block.2.bias", f"encode.res_layers.{l}.block.3.weight"]
-    names += ["encode.final.0.weight", "encode.final.0.bias"]
-    names += ["fuse.fuse.0.block.0.weight", "fuse.fuse.0.block.0.bias", "fuse.fuse.0.block.1.weight",
-              "fuse.fuse.0.block.2.weight", "fuse.fuse.0.block.2.bias", "fuse.fuse.0.block.3.weight",
-              "fuse.fuse.1.weight", "fuse.fuse.1.bias", "fuse.fuse.2.weight"]
-    names += ["decode.deconv.0.weight", "decode.deconv.0.bias", "decode.deconv.1.weight", "decode.final.weight", "decode.final.bias"]
-    return names
-
-
 SHIFTNET_PARAM_NAMES = [f"layer{i}.{j}.{k}" for i in range(1, 9) for j in (0, 1) for k in ("weight", "bias")] + ["fc1.weight", "fc1.bias", "fc2.weight"]
 SHIFTNET_BUFFER_NAMES = [f"layer{i}.1.{k}" for i in range(1, 9) for k in ("running_mean", "running_var")]
 

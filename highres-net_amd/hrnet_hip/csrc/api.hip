@@ -72,22 +72,23 @@ int encoder_impl(const void* pk, int dt, int nl, const float* lrs, int B, int V,
     if ((rc = hrn_launch_median(lrs, ref, B, V, H, W, s))) return rc;
     // stem: channel 0 = view, channel 1 = the sample's reference frame; 2->64 + PReLU  (HRNet.py:200-204, :51-53)
     const size_t lo = stack_lo(dt, B, V, H, W);        // bf16x3: lo plane of bufA / bufB / emb (0 otherwise)
-    if ((rc = hrn_launch_stem(dt, lrs, hw, ref, V, hw, nullptr, (const float*)at(pk, L.stem_w), (const float*)at(pk, L.stem_b),
-                              (const float*)at(pk, L.stem_a), bufA, B * V, H, W, s, lo))) return rc;
+    const ConvSite& stem = L.site[SITE_STEM];
+    if ((rc = hrn_launch_stem(dt, lrs, hw, ref, V, hw, nullptr, (const float*)at(pk, stem.w), (const float*)at(pk, stem.b),
+                              (const float*)at(pk, stem.a), bufA, B * V, H, W, s, lo))) return rc;
     // residual blocks: A -conv+PReLU-> B -conv+PReLU, + A-> A (in place: the residual is read at the stored pixel only)
     for (int l = 0; l < nl; ++l) {
         ConvParams p = conv_base(B * V, H, W);
         p.in = bufA; p.out = bufB; p.in_lo = p.out_lo = lo;
-        p.wpk = at(pk, L.enc_w[2 * l]); p.bias = (const float*)at(pk, L.enc_b[2 * l]); p.slope = (const float*)at(pk, L.enc_a[2 * l]);
+        conv_site(p, pk, L.site[site_enc(l, 0)]);
         if ((rc = hrn_launch_conv3x3(dt, 64, 64, p, s, false))) return rc;
         ConvParams q = conv_base(B * V, H, W);
         q.in = bufB; q.out = bufA; q.res = bufA; q.res_mode = 1; q.in_lo = q.out_lo = q.res_lo = lo;
-        q.wpk = at(pk, L.enc_w[2 * l + 1]); q.bias = (const float*)at(pk, L.enc_b[2 * l + 1]); q.slope = (const float*)at(pk, L.enc_a[2 * l + 1]);
+        conv_site(q, pk, L.site[site_enc(l, 1)]);
         if ((rc = hrn_launch_conv3x3(dt, 64, 64, q, s, false))) return rc;
     }
     ConvParams f = conv_base(B * V, H, W);
     f.in = bufA; f.out = emb; f.in_lo = f.out_lo = lo;
-    f.wpk = at(pk, L.encf_w); f.bias = (const float*)at(pk, L.encf_b); f.slope = nullptr;
+    conv_site(f, pk, L.site[site_enc_final(nl)]);
     return hrn_launch_conv3x3(dt, 64, 64, f, s, false);
 }
 
@@ -110,14 +111,14 @@ int fuse_impl(const void* pk, int dt, int nl, int alpha_residual, void* emb, con
         ConvParams a = conv_base(B * half, H, W);
         a.in_pair = 1; a.stack = emb; a.pair_h = half; a.pair_last = n - parity - 1; a.pair_vs = V;
         a.out = t1; a.stack_lo = a.out_lo = lo;
-        a.wpk = at(pk, L.fres_w[0]); a.bias = (const float*)at(pk, L.fres_b[0]); a.slope = (const float*)at(pk, L.fres_a[0]);
+        conv_site(a, pk, L.site[site_fres(nl, 0)]);
         if ((rc = hrn_launch_conv3x3(dt, 128, 128, a, s, false))) return rc;
         // t2 = z + PReLU(conv(t1))                                          (HRNet.py:20-21, :33)
         ConvParams b = conv_base(B * half, H, W);
         b.in = t1; b.out = t2; b.in_lo = b.out_lo = b.stack_lo = lo;
         b.res_mode = 2;      // residual = the same pair gather, straight from the stack
         b.stack = emb; b.pair_h = half; b.pair_last = n - parity - 1; b.pair_vs = V;
-        b.wpk = at(pk, L.fres_w[1]); b.bias = (const float*)at(pk, L.fres_b[1]); b.slope = (const float*)at(pk, L.fres_a[1]);
+        conv_site(b, pk, L.site[site_fres(nl, 1)]);
         if ((rc = hrn_launch_conv3x3(dt, 128, 128, b, s, false))) return rc;
         // f = PReLU(conv(t2)); s_i <- s_i + alpha_partner * f  (or s_i <- f)  (HRNet.py:95-97, :123-128)
         ConvParams c = conv_base(B * half, H, W);
@@ -126,7 +127,7 @@ int fuse_impl(const void* pk, int dt, int nl, int alpha_residual, void* emb, con
         if (last) { c.out = fused; c.out_vs = 1; c.out_lo = flo; } else { c.out = emb; c.out_vs = V; c.out_lo = lo; }
         c.pair_last = n - parity - 1;
         if (alpha_residual) { c.res_mode = 3; c.res = emb; c.res_vs = V; c.alphas = alphas; c.alpha_vs = V; }
-        c.wpk = at(pk, L.fout_w); c.bias = (const float*)at(pk, L.fout_b); c.slope = (const float*)at(pk, L.fout_a);
+        conv_site(c, pk, L.site[site_fout(nl)]);
         if ((rc = hrn_launch_conv3x3(dt, 128, 64, c, s, false))) return rc;
         n = half;
     }
@@ -186,22 +187,20 @@ int hrn_hrnet_pack_s(const hrn_hrnet_params* P, int dt, int scale, void* packed,
         HRN_HIP(hipMemcpyAsync(at(packed, off), src, n * 4, hipMemcpyDeviceToDevice, s));
         return 0;
     };
-    if ((rc = copy(L.stem_w, P->enc_init_w, 64 * 18)) || (rc = copy(L.stem_b, P->enc_init_b, 64)) || (rc = copy(L.stem_a, P->enc_init_a, 1))) return rc;
-    for (int i = 0; i < 2 * nl; ++i) {
-        HRN_CHECK(P->enc_res_w[i], -2, "hrn_hrnet_pack: null encoder weight %d", i);
-        if ((rc = hrn_launch_conv_pack(dt, 64, 64, P->enc_res_w[i], at(packed, L.enc_w[i]), s))) return rc;
-        if ((rc = copy(L.enc_b[i], P->enc_res_b[i], 64)) || (rc = copy(L.enc_a[i], P->enc_res_a[i], 1))) return rc;
+    for (int k = 0; k < num_sites(nl); ++k) {
+        const ConvSite& c = L.site[k];
+        const SiteParams p = site_params(P, nl, k);
+        if (k == SITE_STEM) {               // the stem kernel reads the raw f32 weights
+            if ((rc = copy(c.w, p.w, 64 * 18))) return rc;
+        } else {
+            if (k < site_enc_final(nl)) HRN_CHECK(p.w, -2, "hrn_hrnet_pack: null encoder weight %d", k - site_enc(0, 0));
+            else if (k == site_fres(nl, 0) || k == site_fres(nl, 1)) HRN_CHECK(p.w, -2, "hrn_hrnet_pack: null fuse weight %d", k - site_fres(nl, 0));
+            else HRN_CHECK(p.w, -2, "hrn_hrnet_pack: null weight pointer");
+            if ((rc = hrn_launch_conv_pack(dt, c.cin, c.cout, p.w, at(packed, c.w), s))) return rc;
+        }
+        if ((rc = copy(c.b, p.b, c.cout)) || (c.prelu && (rc = copy(c.a, p.a, 1)))) return rc;
     }
-    HRN_CHECK(P->enc_final_w && P->fuse_out_w && P->dec_w, -2, "hrn_hrnet_pack: null weight pointer");
-    if ((rc = hrn_launch_conv_pack(dt, 64, 64, P->enc_final_w, at(packed, L.encf_w), s))) return rc;
-    if ((rc = copy(L.encf_b, P->enc_final_b, 64))) return rc;
-    for (int i = 0; i < 2; ++i) {
-        HRN_CHECK(P->fuse_res_w[i], -2, "hrn_hrnet_pack: null fuse weight %d", i);
-        if ((rc = hrn_launch_conv_pack(dt, 128, 128, P->fuse_res_w[i], at(packed, L.fres_w[i]), s))) return rc;
-        if ((rc = copy(L.fres_b[i], P->fuse_res_b[i], 128)) || (rc = copy(L.fres_a[i], P->fuse_res_a[i], 1))) return rc;
-    }
-    if ((rc = hrn_launch_conv_pack(dt, 128, 64, P->fuse_out_w, at(packed, L.fout_w), s))) return rc;
-    if ((rc = copy(L.fout_b, P->fuse_out_b, 64)) || (rc = copy(L.fout_a, P->fuse_out_a, 1))) return rc;
+    HRN_CHECK(P->dec_w, -2, "hrn_hrnet_pack: null weight pointer");
     if ((rc = hrn_launch_decoder_pack(dt == HRN_BF16X3 ? HRN_F32 : dt, P->dec_w, at(packed, L.dec_w), s, scale))) return rc;     // bf16x3: the decoder is the fp32 one
     if ((rc = copy(L.dec_b, P->dec_b, 64)) || (rc = copy(L.dec_a, P->dec_a, 1))) return rc;
     if ((rc = copy(L.fin_w, P->fin_w, 64)) || (rc = copy(L.fin_b, P->fin_b, 1))) return rc;

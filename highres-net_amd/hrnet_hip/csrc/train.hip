@@ -31,10 +31,13 @@ struct TrainWs {
     size_t stack[TMAX + 1], t1[TMAX], u[TMAX], t2[TMAX], f[TMAX];
     size_t g[5];                            // backward: five gradient buffers of one full activation each
     size_t xpre;                            // backward: a recomputed pre-activation (used only behind a PReLU whose slope is <= 0)
-    size_t wt, wtp, zero_bias, scratch;
+    size_t wt, wtp, zero_bias, scratch, scratch_bytes;
     size_t dec_f, dec_g;                    // bf16 / bf16x3: f32 copies of the fused state and of its gradient (the decoder's backward is the fp32 kernel)
     size_t total;
 };
+
+// a fusion level's pair gather of its view stack (h pairs, partner of view v is last - v, vs views per sample); h == 0: a plain activation
+struct PairGather { int h, last, vs; };
 
 // bf16x3: a tensor of n elements is a pair of bf16 planes, the lo plane 2 n bytes behind the hi plane (0 for fp32 and bf16: one plane)
 inline size_t lo_of(int dt, size_t n) { return dt == HRN_BF16X3 ? n * 2 : 0; }
@@ -74,6 +77,7 @@ TrainWs train_ws(int nl, int B, int V, int H, int W) {
     const size_t sd = hrn_decoder_bwd_scratch_bytes(num_cus(), 4);
     if (sd > sc) sc = sd;
     w.scratch = take(sc);
+    w.scratch_bytes = sc;
     w.dec_f = take((size_t)B * hw * 64 * 4);
     w.dec_g = take((size_t)B * hw * 64 * 4);
     w.total = off;
@@ -97,19 +101,23 @@ int check_aligned(const char* fn, int dt, const void* pk, const void* tws) {
     return 0;
 }
 
-// y = conv3x3(x) (+ PReLU) on the forward f32 kernel
-int conv_fwd(int dt, int cin, int cout, const void* x, void* y, const void* wpk, const float* bias, const float* slope, int M, int H, int W,
-             hipStream_t s) {
+// y = conv3x3(x) (+ PReLU) of site c on the forward kernel; x is the activation `in`, or with pg.h > 0 the pair gather of the view stack
+// `in` (M / pg.h samples).  With `nonpos_slope` (the backward's recompute) y is the pre-activation, and the launch does nothing unless
+// that slope, read on the device, is <= 0 (ConvParams::only_if_nonpos)
+int conv_fwd(int dt, const void* pk, const ConvSite& c, const void* in, PairGather pg, void* y, int M, int H, int W, hipStream_t s,
+             const float* nonpos_slope = nullptr) {
+    const size_t hw = (size_t)H * W;
     ConvParams p = conv_base(M, H, W);
-    p.in = x; p.out = y; p.wpk = wpk; p.bias = bias; p.slope = slope;
-    p.in_lo = lo_of(dt, (size_t)M * H * W * cin); p.out_lo = lo_of(dt, (size_t)M * H * W * cout);
-    return hrn_launch_conv3x3(dt, cin, cout, p, s, false);
-}
-
-// dx = conv3x3(g, W^T flipped) (+ res): the data gradient of a cin -> cout convolution with raw weights w [cout][cin][3][3]
-int conv_dgrad(int dt, int cin, int cout, const float* w, const void* g, void* dx, const void* res, int M, int H, int W, void* tws,
-               const TrainWs& L, hipStream_t s) {
-    return hrn_conv_dgrad(dt, cin, cout, w, g, dx, res, M, H, W, (float*)at(tws, L.wt), at(tws, L.wtp), (const float*)at(tws, L.zero_bias), s);
+    if (pg.h > 0) {
+        p.in_pair = 1; p.stack = in; p.pair_h = pg.h; p.pair_last = pg.last; p.pair_vs = pg.vs;
+        p.stack_lo = lo_of(dt, (size_t)(M / pg.h) * pg.vs * hw * 64);
+    } else {
+        p.in = in; p.in_lo = lo_of(dt, (size_t)M * hw * c.cin);
+    }
+    p.out = y; p.out_lo = lo_of(dt, (size_t)M * hw * c.cout);
+    conv_site(p, pk, c);
+    if (nonpos_slope) { p.slope = nullptr; p.only_if_nonpos = nonpos_slope; }
+    return hrn_launch_conv3x3(dt, c.cin, c.cout, p, s, false);
 }
 
 // z + u for the pair gather z of a level: t2[b*half + i][p][c] = (c < 64 ? s_i : s_partner)[p][c % 64] + u[...]
@@ -170,21 +178,18 @@ int hrn_hrnet_backward_sel(const void* pk, int dt, int scale, const hrn_hrnet_pa
     const TrainWs L = train_ws(nl, B, V, H, W);
     HRN_CHECK(tws_bytes >= L.total, -3, "hrn_hrnet_backward: workspace too small (%zu < %zu)", tws_bytes, L.total);
     for (int t = 0; d_alphas && t < L.T; ++t)
-        HRN_CHECK(hrn_alpha_grad_scratch_bytes(B * (L.n_in[t] / 2)) <= L.dec_f - L.scratch, -3, "hrn_hrnet_backward_in: scratch too small for d_alphas");
+        HRN_CHECK(hrn_alpha_grad_scratch_bytes(B * (L.n_in[t] / 2)) <= L.scratch_bytes, -3, "hrn_hrnet_backward_in: scratch too small for d_alphas");
     // ---- what is needed
     auto want = [](const float* g) { return g != nullptr; };
-    auto want_prelu = [&](const float* w, const float* b, const float* a) { return want(w) || want(b) || want(a); };
+    auto want_site = [&](int k) { const SiteParams g = site_params(Gr, nl, k); return want(g.w) || want(g.b) || want(g.a); };
+    const int kF = site_enc_final(nl), kA = site_fres(nl, 0), kB = site_fres(nl, 1), kC = site_fout(nl);
     const bool dec = want(Gr->dec_w) || want(Gr->dec_b) || want(Gr->dec_a) || want(Gr->fin_w) || want(Gr->fin_b);
-    const bool fuse = want_prelu(Gr->fuse_res_w[0], Gr->fuse_res_b[0], Gr->fuse_res_a[0]) ||
-                      want_prelu(Gr->fuse_res_w[1], Gr->fuse_res_b[1], Gr->fuse_res_a[1]) ||
-                      want_prelu(Gr->fuse_out_w, Gr->fuse_out_b, Gr->fuse_out_a);
+    const bool wA = want_site(kA), wB = want_site(kB), wC = want_site(kC), fuse = wA || wB || wC;
     const bool alpha = d_alphas && alpha_residual;
     bool need_da[HRN_MAX_RES_LAYERS + 1], need_ds[TMAX + 1];
-    need_da[0] = want_prelu(Gr->enc_init_w, Gr->enc_init_b, Gr->enc_init_a) || d_lrs;
-    for (int l = 0; l < nl; ++l)
-        need_da[l + 1] = need_da[l] || want_prelu(Gr->enc_res_w[2 * l], Gr->enc_res_b[2 * l], Gr->enc_res_a[2 * l]) ||
-                         want_prelu(Gr->enc_res_w[2 * l + 1], Gr->enc_res_b[2 * l + 1], Gr->enc_res_a[2 * l + 1]);
-    need_ds[0] = need_da[nl] || want(Gr->enc_final_w) || want(Gr->enc_final_b);
+    need_da[0] = want_site(SITE_STEM) || d_lrs;
+    for (int l = 0; l < nl; ++l) need_da[l + 1] = need_da[l] || want_site(site_enc(l, 0)) || want_site(site_enc(l, 1));
+    need_ds[0] = need_da[nl] || want_site(kF);
     for (int t = 0; t < L.T; ++t) need_ds[t + 1] = need_ds[t] || fuse || alpha;
 
     hipStream_t s = (hipStream_t)stream;
@@ -199,44 +204,49 @@ int hrn_hrnet_backward_sel(const void* pk, int dt, int scale, const hrn_hrnet_pa
     if (!dec && !need_ds[L.T]) return 0;
     // gradients are handed over as mutable buffers in a params-shaped struct
     auto mut = [](const float* p) { return const_cast<float*>(p); };
-    // PReLU backward works from the stored post-activation while the slope is positive.  For a slope <= 0 (the reference allows any)
-    // the pre-activation is recomputed into `xpre` by the forward kernel without activation - a launch that does nothing unless the
-    // slope on the device says so (ConvParams::only_if_nonpos): no host round trip, ~3 us per PReLU in the usual case.
     const HrnetLayout P = hrnet_layout(dt, nl, scale);
     void* xpre = at(tws, L.xpre);
-    auto pre = [&](int cin, int cout, const void* x, const void* wpk, const float* bias, const float* slope, int Mi) -> int {
-        ConvParams q = conv_base(Mi, H, W);
-        q.in = x; q.out = xpre; q.wpk = wpk; q.bias = bias; q.only_if_nonpos = slope;
-        q.in_lo = lo_of(dt, (size_t)Mi * hw * cin); q.out_lo = lo_of(dt, (size_t)Mi * hw * cout);
-        return hrn_launch_conv3x3(dt, cin, cout, q, s, false);
+    // dx = conv3x3(g, W^T flipped) (+ res): the data gradient of site c's convolution, from its raw weights w [cout][cin][3][3]
+    auto conv_dgrad = [&](const ConvSite& c, const float* w, const void* g, void* dx, const void* res, int Mi) -> int {
+        return hrn_conv_dgrad(dt, c.cin, c.cout, w, g, dx, res, Mi, H, W, (float*)at(tws, L.wt), at(tws, L.wtp), (const float*)at(tws, L.zero_bias), s);
+    };
+    // The backward of y = PReLU(conv(x)) at site k, for Mi images; x is `in`, plain or with pg.h > 0 pair-gathered, as in conv_fwd.
+    //   prelu   gx = d pre-activation from g = d y (may alias), + the slope and bias gradients where wanted.  It works from the stored
+    //           post-activation y while the slope is positive; for a slope <= 0 (the reference allows any) the pre-activation is first
+    //           recomputed into `xpre` - a launch gated on the device: no host round trip, ~3 us per PReLU in the usual case
+    //   then the weight gradient where wanted, and with `dx` the data gradient dx = dgrad(gx) (+ res)
+    auto site_bwd = [&](int k, const void* in, PairGather pg, const void* y, const void* g, void* gx, int Mi, bool prelu, void* dx,
+                        const void* res) -> int {
+        const ConvSite& c = P.site[k];
+        const SiteParams p = site_params(Pr, nl, k), gr = site_params(Gr, nl, k);
+        if (prelu) {
+            if ((rc = conv_fwd(dt, pk, c, in, pg, xpre, Mi, H, W, s, p.a))) return rc;
+            if ((rc = hrn_launch_prelu_bwd_bias(dt, g, y, xpre, p.a, gx, (size_t)Mi * hw, c.cout, mut(gr.a), mut(gr.b), sc, s))) return rc;
+        }
+        if (want(gr.w) && (rc = hrn_launch_conv_wgrad(dt, pg.h ? nullptr : in, pg.h ? in : nullptr, pg.h > 0, pg.h, pg.last, pg.vs, gx, Mi, H, W,
+                                                      c.cin, c.cout, mut(gr.w), sc, cus, s)))
+            return rc;
+        return dx ? conv_dgrad(c, p.w, gx, dx, res, Mi) : 0;
     };
 
     // ---- decoder: d_sr -> d stack_T (one view left)                                  HRNet.py:147-156,167-169
     // (one launch gives the weight-gradient partials and d stack_T; its finish, which only sums the partials, runs for decoder parameters)
     void* dsn = G[0];                       // gradient of the views leaving the current level
-    if (dt != HRN_F32) {
-        // the decoder's backward is the fp32 kernel (33 MB of state at the training shape): the fused state as f32, its gradient back as planes
-        const size_t nf = (size_t)B * L.n_in[L.T] * hw * 64;
-        float* ff = (float*)at(tws, L.dec_f);
-        float* fg = (float*)at(tws, L.dec_g);
-        if ((rc = hrn_launch_planes_to_f32(at(tws, L.stack[L.T]), lo_of(dt, nf), ff, nf, s))) return rc;
-        if ((rc = hrn_launch_decoder_bwd(ff, d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, fg,
-                                         mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a), mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s,
-                                         scale)))
-            return rc;
-        if (need_ds[L.T] && (rc = hrn_launch_f32_to_planes(fg, dsn, lo_of(dt, nf), nf, s))) return rc;
-    } else if ((rc = hrn_launch_decoder_bwd((const float*)at(tws, L.stack[L.T]), d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, (float*)dsn,
-                                            mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a), mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s,
-                                            scale)))
-        return rc;
+    // the decoder's backward is the fp32 kernel (33 MB of state at the training shape): from planes, the fused state goes in as f32 and
+    // its gradient comes back as planes
+    const bool planes = dt != HRN_F32;
+    const size_t nf = (size_t)B * L.n_in[L.T] * hw * 64;
+    float* ff = (float*)at(tws, planes ? L.dec_f : L.stack[L.T]);
+    float* fg = planes ? (float*)at(tws, L.dec_g) : (float*)dsn;
+    if (planes && (rc = hrn_launch_planes_to_f32(at(tws, L.stack[L.T]), lo_of(dt, nf), ff, nf, s))) return rc;
+    if ((rc = hrn_launch_decoder_bwd(ff, d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, fg, mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a),
+                                     mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s, scale))) return rc;
+    if (planes && need_ds[L.T] && (rc = hrn_launch_f32_to_planes(fg, dsn, lo_of(dt, nf), nf, s))) return rc;
     if (!need_ds[L.T]) return 0;
 
     // ---- fusion levels, last to first                                                HRNet.py:113-132
     // below: the level's input gradient ds is read (a lower level or the encoder); each convolution's PReLU backward runs when its data
     // gradient or one of its own parameters is wanted, and its data gradient when the PReLU backward before it runs
-    const bool wA = want_prelu(Gr->fuse_res_w[0], Gr->fuse_res_b[0], Gr->fuse_res_a[0]);
-    const bool wB = want_prelu(Gr->fuse_res_w[1], Gr->fuse_res_b[1], Gr->fuse_res_a[1]);
-    const bool wC = want_prelu(Gr->fuse_out_w, Gr->fuse_out_b, Gr->fuse_out_a);
     for (int t = L.T - 1; t >= 0; --t) {
         const int n = L.n_in[t], half = n / 2, pair_last = n - (n & 1) - 1, Mh = B * half;
         const bool below = need_ds[t];
@@ -250,34 +260,15 @@ int hrn_hrnet_backward_sel(const void* pk, int dt, int scale, const hrn_hrnet_pa
         void* y2 = G[4];                   // gB, later dz       [Mh][hw][128]
         if (prC && (rc = hrn_launch_fuse_df(dt, dsn, alphas, V, pair_last, half, alpha_residual, x1, hw, B, s))) return rc;
         // x_new = alice + a_bob f: d a_bob = sum dsn f while both are live (the scratch is free until the PReLU backward below)
-        if (alpha && (rc = hrn_launch_alpha_grad(dt, dsn, at(tws, L.f[t]), half, pair_last, d_alphas, B, V, hw, sc, L.dec_f - L.scratch, s)))
+        if (alpha && (rc = hrn_launch_alpha_grad(dt, dsn, at(tws, L.f[t]), half, pair_last, d_alphas, B, V, hw, sc, L.scratch_bytes, s)))
             return rc;
         // f = PReLU(convC(t2))
-        if (prC) {
-            if ((rc = pre(128, 64, at(tws, L.t2[t]), at(pk, P.fout_w), (const float*)at(pk, P.fout_b), Pr->fuse_out_a, Mh))) return rc;
-            if ((rc = hrn_launch_prelu_bwd_bias(dt, x1, at(tws, L.f[t]), xpre, Pr->fuse_out_a, x1, (size_t)Mh * hw, 64, mut(Gr->fuse_out_a), mut(Gr->fuse_out_b), sc, s))) return rc;
-        }
-        if (want(Gr->fuse_out_w) && (rc = hrn_launch_conv_wgrad(dt, at(tws, L.t2[t]), nullptr, 0, 0, 0, 0, x1, Mh, H, W, 128, 64, mut(Gr->fuse_out_w), sc, cus, s))) return rc;
-        if (dgC && (rc = conv_dgrad(dt, 128, 64, Pr->fuse_out_w, x1, y1, nullptr, Mh, H, W, tws, L, s))) return rc;
+        if ((rc = site_bwd(kC, at(tws, L.t2[t]), {}, at(tws, L.f[t]), x1, x1, Mh, prC, dgC ? y1 : nullptr, nullptr))) return rc;
         // t2 = z + u, u = PReLU(convB(t1))
-        if (prB) {
-            if ((rc = pre(128, 128, at(tws, L.t1[t]), at(pk, P.fres_w[1]), (const float*)at(pk, P.fres_b[1]), Pr->fuse_res_a[1], Mh))) return rc;
-            if ((rc = hrn_launch_prelu_bwd_bias(dt, y1, at(tws, L.u[t]), xpre, Pr->fuse_res_a[1], y2, (size_t)Mh * hw, 128, mut(Gr->fuse_res_a[1]), mut(Gr->fuse_res_b[1]), sc, s))) return rc;
-        }
-        if (want(Gr->fuse_res_w[1]) && (rc = hrn_launch_conv_wgrad(dt, at(tws, L.t1[t]), nullptr, 0, 0, 0, 0, y2, Mh, H, W, 128, 128, mut(Gr->fuse_res_w[1]), sc, cus, s))) return rc;
-        if (prA && (rc = conv_dgrad(dt, 128, 128, Pr->fuse_res_w[1], y2, y3, nullptr, Mh, H, W, tws, L, s))) return rc;
-        // t1 = PReLU(convA(z))
-        if (prA) {
-            ConvParams q = conv_base(Mh, H, W);
-            q.in_pair = 1; q.stack = st; q.pair_h = half; q.pair_last = pair_last; q.pair_vs = n;
-            q.out = xpre; q.wpk = at(pk, P.fres_w[0]); q.bias = (const float*)at(pk, P.fres_b[0]); q.only_if_nonpos = Pr->fuse_res_a[0];
-            q.stack_lo = lo_of(dt, (size_t)B * n * hw * 64); q.out_lo = lo_of(dt, (size_t)Mh * hw * 128);
-            if ((rc = hrn_launch_conv3x3(dt, 128, 128, q, s, false))) return rc;
-            if ((rc = hrn_launch_prelu_bwd_bias(dt, y3, at(tws, L.t1[t]), xpre, Pr->fuse_res_a[0], y3, (size_t)Mh * hw, 128, mut(Gr->fuse_res_a[0]), mut(Gr->fuse_res_b[0]), sc, s))) return rc;
-        }
-        if (want(Gr->fuse_res_w[0]) && (rc = hrn_launch_conv_wgrad(dt, nullptr, st, 1, half, pair_last, n, y3, Mh, H, W, 128, 128, mut(Gr->fuse_res_w[0]), sc, cus, s))) return rc;
+        if ((rc = site_bwd(kB, at(tws, L.t1[t]), {}, at(tws, L.u[t]), y1, y2, Mh, prB, prA ? y3 : nullptr, nullptr))) return rc;
+        // t1 = PReLU(convA(z));  dz = d t2 + dgradA(gA)
+        if ((rc = site_bwd(kA, st, {half, pair_last, n}, at(tws, L.t1[t]), y3, y3, Mh, prA, below ? y2 : nullptr, y1))) return rc;
         if (!below) continue;               // (then no level below and not the encoder reads ds: the levels left run only their alpha_grad)
-        if ((rc = conv_dgrad(dt, 128, 128, Pr->fuse_res_w[0], y3, y2, y1, Mh, H, W, tws, L, s))) return rc;     // dz = d t2 + dgradA(gA)
         // dz -> the two views of each pair (+ the alice pass-through)
         if ((rc = hrn_launch_fuse_scatter(dt, dsn, y2, n, half, pair_last, alpha_residual, ds, hw, B, s))) return rc;
         void* tmp = G[0]; G[0] = G[1]; G[1] = tmp;
@@ -287,39 +278,31 @@ int hrn_hrnet_backward_sel(const void* pk, int dt, int scale, const hrn_hrnet_pa
 
     // ---- encoder                                                                     HRNet.py:51-60,62-74
     void* dA = G[1];
-    if (want(Gr->enc_final_w) && (rc = hrn_launch_conv_wgrad(dt, at(tws, L.a[nl]), nullptr, 0, 0, 0, 0, dsn, M, H, W, 64, 64, mut(Gr->enc_final_w), sc, cus, s))) return rc;
-    if (want(Gr->enc_final_b) && (rc = hrn_launch_colsum(dt, dsn, (size_t)M * hw, 64, mut(Gr->enc_final_b), sc, s))) return rc;
+    const SiteParams gF = site_params(Gr, nl, kF);
+    if (want(gF.w) && (rc = hrn_launch_conv_wgrad(dt, at(tws, L.a[nl]), nullptr, 0, 0, 0, 0, dsn, M, H, W, 64, 64, mut(gF.w), sc, cus, s))) return rc;
+    if (want(gF.b) && (rc = hrn_launch_colsum(dt, dsn, (size_t)M * hw, 64, mut(gF.b), sc, s))) return rc;
     if (!need_da[nl]) return 0;
-    if ((rc = conv_dgrad(dt, 64, 64, Pr->enc_final_w, dsn, dA, nullptr, M, H, W, tws, L, s))) return rc;
+    if ((rc = conv_dgrad(P.site[kF], site_params(Pr, nl, kF).w, dsn, dA, nullptr, M))) return rc;
     void* e2 = G[2];
     void* e3 = G[3];
     for (int l = nl - 1; l >= 0; --l) {
         // a_{l+1} = a_l + r_l,  r_l = PReLU(conv2(h_l)),  h_l = PReLU(conv1(a_l));  d a_{l+1} (dA) is wanted here
-        const int j1 = 2 * l, j2 = 2 * l + 1;
-        const bool pr1 = need_da[l] || want_prelu(Gr->enc_res_w[j1], Gr->enc_res_b[j1], Gr->enc_res_a[j1]);
-        const bool pr2 = pr1 || want_prelu(Gr->enc_res_w[j2], Gr->enc_res_b[j2], Gr->enc_res_a[j2]);
-        if (pr2) {
-            if ((rc = pre(64, 64, at(tws, L.h[l]), at(pk, P.enc_w[j2]), (const float*)at(pk, P.enc_b[j2]), Pr->enc_res_a[j2], M))) return rc;
-            if ((rc = hrn_launch_prelu_bwd_bias(dt, dA, at(tws, L.r[l]), xpre, Pr->enc_res_a[j2], e2, (size_t)M * hw, 64, mut(Gr->enc_res_a[j2]), mut(Gr->enc_res_b[j2]), sc, s))) return rc;
-        }
-        if (want(Gr->enc_res_w[j2]) && (rc = hrn_launch_conv_wgrad(dt, at(tws, L.h[l]), nullptr, 0, 0, 0, 0, e2, M, H, W, 64, 64, mut(Gr->enc_res_w[j2]), sc, cus, s))) return rc;
-        if (pr1) {
-            if ((rc = conv_dgrad(dt, 64, 64, Pr->enc_res_w[j2], e2, e3, nullptr, M, H, W, tws, L, s))) return rc;
-            if ((rc = pre(64, 64, at(tws, L.a[l]), at(pk, P.enc_w[j1]), (const float*)at(pk, P.enc_b[j1]), Pr->enc_res_a[j1], M))) return rc;
-            if ((rc = hrn_launch_prelu_bwd_bias(dt, e3, at(tws, L.h[l]), xpre, Pr->enc_res_a[j1], e3, (size_t)M * hw, 64, mut(Gr->enc_res_a[j1]), mut(Gr->enc_res_b[j1]), sc, s))) return rc;
-        }
-        if (want(Gr->enc_res_w[j1]) && (rc = hrn_launch_conv_wgrad(dt, at(tws, L.a[l]), nullptr, 0, 0, 0, 0, e3, M, H, W, 64, 64, mut(Gr->enc_res_w[j1]), sc, cus, s))) return rc;
+        const int k1 = site_enc(l, 0), k2 = site_enc(l, 1);
+        const bool pr1 = need_da[l] || want_site(k1), pr2 = pr1 || want_site(k2);
+        if ((rc = site_bwd(k2, at(tws, L.h[l]), {}, at(tws, L.r[l]), dA, e2, M, pr2, pr1 ? e3 : nullptr, nullptr))) return rc;
+        if ((rc = site_bwd(k1, at(tws, L.a[l]), {}, at(tws, L.h[l]), e3, e3, M, pr1, need_da[l] ? e2 : nullptr, dA))) return rc;
         if (!need_da[l]) return 0;
-        if ((rc = conv_dgrad(dt, 64, 64, Pr->enc_res_w[j1], e3, e2, dA, M, H, W, tws, L, s))) return rc;       // d a_l = d a_{l+1} + dgrad1(g1)
-        void* tmp = dA; dA = e2; e2 = tmp;
+        void* tmp = dA; dA = e2; e2 = tmp;       // d a_l = d a_{l+1} + dgrad1(g1)
     }
     // stem: a_0 = PReLU(conv(cat(view, reference frame)))                               HRNet.py:200-204, :51-53
-    if ((rc = hrn_launch_stem_pre(dt, lrs, hw, (const float*)at(tws, L.ref), V, hw, (const float*)at(pk, P.stem_w), (const float*)at(pk, P.stem_b), xpre, M, H, W,
-                                  Pr->enc_init_a, s))) return rc;
-    if ((rc = hrn_launch_prelu_bwd_bias(dt, dA, at(tws, L.a[0]), xpre, Pr->enc_init_a, dA, (size_t)M * hw, 64, mut(Gr->enc_init_a), mut(Gr->enc_init_b), sc, s))) return rc;
-    if (want(Gr->enc_init_w) && (rc = hrn_launch_stem_wgrad(dt, lrs, hw, (const float*)at(tws, L.ref), V, hw, dA, M, H, W, mut(Gr->enc_init_w), sc, cus, s))) return rc;
+    const ConvSite& stem = P.site[SITE_STEM];
+    const SiteParams pS = site_params(Pr, nl, SITE_STEM), gS = site_params(Gr, nl, SITE_STEM);
+    if ((rc = hrn_launch_stem_pre(dt, lrs, hw, (const float*)at(tws, L.ref), V, hw, (const float*)at(pk, stem.w), (const float*)at(pk, stem.b), xpre, M, H, W,
+                                  pS.a, s))) return rc;
+    if ((rc = hrn_launch_prelu_bwd_bias(dt, dA, at(tws, L.a[0]), xpre, pS.a, dA, (size_t)M * hw, 64, mut(gS.a), mut(gS.b), sc, s))) return rc;
+    if (want(gS.w) && (rc = hrn_launch_stem_wgrad(dt, lrs, hw, (const float*)at(tws, L.ref), V, hw, dA, M, H, W, mut(gS.w), sc, cus, s))) return rc;
     // d lrs: the stem's input gradient, channel 1 (the reference frame) routed to the view the median picked
-    if (d_lrs) return hrn_launch_stem_dgrad_route(dt, dA, Pr->enc_init_w, (float*)at(tws, L.wt), lrs, (const float*)at(tws, L.ref), d_lrs, B, V, H, W, s);
+    if (d_lrs) return hrn_launch_stem_dgrad_route(dt, dA, pS.w, (float*)at(tws, L.wt), lrs, (const float*)at(tws, L.ref), d_lrs, B, V, H, W, s);
     return 0;
 }
 
@@ -339,31 +322,22 @@ int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alp
     const int M = B * V;
     float* ref = (float*)at(tws, L.ref);
     if ((rc = hrn_launch_median(lrs, ref, B, V, H, W, s))) return rc;
-    if ((rc = hrn_launch_stem(dt, lrs, hw, ref, V, hw, nullptr, (const float*)at(pk, P.stem_w), (const float*)at(pk, P.stem_b),
-                              (const float*)at(pk, P.stem_a), at(tws, L.a[0]), M, H, W, s, lo_of(dt, (size_t)M * hw * 64)))) return rc;
+    const ConvSite& stem = P.site[SITE_STEM];
+    if ((rc = hrn_launch_stem(dt, lrs, hw, ref, V, hw, nullptr, (const float*)at(pk, stem.w), (const float*)at(pk, stem.b),
+                              (const float*)at(pk, stem.a), at(tws, L.a[0]), M, H, W, s, lo_of(dt, (size_t)M * hw * 64)))) return rc;
     for (int l = 0; l < nl; ++l) {
-        if ((rc = conv_fwd(dt, 64, 64, at(tws, L.a[l]), at(tws, L.h[l]), at(pk, P.enc_w[2 * l]), (const float*)at(pk, P.enc_b[2 * l]),
-                           (const float*)at(pk, P.enc_a[2 * l]), M, H, W, s))) return rc;
-        if ((rc = conv_fwd(dt, 64, 64, at(tws, L.h[l]), at(tws, L.r[l]), at(pk, P.enc_w[2 * l + 1]), (const float*)at(pk, P.enc_b[2 * l + 1]),
-                           (const float*)at(pk, P.enc_a[2 * l + 1]), M, H, W, s))) return rc;
+        if ((rc = conv_fwd(dt, pk, P.site[site_enc(l, 0)], at(tws, L.a[l]), {}, at(tws, L.h[l]), M, H, W, s))) return rc;
+        if ((rc = conv_fwd(dt, pk, P.site[site_enc(l, 1)], at(tws, L.h[l]), {}, at(tws, L.r[l]), M, H, W, s))) return rc;
         if ((rc = hrn_launch_add(dt, at(tws, L.a[l]), at(tws, L.r[l]), at(tws, L.a[l + 1]), (size_t)M * hw * 64, s))) return rc;
     }
-    if ((rc = conv_fwd(dt, 64, 64, at(tws, L.a[nl]), at(tws, L.stack[0]), at(pk, P.encf_w), (const float*)at(pk, P.encf_b), nullptr, M, H, W, s)))
-        return rc;
+    if ((rc = conv_fwd(dt, pk, P.site[site_enc_final(nl)], at(tws, L.a[nl]), {}, at(tws, L.stack[0]), M, H, W, s))) return rc;
     for (int t = 0; t < L.T; ++t) {
         const int n = L.n_in[t], half = n / 2, pair_last = n - (n & 1) - 1;
         const void* st = at(tws, L.stack[t]);
-        ConvParams a = conv_base(B * half, H, W);
-        a.in_pair = 1; a.stack = st; a.pair_h = half; a.pair_last = pair_last; a.pair_vs = n;
-        a.out = at(tws, L.t1[t]);
-        a.stack_lo = lo_of(dt, (size_t)B * n * hw * 64); a.out_lo = lo_of(dt, (size_t)B * half * hw * 128);
-        a.wpk = at(pk, P.fres_w[0]); a.bias = (const float*)at(pk, P.fres_b[0]); a.slope = (const float*)at(pk, P.fres_a[0]);
-        if ((rc = hrn_launch_conv3x3(dt, 128, 128, a, s, false))) return rc;
-        if ((rc = conv_fwd(dt, 128, 128, at(tws, L.t1[t]), at(tws, L.u[t]), at(pk, P.fres_w[1]), (const float*)at(pk, P.fres_b[1]),
-                           (const float*)at(pk, P.fres_a[1]), B * half, H, W, s))) return rc;
+        if ((rc = conv_fwd(dt, pk, P.site[site_fres(nl, 0)], st, {half, pair_last, n}, at(tws, L.t1[t]), B * half, H, W, s))) return rc;
+        if ((rc = conv_fwd(dt, pk, P.site[site_fres(nl, 1)], at(tws, L.t1[t]), {}, at(tws, L.u[t]), B * half, H, W, s))) return rc;
         if ((rc = hrn_launch_pair_add(dt, st, n, half, pair_last, at(tws, L.u[t]), at(tws, L.t2[t]), hw, B, s))) return rc;
-        if ((rc = conv_fwd(dt, 128, 64, at(tws, L.t2[t]), at(tws, L.f[t]), at(pk, P.fout_w), (const float*)at(pk, P.fout_b),
-                           (const float*)at(pk, P.fout_a), B * half, H, W, s))) return rc;
+        if ((rc = conv_fwd(dt, pk, P.site[site_fout(nl)], at(tws, L.t2[t]), {}, at(tws, L.f[t]), B * half, H, W, s))) return rc;
         if ((rc = hrn_launch_fuse_update(dt, st, n, at(tws, L.f[t]), alphas, V, pair_last, half, alpha_residual,
                                          at(tws, L.stack[t + 1]), hw, B, s))) return rc;
     }

@@ -176,3 +176,31 @@ def test_reader_refuses_what_it_does_not_know(tmp_path):
 def test_every_hook_is_exported(lib):
     for name in kt.SIGNATURES:
         assert hasattr(lib, name), f"{name} is in kt.SIGNATURES but not exported"
+
+
+# ----------------------------------------------------------------------------- the parameter table against the module and the struct
+@pytest.mark.parametrize("num_layers", range(9))
+def test_param_table_keys_are_the_modules_parameters(num_layers):
+    import copy
+    from hrnet_hip import binding
+    from oracle import weights
+    from DeepNetworks.HRNet import HRNet
+    cfg = copy.deepcopy(weights.HRNET_CONFIG)
+    cfg["encoder"]["num_layers"] = num_layers
+    keys = [k for k, _ in HRNet(cfg).named_parameters()]
+    assert [k for k, _, _ in binding.hrnet_param_table(num_layers)] == keys
+    assert binding.hrnet_param_names(num_layers) == keys
+
+
+def test_param_table_covers_every_pointer_of_the_struct_once():
+    from hrnet_hip import binding
+    assert binding.MAX_RES_LAYERS == 8
+    slots = []
+    for name, ctype in binding.HrnetParams._fields_:
+        if ctype is ctypes.c_void_p:
+            slots.append((name, None))
+        elif issubclass(ctype, ctypes.Array):
+            slots += [(name, i) for i in range(ctype._length_)]
+    assert len(slots) == 3 + 3 * 16 + 2 + 3 * 2 + 3 + 5
+    pairs = [(f, i) for _, f, i in binding.hrnet_param_table(8)]
+    assert len(set(pairs)) == len(pairs) and sorted(pairs, key=str) == sorted(slots, key=str)
