@@ -62,15 +62,20 @@ __global__ __launch_bounds__(256) void shift_cpsnr_kernel(const float* __restric
     const float* hr = hrs + (size_t)blockIdx.y * n;
     const float* mp = maps + (size_t)blockIdx.y * n;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    bool bad = false;                                             // a NaN pixel of sr that the clamp would hide
     for (int i = threadIdx.x; i < size * size; i += blockDim.x) {
         const int y = i / size, x = i - y * size;
         float s = sr[(size_t)(y + border) * S + (x + border)];
-        if (clip) s = fminf(fmaxf(s, 0.f), 1.f);                  // np.clip(sr, 0, 1) at the call sites (predict.py:43, train.py:212)
+        if (clip) {                                               // np.clip(sr, 0, 1) at the call sites (predict.py:43, train.py:212)
+            bad |= s != s;                                        // np.clip keeps NaN; fminf / fmaxf turn it into 0
+            s = fminf(fmaxf(s, 0.f), 1.f);
+        }
         const size_t j = (size_t)(y + u) * S + (x + v);
         const double m = (double)mp[j];
         const double d = (double)hr[j] - (double)s;              // Evaluator.py:35 diff = hr - sr
         s0 += m; s1 += m * d; s2 += m * m * d * d;               // :37 squares (diff - bias) * map
     }
+    if (bad) s2 = __longlong_as_double(0x7ff8000000000000LL);     // the score of a frame that holds NaN is NaN, clipped or not
     s0 = block_sum(s0, red); s1 = block_sum(s1, red); s2 = block_sum(s2, red);
     // sum ((d - b) m)^2 with b = S1 / S0 needs sum m^2 d and sum m^2 too for non-binary maps; status maps are binary
     // (m^2 == m), for which it equals S2 - S1^2 / S0
@@ -84,7 +89,10 @@ __global__ void shift_max_kernel(const double* __restrict__ scores, int nshift, 
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     double best = scores[(size_t)b * nshift];
-    for (int i = 1; i < nshift; ++i) best = fmax(best, scores[(size_t)b * nshift + i]);
+    for (int i = 1; i < nshift; ++i) {                            // np.max: a NaN score makes the maximum NaN (fmax would drop it)
+        const double s = scores[(size_t)b * nshift + i];
+        best = (s > best || s != s) ? s : best;
+    }
     out[b] = (float)best;
 }
 

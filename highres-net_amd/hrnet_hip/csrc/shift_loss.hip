@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void shift_loss_partial_kernel(const float* __
             const int y = y0 + ly + 8 * r, x = x0 + 4 * lx + j;
             const bool in = y < h && x < w;
             float t = in ? sr[(size_t)(y + BETA) * W + (x + BETA)] : 0.f;
-            if (clip) t = fminf(fmaxf(t, 0.f), 1.f);
+            if (clip) t = t != t ? t : fminf(fmaxf(t, 0.f), 1.f);       // torch.clamp keeps NaN; fminf / fmaxf alone turn it into 0
             s[r][j] = t;
             valid |= (unsigned)in << (4 * r + j);
         }

@@ -1,6 +1,7 @@
 """The conventions of the per-element kernel tests (tests/test_gpu_kernels_fwd.py, test_gpu_kernels_bwd.py, test_gpu_kernels_shiftnet.py,
-test_gpu_bf16_train.py, test_gpu_shiftnet_bf16.py): the bound |got - want| <= rounding + C T with its one constant C (and C_F32, the
-measured bound of the fp32 forward kernels), the sentinel patterns, the tensor builders whose values make a kernel's products exact, and
+test_gpu_bf16_train.py, test_gpu_shiftnet_bf16.py, test_gpu_kernels_tail.py): the bound |got - want| <= rounding + C T with its one constant
+C (and C_F32 / C_TAIL, the measured bounds of the fp32 forward kernels and of the registered tail's fp32 kernels; the derived bounds of
+the tail's fp64 reductions), the sentinel patterns, the tensor builders whose values make a kernel's products exact, and
 the shapes and launcher grids the tests share."""
 import numpy as np
 import torch
@@ -367,3 +368,100 @@ class Big:
 
     def all_sentinels(self):
         return bool((self.raw == SENT).all())
+
+
+# ----------------------------------------------------------------------------------------------------------- the registered tail
+# tests/test_gpu_kernels_tail.py (GPU) and tests/test_kernels_tail_host.py (CPU): the Lanczos shift, its backward, the loss and score kernels.
+# The fp32 kernels (taps, shift, adjoint, tap gradient, loss_backward_kernel) are held to c T like every other family; the kernels that
+# accumulate in fp64 (masked_cmse, loss_partial + loss_finish, shift_cpsnr) to a derived bound with no constant in it:
+#   a double they store (stats, per-shift scores)   |got - want| <= n 2^-52 T          n = the pixels summed, T = sum |terms| of the value
+#   cMSE = (S2 - S1^2 / S0) / S0                     T = (S2 + S1^2 / S0) / S0
+#   cPSNR = -10 log10 cMSE                           (10 / ln 10) e / (cMSE - e), e = cMSE's bound: the mean-value form of 10 / (ln 10 cMSE);
+#                                                    where cMSE <= 2 e (a window whose cMSE lies within rounding of zero) no cPSNR is determined
+#   a float they store                               + 2^-23 |want| for the store and the log10
+U64 = 2.0 ** -52
+U32 = 2.0 ** -23
+# The fp32 kernels of the tail are held to |got - want| <= C_TAIL T, made the way C_F32 was: four times the largest "C needed" any case of
+# tests/test_gpu_kernels_tail.py measured on the MI355X against fp64, rounded up to one significant digit.  Measured per family (largest,
+# with its case): taps 3.30e-8 at test_taps[63]; lanczos_shift 1.07e-8 at test_lanczos_shift[38x134-b2c3]; d_img 9.76e-9 at
+# test_lanczos_shift_backward[5x64-b2c3]; d_shift 3.6e-10 at test_lanczos_shift_backward[7x9-b2c3]; d_srs 1.59e-7 at
+# test_get_loss_train_and_backward[65-0-B65-mixed-cMSE] (coef, the bias and three operations: 2.7 roundings of float32).  The largest is
+# below C / 4, so the family has its own constant: 4 x 1.59e-7 = 6.4e-7 -> 7e-7.  The float32 restatement of
+# tests/test_kernels_tail_host.py needs 3.3e-8 / 1.1e-8 / 1.3e-8 / 1.1e-9 / 1.6e-7 on the CPU.  The taps' own error inside the Lanczos
+# bounds is e = C_TAIL T_j as well.  C stays the ceiling: C_TAIL <= C.
+C_TAIL = 7e-7
+TAIL_MEASURED = (1.59e-7, "test_get_loss_train_and_backward[65-0-B65-mixed-cMSE]")      # (largest C needed, the id of its case)
+
+
+def cmse_bound(n, S0, S1, S2):
+    """the bound of a cMSE whose three sums run over n pixels in fp64"""
+    return n * U64 * (S2 + S1 * S1 / S0) / S0
+
+
+def cpsnr_bound(cmse, e):
+    """cMSE's bound e carried through -10 log10; inf where cMSE <= 2 e"""
+    ok = cmse > 2 * e
+    return torch.where(ok, (10.0 / np.log(10.0)) * e / torch.where(ok, cmse - e, torch.ones_like(cmse)), torch.full_like(cmse, float("inf")))
+
+
+def _assert_within(tag, got, want, bound, layout="i"):
+    """|got - want| <= bound per element, for bounds that are not C T.  Where want is NaN or +-inf, got must be the same; where the bound is
+    inf (and want finite) anything passes: the value is not determined.  -> max error / bound"""
+    got, want, bound = got.double(), want.double(), bound.double().expand_as(want)
+    odd = ~torch.isfinite(want)
+    same = torch.where(torch.isnan(want), torch.isnan(got), got == want)
+    assert bool(same[odd].all()), (f"{tag}: want {want[odd][~same[odd]][:4].tolist()}, got {got[odd][~same[odd]][:4].tolist()} at "
+                                   f"({layout}) = {torch.nonzero(odd & ~same)[:4].tolist()}")
+    free = odd | torch.isinf(bound)
+    z = torch.zeros_like(want)
+    g, w, b = torch.where(free, z, got), torch.where(free, z, want), torch.where(free, z + 1, bound)
+    assert bool(torch.isfinite(g).all()), f"{tag}: got a non-finite value at ({layout}) = {torch.nonzero(~torch.isfinite(g))[:4].tolist()}"
+    return _assert_close(tag, "f32", g, w, b, layout=layout, c=1.0)
+
+
+def _within_ratio(got, want, bound):
+    """max |got - want| / bound over the elements whose want and bound are finite (a class mismatch counts as inf)"""
+    got, want, bound = got.double(), want.double(), bound.double().expand_as(want)
+    odd = ~torch.isfinite(want)
+    same = torch.where(torch.isnan(want), torch.isnan(got), got == want)
+    if not bool(same[odd].all()):
+        return float("inf")
+    use = ~(odd | torch.isinf(bound))
+    r = (got[use] - want[use]).abs() / (bound[use] + 1e-300)
+    r = torch.where(torch.isnan(r), torch.full_like(r, float("inf")), r)
+    return float(r.max()) if r.numel() else 0.0
+
+
+class Guarded:
+    """`shape` elements of `dtype` (float32 / float64) for a kernel to write, inside a device buffer of sentinel bytes: GUARD words in front
+    (the kernel gets an offset pointer) and behind.  v: the start values (CPU); otherwise every payload byte is `fill` (0x7F: the sentinel;
+    0xFF: NaN in both types, for what a kernel must not read)."""
+
+    def __init__(self, shape, dtype=torch.float32, v=None, fill=SENT & 0xFF):
+        self.shape, self.dtype = tuple(shape), dtype
+        self.n = int(np.prod(shape))
+        self.front = 2 * GUARD                                  # bytes; a multiple of 8
+        self.nbytes = self.n * torch.empty((), dtype=dtype).element_size()
+        raw = torch.full((self.front + self.nbytes + 2 * GUARD,), SENT & 0xFF, dtype=torch.uint8)
+        if v is not None:
+            raw[self.front:self.front + self.nbytes] = v.to(dtype).contiguous().reshape(-1).view(torch.uint8)
+        else:
+            raw[self.front:self.front + self.nbytes] = fill
+        self.raw = raw.cuda()
+
+    @property
+    def ptr(self):
+        import ctypes
+        return ctypes.c_void_p(self.raw.data_ptr() + self.front)
+
+    def bits(self):
+        """the payload's bytes on the CPU (to compare two runs bit for bit)"""
+        return self.raw[self.front:self.front + self.nbytes].cpu()
+
+    def get(self):
+        """the payload on the CPU, in its own type"""
+        return self.bits().view(self.dtype).reshape(self.shape)
+
+    def guard_ok(self):
+        r = self.raw.cpu()
+        return bool((r[:self.front] == (SENT & 0xFF)).all()) and bool((r[self.front + self.nbytes:] == (SENT & 0xFF)).all())

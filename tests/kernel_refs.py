@@ -707,3 +707,428 @@ def _adam_p_ratio(r, **wrong):
     """p' against the fp64 formula on the m', v' the kernel stored: 2^-24 max(|got|, |want|) + C |update|"""
     _, _, _, _, want, upd = ref_adam(*r["ins"], *r["hyper"], m_new=r["m"], v_new=r["v"], **wrong)
     return (r["p"] - want).abs() / (2.0 ** -24 * torch.maximum(r["p"].abs(), want.abs()) + C * upd + 1e-300)
+
+
+# ----------------------------------------------------------------------------------------------------------- the registered tail
+# The Lanczos shift and its backward (csrc/lanczos.hip, lanczos_bwd.hip) and the loss / score kernels (csrc/losses.hip): the definitions in
+# fp64, the inputs, the cases and the checks that tests/test_gpu_kernels_tail.py runs on the GPU's outputs and
+# tests/test_kernels_tail_host.py on a float32 restatement's.  A `k` below is either of the two: an object whose methods taps, shift,
+# shift_bwd, get_loss, loss_train, loss_bwd and shift_cpsnr take CPU float32 tensors and return what the kernels wrote, on the CPU.
+from kernel_bounds import C_TAIL, U32, U64, _assert_close, _assert_within, _ratio, _within_ratio, cmse_bound, cpsnr_bound   # noqa: E402
+
+D64 = torch.float64
+PI32 = float(np.float32(np.pi))             # the kernels' pi: float32(pi), here widened to fp64
+
+
+def _tap_t(d, freeze="where"):
+    """t = pi ((j - 3) - d), (n, 7), and the mask of the taps held constant.  freeze: "where" - the definition: t == 0 is replaced by 1e-6
+    through a where, so that tap passes no gradient; "live" - 1e-6 is added instead, the tap keeps its gradient; "centre" - the wrong
+    variant that holds the centre tap j = 3 constant instead of the t == 0 tap"""
+    j = torch.arange(7, dtype=D64) - 3
+    t = PI32 * (j[None, :] - d.reshape(-1, 1))
+    hit = t == 0
+    if freeze == "where":
+        return torch.where(hit, torch.full_like(t, 1e-6), t), hit
+    t = t + 1e-6 * hit
+    if freeze == "live":
+        return t, torch.zeros_like(hit)
+    centre = (j == 0)[None, :].expand_as(t)
+    return torch.where(centre, t.detach(), t), centre
+
+
+def ref_taps(d, freeze="where"):
+    """d (n,) fp64 -> k (n, 7) = u / sum u, u = sinc(t) sinc(t / 3), and T_j = (1 + 7 |k_j|) / |sum u|: t is rounded to fp32 before the sine,
+    so every u_j carries an ABSOLUTE error e of order 2^-24, and k_j = u_j / s one of (e + |k_j| 7 e) / |s|"""
+    t, _ = _tap_t(d, freeze)
+    u = torch.sin(t) / t * (torch.sin(t / 3) / (t / 3))
+    s = u.sum(1, keepdim=True)
+    k = u / s
+    return k, ((1 + 7 * k.abs()) / s.abs()).detach()
+
+
+def ref_tap_grad(d):
+    """d (n,) fp64 -> dk_j / dd (n, 7) in closed form (the host test holds it to autograd's) and T of it.  With A = sinc t, B = sinc t/3:
+    du = -pi (A' B + A B'), A' = (t cos t - sin t) / t^2, 0 for a frozen tap.  t is rounded to fp32 before the sine and the cosine, so
+    each of A, B, A', B' carries an absolute error e of the order of one rounding besides its relative ones, T(A) = |A| + 1 and
+    T(A') = Ta' + 1 with Ta' = A' on absolute values (that difference cancels for small |t|: T is large, the bound loose, at a shift
+    close to but not on an integer); T_du = pi [2 Ta' |B| + |B| + Ta' + 2 |A| Tb' + |A| + Tb'].  dk = du / s - k ds / s, whose error with
+    e on every u, 7 e on s, e T_j on k is
+      e [ T_du / |s| + 7 |du| / s^2 + T_j |ds| / |s| + |k| sum T_du / |s| + 7 |k| |ds| / s^2 + 2 (|du| / |s| + |k| |ds| / |s|) ]
+    (the last term: the roundings of (du s - u ds) / s^2 itself)"""
+    t, hit = _tap_t(d.detach())
+    t3 = t / 3
+    A, B = torch.sin(t) / t, torch.sin(t3) / t3
+    dA, dB = (torch.cos(t) * t - torch.sin(t)) / t ** 2, (torch.cos(t3) * t3 - torch.sin(t3)) / t3 ** 2 / 3
+    dAa = (torch.cos(t).abs() * t.abs() + torch.sin(t).abs()) / t ** 2
+    dBa = (torch.cos(t3).abs() * t3.abs() + torch.sin(t3).abs()) / t3 ** 2 / 3
+    zero = torch.zeros_like(t)
+    du = torch.where(hit, zero, -PI32 * (dA * B + A * dB))
+    dua = torch.where(hit, zero, PI32 * (2 * dAa * B.abs() + B.abs() + dAa + 2 * A.abs() * dBa + A.abs() + dBa))
+    u = A * B
+    s, ds = u.sum(1, keepdim=True), du.sum(1, keepdim=True)
+    k, sa = u / s, s.abs()
+    Tj = (1 + 7 * k.abs()) / sa
+    Tdk = (dua / sa + 7 * du.abs() / s ** 2 + Tj * ds.abs() / sa + k.abs() * dua.sum(1, keepdim=True) / sa + 7 * k.abs() * ds.abs() / s ** 2
+           + 2 * (du.abs() / sa + k.abs() * ds.abs() / sa))
+    return (du * s - u * ds) / s ** 2, Tdk
+
+
+def shift_with_taps(img, ky, kx, edge="reflect"):
+    """P = pad-3(img) (reflection without edge repeat); out[y][x] = sum_n kx[n] sum_m ky[m] P[y + m][x + n]: vertical, then horizontal.
+    img (b, c, H, W), ky / kx (b, c, 7).  edge = "replicate": the wrong border"""
+    H, W = img.shape[2:]
+    P = F.pad(img, (3, 3, 3, 3), mode=edge)
+    V = sum(ky[:, :, m, None, None] * P[:, :, m:m + H, :] for m in range(7))
+    return sum(kx[:, :, n, None, None] * V[:, :, :, n:n + W] for n in range(7))
+
+
+def _plane_rows(b, c, by_plane=False):
+    """the row of `shift` each plane (b, c) takes: plane % C; by_plane: the plane's running number instead (folded into the table)"""
+    p = torch.arange(b * c)
+    return (p // b if by_plane else p % c).reshape(b, c)
+
+
+def ref_lanczos_shift(img, shift, edge="reflect", swap=False, by_plane=False, freeze="where"):
+    """img (b, c, H, W), shift (c, 2) = (dy, dx) per channel, fp64 torch: d_img and d_shift come from autograd.  swap (dy and dx exchanged),
+    by_plane, edge and freeze are the negative controls"""
+    b, c = img.shape[:2]
+    sh = shift.flip(1) if swap else shift
+    rows = _plane_rows(b, c, by_plane)
+    return shift_with_taps(img, ref_taps(sh[:, 0], freeze)[0][rows], ref_taps(sh[:, 1], freeze)[0][rows], edge)
+
+
+def ref_lanczos_grads(img, shift, dout, **wrong):
+    img, shift = img.clone().requires_grad_(True), shift.clone().requires_grad_(True)
+    (ref_lanczos_shift(img, shift, **wrong) * dout).sum().backward()
+    return img.grad, shift.grad
+
+
+def _abs_taps(shift, b):
+    """per axis (|k|, |k| + e), e = C_TAIL T_j the tap's own error, each (b, c, 7)"""
+    out = []
+    for ax in (0, 1):
+        k, Tj = ref_taps(shift[:, ax].detach())
+        out.append((k.abs()[None].expand(b, -1, -1), (k.abs() + C_TAIL * Tj)[None].expand(b, -1, -1)))
+    return out
+
+
+def _with_tap_error(base, full):
+    """T with C_TAIL T = C_TAIL base + (full - base): the fp32 roundings of the sum on exact taps, plus what the taps' errors e move it by;
+    base = sum |ky| |kx| |P|, full = sum (|ky| + e_y)(|kx| + e_x) |P|"""
+    return base + (full - base) / C_TAIL
+
+
+def lanczos_shift_T(img, shift):
+    (ya, yi), (xa, xi) = _abs_taps(shift, img.shape[0])
+    return _with_tap_error(shift_with_taps(img.abs(), ya, xa), shift_with_taps(img.abs(), yi, xi))
+
+
+def _adjoint(dout, ky, kx):
+    x = torch.zeros_like(dout, requires_grad=True)
+    return torch.autograd.grad(shift_with_taps(x, ky, kx), x, dout)[0]
+
+
+def lanczos_dimg_T(dout, shift):
+    """the same with |dout|, folded back through the reflection"""
+    (ya, yi), (xa, xi) = _abs_taps(shift, dout.shape[0])
+    return _with_tap_error(_adjoint(dout.abs(), ya, xa), _adjoint(dout.abs(), yi, xi))
+
+
+def tap_sums(img, dout, ky, kx):
+    """G (c, 2, 7): dL / dky[m] = sum dout[y][x] HP[y + m][x], HP = the horizontal pass of the padded rows; dL / dkx[n] = sum dout[y][x]
+    V[y][x + n], V = the vertical pass; summed over the batch"""
+    H, W = img.shape[2:]
+    P = F.pad(img, (3, 3, 3, 3), mode="reflect")
+    HP = sum(kx[:, :, n, None, None] * P[:, :, :, n:n + W] for n in range(7))
+    V = sum(ky[:, :, m, None, None] * P[:, :, m:m + H, :] for m in range(7))
+    Gy = torch.stack([(dout * HP[:, :, m:m + H]).sum((0, 2, 3)) for m in range(7)], 1)
+    Gx = torch.stack([(dout * V[:, :, :, n:n + W]).sum((0, 2, 3)) for n in range(7)], 1)
+    return torch.stack([Gy, Gx], 1)
+
+
+def lanczos_dshift_T(img, shift, dout):
+    """d shift = sum_j dk_j G_j: T = sum_j |dk_j| T(G_j) + T(dk_j) sum |dout| |HP|, T(G_j) = sum |dout| |HP| with the taps' error as above"""
+    (ya, yi), (xa, xi) = _abs_taps(shift, img.shape[0])
+    Gb, Gf = tap_sums(img.abs(), dout.abs(), ya, xa), tap_sums(img.abs(), dout.abs(), yi, xi)
+    T = torch.zeros((shift.shape[0], 2), dtype=D64)
+    for ax in (0, 1):
+        dk, Tdk = ref_tap_grad(shift[:, ax])
+        T[:, ax] = (dk.abs() * _with_tap_error(Gb[:, ax], Gf[:, ax]) + Tdk * Gb[:, ax]).sum(1)
+    return T
+
+
+# shifts: dy != dx in every channel; channel 0 an integer shift on the rows only (the frozen tap off-centre: j = 5), channel 1 beyond the
+# +-3 support on the rows, channel 2 an integer shift on the columns only.  c = 1 takes one of the rows, by the shape.
+TAIL_SHIFTS = torch.tensor([[2.0, -0.63], [-3.5, 0.5], [0.37, -1.0]])
+LANCZOS_BC = [(1, 1), (2, 3)]
+LANCZOS_FWD_SHAPES = [(4, 4), (4, 135), (5, 7), (32, 128), (33, 129), (38, 134), (70, 20)]      # the forward's tile: 32 x 128
+LANCZOS_BWD_SHAPES = [(4, 4), (5, 64), (16, 64), (17, 65), (7, 9)]                              # the backward's tile: 16 x 64
+TAP_N = [1, 63, 64, 65]
+TAP_D = ([0.0, -0.0] + [s * v for v in (1.0, 2.0, 3.0) for s in (1, -1)]
+         + [i + s * e for i in (0.0, 1.0, -2.0, 3.0) for e in (1e-6, 1e-4) for s in (1, -1)]
+         + [0.5, -0.5, 2.999, -2.999, 3.5, -7.25])
+
+
+def tap_inputs(n):
+    """n shifts out of TAP_D, from a start that moves with n (n >= 63 takes every one)"""
+    return torch.tensor([TAP_D[(n + i) % len(TAP_D)] for i in range(n)], dtype=torch.float32)
+
+
+def lanczos_inputs(b, c, H, W):
+    """img (values around 0.5: a DC offset), shift, dout, and the values d_shift starts from: float32"""
+    g = torch.Generator().manual_seed(7000 + 131 * H + 7 * W + b)
+    img = 0.5 + 0.25 * torch.randn((b, c, H, W), generator=g)
+    dout = torch.randn((b, c, H, W), generator=g)
+    shift = TAIL_SHIFTS.clone() if c == 3 else TAIL_SHIFTS[(H + W) % 3][None].clone()
+    return img, shift, dout, torch.randn((c, 2), generator=g)
+
+
+def check_taps(k, n):
+    d = tap_inputs(n)
+    want, T = ref_taps(d.double())
+    return _assert_close(f"taps n={n}", "f32", k.taps(d), want, T, layout="i j", c=C_TAIL)
+
+
+def check_lanczos_fwd(k, b, c, H, W):
+    img, shift, _, _ = lanczos_inputs(b, c, H, W)
+    tag = f"lanczos_shift b={b} c={c} {H}x{W}"
+    r = _assert_close(tag, "f32", k.shift(img, shift), ref_lanczos_shift(img.double(), shift.double()), lanczos_shift_T(img.double(), shift.double()),
+                      layout="b c y x", c=C_TAIL)
+    if b > 1:                                           # the same image in every batch entry: the same planes (plane % C picks the shift)
+        img[1:] = img[:1]
+        same = k.shift(img, shift)
+        assert all(torch.equal(same[i], same[0]) for i in range(1, b)), f"{tag}: equal images, different planes"
+    return r
+
+
+def check_lanczos_bwd(k, b, c, H, W):
+    """d_img, d_shift (+= into non-zero values) against autograd of the where form - at the integer shifts that is the frozen tap's
+    gradient, exactly none; then each output alone, the other one NULL: bit-identical"""
+    img, shift, dout, start = lanczos_inputs(b, c, H, W)
+    tag = f"lanczos_shift_backward b={b} c={c} {H}x{W}"
+    d_img, d_shift = k.shift_bwd(img, shift, dout, start)
+    i64, s64, o64 = img.double(), shift.double(), dout.double()
+    wi, ws = ref_lanczos_grads(i64, s64, o64)
+    r1 = _assert_close(tag + " d_img", "f32", d_img, wi, lanczos_dimg_T(o64, s64), layout="b c y x", c=C_TAIL)
+    r2 = _assert_close(tag + " d_shift", "f32", d_shift, start.double() + ws, start.double().abs() + lanczos_dshift_T(i64, s64, o64), layout="c axis", c=C_TAIL)
+    none, only_shift = k.shift_bwd(img, shift, dout, start, need_img=False)
+    assert none is None and torch.equal(only_shift, d_shift), f"{tag}: d_shift changes when d_img is NULL"
+    only_img, none = k.shift_bwd(img, shift, dout, None)
+    assert none is None and torch.equal(only_img, d_img), f"{tag}: d_img changes when d_shift is NULL"
+    return max(r1, r2)
+
+
+# ---- losses and the score
+def crop_mask(S, crop):
+    """get_crop_mask: ones, a border of `crop` pixels zero (crop = 0: no border)"""
+    m = torch.ones((S, S), dtype=D64)
+    if crop > 0:
+        m[:crop], m[-crop:], m[:, :crop], m[:, -crop:] = 0, 0, 0, 0
+    return m
+
+
+def ref_losses(srs, hrs, maps, crop, square_mask=False, drop=None):
+    """train.get_loss on the cropped map, (B, S, S) fp64, in its own two passes: n = sum m, the brightness bias b = sum m (hr - sr) / n,
+    cMSE = sum m (sr + b - hr)^2 / n (the weight is m, not m^2), cPSNR = -10 log10 cMSE, masked_MSE = mean (m sr - m hr)^2; and the bounds
+    of the kernels' fp64 sums.  square_mask (m^2 as the weight) and drop (one pixel left out) are the negative controls"""
+    S = srs.shape[-1]
+    m = maps * crop_mask(S, crop)
+    if drop is not None:
+        m = m.clone()
+        m[drop] = 0
+    d = srs - hrs
+    S0, S1, S2 = m.sum((1, 2)), (m * d).sum((1, 2)), (m * d * d).sum((1, 2))
+    bias = (m * (hrs - srs)).sum((1, 2)) / S0
+    cmse = ((m * m if square_mask else m) * (srs + bias[:, None, None] - hrs) ** 2).sum((1, 2)) / S0
+    mmse = ((m * srs - m * hrs) ** 2).mean((1, 2))
+    e = cmse_bound(S * S, S0, S1, S2)
+    return dict(m=m, S0=S0, bias=bias, cmse=cmse, cpsnr=-10 * torch.log10(cmse), mmse=mmse, e_S0=S * S * U64 * S0,
+                e_bias=S * S * U64 * (m * d.abs()).sum((1, 2)) / S0, e_cmse=e, e_cpsnr=cpsnr_bound(cmse, e), e_mmse=S * S * U64 * mmse)
+
+
+def ref_loss_grad(srs, hrs, r, metric, d_out):
+    """d_srs = d_out (d out / d cMSE) 2 m (d + b) / n, the bias a constant (train.py detaches it); T = |coef| m (|sr| + |hr| + |b|)"""
+    dm = torch.ones_like(r["cmse"]) if metric == 1 else -10.0 / (np.log(10.0) * r["cmse"])
+    coef = (d_out * dm * 2 / r["S0"])[:, None, None]
+    b = r["bias"][:, None, None]
+    return coef * r["m"] * (srs - hrs + b), coef.abs() * r["m"] * (srs.abs() + hrs.abs() + b.abs())
+
+
+LOSS_S = [1, 3, 16, 17, 65]
+TRAIN_S = [3, 17, 65, 129]          # fewer pixels than the 16 slices; a ragged last slice; 65; 16 641 pixels > the backward's 64 x 256 grid
+
+
+def crops(S):
+    return sorted({cr for cr in (0, 3, (S - 1) // 2) if 2 * cr < S})
+
+
+def loss_inputs(B, S, kind, ill=False):
+    """srs, hrs, maps float32.  kind: "bin" (0 / 1), "frac" (values in [0, 1], a fifth exact zeros), "zero" (sample 0 all zero, the others
+    binary), "mixed" (binary and fractional samples in turn).  The centre pixel of every map that is not all zero is 1, so a crop never
+    leaves a sample without a clear pixel.  ill: sr = hr + 0.2 + 1e-3 noise, S2 ~ S1^2 / S0"""
+    g = torch.Generator().manual_seed(9000 + 17 * S + B + 1000 * ["bin", "frac", "zero", "mixed"].index(kind) + (5 if ill else 0))
+    hrs = 0.1 + 0.6 * torch.rand((B, S, S), generator=g)
+    noise = torch.randn((B, S, S), generator=g)
+    srs = hrs + 0.2 + 1e-3 * noise if ill else hrs + 0.02 + 0.05 * noise
+    binary = (torch.rand((B, S, S), generator=g) > 0.3).float()
+    frac = torch.rand((B, S, S), generator=g) * (torch.rand((B, S, S), generator=g) > 0.2)
+    if kind == "frac":
+        maps = frac
+    elif kind == "mixed":
+        maps = torch.where((torch.arange(B) % 2 == 0)[:, None, None], binary, frac)
+    else:
+        maps = binary
+    maps[:, S // 2, S // 2] = 1.0
+    if kind == "zero":
+        maps[0] = 0.0
+    return srs, hrs, maps
+
+
+def check_get_loss(k, S, crop, B, kind, ill=False):
+    srs, hrs, maps = loss_inputs(B, S, kind, ill)
+    r = ref_losses(srs.double(), hrs.double(), maps.double(), crop)
+    tag = f"get_loss S={S} crop={crop} B={B} {kind}{' ill' if ill else ''}"
+    worst = 0.0
+    for metric, key in ((0, "mmse"), (1, "cmse"), (2, "cpsnr")):
+        want = r[key]
+        worst = max(worst, _assert_within(f"{tag} metric {metric}", k.get_loss(srs, hrs, maps, crop, metric), want, r["e_" + key] + U32 * want.abs(), "b"))
+    return worst
+
+
+def train_d_out(B):
+    """different per sample, with a zero and a negative one (B = 1: negative)"""
+    d = torch.randn(B, generator=torch.Generator().manual_seed(77 + B)) + 0.25
+    d[0] = -0.75
+    if B > 2:
+        d[1], d[2] = 0.0, -1.5
+    return d
+
+
+def check_loss_train(k, S, crop, B, kind, metric, drop=None):
+    """loss_partial + loss_finish: out and stats = (S0, -S1 / S0, cMSE, 0); loss_backward_kernel on those stats: d_srs, exact zeros where
+    the cropped map is zero.  Where cMSE lies within rounding of zero (a one-pixel window) cPSNR and its gradient are not determined, and
+    only the stats are checked."""
+    srs, hrs, maps = loss_inputs(B, S, kind)
+    s64, h64 = srs.double(), hrs.double()
+    r = ref_losses(s64, h64, maps.double(), crop, drop=drop)
+    tag = f"get_loss_train S={S} crop={crop} B={B} {kind} metric {metric}"
+    out, stats = k.loss_train(srs, hrs, maps, crop, metric)
+    worst = _assert_within(tag + " S0", stats[:, 0], r["S0"], r["e_S0"], "b")
+    worst = max(worst, _assert_within(tag + " bias", stats[:, 1], r["bias"], r["e_bias"], "b"))
+    worst = max(worst, _assert_within(tag + " cMSE", stats[:, 2], r["cmse"], r["e_cmse"], "b"))
+    assert bool((stats[:, 3] == 0).all()) and not bool(torch.signbit(stats[:, 3]).any()), f"{tag}: the fourth word of stats is not 0"
+    want = r["cmse"] if metric == 1 else r["cpsnr"]
+    e = r["e_cmse"] if metric == 1 else r["e_cpsnr"]
+    worst = max(worst, _assert_within(tag + " out", out, want, e + U32 * want.abs(), "b"))
+    d_out = train_d_out(B)
+    d_srs = k.loss_bwd(srs, hrs, maps, stats, d_out, crop, metric)
+    det = torch.isfinite(e)
+    assert bool(det.any()) or S - 2 * crop == 1, f"{tag}: no sample with a determined gradient"
+    if bool(det.any()):
+        gw, T = ref_loss_grad(s64, h64, r, metric, d_out.double())
+        worst_g = _assert_close(tag + " d_srs", "f32", d_srs[det], gw[det], T[det], layout="b y x", c=C_TAIL)
+        off = r["m"][det] == 0
+        assert bool((d_srs[det][off] == 0).all()), f"{tag}: d_srs is not 0 where the cropped map is"
+        assert bool(off.any()) or crop == 0
+        assert bool((d_srs[det][d_out[det] == 0] == 0).all())
+        return worst, worst_g
+    return worst, 0.0
+
+
+SCORE_BORDERS = [0, 1, 3]
+PLANTED = {0: (0, 0), 1: (1, -1), 3: (1, -2)}       # (rows, columns): unequal, so a transposed offset scores visibly worse
+
+
+def score_inputs(B, S, border):
+    """hrs in [0.1, 0.9]; srs = hrs moved by PLANTED[border] + noise + a brightness offset, with values below 0 and above 1; binary maps"""
+    g = torch.Generator().manual_seed(12000 + 31 * S + 7 * border + B)
+    hrs = 0.1 + 0.8 * torch.rand((B, S, S), generator=g)
+    pu, pv = PLANTED[border]
+    srs = torch.roll(hrs, (-pu, -pv), (1, 2)) + 0.003 + 0.01 * torch.randn((B, S, S), generator=g)
+    sel = torch.rand((B, S, S), generator=g)
+    srs = torch.where(sel < 0.03, torch.full_like(srs, -0.2), torch.where(sel > 0.97, torch.full_like(srs, 1.3), srs))
+    return srs, hrs, (torch.rand((B, S, S), generator=g) > 0.1).float()
+
+
+def ref_shift_scores(srs, hrs, maps, border, clip, transpose=False):
+    """Evaluator.shift_cPSNR's per-offset cPSNR, (B, (2 border + 1)^2) at k = u (2 border + 1) + v for the row offset u and the column offset
+    v of hr and its map against the centre crop of sr (np.clip first when clip: NaN stays NaN), on BINARY maps; and each score's bound.
+    bias = sum (hr - sr) m / n, cMSE = sum ((hr - sr - bias) m)^2 / n, n = sum m.  transpose: (u, v) exchanged, the negative control"""
+    B, S, _ = srs.shape
+    size, nb = S - 2 * border, 2 * border + 1
+    s = srs[:, border:border + size, border:border + size]
+    if clip:
+        s = s.clamp(0, 1)
+    scores, bounds = torch.zeros((B, nb * nb), dtype=D64), torch.zeros((B, nb * nb), dtype=D64)
+    for u in range(nb):
+        for v in range(nb):
+            uu, vv = (v, u) if transpose else (u, v)
+            hr, m = hrs[:, uu:uu + size, vv:vv + size], maps[:, uu:uu + size, vv:vv + size]
+            n, diff = m.sum((1, 2)), hr - s
+            bias = (diff * m).sum((1, 2)) / n
+            cmse = (((diff - bias[:, None, None]) * m) ** 2).sum((1, 2)) / n
+            scores[:, u * nb + v] = -10 * torch.log10(cmse)
+            bounds[:, u * nb + v] = cpsnr_bound(cmse, cmse_bound(size * size, n, (m * diff).sum((1, 2)), (m * diff * diff).sum((1, 2))))
+    return scores, bounds
+
+
+def ref_score_max(scores, bounds):
+    """np.max over the offsets (a NaN score makes it NaN) as the float the kernel stores, and its bound"""
+    want = torch.where(torch.isnan(scores).any(1), torch.full((scores.shape[0],), float("nan"), dtype=D64), scores.amax(1))
+    return want, torch.where(torch.isnan(bounds), torch.zeros_like(bounds), bounds).amax(1) + U32 * want.abs()
+
+
+def check_shift_cpsnr(k, border, S, B, clip):
+    srs, hrs, maps = score_inputs(B, S, border)
+    tag = f"shift_cpsnr border={border} S={S} B={B} clip={clip}"
+    scores, out = k.shift_cpsnr(srs, hrs, maps, border, clip)
+    want, bounds = ref_shift_scores(srs.double(), hrs.double(), maps.double(), border, clip)
+    worst = _assert_within(tag + " scores", scores, want, bounds, "b k")
+    return max(worst, _assert_within(tag + " max", out, *ref_score_max(want, bounds), "b"))
+
+
+# ---- negative controls: a reference wrong in one way must exceed the bound on the outputs that pass against the right one
+TAIL_CONTROLS = ["edge_repeat", "dy_dx_swapped", "frozen_tap_centre", "shift_by_plane", "crop_off_by_one", "square_mask", "pixel_dropped",
+                 "offsets_transposed"]
+
+
+def tail_control(k, control):
+    """-> (error / bound against the right reference, against the wrong one)"""
+    if control in ("edge_repeat", "dy_dx_swapped", "shift_by_plane"):
+        b, c, H, W = 2, 3, 5, 7
+        img, shift, _, _ = lanczos_inputs(b, c, H, W)
+        got, i64, s64 = k.shift(img, shift), img.double(), shift.double()
+        T = lanczos_shift_T(i64, s64)
+        wrong = {"edge_repeat": dict(edge="replicate"), "dy_dx_swapped": dict(swap=True), "shift_by_plane": dict(by_plane=True)}[control]
+        return _ratio("f32", got, ref_lanczos_shift(i64, s64), T, C_TAIL)[0], _ratio("f32", got, ref_lanczos_shift(i64, s64, **wrong), T, C_TAIL)[0]
+    if control == "frozen_tap_centre":
+        b, c, H, W = 2, 3, 7, 9
+        img, shift, dout, start = lanczos_inputs(b, c, H, W)
+        _, got = k.shift_bwd(img, shift, dout, start, need_img=False)
+        i64, s64, o64, st = img.double(), shift.double(), dout.double(), start.double()
+        T = st.abs() + lanczos_dshift_T(i64, s64, o64)
+        return (_ratio("f32", got, st + ref_lanczos_grads(i64, s64, o64)[1], T, C_TAIL)[0],
+                _ratio("f32", got, st + ref_lanczos_grads(i64, s64, o64, freeze="centre")[1], T, C_TAIL)[0])
+    if control in ("crop_off_by_one", "square_mask"):
+        S, crop, B = 17, 3, 3
+        srs, hrs, maps = loss_inputs(B, S, "frac")
+        got = k.get_loss(srs, hrs, maps, crop, 1)
+        r = ref_losses(srs.double(), hrs.double(), maps.double(), crop)
+        bad = (ref_losses(srs.double(), hrs.double(), maps.double(), crop + 1) if control == "crop_off_by_one" else
+               ref_losses(srs.double(), hrs.double(), maps.double(), crop, square_mask=True))
+        return (_within_ratio(got, r["cmse"], r["e_cmse"] + U32 * r["cmse"].abs()),
+                _within_ratio(got, bad["cmse"], bad["e_cmse"] + U32 * bad["cmse"].abs()))
+    if control == "pixel_dropped":
+        S, crop, B = 129, 3, 1
+        srs, hrs, maps = loss_inputs(B, S, "bin")
+        _, stats = k.loss_train(srs, hrs, maps, crop, 2)
+        y, x = [int(v) for v in torch.nonzero(maps[0, crop:S - crop, crop:S - crop])[-1]]
+        r = ref_losses(srs.double(), hrs.double(), maps.double(), crop)
+        bad = ref_losses(srs.double(), hrs.double(), maps.double(), crop, drop=(0, y + crop, x + crop))
+        return _within_ratio(stats[:, 2], r["cmse"], r["e_cmse"]), _within_ratio(stats[:, 2], bad["cmse"], bad["e_cmse"])
+    assert control == "offsets_transposed", control
+    srs, hrs, maps = score_inputs(1, 23, 3)
+    scores, _ = k.shift_cpsnr(srs, hrs, maps, 3, 1)
+    want, bounds = ref_shift_scores(srs.double(), hrs.double(), maps.double(), 3, 1)
+    bad, bb = ref_shift_scores(srs.double(), hrs.double(), maps.double(), 3, 1, transpose=True)
+    return _within_ratio(scores, want, bounds), _within_ratio(scores, bad, bb)
