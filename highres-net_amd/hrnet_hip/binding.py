@@ -149,6 +149,11 @@ SIGNATURES = {
     "hrn_mncc_search_scene": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,
                                                                              _c.c_void_p]),
     "hrn_mncc_apply_scene": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 4 + [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hrn_mncc_local_blocks": (_c.c_int, [_c.c_int] * 2),
+    "hrn_mncc_local_workspace_bytes": (_c.c_size_t, [_c.c_int] * 6),
+    "hrn_mncc_search_local": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 6 + [_c.c_float, _c.c_int, _c.c_float] + [_c.c_void_p] * 4
+                              + [_c.c_size_t, _c.c_void_p]),
+    "hrn_mncc_apply_field": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 5 + [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_collate_device": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
                                       _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_collate_device_s": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
@@ -909,6 +914,7 @@ def shift_loss_backward(srs, hrs, hr_maps, stats, d_out, metric="cPSNR", border_
 # workspace the scene form allocates, and in the limit on a frame's side, nothing else.
 MNCC_SIDES, MNCC_POINTS, MNCC_LEVELS, MNCC_MAX_RADIUS = (16, 128), (3, 9), (1, 16), 4.0     # the limits of include/hrnet_hip.h
 MNCC_SCENE_SIDES = (16, 16384)
+MNCC_LOCAL_BLOCKS = (64, 4096)             # a block of the local search: a multiple of 64 within these
 
 
 def mncc_int(name, value, limits):
@@ -1031,6 +1037,72 @@ def mncc_search_scene(ref, ref_mask, views, view_masks, points_per_dim=7, levels
 def mncc_apply_scene(views, view_masks, shifts):
     """mncc_apply for frames of any size (hrn_mncc_apply_scene); bit-identical to it where both run."""
     return _mncc_apply(True, views, view_masks, shifts)
+
+
+def mncc_block(block):
+    """The side of a block of the local search as the library takes it: a multiple of 64 in 64..4096."""
+    block = int(block)
+    if not MNCC_LOCAL_BLOCKS[0] <= block <= MNCC_LOCAL_BLOCKS[1] or block % 64:
+        raise ValueError(f"block must be a multiple of 64 in {MNCC_LOCAL_BLOCKS[0]}..{MNCC_LOCAL_BLOCKS[1]}; got {block}")
+    return block
+
+
+def mncc_local_blocks(H, W, block):
+    """-> (by, bx): the blocks of an (H, W) frame, by hrn_mncc_local_blocks - the library's own count, not a restatement of it."""
+    lib = load_library()
+    block = mncc_block(block)
+    by, bx = lib.hrn_mncc_local_blocks(int(H), block), lib.hrn_mncc_local_blocks(int(W), block)
+    if by == 0 or bx == 0:
+        raise ValueError(f"frames must be 1..{MNCC_SCENE_SIDES[1]} pixels a side; got {(int(H), int(W))}")
+    return by, bx
+
+
+def mncc_search_local(ref, ref_mask, views, view_masks, init, points_per_dim=7, levels=4, radius=0.5, block=128, min_valid=0.25):
+    """A shift per block of every view (hrn_mncc_search_local): init (B,V,2) or None (zeros) -> (field (B,V,by,bx,2) f32, trace
+    (B,V,by,bx,levels,3) f32 = (dy, dx, score) per level, ok (B,V,by,bx) f32 1 / 0); a block that is not ok holds init."""
+    lib = load_library()
+    ref, ref_mask, views, view_masks = _mncc_args(ref, ref_mask, views, view_masks)
+    B, V, H, W = views.shape
+    if init is not None:
+        init = _dev_f32(init, "init")
+        if tuple(init.shape) != (B, V, 2):
+            raise ValueError(f"init must be ({B}, {V}, 2); got {tuple(init.shape)}")
+    P, levels = mncc_int("points_per_dim", points_per_dim, MNCC_POINTS), mncc_int("levels", levels, MNCC_LEVELS)
+    by, bx = mncc_local_blocks(H, W, block)
+    field = torch.empty((B, V, by, bx, 2), dtype=torch.float32, device=views.device)
+    trace = torch.empty((B, V, by, bx, levels, 3), dtype=torch.float32, device=views.device)
+    ok = torch.empty((B, V, by, bx), dtype=torch.float32, device=views.device)
+    with torch.cuda.device(views.device):
+        nbytes = lib.hrn_mncc_local_workspace_bytes(B, V, H, W, P, int(block))
+        if nbytes == 0:
+            raise HrnetHipError(f"bad registration problem size B={B} V={V} H={H} W={W} P={P} block={block}")
+        ws = _workspace(nbytes, views.device, "mncc_local")
+        _check(lib.hrn_mncc_search_local(_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks), _opt_ptr(init), B, V, H, W, P, levels,
+                                         float(radius), int(block), float(min_valid), _ptr(field), _ptr(trace), _ptr(ok), _ptr(ws), ws.numel(),
+                                         _stream()), "hrn_mncc_search_local")
+    return field, trace, ok
+
+
+def mncc_apply_field(views, view_masks, field, block):
+    """-> (out, valid) as mncc_apply_scene, every pixel by its own shift: the field (B,V,by,bx,2) between the blocks' centres."""
+    lib = load_library()
+    views = _dev_f32(views, "views")
+    if views.dim() != 4:
+        raise ValueError(f"views must be (B,V,H,W); got {tuple(views.shape)}")
+    B, V, H, W = views.shape
+    if view_masks is not None:
+        view_masks = _dev_f32(view_masks, "view_masks")
+        if view_masks.shape != views.shape:
+            raise ValueError(f"view_masks must have views' shape {tuple(views.shape)}; got {tuple(view_masks.shape)}")
+    field = _dev_f32(field, "field")
+    by, bx = mncc_local_blocks(H, W, block)
+    if tuple(field.shape) != (B, V, by, bx, 2):
+        raise ValueError(f"field must be ({B}, {V}, {by}, {bx}, 2); got {tuple(field.shape)}")
+    out, valid = torch.empty_like(views), torch.empty_like(views)
+    with torch.cuda.device(views.device):
+        _check(lib.hrn_mncc_apply_field(_ptr(views), _opt_ptr(view_masks), _ptr(field), B, V, H, W, int(block), _ptr(out), _ptr(valid),
+                                        _stream()), "hrn_mncc_apply_field")
+    return out, valid
 
 
 # --------------------------------------------------------------------------- PyTorch-ROCm custom ops (north_star: "exposed to Python as
@@ -1503,6 +1575,32 @@ def _op_shift_scene(views: torch.Tensor, view_masks: Optional[torch.Tensor], shi
 _op_mncc_grid_scene.register_fake(_fake_mncc_grid)
 _op_mncc_search_scene.register_fake(_fake_mncc_search)
 _op_shift_scene.register_fake(_fake_shift_views)
+
+
+# a shift per block and the resampling by the field (registration_local.hip)
+@torch.library.custom_op("hrnet_hip::mncc_search_local", mutates_args=(), device_types="cuda")
+def _op_mncc_search_local(ref: torch.Tensor, ref_mask: Optional[torch.Tensor], views: torch.Tensor, view_masks: Optional[torch.Tensor],
+                          init: Optional[torch.Tensor], points_per_dim: int, levels: int, radius: float, block: int,
+                          min_valid: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return mncc_search_local(ref, ref_mask, views, view_masks, init, points_per_dim, levels, radius, block, min_valid)
+
+
+@_op_mncc_search_local.register_fake
+def _fake_mncc_search_local(ref, ref_mask, views, view_masks, init, points_per_dim, levels, radius, block, min_valid):
+    B, V, H, W = views.shape
+    by, bx = mncc_local_blocks(H, W, block)
+    return (views.new_empty((B, V, by, bx, 2), dtype=torch.float32), views.new_empty((B, V, by, bx, levels, 3), dtype=torch.float32),
+            views.new_empty((B, V, by, bx), dtype=torch.float32))
+
+
+@torch.library.custom_op("hrnet_hip::shift_field", mutates_args=(), device_types="cuda")
+def _op_shift_field(views: torch.Tensor, view_masks: Optional[torch.Tensor], field: torch.Tensor, block: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    return mncc_apply_field(views, view_masks, field, block)
+
+
+@_op_shift_field.register_fake
+def _fake_shift_field(views, view_masks, field, block):
+    return views.new_empty(views.shape, dtype=torch.float32), views.new_empty(views.shape, dtype=torch.float32)
 
 
 @torch.library.custom_op("hrnet_hip::adam_step", mutates_args=("params", "exp_avg", "exp_avg_sq"), device_types="cuda")

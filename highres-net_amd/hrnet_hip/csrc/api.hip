@@ -525,4 +525,49 @@ int hrn_mncc_apply_scene(const float* views, const float* view_masks, const floa
     return hrn_launch_mncc_apply_scene(views, view_masks, shifts, B, V, H, W, out, out_valid, (hipStream_t)stream);
 }
 
+// a shift per block of tiles and the resampling by the field between them (registration_local.hip)
+static int mncc_local_check(const char* who, int B, int V, int H, int W, int block) {
+    if (int rc = mncc_scene_check(who, B, V, H, W)) return rc;
+    HRN_CHECK(block >= HRN_MNCC_LOCAL_MIN_BLOCK && block <= HRN_MNCC_LOCAL_MAX_BLOCK && block % HRN_MNCC_SCENE_TILE == 0, -2,
+              "%s: bad block %d: a block must be a multiple of %d in %d..%d", who, block, HRN_MNCC_SCENE_TILE, HRN_MNCC_LOCAL_MIN_BLOCK,
+              HRN_MNCC_LOCAL_MAX_BLOCK);
+    HRN_CHECK(hrn_mncc_local_grid_fits(B, V, H, W, block), -2, "%s: bad batch B=%d V=%d: the blocks of %d x %d frames exceed one launch", who, B,
+              V, H, W);
+    return 0;
+}
+
+int hrn_mncc_local_blocks(int L, int block) {
+    if (L < 1 || L > HRN_MNCC_SCENE_MAX_SIDE || block < HRN_MNCC_LOCAL_MIN_BLOCK || block > HRN_MNCC_LOCAL_MAX_BLOCK ||
+        block % HRN_MNCC_SCENE_TILE != 0)
+        return 0;
+    return hrn_mncc_local_blocks_impl(L, block);
+}
+
+size_t hrn_mncc_local_workspace_bytes(int B, int V, int H, int W, int P, int block) {
+    if (hrn_mncc_scene_workspace_bytes(B, V, H, W, P) == 0 || hrn_mncc_local_blocks(H, block) == 0 || !hrn_mncc_local_grid_fits(B, V, H, W, block))
+        return 0;
+    return hrn_mncc_local_workspace_bytes_impl(B, V, H, W, P, block);
+}
+
+int hrn_mncc_search_local(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* init, int B, int V,
+                          int H, int W, int P, int levels, float radius, int block, float min_valid, float* field, float* trace, float* ok,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = mncc_local_check("hrn_mncc_search_local", B, V, H, W, block)) return rc;
+    if (int rc = mncc_check_points("hrn_mncc_search_local", P)) return rc;
+    HRN_CHECK(levels >= 1 && levels <= HRN_MNCC_MAX_LEVELS, -2, "hrn_mncc_search_local: levels %d outside 1..%d", levels, HRN_MNCC_MAX_LEVELS);
+    HRN_CHECK(radius > 0.f && radius <= 4.f, -2, "hrn_mncc_search_local: radius %g outside (0, 4]", (double)radius);
+    HRN_CHECK(min_valid >= 0.f && min_valid <= 1.f, -2, "hrn_mncc_search_local: min_valid %g outside [0, 1]", (double)min_valid);
+    HRN_CHECK(ref && views && field && workspace, -2, "hrn_mncc_search_local: null argument");
+    HRN_CHECK(workspace_bytes >= hrn_mncc_local_workspace_bytes_impl(B, V, H, W, P, block), -3, "hrn_mncc_search_local: workspace too small");
+    return hrn_launch_mncc_search_local(ref, ref_mask, views, view_masks, init, B, V, H, W, P, levels, radius, block, min_valid, field, trace, ok,
+                                        workspace, (hipStream_t)stream);
+}
+
+int hrn_mncc_apply_field(const float* views, const float* view_masks, const float* field, int B, int V, int H, int W, int block, float* out,
+                         float* out_valid, void* stream) {
+    if (int rc = mncc_local_check("hrn_mncc_apply_field", B, V, H, W, block)) return rc;
+    HRN_CHECK(views && field && out && out_valid, -2, "hrn_mncc_apply_field: null argument");
+    return hrn_launch_mncc_apply_field(views, view_masks, field, B, V, H, W, block, out, out_valid, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -79,6 +79,21 @@ int hrn_launch_mncc_search_scene(const float* ref, const float* ref_mask, const 
                                  int W, int P, int levels, float radius, float* shifts, float* trace, void* workspace, hipStream_t stream);
 int hrn_launch_mncc_apply_scene(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
                                 float* out_valid, hipStream_t stream);
+unsigned hrn_mncc_scene_mean_chunks(int H, int W);                 // the chunks of a frame's mean, and the pre-pass that fills
+void hrn_launch_mncc_scene_means(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H,
+                                 int W, double* means, hipStream_t stream);      // means[((plane) * chunks + chunk) * 2] = {sum, count}
+
+// ---- registration_local.hip: a shift per block of tiles of every view, and the views resampled by the field between the blocks'
+// centres.  block: a multiple of 64 in 64..4096; hrn_mncc_local_blocks_impl: the blocks of an axis.
+constexpr int HRN_MNCC_LOCAL_MIN_BLOCK = 64, HRN_MNCC_LOCAL_MAX_BLOCK = 4096;
+int hrn_mncc_local_blocks_impl(int L, int block);
+size_t hrn_mncc_local_workspace_bytes_impl(int B, int V, int H, int W, int P, int block);
+bool hrn_mncc_local_grid_fits(int B, int V, int H, int W, int block);
+int hrn_launch_mncc_search_local(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* init,
+                                 int B, int V, int H, int W, int P, int levels, float radius, int block, float min_valid, float* field,
+                                 float* trace, float* ok, void* workspace, hipStream_t stream);
+int hrn_launch_mncc_apply_field(const float* views, const float* view_masks, const float* field, int B, int V, int H, int W, int block,
+                                float* out, float* out_valid, hipStream_t stream);
 
 // ---- shiftnet.hip.  dt: storage of the activation tensors x / out / y - HRN_F32 or HRN_BF16, one bf16 plane (ShiftNet's bf16
 // training mode); statistics, scale / shift and fc1's input xr are f32 in both

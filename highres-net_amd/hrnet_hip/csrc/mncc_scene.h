@@ -1,0 +1,133 @@
+// What the kernels of the tiled masked-NCC registration share (DESIGN.md sections 7g and 7i): registration_scene.hip, one shift per view,
+// and registration_local.hip, a shift per block of tiles.  The tile, the LDS window and its staging, and the two passes of the sampler are
+// written once here; the body of a level kernel is mncc_scene_level.h.
+#pragma once
+#include "kernels.h"
+#include "wave_sums.h"
+#include "mncc_common.h"            // also turns fp contraction off
+
+namespace {
+
+constexpr int SC_PMAX = HRN_MNCC_MAX_POINTS;
+constexpr int SC_TILE = HRN_MNCC_SCENE_TILE;    // the core: 64 columns = one lane per column of a wave
+constexpr int SC_THREADS = 256, SC_WAVES = SC_THREADS / 64;
+constexpr int SC_RUN = 8;                       // rows of one column that a thread takes at a time
+constexpr int SC_ITEMS = (SC_TILE / SC_RUN) * SC_TILE / SC_THREADS;     // 2 runs a thread: 16 pixels
+constexpr int SC_SPAN = 9;                      // the whole-pixel offsets of one level, less the smallest: 0..SC_SPAN
+constexpr int SC_WIN = SC_TILE + SC_SPAN + 5;   // window rows and columns: offset - 2 .. offset + 3 around every core pixel
+constexpr int SC_MEAN_CHUNK = HRN_MNCC_SCENE_MEAN_CHUNK, SC_MEAN_CHUNKS = HRN_MNCC_SCENE_MEAN_CHUNKS;
+
+static_assert(SC_TILE == 64, "a lane owns a column of the core");
+static_assert(SC_ITEMS * SC_RUN <= 32, "a thread adds at most 32 pixels in fp32, and rbits is one 32-bit word");
+static_assert(SC_ITEMS * SC_THREADS * SC_RUN == SC_TILE * SC_TILE, "the runs cover the core exactly");
+
+struct SceneShared {
+    float T[SC_WIN * SC_WIN];                   // the window of the view, minus the view's mean (the search) or as it is (the resampler)
+    float A[SC_WIN * SC_TILE];                  // the pass along rows for the current dx
+    unsigned char pat[SC_WIN * SC_WIN];         // the four mask bits of the 2 x 2 neighbourhood of every window pixel
+    double red[SC_PMAX][SC_WAVES][8];
+    double tot[SC_PMAX * SC_PMAX][RG_NSUM];
+    double frac[2][SC_PMAX];                    // f per grid coordinate, axis 0 = y
+    float tap[2][SC_PMAX][6];
+    int whole[2][SC_PMAX];                      // n per grid coordinate
+    unsigned table[SC_PMAX * SC_PMAX];          // bit q: the bilinear sample of the 2 x 2 mask pattern q exceeds 0.5
+    float mean[2];                              // of the view, of the reference
+};
+static_assert(sizeof(SceneShared) <= 64 * 1024, "two workgroups per CU");
+static_assert(sizeof(float) * SC_WIN * SC_TILE >= SC_WIN * SC_WIN, "A holds the window's mask bytes while the patterns are formed");
+
+// the mean of a plane out of its chunks, in their order, rounded to fp32 as registration.hip rounds it; 0 without a clear pixel
+__device__ float plane_mean(const double* __restrict__ partial, size_t plane, unsigned chunks) {
+    double s = 0.0, n = 0.0;
+    for (unsigned c = 0; c < chunks; ++c) { s += partial[(plane * chunks + c) * 2]; n += partial[(plane * chunks + c) * 2 + 1]; }
+    return n > 0.0 ? (float)(s / n) : 0.f;
+}
+
+// ----------------------------------------------------------------------------- the window
+// Rows 0 .. ROWS - 1 and columns 0 .. COLS - 1 of the window whose pixel (0, 0) is the frame's (oy, ox): T = view - mean inside the
+// frame and 0 outside, pat = the 2 x 2 mask patterns (a pixel outside the frame, or beyond the staged part, counts as masked).  S.A is
+// scratch here.  Ends with a barrier.
+template <int ROWS, int COLS>
+__device__ void stage_window(const float* __restrict__ view, const float* __restrict__ mask, SceneShared& S, int oy, int ox, int H, int W,
+                             float mean, int tid) {
+    static_assert(ROWS <= SC_WIN && COLS <= SC_WIN, "inside the window");
+    unsigned char* mb = reinterpret_cast<unsigned char*>(S.A);
+    constexpr int n = ROWS * COLS, rows = ROWS, cols = COLS;
+    for (int i = tid; i < n; i += SC_THREADS) {
+        const int wy = i / cols, wx = i - wy * cols;
+        const int y = oy + wy, x = ox + wx;
+        const bool in = y >= 0 && y < H && x >= 0 && x < W;
+        const size_t g = in ? (size_t)y * W + x : 0;
+        S.T[wy * SC_WIN + wx] = in ? view[g] - mean : 0.f;
+        mb[wy * SC_WIN + wx] = in && (mask ? mask[g] != 0.f : true);
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += SC_THREADS) {
+        const int wy = i / cols, wx = i - wy * cols, w = wy * SC_WIN + wx;
+        const bool right = wx + 1 < cols, down = wy + 1 < rows;
+        unsigned q = mb[w];
+        if (right) q |= mb[w + 1] << 1;
+        if (down) q |= mb[w + SC_WIN] << 2;
+        if (right && down) q |= mb[w + SC_WIN + 1] << 3;
+        S.pat[w] = (unsigned char)q;
+    }
+    __syncthreads();
+}
+
+// the pass along rows for one dx over `rows` window rows: A[wy][x] = sum_o tap[o] T[wy][x + off + o], off = n_x less the level's
+// smallest, 0..SC_SPAN: the last column read is 63 + 9 + 5 < SC_WIN.  The operations and their order are registration.hip's row_pass.
+__device__ void scene_row_pass(SceneShared& S, const float* tap, int off, int rows, int tid) {
+    float k[6];
+#pragma unroll
+    for (int o = 0; o < 6; ++o) k[o] = tap[o];
+    const int x = tid & 63;
+    for (int wy = tid >> 6; wy < rows; wy += SC_WAVES) {
+        const float* row = S.T + wy * SC_WIN + x + off;
+        float a = k[0] * row[0];
+#pragma unroll
+        for (int o = 1; o < 6; ++o) a = fmaf(k[o], row[o], a);
+        S.A[wy * SC_TILE + x] = a;
+    }
+}
+
+// One run of one column for one (dy, dx): the six taps down SC_RUN + 5 rows of A, and which of the run's pixels are valid - inside the
+// frame, footprint inside the frame, and the bilinear mask sample above 0.5.  yl: the run's first row in the core; (gy, gx): the same
+// pixel in the frame; offy / offx: n_y / n_x less the level's smallest.  t[p] is defined only where bit p of the result is set.
+__device__ __forceinline__ unsigned scene_column_run(const SceneShared& S, const float* ky, int ny, int nx, int offy, int offx,
+                                                     unsigned table, int x, int yl, int gy, int gx, int H, int W, float* t) {
+    float a[SC_RUN + 5];
+#pragma unroll
+    for (int m = 0; m < SC_RUN + 5; ++m) a[m] = S.A[(yl + offy + m) * SC_TILE + x];           // the last row: 56 + 9 + 12 < SC_WIN
+    const bool xin = gx < W && gx + nx - 2 >= 0 && gx + nx + 3 <= W - 1;
+    const unsigned char* pat = S.pat + (yl + offy + 2) * SC_WIN + x + offx + 2;               // the window's pixel (gy + n_y, gx + n_x)
+    unsigned valid = 0;
+#pragma unroll
+    for (int p = 0; p < SC_RUN; ++p) {
+        float s = ky[0] * a[p];
+#pragma unroll
+        for (int o = 1; o < 6; ++o) s = fmaf(ky[o], a[p + o], s);
+        t[p] = s;
+        const int y = gy + p;
+        const bool yin = y < H && y + ny - 2 >= 0 && y + ny + 3 <= H - 1;
+        const unsigned q = pat[p * SC_WIN];
+        valid |= (unsigned)(xin && yin && ((table >> q) & 1u)) << p;
+    }
+    return valid;
+}
+
+__device__ __forceinline__ int min_whole(const int* whole, int P) {
+    int m = whole[0];
+    for (int i = 1; i < P; ++i) m = whole[i] < m ? whole[i] : m;
+    return m;
+}
+
+// ----------------------------------------------------------------------------- the host side of a level
+double level_ratio(int P) {                      // as registration.hip: 1 / (P - 2), at least 0.25, and 0.9 where that is not below 1
+    const double s = 1.0 / (double)(P - 2);
+    return s >= 1.0 ? 0.9 : (s < 0.25 ? 0.25 : s);
+}
+
+// the counted arithmetic of one level, per pixel, as registration.hip counts it
+double level_flops(int P) { return P * 12.0 + (double)P * P * 32.0; }
+
+}  // namespace

@@ -19,39 +19,9 @@
 // The span: a level's coordinates are d_0 <= ... <= d_{P-1} with d_{P-1} - d_0 <= 8 before the rounding to fp32 (width <= 8), so
 // floor(d_{P-1}) - floor(d_0) <= 9.  A coordinate further than SC_SPAN whole pixels from the smallest cannot occur; the kernels skip it
 // (its score would be -inf) rather than read outside the window.
-#include "kernels.h"
-#include "wave_sums.h"
-#include "mncc_common.h"            // also turns fp contraction off
+#include "mncc_scene.h"
 
 namespace {
-
-constexpr int SC_PMAX = HRN_MNCC_MAX_POINTS;
-constexpr int SC_TILE = HRN_MNCC_SCENE_TILE;    // the core: 64 columns = one lane per column of a wave
-constexpr int SC_THREADS = 256, SC_WAVES = SC_THREADS / 64;
-constexpr int SC_RUN = 8;                       // rows of one column that a thread takes at a time
-constexpr int SC_ITEMS = (SC_TILE / SC_RUN) * SC_TILE / SC_THREADS;     // 2 runs a thread: 16 pixels
-constexpr int SC_SPAN = 9;                      // the whole-pixel offsets of one level, less the smallest: 0..SC_SPAN
-constexpr int SC_WIN = SC_TILE + SC_SPAN + 5;   // window rows and columns: offset - 2 .. offset + 3 around every core pixel
-constexpr int SC_MEAN_CHUNK = HRN_MNCC_SCENE_MEAN_CHUNK, SC_MEAN_CHUNKS = HRN_MNCC_SCENE_MEAN_CHUNKS;
-
-static_assert(SC_TILE == 64, "a lane owns a column of the core");
-static_assert(SC_ITEMS * SC_RUN <= 32, "a thread adds at most 32 pixels in fp32, and rbits is one 32-bit word");
-static_assert(SC_ITEMS * SC_THREADS * SC_RUN == SC_TILE * SC_TILE, "the runs cover the core exactly");
-
-struct SceneShared {
-    float T[SC_WIN * SC_WIN];                   // the window of the view, minus the view's mean (the search) or as it is (the resampler)
-    float A[SC_WIN * SC_TILE];                  // the pass along rows for the current dx
-    unsigned char pat[SC_WIN * SC_WIN];         // the four mask bits of the 2 x 2 neighbourhood of every window pixel
-    double red[SC_PMAX][SC_WAVES][8];
-    double tot[SC_PMAX * SC_PMAX][RG_NSUM];
-    double frac[2][SC_PMAX];                    // f per grid coordinate, axis 0 = y
-    float tap[2][SC_PMAX][6];
-    int whole[2][SC_PMAX];                      // n per grid coordinate
-    unsigned table[SC_PMAX * SC_PMAX];          // bit q: the bilinear sample of the 2 x 2 mask pattern q exceeds 0.5
-    float mean[2];                              // of the view, of the reference
-};
-static_assert(sizeof(SceneShared) <= 64 * 1024, "two workgroups per CU");
-static_assert(sizeof(float) * SC_WIN * SC_TILE >= SC_WIN * SC_WIN, "A holds the window's mask bytes while the patterns are formed");
 
 // ----------------------------------------------------------------------------- the means
 // partial[(plane * chunks + chunk) * 2] = {sum, count} of the clear pixels of one chunk of one plane; planes 0 .. BV - 1 are the views,
@@ -81,91 +51,6 @@ __global__ __launch_bounds__(SC_THREADS) void scene_mean_kernel(const float* __r
     }
 }
 
-// the mean of a plane out of its chunks, in their order, rounded to fp32 as registration.hip rounds it; 0 without a clear pixel
-__device__ float plane_mean(const double* __restrict__ partial, size_t plane, unsigned chunks) {
-    double s = 0.0, n = 0.0;
-    for (unsigned c = 0; c < chunks; ++c) { s += partial[(plane * chunks + c) * 2]; n += partial[(plane * chunks + c) * 2 + 1]; }
-    return n > 0.0 ? (float)(s / n) : 0.f;
-}
-
-// ----------------------------------------------------------------------------- the window
-// Rows 0 .. ROWS - 1 and columns 0 .. COLS - 1 of the window whose pixel (0, 0) is the frame's (oy, ox): T = view - mean inside the
-// frame and 0 outside, pat = the 2 x 2 mask patterns (a pixel outside the frame, or beyond the staged part, counts as masked).  S.A is
-// scratch here.  Ends with a barrier.
-template <int ROWS, int COLS>
-__device__ void stage_window(const float* __restrict__ view, const float* __restrict__ mask, SceneShared& S, int oy, int ox, int H, int W,
-                             float mean, int tid) {
-    static_assert(ROWS <= SC_WIN && COLS <= SC_WIN, "inside the window");
-    unsigned char* mb = reinterpret_cast<unsigned char*>(S.A);
-    constexpr int n = ROWS * COLS, rows = ROWS, cols = COLS;
-    for (int i = tid; i < n; i += SC_THREADS) {
-        const int wy = i / cols, wx = i - wy * cols;
-        const int y = oy + wy, x = ox + wx;
-        const bool in = y >= 0 && y < H && x >= 0 && x < W;
-        const size_t g = in ? (size_t)y * W + x : 0;
-        S.T[wy * SC_WIN + wx] = in ? view[g] - mean : 0.f;
-        mb[wy * SC_WIN + wx] = in && (mask ? mask[g] != 0.f : true);
-    }
-    __syncthreads();
-    for (int i = tid; i < n; i += SC_THREADS) {
-        const int wy = i / cols, wx = i - wy * cols, w = wy * SC_WIN + wx;
-        const bool right = wx + 1 < cols, down = wy + 1 < rows;
-        unsigned q = mb[w];
-        if (right) q |= mb[w + 1] << 1;
-        if (down) q |= mb[w + SC_WIN] << 2;
-        if (right && down) q |= mb[w + SC_WIN + 1] << 3;
-        S.pat[w] = (unsigned char)q;
-    }
-    __syncthreads();
-}
-
-// the pass along rows for one dx over `rows` window rows: A[wy][x] = sum_o tap[o] T[wy][x + off + o], off = n_x less the level's
-// smallest, 0..SC_SPAN: the last column read is 63 + 9 + 5 < SC_WIN.  The operations and their order are registration.hip's row_pass.
-__device__ void scene_row_pass(SceneShared& S, const float* tap, int off, int rows, int tid) {
-    float k[6];
-#pragma unroll
-    for (int o = 0; o < 6; ++o) k[o] = tap[o];
-    const int x = tid & 63;
-    for (int wy = tid >> 6; wy < rows; wy += SC_WAVES) {
-        const float* row = S.T + wy * SC_WIN + x + off;
-        float a = k[0] * row[0];
-#pragma unroll
-        for (int o = 1; o < 6; ++o) a = fmaf(k[o], row[o], a);
-        S.A[wy * SC_TILE + x] = a;
-    }
-}
-
-// One run of one column for one (dy, dx): the six taps down SC_RUN + 5 rows of A, and which of the run's pixels are valid - inside the
-// frame, footprint inside the frame, and the bilinear mask sample above 0.5.  yl: the run's first row in the core; (gy, gx): the same
-// pixel in the frame; offy / offx: n_y / n_x less the level's smallest.  t[p] is defined only where bit p of the result is set.
-__device__ __forceinline__ unsigned scene_column_run(const SceneShared& S, const float* ky, int ny, int nx, int offy, int offx,
-                                                     unsigned table, int x, int yl, int gy, int gx, int H, int W, float* t) {
-    float a[SC_RUN + 5];
-#pragma unroll
-    for (int m = 0; m < SC_RUN + 5; ++m) a[m] = S.A[(yl + offy + m) * SC_TILE + x];           // the last row: 56 + 9 + 12 < SC_WIN
-    const bool xin = gx < W && gx + nx - 2 >= 0 && gx + nx + 3 <= W - 1;
-    const unsigned char* pat = S.pat + (yl + offy + 2) * SC_WIN + x + offx + 2;               // the window's pixel (gy + n_y, gx + n_x)
-    unsigned valid = 0;
-#pragma unroll
-    for (int p = 0; p < SC_RUN; ++p) {
-        float s = ky[0] * a[p];
-#pragma unroll
-        for (int o = 1; o < 6; ++o) s = fmaf(ky[o], a[p + o], s);
-        t[p] = s;
-        const int y = gy + p;
-        const bool yin = y < H && y + ny - 2 >= 0 && y + ny + 3 <= H - 1;
-        const unsigned q = pat[p * SC_WIN];
-        valid |= (unsigned)(xin && yin && ((table >> q) & 1u)) << p;
-    }
-    return valid;
-}
-
-__device__ __forceinline__ int min_whole(const int* whole, int P) {
-    int m = whole[0];
-    for (int i = 1; i < P; ++i) m = whole[i] < m ? whole[i] : m;
-    return m;
-}
-
 // ----------------------------------------------------------------------------- one grid level: the tiles' sums
 // sums[((view * tiles + tile) * P^2 + i P + j) * 6 + q]: the six sums of tile `tile` of view `view` at (dy_i, dx_j) of the P x P grid
 // of `width` around centres[view] ((0, 0) where `centres` is null).  grid (B V tiles), tiles = tiles_x * tiles_y
@@ -174,93 +59,9 @@ __global__ __launch_bounds__(SC_THREADS) void scene_level_kernel(const float* __
                                                                  const float* __restrict__ centres, const double* __restrict__ means,
                                                                  unsigned chunks, unsigned BV, int V, int H, int W, int P, double width,
                                                                  unsigned tiles_x, unsigned tiles, double* __restrict__ sums) {
-    __shared__ SceneShared S;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const size_t view = blockIdx.x / tiles, b = view / V, hw = (size_t)H * W;
-    const unsigned tile = blockIdx.x - (unsigned)view * tiles;
-    const int ty0 = (int)(tile / tiles_x) * SC_TILE, tx0 = (int)(tile % tiles_x) * SC_TILE;
-
-    if (tid < 2 * P) {
-        const int axis = tid / P, i = tid - axis * P;
-        const double c = centres ? (double)centres[2 * view + axis] : 0.0;
-        split_and_taps(grid_coord(c, width, i, P), &S.whole[axis][i], &S.frac[axis][i], S.tap[axis][i]);
-    }
-    if (tid == 64) S.mean[0] = plane_mean(means, view, chunks);
-    if (tid == 128) S.mean[1] = plane_mean(means, (size_t)BV + b, chunks);
-    __syncthreads();
-    if (tid < P * P) S.table[tid] = mask_table(S.frac[0][tid / P], S.frac[1][tid % P]);
-    const int ny0 = min_whole(S.whole[0], P), nx0 = min_whole(S.whole[1], P);
-    stage_window<SC_WIN, SC_WIN>(views + view * hw, view_masks ? view_masks + view * hw : nullptr, S, ty0 + ny0 - 2, tx0 + nx0 - 2, H, W,
-                                 S.mean[0], tid);
-
-    // this thread's pixels of the reference, centred on the reference's mean under its own mask and zero where that mask is set
-    float r[SC_ITEMS][SC_RUN];
-    unsigned rbits = 0;
-    const int x = lane, gx = tx0 + x;
-    {
-        const float* rp = ref + b * hw;
-        const float* rm = ref_mask ? ref_mask + b * hw : nullptr;
-        const float mean = S.mean[1];
-#pragma unroll
-        for (int k = 0; k < SC_ITEMS; ++k)
-#pragma unroll
-            for (int p = 0; p < SC_RUN; ++p) {
-                const int gy = ty0 + (wave + k * SC_WAVES) * SC_RUN + p;
-                const bool in = gy < H && gx < W;
-                const size_t g = in ? (size_t)gy * W + gx : 0;
-                const bool m = in && (rm ? rm[g] != 0.f : true);
-                r[k][p] = m ? rp[g] - mean : 0.f;
-                rbits |= (unsigned)m << (SC_RUN * k + p);
-            }
-    }
-
-#pragma unroll 1
-    for (int j = 0; j < P; ++j) {
-        const int nx = S.whole[1][j], offx = nx - nx0;
-        const bool jok = offx <= SC_SPAN;
-        if (jok) scene_row_pass(S, S.tap[1][j], offx, SC_WIN, tid);
-        __syncthreads();
-#pragma unroll 1
-        for (int i = 0; i < P; ++i) {
-            const int ny = S.whole[0][i], offy = ny - ny0;
-            const unsigned table = S.table[i * P + j];
-            float ky[6];
-#pragma unroll
-            for (int o = 0; o < 6; ++o) ky[o] = S.tap[0][i][o];
-            int n = 0;
-            float st = 0.f, sr = 0.f, stt = 0.f, srr = 0.f, srt = 0.f;
-            if (jok && offy <= SC_SPAN) {
-#pragma unroll
-                for (int k = 0; k < SC_ITEMS; ++k) {
-                    const int yl = (wave + k * SC_WAVES) * SC_RUN;
-                    float t[SC_RUN];
-                    const unsigned c = scene_column_run(S, ky, ny, nx, offy, offx, table, x, yl, ty0 + yl, gx, H, W, t) & (rbits >> (SC_RUN * k));
-#pragma unroll
-                    for (int p = 0; p < SC_RUN; ++p) {
-                        const bool on = (c >> p) & 1u;
-                        const float tm = on ? t[p] : 0.f, rm = on ? r[k][p] : 0.f;
-                        n += on;
-                        st += tm; sr += rm;
-                        stt = fmaf(tm, tm, stt); srr = fmaf(rm, rm, srr); srt = fmaf(rm, tm, srt);
-                    }
-                }
-            }
-            double v[8] = {(double)n, (double)st, (double)sr, (double)stt, (double)srr, (double)srt, 0.0, 0.0};
-            WaveSums<8, 0>::run(v, lane);
-            if (lane < 8) S.red[i][wave][wave_sums_index<8>(lane)] = v[0];
-        }
-        __syncthreads();                         // A and S.red are free again after this
-        if (tid < P * RG_NSUM) {
-            const int i = tid / RG_NSUM, q = tid - i * RG_NSUM;
-            double s = 0.0;
-            for (int w = 0; w < SC_WAVES; ++w) s += S.red[i][w][q];
-            S.tot[i * P + j][q] = s;
-        }
-    }
-    __syncthreads();
-    double* out = sums + (size_t)blockIdx.x * (P * P * RG_NSUM);
-    const double* tot = &S.tot[0][0];
-    for (int i = tid; i < P * P * RG_NSUM; i += SC_THREADS) out[i] = tot[i];
+#define SCENE_LEVEL_CENTRE view
+#include "mncc_scene_level.h"
+#undef SCENE_LEVEL_CENTRE
 }
 
 // ----------------------------------------------------------------------------- one grid level: the finish
@@ -348,14 +149,6 @@ __global__ __launch_bounds__(SC_THREADS) void scene_apply_kernel(const float* __
     }
 }
 
-double level_ratio(int P) {                      // as registration.hip: 1 / (P - 2), at least 0.25, and 0.9 where that is not below 1
-    const double s = 1.0 / (double)(P - 2);
-    return s >= 1.0 ? 0.9 : (s < 0.25 ? 0.25 : s);
-}
-
-// the counted arithmetic of one level, per pixel, as registration.hip counts it
-double level_flops(int P) { return P * 12.0 + (double)P * P * 32.0; }
-
 struct ScenePlan {
     unsigned tiles_x, tiles, chunks;
     size_t means_bytes, centres_bytes, sums_bytes;
@@ -397,6 +190,14 @@ void launch_means(const float* ref, const float* ref_mask, const float* views, c
 }
 
 }  // namespace
+
+// the means pre-pass and its chunks for registration_local.hip, whose workspace begins as this file's does
+unsigned hrn_mncc_scene_mean_chunks(int H, int W) { return plan(1, 1, H, W, HRN_MNCC_MIN_POINTS).chunks; }
+
+void hrn_launch_mncc_scene_means(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H,
+                                 int W, double* means, hipStream_t stream) {
+    launch_means(ref, ref_mask, views, view_masks, B, V, H, W, plan(B, V, H, W, HRN_MNCC_MIN_POINTS), means, stream);
+}
 
 size_t hrn_mncc_scene_workspace_bytes_impl(int B, int V, int H, int W, int P) {
     const ScenePlan p = plan(B, V, H, W, P);

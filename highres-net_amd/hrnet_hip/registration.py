@@ -14,7 +14,11 @@ piecewise constant in the frames - and no CPU fallback: tensors must be on a ROC
 `mncc_search_scene`, `mncc_grid_scene`, `shift_scene` and `register_scene` are the same four for frames of 16..16384 pixels a side
 (DESIGN.md section 7g): the scenes `HRNet.forward_tiled` takes, the large benchmark shape, an SR / HR pair.  A frame is cut into tiles
 of 64 x 64; a level of the search is two launches and the next level reads its centre from device memory.  Same definitions, same
-arguments, same errors; `shift_scene` is bit-identical to `shift_views` where both run."""
+arguments, same errors; `shift_scene` is bit-identical to `shift_views` where both run.
+
+`mncc_search_local`, `shift_field` and `register_scene_local` find and apply a shift FIELD on the scene path: one
+shift per block of `block` x `block` pixels of every view, searched from the view's global shift on the same tiles, and every pixel
+resampled by the bilinear field between the blocks' centres.  `local_blocks` is the library's own count of the blocks."""
 import torch
 
 from . import binding
@@ -163,3 +167,66 @@ def register_scene(lrs, lr_masks=None, **search_kwargs):
     shifts = mncc_search_scene(lrs, lr_masks, **search_kwargs)
     registered, valid = shift_scene(lrs, lr_masks, shifts)
     return registered, valid, shifts
+
+
+# ----------------------------------------------------------------------------- a shift per block of a scene (section 7i)
+def local_blocks(H, W, block):
+    """-> (by, bx): an axis of length L has max(1, (L + block / 2) // block) blocks of `block` pixels, a multiple of 64 in 64..4096; the
+    last block runs to L.  Computed by the library (hrn_mncc_local_blocks)."""
+    return binding.mncc_local_blocks(H, W, block)
+
+
+def _local_args(block, min_valid):
+    block, min_valid = binding.mncc_block(block), float(min_valid)
+    if not 0.0 <= min_valid <= 1.0:
+        raise ValueError(f"min_valid must be in [0, 1]; got {min_valid}")
+    return block, min_valid
+
+
+def mncc_search_local(lrs, lr_masks=None, ref=None, ref_mask=None, block=128, init=None, points_per_dim=7, levels=4, radius=0.5,
+                      min_valid=0.25, return_trace=False):
+    """-> field (B,V,by,bx,2) f32: per view and block of the frame, the shift of maximal masked NCC with the reference mask restricted to
+    the block, by `levels` levels of `mncc_search_scene`'s grid rule around init (B,V,2) - normally the view's global shift; None: zeros.
+    A block is ok when its last score is finite and its common valid pixels are at least min_valid of its area; a block that is not ok
+    holds init.  The deviation from init is bounded by the sum of the levels' half widths; there is no smoothing.  return_trace: also
+    trace (B,V,by,bx,levels,3) = (dy, dx, score) per level and ok (B,V,by,bx) f32 0 / 1.  Not differentiable."""
+    _frames(lrs, lr_masks, True)
+    ref, ref_mask = _reference(lrs, lr_masks, ref, ref_mask)
+    P, levels, radius = _search_args(points_per_dim, levels, radius)
+    block, min_valid = _local_args(block, min_valid)
+    if init is not None:
+        if not torch.is_tensor(init):
+            raise TypeError(f"init must be a torch.Tensor or None; got {type(init).__name__}")
+        if tuple(init.shape) != tuple(lrs.shape[:2]) + (2,):
+            raise ValueError(f"init must be (B,V,2) = {tuple(lrs.shape[:2]) + (2,)}; got {tuple(init.shape)}")
+    _on_device(lrs=lrs, lr_masks=lr_masks, ref=ref, ref_mask=ref_mask, init=init)
+    field, trace, ok = torch.ops.hrnet_hip.mncc_search_local(ref, ref_mask, lrs, lr_masks, init, P, levels, radius, block, min_valid)
+    return (field, trace, ok) if return_trace else field
+
+
+def shift_field(lrs, lr_masks, field, block):
+    """-> (registered, valid) as `shift_scene`, every pixel by its own shift: field (B,V,by,bx,2) holds the shifts at the centres of the
+    blocks' rectangles, bilinear in between and constant beyond the outer centres.  A constant field gives `shift_scene`'s bits."""
+    _frames(lrs, lr_masks, True)
+    block = binding.mncc_block(block)
+    if not torch.is_tensor(field):
+        raise TypeError(f"field must be a torch.Tensor; got {type(field).__name__}")
+    want = tuple(lrs.shape[:2]) + local_blocks(lrs.shape[2], lrs.shape[3], block) + (2,)
+    if tuple(field.shape) != want:
+        raise ValueError(f"field must be (B,V,by,bx,2) = {want}; got {tuple(field.shape)}")
+    _on_device(lrs=lrs, lr_masks=lr_masks, field=field)
+    return torch.ops.hrnet_hip.shift_field(lrs, lr_masks, field, block)
+
+
+def register_scene_local(lrs, lr_masks=None, block=128, local_levels=4, local_radius=0.5, min_valid=0.25, **search_kwargs):
+    """mncc_search_scene with search_kwargs (ref, ref_mask, points_per_dim, levels, radius), mncc_search_local from those shifts with
+    local_levels levels of local_radius, then shift_field: -> (registered, valid, field, shifts)."""
+    if "return_trace" in search_kwargs:
+        raise TypeError("register_scene_local returns no trace: call mncc_search_scene and mncc_search_local(..., return_trace=True)")
+    _local_args(block, min_valid)
+    _search_args(search_kwargs.get("points_per_dim", 7), local_levels, local_radius)
+    shifts = mncc_search_scene(lrs, lr_masks, **search_kwargs)
+    local = {k: search_kwargs[k] for k in ("ref", "ref_mask", "points_per_dim") if k in search_kwargs}
+    field = mncc_search_local(lrs, lr_masks, block=block, init=shifts, levels=local_levels, radius=local_radius, min_valid=min_valid, **local)
+    registered, valid = shift_field(lrs, lr_masks, field, block)
+    return registered, valid, field, shifts

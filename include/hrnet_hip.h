@@ -23,7 +23,8 @@
  *   hrn_shift_loss_train / hrn_shift_loss_backward  <-  the two combined as a differentiable loss (the searched score, trainable)
  *   hrn_mncc_grid / hrn_mncc_search / hrn_mncc_apply  <-  the method of the fork's registration_search.py (recursive_mncc_search over
  *                              compute_grid_mncc), restated: sub-pixel registration of the LR views against a reference frame;
- *                              hrn_mncc_grid_scene / hrn_mncc_search_scene / hrn_mncc_apply_scene: the same for frames of any size
+ *                              hrn_mncc_grid_scene / hrn_mncc_search_scene / hrn_mncc_apply_scene: the same for frames of any size;
+ *                              hrn_mncc_search_local / hrn_mncc_apply_field: a shift per block of a scene and the resampling by that field
  *   hrn_collate_device     <-  collateFunction(min_L) over ImagesetDataset items (src/utils.py:63-113), gathered from
  *                              imagesets decoded once into HBM (DataLoader.DeviceImagesetCache); hrn_collate_device_s
  *                              is the same for x2 / x3 / x4 targets
@@ -369,6 +370,36 @@ int hrn_mncc_search_scene(const float* ref, const float* ref_mask, const float* 
                           int P, int levels, float radius, float* shifts, float* trace, void* workspace, size_t workspace_bytes,
                           void* stream);
 int hrn_mncc_apply_scene(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
+                         float* out_valid, void* stream);
+/* A shift per block of every view - a shift field - on the scene path's tiles.  `block` is a multiple of 64 in
+ * 64..4096.  An axis of length L has n = max(1, (L + block / 2) / block) blocks; block i covers [i block, (i + 1) block) and the last one
+ * runs to L, so a remainder below half a block joins its neighbour and every block is a union of whole 64-pixel tiles.
+ *   local score   of block (i, j) at a shift: the score above with the reference mask set to zero outside the block.  Both images stay
+ *                 centred on their whole-frame means, and a block's sums are its tiles' sums added in tile-index order.
+ *   local search  per (view, block): `levels` levels of the grid rule above, the first centre init[b, v] ((0, 0) for a NULL `init`).  A
+ *                 level without a finite score keeps its centre.  With n the count of common valid pixels at the last level's best
+ *                 point, the block is ok when that point's score is finite and n >= min_valid * (the block's area in pixels), compared
+ *                 in fp64; field[b, v, i, j] is the best point of an ok block and init[b, v] otherwise.
+ *   field at (y, x)  nodes at the centres ((r0 + r1 - 1) / 2, (c0 + c1 - 1) / 2) of the blocks' rectangles.  Per axis k = the last node at
+ *                 or before the pixel, within [0, n - 2], t = clamp((p - node_k) / (node_{k+1} - node_k), 0, 1) (constant beyond the outer
+ *                 nodes; t = 0 with one block), and per component, in fp64 and in this order, (1 - ty) ((1 - tx) N00 + tx N01) + ty ((1 -
+ *                 tx) N10 + tx N11), rounded to fp32.
+ * hrn_mncc_local_blocks  n for an axis of length L; 0 for a `block` that is refused or L outside 1..16384.
+ * hrn_mncc_local_workspace_bytes  0 for arguments hrn_mncc_search_local refuses; else, with T and C as above and by x bx blocks,
+ *                      16 (B V + B) C  +  48 P^2 B V T  +  8 B V by bx   bytes.
+ * hrn_mncc_search_local  init (B,V,2) or NULL; field (B,V,by,bx,2) f32; trace (B,V,by,bx,levels,3) = (dy, dx, score) per level, or NULL;
+ *                 ok (B,V,by,bx) f32 1 / 0, or NULL; min_valid in [0, 1].  1 + 2 levels launches, nothing returns to the host.  With one
+ *                 block, NULL init and min_valid 0, field and trace are hrn_mncc_search_scene's shifts and trace bit for bit.
+ * hrn_mncc_apply_field  out (B,V,H,W) = S(view, the field at the pixel) and out_valid = V(mask, the same), each pixel by its own shift;
+ *                 invalid pixels of `out` are 0.  A constant field gives hrn_mncc_apply_scene's bits.  No workspace.
+ * Fixed-order sums, no atomics: bit-reproducible.  -2 before any launch as above (also: a block that is no multiple of 64 in 64..4096; B V
+ * by bx or B V T beyond 2^31 - 1; min_valid outside [0, 1]), -3 for a workspace that is too small. */
+int hrn_mncc_local_blocks(int L, int block);
+size_t hrn_mncc_local_workspace_bytes(int B, int V, int H, int W, int P, int block);
+int hrn_mncc_search_local(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* init, int B, int V,
+                          int H, int W, int P, int levels, float radius, int block, float min_valid, float* field, float* trace, float* ok,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int hrn_mncc_apply_field(const float* views, const float* view_masks, const float* field, int B, int V, int H, int W, int block, float* out,
                          float* out_valid, void* stream);
 
 /* ------------------------------------------------------------------ optimiser
