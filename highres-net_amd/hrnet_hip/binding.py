@@ -154,6 +154,12 @@ SIGNATURES = {
     "hrn_mncc_search_local": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 6 + [_c.c_float, _c.c_int, _c.c_float] + [_c.c_void_p] * 4
                               + [_c.c_size_t, _c.c_void_p]),
     "hrn_mncc_apply_field": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 5 + [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hrn_mncc_reduce2": (_c.c_int, [_c.c_void_p] * 2 + [_c.c_int] * 3 + [_c.c_void_p] * 3),
+    "hrn_mncc_search_scene_from": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 6 + [_c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                                                                                  _c.c_void_p]),
+    "hrn_mncc_pyramid_workspace_bytes": (_c.c_size_t, [_c.c_int] * 6),
+    "hrn_mncc_search_pyramid": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 7 + [_c.c_float, _c.c_int, _c.c_float] + [_c.c_void_p] * 3
+                                + [_c.c_size_t, _c.c_void_p]),
     "hrn_collate_device": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
                                       _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_collate_device_s": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64, _c.c_void_p,
@@ -915,6 +921,8 @@ def shift_loss_backward(srs, hrs, hr_maps, stats, d_out, metric="cPSNR", border_
 MNCC_SIDES, MNCC_POINTS, MNCC_LEVELS, MNCC_MAX_RADIUS = (16, 128), (3, 9), (1, 16), 4.0     # the limits of include/hrnet_hip.h
 MNCC_SCENE_SIDES = (16, 16384)
 MNCC_LOCAL_BLOCKS = (64, 4096)             # a block of the local search: a multiple of 64 within these
+MNCC_REDUCE_SIDES = (32, 16384)            # a plane reduce2 takes
+MNCC_OCTAVES, MNCC_PYRAMID_MAX_REACH = (0, 6), 128.0       # of the pyramid search; radius * 2^octaves in pixels of the frame
 
 
 def mncc_int(name, value, limits):
@@ -971,16 +979,28 @@ def _mncc_grid(scene, ref, ref_mask, views, view_masks, centres, points_per_dim,
     return scores
 
 
-def _mncc_search(scene, ref, ref_mask, views, view_masks, points_per_dim, levels, radius):
+def _mncc_init(init, B, V):
+    if init is not None:
+        init = _dev_f32(init, "init")
+        if tuple(init.shape) != (B, V, 2):
+            raise ValueError(f"init must be ({B}, {V}, 2); got {tuple(init.shape)}")
+    return init
+
+
+def _mncc_search(scene, ref, ref_mask, views, view_masks, points_per_dim, levels, radius, init=None, from_init=False):
     lib = load_library()
     ref, ref_mask, views, view_masks = _mncc_args(ref, ref_mask, views, view_masks)
     B, V, H, W = views.shape
     P, levels = mncc_int("points_per_dim", points_per_dim, MNCC_POINTS), mncc_int("levels", levels, MNCC_LEVELS)
+    init = _mncc_init(init, B, V)
     shifts = torch.empty((B, V, 2), dtype=torch.float32, device=views.device)
     trace = torch.empty((B, V, levels, 3), dtype=torch.float32, device=views.device)
     args = (_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks), B, V, H, W, P, levels, float(radius), _ptr(shifts), _ptr(trace))
     with torch.cuda.device(views.device):
-        if scene:
+        if from_init:
+            _check(lib.hrn_mncc_search_scene_from(*args[:4], _opt_ptr(init), *args[4:], *_mncc_scene_workspace(lib, B, V, H, W, P, views.device),
+                                                  _stream()), "hrn_mncc_search_scene_from")
+        elif scene:
             _check(lib.hrn_mncc_search_scene(*args, *_mncc_scene_workspace(lib, B, V, H, W, P, views.device), _stream()),
                    "hrn_mncc_search_scene")
         else:
@@ -1037,6 +1057,51 @@ def mncc_search_scene(ref, ref_mask, views, view_masks, points_per_dim=7, levels
 def mncc_apply_scene(views, view_masks, shifts):
     """mncc_apply for frames of any size (hrn_mncc_apply_scene); bit-identical to it where both run."""
     return _mncc_apply(True, views, view_masks, shifts)
+
+
+def mncc_search_scene_from(ref, ref_mask, views, view_masks, init, points_per_dim=7, levels=6, radius=1.0):
+    """mncc_search_scene with the first level's centre read from init (B,V,2) (hrn_mncc_search_scene_from); None: (0, 0)."""
+    return _mncc_search(True, ref, ref_mask, views, view_masks, points_per_dim, levels, radius, init, True)
+
+
+def mncc_reduce2(x, mask):
+    """x (N,H,W), mask (N,H,W) or None (all clear) -> (out (N,H//2,W//2), out_mask f32 1 / 0): the masked [1, 3, 3, 1] / 8 reduction of
+    include/hrnet_hip.h (hrn_mncc_reduce2)."""
+    lib = load_library()
+    x = _dev_f32(x, "x")
+    if x.dim() != 3:
+        raise ValueError(f"x must be (N,H,W); got {tuple(x.shape)}")
+    if mask is not None:
+        mask = _dev_f32(mask, "mask")
+        if mask.shape != x.shape:
+            raise ValueError(f"mask must have x's shape {tuple(x.shape)}; got {tuple(mask.shape)}")
+    N, H, W = x.shape
+    out = torch.empty((N, H // 2, W // 2), dtype=torch.float32, device=x.device)
+    out_mask = torch.empty_like(out)
+    with torch.cuda.device(x.device):
+        _check(lib.hrn_mncc_reduce2(_ptr(x), _opt_ptr(mask), N, H, W, _ptr(out), _ptr(out_mask), _stream()), "hrn_mncc_reduce2")
+    return out, out_mask
+
+
+def mncc_search_pyramid(ref, ref_mask, views, view_masks, octaves=2, points_per_dim=7, levels=6, radius=4.0, coarse_levels=3, refine_radius=1.0):
+    """The coarse-to-fine search (hrn_mncc_search_pyramid): -> (shifts (B,V,2) f32 in pixels of the frame, trace (B,V,octaves+1,3) f32 =
+    (dy, dx, score) of every octave's last level in that octave's pixels, coarsest first)."""
+    lib = load_library()
+    ref, ref_mask, views, view_masks = _mncc_args(ref, ref_mask, views, view_masks)
+    B, V, H, W = views.shape
+    P, levels = mncc_int("points_per_dim", points_per_dim, MNCC_POINTS), mncc_int("levels", levels, MNCC_LEVELS)
+    coarse_levels, K = mncc_int("coarse_levels", coarse_levels, MNCC_LEVELS), mncc_int("octaves", octaves, MNCC_OCTAVES)
+    shifts = torch.empty((B, V, 2), dtype=torch.float32, device=views.device)
+    trace = torch.empty((B, V, K + 1, 3), dtype=torch.float32, device=views.device)
+    with torch.cuda.device(views.device):
+        nbytes = lib.hrn_mncc_pyramid_workspace_bytes(B, V, H, W, P, K)
+        if nbytes == 0:
+            raise HrnetHipError(f"bad registration problem size B={B} V={V} H={H} W={W} P={P} octaves={K}")
+        ws = _workspace(nbytes, views.device, "mncc_pyramid")
+        _check(lib.hrn_mncc_search_pyramid(_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks), B, V, H, W, P, K, levels,
+                                           float(radius), coarse_levels, float(refine_radius), _ptr(shifts), _ptr(trace), _ptr(ws), ws.numel(),
+                                           _stream()), "hrn_mncc_search_pyramid")
+    return shifts, trace
 
 
 def mncc_block(block):
@@ -1601,6 +1666,43 @@ def _op_shift_field(views: torch.Tensor, view_masks: Optional[torch.Tensor], fie
 @_op_shift_field.register_fake
 def _fake_shift_field(views, view_masks, field, block):
     return views.new_empty(views.shape, dtype=torch.float32), views.new_empty(views.shape, dtype=torch.float32)
+
+
+# the masked pyramid and the coarse-to-fine search (registration_pyramid.hip)
+@torch.library.custom_op("hrnet_hip::reduce2", mutates_args=(), device_types="cuda")
+def _op_reduce2(x: torch.Tensor, mask: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    return mncc_reduce2(x, mask)
+
+
+@_op_reduce2.register_fake
+def _fake_reduce2(x, mask):
+    shape = (x.shape[0], x.shape[1] // 2, x.shape[2] // 2)
+    return x.new_empty(shape, dtype=torch.float32), x.new_empty(shape, dtype=torch.float32)
+
+
+@torch.library.custom_op("hrnet_hip::mncc_search_scene_from", mutates_args=(), device_types="cuda")
+def _op_mncc_search_scene_from(ref: torch.Tensor, ref_mask: Optional[torch.Tensor], views: torch.Tensor, view_masks: Optional[torch.Tensor],
+                               init: Optional[torch.Tensor], points_per_dim: int, levels: int,
+                               radius: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    return mncc_search_scene_from(ref, ref_mask, views, view_masks, init, points_per_dim, levels, radius)
+
+
+@_op_mncc_search_scene_from.register_fake
+def _fake_mncc_search_scene_from(ref, ref_mask, views, view_masks, init, points_per_dim, levels, radius):
+    return _fake_mncc_search(ref, ref_mask, views, view_masks, points_per_dim, levels, radius)
+
+
+@torch.library.custom_op("hrnet_hip::mncc_search_pyramid", mutates_args=(), device_types="cuda")
+def _op_mncc_search_pyramid(ref: torch.Tensor, ref_mask: Optional[torch.Tensor], views: torch.Tensor, view_masks: Optional[torch.Tensor],
+                            octaves: int, points_per_dim: int, levels: int, radius: float, coarse_levels: int,
+                            refine_radius: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    return mncc_search_pyramid(ref, ref_mask, views, view_masks, octaves, points_per_dim, levels, radius, coarse_levels, refine_radius)
+
+
+@_op_mncc_search_pyramid.register_fake
+def _fake_mncc_search_pyramid(ref, ref_mask, views, view_masks, octaves, points_per_dim, levels, radius, coarse_levels, refine_radius):
+    B, V = views.shape[:2]
+    return views.new_empty((B, V, 2), dtype=torch.float32), views.new_empty((B, V, octaves + 1, 3), dtype=torch.float32)
 
 
 @torch.library.custom_op("hrnet_hip::adam_step", mutates_args=("params", "exp_avg", "exp_avg_sq"), device_types="cuda")

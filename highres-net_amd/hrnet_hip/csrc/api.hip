@@ -570,4 +570,77 @@ int hrn_mncc_apply_field(const float* views, const float* view_masks, const floa
     return hrn_launch_mncc_apply_field(views, view_masks, field, B, V, H, W, block, out, out_valid, (hipStream_t)stream);
 }
 
+// the masked pyramid and the coarse-to-fine search over it (registration_pyramid.hip)
+int hrn_mncc_reduce2(const float* x, const float* mask, int N, int H, int W, float* out, float* out_mask, void* stream) {
+    HRN_CHECK(N > 0, -2, "hrn_mncc_reduce2: bad plane count N=%d", N);
+    HRN_CHECK(H >= HRN_MNCC_REDUCE_MIN_SIDE && H <= HRN_MNCC_SCENE_MAX_SIDE && W >= HRN_MNCC_REDUCE_MIN_SIDE && W <= HRN_MNCC_SCENE_MAX_SIDE, -2,
+              "hrn_mncc_reduce2: bad shape H=%d W=%d: the sides of a plane must be %d..%d", H, W, HRN_MNCC_REDUCE_MIN_SIDE, HRN_MNCC_SCENE_MAX_SIDE);
+    HRN_CHECK(hrn_mncc_reduce2_grid_fits((size_t)N, H, W), -2, "hrn_mncc_reduce2: N=%d planes of %d x %d exceed one launch", N, H, W);
+    HRN_CHECK(x && out && out_mask, -2, "hrn_mncc_reduce2: null argument");
+    return hrn_launch_mncc_reduce2(x, mask, (size_t)N, nullptr, nullptr, 0, H, W, out, out_mask, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int hrn_mncc_search_scene_from(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* init, int B,
+                               int V, int H, int W, int P, int levels, float radius, float* shifts, float* trace, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    if (int rc = mncc_scene_check("hrn_mncc_search_scene_from", B, V, H, W)) return rc;
+    if (int rc = mncc_check_points("hrn_mncc_search_scene_from", P)) return rc;
+    HRN_CHECK(levels >= 1 && levels <= HRN_MNCC_MAX_LEVELS, -2, "hrn_mncc_search_scene_from: levels %d outside 1..%d", levels, HRN_MNCC_MAX_LEVELS);
+    HRN_CHECK(radius > 0.f && radius <= 4.f, -2, "hrn_mncc_search_scene_from: radius %g outside (0, 4]", (double)radius);
+    HRN_CHECK(ref && views && shifts && workspace, -2, "hrn_mncc_search_scene_from: null argument");
+    HRN_CHECK(workspace_bytes >= hrn_mncc_scene_workspace_bytes_impl(B, V, H, W, P), -3, "hrn_mncc_search_scene_from: workspace too small");
+    return hrn_launch_mncc_search_scene_from(ref, ref_mask, views, view_masks, init, B, V, H, W, P, levels, radius, shifts, trace, nullptr, 0,
+                                             workspace, (hipStream_t)stream);
+}
+
+// what hrn_mncc_search_pyramid refuses beyond the scene search's own limits; `who` null: say nothing
+static int mncc_pyramid_check(const char* who, int H, int W, int octaves, float radius) {
+    const bool quiet = who == nullptr;
+    if (octaves < 0 || octaves > HRN_MNCC_MAX_OCTAVES) {
+        if (!quiet) hrn_set_error("%s: octaves %d outside 0..%d", who, octaves, HRN_MNCC_MAX_OCTAVES);
+        return -2;
+    }
+    if (!(radius > 0.f && radius <= 4.f)) {
+        if (!quiet) hrn_set_error("%s: radius %g outside (0, 4]", who, (double)radius);
+        return -2;
+    }
+    if (radius * (float)(1 << octaves) > HRN_MNCC_PYRAMID_MAX_REACH) {
+        if (!quiet) hrn_set_error("%s: radius %g over %d octaves reaches %g pixels, beyond %g", who, (double)radius, octaves,
+                                  (double)radius * (1 << octaves), (double)HRN_MNCC_PYRAMID_MAX_REACH);
+        return -2;
+    }
+    if (((H < W ? H : W) >> octaves) < HRN_MNCC_SCENE_MIN_SIDE) {
+        if (!quiet) hrn_set_error("%s: bad shape H=%d W=%d: octave %d of the frame must be at least %d a side", who, H, W, octaves,
+                                  HRN_MNCC_SCENE_MIN_SIDE);
+        return -2;
+    }
+    return 0;
+}
+
+size_t hrn_mncc_pyramid_workspace_bytes(int B, int V, int H, int W, int P, int octaves) {
+    if (hrn_mncc_scene_workspace_bytes(B, V, H, W, P) == 0 || mncc_pyramid_check(nullptr, H, W, octaves, 1.f) ||
+        (octaves > 0 && !hrn_mncc_reduce2_grid_fits((size_t)B * V + (size_t)B, H, W)))
+        return 0;
+    return hrn_mncc_pyramid_workspace_bytes_impl(B, V, H, W, P, octaves);
+}
+
+int hrn_mncc_search_pyramid(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H, int W,
+                            int P, int octaves, int levels, float radius, int coarse_levels, float refine_radius, float* shifts, float* trace,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "hrn_mncc_search_pyramid";
+    if (int rc = mncc_scene_check(who, B, V, H, W)) return rc;
+    if (int rc = mncc_check_points(who, P)) return rc;
+    HRN_CHECK(levels >= 1 && levels <= HRN_MNCC_MAX_LEVELS, -2, "%s: levels %d outside 1..%d", who, levels, HRN_MNCC_MAX_LEVELS);
+    HRN_CHECK(coarse_levels >= 1 && coarse_levels <= HRN_MNCC_MAX_LEVELS, -2, "%s: coarse_levels %d outside 1..%d", who, coarse_levels,
+              HRN_MNCC_MAX_LEVELS);
+    if (int rc = mncc_pyramid_check(who, H, W, octaves, radius)) return rc;
+    HRN_CHECK(refine_radius > 0.f && refine_radius <= 4.f, -2, "%s: refine_radius %g outside (0, 4]", who, (double)refine_radius);
+    HRN_CHECK(octaves == 0 || hrn_mncc_reduce2_grid_fits((size_t)B * V + (size_t)B, H, W), -2,
+              "%s: bad batch B=%d V=%d: the planes of %d x %d frames exceed one launch of the reduction", who, B, V, H, W);
+    HRN_CHECK(ref && views && shifts && workspace, -2, "%s: null argument", who);
+    HRN_CHECK(workspace_bytes >= hrn_mncc_pyramid_workspace_bytes_impl(B, V, H, W, P, octaves), -3, "%s: workspace too small", who);
+    return hrn_launch_mncc_search_pyramid(ref, ref_mask, views, view_masks, B, V, H, W, P, octaves, levels, radius, coarse_levels, refine_radius,
+                                          shifts, trace, workspace, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -77,6 +77,10 @@ int hrn_launch_mncc_grid_scene(const float* ref, const float* ref_mask, const fl
                                int B, int V, int H, int W, int P, float width, float* scores, void* workspace, hipStream_t stream);
 int hrn_launch_mncc_search_scene(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H,
                                  int W, int P, int levels, float radius, float* shifts, float* trace, void* workspace, hipStream_t stream);
+// the same from init (B,V,2) or null; last_trace / last_stride: where the last level's (dy, dx, score) goes when `trace` is null
+int hrn_launch_mncc_search_scene_from(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* init,
+                                      int B, int V, int H, int W, int P, int levels, float radius, float* shifts, float* trace,
+                                      float* last_trace, int last_stride, void* workspace, hipStream_t stream);
 int hrn_launch_mncc_apply_scene(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
                                 float* out_valid, hipStream_t stream);
 unsigned hrn_mncc_scene_mean_chunks(int H, int W);                 // the chunks of a frame's mean, and the pre-pass that fills
@@ -94,6 +98,18 @@ int hrn_launch_mncc_search_local(const float* ref, const float* ref_mask, const 
                                  float* trace, float* ok, void* workspace, hipStream_t stream);
 int hrn_launch_mncc_apply_field(const float* views, const float* view_masks, const float* field, int B, int V, int H, int W, int block,
                                 float* out, float* out_valid, hipStream_t stream);
+
+// ---- registration_pyramid.hip: the masked 2:1 reduction of planes and the coarse-to-fine search over `octaves` of them (DESIGN.md
+// section 7j).  reduce2 takes two sets of planes of one size in one launch (nb may be 0); a mask pointer may be null (all clear).
+constexpr int HRN_MNCC_REDUCE_MIN_SIDE = 32, HRN_MNCC_MAX_OCTAVES = 6;
+constexpr float HRN_MNCC_PYRAMID_MAX_REACH = 128.f;                // radius * 2^octaves, in pixels of the frame
+bool hrn_mncc_reduce2_grid_fits(size_t planes, int H, int W);
+int hrn_launch_mncc_reduce2(const float* a, const float* a_mask, size_t na, const float* b, const float* b_mask, size_t nb, int H, int W,
+                            float* a_out, float* a_out_mask, float* b_out, float* b_out_mask, hipStream_t stream);
+size_t hrn_mncc_pyramid_workspace_bytes_impl(int B, int V, int H, int W, int P, int octaves);
+int hrn_launch_mncc_search_pyramid(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H,
+                                   int W, int P, int octaves, int levels, float radius, int coarse_levels, float refine_radius, float* shifts,
+                                   float* trace, void* workspace, hipStream_t stream);
 
 // ---- shiftnet.hip.  dt: storage of the activation tensors x / out / y - HRN_F32 or HRN_BF16, one bf16 plane (ShiftNet's bf16
 // training mode); statistics, scale / shift and fc1's input xr are f32 in both

@@ -229,6 +229,15 @@ int hrn_launch_mncc_grid_scene(const float* ref, const float* ref_mask, const fl
 
 int hrn_launch_mncc_search_scene(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H,
                                  int W, int P, int levels, float radius, float* shifts, float* trace, void* workspace, hipStream_t stream) {
+    return hrn_launch_mncc_search_scene_from(ref, ref_mask, views, view_masks, nullptr, B, V, H, W, P, levels, radius, shifts, trace, nullptr, 0,
+                                             workspace, stream);
+}
+
+// The search with its first centre read from init (B,V,2); null: (0, 0).  last_trace (used where `trace` is null; may be null): the last
+// level's (dy, dx, score) of view v goes to last_trace[v * last_stride] (registration_pyramid.hip: one row per octave).
+int hrn_launch_mncc_search_scene_from(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* init,
+                                      int B, int V, int H, int W, int P, int levels, float radius, float* shifts, float* trace,
+                                      float* last_trace, int last_stride, void* workspace, hipStream_t stream) {
     const ScenePlan p = plan(B, V, H, W, P);
     const SceneWorkspace w = carve(workspace, p);
     const unsigned bv = (unsigned)(B * V);
@@ -238,13 +247,14 @@ int hrn_launch_mncc_search_scene(const float* ref, const float* ref_mask, const 
     double width = (double)(2.f * radius);
     const double ratio = level_ratio(P);
     for (int k = 0; k < levels; ++k) {
-        const float* centres = k ? w.centres : nullptr;          // the first centre is (0, 0)
+        const float* centres = k ? w.centres : init;             // the first centre is init's, (0, 0) without one
+        const bool last = k == levels - 1;
         hipLaunchKernelGGL(scene_level_kernel, dim3(bv * p.tiles), dim3(SC_THREADS), 0, stream, ref, ref_mask, views, view_masks, centres,
                            (const double*)w.means, p.chunks, bv, V, H, W, P, width, p.tiles_x, p.tiles, w.sums);
         HRN_LAUNCH_CHECK();
         hipLaunchKernelGGL(scene_finish_kernel, dim3(bv), dim3(SC_FINISH_THREADS), 0, stream, (const double*)w.sums, centres, P, width, p.tiles,
-                           (float*)nullptr, w.centres, trace ? trace + 3 * k : (float*)nullptr, 3 * levels,
-                           k == levels - 1 ? shifts : (float*)nullptr);
+                           (float*)nullptr, w.centres, trace ? trace + 3 * k : (last ? last_trace : (float*)nullptr),
+                           trace ? 3 * levels : last_stride, last ? shifts : (float*)nullptr);
         HRN_LAUNCH_CHECK();
         width = width * ratio;
     }

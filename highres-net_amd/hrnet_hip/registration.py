@@ -18,7 +18,11 @@ arguments, same errors; `shift_scene` is bit-identical to `shift_views` where bo
 
 `mncc_search_local`, `shift_field` and `register_scene_local` find and apply a shift FIELD on the scene path: one
 shift per block of `block` x `block` pixels of every view, searched from the view's global shift on the same tiles, and every pixel
-resampled by the bilinear field between the blocks' centres.  `local_blocks` is the library's own count of the blocks."""
+resampled by the bilinear field between the blocks' centres.  `local_blocks` is the library's own count of the blocks.
+
+`reduce2`, `mncc_search_pyramid` and `register_scene_pyramid` take the scene search beyond its reach of `radius` <= 4 pixels (DESIGN.md
+section 7j): a masked image pyramid of `octaves` 2:1 reductions, the coarsest octave searched from (0, 0) and every finer one from twice
+the shift of the octave above - `mncc_search_scene(init=...)`.  The reach is radius * 2**octaves pixels."""
 import torch
 
 from . import binding
@@ -81,13 +85,25 @@ def mncc_search(lrs, lr_masks=None, ref=None, ref_mask=None, points_per_dim=7, l
     return _search(False, lrs, lr_masks, ref, ref_mask, points_per_dim, levels, radius, return_trace)
 
 
-def _search(scene, lrs, lr_masks, ref, ref_mask, points_per_dim, levels, radius, return_trace):
+def _init(init, lrs):
+    if init is not None:
+        if not torch.is_tensor(init):
+            raise TypeError(f"init must be a torch.Tensor or None; got {type(init).__name__}")
+        if tuple(init.shape) != tuple(lrs.shape[:2]) + (2,):
+            raise ValueError(f"init must be (B,V,2) = {tuple(lrs.shape[:2]) + (2,)}; got {tuple(init.shape)}")
+
+
+def _search(scene, lrs, lr_masks, ref, ref_mask, points_per_dim, levels, radius, return_trace, init=None):
     _frames(lrs, lr_masks, scene)
     ref, ref_mask = _reference(lrs, lr_masks, ref, ref_mask)
     P, levels, radius = _search_args(points_per_dim, levels, radius)
-    _on_device(lrs=lrs, lr_masks=lr_masks, ref=ref, ref_mask=ref_mask)
-    op = torch.ops.hrnet_hip.mncc_search_scene if scene else torch.ops.hrnet_hip.mncc_search
-    shifts, trace = op(ref, ref_mask, lrs, lr_masks, P, levels, radius)
+    _init(init, lrs)
+    _on_device(lrs=lrs, lr_masks=lr_masks, ref=ref, ref_mask=ref_mask, init=init)
+    if init is not None:
+        shifts, trace = torch.ops.hrnet_hip.mncc_search_scene_from(ref, ref_mask, lrs, lr_masks, init, P, levels, radius)
+    else:
+        op = torch.ops.hrnet_hip.mncc_search_scene if scene else torch.ops.hrnet_hip.mncc_search
+        shifts, trace = op(ref, ref_mask, lrs, lr_masks, P, levels, radius)
     return (shifts, trace) if return_trace else shifts
 
 
@@ -142,11 +158,11 @@ def register_views(lrs, lr_masks=None, **search_kwargs):
 
 
 # ----------------------------------------------------------------------------- the same four for frames of any size (section 7g)
-def mncc_search_scene(lrs, lr_masks=None, ref=None, ref_mask=None, points_per_dim=7, levels=6, radius=1.0, return_trace=False):
+def mncc_search_scene(lrs, lr_masks=None, ref=None, ref_mask=None, points_per_dim=7, levels=6, radius=1.0, return_trace=False, init=None):
     """`mncc_search` for frames of 16..16384 pixels a side: 1 + 2 levels launches of `hrn_mncc_search_scene` on tiles of 64 x 64, no
     return to the host between them.  The level-k scores are `mncc_grid_scene`'s bit for bit, and a view's result does not depend on
-    the batch around it."""
-    return _search(True, lrs, lr_masks, ref, ref_mask, points_per_dim, levels, radius, return_trace)
+    the batch around it.  init (B,V,2): the first level's centre per view (`hrn_mncc_search_scene_from`); None: (0, 0)."""
+    return _search(True, lrs, lr_masks, ref, ref_mask, points_per_dim, levels, radius, return_trace, init)
 
 
 def mncc_grid_scene(lrs, lr_masks=None, ref=None, ref_mask=None, centres=None, points_per_dim=7, width=2.0):
@@ -194,11 +210,7 @@ def mncc_search_local(lrs, lr_masks=None, ref=None, ref_mask=None, block=128, in
     ref, ref_mask = _reference(lrs, lr_masks, ref, ref_mask)
     P, levels, radius = _search_args(points_per_dim, levels, radius)
     block, min_valid = _local_args(block, min_valid)
-    if init is not None:
-        if not torch.is_tensor(init):
-            raise TypeError(f"init must be a torch.Tensor or None; got {type(init).__name__}")
-        if tuple(init.shape) != tuple(lrs.shape[:2]) + (2,):
-            raise ValueError(f"init must be (B,V,2) = {tuple(lrs.shape[:2]) + (2,)}; got {tuple(init.shape)}")
+    _init(init, lrs)
     _on_device(lrs=lrs, lr_masks=lr_masks, ref=ref, ref_mask=ref_mask, init=init)
     field, trace, ok = torch.ops.hrnet_hip.mncc_search_local(ref, ref_mask, lrs, lr_masks, init, P, levels, radius, block, min_valid)
     return (field, trace, ok) if return_trace else field
@@ -218,15 +230,84 @@ def shift_field(lrs, lr_masks, field, block):
     return torch.ops.hrnet_hip.shift_field(lrs, lr_masks, field, block)
 
 
-def register_scene_local(lrs, lr_masks=None, block=128, local_levels=4, local_radius=0.5, min_valid=0.25, **search_kwargs):
+def register_scene_local(lrs, lr_masks=None, block=128, local_levels=4, local_radius=0.5, min_valid=0.25, octaves=0, **search_kwargs):
     """mncc_search_scene with search_kwargs (ref, ref_mask, points_per_dim, levels, radius), mncc_search_local from those shifts with
-    local_levels levels of local_radius, then shift_field: -> (registered, valid, field, shifts)."""
+    local_levels levels of local_radius, then shift_field: -> (registered, valid, field, shifts).  octaves > 0: the global shifts come
+    from mncc_search_pyramid over that many octaves instead (search_kwargs then also takes coarse_levels and refine_radius, and radius
+    defaults to the pyramid's)."""
     if "return_trace" in search_kwargs:
         raise TypeError("register_scene_local returns no trace: call mncc_search_scene and mncc_search_local(..., return_trace=True)")
     _local_args(block, min_valid)
     _search_args(search_kwargs.get("points_per_dim", 7), local_levels, local_radius)
-    shifts = mncc_search_scene(lrs, lr_masks, **search_kwargs)
+    octaves = binding.mncc_int("octaves", octaves, binding.MNCC_OCTAVES)
+    shifts = mncc_search_pyramid(lrs, lr_masks, octaves=octaves, **search_kwargs) if octaves else mncc_search_scene(lrs, lr_masks, **search_kwargs)
     local = {k: search_kwargs[k] for k in ("ref", "ref_mask", "points_per_dim") if k in search_kwargs}
     field = mncc_search_local(lrs, lr_masks, block=block, init=shifts, levels=local_levels, radius=local_radius, min_valid=min_valid, **local)
     registered, valid = shift_field(lrs, lr_masks, field, block)
     return registered, valid, field, shifts
+
+
+# ----------------------------------------------------------------------------- coarse to fine: shifts beyond the search's reach (section 7j)
+def reduce2(frames, masks=None):
+    """frames (B,V,H,W) or (B,H,W), masks of the same shape or None (all clear) -> (reduced, reduced_masks) of (..., H // 2, W // 2): the
+    masked [1, 3, 3, 1] / 8 reduction of include/hrnet_hip.h.  A coarse pixel is clear where more than half of its weight lies on clear
+    pixels of the frame, and exactly 0 otherwise; the masks come back as f32 1 / 0.  Sides are 32..16384, odd ones allowed.  A shift d
+    of the frames is a shift d / 2 of the reduced frames."""
+    if not torch.is_tensor(frames):
+        raise TypeError(f"frames must be a torch.Tensor; got {type(frames).__name__}")
+    if frames.dim() not in (3, 4):
+        raise ValueError(f"frames must be (B,V,H,W) or (B,H,W); got {tuple(frames.shape)}")
+    if masks is not None:
+        if not torch.is_tensor(masks):
+            raise TypeError(f"masks must be a torch.Tensor or None; got {type(masks).__name__}")
+        if masks.shape != frames.shape:
+            raise ValueError(f"masks must have the shape of frames, {tuple(frames.shape)}; got {tuple(masks.shape)}")
+    lo, hi = binding.MNCC_REDUCE_SIDES
+    H, W = frames.shape[-2:]
+    if not (lo <= H <= hi and lo <= W <= hi):
+        raise ValueError(f"frames must be {lo}..{hi} pixels a side; got {(H, W)}")
+    _on_device(frames=frames, masks=masks)
+    out, out_masks = torch.ops.hrnet_hip.reduce2(frames.reshape(-1, H, W), None if masks is None else masks.reshape(-1, H, W))
+    shape = tuple(frames.shape[:-2]) + (H // 2, W // 2)
+    return out.reshape(shape), out_masks.reshape(shape)
+
+
+def _pyramid_args(shape, octaves, radius, coarse_levels, refine_radius):
+    octaves = binding.mncc_int("octaves", octaves, binding.MNCC_OCTAVES)
+    coarse_levels = binding.mncc_int("coarse_levels", coarse_levels, binding.MNCC_LEVELS)
+    refine_radius = float(refine_radius)
+    if not 0.0 < refine_radius <= binding.MNCC_MAX_RADIUS:
+        raise ValueError(f"refine_radius must be in (0, {binding.MNCC_MAX_RADIUS:g}]; got {refine_radius}")
+    if radius * 2 ** octaves > binding.MNCC_PYRAMID_MAX_REACH:
+        raise ValueError(f"radius * 2**octaves must be at most {binding.MNCC_PYRAMID_MAX_REACH:g} pixels; got {radius} * 2**{octaves}")
+    if min(shape[2], shape[3]) >> octaves < binding.MNCC_SCENE_SIDES[0]:
+        raise ValueError(f"octave {octaves} of the frames must be at least {binding.MNCC_SCENE_SIDES[0]} pixels a side; the frames are "
+                         f"{tuple(shape[2:])}")
+    return octaves, coarse_levels, refine_radius
+
+
+def mncc_search_pyramid(lrs, lr_masks=None, ref=None, ref_mask=None, octaves=2, points_per_dim=7, levels=6, radius=4.0, coarse_levels=3,
+                        refine_radius=1.0, return_trace=False):
+    """`mncc_search_scene` for shifts of up to radius * 2**octaves pixels (at most 128): -> shifts (B,V,2) f32 in pixels of the frames.
+    Octaves 1..octaves of the views and the reference are built with `reduce2`; the coarsest is searched from (0, 0) with `radius`, each
+    finer one from twice the shift of the octave above with `refine_radius`; octave 0 takes `levels` levels, the others `coarse_levels`.
+    One call of `hrn_mncc_search_pyramid`: nothing returns to the host in between.  octaves=0 is `mncc_search_scene`, bit for bit.
+    return_trace: also (B,V,octaves+1,3) = (dy, dx, score) of every octave's last level in that octave's pixels, coarsest first.  Not
+    differentiable."""
+    _frames(lrs, lr_masks, True)
+    ref, ref_mask = _reference(lrs, lr_masks, ref, ref_mask)
+    P, levels, radius = _search_args(points_per_dim, levels, radius)
+    octaves, coarse_levels, refine_radius = _pyramid_args(lrs.shape, octaves, radius, coarse_levels, refine_radius)
+    _on_device(lrs=lrs, lr_masks=lr_masks, ref=ref, ref_mask=ref_mask)
+    shifts, trace = torch.ops.hrnet_hip.mncc_search_pyramid(ref, ref_mask, lrs, lr_masks, octaves, P, levels, radius, coarse_levels, refine_radius)
+    return (shifts, trace) if return_trace else shifts
+
+
+def register_scene_pyramid(lrs, lr_masks=None, **search_kwargs):
+    """mncc_search_pyramid, then shift_scene by what it found: -> (registered, valid, shifts).  search_kwargs: ref, ref_mask, octaves,
+    points_per_dim, levels, radius, coarse_levels, refine_radius."""
+    if "return_trace" in search_kwargs:
+        raise TypeError("register_scene_pyramid returns no trace: call mncc_search_pyramid(..., return_trace=True) and shift_scene")
+    shifts = mncc_search_pyramid(lrs, lr_masks, **search_kwargs)
+    registered, valid = shift_scene(lrs, lr_masks, shifts)
+    return registered, valid, shifts

@@ -402,6 +402,48 @@ int hrn_mncc_search_local(const float* ref, const float* ref_mask, const float* 
 int hrn_mncc_apply_field(const float* views, const float* view_masks, const float* field, int B, int V, int H, int W, int block, float* out,
                          float* out_valid, void* stream);
 
+/* ------------------------------------------------------------------ coarse-to-fine: a masked pyramid under the scene search
+ * Nothing in the reference stands behind these: its search starts at (0, 0) with a fixed reach.  hrn_mncc_search_scene reaches `radius`
+ * <= 4 pixels from (0, 0); beyond that it returns a confident wrong shift.  A pyramid of K octaves reaches radius 2^K pixels.
+ * tests/registration_pyramid_ref.py restates all of this in fp64.
+ *   reduce2       a plane (H, W) with a mask -> a plane (H / 2, W / 2) with a mask (integer halves; sides 32..16384, odd sides allowed).
+ *                 Weights w = [1, 3, 3, 1] / 8 per axis; coarse pixel (Y, X) reads fine rows 2Y - 1 .. 2Y + 2 and fine columns 2X - 1 ..
+ *                 2X + 2.  m = 1 where the fine pixel is inside the frame and clear (mask != 0; a NULL mask: every pixel of the frame is
+ *                 clear), else 0.  den = sum over the 16 taps of w_a w_b m, num = sum of w_a w_b (m ? x : 0), taps in row-major order,
+ *                 num by fused multiply-adds in fp32.  The coarse pixel is clear iff den > 0.5 (V(M, s)'s threshold); its value is num /
+ *                 den when clear and exactly 0 otherwise; the coarse mask is always written, f32 1 / 0.  den adds multiples of 1/64 up to
+ *                 1, so it is exact in fp32 and the coarse mask equals its fp64 restatement everywhere.  The filter is even and
+ *                 symmetric and reference and view are reduced alike: a fine shift d is a coarse shift d / 2, with no offset.
+ *   search from a centre   hrn_mncc_search_scene with the first level's centre read from init (B,V,2) instead of (0, 0); nothing else
+ *                 differs.  A NULL init is hrn_mncc_search_scene, bit for bit.
+ *   pyramid search  K = octaves in 0..6.  Octaves 1..K of the views with their masks and of the reference with its mask are built by
+ *                 reduce2, octave k from octave k - 1.  Octave K is searched from (0, 0) with `radius`; each octave k < K from 2 x (the
+ *                 shift of octave k + 1) - exact in fp32 - with `refine_radius`.  Octave 0 takes `levels` levels, every other octave
+ *                 `coarse_levels`.  A view without a finite score at an octave keeps its centre, as in the search.  With K = 0 the result
+ *                 is hrn_mncc_search_scene's bit for bit.  The reach is radius 2^K pixels of the frame.
+ * hrn_mncc_reduce2  x (N,H,W), mask (N,H,W) or NULL -> out (N,H/2,W/2), out_mask (N,H/2,W/2).  One launch, no workspace.
+ * hrn_mncc_search_scene_from  hrn_mncc_search_scene's arguments and workspace (hrn_mncc_scene_workspace_bytes) plus init (B,V,2) or NULL.
+ * hrn_mncc_pyramid_workspace_bytes  0 for arguments hrn_mncc_search_pyramid refuses (radii and levels aside); else, with H_k = H >> k, W_k
+ *                 = W >> k and r16 rounding up to a multiple of 16,
+ *                     sum_{k=1..K} r16(8 (B V + B) H_k W_k)  +  r16(hrn_mncc_scene_workspace_bytes(B, V, H, W, P))  +  16 B V   bytes:
+ *                 the reduced views, view masks, references and reference masks of every octave, the scene search's workspace of the base
+ *                 size (a coarser octave uses its front), and two (B,V,2) centre buffers.  The workspace must be 16-byte aligned.
+ * hrn_mncc_search_pyramid  shifts (B,V,2) in pixels of the frame; trace (B,V,K+1,3) = (dy, dx, score) or NULL: row j is the last level of
+ *                 octave K - j, in that octave's pixels - coarsest first, row K is `shifts` and its score.  2 K + (1 + 2 levels) + K (1 + 2
+ *                 coarse_levels) launches; nothing returns to the host at any point.
+ * Fixed-order arithmetic, no atomics: bit-reproducible.  -2 before any launch, with hrn_last_error() naming the fault: what
+ * hrn_mncc_search_scene refuses; reduce2: N not positive, a side outside 32..16384, N ceil(H/32) ceil(W/128) beyond 2^31 - 1; the
+ * pyramid: octaves outside 0..6, coarse_levels outside 1..16, refine_radius outside (0, 4], radius 2^octaves > 128, min(H, W) >> octaves
+ * < 16.  -3 for a workspace that is too small. */
+int hrn_mncc_reduce2(const float* x, const float* mask, int N, int H, int W, float* out, float* out_mask, void* stream);
+int hrn_mncc_search_scene_from(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* init, int B,
+                               int V, int H, int W, int P, int levels, float radius, float* shifts, float* trace, void* workspace,
+                               size_t workspace_bytes, void* stream);
+size_t hrn_mncc_pyramid_workspace_bytes(int B, int V, int H, int W, int P, int octaves);
+int hrn_mncc_search_pyramid(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H, int W,
+                            int P, int octaves, int levels, float radius, int coarse_levels, float refine_radius, float* shifts, float* trace,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ optimiser
  * hrn_adam_step  <-  optimizer.step() of torch.optim.Adam (src/train.py:191, :252), one launch over a flat fp32 buffer
  *                    holding every parameter of both models (the buffer the gradient all-reduce also works on):
