@@ -141,6 +141,8 @@ SIGNATURES = {
     "hrn_shift_loss_train": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p] + [_c.c_int] * 6 + [_c.c_void_p, _c.c_void_p, _c.c_void_p,
                                                                                                   _c.c_size_t, _c.c_void_p]),
     "hrn_shift_loss_backward": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 6 + [_c.c_void_p, _c.c_void_p]),
+    "hrn_shift_cssim_workspace_bytes": (_c.c_size_t, [_c.c_int] * 5),
+    "hrn_shift_cssim": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 7 + [_c.c_float] + [_c.c_void_p] * 4 + [_c.c_size_t, _c.c_void_p]),
     "hrn_mncc_grid": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 5 + [_c.c_float, _c.c_void_p, _c.c_void_p]),
     "hrn_mncc_search": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_mncc_apply": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 4 + [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
@@ -915,6 +917,38 @@ def shift_loss_backward(srs, hrs, hr_maps, stats, d_out, metric="cPSNR", border_
     return d_srs
 
 
+CSSIM_WINDOWS = {"gaussian": (0, 11), "uniform": (1, 7)}      # name -> (hrn_shift_cssim's `window`, taps)
+
+
+def shift_cssim(srs, hrs, hr_maps, border_w=3, window="gaussian", clip=True, correct_bias=True, data_range=1.0):
+    """The shift-searched, brightness-corrected SSIM (include/hrnet_hip.h) on (B,H,W) frames: -> (out (B,) f32,
+    stats (B,4) f64 = {n, bias, score, k} of the selected offset k = u (2 border_w + 1) + v, scores (B, (2 border_w + 1)^2) f64 =
+    the score of every offset, -inf where an offset has no clear pixel)."""
+    lib = load_library()
+    if window not in CSSIM_WINDOWS:
+        raise ValueError(f"window must be one of {sorted(CSSIM_WINDOWS)}; got {window!r}")
+    code, taps = CSSIM_WINDOWS[window]
+    srs, hrs, hr_maps = _dev_f32(srs, "srs"), _dev_f32(hrs, "hrs"), _dev_f32(hr_maps, "hr_maps")
+    if srs.dim() != 3 or srs.shape != hrs.shape or srs.shape != hr_maps.shape:
+        raise ValueError(f"srs, hrs, hr_maps must be equal (B,H,W) tensors; got {tuple(srs.shape)}, {tuple(hrs.shape)}, {tuple(hr_maps.shape)}")
+    border_w, data_range = int(border_w), float(data_range)
+    if border_w < 0 or border_w > 8 or min(srs.shape[1:]) < 2 * border_w + taps:
+        raise ValueError(f"border_w must be 0..8 and each side at least 2 border_w + {taps} (the {window} window); got {border_w} for "
+                         f"frames {tuple(srs.shape[1:])}")
+    if not data_range > 0.0:
+        raise ValueError(f"data_range must be positive; got {data_range}")
+    B, H, W = srs.shape
+    nk = (2 * border_w + 1) ** 2
+    out = torch.empty((B,), dtype=torch.float32, device=srs.device)
+    stats = torch.empty((B, 4), dtype=torch.float64, device=srs.device)
+    scores = torch.empty((B, nk), dtype=torch.float64, device=srs.device)
+    with torch.cuda.device(srs.device):
+        ws = _workspace(lib.hrn_shift_cssim_workspace_bytes(B, H, W, border_w, code), srs.device, "shift_cssim")
+        _check(lib.hrn_shift_cssim(_ptr(srs), _ptr(hrs), _ptr(hr_maps), B, H, W, border_w, code, int(bool(clip)), int(bool(correct_bias)),
+                                   data_range, _ptr(out), _ptr(stats), _ptr(scores), _ptr(ws), ws.numel(), _stream()), "hrn_shift_cssim")
+    return out, stats, scores
+
+
 # --------------------------------------------------------------------------- sub-pixel registration of LR views (registration.hip,
 # registration_scene.hip).  Every call below has a `scene` form for frames of any size; the two differ in the entry point, in the
 # workspace the scene form allocates, and in the limit on a frame's side, nothing else.
@@ -1583,6 +1617,21 @@ def _shift_loss_backward(ctx, d_out, _d_stats):
 
 
 _op_shift_loss_train.register_autograd(_shift_loss_backward, setup_context=_shift_loss_setup)
+
+
+# cSSIM is a score: no autograd formula.
+@torch.library.custom_op("hrnet_hip::shift_cssim", mutates_args=(), device_types="cuda")
+def _op_shift_cssim(srs: torch.Tensor, hrs: torch.Tensor, hr_maps: torch.Tensor, border_w: int, window: str, clip: bool,
+                    correct_bias: bool, data_range: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The shift-searched SSIM: (score per sample (B,), stats (B,4) f64 = {n, bias, score, k}, scores (B, (2 border_w + 1)^2) f64)."""
+    return shift_cssim(srs, hrs, hr_maps, border_w, window, clip, correct_bias, data_range)
+
+
+@_op_shift_cssim.register_fake
+def _(srs, hrs, hr_maps, border_w, window, clip, correct_bias, data_range):
+    B = srs.shape[0]
+    return (srs.new_empty((B,), dtype=torch.float32), srs.new_empty((B, 4), dtype=torch.float64),
+            srs.new_empty((B, (2 * border_w + 1) ** 2), dtype=torch.float64))
 
 
 # The registration search has no autograd formula: a shift found by a grid search is piecewise constant in the frames.

@@ -441,6 +441,34 @@ int hrn_shift_loss_backward(const float* srs, const float* hrs, const float* map
     return hrn_launch_shift_loss_backward(srs, hrs, maps, stats, d_out, B, H, W, border, metric, clip != 0, d_srs, (hipStream_t)stream);
 }
 
+// the shift-searched SSIM (cssim.hip): the same crops and offsets, no gradient
+static int shift_cssim_check(const char* who, int B, int H, int W, int border, int window) {
+    HRN_CHECK(border >= 0 && border <= 8, -2, "%s: border %d outside 0..8", who, border);
+    HRN_CHECK(window == 0 || window == 1, -2, "%s: window must be 0 (gaussian, 11 taps) or 1 (uniform, 7 taps); got %d", who, window);
+    const int side = 2 * border + (window == 1 ? 7 : 11);
+    HRN_CHECK(B > 0 && H >= side && W >= side, -2, "%s: bad shape B=%d H=%d W=%d: a side must be at least 2 border + taps = %d", who, B, H, W,
+              side);
+    HRN_CHECK(B <= 65535, -2, "%s: batch %d exceeds the grid limit", who, B);
+    return 0;
+}
+
+size_t hrn_shift_cssim_workspace_bytes(int B, int H, int W, int border, int window) {
+    if (border < 0 || border > 8 || (window != 0 && window != 1)) return 0;
+    const int side = 2 * border + (window == 1 ? 7 : 11);
+    if (B <= 0 || B > 65535 || H < side || W < side) return 0;
+    return hrn_shift_cssim_workspace_bytes_impl(B, H, W, border, window);
+}
+
+int hrn_shift_cssim(const float* srs, const float* hrs, const float* maps, int B, int H, int W, int border, int window, int clip,
+                    int correct_bias, float data_range, float* out, double* stats, double* scores, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = shift_cssim_check("hrn_shift_cssim", B, H, W, border, window)) return rc;
+    HRN_CHECK(data_range > 0.f && data_range <= 3.0e38f, -2, "hrn_shift_cssim: data_range must be positive and finite (got %g)", (double)data_range);
+    HRN_CHECK(srs && hrs && maps && out && stats && ws, -2, "hrn_shift_cssim: null argument");
+    HRN_CHECK(ws_bytes >= hrn_shift_cssim_workspace_bytes_impl(B, H, W, border, window), -3, "hrn_shift_cssim: workspace too small");
+    return hrn_launch_shift_cssim(srs, hrs, maps, B, H, W, border, window, clip != 0, correct_bias != 0, data_range, out, stats, scores, ws,
+                                  (hipStream_t)stream);
+}
+
 // the masked-NCC registration search (registration.hip): the reference fork's recursive_mncc_search / compute_grid_mncc, restated
 static int mncc_check(const char* who, int B, int V, int H, int W, int lo = HRN_MNCC_MIN_SIDE, int hi = HRN_MNCC_MAX_SIDE) {
     HRN_CHECK(B > 0 && V > 0 && (long)B * V <= 0x7fffffffL, -2, "%s: bad batch B=%d V=%d", who, B, V);

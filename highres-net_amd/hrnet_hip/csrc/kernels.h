@@ -55,6 +55,14 @@ int hrn_launch_shift_loss_train(const float* srs, const float* hrs, const float*
 int hrn_launch_shift_loss_backward(const float* srs, const float* hrs, const float* maps, const double* stats, const float* d_out, int B,
                                    int H, int W, int border, int metric, int clip, float* d_srs, hipStream_t stream);
 
+// ---- cssim.hip: the shift-searched, brightness-corrected SSIM (the definition is in include/hrnet_hip.h), over
+// shift_loss.hip's crops and offsets.  window: 0 = 11-tap Gaussian, 1 = 7-tap uniform; H, W >= 2 border + taps.  out [B], stats [B][4] =
+// {n*, bias*, score*, k*}, scores [B][(2 border + 1)^2] (may be null).  The callers have checked the arguments.
+size_t hrn_shift_cssim_workspace_bytes_impl(int B, int H, int W, int border, int window);
+int hrn_launch_shift_cssim(const float* srs, const float* hrs, const float* maps, int B, int H, int W, int border, int window, int clip,
+                           int correct_bias, float data_range, float* out, double* stats, double* scores, void* workspace,
+                           hipStream_t stream);
+
 // ---- registration.hip: the masked-NCC sub-pixel registration of LR views (the definitions are in
 // include/hrnet_hip.h).  One workgroup per view; a mask pointer may be null (all ones); the callers have checked the limits below.
 constexpr int HRN_MNCC_MIN_SIDE = 16, HRN_MNCC_MAX_SIDE = 128;     // a view, its row-pass buffer and its mask patterns fit one CU's LDS

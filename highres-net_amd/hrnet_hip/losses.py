@@ -10,7 +10,11 @@ d(srs) with b held constant - the reference detaches it (train.py:83).  Without 
 `shift_loss(srs, hrs, hr_maps, metric, border_w, clip)` is the score the project is judged on, as a loss: shift_cPSNR's search over the
 (2 border_w + 1)^2 integer offsets of the target (Evaluator.py:52-73) around the same brightness-corrected cMSE, differentiable through
 the selected offset (`torch.ops.hrnet_hip.shift_loss_train` / `.shift_loss_backward`).  It has no parameters, takes frames of any size
-and aspect ratio, and is bit-reproducible: the training tail that needs no ShiftNet."""
+and aspect ratio, and is bit-reproducible: the training tail that needs no ShiftNet.
+
+`shift_cssim(srs, hrs, hr_maps, border_w, clip, window, data_range, correct_bias)` is the second score: structural similarity between the
+clear pixels of the target and the brightness-corrected prediction, searched over the same offsets (`torch.ops.hrnet_hip.shift_cssim`
+over `hrn_shift_cssim`).  It is a score, not a loss: it has no gradient."""
 import torch
 
 from . import binding
@@ -58,3 +62,44 @@ def shift_loss(srs, hrs, hr_maps, metric="cPSNR", border_w=3, clip=False, return
     k = stats[:, 3].detach().long()
     nb = 2 * border_w + 1
     return out, torch.stack([torch.div(k, nb, rounding_mode="floor") - border_w, k % nb - border_w], 1)
+
+
+def shift_cssim(srs, hrs, hr_maps, border_w=3, clip=True, window="gaussian", data_range=1.0, correct_bias=True, return_shift=False,
+                return_scores=False):
+    """(B,H,W) x 3 -> (B,): the highest SSIM over the integer offsets (u - border_w, v - border_w), |.| <= border_w, between m hrs and
+    m (srs + bias) on the centre crop of `srs`, m the clear pixels of the offset and bias its brightness correction (0 without
+    correct_bias).  window: "gaussian" (11 taps, sigma 1.5) or "uniform" (7 taps, sample covariance), over the positions where the
+    window fits; data_range: the L of C1 = (0.01 L)^2, C2 = (0.03 L)^2.  clip clamps srs to [0, 1] first.  A (B,1,H,W) `srs` is taken as
+    srs[:, 0].  No gradient.  return_shift: also the (B,2) int64 offsets (row, column) selected, as shift_loss returns them (a
+    (-border_w - 1, ...) row marks a sample without an eligible offset, whose score is NaN).  return_scores: also the (B, (2 border_w
+    + 1)^2) float64 score of every offset, -inf where the offset has no clear pixel."""
+    for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name} must be a torch.Tensor; got {type(t).__name__}")
+    if window not in binding.CSSIM_WINDOWS:
+        raise ValueError(f"window must be one of {sorted(binding.CSSIM_WINDOWS)}; got {window!r}")
+    taps = binding.CSSIM_WINDOWS[window][1]
+    if srs.dim() == 4 and srs.shape[1] == 1:
+        srs = srs[:, 0]
+    if srs.dim() != 3 or srs.shape != hrs.shape or srs.shape != hr_maps.shape:
+        raise ValueError(f"srs, hrs, hr_maps must be equal (B,H,W) tensors; got {tuple(srs.shape)}, {tuple(hrs.shape)}, {tuple(hr_maps.shape)}")
+    border_w, data_range = int(border_w), float(data_range)
+    if border_w < 0 or border_w > 8 or min(srs.shape[1:]) < 2 * border_w + taps:
+        raise ValueError(f"border_w must be 0..8 and each side at least 2 border_w + {taps} (the {window} window); got {border_w} for "
+                         f"frames {tuple(srs.shape[1:])}")
+    if not data_range > 0.0:
+        raise ValueError(f"data_range must be positive; got {data_range}")
+    for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
+        if not t.is_cuda:
+            raise TypeError(f"{name} is on '{t.device}': the searched score runs on a ROCm device only (no CPU fallback)")
+    out, stats, scores = torch.ops.hrnet_hip.shift_cssim(srs.detach().float().contiguous(), hrs.float().contiguous(),
+                                                         hr_maps.float().contiguous(), border_w, window, bool(clip), bool(correct_bias),
+                                                         data_range)
+    res = [out]
+    if return_shift:
+        k = stats[:, 3].long()
+        nb = 2 * border_w + 1
+        res.append(torch.stack([torch.div(k, nb, rounding_mode="floor") - border_w, k % nb - border_w], 1))
+    if return_scores:
+        res.append(scores)
+    return res[0] if len(res) == 1 else tuple(res)

@@ -13,6 +13,10 @@ With a baseline table (the `norm.csv` of a PROBA-V directory: imageset name -> E
 ("flip" / "dihedral") scores the self-ensembled prediction (HRNet.forward_ensemble).  `tile` predicts through HRNet.forward_tiled
 (windows of that side; a rectangular scene is scored like a square one).  `evaluate` is the same pass on one rank that also
 returns the per-imageset cPSNRs.
+
+The second figure, cSSIM (`losses.shift_cssim`, DESIGN.md section 7k: structural similarity under the same offset search), comes from the
+same predictions: `evaluate(..., cssim=True)` adds it per imageset, `sharded_val_score(..., metric="cSSIM")` returns its mean over
+all ranks.
 """
 import collections
 
@@ -29,6 +33,7 @@ def shard_indices(n_items, rank, world_size):
 
 
 Evaluation = collections.namedtuple("Evaluation", "names cpsnr score")
+EvaluationCssim = collections.namedtuple("EvaluationCssim", "names cpsnr score cssim")      # evaluate(..., cssim=True)
 
 
 def _default_score(srs, hrs, hr_maps, border_w):
@@ -39,10 +44,17 @@ def _default_score(srs, hrs, hr_maps, border_w):
     return binding.shift_loss_train(srs, hrs, hr_maps, "cPSNR", border_w, True)[0]
 
 
-def _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, members_per_pass, keep, tile=None):
+def _cssim_score(srs, hrs, hr_maps, border_w):
+    """cSSIM of np.clip(sr, 0, 1) per sample on the device, with the defaults of losses.shift_cssim."""
+    from . import losses
+    return losses.shift_cssim(srs, hrs, hr_maps, border_w=border_w, clip=True)
+
+
+def _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, members_per_pass, keep, tile=None, second_fn=None):
     """The validation loop of train.py:196-215 over this rank's batches, (lrs, alphas, hrs, hr_maps) or (..., names): -> (float64
     sum on the device of cPSNR - or of ESA[name] / cPSNR with a baseline table - or None without a batch, the number of samples,
-    names, the list of per-batch float64 cPSNR tensors when `keep`).  The model's training flag is restored."""
+    names, the list of per-batch float64 cPSNR tensors when `keep` - with `second_fn`, of (cPSNR, second_fn(srs, hrs, hr_maps)) pairs).
+    The model's training flag is restored."""
     from . import augment
     score_fn = score_fn or (lambda s, h, m: _default_score(s, h, m, border_w))
     mode = augment.check_mode(ensemble)
@@ -81,35 +93,52 @@ def _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, s
                 if names is not None:
                     all_names += names
                 if keep:
-                    kept.append(cpsnr)
+                    kept.append(cpsnr if second_fn is None else (cpsnr, second_fn(srs, hrs, hr_maps).double()))
     finally:
         fusion_model.train(was_training)
     return total, count, all_names, kept
 
 
-def evaluate(fusion_model, batches, baseline_cpsnrs=None, ensemble=None, border_w=3, score_fn=None, members_per_pass=None, tile=None):
+def evaluate(fusion_model, batches, baseline_cpsnrs=None, ensemble=None, border_w=3, score_fn=None, members_per_pass=None, tile=None,
+             cssim=False):
     """One rank's evaluation pass over `batches` of (lrs, alphas, hrs, hr_maps, names) (names may be left out without a baseline table):
     -> Evaluation(names, cpsnr, score) with the per-imageset shift_cPSNR as a float64 numpy array in batch order and `score` the
     reference's validation score (train.py:209-217): -mean(cPSNR) without a baseline table, mean(ESA[name] / cPSNR) with one
     (`baseline_cpsnrs`: name -> ESA baseline cPSNR).  ensemble: None, or "flip" / "dihedral" to score
     `fusion_model.forward_ensemble(lrs, alphas, ensemble, members_per_pass)` instead of the plain forward.  The sums stay in float64
     on the device; one read-back at the end.  score_fn as in sharded_val_score.  tile: None, or the window side with which
-    `fusion_model.forward_tiled(lrs, alphas, tile, ensemble=ensemble, members_per_pass=members_per_pass)` predicts instead."""
+    `fusion_model.forward_tiled(lrs, alphas, tile, ensemble=ensemble, members_per_pass=members_per_pass)` predicts instead.
+    cssim: also score every prediction with `losses.shift_cssim(srs, hrs, hr_maps, border_w, clip=True)` in the same pass; the result is
+    then EvaluationCssim(names, cpsnr, score, cssim), `cssim` a float64 numpy array in batch order."""
+    second = (lambda s, h, m: _cssim_score(s, h, m, border_w)) if cssim else None
     total, count, names, kept = _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, members_per_pass, True,
-                                               tile)
+                                               tile, second)
     if count == 0:
         raise ValueError("evaluate: no sample in `batches`")
     mean = float(total / count)
-    return Evaluation(names, torch.cat(kept).cpu().numpy().astype(np.float64), mean if baseline_cpsnrs is not None else -mean)
+    score = mean if baseline_cpsnrs is not None else -mean
+    if not cssim:
+        return Evaluation(names, torch.cat(kept).cpu().numpy().astype(np.float64), score)
+    return EvaluationCssim(names, torch.cat([c for c, _ in kept]).cpu().numpy().astype(np.float64), score,
+                           torch.cat([q for _, q in kept]).cpu().numpy().astype(np.float64))
 
 
-def sharded_val_score(fusion_model, batches, border_w=3, score_fn=None, device=None, baseline_cpsnrs=None, ensemble=None, tile=None):
+def sharded_val_score(fusion_model, batches, border_w=3, score_fn=None, device=None, baseline_cpsnrs=None, ensemble=None, tile=None,
+                      metric="cPSNR"):
     """`batches`: this rank's validation batches of (lrs, alphas, hrs, hr_maps) tensors, or the same with `names` as a fifth element
     (the reference loads them one imageset at a time, train.py:281).  Returns `val_score` of train.py:199-217 over ALL ranks' samples:
     -mean(shift_cPSNR), or with `baseline_cpsnrs` (name -> ESA baseline cPSNR; needs the names) mean(ESA[name] / shift_cPSNR).  Either
     way only (sum, count) is all-reduced.  ensemble: None, or "flip" / "dihedral" to score the model's forward_ensemble.  tile: None, or
     the window side of the model's forward_tiled, which then predicts (with `ensemble`).
-    score_fn(srs (B,S,S), hrs, hr_maps) -> (B,) replaces `hrn_shift_cpsnr` in the CPU rehearsal of the collective (tests/test_dist_cpu.py)."""
+    score_fn(srs (B,S,S), hrs, hr_maps) -> (B,) replaces `hrn_shift_cpsnr` in the CPU rehearsal of the collective (tests/test_dist_cpu.py).
+    metric: "cPSNR", or "cSSIM" for the mean of `losses.shift_cssim(srs, hrs, hr_maps, border_w, clip=True)` over all ranks' samples
+    (returned as it is, not negated: higher is better), through the same collective; a baseline table has no meaning for it."""
+    if metric not in ("cPSNR", "cSSIM"):
+        raise ValueError(f"metric must be 'cPSNR' or 'cSSIM'; got {metric!r}")
+    if metric == "cSSIM":
+        if baseline_cpsnrs is not None:
+            raise ValueError("baseline_cpsnrs normalises cPSNR; it cannot be combined with metric='cSSIM'")
+        score_fn = score_fn or (lambda s, h, m: _cssim_score(s, h, m, border_w))
     total, count, _, _ = _score_batches(fusion_model, batches, baseline_cpsnrs, ensemble, border_w, score_fn, None, False, tile)
     if total is None:
         total = torch.zeros((), dtype=torch.float64, device=device or "cpu")
@@ -121,4 +150,4 @@ def sharded_val_score(fusion_model, batches, border_w=3, score_fn=None, device=N
     if float(acc[1]) == 0:
         raise ValueError("sharded_val_score: no validation sample on any rank")
     mean = float(acc[0] / acc[1])
-    return mean if baseline_cpsnrs is not None else -mean
+    return mean if baseline_cpsnrs is not None or metric == "cSSIM" else -mean

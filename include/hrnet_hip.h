@@ -314,6 +314,29 @@ int hrn_shift_loss_train(const float* srs, const float* hrs, const float* hr_map
 int hrn_shift_loss_backward(const float* srs, const float* hrs, const float* hr_maps, const double* stats, const float* d_out, int B,
                             int H, int W, int border, int metric, int clip, float* d_srs, void* stream);
 
+/* The second score, cSSIM: structural similarity between the clear pixels of the target and the brightness-corrected prediction, searched
+ * over the offsets and crops of hrn_shift_loss_train (the project's own definition; tests/cssim_ref.py restates it in fp64).
+ * srs/hrs/hr_maps (B,H,W) f32, a map is 0 / non-zero; border 0..8; h, w, s (clamped to [0,1] when clip != 0, a NaN stays NaN) and, for
+ * the offset k = u (2 border + 1) + v, g and m as above; n_k = sum m, bias_k = sum m (g - s) / n_k, or 0 when correct_bias == 0.  The
+ * compared pair is X = m g and Y = m (s + bias_k): masked pixels are zero in both.  The window G is separable, sums to 1 and is applied
+ * where it fits ("valid": the SSIM map is (h - T + 1) x (w - T + 1), no padding), so H and W must each be >= 2 border + T:
+ *   window 0 (gaussian)  T = 11 taps exp(-x^2 / (2 1.5^2)), x = -5..5, normalised in fp64 and rounded to fp32; cov_norm = 1
+ *   window 1 (uniform)   T = 7 taps of 1/7; cov_norm = 49/48 (the sample covariance)
+ *   mu_x = G X, mu_y = G Y, v_x = cov_norm (G X^2 - mu_x^2), v_y likewise, v_xy = cov_norm (G XY - mu_x mu_y),
+ *   C1 = (0.01 L)^2, C2 = (0.03 L)^2 with L = data_range > 0,
+ *   SSIM = (2 mu_x mu_y + C1) (2 v_xy + C2) / ((mu_x^2 + mu_y^2 + C1) (v_x + v_y + C2)),  score_k = the mean of the map,
+ * and score_k = -inf where n_k = 0.  k* is the lowest k of maximal score_k among n_k > 0 under a strict >, so a NaN score is never
+ * selected.  out (B) f32 = score_k*, stats (B,4) f64 = {n*, bias*, score*, k*}; without an eligible offset out is NaN and stats {0, 0,
+ * NaN, -1}.  scores (B, (2 border + 1)^2) f64, may be NULL: every score_k.  correct_bias = 0, border = 0, window = 1 with the caller's
+ * data_range is the reference fork's registration_metrics.compute_ssim(..., use_masks=True) on a common mask (zeroed non-common
+ * pixels, skimage's 7 x 7 uniform window and sample covariance, the mean over the un-padded map).  fp32 filters, fp64 sums in a fixed
+ * order, no atomics: bit-reproducible, and a sample's result does not depend on the batch around it.  No gradient: it is a score.
+ * hrn_shift_cssim_workspace_bytes: the fp64 partial sums (0 for arguments the entry point refuses). */
+size_t hrn_shift_cssim_workspace_bytes(int B, int H, int W, int border, int window);
+int hrn_shift_cssim(const float* srs, const float* hrs, const float* hr_maps, int B, int H, int W, int border, int window, int clip,
+                    int correct_bias, float data_range, float* out, double* stats, double* scores, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ sub-pixel registration of LR views: a masked-NCC grid search
  * The method of the reference fork's registration_search.py / registration_metrics.py (compute_shift_ncc -> recursive_mncc_search ->
  * compute_grid_mncc), on definitions of this project's own; tests/registration_ref.py restates them in fp64 and is what the tests
