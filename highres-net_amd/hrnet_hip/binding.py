@@ -949,9 +949,11 @@ def shift_cssim(srs, hrs, hr_maps, border_w=3, window="gaussian", clip=True, cor
     return out, stats, scores
 
 
-# --------------------------------------------------------------------------- sub-pixel registration of LR views (registration.hip,
-# registration_scene.hip).  Every call below has a `scene` form for frames of any size; the two differ in the entry point, in the
-# workspace the scene form allocates, and in the limit on a frame's side, nothing else.
+# --------------------------------------------------------------------------- sub-pixel registration of LR views.  Four files, one per
+# path: registration.hip (frames that fit one CU's LDS), registration_scene.hip (frames of any size, in tiles), registration_local.hip (a
+# shift per block of tiles: a field) and registration_pyramid.hip (coarse to fine, for shifts beyond 4 px).  grid / search / apply have a
+# `scene` form that differs in the entry point, in the workspace it takes from the cache and in the limit on a frame's side, nothing
+# else.  The tensor checks (_mncc_views, _mncc_args, _mncc_init) and the workspace (_mncc_workspace) are shared by all four.
 MNCC_SIDES, MNCC_POINTS, MNCC_LEVELS, MNCC_MAX_RADIUS = (16, 128), (3, 9), (1, 16), 4.0     # the limits of include/hrnet_hip.h
 MNCC_SCENE_SIDES = (16, 16384)
 MNCC_LOCAL_BLOCKS = (64, 4096)             # a block of the local search: a multiple of 64 within these
@@ -966,33 +968,56 @@ def mncc_int(name, value, limits):
     return value
 
 
-def _mncc_args(ref, ref_mask, views, view_masks):
-    """-> the four tensors as contiguous device f32 (a mask may be None: all ones) after the shape checks."""
-    ref, views = _dev_f32(ref, "ref"), _dev_f32(views, "views")
-    if views.dim() != 4 or ref.dim() != 3 or tuple(ref.shape) != (views.shape[0],) + tuple(views.shape[2:]):
+def _mncc_views(views, view_masks, ref=None):
+    """-> views (B,V,H,W) and view_masks (None: all ones) as contiguous device f32; with `ref`, views must be V frames of its shape."""
+    views = _dev_f32(views, "views")
+    if ref is None:
+        if views.dim() != 4:
+            raise ValueError(f"views must be (B,V,H,W); got {tuple(views.shape)}")
+    elif views.dim() != 4 or ref.dim() != 3 or tuple(ref.shape) != (views.shape[0],) + tuple(views.shape[2:]):
         raise ValueError(f"ref must be (B,H,W) and views (B,V,H,W); got {tuple(ref.shape)}, {tuple(views.shape)}")
-    if ref_mask is not None:
-        ref_mask = _dev_f32(ref_mask, "ref_mask")
-        if ref_mask.shape != ref.shape:
-            raise ValueError(f"ref_mask must have ref's shape {tuple(ref.shape)}; got {tuple(ref_mask.shape)}")
     if view_masks is not None:
         view_masks = _dev_f32(view_masks, "view_masks")
         if view_masks.shape != views.shape:
             raise ValueError(f"view_masks must have views' shape {tuple(views.shape)}; got {tuple(view_masks.shape)}")
+    return views, view_masks
+
+
+def _mncc_args(ref, ref_mask, views, view_masks):
+    """-> the four tensors as contiguous device f32 (a mask may be None: all ones) after the shape checks."""
+    ref = _dev_f32(ref, "ref")
+    views, view_masks = _mncc_views(views, view_masks, ref)
+    if ref_mask is not None:
+        ref_mask = _dev_f32(ref_mask, "ref_mask")
+        if ref_mask.shape != ref.shape:
+            raise ValueError(f"ref_mask must have ref's shape {tuple(ref.shape)}; got {tuple(ref_mask.shape)}")
     return ref, ref_mask, views, view_masks
+
+
+def _mncc_init(init, B, V):
+    if init is not None:
+        init = _dev_f32(init, "init")
+        if tuple(init.shape) != (B, V, 2):
+            raise ValueError(f"init must be ({B}, {V}, 2); got {tuple(init.shape)}")
+    return init
 
 
 def _opt_ptr(t):
     return ctypes.c_void_p(0) if t is None else _ptr(t)
 
 
-def _mncc_scene_workspace(lib, B, V, H, W, P, device):
-    """-> the (pointer, bytes) pair of the scene entry points' workspace arguments; the caller is inside torch.cuda.device(device)"""
-    nbytes = lib.hrn_mncc_scene_workspace_bytes(B, V, H, W, P)
+def _mncc_workspace(query, args, tag, problem, device):
+    """-> the (pointer, bytes) pair of an entry point's workspace arguments, from the cache under `tag`.  `query`(*args) is the entry
+    point's size query: 0 where the entry point would refuse the `problem`.  The caller is inside torch.cuda.device(device)."""
+    nbytes = getattr(load_library(), query)(*args)
     if nbytes == 0:
-        raise HrnetHipError(f"bad registration problem size B={B} V={V} H={H} W={W} P={P}")
-    ws = _workspace(nbytes, device, "mncc_scene")
+        raise HrnetHipError(f"bad registration problem size {problem}")
+    ws = _workspace(nbytes, device, tag)
     return _ptr(ws), ws.numel()
+
+
+def _mncc_scene_workspace(B, V, H, W, P, device):
+    return _mncc_workspace("hrn_mncc_scene_workspace_bytes", (B, V, H, W, P), "mncc_scene", f"B={B} V={V} H={H} W={W} P={P}", device)
 
 
 def _mncc_grid(scene, ref, ref_mask, views, view_masks, centres, points_per_dim, width):
@@ -1007,21 +1032,14 @@ def _mncc_grid(scene, ref, ref_mask, views, view_masks, centres, points_per_dim,
     args = (_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks), _ptr(centres), B, V, H, W, P, float(width), _ptr(scores))
     with torch.cuda.device(views.device):
         if scene:
-            _check(lib.hrn_mncc_grid_scene(*args, *_mncc_scene_workspace(lib, B, V, H, W, P, views.device), _stream()), "hrn_mncc_grid_scene")
+            _check(lib.hrn_mncc_grid_scene(*args, *_mncc_scene_workspace(B, V, H, W, P, views.device), _stream()), "hrn_mncc_grid_scene")
         else:
             _check(lib.hrn_mncc_grid(*args, _stream()), "hrn_mncc_grid")
     return scores
 
 
-def _mncc_init(init, B, V):
-    if init is not None:
-        init = _dev_f32(init, "init")
-        if tuple(init.shape) != (B, V, 2):
-            raise ValueError(f"init must be ({B}, {V}, 2); got {tuple(init.shape)}")
-    return init
-
-
-def _mncc_search(scene, ref, ref_mask, views, view_masks, points_per_dim, levels, radius, init=None, from_init=False):
+def _mncc_search(entry, ref, ref_mask, views, view_masks, points_per_dim, levels, radius, init=None):
+    """`entry`: hrn_mncc_search, hrn_mncc_search_scene or hrn_mncc_search_scene_from - the one that takes `init`."""
     lib = load_library()
     ref, ref_mask, views, view_masks = _mncc_args(ref, ref_mask, views, view_masks)
     B, V, H, W = views.shape
@@ -1029,29 +1047,21 @@ def _mncc_search(scene, ref, ref_mask, views, view_masks, points_per_dim, levels
     init = _mncc_init(init, B, V)
     shifts = torch.empty((B, V, 2), dtype=torch.float32, device=views.device)
     trace = torch.empty((B, V, levels, 3), dtype=torch.float32, device=views.device)
-    args = (_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks), B, V, H, W, P, levels, float(radius), _ptr(shifts), _ptr(trace))
+    args = [_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks)]
+    if entry == "hrn_mncc_search_scene_from":
+        args.append(_opt_ptr(init))
+    args += [B, V, H, W, P, levels, float(radius), _ptr(shifts), _ptr(trace)]
     with torch.cuda.device(views.device):
-        if from_init:
-            _check(lib.hrn_mncc_search_scene_from(*args[:4], _opt_ptr(init), *args[4:], *_mncc_scene_workspace(lib, B, V, H, W, P, views.device),
-                                                  _stream()), "hrn_mncc_search_scene_from")
-        elif scene:
-            _check(lib.hrn_mncc_search_scene(*args, *_mncc_scene_workspace(lib, B, V, H, W, P, views.device), _stream()),
-                   "hrn_mncc_search_scene")
-        else:
-            _check(lib.hrn_mncc_search(*args, _stream()), "hrn_mncc_search")
+        if entry != "hrn_mncc_search":
+            args += _mncc_scene_workspace(B, V, H, W, P, views.device)
+        _check(getattr(lib, entry)(*args, _stream()), entry)
     return shifts, trace
 
 
 def _mncc_apply(scene, views, view_masks, shifts):
     lib = load_library()
-    views = _dev_f32(views, "views")
-    if views.dim() != 4:
-        raise ValueError(f"views must be (B,V,H,W); got {tuple(views.shape)}")
+    views, view_masks = _mncc_views(views, view_masks)
     B, V, H, W = views.shape
-    if view_masks is not None:
-        view_masks = _dev_f32(view_masks, "view_masks")
-        if view_masks.shape != views.shape:
-            raise ValueError(f"view_masks must have views' shape {tuple(views.shape)}; got {tuple(view_masks.shape)}")
     shifts = _dev_f32(shifts, "shifts")
     if tuple(shifts.shape) != (B, V, 2):
         raise ValueError(f"shifts must be ({B}, {V}, 2); got {tuple(shifts.shape)}")
@@ -1070,7 +1080,7 @@ def mncc_grid(ref, ref_mask, views, view_masks, centres, points_per_dim, width):
 
 def mncc_search(ref, ref_mask, views, view_masks, points_per_dim=7, levels=6, radius=1.0):
     """The whole search in one launch: -> (shifts (B,V,2) f32 = (dy, dx), trace (B,V,levels,3) f32 = (dy, dx, score) per level)."""
-    return _mncc_search(False, ref, ref_mask, views, view_masks, points_per_dim, levels, radius)
+    return _mncc_search("hrn_mncc_search", ref, ref_mask, views, view_masks, points_per_dim, levels, radius)
 
 
 def mncc_apply(views, view_masks, shifts):
@@ -1085,7 +1095,7 @@ def mncc_grid_scene(ref, ref_mask, views, view_masks, centres, points_per_dim, w
 
 def mncc_search_scene(ref, ref_mask, views, view_masks, points_per_dim=7, levels=6, radius=1.0):
     """mncc_search for frames of any size (hrn_mncc_search_scene): 1 + 2 levels launches, nothing returns to the host between them."""
-    return _mncc_search(True, ref, ref_mask, views, view_masks, points_per_dim, levels, radius)
+    return _mncc_search("hrn_mncc_search_scene", ref, ref_mask, views, view_masks, points_per_dim, levels, radius)
 
 
 def mncc_apply_scene(views, view_masks, shifts):
@@ -1095,7 +1105,7 @@ def mncc_apply_scene(views, view_masks, shifts):
 
 def mncc_search_scene_from(ref, ref_mask, views, view_masks, init, points_per_dim=7, levels=6, radius=1.0):
     """mncc_search_scene with the first level's centre read from init (B,V,2) (hrn_mncc_search_scene_from); None: (0, 0)."""
-    return _mncc_search(True, ref, ref_mask, views, view_masks, points_per_dim, levels, radius, init, True)
+    return _mncc_search("hrn_mncc_search_scene_from", ref, ref_mask, views, view_masks, points_per_dim, levels, radius, init)
 
 
 def mncc_reduce2(x, mask):
@@ -1128,13 +1138,11 @@ def mncc_search_pyramid(ref, ref_mask, views, view_masks, octaves=2, points_per_
     shifts = torch.empty((B, V, 2), dtype=torch.float32, device=views.device)
     trace = torch.empty((B, V, K + 1, 3), dtype=torch.float32, device=views.device)
     with torch.cuda.device(views.device):
-        nbytes = lib.hrn_mncc_pyramid_workspace_bytes(B, V, H, W, P, K)
-        if nbytes == 0:
-            raise HrnetHipError(f"bad registration problem size B={B} V={V} H={H} W={W} P={P} octaves={K}")
-        ws = _workspace(nbytes, views.device, "mncc_pyramid")
+        ws = _mncc_workspace("hrn_mncc_pyramid_workspace_bytes", (B, V, H, W, P, K), "mncc_pyramid",
+                             f"B={B} V={V} H={H} W={W} P={P} octaves={K}", views.device)
         _check(lib.hrn_mncc_search_pyramid(_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks), B, V, H, W, P, K, levels,
-                                           float(radius), coarse_levels, float(refine_radius), _ptr(shifts), _ptr(trace), _ptr(ws), ws.numel(),
-                                           _stream()), "hrn_mncc_search_pyramid")
+                                           float(radius), coarse_levels, float(refine_radius), _ptr(shifts), _ptr(trace), *ws, _stream()),
+               "hrn_mncc_search_pyramid")
     return shifts, trace
 
 
@@ -1162,37 +1170,26 @@ def mncc_search_local(ref, ref_mask, views, view_masks, init, points_per_dim=7, 
     lib = load_library()
     ref, ref_mask, views, view_masks = _mncc_args(ref, ref_mask, views, view_masks)
     B, V, H, W = views.shape
-    if init is not None:
-        init = _dev_f32(init, "init")
-        if tuple(init.shape) != (B, V, 2):
-            raise ValueError(f"init must be ({B}, {V}, 2); got {tuple(init.shape)}")
+    init = _mncc_init(init, B, V)
     P, levels = mncc_int("points_per_dim", points_per_dim, MNCC_POINTS), mncc_int("levels", levels, MNCC_LEVELS)
     by, bx = mncc_local_blocks(H, W, block)
     field = torch.empty((B, V, by, bx, 2), dtype=torch.float32, device=views.device)
     trace = torch.empty((B, V, by, bx, levels, 3), dtype=torch.float32, device=views.device)
     ok = torch.empty((B, V, by, bx), dtype=torch.float32, device=views.device)
     with torch.cuda.device(views.device):
-        nbytes = lib.hrn_mncc_local_workspace_bytes(B, V, H, W, P, int(block))
-        if nbytes == 0:
-            raise HrnetHipError(f"bad registration problem size B={B} V={V} H={H} W={W} P={P} block={block}")
-        ws = _workspace(nbytes, views.device, "mncc_local")
+        ws = _mncc_workspace("hrn_mncc_local_workspace_bytes", (B, V, H, W, P, int(block)), "mncc_local",
+                             f"B={B} V={V} H={H} W={W} P={P} block={block}", views.device)
         _check(lib.hrn_mncc_search_local(_ptr(ref), _opt_ptr(ref_mask), _ptr(views), _opt_ptr(view_masks), _opt_ptr(init), B, V, H, W, P, levels,
-                                         float(radius), int(block), float(min_valid), _ptr(field), _ptr(trace), _ptr(ok), _ptr(ws), ws.numel(),
-                                         _stream()), "hrn_mncc_search_local")
+                                         float(radius), int(block), float(min_valid), _ptr(field), _ptr(trace), _ptr(ok), *ws, _stream()),
+               "hrn_mncc_search_local")
     return field, trace, ok
 
 
 def mncc_apply_field(views, view_masks, field, block):
     """-> (out, valid) as mncc_apply_scene, every pixel by its own shift: the field (B,V,by,bx,2) between the blocks' centres."""
     lib = load_library()
-    views = _dev_f32(views, "views")
-    if views.dim() != 4:
-        raise ValueError(f"views must be (B,V,H,W); got {tuple(views.shape)}")
+    views, view_masks = _mncc_views(views, view_masks)
     B, V, H, W = views.shape
-    if view_masks is not None:
-        view_masks = _dev_f32(view_masks, "view_masks")
-        if view_masks.shape != views.shape:
-            raise ValueError(f"view_masks must have views' shape {tuple(views.shape)}; got {tuple(view_masks.shape)}")
     field = _dev_f32(field, "field")
     by, bx = mncc_local_blocks(H, W, block)
     if tuple(field.shape) != (B, V, by, bx, 2):

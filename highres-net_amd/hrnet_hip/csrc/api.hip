@@ -470,16 +470,41 @@ int hrn_shift_cssim(const float* srs, const float* hrs, const float* maps, int B
 }
 
 // the masked-NCC registration search (registration.hip): the reference fork's recursive_mncc_search / compute_grid_mncc, restated
+//
+// Every limit of a registration problem is stated once, in a check that takes the entry point's name `who`.  A size query runs its entry
+// point's own checks with a null `who` - which refuses without touching hrn_last_error - and answers 0 where they refuse.
+#define MNCC_LIMIT(cond, ...)                                             \
+    do {                                                                  \
+        if (!(cond)) { if (who) hrn_set_error(__VA_ARGS__); return -2; } \
+    } while (0)
+
 static int mncc_check(const char* who, int B, int V, int H, int W, int lo = HRN_MNCC_MIN_SIDE, int hi = HRN_MNCC_MAX_SIDE) {
-    HRN_CHECK(B > 0 && V > 0 && (long)B * V <= 0x7fffffffL, -2, "%s: bad batch B=%d V=%d", who, B, V);
-    HRN_CHECK(H >= lo && H <= hi && W >= lo && W <= hi, -2, "%s: bad shape H=%d W=%d: the sides of a frame must be %d..%d", who, H, W, lo, hi);
+    MNCC_LIMIT(B > 0 && V > 0 && (long)B * V <= 0x7fffffffL, "%s: bad batch B=%d V=%d", who, B, V);
+    MNCC_LIMIT(H >= lo && H <= hi && W >= lo && W <= hi, "%s: bad shape H=%d W=%d: the sides of a frame must be %d..%d", who, H, W, lo, hi);
     return 0;
 }
 
 static int mncc_check_points(const char* who, int P) {
-    HRN_CHECK(P >= HRN_MNCC_MIN_POINTS && P <= HRN_MNCC_MAX_POINTS, -2, "%s: points per axis P=%d outside %d..%d", who, P, HRN_MNCC_MIN_POINTS,
-              HRN_MNCC_MAX_POINTS);
+    MNCC_LIMIT(P >= HRN_MNCC_MIN_POINTS && P <= HRN_MNCC_MAX_POINTS, "%s: points per axis P=%d outside %d..%d", who, P, HRN_MNCC_MIN_POINTS,
+               HRN_MNCC_MAX_POINTS);
     return 0;
+}
+
+static int mncc_check_levels(const char* who, const char* name, int levels) {
+    MNCC_LIMIT(levels >= 1 && levels <= HRN_MNCC_MAX_LEVELS, "%s: %s %d outside 1..%d", who, name, levels, HRN_MNCC_MAX_LEVELS);
+    return 0;
+}
+
+static int mncc_check_radius(const char* who, const char* name, float radius) {
+    MNCC_LIMIT(radius > 0.f && radius <= 4.f, "%s: %s %g outside (0, 4]", who, name, (double)radius);
+    return 0;
+}
+
+// points, levels, radius: what every search checks after its shape
+static int mncc_check_search(const char* who, int P, int levels, float radius) {
+    if (int rc = mncc_check_points(who, P)) return rc;
+    if (int rc = mncc_check_levels(who, "levels", levels)) return rc;
+    return mncc_check_radius(who, "radius", radius);
 }
 
 int hrn_mncc_grid(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* centres, int B, int V,
@@ -494,9 +519,7 @@ int hrn_mncc_grid(const float* ref, const float* ref_mask, const float* views, c
 int hrn_mncc_search(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H, int W, int P,
                     int levels, float radius, float* shifts, float* trace, void* stream) {
     if (int rc = mncc_check("hrn_mncc_search", B, V, H, W)) return rc;
-    if (int rc = mncc_check_points("hrn_mncc_search", P)) return rc;
-    HRN_CHECK(levels >= 1 && levels <= HRN_MNCC_MAX_LEVELS, -2, "hrn_mncc_search: levels %d outside 1..%d", levels, HRN_MNCC_MAX_LEVELS);
-    HRN_CHECK(radius > 0.f && radius <= 4.f, -2, "hrn_mncc_search: radius %g outside (0, 4]", (double)radius);
+    if (int rc = mncc_check_search("hrn_mncc_search", P, levels, radius)) return rc;
     HRN_CHECK(ref && views && shifts, -2, "hrn_mncc_search: null argument");
     return hrn_launch_mncc_search(ref, ref_mask, views, view_masks, B, V, H, W, P, levels, radius, shifts, trace, (hipStream_t)stream);
 }
@@ -511,15 +534,12 @@ int hrn_mncc_apply(const float* views, const float* view_masks, const float* shi
 // the same search and resampling for frames of any size, in tiles (registration_scene.hip)
 static int mncc_scene_check(const char* who, int B, int V, int H, int W) {
     if (int rc = mncc_check(who, B, V, H, W, HRN_MNCC_SCENE_MIN_SIDE, HRN_MNCC_SCENE_MAX_SIDE)) return rc;
-    HRN_CHECK(hrn_mncc_scene_grid_fits(B, V, H, W), -2, "%s: bad batch B=%d V=%d: the tiles of %d x %d frames exceed one launch", who, B, V, H, W);
+    MNCC_LIMIT(hrn_mncc_scene_grid_fits(B, V, H, W), "%s: bad batch B=%d V=%d: the tiles of %d x %d frames exceed one launch", who, B, V, H, W);
     return 0;
 }
 
 size_t hrn_mncc_scene_workspace_bytes(int B, int V, int H, int W, int P) {
-    if (B <= 0 || V <= 0 || (long)B * V > 0x7fffffffL || H < HRN_MNCC_SCENE_MIN_SIDE || H > HRN_MNCC_SCENE_MAX_SIDE ||
-        W < HRN_MNCC_SCENE_MIN_SIDE || W > HRN_MNCC_SCENE_MAX_SIDE || P < HRN_MNCC_MIN_POINTS || P > HRN_MNCC_MAX_POINTS ||
-        !hrn_mncc_scene_grid_fits(B, V, H, W))
-        return 0;
+    if (mncc_scene_check(nullptr, B, V, H, W) || mncc_check_points(nullptr, P)) return 0;
     return hrn_mncc_scene_workspace_bytes_impl(B, V, H, W, P);
 }
 
@@ -533,17 +553,30 @@ int hrn_mncc_grid_scene(const float* ref, const float* ref_mask, const float* vi
     return hrn_launch_mncc_grid_scene(ref, ref_mask, views, view_masks, centres, B, V, H, W, P, width, scores, workspace, (hipStream_t)stream);
 }
 
+// hrn_mncc_search_scene (init null: from (0, 0)) and hrn_mncc_search_scene_from
+static int mncc_search_scene(const char* who, const float* ref, const float* ref_mask, const float* views, const float* view_masks,
+                             const float* init, int B, int V, int H, int W, int P, int levels, float radius, float* shifts, float* trace,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = mncc_scene_check(who, B, V, H, W)) return rc;
+    if (int rc = mncc_check_search(who, P, levels, radius)) return rc;
+    HRN_CHECK(ref && views && shifts && workspace, -2, "%s: null argument", who);
+    HRN_CHECK(workspace_bytes >= hrn_mncc_scene_workspace_bytes_impl(B, V, H, W, P), -3, "%s: workspace too small", who);
+    return hrn_launch_mncc_search_scene_from(ref, ref_mask, views, view_masks, init, B, V, H, W, P, levels, radius, shifts, trace, nullptr, 0,
+                                             workspace, (hipStream_t)stream);
+}
+
 int hrn_mncc_search_scene(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H, int W,
                           int P, int levels, float radius, float* shifts, float* trace, void* workspace, size_t workspace_bytes,
                           void* stream) {
-    if (int rc = mncc_scene_check("hrn_mncc_search_scene", B, V, H, W)) return rc;
-    if (int rc = mncc_check_points("hrn_mncc_search_scene", P)) return rc;
-    HRN_CHECK(levels >= 1 && levels <= HRN_MNCC_MAX_LEVELS, -2, "hrn_mncc_search_scene: levels %d outside 1..%d", levels, HRN_MNCC_MAX_LEVELS);
-    HRN_CHECK(radius > 0.f && radius <= 4.f, -2, "hrn_mncc_search_scene: radius %g outside (0, 4]", (double)radius);
-    HRN_CHECK(ref && views && shifts && workspace, -2, "hrn_mncc_search_scene: null argument");
-    HRN_CHECK(workspace_bytes >= hrn_mncc_scene_workspace_bytes_impl(B, V, H, W, P), -3, "hrn_mncc_search_scene: workspace too small");
-    return hrn_launch_mncc_search_scene(ref, ref_mask, views, view_masks, B, V, H, W, P, levels, radius, shifts, trace, workspace,
-                                        (hipStream_t)stream);
+    return mncc_search_scene("hrn_mncc_search_scene", ref, ref_mask, views, view_masks, nullptr, B, V, H, W, P, levels, radius, shifts, trace,
+                             workspace, workspace_bytes, stream);
+}
+
+int hrn_mncc_search_scene_from(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* init, int B,
+                               int V, int H, int W, int P, int levels, float radius, float* shifts, float* trace, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    return mncc_search_scene("hrn_mncc_search_scene_from", ref, ref_mask, views, view_masks, init, B, V, H, W, P, levels, radius, shifts,
+                             trace, workspace, workspace_bytes, stream);
 }
 
 int hrn_mncc_apply_scene(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
@@ -554,26 +587,28 @@ int hrn_mncc_apply_scene(const float* views, const float* view_masks, const floa
 }
 
 // a shift per block of tiles and the resampling by the field between them (registration_local.hip)
+static int mncc_check_block(const char* who, int block) {
+    MNCC_LIMIT(block >= HRN_MNCC_LOCAL_MIN_BLOCK && block <= HRN_MNCC_LOCAL_MAX_BLOCK && block % HRN_MNCC_SCENE_TILE == 0,
+               "%s: bad block %d: a block must be a multiple of %d in %d..%d", who, block, HRN_MNCC_SCENE_TILE, HRN_MNCC_LOCAL_MIN_BLOCK,
+               HRN_MNCC_LOCAL_MAX_BLOCK);
+    return 0;
+}
+
 static int mncc_local_check(const char* who, int B, int V, int H, int W, int block) {
     if (int rc = mncc_scene_check(who, B, V, H, W)) return rc;
-    HRN_CHECK(block >= HRN_MNCC_LOCAL_MIN_BLOCK && block <= HRN_MNCC_LOCAL_MAX_BLOCK && block % HRN_MNCC_SCENE_TILE == 0, -2,
-              "%s: bad block %d: a block must be a multiple of %d in %d..%d", who, block, HRN_MNCC_SCENE_TILE, HRN_MNCC_LOCAL_MIN_BLOCK,
-              HRN_MNCC_LOCAL_MAX_BLOCK);
-    HRN_CHECK(hrn_mncc_local_grid_fits(B, V, H, W, block), -2, "%s: bad batch B=%d V=%d: the blocks of %d x %d frames exceed one launch", who, B,
-              V, H, W);
+    if (int rc = mncc_check_block(who, block)) return rc;
+    MNCC_LIMIT(hrn_mncc_local_grid_fits(B, V, H, W, block), "%s: bad batch B=%d V=%d: the blocks of %d x %d frames exceed one launch", who, B, V,
+               H, W);
     return 0;
 }
 
 int hrn_mncc_local_blocks(int L, int block) {
-    if (L < 1 || L > HRN_MNCC_SCENE_MAX_SIDE || block < HRN_MNCC_LOCAL_MIN_BLOCK || block > HRN_MNCC_LOCAL_MAX_BLOCK ||
-        block % HRN_MNCC_SCENE_TILE != 0)
-        return 0;
+    if (L < 1 || L > HRN_MNCC_SCENE_MAX_SIDE || mncc_check_block(nullptr, block)) return 0;
     return hrn_mncc_local_blocks_impl(L, block);
 }
 
 size_t hrn_mncc_local_workspace_bytes(int B, int V, int H, int W, int P, int block) {
-    if (hrn_mncc_scene_workspace_bytes(B, V, H, W, P) == 0 || hrn_mncc_local_blocks(H, block) == 0 || !hrn_mncc_local_grid_fits(B, V, H, W, block))
-        return 0;
+    if (mncc_local_check(nullptr, B, V, H, W, block) || mncc_check_points(nullptr, P)) return 0;
     return hrn_mncc_local_workspace_bytes_impl(B, V, H, W, P, block);
 }
 
@@ -581,9 +616,7 @@ int hrn_mncc_search_local(const float* ref, const float* ref_mask, const float* 
                           int H, int W, int P, int levels, float radius, int block, float min_valid, float* field, float* trace, float* ok,
                           void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = mncc_local_check("hrn_mncc_search_local", B, V, H, W, block)) return rc;
-    if (int rc = mncc_check_points("hrn_mncc_search_local", P)) return rc;
-    HRN_CHECK(levels >= 1 && levels <= HRN_MNCC_MAX_LEVELS, -2, "hrn_mncc_search_local: levels %d outside 1..%d", levels, HRN_MNCC_MAX_LEVELS);
-    HRN_CHECK(radius > 0.f && radius <= 4.f, -2, "hrn_mncc_search_local: radius %g outside (0, 4]", (double)radius);
+    if (int rc = mncc_check_search("hrn_mncc_search_local", P, levels, radius)) return rc;
     HRN_CHECK(min_valid >= 0.f && min_valid <= 1.f, -2, "hrn_mncc_search_local: min_valid %g outside [0, 1]", (double)min_valid);
     HRN_CHECK(ref && views && field && workspace, -2, "hrn_mncc_search_local: null argument");
     HRN_CHECK(workspace_bytes >= hrn_mncc_local_workspace_bytes_impl(B, V, H, W, P, block), -3, "hrn_mncc_search_local: workspace too small");
@@ -608,47 +641,29 @@ int hrn_mncc_reduce2(const float* x, const float* mask, int N, int H, int W, flo
     return hrn_launch_mncc_reduce2(x, mask, (size_t)N, nullptr, nullptr, 0, H, W, out, out_mask, nullptr, nullptr, (hipStream_t)stream);
 }
 
-int hrn_mncc_search_scene_from(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* init, int B,
-                               int V, int H, int W, int P, int levels, float radius, float* shifts, float* trace, void* workspace,
-                               size_t workspace_bytes, void* stream) {
-    if (int rc = mncc_scene_check("hrn_mncc_search_scene_from", B, V, H, W)) return rc;
-    if (int rc = mncc_check_points("hrn_mncc_search_scene_from", P)) return rc;
-    HRN_CHECK(levels >= 1 && levels <= HRN_MNCC_MAX_LEVELS, -2, "hrn_mncc_search_scene_from: levels %d outside 1..%d", levels, HRN_MNCC_MAX_LEVELS);
-    HRN_CHECK(radius > 0.f && radius <= 4.f, -2, "hrn_mncc_search_scene_from: radius %g outside (0, 4]", (double)radius);
-    HRN_CHECK(ref && views && shifts && workspace, -2, "hrn_mncc_search_scene_from: null argument");
-    HRN_CHECK(workspace_bytes >= hrn_mncc_scene_workspace_bytes_impl(B, V, H, W, P), -3, "hrn_mncc_search_scene_from: workspace too small");
-    return hrn_launch_mncc_search_scene_from(ref, ref_mask, views, view_masks, init, B, V, H, W, P, levels, radius, shifts, trace, nullptr, 0,
-                                             workspace, (hipStream_t)stream);
-}
-
-// what hrn_mncc_search_pyramid refuses beyond the scene search's own limits; `who` null: say nothing
-static int mncc_pyramid_check(const char* who, int H, int W, int octaves, float radius) {
-    const bool quiet = who == nullptr;
-    if (octaves < 0 || octaves > HRN_MNCC_MAX_OCTAVES) {
-        if (!quiet) hrn_set_error("%s: octaves %d outside 0..%d", who, octaves, HRN_MNCC_MAX_OCTAVES);
-        return -2;
-    }
-    if (!(radius > 0.f && radius <= 4.f)) {
-        if (!quiet) hrn_set_error("%s: radius %g outside (0, 4]", who, (double)radius);
-        return -2;
-    }
-    if (radius * (float)(1 << octaves) > HRN_MNCC_PYRAMID_MAX_REACH) {
-        if (!quiet) hrn_set_error("%s: radius %g over %d octaves reaches %g pixels, beyond %g", who, (double)radius, octaves,
-                                  (double)radius * (1 << octaves), (double)HRN_MNCC_PYRAMID_MAX_REACH);
-        return -2;
-    }
-    if (((H < W ? H : W) >> octaves) < HRN_MNCC_SCENE_MIN_SIDE) {
-        if (!quiet) hrn_set_error("%s: bad shape H=%d W=%d: octave %d of the frame must be at least %d a side", who, H, W, octaves,
-                                  HRN_MNCC_SCENE_MIN_SIDE);
-        return -2;
-    }
+// every limit of hrn_mncc_search_pyramid.  Its size query has no levels and no radii and passes 1 for each: with radius 1 the reach
+// rule cannot fire (2^HRN_MNCC_MAX_OCTAVES <= HRN_MNCC_PYRAMID_MAX_REACH).
+static int mncc_pyramid_check(const char* who, int B, int V, int H, int W, int P, int octaves, int levels, float radius, int coarse_levels,
+                              float refine_radius) {
+    if (int rc = mncc_scene_check(who, B, V, H, W)) return rc;
+    if (int rc = mncc_check_points(who, P)) return rc;
+    if (int rc = mncc_check_levels(who, "levels", levels)) return rc;
+    if (int rc = mncc_check_levels(who, "coarse_levels", coarse_levels)) return rc;
+    MNCC_LIMIT(octaves >= 0 && octaves <= HRN_MNCC_MAX_OCTAVES, "%s: octaves %d outside 0..%d", who, octaves, HRN_MNCC_MAX_OCTAVES);
+    if (int rc = mncc_check_radius(who, "radius", radius)) return rc;
+    MNCC_LIMIT(radius * (float)(1 << octaves) <= HRN_MNCC_PYRAMID_MAX_REACH, "%s: radius %g over %d octaves reaches %g pixels, beyond %g", who,
+               (double)radius, octaves, (double)radius * (1 << octaves), (double)HRN_MNCC_PYRAMID_MAX_REACH);
+    MNCC_LIMIT(((H < W ? H : W) >> octaves) >= HRN_MNCC_SCENE_MIN_SIDE, "%s: bad shape H=%d W=%d: octave %d of the frame must be at least %d a side",
+               who, H, W, octaves, HRN_MNCC_SCENE_MIN_SIDE);
+    if (int rc = mncc_check_radius(who, "refine_radius", refine_radius)) return rc;
+    MNCC_LIMIT(octaves == 0 || hrn_mncc_reduce2_grid_fits((size_t)B * V + (size_t)B, H, W),
+               "%s: bad batch B=%d V=%d: the planes of %d x %d frames exceed one launch of the reduction", who, B, V, H, W);
     return 0;
 }
+static_assert((float)(1 << HRN_MNCC_MAX_OCTAVES) <= HRN_MNCC_PYRAMID_MAX_REACH, "the size query's radius 1 passes the reach rule");
 
 size_t hrn_mncc_pyramid_workspace_bytes(int B, int V, int H, int W, int P, int octaves) {
-    if (hrn_mncc_scene_workspace_bytes(B, V, H, W, P) == 0 || mncc_pyramid_check(nullptr, H, W, octaves, 1.f) ||
-        (octaves > 0 && !hrn_mncc_reduce2_grid_fits((size_t)B * V + (size_t)B, H, W)))
-        return 0;
+    if (mncc_pyramid_check(nullptr, B, V, H, W, P, octaves, 1, 1.f, 1, 1.f)) return 0;
     return hrn_mncc_pyramid_workspace_bytes_impl(B, V, H, W, P, octaves);
 }
 
@@ -656,15 +671,7 @@ int hrn_mncc_search_pyramid(const float* ref, const float* ref_mask, const float
                             int P, int octaves, int levels, float radius, int coarse_levels, float refine_radius, float* shifts, float* trace,
                             void* workspace, size_t workspace_bytes, void* stream) {
     const char* who = "hrn_mncc_search_pyramid";
-    if (int rc = mncc_scene_check(who, B, V, H, W)) return rc;
-    if (int rc = mncc_check_points(who, P)) return rc;
-    HRN_CHECK(levels >= 1 && levels <= HRN_MNCC_MAX_LEVELS, -2, "%s: levels %d outside 1..%d", who, levels, HRN_MNCC_MAX_LEVELS);
-    HRN_CHECK(coarse_levels >= 1 && coarse_levels <= HRN_MNCC_MAX_LEVELS, -2, "%s: coarse_levels %d outside 1..%d", who, coarse_levels,
-              HRN_MNCC_MAX_LEVELS);
-    if (int rc = mncc_pyramid_check(who, H, W, octaves, radius)) return rc;
-    HRN_CHECK(refine_radius > 0.f && refine_radius <= 4.f, -2, "%s: refine_radius %g outside (0, 4]", who, (double)refine_radius);
-    HRN_CHECK(octaves == 0 || hrn_mncc_reduce2_grid_fits((size_t)B * V + (size_t)B, H, W), -2,
-              "%s: bad batch B=%d V=%d: the planes of %d x %d frames exceed one launch of the reduction", who, B, V, H, W);
+    if (int rc = mncc_pyramid_check(who, B, V, H, W, P, octaves, levels, radius, coarse_levels, refine_radius)) return rc;
     HRN_CHECK(ref && views && shifts && workspace, -2, "%s: null argument", who);
     HRN_CHECK(workspace_bytes >= hrn_mncc_pyramid_workspace_bytes_impl(B, V, H, W, P, octaves), -3, "%s: workspace too small", who);
     return hrn_launch_mncc_search_pyramid(ref, ref_mask, views, view_masks, B, V, H, W, P, octaves, levels, radius, coarse_levels, refine_radius,

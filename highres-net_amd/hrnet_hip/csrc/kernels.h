@@ -83,15 +83,13 @@ size_t hrn_mncc_scene_workspace_bytes_impl(int B, int V, int H, int W, int P);
 bool hrn_mncc_scene_grid_fits(int B, int V, int H, int W);
 int hrn_launch_mncc_grid_scene(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* centres,
                                int B, int V, int H, int W, int P, float width, float* scores, void* workspace, hipStream_t stream);
-int hrn_launch_mncc_search_scene(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H,
-                                 int W, int P, int levels, float radius, float* shifts, float* trace, void* workspace, hipStream_t stream);
-// the same from init (B,V,2) or null; last_trace / last_stride: where the last level's (dy, dx, score) goes when `trace` is null
+// init: (B,V,2) or null for (0, 0); last_trace / last_stride: where the last level's (dy, dx, score) goes when `trace` is null
 int hrn_launch_mncc_search_scene_from(const float* ref, const float* ref_mask, const float* views, const float* view_masks, const float* init,
                                       int B, int V, int H, int W, int P, int levels, float radius, float* shifts, float* trace,
                                       float* last_trace, int last_stride, void* workspace, hipStream_t stream);
 int hrn_launch_mncc_apply_scene(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
                                 float* out_valid, hipStream_t stream);
-unsigned hrn_mncc_scene_mean_chunks(int H, int W);                 // the chunks of a frame's mean, and the pre-pass that fills
+// the pre-pass of the frames' means, for registration_local.hip as well
 void hrn_launch_mncc_scene_means(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H,
                                  int W, double* means, hipStream_t stream);      // means[((plane) * chunks + chunk) * 2] = {sum, count}
 

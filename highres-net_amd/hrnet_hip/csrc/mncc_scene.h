@@ -1,6 +1,6 @@
 // What the kernels of the tiled masked-NCC registration share (DESIGN.md sections 7g and 7i): registration_scene.hip, one shift per view,
 // and registration_local.hip, a shift per block of tiles.  The tile, the LDS window and its staging, and the two passes of the sampler are
-// written once here; the body of a level kernel is mncc_scene_level.h.
+// written once here, and so is the host's plan of the tiles and the workspace; the body of a level kernel is mncc_scene_level.h.
 #pragma once
 #include "kernels.h"
 #include "wave_sums.h"
@@ -129,5 +129,43 @@ double level_ratio(int P) {                      // as registration.hip: 1 / (P 
 
 // the counted arithmetic of one level, per pixel, as registration.hip counts it
 double level_flops(int P) { return P * 12.0 + (double)P * P * 32.0; }
+
+// ----------------------------------------------------------------------------- the workspace of a tiled search
+// the tiles of a frame, the chunks of its mean, and the three parts of the workspace in their order: the chunks' {sum, count} of every
+// plane, the six sums of every tile at every grid point, the centres that a level hands to the next
+struct ScenePlan {
+    unsigned tiles_x, tiles_y, tiles, chunks;
+    size_t means_bytes, sums_bytes, centres_bytes;
+    size_t bytes() const { return means_bytes + sums_bytes + centres_bytes; }
+};
+
+ScenePlan plan(int B, int V, int H, int W, int P) {
+    ScenePlan p;
+    p.tiles_x = (unsigned)((W + SC_TILE - 1) / SC_TILE);
+    p.tiles_y = (unsigned)((H + SC_TILE - 1) / SC_TILE);
+    p.tiles = p.tiles_x * p.tiles_y;
+    const size_t hw = (size_t)H * W, chunks = (hw + SC_MEAN_CHUNK - 1) / SC_MEAN_CHUNK;
+    p.chunks = (unsigned)(chunks < (size_t)SC_MEAN_CHUNKS ? chunks : (size_t)SC_MEAN_CHUNKS);
+    const size_t bv = (size_t)B * V;
+    p.means_bytes = 16 * (bv + (size_t)B) * p.chunks;
+    p.sums_bytes = 8 * (size_t)RG_NSUM * P * P * bv * p.tiles;
+    p.centres_bytes = 8 * bv;                    // one (dy, dx) a view; registration_local.hip: one a block
+    return p;
+}
+
+struct SceneWorkspace {
+    double* means;
+    double* sums;
+    float* centres;
+};
+
+SceneWorkspace carve(void* workspace, const ScenePlan& p) {
+    SceneWorkspace w;
+    unsigned char* base = static_cast<unsigned char*>(workspace);
+    w.means = reinterpret_cast<double*>(base);
+    w.sums = reinterpret_cast<double*>(base + p.means_bytes);
+    w.centres = reinterpret_cast<float*>(base + p.means_bytes + p.sums_bytes);
+    return w;
+}
 
 }  // namespace

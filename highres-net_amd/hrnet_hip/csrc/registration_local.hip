@@ -196,23 +196,17 @@ __global__ __launch_bounds__(SC_THREADS) void field_apply_kernel(const float* __
     }
 }
 
-struct LocalPlan {
-    unsigned tiles_x, tiles_y, chunks, bt, nby, nbx;
-    size_t means_bytes, sums_bytes, centres_bytes;
+// the scene search's plan, with the blocks of the two axes and a centre per block
+struct LocalPlan : ScenePlan {
+    unsigned bt, nby, nbx;
 };
 
 LocalPlan plan(int B, int V, int H, int W, int P, int block) {
-    LocalPlan p;
-    p.tiles_x = (unsigned)((W + SC_TILE - 1) / SC_TILE);
-    p.tiles_y = (unsigned)((H + SC_TILE - 1) / SC_TILE);
-    p.chunks = hrn_mncc_scene_mean_chunks(H, W);
+    LocalPlan p{plan(B, V, H, W, P)};
     p.bt = (unsigned)(block / SC_TILE);
     p.nby = (unsigned)hrn_mncc_local_blocks_impl(H, block);
     p.nbx = (unsigned)hrn_mncc_local_blocks_impl(W, block);
-    const size_t bv = (size_t)B * V;
-    p.means_bytes = 16 * (bv + (size_t)B) * p.chunks;
-    p.sums_bytes = 8 * (size_t)RG_NSUM * P * P * bv * p.tiles_x * p.tiles_y;
-    p.centres_bytes = 8 * bv * p.nby * p.nbx;
+    p.centres_bytes *= (size_t)p.nby * p.nbx;
     return p;
 }
 
@@ -224,8 +218,7 @@ int hrn_mncc_local_blocks_impl(int L, int block) {
 }
 
 size_t hrn_mncc_local_workspace_bytes_impl(int B, int V, int H, int W, int P, int block) {
-    const LocalPlan p = plan(B, V, H, W, P, block);
-    return p.means_bytes + p.sums_bytes + p.centres_bytes;
+    return plan(B, V, H, W, P, block).bytes();
 }
 
 // B V tiles is the grid of the level and of the resampler, B V blocks that of the finish
@@ -238,24 +231,21 @@ int hrn_launch_mncc_search_local(const float* ref, const float* ref_mask, const 
                                  int B, int V, int H, int W, int P, int levels, float radius, int block, float min_valid, float* field,
                                  float* trace, float* ok, void* workspace, hipStream_t stream) {
     const LocalPlan p = plan(B, V, H, W, P, block);
-    unsigned char* base = static_cast<unsigned char*>(workspace);
-    double* means = reinterpret_cast<double*>(base);
-    double* sums = reinterpret_cast<double*>(base + p.means_bytes);
-    float* centres = reinterpret_cast<float*>(base + p.means_bytes + p.sums_bytes);
-    const unsigned bv = (unsigned)(B * V), tiles = p.tiles_x * p.tiles_y;
+    const SceneWorkspace w = carve(workspace, p);
+    const unsigned bv = (unsigned)(B * V);
     HrnProfScope prof("mncc_search_local", level_flops(P) * levels * B * V * H * W, 4.0 * B * V * (2.0 + 2.0 * levels) * H * W, stream);
-    hrn_launch_mncc_scene_means(ref, ref_mask, views, view_masks, B, V, H, W, means, stream);
+    hrn_launch_mncc_scene_means(ref, ref_mask, views, view_masks, B, V, H, W, w.means, stream);
     HRN_LAUNCH_CHECK();
     double width = (double)(2.f * radius);
     const double ratio = level_ratio(P);
     for (int k = 0; k < levels; ++k) {
-        const float* from = k ? centres : init;                          // the first centre of every block of a view is init[view]
+        const float* from = k ? w.centres : init;                        // the first centre of every block of a view is init[view]
         const bool last = k == levels - 1;
-        hipLaunchKernelGGL(local_level_kernel, dim3(bv * tiles), dim3(SC_THREADS), 0, stream, ref, ref_mask, views, view_masks, from,
-                           (const double*)means, p.chunks, bv, V, H, W, P, width, p.tiles_x, tiles, sums, k ? 1 : 0, p.bt, p.nby, p.nbx);
+        hipLaunchKernelGGL(local_level_kernel, dim3(bv * p.tiles), dim3(SC_THREADS), 0, stream, ref, ref_mask, views, view_masks, from,
+                           (const double*)w.means, p.chunks, bv, V, H, W, P, width, p.tiles_x, p.tiles, w.sums, k ? 1 : 0, p.bt, p.nby, p.nbx);
         HRN_LAUNCH_CHECK();
-        hipLaunchKernelGGL(local_finish_kernel, dim3(bv * p.nby * p.nbx), dim3(LC_FINISH_THREADS), 0, stream, (const double*)sums, from,
-                           k ? 1 : 0, init, P, width, p.tiles_x, p.tiles_y, p.bt, p.nby, p.nbx, H, W, block, centres,
+        hipLaunchKernelGGL(local_finish_kernel, dim3(bv * p.nby * p.nbx), dim3(LC_FINISH_THREADS), 0, stream, (const double*)w.sums, from,
+                           k ? 1 : 0, init, P, width, p.tiles_x, p.tiles_y, p.bt, p.nby, p.nbx, H, W, block, w.centres,
                            trace ? trace + 3 * k : (float*)nullptr, 3 * levels, last ? field : (float*)nullptr, last ? ok : (float*)nullptr,
                            (double)min_valid);
         HRN_LAUNCH_CHECK();
@@ -267,10 +257,9 @@ int hrn_launch_mncc_search_local(const float* ref, const float* ref_mask, const 
 int hrn_launch_mncc_apply_field(const float* views, const float* view_masks, const float* field, int B, int V, int H, int W, int block,
                                 float* out, float* out_valid, hipStream_t stream) {
     const LocalPlan p = plan(B, V, H, W, HRN_MNCC_MIN_POINTS, block);
-    const unsigned tiles = p.tiles_x * p.tiles_y;
     HrnProfScope prof("mncc_apply_field", 2.0 * 42.0 * B * V * H * W, 4.0 * B * V * (4.0 * H * W + 2.0 * p.nby * p.nbx), stream);
-    hipLaunchKernelGGL(field_apply_kernel, dim3((unsigned)(B * V) * tiles), dim3(SC_THREADS), 0, stream, views, view_masks, field, H, W, block,
-                       (int)p.nby, (int)p.nbx, p.tiles_x, tiles, out, out_valid);
+    hipLaunchKernelGGL(field_apply_kernel, dim3((unsigned)(B * V) * p.tiles), dim3(SC_THREADS), 0, stream, views, view_masks, field, H, W, block,
+                       (int)p.nby, (int)p.nbx, p.tiles_x, p.tiles, out, out_valid);
     HRN_LAUNCH_CHECK();
     return 0;
 }

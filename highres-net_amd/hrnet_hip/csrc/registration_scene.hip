@@ -149,39 +149,6 @@ __global__ __launch_bounds__(SC_THREADS) void scene_apply_kernel(const float* __
     }
 }
 
-struct ScenePlan {
-    unsigned tiles_x, tiles, chunks;
-    size_t means_bytes, centres_bytes, sums_bytes;
-};
-
-ScenePlan plan(int B, int V, int H, int W, int P) {
-    ScenePlan p;
-    p.tiles_x = (unsigned)((W + SC_TILE - 1) / SC_TILE);
-    p.tiles = p.tiles_x * (unsigned)((H + SC_TILE - 1) / SC_TILE);
-    const size_t hw = (size_t)H * W, chunks = (hw + SC_MEAN_CHUNK - 1) / SC_MEAN_CHUNK;
-    p.chunks = (unsigned)(chunks < (size_t)SC_MEAN_CHUNKS ? chunks : (size_t)SC_MEAN_CHUNKS);
-    const size_t bv = (size_t)B * V;
-    p.means_bytes = 16 * (bv + (size_t)B) * p.chunks;
-    p.sums_bytes = 8 * (size_t)RG_NSUM * P * P * bv * p.tiles;
-    p.centres_bytes = 8 * bv;
-    return p;
-}
-
-struct SceneWorkspace {
-    double* means;
-    double* sums;
-    float* centres;
-};
-
-SceneWorkspace carve(void* workspace, const ScenePlan& p) {
-    SceneWorkspace w;
-    unsigned char* base = static_cast<unsigned char*>(workspace);
-    w.means = reinterpret_cast<double*>(base);
-    w.sums = reinterpret_cast<double*>(base + p.means_bytes);
-    w.centres = reinterpret_cast<float*>(base + p.means_bytes + p.sums_bytes);
-    return w;
-}
-
 void launch_means(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H, int W,
                   const ScenePlan& p, double* means, hipStream_t stream) {
     const unsigned bv = (unsigned)(B * V);
@@ -191,17 +158,14 @@ void launch_means(const float* ref, const float* ref_mask, const float* views, c
 
 }  // namespace
 
-// the means pre-pass and its chunks for registration_local.hip, whose workspace begins as this file's does
-unsigned hrn_mncc_scene_mean_chunks(int H, int W) { return plan(1, 1, H, W, HRN_MNCC_MIN_POINTS).chunks; }
-
+// the means pre-pass for registration_local.hip, whose workspace begins as this file's does
 void hrn_launch_mncc_scene_means(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H,
                                  int W, double* means, hipStream_t stream) {
     launch_means(ref, ref_mask, views, view_masks, B, V, H, W, plan(B, V, H, W, HRN_MNCC_MIN_POINTS), means, stream);
 }
 
 size_t hrn_mncc_scene_workspace_bytes_impl(int B, int V, int H, int W, int P) {
-    const ScenePlan p = plan(B, V, H, W, P);
-    return p.means_bytes + p.sums_bytes + p.centres_bytes;
+    return plan(B, V, H, W, P).bytes();
 }
 
 // B V tiles is the grid of the level and of the resampler
@@ -225,12 +189,6 @@ int hrn_launch_mncc_grid_scene(const float* ref, const float* ref_mask, const fl
                        p.tiles, scores, (float*)nullptr, (float*)nullptr, 0, (float*)nullptr);
     HRN_LAUNCH_CHECK();
     return 0;
-}
-
-int hrn_launch_mncc_search_scene(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H,
-                                 int W, int P, int levels, float radius, float* shifts, float* trace, void* workspace, hipStream_t stream) {
-    return hrn_launch_mncc_search_scene_from(ref, ref_mask, views, view_masks, nullptr, B, V, H, W, P, levels, radius, shifts, trace, nullptr, 0,
-                                             workspace, stream);
 }
 
 // The search with its first centre read from init (B,V,2); null: (0, 0).  last_trace (used where `trace` is null; may be null): the last

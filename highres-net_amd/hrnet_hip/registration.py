@@ -76,6 +76,19 @@ def _search_args(points_per_dim, levels, radius):
     return P, levels, radius
 
 
+def _problem(scene, lrs, lr_masks, ref, ref_mask, search=()):
+    """The opening of every search: the frames, the reference and, where given, `search` = (points_per_dim, levels, radius), checked
+    -> (ref, ref_mask) + _search_args(*search).  The caller's own checks come next and _on_device last: a bad argument is reported first."""
+    _frames(lrs, lr_masks, scene)
+    ref, ref_mask = _reference(lrs, lr_masks, ref, ref_mask)
+    return (ref, ref_mask) + (_search_args(*search) if search else ())
+
+
+def _no_trace(search_kwargs, message):
+    if "return_trace" in search_kwargs:
+        raise TypeError(message)
+
+
 def mncc_search(lrs, lr_masks=None, ref=None, ref_mask=None, points_per_dim=7, levels=6, radius=1.0, return_trace=False):
     """lrs (B,V,H,W), lr_masks (B,V,H,W) 0 / non-zero or None (all clear) -> shifts (B,V,2) f32 = (dy, dx): S(view, shift) lies on the
     reference frame.  ref (B,H,W) / ref_mask (B,H,W): the frame to register against; None takes lrs[:, 0] and lr_masks[:, 0].  Level k
@@ -94,9 +107,7 @@ def _init(init, lrs):
 
 
 def _search(scene, lrs, lr_masks, ref, ref_mask, points_per_dim, levels, radius, return_trace, init=None):
-    _frames(lrs, lr_masks, scene)
-    ref, ref_mask = _reference(lrs, lr_masks, ref, ref_mask)
-    P, levels, radius = _search_args(points_per_dim, levels, radius)
+    ref, ref_mask, P, levels, radius = _problem(scene, lrs, lr_masks, ref, ref_mask, (points_per_dim, levels, radius))
     _init(init, lrs)
     _on_device(lrs=lrs, lr_masks=lr_masks, ref=ref, ref_mask=ref_mask, init=init)
     if init is not None:
@@ -114,8 +125,7 @@ def mncc_grid(lrs, lr_masks=None, ref=None, ref_mask=None, centres=None, points_
 
 
 def _grid(scene, lrs, lr_masks, ref, ref_mask, centres, points_per_dim, width):
-    _frames(lrs, lr_masks, scene)
-    ref, ref_mask = _reference(lrs, lr_masks, ref, ref_mask)
+    ref, ref_mask = _problem(scene, lrs, lr_masks, ref, ref_mask)
     P = binding.mncc_int("points_per_dim", points_per_dim, binding.MNCC_POINTS)
     width = float(width)
     if not 0.0 < width <= 2.0 * binding.MNCC_MAX_RADIUS:
@@ -150,8 +160,7 @@ def _shift(scene, lrs, lr_masks, shifts):
 def register_views(lrs, lr_masks=None, **search_kwargs):
     """mncc_search, then shift_views by what it found: -> (registered, valid, shifts).  search_kwargs: ref, ref_mask, points_per_dim,
     levels, radius."""
-    if "return_trace" in search_kwargs:
-        raise TypeError("register_views returns no trace: call mncc_search(..., return_trace=True) and shift_views")
+    _no_trace(search_kwargs, "register_views returns no trace: call mncc_search(..., return_trace=True) and shift_views")
     shifts = mncc_search(lrs, lr_masks, **search_kwargs)
     registered, valid = shift_views(lrs, lr_masks, shifts)
     return registered, valid, shifts
@@ -178,8 +187,7 @@ def shift_scene(lrs, lr_masks, shifts):
 def register_scene(lrs, lr_masks=None, **search_kwargs):
     """mncc_search_scene, then shift_scene by what it found: -> (registered, valid, shifts).  search_kwargs: ref, ref_mask,
     points_per_dim, levels, radius.  `registered` goes to `HRNet.forward_tiled` as the views did."""
-    if "return_trace" in search_kwargs:
-        raise TypeError("register_scene returns no trace: call mncc_search_scene(..., return_trace=True) and shift_scene")
+    _no_trace(search_kwargs, "register_scene returns no trace: call mncc_search_scene(..., return_trace=True) and shift_scene")
     shifts = mncc_search_scene(lrs, lr_masks, **search_kwargs)
     registered, valid = shift_scene(lrs, lr_masks, shifts)
     return registered, valid, shifts
@@ -206,9 +214,7 @@ def mncc_search_local(lrs, lr_masks=None, ref=None, ref_mask=None, block=128, in
     A block is ok when its last score is finite and its common valid pixels are at least min_valid of its area; a block that is not ok
     holds init.  The deviation from init is bounded by the sum of the levels' half widths; there is no smoothing.  return_trace: also
     trace (B,V,by,bx,levels,3) = (dy, dx, score) per level and ok (B,V,by,bx) f32 0 / 1.  Not differentiable."""
-    _frames(lrs, lr_masks, True)
-    ref, ref_mask = _reference(lrs, lr_masks, ref, ref_mask)
-    P, levels, radius = _search_args(points_per_dim, levels, radius)
+    ref, ref_mask, P, levels, radius = _problem(True, lrs, lr_masks, ref, ref_mask, (points_per_dim, levels, radius))
     block, min_valid = _local_args(block, min_valid)
     _init(init, lrs)
     _on_device(lrs=lrs, lr_masks=lr_masks, ref=ref, ref_mask=ref_mask, init=init)
@@ -235,8 +241,7 @@ def register_scene_local(lrs, lr_masks=None, block=128, local_levels=4, local_ra
     local_levels levels of local_radius, then shift_field: -> (registered, valid, field, shifts).  octaves > 0: the global shifts come
     from mncc_search_pyramid over that many octaves instead (search_kwargs then also takes coarse_levels and refine_radius, and radius
     defaults to the pyramid's)."""
-    if "return_trace" in search_kwargs:
-        raise TypeError("register_scene_local returns no trace: call mncc_search_scene and mncc_search_local(..., return_trace=True)")
+    _no_trace(search_kwargs, "register_scene_local returns no trace: call mncc_search_scene and mncc_search_local(..., return_trace=True)")
     _local_args(block, min_valid)
     _search_args(search_kwargs.get("points_per_dim", 7), local_levels, local_radius)
     octaves = binding.mncc_int("octaves", octaves, binding.MNCC_OCTAVES)
@@ -294,9 +299,7 @@ def mncc_search_pyramid(lrs, lr_masks=None, ref=None, ref_mask=None, octaves=2, 
     One call of `hrn_mncc_search_pyramid`: nothing returns to the host in between.  octaves=0 is `mncc_search_scene`, bit for bit.
     return_trace: also (B,V,octaves+1,3) = (dy, dx, score) of every octave's last level in that octave's pixels, coarsest first.  Not
     differentiable."""
-    _frames(lrs, lr_masks, True)
-    ref, ref_mask = _reference(lrs, lr_masks, ref, ref_mask)
-    P, levels, radius = _search_args(points_per_dim, levels, radius)
+    ref, ref_mask, P, levels, radius = _problem(True, lrs, lr_masks, ref, ref_mask, (points_per_dim, levels, radius))
     octaves, coarse_levels, refine_radius = _pyramid_args(lrs.shape, octaves, radius, coarse_levels, refine_radius)
     _on_device(lrs=lrs, lr_masks=lr_masks, ref=ref, ref_mask=ref_mask)
     shifts, trace = torch.ops.hrnet_hip.mncc_search_pyramid(ref, ref_mask, lrs, lr_masks, octaves, P, levels, radius, coarse_levels, refine_radius)
@@ -306,8 +309,7 @@ def mncc_search_pyramid(lrs, lr_masks=None, ref=None, ref_mask=None, octaves=2, 
 def register_scene_pyramid(lrs, lr_masks=None, **search_kwargs):
     """mncc_search_pyramid, then shift_scene by what it found: -> (registered, valid, shifts).  search_kwargs: ref, ref_mask, octaves,
     points_per_dim, levels, radius, coarse_levels, refine_radius."""
-    if "return_trace" in search_kwargs:
-        raise TypeError("register_scene_pyramid returns no trace: call mncc_search_pyramid(..., return_trace=True) and shift_scene")
+    _no_trace(search_kwargs, "register_scene_pyramid returns no trace: call mncc_search_pyramid(..., return_trace=True) and shift_scene")
     shifts = mncc_search_pyramid(lrs, lr_masks, **search_kwargs)
     registered, valid = shift_scene(lrs, lr_masks, shifts)
     return registered, valid, shifts
