@@ -1,18 +1,25 @@
 // The shift-searched, brightness-corrected structural similarity cSSIM (the definition is in include/hrnet_hip.h):
 // the score beside shift_loss.hip's cPSNR, over the same crops and the same (2 beta + 1)^2 offsets.  With s the centre crop of sr and,
 // for the offset k = u (2 beta + 1) + v, g / m the crops of hr / map at (u, v) and b = bias_k, the compared pair is X = m g and
-// Y = m (s + b); G is a separable T-tap window over "valid" positions.  The bias leaves the filters:
-//   G Y = G(m s) + b G m,   G Y^2 = G(m s^2) + 2 b G(m s) + b^2 G m,   G XY = G(m g s) + b G(m g)
-// so only G(m s), G(m s^2), G(m g s) depend on the offset; G m, G(m g), G(m g^2) are functions of the hr position alone.
+// Y = m (s + b); G is a separable T-tap window over "valid" positions.  Variances do not change when a constant leaves both images, and
+// fp32 needs it to: on a bright, clear, low-contrast frame G X^2 - (G X)^2 is the difference of two numbers of the size of level^2.  So
+// a tile takes c = the mean of g over the clear pixels of its hr window and filters the centred pair
+//   X~ = m (g - c),   Y~ = m (s + b - c)          (X = X~ + c m, Y = Y~ + c m; m X~ = X~)
+// and with p = G m, w = 1 - p:
+//   mu_x = G X~ + c p,   v_x / cov_norm = (G X~^2 - (G X~)^2) + 2 c w G X~ + c^2 p w,       mu_y, v_y alike with Y~,
+//   v_xy / cov_norm = (G X~Y~ - G X~ G Y~) + c w (G X~ + G Y~) + c^2 p w.
+// w is filtered as G(1 - m) - (S - 1), S = the squared sum of the definition's taps: in a clear window G(1 - m) is exactly 0 and nothing
+// of the size of c^2 is ever subtracted.  Only G Y~, G Y~^2, G X~Y~ depend on the offset (the bias enters as s - (c - b), one
+// subtraction per pixel read); w, G X~ and v_x are functions of the hr position alone.
 //
 //   cssim_pre_kernel / cssim_pre_finish_kernel   n_k and bias_k of every sample and offset: fp64 sums of a run of crop pixels per
 //                                                wave, the waves' sums added in index order
 //   cssim_tile_kernel<T, BETA>                   a workgroup owns 16 x (64 - T + 1) pixels of one sample's SSIM map.  It stages the
 //                                                (16 + T - 1) x 64 window of s, and of hr / map that window plus 2 beta rows and
-//                                                columns, in LDS once; filters G m, G(m g), G(m g^2) over the tile plus 2 beta once;
+//                                                columns, in LDS once (hr as X~); filters w, G X~, v_x over the tile plus 2 beta once;
 //                                                then walks the offsets out of LDS.  Per offset, pass 1 runs down the columns: a
 //                                                lane owns a window column (64 lanes = the 64 columns, a wave per 4 map rows),
-//                                                reads 4 + T - 1 rows of s / g / m once each and slides the taps over them in
+//                                                reads 4 + T - 1 rows of s / X~ / m once each and slides the taps over them in
 //                                                registers.  Pass 2 runs along the rows: a lane owns 4 map pixels of one row, reads
 //                                                4 + T - 1 values per field once and slides again; the rows' stride of 65 and the
 //                                                lanes' 4-float spacing put a wave's 64 reads on 64 banks.  The SSIM of its 4 pixels is
@@ -46,7 +53,7 @@ __host__ __device__ constexpr int cs_acs(int T, int beta) {                     
     return ac + ((1 - ac) & 3);
 }
 
-// the LDS of a tile, in floats: S | G | A (3 fields) | V | M (bytes)
+// the LDS of a tile, in floats: S | G (X~) | A (3 fields) | V | M (bytes)
 struct TileLds { int s, g, a, v, m, total; };
 __host__ __device__ constexpr TileLds cs_lds(int T, int beta) {
     const int wr = CS_TH + T - 1, gr = wr + 2 * beta, gc = CS_WIN + 2 * beta, ar = CS_TH + 2 * beta;
@@ -140,7 +147,7 @@ template <int T, int BETA>
 __global__ __launch_bounds__(256) void cssim_tile_kernel(const float* __restrict__ srs, const float* __restrict__ hrs,
                                                          const float* __restrict__ maps, const double* __restrict__ nbias, int H, int W,
                                                          int clip, int ntx, Taps tp, float cov_norm, float c1, float c2,
-                                                         double* __restrict__ partial) {
+                                                         float tap_excess, double* __restrict__ partial) {
     constexpr int TW = cs_tw(T), WR = CS_TH + T - 1, NIN = CS_RUN + T - 1, border = BETA;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr TileLds L = cs_lds(T, BETA);
@@ -180,18 +187,49 @@ __global__ __launch_bounds__(256) void cssim_tile_kernel(const float* __restrict
     }
     __syncthreads();
 
-    // ---- the fields of the hr position alone, over the tile plus 2 beta: A[f] = G m, G(m g), G(m g^2)
+    // ---- the tile's centre c: the mean of g over the clear pixels of its hr window (0 without one, or where it is not finite).  Every
+    // thread sums its own pixels in index order, a wave's butterfly leaves one sum in all its lanes, and every thread adds the four
+    // waves' sums in wave order: the same bits in every thread, and a function of the sample's own data and the tile's place alone.
+    float cen;
+    {
+        float n = 0.f, sg = 0.f;
+        for (int i = tid; i < GR * GC; i += 256) {
+            const float m = (float)M[i];
+            n += m;
+            sg = fmaf(m, G[i], sg);
+        }
+#pragma unroll
+        for (int mask = 1; mask < 64; mask <<= 1) { n += __shfl_xor(n, mask); sg += __shfl_xor(sg, mask); }
+        if (lane == 0) { V[2 * wave] = n; V[2 * wave + 1] = sg; }
+        __syncthreads();
+        n = (V[0] + V[2]) + (V[4] + V[6]);
+        sg = (V[1] + V[3]) + (V[5] + V[7]);
+        cen = n > 0.f ? sg / n : 0.f;
+        if (!(fabsf(cen) <= 3.0e38f)) cen = 0.f;
+        __syncthreads();                                            // V is the filters' scratch next
+    }
+    for (int i = tid; i < GR * GC; i += 256) G[i] = (float)M[i] * (G[i] - cen);          // X~; a thread rewrites what it alone reads here
+    __syncthreads();
+
+    // ---- the fields of the hr position alone, over the tile plus 2 beta: A[f] = G(1 - m), G X~, G X~^2 ...
     for (int f = 0; f < 3; ++f) {
         auto field = [&](int r, int c) {
             const int i = r * GC + c;
-            const float m = (float)M[i], g = G[i];
-            const float mg = m * g;
-            return f == 0 ? m : (f == 1 ? mg : mg * g);
+            const float x = G[i];
+            return f == 0 ? 1.f - (float)M[i] : (f == 1 ? x : x * x);
         };
         cs_filter<T, true>(tp, field, V, GC, AR, GC, tid);
         __syncthreads();
         cs_filter<T, false>(tp, [&](int r, int c) { return V[r * GC + c]; }, A + f * AR * ACS, ACS, AR, AC, tid);
         __syncthreads();
+    }
+    // ... made w, G X~, v_x.  A thread reads back the elements it wrote itself; pass 2 reads them behind the offset loop's first barrier.
+    for (int i = tid; i < AR * AC; i += 256) {
+        const int r = i / AC, a = r * ACS + (i - r * AC);
+        const float w = A[a] - tap_excess, ax = A[AR * ACS + a], axx = A[2 * AR * ACS + a];
+        const float cw = cen * w, e = (cen * (1.f - w)) * cw;
+        A[a] = w;
+        A[2 * AR * ACS + a] = cov_norm * (fmaf(2.f * cw, ax, fmaf(-ax, ax, axx)) + e);
     }
 
     // pass 1: window column `lane`, map rows 4 wave ..; pass 2: map row 4 wave + lane / 16, map columns 4 (lane % 16) ..
@@ -205,17 +243,18 @@ __global__ __launch_bounds__(256) void cssim_tile_kernel(const float* __restrict
     for (int k = 0; k < nk; ++k) {
         const int u = k / nb, v = k - u * nb;
         {
-            f32x2 p01[NIN];                                         // (m s, m s^2)
-            float p2[NIN];                                          // m g s
+            f32x2 p01[NIN];                                         // (Y~, Y~^2)
+            float p2[NIN];                                          // X~ Y~
+            const float cs = (float)((double)cen - nbk[2 * k + 1]); // Y~ = m (s - (c - b))
             const int r0 = CS_RUN * wave;
             const float* Sp = S + r0 * CS_WIN + lane;
             const int g0 = (r0 + u) * GC + lane + v;
 #pragma unroll
             for (int i = 0; i < NIN; ++i) {
-                const float s = Sp[i * CS_WIN], m = (float)M[g0 + i * GC], g = G[g0 + i * GC];
-                const float ms = m * s;
-                p01[i] = f32x2{ms, ms * s};
-                p2[i] = (m * g) * s;
+                const float t = Sp[i * CS_WIN] - cs, m = (float)M[g0 + i * GC], x = G[g0 + i * GC];
+                const float mt = m * t;
+                p01[i] = f32x2{mt, mt * t};
+                p2[i] = x * t;
             }
             float* Vp = V + r0 * CS_VS + lane;
 #pragma unroll
@@ -233,7 +272,6 @@ __global__ __launch_bounds__(256) void cssim_tile_kernel(const float* __restrict
             }
         }
         __syncthreads();
-        const float b = (float)nbk[2 * k + 1];
         double sum = 0.0;
         {
             f32x2 q01[NIN];
@@ -248,22 +286,20 @@ __global__ __launch_bounds__(256) void cssim_tile_kernel(const float* __restrict
 #pragma unroll
             for (int j = 0; j < CS_RUN; ++j) {
                 f32x2 f01 = tp.w[0] * q01[j];
-                float mgs = tp.w[0] * q2[j];
+                float axy = tp.w[0] * q2[j];
 #pragma unroll
                 for (int o = 1; o < T; ++o) {
                     f01 = fma2(tp.w[o], q01[j + o], f01);
-                    mgs = fmaf(tp.w[o], q2[j + o], mgs);
+                    axy = fmaf(tp.w[o], q2[j + o], axy);
                 }
-                const float ms = f01.x, mss = f01.y;
+                const float ay = f01.x, ayy = f01.y;
                 const bool ok = (valid >> j) & 1;
                 const int a = ok ? ai + j : 0;                      // the lanes past the tile's last column read nothing out of bounds
-                const float gm = A[a], gmg = A[AR * ACS + a], gmgg = A[2 * AR * ACS + a];
-                const float mux = gmg, muy = fmaf(b, gm, ms);
-                const float eyy = fmaf(b * b, gm, fmaf(2.f * b, ms, mss));
-                const float exy = fmaf(b, gmg, mgs);
-                const float vx = cov_norm * (gmgg - mux * mux);
-                const float vy = cov_norm * (eyy - muy * muy);
-                const float vxy = cov_norm * (exy - mux * muy);
+                const float w = A[a], ax = A[AR * ACS + a], vx = A[2 * AR * ACS + a];
+                const float cp = cen * (1.f - w), cw = cen * w, e = cp * cw;
+                const float mux = ax + cp, muy = ay + cp;
+                const float vy = cov_norm * (fmaf(2.f * cw, ay, fmaf(-ay, ay, ayy)) + e);
+                const float vxy = cov_norm * (fmaf(cw, ax + ay, fmaf(-ax, ay, axy)) + e);
                 const float num = (2.f * mux * muy + c1) * (2.f * vxy + c2);
                 const float den = (mux * mux + muy * muy + c1) * (vx + vy + c2);
                 if (ok) sum += (double)(num / den);
@@ -328,21 +364,22 @@ Plan plan_of(int B, int H, int W, int border, int window) {
 
 template <int T, int BETA>
 int launch_tile_at(const float* srs, const float* hrs, const float* maps, const double* nbias, int B, int H, int W, int clip, const Plan& p,
-                   const Taps& tp, float cov_norm, float c1, float c2, double* partial, hipStream_t stream) {
+                   const Taps& tp, float cov_norm, float c1, float c2, float tap_excess, double* partial, hipStream_t stream) {
     constexpr int bytes = cs_lds(T, BETA).total * (int)sizeof(float);
     hipLaunchKernelGGL((cssim_tile_kernel<T, BETA>), dim3((unsigned)p.tiles, B), dim3(256), bytes, stream, srs, hrs, maps, nbias, H, W, clip,
-                       p.ntx, tp, cov_norm, c1, c2, partial);
+                       p.ntx, tp, cov_norm, c1, c2, tap_excess, partial);
     HRN_LAUNCH_CHECK();
     return 0;
 }
 
 template <int T>
 int launch_tile(const float* srs, const float* hrs, const float* maps, const double* nbias, int B, int H, int W, int border, int clip,
-                const Plan& p, const Taps& tp, float cov_norm, float c1, float c2, double* partial, hipStream_t stream) {
-#define CS_AT(BETA) case BETA: return launch_tile_at<T, BETA>(srs, hrs, maps, nbias, B, H, W, clip, p, tp, cov_norm, c1, c2, partial, stream)
+                const Plan& p, const Taps& tp, float cov_norm, float c1, float c2, float tap_excess, double* partial, hipStream_t stream) {
+#define CS_AT(BETA) \
+    case BETA: return launch_tile_at<T, BETA>(srs, hrs, maps, nbias, B, H, W, clip, p, tp, cov_norm, c1, c2, tap_excess, partial, stream)
     switch (border) {
         CS_AT(0); CS_AT(1); CS_AT(2); CS_AT(3); CS_AT(4); CS_AT(5); CS_AT(6); CS_AT(7);
-        default: return launch_tile_at<T, 8>(srs, hrs, maps, nbias, B, H, W, clip, p, tp, cov_norm, c1, c2, partial, stream);
+        default: return launch_tile_at<T, 8>(srs, hrs, maps, nbias, B, H, W, clip, p, tp, cov_norm, c1, c2, tap_excess, partial, stream);
     }
 #undef CS_AT
 }
@@ -359,14 +396,16 @@ int hrn_launch_shift_cssim(const float* srs, const float* hrs, const float* maps
     HRN_CHECK((size_t)H * W <= 0x7fffffffu, -2, "cssim: a frame of %d x %d exceeds 2^31 pixels", H, W);
     HRN_CHECK(p.tiles <= 0x7fffffffu && p.runs <= 0x7fffffffu, -2, "cssim: %zu tiles exceed the grid limit", p.tiles);
     Taps tp;
-    float cov_norm = 1.f;
+    float cov_norm = 1.f, tap_excess = 0.f;     // tap_excess: (the sum of the definition's taps)^2 - 1, so that G m = 1 + tap_excess - G(1 - m)
     if (p.T == 7) {
         for (int i = 0; i < CS_MAX_TAPS; ++i) tp.w[i] = i < 7 ? (float)(1.0 / 7.0) : 0.f;
         cov_norm = (float)(49.0 / 48.0);
     } else {
         double g[CS_MAX_TAPS], sum = 0.0;
         for (int i = 0; i < 11; ++i) { const double x = i - 5; g[i] = exp(-x * x / (2.0 * 1.5 * 1.5)); sum += g[i]; }
-        for (int i = 0; i < 11; ++i) tp.w[i] = (float)(g[i] / sum);
+        double held = 0.0;
+        for (int i = 0; i < 11; ++i) { tp.w[i] = (float)(g[i] / sum); held += (double)tp.w[i]; }
+        tap_excess = (float)(held * held - 1.0);                // the definition's taps are these fp32 values: -2.8e-9.  1/7 x 7 is 1
     }
     const float c1 = (0.01f * data_range) * (0.01f * data_range), c2 = (0.03f * data_range) * (0.03f * data_range);
     double* pre = (double*)((char*)workspace + p.pre);
@@ -384,8 +423,8 @@ int hrn_launch_shift_cssim(const float* srs, const float* hrs, const float* maps
     {
         // per map pixel and offset: three fields x two passes x T multiply-adds, and about 40 operations of the SSIM itself
         HrnProfScope prof("cssim_tile", maps_pix * p.nk * (12.0 * p.T + 40.0), 12.0 * pix, stream);
-        int rc = p.T == 7 ? launch_tile<7>(srs, hrs, maps, nbias, B, H, W, border, clip, p, tp, cov_norm, c1, c2, partial, stream)
-                          : launch_tile<11>(srs, hrs, maps, nbias, B, H, W, border, clip, p, tp, cov_norm, c1, c2, partial, stream);
+        int rc = p.T == 7 ? launch_tile<7>(srs, hrs, maps, nbias, B, H, W, border, clip, p, tp, cov_norm, c1, c2, tap_excess, partial, stream)
+                          : launch_tile<11>(srs, hrs, maps, nbias, B, H, W, border, clip, p, tp, cov_norm, c1, c2, tap_excess, partial, stream);
         if (rc) return rc;
     }
     {

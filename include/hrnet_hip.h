@@ -316,7 +316,8 @@ int hrn_shift_loss_backward(const float* srs, const float* hrs, const float* hr_
 
 /* The second score, cSSIM: structural similarity between the clear pixels of the target and the brightness-corrected prediction, searched
  * over the offsets and crops of hrn_shift_loss_train (the project's own definition; tests/cssim_ref.py restates it in fp64).
- * srs/hrs/hr_maps (B,H,W) f32, a map is 0 / non-zero; border 0..8; h, w, s (clamped to [0,1] when clip != 0, a NaN stays NaN) and, for
+ * srs/hrs/hr_maps (B,H,W) f32; a map is 0 / non-zero by `!= 0`: a fractional, negative or denormal value is a clear pixel of weight 1 and
+ * -0.0 is masked; a +inf in srs is 1 when clip != 0, and when clip == 0 it makes every score of its sample NaN (no k*); border 0..8; h, w, s (clamped to [0,1] when clip != 0, a NaN stays NaN) and, for
  * the offset k = u (2 border + 1) + v, g and m as above; n_k = sum m, bias_k = sum m (g - s) / n_k, or 0 when correct_bias == 0.  The
  * compared pair is X = m g and Y = m (s + bias_k): masked pixels are zero in both.  The window G is separable, sums to 1 and is applied
  * where it fits ("valid": the SSIM map is (h - T + 1) x (w - T + 1), no padding), so H and W must each be >= 2 border + T:

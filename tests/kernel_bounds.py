@@ -465,3 +465,23 @@ class Guarded:
     def guard_ok(self):
         r = self.raw.cpu()
         return bool((r[:self.front] == (SENT & 0xFF)).all()) and bool((r[self.front + self.nbytes:] == (SENT & 0xFF)).all())
+
+
+# ----------------------------------------------------------------------------------------------------------- the second score, cSSIM
+# tests/test_gpu_cssim_pin.py (GPU) and tests/test_cssim_pin_host.py (CPU).  A score of hrn_shift_cssim is held to an absolute bound for
+# data in [0, 1] with data_range = 1: CSSIM_BOUND is the project's cap, CSSIM_TOL_PIN the pinning pass's bound, made
+# the way C_F32 was: four times the largest |GPU - fp64 restatement| any case of the pinning pass measured on the MI355X, rounded up to one
+# significant digit, never above the cap: 4 x 9.73e-8 = 3.9e-7 -> 4e-7.  CSSIM_MEASURED: the largest per family, with its case.
+# CSSIM_MEASURED_UNCENTRED: the same cases on the tile kernel as it shipped (v = cov_norm (G X^2 - mu^2) on uncentred fields), in the same
+# session - 23 of the 40 conditioning cases, every clear instance case and every clear seam case beyond the cap - which is why the tile
+# kernel centres its fields per tile now.
+CSSIM_BOUND = 1e-5
+CSSIM_TOL_PIN = 4e-7
+CSSIM_MEASURED = {"conditioning": (4.41e-8, "cond-24x24-uniform-L0.05-c0.05-clear"),
+                  "instances": (9.73e-8, "test_all_eighteen_instances_launch: border 8, uniform, 25 x 27"),
+                  "seams": (2.32e-8, "seam-45x129-uniform-clear"),
+                  "runs": (1.44e-8, "runs-2050-uniform")}
+CSSIM_MEASURED_UNCENTRED = {"conditioning": (1.04e-4, "cond-24x24-gaussian-L0.9-c0.005-clear"),
+                            "instances": (6.78e-5, "inst-b5-uniform-clear"),
+                            "seams": (4.69e-5, "seam-45x129-uniform-clear"),
+                            "runs": (1.51e-7, "runs-2048-uniform")}
