@@ -18,7 +18,7 @@ constexpr int SC_WIN = SC_TILE + SC_SPAN + 5;   // window rows and columns: offs
 constexpr int SC_MEAN_CHUNK = HRN_MNCC_SCENE_MEAN_CHUNK, SC_MEAN_CHUNKS = HRN_MNCC_SCENE_MEAN_CHUNKS;
 
 static_assert(SC_TILE == 64, "a lane owns a column of the core");
-static_assert(SC_ITEMS * SC_RUN <= 32, "a thread adds at most 32 pixels in fp32, and rbits is one 32-bit word");
+static_assert(SC_ITEMS * SC_RUN <= 32, "rbits is one 32-bit word");
 static_assert(SC_ITEMS * SC_THREADS * SC_RUN == SC_TILE * SC_TILE, "the runs cover the core exactly");
 
 struct SceneShared {

@@ -58,24 +58,26 @@
 #pragma unroll
             for (int o = 0; o < 6; ++o) ky[o] = S.tap[0][i][o];
             int n = 0;
-            float st = 0.f, sr = 0.f, stt = 0.f, srr = 0.f, srt = 0.f;
+            double st = 0.0, sr = 0.0, stt = 0.0, srr = 0.0, srt = 0.0;
             if (jok && offy <= SC_SPAN) {
 #pragma unroll
                 for (int k = 0; k < SC_ITEMS; ++k) {
                     const int yl = (wave + k * SC_WAVES) * SC_RUN;
                     float t[SC_RUN];
                     const unsigned c = scene_column_run(S, ky, ny, nx, offy, offx, table, x, yl, ty0 + yl, gx, H, W, t) & (rbits >> (SC_RUN * k));
+                    n += __popc(c & ((1u << SC_RUN) - 1u));
 #pragma unroll
                     for (int p = 0; p < SC_RUN; ++p) {
                         const bool on = (c >> p) & 1u;
-                        const float tm = on ? t[p] : 0.f, rm = on ? r[k][p] : 0.f;
-                        n += on;
+                        float tf = on ? t[p] : 0.f, rf = on ? r[k][p] : 0.f;
+                        asm("" : "+v"(tf), "+v"(rf));    // the selects stay in fp32: one each, not two on the halves of a double
+                        const double tm = (double)tf, rm = (double)rf;
                         st += tm; sr += rm;
-                        stt = fmaf(tm, tm, stt); srr = fmaf(rm, rm, srr); srt = fmaf(rm, tm, srt);
+                        stt = fma(tm, tm, stt); srr = fma(rm, rm, srr); srt = fma(rm, tm, srt);
                     }
                 }
             }
-            double v[8] = {(double)n, (double)st, (double)sr, (double)stt, (double)srr, (double)srt, 0.0, 0.0};
+            double v[8] = {(double)n, st, sr, stt, srr, srt, 0.0, 0.0};
             WaveSums<8, 0>::run(v, lane);
             if (lane < 8) S.red[i][wave][wave_sums_index<8>(lane)] = v[0];
         }

@@ -10,8 +10,9 @@
 // the FRAME.  Window pixels outside the frame are staged as zeros with a set mask; no valid pixel reads them.
 //
 // A score's sums are taken on images centred by WHOLE-FRAME means (a pre-pass: fixed-order fp64 sums per chunk, the chunks added in
-// order, the quotient rounded to fp32), never per tile.  A thread adds its 16 pixels in fp32; the wave (WaveSums), the waves in order
-// and - in the finishing kernel of a level - the tiles in index order are added in fp64.  A workgroup writes its 6 P^2 sums to the
+// order, the quotient rounded to fp32), never per tile.  A thread adds its 16 pixels in fp64 - a tile need not have the frame's mean
+// ("Sums") - and the wave (WaveSums), the waves in order and - in the finishing kernel of a level - the tiles in
+// index order are added in fp64 too.  A workgroup writes its 6 P^2 sums to the
 // workspace; there is no atomic anywhere.  The finishing kernel forms the scores, takes the first maximum and writes the next centre to
 // device memory, where the next level's launch reads it: nothing returns to the host between levels.  hrn_mncc_grid_scene and a level of
 // hrn_mncc_search_scene are the same two kernels on the same partition, so their scores agree bit for bit.

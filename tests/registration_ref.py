@@ -151,11 +151,9 @@ PAD = 8                      # the frame is synthesised this much larger per sid
 LOWPASS_SIGMA = 0.12         # cycles / pixel
 
 
-def scene(H, W, shifts, seed):
-    """A reference frame and len(shifts) templates of it: -> (ref (H,W), ref_mask (H,W), views (V,H,W), view_masks (V,H,W)), float32.
-    White noise on a frame padded by PAD, a Gaussian low-pass in the FFT domain, the template at the sub-pixel offset (ty, tx) by a
-    Fourier phase ramp - so that S(template, (ty, tx)) is the reference - then the crop; ref = 0.3 + 0.1 z, template = 0.32 + 0.11
-    z_shifted + 0.002 N(0, 1); every mask has about one zero rectangle of half-sides 2..4 per 400 pixels."""
+def _parts(H, W, shifts, seed):
+    """What `scene` and `scene_stepped` are made of, drawn in one order: -> (z (H,W), z shifted per view, N(0, 1) per view, ref_mask,
+    view_masks), float64 but the float32 masks."""
     rng = np.random.default_rng(seed)
     Hp, Wp = H + 2 * PAD, W + 2 * PAD
     ky, kx = np.fft.fftfreq(Hp)[:, None], np.fft.fftfreq(Wp)[None, :]
@@ -174,11 +172,43 @@ def scene(H, W, shifts, seed):
             m[max(0, cy - hy):cy + hy + 1, max(0, cx - hx):cx + hx + 1] = 0.0
         return m
 
-    ref = (0.3 + 0.1 * crop(0.0, 0.0)).astype(np.float32)
+    z = crop(0.0, 0.0)
     ref_mask = mask()
-    views = np.stack([0.32 + 0.11 * crop(ty, tx) + 0.002 * rng.standard_normal((H, W)) for ty, tx in shifts]).astype(np.float32)
+    shifted, noise = [], []
+    for ty, tx in shifts:
+        shifted.append(crop(ty, tx))
+        noise.append(rng.standard_normal((H, W)))
     view_masks = np.stack([mask() for _ in shifts])
+    return z, shifted, noise, ref_mask, view_masks
+
+
+def scene(H, W, shifts, seed):
+    """A reference frame and len(shifts) templates of it: -> (ref (H,W), ref_mask (H,W), views (V,H,W), view_masks (V,H,W)), float32.
+    White noise on a frame padded by PAD, a Gaussian low-pass in the FFT domain, the template at the sub-pixel offset (ty, tx) by a
+    Fourier phase ramp - so that S(template, (ty, tx)) is the reference - then the crop; ref = 0.3 + 0.1 z, template = 0.32 + 0.11
+    z_shifted + 0.002 N(0, 1); every mask has about one zero rectangle of half-sides 2..4 per 400 pixels."""
+    z, shifted, noise, ref_mask, view_masks = _parts(H, W, shifts, seed)
+    ref = (0.3 + 0.1 * z).astype(np.float32)
+    views = np.stack([0.32 + 0.11 * zs + 0.002 * n for zs, n in zip(shifted, noise)]).astype(np.float32)
     return ref, ref_mask, views, view_masks
+
+
+STEP_BAND = 6                # scene_stepped's band: this many pixels on either side of the step
+
+
+def scene_stepped(H, W, shifts, seed, contrast, step, split, axis):
+    """`scene`'s z, shifts, noise and speckle masks on a level with a step: -> (ref, ref_mask, views, view_masks, band), float32.
+    ref = 0.2 + contrast z + step [p >= split], template = 0.2 + 1.1 contrast z_shifted + 0.002 (contrast / 0.1) N(0, 1) + step
+    [p >= split], p the column (axis = 1) or the row (axis = 0): the level of either side is far from the frame's mean, the contrast may
+    be small against both.  band (H,W) is zero on p = split - STEP_BAND .. split + STEP_BAND - 1 and one elsewhere: under it no pixel's
+    6 x 6 footprint crosses the step for shifts within +-2 pixels."""
+    z, shifted, noise, ref_mask, view_masks = _parts(H, W, shifts, seed)
+    p = np.arange(W)[None, :] if axis == 1 else np.arange(H)[:, None]
+    level = 0.2 + step * np.broadcast_to(p >= split, (H, W))
+    ref = (level + contrast * z).astype(np.float32)
+    views = np.stack([level + 1.1 * contrast * zs + 0.002 * (contrast / 0.1) * n for zs, n in zip(shifted, noise)]).astype(np.float32)
+    band = np.broadcast_to((p < split - STEP_BAND) | (p >= split + STEP_BAND), (H, W)).astype(np.float32)
+    return ref, ref_mask, views, view_masks, band
 
 
 def random_shifts(V, limit, seed):
