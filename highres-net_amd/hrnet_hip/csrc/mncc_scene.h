@@ -1,9 +1,9 @@
 // What the kernels of the tiled masked-NCC registration share (DESIGN.md sections 7g and 7i): registration_scene.hip, one shift per view,
-// and registration_local.hip, a shift per block of tiles.  The tile, the LDS window and its staging, and the two passes of the sampler are
-// written once here, and so is the host's plan of the tiles and the workspace; the body of a level kernel is mncc_scene_level.h.
+// and registration_local.hip, a shift per block of tiles.  The tile, the LDS window and its staging, the two passes of the sampler, a
+// grid level of a tile (scene_level) and the finish of a level over a rectangle of tiles (finish_tiles) are written once here, and so is
+// the host's plan of the tiles and the workspace.
 #pragma once
 #include "kernels.h"
-#include "wave_sums.h"
 #include "mncc_common.h"            // also turns fp contraction off
 
 namespace {
@@ -11,15 +11,14 @@ namespace {
 constexpr int SC_PMAX = HRN_MNCC_MAX_POINTS;
 constexpr int SC_TILE = HRN_MNCC_SCENE_TILE;    // the core: 64 columns = one lane per column of a wave
 constexpr int SC_THREADS = 256, SC_WAVES = SC_THREADS / 64;
-constexpr int SC_RUN = 8;                       // rows of one column that a thread takes at a time
-constexpr int SC_ITEMS = (SC_TILE / SC_RUN) * SC_TILE / SC_THREADS;     // 2 runs a thread: 16 pixels
+constexpr int SC_ITEMS = (SC_TILE / RG_RUN) * SC_TILE / SC_THREADS;     // 2 runs a thread: 16 pixels
 constexpr int SC_SPAN = 9;                      // the whole-pixel offsets of one level, less the smallest: 0..SC_SPAN
 constexpr int SC_WIN = SC_TILE + SC_SPAN + 5;   // window rows and columns: offset - 2 .. offset + 3 around every core pixel
 constexpr int SC_MEAN_CHUNK = HRN_MNCC_SCENE_MEAN_CHUNK, SC_MEAN_CHUNKS = HRN_MNCC_SCENE_MEAN_CHUNKS;
 
 static_assert(SC_TILE == 64, "a lane owns a column of the core");
-static_assert(SC_ITEMS * SC_RUN <= 32, "rbits is one 32-bit word");
-static_assert(SC_ITEMS * SC_THREADS * SC_RUN == SC_TILE * SC_TILE, "the runs cover the core exactly");
+static_assert(SC_ITEMS * RG_RUN <= 32, "rbits is one 32-bit word");
+static_assert(SC_ITEMS * SC_THREADS * RG_RUN == SC_TILE * SC_TILE, "the runs cover the core exactly");
 
 struct SceneShared {
     float T[SC_WIN * SC_WIN];                   // the window of the view, minus the view's mean (the search) or as it is (the resampler)
@@ -90,29 +89,21 @@ __device__ void scene_row_pass(SceneShared& S, const float* tap, int off, int ro
     }
 }
 
-// One run of one column for one (dy, dx): the six taps down SC_RUN + 5 rows of A, and which of the run's pixels are valid - inside the
+// One run of one column for one (dy, dx): the six taps down RG_RUN + 5 rows of A, and which of the run's pixels are valid - inside the
 // frame, footprint inside the frame, and the bilinear mask sample above 0.5.  yl: the run's first row in the core; (gy, gx): the same
 // pixel in the frame; offy / offx: n_y / n_x less the level's smallest.  t[p] is defined only where bit p of the result is set.
 __device__ __forceinline__ unsigned scene_column_run(const SceneShared& S, const float* ky, int ny, int nx, int offy, int offx,
                                                      unsigned table, int x, int yl, int gy, int gx, int H, int W, float* t) {
-    float a[SC_RUN + 5];
+    float a[RG_RUN + 5];
 #pragma unroll
-    for (int m = 0; m < SC_RUN + 5; ++m) a[m] = S.A[(yl + offy + m) * SC_TILE + x];           // the last row: 56 + 9 + 12 < SC_WIN
+    for (int m = 0; m < RG_RUN + 5; ++m) a[m] = S.A[(yl + offy + m) * SC_TILE + x];           // the last row: 56 + 9 + 12 < SC_WIN
+    column_taps(ky, a, t);
     const bool xin = gx < W && gx + nx - 2 >= 0 && gx + nx + 3 <= W - 1;
     const unsigned char* pat = S.pat + (yl + offy + 2) * SC_WIN + x + offx + 2;               // the window's pixel (gy + n_y, gx + n_x)
-    unsigned valid = 0;
+    unsigned q[RG_RUN];
 #pragma unroll
-    for (int p = 0; p < SC_RUN; ++p) {
-        float s = ky[0] * a[p];
-#pragma unroll
-        for (int o = 1; o < 6; ++o) s = fmaf(ky[o], a[p + o], s);
-        t[p] = s;
-        const int y = gy + p;
-        const bool yin = y < H && y + ny - 2 >= 0 && y + ny + 3 <= H - 1;
-        const unsigned q = pat[p * SC_WIN];
-        valid |= (unsigned)(xin && yin && ((table >> q) & 1u)) << p;
-    }
-    return valid;
+    for (int p = 0; p < RG_RUN; ++p) q[p] = pat[p * SC_WIN];
+    return run_valid(xin, gy, ny, H, table, q);
 }
 
 __device__ __forceinline__ int min_whole(const int* whole, int P) {
@@ -121,14 +112,131 @@ __device__ __forceinline__ int min_whole(const int* whole, int P) {
     return m;
 }
 
-// ----------------------------------------------------------------------------- the host side of a level
-double level_ratio(int P) {                      // as registration.hip: 1 / (P - 2), at least 0.25, and 0.9 where that is not below 1
-    const double s = 1.0 / (double)(P - 2);
-    return s >= 1.0 ? 0.9 : (s < 0.25 ? 0.25 : s);
+// ----------------------------------------------------------------------------- one grid level of a tile
+// The body of a level kernel: workgroup blockIdx.x owns tile `tile` of view `view` and writes its six sums at the P x P grid points of
+// `width` around the centre pair number centre(view, tile) of `centres` ((0, 0) where `centres` is null) to
+// sums[(blockIdx.x * P^2 + i P + j) * 6 + q].  The parameters are scene_level_kernel's, qualifiers included.
+template <class Centre>
+__device__ __forceinline__ void scene_level(const float* __restrict__ ref, const float* __restrict__ ref_mask, const float* __restrict__ views,
+                                            const float* __restrict__ view_masks, const float* __restrict__ centres,
+                                            const double* __restrict__ means, unsigned chunks, unsigned BV, int V, int H, int W, int P,
+                                            double width, unsigned tiles_x, unsigned tiles, double* __restrict__ sums, Centre centre) {
+    __shared__ SceneShared S;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t view = blockIdx.x / tiles, b = view / V, hw = (size_t)H * W;
+    const unsigned tile = blockIdx.x - (unsigned)view * tiles;
+    const int ty0 = (int)(tile / tiles_x) * SC_TILE, tx0 = (int)(tile % tiles_x) * SC_TILE;
+
+    if (tid < 2 * P) {
+        const int axis = tid / P, i = tid - axis * P;
+        const double c = centres ? (double)centres[2 * centre(view, tile) + axis] : 0.0;
+        split_and_taps(grid_coord(c, width, i, P), &S.whole[axis][i], &S.frac[axis][i], S.tap[axis][i]);
+    }
+    if (tid == 64) S.mean[0] = plane_mean(means, view, chunks);
+    if (tid == 128) S.mean[1] = plane_mean(means, (size_t)BV + b, chunks);
+    __syncthreads();
+    if (tid < P * P) S.table[tid] = mask_table(S.frac[0][tid / P], S.frac[1][tid % P]);
+    const int ny0 = min_whole(S.whole[0], P), nx0 = min_whole(S.whole[1], P);
+    stage_window<SC_WIN, SC_WIN>(views + view * hw, view_masks ? view_masks + view * hw : nullptr, S, ty0 + ny0 - 2, tx0 + nx0 - 2, H, W,
+                                 S.mean[0], tid);
+
+    // this thread's pixels of the reference, centred on the reference's mean under its own mask and zero where that mask is set
+    float r[SC_ITEMS][RG_RUN];
+    unsigned rbits = 0;
+    const int x = lane, gx = tx0 + x;
+    {
+        const float* rp = ref + b * hw;
+        const float* rm = ref_mask ? ref_mask + b * hw : nullptr;
+        const float mean = S.mean[1];
+#pragma unroll
+        for (int k = 0; k < SC_ITEMS; ++k)
+#pragma unroll
+            for (int p = 0; p < RG_RUN; ++p) {
+                const int gy = ty0 + (wave + k * SC_WAVES) * RG_RUN + p;
+                const bool in = gy < H && gx < W;
+                const size_t g = in ? (size_t)gy * W + gx : 0;
+                const bool m = in && (rm ? rm[g] != 0.f : true);
+                r[k][p] = m ? rp[g] - mean : 0.f;
+                rbits |= (unsigned)m << (RG_RUN * k + p);
+            }
+    }
+
+#pragma unroll 1
+    for (int j = 0; j < P; ++j) {
+        const int nx = S.whole[1][j], offx = nx - nx0;
+        const bool jok = offx <= SC_SPAN;
+        if (jok) scene_row_pass(S, S.tap[1][j], offx, SC_WIN, tid);
+        __syncthreads();
+#pragma unroll 1
+        for (int i = 0; i < P; ++i) {
+            const int ny = S.whole[0][i], offy = ny - ny0;
+            const unsigned table = S.table[i * P + j];
+            float ky[6];
+#pragma unroll
+            for (int o = 0; o < 6; ++o) ky[o] = S.tap[0][i][o];
+            PointSums sum;
+            if (jok && offy <= SC_SPAN) {
+#pragma unroll
+                for (int k = 0; k < SC_ITEMS; ++k) {
+                    const int yl = (wave + k * SC_WAVES) * RG_RUN;
+                    float t[RG_RUN];
+                    const unsigned c = scene_column_run(S, ky, ny, nx, offy, offx, table, x, yl, ty0 + yl, gx, H, W, t) & (rbits >> (RG_RUN * k));
+                    sum.add(c, t, r[k]);
+                }
+            }
+            sum.to_wave(S.red[i][wave], lane);
+        }
+        __syncthreads();                         // A and S.red are free again after this
+        add_waves<SC_WAVES>(S.red, S.tot, P, j, tid);
+    }
+    __syncthreads();
+    double* out = sums + (size_t)blockIdx.x * (P * P * RG_NSUM);
+    const double* tot = &S.tot[0][0];
+    for (int i = tid; i < P * P * RG_NSUM; i += SC_THREADS) out[i] = tot[i];
 }
 
-// the counted arithmetic of one level, per pixel, as registration.hip counts it
-double level_flops(int P) { return P * 12.0 + (double)P * P * 32.0; }
+// ----------------------------------------------------------------------------- the finish of a level
+constexpr int SC_FINISH_THREADS = 128;
+static_assert(SC_FINISH_THREADS >= SC_PMAX * SC_PMAX, "a thread per grid point");
+
+struct FinishShared {
+    float score[SC_PMAX * SC_PMAX];
+    double count[SC_PMAX * SC_PMAX];            // n, the first of the six sums
+    float coord[2][SC_PMAX];
+};
+
+// The P x P grid of `width` around (cy, cx) over the tiles [ty0, ty1) x [tx0, tx1) of a view, tiles_x a row, whose sums begin at
+// `sums`: the six sums of the tiles added in row-major order per grid point, then F.score and F.count.  With `search`, thread 0 then
+// takes the first maximum: (cy, cx) becomes its point, its score is returned, centre_out = the point and trace = (dy, dx, score)
+// (each may be null).  All SC_FINISH_THREADS threads call it; it holds one barrier, after F is written.
+__device__ __forceinline__ float finish_tiles(FinishShared& F, const double* __restrict__ sums, unsigned tiles_x, unsigned ty0, unsigned ty1,
+                                              unsigned tx0, unsigned tx1, int P, double width, float& cy, float& cx, bool search,
+                                              float* centre_out, float* trace, int tid) {
+    const int pp = P * P;
+    if (tid < 2 * P) {
+        const int axis = tid / P, i = tid - axis * P;
+        F.coord[axis][i] = grid_coord((double)(axis ? cx : cy), width, i, P);
+    }
+    if (tid < pp) {
+        double s[RG_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (unsigned ty = ty0; ty < ty1; ++ty)
+            for (unsigned tx = tx0; tx < tx1; ++tx) {
+                const double* in = sums + (((size_t)ty * tiles_x + tx) * pp + tid) * RG_NSUM;
+#pragma unroll
+                for (int q = 0; q < RG_NSUM; ++q) s[q] += in[q];
+            }
+        F.score[tid] = mncc_score(s);
+        F.count[tid] = s[0];
+    }
+    __syncthreads();
+    float best = -INFINITY;
+    if (tid == 0 && search) {
+        best = mncc_first_maximum(F.score, F.coord[0], F.coord[1], P, cy, cx);
+        if (centre_out) { centre_out[0] = cy; centre_out[1] = cx; }
+        if (trace) { trace[0] = cy; trace[1] = cx; trace[2] = best; }
+    }
+    return best;
+}
 
 // ----------------------------------------------------------------------------- the workspace of a tiled search
 // the tiles of a frame, the chunks of its mean, and the three parts of the workspace in their order: the chunks' {sum, count} of every

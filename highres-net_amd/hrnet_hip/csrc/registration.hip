@@ -18,14 +18,13 @@
 // score of contrast 0.01 up to 2e-5 ("Sums").  No atomics: the result is bit-reproducible, and
 // hrn_mncc_grid and a level of hrn_mncc_search are the same device function, so their scores agree bit for bit.
 #include "kernels.h"
-#include "wave_sums.h"
-#include "mncc_common.h"            // what the tiled path (registration_scene.hip) shares; it also turns fp contraction off
+#include "mncc_common.h"            // what the tiled paths share with this one, a thread's sums and the end of a level among it; it also
+                                    // turns fp contraction off
 
 namespace {
 
 constexpr int RG_MAX = HRN_MNCC_MAX_SIDE, RG_PMAX = HRN_MNCC_MAX_POINTS;
 constexpr int RG_THREADS = 512, RG_WAVES = RG_THREADS / 64;
-constexpr int RG_RUN = 8;                       // rows of one column that a thread takes at a time
 constexpr int RG_ITEMS = (RG_MAX / RG_RUN) * RG_MAX / RG_THREADS;   // such runs per thread at 128 x 128
 
 struct RegShared {
@@ -139,21 +138,13 @@ __device__ __forceinline__ unsigned column_run(const float* A, const unsigned ch
     float a[RG_RUN + 5];
 #pragma unroll
     for (int m = 0; m < RG_RUN + 5; ++m) a[m] = A[clampi(y0 + ny - 2 + m, 0, H - 1) * W + x];
+    column_taps(ky, a, t);
     const bool xin = x + nx - 2 >= 0 && x + nx + 3 <= W - 1;
     const int xp = clampi(x + nx, 0, W - 1);
-    unsigned valid = 0;
+    unsigned q[RG_RUN];
 #pragma unroll
-    for (int p = 0; p < RG_RUN; ++p) {
-        float s = ky[0] * a[p];
-#pragma unroll
-        for (int o = 1; o < 6; ++o) s = fmaf(ky[o], a[p + o], s);
-        t[p] = s;
-        const int y = y0 + p;
-        const bool yin = y < H && y + ny - 2 >= 0 && y + ny + 3 <= H - 1;
-        const unsigned q = pat[clampi(y + ny, 0, H - 1) * W + xp];
-        valid |= (unsigned)(xin && yin && ((table >> q) & 1u)) << p;
-    }
-    return valid;
+    for (int p = 0; p < RG_RUN; ++p) q[p] = pat[clampi(y0 + p + ny, 0, H - 1) * W + xp];
+    return run_valid(xin, y0, ny, H, table, q);
 }
 
 // One grid level: S.score[i P + j] = the score at (dy_i, dx_j) of the P x P grid of `width` around (cy, cx).  Ends with a barrier.
@@ -181,43 +172,21 @@ __device__ void mncc_level(const float* T, float* A, const unsigned char* pat, R
             float ky[6];
 #pragma unroll
             for (int o = 0; o < 6; ++o) ky[o] = S.tap[0][i][o];
-            int n = 0;
-            double st = 0.0, sr = 0.0, stt = 0.0, srr = 0.0, srt = 0.0;
+            PointSums sum;
 #pragma unroll
             for (int k = 0; k < RG_ITEMS; ++k) {
                 if (th.y0[k] < 0) continue;
                 float t[RG_RUN];
                 const unsigned c = column_run(A, pat, ky, ny, nx, table, th.x[k], th.y0[k], H, W, t) & (th.rbits >> (RG_RUN * k));
-                n += __popc(c & ((1u << RG_RUN) - 1u));
-#pragma unroll
-                for (int p = 0; p < RG_RUN; ++p) {
-                    const bool on = (c >> p) & 1u;
-                    float tf = on ? t[p] : 0.f, rf = on ? th.r[k][p] : 0.f;
-                    asm("" : "+v"(tf), "+v"(rf));    // the selects stay in fp32: one each, not two on the halves of a double
-                    const double tm = (double)tf, rm = (double)rf;
-                    st += tm; sr += rm;
-                    stt = fma(tm, tm, stt); srr = fma(rm, rm, srr); srt = fma(rm, tm, srt);
-                }
+                sum.add(c, t, th.r[k]);
             }
-            double v[8] = {(double)n, st, sr, stt, srr, srt, 0.0, 0.0};
-            WaveSums<8, 0>::run(v, lane);
-            if (lane < 8) S.red[i][wave][wave_sums_index<8>(lane)] = v[0];
+            sum.to_wave(S.red[i][wave], lane);
         }
         __syncthreads();                         // A and S.red are free again after this
-        if (tid < P * RG_NSUM) {
-            const int i = tid / RG_NSUM, q = tid - i * RG_NSUM;
-            double s = 0.0;
-            for (int w = 0; w < RG_WAVES; ++w) s += S.red[i][w][q];
-            S.tot[i * P + j][q] = s;
-        }
+        add_waves<RG_WAVES>(S.red, S.tot, P, j, tid);
     }
     __syncthreads();
-    if (tid < P * P) {
-        const double* s = S.tot[tid];
-        float score;
-        MNCC_SCORE(s, score);
-        S.score[tid] = score;
-    }
+    if (tid < P * P) S.score[tid] = mncc_score(S.tot[tid]);
     __syncthreads();
 }
 
@@ -291,8 +260,7 @@ __global__ __launch_bounds__(RG_THREADS) void mncc_kernel(const float* __restric
     for (int k = 0; k < levels; ++k) {
         mncc_level(l.T, l.A, l.pat, S, th, H, W, P, cy, cx, width, tid);
         if (tid == 0) {                          // the first maximum in row-major order; without a finite score the centre stays
-            float best;
-            MNCC_FIRST_MAXIMUM(S.score, S.coord[0], S.coord[1], P, best, cy, cx);
+            const float best = mncc_first_maximum(S.score, S.coord[0], S.coord[1], P, cy, cx);
             S.best[0] = cy; S.best[1] = cx; S.best[2] = best;
             if (trace) {
                 float* tr = trace + (view * levels + k) * 3;
@@ -344,14 +312,6 @@ __global__ __launch_bounds__(RG_THREADS) void mncc_apply_kernel(const float* __r
         }
     }
 }
-
-double level_ratio(int P) {                      // the reference fork's rule: 1 / (P - 2), at least 0.25, and 0.9 where that is not below 1
-    const double s = 1.0 / (double)(P - 2);
-    return s >= 1.0 ? 0.9 : (s < 0.25 ? 0.25 : s);
-}
-
-// the counted arithmetic of one level, per pixel: the pass along rows P 6 2, the pass along columns plus mask plus sums P^2 (6 2 + 20)
-double level_flops(int P) { return P * 12.0 + (double)P * P * 32.0; }
 
 }  // namespace
 

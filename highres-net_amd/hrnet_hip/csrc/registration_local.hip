@@ -3,10 +3,10 @@
 //
 // An axis of length L has n = max(1, (L + block / 2) / block) blocks of `block` pixels, a multiple of 64; the last block runs to L, so a
 // remainder below half a block joins its neighbour and every block is a union of whole 64-pixel tiles.  The score of a block at a shift
-// is section 7f's score with the reference mask set to zero outside the block: the level kernel is scene_level_kernel's text with the
-// centre of the grid read per (view, block of this tile), and the finishing kernel adds the sums of a block's tiles, in tile-index
-// order, where scene_finish_kernel adds all tiles of a view.  Both images stay centred on their WHOLE-FRAME means.  A search is 1 + 2
-// levels launches; `init` and every centre are read from device memory, and nothing returns to the host.  No atomics: bit-reproducible.
+// is section 7f's score with the reference mask set to zero outside the block: the level kernel is scene_level_kernel's function
+// (mncc_scene.h: scene_level) with the centre of the grid read per (view, block of this tile), and the finishing kernel calls
+// scene_finish_kernel's (finish_tiles) on the block's rectangle of tiles instead of all tiles of a view.  Both images stay centred
+// on their WHOLE-FRAME means.  A search is 1 + 2 levels launches; `init` and every centre are read from device memory, and nothing returns to the host.  No atomics: bit-reproducible.
 //
 // The field at a pixel is bilinear between the blocks' centres (the nodes) and constant beyond the outer ones, in fp64 in a fixed
 // order, rounded to fp32.  The resampler splits every pixel's own shift into whole pixels, fraction and taps and reads the pixel's 6 x 6
@@ -31,10 +31,11 @@ __global__ __launch_bounds__(SC_THREADS) void local_level_kernel(const float* __
                                                                  unsigned chunks, unsigned BV, int V, int H, int W, int P, double width,
                                                                  unsigned tiles_x, unsigned tiles, double* __restrict__ sums, int per_block,
                                                                  unsigned bt, unsigned nby, unsigned nbx) {
-#define SCENE_LEVEL_CENTRE \
-    (per_block ? view * nby * nbx + block_of_tile(tile / tiles_x, bt, nby) * nbx + block_of_tile(tile % tiles_x, bt, nbx) : view)
-#include "mncc_scene_level.h"
-#undef SCENE_LEVEL_CENTRE
+    scene_level(ref, ref_mask, views, view_masks, centres, means, chunks, BV, V, H, W, P, width, tiles_x, tiles, sums,
+                [=](size_t view, unsigned tile) {
+                    return per_block ? view * nby * nbx + block_of_tile(tile / tiles_x, bt, nby) * nbx + block_of_tile(tile % tiles_x, bt, nbx)
+                                     : view;
+                });
 }
 
 // ----------------------------------------------------------------------------- one grid level: the finish
@@ -42,65 +43,35 @@ __global__ __launch_bounds__(SC_THREADS) void local_level_kernel(const float* __
 // = the best point and trace_k[(view, block) * trace_stride] = (dy, dx, score).  centres_in is read per block (per_block) or per view, and
 // is (0, 0) when null; centres_out may be centres_in.  After the last level (`field` not null): n is the count of common valid pixels
 // at the chosen point, the block is ok when the score is finite and n >= min_valid * the block's area (fp64), field[view, block] = the
-// best point when ok and init[view] ((0, 0) when null) otherwise, ok[view, block] = 1 / 0 (may be null).  grid (B V nby nbx), 128 threads
-constexpr int LC_FINISH_THREADS = 128;
-static_assert(LC_FINISH_THREADS >= SC_PMAX * SC_PMAX, "a thread per grid point");
-
-__global__ __launch_bounds__(LC_FINISH_THREADS) void local_finish_kernel(const double* __restrict__ sums, const float* centres_in,
+// best point when ok and init[view] ((0, 0) when null) otherwise, ok[view, block] = 1 / 0 (may be null).  grid (B V nby nbx),
+// SC_FINISH_THREADS threads
+__global__ __launch_bounds__(SC_FINISH_THREADS) void local_finish_kernel(const double* __restrict__ sums, const float* centres_in,
                                                                          int per_block, const float* __restrict__ init, int P, double width,
                                                                          unsigned tiles_x, unsigned tiles_y, unsigned bt, unsigned nby,
                                                                          unsigned nbx, int H, int W, int block, float* centres_out,
                                                                          float* __restrict__ trace_k, int trace_stride,
                                                                          float* __restrict__ field, float* __restrict__ ok, double min_valid) {
-    __shared__ float score[SC_PMAX * SC_PMAX];
-    __shared__ double count[SC_PMAX * SC_PMAX];
-    __shared__ float coord[2][SC_PMAX];
+    __shared__ FinishShared F;
     const int tid = threadIdx.x, pp = P * P;
     const unsigned blocks = nby * nbx;
     const size_t vb = blockIdx.x, view = vb / blocks;
     const unsigned blk = (unsigned)(vb - view * blocks), by = blk / nbx, bx = blk - by * nbx;
     const size_t c = per_block ? vb : view;
     float cy = centres_in ? centres_in[2 * c] : 0.f, cx = centres_in ? centres_in[2 * c + 1] : 0.f;
-    if (tid < 2 * P) {
-        const int axis = tid / P, i = tid - axis * P;
-        coord[axis][i] = grid_coord((double)(axis ? cx : cy), width, i, P);
-    }
-    if (tid < pp) {
-        double s[RG_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        const unsigned ty1 = by == nby - 1 ? tiles_y : (by + 1) * bt, tx1 = bx == nbx - 1 ? tiles_x : (bx + 1) * bt;
-        for (unsigned ty = by * bt; ty < ty1; ++ty)
-            for (unsigned tx = bx * bt; tx < tx1; ++tx) {
-                const double* in = sums + (((view * tiles_y + ty) * tiles_x + tx) * pp + tid) * RG_NSUM;
-#pragma unroll
-                for (int q = 0; q < RG_NSUM; ++q) s[q] += in[q];
-            }
-        float sc;
-        MNCC_SCORE(s, sc);
-        score[tid] = sc;
-        count[tid] = s[0];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float best;
-        MNCC_FIRST_MAXIMUM(score, coord[0], coord[1], P, best, cy, cx);
-        centres_out[2 * vb] = cy;
-        centres_out[2 * vb + 1] = cx;
-        if (trace_k) {
-            float* tr = trace_k + vb * trace_stride;
-            tr[0] = cy; tr[1] = cx; tr[2] = best;
+    const unsigned ty1 = by == nby - 1 ? tiles_y : (by + 1) * bt, tx1 = bx == nbx - 1 ? tiles_x : (bx + 1) * bt;
+    const float best = finish_tiles(F, sums + view * tiles_y * tiles_x * pp * RG_NSUM, tiles_x, by * bt, ty1, bx * bt, tx1, P, width, cy, cx,
+                                    true, centres_out + 2 * vb, trace_k ? trace_k + vb * trace_stride : nullptr, tid);
+    if (tid == 0 && field) {
+        bool good = false;
+        if (best > -INFINITY) {
+            int at = 0;
+            while (at < pp - 1 && !(F.score[at] == best)) ++at;             // the first maximum is the first point with its score
+            const int r0 = (int)by * block, r1 = by == nby - 1 ? H : r0 + block, c0 = (int)bx * block, c1 = bx == nbx - 1 ? W : c0 + block;
+            good = F.count[at] >= min_valid * ((double)(r1 - r0) * (double)(c1 - c0));
         }
-        if (field) {
-            bool good = false;
-            if (best > -INFINITY) {
-                int at = 0;
-                while (at < pp - 1 && !(score[at] == best)) ++at;           // the first maximum is the first point with its score
-                const int r0 = (int)by * block, r1 = by == nby - 1 ? H : r0 + block, c0 = (int)bx * block, c1 = bx == nbx - 1 ? W : c0 + block;
-                good = count[at] >= min_valid * ((double)(r1 - r0) * (double)(c1 - c0));
-            }
-            field[2 * vb] = good ? cy : (init ? init[2 * view] : 0.f);
-            field[2 * vb + 1] = good ? cx : (init ? init[2 * view + 1] : 0.f);
-            if (ok) ok[vb] = good ? 1.f : 0.f;
-        }
+        field[2 * vb] = good ? cy : (init ? init[2 * view] : 0.f);
+        field[2 * vb + 1] = good ? cx : (init ? init[2 * view + 1] : 0.f);
+        if (ok) ok[vb] = good ? 1.f : 0.f;
     }
 }
 
@@ -124,7 +95,7 @@ __device__ __forceinline__ void field_axis(int p, int L, int block, int n, int* 
 
 // ----------------------------------------------------------------------------- the resampler by a field
 // out = S(view, the field at the pixel), out_valid = V(mask, the same) pixel by pixel; field (B V, nby, nbx, 2).  A thread takes
-// scene_apply_kernel's pixels: column `lane` of its tile, two runs of SC_RUN rows.  grid (B V tiles)
+// scene_apply_kernel's pixels: column `lane` of its tile, two runs of RG_RUN rows.  grid (B V tiles)
 __global__ __launch_bounds__(SC_THREADS) void field_apply_kernel(const float* __restrict__ views, const float* __restrict__ view_masks,
                                                                  const float* __restrict__ field, int H, int W, int block, int nby, int nbx,
                                                                  unsigned tiles_x, unsigned tiles, float* __restrict__ out,
@@ -145,8 +116,8 @@ __global__ __launch_bounds__(SC_THREADS) void field_apply_kernel(const float* __
 #pragma unroll 1
     for (int k = 0; k < SC_ITEMS; ++k) {
 #pragma unroll 1
-        for (int p = 0; p < SC_RUN; ++p) {
-            const int gy = ty0 + (wave + k * SC_WAVES) * SC_RUN + p;
+        for (int p = 0; p < RG_RUN; ++p) {
+            const int gy = ty0 + (wave + k * SC_WAVES) * RG_RUN + p;
             if (gy >= H) break;
             int ky;
             double ty;
@@ -172,8 +143,7 @@ __global__ __launch_bounds__(SC_THREADS) void field_apply_kernel(const float* __
                 if (msk) {
                     q0 = msk[at] != 0.f; q1 = msk[at + 1] != 0.f; q2 = msk[at + W] != 0.f; q3 = msk[at + W + 1] != 0.f;
                 }
-                const double top = (1.0 - fx) * q0 + fx * q1, bot = (1.0 - fx) * q2 + fx * q3;      // mask_table's expression
-                on = (1.0 - fy) * top + fy * bot > 0.5;
+                on = mask_sample(fy, fx, q0, q1, q2, q3);
             }
             if (on) {
                 float a[6];
@@ -244,7 +214,7 @@ int hrn_launch_mncc_search_local(const float* ref, const float* ref_mask, const 
         hipLaunchKernelGGL(local_level_kernel, dim3(bv * p.tiles), dim3(SC_THREADS), 0, stream, ref, ref_mask, views, view_masks, from,
                            (const double*)w.means, p.chunks, bv, V, H, W, P, width, p.tiles_x, p.tiles, w.sums, k ? 1 : 0, p.bt, p.nby, p.nbx);
         HRN_LAUNCH_CHECK();
-        hipLaunchKernelGGL(local_finish_kernel, dim3(bv * p.nby * p.nbx), dim3(LC_FINISH_THREADS), 0, stream, (const double*)w.sums, from,
+        hipLaunchKernelGGL(local_finish_kernel, dim3(bv * p.nby * p.nbx), dim3(SC_FINISH_THREADS), 0, stream, (const double*)w.sums, from,
                            k ? 1 : 0, init, P, width, p.tiles_x, p.tiles_y, p.bt, p.nby, p.nbx, H, W, block, w.centres,
                            trace ? trace + 3 * k : (float*)nullptr, 3 * levels, last ? field : (float*)nullptr, last ? ok : (float*)nullptr,
                            (double)min_valid);

@@ -21,7 +21,7 @@
 //
 // Resources (gfx950, -Rpass-analysis=kernel-resource-usage): see DESIGN.md section 7j.
 #include "kernels.h"
-#include "mncc_common.h"            // turns fp contraction off
+#include "mncc_common.h"            // for turning fp contraction off; none of its functions is used here
 
 namespace {
 

@@ -60,53 +60,27 @@ __global__ __launch_bounds__(SC_THREADS) void scene_level_kernel(const float* __
                                                                  const float* __restrict__ centres, const double* __restrict__ means,
                                                                  unsigned chunks, unsigned BV, int V, int H, int W, int P, double width,
                                                                  unsigned tiles_x, unsigned tiles, double* __restrict__ sums) {
-#define SCENE_LEVEL_CENTRE view
-#include "mncc_scene_level.h"
-#undef SCENE_LEVEL_CENTRE
+    scene_level(ref, ref_mask, views, view_masks, centres, means, chunks, BV, V, H, W, P, width, tiles_x, tiles, sums,
+                [](size_t view, unsigned) { return view; });
 }
 
 // ----------------------------------------------------------------------------- one grid level: the finish
 // Per view: the tiles' sums added in index order, the P^2 scores, and - for the search - the first maximum: centres_out[view] = the
 // best point, trace_k[view * trace_stride] = (dy, dx, score), shifts[view] = the best point (each may be null).  centres_in null: (0, 0).
-// centres_out may be centres_in.  grid (B V), 128 threads
-constexpr int SC_FINISH_THREADS = 128;
-static_assert(SC_FINISH_THREADS >= SC_PMAX * SC_PMAX, "a thread per grid point");
-
+// centres_out may be centres_in.  grid (B V), SC_FINISH_THREADS threads
 __global__ __launch_bounds__(SC_FINISH_THREADS) void scene_finish_kernel(const double* __restrict__ sums, const float* centres_in, int P,
                                                                          double width, unsigned tiles, float* __restrict__ scores,
                                                                          float* centres_out, float* __restrict__ trace_k,
                                                                          int trace_stride, float* __restrict__ shifts) {
-    __shared__ float score[SC_PMAX * SC_PMAX];
-    __shared__ float coord[2][SC_PMAX];
+    __shared__ FinishShared F;
     const int tid = threadIdx.x, pp = P * P;
     const size_t view = blockIdx.x;
     float cy = centres_in ? centres_in[2 * view] : 0.f, cx = centres_in ? centres_in[2 * view + 1] : 0.f;
-    if (tid < 2 * P) {
-        const int axis = tid / P, i = tid - axis * P;
-        coord[axis][i] = grid_coord((double)(axis ? cx : cy), width, i, P);
-    }
-    if (tid < pp) {
-        double s[RG_NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        const double* in = sums + (view * tiles * pp + tid) * RG_NSUM;
-        for (unsigned t = 0; t < tiles; ++t, in += (size_t)pp * RG_NSUM)
-#pragma unroll
-            for (int q = 0; q < RG_NSUM; ++q) s[q] += in[q];
-        float sc;
-        MNCC_SCORE(s, sc);
-        score[tid] = sc;
-        if (scores) scores[view * pp + tid] = sc;
-    }
-    __syncthreads();
-    if (tid == 0 && (centres_out || trace_k || shifts)) {
-        float best;
-        MNCC_FIRST_MAXIMUM(score, coord[0], coord[1], P, best, cy, cx);
-        if (centres_out) { centres_out[2 * view] = cy; centres_out[2 * view + 1] = cx; }
-        if (trace_k) {
-            float* tr = trace_k + view * trace_stride;
-            tr[0] = cy; tr[1] = cx; tr[2] = best;
-        }
-        if (shifts) { shifts[2 * view] = cy; shifts[2 * view + 1] = cx; }
-    }
+    // all tiles of the view as one row: the row-major order of the rectangle is the tiles' index order
+    finish_tiles(F, sums + view * tiles * pp * RG_NSUM, tiles, 0, 1, 0, tiles, P, width, cy, cx, centres_out || trace_k || shifts,
+                 centres_out ? centres_out + 2 * view : nullptr, trace_k ? trace_k + view * trace_stride : nullptr, tid);
+    if (scores && tid < pp) scores[view * pp + tid] = F.score[tid];
+    if (tid == 0 && shifts) { shifts[2 * view] = cy; shifts[2 * view + 1] = cx; }
 }
 
 // ----------------------------------------------------------------------------- the resampler
@@ -135,12 +109,12 @@ __global__ __launch_bounds__(SC_THREADS) void scene_apply_kernel(const float* __
     const int x = lane, gx = tx0 + x;
 #pragma unroll
     for (int k = 0; k < SC_ITEMS; ++k) {
-        const int yl = (wave + k * SC_WAVES) * SC_RUN, gy = ty0 + yl;
-        float t[SC_RUN];
+        const int yl = (wave + k * SC_WAVES) * RG_RUN, gy = ty0 + yl;
+        float t[RG_RUN];
         const unsigned c = scene_column_run(S, ky, ny, nx, 0, 0, table, x, yl, gy, gx, H, W, t);
         if (gx >= W) continue;
 #pragma unroll
-        for (int p = 0; p < SC_RUN; ++p) {
+        for (int p = 0; p < RG_RUN; ++p) {
             if (gy + p >= H) break;
             const bool on = (c >> p) & 1u;
             const size_t i = view * hw + (size_t)(gy + p) * W + gx;

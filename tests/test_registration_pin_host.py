@@ -77,7 +77,7 @@ def sample_f32(T, shift):
 def thread_pixels(H, W, path):
     """(threads, pixels a thread) flat pixel indices in the order a thread of the kernels adds them, -1 where it has none.  "resident":
     registration.hip, 512 threads of four runs of 8 rows of a column, run `item` = tid + 512 k at column item % W, rows 8 (item // W);
-    "scene": mncc_scene_level.h, per tile of 64 x 64 a thread (wave, lane) takes rows 8 (wave + 4 k) .. + 7, k < 2, of column lane."""
+    "scene": mncc_scene.h's scene_level, per tile of 64 x 64 a thread (wave, lane) takes rows 8 (wave + 4 k) .. + 7, k < 2, of column lane."""
     p = np.arange(RUN)
     if path == "resident":
         item = np.arange(RESIDENT_THREADS)[:, None] + RESIDENT_THREADS * np.arange(4)[None, :]
