@@ -50,8 +50,9 @@
  *     -5 HIP runtime error); hrn_last_error() returns a thread-local message for the last failing call;
  *   - dtype selects storage of activations and the MFMA input type:
  *       HRN_DTYPE_F32  : f32 activations, v_mfma_f32_32x32x2_f32 (exact fp32 products and accumulation)
- *       HRN_DTYPE_BF16 : bf16 activations/weights, fp32 accumulation: v_mfma_f32_32x32x16_bf16 in the stem, the encoder and the
- *                        decoder, v_mfma_f32_16x16x32_bf16 in the fusion levels (128 -> {128, 64} convs)
+ *       HRN_DTYPE_BF16 : bf16 activations/weights, fp32 accumulation: v_mfma_f32_16x16x32_bf16 in the encoder's 64 -> 64 convs and
+ *                        the fusion levels (128 -> {128, 64} convs), v_mfma_f32_32x32x16_bf16 in the stem, the decoder and the
+ *                        general conv kernel (the route of images beyond the 32-bit in-image offsets)
  *       HRN_DTYPE_BF16X3 : every fp32 activation / weight as two bf16 planes (hi = bf16(v), lo = bf16(v - hi)); a product is
  *                        hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (~2^-16 per product): the
  *                        reference's fp32 arithmetic (train.py:168-171, predict.py:36-37) to ~1e-5 at a third of the bf16

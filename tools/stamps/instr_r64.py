@@ -20,11 +20,11 @@ constexpr int PH0 = 40;
 #define STAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (cur_ph == PH0) st[i] = t_; else if (cur_ph == PH0 + 1) st[7 + (i)] = t_; } while (0)""")
 rep("    const bool has_slope = p.slope != nullptr;",
     "    unsigned long long st[14];\n#pragma unroll\n    for (int i = 0; i < 14; ++i) st[i] = 0;\n    int cur_ph = -1;\n    const int abl = hrn_r64_abl;\n    const bool has_slope = p.slope != nullptr;")
-rep("        constexpr int NK = 36;", "        STAMP(6);\n        constexpr int NK = 36;")
+rep("        constexpr int NK = 18;", "        STAMP(6);\n        constexpr int NK = 18;")
 rep("        if (more) issue(cur_m, cur_t);                      // in flight while the epilogue runs", "        if (more && !(abl & 2)) issue(cur_m, cur_t);\n        STAMP(3);")
 rep("        {   // the halo DMAs were issued before this tile's stores", "        STAMP(4);\n        {   // the halo DMAs were issued before this tile's stores")
 rep("        fix_borders();\n    };", "        fix_borders();\n        STAMP(5);\n    };")
-rep("    for (int ph = 0; ph <= ntl; ++ph) {\n        const int q = ph - team;", "    for (int ph = 0; ph <= ntl; ++ph) {\n        cur_ph = ph;\n        STAMP(0);\n        const int q = ph - team;")
+rep("    for (int ph = 0; ph <= ntl; ++ph) {\n        const int s = ph - team;", "    for (int ph = 0; ph <= ntl; ++ph) {\n        cur_ph = ph;\n        STAMP(0);\n        const int s = ph - team;")
 rep("        if (ph < ntl) lds_done_then_barrier();\n    }\n}", """        STAMP(1);
         if (ph < ntl) lds_done_then_barrier();
         STAMP(2);
@@ -34,8 +34,7 @@ rep("        if (ph < ntl) lds_done_then_barrier();\n    }\n}", """        STAMP
         for (int i = 0; i < 14; ++i) hrn_r64_stamps[RES ? 1 : 0][(bid * 8 + wave) * 16 + i] = st[i];
     }
 }""")
-s = s.replace("if (gy < H && gx < W) op[g] = u;", "if (gy < H && gx < W && !(abl & 1)) op[g] = u;")
-s = s.replace("if (gy < H && x0 + (r & ~3) + j < W) *(u32x4*)(oq + j * 128) = uu[j];", "if (gy < H && x0 + (r & ~3) + j < W && !(abl & 1)) *(u32x4*)(oq + j * 128) = uu[j];")
+rep("if (gy < H && x0 + 16 * (pxb & 1) + 2 * h + lane_px < W) __builtin_nontemporal_store(", "if (gy < H && x0 + 16 * (pxb & 1) + 2 * h + lane_px < W && !(abl & 1)) __builtin_nontemporal_store(")
 rep("}  // namespace\n\n// bf16 64 -> 64 with a plain input", """}  // namespace
 extern "C" int hrn_dbg_set_abl(int v) {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(hrn_r64_abl), &v, sizeof(int), 0, hipMemcpyHostToDevice);
