@@ -21,7 +21,7 @@ void hrn_set_error(const char* fmt, ...) {
 
 namespace {
 
-using namespace hrn;     // packed-parameter layout, at(), conv_base(): hrnet_layout.h
+using namespace hrn;     // packed-parameter layout, at(), conv_site(): hrnet_layout.h
 
 // ---------------------------------------------------------------- HRNet workspace layout
 struct HrnetWs {

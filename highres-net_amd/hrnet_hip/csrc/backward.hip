@@ -556,11 +556,11 @@ int hrn_launch_conv_wgrad(int dt, const void* x, const void* stack, int in_pair,
     if (dt == HRN_BF16) return hrn_launch_conv_wgrad_bf16(x, stack, in_pair, pair_h, pair_last, pair_vs, g, M, H, W, cin, cout, dw, scratch, num_cus, s);
     HRN_CHECK(dt == HRN_BF16X3, -2, "conv_wgrad: dtype %d", dt);
     HRN_CHECK(!in_pair || pair_h > 0, -2, "conv_wgrad: pair descriptor missing");
-    // the lo plane directly behind the hi plane: of x [M][H][W][cin], or of the level's whole stack, M / pair_h samples x pair_vs views
+    // the lo plane of x [M][H][W][cin], or of the level's whole stack, M / pair_h samples x pair_vs views
     const size_t hw = (size_t)H * W;
-    const size_t x_lo = in_pair ? (size_t)(M / pair_h) * pair_vs * hw * 64 * 2 : (size_t)M * hw * cin * 2;
-    return hrn_launch_conv_wgrad_x3(x, stack, x_lo, in_pair, pair_h, pair_last, pair_vs, g, (size_t)M * hw * cout * 2, M, H, W, cin, cout, dw,
-                                    scratch, num_cus, s);
+    const size_t x_lo = hrn_lo_of(dt, in_pair ? (size_t)(M / pair_h) * pair_vs * hw * 64 : (size_t)M * hw * cin);
+    return hrn_launch_conv_wgrad_x3(x, stack, x_lo, in_pair, pair_h, pair_last, pair_vs, g, hrn_lo_of(dt, (size_t)M * hw * cout), M, H, W, cin,
+                                    cout, dw, scratch, num_cus, s);
 }
 
 int hrn_launch_conv_wgrad_f32(const float* x, const float* stack, int in_pair, int pair_h, int pair_last, int pair_vs, const float* g,
@@ -643,13 +643,10 @@ int hrn_conv_dgrad(int dt, int cin, int cout, const float* w, const void* g, voi
     hrn_count_launch(HRN_LC_CONV_DGRAD);
     if ((rc = hrn_launch_dgrad_weights(w, wt, cin, cout, s))) return rc;
     if ((rc = hrn_launch_conv_pack(dt, cout, cin, wt, wtp, s))) return rc;               // a cout -> cin convolution
-    ConvParams p = ConvParams();
-    p.M = M; p.H = H; p.W = W;
-    p.in = g; p.out = dx; p.wpk = wtp; p.bias = zero_bias; p.slope = nullptr;
+    ConvParams p = conv_base(M, H, W);
+    p.in = g; p.out = dx; p.wpk = wtp; p.bias = zero_bias;
     if (res) { p.res = res; p.res_mode = 1; }
-    if (dt == HRN_BF16X3) {               // every tensor a pair of bf16 planes, the lo plane directly behind the hi plane
-        const size_t px = (size_t)M * H * W;
-        p.in_lo = px * cout * 2; p.out_lo = px * cin * 2; p.res_lo = px * cin * 2;
-    }
+    const size_t px = (size_t)M * H * W;
+    p.in_lo = hrn_lo_of(dt, px * cout); p.out_lo = p.res_lo = hrn_lo_of(dt, px * cin);
     return hrn_launch_conv3x3(dt, cout, cin, p, s, false);
 }

@@ -96,6 +96,7 @@ template <> __device__ __forceinline__ void store4<HRN_BF16>(void* p, size_t i, 
 // HRN_BF16X3, a PAIR of bf16 planes: hi at p, lo `lo` bytes further on.  A bf16x3 tensor of n elements has lo = 2 n (the lo plane
 // directly behind the hi plane), which is how every kernel derives it from the tensor's shape; the other kinds ignore `lo`.
 // Unit: 4 consecutive elements.
+static inline size_t hrn_lo_of(int dt, size_t n) { return dt == HRN_BF16X3 ? n * 2 : 0; }     // `lo` of a tensor of n elements, host side
 template <int ST> __device__ __forceinline__ f32x4 act_ld4(const void* p, size_t lo, size_t i4) {
     if constexpr (ST == HRN_BF16X3) {
         const u32x2 h = __builtin_nontemporal_load((const u32x2*)p + i4);

@@ -1,5 +1,6 @@
 // 3x3 / pad 1 / stride 1 convolution as an LDS-staged implicit GEMM on MFMA (gfx950).
 #pragma once
+#include <string.h>
 #include "common.h"
 
 // Tile geometry shared by the kernel, the weight packer and the host launcher.
@@ -31,24 +32,48 @@ struct ConvParams {
                                       // recomputation of a pre-activation, needed only behind a PReLU whose slope is not positive)
 };
 
+// A well-formed descriptor - what keeps every index the kernels form inside the tensors as described above.  hrn_conv3x3_route checks it
+// first, for every dtype, before any route is considered; a violation is error -2 with a message that names the field.
+//   always                  M, H, W > 0;  wpk, bias, out non-null;  in non-null unless in_pair;  res_mode in 0..3
+//   in_pair                 cin == 128
+//   in_pair or res_mode 2   stack non-null, pair_h > 0, M % pair_h == 0, pair_h - 1 <= pair_last < pair_vs (both views of every pair lie
+//                           in the sample's pair_vs slots);  res_mode 2: cout == 128
+//   res_mode 1              res non-null
+//   res_mode 3              res non-null, out_h > 0, res_vs >= out_h; with alphas: out_h - 1 <= pair_last < alpha_vs
+//   out_h > 0               M % out_h == 0, out_vs >= out_h
+//   bf16x3                  out_lo and in_lo (in_pair: stack_lo) != 0; no scale / relu; no general kernel
+static inline ConvParams conv_base(int M, int H, int W) {
+    ConvParams p;
+    memset(&p, 0, sizeof p);
+    p.M = M; p.H = H; p.W = W;
+    return p;
+}
+
 // Number of packed weight elements of one conv layer (== cin*cout*9).
 static inline size_t conv_packed_elems(int cin, int cout) { return (size_t)cin * cout * 9; }
 
-// Launch on `stream`.  dt: HRN_F32 / HRN_BF16; (cin, cout) in {64,128}^2.  Returns 0 or a negative error.  general_only: this file's
-// general kernel even where r64 / v6 apply (the route HRN_CONV_R64=0 HRN_CONV_V6=0 selects; kernel_test.hip's route 1)
+// ---- Which kernel runs a launch.  Four families: the general kernel (conv3x3.hip), r64 (conv3x3_r64.hip: bf16 64 -> 64, LDS-resident
+// weights), v6 (conv3x3_v6.hip: bf16 with 128 channels on a side - the three layers of a fusion level, and the data gradients 64 -> 128 and
+// 128 -> 128 + plain residual) and v6x3 (conv3x3_v6x3.hip: bf16x3 on the v6 skeleton, the only kernel of that dtype).  A fast family
+// states its instantiated kernels as a table of rows, in the translation unit of its kernels: a layer is applicable to the family exactly
+// when a row matches its (cin, cout, res_mode, in_pair), and that row's pointer is the dispatch.
+enum ConvFamily { CONV_GENERAL, CONV_R64, CONV_V6, CONV_V6X3 };
+typedef int (*ConvLaunchFn)(const ConvParams& p, long grid, hipStream_t stream);
+struct ConvInstance { int cin, cout, res_mode, in_pair; const char* name; ConvLaunchFn launch; };      // name: the profiler's family name
+struct ConvTable { int family, tile_h, tile_w, es; const ConvInstance* rows; int nrows; };            // es: bytes per element, all planes
+const ConvTable &conv_table_r64(), &conv_table_v6(), &conv_table_v6x3();
+// a chosen route: family, profiler name and cost, tile shape, persistent grid, and the launcher of the template instance
+struct ConvRoute { int family; const char* name; int tile_h, tile_w; long grid; double flops, bytes; ConvLaunchFn launch; };
+
+// The pure step: checks the contract above, then chooses.  Launches nothing, allocates nothing.  dt: HRN_F32 / HRN_BF16 / HRN_BF16X3;
+// (cin, cout) in {64,128}^2.  bf16x3 -> v6x3 only (no row, or an image beyond its 32-bit offsets: an error).  bf16 without scale / relu /
+// general_only -> r64, then v6, where a row matches and the image fits (HRN_CONV_R64=0 / HRN_CONV_V6=0, read once per process, switch
+// them off), else general.  Everything else -> general.  Returns 0 or a negative error.
+int hrn_conv3x3_route(int dt, int cin, int cout, const ConvParams& p, bool general_only, ConvRoute& route);
+
+// Route, then launch on `stream`: the one entry the rest of the library calls.  general_only: conv3x3.hip's general kernel even where
+// r64 / v6 apply (the route HRN_CONV_R64=0 HRN_CONV_V6=0 selects; kernel_test.hip's route 1).  Returns 0 or a negative error.
 int hrn_launch_conv3x3(int dt, int cin, int cout, const ConvParams& p, hipStream_t stream, bool general_only);
-
-// bf16 64 -> 64 with LDS-resident weights (conv3x3_r64.hip); -100 = not applicable, caller picks another kernel.
-int hrn_launch_conv3x3_r64(const ConvParams& p, hipStream_t stream);
-
-// bf16 128 -> {128, 64}: the three layers of a fusion level; descriptor-based halo DMA issued from the MFMA gaps, epilogue straight
-// from the accumulators in whole pixel rows (conv3x3_v6.hip).  Also the two data gradients of the bf16 training path the other
-// kernels do not cover: 128 -> 128 + plain residual and 64 -> 128.  -100 = not applicable.
-int hrn_launch_conv3x3_v6(int cin, int cout, const ConvParams& p, hipStream_t stream);
-
-// bf16x3 (split-bf16: hi/lo planes, three MFMAs per product) on the conv3x3_v6 skeleton: (cin, cout) = (64, 64) with res_mode 0 | 1,
-// (128, 128) with 0 | 2 (+ pair-gather input), (128, 64) with 0 | 3 (conv3x3_v6x3.hip).  No other kernel implements this dtype.
-int hrn_launch_conv3x3_v6x3(int cin, int cout, const ConvParams& p, hipStream_t stream);
 
 // Pack OIHW f32 weights [cout][cin][3][3] into the kernel's step-major layout (device to device).
 int hrn_launch_conv_pack(int dt, int cin, int cout, const float* w_oihw, void* packed, hipStream_t stream);

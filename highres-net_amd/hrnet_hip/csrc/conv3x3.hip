@@ -315,25 +315,22 @@ __global__ __launch_bounds__(256 * (COUT / 64), 2) void conv3x3_kernel(const Con
 
 
 template <int DT, int CIN, int COUT>
-int launch(const ConvParams& p, hipStream_t stream) {
+int launch(const ConvParams& p, long grid, hipStream_t stream) {
     constexpr int LDS_BYTES = IN_LDS_BYTES + 2 * COUT * W_ROW_PITCH;
     { const int rc_lds = hrn_allow_lds((const void*)conv3x3_kernel<DT, CIN, COUT>, LDS_BYTES); if (rc_lds) return rc_lds; }
-    const long tiles = (long)((p.W + CONV_TILE_W - 1) / CONV_TILE_W) * ((p.H + CONV_TILE_H - 1) / CONV_TILE_H);
-    const long total = tiles * p.M;
-    HRN_CHECK(total > 0 && total < (1L << 40), -2, "conv3x3: bad tile count %ld", total);
-    long grid = (2L / (COUT / 64)) * hrn_device_cus();     // one persistent round: 8 waves per CU (2 x 256 or 1 x 512 threads)
-    if (total < grid) grid = total;
-    if (grid >= 8) grid &= ~7L;             // windows split evenly over the 8 XCDs
-    static const char* fam_names[2][2][2] = {{{"conv3x3_f32_64x64", "conv3x3_f32_64x128"}, {"conv3x3_f32_128x64", "conv3x3_f32_128x128"}},
-                                             {{"conv3x3_bf16_64x64", "conv3x3_bf16_64x128"}, {"conv3x3_bf16_128x64", "conv3x3_bf16_128x128"}}};
-    const double px = (double)p.M * p.H * p.W, es = ElemOf<DT>::size;
-    HrnProfScope prof(fam_names[DT][CIN / 128][COUT / 128], 2.0 * CIN * COUT * 9 * px,
-                      px * es * (CIN + COUT + (p.res_mode ? COUT : 0)), stream);
     hipLaunchKernelGGL((conv3x3_kernel<DT, CIN, COUT>), dim3((unsigned)grid), dim3(256 * (COUT / 64)), LDS_BYTES, stream, p);
     hrn_count_launch(HRN_LC_CONV_GENERAL);
     HRN_LAUNCH_CHECK();
     return 0;
 }
+
+// The general kernel's instances, [dt][cin / 128][cout / 128].  Each takes any res_mode and either input, and files a residual layer under
+// the plain name: a row's res_mode / in_pair say nothing.
+#define ROW(DT_, TAG_, CI_, CO_) {CI_, CO_, 0, 0, "conv3x3_" TAG_ "_" #CI_ "x" #CO_, launch<DT_, CI_, CO_>}
+const ConvInstance GENERAL_ROWS[2][2][2] = {
+    {{ROW(HRN_F32, "f32", 64, 64), ROW(HRN_F32, "f32", 64, 128)}, {ROW(HRN_F32, "f32", 128, 64), ROW(HRN_F32, "f32", 128, 128)}},
+    {{ROW(HRN_BF16, "bf16", 64, 64), ROW(HRN_BF16, "bf16", 64, 128)}, {ROW(HRN_BF16, "bf16", 128, 64), ROW(HRN_BF16, "bf16", 128, 128)}}};
+#undef ROW
 
 // ---- weight packing: OIHW f32 -> [step][64 cout][128 B of K], step = (chunk*9 + tap)*NHALF + half
 template <int DT>
@@ -375,38 +372,92 @@ __global__ void conv_pack_x3_kernel(const float* __restrict__ w, unsigned short*
     }
 }
 
+// the descriptor contract of conv3x3.h
+int check_descriptor(int dt, int cin, int cout, const ConvParams& p, bool general_only) {
+    HRN_CHECK((dt == HRN_F32 || dt == HRN_BF16 || dt == HRN_BF16X3) && (cin == 64 || cin == 128) && (cout == 64 || cout == 128), -2,
+              "conv3x3: unsupported dtype/channels dt=%d cin=%d cout=%d", dt, cin, cout);
+    HRN_CHECK(p.M > 0 && p.H > 0 && p.W > 0, -2, "conv3x3: empty problem M=%d H=%d W=%d", p.M, p.H, p.W);
+    HRN_CHECK(p.wpk && p.bias && p.out, -2, "conv3x3: null %s", !p.wpk ? "wpk" : !p.bias ? "bias" : "out");
+    HRN_CHECK(p.in_pair || p.in, -2, "conv3x3: null in without in_pair");
+    HRN_CHECK(p.res_mode >= 0 && p.res_mode <= 3, -2, "conv3x3: res_mode %d not in 0..3", p.res_mode);
+    HRN_CHECK(!p.in_pair || cin == 128, -2, "conv3x3: in_pair needs cin=128, not %d", cin);
+    HRN_CHECK(p.res_mode != 2 || cout == 128, -2, "conv3x3: res_mode 2 needs cout=128, not %d", cout);
+    HRN_CHECK(!(p.in_pair || p.res_mode == 2) ||
+                  (p.stack && p.pair_h > 0 && p.M % p.pair_h == 0 && p.pair_h - 1 <= p.pair_last && p.pair_last < p.pair_vs), -2,
+              "conv3x3: the pair gather needs stack, pair_h > 0 dividing M and pair_h - 1 <= pair_last < pair_vs (stack=%p pair_h=%d M=%d "
+              "pair_last=%d pair_vs=%d)", p.stack, p.pair_h, p.M, p.pair_last, p.pair_vs);
+    HRN_CHECK(p.res_mode != 1 || p.res, -2, "conv3x3: res_mode 1 needs res");
+    HRN_CHECK(p.res_mode != 3 || (p.res && p.out_h > 0 && p.res_vs >= p.out_h), -2,
+              "conv3x3: res_mode 3 needs res, slot output and res_vs >= out_h (res=%p out_h=%d res_vs=%d)", p.res, p.out_h, p.res_vs);
+    HRN_CHECK(p.res_mode != 3 || !p.alphas || (p.out_h - 1 <= p.pair_last && p.pair_last < p.alpha_vs), -2,
+              "conv3x3: alphas need out_h - 1 <= pair_last < alpha_vs (out_h=%d pair_last=%d alpha_vs=%d)", p.out_h, p.pair_last, p.alpha_vs);
+    HRN_CHECK(p.out_h <= 0 || (p.M % p.out_h == 0 && p.out_vs >= p.out_h), -2,
+              "conv3x3: slot output needs out_h dividing M and out_vs >= out_h (out_h=%d M=%d out_vs=%d)", p.out_h, p.M, p.out_vs);
+    if (dt != HRN_BF16X3) return 0;
+    HRN_CHECK(!general_only, -2, "conv3x3: bf16x3 has no general kernel");
+    HRN_CHECK(!p.scale && !p.relu, -2, "conv3x3 bf16x3: folded scale / relu are not supported");
+    HRN_CHECK(p.out_lo != 0 && (p.in_pair ? p.stack_lo : p.in_lo) != 0, -2, "conv3x3 bf16x3: lo-plane offsets missing (out_lo / %s)",
+              p.in_pair ? "stack_lo" : "in_lo");
+    return 0;
+}
+
+long tile_count(const ConvParams& p, int th, int tw) { return (long)((p.W + tw - 1) / tw) * ((p.H + th - 1) / th) * p.M; }    // of the whole launch
+
+// The route of `row` on th x tw tiles.  The grid is persistent: one round of wg_per_cu workgroups per CU, at most one per tile, and a
+// multiple of 8 so that the windows split evenly over the 8 XCDs.  The profiler's cost: algorithmic FLOPs, bytes of every plane.
+ConvRoute route_of(int family, const ConvInstance& row, int th, int tw, int es, int wg_per_cu, const ConvParams& p) {
+    long grid = (long)wg_per_cu * hrn_device_cus();
+    if (tile_count(p, th, tw) < grid) grid = tile_count(p, th, tw);
+    if (grid >= 8) grid &= ~7L;
+    const double px = (double)p.M * p.H * p.W;
+    return ConvRoute{family, row.name, th, tw, grid, 2.0 * row.cin * row.cout * 9 * px, px * es * (row.cin + row.cout + (p.res_mode ? row.cout : 0)),
+                     row.launch};
+}
+
+// A fast family's whole rule: the row of its table that matches the layer, if the image fits its 32-bit arithmetic; else it declines - for
+// shape and size only, never a malformed descriptor.  The fast kernels count tiles and in-image bytes in 32 bits: the tile total must stay
+// below 2^30, and ONE image of the wider of input and output (2 bytes per channel and pixel; the plain residual is as wide as the output)
+// below 2^31 bytes - 16.7 Mpixel at 64 channels, 8.3 Mpixel at 128.  (v6 marks an out-of-image lane with bit 31 of its offset, which
+// only a buffer descriptor of fewer than 2^31 bytes drops.)
+enum ConvDecline { CONV_NO_INSTANCE = 1, CONV_TOO_LARGE = 2 };
+int route_fast(const ConvTable& t, int cin, int cout, const ConvParams& p, ConvRoute& r) {
+    for (const ConvInstance* row = t.rows; row < t.rows + t.nrows; ++row) {
+        if (row->cin != cin || row->cout != cout || row->res_mode != p.res_mode || row->in_pair != (p.in_pair != 0)) continue;
+        if (tile_count(p, t.tile_h, t.tile_w) >= (1L << 30) || (long)p.H * p.W * 2 * (cin > cout ? cin : cout) >= (1L << 31)) return CONV_TOO_LARGE;
+        r = route_of(t.family, *row, t.tile_h, t.tile_w, t.es, 1, p);
+        return 0;
+    }
+    return CONV_NO_INSTANCE;
+}
+
 }  // namespace
 
-int hrn_launch_conv3x3(int dt, int cin, int cout, const ConvParams& p, hipStream_t stream, bool general_only) {
-    HRN_CHECK(p.M > 0 && p.H > 0 && p.W > 0, -2, "conv3x3: empty problem M=%d H=%d W=%d", p.M, p.H, p.W);
-    HRN_CHECK(!p.in_pair || (cin == 128 && p.pair_h > 0 && p.stack), -2, "conv3x3: pair input needs cin=128 and a pair descriptor");
-    HRN_CHECK(p.res_mode != 2 || (p.pair_h > 0 && p.stack && cout == 128), -2, "conv3x3: res_mode 2 needs a pair descriptor and cout=128");
-    HRN_CHECK(p.in_pair || p.in, -2, "conv3x3: null input");
-    HRN_CHECK(p.res_mode != 3 || p.out_h > 0, -2, "conv3x3: res_mode 3 needs slot output");
-    HRN_CHECK(!(general_only && dt == HRN_BF16X3), -2, "conv3x3: bf16x3 has no general kernel");
-    if (dt == HRN_BF16X3) return hrn_launch_conv3x3_v6x3(cin, cout, p, stream);      // the only kernel of this precision mode
+int hrn_conv3x3_route(int dt, int cin, int cout, const ConvParams& p, bool general_only, ConvRoute& route) {
+    if (const int rc = check_descriptor(dt, cin, cout, p, general_only)) return rc;
+    if (dt == HRN_BF16X3) {                 // the only kernel of this precision mode: nothing behind it
+        const int rc = route_fast(conv_table_v6x3(), cin, cout, p, route);
+        HRN_CHECK(rc != CONV_NO_INSTANCE, -2, "conv3x3 bf16x3: unsupported layer cin=%d cout=%d res_mode=%d in_pair=%d", cin, cout, p.res_mode, p.in_pair);
+        HRN_CHECK(rc != CONV_TOO_LARGE, -2, "conv3x3 bf16x3: image too large for 32-bit in-image offsets (H=%d W=%d)", p.H, p.W);
+        return 0;
+    }
     if (dt == HRN_BF16 && !p.scale && !p.relu && !general_only) {
-        // the HRNet layers in bf16: resident-weights kernel (conv3x3_r64.hip) for the encoder's 64 -> 64 layers, conv3x3_v6.hip for the
-        // three layers of a fusion level.  What they decline (images beyond their 32-bit in-image offsets: 2^31 bytes of the wider of the
-        // input and output image, i.e. 16.7 Mpixel at 64 channels, 8.3 Mpixel at 128) runs on this file's general kernel;
-        // HRN_CONV_R64=0 / HRN_CONV_V6=0 force that route (A/B timing, and the test that covers it).
+        // the HRNet layers in bf16.  HRN_CONV_R64=0 / HRN_CONV_V6=0 force the general kernel (A/B timing, and the test that covers it)
         static const int r64 = [] { const char* e = getenv("HRN_CONV_R64"); return e ? atoi(e) : 1; }();
         static const int v6 = [] { const char* e = getenv("HRN_CONV_V6"); return e ? atoi(e) : 1; }();
-        if (cin == 64 && cout == 64 && r64) { const int rc = hrn_launch_conv3x3_r64(p, stream); if (rc != -100) return rc; }
-        if ((cin == 128 || cout == 128) && v6) { const int rc = hrn_launch_conv3x3_v6(cin, cout, p, stream); if (rc != -100) return rc; }
+        if (r64 && route_fast(conv_table_r64(), cin, cout, p, route) == 0) return 0;
+        if (v6 && route_fast(conv_table_v6(), cin, cout, p, route) == 0) return 0;
     }
-#define HRN_CONV_CASE(DT_, CI_, CO_) if (dt == DT_ && cin == CI_ && cout == CO_) return launch<DT_, CI_, CO_>(p, stream);
-    HRN_CONV_CASE(HRN_BF16, 64, 64)
-    HRN_CONV_CASE(HRN_BF16, 64, 128)
-    HRN_CONV_CASE(HRN_BF16, 128, 64)
-    HRN_CONV_CASE(HRN_BF16, 128, 128)
-    HRN_CONV_CASE(HRN_F32, 64, 64)
-    HRN_CONV_CASE(HRN_F32, 64, 128)
-    HRN_CONV_CASE(HRN_F32, 128, 64)
-    HRN_CONV_CASE(HRN_F32, 128, 128)
-#undef HRN_CONV_CASE
-    hrn_set_error("conv3x3: unsupported dtype/channels dt=%d cin=%d cout=%d", dt, cin, cout);
-    return -2;
+    HRN_CHECK(tile_count(p, CONV_TILE_H, CONV_TILE_W) < (1L << 40), -2, "conv3x3: bad tile count %ld", tile_count(p, CONV_TILE_H, CONV_TILE_W));
+    // one persistent round is 8 waves per CU: 2 workgroups of 256 threads or 1 of 512
+    route = route_of(CONV_GENERAL, GENERAL_ROWS[dt][cin / 128][cout / 128], CONV_TILE_H, CONV_TILE_W, hrn_esize(dt), 2 / (cout / 64), p);
+    return 0;
+}
+
+int hrn_launch_conv3x3(int dt, int cin, int cout, const ConvParams& p, hipStream_t stream, bool general_only) {
+    ConvRoute r;
+    if (const int rc = hrn_conv3x3_route(dt, cin, cout, p, general_only, r)) return rc;
+    HrnProfScope prof(r.name, r.flops, r.bytes, stream);
+    return r.launch(p, r.grid, stream);
 }
 
 int hrn_launch_conv_pack(int dt, int cin, int cout, const float* w, void* packed, hipStream_t stream) {

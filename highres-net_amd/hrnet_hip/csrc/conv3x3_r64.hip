@@ -444,21 +444,16 @@ int launch_r64(const ConvParams& p, long grid, hipStream_t stream) {
     return 0;
 }
 
+// The instances: <RES> is any residual read at the stored pixel, the plain tensor (1) or the view-stack slot with its alpha (3); a plain
+// input tensor only.
+const ConvInstance R64_ROWS[] = {{64, 64, 0, 0, "conv3x3_bf16_64x64", launch_r64<false>},
+                                 {64, 64, 1, 0, "conv3x3_bf16_64x64+res", launch_r64<true>},
+                                 {64, 64, 3, 0, "conv3x3_bf16_64x64+res", launch_r64<true>}};
+static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
+
 }  // namespace
 
-// bf16 64 -> 64 with a plain input tensor (no pair gather).  Returns -100 when not applicable.
-int hrn_launch_conv3x3_r64(const ConvParams& p, hipStream_t stream) {
-    if (p.scale || p.relu || p.in_pair || p.res_mode == 2) return -100;
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
-    const long tiles = (long)((p.W + CONV_TILE_W - 1) / CONV_TILE_W) * ((p.H + CONV_TILE_H - 1) / CONV_TILE_H);
-    const long total = tiles * p.M;
-    HRN_CHECK(total > 0, -2, "conv3x3_r64: bad tile count %ld", total);
-    if (total >= (1L << 30) || (long)p.H * p.W * 128 >= (1L << 31)) return -100;     // 32-bit tile / in-image byte arithmetic
-    long grid = hrn_device_cus();
-    if (total < grid) grid = total;
-    if (grid >= 8) grid &= ~7L;
-    const double px = (double)p.M * p.H * p.W;
-    HrnProfScope prof(p.res_mode ? "conv3x3_bf16_64x64+res" : "conv3x3_bf16_64x64", 2.0 * 64 * 64 * 9 * px,
-                      px * 2 * (64 + 64 + (p.res_mode ? 64 : 0)), stream);
-    return p.res_mode ? launch_r64<true>(p, grid, stream) : launch_r64<false>(p, grid, stream);
+const ConvTable& conv_table_r64() {
+    static const ConvTable t = {CONV_R64, CONV_TILE_H, CONV_TILE_W, 2, R64_ROWS, sizeof R64_ROWS / sizeof *R64_ROWS};
+    return t;
 }

@@ -45,33 +45,12 @@ extern "C" int hrn_dbg_read_stamps_v6(void* dst, size_t bytes) {
 }
 #endif
 
-// bf16, 128 input channels.  COUT = 128: residual none or the pair gather (res_mode 2); COUT = 64: none or the alpha residual into
-// the view stack (res_mode 3).  The training path's data gradients add 128 -> 128 with a plain residual (res_mode 1: the gradient that
-// bypasses the layer) and 64 -> 128 without one.  Returns -100 when not applicable.
-int hrn_launch_conv3x3_v6(int cin, int cout, const ConvParams& p, hipStream_t stream) {
-    if (p.scale || p.relu) return -100;
-    if (cin == 64) {
-        if (cout != 128 || p.res_mode != 0 || p.in_pair) return -100;
-    } else {
-        if (cin != 128 || (cout != 64 && cout != 128)) return -100;
-        if (cout == 128 && p.res_mode != 0 && p.res_mode != 2 && !(p.res_mode == 1 && !p.in_pair)) return -100;
-        if (cout == 64 && ((p.res_mode != 0 && p.res_mode != 3) || p.in_pair)) return -100;
-    }
-    if ((p.in_pair || p.res_mode == 2) && p.pair_h <= 0) return -100;
-    if (p.res_mode == 3 && (p.out_h <= 0 || !p.res)) return -100;
-    if (p.res_mode == 1 && !p.res) return -100;
-    long grid = 0;
-    { const int rc = v6_grid(p, cin, cout, grid); if (rc) return rc; }
-    const double px = (double)p.M * p.H * p.W;
-    const char* fam = cin == 64 ? "conv3x3_bf16_64x128"
-                    : cout == 128 ? (p.res_mode ? "conv3x3_bf16_128x128+res" : "conv3x3_bf16_128x128")
-                                  : (p.res_mode ? "conv3x3_bf16_128x64+res" : "conv3x3_bf16_128x64");
-    HrnProfScope prof(fam, 2.0 * cin * cout * 9 * px, px * 2 * (cin + cout + (p.res_mode ? cout : 0)), stream);
-    if (cin == 64) return launch_v6<64, 128, 0, false, false>(p, grid, stream);           // the data gradient of a 128 -> 64 layer
-    if (cout == 128) {
-        if (p.in_pair) return p.res_mode ? launch_v6<128, 128, 2, true, false>(p, grid, stream) : launch_v6<128, 128, 0, true, false>(p, grid, stream);
-        if (p.res_mode == 1) return launch_v6<128, 128, 1, false, false>(p, grid, stream);        // data gradient + the gradient that bypasses the layer
-        return p.res_mode ? launch_v6<128, 128, 2, false, false>(p, grid, stream) : launch_v6<128, 128, 0, false, false>(p, grid, stream);
-    }
-    return p.res_mode ? launch_v6<128, 64, 3, false, false>(p, grid, stream) : launch_v6<128, 64, 0, false, false>(p, grid, stream);
+// this file's instances: the family's common rows in bf16
+#define V6_ROW(CI_, CO_, RESM_, PAIR_, NAME_) {CI_, CO_, RESM_, PAIR_, "conv3x3_bf16_" NAME_, launch_v6<CI_, CO_, RESM_, PAIR_, false>},
+static const ConvInstance V6_ROWS[] = {V6_COMMON_ROWS(V6_ROW)};
+#undef V6_ROW
+
+const ConvTable& conv_table_v6() {
+    static const ConvTable t = {CONV_V6, T6_H, T6_W, 2, V6_ROWS, sizeof V6_ROWS / sizeof *V6_ROWS};
+    return t;
 }

@@ -629,21 +629,18 @@ int launch_v6(const ConvParams& p, long grid, hipStream_t stream) {
     return 0;
 }
 
-// tiles, the 32-bit arithmetic limits, the persistent grid: shared by both launchers.  Returns 0, or -100 when not applicable.
-// One image of the WIDER of input and output must stay below 2^31 bytes: the halo offsets and the input descriptor count in_pitch =
-// 2 cin bytes per pixel, the output offsets, the output descriptor ((int)(hw * ROW)) and the plain residual ROW = 2 cout, and an
-// out-of-image lane is marked with bit 31 of its offset (OOB6), which only a descriptor of fewer than 2^31 bytes drops.  (The limit
-// counted the input alone until the 64 -> 128 data gradient joined the family: its output is twice as wide as its input.)
-inline int v6_grid(const ConvParams& p, int cin, int cout, long& grid) {
-    const long tiles = (long)((p.W + T6_W - 1) / T6_W) * ((p.H + T6_H - 1) / T6_H);
-    const long total = tiles * p.M;
-    HRN_CHECK(total > 0, -2, "conv3x3_v6: bad tile count %ld", total);
-    const int wide = cin > cout ? cin : cout;
-    if (total >= (1L << 30) || (long)p.H * p.W * (wide * 2) >= (1L << 31)) return -100;     // 32-bit tile / in-image byte arithmetic
-    grid = hrn_device_cus();
-    if (total < grid) grid = total;
-    if (grid >= 8) grid &= ~7L;
-    return 0;
-}
-
 }  // namespace
+
+// The instances <CIN, COUT, RESM, PAIR> both translation units have, as ROW(CIN, COUT, RESM, PAIR, the profiler name behind the dtype).
+// 128 input channels: COUT = 128 with no residual or the pair gather (res_mode 2), from a plain tensor or the pair gather; COUT = 64
+// with none or the alpha residual into the view stack (res_mode 3).  The training path's data gradients add 128 -> 128 with a plain
+// residual (res_mode 1: the gradient that bypasses the layer) and 64 -> 128 (the data gradient of a 128 -> 64 layer).
+#define V6_COMMON_ROWS(ROW)                   \
+    ROW(64, 128, 0, false, "64x128")          \
+    ROW(128, 128, 0, true, "128x128")         \
+    ROW(128, 128, 2, true, "128x128+res")     \
+    ROW(128, 128, 0, false, "128x128")        \
+    ROW(128, 128, 1, false, "128x128+res")    \
+    ROW(128, 128, 2, false, "128x128+res")    \
+    ROW(128, 64, 0, false, "128x64")          \
+    ROW(128, 64, 3, false, "128x64+res")

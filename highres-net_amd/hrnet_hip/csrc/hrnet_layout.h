@@ -64,13 +64,6 @@ static inline SiteParams site_params(const hrn_hrnet_params* P, int nl, int k) {
 static inline const unsigned char* at(const void* base, size_t off) { return (const unsigned char*)base + off; }
 static inline unsigned char* at(void* base, size_t off) { return (unsigned char*)base + off; }
 
-static inline ConvParams conv_base(int M, int H, int W) {
-    ConvParams p;
-    memset(&p, 0, sizeof p);
-    p.M = M; p.H = H; p.W = W;
-    return p;
-}
-
 // the packed weights, bias and slope (NULL without PReLU) of site k as a convolution launch reads them
 static inline void conv_site(ConvParams& p, const void* pk, const ConvSite& c) {
     p.wpk = at(pk, c.w); p.bias = (const float*)at(pk, c.b); p.slope = c.prelu ? (const float*)at(pk, c.a) : nullptr;

@@ -44,6 +44,15 @@ int hrn_kt_conv3x3_epi(int dt, int route, int cin, int cout, const void* in, con
                        int alpha_vs, void* out, int out_h, int out_vs, size_t in_lo, size_t stack_lo, size_t out_lo, size_t res_lo, int M,
                        int H, int W, void* stream);
 
+// The route hrn_kt_conv3x3_epi's launch would take, without launching: hrn_conv3x3_route alone, on the same arguments (no stream; the
+// pointers are only compared with NULL) plus the fields that hook does not reach - in_pair as ConvParams has it (hrn_kt_conv3x3_epi
+// derives it from in == NULL), scale, relu.  Writes the kernel family ("general" / "r64" / "v6" / "v6x3"), the profiler's family name
+// (both static strings) and the persistent grid; a descriptor outside ConvParams' contract is -2 with hrn_last_error() naming the field.
+int hrn_kt_conv_route(int dt, int route, int cin, int cout, const void* in, const void* stack, int pair_h, int pair_last, int pair_vs,
+                      const void* wpk, const float* bias, const float* slope, const void* res, int res_mode, int res_vs, const float* alphas,
+                      int alpha_vs, void* out, int out_h, int out_vs, size_t in_lo, size_t stack_lo, size_t out_lo, size_t res_lo, int M,
+                      int H, int W, int in_pair, const float* scale, int relu, const char** family, const char** prof_name, long* grid);
+
 // out [M][H][W][64] (dt) = the 2 -> 64 stem + PReLU (slope NULL: none) over channel 0 = image m of in0 (img_stride0 floats apart) and
 // channel 1 = image m / rep1 of in1, as hrn_launch_stem: sub == NULL reaches stem_mfma_kernel (bf16 / bf16x3), `sub` [M][2] the VALU
 // stem_kernel; out_lo: HRN_DTYPE_BF16X3's lo-plane byte offset

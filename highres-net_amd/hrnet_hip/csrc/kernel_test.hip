@@ -20,12 +20,23 @@ int hrn_kt_conv_dgrad(int dt, int cin, int cout, const float* w, const void* g, 
 
 int hrn_kt_conv3x3(int dt, int cin, int cout, const void* in, const void* stack, int pair_h, int pair_last, int pair_vs, const void* wpk,
                    const float* bias, void* out, int M, int H, int W, void* stream) {
-    ConvParams p;
-    memset(&p, 0, sizeof p);
-    p.M = M; p.H = H; p.W = W;
+    ConvParams p = conv_base(M, H, W);
     p.in = in; p.out = out; p.wpk = wpk; p.bias = bias;
     if (!in) { p.in_pair = 1; p.stack = stack; p.pair_h = pair_h; p.pair_last = pair_last; p.pair_vs = pair_vs; }
     return hrn_launch_conv3x3(dt, cin, cout, p, (hipStream_t)stream, false);
+}
+
+// the descriptor of hrn_kt_conv3x3_epi's arguments
+static ConvParams epi_params(const void* in, const void* stack, int pair_h, int pair_last, int pair_vs, const void* wpk, const float* bias,
+                             const float* slope, const void* res, int res_mode, int res_vs, const float* alphas, int alpha_vs, void* out,
+                             int out_h, int out_vs, size_t in_lo, size_t stack_lo, size_t out_lo, size_t res_lo, int M, int H, int W) {
+    ConvParams p = conv_base(M, H, W);
+    p.in = in; p.in_pair = in ? 0 : 1; p.stack = stack; p.pair_h = pair_h; p.pair_last = pair_last; p.pair_vs = pair_vs;
+    p.out = out; p.wpk = wpk; p.bias = bias; p.slope = slope;
+    p.res = res; p.res_mode = res_mode; p.res_vs = res_vs; p.alphas = alphas; p.alpha_vs = alpha_vs;
+    p.out_h = out_h; p.out_vs = out_vs;
+    p.in_lo = in_lo; p.stack_lo = stack_lo; p.out_lo = out_lo; p.res_lo = res_lo;
+    return p;
 }
 
 int hrn_kt_conv3x3_epi(int dt, int route, int cin, int cout, const void* in, const void* stack, int pair_h, int pair_last, int pair_vs,
@@ -33,15 +44,24 @@ int hrn_kt_conv3x3_epi(int dt, int route, int cin, int cout, const void* in, con
                        int alpha_vs, void* out, int out_h, int out_vs, size_t in_lo, size_t stack_lo, size_t out_lo, size_t res_lo, int M,
                        int H, int W, void* stream) {
     HRN_CHECK(route == 0 || route == 1, -2, "hrn_kt_conv3x3_epi: route %d", route);
-    ConvParams p;
-    memset(&p, 0, sizeof p);
-    p.M = M; p.H = H; p.W = W;
-    p.in = in; p.in_pair = in ? 0 : 1; p.stack = stack; p.pair_h = pair_h; p.pair_last = pair_last; p.pair_vs = pair_vs;
-    p.out = out; p.wpk = wpk; p.bias = bias; p.slope = slope;
-    p.res = res; p.res_mode = res_mode; p.res_vs = res_vs; p.alphas = alphas; p.alpha_vs = alpha_vs;
-    p.out_h = out_h; p.out_vs = out_vs;
-    p.in_lo = in_lo; p.stack_lo = stack_lo; p.out_lo = out_lo; p.res_lo = res_lo;
+    const ConvParams p = epi_params(in, stack, pair_h, pair_last, pair_vs, wpk, bias, slope, res, res_mode, res_vs, alphas, alpha_vs, out, out_h,
+                                    out_vs, in_lo, stack_lo, out_lo, res_lo, M, H, W);
     return hrn_launch_conv3x3(dt, cin, cout, p, (hipStream_t)stream, route == 1);
+}
+
+int hrn_kt_conv_route(int dt, int route, int cin, int cout, const void* in, const void* stack, int pair_h, int pair_last, int pair_vs,
+                      const void* wpk, const float* bias, const float* slope, const void* res, int res_mode, int res_vs, const float* alphas,
+                      int alpha_vs, void* out, int out_h, int out_vs, size_t in_lo, size_t stack_lo, size_t out_lo, size_t res_lo, int M,
+                      int H, int W, int in_pair, const float* scale, int relu, const char** family, const char** prof_name, long* grid) {
+    HRN_CHECK(route == 0 || route == 1, -2, "hrn_kt_conv_route: route %d", route);
+    ConvParams p = epi_params(in, stack, pair_h, pair_last, pair_vs, wpk, bias, slope, res, res_mode, res_vs, alphas, alpha_vs, out, out_h,
+                              out_vs, in_lo, stack_lo, out_lo, res_lo, M, H, W);
+    p.in_pair = in_pair; p.scale = scale; p.relu = relu;
+    ConvRoute r;
+    if (const int rc = hrn_conv3x3_route(dt, cin, cout, p, route == 1, r)) return rc;
+    static const char* const families[] = {"general", "r64", "v6", "v6x3"};      // ConvFamily
+    *family = families[r.family]; *prof_name = r.name; *grid = r.grid;
+    return 0;
 }
 
 int hrn_kt_stem(int dt, const float* in0, size_t img_stride0, const float* in1, int rep1, size_t img_stride1, const float* sub,
@@ -92,9 +112,7 @@ int hrn_kt_sn_bn_fold(const float* gamma, const float* beta, const float* rm, co
 }
 int hrn_kt_sn_conv_bn_relu(int cin, int cout, const float* in, const void* wpk, const float* scale, const float* shift, float* out, int M, int H,
                            int W, void* stream) {
-    ConvParams p;
-    memset(&p, 0, sizeof p);
-    p.M = M; p.H = H; p.W = W;
+    ConvParams p = conv_base(M, H, W);
     p.in = in; p.out = out;
     p.wpk = wpk; p.scale = scale; p.bias = shift; p.relu = 1;
     return hrn_launch_conv3x3(HRN_F32, cin, cout, p, (hipStream_t)stream, false);

@@ -39,9 +39,6 @@ struct TrainWs {
 // a fusion level's pair gather of its view stack (h pairs, partner of view v is last - v, vs views per sample); h == 0: a plain activation
 struct PairGather { int h, last, vs; };
 
-// bf16x3: a tensor of n elements is a pair of bf16 planes, the lo plane 2 n bytes behind the hi plane (0 for fp32 and bf16: one plane)
-inline size_t lo_of(int dt, size_t n) { return dt == HRN_BF16X3 ? n * 2 : 0; }
-
 int num_cus() { return hrn_device_cus(); }
 
 TrainWs train_ws(int nl, int B, int V, int H, int W) {
@@ -110,11 +107,11 @@ int conv_fwd(int dt, const void* pk, const ConvSite& c, const void* in, PairGath
     ConvParams p = conv_base(M, H, W);
     if (pg.h > 0) {
         p.in_pair = 1; p.stack = in; p.pair_h = pg.h; p.pair_last = pg.last; p.pair_vs = pg.vs;
-        p.stack_lo = lo_of(dt, (size_t)(M / pg.h) * pg.vs * hw * 64);
+        p.stack_lo = hrn_lo_of(dt, (size_t)(M / pg.h) * pg.vs * hw * 64);
     } else {
-        p.in = in; p.in_lo = lo_of(dt, (size_t)M * hw * c.cin);
+        p.in = in; p.in_lo = hrn_lo_of(dt, (size_t)M * hw * c.cin);
     }
-    p.out = y; p.out_lo = lo_of(dt, (size_t)M * hw * c.cout);
+    p.out = y; p.out_lo = hrn_lo_of(dt, (size_t)M * hw * c.cout);
     conv_site(p, pk, c);
     if (nonpos_slope) { p.slope = nullptr; p.only_if_nonpos = nonpos_slope; }
     return hrn_launch_conv3x3(dt, c.cin, c.cout, p, s, false);
@@ -238,10 +235,10 @@ int hrn_hrnet_backward_sel(const void* pk, int dt, int scale, const hrn_hrnet_pa
     const size_t nf = (size_t)B * L.n_in[L.T] * hw * 64;
     float* ff = (float*)at(tws, planes ? L.dec_f : L.stack[L.T]);
     float* fg = planes ? (float*)at(tws, L.dec_g) : (float*)dsn;
-    if (planes && (rc = hrn_launch_planes_to_f32(at(tws, L.stack[L.T]), lo_of(dt, nf), ff, nf, s))) return rc;
+    if (planes && (rc = hrn_launch_planes_to_f32(at(tws, L.stack[L.T]), hrn_lo_of(dt, nf), ff, nf, s))) return rc;
     if ((rc = hrn_launch_decoder_bwd(ff, d_sr, Pr->dec_w, Pr->dec_b, Pr->dec_a, Pr->fin_w, fg, mut(Gr->dec_w), mut(Gr->dec_b), mut(Gr->dec_a),
                                      mut(Gr->fin_w), mut(Gr->fin_b), B, H, W, sc, cus, s, scale))) return rc;
-    if (planes && need_ds[L.T] && (rc = hrn_launch_f32_to_planes(fg, dsn, lo_of(dt, nf), nf, s))) return rc;
+    if (planes && need_ds[L.T] && (rc = hrn_launch_f32_to_planes(fg, dsn, hrn_lo_of(dt, nf), nf, s))) return rc;
     if (!need_ds[L.T]) return 0;
 
     // ---- fusion levels, last to first                                                HRNet.py:113-132
@@ -324,7 +321,7 @@ int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alp
     if ((rc = hrn_launch_median(lrs, ref, B, V, H, W, s))) return rc;
     const ConvSite& stem = P.site[SITE_STEM];
     if ((rc = hrn_launch_stem(dt, lrs, hw, ref, V, hw, nullptr, (const float*)at(pk, stem.w), (const float*)at(pk, stem.b),
-                              (const float*)at(pk, stem.a), at(tws, L.a[0]), M, H, W, s, lo_of(dt, (size_t)M * hw * 64)))) return rc;
+                              (const float*)at(pk, stem.a), at(tws, L.a[0]), M, H, W, s, hrn_lo_of(dt, (size_t)M * hw * 64)))) return rc;
     for (int l = 0; l < nl; ++l) {
         if ((rc = conv_fwd(dt, pk, P.site[site_enc(l, 0)], at(tws, L.a[l]), {}, at(tws, L.h[l]), M, H, W, s))) return rc;
         if ((rc = conv_fwd(dt, pk, P.site[site_enc(l, 1)], at(tws, L.h[l]), {}, at(tws, L.r[l]), M, H, W, s))) return rc;
@@ -344,7 +341,7 @@ int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alp
     // views left after the last level: 1 (or V itself for V == 1); torch.mean over them (HRNet.py:134) is the identity
     return hrn_launch_decoder(dt, at(tws, L.stack[L.T]), at(pk, P.dec_w), (const float*)at(pk, P.dec_b), (const float*)at(pk, P.dec_a),
                               (const float*)at(pk, P.fin_w), (const float*)at(pk, P.fin_b), sr, B, H, W, s,
-                              lo_of(dt, (size_t)B * L.n_in[L.T] * hw * 64), scale);
+                              hrn_lo_of(dt, (size_t)B * L.n_in[L.T] * hw * 64), scale);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@ SIGNATURES = {
     "hrn_kt_conv_dgrad": (i, [i, i, i, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp]),
     "hrn_kt_conv3x3": (i, [i, i, i, vp, vp, i, i, i, vp, vp, vp, i, i, i, vp]),
     "hrn_kt_conv3x3_epi": (i, [i, i, i, i, vp, vp, i, i, i, vp, vp, vp, vp, i, i, vp, i, vp, i, i, sz, sz, sz, sz, i, i, i, vp]),
+    "hrn_kt_conv_route": (i, [i, i, i, i, vp, vp, i, i, i, vp, vp, vp, vp, i, i, vp, i, vp, i, i, sz, sz, sz, sz, i, i, i, i, vp, i, vp, vp, vp]),
     "hrn_kt_stem": (i, [i, vp, sz, vp, i, sz, vp, vp, vp, vp, vp, sz, i, i, i, vp]),
     "hrn_kt_decoder": (i, [i, i, vp, sz, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp]),
     "hrn_kt_conv_pack": (i, [i, i, i, vp, vp, vp]),

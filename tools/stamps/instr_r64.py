@@ -35,7 +35,7 @@ rep("        if (ph < ntl) lds_done_then_barrier();\n    }\n}", """        STAMP
     }
 }""")
 rep("if (gy < H && x0 + 16 * (pxb & 1) + 2 * h + lane_px < W) __builtin_nontemporal_store(", "if (gy < H && x0 + 16 * (pxb & 1) + 2 * h + lane_px < W && !(abl & 1)) __builtin_nontemporal_store(")
-rep("}  // namespace\n\n// bf16 64 -> 64 with a plain input", """}  // namespace
+rep("}  // namespace\n\nconst ConvTable& conv_table_r64()", """}  // namespace
 extern "C" int hrn_dbg_set_abl(int v) {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(hrn_r64_abl), &v, sizeof(int), 0, hipMemcpyHostToDevice);
 }
@@ -43,5 +43,5 @@ extern "C" int hrn_dbg_read_stamps(void* dst, size_t bytes) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(hrn_r64_stamps), bytes, 0, hipMemcpyDeviceToHost);
 }
 
-// bf16 64 -> 64 with a plain input""")
+const ConvTable& conv_table_r64()""")
 open(fn, "w").write(s)
