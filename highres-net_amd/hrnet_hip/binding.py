@@ -143,6 +143,8 @@ SIGNATURES = {
     "hrn_shift_loss_backward": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 6 + [_c.c_void_p, _c.c_void_p]),
     "hrn_shift_cssim_workspace_bytes": (_c.c_size_t, [_c.c_int] * 5),
     "hrn_shift_cssim": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 7 + [_c.c_float] + [_c.c_void_p] * 4 + [_c.c_size_t, _c.c_void_p]),
+    "hrn_cssim_loss_backward_workspace_bytes": (_c.c_size_t, [_c.c_int] * 5),
+    "hrn_cssim_loss_backward": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 7 + [_c.c_float] + [_c.c_void_p] * 2 + [_c.c_size_t, _c.c_void_p]),
     "hrn_mncc_grid": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 5 + [_c.c_float, _c.c_void_p, _c.c_void_p]),
     "hrn_mncc_search": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_mncc_apply": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 4 + [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
@@ -920,11 +922,8 @@ def shift_loss_backward(srs, hrs, hr_maps, stats, d_out, metric="cPSNR", border_
 CSSIM_WINDOWS = {"gaussian": (0, 11), "uniform": (1, 7)}      # name -> (hrn_shift_cssim's `window`, taps)
 
 
-def shift_cssim(srs, hrs, hr_maps, border_w=3, window="gaussian", clip=True, correct_bias=True, data_range=1.0):
-    """The shift-searched, brightness-corrected SSIM (include/hrnet_hip.h, DESIGN.md section 7k) on (B,H,W) frames: -> (out (B,) f32,
-    stats (B,4) f64 = {n, bias, score, k} of the selected offset k = u (2 border_w + 1) + v, scores (B, (2 border_w + 1)^2) f64 =
-    the score of every offset, -inf where an offset has no clear pixel)."""
-    lib = load_library()
+def _cssim_args(srs, hrs, hr_maps, border_w, window, data_range):
+    """the checks of the cSSIM entry points -> (srs, hrs, hr_maps as dense f32, border_w, hrn_shift_cssim's window code, data_range)"""
     if window not in CSSIM_WINDOWS:
         raise ValueError(f"window must be one of {sorted(CSSIM_WINDOWS)}; got {window!r}")
     code, taps = CSSIM_WINDOWS[window]
@@ -937,16 +936,46 @@ def shift_cssim(srs, hrs, hr_maps, border_w=3, window="gaussian", clip=True, cor
                          f"frames {tuple(srs.shape[1:])}")
     if not data_range > 0.0:
         raise ValueError(f"data_range must be positive; got {data_range}")
+    return srs, hrs, hr_maps, border_w, code, data_range
+
+
+def shift_cssim(srs, hrs, hr_maps, border_w=3, window="gaussian", clip=True, correct_bias=True, data_range=1.0, with_scores=True):
+    """The shift-searched, brightness-corrected SSIM (include/hrnet_hip.h, DESIGN.md section 7k) on (B,H,W) frames: -> (out (B,) f32,
+    stats (B,4) f64 = {n, bias, score, k} of the selected offset k = u (2 border_w + 1) + v, scores (B, (2 border_w + 1)^2) f64 =
+    the score of every offset, -inf where an offset has no clear pixel).  with_scores=False: scores = NULL to the same kernels, and
+    None here."""
+    lib = load_library()
+    srs, hrs, hr_maps, border_w, code, data_range = _cssim_args(srs, hrs, hr_maps, border_w, window, data_range)
     B, H, W = srs.shape
     nk = (2 * border_w + 1) ** 2
     out = torch.empty((B,), dtype=torch.float32, device=srs.device)
     stats = torch.empty((B, 4), dtype=torch.float64, device=srs.device)
-    scores = torch.empty((B, nk), dtype=torch.float64, device=srs.device)
+    scores = torch.empty((B, nk), dtype=torch.float64, device=srs.device) if with_scores else None
     with torch.cuda.device(srs.device):
         ws = _workspace(lib.hrn_shift_cssim_workspace_bytes(B, H, W, border_w, code), srs.device, "shift_cssim")
         _check(lib.hrn_shift_cssim(_ptr(srs), _ptr(hrs), _ptr(hr_maps), B, H, W, border_w, code, int(bool(clip)), int(bool(correct_bias)),
-                                   data_range, _ptr(out), _ptr(stats), _ptr(scores), _ptr(ws), ws.numel(), _stream()), "hrn_shift_cssim")
+                                   data_range, _ptr(out), _ptr(stats), _ptr(scores) if with_scores else None, _ptr(ws), ws.numel(),
+                                   _stream()), "hrn_shift_cssim")
     return out, stats, scores
+
+
+def cssim_loss_backward(srs, hrs, hr_maps, stats, d_out, border_w=3, window="gaussian", clip=False, correct_bias=True, data_range=1.0):
+    """d_out (B,) -> d_srs (B,H,W): d_out[b] times the gradient of the cSSIM score through the offset `stats` selected, the bias attached
+    (include/hrnet_hip.h); zero on the border frame, on masked pixels, where clip clamped and for a sample without
+    an eligible offset."""
+    lib = load_library()
+    srs, hrs, hr_maps, border_w, code, data_range = _cssim_args(srs, hrs, hr_maps, border_w, window, data_range)
+    d_out = _dev_f32(d_out, "d_out")
+    B, H, W = srs.shape
+    if tuple(stats.shape) != (B, 4) or stats.dtype != torch.float64 or tuple(d_out.shape) != (B,):
+        raise ValueError(f"stats must be ({B}, 4) float64 and d_out ({B},); got {tuple(stats.shape)} {stats.dtype}, {tuple(d_out.shape)}")
+    d_srs = torch.empty_like(srs)
+    with torch.cuda.device(srs.device):
+        ws = _workspace(lib.hrn_cssim_loss_backward_workspace_bytes(B, H, W, border_w, code), srs.device, "cssim_loss_backward")
+        _check(lib.hrn_cssim_loss_backward(_ptr(srs), _ptr(hrs), _ptr(hr_maps), _ptr(stats.contiguous()), _ptr(d_out), B, H, W, border_w,
+                                           code, int(bool(clip)), int(bool(correct_bias)), data_range, _ptr(d_srs), _ptr(ws), ws.numel(),
+                                           _stream()), "hrn_cssim_loss_backward")
+    return d_srs
 
 
 # --------------------------------------------------------------------------- sub-pixel registration of LR views.  Four files, one per
@@ -1629,6 +1658,48 @@ def _(srs, hrs, hr_maps, border_w, window, clip, correct_bias, data_range):
     B = srs.shape[0]
     return (srs.new_empty((B,), dtype=torch.float32), srs.new_empty((B, 4), dtype=torch.float64),
             srs.new_empty((B, (2 * border_w + 1) ** 2), dtype=torch.float64))
+
+
+# cSSIM as a loss: the same forward without the per-offset scores, and the gradient through the selected offset.
+@torch.library.custom_op("hrnet_hip::shift_cssim_train", mutates_args=(), device_types="cuda")
+def _op_shift_cssim_train(srs: torch.Tensor, hrs: torch.Tensor, hr_maps: torch.Tensor, border_w: int, window: str, clip: bool,
+                          correct_bias: bool, data_range: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The shift-searched SSIM, differentiable in srs: (score per sample (B,), stats (B,4) f64 = {n, bias, score, k})."""
+    return shift_cssim(srs, hrs, hr_maps, border_w, window, clip, correct_bias, data_range, with_scores=False)[:2]
+
+
+@_op_shift_cssim_train.register_fake
+def _(srs, hrs, hr_maps, border_w, window, clip, correct_bias, data_range):
+    return srs.new_empty((srs.shape[0],), dtype=torch.float32), srs.new_empty((srs.shape[0], 4), dtype=torch.float64)
+
+
+@torch.library.custom_op("hrnet_hip::cssim_loss_backward", mutates_args=(), device_types="cuda")
+def _op_cssim_loss_backward(srs: torch.Tensor, hrs: torch.Tensor, hr_maps: torch.Tensor, stats: torch.Tensor, d_out: torch.Tensor,
+                            border_w: int, window: str, clip: bool, correct_bias: bool, data_range: float) -> torch.Tensor:
+    return cssim_loss_backward(srs, hrs, hr_maps, stats, d_out.contiguous(), border_w, window, clip, correct_bias, data_range)
+
+
+@_op_cssim_loss_backward.register_fake
+def _(srs, hrs, hr_maps, stats, d_out, border_w, window, clip, correct_bias, data_range):
+    return srs.new_empty(srs.shape, dtype=torch.float32)
+
+
+def _cssim_loss_setup(ctx, inputs, output):
+    srs, hrs, hr_maps, ctx.border_w, ctx.window, ctx.clip, ctx.correct_bias, ctx.data_range = inputs
+    ctx.save_for_backward(srs, hrs, hr_maps, output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _cssim_loss_backward(ctx, d_out, _d_stats):
+    srs, hrs, hr_maps, stats = ctx.saved_tensors
+    if d_out is None:
+        return (None,) * 8
+    d_srs = torch.ops.hrnet_hip.cssim_loss_backward(srs, hrs, hr_maps, stats, d_out, ctx.border_w, ctx.window, ctx.clip, ctx.correct_bias,
+                                                    ctx.data_range)
+    return (d_srs,) + (None,) * 7                       # the targets and their status maps get no gradient
+
+
+_op_shift_cssim_train.register_autograd(_cssim_loss_backward, setup_context=_cssim_loss_setup)
 
 
 # The registration search has no autograd formula: a shift found by a grid search is piecewise constant in the frames.

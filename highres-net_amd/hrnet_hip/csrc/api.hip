@@ -469,6 +469,25 @@ int hrn_shift_cssim(const float* srs, const float* hrs, const float* maps, int B
                                   (hipStream_t)stream);
 }
 
+// cSSIM as a loss (cssim_bwd.hip): the gradient through the offset the forward selected
+size_t hrn_cssim_loss_backward_workspace_bytes(int B, int H, int W, int border, int window) {
+    if (hrn_shift_cssim_workspace_bytes(B, H, W, border, window) == 0) return 0;       // the same arguments are refused
+    return hrn_cssim_loss_backward_workspace_bytes_impl(B, H, W, border, window);
+}
+
+int hrn_cssim_loss_backward(const float* srs, const float* hrs, const float* maps, const double* stats, const float* d_out, int B, int H,
+                            int W, int border, int window, int clip, int correct_bias, float data_range, float* d_srs, void* ws,
+                            size_t ws_bytes, void* stream) {
+    if (int rc = shift_cssim_check("hrn_cssim_loss_backward", B, H, W, border, window)) return rc;
+    HRN_CHECK(data_range > 0.f && data_range <= 3.0e38f, -2, "hrn_cssim_loss_backward: data_range must be positive and finite (got %g)",
+              (double)data_range);
+    HRN_CHECK(srs && hrs && maps && stats && d_out && d_srs && ws, -2, "hrn_cssim_loss_backward: null argument");
+    HRN_CHECK(ws_bytes >= hrn_cssim_loss_backward_workspace_bytes_impl(B, H, W, border, window), -3,
+              "hrn_cssim_loss_backward: workspace too small");
+    return hrn_launch_cssim_loss_backward(srs, hrs, maps, stats, d_out, B, H, W, border, window, clip != 0, correct_bias != 0, data_range,
+                                          d_srs, ws, (hipStream_t)stream);
+}
+
 // the masked-NCC registration search (registration.hip): the reference fork's recursive_mncc_search / compute_grid_mncc, restated
 //
 // Every limit of a registration problem is stated once, in a check that takes the entry point's name `who`.  A size query runs its entry

@@ -63,6 +63,13 @@ int hrn_launch_shift_cssim(const float* srs, const float* hrs, const float* maps
                            int correct_bias, float data_range, float* out, double* stats, double* scores, void* workspace,
                            hipStream_t stream);
 
+// ---- cssim_bwd.hip: the gradient of that score with respect to srs through the offset k* of `stats`, the bias attached (DESIGN.md
+// section 7l).  d_srs [B][H][W], every element written.  The callers have checked the arguments.
+size_t hrn_cssim_loss_backward_workspace_bytes_impl(int B, int H, int W, int border, int window);
+int hrn_launch_cssim_loss_backward(const float* srs, const float* hrs, const float* maps, const double* stats, const float* d_out, int B,
+                                   int H, int W, int border, int window, int clip, int correct_bias, float data_range, float* d_srs,
+                                   void* workspace, hipStream_t stream);
+
 // ---- registration.hip: the masked-NCC sub-pixel registration of LR views (the definitions are in
 // include/hrnet_hip.h).  One workgroup per view; a mask pointer may be null (all ones); the callers have checked the limits below.
 constexpr int HRN_MNCC_MIN_SIDE = 16, HRN_MNCC_MAX_SIDE = 128;     // a view, its row-pass buffer and its mask patterns fit one CU's LDS

@@ -14,7 +14,11 @@ and aspect ratio, and is bit-reproducible: the training tail that needs no Shift
 
 `shift_cssim(srs, hrs, hr_maps, border_w, clip, window, data_range, correct_bias)` is the second score: structural similarity between the
 clear pixels of the target and the brightness-corrected prediction, searched over the same offsets (`torch.ops.hrnet_hip.shift_cssim`
-over `hrn_shift_cssim`).  It is a score, not a loss: it has no gradient."""
+over `hrn_shift_cssim`).  It is a score: it has no gradient.
+
+`cssim_loss(srs, hrs, hr_maps, border_w, clip, window, data_range, correct_bias)` is that score as a loss, 1 - cSSIM per sample,
+differentiable through the selected offset with the brightness bias attached (`torch.ops.hrnet_hip.shift_cssim_train` /
+`.cssim_loss_backward` over `hrn_shift_cssim` / `hrn_cssim_loss_backward`)."""
 import torch
 
 from . import binding
@@ -64,15 +68,8 @@ def shift_loss(srs, hrs, hr_maps, metric="cPSNR", border_w=3, clip=False, return
     return out, torch.stack([torch.div(k, nb, rounding_mode="floor") - border_w, k % nb - border_w], 1)
 
 
-def shift_cssim(srs, hrs, hr_maps, border_w=3, clip=True, window="gaussian", data_range=1.0, correct_bias=True, return_shift=False,
-                return_scores=False):
-    """(B,H,W) x 3 -> (B,): the highest SSIM over the integer offsets (u - border_w, v - border_w), |.| <= border_w, between m hrs and
-    m (srs + bias) on the centre crop of `srs`, m the clear pixels of the offset and bias its brightness correction (0 without
-    correct_bias).  window: "gaussian" (11 taps, sigma 1.5) or "uniform" (7 taps, sample covariance), over the positions where the
-    window fits; data_range: the L of C1 = (0.01 L)^2, C2 = (0.03 L)^2.  clip clamps srs to [0, 1] first.  A (B,1,H,W) `srs` is taken as
-    srs[:, 0].  No gradient.  return_shift: also the (B,2) int64 offsets (row, column) selected, as shift_loss returns them (a
-    (-border_w - 1, ...) row marks a sample without an eligible offset, whose score is NaN).  return_scores: also the (B, (2 border_w
-    + 1)^2) float64 score of every offset, -inf where the offset has no clear pixel."""
+def _cssim_inputs(srs, hrs, hr_maps, border_w, window, data_range):
+    """the argument checks of the two cSSIM wrappers -> (srs (B,H,W), border_w, data_range)"""
     for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
         if not torch.is_tensor(t):
             raise TypeError(f"{name} must be a torch.Tensor; got {type(t).__name__}")
@@ -92,14 +89,49 @@ def shift_cssim(srs, hrs, hr_maps, border_w=3, clip=True, window="gaussian", dat
     for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
         if not t.is_cuda:
             raise TypeError(f"{name} is on '{t.device}': the searched score runs on a ROCm device only (no CPU fallback)")
+    return srs, border_w, data_range
+
+
+def _shift_of(stats, border_w):
+    """stats' k -> the (B,2) int64 offsets (row, column), as shift_loss returns them"""
+    k = stats[:, 3].detach().long()
+    nb = 2 * border_w + 1
+    return torch.stack([torch.div(k, nb, rounding_mode="floor") - border_w, k % nb - border_w], 1)
+
+
+def shift_cssim(srs, hrs, hr_maps, border_w=3, clip=True, window="gaussian", data_range=1.0, correct_bias=True, return_shift=False,
+                return_scores=False):
+    """(B,H,W) x 3 -> (B,): the highest SSIM over the integer offsets (u - border_w, v - border_w), |.| <= border_w, between m hrs and
+    m (srs + bias) on the centre crop of `srs`, m the clear pixels of the offset and bias its brightness correction (0 without
+    correct_bias).  window: "gaussian" (11 taps, sigma 1.5) or "uniform" (7 taps, sample covariance), over the positions where the
+    window fits; data_range: the L of C1 = (0.01 L)^2, C2 = (0.03 L)^2.  clip clamps srs to [0, 1] first.  A (B,1,H,W) `srs` is taken as
+    srs[:, 0].  No gradient (`cssim_loss` is the differentiable form).  return_shift: also the (B,2) int64 offsets (row, column)
+    selected, as shift_loss returns them (a (-border_w - 1, ...) row marks a sample without an eligible offset, whose score is NaN).
+    return_scores: also the (B, (2 border_w + 1)^2) float64 score of every offset, -inf where the offset has no clear pixel."""
+    srs, border_w, data_range = _cssim_inputs(srs, hrs, hr_maps, border_w, window, data_range)
     out, stats, scores = torch.ops.hrnet_hip.shift_cssim(srs.detach().float().contiguous(), hrs.float().contiguous(),
                                                          hr_maps.float().contiguous(), border_w, window, bool(clip), bool(correct_bias),
                                                          data_range)
     res = [out]
     if return_shift:
-        k = stats[:, 3].long()
-        nb = 2 * border_w + 1
-        res.append(torch.stack([torch.div(k, nb, rounding_mode="floor") - border_w, k % nb - border_w], 1))
+        res.append(_shift_of(stats, border_w))
     if return_scores:
         res.append(scores)
     return res[0] if len(res) == 1 else tuple(res)
+
+
+def cssim_loss(srs, hrs, hr_maps, border_w=3, clip=False, window="gaussian", data_range=1.0, correct_bias=True, return_shift=False):
+    """(B,H,W) x 3 -> (B,): 1 - cSSIM per sample, to be minimised; `shift_cssim`'s arguments, checks and search (clip defaults to False,
+    as in shift_loss).  With grad enabled and a gradient-requiring `srs` the result is differentiable through the selected offset, the
+    brightness bias attached (`torch.ops.hrnet_hip.shift_cssim_train` / `.cssim_loss_backward`; no gradient to
+    hrs / hr_maps); without either it is 1 - shift_cssim(...), the same bits.  The loss is piecewise in the offset, and NaN, with a zero
+    gradient, for a sample without an eligible offset.  return_shift: also the (B,2) int64 offsets selected, as in shift_loss."""
+    srs, border_w, data_range = _cssim_inputs(srs, hrs, hr_maps, border_w, window, data_range)
+    srs = srs if srs.dtype == torch.float32 else srs.float()
+    if torch.is_grad_enabled() and srs.requires_grad:
+        out, stats = torch.ops.hrnet_hip.shift_cssim_train(srs.contiguous(), hrs.float().contiguous(), hr_maps.float().contiguous(), border_w,
+                                                           window, bool(clip), bool(correct_bias), data_range)
+    else:
+        out, stats, _ = binding.shift_cssim(srs.detach(), hrs, hr_maps, border_w, window, clip, correct_bias, data_range, with_scores=False)
+    loss = 1.0 - out
+    return (loss, _shift_of(stats, border_w)) if return_shift else loss

@@ -21,6 +21,8 @@
  *   hrn_adam_step          <-  optimizer.step() of torch.optim.Adam   src/train.py:191, :252
  *   hrn_get_loss / hrn_shift_cpsnr  <-  get_loss (train.py:66-87) / shift_cPSNR (Evaluator.py:52-73)
  *   hrn_shift_loss_train / hrn_shift_loss_backward  <-  the two combined as a differentiable loss (the searched score, trainable)
+ *   hrn_shift_cssim / hrn_cssim_loss_backward  <-  (no counterpart: the project's second score) the shift-searched, brightness-corrected
+ *                              SSIM, and its gradient through the selected offset: cSSIM as a training loss
  *   hrn_mncc_grid / hrn_mncc_search / hrn_mncc_apply  <-  the method of the fork's registration_search.py (recursive_mncc_search over
  *                              compute_grid_mncc), restated: sub-pixel registration of the LR views against a reference frame;
  *                              hrn_mncc_grid_scene / hrn_mncc_search_scene / hrn_mncc_apply_scene: the same for frames of any size;
@@ -338,6 +340,27 @@ size_t hrn_shift_cssim_workspace_bytes(int B, int H, int W, int border, int wind
 int hrn_shift_cssim(const float* srs, const float* hrs, const float* hr_maps, int B, int H, int W, int border, int window, int clip,
                     int correct_bias, float data_range, float* out, double* stats, double* scores, void* workspace,
                     size_t workspace_bytes, void* stream);
+/* cSSIM as a training loss: the gradient of score_k* with respect to srs, with k* HELD FIXED (as hrn_shift_loss_backward holds it) and the
+ * bias ATTACHED (unlike the cMSE its term does not cancel: this is the derivative of the number hrn_shift_cssim returns).  The forward of
+ * the loss is hrn_shift_cssim itself (scores may be NULL); `stats` is its (B,4) {n*, bias*, score*, k*}.  With s, g, m, n = n*, b = bias*
+ * at k*, X = m g, Y = m (s + b), Np = (h - T + 1)(w - T + 1) and, per map pixel, a = mu_x, c = mu_y:
+ *   A1 = 2ac + C1,  A2 = 2 v_xy + C2,  B1 = a^2 + c^2 + C1,  B2 = v_x + v_y + C2,
+ *   S_c = 2a A2/(B1 B2) - 2c A1 A2/(B1^2 B2),   S_vy = -A1 A2/(B1 B2^2),   S_vxy = 2 A1/(B1 B2),
+ *   beta = 2 cov_norm S_vy,   gamma = cov_norm S_vxy,   alpha = S_c - beta c - gamma a,
+ *   D_q = [ (G^T alpha)_q + Y_q (G^T beta)_q + X_q (G^T gamma)_q ] / Np     for a crop pixel q,
+ *   M   = sum_q m_q D_q / n   (0 when correct_bias == 0),
+ *   d score / d srs[border + y, border + x] = pass m (D - M),
+ * G^T the adjoint of the "valid" window (the map-sized field, zero outside the map, correlated with the same taps back onto the h x w
+ * crop) and pass = 1 where torch.clamp passes a gradient (0 <= s <= 1 before clamping), or everywhere when clip == 0.
+ * hrn_cssim_loss_backward  <-  autograd through that score: d_srs (B,H,W), every element written = d_out[b] times the above; exactly 0 on
+ *                              the border frame, where clip clamped s, on masked pixels and for a sample without an eligible offset
+ *                              (k* = -1).  No gradient to hrs / hr_maps.  fp32 filters, fp64 sums in a fixed order, no atomics:
+ *                              bit-reproducible, and a sample's gradient does not depend on the batch around it.
+ * hrn_cssim_loss_backward_workspace_bytes: the tiles' fp64 sums (0 for arguments the entry point refuses). */
+size_t hrn_cssim_loss_backward_workspace_bytes(int B, int H, int W, int border, int window);
+int hrn_cssim_loss_backward(const float* srs, const float* hrs, const float* hr_maps, const double* stats, const float* d_out, int B, int H,
+                            int W, int border, int window, int clip, int correct_bias, float data_range, float* d_srs, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ sub-pixel registration of LR views: a masked-NCC grid search
  * The method of the reference fork's registration_search.py / registration_metrics.py (compute_shift_ncc -> recursive_mncc_search ->

@@ -18,7 +18,19 @@ of the counted arithmetic - 12 T + 40 flops per (map pixel, offset): three field
 the 157.3 TFLOP/s fp32 vector peak of an MI355X, the ratio to the torch composition, and the largest |difference| between the two
 paths' scores, taken before anything is timed.  There is no pass / fail threshold on time.
 
+--backward times the gradient of the score as a loss instead, again call by call in one process:
+
+    cssim_bwd_tile     the backward's tile kernel: six fields filtered at the selected offset, alpha', beta, gamma per map pixel, the
+                       three filtered back, the raw D and the fp64 sums of m D
+    cssim_bwd_finish   the mean M and the elementwise pass that writes d_srs
+    cssim_tile         the forward's tile kernel in the same calls, the 49 offsets the backward does not walk
+    torch              torch autograd (forward and backward) through the composition of the ONE offset the forward selected
+
+and prints the backward beside the forward's tile kernel and beside torch, and the largest |difference| of the two gradients over
+the largest |gradient|.
+
 usage: python tools/cssim_bench.py [B] [--sizes S[,S...]] [--border W] [--windows gaussian,uniform] [--rounds R] [--reps N] [--torch-reps N]
+                                   [--backward]
 """
 import _common
 import torch
@@ -27,10 +39,12 @@ from _common import LLC_BYTES
 from hrnet_hip import binding
 
 FAMILIES = ("cssim_pre", "cssim_tile", "cssim_finish")
+BWD_FAMILIES = ("cssim_bwd_tile", "cssim_bwd_finish")
 FP32_VECTOR_PEAK = 157.3e12          # flop / s
 
-PARSER = _common.parser(__doc__, positional=dict(B=32), sizes=[192, 384], border=3, windows=["gaussian", "uniform"], rounds=5, reps=10,
-                        torch_reps=2)
+OPTIONS = dict(positional=dict(B=32), sizes=[192, 384], border=3, windows=["gaussian", "uniform"], rounds=5, reps=10, torch_reps=2)
+PARSER = _common.parser(__doc__, **OPTIONS)                          # what a measurement of either mode takes
+CLI = _common.parser(__doc__, backward=False, **OPTIONS)             # the command line: those, and the switch between the modes
 
 
 def taps_of(window, device):
@@ -73,6 +87,85 @@ def torch_cssim(srs, hrs, maps, border, taps, cov_norm, data_range=1.0):
             ssim = ((2 * mx * my + c1) * (2 * vxy + c2)) / ((mx * mx + my * my + c1) * (vx + vy + c2))
             scores.append(torch.where(n > 0, ssim.mean((1, 2)), torch.full_like(n, float("-inf"))))
     return torch.stack(scores, 1)
+
+
+def torch_cssim_at(srs, hrs, maps, k, border, taps, cov_norm, data_range=1.0):
+    """(B,) fp32 scores at the offsets k (B,) int64, differentiable in srs, no clamp: what a user writes to train on the score once the
+    offset is known"""
+    B, H, W = srs.shape
+    h, w, nb = H - 2 * border, W - 2 * border, 2 * border + 1
+    c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    s = srs[:, border:border + h, border:border + w]
+    at = lambda t: torch.stack([t[b, int(k[b]) // nb:int(k[b]) // nb + h, int(k[b]) % nb:int(k[b]) % nb + w] for b in range(B)])
+    g, m = at(hrs), (at(maps) != 0).float()
+    bias = (m * (g - s)).sum((1, 2)) / m.sum((1, 2))
+    X, Y = m * g, m * (s + bias[:, None, None])
+    mx, my = filt(X, taps), filt(Y, taps)
+    vx = cov_norm * (filt(X * X, taps) - mx * mx)
+    vy = cov_norm * (filt(Y * Y, taps) - my * my)
+    vxy = cov_norm * (filt(X * Y, taps) - mx * my)
+    return (((2 * mx * my + c1) * (2 * vxy + c2)) / ((mx * mx + my * my + c1) * (vx + vy + c2))).mean((1, 2))
+
+
+def bench_backward(B, S, border, window, rounds, reps, torch_reps):
+    dev = torch.device("cuda:0")
+    nsets = max(2, -(-2 * LLC_BYTES // (16 * B * S * S)))
+    gen = torch.Generator(device=dev).manual_seed(S)
+    sets = []
+    for _ in range(nsets):
+        hrs = torch.rand((B, S, S), device=dev, generator=gen)
+        srs = 0.9 * hrs + 0.03 + 0.02 * torch.randn((B, S, S), device=dev, generator=gen)
+        maps = (torch.rand((B, S, S), device=dev, generator=gen) > 0.15).float()
+        sets.append((srs, hrs, maps))
+    taps, cov_norm = taps_of(window, dev)
+    T = len(taps)
+    d_out = torch.ones((B,), device=dev)
+    kw = dict(border_w=border, window=window, clip=False)
+
+    def fused(i):
+        x = sets[i % nsets]
+        _, stats, _ = binding.shift_cssim(*x, with_scores=False, **kw)
+        return stats, binding.cssim_loss_backward(*x, stats, d_out, **kw)
+
+    def composed(i, k):
+        srs, hrs, maps = sets[i % nsets]
+        s = srs.detach().requires_grad_(True)
+        torch_cssim_at(s, hrs, maps, k, border, taps, cov_norm).sum().backward()
+        return s.grad
+
+    ks = [fused(i)[0][:, 3].long().cpu() for i in range(nsets)]     # read back once, before anything is timed
+    want = composed(0, ks[0])
+    worst = float((fused(0)[1] - want).abs().max() / want.abs().max())
+    torch.cuda.synchronize()
+    names = BWD_FAMILIES + ("cssim_tile",)
+    per_round = {f: [] for f in names + ("torch",)}
+    for r in range(rounds):
+        binding.profile_enable(True)
+        spent = []
+        for i in range(reps):
+            fused(r * reps + i)
+            if i < torch_reps:
+                spent.append(_common.timed_us(lambda: composed(r * reps + i, ks[(r * reps + i) % nsets]), 1))
+        torch.cuda.synchronize()
+        rec = binding.profile_read()
+        binding.profile_enable(False)
+        for f in names:
+            per_round[f].append(rec[f]["ms"] * 1e3 / rec[f]["launches"])
+        per_round["torch"].append(sum(spent) / len(spent))
+    res = {"mode": "backward", "B": B, "S": S, "border": border, "window": window, "taps": T, "input_sets": nsets, "rounds": rounds,
+           "reps": reps, "torch_reps": torch_reps, "max_rel_diff_vs_torch": worst}
+    print(f"backward B={B} {S}x{S} border {border} {window} ({T} taps): median of {rounds} rounds x {reps} calls over {nsets} input sets "
+          f"(fused vs torch autograd: max |difference| {worst:.1e} of the max |gradient|)")
+    for f in per_round:
+        med, lo, hi = _common.spread(per_round[f])
+        res[f] = {"median_us": med, "min_us": lo, "max_us": hi}
+        print(f"    {f:17s} {med:11.1f} us   (min {lo:.1f}, max {hi:.1f})")
+    total = sum(res[f]["median_us"] for f in BWD_FAMILIES)
+    res.update(backward_us=total, backward_over_forward_tile=total / res["cssim_tile"]["median_us"],
+               torch_over_backward=res["torch"]["median_us"] / total, ns_per_pixel=total * 1e3 / (B * S * S))
+    print(f"    backward total {total:.1f} us = {res['ns_per_pixel'] * 1e3:.1f} ps per pixel = {res['backward_over_forward_tile']:.3f} x the "
+          f"forward's cssim_tile;  torch autograd at the selected offset / backward: {res['torch_over_backward']:.1f} x")
+    return res
 
 
 def bench(B, S, border, window, rounds, reps, torch_reps):
@@ -129,9 +222,10 @@ def bench(B, S, border, window, rounds, reps, torch_reps):
 
 
 def main():
-    o = PARSER.parse_args()
+    o = CLI.parse_args()
     _common.require_gpu("cssim_bench")
-    _common.emit("cssim_bench", [bench(o.B, S, o.border, w, o.rounds, o.reps, o.torch_reps) for S in o.sizes for w in o.windows])
+    run = bench_backward if o.backward else bench
+    _common.emit("cssim_bench", [run(o.B, S, o.border, w, o.rounds, o.reps, o.torch_reps) for S in o.sizes for w in o.windows])
 
 
 if __name__ == "__main__":

@@ -17,7 +17,8 @@ alternate in one process like the precisions.  --scale K (2, 3 or 4; default 3) 
 initialised for K != 3, on the seeded x3 encoder and fusion block) and K S x K S targets; K * S must reach ShiftNet's 128-pixel window.
 --loss picks the tail of the step: shiftnet (default) is the reference's ShiftNet -> Lanczos -> cPSNR above; shift is the searched loss,
 loss = -shift_loss(srs, hrs, hr_maps) (hrnet_hip.losses): no ShiftNet is built, the optimiser holds HRNet's parameters
-only, and the 128-pixel window does not apply.  Several values alternate in one process like the precisions.
+only, and the 128-pixel window does not apply; cssim is the second score as a loss, loss = mean(cssim_loss(srs, hrs, hr_maps)) (DESIGN.md
+section 7l), HRNet alone as for shift.  Several values alternate in one process like the precisions.
 """
 import copy
 import time
@@ -29,7 +30,7 @@ import torch
 from oracle import synth, weights            # seeded weights / synthetic inputs only (no oracle arithmetic on the path)
 from DeepNetworks.HRNet import HRNet
 from DeepNetworks.ShiftNet import ShiftNet
-from hrnet_hip.losses import shift_loss
+from hrnet_hip.losses import cssim_loss, shift_loss
 from hrnet_hip.optim import FusedAdam
 
 
@@ -58,6 +59,8 @@ def _label(key):
             + (f" loss={ls}" if ls != "shiftnet" else ""))
 
 
+SEARCHED = {"shift": lambda srs, hrs, maps: -shift_loss(srs, hrs, maps), "cssim": cssim_loss}       # --loss -> the loss per sample
+
 PARSER = _common.parser(__doc__, group=("B V S steps", (32, 32, 64, 5)), torch_adam=False, precision=[None], shiftnet_precision=[None], repeats=1,
                         freeze=["none"], scale=3, loss=["shiftnet"])      # scale: decoder stride and HR / LR ratio of the targets
 
@@ -65,7 +68,7 @@ PARSER = _common.parser(__doc__, group=("B V S steps", (32, 32, 64, 5)), torch_a
 def options(argv=None):
     o = PARSER.parse_args(argv)
     for flag, got, allowed in (("--freeze", o.freeze, tuple(FREEZE)), ("--precision", o.precision, (None, "fp32", "bf16x3", "bf16")),
-                               ("--shiftnet-precision", o.shiftnet_precision, (None, "fp32", "bf16")), ("--loss", o.loss, ("shiftnet", "shift"))):
+                               ("--shiftnet-precision", o.shiftnet_precision, (None, "fp32", "bf16")), ("--loss", o.loss, ("shiftnet", "shift", "cssim"))):
         for v in got:
             if v not in allowed:
                 PARSER.error(f"{flag}: {', '.join(a for a in allowed if a)} (got {v!r})")
@@ -98,12 +101,12 @@ def main():
             state = {k: v for k, v in state.items() if not k.startswith("decode.")}
         fusion.load_state_dict(state, strict=scale == 3)
         fusion.train_precision = prec
-        if tail == "shift":                                  # the searched loss has no parameters: HRNet alone is built and optimised
+        if tail in SEARCHED:                                 # a searched loss has no parameters: HRNet alone is built and optimised
             fusion = fusion.to(dev).train()
             for k, p in fusion.named_parameters():
                 p.requires_grad_(not FREEZE[freeze]("fusion." + k))
             params = list(fusion.parameters())
-            return fusion, None, adam(params, lr=1e-4)
+            return fusion, SEARCHED[tail], adam(params, lr=1e-4)
         regis = ShiftNet()
         if sprec is not None:
             regis.train_precision = sprec
@@ -118,8 +121,8 @@ def main():
     def step(fusion, regis, opt):
         opt.zero_grad()
         srs = fusion(x, a)
-        if regis is None:
-            loss = torch.mean(-shift_loss(srs, hrs, maps))
+        if not isinstance(regis, torch.nn.Module):           # a searched loss: `regis` is the function of (srs, hrs, maps)
+            loss = torch.mean(regis(srs, hrs, maps))
             loss.backward()
             opt.step()
             return loss
@@ -132,7 +135,7 @@ def main():
         return loss
 
     runs = {(p, sp, f, t): setup(p, sp, f, t) for p in precs for t in tails for sp in (sprecs if t == "shiftnet" else [None]) for f in freezes
-            if not (t == "shift" and f == "shiftnet")}
+            if not (t in SEARCHED and f == "shiftnet")}
     for r in runs.values():
         for _ in range(2):
             step(*r)
