@@ -145,6 +145,9 @@ SIGNATURES = {
     "hrn_shift_cssim": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 7 + [_c.c_float] + [_c.c_void_p] * 4 + [_c.c_size_t, _c.c_void_p]),
     "hrn_cssim_loss_backward_workspace_bytes": (_c.c_size_t, [_c.c_int] * 5),
     "hrn_cssim_loss_backward": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 7 + [_c.c_float] + [_c.c_void_p] * 2 + [_c.c_size_t, _c.c_void_p]),
+    "hrn_cl1_loss_workspace_bytes": (_c.c_size_t, [_c.c_int] * 4),
+    "hrn_cl1_loss_train": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 5 + [_c.c_float] + [_c.c_void_p] * 3 + [_c.c_size_t, _c.c_void_p]),
+    "hrn_cl1_loss_backward": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 5 + [_c.c_float] + [_c.c_void_p] * 2),
     "hrn_mncc_grid": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 5 + [_c.c_float, _c.c_void_p, _c.c_void_p]),
     "hrn_mncc_search": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_mncc_apply": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 4 + [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
@@ -916,6 +919,49 @@ def shift_loss_backward(srs, hrs, hr_maps, stats, d_out, metric="cPSNR", border_
     with torch.cuda.device(srs.device):
         _check(lib.hrn_shift_loss_backward(_ptr(srs), _ptr(hrs), _ptr(hr_maps), _ptr(stats.contiguous()), _ptr(d_out), B, H, W, border_w,
                                            _METRICS[metric], int(bool(clip)), _ptr(d_srs), _stream()), "hrn_shift_loss_backward")
+    return d_srs
+
+
+def _cl1_loss_args(srs, hrs, hr_maps, border_w, eps):
+    srs, hrs, hr_maps = _dev_f32(srs, "srs"), _dev_f32(hrs, "hrs"), _dev_f32(hr_maps, "hr_maps")
+    if srs.dim() != 3 or srs.shape != hrs.shape or srs.shape != hr_maps.shape:
+        raise ValueError(f"srs, hrs, hr_maps must be equal (B,H,W) tensors; got {tuple(srs.shape)}, {tuple(hrs.shape)}, {tuple(hr_maps.shape)}")
+    border_w, eps = int(border_w), float(eps)
+    if border_w < 0 or min(srs.shape[1:]) <= 2 * border_w:
+        raise ValueError(f"border_w={border_w} needs frames larger than {2 * border_w} pixels each way; got {tuple(srs.shape[1:])}")
+    if not 0.0 <= eps < float("inf"):
+        raise ValueError(f"eps must be finite and not negative; got {eps}")
+    return srs, hrs, hr_maps, border_w, eps
+
+
+def cl1_loss_train(srs, hrs, hr_maps, border_w=3, clip=False, eps=0.0):
+    """Forward of the shift-searched, brightness-corrected L1 (eps == 0) / Charbonnier loss on (B,H,W) frames of any
+    aspect ratio: -> (out (B,), stats (B,5) f64 = {n, bias, cL1, k, sigma} of the selected offset k = u (2 border_w + 1) + v)."""
+    lib = load_library()
+    srs, hrs, hr_maps, border_w, eps = _cl1_loss_args(srs, hrs, hr_maps, border_w, eps)
+    B, H, W = srs.shape
+    out = torch.empty((B,), dtype=torch.float32, device=srs.device)
+    stats = torch.empty((B, 5), dtype=torch.float64, device=srs.device)
+    with torch.cuda.device(srs.device):
+        ws = _workspace(lib.hrn_cl1_loss_workspace_bytes(B, H, W, border_w), srs.device, "cl1_loss")
+        _check(lib.hrn_cl1_loss_train(_ptr(srs), _ptr(hrs), _ptr(hr_maps), B, H, W, border_w, int(bool(clip)), eps, _ptr(out), _ptr(stats),
+                                      _ptr(ws), ws.numel(), _stream()), "hrn_cl1_loss_train")
+    return out, stats
+
+
+def cl1_loss_backward(srs, hrs, hr_maps, stats, d_out, border_w=3, clip=False, eps=0.0):
+    """d_out (B,) -> d_srs (B,H,W) through the offset `stats` selected, the bias attached; zero on the border frame and where clip
+    clamped."""
+    lib = load_library()
+    srs, hrs, hr_maps, border_w, eps = _cl1_loss_args(srs, hrs, hr_maps, border_w, eps)
+    d_out = _dev_f32(d_out, "d_out")
+    B, H, W = srs.shape
+    if tuple(stats.shape) != (B, 5) or stats.dtype != torch.float64 or tuple(d_out.shape) != (B,):
+        raise ValueError(f"stats must be ({B}, 5) float64 and d_out ({B},); got {tuple(stats.shape)} {stats.dtype}, {tuple(d_out.shape)}")
+    d_srs = torch.empty_like(srs)
+    with torch.cuda.device(srs.device):
+        _check(lib.hrn_cl1_loss_backward(_ptr(srs), _ptr(hrs), _ptr(hr_maps), _ptr(stats.contiguous()), _ptr(d_out), B, H, W, border_w,
+                                         int(bool(clip)), eps, _ptr(d_srs), _stream()), "hrn_cl1_loss_backward")
     return d_srs
 
 
@@ -1700,6 +1746,47 @@ def _cssim_loss_backward(ctx, d_out, _d_stats):
 
 
 _op_shift_cssim_train.register_autograd(_cssim_loss_backward, setup_context=_cssim_loss_setup)
+
+
+# The shift-searched L1 / Charbonnier: the gradient through the selected offset, the bias attached.
+@torch.library.custom_op("hrnet_hip::cl1_loss_train", mutates_args=(), device_types="cuda")
+def _op_cl1_loss_train(srs: torch.Tensor, hrs: torch.Tensor, hr_maps: torch.Tensor, border_w: int, clip: bool,
+                       eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The shift-searched L1 / Charbonnier: (loss per sample (B,), stats (B,5) f64 = {n, bias, cL1, k, sigma})."""
+    return cl1_loss_train(srs, hrs, hr_maps, border_w, clip, eps)
+
+
+@_op_cl1_loss_train.register_fake
+def _(srs, hrs, hr_maps, border_w, clip, eps):
+    return srs.new_empty((srs.shape[0],), dtype=torch.float32), srs.new_empty((srs.shape[0], 5), dtype=torch.float64)
+
+
+@torch.library.custom_op("hrnet_hip::cl1_loss_backward", mutates_args=(), device_types="cuda")
+def _op_cl1_loss_backward(srs: torch.Tensor, hrs: torch.Tensor, hr_maps: torch.Tensor, stats: torch.Tensor, d_out: torch.Tensor,
+                          border_w: int, clip: bool, eps: float) -> torch.Tensor:
+    return cl1_loss_backward(srs, hrs, hr_maps, stats, d_out.contiguous(), border_w, clip, eps)
+
+
+@_op_cl1_loss_backward.register_fake
+def _(srs, hrs, hr_maps, stats, d_out, border_w, clip, eps):
+    return srs.new_empty(srs.shape, dtype=torch.float32)
+
+
+def _cl1_loss_setup(ctx, inputs, output):
+    srs, hrs, hr_maps, ctx.border_w, ctx.clip, ctx.eps = inputs
+    ctx.save_for_backward(srs, hrs, hr_maps, output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _cl1_loss_backward(ctx, d_out, _d_stats):
+    srs, hrs, hr_maps, stats = ctx.saved_tensors
+    if d_out is None:
+        return (None,) * 6
+    d_srs = torch.ops.hrnet_hip.cl1_loss_backward(srs, hrs, hr_maps, stats, d_out, ctx.border_w, ctx.clip, ctx.eps)
+    return (d_srs,) + (None,) * 5                       # the targets and their status maps get no gradient
+
+
+_op_cl1_loss_train.register_autograd(_cl1_loss_backward, setup_context=_cl1_loss_setup)
 
 
 # The registration search has no autograd formula: a shift found by a grid search is piecewise constant in the frames.

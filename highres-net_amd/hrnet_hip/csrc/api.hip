@@ -488,6 +488,36 @@ int hrn_cssim_loss_backward(const float* srs, const float* hrs, const float* map
                                           d_srs, ws, (hipStream_t)stream);
 }
 
+// the shift-searched L1 / Charbonnier (cl1_loss.hip): shift_loss's crops, offsets and limits
+static int cl1_loss_check(const char* who, int B, int H, int W, int border, float eps) {
+    HRN_CHECK(border >= 0 && border <= 8, -2, "%s: border %d outside 0..8", who, border);
+    HRN_CHECK(B > 0 && H > 2 * border && W > 2 * border, -2, "%s: bad shape B=%d H=%d W=%d border=%d", who, B, H, W, border);
+    HRN_CHECK(B <= 65535, -2, "%s: batch %d exceeds the grid limit", who, B);
+    HRN_CHECK((long long)H * W <= 0x7fffffffLL, -2, "%s: a frame of %d x %d exceeds 2^31 - 1 pixels", who, H, W);
+    HRN_CHECK(eps >= 0.f && eps <= 3.0e38f, -2, "%s: eps must be finite and not negative (got %g)", who, (double)eps);
+    return 0;
+}
+
+size_t hrn_cl1_loss_workspace_bytes(int B, int H, int W, int border) {
+    if (B <= 0 || B > 65535 || border < 0 || border > 8 || H <= 2 * border || W <= 2 * border || (long long)H * W > 0x7fffffffLL) return 0;
+    return hrn_cl1_loss_workspace_bytes_impl(B, H, W, border);
+}
+
+int hrn_cl1_loss_train(const float* srs, const float* hrs, const float* maps, int B, int H, int W, int border, int clip, float eps, float* out,
+                       double* stats, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = cl1_loss_check("hrn_cl1_loss_train", B, H, W, border, eps)) return rc;
+    HRN_CHECK(srs && hrs && maps && out && stats && ws, -2, "hrn_cl1_loss_train: null argument");
+    HRN_CHECK(ws_bytes >= hrn_cl1_loss_workspace_bytes_impl(B, H, W, border), -3, "hrn_cl1_loss_train: workspace too small");
+    return hrn_launch_cl1_loss_train(srs, hrs, maps, B, H, W, border, clip != 0, eps, out, stats, (double*)ws, (hipStream_t)stream);
+}
+
+int hrn_cl1_loss_backward(const float* srs, const float* hrs, const float* maps, const double* stats, const float* d_out, int B, int H, int W,
+                          int border, int clip, float eps, float* d_srs, void* stream) {
+    if (int rc = cl1_loss_check("hrn_cl1_loss_backward", B, H, W, border, eps)) return rc;
+    HRN_CHECK(srs && hrs && maps && stats && d_out && d_srs, -2, "hrn_cl1_loss_backward: null argument");
+    return hrn_launch_cl1_loss_backward(srs, hrs, maps, stats, d_out, B, H, W, border, clip != 0, eps, d_srs, (hipStream_t)stream);
+}
+
 // the masked-NCC registration search (registration.hip): the reference fork's recursive_mncc_search / compute_grid_mncc, restated
 //
 // Every limit of a registration problem is stated once, in a check that takes the entry point's name `who`.  A size query runs its entry

@@ -70,6 +70,17 @@ int hrn_launch_cssim_loss_backward(const float* srs, const float* hrs, const flo
                                    int H, int W, int border, int window, int clip, int correct_bias, float data_range, float* d_srs,
                                    void* workspace, hipStream_t stream);
 
+// ---- cl1_loss.hip: the shift-searched, brightness-corrected L1 / Charbonnier as a training tail (the definition is
+// in include/hrnet_hip.h), over shift_loss.hip's crops and offsets, border 0..8.  Forward: a pre-pass for every offset's {n_k, b_k}, a
+// main pass for sum m rho(e) and sum m rho'(e), fixed-order finishes -> out [B], stats [B][5] = {n*, b*, cL1*, k*, sigma*} (n* = 0,
+// k* = -1, out NaN without a clear pixel).  Backward: d_srs [B][H][W], every element written, through the selected offset only, the bias
+// attached.  eps: 0 = |e|, else sqrt(e^2 + eps^2).  The callers have checked the arguments.
+size_t hrn_cl1_loss_workspace_bytes_impl(int B, int H, int W, int border);
+int hrn_launch_cl1_loss_train(const float* srs, const float* hrs, const float* maps, int B, int H, int W, int border, int clip, float eps,
+                              float* out, double* stats, double* workspace, hipStream_t stream);
+int hrn_launch_cl1_loss_backward(const float* srs, const float* hrs, const float* maps, const double* stats, const float* d_out, int B,
+                                 int H, int W, int border, int clip, float eps, float* d_srs, hipStream_t stream);
+
 // ---- registration.hip: the masked-NCC sub-pixel registration of LR views (the definitions are in
 // include/hrnet_hip.h).  One workgroup per view; a mask pointer may be null (all ones); the callers have checked the limits below.
 constexpr int HRN_MNCC_MIN_SIDE = 16, HRN_MNCC_MAX_SIDE = 128;     // a view, its row-pass buffer and its mask patterns fit one CU's LDS

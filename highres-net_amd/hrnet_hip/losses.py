@@ -18,7 +18,12 @@ over `hrn_shift_cssim`).  It is a score: it has no gradien
 
 `cssim_loss(srs, hrs, hr_maps, border_w, clip, window, data_range, correct_bias)` is that score as a loss, 1 - cSSIM per sample,
 differentiable through the selected offset with the brightness bias attached (`torch.ops.hrnet_hip.shift_cssim_train` /
-`.cssim_loss_backward` over `hrn_shift_cssim` / `hrn_cssim_loss_backward`)."""
+`.cssim_loss_backward` over `hrn_shift_cssim` / `hrn_cssim_loss_backward`).
+
+`cl1_loss(srs, hrs, hr_maps, border_w, clip, eps)` is the third searched loss: the brightness-corrected L1 (cMAE, eps = 0) or Charbonnier
+sqrt(e^2 + eps^2) over the same offsets, the map a weight as in `shift_loss`, to be minimised as it is and differentiable through the
+selected offset with the brightness bias attached (`torch.ops.hrnet_hip.cl1_loss_train` / `.cl1_loss_backward` over `hrn_cl1_loss_train`
+/ `hrn_cl1_loss_backward`)."""
 import torch
 
 from . import binding
@@ -135,3 +140,34 @@ def cssim_loss(srs, hrs, hr_maps, border_w=3, clip=False, window="gaussian", dat
         out, stats, _ = binding.shift_cssim(srs.detach(), hrs, hr_maps, border_w, window, clip, correct_bias, data_range, with_scores=False)
     loss = 1.0 - out
     return (loss, _shift_of(stats, border_w)) if return_shift else loss
+
+
+def cl1_loss(srs, hrs, hr_maps, border_w=3, clip=False, eps=0.0, return_shift=False):
+    """(B,H,W) x 3 -> (B,): the lowest brightness-corrected mean of rho(srs + bias - hrs), weighted by `hr_maps`, over the integer offsets
+    (u - border_w, v - border_w), |.| <= border_w, of `hrs` against the centre crop of `srs`; rho(e) = |e| for eps == 0 (cMAE) and
+    sqrt(e^2 + eps^2) otherwise (Charbonnier).  To be minimised as it is.  clip clamps srs to [0, 1] first.  A (B,1,H,W) `srs` is taken as
+    srs[:, 0].  With grad enabled and a gradient-requiring `srs` the result is differentiable through the selected offset, the bias
+    attached (no gradient to hrs / hr_maps); without either the same forward runs and returns the same bits.  NaN,
+    with a zero gradient, for a sample without a clear pixel.  return_shift: also the (B,2) int64 offsets selected, as in shift_loss."""
+    for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name} must be a torch.Tensor; got {type(t).__name__}")
+    if srs.dim() == 4 and srs.shape[1] == 1:
+        srs = srs[:, 0]
+    if srs.dim() != 3 or srs.shape != hrs.shape or srs.shape != hr_maps.shape:
+        raise ValueError(f"srs, hrs, hr_maps must be equal (B,H,W) tensors; got {tuple(srs.shape)}, {tuple(hrs.shape)}, {tuple(hr_maps.shape)}")
+    border_w, eps = int(border_w), float(eps)
+    if border_w < 0 or border_w > 8 or min(srs.shape[1:]) <= 2 * border_w:
+        raise ValueError(f"border_w must be 0..8 and smaller than half of each side; got {border_w} for frames {tuple(srs.shape[1:])}")
+    if not 0.0 <= eps < float("inf"):
+        raise ValueError(f"eps must be finite and not negative; got {eps}")
+    for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
+        if not t.is_cuda:
+            raise TypeError(f"{name} is on '{t.device}': the searched loss runs on a ROCm device only (no CPU fallback)")
+    srs = srs if srs.dtype == torch.float32 else srs.float()
+    if torch.is_grad_enabled() and srs.requires_grad:
+        out, stats = torch.ops.hrnet_hip.cl1_loss_train(srs.contiguous(), hrs.float().contiguous(), hr_maps.float().contiguous(), border_w,
+                                                        bool(clip), eps)
+    else:
+        out, stats = binding.cl1_loss_train(srs.detach(), hrs, hr_maps, border_w, clip, eps)
+    return (out, _shift_of(stats, border_w)) if return_shift else out

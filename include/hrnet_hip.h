@@ -23,6 +23,8 @@
  *   hrn_shift_loss_train / hrn_shift_loss_backward  <-  the two combined as a differentiable loss (the searched score, trainable)
  *   hrn_shift_cssim / hrn_cssim_loss_backward  <-  (no counterpart: the project's second score) the shift-searched, brightness-corrected
  *                              SSIM, and its gradient through the selected offset: cSSIM as a training loss
+ *   hrn_cl1_loss_train / hrn_cl1_loss_backward  <-  (no counterpart: the project's third searched loss) the shift-searched,
+ *                              brightness-corrected L1 / Charbonnier, and its gradient through the selected offset
  *   hrn_mncc_grid / hrn_mncc_search / hrn_mncc_apply  <-  the method of the fork's registration_search.py (recursive_mncc_search over
  *                              compute_grid_mncc), restated: sub-pixel registration of the LR views against a reference frame;
  *                              hrn_mncc_grid_scene / hrn_mncc_search_scene / hrn_mncc_apply_scene: the same for frames of any size;
@@ -361,6 +363,31 @@ size_t hrn_cssim_loss_backward_workspace_bytes(int B, int H, int W, int border, 
 int hrn_cssim_loss_backward(const float* srs, const float* hrs, const float* hr_maps, const double* stats, const float* d_out, int B, int H,
                             int W, int border, int window, int clip, int correct_bias, float data_range, float* d_srs, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* The third searched loss, cL1: the brightness-corrected, shift-searched L1 (cMAE) and its smooth form, Charbonnier, over the offsets and
+ * crops of hrn_shift_loss_train (the project's own definition; tests/cl1_ref.py restates it in fp64).  srs/hrs/hr_maps (B,H,W) f32, H and
+ * W > 2 border, H W < 2^31, border 0..8; h, w, s (clamped to [0,1] when clip != 0) and, for the offset k = u (2 border + 1) + v, g and m
+ * as above.  The map is a WEIGHT, as in hrn_shift_loss_train (it is not binarised as cSSIM's is).  With rho(e) = |e| for eps == 0 and
+ * sqrt(e^2 + eps^2) otherwise, rho' its derivative (rho'(0) = 0 at eps == 0), eps finite and >= 0:
+ *   n_k = sum m,  b_k = sum m (g - s) / n_k,  e = s + b_k - g,  cL1_k = sum m rho(e) / n_k,  sigma_k = sum m rho'(e) / n_k.
+ * k* is the lowest k of minimal cL1_k among n_k > 0 under a strict <; a NaN is never selected over a number.  out = cL1_k*, to be
+ * minimised as it is (no sign flip, unlike 'cPSNR').
+ * hrn_cl1_loss_train      <-  out (B) f32 and stats (B,5) f64 = {n*, b*, cL1*, k*, sigma*}; without a clear pixel at any offset out is NaN
+ *                             and stats {0, 0, NaN, -1, 0}.  Two walks over the offsets (|e| does not expand as e^2 does: every b_k must be
+ *                             known, over the whole sample, before an absolute value is taken), e and its sign formed in fp64 from the fp64
+ *                             bias, fp64 sums in a fixed order, no atomics: bit-reproducible, and a sample's result does not depend on
+ *                             the batch around it.
+ * hrn_cl1_loss_backward   <-  autograd through that loss with k* held fixed and the bias ATTACHED (unlike the cMSE its term does not
+ *                             cancel: this is the derivative of the number returned): d_srs (B,H,W), every element written =
+ *                             d_out[b] m* / n* (rho'(e*) - sigma*) at the selected offset; exactly 0 on the border frame, where clip
+ *                             clamped s (0 <= s <= 1 passes, as torch.clamp has it; clamped pixels still count in sigma*) and for a
+ *                             sample without a clear pixel.  No gradient to hrs / hr_maps.
+ * hrn_cl1_loss_workspace_bytes: the tiles' fp64 sums and every offset's {n_k, b_k} (0 for arguments the entry points refuse). */
+size_t hrn_cl1_loss_workspace_bytes(int B, int H, int W, int border);
+int hrn_cl1_loss_train(const float* srs, const float* hrs, const float* hr_maps, int B, int H, int W, int border, int clip, float eps,
+                       float* out, double* stats, void* workspace, size_t workspace_bytes, void* stream);
+int hrn_cl1_loss_backward(const float* srs, const float* hrs, const float* hr_maps, const double* stats, const float* d_out, int B, int H,
+                          int W, int border, int clip, float eps, float* d_srs, void* stream);
 
 /* ------------------------------------------------------------------ sub-pixel registration of LR views: a masked-NCC grid search
  * The method of the reference fork's registration_search.py / registration_metrics.py (compute_shift_ncc -> recursive_mncc_search ->
