@@ -123,6 +123,11 @@ SIGNATURES = {
                                              _c.POINTER(ShiftnetParams), _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_adam_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_float, _c.c_float, _c.c_float,
                                  _c.c_float, _c.c_float, _c.c_int, _c.c_void_p]),
+    "hrn_grad_sumsq_workspace_bytes": (_c.c_size_t, [_c.c_size_t]),
+    "hrn_grad_sumsq": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_optim_prepare": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float, _c.c_float, _c.c_void_p,
+                                     _c.c_void_p]),
+    "hrn_adam_step_ex": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_size_t] + [_c.c_float] * 4 + [_c.c_int, _c.c_float, _c.c_void_p, _c.c_void_p]),
     "hrn_lanczos_kernel": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "hrn_lanczos_shift": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "hrn_lanczos_shift_backward_workspace_bytes": (_c.c_size_t, [_c.c_int] * 4),
@@ -613,6 +618,81 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_
     with torch.cuda.device(params.device):
         _check(lib.hrn_adam_step(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), params.numel(), float(lr), float(beta1),
                                  float(beta2), float(eps), float(weight_decay), int(step), _stream()), "hrn_adam_step")
+    bump_param_epoch()
+
+
+# The guarded step (csrc/optim_guard.hip).  One step-control block per parameter group, as include/hrnet_hip.h lays hrn_optim_ctl out;
+# a (G, OPTIM_CTL_WORDS) int64 device tensor holds G of them.
+OPTIM_MAX_GROUPS = 8
+OPTIM_CTL_BYTES = 48
+OPTIM_CTL_WORDS = OPTIM_CTL_BYTES // 8
+OPTIM_CTL_FIELDS = {"applied": (0, torch.int64), "skipped": (8, torch.int64), "norm": (16, torch.float64), "coef": (24, torch.float32),
+                    "step_size": (28, torch.float32), "inv_bc2_sqrt": (32, torch.float32), "lr": (36, torch.float32),
+                    "skip": (40, torch.int32)}
+
+
+def optim_ctl_field(ctl, group, name):
+    """A 0-d view of one field of the control block of `group` in `ctl` (a (G, OPTIM_CTL_WORDS) int64 device tensor); no sync."""
+    off, dtype = OPTIM_CTL_FIELDS[name]
+    row = ctl[group].view(torch.uint8)
+    return row[off:off + torch.empty((), dtype=dtype).element_size()].view(dtype)[0]
+
+
+def _flat_f32(name, t, n=None):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1 and (n is None or t.numel() == n)):
+        raise ValueError(f"{name} must be a contiguous 1-d float32 device tensor" + (f" of {n} elements" if n is not None else ""))
+
+
+def _optim_ctl(ctl, n_groups):
+    if not (ctl.is_cuda and ctl.dtype == torch.int64 and ctl.is_contiguous() and tuple(ctl.shape) == (n_groups, OPTIM_CTL_WORDS)):
+        raise ValueError(f"ctl must be a contiguous int64 device tensor of shape ({n_groups}, {OPTIM_CTL_WORDS})")
+
+
+def grad_sumsq(grads):
+    """(sum of g^2 over the finite elements, number of non-finite elements) of a flat fp32 device buffer, as a float64 (2,) device
+    tensor: fp64 accumulation in a fixed order, bit-reproducible, no sync."""
+    lib = load_library()
+    _flat_f32("grads", grads)
+    n = grads.numel()
+    out = torch.empty(2, dtype=torch.float64, device=grads.device)
+    nbytes = lib.hrn_grad_sumsq_workspace_bytes(n)
+    ws = _workspace(nbytes, grads.device, "grad_sumsq")
+    with torch.cuda.device(grads.device):
+        _check(lib.hrn_grad_sumsq(_ptr(grads), n, _ptr(out), _ptr(ws), ws.numel(), _stream()), "hrn_grad_sumsq")
+    return out
+
+
+def optim_prepare(sums, ctl, group, max_norm, lr, beta1, beta2):
+    """sums: (G, 2) float64, every group's grad_sumsq.  Updates the control block ctl[group] in place (norm, coef, skip, the counters
+    and the bias corrections of the group whose lr / betas are given).  max_norm <= 0: no clipping."""
+    lib = load_library()
+    if not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous() and sums.dim() == 2 and sums.shape[1] == 2):
+        raise ValueError("sums must be a contiguous float64 device tensor of shape (n_groups, 2)")
+    G = sums.shape[0]
+    if not 1 <= G <= OPTIM_MAX_GROUPS:
+        raise ValueError(f"n_groups must be in 1..{OPTIM_MAX_GROUPS} (got {G})")
+    _optim_ctl(ctl, G)
+    with torch.cuda.device(sums.device):
+        _check(lib.hrn_optim_prepare(_ptr(sums), G, int(group), float(max_norm), float(lr), float(beta1), float(beta2), _ptr(ctl),
+                                     _stream()), "hrn_optim_prepare")
+
+
+def adam_step_ex(params, grads, exp_avg, exp_avg_sq, ema, ctl, group, beta1, beta2, eps, weight_decay, decoupled, ema_decay):
+    """The guarded Adam / AdamW update of the flat fp32 buffer `params` under the control block ctl[group]; `ema` (or None) is updated
+    towards the new parameters.  `grads` is not written: the clipped gradient exists in registers only."""
+    lib = load_library()
+    n = params.numel()
+    for name, t in (("params", params), ("grads", grads), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("ema", ema)):
+        if t is not None:
+            _flat_f32(name, t, n)
+    if ctl.dim() != 2 or not 0 <= group < ctl.shape[0]:
+        raise ValueError(f"group {group} is not a row of ctl")
+    _optim_ctl(ctl, ctl.shape[0])
+    with torch.cuda.device(params.device):
+        _check(lib.hrn_adam_step_ex(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(ema) if ema is not None else None, n,
+                                    float(beta1), float(beta2), float(eps), float(weight_decay), int(bool(decoupled)),
+                                    float(ema_decay), ctypes.c_void_p(ctl.data_ptr() + group * OPTIM_CTL_BYTES), _stream()),
+               "hrn_adam_step_ex")
     bump_param_epoch()
 
 
@@ -1914,3 +1994,28 @@ def _op_adam_step(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tens
                   beta2: float, eps: float, weight_decay: float, step: int) -> None:
     """`optimizer.step()` of torch.optim.Adam (train.py:191) on one flat fp32 buffer, in place."""
     adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step)
+
+
+@torch.library.custom_op("hrnet_hip::grad_sumsq", mutates_args=(), device_types="cuda")
+def _op_grad_sumsq(grads: torch.Tensor) -> torch.Tensor:
+    """(sum of squares of the finite elements, number of non-finite ones) of a flat fp32 buffer, float64 (2,)"""
+    return grad_sumsq(grads)
+
+
+@_op_grad_sumsq.register_fake
+def _fake_grad_sumsq(grads):
+    return grads.new_empty((2,), dtype=torch.float64)
+
+
+@torch.library.custom_op("hrnet_hip::optim_prepare", mutates_args=("ctl",), device_types="cuda")
+def _op_optim_prepare(sums: torch.Tensor, ctl: torch.Tensor, group: int, max_norm: float, lr: float, beta1: float, beta2: float) -> None:
+    """every group's sums -> the step-control block of one group (norm, clip coefficient, skip, counters, bias corrections), in place"""
+    optim_prepare(sums, ctl, group, max_norm, lr, beta1, beta2)
+
+
+@torch.library.custom_op("hrnet_hip::adam_step_ex", mutates_args=("params", "exp_avg", "exp_avg_sq", "ema"), device_types="cuda")
+def _op_adam_step_ex(params: torch.Tensor, grads: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, ema: Optional[torch.Tensor],
+                     ctl: torch.Tensor, group: int, beta1: float, beta2: float, eps: float, weight_decay: float, decoupled: bool,
+                     ema_decay: float) -> None:
+    """the clipped, guarded Adam / AdamW step with the EMA of the new weights, on one flat fp32 buffer, in place"""
+    adam_step_ex(params, grads, exp_avg, exp_avg_sq, ema, ctl, group, beta1, beta2, eps, weight_decay, decoupled, ema_decay)

@@ -19,6 +19,8 @@
  *   hrn_hrnet_forward_train / hrn_hrnet_backward, hrn_shiftnet_forward_train / hrn_shiftnet_backward,
  *   hrn_lanczos_shift_backward  <-  torch autograd through the three symbols above, src/train.py:172-190
  *   hrn_adam_step          <-  optimizer.step() of torch.optim.Adam   src/train.py:191, :252
+ *   hrn_grad_sumsq / hrn_optim_prepare / hrn_adam_step_ex  <-  (no counterpart: the reference's loop has none of them)
+ *                              torch.nn.utils.clip_grad_norm_, a skip of non-finite steps, torch.optim.AdamW and an EMA of the weights
  *   hrn_get_loss / hrn_shift_cpsnr  <-  get_loss (train.py:66-87) / shift_cPSNR (Evaluator.py:52-73)
  *   hrn_shift_loss_train / hrn_shift_loss_backward  <-  the two combined as a differentiable loss (the searched score, trainable)
  *   hrn_shift_cssim / hrn_cssim_loss_backward  <-  (no counterpart: the project's second score) the shift-searched, brightness-corrected
@@ -526,6 +528,55 @@ int hrn_mncc_search_pyramid(const float* ref, const float* ref_mask, const float
  *                    p -= lr / (1 - b1^step) * m / (sqrt(v) / sqrt(1 - b2^step) + eps).  step counts from 1. */
 int hrn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int step, void* stream);
+
+/* The guarded step (csrc/optim_guard.hip): clipping by the global gradient norm, a skip when any gradient element is not finite,
+ * decoupled weight decay (AdamW) and an exponential moving average of the weights, with nothing returning to the host.  Per step:
+ * hrn_grad_sumsq once per parameter group, then hrn_optim_prepare and hrn_adam_step_ex once per group, all on one stream.
+ *
+ * hrn_optim_ctl  the step-control block of one group, 48 bytes of device memory, zero before the first step.  The layout (offsets
+ *                in bytes) is part of the ABI: the caller reads norm and the counters from it and may preset the counters.
+ *                    0 int64 applied         steps applied so far (the `step` of the bias corrections)
+ *                    8 int64 skipped         steps skipped because a gradient element was not finite
+ *                   16 double norm           sqrt of the sum of squares of the finite gradient elements of every group, before clipping
+ *                   24 float coef            min(1, max_norm / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s coefficient, taken in fp64
+ *                                            and rounded once; exactly 1 with max_norm <= 0 (no clipping)
+ *                   28 float step_size       lr / (1 - beta1^applied)
+ *                   32 float inv_bc2_sqrt    1 / sqrt(1 - beta2^applied), both in fp64 as hrn_adam_step takes them on the host
+ *                   36 float lr
+ *                   40 int skip              1: hrn_adam_step_ex writes nothing
+ *                   44 int reserved
+ * hrn_grad_sumsq_workspace_bytes  16 bytes per block of the first launch; the grid is a function of n alone.
+ * hrn_grad_sumsq out[0] = sum of g^2 over the finite elements, each square exact in fp64 and the additions in a fixed order (no atomics:
+ *                bit-reproducible, whatever else runs); out[1] = the number of non-finite elements (+-inf, NaN), as a double.  Two launches.
+ *                n == 0 launches only the second and writes {0, 0}.  fp32 sums would overflow at |g| ~ 2e19; these do not.
+ * hrn_optim_prepare  sums (n_groups, 2): every group's hrn_grad_sumsq output.  Writes ctl[group] (ctl: the array of n_groups blocks) for the
+ *                group whose lr / betas are given: total = the groups' finite sums added in index order, norm = sqrt(total) (always written);
+ *                skip = any group has a non-finite element.  Skipping: skipped += 1, skip = 1, and every other field stays as the last
+ *                applied step left it - a skipped step does not advance the bias corrections, as a skipped optimizer.step() does not
+ *                count.  Otherwise applied += 1, skip = 0 and coef, step_size, inv_bc2_sqrt, lr as above.  One wave.
+ * hrn_adam_step_ex  ctl: the block of this group.  skip set: returns without writing (params, moments and ema keep their bits).  Else
+ *                    g' = coef g (+ weight_decay p unless decoupled);  m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;
+ *                    p = p (1 - lr weight_decay) [decoupled only] - step_size m / (sqrt(v) inv_bc2_sqrt + eps);
+ *                    ema = ema_decay ema + (1 - ema_decay) p  [ema_or_null given; p is the new value; taken in fp64, rounded once].
+ *                grads is never written: the clipped gradient exists in registers only (clip_grad_norm_ rescales .grad in place).
+ *                16 B read + 12 B written per parameter, + 4 + 4 with the EMA.
+ * -2 before any launch, hrn_last_error() naming the argument: a null pointer, a buffer that is not 16-byte aligned, n_groups outside
+ * 1..HRN_OPTIM_MAX_GROUPS, group outside 0..n_groups-1, a beta outside [0, 1), ema_decay outside [0, 1) when ema_or_null is given, a
+ * workspace smaller than hrn_grad_sumsq_workspace_bytes(n). */
+#define HRN_OPTIM_MAX_GROUPS 8
+typedef struct hrn_optim_ctl {
+    int64_t applied, skipped;
+    double norm;
+    float coef, step_size, inv_bc2_sqrt, lr;
+    int skip, reserved;
+} hrn_optim_ctl;
+size_t hrn_grad_sumsq_workspace_bytes(size_t n);
+int hrn_grad_sumsq(const float* grads, size_t n, double* out, void* ws, size_t ws_bytes, void* stream);
+int hrn_optim_prepare(const double* sums, int n_groups, int group, float max_norm, float lr, float beta1, float beta2,
+                      hrn_optim_ctl* ctl, void* stream);
+int hrn_adam_step_ex(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema_or_null, size_t n,
+                     float beta1, float beta2, float eps, float weight_decay, int decoupled, float ema_decay,
+                     const hrn_optim_ctl* ctl, void* stream);
 
 /* ------------------------------------------------------------------ input pipeline: batch assembly on the device
  * hrn_collate_device  <-  ImagesetDataset.load_batch (highres-net_amd/DataLoader.py) from imagesets decoded once into HBM:
