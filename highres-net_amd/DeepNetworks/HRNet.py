@@ -33,6 +33,13 @@ Tiled inference (`HRNet.tile`, or key "tile" in the config dict; default None):
     an integer        the forward WITHOUT a graph routes an input that is not square, or larger than `tile` pixels a side, through
                       `forward_tiled(lrs, alphas, tile, ensemble=self.ensemble)`: overlapping square windows whose cores tile the
                       scene (hrnet_hip/tiling.py).  Scenes of any size and aspect ratio; the training branch is never tiled.
+
+Reference frame (`forward(lrs, alphas, ref=None)`, likewise forward_ensemble and forward_tiled):
+    None              the network's own frame, the lower median of lrs[:, :9]: the code path it always was
+    a (B,H,W) float tensor on the device
+                      that frame is the second input channel of every view instead, e.g. the cloud-free composite of
+                      hrnet_hip.composite.masked_composite.  It is data: in training it gets a gradient of its own when it requires one,
+                      and nothing flows from it into lrs.  With ref equal to the median every result is bit-identical to ref=None.
 """
 import os
 
@@ -195,7 +202,9 @@ class HRNet(nn.Module):
         dt = self._dtype()
         return self._packed_for(dt), dt
 
-    def forward(self, lrs, alphas):
+    def forward(self, lrs, alphas, ref=None):
+        if ref is not None:
+            return self._forward_ref(lrs, alphas, ref)
         if lrs.dim() != 4:
             raise ValueError(f"lrs must be (B, L, H, W); got {tuple(lrs.shape)}")
         grad_params = self.training and any(p.requires_grad for p in self.parameters())
@@ -241,13 +250,52 @@ class HRNet(nn.Module):
         return torch.ops.hrnet_hip.hrnet_forward(packed, dt, self._num_layers, bool(self.fuse.alpha_residual), lrs.detach(), alphas.detach(),
                                                  self._scale)
 
-    def forward_ensemble(self, lrs, alphas, mode="dihedral", members_per_pass=None):
+    def _forward_ref(self, lrs, alphas, ref):
+        """forward with the reference frame given: the same routing as forward, on the *_ref ops"""
+        if lrs.dim() != 4:
+            raise ValueError(f"lrs must be (B, L, H, W); got {tuple(lrs.shape)}")
+        ref = binding._ref_frame(ref, lrs)
+        grad_params = self.training and any(p.requires_grad for p in self.parameters())
+        grad_inputs = lrs.requires_grad or alphas.requires_grad or ref.requires_grad
+        graph = torch.is_grad_enabled() and (grad_params or grad_inputs)
+        if self.tile is not None and not graph and (lrs.shape[2] != lrs.shape[3] or lrs.shape[2] > self._tile_side(self.tile)):
+            return self.forward_tiled(lrs, alphas, self.tile, ensemble=self.ensemble, ref=ref)
+        if lrs.shape[2] != lrs.shape[3]:
+            raise ValueError("square low-res images only: the reference reinterprets (H,W) as (W,H) in its .view() "
+                             "(HRNet.py:204), which is the identity only for H == W"
+                             + ("" if graph else "; forward_tiled (or the `tile` attribute) takes scenes of any shape at inference"))
+        if graph:
+            names = [k for k, _ in self.named_parameters()]
+            params = [p for _, p in self.named_parameters()]
+            dt = self._train_dtype()
+            if dt is None:
+                if self._dtype() == binding.BF16:
+                    raise NotImplementedError(
+                        "HRNet(precision='bf16') without train_precision recomputes its forward in fp32 when a backward pass comes; that "
+                        "path does not carry a reference frame.  Set train_precision ('fp32', 'bf16' or 'bf16x3') to train with ref=, or "
+                        "call under no_grad / .eval() for inference.")
+                dt = self._dtype()
+            if names != binding.hrnet_param_names(self._num_layers):
+                raise RuntimeError("HRNet parameters are not in the reference's registration order")
+            packed = self._packed_for(dt)
+            sr, _tws = torch.ops.hrnet_hip.hrnet_forward_train_ref(packed, lrs.float().contiguous(), alphas.float().contiguous(), ref,
+                                                                   params, self._num_layers, bool(self.fuse.alpha_residual), dt,
+                                                                   self._scale)
+            return sr
+        if self.ensemble is not None and augment.check_mode(self.ensemble) is not None:
+            return self.forward_ensemble(lrs, alphas, self.ensemble, ref=ref)
+        packed, dt = self.packed_parameters()
+        return torch.ops.hrnet_hip.hrnet_forward_ref(packed, dt, self._num_layers, bool(self.fuse.alpha_residual), lrs.detach(),
+                                                     alphas.detach(), ref.detach(), self._scale)
+
+    def forward_ensemble(self, lrs, alphas, mode="dihedral", members_per_pass=None, ref=None):
         """Self-ensemble at inference: (B,L,H,W), (B,L) -> (B,1,SH,SW), the mean over the K = 4 ("flip") or 8 ("dihedral") members
         of augment.ensemble_codes(mode) of `forward(apply(lrs, code))` transformed back with the inverse code; bit for bit
         `augment.mean_inverse(forward(member-major batch), codes)`.  Always the inference kernels of `precision`, no autograd graph.
         One hrn_dihedral_expand launch builds the (K*B, L, H, W) member-major batch, the forward writes into slices of one
         (K, B, 1, SH, SW) buffer, one hrn_dihedral_mean launch averages.  members_per_pass (1..K, default K): how many members one
-        forward takes, which bounds its workspace; a sample's result does not depend on its batch, so this changes no bit."""
+        forward takes, which bounds its workspace; a sample's result does not depend on its batch, so this changes no bit.
+        ref (B,H,W): the reference frame; every member receives it under the member's own transform (the same expand, as a one-view stack)."""
         codes = augment.ensemble_codes(mode)
         K = len(codes)
         per_pass = K if members_per_pass is None else members_per_pass
@@ -262,15 +310,19 @@ class HRNet(nn.Module):
             raise ValueError(f"alphas must be {tuple(lrs.shape[:2])}; got {tuple(alphas.shape)}")
         B, V, H, W = lrs.shape
         S = self._scale
+        if ref is not None:
+            ref = binding._ref_frame(ref, lrs)
         packed, dt = self.packed_parameters()
         with torch.no_grad():
             members = torch.ops.hrnet_hip.dihedral_expand(lrs.detach().float().contiguous(), codes)         # (K,B,V,H,W)
+            refs = None if ref is None else torch.ops.hrnet_hip.dihedral_expand(ref.detach().view(B, 1, H, W), codes)      # (K,B,1,H,W)
             alphas = alphas.detach().float().contiguous()
             srs = torch.empty((K, B, 1, S * H, S * W), dtype=torch.float32, device=members.device)
             for k0 in range(0, K, per_pass):
                 k1 = min(K, k0 + per_pass)
                 binding.hrnet_forward(packed, dt, self._num_layers, self.fuse.alpha_residual, members[k0:k1].view(-1, V, H, W),
-                                      alphas.repeat(k1 - k0, 1), out=srs[k0:k1].view(-1, 1, S * H, S * W), scale=S)
+                                      alphas.repeat(k1 - k0, 1), out=srs[k0:k1].view(-1, 1, S * H, S * W), scale=S,
+                                      ref=None if refs is None else refs[k0:k1].view(-1, H, W))
             return torch.ops.hrnet_hip.dihedral_mean(srs, codes)
 
     @staticmethod
@@ -279,7 +331,7 @@ class HRNet(nn.Module):
             raise ValueError(f"tile must be a positive integer, got {tile!r}")
         return tile
 
-    def forward_tiled(self, lrs, alphas, tile=128, windows_per_pass=None, ensemble=None, members_per_pass=None):
+    def forward_tiled(self, lrs, alphas, tile=128, windows_per_pass=None, ensemble=None, members_per_pass=None, ref=None):
         """Inference on a scene of any size and aspect ratio: (B,L,H,W), (B,L) -> (B,1,SH,SW), H, W >= 1, from overlapping square
         windows of side t = min(tile, H, W) (hrnet_hip/tiling.py).  A window is responsible for its core, whose every edge is on the
         scene's border or at least R = tiling.halo(num_layers, L) LR pixels inside the window - the network's receptive field - so
@@ -296,7 +348,9 @@ class HRNet(nn.Module):
         (expand / forward / mean, `members_per_pass` members per forward).  For a square scene this is forward_ensemble of the whole
         frame; for a rectangular one it DEFINES the ensemble, transposing members included: the windows are square.
 
-        A scene that is one window (H == W <= tile) goes straight to the plain forward (or forward_ensemble)."""
+        A scene that is one window (H == W <= tile) goes straight to the plain forward (or forward_ensemble).
+
+        ref (B,H,W): the reference frame of the scene; every window receives its own cut of it (the same gather, as a one-view stack)."""
         tile = self._tile_side(tile)
         if lrs.dim() != 4 or lrs.numel() == 0:
             raise ValueError(f"lrs must be a non-empty (B, L, H, W); got {tuple(lrs.shape)}")
@@ -305,6 +359,8 @@ class HRNet(nn.Module):
         mode = augment.check_mode(ensemble)
         B, V, H, W = lrs.shape
         S = self._scale
+        if ref is not None:
+            ref = binding._ref_frame(ref, lrs).detach()
         per_pass = max(1, 32 // B) if windows_per_pass is None else windows_per_pass
         if isinstance(per_pass, bool) or not isinstance(per_pass, int) or per_pass < 1:
             raise ValueError(f"windows_per_pass must be a positive integer, got {windows_per_pass!r}")
@@ -315,8 +371,11 @@ class HRNet(nn.Module):
             raise ValueError(f"members_per_pass must be an integer in 1..{K}, got {members_per_pass!r}")
         if H == W and H <= tile:
             if mode is not None:
-                return self.forward_ensemble(lrs, alphas, mode, members_per_pass)
+                return self.forward_ensemble(lrs, alphas, mode, members_per_pass, ref=ref)
             packed, dt = self.packed_parameters()
+            if ref is not None:
+                return torch.ops.hrnet_hip.hrnet_forward_ref(packed, dt, self._num_layers, bool(self.fuse.alpha_residual), lrs.detach(),
+                                                             alphas.detach(), ref, S)
             return torch.ops.hrnet_hip.hrnet_forward(packed, dt, self._num_layers, bool(self.fuse.alpha_residual), lrs.detach(),
                                                      alphas.detach(), S)
         R = tiling.halo(self._num_layers, V)
@@ -332,18 +391,22 @@ class HRNet(nn.Module):
                 w1 = min(n, w0 + per_pass)
                 c = w1 - w0
                 wins = ops.tile_gather(lrs, t, R, w0, w1)                                                   # (c,B,V,t,t)
+                rwin = None if ref is None else ops.tile_gather(ref.view(B, 1, H, W), t, R, w0, w1).view(-1, t, t)          # (c*B,t,t)
                 a = alphas.repeat(c, 1)
                 if codes is None:
-                    srs = binding.hrnet_forward(packed, dt, self._num_layers, self.fuse.alpha_residual, wins.view(-1, V, t, t), a, scale=S)
+                    srs = binding.hrnet_forward(packed, dt, self._num_layers, self.fuse.alpha_residual, wins.view(-1, V, t, t), a, scale=S,
+                                                ref=rwin)
                 else:                                                                                       # forward_ensemble on c * B samples
                     members = ops.dihedral_expand(wins.view(-1, V, t, t), codes)                            # (K,c*B,V,t,t)
+                    rmem = None if rwin is None else ops.dihedral_expand(rwin.view(-1, 1, t, t), codes)      # (K,c*B,1,t,t)
                     srs = torch.empty((K, c * B, 1, S * t, S * t), dtype=torch.float32, device=lrs.device)
                     for k0 in range(0, K, m_pass):
                         k1 = min(K, k0 + m_pass)
                         binding.hrnet_forward(packed, dt, self._num_layers, self.fuse.alpha_residual, members[k0:k1].view(-1, V, t, t),
-                                              a.repeat(k1 - k0, 1), out=srs[k0:k1].view(-1, 1, S * t, S * t), scale=S)
+                                              a.repeat(k1 - k0, 1), out=srs[k0:k1].view(-1, 1, S * t, S * t), scale=S,
+                                              ref=None if rmem is None else rmem[k0:k1].view(-1, t, t))
                     srs = ops.dihedral_mean(srs, codes)
-                    del members
+                    del members, rmem
                 ops.tile_scatter(out, srs.view(c, B, 1, S * t, S * t), t, R, S, w0, w1)
                 del wins, srs                     # before the next chunk is allocated: one chunk at a time, as the bound says
             return out

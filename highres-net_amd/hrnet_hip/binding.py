@@ -104,6 +104,14 @@ SIGNATURES = {
     "hrn_hrnet_backward_sel": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(HrnetParams), _c.c_int, _c.c_void_p, _c.c_void_p,
                                           _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(HrnetParams), _c.c_void_p,
                                           _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_masked_composite": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 5 + [_c.c_void_p] * 4),
+    "hrn_hrnet_forward_ref": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                         _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_hrnet_forward_train_ref": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                               _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "hrn_hrnet_backward_ref": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(HrnetParams), _c.c_int, _c.c_void_p, _c.c_void_p,
+                                          _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(HrnetParams),
+                                          _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_shiftnet_packed_bytes": (_c.c_size_t, []),
     "hrn_shiftnet_pack": (_c.c_int, [_c.POINTER(ShiftnetParams), _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_shiftnet_workspace_bytes": (_c.c_size_t, [_c.c_int]),
@@ -338,19 +346,40 @@ def hrnet_workspace(dtype, B, V, H, W, device):
     return _workspace(n, device, "hrnet")
 
 
-def hrnet_forward(packed, dtype, num_layers, alpha_residual, lrs, alphas, out=None, scale=3):
-    """-> sr (B, 1, scale H, scale W); `packed` is the blob of hrnet_pack at this dtype and scale."""
+def _ref_frame(ref, lrs):
+    """the reference frame given to the network: a float (B,H,W) tensor on the device of lrs (B,V,H,W) -> contiguous f32"""
+    if not isinstance(ref, torch.Tensor):
+        raise TypeError(f"ref must be a torch.Tensor, got {type(ref).__name__}")
+    if not ref.is_floating_point():
+        raise TypeError(f"ref must be a floating-point tensor, got {ref.dtype}")
+    want = (lrs.shape[0],) + tuple(lrs.shape[2:])
+    if tuple(ref.shape) != want:
+        raise ValueError(f"ref must be (B,H,W) = {want} for lrs {tuple(lrs.shape)}; got {tuple(ref.shape)}")
+    if ref.device != lrs.device:
+        raise RuntimeError(f"ref is on '{ref.device}' but lrs on '{lrs.device}': the reference frame must be on the views' device")
+    return ref.float().contiguous()
+
+
+def hrnet_forward(packed, dtype, num_layers, alpha_residual, lrs, alphas, out=None, scale=3, ref=None):
+    """-> sr (B, 1, scale H, scale W); `packed` is the blob of hrnet_pack at this dtype and scale.  ref (B,H,W): the reference frame in place
+    of the median of lrs[:, :9] (hrn_hrnet_forward_ref)."""
     lib = load_library()
     lrs = _dev_f32(lrs, "lrs")
     alphas = _dev_f32(alphas, "alphas").to(lrs.device)
     if lrs.dim() != 4 or alphas.shape != lrs.shape[:2]:
         raise ValueError(f"lrs must be (B,V,H,W) and alphas (B,V); got {tuple(lrs.shape)} / {tuple(alphas.shape)}")
     B, V, H, W = lrs.shape
+    if ref is not None:
+        ref = _ref_frame(ref, lrs)
     with torch.cuda.device(lrs.device):
         ws = hrnet_workspace(dtype, B, V, H, W, lrs.device)
         if out is not None and (tuple(out.shape) != (B, 1, scale * H, scale * W) or out.dtype != torch.float32 or not out.is_contiguous()):
             raise ValueError(f"out must be a contiguous float32 tensor of shape {(B, 1, scale * H, scale * W)}")
         sr = out if out is not None else torch.empty((B, 1, scale * H, scale * W), dtype=torch.float32, device=lrs.device)
+        if ref is not None:
+            _check(lib.hrn_hrnet_forward_ref(_ptr(packed), dtype, num_layers, scale, int(bool(alpha_residual)), _ptr(lrs), _ptr(alphas),
+                                             _ptr(ref), B, V, H, W, _ptr(sr), _ptr(ws), ws.numel(), _stream()), "hrn_hrnet_forward_ref")
+            return sr
         _check(lib.hrn_hrnet_forward_s(_ptr(packed), dtype, num_layers, scale, int(bool(alpha_residual)), _ptr(lrs), _ptr(alphas),
                                        B, V, H, W, _ptr(sr), _ptr(ws), ws.numel(), _stream()), "hrn_hrnet_forward")
     return sr
@@ -397,31 +426,41 @@ def hrnet_decoder(packed, dtype, num_layers, fused, scale=3):
     return sr
 
 
-def hrnet_forward_train(packed_f32, lrs, alphas, num_layers, alpha_residual, dtype=F32, scale=3):
+def hrnet_forward_train(packed_f32, lrs, alphas, num_layers, alpha_residual, dtype=F32, scale=3, ref=None):
     """Training forward: returns (sr, train_ws); train_ws holds every intermediate for hrnet_backward.  dtype F32 (exact-fp32 MFMA),
     BF16X3 (split-bf16: `packed_f32` is then the BF16X3 blob and the workspace holds pairs of bf16 planes) or BF16 (`packed_f32` the BF16
-    blob, one bf16 plane per activation, fp32 accumulation)."""
+    blob, one bf16 plane per activation, fp32 accumulation).  ref (B,H,W) contiguous f32: the reference frame in place of the median
+    (hrn_hrnet_forward_train_ref); it is read in place, so hand the same, unchanged tensor to hrnet_backward."""
     lib = load_library()
     lrs = _dev_f32(lrs, "lrs")
     alphas = _dev_f32(alphas, "alphas")
     B, V, H, W = lrs.shape
+    if ref is not None:
+        ref = _ref_frame(ref, lrs)
     nbytes = lib.hrn_hrnet_train_workspace_bytes(num_layers, B, V, H, W)
     if nbytes == 0:
         raise HrnetHipError(f"bad training shape B={B} V={V} H={H} W={W} num_layers={num_layers}")
     tws = torch.empty(nbytes, dtype=torch.uint8, device=lrs.device)
     sr = torch.empty((B, 1, scale * H, scale * W), dtype=torch.float32, device=lrs.device)
     with torch.cuda.device(lrs.device):
+        if ref is not None:
+            _check(lib.hrn_hrnet_forward_train_ref(_ptr(packed_f32), int(dtype), num_layers, int(scale), int(bool(alpha_residual)), _ptr(lrs),
+                                                   _ptr(alphas), _ptr(ref), B, V, H, W, _ptr(sr), _ptr(tws), nbytes, _stream()),
+                   "hrn_hrnet_forward_train_ref")
+            return sr, tws
         _check(lib.hrn_hrnet_forward_train_s(_ptr(packed_f32), int(dtype), num_layers, int(scale), int(bool(alpha_residual)), _ptr(lrs),
                                              _ptr(alphas), B, V, H, W, _ptr(sr), _ptr(tws), nbytes, _stream()), "hrn_hrnet_forward_train")
     return sr, tws
 
 
 def hrnet_backward(packed_f32, named_params, named_grads, num_layers, alpha_residual, lrs, alphas, d_sr, tws, dtype=F32, scale=3,
-                   d_lrs=None, d_alphas=None, select=False):
+                   d_lrs=None, d_alphas=None, select=False, ref=None, d_ref=None):
     """Accumulates dLoss/dparam into named_grads (same keys / shapes as named_params, f32, zero them for plain gradients).  d_lrs
     (B,V,H,W) / d_alphas (B,V): contiguous f32 device tensors that receive (are overwritten with) the input gradients, or None.
     select: named_grads holds only the parameters that want a gradient (the work of the others is skipped); otherwise it must hold
-    every parameter.  One C call either way: hrn_hrnet_backward_sel, which leaves out whatever a NULL field or pointer does not ask for."""
+    every parameter.  One C call either way: hrn_hrnet_backward_sel, which leaves out whatever a NULL field or pointer does not ask for.
+    ref (B,H,W): the reference frame the training forward was given (hrn_hrnet_backward_ref); d_lrs is then the stem's channel 0 alone, and
+    d_ref (B,H,W) or None receives the frame's gradient."""
     lib = load_library()
     lrs = _dev_f32(lrs, "lrs")
     alphas = _dev_f32(alphas, "alphas")
@@ -437,10 +476,20 @@ def hrnet_backward(packed_f32, named_params, named_grads, num_layers, alpha_resi
             raise ValueError("gradient buffers must match the parameters' shapes and not alias them")
     if select and (set(named_grads) - set(hrnet_param_names(num_layers))):
         raise ValueError(f"unknown HRNet parameters among the gradients: {sorted(set(named_grads) - set(hrnet_param_names(num_layers)))}")
-    for name, t, shape in (("d_lrs", d_lrs, (B, V, H, W)), ("d_alphas", d_alphas, (B, V))):
+    if ref is not None:
+        ref = _ref_frame(ref, lrs)
+    elif d_ref is not None:
+        raise ValueError("d_ref needs ref: without an outside frame its gradient is routed into d_lrs")
+    for name, t, shape in (("d_lrs", d_lrs, (B, V, H, W)), ("d_alphas", d_alphas, (B, V)), ("d_ref", d_ref, (B, H, W))):
         if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != lrs.device):
             raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on {lrs.device}")
+    opt = lambda t: _ptr(t) if t is not None else None
     with torch.cuda.device(lrs.device):
+        if ref is not None:
+            _check(lib.hrn_hrnet_backward_ref(_ptr(packed_f32), int(dtype), int(scale), ctypes.byref(P), int(bool(alpha_residual)),
+                                              _ptr(lrs), _ptr(alphas), _ptr(ref), B, V, H, W, _ptr(d_sr), ctypes.byref(G), opt(d_lrs),
+                                              opt(d_alphas), opt(d_ref), _ptr(tws), tws.numel(), _stream()), "hrn_hrnet_backward_ref")
+            return
         _check(lib.hrn_hrnet_backward_sel(_ptr(packed_f32), int(dtype), int(scale), ctypes.byref(P), int(bool(alpha_residual)),
                                           _ptr(lrs), _ptr(alphas), B, V, H, W, _ptr(d_sr), ctypes.byref(G),
                                           _ptr(d_lrs) if d_lrs is not None else None, _ptr(d_alphas) if d_alphas is not None else None,
@@ -1356,6 +1405,24 @@ def mncc_apply_field(views, view_masks, field, block):
     return out, valid
 
 
+# --------------------------------------------------------------------------- cloud-free composite reference frame
+COMPOSITE_MAX_REF = 32    # hrn_masked_composite: 1 <= n_ref <= 32
+
+
+def masked_composite(lrs, lr_masks=None, alphas=None, n_ref=9, want_count=False, fill=True):
+    """hrn_masked_composite on contiguous f32 device tensors (hrnet_hip/composite.py checks them): -> (ref (B,H,W), filled (B,V,H,W) or
+    None, count (B,H,W) or None)."""
+    lib = load_library()
+    B, V, H, W = lrs.shape
+    ref = torch.empty((B, H, W), dtype=torch.float32, device=lrs.device)
+    filled = torch.empty((B, V, H, W), dtype=torch.float32, device=lrs.device) if fill else None
+    count = torch.empty((B, H, W), dtype=torch.float32, device=lrs.device) if want_count else None
+    with torch.cuda.device(lrs.device):
+        _check(lib.hrn_masked_composite(_ptr(lrs), _opt_ptr(lr_masks), _opt_ptr(alphas), B, V, H, W, int(n_ref), _ptr(ref), _opt_ptr(count),
+                                        _opt_ptr(filled), _stream()), "hrn_masked_composite")
+    return ref, filled, count
+
+
 # --------------------------------------------------------------------------- PyTorch-ROCm custom ops (north_star: "exposed to Python as
 # PyTorch-ROCm custom ops"): the inference entry points are registered with the dispatcher as torch.ops.hrnet_hip.*, with fake
 # (meta) implementations, so that they are visible to torch.compile / export and to anyone calling through torch.ops.  Each is a
@@ -1370,6 +1437,36 @@ def _op_hrnet_forward(packed: torch.Tensor, dtype: int, num_layers: int, alpha_r
 def _(packed, dtype, num_layers, alpha_residual, lrs, alphas, scale=3):
     b, _, h, w = lrs.shape
     return lrs.new_empty((b, 1, scale * h, scale * w), dtype=torch.float32)
+
+
+@torch.library.custom_op("hrnet_hip::hrnet_forward_ref", mutates_args=(), device_types="cuda")
+def _op_hrnet_forward_ref(packed: torch.Tensor, dtype: int, num_layers: int, alpha_residual: bool, lrs: torch.Tensor,
+                          alphas: torch.Tensor, ref: torch.Tensor, scale: int = 3) -> torch.Tensor:
+    """hrnet_forward with the reference frame `ref` (B,H,W) in place of the median of lrs[:, :9] (hrn_hrnet_forward_ref)."""
+    return hrnet_forward(packed, dtype, num_layers, alpha_residual, lrs, alphas, scale=scale, ref=ref)
+
+
+@_op_hrnet_forward_ref.register_fake
+def _(packed, dtype, num_layers, alpha_residual, lrs, alphas, ref, scale=3):
+    b, _, h, w = lrs.shape
+    return lrs.new_empty((b, 1, scale * h, scale * w), dtype=torch.float32)
+
+
+@torch.library.custom_op("hrnet_hip::masked_composite", mutates_args=(), device_types="cuda")
+def _op_masked_composite(lrs: torch.Tensor, lr_masks: Optional[torch.Tensor], alphas: Optional[torch.Tensor], n_ref: int, want_count: bool,
+                         fill: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """hrn_masked_composite: (ref (B,H,W), filled (B,V,H,W), count (B,H,W)); an output that was not asked for comes back empty.  No
+    gradient: the frame is data."""
+    ref, filled, count = masked_composite(lrs, lr_masks, alphas, n_ref, want_count, fill)
+    return (ref, filled if fill else lrs.new_empty((0,), dtype=torch.float32),
+            count if want_count else lrs.new_empty((0,), dtype=torch.float32))
+
+
+@_op_masked_composite.register_fake
+def _(lrs, lr_masks, alphas, n_ref, want_count, fill):
+    b, _, h, w = lrs.shape
+    return (lrs.new_empty((b, h, w), dtype=torch.float32), lrs.new_empty(lrs.shape if fill else (0,), dtype=torch.float32),
+            lrs.new_empty((b, h, w) if want_count else (0,), dtype=torch.float32))
 
 
 @torch.library.custom_op("hrnet_hip::lanczos_shift", mutates_args=(), device_types="cuda")
@@ -1464,7 +1561,7 @@ def _(packed, lrs, alphas, params, num_layers, alpha_residual, dtype, scale=3):
 
 
 def _hrnet_backward_body(packed, params, lrs, alphas, d_sr, tws, num_layers, alpha_residual, dtype, scale, need_params=None,
-                         need_lrs=False, need_alphas=False):
+                         need_lrs=False, need_alphas=False, ref=None, need_ref=False):
     """The three HRNet backward ops: (parameter gradients in `hrnet_param_names` order, d_lrs, d_alphas), an empty tensor for whatever
     was not asked for.  need_params None: every parameter; else need_params[i] says whether params[i] wants a gradient."""
     names = hrnet_param_names(num_layers)
@@ -1475,6 +1572,14 @@ def _hrnet_backward_body(packed, params, lrs, alphas, d_sr, tws, num_layers, alp
              for i, (k, p) in enumerate(named.items()) if need_params is None or need_params[i]}
     d_lrs = torch.empty(lrs.shape, dtype=torch.float32, device=lrs.device) if need_lrs else None
     d_alphas = torch.empty(alphas.shape, dtype=torch.float32, device=alphas.device) if need_alphas else None
+    if ref is not None:
+        d_ref = torch.empty(ref.shape, dtype=torch.float32, device=ref.device) if need_ref else None
+        hrnet_backward(packed, named, grads, num_layers, alpha_residual, lrs, alphas, d_sr.contiguous(), tws, dtype, scale, d_lrs=d_lrs,
+                       d_alphas=d_alphas, select=True, ref=ref, d_ref=d_ref)
+        return ([grads[k] if k in grads else named[k].new_empty((0,), dtype=torch.float32) for k in names],
+                d_lrs if need_lrs else lrs.new_empty((0,), dtype=torch.float32),
+                d_alphas if need_alphas else alphas.new_empty((0,), dtype=torch.float32),
+                d_ref if need_ref else ref.new_empty((0,), dtype=torch.float32))
     hrnet_backward(packed, named, grads, num_layers, alpha_residual, lrs, alphas, d_sr.contiguous(), tws, dtype, scale, d_lrs=d_lrs,
                    d_alphas=d_alphas, select=need_params is not None)
     return ([grads[k] if k in grads else named[k].new_empty((0,), dtype=torch.float32) for k in names],
@@ -1560,6 +1665,71 @@ def _hrnet_train_backward(ctx, d_sr, _d_tws):
 
 
 _op_hrnet_forward_train.register_autograd(_hrnet_train_backward, setup_context=_hrnet_train_setup)
+
+
+# the training pair with the reference frame given (hrn_hrnet_forward_train_ref / hrn_hrnet_backward_ref)
+@torch.library.custom_op("hrnet_hip::hrnet_forward_train_ref", mutates_args=(), device_types="cuda")
+def _op_hrnet_forward_train_ref(packed: torch.Tensor, lrs: torch.Tensor, alphas: torch.Tensor, ref: torch.Tensor,
+                                params: Sequence[torch.Tensor], num_layers: int, alpha_residual: bool, dtype: int,
+                                scale: int = 3) -> Tuple[torch.Tensor, torch.Tensor]:
+    """hrnet_forward_train with the reference frame `ref` (B,H,W) contiguous f32 in place of the median of lrs[:, :9]; `ref` is a
+    differentiable input of its own (its gradient: the stem's second input channel summed over the views)."""
+    return hrnet_forward_train(packed, lrs, alphas, num_layers, alpha_residual, dtype, scale, ref=ref)
+
+
+@_op_hrnet_forward_train_ref.register_fake
+def _(packed, lrs, alphas, ref, params, num_layers, alpha_residual, dtype, scale=3):
+    b, v, h, w = lrs.shape
+    nbytes = load_library().hrn_hrnet_train_workspace_bytes(num_layers, b, v, h, w)
+    return lrs.new_empty((b, 1, scale * h, scale * w), dtype=torch.float32), lrs.new_empty((nbytes,), dtype=torch.uint8)
+
+
+@torch.library.custom_op("hrnet_hip::hrnet_backward_ref", mutates_args=("tws",), device_types="cuda")
+def _op_hrnet_backward_ref(packed: torch.Tensor, params: Sequence[torch.Tensor], lrs: torch.Tensor, alphas: torch.Tensor, ref: torch.Tensor,
+                           d_sr: torch.Tensor, tws: torch.Tensor, num_layers: int, alpha_residual: bool, dtype: int, scale: int,
+                           need_params: Sequence[bool], need_lrs: bool, need_alphas: bool,
+                           need_ref: bool) -> Tuple[List[torch.Tensor], torch.Tensor, torch.Tensor, torch.Tensor]:
+    """hrnet_backward_sel for a forward that was given its reference frame (hrn_hrnet_backward_ref): (parameter gradients, d_lrs - the
+    stem's channel 0 alone -, d_alphas, d_ref (B,H,W)); whatever was not asked for comes back empty."""
+    return _hrnet_backward_body(packed, params, lrs, alphas, d_sr, tws, num_layers, alpha_residual, dtype, scale, list(need_params), need_lrs,
+                                need_alphas, ref=ref, need_ref=need_ref)
+
+
+@_op_hrnet_backward_ref.register_fake
+def _(packed, params, lrs, alphas, ref, d_sr, tws, num_layers, alpha_residual, dtype, scale, need_params, need_lrs, need_alphas, need_ref):
+    return ([p.new_empty(p.shape if need else (0,), dtype=torch.float32) for p, need in zip(params, need_params)],
+            lrs.new_empty(lrs.shape if need_lrs else (0,), dtype=torch.float32),
+            alphas.new_empty(alphas.shape if need_alphas else (0,), dtype=torch.float32),
+            ref.new_empty(ref.shape if need_ref else (0,), dtype=torch.float32))
+
+
+def _hrnet_train_ref_setup(ctx, inputs, output):
+    packed, lrs, alphas, ref, params, num_layers, alpha_residual, dtype, scale = inputs
+    ctx.num_layers, ctx.alpha_residual, ctx.n, ctx.dtype, ctx.scale = num_layers, alpha_residual, len(params), dtype, scale
+    ctx.need_params = [bool(p.requires_grad) for p in params]
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(packed, lrs, alphas, ref, output[1], *params)
+
+
+def _hrnet_train_ref_backward(ctx, d_sr, _d_tws):
+    packed, lrs, alphas, ref, tws, *params = ctx.saved_tensors
+    tail = (None,) * (len(ctx.needs_input_grad) - 5)
+    none = (None, None, None, None, [None] * len(params)) + tail
+    if d_sr is None:
+        return none
+    need_lrs, need_ref = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+    need_alphas = ctx.needs_input_grad[2] and bool(ctx.alpha_residual) and lrs.shape[1] > 1
+    if not (any(ctx.need_params) or need_lrs or need_alphas or need_ref):
+        return none
+    grads, d_lrs, d_alphas, d_ref = torch.ops.hrnet_hip.hrnet_backward_ref(packed, params, lrs, alphas, ref, d_sr, tws.data, ctx.num_layers,
+                                                                           ctx.alpha_residual, ctx.dtype, ctx.scale, ctx.need_params,
+                                                                           need_lrs, need_alphas, need_ref)
+    return (None, d_lrs.to(lrs.dtype) if need_lrs else None, d_alphas.to(alphas.dtype) if need_alphas else None,
+            d_ref.to(ref.dtype) if need_ref else None,
+            [g.to(p.dtype) if need else None for g, p, need in zip(grads, params, ctx.need_params)]) + tail
+
+
+_op_hrnet_forward_train_ref.register_autograd(_hrnet_train_ref_backward, setup_context=_hrnet_train_ref_setup)
 
 
 def _shiftnet_named(params, buffers):

@@ -61,15 +61,16 @@ int check_common(int dt, int nl, int B, int V, int H, int W) {
     return 0;
 }
 
-int encoder_impl(const void* pk, int dt, int nl, const float* lrs, int B, int V, int H, int W,
+// ext_ref: the reference frame (B,H,W) the stem reads in place of the median of lrs[:, :9] (null: the median, into the workspace's slot)
+int encoder_impl(const void* pk, int dt, int nl, const float* lrs, const float* ext_ref, int B, int V, int H, int W,
                  void* emb, void* ws, const HrnetWs& wl, hipStream_t s) {
     const HrnetLayout L = hrnet_layout(dt, nl, 3);        // (the encoder's offsets are the same at every scale)
     const size_t hw = (size_t)H * W;
-    float* ref = (float*)at(ws, wl.ref);
+    const float* ref = ext_ref ? ext_ref : (const float*)at(ws, wl.ref);
     void* bufA = at(ws, wl.buf_a);
     void* bufB = at(ws, wl.buf_b);
     int rc;
-    if ((rc = hrn_launch_median(lrs, ref, B, V, H, W, s))) return rc;
+    if (!ext_ref && (rc = hrn_launch_median(lrs, (float*)at(ws, wl.ref), B, V, H, W, s))) return rc;
     // stem: channel 0 = view, channel 1 = the sample's reference frame; 2->64 + PReLU  (HRNet.py:200-204, :51-53)
     const size_t lo = stack_lo(dt, B, V, H, W);        // bf16x3: lo plane of bufA / bufB / emb (0 otherwise)
     const ConvSite& stem = L.site[SITE_STEM];
@@ -219,7 +220,7 @@ int hrn_encoder_forward(const void* packed, int dt, int nl, const float* lrs, in
     HRN_CHECK(packed && lrs && emb && ws, -2, "hrn_encoder_forward: null argument");
     const HrnetWs wl = hrnet_ws(dt, B, V, H, W);
     HRN_CHECK(ws_bytes >= wl.total, -3, "hrn_encoder_forward: workspace too small (%zu < %zu)", ws_bytes, wl.total);
-    return encoder_impl(packed, dt, nl, lrs, B, V, H, W, emb, ws, wl, (hipStream_t)stream);
+    return encoder_impl(packed, dt, nl, lrs, nullptr, B, V, H, W, emb, ws, wl, (hipStream_t)stream);
 }
 
 int hrn_fuse_forward(const void* packed, int dt, int nl, int alpha_residual, void* emb, const float* alphas,
@@ -239,8 +240,8 @@ int hrn_decoder_forward_s(const void* packed, int dt, int nl, int scale, const v
     return decoder_impl(packed, dt, nl, scale, fused, N, H, W, sr, (hipStream_t)stream);
 }
 
-int hrn_hrnet_forward_s(const void* packed, int dt, int nl, int scale, int alpha_residual, const float* lrs, const float* alphas,
-                        int B, int V, int H, int W, float* sr, void* ws, size_t ws_bytes, void* stream) {
+static int hrnet_forward_impl(const void* packed, int dt, int nl, int scale, int alpha_residual, const float* lrs, const float* alphas,
+                              const float* ext_ref, int B, int V, int H, int W, float* sr, void* ws, size_t ws_bytes, void* stream) {
     int rc;
     if ((rc = check_scale(scale)) || (rc = check_common(dt, nl, B, V, H, W))) return rc;
     HRN_CHECK(packed && lrs && alphas && sr && ws, -2, "hrn_hrnet_forward: null argument");
@@ -249,9 +250,20 @@ int hrn_hrnet_forward_s(const void* packed, int dt, int nl, int scale, int alpha
     hipStream_t s = (hipStream_t)stream;
     void* emb = at(ws, wl.emb);
     void* fused = at(ws, wl.fused);
-    if ((rc = encoder_impl(packed, dt, nl, lrs, B, V, H, W, emb, ws, wl, s))) return rc;
+    if ((rc = encoder_impl(packed, dt, nl, lrs, ext_ref, B, V, H, W, emb, ws, wl, s))) return rc;
     if ((rc = fuse_impl(packed, dt, nl, alpha_residual, emb, alphas, B, V, H, W, fused, ws, wl, s))) return rc;
     return decoder_impl(packed, dt, nl, scale, fused, B, H, W, sr, s);
+}
+
+int hrn_hrnet_forward_s(const void* packed, int dt, int nl, int scale, int alpha_residual, const float* lrs, const float* alphas,
+                        int B, int V, int H, int W, float* sr, void* ws, size_t ws_bytes, void* stream) {
+    return hrnet_forward_impl(packed, dt, nl, scale, alpha_residual, lrs, alphas, nullptr, B, V, H, W, sr, ws, ws_bytes, stream);
+}
+
+int hrn_hrnet_forward_ref(const void* packed, int dt, int nl, int scale, int alpha_residual, const float* lrs, const float* alphas,
+                          const float* ref, int B, int V, int H, int W, float* sr, void* ws, size_t ws_bytes, void* stream) {
+    HRN_CHECK(ref, -2, "hrn_hrnet_forward_ref: null argument (ref)");
+    return hrnet_forward_impl(packed, dt, nl, scale, alpha_residual, lrs, alphas, ref, B, V, H, W, sr, ws, ws_bytes, stream);
 }
 
 // ----------------------------------------------------------------- ShiftNet

@@ -70,6 +70,10 @@ int hrn_conv_dgrad(int dt, int cin, int cout, const float* w, const void* g, voi
 // wt: scratch for 64 * 18 floats (the weights transposed tap-major)
 int hrn_launch_stem_dgrad_route(int dt, const void* dA, const float* w, float* wt, const float* lrs, const float* ref, float* d_lrs, int B,
                                 int V, int H, int W, hipStream_t s);
+// The same data gradient for a reference frame that came from outside (no median to route to): d_lrs [B][V][H][W] gets channel 0 alone,
+// d_ref [B][H][W] channel 1 summed over the sample's views in view order.  Either may be null (not both)
+int hrn_launch_stem_dgrad_ref(int dt, const void* dA, const float* w, float* wt, float* d_lrs, float* d_ref, int B, int V, int H, int W,
+                              hipStream_t s);
 // One fusion level's alpha gradient: d_alphas[b][pair_last - v] = sum over pixels and channels of dsn * f, image b * half + v of the
 // level's outputs ([B*half][hw][64] each, dt); uses hrn_alpha_grad_scratch_bytes(B * half) bytes of `scratch`
 size_t hrn_alpha_grad_scratch_bytes(int nimg);

@@ -145,6 +145,86 @@ __global__ __launch_bounds__(256) void stem_dgrad_route_kernel(const void* __res
     if (inside) d_lrs[((size_t)b * V + sel) * hw + pix] = keep + acc1;
 }
 
+// The same data gradient for a reference frame that came from outside (hrn_hrnet_backward_ref): there is no median to route to, so d_lrs (or
+// null) gets channel 0 alone and d_ref (or null) [B][H][W] channel 1 summed over the sample's views in view order.  The text of the kernel
+// above with the routing taken out, as a kernel of its own: the routed kernel keeps its device code, register allocation included
+template <int ST>
+__global__ __launch_bounds__(256) void stem_dgrad_ref_kernel(const void* __restrict__ dA, const float* __restrict__ wt,
+                                                             float* __restrict__ d_lrs, float* __restrict__ d_ref, int B, int V, int H,
+                                                             int W) {
+    __shared__ __attribute__((aligned(16))) float tile[SD_HH * SD_HW * SD_PS];
+    const int tid = threadIdx.x, tx = tid & (SD_TW - 1), ty = tid / SD_TW;
+    const int tiles_x = (W + SD_TW - 1) / SD_TW, tiles_y = (H + SD_TH - 1) / SD_TH, tiles = tiles_x * tiles_y;
+    const int b = blockIdx.x / tiles, t = blockIdx.x - b * tiles;
+    const int y0 = (t / tiles_x) * SD_TH, x0 = (t % tiles_x) * SD_TW;
+    const int gy = y0 + ty, gx = x0 + tx;
+    const bool inside = gy < H && gx < W;
+    const size_t hw = (size_t)H * W, pix = (size_t)gy * W + gx;
+    const size_t lo = (size_t)B * V * hw * 64 * 2;          // bf16x3: byte offset of dA's lo plane
+    // the halo tile of one (view, 32-channel chunk) as raw 16-byte units, NLD per thread: chunk c + 1 is in flight while chunk c is
+    // computed from LDS
+    constexpr int NU = SD_HH * SD_HW * (SD_CC / 4), NLD = (NU + 255) / 256;
+    u32x4 raw[NLD];
+    unsigned ok = 0;                                        // bit u: unit u lies in the image (else it is stored as zero padding)
+    auto fetch = [&](int c) {
+        const size_t img = (size_t)b * V + (c >> 1);
+        const int k = c & 1;
+        ok = 0;
+#pragma unroll
+        for (int u = 0; u < NLD; ++u) {
+            const int i = tid + u * 256;
+            const int hp = i / (SD_CC / 4), q = i - hp * (SD_CC / 4);
+            const int hy = hp / SD_HW, hx = hp - hy * SD_HW;
+            const int yy = y0 + hy - 1, xx = x0 + hx - 1;
+            const bool in = i < NU && (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
+            ok |= (unsigned)in << u;
+            // unconditional load from a clamped address (no branch: the loads of all units stay in flight together)
+            const int cy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy), cx = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
+            raw[u] = ld_raw<ST>(dA, lo, (img * hw + (size_t)cy * W + cx) * 16 + k * (SD_CC / 4) + q);
+        }
+    };
+    float acc1 = 0.f, o0 = 0.f, o1 = 0.f;
+    fetch(0);
+#pragma unroll 1
+    for (int c = 0; c < 2 * V; ++c) {
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < NLD; ++u) {
+            const int i = tid + u * 256;
+            const int hp = i / (SD_CC / 4), q = i - hp * (SD_CC / 4);
+            const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+            if (i < NU) *(f32x4*)&tile[hp * SD_PS + q * 4] = (ok >> u) & 1 ? raw_to_f32<ST>(raw[u]) : z;
+        }
+        __syncthreads();
+        if (c + 1 < 2 * V) fetch(c + 1);
+        const int k = c & 1;
+        // one tap at a time (not unrolled): its 64 weights of the chunk are contiguous in wt and come in by scalar loads
+#pragma unroll 1
+        for (int tap = 0; tap < 9; ++tap) {
+            const int ky = tap / 3, kx = tap - ky * 3;
+            // forward: out[p] += W[tap] in[p + (ky-1, kx-1)]  =>  d in[q] += W[tap] dA[q - (ky-1, kx-1)]
+            const float* src = &tile[((ty + 2 - ky) * SD_HW + (tx + 2 - kx)) * SD_PS];
+            const float* wk = wt + ((size_t)tap * 64 + k * SD_CC) * 2;
+#pragma unroll
+            for (int j = 0; j < SD_CC / 4; ++j) {
+                const f32x4 d = *(const f32x4*)&src[j * 4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    o0 = fmaf(wk[(j * 4 + e) * 2], d[e], o0);
+                    o1 = fmaf(wk[(j * 4 + e) * 2 + 1], d[e], o1);
+                }
+            }
+        }
+        if (k == 1) {                                       // view c / 2 complete
+            const int v = c >> 1;
+            acc1 += o1;
+            if (inside && d_lrs) d_lrs[((size_t)b * V + v) * hw + pix] = o0;
+            o0 = o1 = 0.f;
+        }
+    }
+    if (inside && d_ref) d_ref[(size_t)b * hw + pix] = acc1;
+}
+
 // partial[img * P + part] = sum over part `part` of image img of dsn * f (fp32 per thread, double across the block, fixed tree)
 template <int ST>
 __global__ __launch_bounds__(256) void alpha_grad_partial_kernel(const void* __restrict__ dsn, const void* __restrict__ f, size_t img4,
@@ -195,6 +275,19 @@ int hrn_launch_stem_dgrad_route(int dt, const void* dA, const float* w, float* w
     HrnProfScope prof("stem_dgrad_route", 2.0 * 18 * 64 * px, px * (64.0 * 4 + 4) + (double)B * H * W * 4 * ((V < 9 ? V : 9) + 1), s);
     hipLaunchKernelGGL(stem_dgrad_weights_kernel, dim3((64 * 18 + 255) / 256), dim3(256), 0, s, w, wt);
     HRN_LAUNCH_ST(dt, stem_dgrad_route_kernel, dim3((unsigned)(tiles * B)), dim3(256), 0, s, dA, (const float*)wt, lrs, ref, d_lrs, B, V, H, W);
+    HRN_LAUNCH_CHECK();
+    return 0;
+}
+
+int hrn_launch_stem_dgrad_ref(int dt, const void* dA, const float* w, float* wt, float* d_lrs, float* d_ref, int B, int V, int H, int W,
+                              hipStream_t s) {
+    HRN_CHECK(d_lrs || d_ref, -2, "stem dgrad: neither d_lrs nor d_ref is wanted");
+    const long tiles = (long)((W + SD_TW - 1) / SD_TW) * ((H + SD_TH - 1) / SD_TH);
+    HRN_CHECK(tiles * B < (1L << 31), -2, "stem dgrad: %d samples of %d x %d exceed the grid", B, H, W);
+    const double px = (double)B * V * H * W;
+    HrnProfScope prof("stem_dgrad_ref", 2.0 * 18 * 64 * px, px * (64.0 * 4 + 4) + (double)B * H * W * 4, s);
+    hipLaunchKernelGGL(stem_dgrad_weights_kernel, dim3((64 * 18 + 255) / 256), dim3(256), 0, s, w, wt);
+    HRN_LAUNCH_ST(dt, stem_dgrad_ref_kernel, dim3((unsigned)(tiles * B)), dim3(256), 0, s, dA, (const float*)wt, d_lrs, d_ref, B, V, H, W);
     HRN_LAUNCH_CHECK();
     return 0;
 }

@@ -6,6 +6,9 @@
 #include "common.h"
 #include "conv3x3.h"
 
+// ---- composite.hip: the masked lower median of the first min(V, n_ref) views and the filled views (masks / alphas / count / filled may be null)
+int hrn_launch_masked_composite(const float* views, const float* masks, const float* alphas, int B, int V, int H, int W, int n_ref, float* ref,
+                                float* count, float* filled, hipStream_t stream);
 // ---- stem.hip
 int hrn_launch_median(const float* lrs, float* ref, int B, int V, int H, int W, hipStream_t stream);
 int hrn_launch_stem(int dt, const float* in0, size_t img_stride0, const float* in1, int rep1, size_t img_stride1,

@@ -162,9 +162,11 @@ size_t hrn_hrnet_train_workspace_bytes(int num_layers, int B, int V, int H, int 
 //   need_da[l]   the gradient of the encoder activation a_l (l = 0: the stem's output)
 // Decoder parameters need only the decoder's weight-gradient part; fusion parameters (shared by every level) and d_alphas (alpha
 // residual only) every level's data gradient above them; encoder / stem parameters and d_lrs the chain down to stack_0.
-int hrn_hrnet_backward_sel(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
-                           int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, float* d_lrs, float* d_alphas, void* tws,
-                           size_t tws_bytes, void* stream) {
+//   ext_ref      the reference frame of hrn_hrnet_forward_train_ref (null: the forward's own median, in the workspace); then d_lrs is the
+//                stem's channel 0 alone and d_ref (or null) its channel 1 summed over the sample's views
+static int backward_impl(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
+                         const float* ext_ref, int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, float* d_lrs,
+                         float* d_alphas, float* d_ref, void* tws, size_t tws_bytes, void* stream) {
     int rc;
     HRN_CHECK(hrn_scale_ok(scale), -2, "hrn_hrnet_backward: scale must be 2, 3 or 4 (got %d)", scale);
     HRN_CHECK(dt == HRN_F32 || dt == HRN_BF16 || dt == HRN_BF16X3, -2, "hrn_hrnet_backward: dtype must be HRN_DTYPE_F32, HRN_DTYPE_BF16 or HRN_DTYPE_BF16X3 (got %d)", dt);
@@ -184,7 +186,7 @@ int hrn_hrnet_backward_sel(const void* pk, int dt, int scale, const hrn_hrnet_pa
     const bool wA = want_site(kA), wB = want_site(kB), wC = want_site(kC), fuse = wA || wB || wC;
     const bool alpha = d_alphas && alpha_residual;
     bool need_da[HRN_MAX_RES_LAYERS + 1], need_ds[TMAX + 1];
-    need_da[0] = want_site(SITE_STEM) || d_lrs;
+    need_da[0] = want_site(SITE_STEM) || d_lrs || d_ref;
     for (int l = 0; l < nl; ++l) need_da[l + 1] = need_da[l] || want_site(site_enc(l, 0)) || want_site(site_enc(l, 1));
     need_ds[0] = need_da[nl] || want_site(kF);
     for (int t = 0; t < L.T; ++t) need_ds[t + 1] = need_ds[t] || fuse || alpha;
@@ -294,17 +296,34 @@ int hrn_hrnet_backward_sel(const void* pk, int dt, int scale, const hrn_hrnet_pa
     // stem: a_0 = PReLU(conv(cat(view, reference frame)))                               HRNet.py:200-204, :51-53
     const ConvSite& stem = P.site[SITE_STEM];
     const SiteParams pS = site_params(Pr, nl, SITE_STEM), gS = site_params(Gr, nl, SITE_STEM);
-    if ((rc = hrn_launch_stem_pre(dt, lrs, hw, (const float*)at(tws, L.ref), V, hw, (const float*)at(pk, stem.w), (const float*)at(pk, stem.b), xpre, M, H, W,
+    const float* ref = ext_ref ? ext_ref : (const float*)at(tws, L.ref);
+    if ((rc = hrn_launch_stem_pre(dt, lrs, hw, ref, V, hw, (const float*)at(pk, stem.w), (const float*)at(pk, stem.b), xpre, M, H, W,
                                   pS.a, s))) return rc;
     if ((rc = hrn_launch_prelu_bwd_bias(dt, dA, at(tws, L.a[0]), xpre, pS.a, dA, (size_t)M * hw, 64, mut(gS.a), mut(gS.b), sc, s))) return rc;
-    if (want(gS.w) && (rc = hrn_launch_stem_wgrad(dt, lrs, hw, (const float*)at(tws, L.ref), V, hw, dA, M, H, W, mut(gS.w), sc, cus, s))) return rc;
+    if (want(gS.w) && (rc = hrn_launch_stem_wgrad(dt, lrs, hw, ref, V, hw, dA, M, H, W, mut(gS.w), sc, cus, s))) return rc;
     // d lrs: the stem's input gradient, channel 1 (the reference frame) routed to the view the median picked
-    if (d_lrs) return hrn_launch_stem_dgrad_route(dt, dA, pS.w, (float*)at(tws, L.wt), lrs, (const float*)at(tws, L.ref), d_lrs, B, V, H, W, s);
+    if (ext_ref) return d_lrs || d_ref ? hrn_launch_stem_dgrad_ref(dt, dA, pS.w, (float*)at(tws, L.wt), d_lrs, d_ref, B, V, H, W, s) : 0;
+    if (d_lrs) return hrn_launch_stem_dgrad_route(dt, dA, pS.w, (float*)at(tws, L.wt), lrs, ref, d_lrs, B, V, H, W, s);
     return 0;
 }
 
-int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alpha_residual, const float* lrs, const float* alphas, int B, int V,
-                              int H, int W, float* sr, void* tws, size_t tws_bytes, void* stream) {
+int hrn_hrnet_backward_sel(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
+                           int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, float* d_lrs, float* d_alphas, void* tws,
+                           size_t tws_bytes, void* stream) {
+    return backward_impl(pk, dt, scale, Pr, alpha_residual, lrs, alphas, nullptr, B, V, H, W, d_sr, Gr, d_lrs, d_alphas, nullptr, tws, tws_bytes,
+                         stream);
+}
+
+int hrn_hrnet_backward_ref(const void* pk, int dt, int scale, const hrn_hrnet_params* Pr, int alpha_residual, const float* lrs, const float* alphas,
+                           const float* ref, int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* Gr, float* d_lrs,
+                           float* d_alphas, float* d_ref, void* tws, size_t tws_bytes, void* stream) {
+    HRN_CHECK(ref, -2, "hrn_hrnet_backward_ref: null argument (ref)");
+    return backward_impl(pk, dt, scale, Pr, alpha_residual, lrs, alphas, ref, B, V, H, W, d_sr, Gr, d_lrs, d_alphas, d_ref, tws, tws_bytes, stream);
+}
+
+// ext_ref: the reference frame (B,H,W) the stem reads in place of the median of lrs[:, :9] (null: the median, into the workspace)
+static int forward_train_impl(const void* pk, int dt, int nl, int scale, int alpha_residual, const float* lrs, const float* alphas,
+                              const float* ext_ref, int B, int V, int H, int W, float* sr, void* tws, size_t tws_bytes, void* stream) {
     int rc;
     HRN_CHECK(hrn_scale_ok(scale), -2, "hrn_hrnet_forward_train: scale must be 2, 3 or 4 (got %d)", scale);
     if ((rc = check_train(nl, B, V, H, W))) return rc;
@@ -317,8 +336,9 @@ int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alp
     hipStream_t s = (hipStream_t)stream;
     const size_t hw = (size_t)H * W;
     const int M = B * V;
-    float* ref = (float*)at(tws, L.ref);
-    if ((rc = hrn_launch_median(lrs, ref, B, V, H, W, s))) return rc;
+    // (an outside frame is read where it lies, by the stem here and by the backward, which is handed it again: no copy, no median launch)
+    const float* ref = ext_ref ? ext_ref : (const float*)at(tws, L.ref);
+    if (!ext_ref && (rc = hrn_launch_median(lrs, (float*)at(tws, L.ref), B, V, H, W, s))) return rc;
     const ConvSite& stem = P.site[SITE_STEM];
     if ((rc = hrn_launch_stem(dt, lrs, hw, ref, V, hw, nullptr, (const float*)at(pk, stem.w), (const float*)at(pk, stem.b),
                               (const float*)at(pk, stem.a), at(tws, L.a[0]), M, H, W, s, hrn_lo_of(dt, (size_t)M * hw * 64)))) return rc;
@@ -342,6 +362,17 @@ int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alp
     return hrn_launch_decoder(dt, at(tws, L.stack[L.T]), at(pk, P.dec_w), (const float*)at(pk, P.dec_b), (const float*)at(pk, P.dec_a),
                               (const float*)at(pk, P.fin_w), (const float*)at(pk, P.fin_b), sr, B, H, W, s,
                               hrn_lo_of(dt, (size_t)B * L.n_in[L.T] * hw * 64), scale);
+}
+
+int hrn_hrnet_forward_train_s(const void* pk, int dt, int nl, int scale, int alpha_residual, const float* lrs, const float* alphas, int B, int V,
+                              int H, int W, float* sr, void* tws, size_t tws_bytes, void* stream) {
+    return forward_train_impl(pk, dt, nl, scale, alpha_residual, lrs, alphas, nullptr, B, V, H, W, sr, tws, tws_bytes, stream);
+}
+
+int hrn_hrnet_forward_train_ref(const void* pk, int dt, int nl, int scale, int alpha_residual, const float* lrs, const float* alphas,
+                                const float* ref, int B, int V, int H, int W, float* sr, void* tws, size_t tws_bytes, void* stream) {
+    HRN_CHECK(ref, -2, "hrn_hrnet_forward_train_ref: null argument (ref)");
+    return forward_train_impl(pk, dt, nl, scale, alpha_residual, lrs, alphas, ref, B, V, H, W, sr, tws, tws_bytes, stream);
 }
 
 }  // extern "C"

@@ -44,6 +44,8 @@
  *   hrn_tile_gather / hrn_tile_scatter / hrn_tile_count / hrn_hrnet_halo  <-  (no counterpart in the reference: it predicts
  *                              square chips whole) the two ends of tiled inference: overlapping square windows of a scene of
  *                              any size and aspect ratio, and the windows' cores put back into the scene's prediction
+ *   hrn_masked_composite / hrn_hrnet_*_ref  <-  (no counterpart: the reference's frame is the plain median of lrs[:, :9], HRNet.py:200)
+ *                              a cloud-free reference frame from the views and their quality masks, and HRNet given that frame
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor's data_ptr) unless stated;
@@ -204,6 +206,47 @@ int hrn_hrnet_backward_in(const void* packed, int dtype, int scale, const hrn_hr
 int hrn_hrnet_backward_sel(const void* packed, int dtype, int scale, const hrn_hrnet_params* params, int alpha_residual, const float* lrs,
                            const float* alphas, int B, int V, int H, int W, const float* d_sr, const hrn_hrnet_params* grads,
                            float* d_lrs, float* d_alphas, void* train_ws, size_t train_ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------ cloud-free composite reference frame
+ * (No counterpart in the reference, whose HRNet.py:200 takes the plain lower median of lrs[:, :9], clouds, concealed pixels and the
+ * zeros of registered views included.)
+ *
+ * hrn_masked_composite: views (B,V,H,W) f32, masks (B,V,H,W) f32 or NULL (all clear), alphas (B,V) f32 or NULL (every view real)
+ * -> ref (B,H,W), count (B,H,W) or NULL, filled (B,V,H,W) or NULL.  Per sample b and pixel p, with n = min(V, n_ref), 1 <= n_ref <= 32:
+ *   - a view v < n is REAL when alphas is NULL or alphas[b,v] != 0, and a CANDIDATE when it is real and masks is NULL or masks[b,v,p] != 0;
+ *   - with c >= 1 candidates ref[b,p] is their LOWER median - the element at index (c - 1) / 2 in ascending order, the rule of the
+ *     network's own reference frame - and count[b,p] = c;
+ *   - with c == 0, ref is the lower median over the real views v < n, masks ignored, and count = 0; with no real view either it is the
+ *     lower median over all n views, which is the network's own reference frame;
+ *   - filled[b,v,p] = views[b,v,p] where view v is not real (padding stays as it is), or masks is NULL, or masks[b,v,p] != 0; otherwise
+ *     ref[b,p].  This covers all V views, not only the first n.
+ * The inputs must be finite (+inf is the padding key of the selection).  The result is always one of the input values, so it is exact;
+ * it is bit-reproducible and a sample does not depend on its batch.  With masks == NULL, alphas == NULL and n_ref == 9, `ref` is the
+ * reference frame hrn_hrnet_forward computes, bit for bit.  One launch; views and masks are read once; `filled` must not alias `views`.
+ * -2 before any launch for NULL views / ref, n_ref outside 1..32, non-positive sizes, or a batch beyond one launch's grid. */
+int hrn_masked_composite(const float* views, const float* masks, const float* alphas, int B, int V, int H, int W, int n_ref, float* ref,
+                         float* count, float* filled, void* stream);
+
+/* HRNet with the reference frame given: `ref` (B,H,W) f32 takes the place of the median of lrs[:, :9] as the second input channel of
+ * every view (HRNet.py:200-204); everything after it is the same kernels in the same order, and the median is not launched.  With ref
+ * equal to that median the results are bit-identical to the plain entry points'.
+ *   hrn_hrnet_forward_ref         hrn_hrnet_forward_s plus ref
+ *   hrn_hrnet_forward_train_ref   hrn_hrnet_forward_train_s plus ref (read in place: it must stay unchanged until the backward)
+ *   hrn_hrnet_backward_ref        hrn_hrnet_backward_sel plus ref (the frame the forward was given) and d_ref (B,H,W) f32 or NULL.
+ *                                 d_lrs is the stem's input gradient of channel 0 alone; d_ref is channel 1 summed over the sample's
+ *                                 views in view order, WRITTEN like the other input gradients.  The frame is data: nothing is routed
+ *                                 back into the views it was made from.
+ * A NULL ref is refused with -2; otherwise arguments, checks, workspaces and return codes are those of the forms they extend. */
+int hrn_hrnet_forward_ref(const void* packed, int dtype, int num_layers, int scale, int alpha_residual, const float* lrs,
+                          const float* alphas, const float* ref, int B, int V, int H, int W, float* sr, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int hrn_hrnet_forward_train_ref(const void* packed, int dtype, int num_layers, int scale, int alpha_residual, const float* lrs,
+                                const float* alphas, const float* ref, int B, int V, int H, int W, float* sr, void* train_ws,
+                                size_t train_ws_bytes, void* stream);
+int hrn_hrnet_backward_ref(const void* packed, int dtype, int scale, const hrn_hrnet_params* params, int alpha_residual, const float* lrs,
+                           const float* alphas, const float* ref, int B, int V, int H, int W, const float* d_sr,
+                           const hrn_hrnet_params* grads, float* d_lrs, float* d_alphas, float* d_ref, void* train_ws, size_t train_ws_bytes,
+                           void* stream);
 
 /* ------------------------------------------------------------------ ShiftNet */
 typedef struct hrn_shiftnet_params {
