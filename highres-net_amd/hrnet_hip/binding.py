@@ -169,6 +169,8 @@ SIGNATURES = {
     "hrn_mncc_search_scene": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 6 + [_c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,
                                                                              _c.c_void_p]),
     "hrn_mncc_apply_scene": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 4 + [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hrn_mncc_apply_backward_workspace_bytes": (_c.c_size_t, [_c.c_int] * 4),
+    "hrn_mncc_apply_backward": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 4 + [_c.c_void_p] * 3 + [_c.c_size_t, _c.c_void_p]),
     "hrn_mncc_local_blocks": (_c.c_int, [_c.c_int] * 2),
     "hrn_mncc_local_workspace_bytes": (_c.c_size_t, [_c.c_int] * 6),
     "hrn_mncc_search_local": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 6 + [_c.c_float, _c.c_int, _c.c_float] + [_c.c_void_p] * 4
@@ -1307,6 +1309,33 @@ def mncc_apply_scene(views, view_masks, shifts):
     return _mncc_apply(True, views, view_masks, shifts)
 
 
+def mncc_apply_backward(views, shifts, valid, d_out, need_views=True, need_shifts=True):
+    """The backward of mncc_apply_scene (hrn_mncc_apply_backward): valid = its second result, d_out = the gradient at its first ->
+    (d_views (B,V,H,W) or None, d_shifts (B,V,2) or None), each computed only where needed; both unneeded is an error.  The gradient
+    takes d_out where `valid` is set and the pixel's footprint lies inside the frame.  Bit-reproducible."""
+    if not (need_views or need_shifts):
+        raise ValueError("mncc_apply_backward: neither d_views nor d_shifts is needed")
+    lib = load_library()
+    views, _ = _mncc_views(views, None)
+    B, V, H, W = views.shape
+    shifts, valid, d_out = _dev_f32(shifts, "shifts"), _dev_f32(valid, "valid"), _dev_f32(d_out, "d_out")
+    if tuple(shifts.shape) != (B, V, 2):
+        raise ValueError(f"shifts must be ({B}, {V}, 2); got {tuple(shifts.shape)}")
+    for name, t in (("valid", valid), ("d_out", d_out)):
+        if t.shape != views.shape:
+            raise ValueError(f"{name} must have views' shape {tuple(views.shape)}; got {tuple(t.shape)}")
+    d_views = torch.empty_like(views) if need_views else None
+    d_shifts = torch.empty((B, V, 2), dtype=torch.float32, device=views.device) if need_shifts else None
+    with torch.cuda.device(views.device):
+        ws = (ctypes.c_void_p(0), 0)
+        if need_shifts:
+            ws = _mncc_workspace("hrn_mncc_apply_backward_workspace_bytes", (B, V, H, W), "mncc_apply_backward", f"B={B} V={V} H={H} W={W}",
+                                 views.device)
+        _check(lib.hrn_mncc_apply_backward(_ptr(views), _ptr(shifts), _ptr(valid), _ptr(d_out), B, V, H, W, _opt_ptr(d_views),
+                                           _opt_ptr(d_shifts), *ws, _stream()), "hrn_mncc_apply_backward")
+    return d_views, d_shifts
+
+
 def mncc_search_scene_from(ref, ref_mask, views, view_masks, init, points_per_dim=7, levels=6, radius=1.0):
     """mncc_search_scene with the first level's centre read from init (B,V,2) (hrn_mncc_search_scene_from); None: (0, 0)."""
     return _mncc_search("hrn_mncc_search_scene_from", ref, ref_mask, views, view_masks, points_per_dim, levels, radius, init)
@@ -2094,6 +2123,50 @@ def _op_shift_scene(views: torch.Tensor, view_masks: Optional[torch.Tensor], shi
 _op_mncc_grid_scene.register_fake(_fake_mncc_grid)
 _op_mncc_search_scene.register_fake(_fake_mncc_search)
 _op_shift_scene.register_fake(_fake_shift_views)
+
+
+# The resampler as a differentiable warp (resample_bwd.hip): shift_scene's forward with an autograd formula in the views and the shifts.
+# The sampler is linear in the view and C^1 in the shift; `valid` and the masks are piecewise constant and get no gradient.
+@torch.library.custom_op("hrnet_hip::warp", mutates_args=(), device_types="cuda")
+def _op_warp(views: torch.Tensor, view_masks: Optional[torch.Tensor], shifts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return mncc_apply_scene(views, view_masks, shifts)
+
+
+_op_warp.register_fake(_fake_shift_views)
+
+
+@torch.library.custom_op("hrnet_hip::warp_backward", mutates_args=(), device_types="cuda")
+def _op_warp_backward(views: torch.Tensor, shifts: torch.Tensor, valid: torch.Tensor, d_out: torch.Tensor, need_views: bool,
+                      need_shifts: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(d_views, d_shifts) of mncc_apply_backward; a half that is not needed is not launched and comes back as an empty (0,) tensor."""
+    d_views, d_shifts = mncc_apply_backward(views, shifts, valid, d_out, need_views, need_shifts)
+    none = views.new_empty((0,), dtype=torch.float32)
+    return (d_views if need_views else none), (d_shifts if need_shifts else none.clone())
+
+
+@_op_warp_backward.register_fake
+def _fake_warp_backward(views, shifts, valid, d_out, need_views, need_shifts):
+    return (views.new_empty(views.shape if need_views else (0,), dtype=torch.float32),
+            views.new_empty(tuple(views.shape[:2]) + (2,) if need_shifts else (0,), dtype=torch.float32))
+
+
+def _warp_setup(ctx, inputs, output):
+    views, _, shifts = inputs
+    ctx.save_for_backward(views, shifts, output[1])
+    ctx.mark_non_differentiable(output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _warp_backward(ctx, d_out, _d_valid):
+    views, shifts, valid = ctx.saved_tensors
+    need_views, need_shifts = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+    if d_out is None or not (need_views or need_shifts):
+        return None, None, None
+    d_views, d_shifts = torch.ops.hrnet_hip.warp_backward(views, shifts, valid, d_out, need_views, need_shifts)
+    return (d_views.to(views.dtype) if need_views else None), None, (d_shifts.to(shifts.dtype) if need_shifts else None)
+
+
+_op_warp.register_autograd(_warp_backward, setup_context=_warp_setup)
 
 
 # a shift per block and the resampling by the field (registration_local.hip)

@@ -647,6 +647,25 @@ int hrn_mncc_apply_scene(const float* views, const float* view_masks, const floa
     return hrn_launch_mncc_apply_scene(views, view_masks, shifts, B, V, H, W, out, out_valid, (hipStream_t)stream);
 }
 
+// the backward of hrn_mncc_apply_scene (resample_bwd.hip)
+size_t hrn_mncc_apply_backward_workspace_bytes(int B, int V, int H, int W) {
+    if (mncc_scene_check(nullptr, B, V, H, W)) return 0;
+    return hrn_mncc_apply_backward_workspace_bytes_impl(B, V, H, W);
+}
+
+int hrn_mncc_apply_backward(const float* views, const float* shifts, const float* valid, const float* d_out, int B, int V, int H, int W,
+                            float* d_views, float* d_shifts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = mncc_scene_check("hrn_mncc_apply_backward", B, V, H, W)) return rc;
+    HRN_CHECK(d_views || d_shifts, -2, "hrn_mncc_apply_backward: d_views and d_shifts are both null: nothing to compute");
+    HRN_CHECK(shifts && valid && d_out, -2, "hrn_mncc_apply_backward: null argument");
+    if (d_shifts) {
+        HRN_CHECK(views && workspace, -2, "hrn_mncc_apply_backward: d_shifts needs views and a workspace: null argument");
+        HRN_CHECK(workspace_bytes >= hrn_mncc_apply_backward_workspace_bytes_impl(B, V, H, W), -3,
+                  "hrn_mncc_apply_backward: workspace too small");
+    }
+    return hrn_launch_mncc_apply_backward(views, shifts, valid, d_out, B, V, H, W, d_views, d_shifts, workspace, (hipStream_t)stream);
+}
+
 // a shift per block of tiles and the resampling by the field between them (registration_local.hip)
 static int mncc_check_block(const char* who, int block) {
     MNCC_LIMIT(block >= HRN_MNCC_LOCAL_MIN_BLOCK && block <= HRN_MNCC_LOCAL_MAX_BLOCK && block % HRN_MNCC_SCENE_TILE == 0,

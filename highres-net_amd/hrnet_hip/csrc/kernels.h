@@ -114,6 +114,12 @@ int hrn_launch_mncc_apply_scene(const float* views, const float* view_masks, con
 void hrn_launch_mncc_scene_means(const float* ref, const float* ref_mask, const float* views, const float* view_masks, int B, int V, int H,
                                  int W, double* means, hipStream_t stream);      // means[((plane) * chunks + chunk) * 2] = {sum, count}
 
+// ---- resample_bwd.hip: the backward of hrn_launch_mncc_apply_scene.  d_views or d_shifts may be null: that half
+// is not launched; views and the workspace (hrn_mncc_apply_backward_workspace_bytes_impl bytes) are read only for d_shifts.
+size_t hrn_mncc_apply_backward_workspace_bytes_impl(int B, int V, int H, int W);
+int hrn_launch_mncc_apply_backward(const float* views, const float* shifts, const float* valid, const float* d_out, int B, int V, int H,
+                                   int W, float* d_views, float* d_shifts, void* workspace, hipStream_t stream);
+
 // ---- registration_local.hip: a shift per block of tiles of every view, and the views resampled by the field between the blocks'
 // centres.  block: a multiple of 64 in 64..4096; hrn_mncc_local_blocks_impl: the blocks of an axis.
 constexpr int HRN_MNCC_LOCAL_MIN_BLOCK = 64, HRN_MNCC_LOCAL_MAX_BLOCK = 4096;

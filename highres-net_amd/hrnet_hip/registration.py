@@ -8,8 +8,13 @@ pixels, so that it stays in [-1, 1].  A shift (dy, dx) means Output(y, x) = Inpu
 `lanczos_shift`'s argument, the negative of the fork's.
 
 `mncc_search` is one launch of `hrn_mncc_search`: a workgroup owns a view, keeps it in LDS and walks every level, argmax included.
-`shift_views` is `hrn_mncc_apply`.  Both are bit-reproducible.  There is no autograd formula - a shift found by a grid search is
-piecewise constant in the frames - and no CPU fallback: tensors must be on a ROCm device.  Frames are 16..128 pixels a side.
+`shift_views` is `hrn_mncc_apply`.  Both are bit-reproducible.  The searches have no autograd formula - a shift found by a grid search
+is piecewise constant in the frames - and there is no CPU fallback: tensors must be on a ROCm device.  Frames are 16..128 pixels a side.
+
+The sampler itself is linear in the frame and C^1 in the shift, and `warp` is the resampler with that gradient:
+`shift_scene`'s forward, bit for bit, differentiable in the frames and in the shifts (`hrn_mncc_apply_backward`).  It is what a loss on
+registered frames, or a shift refined by descent, rests on.  `shift_views`, `shift_scene` and `shift_field` stay without a gradient:
+the first two are `warp` without one, and a shift per pixel makes the frames' gradient a scatter, which is not built.
 
 `mncc_search_scene`, `mncc_grid_scene`, `shift_scene` and `register_scene` are the same four for frames of 16..16384 pixels a side
 (DESIGN.md section 7g): the scenes `HRNet.forward_tiled` takes, the large benchmark shape, an SR / HR pair.  A frame is cut into tiles
@@ -182,6 +187,34 @@ def mncc_grid_scene(lrs, lr_masks=None, ref=None, ref_mask=None, centres=None, p
 def shift_scene(lrs, lr_masks, shifts):
     """`shift_views` for frames of 16..16384 pixels a side; bit-identical to it where both run."""
     return _shift(True, lrs, lr_masks, shifts)
+
+
+def warp(frames, shifts, masks=None):
+    """`shift_scene` as a differentiable function: frames (B,V,H,W) with shifts (B,V,2), or (B,H,W) with shifts (B,2); masks of the
+    frames' shape or None -> (warped = S(frame, shift), valid f32 0 / 1), of the frames' shape and with `shift_scene`'s bits.  autograd
+    reaches `frames` (the adjoint of the sampler, a gather) and `shifts` (through the derivative of the six taps: the sampler is C^1 in
+    the shift, across whole pixels as well) and computes only the half that is needed; `valid` and the masks are piecewise constant
+    and carry no gradient.  The gradient that arrives at `warped` counts where `valid` is set, so a loss is the map times `valid`.
+    One `hrn_mncc_apply_backward` per backward, bit-reproducible.  A shift of +-256 or beyond has zero slope."""
+    if not torch.is_tensor(frames):
+        raise TypeError(f"frames must be a torch.Tensor; got {type(frames).__name__}")
+    if frames.dim() not in (3, 4):
+        raise ValueError(f"frames must be (B,V,H,W) or (B,H,W); got {tuple(frames.shape)}")
+    single = frames.dim() == 3
+    if single:
+        if torch.is_tensor(shifts) and tuple(shifts.shape) != (frames.shape[0], 2):
+            raise ValueError(f"shifts must be (B,2) = {(frames.shape[0], 2)}; got {tuple(shifts.shape)}")
+        frames = frames[:, None]
+        masks = masks[:, None] if torch.is_tensor(masks) and masks.dim() == 3 else masks
+        shifts = shifts[:, None] if torch.is_tensor(shifts) else shifts
+    _frames(frames, masks, True, "frames")
+    if not torch.is_tensor(shifts):
+        raise TypeError(f"shifts must be a torch.Tensor; got {type(shifts).__name__}")
+    if tuple(shifts.shape) != tuple(frames.shape[:2]) + (2,):
+        raise ValueError(f"shifts must be (B,V,2) = {tuple(frames.shape[:2]) + (2,)}; got {tuple(shifts.shape)}")
+    _on_device(frames=frames, masks=masks, shifts=shifts)
+    warped, valid = torch.ops.hrnet_hip.warp(frames, masks, shifts)
+    return (warped[:, 0], valid[:, 0]) if single else (warped, valid)
 
 
 def register_scene(lrs, lr_masks=None, **search_kwargs):

@@ -31,6 +31,8 @@
  *                              compute_grid_mncc), restated: sub-pixel registration of the LR views against a reference frame;
  *                              hrn_mncc_grid_scene / hrn_mncc_search_scene / hrn_mncc_apply_scene: the same for frames of any size;
  *                              hrn_mncc_search_local / hrn_mncc_apply_field: a shift per block of a scene and the resampling by that field
+ *   hrn_mncc_apply_backward  <-  (no counterpart: the fork's search is never differentiated) the gradient of hrn_mncc_apply_scene with
+ *                              respect to the views and to the shifts: the resampler as a differentiable warp
  *   hrn_collate_device     <-  collateFunction(min_L) over ImagesetDataset items (src/utils.py:63-113), gathered from
  *                              imagesets decoded once into HBM (DataLoader.DeviceImagesetCache); hrn_collate_device_s
  *                              is the same for x2 / x3 / x4 targets
@@ -491,6 +493,30 @@ int hrn_mncc_search_scene(const float* ref, const float* ref_mask, const float* 
                           void* stream);
 int hrn_mncc_apply_scene(const float* views, const float* view_masks, const float* shifts, int B, int V, int H, int W, float* out,
                          float* out_valid, void* stream);
+/* The backward of the sampler: out = S(view, shift) is linear in the view and C^1 in the shift - the six normalised taps are continuous
+ * with their first derivative across whole-pixel boundaries, because L3'(+-3) = 0 with L3(t) = sinc(t) sinc(t / 3).  valid / d_out
+ * (B,V,H,W) are hrn_mncc_apply_scene's out_valid and the gradient that arrives at `out`.  With (n_y, f_y), (n_x, f_x) and the taps k of
+ * the view's shift as above:
+ *   g         = d_out where `valid` is non-zero AND the pixel's 6 x 6 footprint lies inside the frame, else 0.  The footprint is tested
+ *               again here, so whatever `valid` holds nothing outside a frame is read.
+ *   d_views   (B,V,H,W): d_views(p, q) = sum_{a, b = -2..3} k^y_a k^x_b g(p - n_y - a, q - n_x - b), g zero outside the frame: the adjoint
+ *               as a gather (one shift per view) - the sampler's two passes with the taps reversed, the whole parts (-n_y - 1, -n_x - 1)
+ *               and zero padding.  Every element is written; exactly 0 where no valid pixel's footprint reaches.
+ *   d_shifts  (B,V,2): d_shifts[., 0] = sum_pixels g dS/ddy, where dS/ddy takes the taps k'^y along columns and k^x along rows; [., 1] is
+ *               the mirror.  k'_o = (u'_o - k_o sum u') / sum u with u_o = L3(o - f), u'_o = -L3'(o - f), formed in fp64 per view and
+ *               rounded to fp32 as k is.  A pixel's product is fp32; every sum is fp64 in a fixed order (thread, wave, waves, tiles in
+ *               index order), rounded to fp32 once.  Exactly 0 for a view without a valid pixel, and for a coordinate at or beyond +-256
+ *               (or a NaN): the sampler clamps it there, and the clamp has zero slope.
+ * There is no gradient to the masks or to `valid`: they are piecewise constant in the shift.
+ * hrn_mncc_apply_backward_workspace_bytes  16 B V T bytes, T = ceil(H / 64) ceil(W / 64): the tiles' two fp64 sums; 0 for arguments the
+ *                  entry point refuses.
+ * hrn_mncc_apply_backward  either of d_views / d_shifts may be NULL: that half is not run (one launch for d_views, two for d_shifts);
+ *                  both NULL is refused.  `views` and `workspace` are needed only for d_shifts and may be NULL without it.  16 <= H, W
+ *                  <= 16384.  No atomics: both results are bit-reproducible, and a view's does not depend on the batch around it.  -2
+ *                  before any launch as above, -3 for a workspace that is too small. */
+size_t hrn_mncc_apply_backward_workspace_bytes(int B, int V, int H, int W);
+int hrn_mncc_apply_backward(const float* views, const float* shifts, const float* valid, const float* d_out, int B, int V, int H, int W,
+                            float* d_views, float* d_shifts, void* workspace, size_t workspace_bytes, void* stream);
 /* A shift per block of every view - a shift field - on the scene path's tiles.  `block` is a multiple of 64 in
  * 64..4096.  An axis of length L has n = max(1, (L + block / 2) / block) blocks; block i covers [i block, (i + 1) block) and the last one
  * runs to L, so a remainder below half a block joins its neighbour and every block is a union of whole 64-pixel tiles.
