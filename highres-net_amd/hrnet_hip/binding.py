@@ -1011,12 +1011,18 @@ def shift_cpsnr(srs, hrs, hr_maps, border_w=3, clip=True):
     return out
 
 
-def _shift_loss_args(srs, hrs, hr_maps, metric, border_w):
-    if metric not in ("cMSE", "cPSNR"):
-        raise ValueError(f"the searched loss is defined for 'cMSE' and 'cPSNR'; got {metric!r}")
+def _bhw_frames(srs, hrs, hr_maps):
+    """the frame check of the searched losses and scores -> three dense f32 device tensors of equal (B,H,W) shapes"""
     srs, hrs, hr_maps = _dev_f32(srs, "srs"), _dev_f32(hrs, "hrs"), _dev_f32(hr_maps, "hr_maps")
     if srs.dim() != 3 or srs.shape != hrs.shape or srs.shape != hr_maps.shape:
         raise ValueError(f"srs, hrs, hr_maps must be equal (B,H,W) tensors; got {tuple(srs.shape)}, {tuple(hrs.shape)}, {tuple(hr_maps.shape)}")
+    return srs, hrs, hr_maps
+
+
+def _shift_loss_args(srs, hrs, hr_maps, metric, border_w):
+    if metric not in ("cMSE", "cPSNR"):
+        raise ValueError(f"the searched loss is defined for 'cMSE' and 'cPSNR'; got {metric!r}")
+    srs, hrs, hr_maps = _bhw_frames(srs, hrs, hr_maps)
     border_w = int(border_w)
     if border_w < 0 or min(srs.shape[1:]) <= 2 * border_w:
         raise ValueError(f"border_w={border_w} needs frames larger than {2 * border_w} pixels each way; got {tuple(srs.shape[1:])}")
@@ -1054,9 +1060,7 @@ def shift_loss_backward(srs, hrs, hr_maps, stats, d_out, metric="cPSNR", border_
 
 
 def _cl1_loss_args(srs, hrs, hr_maps, border_w, eps):
-    srs, hrs, hr_maps = _dev_f32(srs, "srs"), _dev_f32(hrs, "hrs"), _dev_f32(hr_maps, "hr_maps")
-    if srs.dim() != 3 or srs.shape != hrs.shape or srs.shape != hr_maps.shape:
-        raise ValueError(f"srs, hrs, hr_maps must be equal (B,H,W) tensors; got {tuple(srs.shape)}, {tuple(hrs.shape)}, {tuple(hr_maps.shape)}")
+    srs, hrs, hr_maps = _bhw_frames(srs, hrs, hr_maps)
     border_w, eps = int(border_w), float(eps)
     if border_w < 0 or min(srs.shape[1:]) <= 2 * border_w:
         raise ValueError(f"border_w={border_w} needs frames larger than {2 * border_w} pixels each way; got {tuple(srs.shape[1:])}")
@@ -1104,9 +1108,7 @@ def _cssim_args(srs, hrs, hr_maps, border_w, window, data_range):
     if window not in CSSIM_WINDOWS:
         raise ValueError(f"window must be one of {sorted(CSSIM_WINDOWS)}; got {window!r}")
     code, taps = CSSIM_WINDOWS[window]
-    srs, hrs, hr_maps = _dev_f32(srs, "srs"), _dev_f32(hrs, "hrs"), _dev_f32(hr_maps, "hr_maps")
-    if srs.dim() != 3 or srs.shape != hrs.shape or srs.shape != hr_maps.shape:
-        raise ValueError(f"srs, hrs, hr_maps must be equal (B,H,W) tensors; got {tuple(srs.shape)}, {tuple(hrs.shape)}, {tuple(hr_maps.shape)}")
+    srs, hrs, hr_maps = _bhw_frames(srs, hrs, hr_maps)
     border_w, data_range = int(border_w), float(data_range)
     if border_w < 0 or border_w > 8 or min(srs.shape[1:]) < 2 * border_w + taps:
         raise ValueError(f"border_w must be 0..8 and each side at least 2 border_w + {taps} (the {window} window); got {border_w} for "
@@ -1953,21 +1955,23 @@ def _(srs, hrs, hr_maps, stats, d_out, metric, border_w, clip):
     return srs.new_empty(srs.shape, dtype=torch.float32)
 
 
-def _shift_loss_setup(ctx, inputs, output):
-    srs, hrs, hr_maps, ctx.metric, ctx.border_w, ctx.clip = inputs
-    ctx.save_for_backward(srs, hrs, hr_maps, output[1])
-    ctx.set_materialize_grads(False)
+def _register_searched_loss(train_op, backward_name, n_args):
+    """The autograd of a searched loss: train_op(srs, hrs, hr_maps, *args) -> (out, stats), d_srs = the op hrnet_hip::<backward_name>
+    (srs, hrs, hr_maps, stats, d_out, *args) of the same n_args non-tensor arguments; the targets and their status maps get no gradient."""
+    def setup(ctx, inputs, output):
+        ctx.args = tuple(inputs[3:])
+        ctx.save_for_backward(*inputs[:3], output[1])
+        ctx.set_materialize_grads(False)
+
+    def backward(ctx, d_out, _d_stats):
+        if d_out is None:
+            return (None,) * (3 + n_args)
+        return (getattr(torch.ops.hrnet_hip, backward_name)(*ctx.saved_tensors, d_out, *ctx.args),) + (None,) * (2 + n_args)
+
+    train_op.register_autograd(backward, setup_context=setup)
 
 
-def _shift_loss_backward(ctx, d_out, _d_stats):
-    srs, hrs, hr_maps, stats = ctx.saved_tensors
-    if d_out is None:
-        return None, None, None, None, None, None
-    d_srs = torch.ops.hrnet_hip.shift_loss_backward(srs, hrs, hr_maps, stats, d_out, ctx.metric, ctx.border_w, ctx.clip)
-    return d_srs, None, None, None, None, None          # the targets and their status maps get no gradient
-
-
-_op_shift_loss_train.register_autograd(_shift_loss_backward, setup_context=_shift_loss_setup)
+_register_searched_loss(_op_shift_loss_train, "shift_loss_backward", 3)
 
 
 # cSSIM is a score: no autograd formula.
@@ -2009,22 +2013,7 @@ def _(srs, hrs, hr_maps, stats, d_out, border_w, window, clip, correct_bias, dat
     return srs.new_empty(srs.shape, dtype=torch.float32)
 
 
-def _cssim_loss_setup(ctx, inputs, output):
-    srs, hrs, hr_maps, ctx.border_w, ctx.window, ctx.clip, ctx.correct_bias, ctx.data_range = inputs
-    ctx.save_for_backward(srs, hrs, hr_maps, output[1])
-    ctx.set_materialize_grads(False)
-
-
-def _cssim_loss_backward(ctx, d_out, _d_stats):
-    srs, hrs, hr_maps, stats = ctx.saved_tensors
-    if d_out is None:
-        return (None,) * 8
-    d_srs = torch.ops.hrnet_hip.cssim_loss_backward(srs, hrs, hr_maps, stats, d_out, ctx.border_w, ctx.window, ctx.clip, ctx.correct_bias,
-                                                    ctx.data_range)
-    return (d_srs,) + (None,) * 7                       # the targets and their status maps get no gradient
-
-
-_op_shift_cssim_train.register_autograd(_cssim_loss_backward, setup_context=_cssim_loss_setup)
+_register_searched_loss(_op_shift_cssim_train, "cssim_loss_backward", 5)
 
 
 # The shift-searched L1 / Charbonnier: the gradient through the selected offset, the bias attached.
@@ -2051,21 +2040,7 @@ def _(srs, hrs, hr_maps, stats, d_out, border_w, clip, eps):
     return srs.new_empty(srs.shape, dtype=torch.float32)
 
 
-def _cl1_loss_setup(ctx, inputs, output):
-    srs, hrs, hr_maps, ctx.border_w, ctx.clip, ctx.eps = inputs
-    ctx.save_for_backward(srs, hrs, hr_maps, output[1])
-    ctx.set_materialize_grads(False)
-
-
-def _cl1_loss_backward(ctx, d_out, _d_stats):
-    srs, hrs, hr_maps, stats = ctx.saved_tensors
-    if d_out is None:
-        return (None,) * 6
-    d_srs = torch.ops.hrnet_hip.cl1_loss_backward(srs, hrs, hr_maps, stats, d_out, ctx.border_w, ctx.clip, ctx.eps)
-    return (d_srs,) + (None,) * 5                       # the targets and their status maps get no gradient
-
-
-_op_cl1_loss_train.register_autograd(_cl1_loss_backward, setup_context=_cl1_loss_setup)
+_register_searched_loss(_op_cl1_loss_train, "cl1_loss_backward", 3)
 
 
 # The registration search has no autograd formula: a shift found by a grid search is piecewise constant in the frames.

@@ -1,5 +1,5 @@
-// Fixed-order sums of several values per lane over a wave, for the reductions whose results must be bit-reproducible (shift_loss.hip,
-// registration.hip).
+// Fixed-order sums of several values per lane over a wave, for the reductions whose results must be bit-reproducible (offset_walk.h for
+// shift_loss.hip and cl1_loss.hip, registration.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

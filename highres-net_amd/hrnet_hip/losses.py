@@ -39,62 +39,28 @@ def get_loss(srs, hrs, hr_maps, metric="cMSE", crop=0):
     return binding.get_loss(srs, hrs, hr_maps, metric, crop)
 
 
-def shift_loss(srs, hrs, hr_maps, metric="cPSNR", border_w=3, clip=False, return_shift=False):
-    """(B,H,W) x 3 -> (B,): the lowest cMSE over the integer offsets (u - border_w, v - border_w), |.| <= border_w, of `hrs` against the
-    centre crop of `srs`, as 'cMSE' or 'cPSNR' (= -10 log10 cMSE, the reference's sign: negate to minimise).  clip clamps srs to [0, 1]
-    first, as the scorer does.  A (B,1,H,W) `srs` is taken as srs[:, 0].  With grad enabled and a gradient-requiring `srs` the result
-    is differentiable (no gradient to hrs / hr_maps).  return_shift: also the (B,2) int64 offsets (row, column) the loss selected, the
-    registration diagnostic ((-border_w - 1, ...) rows mark a sample without a clear pixel, whose loss is NaN)."""
+def _searched_inputs(srs, hrs, hr_maps, border_w, noun, window=None):
+    """the argument checks of the searched wrappers -> (srs (B,H,W), border_w); `noun`: what the caller computes, for the device error"""
     for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
         if not torch.is_tensor(t):
             raise TypeError(f"{name} must be a torch.Tensor; got {type(t).__name__}")
-    if metric not in ("cMSE", "cPSNR"):
-        raise ValueError(f"metric must be 'cMSE' or 'cPSNR'; got {metric!r}")
+    if window is not None and window not in binding.CSSIM_WINDOWS:
+        raise ValueError(f"window must be one of {sorted(binding.CSSIM_WINDOWS)}; got {window!r}")
     if srs.dim() == 4 and srs.shape[1] == 1:
         srs = srs[:, 0]
     if srs.dim() != 3 or srs.shape != hrs.shape or srs.shape != hr_maps.shape:
         raise ValueError(f"srs, hrs, hr_maps must be equal (B,H,W) tensors; got {tuple(srs.shape)}, {tuple(hrs.shape)}, {tuple(hr_maps.shape)}")
     border_w = int(border_w)
-    if border_w < 0 or border_w > 8 or min(srs.shape[1:]) <= 2 * border_w:
-        raise ValueError(f"border_w must be 0..8 and smaller than half of each side; got {border_w} for frames {tuple(srs.shape[1:])}")
-    for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
-        if not t.is_cuda:
-            raise TypeError(f"{name} is on '{t.device}': the searched loss runs on a ROCm device only (no CPU fallback)")
-    srs = srs if srs.dtype == torch.float32 else srs.float()
-    if torch.is_grad_enabled() and srs.requires_grad:
-        out, stats = torch.ops.hrnet_hip.shift_loss_train(srs.contiguous(), hrs.float().contiguous(), hr_maps.float().contiguous(), metric,
-                                                          border_w, bool(clip))
-    else:
-        out, stats = binding.shift_loss_train(srs, hrs, hr_maps, metric, border_w, clip)
-    if not return_shift:
-        return out
-    k = stats[:, 3].detach().long()
-    nb = 2 * border_w + 1
-    return out, torch.stack([torch.div(k, nb, rounding_mode="floor") - border_w, k % nb - border_w], 1)
-
-
-def _cssim_inputs(srs, hrs, hr_maps, border_w, window, data_range):
-    """the argument checks of the two cSSIM wrappers -> (srs (B,H,W), border_w, data_range)"""
-    for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
-        if not torch.is_tensor(t):
-            raise TypeError(f"{name} must be a torch.Tensor; got {type(t).__name__}")
-    if window not in binding.CSSIM_WINDOWS:
-        raise ValueError(f"window must be one of {sorted(binding.CSSIM_WINDOWS)}; got {window!r}")
-    taps = binding.CSSIM_WINDOWS[window][1]
-    if srs.dim() == 4 and srs.shape[1] == 1:
-        srs = srs[:, 0]
-    if srs.dim() != 3 or srs.shape != hrs.shape or srs.shape != hr_maps.shape:
-        raise ValueError(f"srs, hrs, hr_maps must be equal (B,H,W) tensors; got {tuple(srs.shape)}, {tuple(hrs.shape)}, {tuple(hr_maps.shape)}")
-    border_w, data_range = int(border_w), float(data_range)
+    taps = 1 if window is None else binding.CSSIM_WINDOWS[window][1]
     if border_w < 0 or border_w > 8 or min(srs.shape[1:]) < 2 * border_w + taps:
+        if window is None:
+            raise ValueError(f"border_w must be 0..8 and smaller than half of each side; got {border_w} for frames {tuple(srs.shape[1:])}")
         raise ValueError(f"border_w must be 0..8 and each side at least 2 border_w + {taps} (the {window} window); got {border_w} for "
                          f"frames {tuple(srs.shape[1:])}")
-    if not data_range > 0.0:
-        raise ValueError(f"data_range must be positive; got {data_range}")
     for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
         if not t.is_cuda:
-            raise TypeError(f"{name} is on '{t.device}': the searched score runs on a ROCm device only (no CPU fallback)")
-    return srs, border_w, data_range
+            raise TypeError(f"{name} is on '{t.device}': the searched {noun} runs on a ROCm device only (no CPU fallback)")
+    return srs, border_w
 
 
 def _shift_of(stats, border_w):
@@ -102,6 +68,33 @@ def _shift_of(stats, border_w):
     k = stats[:, 3].detach().long()
     nb = 2 * border_w + 1
     return torch.stack([torch.div(k, nb, rounding_mode="floor") - border_w, k % nb - border_w], 1)
+
+
+def shift_loss(srs, hrs, hr_maps, metric="cPSNR", border_w=3, clip=False, return_shift=False):
+    """(B,H,W) x 3 -> (B,): the lowest cMSE over the integer offsets (u - border_w, v - border_w), |.| <= border_w, of `hrs` against the
+    centre crop of `srs`, as 'cMSE' or 'cPSNR' (= -10 log10 cMSE, the reference's sign: negate to minimise).  clip clamps srs to [0, 1]
+    first, as the scorer does.  A (B,1,H,W) `srs` is taken as srs[:, 0].  With grad enabled and a gradient-requiring `srs` the result
+    is differentiable (no gradient to hrs / hr_maps).  return_shift: also the (B,2) int64 offsets (row, column) the loss selected, the
+    registration diagnostic ((-border_w - 1, ...) rows mark a sample without a clear pixel, whose loss is NaN)."""
+    if metric not in ("cMSE", "cPSNR"):
+        raise ValueError(f"metric must be 'cMSE' or 'cPSNR'; got {metric!r}")
+    srs, border_w = _searched_inputs(srs, hrs, hr_maps, border_w, "loss")
+    srs = srs if srs.dtype == torch.float32 else srs.float()
+    if torch.is_grad_enabled() and srs.requires_grad:
+        out, stats = torch.ops.hrnet_hip.shift_loss_train(srs.contiguous(), hrs.float().contiguous(), hr_maps.float().contiguous(), metric,
+                                                          border_w, bool(clip))
+    else:
+        out, stats = binding.shift_loss_train(srs, hrs, hr_maps, metric, border_w, clip)
+    return (out, _shift_of(stats, border_w)) if return_shift else out
+
+
+def _cssim_inputs(srs, hrs, hr_maps, border_w, window, data_range):
+    """the argument checks of the two cSSIM wrappers -> (srs (B,H,W), border_w, data_range)"""
+    data_range = float(data_range)
+    if not data_range > 0.0:
+        raise ValueError(f"data_range must be positive; got {data_range}")
+    srs, border_w = _searched_inputs(srs, hrs, hr_maps, border_w, "score", window)
+    return srs, border_w, data_range
 
 
 def shift_cssim(srs, hrs, hr_maps, border_w=3, clip=True, window="gaussian", data_range=1.0, correct_bias=True, return_shift=False,
@@ -149,21 +142,10 @@ def cl1_loss(srs, hrs, hr_maps, border_w=3, clip=False, eps=0.0, return_shift=Fa
     srs[:, 0].  With grad enabled and a gradient-requiring `srs` the result is differentiable through the selected offset, the bias
     attached (no gradient to hrs / hr_maps); without either the same forward runs and returns the same bits.  NaN,
     with a zero gradient, for a sample without a clear pixel.  return_shift: also the (B,2) int64 offsets selected, as in shift_loss."""
-    for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
-        if not torch.is_tensor(t):
-            raise TypeError(f"{name} must be a torch.Tensor; got {type(t).__name__}")
-    if srs.dim() == 4 and srs.shape[1] == 1:
-        srs = srs[:, 0]
-    if srs.dim() != 3 or srs.shape != hrs.shape or srs.shape != hr_maps.shape:
-        raise ValueError(f"srs, hrs, hr_maps must be equal (B,H,W) tensors; got {tuple(srs.shape)}, {tuple(hrs.shape)}, {tuple(hr_maps.shape)}")
-    border_w, eps = int(border_w), float(eps)
-    if border_w < 0 or border_w > 8 or min(srs.shape[1:]) <= 2 * border_w:
-        raise ValueError(f"border_w must be 0..8 and smaller than half of each side; got {border_w} for frames {tuple(srs.shape[1:])}")
+    eps = float(eps)
     if not 0.0 <= eps < float("inf"):
         raise ValueError(f"eps must be finite and not negative; got {eps}")
-    for name, t in (("srs", srs), ("hrs", hrs), ("hr_maps", hr_maps)):
-        if not t.is_cuda:
-            raise TypeError(f"{name} is on '{t.device}': the searched loss runs on a ROCm device only (no CPU fallback)")
+    srs, border_w = _searched_inputs(srs, hrs, hr_maps, border_w, "loss")
     srs = srs if srs.dtype == torch.float32 else srs.float()
     if torch.is_grad_enabled() and srs.requires_grad:
         out, stats = torch.ops.hrnet_hip.cl1_loss_train(srs.contiguous(), hrs.float().contiguous(), hr_maps.float().contiguous(), border_w,

@@ -8,6 +8,8 @@ B = 3
 SHAPES = [(20, 20), (37, 53), (53, 37), (96, 96)]     # one tile; odd and rectangular; two tile rows; three tile rows
 BORDERS = [0, 1, 3]
 WIDE = [((40, 300), 8), ((70, 139), 5)]               # the widest halo and three tile columns; a second tile column
+TALL = [((280, 24), 8), ((1900, 12), 1)]              # one column of 9 tiles, added as one run: eight tiles at a time and a tail of one;
+#                                                       one column of 60 tiles, added in runs of 2, of which only the first 30 hold tiles
 EPS = (0.0, float(np.float32(1e-3)))                  # the C ABI takes eps as a float: the restatement gets the same number
 
 
@@ -58,4 +60,5 @@ def case(kind, shape, border):
 
 # every input set the GPU file compares against the restatement: (kind, shape, border)
 CASES = ([(kind, shape, border) for kind in ("rand", "clip", "plant") for shape in SHAPES for border in BORDERS]
-         + [("wide", shape, border) for shape, border in WIDE] + [("weight", (37, 53), 3), ("weight", (96, 96), 1)])
+         + [("wide", shape, border) for shape, border in WIDE] + [("weight", (37, 53), 3), ("weight", (96, 96), 1)]
+         + [("rand", shape, border) for shape, border in TALL])

@@ -3,7 +3,8 @@ section 7m) against its fp64 restatement (tests/cl1_ref.py), and as the tail of 
 
 Shapes: B = 3 and (20, 20), (37, 53), (53, 37), (96, 96) - one tile; odd, rectangular and no multiple of the 32 x 128 tile; the same
 transposed (two tile rows); three tile rows - at borders 0, 1, 3, plus (40, 300) at border 8 and (70, 139) at border 5 (the widest
-halo, more than one tile column), each at eps = 0 (L1) and 1e-3 (Charbonnier).  Tolerances, as tests/test_gpu_shift_loss.py holds
+halo, more than one tile column) and (280, 24) at border 8 and (1900, 12) at border 1 (9 and 60 tiles in one column: the sum of a
+sample's tiles in runs longer than eight tiles, and with runs that hold no tile), each at eps = 0 (L1) and 1e-3 (Charbonnier).  Tolerances, as tests/test_gpu_shift_loss.py holds
 them: 1e-5 relative on out, n, bias, cL1 and sigma (fp64 sums of exact fp32 inputs; out is one fp32 rounding of cL1); 1e-6 of the
 tensor's max-norm per element of d_srs (e, rho' and the product in fp64, one fp32 rounding of the result, <= 2^-24 relative); k* and
 the returned shifts exact.  No sample is excluded: tests/test_cl1_host.py asserts on the CPU that no input set of tests/cl1_cases.py
@@ -106,6 +107,16 @@ def test_large_border_and_wide_frames(eps):
         x, clip, _, _, _, want = _restated("wide", shape, border, eps)
         _check_forward("wide", shape, border, eps)
         _check_grad(_device_grad(x, border, clip, eps), want, border, f"wide {shape} border {border} eps {eps}")
+
+
+@pytest.mark.parametrize("eps", C.EPS)
+def test_long_columns_of_tiles(eps):
+    """9 tiles added as one run (a block of eight and a tail of one) and 60 tiles added in 56 runs of 2, the last 26 of them empty:
+    forward, selected offset and gradient"""
+    for shape, border in C.TALL:
+        x, clip, _, _, _, want = _restated("rand", shape, border, eps)
+        _check_forward("rand", shape, border, eps)
+        _check_grad(_device_grad(x, border, clip, eps), want, border, f"tall {shape} border {border} eps {eps}")
 
 
 @pytest.mark.parametrize("eps", C.EPS)

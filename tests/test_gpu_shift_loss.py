@@ -3,7 +3,8 @@ against its fp64 restatement (tests/shift_loss_ref.py), against the kernels it g
 _backward), and as the tail of a training step without ShiftNet.
 
 Shapes: B = 3 and (20, 20), (37, 53), (53, 37), (96, 96): one tile; odd, rectangular and no multiple of the 32 x 128 tile; the same
-transposed (two tile rows); and a square with three tile rows.  Tolerances: 1e-5 relative on the reductions, as tests/test_gpu_losses.py
+transposed (two tile rows); and a square with three tile rows; (280, 24) at border 8 and (1900, 12) at border 1 for the sum of a sample's
+tiles (9 and 60 tiles in one column: a run longer than eight tiles, and runs that hold no tile).  Tolerances: 1e-5 relative on the reductions, as tests/test_gpu_losses.py
 holds them; 1e-6 of the tensor's max-norm per element of d_srs (fp32 inputs taken exactly, three fp32 roundings per element - the
 difference, the bias, the product with the coefficient - each <= 2^-24 relative, and fp64 statistics)."""
 import itertools
@@ -245,6 +246,40 @@ def test_large_border_and_wide_frames():
         want, k, _ = R.shift_loss(*x, "cPSNR", border)
         got, shift = losses.shift_loss(*_cuda(*x), border_w=border, return_shift=True)
         assert util.rel_err(got.cpu().numpy(), want.numpy()) <= TOL and torch.equal(shift.cpu(), R.offsets(k, border))
+
+
+def test_long_columns_of_tiles():
+    """9 tiles added as one run (a block of eight and a tail of one) and 60 tiles added in 37 runs of 2, the last 7 of them empty:
+    forward, selected offset and gradient against the restatement, no sample excluded"""
+    from hrnet_hip import losses
+    d_out = torch.tensor([1.0, -0.5, 2.0])
+    for (H, W), border in (((280, 24), 8), ((1900, 12), 1)):
+        x = _random(H, W, 11 + border)
+        d = _cuda(*x)
+        for metric in ("cMSE", "cPSNR"):
+            want, k, cm, wgrad = _ref(("tall", (H, W), border, metric), lambda: _restated(*x, metric, border, False, d_out))
+            assert float(R.top_two_gap(cm).min()) > 1e-6
+            s = d[0].clone().requires_grad_(True)
+            got, shift = losses.shift_loss(s, d[1], d[2], metric=metric, border_w=border, return_shift=True)
+            (got * d_out.cuda()).sum().backward()
+            e = util.rel_err(got.detach().cpu().numpy(), want.numpy())
+            print(f"forward ({H}, {W}) border {border} {metric}: rel err {e:.2e}")
+            assert e <= TOL and torch.equal(shift.cpu(), R.offsets(k, border))
+            _check_grad(s.grad, wgrad, border, f"tall ({H}, {W}) border {border} {metric}")
+
+
+def test_a_sample_does_not_depend_on_its_batch():
+    from hrnet_hip import binding
+    d = _cuda(*_random(96, 96, 141))
+    d_out = torch.tensor([1.0, -0.5, 2.0], device="cuda")
+    for metric in ("cMSE", "cPSNR"):
+        out, stats = binding.shift_loss_train(*d, metric, 3, True)
+        grad = binding.shift_loss_backward(*d, stats, d_out, metric, 3, True)
+        for b in range(B):
+            one = tuple(t[b:b + 1].contiguous() for t in d)
+            out1, stats1 = binding.shift_loss_train(*one, metric, 3, True)
+            grad1 = binding.shift_loss_backward(*one, stats1, d_out[b:b + 1], metric, 3, True)
+            assert torch.equal(out1, out[b:b + 1]) and torch.equal(stats1, stats[b:b + 1]) and torch.equal(grad1, grad[b:b + 1])
 
 
 # ----------------------------------------------------------------------------- dispatcher

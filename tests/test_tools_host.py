@@ -40,6 +40,16 @@ def child(script, *argv):
     return subprocess.run([sys.executable, os.path.join(TOOLS, script), *argv], capture_output=True, text=True, cwd=ROOT)
 
 
+# ---------------------------------------------------------------- device_code_diff.py --opcodes
+
+def test_opcode_differences_counts_per_opcode_and_skips_labels():
+    diff = tool("device_code_diff").opcode_differences
+    a = ("s_load_dword s0, s[0:1], 0x0", ".LBB_1:", "v_add_f64 v[0:1], v[0:1], v[2:3]", "s_nop 0", "s_endpgm")
+    b = ("s_load_dword s0, s[0:1], 0x0", "v_add_f64 v[0:1], v[0:1], v[2:3]", ".LBB_2:", "v_add_f64 v[4:5], v[0:1], v[2:3]", "s_endpgm")
+    assert diff(a, b) == [("s_nop", 1, 0), ("v_add_f64", 1, 2)]
+    assert diff(a, a) == [] and diff((), b[:1]) == [("s_load_dword", 0, 1)]
+
+
 # ---------------------------------------------------------------- timing helpers
 
 def test_spread_is_median_min_max():

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two checkouts of this repository, function by function.  No GPU needed.
 
-    python tools/device_code_diff.py <tree_a> <tree_b> [--jobs N] [--keep DIR]
+    python tools/device_code_diff.py <tree_a> <tree_b> [--jobs N] [--keep DIR] [--opcodes]
 
 Every entry of SOURCES in each tree's highres-net_amd/hrnet_hip/build.py is compiled with that file's FLAGS plus
 `--offload-device-only -S`.  The assembly is split per function symbol (the order in which templates are instantiated may move with
@@ -10,9 +10,12 @@ are compared.  What is ignored: comments, the lines that mention `__hip_cuid_` (
 two compiles), and the per-file running number inside local labels (`.LBB7_3` is block 3 of the file's 8th function).
 
 Prints the device functions per source and every symbol that differs, and exits non-zero on any difference - a symbol present in one
-tree only included.  A refactor that claims to touch host code only has to come out of this with "device code identical".
+tree only included.  A refactor that claims to touch host code only has to come out of this with "device code identical".  For one
+that moves device code without changing what it computes, --opcodes lists under every differing symbol the opcodes whose counts differ
+and the descriptor lines that differ.
 """
 import argparse
+import collections
 import importlib.util
 import os
 import re
@@ -109,12 +112,20 @@ def first_difference(a, b):
     return f"{len(a)} / {len(b)} lines"
 
 
+def opcode_differences(a, b):
+    """-> [(opcode, count in a, count in b)] of the opcodes that two instruction lists do not hold equally often; labels are left out"""
+    count = lambda code: collections.Counter(line.split()[0] for line in code if not line.endswith(":"))
+    ca, cb = count(a), count(b)
+    return [(op, ca[op], cb[op]) for op in sorted(set(ca) | set(cb)) if ca[op] != cb[op]]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("tree_a")
     ap.add_argument("tree_b")
     ap.add_argument("--jobs", type=int, default=min(6, os.cpu_count() or 1), help="parallel compiles (default %(default)s)")
     ap.add_argument("--keep", metavar="DIR", help="leave the assembly under DIR/a and DIR/b instead of a temporary directory")
+    ap.add_argument("--opcodes", action="store_true", help="under every symbol that differs, the opcodes whose counts differ: a / b")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         work = args.keep or tmp
@@ -135,6 +146,12 @@ def main():
             (ca, da), (cb, db) = min(la[sym], key=repr), min(lb[sym], key=repr)
             what = "instructions, " + first_difference(ca, cb) if ca != cb else "descriptor, " + first_difference(da or (), db or ())
             print(f"DIFFERS: {sym} ({what})")
+            if args.opcodes:
+                for op, x, y in opcode_differences(ca, cb):
+                    print(f"    {op:<28}{x:>7}{y:>7}")
+                for x, y in zip(da or (), db or ()):
+                    if x != y:
+                        print(f"    {x} / {y.split()[-1]}")
         else:
             continue
         bad += 1
