@@ -135,6 +135,11 @@ int hrn_kt_stem_wgrad(int dt, const float* in0, size_t stride0, const float* in1
 // d_lrs [B][V][H][W] = the stem's input gradient with the median routing; wt: 64 * 18 floats of scratch
 int hrn_kt_stem_dgrad_route(int dt, const void* dA, const float* w, float* wt, const float* lrs, const float* ref, float* d_lrs, int B, int V,
                             int H, int W, void* stream);
+// the same data gradient with the reference frame given from outside (hrn_launch_stem_dgrad_ref, no routing): d_lrs [B][V][H][W] = channel 0
+// per view, d_ref [B][H][W] = channel 1 summed over the sample's V views in view order; either may be NULL (not wanted, not written), both
+// NULL is -2 before any launch; dA [B V][H][W][64] in storage dt is only read; wt: 64 * 18 floats of scratch; tiles B < 2^31 or -2
+int hrn_kt_stem_dgrad_ref(int dt, const void* dA, const float* w, float* wt, float* d_lrs, float* d_ref, int B, int V, int H, int W,
+                          void* stream);
 // out [M][H][W][64] (dt) = the stem's pre-activation, only if only_if_nonpos[0] <= 0
 int hrn_kt_stem_pre(int dt, const float* in0, size_t img_stride0, const float* in1, int rep1, size_t img_stride1, const float* w,
                     const float* bias, void* out, int M, int H, int W, const float* only_if_nonpos, void* stream);

@@ -180,6 +180,10 @@ int hrn_kt_stem_dgrad_route(int dt, const void* dA, const float* w, float* wt, c
                             int H, int W, void* stream) {
     return hrn_launch_stem_dgrad_route(dt, dA, w, wt, lrs, ref, d_lrs, B, V, H, W, (hipStream_t)stream);
 }
+int hrn_kt_stem_dgrad_ref(int dt, const void* dA, const float* w, float* wt, float* d_lrs, float* d_ref, int B, int V, int H, int W,
+                          void* stream) {
+    return hrn_launch_stem_dgrad_ref(dt, dA, w, wt, d_lrs, d_ref, B, V, H, W, (hipStream_t)stream);
+}
 int hrn_kt_stem_pre(int dt, const float* in0, size_t img_stride0, const float* in1, int rep1, size_t img_stride1, const float* w,
                     const float* bias, void* out, int M, int H, int W, const float* only_if_nonpos, void* stream) {
     return hrn_launch_stem_pre(dt, in0, img_stride0, in1, rep1, img_stride1, w, bias, out, M, H, W, only_if_nonpos, (hipStream_t)stream);

@@ -118,13 +118,31 @@ def ref_stem_dgrad_route(dA, w, lrs, ref, highest=False):
     """dA (B V, H, W, 64), w (64, 2, 3, 3) fp64 -> d_lrs (B, V, H, W) = channel 0 of conv_transpose(dA) per view plus, at the routed
     view, channel 1 summed over the sample's views; and T"""
     B, V, H, W = lrs.shape
-    d = torch.nn.grad.conv2d_input((B * V, 2, H, W), w, _nchw(dA), padding=1).reshape(B, V, 2, H, W)
-    Ta = torch.nn.grad.conv2d_input((B * V, 2, H, W), w.abs(), _nchw(dA).abs(), padding=1).reshape(B, V, 2, H, W)
+    d, Ta = _stem_dgrad_both(dA, w, B, V)
     out, T = d[:, :, 0].clone(), Ta[:, :, 0].clone()
     sel = ref_route_index(lrs, ref, highest)[:, None]
     out.scatter_add_(1, sel, d[:, :, 1].sum(1, keepdim=True))
     T.scatter_add_(1, sel, Ta[:, :, 1].sum(1, keepdim=True))
     return out, T
+
+
+def _stem_dgrad_both(dA, w, B, V):
+    """dA (B V, H, W, 64), w (64, 2, 3, 3) fp64 -> the stem's input gradient (B, V, 2, H, W), both channels per view, and the same
+    expression on absolute values"""
+    H, W = dA.shape[1:3]
+    d = torch.nn.grad.conv2d_input((B * V, 2, H, W), w, _nchw(dA), padding=1).reshape(B, V, 2, H, W)
+    Ta = torch.nn.grad.conv2d_input((B * V, 2, H, W), w.abs(), _nchw(dA).abs(), padding=1).reshape(B, V, 2, H, W)
+    return d, Ta
+
+
+def ref_stem_dgrad_ref(dA, w, B, V, drop_last_view=False, swap_channels=False):
+    """The stem's input gradient with the frame given from outside: dA (B V, H, W, 64), w (64, 2, 3, 3) fp64 ->
+    (d_lrs (B, V, H, W), T_lrs, d_ref (B, H, W), T_ref): d_lrs channel 0 per view, d_ref channel 1 summed over the sample's V views, each T
+    the same expression on absolute values.  drop_last_view / swap_channels: the wrong references of the negative controls"""
+    d, Ta = _stem_dgrad_both(dA, w, B, V)
+    c0, c1 = (1, 0) if swap_channels else (0, 1)
+    n = V - 1 if drop_last_view else V
+    return d[:, :, c0].clone(), Ta[:, :, c0].clone(), d[:, :n, c1].sum(1), Ta[:, :n, c1].sum(1)
 
 
 def ref_decoder_up(fused, wd, bd, S):

@@ -53,6 +53,7 @@ SIGNATURES = {
     "hrn_kt_alpha_grad": (i, [i, vp, vp, i, i, vp, i, i, sz, vp, sz, vp]),
     "hrn_kt_stem_wgrad": (i, [i, vp, sz, vp, i, sz, vp, vp, i, i, i, vp, vp, vp]),
     "hrn_kt_stem_dgrad_route": (i, [i, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]),
+    "hrn_kt_stem_dgrad_ref": (i, [i, vp, vp, vp, vp, vp, i, i, i, i, vp]),
     "hrn_kt_stem_pre": (i, [i, vp, sz, vp, i, sz, vp, vp, vp, i, i, i, vp, vp]),
     "hrn_kt_decoder_bwd": (i, [i] + [vp] * 12 + [i, i, i, vp, vp]),
     "hrn_kt_planes_to_f32": (i, [vp, sz, vp, sz, vp]),

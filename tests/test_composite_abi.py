@@ -61,6 +61,10 @@ def test_composite_bad_arguments_fail_before_any_launch(lib):
         for bad in (0, -3):
             assert _composite(lib, p, **{name: bad}) == -2 and b"empty" in lib.hrn_last_error()
     assert _composite(lib, p, B=1 << 20, H=1 << 12, W=1 << 12) == -2 and b"one launch" in lib.hrn_last_error()
+    # the limit itself: one workgroup per (sample, tile of 256 pixels), tiles B = 2^31 exactly, with whole tiles and with a ragged last one
+    for B, H, W in ((1 << 27, 64, 64), (1 << 27, 63, 61), (1 << 30, 33, 10)):
+        assert -(-H * W // 256) * B == 1 << 31
+        assert _composite(lib, p, B=B, H=H, W=W) == -2 and f"{B} samples of {H} x {W} exceed one launch".encode() in lib.hrn_last_error()
 
 
 def test_ref_entry_points_refuse_a_null_frame_and_what_their_base_forms_refuse(lib):

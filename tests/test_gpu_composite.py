@@ -11,19 +11,29 @@ import util
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(2, 1, 5, 7), (2, 2, 5, 7), (1, 9, 16, 16), (2, 10, 9, 33), (1, 17, 8, 8), (2, 32, 16, 16)]
+# (1, 13, 5, 7) and (1, 24, 5, 7): n = min(V, n_ref) strictly inside 10..15 and 18..31, keys of the 16- and 32-key networks that are padding
+SHAPES = [(2, 1, 5, 7), (2, 2, 5, 7), (1, 9, 16, 16), (2, 10, 9, 33), (1, 17, 8, 8), (2, 32, 16, 16), (1, 13, 5, 7), (1, 24, 5, 7)]
 N_REFS = [1, 5, 9, 16, 17, 32]
 _cases = {}
 
 
-def _case(shape):
-    """(views, masks, alphas) of a shape, numpy f32; made once, shared, never modified.  Values: non-negative eighths (ties, no -0.0).
+def _case(shape, family="eighths"):
+    """(views, masks, alphas) of a shape, numpy f32; made once, shared, never modified.  Values, family "eighths": non-negative eighths
+    (ties, no -0.0); family "signed": eighths in [-1.5, 1.5) (ties, both signs, no -0.0) with about 2 % of them +inf - a voter that is
+    +inf sorts among the +inf keys of the views that do not vote, and the result is still the restatement's.
     Masks: ~60 % clear, with pixels forced to no candidate, exactly one, and all.  Alphas: trailing zeros; with B = 2 the second sample
     has no real view at all."""
-    if shape not in _cases:
+    if (shape, family) not in _cases:
         B, V, H, W = shape
         rng = np.random.Generator(np.random.PCG64(sum(shape)))
-        views = np.floor(rng.random(shape) * 24).astype(np.float32) / 8
+        if family == "eighths":
+            views = np.floor(rng.random(shape) * 24).astype(np.float32) / 8
+        else:
+            assert family == "signed", family
+            views = (np.floor(rng.random(shape) * 24) - 12).astype(np.float32) / 8 + np.float32(0.0)
+            views[rng.random(shape) < 0.02] = np.inf
+            views[0, 0, H // 2, W // 2], views[0, 0, H // 2, W // 2 + 1] = -1.5, np.inf      # both ends present whatever the shape
+            assert not np.signbit(views[views == 0]).any()
         masks = (rng.random(shape) < 0.6).astype(np.float32)
         masks[:, :, 0, 0] = 0                                    # no candidate
         masks[:, :, 0, 1] = 0
@@ -37,8 +47,8 @@ def _case(shape):
         alphas[0, max(1, (2 * V) // 3):] = 0                     # n_real < V (and < n_ref for the larger n_ref)
         if B > 1:
             alphas[1] = 0                                        # n_real = 0
-        _cases[shape] = (views, masks, alphas)
-    return _cases[shape]
+        _cases[(shape, family)] = (views, masks, alphas)
+    return _cases[(shape, family)]
 
 
 def _run(views, masks, alphas, n_ref, count=True, fill=True):
@@ -53,10 +63,7 @@ def _same(t, want):
     return t.dtype == torch.float32 and np.array_equal(t.cpu().numpy().view(np.uint32), np.ascontiguousarray(want).view(np.uint32))
 
 
-@pytest.mark.parametrize("n_ref", N_REFS)
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
-def test_composite_equals_the_restatement(shape, n_ref):
-    views, masks, alphas = _case(shape)
+def _check_restatement(views, masks, alphas, n_ref):
     for m, a in ((masks, alphas), (masks, None), (None, alphas), (None, None)):
         want_ref, want_count, want_filled = R.masked_composite(views, m, a, n_ref)
         ref, filled, cnt = _run(views, m, a, n_ref)
@@ -68,10 +75,30 @@ def test_composite_equals_the_restatement(shape, n_ref):
     for count, fill in ((False, True), (True, False), (False, False)):
         ref, filled, cnt = _run(views, masks, alphas, n_ref, count, fill)
         assert _same(ref, want_ref) and (filled is None) == (not fill) and (cnt is None) == (not count)
+
+
+@pytest.mark.parametrize("n_ref", N_REFS)
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_composite_equals_the_restatement(shape, n_ref):
+    views, masks, alphas = _case(shape)
+    _check_restatement(views, masks, alphas, n_ref)
     if shape == SHAPES[3]:                                       # the forced pixels are what they are meant to be (sample 0: real views)
         cnt = R.masked_composite(views, masks, alphas, 32)[1]
         n_real = int((alphas[0] != 0).sum())
         assert cnt[0, 0, 0] == 0 and cnt[0, 0, 1] == 1 and cnt[0, 0, 2] == 1 and cnt[0, 0, 3] == n_real and (cnt[1] == 0).all()
+
+
+@pytest.mark.parametrize("n_ref", N_REFS)
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_composite_signed_values_and_inf_voters(shape, n_ref):
+    """the second value family: negative values, and voters equal to the +inf key of a view that does not vote"""
+    views, masks, alphas = _case(shape, "signed")
+    _check_restatement(views, masks, alphas, n_ref)
+    if shape == (2, 32, 16, 16) and n_ref == 32:                 # the family does what it is for: +inf among the voters of the 32-key sort
+        n_real = int((alphas[0] != 0).sum())
+        assert ((masks[0, :n_real] != 0) & np.isinf(views[0, :n_real])).any()
+    if shape == (2, 10, 9, 33) and n_ref == 16:                  # ... and as the median itself
+        assert np.isinf(R.masked_composite(views, masks, alphas, n_ref)[0]).any()
 
 
 @pytest.mark.parametrize("shape", SHAPES + [(3, 12, 40, 56)], ids=lambda s: "x".join(map(str, s)))

@@ -7,8 +7,11 @@
                  on the hand-stacked (view, ref) input, with the parity bounds of tests/test_gpu_parity.py (util._check); d_lrs, d_ref and
                  the parameter gradients against fp64 torch autograd of the restatement below, with the d_lrs bound of
                  tests/test_gpu_input_grad.py (2e-4 of the max-norm, in fp32 and bf16x3, the two precisions that file bounds: with every
-                 slope at 1 at (2, 5, 16, 16), and in fp32 at the default slopes on a small case that no PReLU flip can reach.  Measured:
+                 slope at 1 at (2, 5, 16, 16) and at the ragged (2, 3, 17, 50), and in fp32 at the default slopes on a small case that no PReLU flip
+                 can reach.  Measured:
                  worst of d_lrs / d_ref / any parameter gradient 1.7e-6 fp32 and 2.5e-5 bf16x3 at slopes 1, 2.6e-5 at the default slopes;
+                 at (2, 3, 17, 50) 9.6e-6 fp32 and 1.7e-4 bf16x3 (both fuse.fuse.2.weight, one slope: a single sum; every other
+                 parameter gradient <= 7.3e-5, d_lrs / d_ref 1.1e-6 / 1.5e-6 and 1.3e-5 / 1.2e-5);
                  at the default slopes at (2, 5, 16, 16) the same kernels gave 7.9e-3 with an sr within 1.8e-6: a flipped activation)
   frozen, tiled, ensemble, end to end, the dispatcher ops
 """
@@ -44,8 +47,8 @@ def _batch(V, seed=5, B=2, S=16):
     return lrs, alphas
 
 
-def _cot(B, S, scale=3):
-    return np.random.Generator(np.random.PCG64(77)).standard_normal((B, 1, scale * S, scale * S)).astype(np.float32)
+def _cot(B, S, scale=3, W=None):
+    return np.random.Generator(np.random.PCG64(77)).standard_normal((B, 1, scale * S, scale * (W or S))).astype(np.float32)
 
 
 def _first_tied(lrs, med):
@@ -202,16 +205,32 @@ def _small_case():
     return lrs, alphas, ref
 
 
-@pytest.mark.parametrize("prec,slopes_at_1,small", [("fp32", False, True), ("fp32", True, False), ("bf16x3", True, False)])
+def _ragged_case():
+    """A (2, 3, 17, 50) batch (a 50 x 50 scene cut down; the second sample's last view is padding) with its masked composite: no strip,
+    tile or segment size of the backward divides the frame, and the stem's data gradient runs two tile columns by three tile rows"""
+    lrs, alphas, _ = synth.make_batch(1750, 2, 3, 50, [3, 2])
+    lrs = np.ascontiguousarray(lrs[:, :, :17, :])
+    masks = (np.random.Generator(np.random.PCG64(1750)).random(lrs.shape) < 0.6).astype(np.float32)
+    ref = R.masked_composite(lrs, masks, alphas, 9)[0]
+    assert lrs.shape == (2, 3, 17, 50) and not np.array_equal(ref, O.reference_frame(lrs))
+    return lrs, alphas, ref
+
+
+@pytest.mark.parametrize("prec,slopes_at_1,small", [("fp32", False, True), ("fp32", True, False), ("bf16x3", True, False),
+                                                    ("fp32", True, "ragged"), ("bf16x3", True, "ragged")])
 def test_gradients_with_a_composite_frame_vs_fp64_autograd(prec, slopes_at_1, small):
     """The kernels are pinned at (2, 5, 16, 16) with every PReLU slope at 1, where nothing can flip (as tests/test_gpu_input_grad.py does
-    for bf16x3 and for fp32 at V = 32); the default slopes, PReLU backward included, on the small case no activation of which can flip."""
-    if small:
+    for bf16x3 and for fp32 at V = 32); the default slopes, PReLU backward included, on the small case no activation of which can flip;
+    and with every slope at 1 again at (2, 3, 17, 50), where the frame is wider than one 32-column tile and ragged in both directions
+    (hrn_hrnet_forward_train_ref / hrn_hrnet_backward_ref through their dispatcher op: HRNet.forward itself refuses a frame that is not square)."""
+    if small == "ragged":
+        lrs, alphas, ref = _ragged_case()
+    elif small:
         lrs, alphas, ref = _small_case()
     else:
         lrs, alphas, _, ref, _ = _masked_case()
     slopes = {k: 1.0 for k in _SLOPE_KEYS} if slopes_at_1 else None
-    cot = _cot(lrs.shape[0], lrs.shape[2])
+    cot = _cot(lrs.shape[0], lrs.shape[2], W=lrs.shape[3])
     st = {k: v.double().requires_grad_(True) for k, v in _state(3, slopes=slopes).items()}
     tx = torch.from_numpy(lrs).double().requires_grad_(True)
     ta = torch.from_numpy(alphas).double().requires_grad_(True)
@@ -234,7 +253,18 @@ def test_gradients_with_a_composite_frame_vs_fp64_autograd(prec, slopes_at_1, sm
     assert slopes_at_1 or nearest[0] >= 1e-5, nearest
     m = _fresh_model(True, precision=prec, slopes=slopes)
     x, a, r = util.dev(lrs).requires_grad_(True), util.dev(alphas).requires_grad_(True), util.dev(ref).requires_grad_(True)
-    sr = m(x, a, ref=r)
+    if small == "ragged":
+        # the module's forward takes square frames only (the reference's .view()); the training op behind it takes any, and is called
+        # here exactly as HRNet._forward_ref calls it
+        from hrnet_hip import binding
+        dt = m._train_dtype()
+        dt = m._dtype() if dt is None else dt
+        assert [k for k, _ in m.named_parameters()] == binding.hrnet_param_names(m._num_layers)
+        sr, _ = torch.ops.hrnet_hip.hrnet_forward_train_ref(m._packed_for(dt), x.float().contiguous(), a.float().contiguous(),
+                                                            binding._ref_frame(r, x), [p for _, p in m.named_parameters()], m._num_layers,
+                                                            bool(m.fuse.alpha_residual), dt, m._scale)
+    else:
+        sr = m(x, a, ref=r)
     (sr * util.dev(cot)).sum().backward()
     tol = 2e-4                                                  # tests/test_gpu_input_grad.py: d lrs, of the max-norm
     e_sr = util.rel_err(sr.detach().cpu().numpy(), want_sr.detach().numpy())

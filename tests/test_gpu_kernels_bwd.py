@@ -10,7 +10,7 @@ Bound per element, T = the same expression on absolute values, C = kernel_bounds
   bf16x3 output (hi + lo)              |got - want| <= 2^-16 |want| + C T
   f32 output, every parameter gradient |got - want| <= C T       (accumulated gradients: want = start + sum, T = |start| + sum |terms|)
 Kernels that add in fp32 along a chain keep it at <= 128 terms by the choice of shape; where a case cannot (stem_wgrad's many-tile case,
-stem_dgrad_route's 9 x 64 taps per view) its constant is max(C, n_seq 2^-24) with n_seq computed from the shape, and printed.
+stem_dgrad_route's and stem_dgrad_ref's 9 x 64 taps per view) its constant is max(C, n_seq 2^-24) with n_seq computed from the shape, and printed.
 bf16x3 tensors lie as the backward lays them out (the lo plane directly behind the hi plane) in a buffer with sentinels behind; outputs
 start as sentinels, accumulated gradients from random values; every test asserts that the guards and the inputs are bit-identical after.
 Bit-exact: planes_to_f32 / f32_to_planes and the median.
@@ -28,6 +28,8 @@ Template instance -> production call site (train.hip unless noted) -> tests
   stem_wgrad_kernel<*> + finish         HRNet's stem (sub NULL), ShiftNet's stem (`sub`, strides 2 plane)
                                                                                                  test_stem_wgrad[*-*-*]
   stem_dgrad_route_kernel<*>            d lrs with the median routing                            test_stem_dgrad_route[*-V*-B*-*]
+  stem_dgrad_ref_kernel<*>              d lrs and d ref with the frame given from outside (hrn_hrnet_backward_ref)
+                                                                                                 test_stem_dgrad_ref[*-V*-B*-*], test_stem_dgrad_ref_agrees_with_route[*-V*]
   stem_kernel<*> (only_if_nonpos)       the gated recompute of the stem's pre-activation         test_stem_pre[*-*-*]
   decoder_bwd_kernel<2,4|3,9|4,8> + decoder_bwd_finish_kernel<S>   (f32)
                                         the decoder's backward, every mode                       test_decoder_bwd[S*-*], test_decoder_bwd_null[S*-*]
@@ -43,8 +45,8 @@ import torch
 
 from kernel_bounds import BF, C, GUARD, NAN16, SENT, Acc, Ten, _assert_close, _nchw, _ratio, rnd
 from kernel_refs import (DEC_SLOPES, LEVELS, PRELU_SLOPES, _alphas, decoder_inputs, prelu_inputs, ref_alpha_grad, ref_decoder_bwd, ref_decoder_up,
-                         ref_fuse_df, ref_fuse_scatter, ref_fuse_update, ref_median, ref_pair_add, ref_prelu_bwd, ref_split_planes, ref_stem_dgrad_route,
-                         ref_stem_pre, ref_stem_wgrad, route_inputs, split_inputs)
+                         ref_fuse_df, ref_fuse_scatter, ref_fuse_update, ref_median, ref_pair_add, ref_prelu_bwd, ref_route_index, ref_split_planes,
+                         ref_stem_dgrad_ref, ref_stem_dgrad_route, ref_stem_pre, ref_stem_wgrad, route_inputs, split_inputs)
 from kt import BF16, BF16X3, F32, _cus, _p, _stream, lib as _lib
 
 pytestmark = pytest.mark.gpu
@@ -400,6 +402,112 @@ def test_stem_dgrad_route(dt, V, B, shape):
     _assert_close(f"stem_dgrad_route {KIND[dt]} V={V} B={B} {shape}", "f32", r["got"], want, T * (c / C), layout="b v y x")
 
 
+# the frame given from outside: the routed kernel's shapes and 16 x 64, whose 8 x 32 tiles divide the image exactly (every halo column of a
+# tile seam is an image column, every halo column past the last tile lies outside); 17 x 50 has two tile columns and three tile rows
+REF_SHAPES = dict(ROUTE_SHAPES, **{"16x64": (16, 64)})
+REF_VS = (1, 2, 3, 9, 10, 12)
+REF_CASES = []
+for _dt in (F32, BF16, BF16X3):
+    for _V in REF_VS:
+        for _B in (1, 2):
+            for _sh in REF_SHAPES:
+                REF_CASES.append(pytest.param(_dt, _V, _B, _sh, id=f"{KIND[_dt].replace('x3', 'bf16x3')}-V{_V}-B{_B}-{_sh}"))
+
+
+def _nan_tailed(n):
+    return torch.full((n + 64,), float("nan"), device="cuda")
+
+
+def _ref_case(dt, V, B, shape, every_variant=True):
+    """hrn_kt_stem_dgrad_ref on _route_case's dA and w.  every_variant: three launches - both outputs, d_lrs alone (d_ref NULL), d_ref
+    alone (d_lrs NULL) - and both NULL, which is refused; otherwise the both-outputs launch only.  -> the both-outputs run (the fp32
+    outputs as the kernel wrote them, on the CPU), after the single-output runs were held to it bit for bit"""
+    lib = _lib()
+    H, W = REF_SHAPES[shape]
+    nl, nr = B * V * H * W, B * H * W
+    dA = Ten((B * V, H, W, 64), dt, rnd((B * V, H, W, 64), 72 + V, dt))
+    w = torch.randn((64, 2, 3, 3), generator=torch.Generator().manual_seed(73)) * 0.3
+    wd_, wt = w.cuda(), torch.empty(64 * 18, device="cuda")
+    runs = []
+    for want_lrs, want_ref in ((True, True), (True, False), (False, True))[:3 if every_variant else 1]:
+        dl, dr = _nan_tailed(nl) if want_lrs else None, _nan_tailed(nr) if want_ref else None
+        rc = lib.hrn_kt_stem_dgrad_ref(dt, dA.ptr, _p(wd_), _p(wt), _p(dl), _p(dr), B, V, H, W, _stream())
+        assert rc == 0, (rc, lib.hrn_last_error())
+        torch.cuda.synchronize()
+        runs.append((None if dl is None else dl.cpu(), None if dr is None else dr.cpu()))
+    assert dA.unchanged() and dA.guard_ok() and torch.equal(wd_.cpu(), w), "an input was written"
+    dl0, dr0 = runs[0]
+    out = dict(d_lrs=dl0[:nl].reshape(B, V, H, W), d_ref=dr0[:nr].reshape(B, H, W), dA=dA, w=w, wd=wd_)
+    for t, n in ((dl0, nl), (dr0, nr)):
+        assert bool(torch.isnan(t[n:]).all()), "a write past an output"
+        assert not bool(torch.isnan(t[:n]).any()), "an element was not written"
+    if not every_variant:
+        return out
+    dl1, dr2 = runs[1][0], runs[2][1]
+    for t, n in ((dl1, nl), (dr2, nr)):
+        assert bool(torch.isnan(t[n:]).all()), "a write past an output"
+        assert not bool(torch.isnan(t[:n]).any()), "an element was not written"
+    assert torch.equal(dl1[:nl].view(torch.int32), dl0[:nl].view(torch.int32)), "d_lrs alone differs from d_lrs of the both-outputs run"
+    assert torch.equal(dr2[:nr].view(torch.int32), dr0[:nr].view(torch.int32)), "d_ref alone differs from d_ref of the both-outputs run"
+    # neither output: refused before any launch (wt, the one buffer a launch could still write, stays as it was)
+    wt_nan = torch.full((64 * 18,), float("nan"), device="cuda")
+    rc = lib.hrn_kt_stem_dgrad_ref(dt, dA.ptr, _p(wd_), _p(wt_nan), None, None, B, V, H, W, _stream())
+    msg = lib.hrn_last_error()
+    torch.cuda.synchronize()
+    assert rc == -2 and b"stem dgrad: neither d_lrs nor d_ref is wanted" in msg, (rc, msg)
+    assert bool(torch.isnan(wt_nan).all()) and dA.unchanged()
+    return out
+
+
+def _ref_check(tag, r, B, V, **wrong):
+    """both outputs of _ref_case against ref_stem_dgrad_ref under test_stem_dgrad_route's bound -> (error / bound of d_lrs, of d_ref)"""
+    c = max(C, (9 * 64 + V) * 2.0 ** -24)
+    d_lrs, T_lrs, d_ref, T_ref = ref_stem_dgrad_ref(r["dA"].val, r["w"].double(), B, V, **wrong)
+    if wrong:
+        return (_ratio("f32", r["d_lrs"].double(), d_lrs, T_lrs * (c / C))[0], _ratio("f32", r["d_ref"].double(), d_ref, T_ref * (c / C))[0])
+    return (_assert_close(f"{tag} d_lrs", "f32", r["d_lrs"].double(), d_lrs, T_lrs * (c / C), layout="b v y x"),
+            _assert_close(f"{tag} d_ref", "f32", r["d_ref"].double(), d_ref, T_ref * (c / C), layout="b y x"))
+
+
+@pytest.mark.parametrize("dt,V,B,shape", REF_CASES)
+def test_stem_dgrad_ref(dt, V, B, shape):
+    """stem_dgrad_ref_kernel<ST>: d_lrs and d_ref per element, no element excluded, with test_stem_dgrad_route's bound for its reason: each
+    view's two outputs are chains of 9 x 64 fused multiply-adds in fp32, and d_ref then adds the V views' channel 1: n_seq = 9 * 64 + V.
+    The single-output launches are bit-equal to the both-outputs launch; no output wanted is -2"""
+    r = _ref_case(dt, V, B, shape)
+    n_seq = 9 * 64 + V
+    print(f"stem_dgrad_ref V={V}: n_seq = {n_seq}, constant = {max(C, n_seq * 2.0 ** -24):.3e}")
+    _ref_check(f"stem_dgrad_ref {KIND[dt]} V={V} B={B} {shape}", r, B, V)
+
+
+@pytest.mark.parametrize("V", [9, 10], ids=["V9", "V10"])
+@pytest.mark.parametrize("dt", DTS)
+def test_stem_dgrad_ref_agrees_with_route(dt, V):
+    """The copy against the original, bit for bit, on one dA and w: away from the routed view the routed kernel's d_lrs is the copy's, at
+    the routed view it is float32(d_lrs + d_ref) - both kernels run the same fmaf chains in the same order, acc1 adds the views' channel 1
+    in view order in both, and the routed kernel's last store is the one fp32 add keep + acc1"""
+    lib = _lib()
+    B, shape = 2, "15x33"
+    H, W = REF_SHAPES[shape]
+    r = _ref_case(dt, V, B, shape, every_variant=False)
+    lrs, ref = route_inputs(B, V, H, W, 71 + V)
+    ld, rd, wt = lrs.cuda(), ref.cuda(), torch.empty(64 * 18, device="cuda")
+    routed = _nan_tailed(B * V * H * W)
+    assert lib.hrn_kt_stem_dgrad_route(dt, r["dA"].ptr, _p(r["wd"]), _p(wt), _p(ld), _p(rd), _p(routed), B, V, H, W, _stream()) == 0
+    torch.cuda.synchronize()
+    got = routed.cpu()
+    assert bool(torch.isnan(got[B * V * H * W:]).all()) and r["dA"].unchanged()
+    got = got[:B * V * H * W].reshape(B, V, H, W)
+    sel = ref_route_index(lrs, ref)[:, None]
+    want = r["d_lrs"].scatter_add(1, sel, r["d_ref"][:, None])         # one fp32 add per pixel, at the routed view
+    at_sel = torch.zeros((B, V, H, W), dtype=torch.bool).scatter_(1, sel, True)
+    diff = got.view(torch.int32) != want.view(torch.int32)
+    print(f"stem_dgrad_ref against stem_dgrad_route {KIND[dt]} V={V}: {int((diff & ~at_sel).sum())} of {int((~at_sel).sum())} elements differ away "
+          f"from the routed view, {int((diff & at_sel).sum())} of {int(at_sel.sum())} at it; max |difference| {float((got - want).abs().max()):.3e}")
+    assert int(sel.max()) > 0 and float(r["d_ref"].abs().max()) > 0
+    assert not bool(diff.any())
+
+
 @pytest.mark.parametrize("shape", ["2x3", "15x33", "17x50"])
 @pytest.mark.parametrize("a", [0.25, 0.0, BF(-0.3)], ids=["pos", "zero", "neg"])
 @pytest.mark.parametrize("dt", DTS)
@@ -589,7 +697,7 @@ def test_median_grid_cap():
 
 # ----------------------------------------------------------------------------------------------------------- negative controls
 CONTROLS = ["prelu_zero_positive", "dslope_no_inv", "fuse_df_own_alpha", "fuse_scatter_swap_halves", "median_upper", "route_highest",
-            "decoder_taps_transposed", "f32_to_planes_truncate"]
+            "decoder_taps_transposed", "f32_to_planes_truncate", "ref_drops_last_view", "ref_channels_swapped"]
 
 
 @pytest.mark.parametrize("control", CONTROLS)
@@ -632,6 +740,14 @@ def test_negative_control(control):
         ok = _assert_close("stem_dgrad_route (right reference)", "f32", r["got"], want, T * (c / C), layout="b v y x")
         bad, T = ref_stem_dgrad_route(r["dA"], r["w"], r["lrs"], r["ref"], highest=True)
         worst, _ = _ratio("f32", r["got"], bad, T * (c / C))
+    elif control in ("ref_drops_last_view", "ref_channels_swapped"):
+        B, V = 2, 10
+        r = _ref_case(BF16, V, B, "15x33", every_variant=False)
+        ok = max(_ref_check("stem_dgrad_ref (right reference)", r, B, V))
+        if control == "ref_drops_last_view":        # the window of nine the median has and this sum has not: only d_ref can tell
+            worst = _ref_check("", r, B, V, drop_last_view=True)[1]
+        else:                                       # both outputs must tell
+            worst = min(_ref_check("", r, B, V, swap_channels=True))
     elif control == "decoder_taps_transposed":
         r = _decoder_case(3, "9x27", 0.25)
         ref = ref_decoder_bwd(*r["args"])

@@ -15,7 +15,9 @@ A  deep batch    many 64 x 64 images, and for every hook at least one case of ra
 B  big frame     one image at each fast kernel's in-image limit, W a multiple of 32 and ragged, and the smallest image the guard refuses:
                  three strips (top, middle, bottom; tile-aligned, >= 24 rows, real neighbour rows as halo) per element.  The bf16
                  convolutions must then run on conv3x3.hip's general kernel (read from the profiler's family names) and be right;
-                 v6x3, wgrad_x3, the MFMA stem and stem_dgrad_route must return -2 with their message and write nothing.
+                 v6x3, wgrad_x3, the MFMA stem, stem_dgrad_route and stem_dgrad_ref must return -2 with their message and write nothing.
+                 The masked composite (hrn_masked_composite, f32 only) has both regimes too: a deep batch of 32-view samples, and one
+                 sample whose 32 views of 8200 x 8190 pass 2^31 elements; bit for bit against its numpy restatement.
 C  whole network HRNet.forward in bf16 with B V H W 64 > 2^31 elements (B = 33, V = 16, 256 x 256): samples 0 and B - 1 bit-identical to their
                  forward alone.
 Negative controls: the comparison fails when the reference is taken from the image a 32-bit base would address (m - 2^32 / image bytes).
@@ -447,6 +449,38 @@ def test_stem_dgrad_route_deep_batch(pool, dtn, shape):
         _assert_close(f"stem_dgrad_route {dtn} sample {b}", "f32", got, want, T * (c / C), layout="b v y x")
 
 
+@pytest.mark.parametrize("dtn,shape", DT_SHAPES, ids=DT_SHAPE_IDS)
+def test_stem_dgrad_ref_deep_batch(pool, dtn, shape):
+    """hrn_kt_stem_dgrad_ref (the frame given from outside: no routing, d_lrs and d_ref both wanted): dA [B V][H][W][64] past 2^31 elements;
+    the bound is test_stem_dgrad_ref's (n_seq = 9 x 64 + V fp32 terms), no element excluded"""
+    dt, (H, W), V = DT[dtn], SHAPES[shape], 2
+    lib = _lib()
+    M = _count(dt, "2^31el", H * W * 64)
+    M += M % V
+    B = M // V
+    _need(M * H * W * 64 * ES[dt] * (2 if dt == BF16X3 else 1) / GIB + 2)
+    bs = sorted({m // V for m in boundary_images(M, H * W * 64, ES[dt])})
+    dA = pool.big(M, (H, W, 64), dt, "rand", 105)
+    w = torch.randn((64, 2, 3, 3), generator=torch.Generator().manual_seed(106)) * 0.3
+    d_lrs = pool.keep(torch.full((B * V * H * W + 64,), float("nan"), device="cuda"))
+    d_ref = pool.keep(torch.full((B * H * W + 64,), float("nan"), device="cuda"))
+    wd, wt = w.cuda(), torch.empty(64 * 18, device="cuda")
+    c0 = dA.checksum()
+    rc = lib.hrn_kt_stem_dgrad_ref(dt, dA.ptr, _p(wd), _p(wt), _p(d_lrs), _p(d_ref), B, V, H, W, _stream())
+    assert rc == 0, (rc, lib.hrn_last_error())
+    torch.cuda.synchronize()
+    assert dA.checksum() == c0 and bool(torch.isnan(d_lrs[B * V * H * W:]).all()) and bool(torch.isnan(d_ref[B * H * W:]).all())
+    _says(f"stem_dgrad_ref {dtn} B={B}", "2^31el", dA)
+    c = max(C, (9 * 64 + V) * 2.0 ** -24)
+    for b in bs:
+        dAb = torch.stack([dA.img(b * V + v) for v in range(V)])
+        want_l, T_l, want_r, T_r = K.ref_stem_dgrad_ref(dAb, w.double(), 1, V)
+        got_l = d_lrs[b * V * H * W:(b + 1) * V * H * W].cpu().double().reshape(1, V, H, W)
+        got_r = d_ref[b * H * W:(b + 1) * H * W].cpu().double().reshape(1, H, W)
+        _assert_close(f"stem_dgrad_ref {dtn} sample {b} d_lrs", "f32", got_l, want_l, T_l * (c / C), layout="b v y x")
+        _assert_close(f"stem_dgrad_ref {dtn} sample {b} d_ref", "f32", got_r, want_r, T_r * (c / C), layout="b y x")
+
+
 # ----------------------------------------------------------------------------------------------------------- the decoder
 DEC_CASES = [(2, d, "64x64") for d in DTN] + [(2, "bf16", "33x50")] + [(4, d, "64x64") for d in DTN]
 
@@ -785,6 +819,128 @@ def test_median_deep_batch(pool, shape):
         assert bad == 0
 
 
+# ----------------------------------------------------------------------------------------------------------- the masked composite
+def _sum64(t):
+    """a wrapping int64 sum of an f32 device tensor's words (an even count), computed on the device: equal before and after <=> unchanged"""
+    return int(t.view(torch.int64).sum())
+
+
+def _composite_inputs(pool, B, V, H, W, seed):
+    """views (eighths in [0, 3): ties) and masks (0 at 40 % of the pixels, else 1, 2 or 3) of (B, V, H, W), generated on the device in
+    place, chunk by chunk; alphas (B, V) with 0, 3, 6, 9 or 12 trailing zeros by sample"""
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    n = B * V * H * W
+    views, masks = pool.keep(torch.empty(n, device="cuda")), pool.keep(torch.empty(n, device="cuda"))
+    for a in range(0, n, Big.CHUNK):
+        b = min(n, a + Big.CHUNK)
+        views[a:b].random_(0, 24, generator=gen).mul_(0.125)
+        masks[a:b].random_(0, 5, generator=gen).sub_(1.0).clamp_(min=0.0)
+    alphas = (torch.arange(V)[None] < (V - 3 * (torch.arange(B)[:, None] % 5))).float()
+    return views.view(B, V, H, W), masks.view(B, V, H, W), alphas
+
+
+def _nan_out(pool, n):
+    return pool.keep(torch.full((n + 64,), float("nan"), device="cuda"))
+
+
+def _bits_equal(got, want):
+    import numpy as np
+    return np.array_equal(got.cpu().numpy().view(np.uint32), np.ascontiguousarray(want).view(np.uint32))
+
+
+@pytest.mark.parametrize("shape", list(SHAPES), ids=[s + "-2^31el" for s in SHAPES])
+def test_masked_composite_deep_batch(pool, shape):
+    """hrn_masked_composite, masked_composite_kernel<9>: views, masks and filled [B][32][H][W] f32 past 2^31 elements, n_ref = 9 so that the
+    loop over the views 9..31 that do not vote runs at the high offsets too; ref, count and filled bit for bit against the numpy
+    restatement at sample 0, the last sample and the samples at every crossing.  Control (64 x 64, where it is a whole number of samples):
+    the restatement of the views a 32-bit byte base would address, sample b - 2^32 / (V H W 4), is told from the output"""
+    import composite_ref as R
+    lib = _lib()
+    V, n_ref, (H, W) = 32, 9, SHAPES[shape]
+    hw = H * W
+    B = _count(F32, "2^31el", V * hw)
+    _need(3 * B * V * hw * 4 / GIB + 2 * B * hw * 4 / GIB + 2)
+    bs = boundary_images(B, V * hw, 4)
+    views, masks, alphas = _composite_inputs(pool, B, V, H, W, 261)
+    ad = alphas.cuda()
+    ref, count, filled = _nan_out(pool, B * hw), _nan_out(pool, B * hw), _nan_out(pool, B * V * hw)
+    sums = [(t, _sum64(t)) for t in (views, masks)]
+    rc = lib.hrn_masked_composite(_p(views), _p(masks), _p(ad), B, V, H, W, n_ref, _p(ref), _p(count), _p(filled), _stream())
+    assert rc == 0, (rc, lib.hrn_last_error())
+    torch.cuda.synchronize()
+    assert all(_sum64(t) == c for t, c in sums) and torch.equal(ad.cpu(), alphas), "the launch wrote one of its inputs"
+    for t, n in ((ref, B * hw), (count, B * hw), (filled, B * V * hw)):
+        assert bool(torch.isnan(t[n:]).all()), "a write past an output"
+    got = crossed(B * V * hw, 4)
+    print(f"masked_composite {shape} B={B}: views {B * V * hw * 4 / GIB:.2f} GiB {got}; samples {bs}")
+    assert "2^31el" in got and len(bs) >= 5
+    assert any(float(alphas[b, -1]) == 0 for b in bs) and any(float(alphas[b, -1]) != 0 for b in bs)
+    wrap = (1 << 32) // (V * hw * 4) if (1 << 32) % (V * hw * 4) == 0 else None
+    told = 0
+    for b in bs:
+        v, m, a = views[b:b + 1].cpu().numpy(), masks[b:b + 1].cpu().numpy(), alphas[b:b + 1].numpy()
+        want_ref, want_count, want_filled = R.masked_composite(v, m, a, n_ref)
+        g_ref, g_count = ref[b * hw:(b + 1) * hw].view(1, H, W), count[b * hw:(b + 1) * hw].view(1, H, W)
+        assert _bits_equal(g_ref, want_ref), ("ref", b)
+        assert _bits_equal(g_count, want_count), ("count", b)
+        assert _bits_equal(filled[b * V * hw:(b + 1) * V * hw].view(1, V, H, W), want_filled), ("filled", b)
+        if wrap is not None and b >= wrap:
+            wrong = R.masked_composite(views[b - wrap:b - wrap + 1].cpu().numpy(), m, a, n_ref)[0]
+            differ = int((g_ref.cpu().numpy() != wrong).sum())
+            print(f"masked_composite sample {b} against the views of sample {b - wrap}: {differ} of {hw} pixels differ")
+            assert differ > hw // 2, f"the comparison does not tell sample {b - wrap} from sample {b}"
+            told += 1
+    assert wrap is None or told >= 2
+
+
+def test_masked_composite_big_frame(pool):
+    """hrn_masked_composite, masked_composite_kernel<32>: one sample of 32 views of 8200 x 8190, 32 H W > 2^31 elements.  Only view 31 reaches
+    past element 2^31 (from row 8008 on; views 16..31 lie past byte 2^32), so view 31 is a real view that votes - the views without a
+    vote are 3, 4 and 5 - and the bottom strip lies wholly past element 2^31 in it.  The grid is 262336 tiles of one sample.  ref and count
+    bit for bit against the numpy restatement on two rows each at the top, in the middle and at the bottom.  Control: at the bottom strip
+    the restatement of the same pixels with view 31's values and mask exchanged for others must NOT be the output - a kernel that read view
+    31 from a wrapped offset would otherwise pass"""
+    import composite_ref as R
+    lib = _lib()
+    B, V, n_ref, H, W = 1, 32, 32, 8200, 8190
+    hw = H * W
+    first_past = ((1 << 31) - (V - 1) * hw) // W                 # the first row of view 31 that lies wholly or partly past element 2^31
+    assert (V - 1) * hw < 1 << 31 < V * hw and first_past == 8008 and first_past < H - 2
+    _need(2 * V * hw * 4 / GIB + 2 * hw * 4 / GIB + 2)
+    views, masks, alphas = _composite_inputs(pool, B, V, H, W, 262)
+    alphas[0, 3:6] = 0
+    assert float(alphas[0, V - 1]) != 0
+    ad = alphas.cuda()
+    ref, count = _nan_out(pool, hw), _nan_out(pool, hw)
+    sums = [(t, _sum64(t)) for t in (views, masks)]
+    rc = lib.hrn_masked_composite(_p(views), _p(masks), _p(ad), B, V, H, W, n_ref, _p(ref), _p(count), None, _stream())
+    assert rc == 0, (rc, lib.hrn_last_error())
+    torch.cuda.synchronize()
+    assert all(_sum64(t) == c for t, c in sums), "the launch wrote one of its inputs"
+    assert bool(torch.isnan(ref[hw:]).all()) and bool(torch.isnan(count[hw:]).all()), "a write past an output"
+    print(f"masked_composite big frame {H}x{W}: views {V * hw * 4 / GIB:.2f} GiB {crossed(V * hw, 4)}")
+    assert "2^31el" in crossed(V * hw, 4)
+    for y0 in (0, H // 2, H - 2):
+        y1 = y0 + 2
+        v, m = views[:, :, y0:y1].cpu().numpy(), masks[:, :, y0:y1].cpu().numpy()
+        want_ref, want_count, _ = R.masked_composite(v, m, alphas.numpy(), n_ref)
+        g_ref, g_count = ref[y0 * W:y1 * W].view(1, 2, W), count[y0 * W:y1 * W].view(1, 2, W)
+        assert _bits_equal(g_ref, want_ref), ("ref", y0)
+        assert _bits_equal(g_count, want_count), ("count", y0)
+        assert want_count.max() > 16 and want_count.min() < 16
+        if y0 >= first_past:
+            # the outputs depend on view 31 here: its mask inverted moves count at every pixel, its values moved out of the others' range
+            # move the median wherever it votes as one of the upper half
+            v2, m2 = v.copy(), m.copy()
+            v2[:, V - 1] += 100.0
+            m2[:, V - 1] = (m[:, V - 1] == 0).astype(m.dtype)
+            wrong_ref = R.masked_composite(v2, m, alphas.numpy(), n_ref)[0]
+            wrong_count = R.masked_composite(v, m2, alphas.numpy(), n_ref)[1]
+            d_ref, d_count = int((g_ref.cpu().numpy() != wrong_ref).sum()), int((g_count.cpu().numpy() != wrong_count).sum())
+            print(f"masked_composite big frame rows {y0}..{y1}: with another view 31, ref differs at {d_ref} and count at {d_count} of {2 * W} pixels")
+            assert d_count == 2 * W and d_ref > 2 * W // 20, "the comparison does not see view 31, the one view past element 2^31"
+
+
 # ----------------------------------------------------------------------------------------------------------- negative controls
 @pytest.mark.parametrize("which", ["conv", "add"])
 def test_negative_control(pool, which):
@@ -940,6 +1096,18 @@ def test_stem_dgrad_route_refuses_grid(pool):
     torch.cuda.synchronize()
     assert rc == -2 and b"exceed the grid" in msg, (rc, msg)
     assert bool(torch.isnan(out).all())
+
+
+def test_stem_dgrad_ref_refuses_grid(pool):
+    """stem_dgrad_ref launches the routed kernel's grid: tiles B = 2^31 is refused before any launch, and neither output is written"""
+    lib = _lib()
+    d_lrs, d_ref = pool.keep(torch.full((4096,), float("nan"), device="cuda")), pool.keep(torch.full((4096,), float("nan"), device="cuda"))
+    small = torch.zeros(4096, device="cuda")
+    rc = lib.hrn_kt_stem_dgrad_ref(BF16, _p(small), _p(small), _p(small), _p(d_lrs), _p(d_ref), 1 << 30, 1, 9, 1, _stream())
+    msg = lib.hrn_last_error()
+    torch.cuda.synchronize()
+    assert rc == -2 and b"exceed the grid" in msg, (rc, msg)
+    assert bool(torch.isnan(d_lrs).all()) and bool(torch.isnan(d_ref).all()) and not bool(small.any())
 
 
 # ----------------------------------------------------------------------------------------------------------- C: the whole network

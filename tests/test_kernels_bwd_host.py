@@ -148,6 +148,35 @@ def test_stem_references(V):
     assert bool((T >= d_lrs.abs() - 1e-12).all())
 
 
+@pytest.mark.parametrize("V", [1, 2, 3, 9, 10, 12])
+def test_stem_dgrad_ref_reference(V):
+    """conv2d(cat(lr, ref)) with `ref` a leaf of its own (the frame given from outside): d_lrs is channel 0 per view, d_ref channel 1 summed
+    over ALL V views of the sample (no window of nine, unlike the median), at a ragged shape with two tile columns and three tile rows"""
+    B, H, W = 2, 17, 50
+    lrs = _rand((B, V, H, W), 20 + V).requires_grad_(True)
+    ref = _rand((B, H, W), 21 + V).requires_grad_(True)
+    w = _rand((64, 2, 3, 3), 22) * 0.3
+    x = torch.stack([lrs, ref[:, None].expand(-1, V, -1, -1)], 2).reshape(B * V, 2, H, W)
+    dA = _rand((B * V, H, W, 64), 23)
+    (F.conv2d(x, w, None, padding=1) * K._nchw(dA)).sum().backward()
+    d_lrs, T_lrs, d_ref, T_ref = K.ref_stem_dgrad_ref(dA, w, B, V)
+    assert tuple(d_lrs.shape) == (B, V, H, W) and tuple(d_ref.shape) == (B, H, W)
+    _close(d_lrs, lrs.grad)
+    _close(d_ref, ref.grad)
+    assert bool((T_lrs >= d_lrs.abs() - 1e-12).all()) and bool((T_ref >= d_ref.abs() - 1e-12).all())
+    # the routed reference is this one with d_ref added at the routed view
+    li, med = K.route_inputs(B, V, H, W, 71 + V)
+    routed, Tr = K.ref_stem_dgrad_route(dA, w, li, med)
+    sel = K.ref_route_index(li, med)[:, None]
+    _close(routed, d_lrs.scatter_add(1, sel, d_ref[:, None]))
+    _close(Tr, T_lrs.scatter_add(1, sel, T_ref[:, None]))
+    # the wrong references of the GPU negative controls are wrong
+    if V > 1:
+        assert not torch.equal(K.ref_stem_dgrad_ref(dA, w, B, V, drop_last_view=True)[2], d_ref)
+    sw = K.ref_stem_dgrad_ref(dA, w, B, V, swap_channels=True)
+    assert not torch.equal(sw[0], d_lrs) and not torch.equal(sw[2], d_ref)
+
+
 def test_stem_wgrad_reference_with_sub():
     """`sub` is subtracted inside the image only, before the zero padding (ShiftNet's mean-free input)"""
     M, H, W = 5, 4, 6

@@ -51,6 +51,12 @@ def test_wgrad_x3_and_stem_limits(lib):
         assert rc == -2 and b"exceed the 32-bit segment count" in lib.hrn_last_error()
     rc = lib.hrn_kt_stem_dgrad_route(BF16, p, p, p, p, p, p, 1 << 30, 1, 9, 1, None)
     assert rc == -2 and b"exceed the grid" in lib.hrn_last_error()
+    # the frame given from outside: the same grid, the same limit, whichever outputs are wanted; and no output wanted at all
+    for d_lrs, d_ref in ((p, p), (p, None), (None, p)):
+        rc = lib.hrn_kt_stem_dgrad_ref(BF16, p, p, p, d_lrs, d_ref, 1 << 30, 1, 9, 1, None)
+        assert rc == -2 and b"stem dgrad: 1073741824 samples of 9 x 1 exceed the grid" in lib.hrn_last_error()
+    rc = lib.hrn_kt_stem_dgrad_ref(BF16, p, p, p, None, None, 1, 1, 9, 1, None)
+    assert rc == -2 and b"neither d_lrs nor d_ref is wanted" in lib.hrn_last_error()
     assert lib.hrn_kt_launch_count(b"conv_general") == 0 and lib.hrn_kt_launch_count(b"stem_wgrad") == 0
 
 
