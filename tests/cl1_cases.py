@@ -5,6 +5,9 @@ import numpy as np
 import torch
 
 B = 3
+# the tolerances of tests/test_gpu_cl1_loss.py (its docstring): relative on out and the statistics; of the max-norm per element of d_srs
+TOL = 1e-5
+GRAD_TOL = 1e-6
 SHAPES = [(20, 20), (37, 53), (53, 37), (96, 96)]     # one tile; odd and rectangular; two tile rows; three tile rows
 BORDERS = [0, 1, 3]
 WIDE = [((40, 300), 8), ((70, 139), 5)]               # the widest halo and three tile columns; a second tile column

@@ -370,6 +370,54 @@ class Big:
         return bool((self.raw == SENT).all())
 
 
+GIB = 1 << 30
+
+
+class _Pool:
+    """the device tensors of one test: freed at teardown whatever happened (a failed test's frames would otherwise keep them alive).
+    tests/test_gpu_large_offsets.py and tests/test_gpu_large_offsets_scene.py each build their `pool` fixture from it."""
+
+    def __init__(self):
+        self.items = []
+
+    def big(self, *a, **k):
+        t = Big(*a, **k)
+        self.items.append(t)
+        return t
+
+    def keep(self, t):
+        self.items.append(t)
+        return t
+
+    def free(self):
+        for t in self.items:
+            if isinstance(t, Big):
+                t.raw = None
+            else:
+                t.untyped_storage().resize_(0)
+        self.items = []
+
+
+def _need(gib):
+    import pytest
+    free, _ = torch.cuda.mem_get_info()
+    if free < gib * GIB:
+        pytest.skip(f"needs {gib} GiB of device memory, {free / GIB:.1f} free")
+
+
+def _sum64(t):
+    """a wrapping int64 sum of an f32 device tensor's words (an even count), computed on the device: equal before and after <=> unchanged"""
+    return int(t.view(torch.int64).sum())
+
+
+def _nan_out(pool, n):
+    return pool.keep(torch.full((n + 64,), float("nan"), device="cuda"))
+
+
+def _bits_equal(got, want):
+    return np.array_equal(got.cpu().numpy().view(np.uint32), np.ascontiguousarray(want).view(np.uint32))
+
+
 # ----------------------------------------------------------------------------------------------------------- the registered tail
 # tests/test_gpu_kernels_tail.py (GPU) and tests/test_kernels_tail_host.py (CPU): the Lanczos shift, its backward, the loss and score kernels.
 # The fp32 kernels (taps, shift, adjoint, tap gradient, loss_backward_kernel) are held to c T like every other family; the kernels that

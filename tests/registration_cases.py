@@ -19,6 +19,9 @@ import registration_ref as R
 
 SCORE_BOUND = 4e-7           # DESIGN.md sections 7f / 7g: a device score against fp64 (GRID_BOUND, SCORE_BOUND of the existing tests)
 DEVICE_BOUND = 8e-7          # section 7g: two device paths against each other
+# tests/test_gpu_registration_scene.py's two bounds (tests/test_gpu_large_offsets_scene.py holds its alone launches to APPLY_BOUND too)
+GRID_BOUND = 4e-7            # measured 8.04e-8 there, times 4; this path on an MI355X: 8.04e-8 (16 x 16), 4.3e-8 beyond
+APPLY_BOUND = 8e-7           # section 7f: measured 1.77e-7 there, times 4; this path on an MI355X: 1.77e-7 (257 x 144)
 ADMIT = 1e-7                 # a quarter of SCORE_BOUND: what the fp32 resampling alone may cost on a case (the admission rule)
 
 PAIRS = {"control": (0.1, 0.0), "c0.01-s0.3": (0.01, 0.3), "c0.01-s0.6": (0.01, 0.6)}

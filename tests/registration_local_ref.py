@@ -80,11 +80,11 @@ def axis_weights(L, block):
     return k, k + 1, t
 
 
-def field_at_pixels(field, H, W, block, rounded=True):
+def field_at_pixels(field, H, W, block, rounded=True, rows=None):
     """field (by, bx, 2) -> (H, W, 2): (1 - ty) ((1 - tx) N00 + tx N01) + ty ((1 - tx) N10 + tx N11) in fp64, in this order; rounded to
-    fp32 as a grid coordinate is (rounded=False: the fp64 values)."""
+    fp32 as a grid coordinate is (rounded=False: the fp64 values).  rows = (a, b): only the frame's rows a .. b - 1, (b - a, W, 2)."""
     N = np.asarray(field, np.float32).astype(np.float64)
-    ky, ky1, ty = axis_weights(H, block)
+    ky, ky1, ty = (w[slice(*rows)] if rows is not None else w for w in axis_weights(H, block))
     kx, kx1, tx = axis_weights(W, block)
     ty, tx = ty[:, None, None], tx[None, :, None]
     n00, n01 = N[ky[:, None], kx[None, :]], N[ky[:, None], kx1[None, :]]

@@ -7,6 +7,11 @@ import numpy as np
 import registration_ref as R
 
 WEIGHTS = np.array([1.0, 3.0, 3.0, 1.0]) / 8.0
+# reduce2 against fp64 on values in [0, 1): 1.67e-7 is the largest |device - fp64| measured on an MI355X over the five shapes, four
+# alignments and both mask forms of tests/test_gpu_registration_pyramid.py (under three ulp of a value in 0.5..1: sixteen fused
+# multiply-adds and one divide); times 4, rounded up to one digit, and under the cap of 1e-6.  The neighbour of tests/kernel_bounds.py's
+# figures.
+REDUCE2_BOUND = 7e-7
 
 
 def reduce2(x, mask=None):

@@ -3,6 +3,22 @@ Evaluator.shift_cPSNR (src/Evaluator.py:52-73) over the brightness-corrected cMS
 gradient: the selected offset is picked on detached values, so the gradient flows through that offset alone.  No test logic here."""
 import torch
 
+# the tolerances of tests/test_gpu_shift_loss.py (derived in its docstring): relative on the reductions; of the max-norm per element of d_srs
+TOL = 1e-5
+GRAD_TOL = 1e-6
+
+
+def frame_of_row_ranges(rows_of, ranges, H, reach):
+    """For maps that are zero outside the row ranges [(y0, y1)] of an (H, W) frame: the small frame whose searched loss is the big frame's -
+    each range with `reach` real neighbour rows on either side (cut at the frame's edges, where the crop's own limits are the same),
+    stacked.  A clear pixel meets only rows within 2 border (and, for cSSIM, a window) of itself, so with reach >= that every term of
+    every sum of the big frame is a term of the small one and the rest of both is masked.  rows_of(a, b) -> a tuple of (b - a, W)
+    tensors (srs, hrs, maps).  -> (the stacked tensors, each (1, rows, W); the windows [(a, b)])"""
+    windows = [(max(0, y0 - reach), min(H, y1 + reach)) for y0, y1 in sorted(ranges)]
+    assert all(b0 <= a1 for (_, b0), (a1, _) in zip(windows, windows[1:])), "ranges closer than their reach"
+    parts = [rows_of(a, b) for a, b in windows]
+    return tuple(torch.cat([p[i] for p in parts])[None] for i in range(len(parts[0]))), windows
+
 
 def all_cmse(srs, hrs, maps, border, clip=False):
     """(B,H,W) x 3 -> (cMSE (B, (2 border + 1)^2) float64, differentiable in srs; n (B, K) clear pixels), k = u (2 border + 1) + v."""

@@ -20,8 +20,7 @@ import util
 pytestmark = pytest.mark.gpu
 
 B = C.B
-TOL = 1e-5
-GRAD_TOL = 1e-6
+TOL, GRAD_TOL = C.TOL, C.GRAD_TOL
 D_OUT = torch.tensor([1.0, -0.5, 2.0])
 
 _cache = {}

@@ -30,12 +30,12 @@ import pytest
 import torch
 
 import kernel_refs as K
-from kernel_bounds import C, C_F32, Acc, Big, _assert_close, _nchw, _ratio, boundary_images, crossed
+from kernel_bounds import (C, C_F32, GIB, Acc, Big, _assert_close, _bits_equal, _nan_out, _nchw, _need, _Pool, _ratio, _sum64, boundary_images,
+                           crossed)
 from kt import BF16, BF16X3, F32, _launches, _p, _stream, lib as _lib
 
 pytestmark = pytest.mark.gpu
 
-GIB = 1 << 30
 DT = {"bf16": BF16, "bf16x3": BF16X3, "f32": F32}
 DTN = ["bf16", "bf16x3", "f32"]
 KIND = {F32: "f32", BF16: "bf16", BF16X3: "x3"}
@@ -57,30 +57,6 @@ def _count(dt, cross, per):
     return _top(dt, cross) // per + 2
 
 
-class _Pool:
-    """the device tensors of one test: freed at teardown whatever happened (a failed test's frames would otherwise keep them alive)"""
-
-    def __init__(self):
-        self.items = []
-
-    def big(self, *a, **k):
-        t = Big(*a, **k)
-        self.items.append(t)
-        return t
-
-    def keep(self, t):
-        self.items.append(t)
-        return t
-
-    def free(self):
-        for t in self.items:
-            if isinstance(t, Big):
-                t.raw = None
-            else:
-                t.untyped_storage().resize_(0)
-        self.items = []
-
-
 @pytest.fixture
 def pool(request):
     gc.collect()
@@ -95,12 +71,6 @@ def pool(request):
     torch.cuda.empty_cache()
     print(f"\nPEAK {request.node.name}: {peak / GIB:.2f} GiB")
     assert peak <= 32 * GIB, f"{peak / GIB:.1f} GiB held at once"
-
-
-def _need(gib):
-    free, _ = torch.cuda.mem_get_info()
-    if free < gib * GIB:
-        pytest.skip(f"needs {gib} GiB of device memory, {free / GIB:.1f} free")
 
 
 def _scratch(pool):
@@ -820,11 +790,6 @@ def test_median_deep_batch(pool, shape):
 
 
 # ----------------------------------------------------------------------------------------------------------- the masked composite
-def _sum64(t):
-    """a wrapping int64 sum of an f32 device tensor's words (an even count), computed on the device: equal before and after <=> unchanged"""
-    return int(t.view(torch.int64).sum())
-
-
 def _composite_inputs(pool, B, V, H, W, seed):
     """views (eighths in [0, 3): ties) and masks (0 at 40 % of the pixels, else 1, 2 or 3) of (B, V, H, W), generated on the device in
     place, chunk by chunk; alphas (B, V) with 0, 3, 6, 9 or 12 trailing zeros by sample"""
@@ -837,15 +802,6 @@ def _composite_inputs(pool, B, V, H, W, seed):
         masks[a:b].random_(0, 5, generator=gen).sub_(1.0).clamp_(min=0.0)
     alphas = (torch.arange(V)[None] < (V - 3 * (torch.arange(B)[:, None] % 5))).float()
     return views.view(B, V, H, W), masks.view(B, V, H, W), alphas
-
-
-def _nan_out(pool, n):
-    return pool.keep(torch.full((n + 64,), float("nan"), device="cuda"))
-
-
-def _bits_equal(got, want):
-    import numpy as np
-    return np.array_equal(got.cpu().numpy().view(np.uint32), np.ascontiguousarray(want).view(np.uint32))
 
 
 @pytest.mark.parametrize("shape", list(SHAPES), ids=[s + "-2^31el" for s in SHAPES])

@@ -22,9 +22,8 @@ import registration_ref as R
 
 pytestmark = pytest.mark.gpu
 
-SCORE_BOUND = 4e-7           # DESIGN.md sections 7f / 7g: a device score against fp64
-DEVICE_BOUND = 8e-7          # section 7g: two device paths against each other
-APPLY_BOUND = 8e-7           # sections 7f / 7g: a resampled pixel against fp64
+from registration_cases import APPLY_BOUND, DEVICE_BOUND, SCORE_BOUND      # sections 7f / 7g: 4e-7 of a score against fp64, 8e-7 between two
+                                                                           # device paths, 8e-7 of a resampled pixel against fp64
 NODE_BOUND_PX = 1.5 * 0.0243  # tests/test_registration_local_host.py: 1.5 times the restatement's worst node error over seeds 1..3
 
 CASES = [((1, 2, 16, 16), 64), ((1, 2, 130, 203), 64), ((1, 2, 257, 144), 128), ((2, 3, 200, 264), 64)]

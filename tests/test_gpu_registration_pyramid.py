@@ -26,10 +26,7 @@ import registration_ref as R
 pytestmark = pytest.mark.gpu
 
 SCORE_BOUND = 4e-7           # DESIGN.md sections 7f / 7g: a device score against fp64
-# reduce2 against fp64 on values in [0, 1): 1.67e-7 is the largest |device - fp64| measured on an MI355X over the five shapes, four
-# alignments and both mask forms below (under three ulp of a value in 0.5..1: sixteen fused multiply-adds and one divide); times 4, rounded
-# up to one digit, and under the cap of 1e-6.  The neighbour of tests/kernel_bounds.py's figures.
-REDUCE2_BOUND = 7e-7
+REDUCE2_BOUND = Y.REDUCE2_BOUND
 SHIFT_BOUND_PX = 0.02        # the project's bound on a recovered shift
 # tests/test_registration_pyramid_host.py: the restatement's worst error over seeds 1..3, four views each
 RESTATEMENT_WORST_PX = {(64, 80): 0.00540, (96, 144): 0.00406}

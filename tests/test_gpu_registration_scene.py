@@ -16,11 +16,10 @@ import pytest
 import torch
 
 import registration_ref as R
+from registration_cases import APPLY_BOUND, GRID_BOUND        # the bounds of this file; tests/registration_cases.py holds them
 
 pytestmark = pytest.mark.gpu
 
-GRID_BOUND = 4e-7            # measured 8.04e-8 there, times 4; this path on an MI355X: 8.04e-8 (16 x 16), 4.3e-8 beyond
-APPLY_BOUND = 8e-7           # section 7f: measured 1.77e-7 there, times 4; this path on an MI355X: 1.77e-7 (257 x 144)
 RECOVERY_PX = 0.02           # the project's bound on every component of a recovered shift
 
 SHAPES = [(2, 3, 16, 16), (1, 2, 33, 47), (1, 2, 128, 128), (1, 2, 130, 203), (1, 2, 257, 144), (1, 2, 16, 300)]

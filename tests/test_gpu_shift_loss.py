@@ -21,8 +21,7 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(20, 20), (37, 53), (53, 37), (96, 96)]
 BORDERS = [0, 1, 3]
 B = 3
-TOL = 1e-5
-GRAD_TOL = 1e-6
+TOL, GRAD_TOL = R.TOL, R.GRAD_TOL
 
 
 def _random(H, W, seed, lo=0.0, hi=1.0):

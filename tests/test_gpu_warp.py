@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 2, 24, 40), (1, 3, 33, 47), (2, 2, 130, 203)]
 IDS = ["x".join(map(str, s)) for s in SHAPES]
-SHIFTS = [(0.37, -0.62), (2.0, 0.0), (0.0, 0.0), (-3.75, 4.125), (0.9999999, -1e-7), (30.0, 0.0), (300.0, 0.0)]
+SHIFTS = WR.SHIFTS
 SENTINEL = 0x7F7F7F7F
 
 

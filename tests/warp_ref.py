@@ -13,6 +13,10 @@ import numpy as np
 
 import registration_ref as R
 
+# the shifts every shape of tests/test_gpu_warp.py meets (its docstring says what each is for); tests/test_gpu_large_offsets_scene.py cycles
+# through them too
+SHIFTS = [(0.37, -0.62), (2.0, 0.0), (0.0, 0.0), (-3.75, 4.125), (0.9999999, -1e-7), (30.0, 0.0), (300.0, 0.0)]
+
 
 def _sinc_slope(t):
     """sinc'(t) for sinc(t) = sin(pi t) / (pi t).  The closed form (cos(pi t) - sinc(t)) / t cancels near 0: below 1e-2 the series
