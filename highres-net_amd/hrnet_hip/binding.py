@@ -171,6 +171,10 @@ SIGNATURES = {
     "hrn_mncc_apply_scene": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 4 + [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hrn_mncc_apply_backward_workspace_bytes": (_c.c_size_t, [_c.c_int] * 4),
     "hrn_mncc_apply_backward": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 4 + [_c.c_void_p] * 3 + [_c.c_size_t, _c.c_void_p]),
+    "hrn_subpixel_loss_workspace_bytes": (_c.c_size_t, [_c.c_int] * 4),
+    "hrn_subpixel_loss_train": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 6 + [_c.c_float, _c.c_int] + [_c.c_void_p] * 4
+                                + [_c.c_size_t, _c.c_void_p]),
+    "hrn_subpixel_loss_backward": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 5 + [_c.c_void_p] * 2 + [_c.c_size_t, _c.c_void_p]),
     "hrn_mncc_local_blocks": (_c.c_int, [_c.c_int] * 2),
     "hrn_mncc_local_workspace_bytes": (_c.c_size_t, [_c.c_int] * 6),
     "hrn_mncc_search_local": (_c.c_int, [_c.c_void_p] * 5 + [_c.c_int] * 6 + [_c.c_float, _c.c_int, _c.c_float] + [_c.c_void_p] * 4
@@ -1097,6 +1101,61 @@ def cl1_loss_backward(srs, hrs, hr_maps, stats, d_out, border_w=3, clip=False, e
     with torch.cuda.device(srs.device):
         _check(lib.hrn_cl1_loss_backward(_ptr(srs), _ptr(hrs), _ptr(hr_maps), _ptr(stats.contiguous()), _ptr(d_out), B, H, W, border_w,
                                          int(bool(clip)), eps, _ptr(d_srs), _stream()), "hrn_cl1_loss_backward")
+    return d_srs
+
+
+SUBPIXEL_STATS = 8        # hrn_subpixel_loss_train's stats: n*, b*, cMSE*, dy*, dx*, mean sr, mean hr under m0, centred bias
+
+
+def _subpixel_loss_args(srs, hrs, hr_maps, metric, border_w):
+    """the frames, the metric and the border of the sub-pixel searched loss; the search's own limits are mncc_int's"""
+    if metric not in ("cMSE", "cPSNR"):
+        raise ValueError(f"the searched loss is defined for 'cMSE' and 'cPSNR'; got {metric!r}")
+    srs, hrs, hr_maps = _bhw_frames(srs, hrs, hr_maps)
+    border_w = int(border_w)
+    if border_w < 0 or border_w > 8 or min(srs.shape[1:]) <= 2 * border_w:
+        raise ValueError(f"border_w must be 0..8 and smaller than half of each side; got {border_w} for frames {tuple(srs.shape[1:])}")
+    return srs, hrs, hr_maps, border_w
+
+
+def _subpixel_workspace(B, H, W, P, device):
+    # MNCC_POINTS is defined with the registration wrappers below; this runs after the module is loaded
+    return _mncc_workspace("hrn_subpixel_loss_workspace_bytes", (B, H, W, P), "subpixel_loss", f"B={B} H={H} W={W} P={P}", device)
+
+
+def subpixel_loss_train(srs, hrs, hr_maps, metric="cPSNR", border_w=3, points_per_dim=7, levels=4, radius=3.0):
+    """Forward of the sub-pixel searched loss on (B,H,W) frames: -> (out (B,), stats (B,8) f64 = {n*, b*, cMSE*,
+    dy*, dx*, mean sr, mean hr, centred bias} at the point s* = (dy*, dx*) the search found, trace (B,levels,3) f32 = (dy, dx, cMSE) of
+    every level's point)."""
+    lib = load_library()
+    srs, hrs, hr_maps, border_w = _subpixel_loss_args(srs, hrs, hr_maps, metric, border_w)
+    P, levels = mncc_int("points_per_dim", points_per_dim, MNCC_POINTS), mncc_int("levels", levels, MNCC_LEVELS)
+    B, H, W = srs.shape
+    out = torch.empty((B,), dtype=torch.float32, device=srs.device)
+    stats = torch.empty((B, SUBPIXEL_STATS), dtype=torch.float64, device=srs.device)
+    trace = torch.empty((B, levels, 3), dtype=torch.float32, device=srs.device)
+    with torch.cuda.device(srs.device):
+        _check(lib.hrn_subpixel_loss_train(_ptr(srs), _ptr(hrs), _ptr(hr_maps), B, H, W, border_w, P, levels, float(radius), _METRICS[metric],
+                                           _ptr(out), _ptr(stats), _ptr(trace), *_subpixel_workspace(B, H, W, P, srs.device), _stream()),
+               "hrn_subpixel_loss_train")
+    return out, stats, trace
+
+
+def subpixel_loss_backward(srs, hrs, hr_maps, stats, d_out, metric="cPSNR", border_w=3):
+    """d_out (B,) -> d_srs (B,H,W): the sampler's adjoint, at the point `stats` holds, of the residual's gradient; every element written,
+    exactly zero where no counted pixel's footprint reaches."""
+    lib = load_library()
+    srs, hrs, hr_maps, border_w = _subpixel_loss_args(srs, hrs, hr_maps, metric, border_w)
+    d_out = _dev_f32(d_out, "d_out")
+    B, H, W = srs.shape
+    if tuple(stats.shape) != (B, SUBPIXEL_STATS) or stats.dtype != torch.float64 or tuple(d_out.shape) != (B,):
+        raise ValueError(f"stats must be ({B}, {SUBPIXEL_STATS}) float64 and d_out ({B},); got {tuple(stats.shape)} {stats.dtype}, "
+                         f"{tuple(d_out.shape)}")
+    d_srs = torch.empty_like(srs)
+    with torch.cuda.device(srs.device):
+        _check(lib.hrn_subpixel_loss_backward(_ptr(srs), _ptr(hrs), _ptr(hr_maps), _ptr(stats.contiguous()), _ptr(d_out), B, H, W, border_w,
+                                              _METRICS[metric], _ptr(d_srs), *_subpixel_workspace(B, H, W, MNCC_POINTS[0], srs.device),
+                                              _stream()), "hrn_subpixel_loss_backward")
     return d_srs
 
 
@@ -2041,6 +2100,48 @@ def _(srs, hrs, hr_maps, stats, d_out, border_w, clip, eps):
 
 
 _register_searched_loss(_op_cl1_loss_train, "cl1_loss_backward", 3)
+
+
+# The sub-pixel searched cMSE / cPSNR: the gradient through the sampler at the point the search found, which is held fixed.
+@torch.library.custom_op("hrnet_hip::subpixel_loss_train", mutates_args=(), device_types="cuda")
+def _op_subpixel_loss_train(srs: torch.Tensor, hrs: torch.Tensor, hr_maps: torch.Tensor, metric: str, border_w: int, points_per_dim: int,
+                            levels: int, radius: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The sub-pixel searched loss: (loss per sample (B,), stats (B,8) f64 = {n*, b*, cMSE*, dy*, dx*, mean sr, mean hr, centred bias},
+    trace (B,levels,3) f32)."""
+    return subpixel_loss_train(srs, hrs, hr_maps, metric, border_w, points_per_dim, levels, radius)
+
+
+@_op_subpixel_loss_train.register_fake
+def _(srs, hrs, hr_maps, metric, border_w, points_per_dim, levels, radius):
+    B = srs.shape[0]
+    return (srs.new_empty((B,), dtype=torch.float32), srs.new_empty((B, SUBPIXEL_STATS), dtype=torch.float64),
+            srs.new_empty((B, levels, 3), dtype=torch.float32))
+
+
+@torch.library.custom_op("hrnet_hip::subpixel_loss_backward", mutates_args=(), device_types="cuda")
+def _op_subpixel_loss_backward(srs: torch.Tensor, hrs: torch.Tensor, hr_maps: torch.Tensor, stats: torch.Tensor, d_out: torch.Tensor,
+                               metric: str, border_w: int) -> torch.Tensor:
+    return subpixel_loss_backward(srs, hrs, hr_maps, stats, d_out.contiguous(), metric, border_w)
+
+
+@_op_subpixel_loss_backward.register_fake
+def _(srs, hrs, hr_maps, stats, d_out, metric, border_w):
+    return srs.new_empty(srs.shape, dtype=torch.float32)
+
+
+def _subpixel_setup(ctx, inputs, output):
+    ctx.metric, ctx.border_w = inputs[3], inputs[4]
+    ctx.save_for_backward(*inputs[:3], output[1])
+    ctx.set_materialize_grads(False)
+
+
+def _subpixel_backward(ctx, d_out, _d_stats, _d_trace):
+    if d_out is None or not ctx.needs_input_grad[0]:      # stats and trace carry no gradient; no launch unless srs needs one
+        return (None,) * 8
+    return (torch.ops.hrnet_hip.subpixel_loss_backward(*ctx.saved_tensors, d_out, ctx.metric, ctx.border_w),) + (None,) * 7
+
+
+_op_subpixel_loss_train.register_autograd(_subpixel_backward, setup_context=_subpixel_setup)
 
 
 # The registration search has no autograd formula: a shift found by a grid search is piecewise constant in the frames.

@@ -666,6 +666,43 @@ int hrn_mncc_apply_backward(const float* views, const float* shifts, const float
     return hrn_launch_mncc_apply_backward(views, shifts, valid, d_out, B, V, H, W, d_views, d_shifts, workspace, (hipStream_t)stream);
 }
 
+// the sub-pixel searched cMSE / cPSNR loss (subpixel_loss.hip): the scene search's limits and the searched losses' border
+static int subpixel_loss_check(const char* who, int B, int H, int W, int border, int metric) {
+    if (int rc = mncc_scene_check(who, B, 1, H, W)) return rc;
+    MNCC_LIMIT(border >= 0 && border <= 8, "%s: border %d outside 0..8", who, border);
+    MNCC_LIMIT(2 * border < H && 2 * border < W, "%s: bad shape H=%d W=%d border=%d: the border must be below half of each side", who, H, W,
+               border);
+    MNCC_LIMIT(metric == 1 || metric == 2, "%s: metric must be 1 (cMSE) or 2 (cPSNR)", who);
+    return 0;
+}
+
+size_t hrn_subpixel_loss_workspace_bytes(int B, int H, int W, int P) {
+    if (mncc_scene_check(nullptr, B, 1, H, W) || mncc_check_points(nullptr, P)) return 0;
+    const size_t fwd = hrn_subpixel_loss_forward_bytes_impl(B, H, W, P), bwd = hrn_subpixel_loss_backward_bytes_impl(B, H, W);
+    return fwd > bwd ? fwd : bwd;
+}
+
+int hrn_subpixel_loss_train(const float* srs, const float* hrs, const float* maps, int B, int H, int W, int border, int P, int levels,
+                            float radius, int metric, float* out, double* stats, float* trace, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    const char* who = "hrn_subpixel_loss_train";
+    if (int rc = subpixel_loss_check(who, B, H, W, border, metric)) return rc;
+    if (int rc = mncc_check_search(who, P, levels, radius)) return rc;
+    HRN_CHECK(srs && hrs && maps && out && stats && workspace, -2, "%s: null argument", who);
+    HRN_CHECK(workspace_bytes >= hrn_subpixel_loss_workspace_bytes(B, H, W, P), -3, "%s: workspace too small", who);
+    return hrn_launch_subpixel_loss_train(srs, hrs, maps, B, H, W, border, P, levels, radius, metric, out, stats, trace, workspace,
+                                          (hipStream_t)stream);
+}
+
+int hrn_subpixel_loss_backward(const float* srs, const float* hrs, const float* maps, const double* stats, const float* d_out, int B, int H,
+                               int W, int border, int metric, float* d_srs, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "hrn_subpixel_loss_backward";
+    if (int rc = subpixel_loss_check(who, B, H, W, border, metric)) return rc;
+    HRN_CHECK(srs && hrs && maps && stats && d_out && d_srs && workspace, -2, "%s: null argument", who);
+    HRN_CHECK(workspace_bytes >= hrn_subpixel_loss_backward_bytes_impl(B, H, W), -3, "%s: workspace too small", who);
+    return hrn_launch_subpixel_loss_backward(srs, hrs, maps, stats, d_out, B, H, W, border, metric, d_srs, workspace, (hipStream_t)stream);
+}
+
 // a shift per block of tiles and the resampling by the field between them (registration_local.hip)
 static int mncc_check_block(const char* who, int block) {
     MNCC_LIMIT(block >= HRN_MNCC_LOCAL_MIN_BLOCK && block <= HRN_MNCC_LOCAL_MAX_BLOCK && block % HRN_MNCC_SCENE_TILE == 0,

@@ -120,6 +120,18 @@ size_t hrn_mncc_apply_backward_workspace_bytes_impl(int B, int V, int H, int W);
 int hrn_launch_mncc_apply_backward(const float* views, const float* shifts, const float* valid, const float* d_out, int B, int V, int H,
                                    int W, float* d_views, float* d_shifts, void* workspace, hipStream_t stream);
 
+// ---- subpixel_loss.hip: the sub-pixel searched cMSE / cPSNR loss (the definition is in include/hrnet_hip.h): the
+// scene path's grid search scored by the brightness-corrected cMSE of S(sr, s) against hr, and the gradient through the sampler at the
+// point found.  out [B], stats [B][8] = {n*, b*, cMSE*, dy*, dx*, mean sr, mean hr under m0, centred bias}, trace [B][levels][3] or null.
+// The two workspaces are apart: the forward's m0 and scene plan, the backward's g, c and fp32 shifts.  The callers have checked the
+// arguments.
+size_t hrn_subpixel_loss_forward_bytes_impl(int B, int H, int W, int P);
+size_t hrn_subpixel_loss_backward_bytes_impl(int B, int H, int W);
+int hrn_launch_subpixel_loss_train(const float* srs, const float* hrs, const float* maps, int B, int H, int W, int border, int P, int levels,
+                                   float radius, int metric, float* out, double* stats, float* trace, void* workspace, hipStream_t stream);
+int hrn_launch_subpixel_loss_backward(const float* srs, const float* hrs, const float* maps, const double* stats, const float* d_out, int B,
+                                      int H, int W, int border, int metric, float* d_srs, void* workspace, hipStream_t stream);
+
 // ---- registration_local.hip: a shift per block of tiles of every view, and the views resampled by the field between the blocks'
 // centres.  block: a multiple of 64 in 64..4096; hrn_mncc_local_blocks_impl: the blocks of an axis.
 constexpr int HRN_MNCC_LOCAL_MIN_BLOCK = 64, HRN_MNCC_LOCAL_MAX_BLOCK = 4096;

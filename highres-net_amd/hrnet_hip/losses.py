@@ -23,7 +23,12 @@ differentiable through the selected offset with the brightness bias attached (`t
 `cl1_loss(srs, hrs, hr_maps, border_w, clip, eps)` is the third searched loss: the brightness-corrected L1 (cMAE, eps = 0) or Charbonnier
 sqrt(e^2 + eps^2) over the same offsets, the map a weight as in `shift_loss`, to be minimised as it is and differentiable through the
 selected offset with the brightness bias attached (`torch.ops.hrnet_hip.cl1_loss_train` / `.cl1_loss_backward` over `hrn_cl1_loss_train`
-/ `hrn_cl1_loss_backward`)."""
+/ `hrn_cl1_loss_backward`).
+
+`subpixel_loss(srs, hrs, hr_maps, metric, border_w, points_per_dim, levels, radius)` is `shift_loss`'s cMSE / cPSNR with the prediction
+registered to its target at a sub-pixel shift: the scene path's grid search scored by the cMSE itself, differentiable through the six-tap
+sampler at the point found (`torch.ops.hrnet_hip.subpixel_loss_train` / `.subpixel_loss_backward` over `hrn_subpixel_loss_train` /
+`hrn_subpixel_loss_backward`)."""
 import torch
 
 from . import binding
@@ -153,3 +158,41 @@ def cl1_loss(srs, hrs, hr_maps, border_w=3, clip=False, eps=0.0, return_shift=Fa
     else:
         out, stats = binding.cl1_loss_train(srs.detach(), hrs, hr_maps, border_w, clip, eps)
     return (out, _shift_of(stats, border_w)) if return_shift else out
+
+
+def subpixel_loss(srs, hrs, hr_maps, metric="cPSNR", border_w=3, points_per_dim=7, levels=4, radius=3.0, return_shift=False,
+                  return_trace=False):
+    """(B,H,W) x 3 -> (B,): the brightness-corrected cMSE of the prediction registered to its target at a SUB-PIXEL shift, as 'cMSE' or
+    'cPSNR' (= -10 log10 cMSE, the reference's sign: negate to minimise).  The shift s* = (dy, dx) is found on device by `levels` grids of
+    points_per_dim^2 points, the first of width 2 radius around (0, 0), each around the best point of the one before - the search of
+    `registration.mncc_search_scene`, scored by the cMSE of S(srs, s) against `hrs` over the clear pixels (hr_maps != 0, binary) at
+    least border_w from every edge whose six-tap footprint lies inside the frame.  Frames of 16..16384 pixels a
+    side, border_w 0..8 and below half of each side, points_per_dim 3..9, levels 1..16, radius in (0, 4]; there is no `clip`.  A
+    (B,1,H,W) `srs` is taken as srs[:, 0].  With grad enabled and a gradient-requiring `srs` the result is differentiable through the
+    sampler at s*, which is held fixed (no gradient to hrs / hr_maps or to the shift); without either the same forward runs and returns
+    the same bits - the sub-pixel score diagnostic.  NaN, with a zero gradient, for a sample without a counted pixel.
+    return_shift: also the (B,2) float32 s*.  S(srs, s)(p) = srs(p + s), so s* is the NEGATIVE of the (row, column) offset `shift_loss`
+    selects, which pairs srs(p) with hrs(p + offset): for a whole-pixel misregistration within both reaches, round(s*) = -offset.
+    return_trace: also the (B,levels,3) float32 (dy, dx, cMSE) of every level's point."""
+    if metric not in ("cMSE", "cPSNR"):
+        raise ValueError(f"metric must be 'cMSE' or 'cPSNR'; got {metric!r}")
+    P = binding.mncc_int("points_per_dim", points_per_dim, binding.MNCC_POINTS)
+    levels, radius = binding.mncc_int("levels", levels, binding.MNCC_LEVELS), float(radius)
+    if not 0.0 < radius <= binding.MNCC_MAX_RADIUS:
+        raise ValueError(f"radius must be in (0, {binding.MNCC_MAX_RADIUS:g}]; got {radius}")
+    lo, hi = binding.MNCC_SCENE_SIDES
+    if torch.is_tensor(srs) and srs.dim() >= 2 and not (lo <= min(srs.shape[-2:]) and max(srs.shape[-2:]) <= hi):
+        raise ValueError(f"the sides of a frame must be {lo}..{hi}; got {tuple(srs.shape[-2:])}")
+    srs, border_w = _searched_inputs(srs, hrs, hr_maps, border_w, "loss")
+    srs = srs if srs.dtype == torch.float32 else srs.float()
+    if torch.is_grad_enabled() and srs.requires_grad:
+        out, stats, trace = torch.ops.hrnet_hip.subpixel_loss_train(srs.contiguous(), hrs.float().contiguous(), hr_maps.float().contiguous(),
+                                                                    metric, border_w, P, levels, radius)
+    else:
+        out, stats, trace = binding.subpixel_loss_train(srs.detach(), hrs, hr_maps, metric, border_w, P, levels, radius)
+    res = [out]
+    if return_shift:
+        res.append(stats[:, 3:5].detach().float())
+    if return_trace:
+        res.append(trace.detach())
+    return res[0] if len(res) == 1 else tuple(res)

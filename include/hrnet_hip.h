@@ -517,6 +517,45 @@ int hrn_mncc_apply_scene(const float* views, const float* view_masks, const floa
 size_t hrn_mncc_apply_backward_workspace_bytes(int B, int V, int H, int W);
 int hrn_mncc_apply_backward(const float* views, const float* shifts, const float* valid, const float* d_out, int B, int V, int H, int W,
                             float* d_views, float* d_shifts, void* workspace, size_t workspace_bytes, void* stream);
+/* The sub-pixel searched loss: the brightness-corrected cMSE / cPSNR of the prediction REGISTERED to its target by
+ * the search above, scored by the cMSE itself instead of the NCC (which is invariant to gain and so is not the score);
+ * tests/subpixel_ref.py restates it in fp64.  srs / hrs / hr_maps (B,H,W) f32, 16 <= H, W <= 16384, border 0..8 and below half of each
+ * side.  A shift s = (dy, dx) means S(sr, s)(p) = sr(p + s), S the six-tap sampler above.  For one sample:
+ *   m0        hr_map != 0 (the map is binary here, as in cSSIM) and p at least `border` from every frame edge.
+ *   c(s)      m0 and the 6 x 6 footprint of p at s inside the frame; the prediction has no mask of its own.  n(s) = |c|.
+ *   b(s)      the mean over c of hr - S(sr, s).
+ *   cMSE(s)   the mean over c of (S(sr, s) + b - hr)^2, clamped at 0.  It is formed in fp64 from the level's six sums n, sum t, sum r,
+ *             sum t^2, sum r^2, sum r t over c, t = S(sr - mean sr, s) and r = hr - mean hr (whole-frame means, of hr under m0, rounded to
+ *             fp32 as above), as (sum t^2 + sum r^2 - 2 sum r t - (sum t - sum r)^2 / n) / n: a constant taken off either image cancels.
+ *   search    `levels` grids of P x P points as above (grid, search: the first centre (0, 0), w_0 = 2 radius, the ratio rule, fp32
+ *             coordinates), the best point the first maximum of -cMSE in row-major order (strict >, compared in fp64), -inf where n = 0;
+ *             a NaN is never taken; without a point the centre stays.
+ *   result    cMSE (metric 1) or cPSNR = -10 log10 cMSE (metric 2, the reference's sign: negate to minimise) at the last level's point
+ *             s*.  A sample whose last level has no counted pixel at any point - as one without a clear pixel inside the border frame -
+ *             gives NaN.
+ * hrn_subpixel_loss_train     <-  out (B) f32, stats (B,8) f64 = {n*, b* in image units, cMSE*, dy*, dx*, mean sr, mean hr under m0, the
+ *                                 centred bias (sum r - sum t) / n*} ({0, 0, NaN, cy, cx, means, 0} for a NaN sample), trace (B,levels,3)
+ *                                 f32 = (dy, dx, cMSE) of every level's point, or NULL.  2 + 2 levels launches; nothing returns to the
+ *                                 host, no atomics, fixed-order fp64 sums: bit-reproducible, and a sample's result does not depend on the
+ *                                 batch around it.
+ * hrn_subpixel_loss_backward  <-  autograd through that loss with s* held fixed; the bias term cancels for a square, so with e = S(sr, s*)
+ *                                 + b* - hr (formed as t + centred bias - r in fp64, t and r by the forward's operations on the means of
+ *                                 `stats`): g = d_out[b] factor 2 c e / n*, factor 1 for cMSE and -10 / (ln 10 cMSE*) for cPSNR, and d_srs
+ *                                 (B,H,W) = the sampler's adjoint of g (d_views above).  Every element is written; exactly 0 where no
+ *                                 counted pixel's footprint reaches, and everywhere for a NaN sample.  No gradient to hrs / hr_maps or to
+ *                                 the shift.  Two launches.
+ * hrn_subpixel_loss_workspace_bytes  one size for both entry points, 0 for arguments they refuse: the larger of the forward's (m0 and
+ *                                 hrn_mncc_scene_workspace_bytes(B, 1, H, W, P)) and the backward's (g, c and the fp32 shifts: 8 B H W +
+ *                                 8 B, each plane rounded up to 16 bytes).  The backward takes any P's size.
+ * -2 before any launch, with hrn_last_error() naming the fault: a null pointer other than `trace`, B not positive, a side outside
+ * 16..16384, border outside 0..8 or not below half of each side, P outside 3..9, levels outside 1..16, radius outside (0, 4], a metric
+ * other than 1 or 2, B T beyond 2^31 - 1 workgroups; -3 for a workspace that is too small.  `clip` is not offered. */
+size_t hrn_subpixel_loss_workspace_bytes(int B, int H, int W, int P);
+int hrn_subpixel_loss_train(const float* srs, const float* hrs, const float* hr_maps, int B, int H, int W, int border, int P, int levels,
+                            float radius, int metric, float* out, double* stats, float* trace, void* workspace, size_t workspace_bytes,
+                            void* stream);
+int hrn_subpixel_loss_backward(const float* srs, const float* hrs, const float* hr_maps, const double* stats, const float* d_out, int B,
+                               int H, int W, int border, int metric, float* d_srs, void* workspace, size_t workspace_bytes, void* stream);
 /* A shift per block of every view - a shift field - on the scene path's tiles.  `block` is a multiple of 64 in
  * 64..4096.  An axis of length L has n = max(1, (L + block / 2) / block) blocks; block i covers [i block, (i + 1) block) and the last one
  * runs to L, so a remainder below half a block joins its neighbour and every block is a union of whole 64-pixel tiles.

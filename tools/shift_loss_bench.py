@@ -15,6 +15,16 @@ and, in a window of their own in every round, cl1_fwd / cl1_bwd at eps = 1e-3 (C
 and `torch_cl1` / `torch_cl1_charbonnier`: the same definition's forward composed in torch on the device, one offset at a time in fp32
 (what a user writes without the kernel), a pair of device events around each of --torch-reps calls.
 
+In windows of their own in every round, the sub-pixel searched loss (P = 7, 4 levels, radius 3) on the same inputs:
+
+    subpixel_fwd       hrn_subpixel_loss_train     m0, the means, four levels of the scene search's level body and the cMSE finish
+    subpixel_bwd       hrn_subpixel_loss_backward  the residual's tile kernel and the sampler's adjoint
+    mncc_search_scene  hrn_mncc_search_scene       the masked-NCC search with the same P and levels on the same pixels (V = 1)
+
+and `subpixel_step` / `composed_step`: a forward and a backward of `losses.subpixel_loss` beside the composition it replaces
+(`mncc_search_scene`, `warp`, the masked brightness-corrected MSE in torch, autograd), a pair of device events around each of --torch-reps
+calls of either, alternating.
+
 Each call's time is the pair of device events the library's profiler (hrn_profile_enable) puts around its launches, so the Python
 between two calls is not in it.  The calls walk over enough input sets to exceed the 256 MB last-level cache, so the bytes come from
 HBM.  A round is `reps` calls of each; the figure is the median over the rounds, with min and max as the run-to-run spread.  The byte
@@ -31,6 +41,8 @@ from hrnet_hip import binding
 
 FAMILIES = ("shift_loss_fwd", "shift_loss_bwd", "shift_cpsnr", "cl1_fwd", "cl1_bwd")
 CL1 = ("cl1_fwd", "cl1_bwd")
+SUBPIXEL = ("subpixel_fwd", "subpixel_bwd", "mncc_search_scene")
+SUBPIXEL_SEARCH = dict(points_per_dim=7, levels=4, radius=3.0)
 CHARBONNIER_EPS = 1e-3
 
 
@@ -56,6 +68,63 @@ def torch_cl1(srs, hrs, maps, border, eps):
             rho = e.abs() if eps == 0 else torch.sqrt(e * e + eps * eps)
             values.append(torch.where(n > 0, (m * rho).sum((1, 2)) / n, torch.full_like(n, float("inf"))))
     return torch.stack(values, 1).min(1).values
+
+
+def composed_loss(srs, hrs, maps, border):
+    """(B,) fp32: -cPSNR of srs registered to hrs, as INTEGRATION.md composed it before hrnet_hip.losses.subpixel_loss: the masked-NCC
+    search, `warp`, the brightness-corrected masked MSE in torch; autograd reaches srs through warp"""
+    from hrnet_hip import registration
+    crop = torch.zeros_like(maps)
+    crop[:, border:maps.shape[1] - border, border:maps.shape[2] - border] = 1.0
+    m0 = (maps != 0).float() * crop
+    shifts = registration.mncc_search_scene(srs.detach()[:, None], None, ref=hrs, ref_mask=m0, **SUBPIXEL_SEARCH)[:, 0]
+    warped, valid = registration.warp(srs, shifts)
+    m = m0 * valid
+    n = m.sum((1, 2))
+    b = ((m * (hrs - warped)).sum((1, 2)) / n).detach()
+    return 10.0 * torch.log10((m * (warped + b[:, None, None] - hrs) ** 2).sum((1, 2)) / n)
+
+
+def bench_subpixel(sets, border, rounds, reps, torch_reps):
+    """-> {name: [microseconds per call, one per round]} of SUBPIXEL and of the two training tails"""
+    from hrnet_hip import losses
+    nsets = len(sets)
+    B = sets[0][0].shape[0]
+    d_out = torch.full((B,), -1.0 / B, device=sets[0][0].device)
+    P, levels, radius = SUBPIXEL_SEARCH["points_per_dim"], SUBPIXEL_SEARCH["levels"], SUBPIXEL_SEARCH["radius"]
+
+    def kernels(i):
+        s, h, m = sets[i % nsets]
+        out, stats, _ = binding.subpixel_loss_train(s, h, m, "cPSNR", border, P, levels, radius)
+        binding.subpixel_loss_backward(s, h, m, stats, d_out, "cPSNR", border)
+        binding.mncc_search_scene(h, m, s[:, None], None, P, levels, radius)
+
+    def step(fn, i):
+        s, h, m = sets[i % nsets]
+        x = s.detach().requires_grad_(True)
+        fn(x, h, m).mean().backward()
+
+    tails = {"subpixel_step": lambda x, h, m: -losses.subpixel_loss(x, h, m, "cPSNR", border, **SUBPIXEL_SEARCH),
+             "composed_step": lambda x, h, m: composed_loss(x, h, m, border)}
+    for i in range(2):
+        kernels(i)
+        for fn in tails.values():
+            step(fn, i)
+    torch.cuda.synchronize()
+    per_round = {f: [] for f in SUBPIXEL + tuple(tails)}
+    for r in range(rounds):
+        binding.profile_enable(True)
+        for i in range(reps):
+            kernels(r * reps + i)
+        torch.cuda.synchronize()
+        rec = binding.profile_read()
+        binding.profile_enable(False)
+        for f in SUBPIXEL:
+            per_round[f].append(rec[f]["ms"] * 1e3 / rec[f]["launches"])
+        for name, fn in tails.items():
+            spent = [_common.timed_us(lambda: step(fn, r * torch_reps + i), 1) for i in range(torch_reps)]
+            per_round[name].append(sum(spent) / len(spent))
+    return per_round
 
 
 def bench(B, S, border, rounds, reps, torch_reps=2):
@@ -113,6 +182,7 @@ def bench(B, S, border, rounds, reps, torch_reps=2):
         for name, eps in (("torch_cl1", 0.0), ("torch_cl1_charbonnier", CHARBONNIER_EPS)):
             spent = [_common.timed_us(lambda: torch_cl1(*sets[(r * torch_reps + i) % nsets], border, eps), 1) for i in range(torch_reps)]
             per_round[name].append(sum(spent) / len(spent))
+    subpixel = bench_subpixel(sets, border, rounds, reps, torch_reps)
     fwd_floor, bwd_floor = floors_us(B, S)
     res = {"B": B, "S": S, "border": border, "input_sets": nsets, "rounds": rounds, "reps": reps, "torch_reps": torch_reps,
            "fwd_vs_shift_cpsnr_rel": worst, "cl1_fwd_vs_torch_rel": cl1_worst, "fwd_floor_us": fwd_floor, "bwd_floor_us": bwd_floor,
@@ -135,6 +205,14 @@ def bench(B, S, border, rounds, reps, torch_reps=2):
         res["torch_cl1" + tag + "_over_cl1_fwd"] = res["torch_cl1" + tag]["median_us"] / fwd
         print(f"    hrn_cl1_loss_train{' (eps 1e-3)' if tag else ''} / hrn_shift_loss_train: {res['cl1_fwd' + tag + '_over_shift_loss_fwd']:.2f} x;  "
               f"torch composition / hrn_cl1_loss_train: {res['torch_cl1' + tag + '_over_cl1_fwd']:.1f} x")
+    for f, values in subpixel.items():
+        med, lo, hi = _common.spread(values)
+        res[f] = {"median_us": med, "min_us": lo, "max_us": hi}
+        print(f"    {f:22s} {med:9.1f} us   (min {lo:.1f}, max {hi:.1f})")
+    res["subpixel_fwd_over_mncc_search_scene"] = res["subpixel_fwd"]["median_us"] / res["mncc_search_scene"]["median_us"]
+    res["composed_step_over_subpixel_step"] = res["composed_step"]["median_us"] / res["subpixel_step"]["median_us"]
+    print(f"    hrn_subpixel_loss_train / hrn_mncc_search_scene: {res['subpixel_fwd_over_mncc_search_scene']:.2f} x;  "
+          f"composed forward + backward / subpixel_loss forward + backward: {res['composed_step_over_subpixel_step']:.2f} x")
     return res
 
 

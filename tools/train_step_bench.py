@@ -18,7 +18,9 @@ initialised for K != 3, on the seeded x3 encoder and fusion block) and K S x K S
 --loss picks the tail of the step: shiftnet (default) is the reference's ShiftNet -> Lanczos -> cPSNR above; shift is the searched loss,
 loss = -shift_loss(srs, hrs, hr_maps) (hrnet_hip.losses): no ShiftNet is built, the optimiser holds HRNet's parameters
 only, and the 128-pixel window does not apply; cssim is the second score as a loss, loss = mean(cssim_loss(srs, hrs, hr_maps)) (DESIGN.md
-section 7l), HRNet alone as for shift; l1 is the searched L1, loss = mean(cl1_loss(srs, hrs, hr_maps)), likewise.  Several values alternate in one process like the precisions.
+section 7l), HRNet alone as for shift; l1 is the searched L1, loss = mean(cl1_loss(srs, hrs, hr_maps)) (DESIGN.md section 7m), likewise;
+subpixel is the cPSNR registered at a sub-pixel shift, loss = -subpixel_loss(srs, hrs, hr_maps), likewise.  Several
+values alternate in one process like the precisions.
 """
 import copy
 import time
@@ -30,7 +32,7 @@ import torch
 from oracle import synth, weights            # seeded weights / synthetic inputs only (no oracle arithmetic on the path)
 from DeepNetworks.HRNet import HRNet
 from DeepNetworks.ShiftNet import ShiftNet
-from hrnet_hip.losses import cl1_loss, cssim_loss, shift_loss
+from hrnet_hip.losses import cl1_loss, cssim_loss, shift_loss, subpixel_loss
 from hrnet_hip.optim import FusedAdam
 
 
@@ -59,7 +61,8 @@ def _label(key):
             + (f" loss={ls}" if ls != "shiftnet" else ""))
 
 
-SEARCHED = {"shift": lambda srs, hrs, maps: -shift_loss(srs, hrs, maps), "cssim": cssim_loss, "l1": cl1_loss}       # --loss -> the loss per sample
+SEARCHED = {"shift": lambda srs, hrs, maps: -shift_loss(srs, hrs, maps), "cssim": cssim_loss, "l1": cl1_loss,
+            "subpixel": lambda srs, hrs, maps: -subpixel_loss(srs, hrs, maps)}                                       # --loss -> the loss per sample
 
 PARSER = _common.parser(__doc__, group=("B V S steps", (32, 32, 64, 5)), torch_adam=False, precision=[None], shiftnet_precision=[None], repeats=1,
                         freeze=["none"], scale=3, loss=["shiftnet"])      # scale: decoder stride and HR / LR ratio of the targets
@@ -68,7 +71,7 @@ PARSER = _common.parser(__doc__, group=("B V S steps", (32, 32, 64, 5)), torch_a
 def options(argv=None):
     o = PARSER.parse_args(argv)
     for flag, got, allowed in (("--freeze", o.freeze, tuple(FREEZE)), ("--precision", o.precision, (None, "fp32", "bf16x3", "bf16")),
-                               ("--shiftnet-precision", o.shiftnet_precision, (None, "fp32", "bf16")), ("--loss", o.loss, ("shiftnet", "shift", "cssim", "l1"))):
+                               ("--shiftnet-precision", o.shiftnet_precision, (None, "fp32", "bf16")), ("--loss", o.loss, ("shiftnet", "shift", "cssim", "l1", "subpixel"))):
         for v in got:
             if v not in allowed:
                 PARSER.error(f"{flag}: {', '.join(a for a in allowed if a)} (got {v!r})")
