@@ -40,16 +40,29 @@ Reference frame (`forward(lrs, alphas, ref=None)`, likewise forward_ensemble and
                       that frame is the second input channel of every view instead, e.g. the cloud-free composite of
                       hrnet_hip.composite.masked_composite.  It is data: in training it gets a gradient of its own when it requires one,
                       and nothing flows from it into lrs.  With ref equal to the median every result is bit-identical to ref=None.
+
+Global residual (`HRNet.global_residual`, or key "global_residual" in the config dict; default None):
+    None / False      off: every path is the code path it always was
+    True              every forward returns net(...) + up(frame) at the model's scale: the network predicts the difference to the
+                      bicubic upsample (hrnet_hip/upsample.py, a = -0.75) of `ref` when one is given, else of its own median of
+                      lrs[:, :9] (bit for bit, taken as data).  One fused in-place hrn_upsample on the output, in fp32 in every
+                      `precision`: after the inference kernels in `forward`, once after the mean in `forward_ensemble`, once on the
+                      whole scene after the last scatter in `forward_tiled`.  In training the differentiable op sits around the
+                      training op's output: parameter gradients are unchanged, a `ref` that requires grad receives the stem's d_ref
+                      plus the adjoint of d_sr; ref=None with lrs.requires_grad raises (pass ref= explicitly).  No new parameters:
+                      the state_dict is unchanged, a checkpoint trained with the flag needs the flag, and zeroing decode.final
+                      starts such a model exactly at the bicubic baseline.
 """
 import os
 
 import torch
 import torch.nn as nn
 
-from hrnet_hip import augment, binding, tiling
+from hrnet_hip import augment, binding, composite, tiling
 
 _PRECISIONS = {"fp32": binding.F32, "f32": binding.F32, "float32": binding.F32, "bf16": binding.BF16, "bfloat16": binding.BF16,
                "bf16x3": binding.BF16X3}
+_RESIDUAL_A = -0.75       # the cubic of the global residual's upsampler: torch's and OpenCV's bicubic
 
 
 class _Holder(nn.Module):
@@ -171,6 +184,7 @@ class HRNet(nn.Module):
         self.train_precision = config.get("train_precision")
         self.ensemble = config.get("ensemble")
         self.tile = config.get("tile")
+        self.global_residual = config.get("global_residual")
         self._packed = {}                   # dtype -> (key, blob): the inference and the training blob do not evict each other
 
     # -- packed-parameter cache: re-packed whenever a parameter was modified (optimizer step, load_state_dict, .to())
@@ -202,7 +216,85 @@ class HRNet(nn.Module):
         dt = self._dtype()
         return self._packed_for(dt), dt
 
+    # -- the global residual (module docstring): the three public forwards are their `_plain` forms plus one fused add
+    def _residual_on(self):
+        g = self.global_residual
+        if g is None or g is False:
+            return False
+        if g is True:
+            return True
+        raise ValueError(f"global_residual must be None, False or True; got {g!r}")
+
+    def _residual_frame(self, lrs, ref):
+        """the frame the skip upsamples: `ref` when given, else the network's own median of lrs[:, :9], bit for bit, as data"""
+        if ref is not None:
+            return binding._ref_frame(ref, lrs)
+        return composite.masked_composite(lrs, n_ref=9, fill=False)[0]
+
+    def _add_residual(self, sr, lrs, ref):
+        """sr (B,1,SH,SW) -> sr + up(frame).  Without a graph: hrn_upsample in place on sr (no pass of its own over sr beyond the add).
+        With one: the differentiable op around the training op's output - d_sr passes through unchanged, a ref that requires grad
+        receives the adjoint of d_sr on top of the stem's d_ref."""
+        B, _, SH, SW = sr.shape
+        frame = self._residual_frame(lrs, ref)
+        if sr.requires_grad:                  # the training branch of forward (a ref that requires grad puts sr into a graph too)
+            return torch.ops.hrnet_hip.upsample(frame, sr.view(B, SH, SW), self._scale, _RESIDUAL_A).view(B, 1, SH, SW)
+        with torch.no_grad():
+            plane = sr.view(B, SH, SW)        # the inference outputs are dense: base and out are sr's own memory
+            binding.upsample(frame.detach(), plane, self._scale, _RESIDUAL_A, out=plane)
+        return sr
+
     def forward(self, lrs, alphas, ref=None):
+        if not self._residual_on():
+            return self._forward_plain(lrs, alphas, ref)
+        if ref is None and torch.is_grad_enabled() and torch.is_tensor(lrs) and lrs.requires_grad:
+            raise NotImplementedError(
+                "HRNet(global_residual=True) with lrs.requires_grad and ref=None: the skip's frame is the median of lrs[:, :9], taken as "
+                "data, so its share of the gradient would silently never reach lrs.  Pass ref= explicitly (e.g. "
+                "hrnet_hip.composite.masked_composite(lrs)[0], a leaf of its own when it needs a gradient).")
+        return self._add_residual(self._forward_plain(lrs, alphas, ref), lrs, ref)
+
+    def forward_ensemble(self, lrs, alphas, mode="dihedral", members_per_pass=None, ref=None):
+        """Self-ensemble at inference: (B,L,H,W), (B,L) -> (B,1,SH,SW), the mean over the K = 4 ("flip") or 8 ("dihedral") members
+        of augment.ensemble_codes(mode) of `forward(apply(lrs, code))` transformed back with the inverse code; bit for bit
+        `augment.mean_inverse(forward(member-major batch), codes)`.  Always the inference kernels of `precision`, no autograd graph.
+        One hrn_dihedral_expand launch builds the (K*B, L, H, W) member-major batch, the forward writes into slices of one
+        (K, B, 1, SH, SW) buffer, one hrn_dihedral_mean launch averages.  members_per_pass (1..K, default K): how many members one
+        forward takes, which bounds its workspace; a sample's result does not depend on its batch, so this changes no bit.
+        ref (B,H,W): the reference frame; every member receives it under the member's own transform (the same expand, as a one-view stack).
+        With `global_residual` the skip is added once, on the untransformed frame, after the mean: the filter is symmetric, so in
+        exact arithmetic this is the ensemble of the members' own skips, and the ensemble keeps its bits."""
+        sr = self._forward_ensemble_plain(lrs, alphas, mode, members_per_pass, ref)
+        return self._add_residual(sr, lrs, ref) if self._residual_on() else sr
+
+    def forward_tiled(self, lrs, alphas, tile=128, windows_per_pass=None, ensemble=None, members_per_pass=None, ref=None):
+        """Inference on a scene of any size and aspect ratio: (B,L,H,W), (B,L) -> (B,1,SH,SW), H, W >= 1, from overlapping square
+        windows of side t = min(tile, H, W) (hrnet_hip/tiling.py).  A window is responsible for its core, whose every edge is on the
+        scene's border or at least R = tiling.halo(num_layers, L) LR pixels inside the window - the network's receptive field - so
+        the result is what a whole-frame forward would give, where one exists.  Always the inference kernels of `precision`, no
+        autograd graph.
+
+        The plan's windows go through in chunks of `windows_per_pass` (default max(1, 32 // B): 32 samples per forward): one
+        hrn_tile_gather launch builds the (chunk, B, L, t, t) window-major batch, one forward takes it as chunk * B samples, one
+        hrn_tile_scatter launch puts the cores into the output.  Peak memory: the output, one chunk of windows (LR and SR) and one
+        forward's workspace; all windows are never materialised at once.  A sample's result does not depend on its batch, so the
+        chunking changes no bit.  The work grows by the plan's overhead factor n_windows * t * t / (H * W).
+
+        ensemble ("flip" / "dihedral"; None: off): every chunk of windows goes through the self-ensemble of forward_ensemble
+        (expand / forward / mean, `members_per_pass` members per forward).  For a square scene this is forward_ensemble of the whole
+        frame; for a rectangular one it DEFINES the ensemble, transposing members included: the windows are square.
+
+        A scene that is one window (H == W <= tile) goes straight to the plain forward (or forward_ensemble).
+
+        ref (B,H,W): the reference frame of the scene; every window receives its own cut of it (the same gather, as a one-view stack).
+
+        With `global_residual` the skip is added once, on the whole scene (the upsampler takes rectangular planes), after the last
+        scatter: the result stays bit-identical to the whole-frame forward wherever one exists."""
+        sr = self._forward_tiled_plain(lrs, alphas, tile, windows_per_pass, ensemble, members_per_pass, ref)
+        return self._add_residual(sr, lrs, ref) if self._residual_on() else sr
+
+    def _forward_plain(self, lrs, alphas, ref=None):
+        """forward without the global residual: the network's own output"""
         if ref is not None:
             return self._forward_ref(lrs, alphas, ref)
         if lrs.dim() != 4:
@@ -211,7 +303,7 @@ class HRNet(nn.Module):
         grad_inputs = lrs.requires_grad or alphas.requires_grad
         graph = torch.is_grad_enabled() and (grad_params or grad_inputs)
         if self.tile is not None and not graph and (lrs.shape[2] != lrs.shape[3] or lrs.shape[2] > self._tile_side(self.tile)):
-            return self.forward_tiled(lrs, alphas, self.tile, ensemble=self.ensemble)
+            return self._forward_tiled_plain(lrs, alphas, self.tile, ensemble=self.ensemble)
         if lrs.shape[2] != lrs.shape[3]:
             raise ValueError("square low-res images only: the reference reinterprets (H,W) as (W,H) in its .view() "
                              "(HRNet.py:204), which is the identity only for H == W"
@@ -245,7 +337,7 @@ class HRNet(nn.Module):
                                                                self._scale)
             return sr
         if self.ensemble is not None and augment.check_mode(self.ensemble) is not None:
-            return self.forward_ensemble(lrs, alphas, self.ensemble)
+            return self._forward_ensemble_plain(lrs, alphas, self.ensemble)
         packed, dt = self.packed_parameters()
         return torch.ops.hrnet_hip.hrnet_forward(packed, dt, self._num_layers, bool(self.fuse.alpha_residual), lrs.detach(), alphas.detach(),
                                                  self._scale)
@@ -259,7 +351,7 @@ class HRNet(nn.Module):
         grad_inputs = lrs.requires_grad or alphas.requires_grad or ref.requires_grad
         graph = torch.is_grad_enabled() and (grad_params or grad_inputs)
         if self.tile is not None and not graph and (lrs.shape[2] != lrs.shape[3] or lrs.shape[2] > self._tile_side(self.tile)):
-            return self.forward_tiled(lrs, alphas, self.tile, ensemble=self.ensemble, ref=ref)
+            return self._forward_tiled_plain(lrs, alphas, self.tile, ensemble=self.ensemble, ref=ref)
         if lrs.shape[2] != lrs.shape[3]:
             raise ValueError("square low-res images only: the reference reinterprets (H,W) as (W,H) in its .view() "
                              "(HRNet.py:204), which is the identity only for H == W"
@@ -283,19 +375,13 @@ class HRNet(nn.Module):
                                                                    self._scale)
             return sr
         if self.ensemble is not None and augment.check_mode(self.ensemble) is not None:
-            return self.forward_ensemble(lrs, alphas, self.ensemble, ref=ref)
+            return self._forward_ensemble_plain(lrs, alphas, self.ensemble, ref=ref)
         packed, dt = self.packed_parameters()
         return torch.ops.hrnet_hip.hrnet_forward_ref(packed, dt, self._num_layers, bool(self.fuse.alpha_residual), lrs.detach(),
                                                      alphas.detach(), ref.detach(), self._scale)
 
-    def forward_ensemble(self, lrs, alphas, mode="dihedral", members_per_pass=None, ref=None):
-        """Self-ensemble at inference: (B,L,H,W), (B,L) -> (B,1,SH,SW), the mean over the K = 4 ("flip") or 8 ("dihedral") members
-        of augment.ensemble_codes(mode) of `forward(apply(lrs, code))` transformed back with the inverse code; bit for bit
-        `augment.mean_inverse(forward(member-major batch), codes)`.  Always the inference kernels of `precision`, no autograd graph.
-        One hrn_dihedral_expand launch builds the (K*B, L, H, W) member-major batch, the forward writes into slices of one
-        (K, B, 1, SH, SW) buffer, one hrn_dihedral_mean launch averages.  members_per_pass (1..K, default K): how many members one
-        forward takes, which bounds its workspace; a sample's result does not depend on its batch, so this changes no bit.
-        ref (B,H,W): the reference frame; every member receives it under the member's own transform (the same expand, as a one-view stack)."""
+    def _forward_ensemble_plain(self, lrs, alphas, mode="dihedral", members_per_pass=None, ref=None):
+        """forward_ensemble without the global residual"""
         codes = augment.ensemble_codes(mode)
         K = len(codes)
         per_pass = K if members_per_pass is None else members_per_pass
@@ -331,26 +417,8 @@ class HRNet(nn.Module):
             raise ValueError(f"tile must be a positive integer, got {tile!r}")
         return tile
 
-    def forward_tiled(self, lrs, alphas, tile=128, windows_per_pass=None, ensemble=None, members_per_pass=None, ref=None):
-        """Inference on a scene of any size and aspect ratio: (B,L,H,W), (B,L) -> (B,1,SH,SW), H, W >= 1, from overlapping square
-        windows of side t = min(tile, H, W) (hrnet_hip/tiling.py).  A window is responsible for its core, whose every edge is on the
-        scene's border or at least R = tiling.halo(num_layers, L) LR pixels inside the window - the network's receptive field - so
-        the result is what a whole-frame forward would give, where one exists.  Always the inference kernels of `precision`, no
-        autograd graph.
-
-        The plan's windows go through in chunks of `windows_per_pass` (default max(1, 32 // B): 32 samples per forward): one
-        hrn_tile_gather launch builds the (chunk, B, L, t, t) window-major batch, one forward takes it as chunk * B samples, one
-        hrn_tile_scatter launch puts the cores into the output.  Peak memory: the output, one chunk of windows (LR and SR) and one
-        forward's workspace; all windows are never materialised at once.  A sample's result does not depend on its batch, so the
-        chunking changes no bit.  The work grows by the plan's overhead factor n_windows * t * t / (H * W).
-
-        ensemble ("flip" / "dihedral"; None: off): every chunk of windows goes through the self-ensemble of forward_ensemble
-        (expand / forward / mean, `members_per_pass` members per forward).  For a square scene this is forward_ensemble of the whole
-        frame; for a rectangular one it DEFINES the ensemble, transposing members included: the windows are square.
-
-        A scene that is one window (H == W <= tile) goes straight to the plain forward (or forward_ensemble).
-
-        ref (B,H,W): the reference frame of the scene; every window receives its own cut of it (the same gather, as a one-view stack)."""
+    def _forward_tiled_plain(self, lrs, alphas, tile=128, windows_per_pass=None, ensemble=None, members_per_pass=None, ref=None):
+        """forward_tiled without the global residual"""
         tile = self._tile_side(tile)
         if lrs.dim() != 4 or lrs.numel() == 0:
             raise ValueError(f"lrs must be a non-empty (B, L, H, W); got {tuple(lrs.shape)}")
@@ -371,7 +439,7 @@ class HRNet(nn.Module):
             raise ValueError(f"members_per_pass must be an integer in 1..{K}, got {members_per_pass!r}")
         if H == W and H <= tile:
             if mode is not None:
-                return self.forward_ensemble(lrs, alphas, mode, members_per_pass, ref=ref)
+                return self._forward_ensemble_plain(lrs, alphas, mode, members_per_pass, ref=ref)
             packed, dt = self.packed_parameters()
             if ref is not None:
                 return torch.ops.hrnet_hip.hrnet_forward_ref(packed, dt, self._num_layers, bool(self.fuse.alpha_residual), lrs.detach(),

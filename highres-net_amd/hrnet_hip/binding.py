@@ -105,6 +105,8 @@ SIGNATURES = {
                                           _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(HrnetParams), _c.c_void_p,
                                           _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_masked_composite": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 5 + [_c.c_void_p] * 4),
+    "hrn_upsample": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int64] + [_c.c_int] * 3 + [_c.c_float, _c.c_void_p]),
+    "hrn_upsample_backward": (_c.c_int, [_c.c_void_p] * 2 + [_c.c_int64] + [_c.c_int] * 3 + [_c.c_float, _c.c_void_p]),
     "hrn_hrnet_forward_ref": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                          _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_hrnet_forward_train_ref": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
@@ -1513,6 +1515,34 @@ def masked_composite(lrs, lr_masks=None, alphas=None, n_ref=9, want_count=False,
     return ref, filled, count
 
 
+# --------------------------------------------------------------------------- bicubic upsampling (the global residual's frame)
+UPSAMPLE_TILE = (8, 32)       # HRN_UPSAMPLE_TILE_H x HRN_UPSAMPLE_TILE_W: the LR pixels a workgroup of either kernel owns
+UPSAMPLE_MAX_SIDE = 16384     # hrn_upsample: planes of 1 .. 16384 a side
+
+
+def upsample(frames, base, scale, a, out=None):
+    """hrn_upsample on contiguous f32 device tensors (hrnet_hip/upsample.py checks them): frames (N,H,W), base (N,SH,SW) or None ->
+    out (N,SH,SW) = base + up(frames).  out: where the result goes (a new tensor when None); base may be out itself."""
+    lib = load_library()
+    N, H, W = frames.shape
+    if out is None:
+        out = torch.empty((N, scale * H, scale * W), dtype=torch.float32, device=frames.device)
+    with torch.cuda.device(frames.device):
+        _check(lib.hrn_upsample(_ptr(frames), _opt_ptr(base), _ptr(out), N, H, W, int(scale), float(a), _stream()), "hrn_upsample")
+    return out
+
+
+def upsample_backward(d_out, H, W, scale, a):
+    """hrn_upsample_backward: d_out (N,SH,SW) contiguous f32 -> d_frames (N,H,W) = the adjoint of up() applied to d_out."""
+    lib = load_library()
+    N = d_out.shape[0]
+    d_frames = torch.empty((N, H, W), dtype=torch.float32, device=d_out.device)
+    with torch.cuda.device(d_out.device):
+        _check(lib.hrn_upsample_backward(_ptr(d_out), _ptr(d_frames), N, int(H), int(W), int(scale), float(a), _stream()),
+               "hrn_upsample_backward")
+    return d_frames
+
+
 # --------------------------------------------------------------------------- PyTorch-ROCm custom ops (north_star: "exposed to Python as
 # PyTorch-ROCm custom ops"): the inference entry points are registered with the dispatcher as torch.ops.hrnet_hip.*, with fake
 # (meta) implementations, so that they are visible to torch.compile / export and to anyone calling through torch.ops.  Each is a
@@ -1557,6 +1587,46 @@ def _(lrs, lr_masks, alphas, n_ref, want_count, fill):
     b, _, h, w = lrs.shape
     return (lrs.new_empty((b, h, w), dtype=torch.float32), lrs.new_empty(lrs.shape if fill else (0,), dtype=torch.float32),
             lrs.new_empty((b, h, w) if want_count else (0,), dtype=torch.float32))
+
+
+# Bicubic upsampling with an add (upsample.hip): out = base + up(frames).  Linear in both inputs: d_frames is the adjoint kernel applied
+# to d_out (a registered op itself), d_base is d_out.
+@torch.library.custom_op("hrnet_hip::upsample", mutates_args=(), device_types="cuda")
+def _op_upsample(frames: torch.Tensor, base: Optional[torch.Tensor], scale: int, a: float) -> torch.Tensor:
+    """frames (N,H,W), base (N,scale H,scale W) or None -> base + up(frames), f32 (hrn_upsample)."""
+    return upsample(frames.float().contiguous(), None if base is None else base.float().contiguous(), scale, a)
+
+
+@_op_upsample.register_fake
+def _(frames, base, scale, a):
+    n, h, w = frames.shape
+    return frames.new_empty((n, scale * h, scale * w), dtype=torch.float32)
+
+
+@torch.library.custom_op("hrnet_hip::upsample_backward", mutates_args=(), device_types="cuda")
+def _op_upsample_backward(d_out: torch.Tensor, H: int, W: int, scale: int, a: float) -> torch.Tensor:
+    """d_out (N,scale H,scale W) -> d_frames (N,H,W), the adjoint of up() (hrn_upsample_backward)."""
+    return upsample_backward(d_out.float().contiguous(), H, W, scale, a)
+
+
+@_op_upsample_backward.register_fake
+def _(d_out, H, W, scale, a):
+    return d_out.new_empty((d_out.shape[0], H, W), dtype=torch.float32)
+
+
+def _upsample_setup(ctx, inputs, output):
+    frames, base, scale, a = inputs
+    ctx.hw, ctx.scale, ctx.a = tuple(frames.shape[1:]), scale, a
+    ctx.frames_dtype, ctx.base_dtype = frames.dtype, None if base is None else base.dtype
+
+
+def _upsample_backward(ctx, d_out):
+    need_frames, need_base = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    d_frames = torch.ops.hrnet_hip.upsample_backward(d_out, ctx.hw[0], ctx.hw[1], ctx.scale, ctx.a).to(ctx.frames_dtype) if need_frames else None
+    return d_frames, (d_out.to(ctx.base_dtype) if need_base else None), None, None
+
+
+_op_upsample.register_autograd(_upsample_backward, setup_context=_upsample_setup)
 
 
 @torch.library.custom_op("hrnet_hip::lanczos_shift", mutates_args=(), device_types="cuda")

@@ -123,6 +123,31 @@ def evaluate(fusion_model, batches, baseline_cpsnrs=None, ensemble=None, border_
                            torch.cat([q for _, q in kept]).cpu().numpy().astype(np.float64))
 
 
+def baseline_table(batches, border_w=3, a=-0.75, n_ref=9):
+    """ESA's baseline for data without ESA's table - "cPSNR of a bicubic upsample of an averaged clear frame": over `batches` of
+    (lrs, alphas, hrs, hr_maps, names) -> {name: shift_cPSNR(clip(upsample.baseline(lrs, alphas, scale=S, a=a, n_ref=n_ref), 0, 1), hr,
+    hr_map, border_w)}, scored on the device by the scorer `evaluate` uses.  S is taken from the shapes (hrs against lrs: 2, 3 or 4).  The
+    result is what `evaluate(..., baseline_cpsnrs=)` takes; `utils.writeBaselineCPSNR` stores it in the format of norm.csv."""
+    from . import upsample
+    table = {}
+    with torch.no_grad():
+        for batch in batches:
+            if len(batch) != 5:
+                raise ValueError(f"a baseline batch is (lrs, alphas, hrs, hr_maps, names); got {len(batch)} elements")
+            lrs, alphas, hrs, hr_maps, names = batch
+            names = list(names)
+            if len(names) != lrs.shape[0]:
+                raise ValueError(f"{len(names)} names for a batch of {lrs.shape[0]}")
+            S = hrs.shape[-2] // lrs.shape[-2]
+            if tuple(hrs.shape[-2:]) != (S * lrs.shape[-2], S * lrs.shape[-1]):
+                raise ValueError(f"hrs {tuple(hrs.shape)} is no integer multiple of lrs {tuple(lrs.shape)}")
+            srs = upsample.baseline(lrs, alphas, scale=S, a=a, n_ref=n_ref)[:, 0]
+            cpsnr = _default_score(srs, hrs, hr_maps, border_w).double().cpu().numpy()
+            for name, c in zip(names, cpsnr):
+                table[name] = float(c)
+    return table
+
+
 def sharded_val_score(fusion_model, batches, border_w=3, score_fn=None, device=None, baseline_cpsnrs=None, ensemble=None, tile=None,
                       metric="cPSNR"):
     """`batches`: this rank's validation batches of (lrs, alphas, hrs, hr_maps) tensors, or the same with `names` as a fifth element

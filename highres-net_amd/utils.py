@@ -27,6 +27,17 @@ def readBaselineCPSNR(path):
     return table
 
 
+def writeBaselineCPSNR(path, table):
+    """{imageset: baseline cPSNR} -> norm.csv, the format readBaselineCPSNR reads: one "<imageset> <cPSNR>" per line, in the table's
+    order; repr() of a float round-trips, so reading the file back gives the table."""
+    with open(path, "w") as fh:
+        for name, value in table.items():
+            name = str(name)
+            if not name.strip() or any(ch.isspace() for ch in name):
+                raise ValueError(f"an imageset name must be non-empty without blanks; got {name!r}")
+            fh.write(f"{name} {float(value)!r}\n")
+
+
 def getImageSetDirectories(data_dir):
     """Every imageset directory of a split: data_dir/RED/* then data_dir/NIR/*, each band in os.listdir order."""
     return [os.path.join(data_dir, band, entry) for band in _CHANNELS for entry in os.listdir(os.path.join(data_dir, band))]

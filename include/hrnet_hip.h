@@ -48,6 +48,8 @@
  *                              any size and aspect ratio, and the windows' cores put back into the scene's prediction
  *   hrn_masked_composite / hrn_hrnet_*_ref  <-  (no counterpart: the reference's frame is the plain median of lrs[:, :9], HRNet.py:200)
  *                              a cloud-free reference frame from the views and their quality masks, and HRNet given that frame
+ *   hrn_upsample / hrn_upsample_backward  <-  (no counterpart: the reference's network synthesises the whole image) bicubic x2 / x3 / x4
+ *                              interpolation of a frame with an add, and its adjoint: the global residual over an upsampled LR frame
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor's data_ptr) unless stated;
@@ -249,6 +251,34 @@ int hrn_hrnet_backward_ref(const void* packed, int dtype, int scale, const hrn_h
                            const float* alphas, const float* ref, int B, int V, int H, int W, const float* d_sr,
                            const hrn_hrnet_params* grads, float* d_lrs, float* d_alphas, float* d_ref, void* train_ws, size_t train_ws_bytes,
                            void* stream);
+
+/* ------------------------------------------------------------------ bicubic upsampling and the global residual
+ * (No counterpart in the reference, whose network synthesises the whole image; DeepSUM, RAMS and their successors predict the
+ * difference to an upsampled LR frame.  HRNet's `global_residual` adds up(frame) to the decoder's output with hrn_upsample.)
+ *
+ * hrn_upsample: frames (n_planes,H,W) f32, base (n_planes,SH,SW) f32 or NULL -> out[n] = (base ? base[n] : 0) + up(frames[n]),
+ * (n_planes,SH,SW), for an integer scale S in {2, 3, 4}.  up() is the bicubic interpolation of
+ * torch.nn.functional.interpolate(mode="bicubic", align_corners=False) with Keys' parameter a (-0.75: torch and OpenCV; -0.5: Keys and
+ * Pillow).  Output row j has the source coordinate x_j = (j + 0.5) / S - 0.5, i = floor(x_j), t = x_j - i; its four taps sit on the rows
+ * i - 1 .. i + 2, the INDICES CLAMPED to 0 .. H - 1, with the weights w2(t + 1), w1(t), w1(1 - t), w2(2 - t),
+ *     w1(x) = ((a + 2) x - (a + 3)) x^2 + 1,    w2(x) = ((a x - 5 a) x + 8 a) x - 4 a.
+ * Columns likewise; the 2-D filter is the separable product.  An axis has only S phases t: the S x 4 weights are computed on the host in
+ * fp64, rounded to fp32 and handed to the kernel by value.  Every phase's weights sum to 1.  The sum is formed in fp32 in one fixed order:
+ * the column taps first (w0 f0, then one fma per tap, taps ascending), then the row taps over those sums in the same way, then the add
+ * of base.  base may be out itself (the in-place add); frames must not overlap out.  One launch for any n_planes.
+ *
+ * hrn_upsample_backward WRITES d_frames (n_planes,H,W) = up^T(d_out), the adjoint as a gather: an LR pixel sums the output-gradient
+ * pixels whose taps reach it, a border pixel also what the clamped rows and columns beyond the edge collect (with H or W below 3 several
+ * fold onto one).  No atomics, one fixed order, bit-reproducible; a plane's result does not depend on its batch, in either function.
+ * The gradient with respect to base is d_out itself.
+ *
+ * Planes of 1 .. 16384 a side, any aspect ratio; every plane and row offset is 64-bit.  -2 before any launch for NULL frames / out /
+ * d_out / d_frames, a scale outside {2, 3, 4}, a non-finite a, non-positive sizes, a side beyond 16384, frames overlapping out, a base
+ * that overlaps out without being out, or d_frames overlapping d_out.  A workgroup owns HRN_UPSAMPLE_TILE_H x HRN_UPSAMPLE_TILE_W LR pixels. */
+#define HRN_UPSAMPLE_TILE_H 8
+#define HRN_UPSAMPLE_TILE_W 32
+int hrn_upsample(const float* frames, const float* base, float* out, int64_t n_planes, int H, int W, int scale, float a, void* stream);
+int hrn_upsample_backward(const float* d_out, float* d_frames, int64_t n_planes, int H, int W, int scale, float a, void* stream);
 
 /* ------------------------------------------------------------------ ShiftNet */
 typedef struct hrn_shiftnet_params {
