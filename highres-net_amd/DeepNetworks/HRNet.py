@@ -52,6 +52,12 @@ Global residual (`HRNet.global_residual`, or key "global_residual" in the config
                       plus the adjoint of d_sr; ref=None with lrs.requires_grad raises (pass ref= explicitly).  No new parameters:
                       the state_dict is unchanged, a checkpoint trained with the flag needs the flag, and zeroing decode.final
                       starts such a model exactly at the bicubic baseline.
+    base= (forward, forward_ensemble, forward_tiled; None by default)
+                      with the flag on, a (B,SH,SW) or (B,1,SH,SW) float tensor on the device that takes the place of up(frame): the
+                      model returns net(...) + base, the base added once, at the places the skip is added - e.g. the shift-and-add
+                      frame of hrnet_hip.shiftadd.register_and_add, a registered multi-frame base instead of a single upsampled
+                      frame.  `ref` keeps its own meaning (the stem's second channel).  In training it is a differentiable add:
+                      d_base = d_sr, parameter gradients untouched.  base= with the flag off raises; base=None is the path above.
 """
 import os
 
@@ -244,9 +250,35 @@ class HRNet(nn.Module):
             binding.upsample(frame.detach(), plane, self._scale, _RESIDUAL_A, out=plane)
         return sr
 
-    def forward(self, lrs, alphas, ref=None):
+    def _add_base(self, sr, base):
+        """sr (B,1,SH,SW) -> sr + base, base (B,SH,SW) or (B,1,SH,SW) given by the caller in up(frame)'s place.  Without a graph the add
+        is in place on sr (the inference outputs are the model's own memory); with one it is the differentiable add, d_base = d_sr."""
+        if not torch.is_tensor(base):
+            raise TypeError(f"base must be a torch.Tensor or None; got {type(base).__name__}")
+        B, _, SH, SW = sr.shape
+        if tuple(base.shape) not in ((B, SH, SW), (B, 1, SH, SW)):
+            raise ValueError(f"base must be {(B, SH, SW)} or {(B, 1, SH, SW)}; got {tuple(base.shape)}")
+        if not base.is_floating_point():
+            raise TypeError(f"base must be a floating-point tensor; got {base.dtype}")
+        if base.device != sr.device:
+            raise TypeError(f"base is on '{base.device}' but the model's output on '{sr.device}'")
+        base = base.float().view(B, 1, SH, SW)
+        if torch.is_grad_enabled() and (sr.requires_grad or base.requires_grad):
+            return sr + base
+        with torch.no_grad():
+            return sr.add_(base.detach())
+
+    def _check_base_off(self, base):
+        if base is not None:
+            raise ValueError("base= needs HRNet(global_residual=True): without the flag the model returns net(...) alone and the base "
+                             "would be dropped")
+
+    def forward(self, lrs, alphas, ref=None, base=None):
         if not self._residual_on():
+            self._check_base_off(base)
             return self._forward_plain(lrs, alphas, ref)
+        if base is not None:
+            return self._add_base(self._forward_plain(lrs, alphas, ref), base)
         if ref is None and torch.is_grad_enabled() and torch.is_tensor(lrs) and lrs.requires_grad:
             raise NotImplementedError(
                 "HRNet(global_residual=True) with lrs.requires_grad and ref=None: the skip's frame is the median of lrs[:, :9], taken as "
@@ -254,7 +286,7 @@ class HRNet(nn.Module):
                 "hrnet_hip.composite.masked_composite(lrs)[0], a leaf of its own when it needs a gradient).")
         return self._add_residual(self._forward_plain(lrs, alphas, ref), lrs, ref)
 
-    def forward_ensemble(self, lrs, alphas, mode="dihedral", members_per_pass=None, ref=None):
+    def forward_ensemble(self, lrs, alphas, mode="dihedral", members_per_pass=None, ref=None, base=None):
         """Self-ensemble at inference: (B,L,H,W), (B,L) -> (B,1,SH,SW), the mean over the K = 4 ("flip") or 8 ("dihedral") members
         of augment.ensemble_codes(mode) of `forward(apply(lrs, code))` transformed back with the inverse code; bit for bit
         `augment.mean_inverse(forward(member-major batch), codes)`.  Always the inference kernels of `precision`, no autograd graph.
@@ -263,11 +295,16 @@ class HRNet(nn.Module):
         forward takes, which bounds its workspace; a sample's result does not depend on its batch, so this changes no bit.
         ref (B,H,W): the reference frame; every member receives it under the member's own transform (the same expand, as a one-view stack).
         With `global_residual` the skip is added once, on the untransformed frame, after the mean: the filter is symmetric, so in
-        exact arithmetic this is the ensemble of the members' own skips, and the ensemble keeps its bits."""
+        exact arithmetic this is the ensemble of the members' own skips, and the ensemble keeps its bits.  base (B,SH,SW): with
+        `global_residual`, the frame added in the skip's place (module docstring), once, untransformed, after the mean."""
+        if not self._residual_on():
+            self._check_base_off(base)
         sr = self._forward_ensemble_plain(lrs, alphas, mode, members_per_pass, ref)
+        if base is not None:
+            return self._add_base(sr, base)
         return self._add_residual(sr, lrs, ref) if self._residual_on() else sr
 
-    def forward_tiled(self, lrs, alphas, tile=128, windows_per_pass=None, ensemble=None, members_per_pass=None, ref=None):
+    def forward_tiled(self, lrs, alphas, tile=128, windows_per_pass=None, ensemble=None, members_per_pass=None, ref=None, base=None):
         """Inference on a scene of any size and aspect ratio: (B,L,H,W), (B,L) -> (B,1,SH,SW), H, W >= 1, from overlapping square
         windows of side t = min(tile, H, W) (hrnet_hip/tiling.py).  A window is responsible for its core, whose every edge is on the
         scene's border or at least R = tiling.halo(num_layers, L) LR pixels inside the window - the network's receptive field - so
@@ -289,8 +326,13 @@ class HRNet(nn.Module):
         ref (B,H,W): the reference frame of the scene; every window receives its own cut of it (the same gather, as a one-view stack).
 
         With `global_residual` the skip is added once, on the whole scene (the upsampler takes rectangular planes), after the last
-        scatter: the result stays bit-identical to the whole-frame forward wherever one exists."""
+        scatter: the result stays bit-identical to the whole-frame forward wherever one exists.  base (B,SH,SW): with
+        `global_residual`, the scene-sized frame added in the skip's place (module docstring), once, after the last scatter."""
+        if not self._residual_on():
+            self._check_base_off(base)
         sr = self._forward_tiled_plain(lrs, alphas, tile, windows_per_pass, ensemble, members_per_pass, ref)
+        if base is not None:
+            return self._add_base(sr, base)
         return self._add_residual(sr, lrs, ref) if self._residual_on() else sr
 
     def _forward_plain(self, lrs, alphas, ref=None):

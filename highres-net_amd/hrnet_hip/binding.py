@@ -107,6 +107,8 @@ SIGNATURES = {
     "hrn_masked_composite": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 5 + [_c.c_void_p] * 4),
     "hrn_upsample": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int64] + [_c.c_int] * 3 + [_c.c_float, _c.c_void_p]),
     "hrn_upsample_backward": (_c.c_int, [_c.c_void_p] * 2 + [_c.c_int64] + [_c.c_int] * 3 + [_c.c_float, _c.c_void_p]),
+    "hrn_shift_add": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_int] * 5 + [_c.c_float, _c.c_float, _c.c_void_p]),
+    "hrn_shift_add_backward": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_int] * 5 + [_c.c_float, _c.c_float, _c.c_void_p]),
     "hrn_hrnet_forward_ref": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                          _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_hrnet_forward_train_ref": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
@@ -1543,6 +1545,43 @@ def upsample_backward(d_out, H, W, scale, a):
     return d_frames
 
 
+# --------------------------------------------------------------------------- shift-and-add (normalised convolution)
+SHIFT_ADD_TILE = (8, 32)      # HRN_SHIFT_ADD_TILE_H x HRN_SHIFT_ADD_TILE_W: the LR pixels a workgroup of either kernel owns
+SHIFT_ADD_MAX_SIDE = 16384    # hrn_shift_add: frames of 1 .. 16384 a side
+SHIFT_ADD_SIGMA = (0.1, 1.0)  # the range of sigma, LR pixels
+
+
+def shift_add(views, view_masks, alphas, shifts, base, scale, sigma, prior, want_weight=True, out=None):
+    """hrn_shift_add on contiguous f32 device tensors (hrnet_hip/shiftadd.py checks them): views (B,V,H,W), view_masks the same or None,
+    alphas (B,V) or None, shifts (B,V,2), base (B,SH,SW) or None -> (out (B,SH,SW), weight (B,SH,SW) or None).  out: where the result
+    goes (a new tensor when None); base may be out itself."""
+    lib = load_library()
+    B, V, H, W = views.shape
+    if out is None:
+        out = torch.empty((B, scale * H, scale * W), dtype=torch.float32, device=views.device)
+    weight = torch.empty((B, scale * H, scale * W), dtype=torch.float32, device=views.device) if want_weight else None
+    with torch.cuda.device(views.device):
+        _check(lib.hrn_shift_add(_ptr(views), _opt_ptr(view_masks), _opt_ptr(alphas), _ptr(shifts), _opt_ptr(base), _ptr(out), _opt_ptr(weight),
+                                 B, V, H, W, int(scale), float(sigma), float(prior), _stream()), "hrn_shift_add")
+    return out, weight
+
+
+def shift_add_backward(d_out, weight, view_masks, alphas, shifts, V, H, W, scale, sigma, prior, need_views=True, need_base=True):
+    """hrn_shift_add_backward: d_out, weight (B,SH,SW) contiguous f32 (weight: the forward's second result) -> (d_views (B,V,H,W) or None,
+    d_base (B,SH,SW) or None), each computed only where needed; both unneeded is an error."""
+    if not (need_views or need_base):
+        raise ValueError("shift_add_backward: neither d_views nor d_base is asked for")
+    lib = load_library()
+    B = d_out.shape[0]
+    d_views = torch.empty((B, V, H, W), dtype=torch.float32, device=d_out.device) if need_views else None
+    d_base = torch.empty_like(d_out) if need_base else None
+    with torch.cuda.device(d_out.device):
+        _check(lib.hrn_shift_add_backward(_ptr(d_out), _ptr(weight), _opt_ptr(view_masks), _opt_ptr(alphas), _ptr(shifts), _opt_ptr(d_views),
+                                          _opt_ptr(d_base), B, int(V), int(H), int(W), int(scale), float(sigma), float(prior), _stream()),
+               "hrn_shift_add_backward")
+    return d_views, d_base
+
+
 # --------------------------------------------------------------------------- PyTorch-ROCm custom ops (north_star: "exposed to Python as
 # PyTorch-ROCm custom ops"): the inference entry points are registered with the dispatcher as torch.ops.hrnet_hip.*, with fake
 # (meta) implementations, so that they are visible to torch.compile / export and to anyone calling through torch.ops.  Each is a
@@ -1627,6 +1666,71 @@ def _upsample_backward(ctx, d_out):
 
 
 _op_upsample.register_autograd(_upsample_backward, setup_context=_upsample_setup)
+
+
+# Shift-and-add (shift_add.hip): (out, weight) = hrn_shift_add.  out is linear in views and base; weight depends on masks and shifts only
+# and carries no gradient, nor do shifts, masks and alphas.  The autograd formula is hrn_shift_add_backward (a registered op itself) on
+# the saved weight.
+def _f32c(t):
+    return None if t is None else t.float().contiguous()
+
+
+@torch.library.custom_op("hrnet_hip::shift_add", mutates_args=(), device_types="cuda")
+def _op_shift_add(views: torch.Tensor, view_masks: Optional[torch.Tensor], alphas: Optional[torch.Tensor], shifts: torch.Tensor,
+                  base: Optional[torch.Tensor], scale: int, sigma: float, prior: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """views (B,V,H,W), view_masks or None, alphas (B,V) or None, shifts (B,V,2), base (B,SH,SW) or None -> (out, weight) (hrn_shift_add)."""
+    return shift_add(_f32c(views), _f32c(view_masks), _f32c(alphas), _f32c(shifts), _f32c(base), scale, sigma, prior)
+
+
+@_op_shift_add.register_fake
+def _(views, view_masks, alphas, shifts, base, scale, sigma, prior):
+    b, _, h, w = views.shape
+    return (views.new_empty((b, scale * h, scale * w), dtype=torch.float32), views.new_empty((b, scale * h, scale * w), dtype=torch.float32))
+
+
+@torch.library.custom_op("hrnet_hip::shift_add_backward", mutates_args=(), device_types="cuda")
+def _op_shift_add_backward(d_out: torch.Tensor, weight: torch.Tensor, view_masks: Optional[torch.Tensor], alphas: Optional[torch.Tensor],
+                           shifts: torch.Tensor, V: int, H: int, W: int, scale: int, sigma: float, prior: float, need_views: bool,
+                           need_base: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (d_views (B,V,H,W), d_base (B,SH,SW)) (hrn_shift_add_backward); a half that is not needed is an empty tensor and does not run."""
+    d_views, d_base = shift_add_backward(_f32c(d_out), _f32c(weight), _f32c(view_masks), _f32c(alphas), _f32c(shifts), V, H, W, scale, sigma,
+                                         prior, need_views, need_base)
+    empty = d_out.new_empty((0,), dtype=torch.float32)
+    return (empty if d_views is None else d_views), (empty.clone() if d_base is None else d_base)
+
+
+@_op_shift_add_backward.register_fake
+def _(d_out, weight, view_masks, alphas, shifts, V, H, W, scale, sigma, prior, need_views, need_base):
+    b = d_out.shape[0]
+    return (d_out.new_empty((b, V, H, W) if need_views else (0,), dtype=torch.float32),
+            d_out.new_empty(tuple(d_out.shape) if need_base else (0,), dtype=torch.float32))
+
+
+def _shift_add_setup(ctx, inputs, output):
+    views, view_masks, alphas, shifts, base, scale, sigma, prior = inputs
+    ctx.vhw, ctx.scale, ctx.sigma, ctx.prior = tuple(views.shape[1:]), scale, sigma, prior
+    ctx.views_dtype, ctx.base_dtype = views.dtype, None if base is None else base.dtype
+    ctx.has = (view_masks is not None, alphas is not None)
+    ctx.save_for_backward(output[1], shifts, *(t for t in (view_masks, alphas) if t is not None))
+
+
+def _shift_add_backward(ctx, d_out, d_weight):
+    need_views, need_base = ctx.needs_input_grad[0], ctx.needs_input_grad[4]
+    if not (need_views or need_base):
+        return (None,) * 8
+    saved = list(ctx.saved_tensors)
+    weight, shifts = saved[0], saved[1]
+    rest = saved[2:]
+    view_masks = rest.pop(0) if ctx.has[0] else None
+    alphas = rest.pop(0) if ctx.has[1] else None
+    V, H, W = ctx.vhw
+    d_views, d_base = torch.ops.hrnet_hip.shift_add_backward(d_out, weight, view_masks, alphas, shifts, V, H, W, ctx.scale, ctx.sigma,
+                                                             ctx.prior, need_views, need_base)
+    return (d_views.to(ctx.views_dtype) if need_views else None, None, None, None, d_base.to(ctx.base_dtype) if need_base else None,
+            None, None, None)
+
+
+_op_shift_add.register_autograd(_shift_add_backward, setup_context=_shift_add_setup)
 
 
 @torch.library.custom_op("hrnet_hip::lanczos_shift", mutates_args=(), device_types="cuda")

@@ -123,25 +123,38 @@ def evaluate(fusion_model, batches, baseline_cpsnrs=None, ensemble=None, border_
                            torch.cat([q for _, q in kept]).cpu().numpy().astype(np.float64))
 
 
-def baseline_table(batches, border_w=3, a=-0.75, n_ref=9):
+def baseline_table(batches, border_w=3, a=-0.75, n_ref=9, method="bicubic", **method_kwargs):
     """ESA's baseline for data without ESA's table - "cPSNR of a bicubic upsample of an averaged clear frame": over `batches` of
     (lrs, alphas, hrs, hr_maps, names) -> {name: shift_cPSNR(clip(upsample.baseline(lrs, alphas, scale=S, a=a, n_ref=n_ref), 0, 1), hr,
     hr_map, border_w)}, scored on the device by the scorer `evaluate` uses.  S is taken from the shapes (hrs against lrs: 2, 3 or 4).  The
-    result is what `evaluate(..., baseline_cpsnrs=)` takes; `utils.writeBaselineCPSNR` stores it in the format of norm.csv."""
-    from . import upsample
+    result is what `evaluate(..., baseline_cpsnrs=)` takes; `utils.writeBaselineCPSNR` stores it in the format of norm.csv.
+
+    method="shift_add" scores the registered multi-frame baseline instead: `shiftadd.register_and_add(lrs, lr_masks, alphas, scale=S,
+    **method_kwargs)` (the views registered against the first one, then shift-and-add over the bicubic base; a and n_ref are not used).
+    A batch may carry lr_masks (B,V,H,W) as a sixth item, which that method uses (None: all clear); the bicubic method does not read
+    it."""
+    if method not in ("bicubic", "shift_add"):
+        raise ValueError(f"method must be \"bicubic\" or \"shift_add\"; got {method!r}")
+    if method == "bicubic" and method_kwargs:
+        raise TypeError(f"method=\"bicubic\" takes no further arguments; got {sorted(method_kwargs)}")
+    from . import shiftadd, upsample
     table = {}
     with torch.no_grad():
         for batch in batches:
-            if len(batch) != 5:
-                raise ValueError(f"a baseline batch is (lrs, alphas, hrs, hr_maps, names); got {len(batch)} elements")
-            lrs, alphas, hrs, hr_maps, names = batch
+            if len(batch) not in (5, 6):
+                raise ValueError(f"a baseline batch is (lrs, alphas, hrs, hr_maps, names[, lr_masks]); got {len(batch)} elements")
+            lrs, alphas, hrs, hr_maps, names = batch[:5]
+            lr_masks = batch[5] if len(batch) == 6 else None
             names = list(names)
             if len(names) != lrs.shape[0]:
                 raise ValueError(f"{len(names)} names for a batch of {lrs.shape[0]}")
             S = hrs.shape[-2] // lrs.shape[-2]
             if tuple(hrs.shape[-2:]) != (S * lrs.shape[-2], S * lrs.shape[-1]):
                 raise ValueError(f"hrs {tuple(hrs.shape)} is no integer multiple of lrs {tuple(lrs.shape)}")
-            srs = upsample.baseline(lrs, alphas, scale=S, a=a, n_ref=n_ref)[:, 0]
+            if method == "bicubic":
+                srs = upsample.baseline(lrs, alphas, scale=S, a=a, n_ref=n_ref)[:, 0]
+            else:
+                srs = shiftadd.register_and_add(lrs, lr_masks, alphas, scale=S, **method_kwargs)[0]
             cpsnr = _default_score(srs, hrs, hr_maps, border_w).double().cpu().numpy()
             for name, c in zip(names, cpsnr):
                 table[name] = float(c)

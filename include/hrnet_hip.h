@@ -50,6 +50,8 @@
  *                              a cloud-free reference frame from the views and their quality masks, and HRNet given that frame
  *   hrn_upsample / hrn_upsample_backward  <-  (no counterpart: the reference's network synthesises the whole image) bicubic x2 / x3 / x4
  *                              interpolation of a frame with an add, and its adjoint: the global residual over an upsampled LR frame
+ *   hrn_shift_add / hrn_shift_add_backward  <-  (no counterpart: the reference has no classical multi-frame predictor) shift-and-add of the
+ *                              registered views onto the x2 / x3 / x4 grid (normalised convolution), and its adjoint
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor's data_ptr) unless stated;
@@ -279,6 +281,45 @@ int hrn_hrnet_backward_ref(const void* packed, int dtype, int scale, const hrn_h
 #define HRN_UPSAMPLE_TILE_W 32
 int hrn_upsample(const float* frames, const float* base, float* out, int64_t n_planes, int H, int W, int scale, float a, void* stream);
 int hrn_upsample_backward(const float* d_out, float* d_frames, int64_t n_planes, int H, int W, int scale, float a, void* stream);
+
+/* ------------------------------------------------------------------ shift-and-add (normalised convolution)
+ * (No counterpart in the reference.)  Every clear LR sample of every registered view is placed at its sub-pixel position on the HR grid,
+ * and an HR pixel is the weighted mean of the samples near it, blended with an optional base frame.
+ *
+ * views, view_masks (B,V,H,W) f32; a mask is 0 / non-zero, view_masks NULL = all ones.  alphas (B,V) or NULL; a view counts iff its alpha
+ * is non-zero (a flag, not a weight).  shifts (B,V,2) f32 = (dy, dx) in the registration convention Registered(y,x) = View(y+dy, x+dx):
+ * reference coordinate y lies at view coordinate y + dy, so what the masked-NCC searches return goes in unchanged.  scale S in {2, 3, 4}.
+ *   HR grid: HR row Y = S m + p has the reference coordinate y = m + t_p, t_p = (p + 0.5) / S - 0.5 (the upsampler's grid).
+ *   Taps, per axis and view: d = t_p + dy, formed in fp64 from the fp32 shift, rounded to fp32; at or beyond +-256 it is taken as +-256.
+ *     A view with a non-finite shift contributes nothing.  n = floor(d), f = d - n in fp64 (exact); four taps o = -1 .. 2, tap o reads view
+ *     row m + n + o at distance u = o - f with the weight
+ *         k(u) = exp(-u^2 / (2 sigma^2)) cos^2(pi u / 4)  for |u| < 2,  else 0,
+ *     which is non-negative and vanishes with zero slope at the ends of its support: a floor that falls the other way moves nothing, and
+ *     the result is C^1 in the shift.  The S x 4 weights of an axis of a view are formed in fp64 (u from the fp32 d, sigma from its fp32
+ *     value) and rounded to fp32; a weight below 2^-60 is taken as 0, so that every product k_y k_x that enters a sum is a normal fp32
+ *     number (no term of D underflows, and D is either exactly 0 or at least 2^-120).  sigma is in LR pixels, in [0.1, 1].  Columns likewise; a sample's weight is the product k_y k_x.
+ *   Sums: N(Y,X) = sum over v, o_y, o_x of k_y k_x x, D(Y,X) the same without x.  A tap outside the frame, a masked sample and a view that
+ *     does not count contribute nothing (there is no padding rule).  fp32: per view the column taps first, then the row taps over those
+ *     sums (slots ascending, one fma each), added to N and D with the views in index order.
+ *   Output: out = (N + prior b) / (D + prior) where D + prior >= 2^-20, else b; b = base (B,SH,SW), 0 when base is NULL; prior >= 0 is the
+ *     weight of the base in units where one sample at distance 0 weighs 1.  weight (B,SH,SW) = D is a second output and may be NULL.
+ *     base may be out itself; nothing else may overlap an output.
+ * hrn_shift_add_backward: out is linear in views and base, D depends on masks and shifts only.  It takes the forward's `weight` (D) and,
+ * with q = d_out / (D + prior) where D + prior >= 2^-20, else 0, WRITES
+ *     d_views(v,i,j) = [v counts][(i,j) clear] * sum over the HR pixels whose taps reach (i,j) of k_y k_x q   (a gather over at most
+ *                      (4 S)^2 HR pixels, no atomics),
+ *     d_base = prior q, or d_out where the fallback holds.
+ * Either of d_views / d_base may be NULL, and then that half does not run.  There is no gradient to shifts, masks or alphas.
+ * Both functions are bit-reproducible, a sample's result does not depend on its batch, and appended views with alpha 0 change no bit.
+ * H, W in 1 .. 16384, any B, V >= 1; every offset is 64-bit.  -2 before any launch for a NULL views / shifts / out / d_out / weight (of the
+ * backward), non-positive sizes, a side beyond 16384, a scale outside {2, 3, 4}, a sigma outside [0.1, 1] or a prior below 0 (or either not
+ * finite), or overlapping arguments.  A workgroup owns HRN_SHIFT_ADD_TILE_H x HRN_SHIFT_ADD_TILE_W LR pixels. */
+#define HRN_SHIFT_ADD_TILE_H 8
+#define HRN_SHIFT_ADD_TILE_W 32
+int hrn_shift_add(const float* views, const float* view_masks, const float* alphas, const float* shifts, const float* base, float* out,
+                  float* weight, int B, int V, int H, int W, int scale, float sigma, float prior, void* stream);
+int hrn_shift_add_backward(const float* d_out, const float* weight, const float* view_masks, const float* alphas, const float* shifts,
+                           float* d_views, float* d_base, int B, int V, int H, int W, int scale, float sigma, float prior, void* stream);
 
 /* ------------------------------------------------------------------ ShiftNet */
 typedef struct hrn_shiftnet_params {
