@@ -109,6 +109,11 @@ SIGNATURES = {
     "hrn_upsample_backward": (_c.c_int, [_c.c_void_p] * 2 + [_c.c_int64] + [_c.c_int] * 3 + [_c.c_float, _c.c_void_p]),
     "hrn_shift_add": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_int] * 5 + [_c.c_float, _c.c_float, _c.c_void_p]),
     "hrn_shift_add_backward": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_int] * 5 + [_c.c_float, _c.c_float, _c.c_void_p]),
+    "hrn_observe_workspace_bytes": (_c.c_size_t, [_c.c_int] * 4),
+    "hrn_observe": (_c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 5 + [_c.c_void_p]),
+    "hrn_consistency_residual": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_size_t] + [_c.c_int] * 5 + [_c.c_void_p]),
+    "hrn_consistency_finish": (_c.c_int, [_c.c_void_p, _c.c_size_t] + [_c.c_void_p] * 7 + [_c.c_int] * 5 + [_c.c_float, _c.c_int, _c.c_void_p]),
+    "hrn_observe_adjoint": (_c.c_int, [_c.c_void_p] * 9 + [_c.c_int] * 5 + [_c.c_void_p]),
     "hrn_hrnet_forward_ref": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                          _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_hrnet_forward_train_ref": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
@@ -1582,6 +1587,86 @@ def shift_add_backward(d_out, weight, view_masks, alphas, shifts, V, H, W, scale
     return d_views, d_base
 
 
+# --------------------------------------------------------------------------- the observation model (observe.hip)
+OBSERVE_TILE = (8, 32)        # HRN_OBSERVE_TILE_H x HRN_OBSERVE_TILE_W: the LR samples a workgroup owns
+OBSERVE_MAX_SIDE = 16384      # frames of 1 .. 16384 a side
+OBSERVE_STEP = (0.0, 2.0)     # back-projection's step lies strictly between these
+
+
+def observe(hr, shifts, scale):
+    """hrn_observe on contiguous f32 device tensors (hrnet_hip/observation.py checks them): hr (B,SH,SW), shifts (B,V,2) ->
+    (views (B,V,H,W), valid (B,V,H,W) 0 / 1)."""
+    lib = load_library()
+    B, V = shifts.shape[:2]
+    H, W = hr.shape[1] // scale, hr.shape[2] // scale
+    views = torch.empty((B, V, H, W), dtype=torch.float32, device=hr.device)
+    valid = torch.empty_like(views)
+    with torch.cuda.device(hr.device):
+        _check(lib.hrn_observe(_ptr(hr), _ptr(shifts), _ptr(views), _ptr(valid), B, V, H, W, int(scale), _stream()), "hrn_observe")
+    return views, valid
+
+
+def observe_adjoint(residual, lr_masks, alphas, shifts, beta, coef, gain, x, scale, out=None):
+    """hrn_observe_adjoint: residual (B,V,H,W), beta (B,V) or None, coef, gain (B,) or None, x (B,SH,SW) or None -> out (B,SH,SW) =
+    coef gain G, or x - coef gain G.  out: where the result goes (a new tensor when None); x may be out itself."""
+    lib = load_library()
+    B, V, H, W = residual.shape
+    if out is None:
+        out = torch.empty((B, scale * H, scale * W), dtype=torch.float32, device=residual.device)
+    with torch.cuda.device(residual.device):
+        _check(lib.hrn_observe_adjoint(_ptr(residual), _opt_ptr(lr_masks), _opt_ptr(alphas), _ptr(shifts), _opt_ptr(beta), _opt_ptr(coef),
+                                       _opt_ptr(gain), _opt_ptr(x), _ptr(out), B, V, H, W, int(scale), _stream()), "hrn_observe_adjoint")
+    return out
+
+
+class ConsistencyState:
+    """What the residual / finish pair of launches writes, allocated once and reused by every iteration of a back-projection: residual
+    (B,V,H,W), the tiles' workspace, beta (B,V), count (B,V) int32, ssr (B,V) fp64, n_views (B,) int32, coef_loss, coef_step (B,)."""
+
+    def __init__(self, B, V, H, W, device):
+        lib = load_library()
+        self.shape = (B, V, H, W)
+        self.ws_bytes = int(lib.hrn_observe_workspace_bytes(B, V, H, W))
+        if self.ws_bytes == 0:
+            raise HrnetHipError(f"hrn_observe_workspace_bytes refuses B={B} V={V} H={H} W={W}")
+        f32 = dict(dtype=torch.float32, device=device)
+        self.workspace = torch.empty((self.ws_bytes // 8,), dtype=torch.float64, device=device)
+        self.residual = torch.empty((B, V, H, W), **f32)
+        self.beta = torch.empty((B, V), **f32)
+        self.count = torch.empty((B, V), dtype=torch.int32, device=device)
+        self.ssr = torch.empty((B, V), dtype=torch.float64, device=device)
+        self.n_views = torch.empty((B,), dtype=torch.int32, device=device)
+        self.coef_loss = torch.empty((B,), **f32)
+        self.coef_step = torch.empty((B,), **f32)
+
+
+def consistency_residual(hr, lrs, lr_masks, alphas, shifts, scale, step, brightness, state, loss):
+    """hrn_consistency_residual then hrn_consistency_finish into `state` (a ConsistencyState) and `loss` (B,) f32: two launches, nothing
+    returns to the host."""
+    lib = load_library()
+    B, V, H, W = state.shape
+    with torch.cuda.device(hr.device):
+        _check(lib.hrn_consistency_residual(_ptr(hr), _ptr(lrs), _opt_ptr(lr_masks), _opt_ptr(alphas), _ptr(shifts), _ptr(state.residual),
+                                            _ptr(state.workspace), state.ws_bytes, B, V, H, W, int(scale), _stream()), "hrn_consistency_residual")
+        _check(lib.hrn_consistency_finish(_ptr(state.workspace), state.ws_bytes, _ptr(state.beta), _ptr(state.count), _ptr(state.ssr), _ptr(loss),
+                                          _ptr(state.n_views), _ptr(state.coef_loss), _ptr(state.coef_step), B, V, H, W, int(scale), float(step),
+                                          int(bool(brightness)), _stream()), "hrn_consistency_finish")
+
+
+def back_project(sr0, lrs, lr_masks, alphas, shifts, scale, iters, step, brightness):
+    """iters back-projection steps from sr0 (B,SH,SW): three launches each (residual, finish, adjoint in place) on the current stream ->
+    (sr, losses (iters,B) = L_b of the frame each step STARTED from).  iters = 0 returns a copy of sr0."""
+    B, V, H, W = lrs.shape
+    x = sr0.clone()
+    losses = torch.empty((iters, B), dtype=torch.float32, device=sr0.device)
+    if iters:
+        state = ConsistencyState(B, V, H, W, sr0.device)
+        for t in range(iters):
+            consistency_residual(x, lrs, lr_masks, alphas, shifts, scale, step, brightness, state, losses[t])
+            observe_adjoint(state.residual, lr_masks, alphas, shifts, state.beta, state.coef_step, None, x, scale, out=x)
+    return x, losses
+
+
 # --------------------------------------------------------------------------- PyTorch-ROCm custom ops (north_star: "exposed to Python as
 # PyTorch-ROCm custom ops"): the inference entry points are registered with the dispatcher as torch.ops.hrnet_hip.*, with fake
 # (meta) implementations, so that they are visible to torch.compile / export and to anyone calling through torch.ops.  Each is a
@@ -1731,6 +1816,118 @@ def _shift_add_backward(ctx, d_out, d_weight):
 
 
 _op_shift_add.register_autograd(_shift_add_backward, setup_context=_shift_add_setup)
+
+
+# The observation model (observe.hip).  observe is linear in hr: its autograd formula is the adjoint of the incoming gradient (a
+# registered op itself).  consistency_loss_train returns the loss with what its backward needs (the residual plane, beta, 2 / sum n); the
+# formula is consistency_loss_backward.  There is no gradient to lrs, shifts, masks or alphas.  back_project carries no gradient at all.
+@torch.library.custom_op("hrnet_hip::observe", mutates_args=(), device_types="cuda")
+def _op_observe(hr: torch.Tensor, shifts: torch.Tensor, scale: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """hr (B,SH,SW), shifts (B,V,2) -> (views (B,V,H,W), valid (B,V,H,W) 0 / 1) (hrn_observe)."""
+    return observe(_f32c(hr), _f32c(shifts), scale)
+
+
+@_op_observe.register_fake
+def _(hr, shifts, scale):
+    shape = (hr.shape[0], shifts.shape[1], hr.shape[1] // scale, hr.shape[2] // scale)
+    return hr.new_empty(shape, dtype=torch.float32), hr.new_empty(shape, dtype=torch.float32)
+
+
+@torch.library.custom_op("hrnet_hip::observe_backward", mutates_args=(), device_types="cuda")
+def _op_observe_backward(d_views: torch.Tensor, shifts: torch.Tensor, scale: int) -> torch.Tensor:
+    """d_views (B,V,H,W) -> d_hr (B,SH,SW) = sum_v A_v^T [valid] d_views (hrn_observe_adjoint)."""
+    return observe_adjoint(_f32c(d_views), None, None, _f32c(shifts), None, None, None, None, scale)
+
+
+@_op_observe_backward.register_fake
+def _(d_views, shifts, scale):
+    b, _, h, w = d_views.shape
+    return d_views.new_empty((b, scale * h, scale * w), dtype=torch.float32)
+
+
+def _observe_setup(ctx, inputs, output):
+    hr, shifts, scale = inputs
+    ctx.scale, ctx.hr_dtype = scale, hr.dtype
+    ctx.save_for_backward(shifts)
+
+
+def _observe_backward(ctx, d_views, d_valid):
+    if not ctx.needs_input_grad[0]:
+        return None, None, None
+    (shifts,) = ctx.saved_tensors
+    return torch.ops.hrnet_hip.observe_backward(d_views, shifts, ctx.scale).to(ctx.hr_dtype), None, None
+
+
+_op_observe.register_autograd(_observe_backward, setup_context=_observe_setup)
+
+
+@torch.library.custom_op("hrnet_hip::consistency_loss_train", mutates_args=(), device_types="cuda")
+def _op_consistency_loss_train(srs: torch.Tensor, lrs: torch.Tensor, lr_masks: Optional[torch.Tensor], alphas: Optional[torch.Tensor],
+                               shifts: torch.Tensor, scale: int, brightness: bool
+                               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """srs (B,SH,SW), lrs (B,V,H,W) -> (loss (B,), residual (B,V,H,W), beta (B,V), count (B,V) int32, coef (B,) = 2 / sum n)."""
+    srs, lrs = _f32c(srs), _f32c(lrs)
+    B, V, H, W = lrs.shape
+    state = ConsistencyState(B, V, H, W, srs.device)
+    loss = torch.empty((B,), dtype=torch.float32, device=srs.device)
+    consistency_residual(srs, lrs, _f32c(lr_masks), _f32c(alphas), _f32c(shifts), scale, 1.0, brightness, state, loss)
+    return loss, state.residual, state.beta, state.count, state.coef_loss
+
+
+@_op_consistency_loss_train.register_fake
+def _(srs, lrs, lr_masks, alphas, shifts, scale, brightness):
+    b, v = lrs.shape[:2]
+    f32 = dict(dtype=torch.float32)
+    return (srs.new_empty((b,), **f32), srs.new_empty(tuple(lrs.shape), **f32), srs.new_empty((b, v), **f32),
+            srs.new_empty((b, v), dtype=torch.int32), srs.new_empty((b,), **f32))
+
+
+@torch.library.custom_op("hrnet_hip::consistency_loss_backward", mutates_args=(), device_types="cuda")
+def _op_consistency_loss_backward(d_loss: torch.Tensor, residual: torch.Tensor, beta: torch.Tensor, coef: torch.Tensor,
+                                  lr_masks: Optional[torch.Tensor], alphas: Optional[torch.Tensor], shifts: torch.Tensor,
+                                  scale: int) -> torch.Tensor:
+    """-> d_srs (B,SH,SW) = d_loss_b coef_b sum_v A_v^T r_v (hrn_observe_adjoint)."""
+    return observe_adjoint(_f32c(residual), _f32c(lr_masks), _f32c(alphas), _f32c(shifts), _f32c(beta), _f32c(coef), _f32c(d_loss), None, scale)
+
+
+@_op_consistency_loss_backward.register_fake
+def _(d_loss, residual, beta, coef, lr_masks, alphas, shifts, scale):
+    b, _, h, w = residual.shape
+    return residual.new_empty((b, scale * h, scale * w), dtype=torch.float32)
+
+
+def _consistency_setup(ctx, inputs, output):
+    srs, lrs, lr_masks, alphas, shifts, scale, brightness = inputs
+    ctx.scale, ctx.srs_dtype = scale, srs.dtype
+    ctx.has = (lr_masks is not None, alphas is not None)
+    ctx.save_for_backward(output[1], output[2], output[4], shifts, *(t for t in (lr_masks, alphas) if t is not None))
+
+
+def _consistency_backward(ctx, d_loss, d_residual, d_beta, d_count, d_coef):
+    if not ctx.needs_input_grad[0]:
+        return (None,) * 7
+    saved = list(ctx.saved_tensors)
+    residual, beta, coef, shifts = saved[:4]
+    rest = saved[4:]
+    lr_masks = rest.pop(0) if ctx.has[0] else None
+    alphas = rest.pop(0) if ctx.has[1] else None
+    d_srs = torch.ops.hrnet_hip.consistency_loss_backward(d_loss, residual, beta, coef, lr_masks, alphas, shifts, ctx.scale)
+    return (d_srs.to(ctx.srs_dtype),) + (None,) * 6
+
+
+_op_consistency_loss_train.register_autograd(_consistency_backward, setup_context=_consistency_setup)
+
+
+@torch.library.custom_op("hrnet_hip::back_project", mutates_args=(), device_types="cuda")
+def _op_back_project(sr0: torch.Tensor, lrs: torch.Tensor, lr_masks: Optional[torch.Tensor], alphas: Optional[torch.Tensor],
+                     shifts: torch.Tensor, scale: int, iters: int, step: float, brightness: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (sr (B,SH,SW) after `iters` back-projection steps from sr0, losses (iters,B)); no gradient."""
+    return back_project(_f32c(sr0), _f32c(lrs), _f32c(lr_masks), _f32c(alphas), _f32c(shifts), scale, iters, step, brightness)
+
+
+@_op_back_project.register_fake
+def _(sr0, lrs, lr_masks, alphas, shifts, scale, iters, step, brightness):
+    return sr0.new_empty(tuple(sr0.shape), dtype=torch.float32), sr0.new_empty((iters, sr0.shape[0]), dtype=torch.float32)
 
 
 @torch.library.custom_op("hrnet_hip::lanczos_shift", mutates_args=(), device_types="cuda")

@@ -1,0 +1,159 @@
+"""The observation model on device: what every registered LR view should have recorded of an HR frame, the
+data-consistency loss that compares it with the views themselves, and iterative back-projection - the way back from the HR grid that
+shift-and-add (`shiftadd`) lacks.
+
+`A_v x`: view sample i integrates the HR frame over one LR pixel, as `scale` point samples per axis at the HR coordinates
+`scale (i - dy) + k`, each read with the six-tap sampler of the registration code and averaged - a separable (scale + 5)-tap filter per
+view and a decimation (include/hrnet_hip.h holds the definition).  `shifts (B,V,2)` are what any masked-NCC search returns
+(Registered(y,x) = View(y+dy, x+dx)); there is no padding rule, so a sample whose footprint leaves the HR frame is not valid.
+
+`observe` makes synthetic LR views of HR frames; `consistency_loss` is `sum_v |counted (A_v sr - lr_v + beta_v)|^2 / sum_v n_v`, a loss
+without an HR target (self-supervised fine-tuning, PROBA-V's test split) with the brightness bias beta_v every loss here corrects;
+`back_project` refines a frame against the views, `x <- x - step (scale^2 / V_b) sum_v A_v^T r_v`; `register_and_refine` registers,
+starts from shift-and-add or the bicubic baseline and refines.  Gradients go to the HR frame only; there is NONE to shifts, lrs, masks or
+alphas.  There is no CPU fallback: tensors must be on a ROCm device."""
+import numpy as np
+import torch
+
+from . import binding, registration
+from .resample import check_scale
+
+
+def _tensor(name, t, shape=None, optional=False):
+    if t is None and optional:
+        return
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name} must be a torch.Tensor{' or None' if optional else ''}; got {type(t).__name__}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {tuple(shape)}; got {tuple(t.shape)}")
+
+
+def _on_device(first, **tensors):
+    for name, t in tensors.items():
+        if not torch.is_tensor(t):
+            continue
+        if not t.is_cuda:
+            raise TypeError(f"{name} is on '{t.device}': the observation model runs on a ROCm device only (no CPU fallback)")
+        if t.device != first.device:
+            raise TypeError(f"{name} is on '{t.device}' but the first argument on '{first.device}'")
+
+
+def _flag(name, v):
+    if not isinstance(v, (bool, np.bool_)):
+        raise TypeError(f"{name} must be a bool; got {v!r}")
+    return bool(v)
+
+
+def check_step(step):
+    if isinstance(step, bool) or not isinstance(step, (int, float, np.floating, np.integer)):
+        raise TypeError(f"step must be a number; got {step!r}")
+    lo, hi = binding.OBSERVE_STEP
+    if not (np.isfinite(step) and lo < float(np.float32(step)) < hi):
+        raise ValueError(f"step must lie in ({lo}, {hi}); got {step}")
+    return float(step)
+
+
+def check_iters(iters):
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
+        raise ValueError(f"iters must be an integer >= 0; got {iters!r}")
+    return int(iters)
+
+
+def _check_views(srs, lrs, shifts, lr_masks, alphas, scale, what="srs"):
+    """the checks every function with LR views shares -> (srs as (B,SH,SW), whether it came as (B,1,SH,SW), scale)"""
+    _tensor(what, srs)
+    _tensor("lrs", lrs)
+    if lrs.dim() != 4 or lrs.numel() == 0:
+        raise ValueError(f"lrs must be a non-empty (B,V,H,W); got {tuple(lrs.shape)}")
+    B, V, H, W = lrs.shape
+    scale = check_scale(scale)
+    channel = srs.dim() == 4
+    if channel and srs.shape[1] != 1:
+        raise ValueError(f"{what} must be (B,SH,SW) or (B,1,SH,SW); got {tuple(srs.shape)}")
+    want = (B, scale * H, scale * W)
+    if tuple(srs.shape) not in (want, (B, 1) + want[1:]):
+        raise ValueError(f"{what} must be {want} (or with a channel of 1) for lrs {tuple(lrs.shape)} at scale {scale}; got {tuple(srs.shape)}")
+    _tensor("shifts", shifts, (B, V, 2))
+    _tensor("lr_masks", lr_masks, lrs.shape, optional=True)
+    _tensor("alphas", alphas, (B, V), optional=True)
+    if max(H, W) > binding.OBSERVE_MAX_SIDE:
+        raise ValueError(f"frames of 1..{binding.OBSERVE_MAX_SIDE} a side; got {H} x {W}")
+    if not (srs.is_floating_point() and lrs.is_floating_point() and shifts.is_floating_point()):
+        raise TypeError(f"{what}, lrs and shifts must be floating-point tensors")
+    _on_device(srs, lrs=lrs, shifts=shifts, lr_masks=lr_masks, alphas=alphas, **{what: srs})
+    return (srs[:, 0] if channel else srs), channel, scale
+
+
+def observe(hr, shifts, scale=3):
+    """hr (B, scale H, scale W), shifts (B,V,2) -> (views (B,V,H,W), valid (B,V,H,W) f32 0 / 1): what a view at each shift records of the
+    HR frame - synthetic LR views with the library's own sampler.  A sample whose footprint leaves the frame is 0 and not valid, and so is
+    every sample of a view with a non-finite shift (or one of 256 / scale LR pixels or more).  Differentiable in hr (the adjoint kernel);
+    the gradient that arrives at `views` counts where `valid` is set.  The HR sides must be multiples of scale, H, W in 1..16384."""
+    _tensor("hr", hr)
+    _tensor("shifts", shifts)
+    scale = check_scale(scale)
+    if hr.dim() != 3 or hr.numel() == 0:
+        raise ValueError(f"hr must be a non-empty (B,SH,SW); got {tuple(hr.shape)}")
+    if hr.shape[1] % scale or hr.shape[2] % scale:
+        raise ValueError(f"the sides of hr must be multiples of scale {scale}; got {tuple(hr.shape)}")
+    if shifts.dim() != 3 or shifts.shape[0] != hr.shape[0] or shifts.shape[1] == 0 or shifts.shape[2] != 2:
+        raise ValueError(f"shifts must be (B,V,2) with B = {hr.shape[0]} and V >= 1; got {tuple(shifts.shape)}")
+    if max(hr.shape[1:]) > scale * binding.OBSERVE_MAX_SIDE:
+        raise ValueError(f"LR frames of 1..{binding.OBSERVE_MAX_SIDE} a side; got hr {tuple(hr.shape)} at scale {scale}")
+    if not (hr.is_floating_point() and shifts.is_floating_point()):
+        raise TypeError("hr and shifts must be floating-point tensors")
+    _on_device(hr, hr=hr, shifts=shifts)
+    views, valid = torch.ops.hrnet_hip.observe(hr, shifts.detach(), scale)
+    return views, valid.detach()
+
+
+def consistency_loss(srs, lrs, shifts, lr_masks=None, alphas=None, scale=3, brightness=True, return_residual=False):
+    """srs (B,SH,SW) or (B,1,SH,SW), lrs (B,V,H,W), shifts (B,V,2)[, lr_masks (B,V,H,W) 0 / non-zero, alphas (B,V): a view counts iff its
+    alpha is non-zero] -> loss (B,) = sum_v sum (counted (A_v sr - lr_v + beta_v))^2 / sum_v n_v, exactly 0 for a sample in which nothing
+    counts.  brightness: beta_v = -mean of the counted A_v sr - lr_v (the views' brightness bias), else 0.  return_residual: also
+    (residual (B,V,H,W) = A_v sr - lr_v where counted and 0 elsewhere, beta (B,V), count (B,V) int32), all without a gradient.
+    Differentiable in srs only.  Two launches forward (nothing returns to the host), one backward."""
+    brightness = _flag("brightness", brightness)
+    srs3, _, scale = _check_views(srs, lrs, shifts, lr_masks, alphas, scale)
+    det = lambda t: None if t is None else t.detach()
+    loss, residual, beta, count, _ = torch.ops.hrnet_hip.consistency_loss_train(srs3, lrs.detach(), det(lr_masks), det(alphas), shifts.detach(),
+                                                                                scale, brightness)
+    return (loss, residual.detach(), beta.detach(), count) if return_residual else loss
+
+
+def back_project(sr0, lrs, shifts, lr_masks=None, alphas=None, scale=3, iters=10, step=1.0, brightness=True, return_loss=False):
+    """sr0 (B,SH,SW) or (B,1,SH,SW) -> sr of the same shape after `iters` steps x <- x - step (scale^2 / V_b) sum_v A_v^T r_v(x), V_b the
+    number of views with a counted pixel (a sample without one is returned unchanged).  step in (0, 2): the largest eigenvalue of
+    (scale^2 / V) sum_v A_v^T M A_v is 1 within 2 %.  iters = 0 returns sr0's bits.  return_loss: also losses (iters,B), the
+    consistency loss of the frame every step started from, on the device.  No gradient.  3 iters launches on the current stream."""
+    iters, step, brightness = check_iters(iters), check_step(step), _flag("brightness", brightness)
+    srs3, channel, scale = _check_views(sr0, lrs, shifts, lr_masks, alphas, scale, what="sr0")
+    with torch.no_grad():
+        sr, losses = torch.ops.hrnet_hip.back_project(srs3, lrs, lr_masks, alphas, shifts, scale, iters, step, brightness)
+    sr = sr.unsqueeze(1) if channel else sr
+    return (sr, losses) if return_loss else sr
+
+
+def register_and_refine(lrs, lr_masks=None, alphas=None, scale=3, iters=10, step=1.0, init="shift_add", octaves=0, **search_kwargs):
+    """lrs (B,V,H,W)[, lr_masks, alphas] -> (sr (B, scale H, scale W), shifts (B,V,2)): the views registered against the first one, a
+    start - init="shift_add": `shiftadd.register_and_add`; "bicubic": the search (`registration.mncc_search_scene`, or with octaves > 0
+    `mncc_search_pyramid`) and `upsample.baseline` - and `iters` back-projection steps from it.  search_kwargs go to the search; frames are
+    16..16384 a side, the search's limits.  No gradient."""
+    if init not in ("shift_add", "bicubic"):
+        raise ValueError(f"init must be \"shift_add\" or \"bicubic\"; got {init!r}")
+    iters, step, scale = check_iters(iters), check_step(step), check_scale(scale)
+    registration._no_trace(search_kwargs, "register_and_refine returns no trace; call the search itself for it")
+    if isinstance(octaves, bool) or not isinstance(octaves, (int, np.integer)) or octaves < 0:
+        raise ValueError(f"octaves must be an integer >= 0; got {octaves!r}")
+    from . import shiftadd, upsample
+    with torch.no_grad():
+        if init == "shift_add":
+            sr0, _, shifts = shiftadd.register_and_add(lrs, lr_masks, alphas, scale=scale, octaves=octaves, **search_kwargs)
+        else:
+            if octaves > 0:
+                shifts = registration.mncc_search_pyramid(lrs, lr_masks, octaves=int(octaves), **search_kwargs)
+            else:
+                shifts = registration.mncc_search_scene(lrs, lr_masks, **search_kwargs)
+            sr0 = upsample.baseline(lrs, alphas, lr_masks, scale)[:, 0]
+        sr = back_project(sr0, lrs, shifts, lr_masks, alphas, scale, iters, step)
+    return sr, shifts

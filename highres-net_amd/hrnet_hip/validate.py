@@ -131,13 +131,15 @@ def baseline_table(batches, border_w=3, a=-0.75, n_ref=9, method="bicubic", **me
 
     method="shift_add" scores the registered multi-frame baseline instead: `shiftadd.register_and_add(lrs, lr_masks, alphas, scale=S,
     **method_kwargs)` (the views registered against the first one, then shift-and-add over the bicubic base; a and n_ref are not used).
-    A batch may carry lr_masks (B,V,H,W) as a sixth item, which that method uses (None: all clear); the bicubic method does not read
+    method="back_projection" scores `observation.register_and_refine(lrs, lr_masks, alphas, scale=S, **method_kwargs)`: the same
+    registration, then iterative back-projection against the views (iters, step, init).
+    A batch may carry lr_masks (B,V,H,W) as a sixth item, which those two methods use (None: all clear); the bicubic method does not read
     it."""
-    if method not in ("bicubic", "shift_add"):
-        raise ValueError(f"method must be \"bicubic\" or \"shift_add\"; got {method!r}")
+    if method not in ("bicubic", "shift_add", "back_projection"):
+        raise ValueError(f"method must be \"bicubic\", \"shift_add\" or \"back_projection\"; got {method!r}")
     if method == "bicubic" and method_kwargs:
         raise TypeError(f"method=\"bicubic\" takes no further arguments; got {sorted(method_kwargs)}")
-    from . import shiftadd, upsample
+    from . import observation, shiftadd, upsample
     table = {}
     with torch.no_grad():
         for batch in batches:
@@ -153,8 +155,10 @@ def baseline_table(batches, border_w=3, a=-0.75, n_ref=9, method="bicubic", **me
                 raise ValueError(f"hrs {tuple(hrs.shape)} is no integer multiple of lrs {tuple(lrs.shape)}")
             if method == "bicubic":
                 srs = upsample.baseline(lrs, alphas, scale=S, a=a, n_ref=n_ref)[:, 0]
-            else:
+            elif method == "shift_add":
                 srs = shiftadd.register_and_add(lrs, lr_masks, alphas, scale=S, **method_kwargs)[0]
+            else:
+                srs = observation.register_and_refine(lrs, lr_masks, alphas, scale=S, **method_kwargs)[0]
             cpsnr = _default_score(srs, hrs, hr_maps, border_w).double().cpu().numpy()
             for name, c in zip(names, cpsnr):
                 table[name] = float(c)

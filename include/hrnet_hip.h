@@ -52,6 +52,8 @@
  *                              interpolation of a frame with an add, and its adjoint: the global residual over an upsampled LR frame
  *   hrn_shift_add / hrn_shift_add_backward  <-  (no counterpart: the reference has no classical multi-frame predictor) shift-and-add of the
  *                              registered views onto the x2 / x3 / x4 grid (normalised convolution), and its adjoint
+ *   hrn_observe / hrn_consistency_residual / hrn_consistency_finish / hrn_observe_adjoint  <-  (no counterpart) the observation model: what
+ *                              every registered view should have recorded of an HR frame, the data-consistency loss and back-projection
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor's data_ptr) unless stated;
@@ -320,6 +322,60 @@ int hrn_shift_add(const float* views, const float* view_masks, const float* alph
                   float* weight, int B, int V, int H, int W, int scale, float sigma, float prior, void* stream);
 int hrn_shift_add_backward(const float* d_out, const float* weight, const float* view_masks, const float* alphas, const float* shifts,
                            float* d_views, float* d_base, int B, int V, int H, int W, int scale, float sigma, float prior, void* stream);
+
+/* ------------------------------------------------------------------ the observation model: A_v, its adjoint, the consistency loss
+ * (No counterpart in the reference.)  A_v x is what view v should have recorded of the HR frame x at its registered sub-pixel position.
+ *
+ * hr (B,SH,SW) f32 with SH = S H, SW = S W exactly, S = scale in {2, 3, 4}; lrs, lr_masks, residual, views, valid (B,V,H,W) f32; a mask is
+ * 0 / non-zero, lr_masks NULL = all ones; alphas (B,V) or NULL, a view counts iff its alpha is non-zero (a flag) and both components of its
+ * shift are finite.  shifts (B,V,2) f32 = (dy, dx), Registered(y,x) = View(y+dy, x+dx): what the masked-NCC searches return goes in
+ * unchanged.  HR row Y lies at the reference coordinate (Y + 0.5) / S - 0.5.
+ *   Operator: view sample i integrates the HR frame over one LR pixel, as S point samples per axis at the HR coordinates S (i - dy) + k,
+ *     k = 0 .. S - 1, each read with the six-tap sampler of the registration code, t_o(f) = sinc(o - f) sinc((o - f) / 3), o = -2 .. 3,
+ *     normalised to sum 1, and averaged.  Per axis and view: c = -S dy, formed in fp64 from the fp32 shift, rounded to fp32, clamped to
+ *     +-256; n = floor(c), f = c - n (exact in fp64).  The S samples share f, so there is ONE vector of S + 5 weights,
+ *         w_j = (1 / S) sum_{k=0}^{S-1} t_{j-2-k}(f),  t zero outside -2 .. 3,  j = 0 .. S + 4,
+ *     formed in fp64 and rounded to fp32 once; it acts on the HR rows S i + n - 2 + j and sums to 1.  Columns likewise; the operator is a
+ *     separable (S + 5)-tap filter, the same for every sample of a view, and a decimation by S at an integer offset.  fp32: the row pass
+ *     (along x) first, then the column pass, j ascending, one fma each.
+ *   No padding rule: sample i is valid iff 0 <= S i + n - 2 and S i + n + S + 2 <= S H - 1, on both axes, at f = 0 too.  One rule is added
+ *     to that: a view whose unclamped |c| reaches 256 on an axis (a shift of 256 / S LR pixels or more) has no valid sample at all, since
+ *     the clamped coordinate is no longer the view's.
+ *   counted = valid and mask != 0 and the view counts.
+ *   Adjoint: (A_v^T r)(Y) = sum_i w_{Y - S i - n + 2} r(i) over the at most 4 / 3 / 3 (x2 / x3 / x4) view rows per axis that reach Y: a
+ *     gather, no atomics.
+ *   Loss, per sample b: e = A_v x - y_v; n_v = sum counted; beta_v = -sum counted e / n_v with `brightness`, else 0 (and 0 when n_v = 0);
+ *     r_v = counted (e + beta_v); L_b = sum_v sum r_v^2 / sum_v n_v, exactly 0 when nothing counts; dL_b/dx = (2 / sum n_v) sum_v A_v^T r_v.
+ *   Back-projection: x' = x - step (S^2 / V_b) sum_v A_v^T r_v(x), V_b the number of views with n_v > 0 (x' = x when V_b = 0), step in (0, 2).
+ *
+ * hrn_observe WRITES views = A_v hr where valid and 0 elsewhere, and valid 0 / 1 (there are no masks or alphas here: a view with a
+ *   non-finite shift is 0 and nowhere valid).
+ * hrn_consistency_residual WRITES residual = e where counted, exact 0 elsewhere, and per tile of HRN_OBSERVE_TILE_H x HRN_OBSERVE_TILE_W
+ *   samples the fp64 sums n, sum e, sum e^2 into `workspace` (hrn_observe_workspace_bytes(B, V, H, W) bytes, 8-byte aligned; 0 for sizes
+ *   the functions refuse).
+ * hrn_consistency_finish adds the tiles' partials of every view in a fixed order (fp64) and WRITES beta (B,V) f32, count (B,V) int32 = n_v,
+ *   ssr (B,V) fp64 = sum r_v^2, loss (B) f32 = L_b, n_views (B) int32 = V_b, coef_loss (B) f32 = 2 / sum_v n_v (0 when nothing counts) and
+ *   coef_step (B) f32 = step S^2 / V_b (0 when V_b = 0).  Nothing returns to the host.
+ * hrn_observe_adjoint: G = sum_v A_v^T [counted] (residual_v + beta_v), counted re-derived from shifts, lr_masks and alphas, the views in
+ *   index order; with c_b = coef[b] gain[b] (either NULL = 1) it WRITES out = c_b G when x is NULL, else out = x - c_b G, where x may be out
+ *   itself.  beta NULL = 0.  The loss' gradient is (residual, beta, coef_loss, gain = dL), one back-projection step (residual, beta,
+ *   coef_step, NULL, x), the adjoint of hrn_observe (the incoming gradient as residual and nothing else).
+ * All four are bit-reproducible (one writer per element, fixed orders, no atomics), a sample's result does not depend on its batch, and
+ * appended views with alpha 0 change no bit.  H, W in 1 .. 16384, any B, V >= 1; every offset is 64-bit.  -2 before any launch for a NULL
+ * required pointer, non-positive sizes, a side beyond 16384, a scale outside {2, 3, 4}, a step outside (0, 2), a workspace that is too
+ * small or misaligned, or overlapping arguments (only x may be out). */
+#define HRN_OBSERVE_TILE_H 8
+#define HRN_OBSERVE_TILE_W 32
+size_t hrn_observe_workspace_bytes(int B, int V, int H, int W);
+int hrn_observe(const float* hr, const float* shifts, float* views, float* valid, int B, int V, int H, int W, int scale, void* stream);
+int hrn_consistency_residual(const float* hr, const float* lrs, const float* lr_masks, const float* alphas, const float* shifts,
+                             float* residual, void* workspace, size_t workspace_bytes, int B, int V, int H, int W, int scale, void* stream);
+int hrn_consistency_finish(const void* workspace, size_t workspace_bytes, float* beta, int* count, void* ssr, float* loss, int* n_views,
+                           float* coef_loss, float* coef_step, int B, int V, int H, int W, int scale, float step, int brightness,
+                           void* stream);
+int hrn_observe_adjoint(const float* residual, const float* lr_masks, const float* alphas, const float* shifts, const float* beta,
+                        const float* coef, const float* gain, const float* x, float* out, int B, int V, int H, int W, int scale,
+                        void* stream);
 
 /* ------------------------------------------------------------------ ShiftNet */
 typedef struct hrn_shiftnet_params {

@@ -19,8 +19,10 @@ initialised for K != 3, on the seeded x3 encoder and fusion block) and K S x K S
 loss = -shift_loss(srs, hrs, hr_maps) (hrnet_hip.losses): no ShiftNet is built, the optimiser holds HRNet's parameters
 only, and the 128-pixel window does not apply; cssim is the second score as a loss, loss = mean(cssim_loss(srs, hrs, hr_maps)) (DESIGN.md
 section 7l), HRNet alone as for shift; l1 is the searched L1, loss = mean(cl1_loss(srs, hrs, hr_maps)) (DESIGN.md section 7m), likewise;
-subpixel is the cPSNR registered at a sub-pixel shift, loss = -subpixel_loss(srs, hrs, hr_maps), likewise.  Several
-values alternate in one process like the precisions.
+subpixel is the cPSNR registered at a sub-pixel shift, loss = -subpixel_loss(srs, hrs, hr_maps) (DESIGN.md section 7q), likewise;
+consistency is the loss without an HR target, loss = mean(consistency_loss(srs, lrs, shifts, alphas=alphas)) (hrnet_hip.observation,
+DESIGN.md section 7t), HRNet alone again: it is timed twice, with shifts = mncc_search_scene(lrs) found under no_grad inside the step
+("consistency") and with the shifts given ("consistency, shifts given").  Several values alternate in one process like the precisions.
 """
 import copy
 import time
@@ -32,7 +34,9 @@ import torch
 from oracle import synth, weights            # seeded weights / synthetic inputs only (no oracle arithmetic on the path)
 from DeepNetworks.HRNet import HRNet
 from DeepNetworks.ShiftNet import ShiftNet
+from hrnet_hip import registration
 from hrnet_hip.losses import cl1_loss, cssim_loss, shift_loss, subpixel_loss
+from hrnet_hip.observation import consistency_loss
 from hrnet_hip.optim import FusedAdam
 
 
@@ -58,11 +62,14 @@ FREEZE = {"none": lambda k: False, "encoder": lambda k: k.startswith("fusion.enc
 def _label(key):
     p, sp, fr, ls = key
     return (f"train_precision={p}" + (f" shiftnet_train_precision={sp}" if sp is not None else "") + (f" freeze={fr}" if fr != "none" else "")
-            + (f" loss={ls}" if ls != "shiftnet" else ""))
+            + (f" loss={CONSISTENCY.get(ls, ls)}" if ls != "shiftnet" else ""))
 
 
 SEARCHED = {"shift": lambda srs, hrs, maps: -shift_loss(srs, hrs, maps), "cssim": cssim_loss, "l1": cl1_loss,
             "subpixel": lambda srs, hrs, maps: -subpixel_loss(srs, hrs, maps)}                                       # --loss -> the loss per sample
+
+# --loss consistency is two runs: the tail's key -> its label
+CONSISTENCY = {"consistency": "consistency", "consistency-given": "consistency, shifts given"}
 
 PARSER = _common.parser(__doc__, group=("B V S steps", (32, 32, 64, 5)), torch_adam=False, precision=[None], shiftnet_precision=[None], repeats=1,
                         freeze=["none"], scale=3, loss=["shiftnet"])      # scale: decoder stride and HR / LR ratio of the targets
@@ -71,7 +78,7 @@ PARSER = _common.parser(__doc__, group=("B V S steps", (32, 32, 64, 5)), torch_a
 def options(argv=None):
     o = PARSER.parse_args(argv)
     for flag, got, allowed in (("--freeze", o.freeze, tuple(FREEZE)), ("--precision", o.precision, (None, "fp32", "bf16x3", "bf16")),
-                               ("--shiftnet-precision", o.shiftnet_precision, (None, "fp32", "bf16")), ("--loss", o.loss, ("shiftnet", "shift", "cssim", "l1", "subpixel"))):
+                               ("--shiftnet-precision", o.shiftnet_precision, (None, "fp32", "bf16")), ("--loss", o.loss, ("shiftnet", "shift", "cssim", "l1", "subpixel", "consistency"))):
         for v in got:
             if v not in allowed:
                 PARSER.error(f"{flag}: {', '.join(a for a in allowed if a)} (got {v!r})")
@@ -94,6 +101,17 @@ def main():
     maps[:, :3] = 0; maps[:, -3:] = 0; maps[:, :, :3] = 0; maps[:, :, -3:] = 0
     x, a = torch.from_numpy(lrs).to(dev), torch.from_numpy(alphas).to(dev)
     off = (scale * S - 128) // 2
+    searched = dict(SEARCHED)
+    if "consistency" in tails:                               # the views are the data: no hrs, no maps
+        with torch.no_grad():
+            given = registration.mncc_search_scene(x)
+
+        def searching(srs, hrs, maps):
+            with torch.no_grad():
+                shifts = registration.mncc_search_scene(x)
+            return consistency_loss(srs, x, shifts, alphas=a, scale=scale)
+        searched.update({"consistency": searching, "consistency-given": lambda srs, hrs, maps: consistency_loss(srs, x, given, alphas=a, scale=scale)})
+        tails = [t for tail in tails for t in (tuple(CONSISTENCY) if tail == "consistency" else (tail,))]
 
     def setup(prec, sprec, freeze, tail):
         cfg = copy.deepcopy(weights.HRNET_CONFIG)
@@ -104,12 +122,12 @@ def main():
             state = {k: v for k, v in state.items() if not k.startswith("decode.")}
         fusion.load_state_dict(state, strict=scale == 3)
         fusion.train_precision = prec
-        if tail in SEARCHED:                                 # a searched loss has no parameters: HRNet alone is built and optimised
+        if tail in searched:                                 # a searched loss has no parameters: HRNet alone is built and optimised
             fusion = fusion.to(dev).train()
             for k, p in fusion.named_parameters():
                 p.requires_grad_(not FREEZE[freeze]("fusion." + k))
             params = list(fusion.parameters())
-            return fusion, SEARCHED[tail], adam(params, lr=1e-4)
+            return fusion, searched[tail], adam(params, lr=1e-4)
         regis = ShiftNet()
         if sprec is not None:
             regis.train_precision = sprec
@@ -138,7 +156,7 @@ def main():
         return loss
 
     runs = {(p, sp, f, t): setup(p, sp, f, t) for p in precs for t in tails for sp in (sprecs if t == "shiftnet" else [None]) for f in freezes
-            if not (t in SEARCHED and f == "shiftnet")}
+            if not (t in searched and f == "shiftnet")}
     for r in runs.values():
         for _ in range(2):
             step(*r)
