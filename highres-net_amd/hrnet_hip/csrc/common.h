@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 #include "prof.h"
 
 #define HRN_F32 0
@@ -168,4 +169,14 @@ static inline size_t hrn_align_up(size_t x, size_t a) { return (x + a - 1) / a *
 static inline int hrn_esize(int dt) { return dt == HRN_BF16 ? 2 : 4; }
 // HRNet upscale factors the decoder is built for (ConvTranspose2d kernel_size == stride == S)
 static inline bool hrn_scale_ok(int s) { return s >= 2 && s <= 4; }
+// -> f(std::integral_constant<int, scale>()) for a scale the caller has checked with hrn_scale_ok: the one place a run-time scale becomes
+// a template argument (decltype(s)::value inside f)
+template <class F>
+static inline auto hrn_by_scale(int scale, F&& f) {
+    switch (scale) {
+        case 2: return f(std::integral_constant<int, 2>());
+        case 3: return f(std::integral_constant<int, 3>());
+        default: return f(std::integral_constant<int, 4>());
+    }
+}
 

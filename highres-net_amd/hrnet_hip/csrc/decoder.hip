@@ -234,14 +234,12 @@ int hrn_launch_decoder(int dt, const void* fused, const void* wpk, const float* 
                                             {"decoder_f32_x4", "decoder_bf16_x4", "decoder_bf16x3_x4"}};
     const double k = 64.0 * scale * scale;      // deconv outputs per LR pixel
     HrnProfScope prof(names[scale - 2][dt], (2.0 * 64 * k + 2.0 * k) * npix, (double)npix * (64.0 * hrn_esize(dt) + 4.0 * scale * scale), stream);
-    if (scale == 2) return launch_decoder<2>(dt, fused, wpk, bias, slope, wf, bf, sr, npix, H, W, stream, fused_lo);
-    if (scale == 4) return launch_decoder<4>(dt, fused, wpk, bias, slope, wf, bf, sr, npix, H, W, stream, fused_lo);
-    return launch_decoder<3>(dt, fused, wpk, bias, slope, wf, bf, sr, npix, H, W, stream, fused_lo);
+    return hrn_by_scale(scale, [&](auto s) {
+        return launch_decoder<decltype(s)::value>(dt, fused, wpk, bias, slope, wf, bf, sr, npix, H, W, stream, fused_lo);
+    });
 }
 
 int hrn_launch_decoder_pack(int dt, const float* w, void* packed, hipStream_t stream, int scale) {
     HRN_CHECK(hrn_scale_ok(scale), -2, "decoder pack: scale must be 2, 3 or 4 (got %d)", scale);
-    if (scale == 2) return launch_decoder_pack<2>(dt, w, packed, stream);
-    if (scale == 4) return launch_decoder_pack<4>(dt, w, packed, stream);
-    return launch_decoder_pack<3>(dt, w, packed, stream);
+    return hrn_by_scale(scale, [&](auto s) { return launch_decoder_pack<decltype(s)::value>(dt, w, packed, stream); });
 }

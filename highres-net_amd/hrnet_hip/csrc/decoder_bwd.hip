@@ -191,7 +191,7 @@ int hrn_launch_decoder_bwd(const float* fused, const float* d_sr, const float* w
     const long P = (long)N * H * W;
     int grid = num_cus;
     if (P < grid) grid = (int)P;
-    if (scale == 2) return launch_decoder_bwd<2>(fused, d_sr, wd, bd, ad, wf, d_fused, dwd, dbd, dad, dwf, dbf, N, H, W, scratch, grid, s);
-    if (scale == 4) return launch_decoder_bwd<4>(fused, d_sr, wd, bd, ad, wf, d_fused, dwd, dbd, dad, dwf, dbf, N, H, W, scratch, grid, s);
-    return launch_decoder_bwd<3>(fused, d_sr, wd, bd, ad, wf, d_fused, dwd, dbd, dad, dwf, dbf, N, H, W, scratch, grid, s);
+    return hrn_by_scale(scale, [&](auto sc) {
+        return launch_decoder_bwd<decltype(sc)::value>(fused, d_sr, wd, bd, ad, wf, d_fused, dwd, dbd, dad, dwf, dbf, N, H, W, scratch, grid, s);
+    });
 }

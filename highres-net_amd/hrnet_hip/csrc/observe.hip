@@ -7,6 +7,9 @@
 // taps are the formula of split_and_taps kept in fp64 (that function rounds each tap to fp32; the definition rounds once, after the box
 // sum): one (view, axis, tap) per thread into LDS, then one (view, axis, j) per thread.
 //
+// The tile, its walk, the test whether a view counts and the list of a chunk's views are lr_tile.h's, shared with upsample.hip and
+// shift_add.hip.
+//
 // Forward / residual: a workgroup of 256 threads owns TH x TW = 8 x 32 samples of ONE view.
 //   1. win[8 S + 5][S][PW]  <- the HR window whose origin follows (n_y, n_x), DE-INTERLEAVED by column phase (column u -> plane u mod S,
 //      index u div S), zero outside the frame; 16-byte global loads where a row allows (its address 16-byte aligned, chosen per row; the
@@ -32,19 +35,16 @@
 //   then out = coef G, or x - coef G (x may be out: a thread reads what it writes).  One writer per element, no atomics.
 //
 // Resources (gfx950, -Rpass-analysis=kernel-resource-usage) are stated in DESIGN.md section 7t.
-#include "../../../include/hrnet_hip.h"
-#include "kernels.h"
+#include "lr_tile.h"
 
 #include <cmath>
 
 namespace {
 
-constexpr int kTH = HRN_OBSERVE_TILE_H, kTW = HRN_OBSERVE_TILE_W, kThreads = 256, kChunk = 32;
-constexpr unsigned kMaxBlocks = 1u << 16;                // tiles are grid-strided beyond this
-constexpr int kMaxSide = 16384;
+constexpr int kChunk = 32;                               // views whose weights a workgroup of the adjoint forms at a time
+static_assert(kChunk <= 64, "compact_chunk takes a chunk in one wave");
 constexpr float kMaxCoord = 256.f;                       // RG_DMAX of mncc_common.h: the clamp of split_and_taps
 constexpr int kFinishThreads = 1024;
-static_assert(kThreads == kTH * kTW, "the last pass of the forward is one thread per LR sample of the tile");
 
 constexpr int plane_stride(int S) { return S == 2 ? 48 : (S == 3 ? 43 : 40); }
 
@@ -83,11 +83,7 @@ __device__ __forceinline__ float box_weight(const double* k, int j) {
     return (float)(w / (double)S);
 }
 
-// a view counts: alpha non-zero (a flag) and both shift components finite; it is IN REACH when neither coordinate was clamped
-__device__ __forceinline__ bool view_counts(const float* alphas, const float* shifts, size_t bv) {
-    const float dy = shifts[2 * bv], dx = shifts[2 * bv + 1];
-    return (!alphas || alphas[bv] != 0.f) && isfinite(dy) && isfinite(dx);
-}
+// a view that counts (view_counts of lr_tile.h) is IN REACH when neither coordinate was clamped
 template <int S>
 __device__ __forceinline__ bool view_in_reach(const float* shifts, size_t bv) {
     return fabsf(hr_coord(S, shifts[2 * bv])) < kMaxCoord && fabsf(hr_coord(S, shifts[2 * bv + 1])) < kMaxCoord;
@@ -98,18 +94,6 @@ template <int S>
 __device__ __forceinline__ bool sample_valid(int i, int n, int L) {
     const long lo = (long)S * i + n - 2;
     return i >= 0 && i < L && lo >= 0 && lo + S + 4 <= (long)S * L - 1;
-}
-
-struct TilePos { size_t n; int y0, x0; };
-
-__device__ __forceinline__ TilePos tile_pos(size_t tile, unsigned tiles_x, unsigned tiles_y) {
-    const size_t per = (size_t)tiles_x * tiles_y;
-    TilePos t;
-    t.n = tile / per;
-    const unsigned r = (unsigned)(tile - t.n * per);
-    t.y0 = (int)(r / tiles_x) * kTH;
-    t.x0 = (int)(r % tiles_x) * kTW;
-    return t;
 }
 
 __device__ __forceinline__ int floor_div(int a, int b) { return (a >= 0 ? a : a - b + 1) / b; }
@@ -358,10 +342,7 @@ __global__ __launch_bounds__(kThreads) void observe_adjoint_kernel(const float* 
             }
             if (tid < 64) {                              // the first wave compacts the chunk's views (kChunk <= 64)
                 const size_t bv = tp.n * (size_t)V + (size_t)(v0 + min(tid, nv - 1));
-                const bool ok = tid < nv && view_counts(alphas, shifts, bv) && view_in_reach<S>(shifts, bv);
-                const unsigned long long votes = __ballot(ok);
-                if (ok) list[__popcll(votes & ((1ull << tid) - 1ull))] = tid;
-                if (tid == 0) n_list = __popcll(votes);
+                compact_chunk(tid < nv && view_counts(alphas, shifts, bv) && view_in_reach<S>(shifts, bv), list, &n_list);
             }
             __syncthreads();
             for (int e = tid; e < nv * 2 * NW; e += kThreads) {
@@ -441,31 +422,22 @@ __global__ __launch_bounds__(kThreads) void observe_adjoint_kernel(const float* 
     }
 }
 
-bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
-    return a0 < b1 && b0 < a1;
-}
-
 // what every entry point refuses; -> true, or false with the error set
 bool check_shape(const char* fn, int B, int V, int H, int W, int scale, unsigned* tiles_x, unsigned* tiles_y) {
     *tiles_x = *tiles_y = 0;
     if (!(B > 0 && V > 0 && H > 0 && W > 0)) { hrn_set_error("%s: empty input B=%d V=%d H=%d W=%d", fn, B, V, H, W); return false; }
-    if (H > kMaxSide || W > kMaxSide) { hrn_set_error("%s: frames of 1..%d a side; got H=%d W=%d", fn, kMaxSide, H, W); return false; }
-    if (!hrn_scale_ok(scale)) { hrn_set_error("%s: scale must be 2, 3 or 4 (got %d)", fn, scale); return false; }
+    if (!check_side_scale(fn, "frames", H, W, scale)) return false;
+    // 2^60 elements (upsample.hip and shift_add.hip stop at 2^62; no reason for the difference is recorded)
     if ((size_t)B > ((size_t)1 << 60) / ((size_t)V * scale * scale * H * W)) {
         hrn_set_error("%s: %d x %d frames of %d x %d exceed the address space", fn, B, V, H, W);
         return false;
     }
-    *tiles_y = (unsigned)((H + kTH - 1) / kTH);
-    *tiles_x = (unsigned)((W + kTW - 1) / kTW);
+    plane_tiles(H, W, tiles_x, tiles_y);
     return true;
 }
 
-unsigned blocks_for(size_t tiles) { return (unsigned)(tiles < kMaxBlocks ? tiles : kMaxBlocks); }
-
-size_t workspace_bytes(int B, int V, int H, int W) {
-    return (size_t)B * V * ((H + kTH - 1) / kTH) * ((W + kTW - 1) / kTW) * 3 * sizeof(double);
-}
+// three fp64 partials per tile of every view
+size_t workspace_bytes(int B, int V, int H, int W) { return (size_t)B * V * plane_tiles(H, W) * 3 * sizeof(double); }
 
 }  // namespace
 
@@ -487,12 +459,10 @@ extern "C" int hrn_observe(const float* hr, const float* shifts, float* views, f
     const size_t tiles = (size_t)tx * ty * (size_t)B * (size_t)V;
     HrnProfScope prof("observe", 0.0, (double)sr + 2.0 * (double)lr, stream);
     const dim3 grid(blocks_for(tiles)), block(kThreads);
-#define HRN_OB_LAUNCH(S_) hipLaunchKernelGGL((observe_kernel<S_, false>), grid, block, 0, stream, hr, (const float*)nullptr, (const float*)nullptr, \
-                                             (const float*)nullptr, shifts, views, valid, (double*)nullptr, tiles, V, H, W, tx, ty)
-    if (scale == 2) HRN_OB_LAUNCH(2);
-    else if (scale == 3) HRN_OB_LAUNCH(3);
-    else HRN_OB_LAUNCH(4);
-#undef HRN_OB_LAUNCH
+    hrn_by_scale(scale, [&](auto s) {
+        hipLaunchKernelGGL((observe_kernel<decltype(s)::value, false>), grid, block, 0, stream, hr, (const float*)nullptr, (const float*)nullptr,
+                           (const float*)nullptr, shifts, views, valid, (double*)nullptr, tiles, V, H, W, tx, ty);
+    });
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -517,12 +487,10 @@ extern "C" int hrn_consistency_residual(const float* hr, const float* lrs, const
     const size_t tiles = (size_t)tx * ty * (size_t)B * (size_t)V;
     HrnProfScope prof("consistency_residual", 0.0, (double)sr + (double)lr * (lr_masks ? 3 : 2) + (double)need, stream);
     const dim3 grid(blocks_for(tiles)), block(kThreads);
-#define HRN_OB_LAUNCH(S_) hipLaunchKernelGGL((observe_kernel<S_, true>), grid, block, 0, stream, hr, lrs, lr_masks, alphas, shifts, residual, \
-                                             (float*)nullptr, (double*)workspace, tiles, V, H, W, tx, ty)
-    if (scale == 2) HRN_OB_LAUNCH(2);
-    else if (scale == 3) HRN_OB_LAUNCH(3);
-    else HRN_OB_LAUNCH(4);
-#undef HRN_OB_LAUNCH
+    hrn_by_scale(scale, [&](auto s) {
+        hipLaunchKernelGGL((observe_kernel<decltype(s)::value, true>), grid, block, 0, stream, hr, lrs, lr_masks, alphas, shifts, residual,
+                           (float*)nullptr, (double*)workspace, tiles, V, H, W, tx, ty);
+    });
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -569,12 +537,10 @@ extern "C" int hrn_observe_adjoint(const float* residual, const float* lr_masks,
     const size_t tiles = (size_t)tx * ty * (size_t)B;
     HrnProfScope prof("observe_adjoint", 0.0, (double)lr * (lr_masks ? 2 : 1) + (double)sr * (x ? 2 : 1), stream);
     const dim3 grid(blocks_for(tiles)), block(kThreads);
-#define HRN_OB_LAUNCH(S_) hipLaunchKernelGGL(observe_adjoint_kernel<S_>, grid, block, 0, stream, residual, lr_masks, alphas, shifts, beta, coef, gain, \
-                                             x, out, tiles, V, H, W, tx, ty)
-    if (scale == 2) HRN_OB_LAUNCH(2);
-    else if (scale == 3) HRN_OB_LAUNCH(3);
-    else HRN_OB_LAUNCH(4);
-#undef HRN_OB_LAUNCH
+    hrn_by_scale(scale, [&](auto s) {
+        hipLaunchKernelGGL(observe_adjoint_kernel<decltype(s)::value>, grid, block, 0, stream, residual, lr_masks, alphas, shifts, beta, coef, gain,
+                           x, out, tiles, V, H, W, tx, ty);
+    });
     HRN_LAUNCH_CHECK();
     return 0;
 }

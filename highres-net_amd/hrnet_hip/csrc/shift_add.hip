@@ -10,7 +10,8 @@
 //
 // Forward: a workgroup of 256 threads owns TH x TW = 8 x 32 LR cells of one sample (S TH x S TW output pixels) and walks the views in
 // index order, in chunks of kChunk whose weights it forms first.  A view that does not count (alpha 0, a non-finite shift) is skipped - the
-// branch is uniform; the chunk's counting views are compacted into a list first.  Per view:
+// branch is uniform; the chunk's counting views are compacted into a list first.  (The tile, its walk, the test of a view and the list
+// are lr_tile.h's, shared with upsample.hip and observe.hip.)  Per view:
 //   1. rawx / rawm[TH + 4][TW + 4]  <- m x and m of the window whose origin is moved by (n_0y, n_0x); the mask, the frame test at the load
 //      (a thread's loads issued together, and the NEXT view's in flight during passes 2 and 3)
 //   2. hx / hm[TH + 4][S TW]        <- the column taps of both planes (five fmas per phase, slots ascending)
@@ -27,16 +28,14 @@
 // d_base is one element-wise kernel.  Neither kernel uses atomics; each element has one writer and one fixed order.
 //
 // Resources (gfx950, -Rpass-analysis=kernel-resource-usage) are stated in DESIGN.md section 7s.
-#include "../../../include/hrnet_hip.h"
-#include "kernels.h"
+#include "lr_tile.h"
 
 #include <cmath>
 
 namespace {
 
-constexpr int kTH = HRN_SHIFT_ADD_TILE_H, kTW = HRN_SHIFT_ADD_TILE_W, kThreads = 256, kChunk = 32;
-constexpr unsigned kMaxBlocks = 1u << 16;                // tiles are grid-strided beyond this
-constexpr int kMaxSide = 16384;
+constexpr int kChunk = 32;                               // views whose weights a workgroup forms at a time
+static_assert(kChunk <= 64, "compact_chunk takes a chunk in one wave");
 constexpr float kMinDen = 9.5367431640625e-07f;          // 2^-20
 constexpr float kMaxShift = 256.f;
 constexpr double kMinTap = 8.673617379884035e-19;        // 2^-60: a smaller tap weight is taken as 0
@@ -62,23 +61,6 @@ __device__ __forceinline__ float slot_weight(int S, int p, int j, float shift, f
     if (k < 0 || k > 3) return 0.f;
     const double w = tap_kernel((double)(k - 1) - ((double)d - (double)n), (double)sigma);
     return w < kMinTap ? 0.f : (float)w;                 // every product k_y k_x that is kept is a normal fp32 number
-}
-
-__device__ __forceinline__ bool view_counts(const float* alphas, const float* shifts, size_t bv) {
-    const float dy = shifts[2 * bv], dx = shifts[2 * bv + 1];
-    return (!alphas || alphas[bv] != 0.f) && isfinite(dy) && isfinite(dx);
-}
-
-struct TilePos { size_t n; int y0, x0; };
-
-__device__ __forceinline__ TilePos tile_pos(size_t tile, unsigned tiles_x, unsigned tiles_y) {
-    const size_t per = (size_t)tiles_x * tiles_y;
-    TilePos t;
-    t.n = tile / per;
-    const unsigned r = (unsigned)(tile - t.n * per);
-    t.y0 = (int)(r / tiles_x) * kTH;
-    t.x0 = (int)(r % tiles_x) * kTW;
-    return t;
 }
 
 // five slots ascending: w0 f0, then one fma per further slot
@@ -117,12 +99,8 @@ __global__ __launch_bounds__(kThreads) void shift_add_kernel(const float* __rest
                 w5[vi][ax][p][j] = slot_weight(S, p, j, sh, sigma);
                 if (p == 0 && j == 0) n0[vi][ax] = (int)floorf(tap_coord(S, 0, sh));
             }
-            if (tid < 64) {                              // the first wave compacts the chunk's counting views (kChunk <= 64)
-                const bool ok = tid < nv && view_counts(alphas, shifts, tp.n * (size_t)V + (size_t)(v0 + min(tid, nv - 1)));
-                const unsigned long long votes = __ballot(ok);
-                if (ok) list[__popcll(votes & ((1ull << tid) - 1ull))] = tid;
-                if (tid == 0) n_list = __popcll(votes);
-            }
+            if (tid < 64)                                // the first wave compacts the chunk's counting views (kChunk <= 64)
+                compact_chunk(tid < nv && view_counts(alphas, shifts, tp.n * (size_t)V + (size_t)(v0 + min(tid, nv - 1))), list, &n_list);
             __syncthreads();
             // The window of a view: tile + 4 rows / columns from (y0 + n_0y - 1, x0 + n_0x - 1).  A thread's LPT elements are loaded
             // together - value and mask unconditionally wherever the element is inside the frame, so no load waits for another - and
@@ -295,7 +273,6 @@ __global__ __launch_bounds__(kThreads) void shift_add_bwd_views_kernel(const flo
         __syncthreads();                                            // qs, tv and w5 are free for the next tile
     }
 }
-static_assert(kThreads == kTH * kTW, "the backward's last pass is one thread per LR pixel of the tile");
 
 // d_base = prior q, or d_out where the fallback holds
 __global__ __launch_bounds__(kThreads) void shift_add_bwd_base_kernel(const float* __restrict__ d_out, const float* __restrict__ weight,
@@ -306,29 +283,21 @@ __global__ __launch_bounds__(kThreads) void shift_add_bwd_base_kernel(const floa
     }
 }
 
-bool overlaps(const float* a, size_t na, const float* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na * sizeof(float), b0 = (uintptr_t)b, b1 = b0 + nb * sizeof(float);
-    return a0 < b1 && b0 < a1;
-}
-
 // what both entry points refuse; -> true, or false with the error set
 bool check_shape(const char* fn, int B, int V, int H, int W, int scale, float sigma, float prior, unsigned* tiles_x, unsigned* tiles_y) {
     *tiles_x = *tiles_y = 0;
     if (!(B > 0 && V > 0 && H > 0 && W > 0)) { hrn_set_error("%s: empty input B=%d V=%d H=%d W=%d", fn, B, V, H, W); return false; }
-    if (H > kMaxSide || W > kMaxSide) { hrn_set_error("%s: frames of 1..%d a side; got H=%d W=%d", fn, kMaxSide, H, W); return false; }
-    if (!hrn_scale_ok(scale)) { hrn_set_error("%s: scale must be 2, 3 or 4 (got %d)", fn, scale); return false; }
+    if (!check_side_scale(fn, "frames", H, W, scale)) return false;
     if (!(std::isfinite(sigma) && sigma >= 0.1f && sigma <= 1.f)) { hrn_set_error("%s: sigma must lie in [0.1, 1] (got %g)", fn, (double)sigma); return false; }
     if (!(std::isfinite(prior) && prior >= 0.f)) { hrn_set_error("%s: prior must be finite and >= 0 (got %g)", fn, (double)prior); return false; }
+    // 2^62 elements (upsample.hip's limit too; observe.hip stops at 2^60; no reason for the difference is recorded)
     if ((size_t)B > ((size_t)1 << 62) / ((size_t)V * scale * scale * H * W)) {
         hrn_set_error("%s: %d x %d frames of %d x %d exceed the address space", fn, B, V, H, W);
         return false;
     }
-    *tiles_y = (unsigned)((H + kTH - 1) / kTH);
-    *tiles_x = (unsigned)((W + kTW - 1) / kTW);
+    plane_tiles(H, W, tiles_x, tiles_y);
     return true;
 }
-
-unsigned blocks_for(size_t tiles) { return (unsigned)(tiles < kMaxBlocks ? tiles : kMaxBlocks); }
 
 }  // namespace
 
@@ -337,23 +306,21 @@ extern "C" int hrn_shift_add(const float* views, const float* view_masks, const 
     HRN_CHECK(views && shifts && out, -2, "hrn_shift_add: null argument");
     unsigned tx, ty;
     if (!check_shape("hrn_shift_add", B, V, H, W, scale, sigma, prior, &tx, &ty)) return -2;
-    const size_t lr = (size_t)B * V * H * W, sr = (size_t)B * H * W * scale * scale;
-    HRN_CHECK(!overlaps(views, lr, out, sr) && !(view_masks && overlaps(view_masks, lr, out, sr)), -2,
+    const size_t lr = (size_t)B * V * H * W, sr = (size_t)B * H * W * scale * scale, lrb = lr * sizeof(float), srb = sr * sizeof(float);
+    HRN_CHECK(!overlaps(views, lrb, out, srb) && !(view_masks && overlaps(view_masks, lrb, out, srb)), -2,
               "hrn_shift_add: views and view_masks must not alias out (only base may be out itself)");
-    HRN_CHECK(!base || base == out || !overlaps(base, sr, out, sr), -2, "hrn_shift_add: base must be out itself or apart from it");
-    HRN_CHECK(!weight || (!overlaps(weight, sr, out, sr) && !(base && overlaps(weight, sr, base, sr)) && !overlaps(views, lr, weight, sr) &&
-                          !(view_masks && overlaps(view_masks, lr, weight, sr))),
+    HRN_CHECK(!base || base == out || !overlaps(base, srb, out, srb), -2, "hrn_shift_add: base must be out itself or apart from it");
+    HRN_CHECK(!weight || (!overlaps(weight, srb, out, srb) && !(base && overlaps(weight, srb, base, srb)) && !overlaps(views, lrb, weight, srb) &&
+                          !(view_masks && overlaps(view_masks, lrb, weight, srb))),
               -2, "hrn_shift_add: weight must not alias another argument");
     hipStream_t stream = (hipStream_t)stream_;
     const size_t tiles = (size_t)tx * ty * (size_t)B;
     HrnProfScope prof("shift_add", 0.0, 4.0 * ((double)lr * (view_masks ? 2 : 1) + (double)sr * (1 + (base ? 1 : 0) + (weight ? 1 : 0))), stream);
     const dim3 grid(blocks_for(tiles)), block(kThreads);
-#define HRN_SA_LAUNCH(S_) hipLaunchKernelGGL(shift_add_kernel<S_>, grid, block, 0, stream, views, view_masks, alphas, shifts, base, out, weight, \
-                                             tiles, V, H, W, tx, ty, sigma, prior)
-    if (scale == 2) HRN_SA_LAUNCH(2);
-    else if (scale == 3) HRN_SA_LAUNCH(3);
-    else HRN_SA_LAUNCH(4);
-#undef HRN_SA_LAUNCH
+    hrn_by_scale(scale, [&](auto s) {
+        hipLaunchKernelGGL(shift_add_kernel<decltype(s)::value>, grid, block, 0, stream, views, view_masks, alphas, shifts, base, out, weight,
+                           tiles, V, H, W, tx, ty, sigma, prior);
+    });
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -364,23 +331,21 @@ extern "C" int hrn_shift_add_backward(const float* d_out, const float* weight, c
     HRN_CHECK(d_out && weight && shifts, -2, "hrn_shift_add_backward: null argument");
     unsigned tx, ty;
     if (!check_shape("hrn_shift_add_backward", B, V, H, W, scale, sigma, prior, &tx, &ty)) return -2;
-    const size_t lr = (size_t)B * V * H * W, sr = (size_t)B * H * W * scale * scale;
-    HRN_CHECK(!d_views || (!overlaps(d_views, lr, d_out, sr) && !overlaps(d_views, lr, weight, sr) &&
-                           !(view_masks && overlaps(d_views, lr, view_masks, lr))),
+    const size_t lr = (size_t)B * V * H * W, sr = (size_t)B * H * W * scale * scale, lrb = lr * sizeof(float), srb = sr * sizeof(float);
+    HRN_CHECK(!d_views || (!overlaps(d_views, lrb, d_out, srb) && !overlaps(d_views, lrb, weight, srb) &&
+                           !(view_masks && overlaps(d_views, lrb, view_masks, lrb))),
               -2, "hrn_shift_add_backward: d_views must not alias an input");
-    HRN_CHECK(!d_base || (!overlaps(d_base, sr, d_out, sr) && !overlaps(d_base, sr, weight, sr) && !(d_views && overlaps(d_base, sr, d_views, lr))),
+    HRN_CHECK(!d_base || (!overlaps(d_base, srb, d_out, srb) && !overlaps(d_base, srb, weight, srb) && !(d_views && overlaps(d_base, srb, d_views, lrb))),
               -2, "hrn_shift_add_backward: d_base must not alias d_out, weight or d_views");
     hipStream_t stream = (hipStream_t)stream_;
     HrnProfScope prof("shift_add_backward", 0.0, 4.0 * ((d_views ? (double)lr * (view_masks ? 2 : 1) : 0.0) + (double)sr * (2 + (d_base ? 1 : 0))), stream);
     if (d_views) {
         const size_t tiles = (size_t)tx * ty * (size_t)B * (size_t)V;
         const dim3 grid(blocks_for(tiles)), block(kThreads);
-#define HRN_SA_LAUNCH(S_) hipLaunchKernelGGL(shift_add_bwd_views_kernel<S_>, grid, block, 0, stream, d_out, weight, view_masks, alphas, shifts, \
-                                             d_views, tiles, V, H, W, tx, ty, sigma, prior)
-        if (scale == 2) HRN_SA_LAUNCH(2);
-        else if (scale == 3) HRN_SA_LAUNCH(3);
-        else HRN_SA_LAUNCH(4);
-#undef HRN_SA_LAUNCH
+        hrn_by_scale(scale, [&](auto s) {
+            hipLaunchKernelGGL(shift_add_bwd_views_kernel<decltype(s)::value>, grid, block, 0, stream, d_out, weight, view_masks, alphas, shifts,
+                               d_views, tiles, V, H, W, tx, ty, sigma, prior);
+        });
         HRN_LAUNCH_CHECK();
     }
     if (d_base) {

@@ -1,7 +1,8 @@
 // Bicubic x2 / x3 / x4 interpolation of f32 planes with an optional add, and its adjoint (hrn_upsample / hrn_upsample_backward; the
 // definition is in include/hrnet_hip.h).  (No counterpart in the reference, whose network synthesises the whole
 // image.)  Both kernels are separable passes through LDS over a tile of TH x TW = 8 x 32 LR pixels per workgroup of 256 threads; a
-// workgroup walks tiles (plane-major) with a grid stride, so any number of planes goes through one launch.  The S x 4 tap weights come by
+// workgroup walks tiles (plane-major) with a grid stride, so any number of planes goes through one launch (the tile, its walk and the
+// limits of a side: lr_tile.h, which shift_add.hip and observe.hip share).  The S x 4 tap weights come by
 // value (computed on the host in fp64, rounded to fp32): a phase's weights are scalars, and every tap index below is a compile-time
 // constant after unrolling - no array is indexed by a run-time value, no scratch.
 //
@@ -25,16 +26,11 @@
 // A cell outside the staged range is always outside the plane (the folds reach at most two cells past a border pixel), so it is skipped.
 //
 // Resources (gfx950, -Rpass-analysis=kernel-resource-usage) are stated in DESIGN.md section 7r.
-#include "../../../include/hrnet_hip.h"
-#include "kernels.h"
+#include "lr_tile.h"
 
 #include <cmath>
 
 namespace {
-
-constexpr int kTH = HRN_UPSAMPLE_TILE_H, kTW = HRN_UPSAMPLE_TILE_W, kThreads = 256;
-constexpr unsigned kMaxBlocks = 1u << 16;                // tiles are grid-strided beyond this
-constexpr int kMaxSide = 16384;
 
 struct UpWeights { float w[4][4]; };                     // [phase][tap], phases 0 .. S - 1
 
@@ -43,18 +39,6 @@ template <int S> __host__ __device__ constexpr int phase_shift(int p) { return 2
 // taps ascending: w0 f0, then one fma per further tap
 __device__ __forceinline__ float taps4(const float (&w)[4], float f0, float f1, float f2, float f3) {
     return fmaf(w[3], f3, fmaf(w[2], f2, fmaf(w[1], f1, w[0] * f0)));
-}
-
-struct TilePos { size_t n; int y0, x0; };
-
-__device__ __forceinline__ TilePos tile_pos(size_t tile, unsigned tiles_x, unsigned tiles_y) {
-    const size_t per = (size_t)tiles_x * tiles_y;
-    TilePos t;
-    t.n = tile / per;
-    const unsigned r = (unsigned)(tile - t.n * per);
-    t.y0 = (int)(r / tiles_x) * kTH;
-    t.x0 = (int)(r % tiles_x) * kTW;
-    return t;
 }
 
 // base and out may be the same pointer (no __restrict__ on either)
@@ -207,7 +191,6 @@ __global__ __launch_bounds__(kThreads) void upsample_bwd_kernel(const float* __r
         __syncthreads();                                                // tv and gs are free for the next tile
     }
 }
-static_assert(kThreads == kTH * kTW, "the backward's last pass is one thread per LR pixel of the tile");
 
 // Keys' cubic with parameter a: the weights of the taps i - 1 .. i + 2 at every phase, fp64 rounded to fp32 (hrnet_hip/upsample.py
 // restates this table)
@@ -226,29 +209,19 @@ UpWeights phase_weights(int S, float a_) {
     return w;
 }
 
-bool overlaps(const float* a, size_t na, const float* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na * sizeof(float), b0 = (uintptr_t)b, b1 = b0 + nb * sizeof(float);
-    return a0 < b1 && b0 < a1;
-}
-
 // what both entry points refuse; -> the number of tiles, or 0 with the error set
 size_t check_shape(const char* fn, int64_t n_planes, int H, int W, int scale, float a, unsigned* tiles_x, unsigned* tiles_y) {
     *tiles_x = *tiles_y = 0;
     if (!(n_planes > 0 && H > 0 && W > 0)) { hrn_set_error("%s: empty input n_planes=%lld H=%d W=%d", fn, (long long)n_planes, H, W); return 0; }
-    if (H > kMaxSide || W > kMaxSide) { hrn_set_error("%s: planes of 1..%d a side; got H=%d W=%d", fn, kMaxSide, H, W); return 0; }
-    if (!hrn_scale_ok(scale)) { hrn_set_error("%s: scale must be 2, 3 or 4 (got %d)", fn, scale); return 0; }
+    if (!check_side_scale(fn, "planes", H, W, scale)) return 0;
     if (!std::isfinite(a)) { hrn_set_error("%s: the kernel parameter a must be finite", fn); return 0; }
-    *tiles_y = (unsigned)((H + kTH - 1) / kTH);
-    *tiles_x = (unsigned)((W + kTW - 1) / kTW);
-    const size_t per = (size_t)*tiles_x * *tiles_y;
+    // 2^62 elements (shift_add.hip's limit too; observe.hip stops at 2^60; no reason for the difference is recorded)
     if ((size_t)n_planes > ((size_t)1 << 62) / ((size_t)scale * scale * H * W)) {
         hrn_set_error("%s: %lld planes of %d x %d exceed the address space", fn, (long long)n_planes, H, W);
         return 0;
     }
-    return per * (size_t)n_planes;
+    return plane_tiles(H, W, tiles_x, tiles_y) * (size_t)n_planes;
 }
-
-unsigned blocks_for(size_t tiles) { return (unsigned)(tiles < kMaxBlocks ? tiles : kMaxBlocks); }
 
 }  // namespace
 
@@ -258,16 +231,16 @@ extern "C" int hrn_upsample(const float* frames, const float* base, float* out, 
     unsigned tx, ty;
     const size_t tiles = check_shape("hrn_upsample", n_planes, H, W, scale, a, &tx, &ty);
     if (!tiles) return -2;
-    const size_t lr = (size_t)n_planes * H * W, sr = lr * scale * scale;
-    HRN_CHECK(!overlaps(frames, lr, out, sr), -2, "hrn_upsample: frames must not alias out (only base may be out itself)");
-    HRN_CHECK(!base || base == out || !overlaps(base, sr, out, sr), -2, "hrn_upsample: base must be out itself or apart from it");
+    const size_t lr = (size_t)n_planes * H * W, lrb = lr * sizeof(float), srb = lrb * scale * scale;
+    HRN_CHECK(!overlaps(frames, lrb, out, srb), -2, "hrn_upsample: frames must not alias out (only base may be out itself)");
+    HRN_CHECK(!base || base == out || !overlaps(base, srb, out, srb), -2, "hrn_upsample: base must be out itself or apart from it");
     hipStream_t stream = (hipStream_t)stream_;
     const UpWeights wt = phase_weights(scale, a);
     HrnProfScope prof("upsample", 0.0, (double)lr * 4 * (1 + (base ? 2 : 1) * scale * scale), stream);
     const dim3 grid(blocks_for(tiles)), block(kThreads);
-    if (scale == 2) hipLaunchKernelGGL(upsample_kernel<2>, grid, block, 0, stream, frames, base, out, tiles, H, W, tx, ty, wt);
-    else if (scale == 3) hipLaunchKernelGGL(upsample_kernel<3>, grid, block, 0, stream, frames, base, out, tiles, H, W, tx, ty, wt);
-    else hipLaunchKernelGGL(upsample_kernel<4>, grid, block, 0, stream, frames, base, out, tiles, H, W, tx, ty, wt);
+    hrn_by_scale(scale, [&](auto s) {
+        hipLaunchKernelGGL(upsample_kernel<decltype(s)::value>, grid, block, 0, stream, frames, base, out, tiles, H, W, tx, ty, wt);
+    });
     HRN_LAUNCH_CHECK();
     return 0;
 }
@@ -277,15 +250,15 @@ extern "C" int hrn_upsample_backward(const float* d_out, float* d_frames, int64_
     unsigned tx, ty;
     const size_t tiles = check_shape("hrn_upsample_backward", n_planes, H, W, scale, a, &tx, &ty);
     if (!tiles) return -2;
-    const size_t lr = (size_t)n_planes * H * W;
-    HRN_CHECK(!overlaps(d_frames, lr, d_out, lr * scale * scale), -2, "hrn_upsample_backward: d_frames must not alias d_out");
+    const size_t lr = (size_t)n_planes * H * W, lrb = lr * sizeof(float), srb = lrb * scale * scale;
+    HRN_CHECK(!overlaps(d_frames, lrb, d_out, srb), -2, "hrn_upsample_backward: d_frames must not alias d_out");
     hipStream_t stream = (hipStream_t)stream_;
     const UpWeights wt = phase_weights(scale, a);
     HrnProfScope prof("upsample_backward", 0.0, (double)lr * 4 * (1 + scale * scale), stream);
     const dim3 grid(blocks_for(tiles)), block(kThreads);
-    if (scale == 2) hipLaunchKernelGGL(upsample_bwd_kernel<2>, grid, block, 0, stream, d_out, d_frames, tiles, H, W, tx, ty, wt);
-    else if (scale == 3) hipLaunchKernelGGL(upsample_bwd_kernel<3>, grid, block, 0, stream, d_out, d_frames, tiles, H, W, tx, ty, wt);
-    else hipLaunchKernelGGL(upsample_bwd_kernel<4>, grid, block, 0, stream, d_out, d_frames, tiles, H, W, tx, ty, wt);
+    hrn_by_scale(scale, [&](auto s) {
+        hipLaunchKernelGGL(upsample_bwd_kernel<decltype(s)::value>, grid, block, 0, stream, d_out, d_frames, tiles, H, W, tx, ty, wt);
+    });
     HRN_LAUNCH_CHECK();
     return 0;
 }

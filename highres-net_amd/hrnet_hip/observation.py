@@ -143,17 +143,13 @@ def register_and_refine(lrs, lr_masks=None, alphas=None, scale=3, iters=10, step
         raise ValueError(f"init must be \"shift_add\" or \"bicubic\"; got {init!r}")
     iters, step, scale = check_iters(iters), check_step(step), check_scale(scale)
     registration._no_trace(search_kwargs, "register_and_refine returns no trace; call the search itself for it")
-    if isinstance(octaves, bool) or not isinstance(octaves, (int, np.integer)) or octaves < 0:
-        raise ValueError(f"octaves must be an integer >= 0; got {octaves!r}")
+    octaves = registration.check_octaves(octaves)
     from . import shiftadd, upsample
     with torch.no_grad():
         if init == "shift_add":
             sr0, _, shifts = shiftadd.register_and_add(lrs, lr_masks, alphas, scale=scale, octaves=octaves, **search_kwargs)
         else:
-            if octaves > 0:
-                shifts = registration.mncc_search_pyramid(lrs, lr_masks, octaves=int(octaves), **search_kwargs)
-            else:
-                shifts = registration.mncc_search_scene(lrs, lr_masks, **search_kwargs)
+            shifts = registration.search_global(lrs, lr_masks, octaves, **search_kwargs)
             sr0 = upsample.baseline(lrs, alphas, lr_masks, scale)[:, 0]
         sr = back_project(sr0, lrs, shifts, lr_masks, alphas, scale, iters, step)
     return sr, shifts

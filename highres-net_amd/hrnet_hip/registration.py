@@ -28,6 +28,7 @@ resampled by the bilinear field between the blocks' centres.  `local_blocks` is 
 `reduce2`, `mncc_search_pyramid` and `register_scene_pyramid` take the scene search beyond its reach of `radius` <= 4 pixels (DESIGN.md
 section 7j): a masked image pyramid of `octaves` 2:1 reductions, the coarsest octave searched from (0, 0) and every finer one from twice
 the shift of the octave above - `mncc_search_scene(init=...)`.  The reach is radius * 2**octaves pixels."""
+import numpy as np
 import torch
 
 from . import binding
@@ -277,8 +278,7 @@ def register_scene_local(lrs, lr_masks=None, block=128, local_levels=4, local_ra
     _no_trace(search_kwargs, "register_scene_local returns no trace: call mncc_search_scene and mncc_search_local(..., return_trace=True)")
     _local_args(block, min_valid)
     _search_args(search_kwargs.get("points_per_dim", 7), local_levels, local_radius)
-    octaves = binding.mncc_int("octaves", octaves, binding.MNCC_OCTAVES)
-    shifts = mncc_search_pyramid(lrs, lr_masks, octaves=octaves, **search_kwargs) if octaves else mncc_search_scene(lrs, lr_masks, **search_kwargs)
+    shifts = search_global(lrs, lr_masks, binding.mncc_int("octaves", octaves, binding.MNCC_OCTAVES), **search_kwargs)
     local = {k: search_kwargs[k] for k in ("ref", "ref_mask", "points_per_dim") if k in search_kwargs}
     field = mncc_search_local(lrs, lr_masks, block=block, init=shifts, levels=local_levels, radius=local_radius, min_valid=min_valid, **local)
     registered, valid = shift_field(lrs, lr_masks, field, block)
@@ -337,6 +337,21 @@ def mncc_search_pyramid(lrs, lr_masks=None, ref=None, ref_mask=None, octaves=2, 
     _on_device(lrs=lrs, lr_masks=lr_masks, ref=ref, ref_mask=ref_mask)
     shifts, trace = torch.ops.hrnet_hip.mncc_search_pyramid(ref, ref_mask, lrs, lr_masks, octaves, P, levels, radius, coarse_levels, refine_radius)
     return (shifts, trace) if return_trace else shifts
+
+
+def check_octaves(octaves):
+    """the `octaves` of a function that registers and then fuses (shiftadd.register_and_add, observation.register_and_refine)"""
+    if isinstance(octaves, bool) or not isinstance(octaves, (int, np.integer)) or octaves < 0:
+        raise ValueError(f"octaves must be an integer >= 0; got {octaves!r}")
+    return int(octaves)
+
+
+def search_global(lrs, lr_masks, octaves, **search_kwargs):
+    """-> shifts (B,V,2): the global shift of every view against the first one (or search_kwargs' ref) - `mncc_search_pyramid` over
+    `octaves` octaves if octaves > 0, else `mncc_search_scene`.  octaves: an int the caller has checked."""
+    if octaves:
+        return mncc_search_pyramid(lrs, lr_masks, octaves=octaves, **search_kwargs)
+    return mncc_search_scene(lrs, lr_masks, **search_kwargs)
 
 
 def register_scene_pyramid(lrs, lr_masks=None, **search_kwargs):

@@ -105,12 +105,8 @@ def register_and_add(lrs, lr_masks=None, alphas=None, scale=3, octaves=0, sigma=
     and fused by `shift_and_add`.  search_kwargs go to the search (points_per_dim, levels, radius, ...); frames are 16..16384 a side,
     the search's limits.  The shifts are found without a gradient; sr is differentiable in lrs at those shifts."""
     registration._no_trace(search_kwargs, "register_and_add returns no trace; call the search itself for it")
-    if isinstance(octaves, bool) or not isinstance(octaves, (int, np.integer)) or octaves < 0:
-        raise ValueError(f"octaves must be an integer >= 0; got {octaves!r}")
+    octaves = registration.check_octaves(octaves)
     with torch.no_grad():
-        if octaves > 0:
-            shifts = registration.mncc_search_pyramid(lrs, lr_masks, octaves=int(octaves), **search_kwargs)
-        else:
-            shifts = registration.mncc_search_scene(lrs, lr_masks, **search_kwargs)
+        shifts = registration.search_global(lrs, lr_masks, octaves, **search_kwargs)
     sr, weight = shift_and_add(lrs, shifts, lr_masks, alphas, scale, sigma, prior, base, return_weight=True)
     return sr, weight, shifts
