@@ -114,6 +114,14 @@ SIGNATURES = {
     "hrn_consistency_residual": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_size_t] + [_c.c_int] * 5 + [_c.c_void_p]),
     "hrn_consistency_finish": (_c.c_int, [_c.c_void_p, _c.c_size_t] + [_c.c_void_p] * 7 + [_c.c_int] * 5 + [_c.c_float, _c.c_int, _c.c_void_p]),
     "hrn_observe_adjoint": (_c.c_int, [_c.c_void_p] * 9 + [_c.c_int] * 5 + [_c.c_void_p]),
+    "hrn_robust_workspace_bytes": (_c.c_size_t, [_c.c_int] * 4),
+    "hrn_robust_sums": (_c.c_int, [_c.c_void_p] * 6 + [_c.c_size_t] + [_c.c_int] * 5 + [_c.c_float, _c.c_void_p]),
+    "hrn_robust_finish": (_c.c_int, [_c.c_void_p, _c.c_size_t] + [_c.c_void_p] * 4 + [_c.c_int] * 5 + [_c.c_void_p]),
+    "hrn_robust_apply": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_int] * 5 + [_c.c_float, _c.c_void_p]),
+    "hrn_btv_step": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 4 + [_c.c_float, _c.c_float, _c.c_void_p]),
+    "hrn_btv_backward": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 4 + [_c.c_float, _c.c_float, _c.c_void_p]),
+    "hrn_btv_workspace_bytes": (_c.c_size_t, [_c.c_int] * 3),
+    "hrn_btv_value": (_c.c_int, [_c.c_void_p] * 3 + [_c.c_size_t] + [_c.c_int] * 4 + [_c.c_float] * 3 + [_c.c_void_p]),
     "hrn_hrnet_forward_ref": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                          _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "hrn_hrnet_forward_train_ref": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
@@ -1667,6 +1675,132 @@ def back_project(sr0, lrs, lr_masks, alphas, shifts, scale, iters, step, brightn
     return x, losses
 
 
+# --------------------------------------------------------------------------- robust, regularised reconstruction (robust_sr.hip)
+BTV_TILE = (16, 64)           # HRN_BTV_TILE_H x HRN_BTV_TILE_W: the HR pixels a workgroup owns
+BTV_MAX_P = 3                 # the window's radius is 1 .. 3
+BTV_MAX_SIDE = 49152          # planes of 1 .. 3 x 16384 a side
+DATA_EIGENVALUE = 1.02        # the bound on the data operator's largest eigenvalue
+
+
+def btv_weight_sum(P, alpha):
+    """W = sum over (l, m) != (0, 0), |l|, |m| <= P, of alpha^(|l| + |m|)"""
+    return sum(float(alpha) ** (abs(l) + abs(m)) for l in range(-P, P + 1) for m in range(-P, P + 1) if (l, m) != (0, 0))
+
+
+def step_bound(step, lam, P, alpha, eps):
+    """step (1.02 + 4 lam W / eps): the iteration of `reconstruct` is stable while this is below 2"""
+    return float(step) * (DATA_EIGENVALUE + 4.0 * float(lam) * btv_weight_sum(P, alpha) / float(eps))
+
+
+def btv_step(x, c, P, alpha, eps, out):
+    """hrn_btv_step: x (planes,SH,SW), c (planes,) -> out = x - c g(x); out is another tensor than x."""
+    lib = load_library()
+    n, SH, SW = x.shape
+    with torch.cuda.device(x.device):
+        _check(lib.hrn_btv_step(_ptr(x), _ptr(c), _ptr(out), n, SH, SW, int(P), float(alpha), float(eps), _stream()), "hrn_btv_step")
+    return out
+
+
+def btv_backward(x, gain, P, alpha, eps):
+    """hrn_btv_backward: x (planes,SH,SW), gain (planes,) -> gain g(x), a new tensor."""
+    lib = load_library()
+    n, SH, SW = x.shape
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _check(lib.hrn_btv_backward(_ptr(x), _ptr(gain), _ptr(out), n, SH, SW, int(P), float(alpha), float(eps), _stream()), "hrn_btv_backward")
+    return out
+
+
+def btv_workspace(n, SH, SW, device):
+    nbytes = int(load_library().hrn_btv_workspace_bytes(n, SH, SW))
+    if nbytes == 0:
+        raise HrnetHipError(f"hrn_btv_workspace_bytes refuses planes={n} SH={SH} SW={SW}")
+    return torch.empty((nbytes // 8,), dtype=torch.float64, device=device)
+
+
+def btv_value(x, P, alpha, eps, gain=1.0, out=None, workspace=None):
+    """hrn_btv_value: x (planes,SH,SW) -> (planes,) f32 = gain R(x) / (SH SW).  out, workspace: reused when given."""
+    lib = load_library()
+    n, SH, SW = x.shape
+    if out is None:
+        out = torch.empty((n,), dtype=torch.float32, device=x.device)
+    if workspace is None:
+        workspace = btv_workspace(n, SH, SW, x.device)
+    with torch.cuda.device(x.device):
+        _check(lib.hrn_btv_value(_ptr(x), _ptr(out), _ptr(workspace), workspace.numel() * 8, n, SH, SW, int(P), float(alpha), float(eps),
+                                 float(gain), _stream()), "hrn_btv_value")
+    return out
+
+
+class RobustState:
+    """What the robust data step writes, allocated once per reconstruction: the tiles' workspace, beta_prev and beta (B,V) (swapped after
+    every iteration), the inlier fraction (B,V) and the re-weighted residual (B,V,H,W) that the adjoint reads."""
+
+    def __init__(self, B, V, H, W, device):
+        lib = load_library()
+        self.shape = (B, V, H, W)
+        self.ws_bytes = int(lib.hrn_robust_workspace_bytes(B, V, H, W))
+        if self.ws_bytes == 0:
+            raise HrnetHipError(f"hrn_robust_workspace_bytes refuses B={B} V={V} H={H} W={W}")
+        f32 = dict(dtype=torch.float32, device=device)
+        self.workspace = torch.empty((self.ws_bytes // 8,), dtype=torch.float64, device=device)
+        self.beta_prev = torch.empty((B, V), **f32)
+        self.beta = torch.empty((B, V), **f32)
+        self.inlier = torch.empty((B, V), **f32)
+        self.weighted = torch.empty((B, V, H, W), **f32)
+
+
+def robust_step(cstate, rstate, lr_masks, alphas, shifts, scale, delta, brightness, loss):
+    """hrn_robust_sums, hrn_robust_finish and hrn_robust_apply on the residual in `cstate` (a ConsistencyState that consistency_residual
+    has filled): rstate.beta, .inlier, .weighted and `loss` (B,) are written; rstate.beta_prev is read."""
+    lib = load_library()
+    B, V, H, W = rstate.shape
+    with torch.cuda.device(shifts.device):
+        _check(lib.hrn_robust_sums(_ptr(cstate.residual), _opt_ptr(lr_masks), _opt_ptr(alphas), _ptr(shifts), _ptr(rstate.beta_prev),
+                                   _ptr(rstate.workspace), rstate.ws_bytes, B, V, H, W, int(scale), float(delta), _stream()), "hrn_robust_sums")
+        _check(lib.hrn_robust_finish(_ptr(rstate.workspace), rstate.ws_bytes, _ptr(cstate.count), _ptr(rstate.beta), _ptr(rstate.inlier),
+                                     _ptr(loss), B, V, H, W, int(bool(brightness)), _stream()), "hrn_robust_finish")
+        _check(lib.hrn_robust_apply(_ptr(cstate.residual), _opt_ptr(lr_masks), _opt_ptr(alphas), _ptr(shifts), _ptr(rstate.beta_prev),
+                                    _ptr(rstate.beta), _ptr(rstate.weighted), B, V, H, W, int(scale), float(delta), _stream()),
+               "hrn_robust_apply")
+
+
+def reconstruct(sr0, lrs, lr_masks, alphas, shifts, scale, iters, step, brightness, robust, delta, lam, P, alpha, eps, want_trace=True):
+    """iters iterations from sr0 (B,SH,SW) on the current stream, nothing returning to the host: the data step - back_project's three
+    launches, or with `robust` residual, finish, the three robust launches and the adjoint of the re-weighted residual - and with lam > 0
+    the bilateral-TV half-step between two frames -> (sr, trace (iters,B,3)): the plain consistency loss, the weighted loss (the plain one
+    again without `robust`) and lam R / pixels (0 without the prior, or when want_trace is off) of the frame each iteration STARTED from."""
+    B, V, H, W = lrs.shape
+    dev = sr0.device
+    x = sr0.clone()
+    plain, weighted, prior = (torch.zeros((iters, B), dtype=torch.float32, device=dev) for _ in range(3))
+    if iters:
+        state = ConsistencyState(B, V, H, W, dev)
+        rstate = RobustState(B, V, H, W, dev) if robust else None
+        if lam > 0:
+            y = torch.empty_like(x)
+            c = torch.full((B,), float(step) * float(lam), dtype=torch.float32, device=dev)
+            ws = btv_workspace(B, x.shape[1], x.shape[2], dev) if want_trace else None
+        for t in range(iters):
+            if lam > 0 and want_trace:
+                btv_value(x, P, alpha, eps, gain=lam, out=prior[t], workspace=ws)
+            consistency_residual(x, lrs, lr_masks, alphas, shifts, scale, step, brightness, state, plain[t])
+            if robust:
+                if t == 0:
+                    rstate.beta_prev.copy_(state.beta)
+                robust_step(state, rstate, lr_masks, alphas, shifts, scale, delta, brightness, weighted[t])
+                observe_adjoint(rstate.weighted, lr_masks, alphas, shifts, None, state.coef_step, None, x, scale, out=x)
+                rstate.beta_prev, rstate.beta = rstate.beta, rstate.beta_prev
+            else:
+                observe_adjoint(state.residual, lr_masks, alphas, shifts, state.beta, state.coef_step, None, x, scale, out=x)
+            if lam > 0:
+                btv_step(x, c, P, alpha, eps, out=y)
+                x, y = y, x
+        if not robust:
+            weighted = plain.clone()
+    return x, torch.stack((plain, weighted, prior), dim=2)
+
+
 # --------------------------------------------------------------------------- PyTorch-ROCm custom ops (north_star: "exposed to Python as
 # PyTorch-ROCm custom ops"): the inference entry points are registered with the dispatcher as torch.ops.hrnet_hip.*, with fake
 # (meta) implementations, so that they are visible to torch.compile / export and to anyone calling through torch.ops.  Each is a
@@ -1928,6 +2062,62 @@ def _op_back_project(sr0: torch.Tensor, lrs: torch.Tensor, lr_masks: Optional[to
 @_op_back_project.register_fake
 def _(sr0, lrs, lr_masks, alphas, shifts, scale, iters, step, brightness):
     return sr0.new_empty(tuple(sr0.shape), dtype=torch.float32), sr0.new_empty((iters, sr0.shape[0]), dtype=torch.float32)
+
+
+# Robust, regularised reconstruction (robust_sr.hip).  reconstruct carries no gradient.  btv_loss_train is R / pixels per plane; its
+# autograd formula is btv_loss_backward, the same kernel as the half-step with out = gain g.
+@torch.library.custom_op("hrnet_hip::reconstruct", mutates_args=(), device_types="cuda")
+def _op_reconstruct(sr0: torch.Tensor, lrs: torch.Tensor, lr_masks: Optional[torch.Tensor], alphas: Optional[torch.Tensor],
+                    shifts: torch.Tensor, scale: int, iters: int, step: float, brightness: bool, robust: bool, delta: float, lam: float,
+                    P: int, alpha: float, eps: float, trace: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (sr (B,SH,SW) after `iters` iterations from sr0, trace (iters,B,3)); robust: Welsch weights; no gradient."""
+    return reconstruct(_f32c(sr0), _f32c(lrs), _f32c(lr_masks), _f32c(alphas), _f32c(shifts), scale, iters, step, brightness, robust, delta, lam,
+                       P, alpha, eps, trace)
+
+
+@_op_reconstruct.register_fake
+def _(sr0, lrs, lr_masks, alphas, shifts, scale, iters, step, brightness, robust, delta, lam, P, alpha, eps, trace):
+    return sr0.new_empty(tuple(sr0.shape), dtype=torch.float32), sr0.new_empty((iters, sr0.shape[0], 3), dtype=torch.float32)
+
+
+@torch.library.custom_op("hrnet_hip::btv_loss_train", mutates_args=(), device_types="cuda")
+def _op_btv_loss_train(srs: torch.Tensor, P: int, alpha: float, eps: float) -> torch.Tensor:
+    """srs (B,SH,SW) -> (B,) = R(srs_b) / (SH SW) (hrn_btv_value)."""
+    return btv_value(_f32c(srs), P, alpha, eps)
+
+
+@_op_btv_loss_train.register_fake
+def _(srs, P, alpha, eps):
+    return srs.new_empty((srs.shape[0],), dtype=torch.float32)
+
+
+@torch.library.custom_op("hrnet_hip::btv_loss_backward", mutates_args=(), device_types="cuda")
+def _op_btv_loss_backward(d_loss: torch.Tensor, srs: torch.Tensor, P: int, alpha: float, eps: float) -> torch.Tensor:
+    """-> d_srs (B,SH,SW) = (d_loss_b / (SH SW)) g(srs_b) (hrn_btv_backward)."""
+    srs = _f32c(srs)
+    gain = (_f32c(d_loss) / float(srs.shape[1] * srs.shape[2])).contiguous()
+    return btv_backward(srs, gain, P, alpha, eps)
+
+
+@_op_btv_loss_backward.register_fake
+def _(d_loss, srs, P, alpha, eps):
+    return srs.new_empty(tuple(srs.shape), dtype=torch.float32)
+
+
+def _btv_setup(ctx, inputs, output):
+    srs, ctx.P, ctx.alpha, ctx.eps = inputs
+    ctx.srs_dtype = srs.dtype
+    ctx.save_for_backward(srs)
+
+
+def _btv_backward(ctx, d_loss):
+    if not ctx.needs_input_grad[0]:
+        return None, None, None, None
+    (srs,) = ctx.saved_tensors
+    return torch.ops.hrnet_hip.btv_loss_backward(d_loss, srs, ctx.P, ctx.alpha, ctx.eps).to(ctx.srs_dtype), None, None, None
+
+
+_op_btv_loss_train.register_autograd(_btv_backward, setup_context=_btv_setup)
 
 
 @torch.library.custom_op("hrnet_hip::lanczos_shift", mutates_args=(), device_types="cuda")

@@ -35,7 +35,7 @@
 //   then out = coef G, or x - coef G (x may be out: a thread reads what it writes).  One writer per element, no atomics.
 //
 // Resources (gfx950, -Rpass-analysis=kernel-resource-usage) are stated in DESIGN.md section 7t.
-#include "lr_tile.h"
+#include "observe_geom.h"
 
 #include <cmath>
 
@@ -43,21 +43,11 @@ namespace {
 
 constexpr int kChunk = 32;                               // views whose weights a workgroup of the adjoint forms at a time
 static_assert(kChunk <= 64, "compact_chunk takes a chunk in one wave");
-constexpr float kMaxCoord = 256.f;                       // RG_DMAX of mncc_common.h: the clamp of split_and_taps
 constexpr int kFinishThreads = 1024;
 
 constexpr int plane_stride(int S) { return S == 2 ? 48 : (S == 3 ? 43 : 40); }
 
-// c = -S d of a shift component: fp64 product, rounded to fp32 (not yet clamped)
-__device__ __forceinline__ float hr_coord(int S, float d) { return (float)(-(double)S * (double)d); }
-
-// the split of split_and_taps: the clamp (a NaN goes to a finite value), n = floor, f = c - n exact in fp64
-__device__ __forceinline__ void split64(float c, int* n, double* f) {
-    const float cc = fminf(fmaxf(c, -kMaxCoord), kMaxCoord);
-    const double fl = floor((double)cc);
-    *n = (int)fl;
-    *f = (double)cc - fl;
-}
+// (hr_coord, split64, view_in_reach and sample_valid are observe_geom.h's, shared with robust_sr.hip)
 
 // tap o (-2 .. 3) of split_and_taps before its normalisation, fp64
 __device__ __forceinline__ double tap64(int o, double f) {
@@ -81,19 +71,6 @@ __device__ __forceinline__ float box_weight(const double* k, int j) {
         if (o >= 0 && o < 6) w += k[o] / sum;
     }
     return (float)(w / (double)S);
-}
-
-// a view that counts (view_counts of lr_tile.h) is IN REACH when neither coordinate was clamped
-template <int S>
-__device__ __forceinline__ bool view_in_reach(const float* shifts, size_t bv) {
-    return fabsf(hr_coord(S, shifts[2 * bv])) < kMaxCoord && fabsf(hr_coord(S, shifts[2 * bv + 1])) < kMaxCoord;
-}
-
-// sample i of an axis of L LR samples is valid: its S + 5 HR rows S i + n - 2 .. S i + n + S + 2 lie inside 0 .. S L - 1
-template <int S>
-__device__ __forceinline__ bool sample_valid(int i, int n, int L) {
-    const long lo = (long)S * i + n - 2;
-    return i >= 0 && i < L && lo >= 0 && lo + S + 4 <= (long)S * L - 1;
 }
 
 __device__ __forceinline__ int floor_div(int a, int b) { return (a >= 0 ? a : a - b + 1) / b; }

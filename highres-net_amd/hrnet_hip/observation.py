@@ -134,14 +134,101 @@ def back_project(sr0, lrs, shifts, lr_masks=None, alphas=None, scale=3, iters=10
     return (sr, losses) if return_loss else sr
 
 
-def register_and_refine(lrs, lr_masks=None, alphas=None, scale=3, iters=10, step=1.0, init="shift_add", octaves=0, **search_kwargs):
+def _number(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
+        raise TypeError(f"{name} must be a number; got {v!r}")
+    if not np.isfinite(v):
+        raise ValueError(f"{name} must be finite; got {v}")
+    return float(v)
+
+
+def check_btv(P, alpha, eps):
+    """the bilateral-TV window: P in 1..3, 0 < alpha <= 1, eps > 0 -> (P, alpha, eps)"""
+    if isinstance(P, bool) or not isinstance(P, (int, np.integer)) or not 1 <= P <= binding.BTV_MAX_P:
+        raise ValueError(f"P must be an integer in 1..{binding.BTV_MAX_P}; got {P!r}")
+    alpha, eps = _number("alpha", alpha), _number("eps", eps)
+    if not 0.0 < alpha <= 1.0:
+        raise ValueError(f"alpha must lie in (0, 1]; got {alpha}")
+    if not eps > 0.0:
+        raise ValueError(f"eps must be positive; got {eps}")
+    return int(P), alpha, eps
+
+
+def check_reconstruct(step, robust, delta, lam, P, alpha, eps):
+    """the options of `reconstruct` -> (step, robust as a bool, delta, lam, P, alpha, eps).  The step-size rule: the Hessian of lam R is
+    bounded by 4 lam W / eps, W = sum_{(l,m) != 0} alpha^(|l|+|m|), the data operator's largest eigenvalue by 1.02, so
+    step (1.02 + 4 lam W / eps) must stay below 2."""
+    step = check_step(step)
+    if robust not in (None, "welsch"):
+        raise ValueError(f"robust must be None or \"welsch\"; got {robust!r}")
+    delta, lam = _number("delta", delta), _number("lam", lam)
+    if not delta > 0.0:
+        raise ValueError(f"delta must be positive; got {delta}")
+    if lam < 0.0:
+        raise ValueError(f"lam must be >= 0; got {lam}")
+    P, alpha, eps = check_btv(P, alpha, eps)
+    if lam > 0.0:
+        W = binding.btv_weight_sum(P, alpha)
+        bound = binding.step_bound(step, lam, P, alpha, eps)
+        if not bound < 2.0:
+            raise ValueError(f"step (1.02 + 4 lam W / eps) must be below 2 for the iteration to be stable; got {bound:.4g} from step={step}, "
+                             f"lam={lam}, W={W:.4g} (P={P}, alpha={alpha}), eps={eps}: lower step or lam, or raise eps")
+    return step, robust is not None, delta, lam, P, alpha, eps
+
+
+def reconstruct(sr0, lrs, shifts, lr_masks=None, alphas=None, scale=3, iters=30, step=1.0, brightness=True, robust="welsch", delta=0.1,
+                lam=4e-4, P=2, alpha=0.7, eps=0.02, return_trace=False):
+    """sr0 (B,SH,SW) or (B,1,SH,SW) -> sr of the same shape after `iters` iterations of a robust, regularised back-projection.
+    Each iteration takes a data step and, with lam > 0, a bilateral-TV half-step evaluated at the data step's result (a splitting scheme):
+      data step, robust="welsch": w = counted exp(-((e + beta_prev) / delta)^2), beta_v = -sum w e / sum w (0 without `brightness`),
+        x' = x - step (scale^2 / V_b) sum_v A_v^T (w (e + beta_v)); beta_prev starts as the plain mean bias of the first iteration.  A
+        redescending weight: a pixel far from the model (an unmasked cloud) loses its pull, and the bias is not contaminated by it.
+        robust=None: back_project's step.  A sample in which nothing counts takes no data step.
+      prior: x'' = x' - step lam g(x'), g the gradient of R(x) = sum_{(l,m) != 0, |l|,|m| <= P} alpha^(|l|+|m|) sum_p phi(x_p - x_{p-(l,m)}),
+        phi(t) = sqrt(t^2 + eps^2) - eps, pairs inside the frame only.  A sample in which nothing counts STILL takes this half-step.
+    step (1.02 + 4 lam W / eps) must stay below 2 (ValueError otherwise; W = sum of the window's weights, 10.42 for P=2, alpha=0.7).
+    robust=None, lam=0 returns back_project's bits; iters = 0 returns sr0's bits.  return_trace: also trace (iters,B,3) on the device =
+    (the plain consistency loss, the weighted loss sum w (e + beta_prev)^2 / sum w, lam R / pixels) of the frame each iteration started
+    from.  No gradient.  Per iteration 3 launches, 6 with robust, 1 more with lam > 0 (2 more with return_trace), on the current stream."""
+    iters, brightness = check_iters(iters), _flag("brightness", brightness)
+    return_trace = _flag("return_trace", return_trace)
+    step, robust, delta, lam, P, alpha, eps = check_reconstruct(step, robust, delta, lam, P, alpha, eps)
+    srs3, channel, scale = _check_views(sr0, lrs, shifts, lr_masks, alphas, scale, what="sr0")
+    with torch.no_grad():
+        sr, trace = torch.ops.hrnet_hip.reconstruct(srs3, lrs, lr_masks, alphas, shifts, scale, iters, step, brightness, robust, delta, lam, P,
+                                                    alpha, eps, return_trace)
+    sr = sr.unsqueeze(1) if channel else sr
+    return (sr, trace) if return_trace else sr
+
+
+def btv_loss(srs, P=2, alpha=0.7, eps=0.02):
+    """srs (B,SH,SW) or (B,1,SH,SW) -> (B,) = R(srs_b) / (SH SW), the bilateral-TV prior of `reconstruct` as a training regulariser beside
+    any loss here.  Differentiable in srs (the half-step's kernel with out = gain g).  Sides of 1..49152."""
+    _tensor("srs", srs)
+    P, alpha, eps = check_btv(P, alpha, eps)
+    if srs.dim() == 4 and srs.shape[1] == 1:
+        srs = srs[:, 0]
+    if srs.dim() != 3 or srs.numel() == 0:
+        raise ValueError(f"srs must be a non-empty (B,SH,SW) or (B,1,SH,SW); got {tuple(srs.shape)}")
+    if max(srs.shape[1:]) > binding.BTV_MAX_SIDE:
+        raise ValueError(f"planes of 1..{binding.BTV_MAX_SIDE} a side; got {tuple(srs.shape)}")
+    if not srs.is_floating_point():
+        raise TypeError("srs must be a floating-point tensor")
+    _on_device(srs, srs=srs)
+    return torch.ops.hrnet_hip.btv_loss_train(srs, P, alpha, eps)
+
+
+def register_and_refine(lrs, lr_masks=None, alphas=None, scale=3, iters=10, step=1.0, init="shift_add", octaves=0, robust=None, delta=0.1,
+                        lam=0.0, P=2, alpha=0.7, eps=0.02, **search_kwargs):
     """lrs (B,V,H,W)[, lr_masks, alphas] -> (sr (B, scale H, scale W), shifts (B,V,2)): the views registered against the first one, a
     start - init="shift_add": `shiftadd.register_and_add`; "bicubic": the search (`registration.mncc_search_scene`, or with octaves > 0
-    `mncc_search_pyramid`) and `upsample.baseline` - and `iters` back-projection steps from it.  search_kwargs go to the search; frames are
-    16..16384 a side, the search's limits.  No gradient."""
+    `mncc_search_pyramid`) and `upsample.baseline` - and `iters` back-projection steps from it; with robust="welsch" or lam > 0 the
+    iterations are `reconstruct`'s (delta, lam, P, alpha, eps are its).  search_kwargs go to the search; frames are 16..16384 a side, the
+    search's limits.  No gradient."""
     if init not in ("shift_add", "bicubic"):
         raise ValueError(f"init must be \"shift_add\" or \"bicubic\"; got {init!r}")
     iters, step, scale = check_iters(iters), check_step(step), check_scale(scale)
+    check_reconstruct(step, robust, delta, lam, P, alpha, eps)
     registration._no_trace(search_kwargs, "register_and_refine returns no trace; call the search itself for it")
     octaves = registration.check_octaves(octaves)
     from . import shiftadd, upsample
@@ -151,5 +238,8 @@ def register_and_refine(lrs, lr_masks=None, alphas=None, scale=3, iters=10, step
         else:
             shifts = registration.search_global(lrs, lr_masks, octaves, **search_kwargs)
             sr0 = upsample.baseline(lrs, alphas, lr_masks, scale)[:, 0]
-        sr = back_project(sr0, lrs, shifts, lr_masks, alphas, scale, iters, step)
+        if robust is None and lam == 0:
+            sr = back_project(sr0, lrs, shifts, lr_masks, alphas, scale, iters, step)
+        else:
+            sr = reconstruct(sr0, lrs, shifts, lr_masks, alphas, scale, iters, step, True, robust, delta, lam, P, alpha, eps)
     return sr, shifts

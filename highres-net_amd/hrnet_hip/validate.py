@@ -133,10 +133,14 @@ def baseline_table(batches, border_w=3, a=-0.75, n_ref=9, method="bicubic", **me
     **method_kwargs)` (the views registered against the first one, then shift-and-add over the bicubic base; a and n_ref are not used).
     method="back_projection" scores `observation.register_and_refine(lrs, lr_masks, alphas, scale=S, **method_kwargs)`: the same
     registration, then iterative back-projection against the views (iters, step, init).
-    A batch may carry lr_masks (B,V,H,W) as a sixth item, which those two methods use (None: all clear); the bicubic method does not read
+    method="robust" scores the same call with robust="welsch" and lam=4e-4 unless method_kwargs set them: `observation.reconstruct`'s
+    Welsch-weighted data term and bilateral-TV prior (delta, lam, P, alpha, eps).
+    A batch may carry lr_masks (B,V,H,W) as a sixth item, which those methods use (None: all clear); the bicubic method does not read
     it."""
-    if method not in ("bicubic", "shift_add", "back_projection"):
-        raise ValueError(f"method must be \"bicubic\", \"shift_add\" or \"back_projection\"; got {method!r}")
+    if method not in ("bicubic", "shift_add", "back_projection", "robust"):
+        raise ValueError(f"method must be \"bicubic\", \"shift_add\", \"back_projection\" or \"robust\"; got {method!r}")
+    if method == "robust":
+        method_kwargs = dict(dict(robust="welsch", lam=4e-4), **method_kwargs)
     if method == "bicubic" and method_kwargs:
         raise TypeError(f"method=\"bicubic\" takes no further arguments; got {sorted(method_kwargs)}")
     from . import observation, shiftadd, upsample

@@ -54,6 +54,8 @@
  *                              registered views onto the x2 / x3 / x4 grid (normalised convolution), and its adjoint
  *   hrn_observe / hrn_consistency_residual / hrn_consistency_finish / hrn_observe_adjoint  <-  (no counterpart) the observation model: what
  *                              every registered view should have recorded of an HR frame, the data-consistency loss and back-projection
+ *   hrn_robust_sums / hrn_robust_finish / hrn_robust_apply / hrn_btv_step / hrn_btv_backward / hrn_btv_value  <-  (no counterpart) Welsch
+ *                              weights for the data term and a bilateral-TV prior: the robust, regularised reconstruction
  *
  * Conventions
  *   - every pointer is a DEVICE pointer (hipMalloc'ed or a torch CUDA tensor's data_ptr) unless stated;
@@ -376,6 +378,49 @@ int hrn_consistency_finish(const void* workspace, size_t workspace_bytes, float*
 int hrn_observe_adjoint(const float* residual, const float* lr_masks, const float* alphas, const float* shifts, const float* beta,
                         const float* coef, const float* gain, const float* x, float* out, int B, int V, int H, int W, int scale,
                         void* stream);
+
+/* ------------------------------------------------------------------ a robust data term and a bilateral-TV prior for the reconstruction
+ * (No counterpart in the reference)  Tensors, `counted`, n_v and V_b are the observation model's, above.
+ *
+ * Robust data step (Welsch weights), per sample and iteration, from the residual e that hrn_consistency_residual wrote and a state
+ * beta_prev (B,V) - the plain mean bias of the first iteration (hrn_consistency_finish's beta), afterwards the previous beta:
+ *     w = counted exp(-((e + beta_prev) / delta)^2)        (fp32: the sum, the quotient, the square, expf)
+ *     beta_v = -sum w e / sum w, 0 when sum w < 2^-60 and 0 without `brightness`;   r' = w (e + beta_v)
+ *     x' = x - step (S^2 / V_b) sum_v A_v^T r'_v           (hrn_observe_adjoint on r' with beta = NULL and hrn_consistency_finish's coef_step)
+ * hrn_robust_sums WRITES per tile of HRN_OBSERVE_TILE_H x HRN_OBSERVE_TILE_W samples the fp64 sums of w, w e and w (e + beta_prev)^2 (the
+ *   products in fp64 of the fp32 w and e) into `workspace` (hrn_robust_workspace_bytes(B, V, H, W) bytes, 8-byte aligned).
+ * hrn_robust_finish adds them in a fixed order and WRITES beta (B,V), inlier (B,V) = sum w / n_v (0 when n_v = 0; count is
+ *   hrn_consistency_finish's) and loss (B) = sum_v sum w (e + beta_prev)^2 / sum_v sum w (0 when that is below 2^-60).
+ * hrn_robust_apply WRITES weighted (B,V,H,W) = r' where counted and exact 0 elsewhere; it must not alias the residual.
+ *
+ * Bilateral TV of a plane x (SH, SW), P in 1 .. HRN_BTV_MAX_P, 0 < alpha <= 1, eps > 0:
+ *     R(x) = sum_{(l,m) != (0,0), |l|,|m| <= P} alpha^(|l|+|m|) sum_p phi(x_p - x_{p-(l,m)}),  phi(t) = sqrt(t^2 + eps^2) - eps,
+ *   the inner sum over the pixels whose partner lies inside the plane (no padding; every unordered pair appears twice), and
+ *     g_p = dR/dx_p = 2 sum_q alpha^(|l|+|m|) phi'(x_p - x_q),  phi'(t) = t / sqrt(t^2 + eps^2),
+ *   over the neighbours q = p + (l, m) inside the plane, in raster order of (l, m), one fma each.  The weights alpha^k are formed in fp64
+ *   and rounded to fp32 once; phi' is t rsqrt(fma(t, t, eps^2)), exactly 0 for equal neighbours.
+ * hrn_btv_step WRITES out = x - c[plane] g; hrn_btv_backward WRITES out = gain[plane] g.  out must not overlap x (a stencil).
+ * hrn_btv_value WRITES value (planes) f32 = gain R / (SH SW) from per-tile fp64 partials (`workspace`: hrn_btv_workspace_bytes bytes,
+ *   8-byte aligned), tiles of HRN_BTV_TILE_H x HRN_BTV_TILE_W pixels, added in a fixed order by a second launch.
+ * All are bit-reproducible and a plane's or sample's result does not depend on its batch; appended views with alpha 0 change no bit.
+ * Sides of 1 .. HRN_BTV_MAX_SIDE for the planes; every offset is 64-bit.  -2 before any launch for a NULL pointer, non-positive or too
+ * large sizes, a bad scale, delta, P, alpha, eps or gain, a workspace that is too small or misaligned, or overlapping arguments. */
+#define HRN_BTV_TILE_H 16
+#define HRN_BTV_TILE_W 64
+#define HRN_BTV_MAX_P 3
+#define HRN_BTV_MAX_SIDE 49152
+size_t hrn_robust_workspace_bytes(int B, int V, int H, int W);
+int hrn_robust_sums(const float* residual, const float* lr_masks, const float* alphas, const float* shifts, const float* beta_prev,
+                    void* workspace, size_t workspace_bytes, int B, int V, int H, int W, int scale, float delta, void* stream);
+int hrn_robust_finish(const void* workspace, size_t workspace_bytes, const int* count, float* beta, float* inlier, float* loss, int B, int V,
+                      int H, int W, int brightness, void* stream);
+int hrn_robust_apply(const float* residual, const float* lr_masks, const float* alphas, const float* shifts, const float* beta_prev,
+                     const float* beta, float* weighted, int B, int V, int H, int W, int scale, float delta, void* stream);
+int hrn_btv_step(const float* x, const float* c, float* out, int planes, int SH, int SW, int P, float alpha, float eps, void* stream);
+int hrn_btv_backward(const float* x, const float* gain, float* out, int planes, int SH, int SW, int P, float alpha, float eps, void* stream);
+size_t hrn_btv_workspace_bytes(int planes, int SH, int SW);
+int hrn_btv_value(const float* x, float* value, void* workspace, size_t workspace_bytes, int planes, int SH, int SW, int P, float alpha,
+                  float eps, float gain, void* stream);
 
 /* ------------------------------------------------------------------ ShiftNet */
 typedef struct hrn_shiftnet_params {
