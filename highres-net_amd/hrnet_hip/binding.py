@@ -114,6 +114,12 @@ SIGNATURES = {
     "hrn_consistency_residual": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_size_t] + [_c.c_int] * 5 + [_c.c_void_p]),
     "hrn_consistency_finish": (_c.c_int, [_c.c_void_p, _c.c_size_t] + [_c.c_void_p] * 7 + [_c.c_int] * 5 + [_c.c_float, _c.c_int, _c.c_void_p]),
     "hrn_observe_adjoint": (_c.c_int, [_c.c_void_p] * 9 + [_c.c_int] * 5 + [_c.c_void_p]),
+    "hrn_observe_shift_workspace_bytes": (_c.c_size_t, [_c.c_int] * 4),
+    "hrn_observe_shift_grad": (_c.c_int, [_c.c_void_p] * 7 + [_c.c_size_t] + [_c.c_int] * 5 + [_c.c_void_p]),
+    "hrn_observe_shift_grad_finish": (_c.c_int, [_c.c_void_p, _c.c_size_t] + [_c.c_void_p] * 3 + [_c.c_int] * 4 + [_c.c_void_p]),
+    "hrn_shift_normal": (_c.c_int, [_c.c_void_p] * 6 + [_c.c_float] + [_c.c_void_p] * 2 + [_c.c_size_t, _c.c_void_p, _c.c_size_t] + [_c.c_int] * 5
+                         + [_c.c_void_p]),
+    "hrn_shift_normal_finish": (_c.c_int, [_c.c_void_p, _c.c_size_t] + [_c.c_void_p] * 5 + [_c.c_int] * 6 + [_c.c_float] * 2 + [_c.c_void_p]),
     "hrn_robust_workspace_bytes": (_c.c_size_t, [_c.c_int] * 4),
     "hrn_robust_sums": (_c.c_int, [_c.c_void_p] * 6 + [_c.c_size_t] + [_c.c_int] * 5 + [_c.c_float, _c.c_void_p]),
     "hrn_robust_finish": (_c.c_int, [_c.c_void_p, _c.c_size_t] + [_c.c_void_p] * 4 + [_c.c_int] * 5 + [_c.c_void_p]),
@@ -1675,6 +1681,127 @@ def back_project(sr0, lrs, lr_masks, alphas, shifts, scale, iters, step, brightn
     return x, losses
 
 
+# --------------------------------------------------------------------------- the derivative in the shifts (observe_shift.hip)
+SHIFT_NORMAL_SUMS = 10        # HRN_SHIFT_NORMAL_SUMS: the doubles a tile leaves in the workspace
+SHIFT_MIN_WEIGHT = 3.0        # a view whose sum p is below this keeps its shift
+
+
+def shift_workspace(B, V, H, W, device):
+    nbytes = int(load_library().hrn_observe_shift_workspace_bytes(B, V, H, W))
+    if nbytes == 0:
+        raise HrnetHipError(f"hrn_observe_shift_workspace_bytes refuses B={B} V={V} H={H} W={W}")
+    return torch.empty((nbytes // 8,), dtype=torch.float64, device=device)
+
+
+def observe_shift_grad(hr, g, lr_masks, alphas, shifts, beta, coef, gain, scale, workspace=None):
+    """hrn_observe_shift_grad then hrn_observe_shift_grad_finish: hr (B,SH,SW), g (B,V,H,W), beta (B,V) or None, coef, gain (B,) or None ->
+    d_shifts (B,V,2) = coef gain sum [counted] (g + beta) D.  Two launches."""
+    lib = load_library()
+    B, V, H, W = g.shape
+    ws = shift_workspace(B, V, H, W, hr.device) if workspace is None else workspace
+    out = torch.empty((B, V, 2), dtype=torch.float32, device=hr.device)
+    with torch.cuda.device(hr.device):
+        _check(lib.hrn_observe_shift_grad(_ptr(hr), _ptr(g), _opt_ptr(lr_masks), _opt_ptr(alphas), _ptr(shifts), _opt_ptr(beta), _ptr(ws),
+                                          ws.numel() * 8, B, V, H, W, int(scale), _stream()), "hrn_observe_shift_grad")
+        _check(lib.hrn_observe_shift_grad_finish(_ptr(ws), ws.numel() * 8, _opt_ptr(coef), _opt_ptr(gain), _ptr(out), B, V, H, W, _stream()),
+               "hrn_observe_shift_grad_finish")
+    return out
+
+
+def shift_normal(hr, lrs, lr_masks, alphas, shifts, scale, brightness, beta_prev=None, delta=0.1, fixed=None, damping=0.0, max_step=1.0,
+                 shifts_out=None, residual=None, workspace=None, normal=None, state=None, step=1.0, loss=None):
+    """hrn_shift_normal then hrn_shift_normal_finish -> normal (B,V,8) fp64.  beta_prev (B,V): Welsch weights.  shifts_out (B,V,2): the
+    damped Gauss-Newton update is written there (fixed: (B,V) uint8 or None).  residual (B,V,H,W): the residual plane too.  Two launches.
+    state (a ConsistencyState) with loss (B,): the pass stands in for consistency_residual - it writes state.residual and the three plain
+    sums into state.workspace, and hrn_consistency_finish runs on them between the two launches (three launches; the bits are
+    consistency_residual's)."""
+    lib = load_library()
+    B, V, H, W = lrs.shape
+    ws = shift_workspace(B, V, H, W, hr.device) if workspace is None else workspace
+    if normal is None:
+        normal = torch.empty((B, V, 8), dtype=torch.float64, device=hr.device)
+    with torch.cuda.device(hr.device):
+        if state is not None:
+            residual = state.residual
+        _check(lib.hrn_shift_normal(_ptr(hr), _ptr(lrs), _opt_ptr(lr_masks), _opt_ptr(alphas), _ptr(shifts), _opt_ptr(beta_prev), float(delta),
+                                    _opt_ptr(residual), _opt_ptr(None if state is None else state.workspace), 0 if state is None else state.ws_bytes,
+                                    _ptr(ws), ws.numel() * 8, B, V, H, W, int(scale), _stream()), "hrn_shift_normal")
+        if state is not None:
+            _check(lib.hrn_consistency_finish(_ptr(state.workspace), state.ws_bytes, _ptr(state.beta), _ptr(state.count), _ptr(state.ssr),
+                                              _ptr(loss), _ptr(state.n_views), _ptr(state.coef_loss), _ptr(state.coef_step), B, V, H, W, int(scale),
+                                              float(step), int(bool(brightness)), _stream()), "hrn_consistency_finish")
+        _check(lib.hrn_shift_normal_finish(_ptr(ws), ws.numel() * 8, _opt_ptr(alphas), _ptr(shifts), _opt_ptr(fixed), _ptr(normal),
+                                           _opt_ptr(shifts_out), B, V, H, W, int(scale), int(bool(brightness)), float(damping), float(max_step),
+                                           _stream()), "hrn_shift_normal_finish")
+    return normal
+
+
+def refine_shifts(sr, lrs, lr_masks, alphas, shifts, fixed, scale, iters, damping, max_step, brightness, robust, delta):
+    """iters Gauss-Newton steps on the shifts with the frame held, two launches each between two shift buffers -> (shifts', trace
+    (iters,B,V,8): the normal equations every step started from).  robust: Welsch weights around the plain mean bias of each step's frame
+    (hrn_consistency_residual + finish: two more launches a step)."""
+    B, V, H, W = lrs.shape
+    dev = sr.device
+    cur, nxt = shifts.clone(), torch.empty_like(shifts)
+    trace = torch.empty((iters, B, V, 8), dtype=torch.float64, device=dev)
+    if iters:
+        ws = shift_workspace(B, V, H, W, dev)
+        state = ConsistencyState(B, V, H, W, dev) if robust else None
+        loss = torch.empty((B,), dtype=torch.float32, device=dev) if robust else None
+        for t in range(iters):
+            if robust:
+                consistency_residual(sr, lrs, lr_masks, alphas, cur, scale, 1.0, brightness, state, loss)
+            shift_normal(sr, lrs, lr_masks, alphas, cur, scale, brightness, state.beta if robust else None, delta, fixed, damping, max_step,
+                         shifts_out=nxt, workspace=ws, normal=trace[t])
+            cur, nxt = nxt, cur
+    return cur, trace
+
+
+def reconstruct_joint(sr0, lrs, lr_masks, alphas, shifts, fixed, scale, iters, refine_every, refine_from, damping, max_step, step, brightness,
+                      robust, delta, lam, P, alpha, eps):
+    """`reconstruct`'s iteration (its launches, unchanged) with a shift update beside the data step of iteration t when refine_every > 0,
+    t >= refine_from and (t - refine_from) % refine_every == 0 (with `robust` also t >= 1: the update's weights need a beta_prev).  The
+    update reads the frame and the shifts the iteration started from and writes a second shift buffer, so the adjoint still runs on the
+    old shifts; the buffers are swapped after the iteration.  In an updating iteration hrn_shift_normal takes the place of
+    hrn_consistency_residual (one pass over the frame; hrn_consistency_finish runs on the plain sums it leaves) and
+    hrn_shift_normal_finish is the one launch more -> (sr, shifts)."""
+    B, V, H, W = lrs.shape
+    dev = sr0.device
+    x = sr0.clone()
+    cur, nxt = shifts.clone(), torch.empty_like(shifts)
+    if iters:
+        state = ConsistencyState(B, V, H, W, dev)
+        rstate = RobustState(B, V, H, W, dev) if robust else None
+        loss, wloss = (torch.empty((B,), dtype=torch.float32, device=dev) for _ in range(2))
+        if refine_every > 0:
+            ws = shift_workspace(B, V, H, W, dev)
+            normal = torch.empty((B, V, 8), dtype=torch.float64, device=dev)
+        if lam > 0:
+            y = torch.empty_like(x)
+            c = torch.full((B,), float(step) * float(lam), dtype=torch.float32, device=dev)
+        for t in range(iters):
+            refine = refine_every > 0 and t >= refine_from and (t - refine_from) % refine_every == 0 and not (robust and t == 0)
+            if refine:                                   # the normal pass stands in for the residual pass: the same residual, sums and finish
+                shift_normal(x, lrs, lr_masks, alphas, cur, scale, brightness, rstate.beta_prev if robust else None, delta, fixed, damping,
+                             max_step, shifts_out=nxt, workspace=ws, normal=normal, state=state, step=step, loss=loss)
+            else:
+                consistency_residual(x, lrs, lr_masks, alphas, cur, scale, step, brightness, state, loss)
+            if robust and t == 0:
+                rstate.beta_prev.copy_(state.beta)
+            if robust:
+                robust_step(state, rstate, lr_masks, alphas, cur, scale, delta, brightness, wloss)
+                observe_adjoint(rstate.weighted, lr_masks, alphas, cur, None, state.coef_step, None, x, scale, out=x)
+                rstate.beta_prev, rstate.beta = rstate.beta, rstate.beta_prev
+            else:
+                observe_adjoint(state.residual, lr_masks, alphas, cur, state.beta, state.coef_step, None, x, scale, out=x)
+            if lam > 0:
+                btv_step(x, c, P, alpha, eps, out=y)
+                x, y = y, x
+            if refine:
+                cur, nxt = nxt, cur
+    return x, cur
+
+
 # --------------------------------------------------------------------------- robust, regularised reconstruction (robust_sr.hip)
 BTV_TILE = (16, 64)           # HRN_BTV_TILE_H x HRN_BTV_TILE_W: the HR pixels a workgroup owns
 BTV_MAX_P = 3                 # the window's radius is 1 .. 3
@@ -2062,6 +2189,141 @@ def _op_back_project(sr0: torch.Tensor, lrs: torch.Tensor, lr_masks: Optional[to
 @_op_back_project.register_fake
 def _(sr0, lrs, lr_masks, alphas, shifts, scale, iters, step, brightness):
     return sr0.new_empty(tuple(sr0.shape), dtype=torch.float32), sr0.new_empty((iters, sr0.shape[0]), dtype=torch.float32)
+
+
+# The derivative in the shifts (observe_shift.hip).  observe_sg and consistency_loss_sg are observe and consistency_loss_train - the same
+# launches, the same bits - whose autograd formulas also return d_shifts (observe_shift_backward), each half only when it is asked for.
+# shift_normal, refine_shifts and reconstruct_joint carry no gradient.
+@torch.library.custom_op("hrnet_hip::observe_shift_backward", mutates_args=(), device_types="cuda")
+def _op_observe_shift_backward(hr: torch.Tensor, g: torch.Tensor, lr_masks: Optional[torch.Tensor], alphas: Optional[torch.Tensor],
+                               shifts: torch.Tensor, beta: Optional[torch.Tensor], coef: Optional[torch.Tensor],
+                               gain: Optional[torch.Tensor], scale: int) -> torch.Tensor:
+    """-> d_shifts (B,V,2) = coef gain sum [counted] (g + beta) D (hrn_observe_shift_grad, hrn_observe_shift_grad_finish)."""
+    return observe_shift_grad(_f32c(hr), _f32c(g), _f32c(lr_masks), _f32c(alphas), _f32c(shifts), _f32c(beta), _f32c(coef), _f32c(gain), scale)
+
+
+@_op_observe_shift_backward.register_fake
+def _(hr, g, lr_masks, alphas, shifts, beta, coef, gain, scale):
+    return hr.new_empty(tuple(shifts.shape), dtype=torch.float32)
+
+
+@torch.library.custom_op("hrnet_hip::observe_sg", mutates_args=(), device_types="cuda")
+def _op_observe_sg(hr: torch.Tensor, shifts: torch.Tensor, scale: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """observe, differentiable in hr and in shifts."""
+    return observe(_f32c(hr), _f32c(shifts), scale)
+
+
+@_op_observe_sg.register_fake
+def _(hr, shifts, scale):
+    shape = (hr.shape[0], shifts.shape[1], hr.shape[1] // scale, hr.shape[2] // scale)
+    return hr.new_empty(shape, dtype=torch.float32), hr.new_empty(shape, dtype=torch.float32)
+
+
+def _observe_sg_setup(ctx, inputs, output):
+    hr, shifts, scale = inputs
+    ctx.scale, ctx.hr_dtype, ctx.shifts_dtype = scale, hr.dtype, shifts.dtype
+    ctx.save_for_backward(hr, shifts)
+
+
+def _observe_sg_backward(ctx, d_views, d_valid):
+    hr, shifts = ctx.saved_tensors
+    d_hr = d_shifts = None
+    if ctx.needs_input_grad[0]:
+        d_hr = torch.ops.hrnet_hip.observe_backward(d_views, shifts, ctx.scale).to(ctx.hr_dtype)
+    if ctx.needs_input_grad[1]:
+        d_shifts = torch.ops.hrnet_hip.observe_shift_backward(hr, d_views, None, None, shifts, None, None, None, ctx.scale).to(ctx.shifts_dtype)
+    return d_hr, d_shifts, None
+
+
+_op_observe_sg.register_autograd(_observe_sg_backward, setup_context=_observe_sg_setup)
+
+
+@torch.library.custom_op("hrnet_hip::consistency_loss_sg", mutates_args=(), device_types="cuda")
+def _op_consistency_loss_sg(srs: torch.Tensor, lrs: torch.Tensor, lr_masks: Optional[torch.Tensor], alphas: Optional[torch.Tensor],
+                            shifts: torch.Tensor, scale: int, brightness: bool
+                            ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """consistency_loss_train, differentiable in srs and in shifts."""
+    srs, lrs = _f32c(srs), _f32c(lrs)
+    B, V, H, W = lrs.shape
+    state = ConsistencyState(B, V, H, W, srs.device)
+    loss = torch.empty((B,), dtype=torch.float32, device=srs.device)
+    consistency_residual(srs, lrs, _f32c(lr_masks), _f32c(alphas), _f32c(shifts), scale, 1.0, brightness, state, loss)
+    return loss, state.residual, state.beta, state.count, state.coef_loss
+
+
+@_op_consistency_loss_sg.register_fake
+def _(srs, lrs, lr_masks, alphas, shifts, scale, brightness):
+    b, v = lrs.shape[:2]
+    f32 = dict(dtype=torch.float32)
+    return (srs.new_empty((b,), **f32), srs.new_empty(tuple(lrs.shape), **f32), srs.new_empty((b, v), **f32),
+            srs.new_empty((b, v), dtype=torch.int32), srs.new_empty((b,), **f32))
+
+
+def _consistency_sg_setup(ctx, inputs, output):
+    srs, lrs, lr_masks, alphas, shifts, scale, brightness = inputs
+    ctx.scale, ctx.srs_dtype, ctx.shifts_dtype = scale, srs.dtype, shifts.dtype
+    ctx.has = (lr_masks is not None, alphas is not None)
+    ctx.save_for_backward(output[1], output[2], output[4], shifts, srs, *(t for t in (lr_masks, alphas) if t is not None))
+
+
+def _consistency_sg_backward(ctx, d_loss, d_residual, d_beta, d_count, d_coef):
+    saved = list(ctx.saved_tensors)
+    residual, beta, coef, shifts, srs = saved[:5]
+    rest = saved[5:]
+    lr_masks = rest.pop(0) if ctx.has[0] else None
+    alphas = rest.pop(0) if ctx.has[1] else None
+    d_srs = d_shifts = None
+    if ctx.needs_input_grad[0]:
+        d_srs = torch.ops.hrnet_hip.consistency_loss_backward(d_loss, residual, beta, coef, lr_masks, alphas, shifts, ctx.scale).to(ctx.srs_dtype)
+    if ctx.needs_input_grad[4]:
+        d_shifts = torch.ops.hrnet_hip.observe_shift_backward(srs, residual, lr_masks, alphas, shifts, beta, coef, d_loss,
+                                                              ctx.scale).to(ctx.shifts_dtype)
+    return d_srs, None, None, None, d_shifts, None, None
+
+
+_op_consistency_loss_sg.register_autograd(_consistency_sg_backward, setup_context=_consistency_sg_setup)
+
+
+@torch.library.custom_op("hrnet_hip::shift_normal", mutates_args=(), device_types="cuda")
+def _op_shift_normal(sr: torch.Tensor, lrs: torch.Tensor, lr_masks: Optional[torch.Tensor], alphas: Optional[torch.Tensor],
+                     shifts: torch.Tensor, beta_prev: Optional[torch.Tensor], scale: int, brightness: bool, delta: float) -> torch.Tensor:
+    """-> normal (B,V,8) fp64 (hrn_shift_normal, hrn_shift_normal_finish); beta_prev: Welsch weights; no gradient."""
+    return shift_normal(_f32c(sr), _f32c(lrs), _f32c(lr_masks), _f32c(alphas), _f32c(shifts), scale, brightness, _f32c(beta_prev), delta)
+
+
+@_op_shift_normal.register_fake
+def _(sr, lrs, lr_masks, alphas, shifts, beta_prev, scale, brightness, delta):
+    return sr.new_empty((lrs.shape[0], lrs.shape[1], 8), dtype=torch.float64)
+
+
+@torch.library.custom_op("hrnet_hip::refine_shifts", mutates_args=(), device_types="cuda")
+def _op_refine_shifts(sr: torch.Tensor, lrs: torch.Tensor, lr_masks: Optional[torch.Tensor], alphas: Optional[torch.Tensor],
+                      shifts: torch.Tensor, fixed: Optional[torch.Tensor], scale: int, iters: int, damping: float, max_step: float,
+                      brightness: bool, robust: bool, delta: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (shifts' (B,V,2), trace (iters,B,V,8) fp64); fixed (B,V) uint8 or None; no gradient."""
+    return refine_shifts(_f32c(sr), _f32c(lrs), _f32c(lr_masks), _f32c(alphas), _f32c(shifts), fixed, scale, iters, damping, max_step,
+                         brightness, robust, delta)
+
+
+@_op_refine_shifts.register_fake
+def _(sr, lrs, lr_masks, alphas, shifts, fixed, scale, iters, damping, max_step, brightness, robust, delta):
+    return (sr.new_empty(tuple(shifts.shape), dtype=torch.float32), sr.new_empty((iters,) + tuple(shifts.shape[:2]) + (8,), dtype=torch.float64))
+
+
+@torch.library.custom_op("hrnet_hip::reconstruct_joint", mutates_args=(), device_types="cuda")
+def _op_reconstruct_joint(sr0: torch.Tensor, lrs: torch.Tensor, lr_masks: Optional[torch.Tensor], alphas: Optional[torch.Tensor],
+                          shifts: torch.Tensor, fixed: Optional[torch.Tensor], scale: int, iters: int, refine_every: int, refine_from: int,
+                          damping: float, max_step: float, step: float, brightness: bool, robust: bool, delta: float, lam: float, P: int,
+                          alpha: float, eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (sr (B,SH,SW), shifts (B,V,2)) after `iters` iterations of reconstruct with shift updates; no gradient."""
+    return reconstruct_joint(_f32c(sr0), _f32c(lrs), _f32c(lr_masks), _f32c(alphas), _f32c(shifts), fixed, scale, iters, refine_every,
+                             refine_from, damping, max_step, step, brightness, robust, delta, lam, P, alpha, eps)
+
+
+@_op_reconstruct_joint.register_fake
+def _(sr0, lrs, lr_masks, alphas, shifts, fixed, scale, iters, refine_every, refine_from, damping, max_step, step, brightness, robust, delta,
+      lam, P, alpha, eps):
+    return sr0.new_empty(tuple(sr0.shape), dtype=torch.float32), sr0.new_empty(tuple(shifts.shape), dtype=torch.float32)
 
 
 # Robust, regularised reconstruction (robust_sr.hip).  reconstruct carries no gradient.  btv_loss_train is R / pixels per plane; its

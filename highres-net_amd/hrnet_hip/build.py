@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libhrnet_hip.so")
-SOURCES = ["api.hip", "abi_fixed.hip", "prof.hip", "conv3x3.hip", "conv3x3_r64.hip", "conv3x3_v6.hip", "conv3x3_v6x3.hip", "backward.hip", "wgrad_x3.hip", "decoder_bwd.hip", "train.hip", "stem.hip", "composite.hip", "upsample.hip", "shift_add.hip", "observe.hip", "robust_sr.hip", "decoder.hip", "lanczos.hip", "lanczos_bwd.hip", "shiftnet.hip", "shiftnet_bwd.hip", "adam.hip", "optim_guard.hip", "losses.hip", "shift_loss.hip", "cssim.hip", "cssim_bwd.hip", "cl1_loss.hip", "registration.hip", "registration_scene.hip", "registration_local.hip", "registration_pyramid.hip", "resample_bwd.hip", "subpixel_loss.hip", "input_grad.hip", "collate.hip", "collate_mask.hip", "dihedral.hip", "tile.hip", "resample.hip", "kernel_test.hip"]
+SOURCES = ["api.hip", "abi_fixed.hip", "prof.hip", "conv3x3.hip", "conv3x3_r64.hip", "conv3x3_v6.hip", "conv3x3_v6x3.hip", "backward.hip", "wgrad_x3.hip", "decoder_bwd.hip", "train.hip", "stem.hip", "composite.hip", "upsample.hip", "shift_add.hip", "observe.hip", "observe_shift.hip", "robust_sr.hip", "decoder.hip", "lanczos.hip", "lanczos_bwd.hip", "shiftnet.hip", "shiftnet_bwd.hip", "adam.hip", "optim_guard.hip", "losses.hip", "shift_loss.hip", "cssim.hip", "cssim_bwd.hip", "cl1_loss.hip", "registration.hip", "registration_scene.hip", "registration_local.hip", "registration_pyramid.hip", "resample_bwd.hip", "subpixel_loss.hip", "input_grad.hip", "collate.hip", "collate_mask.hip", "dihedral.hip", "tile.hip", "resample.hip", "kernel_test.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 

@@ -32,6 +32,35 @@ __device__ __forceinline__ bool sample_valid(int i, int n, int L) {
     return i >= 0 && i < L && lo >= 0 && lo + S + 4 <= (long)S * L - 1;
 }
 
+// The weights and the staged window that observe.hip and observe_shift.hip share.
+constexpr int plane_stride(int S) { return S == 2 ? 48 : (S == 3 ? 43 : 40); }
+
+// tap o (-2 .. 3) of split_and_taps before its normalisation, fp64
+__device__ __forceinline__ double tap64(int o, double f) {
+    const double x = (double)o - f;
+    const double px = 3.141592653589793 * x, px3 = 3.141592653589793 * (x / 3.0);
+    const double a = x == 0.0 ? 1.0 : sin(px) / px;
+    const double b = x == 0.0 ? 1.0 : sin(px3) / px3;
+    return fabs(x) >= 3.0 ? 0.0 : a * b;
+}
+
+// w_j out of the six raw taps k[0..5] (o = -2 .. 3): normalised as split_and_taps does (the sum in order), box-summed, rounded once
+template <int S>
+__device__ __forceinline__ float box_weight(const double* k, int j) {
+    double sum = 0.0;
+#pragma unroll
+    for (int o = 0; o < 6; ++o) sum += k[o];
+    double w = 0.0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        const int o = j - s;                             // tap index o + 2 = j - s
+        if (o >= 0 && o < 6) w += k[o] / sum;
+    }
+    return (float)(w / (double)S);
+}
+
+__device__ __forceinline__ int floor_div(int a, int b) { return (a >= 0 ? a : a - b + 1) / b; }
+
 // What a kernel that only needs `counted` keeps of a view: whether it counts and is in reach (uniform per view), and n of both axes.
 struct ViewGeom { bool counts; int ny, nx; };
 

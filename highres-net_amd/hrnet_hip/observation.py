@@ -10,8 +10,10 @@ view and a decimation (include/hrnet_hip.h holds the definition).  `shifts (B,V,
 `observe` makes synthetic LR views of HR frames; `consistency_loss` is `sum_v |counted (A_v sr - lr_v + beta_v)|^2 / sum_v n_v`, a loss
 without an HR target (self-supervised fine-tuning, PROBA-V's test split) with the brightness bias beta_v every loss here corrects;
 `back_project` refines a frame against the views, `x <- x - step (scale^2 / V_b) sum_v A_v^T r_v`; `register_and_refine` registers,
-starts from shift-and-add or the bicubic baseline and refines.  Gradients go to the HR frame only; there is NONE to shifts, lrs, masks or
-alphas.  There is no CPU fallback: tensors must be on a ROCm device."""
+starts from shift-and-add or the bicubic baseline and refines.  Gradients go to the HR frame and - with shift_grad=True, DESIGN.md section
+7v - to the shifts; there is NONE to lrs, masks or alphas.  `shift_normal`, `refine_shifts` and `reconstruct_joint` use the same derivative
+for Gauss-Newton steps on the shifts: joint estimation of the frame and its registration.  There is no CPU fallback: tensors must be on a
+ROCm device."""
 import numpy as np
 import torch
 
@@ -84,11 +86,14 @@ def _check_views(srs, lrs, shifts, lr_masks, alphas, scale, what="srs"):
     return (srs[:, 0] if channel else srs), channel, scale
 
 
-def observe(hr, shifts, scale=3):
+def observe(hr, shifts, scale=3, shift_grad=False):
     """hr (B, scale H, scale W), shifts (B,V,2) -> (views (B,V,H,W), valid (B,V,H,W) f32 0 / 1): what a view at each shift records of the
     HR frame - synthetic LR views with the library's own sampler.  A sample whose footprint leaves the frame is 0 and not valid, and so is
     every sample of a view with a non-finite shift (or one of 256 / scale LR pixels or more).  Differentiable in hr (the adjoint kernel);
-    the gradient that arrives at `views` counts where `valid` is set.  The HR sides must be multiples of scale, H, W in 1..16384."""
+    the gradient that arrives at `views` counts where `valid` is set.  shift_grad: the same bits, differentiable in shifts too (the
+    operator is C^1 in them; `valid` is piecewise constant and not differentiated), each gradient computed only when it is needed.  The HR
+    sides must be multiples of scale, H, W in 1..16384."""
+    shift_grad = _flag("shift_grad", shift_grad)
     _tensor("hr", hr)
     _tensor("shifts", shifts)
     scale = check_scale(scale)
@@ -103,21 +108,28 @@ def observe(hr, shifts, scale=3):
     if not (hr.is_floating_point() and shifts.is_floating_point()):
         raise TypeError("hr and shifts must be floating-point tensors")
     _on_device(hr, hr=hr, shifts=shifts)
-    views, valid = torch.ops.hrnet_hip.observe(hr, shifts.detach(), scale)
+    if shift_grad:
+        views, valid = torch.ops.hrnet_hip.observe_sg(hr, shifts, scale)
+    else:
+        views, valid = torch.ops.hrnet_hip.observe(hr, shifts.detach(), scale)
     return views, valid.detach()
 
 
-def consistency_loss(srs, lrs, shifts, lr_masks=None, alphas=None, scale=3, brightness=True, return_residual=False):
+def consistency_loss(srs, lrs, shifts, lr_masks=None, alphas=None, scale=3, brightness=True, return_residual=False, shift_grad=False):
     """srs (B,SH,SW) or (B,1,SH,SW), lrs (B,V,H,W), shifts (B,V,2)[, lr_masks (B,V,H,W) 0 / non-zero, alphas (B,V): a view counts iff its
     alpha is non-zero] -> loss (B,) = sum_v sum (counted (A_v sr - lr_v + beta_v))^2 / sum_v n_v, exactly 0 for a sample in which nothing
     counts.  brightness: beta_v = -mean of the counted A_v sr - lr_v (the views' brightness bias), else 0.  return_residual: also
     (residual (B,V,H,W) = A_v sr - lr_v where counted and 0 elsewhere, beta (B,V), count (B,V) int32), all without a gradient.
-    Differentiable in srs only.  Two launches forward (nothing returns to the host), one backward."""
-    brightness = _flag("brightness", brightness)
+    Differentiable in srs only; with shift_grad the same bits, differentiable in shifts too (the loss a registration network can be
+    trained on without an HR target).  Two launches forward (nothing returns to the host), one backward, two more for d_shifts."""
+    brightness, shift_grad = _flag("brightness", brightness), _flag("shift_grad", shift_grad)
     srs3, _, scale = _check_views(srs, lrs, shifts, lr_masks, alphas, scale)
     det = lambda t: None if t is None else t.detach()
-    loss, residual, beta, count, _ = torch.ops.hrnet_hip.consistency_loss_train(srs3, lrs.detach(), det(lr_masks), det(alphas), shifts.detach(),
-                                                                                scale, brightness)
+    if shift_grad:
+        op, sh = torch.ops.hrnet_hip.consistency_loss_sg, shifts
+    else:
+        op, sh = torch.ops.hrnet_hip.consistency_loss_train, shifts.detach()
+    loss, residual, beta, count, _ = op(srs3, lrs.detach(), det(lr_masks), det(alphas), sh, scale, brightness)
     return (loss, residual.detach(), beta.detach(), count) if return_residual else loss
 
 
@@ -201,6 +213,104 @@ def reconstruct(sr0, lrs, shifts, lr_masks=None, alphas=None, scale=3, iters=30,
     return (sr, trace) if return_trace else sr
 
 
+def check_refine(damping, max_step, delta, robust):
+    """the options of the shift update -> (damping, max_step, delta, robust as a bool): damping >= 0, max_step > 0 (LR pixels), delta > 0"""
+    damping, max_step, delta = _number("damping", damping), _number("max_step", max_step), _number("delta", delta)
+    if damping < 0.0:
+        raise ValueError(f"damping must be >= 0; got {damping}")
+    if not max_step > 0.0:
+        raise ValueError(f"max_step must be positive; got {max_step}")
+    if not delta > 0.0:
+        raise ValueError(f"delta must be positive; got {delta}")
+    if robust not in (None, "welsch"):
+        raise ValueError(f"robust must be None or \"welsch\"; got {robust!r}")
+    return damping, max_step, delta, robust is not None
+
+
+def _check_fixed(fixed, lrs):
+    """`fixed` is a view index, None, or a (B,V) bool tensor (judged before any device is asked for)"""
+    if fixed is None or not torch.is_tensor(lrs) or lrs.dim() != 4:
+        return
+    B, V = lrs.shape[:2]
+    if torch.is_tensor(fixed):
+        if tuple(fixed.shape) != (B, V) or fixed.dtype != torch.bool:
+            raise ValueError(f"fixed must be a view index, None or a ({B}, {V}) bool tensor; got {tuple(fixed.shape)} {fixed.dtype}")
+    elif isinstance(fixed, bool) or not isinstance(fixed, (int, np.integer)) or not 0 <= fixed < V:
+        raise ValueError(f"fixed must be a view index in 0..{V - 1}, None or a ({B}, {V}) bool tensor; got {fixed!r}")
+
+
+def _fixed_views(fixed, B, V, first):
+    """a checked `fixed` -> (B,V) uint8 on the device of `first`, or None"""
+    if fixed is None:
+        return None
+    if torch.is_tensor(fixed):
+        _on_device(first, fixed=fixed)
+        return fixed.to(torch.uint8).contiguous()
+    mask = torch.zeros((B, V), dtype=torch.uint8, device=first.device)
+    mask[:, int(fixed)] = 1
+    return mask
+
+
+def shift_normal(sr, lrs, shifts, lr_masks=None, alphas=None, scale=3, brightness=True, robust=None, delta=0.1, beta_prev=None):
+    """-> normal (B,V,8) fp64 = [sum p, g_y, g_x, H_yy, H_yx, H_xx, beta, sum p (e + beta)^2], the normal equations of every view's shift
+    against the frame sr (a diagnostic): p = counted, or with robust="welsch" the Welsch weight of e + beta_prev (beta_prev
+    (B,V); None: the plain mean bias of this frame, what `reconstruct`'s first iteration uses).  With `brightness` the bias is projected
+    out of the derivative images.  No gradient.  Two launches (four with robust and no beta_prev)."""
+    brightness = _flag("brightness", brightness)
+    _, _, delta, robust = check_refine(0.0, 1.0, delta, robust)
+    if beta_prev is not None and not robust:
+        raise ValueError("beta_prev is the state of robust=\"welsch\"; got robust=None")
+    srs3, _, scale = _check_views(sr, lrs, shifts, lr_masks, alphas, scale, what="sr")
+    _tensor("beta_prev", beta_prev, shifts.shape[:2], optional=True)
+    _on_device(sr, beta_prev=beta_prev)
+    with torch.no_grad():
+        if robust and beta_prev is None:
+            beta_prev = torch.ops.hrnet_hip.consistency_loss_train(srs3, lrs, lr_masks, alphas, shifts, scale, brightness)[2]
+        return torch.ops.hrnet_hip.shift_normal(srs3, lrs, lr_masks, alphas, shifts, beta_prev, scale, brightness, delta)
+
+
+def refine_shifts(sr, lrs, shifts, lr_masks=None, alphas=None, scale=3, iters=2, damping=1e-3, max_step=0.5, fixed=0, brightness=True,
+                  robust=None, delta=0.1, return_trace=False):
+    """-> shifts' (B,V,2) after `iters` Levenberg-damped Gauss-Newton steps on every view's shift against the frame sr, which is held
+    (DESIGN 7v): step = -(H + damping tr(H) / 2 I)^-1 g, its largest component at most max_step LR pixels.  fixed: a view index, None, or a
+    (B,V) bool tensor - view 0 by default, the gauge: a common translation of all views and the frame is otherwise free.  A view keeps
+    its shift's bits when it is fixed, does not count, has fewer than 3 pixels' weight, or its damped system is singular.  It repairs
+    rough shifts (about 0.3 px off); it does NOT improve on a good masked-NCC search.  return_trace: also (iters,B,V,8) fp64, the normal
+    equations every step started from.  No gradient; nothing returns to the host.  Two launches a step (four with robust)."""
+    iters, brightness, return_trace = check_iters(iters), _flag("brightness", brightness), _flag("return_trace", return_trace)
+    damping, max_step, delta, robust = check_refine(damping, max_step, delta, robust)
+    _check_fixed(fixed, lrs)
+    srs3, _, scale = _check_views(sr, lrs, shifts, lr_masks, alphas, scale, what="sr")
+    fixed = _fixed_views(fixed, lrs.shape[0], lrs.shape[1], sr)
+    with torch.no_grad():
+        out, trace = torch.ops.hrnet_hip.refine_shifts(srs3, lrs, lr_masks, alphas, shifts, fixed, scale, iters, damping, max_step, brightness,
+                                                       robust, delta)
+    return (out, trace) if return_trace else out
+
+
+def reconstruct_joint(sr0, lrs, shifts, lr_masks=None, alphas=None, scale=3, iters=30, refine_every=1, refine_from=1, damping=1e-3,
+                      max_step=0.5, fixed=0, step=1.0, brightness=True, robust="welsch", delta=0.1, lam=4e-4, P=2, alpha=0.7, eps=0.02):
+    """-> (sr, shifts): `reconstruct`'s iteration with a Gauss-Newton update of the shifts (`refine_shifts`' step) beside the data step of
+    iteration t = refine_from, refine_from + refine_every, ... (0-based); both read the frame and the shifts the iteration started from.
+    In Welsch mode the update's weights need a beta_prev, so iteration 0 never updates.  refine_every = 0 returns `reconstruct`'s bits and
+    the input shifts' bits.  The other options are `reconstruct`'s and `refine_shifts`'.  No gradient.  Per iteration `reconstruct`'s
+    launches; an iteration that updates runs the normal pass in place of the residual pass (one pass over the frame) and one launch more."""
+    iters, brightness = check_iters(iters), _flag("brightness", brightness)
+    for name, v in (("refine_every", refine_every), ("refine_from", refine_from)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError(f"{name} must be an integer >= 0; got {v!r}")
+    refine_every, refine_from = int(refine_every), int(refine_from)
+    damping, max_step, _, _ = check_refine(damping, max_step, delta, robust)
+    step, robust, delta, lam, P, alpha, eps = check_reconstruct(step, robust, delta, lam, P, alpha, eps)
+    _check_fixed(fixed, lrs)
+    srs3, channel, scale = _check_views(sr0, lrs, shifts, lr_masks, alphas, scale, what="sr0")
+    fixed = _fixed_views(fixed, lrs.shape[0], lrs.shape[1], sr0)
+    with torch.no_grad():
+        sr, out = torch.ops.hrnet_hip.reconstruct_joint(srs3, lrs, lr_masks, alphas, shifts, fixed, scale, iters, refine_every, refine_from,
+                                                        damping, max_step, step, brightness, robust, delta, lam, P, alpha, eps)
+    return (sr.unsqueeze(1) if channel else sr), out
+
+
 def btv_loss(srs, P=2, alpha=0.7, eps=0.02):
     """srs (B,SH,SW) or (B,1,SH,SW) -> (B,) = R(srs_b) / (SH SW), the bilateral-TV prior of `reconstruct` as a training regulariser beside
     any loss here.  Differentiable in srs (the half-step's kernel with out = gain g).  Sides of 1..49152."""
@@ -219,12 +329,14 @@ def btv_loss(srs, P=2, alpha=0.7, eps=0.02):
 
 
 def register_and_refine(lrs, lr_masks=None, alphas=None, scale=3, iters=10, step=1.0, init="shift_add", octaves=0, robust=None, delta=0.1,
-                        lam=0.0, P=2, alpha=0.7, eps=0.02, **search_kwargs):
+                        lam=0.0, P=2, alpha=0.7, eps=0.02, joint=False, **search_kwargs):
     """lrs (B,V,H,W)[, lr_masks, alphas] -> (sr (B, scale H, scale W), shifts (B,V,2)): the views registered against the first one, a
     start - init="shift_add": `shiftadd.register_and_add`; "bicubic": the search (`registration.mncc_search_scene`, or with octaves > 0
     `mncc_search_pyramid`) and `upsample.baseline` - and `iters` back-projection steps from it; with robust="welsch" or lam > 0 the
     iterations are `reconstruct`'s (delta, lam, P, alpha, eps are its).  search_kwargs go to the search; frames are 16..16384 a side, the
-    search's limits.  No gradient."""
+    search's limits.  joint: the iterations are `reconstruct_joint`'s with its defaults (view 0 fixed), and the shifts returned are the
+    refined ones - for rough shifts; it does not improve on a search that worked.  No gradient."""
+    joint = _flag("joint", joint)
     if init not in ("shift_add", "bicubic"):
         raise ValueError(f"init must be \"shift_add\" or \"bicubic\"; got {init!r}")
     iters, step, scale = check_iters(iters), check_step(step), check_scale(scale)
@@ -238,7 +350,10 @@ def register_and_refine(lrs, lr_masks=None, alphas=None, scale=3, iters=10, step
         else:
             shifts = registration.search_global(lrs, lr_masks, octaves, **search_kwargs)
             sr0 = upsample.baseline(lrs, alphas, lr_masks, scale)[:, 0]
-        if robust is None and lam == 0:
+        if joint:
+            sr, shifts = reconstruct_joint(sr0, lrs, shifts, lr_masks, alphas, scale, iters, step=step, robust=robust, delta=delta, lam=lam, P=P,
+                                           alpha=alpha, eps=eps)
+        elif robust is None and lam == 0:
             sr = back_project(sr0, lrs, shifts, lr_masks, alphas, scale, iters, step)
         else:
             sr = reconstruct(sr0, lrs, shifts, lr_masks, alphas, scale, iters, step, True, robust, delta, lam, P, alpha, eps)

@@ -135,12 +135,16 @@ def baseline_table(batches, border_w=3, a=-0.75, n_ref=9, method="bicubic", **me
     registration, then iterative back-projection against the views (iters, step, init).
     method="robust" scores the same call with robust="welsch" and lam=4e-4 unless method_kwargs set them: `observation.reconstruct`'s
     Welsch-weighted data term and bilateral-TV prior (delta, lam, P, alpha, eps).
+    method="joint" scores the same call with joint=True unless method_kwargs set it: `observation.reconstruct_joint`'s Gauss-Newton
+    refinement of the shifts beside every data step (for rough registrations; it does not improve on a search that worked).
     A batch may carry lr_masks (B,V,H,W) as a sixth item, which those methods use (None: all clear); the bicubic method does not read
     it."""
-    if method not in ("bicubic", "shift_add", "back_projection", "robust"):
-        raise ValueError(f"method must be \"bicubic\", \"shift_add\", \"back_projection\" or \"robust\"; got {method!r}")
+    if method not in ("bicubic", "shift_add", "back_projection", "robust", "joint"):
+        raise ValueError(f"method must be \"bicubic\", \"shift_add\", \"back_projection\", \"robust\" or \"joint\"; got {method!r}")
     if method == "robust":
         method_kwargs = dict(dict(robust="welsch", lam=4e-4), **method_kwargs)
+    if method == "joint":
+        method_kwargs = dict(dict(joint=True), **method_kwargs)
     if method == "bicubic" and method_kwargs:
         raise TypeError(f"method=\"bicubic\" takes no further arguments; got {sorted(method_kwargs)}")
     from . import observation, shiftadd, upsample

@@ -54,6 +54,8 @@
  *                              registered views onto the x2 / x3 / x4 grid (normalised convolution), and its adjoint
  *   hrn_observe / hrn_consistency_residual / hrn_consistency_finish / hrn_observe_adjoint  <-  (no counterpart) the observation model: what
  *                              every registered view should have recorded of an HR frame, the data-consistency loss and back-projection
+ *   hrn_observe_shift_grad / _grad_finish / hrn_shift_normal / hrn_shift_normal_finish  <-  (no counterpart) the observation model's
+ *                              derivative in the shifts: the gradient to a registration, and Gauss-Newton refinement of the shifts
  *   hrn_robust_sums / hrn_robust_finish / hrn_robust_apply / hrn_btv_step / hrn_btv_backward / hrn_btv_value  <-  (no counterpart) Welsch
  *                              weights for the data term and a bilateral-TV prior: the robust, regularised reconstruction
  *
@@ -378,6 +380,57 @@ int hrn_consistency_finish(const void* workspace, size_t workspace_bytes, float*
 int hrn_observe_adjoint(const float* residual, const float* lr_masks, const float* alphas, const float* shifts, const float* beta,
                         const float* coef, const float* gain, const float* x, float* out, int B, int V, int H, int W, int scale,
                         void* stream);
+
+/* ------------------------------------------------------------------ the observation model's derivative in the shifts
+ * (No counterpart in the reference)  Tensors, c, n, f, w_j, `valid`, `counted` are the observation model's, above.
+ *
+ *   Derivative weights: omega_j = dw_j / dd = -sum_{k=0}^{S-1} k'_{j-2-k}(f) (c = -S d: the factor S cancels the box mean's 1 / S), with
+ *     k'_o = (u'_o - k_o sum u') / sum u the derivative tap of the six-tap sampler, u_o = sinc(o - f) sinc((o - f) / 3), u'_o = du_o / df,
+ *     sinc' by the series pi (-z / 3 + z^3 / 30 - z^5 / 840), z = pi t, below |t| = 1e-2 (hrn_mncc_apply_backward's k').  omega is formed
+ *     in fp64 and rounded to fp32 once, as w is; sum_j omega_j = 0.
+ *   Derivative images, for a valid sample: D_y = (omega^y (x) w^x) x and D_x = (w^y (x) omega^x) x on the (S + 5)^2 footprint of A x; fp32,
+ *     the row pass first, j ascending, one fma each.  D = 0 - and the matching component of d_shifts exactly 0 - for a view that does not
+ *     count, has a non-finite shift or an unclamped |c| >= 256.  The counted set is piecewise constant in the shift: not differentiated.
+ *   Gradient: d_shifts[b,v,a] = coef[b] gain[b] sum_i [counted] (g_i + beta_v) D_a,i, the bracket a select, the product and the sums fp64,
+ *     rounded to fp32 once.  observe's backward: g = the incoming gradient, no masks, alphas, beta, coef or gain.  The consistency loss':
+ *     g = hrn_consistency_residual's residual with hrn_consistency_finish's beta and coef_loss, gain = dL (the derivative of beta_v drops
+ *     out because sum r = 0; without `brightness` beta is 0 and the formula the same).
+ *   Normal equations of a view: e = A x - y where counted; p = counted, or with beta_prev (B,V) given the Welsch weight
+ *     counted exp(-((e + beta_prev) / delta)^2) of hrn_robust_sums.  From the ten fp64 sums P = sum p, sum p e, sum p e^2, sum p D_a,
+ *     sum p e D_a, sum p D_a D_b: beta = -sum p e / P with `brightness` (0 without, and 0 when P < 2^-60), m_a = sum p D_a / P with
+ *     `brightness` (else 0; D'_a = D_a - m_a projects the bias out),
+ *         g_a = sum p (e + beta) D'_a,   H_ab = sum p D'_a D'_b,   q = sum p (e + beta)^2,
+ *     normal (B,V,8) fp64 = [P, g_y, g_x, H_yy, H_yx, H_xx, beta, q].
+ *   Update (Levenberg-damped Gauss-Newton, fp64): lam = damping (H_yy + H_xx) / 2, step = -(H + lam I)^-1 g, scaled so that its largest
+ *     component is at most max_step in magnitude, shifts_out = fp32(shifts + step).  A view keeps its shift's BITS when fixed[b,v] is
+ *     non-zero (fixed NULL: none), when it does not count (alpha 0, a non-finite shift, |c| >= 256), when P < 3 (three pixels of full
+ *     weight; a Welsch weight is at most 1, so in that mode three inliers' worth), or when the damped determinant or the step is not
+ *     positive and finite.
+ *
+ * hrn_observe_shift_grad WRITES per tile of HRN_OBSERVE_TILE_H x HRN_OBSERVE_TILE_W samples the two sums into `workspace`
+ *   (hrn_observe_shift_workspace_bytes(B, V, H, W) bytes = HRN_SHIFT_NORMAL_SUMS doubles per tile, 8-byte aligned; 0 for sizes the functions
+ *   refuse); hrn_observe_shift_grad_finish adds a view's tiles in index order and WRITES d_shifts (B,V,2) f32.
+ * hrn_shift_normal WRITES the ten sums per tile, with `residual` non-NULL the residual plane with the bits of
+ *   hrn_consistency_residual, and with `plain_workspace` non-NULL (hrn_observe_workspace_bytes(B, V, H, W) bytes, 8-byte aligned) that
+ *   function's three plain sums n, sum e, sum e^2 per tile with its bits - in both modes - so that hrn_consistency_finish runs on them
+ *   unchanged and an iteration that updates the shifts needs no second pass over the frame; hrn_shift_normal_finish WRITES normal and, with shifts_out non-NULL, the updated shifts (shifts_out must not
+ *   alias shifts: the adjoint may still run on the old ones).
+ * All are bit-reproducible (fixed orders, no atomics), a sample's result does not depend on its batch, appended views with alpha 0 change no
+ * bit.  H, W in 1 .. 16384, any B, V >= 1; every offset is 64-bit.  -2 before any launch for a NULL required pointer, non-positive sizes, a
+ * side beyond 16384, a scale outside {2, 3, 4}, a delta that is not positive (with beta_prev), a negative or non-finite damping, a max_step
+ * that is not positive and finite, a workspace that is too small or misaligned, or overlapping arguments. */
+#define HRN_SHIFT_NORMAL_SUMS 10
+size_t hrn_observe_shift_workspace_bytes(int B, int V, int H, int W);
+int hrn_observe_shift_grad(const float* hr, const float* g, const float* lr_masks, const float* alphas, const float* shifts,
+                           const float* beta, void* workspace, size_t workspace_bytes, int B, int V, int H, int W, int scale, void* stream);
+int hrn_observe_shift_grad_finish(const void* workspace, size_t workspace_bytes, const float* coef, const float* gain, float* d_shifts,
+                                  int B, int V, int H, int W, void* stream);
+int hrn_shift_normal(const float* hr, const float* lrs, const float* lr_masks, const float* alphas, const float* shifts,
+                     const float* beta_prev, float delta, float* residual, void* plain_workspace, size_t plain_workspace_bytes,
+                     void* workspace, size_t workspace_bytes, int B, int V, int H, int W, int scale, void* stream);
+int hrn_shift_normal_finish(const void* workspace, size_t workspace_bytes, const float* alphas, const float* shifts,
+                            const unsigned char* fixed, void* normal, float* shifts_out, int B, int V, int H, int W, int scale,
+                            int brightness, float damping, float max_step, void* stream);
 
 /* ------------------------------------------------------------------ a robust data term and a bilateral-TV prior for the reconstruction
  * (No counterpart in the reference)  Tensors, `counted`, n_v and V_b are the observation model's, above.
